@@ -16,11 +16,16 @@ Multi-GPU: independent prompts shard over ranks (one process per GPU, no data-pa
 RCCL only broadcasts the text embeddings at start and gathers the final latents at the end, both
 outside the timed region) -> weak scaling; value = all prompts' steps / max-over-ranks time.
 
-Timing: the K-step timed region (barrier + synchronize on both sides, max over ranks) is repeated
---repeats times (default 5, README.md:79-91 of the reference reports medians); `value` and
-`ms_per_step` come from the MEDIAN repeat, every repeat is listed under "repeats_ms_per_step".
+Timing: the K-step timed region (barrier + synchronize on both sides, max over ranks) runs
+--repeats times (default 1, so --steps K times exactly K steps; 5 with --full, README.md:79-91 of
+the reference reports medians); `value` and `ms_per_step` come from the MEDIAN repeat, every repeat
+is listed under "repeats_ms_per_step".
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the steps, writes the outputs (--dump-outputs DIR: the final
+latents of the last timed loop as DIR/latents.npy, float32; inputs are seeded, so two builds can be
+compared output for output) and prints the line.  Everything else runs only with --full.
+
+Extra objects on the JSON line with --full:
   roofline     MFMA roofline of the step graph: algorithmic FLOP per step (SURVEY.md section 8d:
                1.6085e12 per CFG-batch-2 step) / HIP-event time per step on the handle's stream;
                `traffic` = HBM bytes per step from rocprofv3 PMC passes (profiles/r06_final_hbm_traffic.json,
@@ -74,21 +79,30 @@ def main():
     ap.add_argument("--prompts-per-gpu", type=int, default=1)
     ap.add_argument("--attention", default="ORIGINAL", choices=["ORIGINAL", "SPLIT_EINSUM", "SPLIT_EINSUM_V2"])
     ap.add_argument("--guidance-scale", type=float, default=7.5)
-    ap.add_argument("--cpu-steps", type=int, default=5, help="oracle steps timed for cpu_baseline (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary measurements: gpu_state, calibration, sustained leg, roofline / kernel families / "
+                         "HBM traffic, end-to-end latency, --streams, cpu_baseline; 5 timed repeats by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the final latents of the last timed loop (all prompts, gathered) to DIR/latents.npy (float32)")
+    ap.add_argument("--cpu-steps", type=int, default=5, help="oracle steps timed for cpu_baseline (--full only; 0 = skip)")
     ap.add_argument("--sustain-s", type=float, default=12.0,
-                    help="untimed back-to-back replays of the step graph AFTER the timed repeats (result discarded, never part of "
-                         "`value`): long enough for an outside GPU-utilisation sampler to see the run (0 = skip)")
-    ap.add_argument("--repeats", type=int, default=5, help="repeats of the K-step timed region (median reported)")
+                    help="untimed back-to-back replays of the step graph AFTER the timed repeats (--full only; result discarded, "
+                         "never part of `value`): long enough for an outside GPU-utilisation sampler to see the run (0 = skip)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="repeats of the K-step timed region (median reported; default 1, 5 with --full)")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--model", default="sd21-base", choices=sorted(MODELS), help="UNet of BASELINE configs 2 / 4 / 5")
     ap.add_argument("--latent", type=int, default=0, choices=[0, 64, 96, 128],
                     help="latent height = width (64: 512x512 images, 96: 768x768); 0 = the model's BASELINE size")
     ap.add_argument("--streams", type=int, default=0,
-                    help="extra measurement (N=1 only): S prompts served by S handles on S HIP streams at the same time; reported "
-                         "as 'concurrent_prompts', never as 'value'")
+                    help="extra measurement (--full, N=1 only): S prompts served by S handles on S HIP streams at the same time; "
+                         "reported as 'concurrent_prompts', never as 'value'")
     ap.add_argument("--stub-model", action="store_true", help=argparse.SUPPRESS)   # tests/test_parallel.py: the launch /
     # rendezvous / barrier / max-over-ranks / gather plumbing of this script under gloo on CPU, with StubModel in the UNet's place
     args = ap.parse_args()
+    if args.streams > 1 and not args.full:
+        ap.error("--streams is a secondary measurement: add --full")
+    n_repeats = max(1, args.repeats if args.repeats is not None else (5 if args.full else 1))
     spec = MODELS[args.model]
     lat_hw = args.latent or spec["latent"]
     default_cfg = args.model == "sd21-base" and lat_hw == 64
@@ -141,7 +155,7 @@ def main():
         control_cond = np.random.RandomState(95).rand(2 * ppg, 3, lat_hw * 8, lat_hw * 8).astype(np.float16)
         control.set_controlnet_cond(control_cond)
         model.attach_controlnets([control])
-    if not default_cfg:
+    if not (args.full and default_cfg):   # kept for cpu_baseline only
         del ckpt
         ckpt = None
     build_s = time.time() - t_build
@@ -174,15 +188,16 @@ def main():
             dist.barrier()
         sync()
 
-    gpu_before = gpu_state(local_rank) if rank == 0 and not stub else None
+    full = args.full and not stub
+    gpu_before = gpu_state(local_rank) if rank == 0 and full else None
     calib = None
-    if rank == 0 and not stub:   # what THIS box can do, measured before the warm-up by four fixed micro-kernels (calib.hip)
+    if rank == 0 and full:   # what THIS box can do, measured before the warm-up by four fixed micro-kernels (calib.hip)
         from python_hip_stable_diffusion import _lib as _sdlib
         calib = _sdlib.calibrate(local_rank)
     if args.warmup > 0:
         run(args.warmup)
     rep_s, rep_ev = [], []
-    for _ in range(max(1, args.repeats)):
+    for _ in range(n_repeats):
         barrier()
         t0 = time.perf_counter()
         final, ev_ms = run(args.steps)
@@ -195,9 +210,9 @@ def main():
             dist.barrier()
         rep_s.append(el)
         rep_ev.append(float(np.median(ev_ms)))
-    gpu_after = gpu_state(local_rank) if rank == 0 and not stub else None   # right behind the timed repeats: clocks under load
+    gpu_after = gpu_state(local_rank) if rank == 0 and full else None   # right behind the timed repeats: clocks under load
     sustain = None
-    if not stub and args.sustain_s > 0:   # the timed region is 0.5 s of a 60-s run; make the GPU leg visible
+    if full and args.sustain_s > 0:   # the timed region is 0.5 s of a 60-s run; make the GPU leg visible
         t0 = time.perf_counter()
         n_sus = 0
         while time.perf_counter() - t0 < args.sustain_s:
@@ -216,12 +231,12 @@ def main():
         if dist is not None:
             dist.destroy_process_group()
         return
+    if args.dump_outputs:   # what the last timed loop returned to its caller: the final latents of every prompt
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "latents.npy"), np.asarray(all_final, np.float32))
     total_prompt_steps = world * ppg * args.steps
     value = total_prompt_steps / elapsed
     ev_ms_step = rep_ev[mid]
-    x = np.concatenate([latents, latents]).astype(np.float16)
-    fwd_inputs = dict(loop_inputs, sample=x, timestep=np.full((2 * ppg,), 951, np.float16))
-    ops = None
     if stub:         # plumbing test: the line's bookkeeping fields only
         print(json.dumps({"metric": "stub", "value": round(value, 3), "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                           "ms_per_step": round(elapsed / args.steps * 1e3, 4), "scaling": "weak",
@@ -230,20 +245,6 @@ def main():
         if dist is not None:
             dist.destroy_process_group()
         return
-    if world == 1:   # per-op HIP-event times of one eager step (sd_unet_profile), attached ControlNet included
-        model(**fwd_inputs)
-        ops = model.profile(iters=7)
-        if control is not None:   # the ControlNet runs inside the UNet handle's step; profiled as a handle of its own
-            control(sample=x, timestep=fwd_inputs["timestep"], encoder_hidden_states=my_ehs, controlnet_cond=control_cond)
-            ops = control.profile(iters=7) + ops
-    if default_cfg:
-        flop_per_launch = FLOP_PER_SAMPLE_STEP * 2 * ppg
-        flop_note = "algorithmic: 804.3 GFLOP per latent sample (SURVEY.md section 8d)"
-    else:   # executed MFMA FLOP of the launch list (the prompt's K/V projections are hoisted out of the step)
-        assert ops is not None, "--model / --latent other than the default are single-GPU lines"
-        flop_per_launch = float(sum(fl for _, fl, _ in ops))
-        flop_note = "sum of the algorithmic FLOP of every conv / GEMM / attention launch of the step (sd_unet_profile labels)"
-    achieved = flop_per_launch / (ev_ms_step * 1e-3) / 1e12
     px = lat_hw * 8
     metric = ("diffusion iter/s (UNet steps/s), SD2.1-base 512x512 fp16" if default_cfg else
               f"diffusion iter/s (UNet steps/s), {args.model} {px}x{px} fp16")
@@ -262,17 +263,39 @@ def main():
                    "attention": args.attention, "prompts_per_gpu": ppg, "global_batch": 2 * ppg * world,
                    "guidance_scale": args.guidance_scale, "hip_graph": not args.no_graph,
                    "parallelism": f"dp{world} (independent prompts per rank, no data-path collective)"},
-        "roofline": {"bound": "mfma", "kernel": "unet_step_graph (all MFMA conv/GEMM/attention launches of one step)",
-                     "achieved": round(achieved, 2), "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                     "frac": round(achieved / MFMA_PEAK_TFLOPS, 4), "traffic": None,
-                     "flop_per_launch": flop_per_launch, "flop_definition": flop_note, "launch_ms": round(ev_ms_step, 4),
-                     "timing": "hipEvent on the handle's stream: median step of the median repeat"},
-        "gpu_state": {"before_warmup": gpu_before, "after_timed_region": gpu_after,
-                      "note": "rocm-smi clocks / power / junction temperature of this rank's GPU: attributes box-to-box spread"},
         "e2e": {"model_build_s": round(build_s, 1), "final_latents_finite": True,
                 "gathered_latents": list(all_final.shape), "hbm_bytes": int(model.device_bytes)},
         "sustained_leg": sustain,
     }
+    if not full:
+        print(json.dumps(out), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+    x = np.concatenate([latents, latents]).astype(np.float16)
+    fwd_inputs = dict(loop_inputs, sample=x, timestep=np.full((2 * ppg,), 951, np.float16))
+    ops = None
+    if world == 1:   # per-op HIP-event times of one eager step (sd_unet_profile), attached ControlNet included
+        model(**fwd_inputs)
+        ops = model.profile(iters=7)
+        if control is not None:   # the ControlNet runs inside the UNet handle's step; profiled as a handle of its own
+            control(sample=x, timestep=fwd_inputs["timestep"], encoder_hidden_states=my_ehs, controlnet_cond=control_cond)
+            ops = control.profile(iters=7) + ops
+    if default_cfg:
+        flop_per_launch = FLOP_PER_SAMPLE_STEP * 2 * ppg
+        flop_note = "algorithmic: 804.3 GFLOP per latent sample (SURVEY.md section 8d)"
+    else:   # executed MFMA FLOP of the launch list (the prompt's K/V projections are hoisted out of the step)
+        assert ops is not None, "--model / --latent other than the default are single-GPU lines"
+        flop_per_launch = float(sum(fl for _, fl, _ in ops))
+        flop_note = "sum of the algorithmic FLOP of every conv / GEMM / attention launch of the step (sd_unet_profile labels)"
+    achieved = flop_per_launch / (ev_ms_step * 1e-3) / 1e12
+    out["roofline"] = {"bound": "mfma", "kernel": "unet_step_graph (all MFMA conv/GEMM/attention launches of one step)",
+                       "achieved": round(achieved, 2), "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                       "frac": round(achieved / MFMA_PEAK_TFLOPS, 4), "traffic": None,
+                       "flop_per_launch": flop_per_launch, "flop_definition": flop_note, "launch_ms": round(ev_ms_step, 4),
+                       "timing": "hipEvent on the handle's stream: median step of the median repeat"}
+    out["gpu_state"] = {"before_warmup": gpu_before, "after_timed_region": gpu_after,
+                        "note": "rocm-smi clocks / power / junction temperature of this rank's GPU: attributes box-to-box spread"}
     if calib is not None:
         out.update(calibration_record(calib))
     if world == 1:

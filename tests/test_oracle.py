@@ -197,18 +197,18 @@ def test_philox_block_function_matches_the_published_known_answer_vectors():
 def test_tokenizer_reproduces_the_reference_test_vectors(tmp_path):
     """The tokenizer is out of scope (transformers' CLIPTokenizer is used like the reference's Python pipeline does), but the
     reference's own test holds two known-answer prompts (swift/StableDiffusionTests/StableDiffusionTests.swift:43-49) for the
-    vocabulary it ships: `load_tokenizer` on that vocabulary must give the same ids.  Reads the vocabulary from the reference
-    tree in place, so it only runs where /root/reference exists (never on the GPU box)."""
+    vocabulary it ships: `load_tokenizer` on that vocabulary must give the same ids.  The vocabulary is stored gzipped under
+    tests/golden/clip_tokenizer_{vocab.json,merges.txt}.gz (the reference's test resources, byte for byte)."""
+    import gzip
     import os
     import shutil
-    res = "/root/reference/swift/StableDiffusionTests/Resources"
-    if not os.path.exists(os.path.join(res, "vocab.json")):
-        pytest.skip("reference resources not available here")
+    from conftest import GOLDEN
     from python_hip_stable_diffusion.text_encoder import load_tokenizer
     folder = tmp_path / "tokenizer"
     folder.mkdir()
     for f in ("vocab.json", "merges.txt"):
-        shutil.copy(os.path.join(res, f), folder / f)       # temporary copy outside the repository
+        with gzip.open(os.path.join(GOLDEN, f"clip_tokenizer_{f}.gz"), "rb") as src, open(folder / f, "wb") as dst:
+            shutil.copyfileobj(src, dst)
     tok = load_tokenizer(str(folder))
     for prompt, want in (("a photo of an astronaut riding a horse on mars",
                           [49406, 320, 1125, 539, 550, 18376, 6765, 320, 4558, 525, 7496, 49407]),

@@ -24,12 +24,12 @@ for step in "$@"; do
     smoke)
       timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke_$TAG.log 2>&1; note "smoke rc=$? $(tail -n 1 $OUT/smoke_$TAG.log | cut -c1-120)" ;;
     bench)
-      timeout 900 python bench.py > $OUT/bench_$TAG.log 2> $OUT/bench_$TAG.err; note "bench rc=$?"
+      timeout 900 python bench.py --full > $OUT/bench_$TAG.log 2> $OUT/bench_$TAG.err; note "bench rc=$?"
       tail -n 1 $OUT/bench_$TAG.log | cut -c1-600 ;;
     ab:*)
       kv=${step#ab:}; fl=""
       case "$kv" in *@*) fl=${kv#*@}; kv=${kv%%@*} ;; esac      # "ab:ENV=VAL@--prompts-per-gpu 8": extra bench flags behind @
-      r=$(env ${kv//,/ } timeout 300 python bench.py --cpu-steps 0 --sustain-s 0 --repeats 5 $fl 2>/dev/null | tail -n 1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); g=(d.get('gpu_state') or {}).get('after_timed_region') or {}; c=d.get('calibration') or {}; print(d['ms_per_step'], d['value'], 'calib', c.get('copy_gbs'), c.get('mfma_tflops'), c.get('empty_launch_us'), c.get('chain_us'), c.get('handover_us'), c.get('latency_hbm_ns'), c.get('latency_cache_ns'), c.get('small_grid_us'), c.get('cold_code_us'), 'sclk', g.get('sclk clock speed:'), 'W', g.get('Current Socket Graphics Package Power (W)'))" 2>&1)
+      r=$(env ${kv//,/ } timeout 300 python bench.py --full --cpu-steps 0 --sustain-s 0 --repeats 5 $fl 2>/dev/null | tail -n 1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); g=(d.get('gpu_state') or {}).get('after_timed_region') or {}; c=d.get('calibration') or {}; print(d['ms_per_step'], d['value'], 'calib', c.get('copy_gbs'), c.get('mfma_tflops'), c.get('empty_launch_us'), c.get('chain_us'), c.get('handover_us'), c.get('latency_hbm_ns'), c.get('latency_cache_ns'), c.get('small_grid_us'), c.get('cold_code_us'), 'sclk', g.get('sclk clock speed:'), 'W', g.get('Current Socket Graphics Package Power (W)'))" 2>&1)
       note "ab[$kv $fl] ms/step, it/s: $r" ;;
     profile)
       timeout 300 python tools/op_profile.py $OUT/op_profile_$TAG.json 2 ORIGINAL > $OUT/op_profile_$TAG.txt 2>&1; note "profile rc=$?"; head -n 28 $OUT/op_profile_$TAG.txt | cut -c1-150 ;;
@@ -51,7 +51,7 @@ for step in "$@"; do
       rm -rf $OUT/pmc_FETCH_SIZE $OUT/pmc_WRITE_SIZE $OUT/pmc_SQ_VALU_MFMA_BUSY_CYCLES ;;
     bench:*)   # bench with extra flags, e.g. "bench:--model sdxl-base --latent 96"
       fl=${step#bench:}
-      timeout 900 python bench.py $fl > $OUT/bench_${TAG}_$i.log 2> $OUT/bench_${TAG}_$i.err; note "bench[$fl] rc=$?"
+      timeout 900 python bench.py --full $fl > $OUT/bench_${TAG}_$i.log 2> $OUT/bench_${TAG}_$i.err; note "bench[$fl] rc=$?"
       tail -n 1 $OUT/bench_${TAG}_$i.log | python -c "import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']; print(d['metric'], d['ms_per_step'], 'ms', d['value'], 'it/s frac', r['frac'], 'dominant', r.get('dominant_kernel',{}).get('kernel'), r.get('dominant_kernel',{}).get('share'), r.get('dominant_kernel',{}).get('frac'))" 2>&1 | cut -c1-400 ;;
     pytest:*)   # one test file / selection
       sel=${step#pytest:}
