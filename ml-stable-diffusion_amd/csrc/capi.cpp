@@ -499,6 +499,10 @@ int sd_op_conv2d(const void* x, const void* w, const float* bias, const void* re
       d.tile = 11;
       d.staging = tile - 110;
     }
+    if (tile >= 140 && tile <= 142) {   // 140 / 141 / 142: plan tile 12 (smgemm.hip) with the tile height by M / 32 rows / 64 rows
+      d.tile = 12;                       // (12x / 13x are igemm_kernel tiles with staging 12 / 13, the in-workgroup split-K rings)
+      d.staging = tile - 140;
+    }
     d.splitk = splitk;
     d.debug = force_generic >= 2 ? force_generic - 1 : 0;   // 2: loads only, 3: compute only (ablation)
     if (d.debug & 4) d.prof = sc.dev<long long>(8);
@@ -516,7 +520,7 @@ int sd_op_conv2d(const void* x, const void* w, const float* bias, const void* re
       launch_bvgemm_retile(d.w, wtd, Cout, Cin, false, sc.stream);
       d.w_bv = wtd;
     }
-    if (fast && d.tile != 11) {
+    if (fast && d.tile != 11 && d.tile != 12) {
       ws.partial_bytes = conv_workspace_bytes(d);
       if (ws.partial_bytes) ws.partial = reinterpret_cast<float*>(sc.dev<char>(ws.partial_bytes));
     }

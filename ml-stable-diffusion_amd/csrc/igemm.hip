@@ -2833,6 +2833,14 @@ int launch_conv(const ConvDesc& d, const ConvWorkspace& ws, hipStream_t s) {
     launch_bvgemm(d, d.staging, s);
     return 0;
   }
+  {   // plan tile 12 (smgemm.hip) on the library's own rule (SD_SMGEMM=0 with SD_TUNE: off, A/B); staging 1 / 2 force a tile height
+    static const bool sm_on = tune_env_int("SD_SMGEMM", 1) != 0;
+    const bool forced = d.tile == 12;
+    if (forced || (sm_on && d.tile == 0 && d.splitk == 0 && d.staging == 0 && g_tune.tile == 0 && smgemm_wanted(d))) {
+      launch_smgemm(d, forced ? d.staging : 0, s);
+      return 0;
+    }
+  }
   IgemmArgs a = make_args(d);
   Plan p = choose_plan(d, a);
   bool halo = p.tile == 7;

@@ -141,6 +141,11 @@ void launch_bvgemm_retile(const half_t* w, half_t* wt, int N, int K, bool geglu,
 void launch_bvgemm(const ConvDesc& d, int variant, hipStream_t s);   // variant 1-4 (bvgemm.hip), 0 = the library's choice
 bool bvgemm_wanted(const ConvDesc& d);                                // the library's rule for taking plan tile 11 on its own
 
+// smgemm.hip: small-M single-source 1x1 GEMM, whole-LDS ring, epilogue from the accumulators (plan tile 12)
+bool smgemm_shape_ok(const ConvDesc& d, int variant);                 // variant 1 / 2: 32- / 64-row tiles, 0: by M
+bool smgemm_wanted(const ConvDesc& d);                                // the library's rule for taking plan tile 12 on its own
+void launch_smgemm(const ConvDesc& d, int variant, hipStream_t s);
+
 // calib.hip: box calibration for bench.py - out[0..6] = copy GB/s, dense MFMA TFLOP/s, us per launch of a 323-launch empty
 // graph, us per launch of a 323-launch chain of short kernels on cold operands, us per launch of a 323-launch chain handing 8 MB
 // over between the XCDs' L2s, ns per dependent load from HBM / from the caches
