@@ -329,7 +329,12 @@ int sd_op_geglu(const void* x, const void* w, const float* bias, void* out, int 
 /* The same projection with the LayerNorm in front of it folded into the GEMM, as the UNet runs it (unet.py:583-591 norm3 ->
  * :609-617; host-side fold of UNet::fold_layernorm): x (M, C) f16 UN-normalised, ln_weight / ln_bias (C) f32 or both NULL,
  * w (N2, C) f16, bias (N2) f32 or NULL -> out (M, N2 / 2) f16.  kernel: 0 = the library's plan, 1 = the tiled GEMM kernels,
- * 2 = the weight-stationary kernel (wsgemm.hip: C = 320, N2 % 256 == 0, M >= 2048; other shapes -> SD_ERR_INVALID_ARGUMENT). */
+ * 2 = the weight-stationary kernel (wsgemm.hip: C = 320, N2 % 256 == 0, M >= 2048; other shapes -> SD_ERR_INVALID_ARGUMENT),
+ * 3-9 = bvgemm.hip (its own choice / variants 1-6), 100 = the one-round kernel of smgeglu.hip (plan tile 13: BM x 80 output tiles,
+ * one workgroup per CU) with the tile height BM by the grid size, 101 / 102 = BM 128 / 256 forced.  100-102 need C % 64 == 0,
+ * N2 % 160 == 0, M % BM == 0, at least two tiles each way and a tile count that is a multiple of 8; other shapes ->
+ * SD_ERR_INVALID_ARGUMENT.  110-112 = 100-102 through the kernel's phase-clock build, which prints its per-wave cycle table to
+ * stderr (measurement tools only). */
 int sd_op_geglu_ln(const void* x, const float* ln_weight, const float* ln_bias, const void* w, const float* bias, void* out, int M, int C,
                    int N2, float eps, int kernel, int iters, float* ms);
 /* Fused q|k|v projection of self-attention with norm1 folded in (unet.py:583-586 -> :74-84 as ONE GEMM): x (B * HW, C) f16,

@@ -1,5 +1,7 @@
 // extern "C" surface of libsdmi355 (include/sd_mi355x.h).  Exceptions never cross the ABI:
 // every entry point converts sd::Error into a status code + thread-local message.
+#include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -1117,10 +1119,17 @@ int sd_op_geglu(const void* x, const void* w, const float* bias, void* out, int 
 // GEGLU projection with the LayerNorm in front of it folded in (unet.py:583-591 norm3 -> :609-617 ff.net.0.proj), exactly as the
 // UNet builder folds it (UNet::fold_layernorm): x (M, C) f16 un-normalised rows, ln_weight / ln_bias (C) f32 or both NULL (plain
 // GEGLU), w (N2, C) f16 [values | gates], bias (N2) f32 or NULL -> out (M, N2 / 2) f16.  kernel: 0 = the plan the library picks,
-// 1 = the tiled igemm / gemm_pipe kernels, 2 = the weight-stationary kernel of wsgemm.hip (plan tile 10; refused for other shapes).
+// 1 = the tiled igemm / gemm_pipe kernels, 2 = the weight-stationary kernel of wsgemm.hip (plan tile 10; refused for other shapes),
+// 3-9 = plan tile 11 (bvgemm.hip: its own choice / variants 1-6), 100 = plan tile 13 (smgeglu.hip) with the tile height by the grid
+// size, 101 / 102 = its 128- / 256-row tiles (refused for shapes it does not tile); 110-112 = the same through the phase-clock
+// build, which prints its table.
 int sd_op_geglu_ln(const void* x, const float* ln_weight, const float* ln_bias, const void* w, const float* bias, void* out, int M, int C,
                    int N2, float eps, int kernel, int iters, float* ms) {
   return guarded([&] {
+    const bool smgeglu = kernel >= 100 && kernel <= 112 && kernel % 10 <= 2;   // 100-102, 110-112: plan tile 13 (smgeglu.hip)
+    const int sg_variant = smgeglu ? kernel % 10 : 0;                          // tile height by grid size / 128 rows / 256 rows
+    const bool sg_clock = smgeglu && kernel >= 110;
+    if (smgeglu) kernel = 0;
     const int abl = kernel / 10;   // kernel = 2 + 10 * n: ablation build n of the weight-stationary kernel (measurement tools only)
     kernel %= 10;
     SD_REQUIRE(x && w && out && N2 % 64 == 0 && (ln_weight == nullptr) == (ln_bias == nullptr) && kernel >= 0 && kernel <= 9 &&
@@ -1157,14 +1166,24 @@ int sd_op_geglu_ln(const void* x, const float* ln_weight, const float* ln_bias, 
     d.B = 1; d.Hi = 1; d.Wi = M; d.Ho = 1; d.Wo = M;
     d.N = N2;
     d.out_mode = kOutGeglu;
+    SD_REQUIRE(!smgeglu || smgeglu_shape_ok(d, sg_variant), kInvalidArgument,
+               "GEGLU shape not eligible for plan tile 13 (smgeglu.hip): M=%d C=%d N2=%d", M, C, N2);
     SD_REQUIRE(conv_fast_path_ok(d), kUnsupported, "GEGLU shape off the MFMA path (C=%d N2=%d)", C, N2);
-    if (kernel != 1 && kernel < 3 && wsgemm_shape_ok(d)) {
+    if (kernel != 1 && kernel < 3 && !smgeglu && wsgemm_shape_ok(d)) {
       half_t* wtd = sc.dev<half_t>(wsgemm_tiled_halves(N2));
       launch_wsgemm_retile(d.w, wtd, N2, true, sc.stream);
       d.w_ws = wtd;
     }
     if (kernel == 2) d.tile = 10;
-    if (kernel >= 3) {   // 3 / 4 / 5 / 6: plan tile 11 (bvgemm.hip) by grid size / variants 1-3
+    size_t sg_prof = 0;
+    if (smgeglu) {
+      d.tile = 13;
+      d.staging = sg_variant;
+      if (sg_clock) {
+        sg_prof = smgeglu_prof_entries(d, d.staging);
+        d.prof = sc.dev<long long>(sg_prof);
+      }
+    } else if (kernel >= 3) {   // 3 ... 9: plan tile 11 (bvgemm.hip) by grid size / variants 1-6
       SD_REQUIRE(bvgemm_shape_ok(d), kInvalidArgument, "GEGLU shape not eligible for plan tile 11 (bvgemm.hip)");
       half_t* wtd = sc.dev<half_t>(bvgemm_tiled_halves(N2, C));
       launch_bvgemm_retile(d.w, wtd, N2, C, true, sc.stream);
@@ -1177,7 +1196,26 @@ int sd_op_geglu_ln(const void* x, const float* ln_weight, const float* ln_bias, 
     if (abl == 5) d.prof = sc.dev<long long>(64);
     ConvWorkspace ws;
     sc.timed(iters, ms, [&] { launch_conv(d, ws, sc.stream); });
-    if (d.prof) {   // workgroup (0, 0), thread 0: shader-clock stamps of its first pipeline iterations
+    if (sg_prof) {   // every wave's stamps of the last launch: cycles from kernel entry to the end of each phase
+      std::vector<long long> t(sg_prof);
+      SD_HIP(hipMemcpy(t.data(), d.prof, sg_prof * sizeof(long long), hipMemcpyDeviceToHost));
+      static const char* const phase[5] = {"first ring stages + epilogue operands issued", "first stage landed (counted wait + barrier)",
+                                           "K loop done", "row statistics exchanged", "last store issued"};
+      const size_t waves = sg_prof / 8;
+      fprintf(stderr, "[sd prof] smgeglu M=%d K=%d N=%d kernel=%d: %zu waves, shader-clock cycles since the wave's kernel entry (min / mean / max)\n",
+              M, C, N2, 110 + sg_variant, waves);
+      for (int k = 1; k <= 5; ++k) {
+        long long lo = LLONG_MAX, hi = 0;
+        double sum = 0.0;
+        for (size_t wv = 0; wv < waves; ++wv) {
+          const long long dt = t[wv * 8 + k] - t[wv * 8];
+          lo = std::min(lo, dt);
+          hi = std::max(hi, dt);
+          sum += (double)dt;
+        }
+        fprintf(stderr, "[sd prof]   %-46s %8lld %10.0f %8lld\n", phase[k - 1], lo, sum / (double)waves, hi);
+      }
+    } else if (d.prof) {   // workgroup (0, 0), thread 0: shader-clock stamps of its first pipeline iterations
       long long t[64];
       SD_HIP(hipMemcpy(t, d.prof, sizeof(t), hipMemcpyDeviceToHost));
       for (int i = 0; i < 6; ++i)

@@ -2841,6 +2841,14 @@ int launch_conv(const ConvDesc& d, const ConvWorkspace& ws, hipStream_t s) {
       return 0;
     }
   }
+  {   // plan tile 13 (smgeglu.hip) on the library's own rule (SD_SMGEGLU=0 with SD_TUNE: off, A/B); staging 1 / 2 force a tile height
+    static const bool sg_on = tune_env_int("SD_SMGEGLU", 1) != 0;
+    const bool forced = d.tile == 13;
+    if (forced || (sg_on && d.tile == 0 && d.splitk == 0 && d.staging == 0 && g_tune.tile == 0 && smgeglu_wanted(d))) {
+      launch_smgeglu(d, forced ? d.staging : 0, s);
+      return 0;
+    }
+  }
   IgemmArgs a = make_args(d);
   Plan p = choose_plan(d, a);
   bool halo = p.tile == 7;

@@ -146,6 +146,13 @@ bool smgemm_shape_ok(const ConvDesc& d, int variant);                 // variant
 bool smgemm_wanted(const ConvDesc& d);                                // the library's rule for taking plan tile 12 on its own
 void launch_smgemm(const ConvDesc& d, int variant, hipStream_t s);
 
+// smgeglu.hip: GEGLU projection (with or without the LayerNorm fold) on BM x 80 tiles, one workgroup per CU, whole-LDS ring, weights
+// as uploaded (plan tile 13)
+bool smgeglu_shape_ok(const ConvDesc& d, int variant);                // variant 1 / 2: 128- / 256-row tiles, 0: by the grid size
+bool smgeglu_wanted(const ConvDesc& d);                               // the library's rule for taking plan tile 13 on its own
+void launch_smgeglu(const ConvDesc& d, int variant, hipStream_t s);   // d.prof set: the phase-clock build, which fills
+size_t smgeglu_prof_entries(const ConvDesc& d, int variant);          // this many long long: [workgroup][10 waves][8], six stamps used
+
 // calib.hip: box calibration for bench.py - out[0..6] = copy GB/s, dense MFMA TFLOP/s, us per launch of a 323-launch empty
 // graph, us per launch of a 323-launch chain of short kernels on cold operands, us per launch of a 323-launch chain handing 8 MB
 // over between the XCDs' L2s, ns per dependent load from HBM / from the caches

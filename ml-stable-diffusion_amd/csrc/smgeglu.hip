@@ -1,0 +1,421 @@
+// GEGLU projection of the 640- and 1280-channel levels in one chip-filling round (plan tile 13): unet.py:609-617 ff.net.0.proj with
+// or without the LayerNorm in front of it folded in (UNet::fold_layernorm), out[m][j] = v * gelu_erf(g).
+//
+// On igemm_kernel's 64 x 128 tile these launches are 640 / 1280 workgroups on 512 slots (1.25 / 2.5 rounds, each round paying the
+// kernel's shell), every workgroup pulls (64 + 128) rows x K through LDS (43 FLOP per byte filled) and the ring is 2 stages deep.
+// This kernel is smgemm.hip's whole-LDS ring cut to the GEGLU case:
+//   * workgroup = BM rows x 80 output columns = 160 weight rows, BM = 128 (M = 512) / 256 (M = 2048): 256 workgroups, one per CU;
+//   * the weights are read as uploaded (rows interleaved 32 value / 32 gate): a 16-column unit is 16 value rows + the 16 gate rows
+//     32 further on, both as A operands of v_mfma_f32_16x16x32_f16, so value and gate of an output meet in one lane's accumulators;
+//   * ten waves = 5 column units x 2 row halves (3, 3, 2, 2 per SIMD); per K64 stage a wave reads its unit's two weight fragments
+//     and its BM / 32 row blocks, two K32 sub-steps each;
+//   * ring stage = [160 weight rows, unit-major | BM activation rows] of 128 B: 36 KB x 4 stages / 52 KB x 3 stages, no padding.
+//     36 / 52 1-KiB pieces do not divide by ten: the first 6 / 2 waves issue one piece more per stage than the others, and every
+//     wave counts its own vmcnt (two instances of the wait ladder behind a wave-uniform branch);
+//   * LayerNorm row statistics by fdot2 from the activation fragments, the row blocks of a half dealt out to four of its five
+//     waves, exchanged once through LDS behind one barrier after the K loop;
+//   * bias / colsum of the lane's columns requested right behind the first ring stages (same vmcnt); epilogue from the
+//     accumulators with the arithmetic of igemm.hip tile_epilogue, fp16 pairs of two row blocks meet through v_permlane16_swap,
+//     every lane stores 16 B of one output row.
+// PROF instantiation (ConvDesc::prof): every wave leaves six shader-clock stamps (sd_op_geglu_ln prints the table).
+#include <algorithm>
+
+#include "kernels.h"
+#include "sm_ring.h"
+
+namespace sd {
+
+namespace {
+
+constexpr int SG_BK = 64;                  // K halves per ring stage (128-B rows)
+constexpr int SG_UNITS = 5;                // 16-column units side by side
+constexpr int SG_WROWS = 32 * SG_UNITS;    // weight rows per workgroup: 16 value + 16 gate rows per unit
+constexpr int SG_BN = 16 * SG_UNITS;       // output columns per workgroup
+constexpr int SG_NW = 2 * SG_UNITS;        // waves: unit x row half
+constexpr int SG_LDS = 160 * 1024;
+constexpr int SG_STAMPS = 8;               // long long slots per wave in ConvDesc::prof (six used)
+
+struct SgArgs {
+  const half_t* x;       // [M][K]
+  const half_t* w;       // [N][K], rows interleaved 32 value / 32 gate
+  const float* bias;     // [N]; has_bias == 0: any readable float[N] (the loads keep their count)
+  const float* colsum;   // [N]; lnf == 0: any readable float[N]
+  half_t* out;           // [M][N / 2]
+  long long* prof;       // PROF: [workgroup][wave][SG_STAMPS]
+  int K, nk, ldo;
+  int has_bias, lnf;
+  float ln_eps;
+  unsigned per_xcd;      // workgroups of one XCD's contiguous tile run (grid % 8 == 0)
+  unsigned fast_div;     // tiles along the fast dimension (>= 2)
+  unsigned fast_magic;   // floor(2^32 / fast_div) + 1 (smgemm.hip)
+  int n_fast;            // 1: consecutive tiles share an activation panel, 0: a weight panel
+};
+
+template <int BM>
+struct SgCfg {
+  static constexpr int ROWS = SG_WROWS + BM;                   // staged rows per stage: weights, then activations
+  static constexpr int PIECES = ROWS / 8;                      // 1-KiB LDS-DMA pieces (8 rows x 128 B) per stage
+  static constexpr int PPW = (PIECES + SG_NW - 1) / SG_NW;     // pieces per wave per stage: the first FULL waves; the others one less
+  static constexpr int FULL = PIECES - SG_NW * (PPW - 1);
+  static constexpr int STAGE = PIECES * 1024;                  // bytes per stage
+  static constexpr int NST = (SG_LDS - BM * 8) / STAGE;        // ring depth; the row statistics (float2 per row) sit behind the ring
+  static constexpr int TM = BM / 32;                           // 16-row blocks per wave (one row half)
+  static constexpr int SB = TM / 4;                            // blocks whose statistics a wave of units 0-3 carries
+  static constexpr int EPI = 4;                                // epilogue loads per lane: bias and colsum of value / gate rows
+  static constexpr size_t LDS = (size_t)NST * STAGE + BM * 8;
+  static_assert(BM % 128 == 0 && ROWS % 8 == 0 && PPW >= 2 && FULL >= 1 && FULL <= SG_NW, "tile");
+  static_assert(NST >= 3 && LDS <= SG_LDS, "ring");
+  static_assert(PPW * (NST - 2) + EPI <= 63, "vmcnt range");
+};
+
+__device__ __forceinline__ float sg_gelu_erf(float x) {   // igemm.hip gelu_erf (Abramowitz-Stegun 7.1.26)
+  const float z = x * 0.70710678118654752f;
+  const float az = fabsf(z);
+  const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, az, 1.0f));
+  float p = 1.061405429f;
+  p = fmaf(p, t, -1.453152027f);
+  p = fmaf(p, t, 1.421413741f);
+  p = fmaf(p, t, -0.284496736f);
+  p = fmaf(p, t, 0.254829592f);
+  const float e = __builtin_amdgcn_exp2f(-az * az * 1.4426950408889634f);
+  const float erf_abs = fmaf(-p * t, e, 1.0f);
+  return 0.5f * x * (1.0f + copysignf(erf_abs, z));
+}
+
+// first weight row of 16-column unit U of the output: its 16 value rows; the gate rows are 32 further on
+__device__ __forceinline__ int sg_unit_row(int U) { return 64 * (U >> 1) + 16 * (U & 1); }
+
+template <int BM, bool PROF>
+__global__ __launch_bounds__(64 * SG_NW, 1) void smgeglu_kernel(SgArgs a) {
+  using C = SgCfg<BM>;
+  constexpr int NST = C::NST, PPW = C::PPW, TM = C::TM, SB = C::SB;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  long long stamp[6] = {};
+  if constexpr (PROF) stamp[0] = clock64();
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+  const int u = wave % SG_UNITS, h = wave / SG_UNITS;   // column unit, row half
+
+  // XCD-aware tile order (block b runs on XCD b % 8): XCD x walks tiles [x * per_xcd, (x + 1) * per_xcd)
+  const unsigned t = (blockIdx.x & 7u) * a.per_xcd + (blockIdx.x >> 3);
+  const unsigned slow = __umulhi(t, a.fast_magic);
+  const unsigned fast = t - slow * a.fast_div;
+  const int m_blk = (int)(a.n_fast ? slow : fast) * BM;
+  const int u_blk = (int)(a.n_fast ? fast : slow) * SG_UNITS;   // first 16-column unit of the tile
+
+  // ---- staging: piece wave + 10 j of every stage (the last j only on the first FULL waves), one 16-B chunk of one staged row per
+  // lane.  Staged weight row r: unit r / 32, value (r & 16 == 0) or gate row r & 15 ----
+  const bool full = wave < C::FULL;
+  const half_t* src[PPW];
+  int pdst[PPW];
+#pragma unroll
+  for (int j = 0; j < PPW; ++j) {
+    int p = wave + SG_NW * j;
+    if (p >= C::PIECES) p -= C::PIECES;                   // (never issued: keeps the address in range)
+    pdst[j] = p * 1024;
+    const int r = p * 8 + (lane >> 3);                    // staged row
+    const int chunk = (lane & 7) ^ ((r >> 1) & 7);        // logical chunk at physical slot lane & 7
+    const int wrow = sg_unit_row(u_blk + (r >> 5)) + 2 * (r & 16) + (r & 15);
+    src[j] = (r < SG_WROWS ? a.w + (size_t)wrow * a.K : a.x + (size_t)(m_blk + r - SG_WROWS) * a.K) + chunk * 8;
+  }
+  // ring stage into slot `slot`
+  auto issue = [&](int slot) {
+    char* st = smem + slot * C::STAGE;
+#pragma unroll
+    for (int j = 0; j < PPW; ++j) {
+      if (j == PPW - 1 && !full) break;
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src[j],
+                                       (__attribute__((address_space(3))) void*)(st + pdst[j]), 16, 0, 0);
+      src[j] += SG_BK;
+    }
+  };
+
+#pragma unroll
+  for (int p = 0; p < NST - 1; ++p)
+    if (p < a.nk) issue(p);
+  // the epilogue operands right behind the first ring stages: bias and colsum of this lane's four value and four gate rows
+  // (absent: a readable dummy, so that every launch counts the same loads)
+  const int g = lane >> 4, r16 = lane & 15;
+  const int vrow = sg_unit_row(u_blk + u) + 4 * g;
+  __builtin_amdgcn_sched_barrier(0);
+  const floatx4 bias_v = *reinterpret_cast<const floatx4*>(a.bias + vrow);
+  const floatx4 bias_g = *reinterpret_cast<const floatx4*>(a.bias + vrow + 32);
+  const floatx4 cs_v = *reinterpret_cast<const floatx4*>(a.colsum + vrow);
+  const floatx4 cs_g = *reinterpret_cast<const floatx4*>(a.colsum + vrow + 32);
+  __builtin_amdgcn_sched_barrier(0);
+  if constexpr (PROF) stamp[1] = clock64();
+
+  // fragment offsets inside a stage: row (16-row block base + r16), logical chunk 4 kk + g; every block base is a multiple of 16,
+  // so the swizzle of the row is (r16 >> 1) & 7
+  int foff[2];
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk) foff[kk] = r16 * 128 + (((4 * kk + g) ^ ((r16 >> 1) & 7)) * 16);
+  const int w_off = 32 * u * 128;                                   // the unit's value rows; gate rows 16 further on
+  const int x_off = (SG_WROWS + h * (BM / 2)) * 128;                // the half's first row block
+
+  floatx4 accv[TM], accg[TM];
+#pragma unroll
+  for (int i = 0; i < TM; ++i) accv[i] = accg[i] = floatx4{0.f, 0.f, 0.f, 0.f};
+  float ln_s1[SB], ln_s2[SB];   // sum x, sum x^2 over this lane's K chunks of row r16 of blocks u * SB .. (units 0-3)
+#pragma unroll
+  for (int s = 0; s < SB; ++s) ln_s1[s] = ln_s2[s] = 0.f;
+  const half2v one2 = {(half_t)1.f, (half_t)1.f};
+
+  // The K loop runs on the stage in quarters q = (sub-step kk = q / NG, row blocks 4 (q % NG) .. + 3), software-pipelined across
+  // the stage boundary: while the MFMAs of one quarter run, the fragments of the next are on their way from LDS - the next
+  // stage's weight fragments and first quarter during the last quarter of this one, so a wave never holds more than two
+  // quarters of fragments beside its 2 TM accumulators (all of a 256-row stage's would not fit in 168 VGPRs).  Against reading a
+  // whole stage behind the barrier and then running its MFMAs this measured no gain at BM = 128 (LAB_NOTES Finding 22).
+  constexpr int NG = TM / 4, NQ = 2 * NG;
+  half8 wv[2], wg[2], wvn[2], wgn[2], xq[2][4];
+  auto read_w = [&](const char* st, half8 (&v)[2], half8 (&gt)[2]) {
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      v[kk] = *reinterpret_cast<const half8*>(st + w_off + foff[kk]);
+      gt[kk] = *reinterpret_cast<const half8*>(st + w_off + 16 * 128 + foff[kk]);
+    }
+  };
+  auto read_q = [&](const char* st, int q) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      xq[q & 1][i] = *reinterpret_cast<const half8*>(st + x_off + 16 * (4 * (q % NG) + i) * 128 + foff[q / NG]);
+  };
+  // stage s has landed for this wave once only the newer ring stages - and, while s is one of the first NST - 1, the epilogue
+  // loads - are in flight; the barrier then says so for every wave
+  auto wait_stage = [&](int s) {
+    const int ahead = min(NST - 2, a.nk - 1 - s);
+    if (full) {
+      if (s <= NST - 2) sm_wait<PPW, C::EPI, NST - 2>(ahead);
+      else sm_wait<PPW, 0, NST - 2>(ahead);
+    } else {
+      if (s <= NST - 2) sm_wait<PPW - 1, C::EPI, NST - 2>(ahead);
+      else sm_wait<PPW - 1, 0, NST - 2>(ahead);
+    }
+  };
+
+  wait_stage(0);
+  if constexpr (PROF) stamp[2] = clock64();
+  if (NST - 1 < a.nk) issue(NST - 1);
+  read_w(smem, wv, wg);
+  read_q(smem, 0);
+  __builtin_amdgcn_sched_barrier(0);
+  int slot = 0;   // slot of stage rel
+  for (int rel = 0; rel < a.nk; ++rel) {
+    const char* st = smem + slot * C::STAGE;
+    const int nslot = slot + 1 == NST ? 0 : slot + 1;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const int kk = q / NG;
+      const bool next_stage = q + 1 == NQ && rel + 1 < a.nk;
+      if (next_stage) {
+        // every read of stage rel is back (this wave), the next stage has landed, and behind the barrier both hold for every
+        // wave: stage rel + NST may overwrite this stage's slot
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_stage(rel + 1);
+        if (rel + NST < a.nk) issue(slot);
+      }
+      // the quarter's first MFMA, then the next quarter's reads, then the rest: hipcc waits for ALL outstanding LDS reads in front
+      // of the first MFMA that needs one (lgkmcnt(0), not a counted wait), so the new reads must not be among them
+      __builtin_amdgcn_sched_barrier(0);
+      accv[4 * (q % NG)] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wv[kk], xq[q & 1][0], accv[4 * (q % NG)], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+      if (q + 1 < NQ) {
+        read_q(st, q + 1);
+      } else if (next_stage) {
+        read_w(smem + nslot * C::STAGE, wvn, wgn);
+        read_q(smem + nslot * C::STAGE, 0);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {   // rows = weight row, cols = m: lane holds columns 4 g + e of pixel r16
+        const int blk = 4 * (q % NG) + i;
+        if (i > 0) accv[blk] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wv[kk], xq[q & 1][i], accv[blk], 0, 0, 0);
+        accg[blk] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wg[kk], xq[q & 1][i], accg[blk], 0, 0, 0);
+      }
+      if (a.lnf) {   // VALU work between the MFMAs; row block blk belongs to the wave of unit blk / SB
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int blk = 4 * (q % NG) + i;
+          if (blk / SB == u) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const half2v p2 = {xq[q & 1][i][2 * e], xq[q & 1][i][2 * e + 1]};
+              ln_s2[blk % SB] = __builtin_amdgcn_fdot2(p2, p2, ln_s2[blk % SB], false);
+              ln_s1[blk % SB] = __builtin_amdgcn_fdot2(p2, one2, ln_s1[blk % SB], false);
+            }
+          }
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);   // keeps the later quarters' reads from being hoisted over this one
+    }
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) wv[kk] = wvn[kk], wg[kk] = wgn[kk];
+    slot = nslot;
+  }
+  if constexpr (PROF) stamp[3] = clock64();
+
+  // ---- row statistics: the four K-chunk groups of a row meet by lane shuffles, (ln_a, ln_b) of the tile's rows through LDS ----
+  float ln_a[TM], ln_b[TM];
+  if (a.lnf) {
+    float2* stat = reinterpret_cast<float2*>(smem + NST * C::STAGE);   // [BM], behind the ring
+    const float inv_k = 1.0f / (float)a.K;
+#pragma unroll
+    for (int s = 0; s < SB; ++s) {
+      float s1 = ln_s1[s], s2 = ln_s2[s];
+      s1 += __shfl_xor(s1, 16);
+      s2 += __shfl_xor(s2, 16);
+      s1 += __shfl_xor(s1, 32);
+      s2 += __shfl_xor(s2, 32);
+      const float mean = s1 * inv_k;
+      const float var = fmaxf(s2 * inv_k - mean * mean, 0.f);
+      const float la = rsqrtf(var + a.ln_eps);
+      if (u < 4 && g == 0) stat[h * (BM / 2) + 16 * (u * SB + s) + r16] = make_float2(la, -la * mean);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+      const float2 ab = stat[h * (BM / 2) + 16 * i + r16];
+      ln_a[i] = ab.x;
+      ln_b[i] = ab.y;
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < TM; ++i) ln_a[i] = 1.f, ln_b[i] = 0.f;
+  }
+  if constexpr (PROF) stamp[4] = clock64();
+
+  // ---- epilogue: tile_epilogue's arithmetic in fp32, one rounding to fp16, blocks (2p, 2p + 1) paired by v_permlane16_swap ----
+  const floatx4 zero4 = {0.f, 0.f, 0.f, 0.f};
+  const floatx4 bv = a.has_bias ? bias_v : zero4, bg = a.has_bias ? bias_g : zero4;
+  const int n = (u_blk + u) * 16 + 8 * (g >> 1);
+#pragma unroll
+  for (int p = 0; p < TM / 2; ++p) {
+    unsigned lo[2], hi[2];   // [block 2p | block 2p + 1] x {columns 4 g, 4 g + 1 | 4 g + 2, 4 g + 3}
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      const int i = 2 * p + b;
+      float o[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float v, gt;
+        if (a.lnf) {
+          v = fmaf(accv[i][e], ln_a[i], fmaf(ln_b[i], cs_v[e], bv[e]));
+          gt = fmaf(accg[i][e], ln_a[i], fmaf(ln_b[i], cs_g[e], bg[e]));
+        } else {
+          v = accv[i][e] + bv[e];
+          gt = accg[i][e] + bg[e];
+        }
+        o[e] = v * sg_gelu_erf(gt);
+      }
+      const half2v h01 = {(half_t)o[0], (half_t)o[1]};
+      const half2v h23 = {(half_t)o[2], (half_t)o[3]};
+      lo[b] = __builtin_bit_cast(unsigned, h01);
+      hi[b] = __builtin_bit_cast(unsigned, h23);
+    }
+    // the odd 16-lane rows of block 2p trade with the even rows of block 2p + 1: afterwards lane (g, r16) holds columns
+    // 8 (g >> 1) .. + 7 of row 16 (2p + (g & 1)) + r16, the first four in the `vdst` results (smgemm.hip)
+    const auto s0 = __builtin_amdgcn_permlane16_swap(lo[0], lo[1], false, false);
+    const auto s1 = __builtin_amdgcn_permlane16_swap(hi[0], hi[1], false, false);
+    const unsigned d0 = s0[0], d1 = s1[0], d2 = s0[1], d3 = s1[1];   // scalars first (igemm.hip xor32_sum)
+    typedef unsigned u4 __attribute__((ext_vector_type(4)));
+    const half8 o8 = __builtin_bit_cast(half8, (u4){d0, d1, d2, d3});
+    const int m = m_blk + h * (BM / 2) + 32 * p + 16 * (g & 1) + r16;
+    out_store(reinterpret_cast<half8*>(a.out + (size_t)m * a.ldo + n), o8);
+  }
+  if constexpr (PROF) {
+    stamp[5] = clock64();
+    if (lane == 0) {
+      long long* dst = a.prof + ((size_t)blockIdx.x * SG_NW + wave) * SG_STAMPS;
+#pragma unroll
+      for (int k = 0; k < 6; ++k) dst[k] = stamp[k];
+    }
+  }
+}
+
+// variant 1 / 2: BM = 128 / 256; 0: the smaller tile height whose grid is at most one round of 256 CUs
+int sg_bm(const ConvDesc& d, int variant) {
+  if (variant == 1) return 128;
+  if (variant == 2) return 256;
+  const long M = (long)d.B * d.Ho * d.Wo;
+  return M % 128 == 0 && M / 128 * (d.N / SG_WROWS) <= 256 ? 128 : 256;
+}
+
+template <int BM, bool PROF>
+void sg_launch(const SgArgs& a, unsigned nwg, hipStream_t s) {
+  auto k = smgeglu_kernel<BM, PROF>;
+  static DynLdsOnce once;
+  once.set(k, SgCfg<BM>::LDS);
+  hipLaunchKernelGGL(k, dim3(nwg), dim3(64 * SG_NW), SgCfg<BM>::LDS, s, a);
+}
+
+}  // namespace
+
+size_t smgeglu_prof_entries(const ConvDesc& d, int variant) {
+  const long M = (long)d.B * d.Ho * d.Wo;
+  return (size_t)(M / sg_bm(d, variant) * (d.N / SG_WROWS)) * SG_NW * SG_STAMPS;
+}
+
+bool smgeglu_shape_ok(const ConvDesc& d, int variant) {
+  if (!(d.ksize == 1 && d.stride == 1 && d.up == 1 && !d.x1 && d.out_mode == kOutGeglu && !d.out_t && !d.temb && !d.res &&
+        d.q_cols == 0 && !d.gnf_partial && !d.gn_partial && d.n_twins == 0 && !d.debug && (!d.ln_colsum || d.bias) && variant >= 0 &&
+        variant <= 2))
+    return false;
+  const long M = (long)d.B * d.Ho * d.Wo;
+  const int bm = sg_bm(d, variant);
+  const long mt = M / bm, nt = d.N / SG_WROWS;
+  return d.C0 % SG_BK == 0 && d.C0 >= SG_BK && d.N % SG_WROWS == 0 && d.N % 64 == 0 && M % bm == 0 && mt >= 2 && nt >= 2 &&
+         (mt * nt) % 8 == 0 && mt * nt <= 65535;
+}
+
+// the library's rule: GEGLU projections whose grid of BM x 80 tiles fills the chip once (192-256 workgroups): SD2.1's 1280 -> 10240
+// at M = 512 and 640 -> 5120 at M = 2048.  Everything else - the M = 128 level (64 tiles), the 64 x 64 level (wsgemm.hip), SDXL's and
+// the refiner's widths, batched prompts (more than one round) - keeps its measured plan.
+bool smgeglu_wanted(const ConvDesc& d) {
+  if (!smgeglu_shape_ok(d, 0)) return false;
+  const long M = (long)d.B * d.Ho * d.Wo;
+  const long tiles = M / sg_bm(d, 0) * (d.N / SG_WROWS);
+  return tiles >= 192 && tiles <= 256;
+}
+
+void launch_smgeglu(const ConvDesc& d, int variant, hipStream_t s) {
+  SD_REQUIRE(smgeglu_shape_ok(d, variant), kInvalidArgument,
+             "plan tile 13 (smgeglu.hip): not a single-source 1x1 GEGLU projection it tiles (C0=%d N=%d M=%d)", d.C0, d.N, d.B * d.Ho * d.Wo);
+  const int M = d.B * d.Ho * d.Wo, K = d.C0;
+  const int bm = sg_bm(d, variant);
+  const unsigned mt = M / bm, nt = d.N / SG_WROWS, nwg = mt * nt;
+  SgArgs a;
+  a.x = d.x0;
+  a.w = d.w;
+  a.bias = d.bias ? d.bias : reinterpret_cast<const float*>(d.w);   // K >= 64: the weights hold more than N floats
+  a.colsum = d.ln_colsum ? d.ln_colsum : a.bias;
+  a.out = d.out;
+  a.prof = d.prof;
+  a.K = K;
+  a.nk = K / SG_BK;
+  a.ldo = d.N / 2;
+  a.has_bias = d.bias != nullptr;
+  a.lnf = d.ln_colsum != nullptr;
+  a.ln_eps = d.ln_eps;
+  a.per_xcd = nwg / 8;
+  // tile order by the bytes each pulls into the 8 XCD L2s (smgemm.hip, igemm.hip choose_tile_order)
+  const double a_bytes = 2.0 * M * K, w_bytes = 2.0 * d.N * K, l2 = 3.5e6;
+  const double m_fast_cost = w_bytes + a_bytes * (a_bytes <= l2 ? std::min(8.0, (double)nt) : (double)nt);
+  const double n_fast_cost = a_bytes + w_bytes * (w_bytes <= l2 ? std::min(8.0, (double)mt) : (double)mt);
+  a.n_fast = n_fast_cost < m_fast_cost;
+  a.fast_div = a.n_fast ? nt : mt;
+  a.fast_magic = (unsigned)((1ull << 32) / a.fast_div + 1);
+  static const bool log_plans = tune_env_set("SD_LOG_CONVS");
+  if (log_plans)
+    fprintf(stderr, "[sd conv] k1 s1 up1 C0=%d C1=0 M=%d N=%d K=%d mode=%d tile=13 bm=%d n_fast=%d\n", d.C0, M, d.N, K, d.out_mode, bm,
+            a.n_fast);
+  if (bm == 128) {
+    if (d.prof) sg_launch<128, true>(a, nwg, s);
+    else sg_launch<128, false>(a, nwg, s);
+  } else {
+    if (d.prof) sg_launch<256, true>(a, nwg, s);
+    else sg_launch<256, false>(a, nwg, s);
+  }
+  SD_HIP(hipGetLastError());
+}
+
+}  // namespace sd

@@ -19,6 +19,7 @@
 #include <algorithm>
 
 #include "kernels.h"
+#include "sm_ring.h"
 
 namespace sd {
 
@@ -56,26 +57,6 @@ struct SmCfg {
   static_assert(NST >= 3 && NST * STAGE <= SM_LDS, "ring");
   static_assert(PPW * (NST - 2) + EPI <= 63, "vmcnt range");
 };
-
-template <int N>
-__device__ __forceinline__ void sm_wait_barrier() {   // counted wait + raw barrier in one statement (no LDS access moves across)
-  asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
-}
-
-// counted wait for the stage to consume: `ahead` newer ring stages in flight (PPW pieces each), plus E epilogue loads issued after
-// it (the immediate must be a literal, hence the ladder)
-template <int PPW, int E, int A>
-__device__ __forceinline__ void sm_wait(int ahead) {
-  if constexpr (A > 0) {
-    if (ahead == A) {
-      sm_wait_barrier<PPW * A + E>();
-      return;
-    }
-    sm_wait<PPW, E, A - 1>(ahead);
-  } else {
-    sm_wait_barrier<E>();
-  }
-}
 
 template <int BM>
 __global__ __launch_bounds__(64 * SM_NW, 1) void smgemm_kernel(SmArgs a) {

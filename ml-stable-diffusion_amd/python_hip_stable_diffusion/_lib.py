@@ -378,7 +378,10 @@ def geglu(x, w, bias=None, iters=1):
 
 def geglu_ln(x, w, bias=None, ln_weight=None, ln_bias=None, eps=1e-5, kernel=0, iters=1):
     """GEGLU projection with the LayerNorm in front of it folded in (unet.py:583-591 -> :609-617).  kernel: 0 the library's plan,
-    1 the tiled GEMM kernels, 2 the weight-stationary kernel (wsgemm.hip)."""
+    1 the tiled GEMM kernels, 2 the weight-stationary kernel (wsgemm.hip), 3-9 bvgemm.hip, 100 the one-round kernel of smgeglu.hip
+    (plan tile 13) with the tile height by the grid size, 101 / 102 its 128- / 256-row tiles (ValueError for shapes it does not
+    tile: it needs C % 64 == 0, N2 % 160 == 0, M a multiple of the tile height); 110-112: the same through the phase-clock build,
+    which prints its per-wave cycle table to stderr."""
     x, w = f16(x), f16(w)
     M, Cn = x.shape
     N2 = w.shape[0]
