@@ -303,9 +303,16 @@ int sd_op_conv2d_groupnorm_conv3x3(const void* x, const void* w, const float* bi
  * out = res2 + proj_out(res1 + ff.net.2(g) + b1) + b2.  fused = 1: ONE launch (32 tokens x 5 waves per workgroup, C = 320,
  * S % 32 == 0; the intermediate never goes to HBM), fused = 0: the two 1x1 GEMMs.  g (B, 4C, 1, S), res1 / res2 / out (B, C, 1, S) f16,
  * w1 (C, 4C), w2 (C, C) f16, b1 / b2 (C) f32.  gn_sums (may be NULL): (B, groups, 2) f32 - the GroupNorm statistics (sum, sum of
- * squares per sample and group) the launch left for a consuming GroupNorm, folded; NaN when it left none. */
+ * squares per sample and group) the launch left for a consuming GroupNorm, folded; NaN when it left none.
+ * fused = 2 .. 5: the merged tail - the weights folded on the device ([w2 w1 | w2], bias w2 b1 + b2: sd_op_fold_linear, outside the timed
+ * region) and ONE GEMM over the K-concatenation [g | res1] with residual res2, any C % 64 == 0: 2 = on the library's own plan, 3 = forced
+ * onto the tiled igemm kernels, 4 / 5 = forced onto smgemm.hip's 32- / 64-row tiles (SD_ERR_INVALID_ARGUMENT for a shape the forced kernel
+ * does not tile).  gn_sums with 2 and 3 as with 0. */
 int sd_op_ffn_out_proj(const void* g, const void* w1, const float* b1, const void* res1, const void* w2, const float* b2, const void* res2,
                        void* out, float* gn_sums, int B, int C, int S, int groups, int fused, int iters, float* ms);
+/* Debug entry of the weight fold behind the merged tail (wfold.hip): wm_out (N, K) f16 = fp16(wp w2) with fp32 accumulation in a fixed
+ * order and one round-to-nearest-even, bm_out (N) f32 = bp + wp b2.  wp (N, J), w2 (J, K) f16, bp (N), b2 (J) f32. */
+int sd_op_fold_linear(const void* wp, const float* bp, const void* w2, const float* b2, void* wm_out, float* bm_out, int N, int J, int K);
 /* Cross-attention front half as one launch (unet.py:87-118 inside :586-591): out = softmax(to_q(LayerNormANE(x)) k^T / 8) v
  * per head, head dim 64, Sk <= 96 (the prompt), any Sq >= 1 (ragged last token tile).  V^T columns [Sk, round_up(Sk, 8)) must be
  * zero (this entry point zero-fills them; the masked probabilities there are 0 but 0 * inf would be NaN).  x (B, heads*64, 1, Sq), k / v (B, heads*64, 1, Sk) f16 BC1S,

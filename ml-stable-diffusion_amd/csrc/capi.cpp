@@ -998,7 +998,8 @@ int sd_op_ffn_out_proj(const void* g, const void* w1, const float* b1, const voi
     SD_REQUIRE(g && w1 && b1 && res1 && w2 && b2 && res2 && out, kInvalidArgument, "NULL argument");
     const int K1 = 4 * C, M = B * S;
     SD_REQUIRE(B > 0 && C % 64 == 0 && S > 0, kInvalidArgument, "ffn_out_proj: B=%d C=%d S=%d", B, C, S);
-    SD_REQUIRE(!fused || ffn_proj_ok(C, K1, M, S), kUnsupported, "ffn_out_proj: the one-launch form takes C = 320 and S %% 32 == 0 (C=%d S=%d)", C, S);
+    SD_REQUIRE(fused >= 0 && fused <= 5, kInvalidArgument, "ffn_out_proj: fused code %d", fused);
+    SD_REQUIRE(fused != 1 || ffn_proj_ok(C, K1, M, S), kUnsupported, "ffn_out_proj: the one-launch form takes C = 320 and S %% 32 == 0 (C=%d S=%d)", C, S);
     SD_REQUIRE(!gn_sums || (groups >= 1 && C % groups == 0), kInvalidArgument, "ffn_out_proj: groups %d", groups);
     Scratch sc;
     auto to_tokens = [&](const void* p, int ch) {   // (B, ch, 1, S) -> [B * S][ch]
@@ -1026,7 +1027,23 @@ int sd_op_ffn_out_proj(const void* g, const void* w1, const float* b1, const voi
       SD_HIP(hipMemcpy(partial, poison.data(), pf * sizeof(float), hipMemcpyHostToDevice));
     }
     int n_entries = 0;
-    if (fused) {
+    if (fused >= 2) {   // the merged tail: weight fold (once per handle, outside the timed region), then ONE two-source GEMM
+      half_t* wm = sc.dev<half_t>((size_t)C * (K1 + C));
+      float* bm = sc.dev<float>(C);
+      launch_wfold(dw2, db2, dw1, db1, wm, bm, C, C, K1, sc.stream);
+      ConvDesc cd;
+      cd.x0 = dg; cd.C0 = K1; cd.x1 = dr1; cd.C1 = C; cd.w = wm; cd.bias = bm; cd.res = dr2; cd.out = o;
+      cd.B = B; cd.Hi = 1; cd.Wi = S; cd.Ho = 1; cd.Wo = S; cd.N = C;
+      cd.gn_partial = partial;
+      cd.gn_groups = groups;
+      SD_REQUIRE(conv_fast_path_ok(cd), kInvalidArgument, "ffn_out_proj: off the MFMA path");
+      if (fused == 3) cd.tile = 3;                        // igemm_kernel's 64 x 64 tile, split-K by the heuristic
+      if (fused >= 4) cd.tile = 12, cd.staging = fused - 3;   // smgemm.hip, 32- / 64-row tiles
+      ConvWorkspace ws;
+      ws.partial_bytes = conv_workspace_bytes(cd);
+      if (ws.partial_bytes) ws.partial = reinterpret_cast<float*>(sc.dev<char>(ws.partial_bytes));
+      sc.timed(iters, ms, [&] { n_entries = launch_conv(cd, ws, sc.stream); });
+    } else if (fused) {
       half_t* w1_t = sc.dev<half_t>((size_t)C * K1);
       half_t* w2_t = sc.dev<half_t>((size_t)C * C);
       launch_xattn_out_retile_nk(dw1, w1_t, C, K1, sc.stream);
@@ -1075,6 +1092,27 @@ int sd_op_ffn_out_proj(const void* g, const void* w1, const float* b1, const voi
           gn_sums[((size_t)b * groups + gi) * 2 + 1] = n_entries ? (float)s2 : NAN;
         }
     }
+  });
+}
+
+int sd_op_fold_linear(const void* wp, const float* bp, const void* w2, const float* b2, void* wm_out, float* bm_out, int N, int J, int K) {
+  return guarded([&] {
+    SD_REQUIRE(wp && bp && w2 && b2 && wm_out && bm_out && N > 0 && J > 0 && K > 0, kInvalidArgument, "fold_linear: N=%d J=%d K=%d", N, J, K);
+    Scratch sc;
+    half_t* dwp = sc.dev<half_t>((size_t)N * J, reinterpret_cast<const half_t*>(wp));
+    half_t* dw2 = sc.dev<half_t>((size_t)J * K, reinterpret_cast<const half_t*>(w2));
+    float* dbp = sc.dev<float>(N, bp);
+    float* db2 = sc.dev<float>(J, b2);
+    half_t* merged = sc.dev<half_t>((size_t)N * (K + J));
+    float* bm = sc.dev<float>(N);
+    launch_wfold(dwp, dbp, dw2, db2, merged, bm, N, J, K, sc.stream);
+    SD_HIP(hipStreamSynchronize(sc.stream));
+    SD_HIP(hipMemcpy2D(wm_out, (size_t)K * 2, merged, (size_t)(K + J) * 2, (size_t)K * 2, N, hipMemcpyDeviceToHost));
+    SD_HIP(hipMemcpy(bm_out, bm, (size_t)N * sizeof(float), hipMemcpyDeviceToHost));
+    // the copied block behind the folded columns must be Wp itself
+    std::vector<half_t> tail((size_t)N * J);
+    SD_HIP(hipMemcpy2D(tail.data(), (size_t)J * 2, merged + K, (size_t)(K + J) * 2, (size_t)J * 2, N, hipMemcpyDeviceToHost));
+    SD_REQUIRE(std::memcmp(tail.data(), wp, tail.size() * 2) == 0, kInternal, "fold_linear: the Wp columns of the merged matrix differ from Wp");
   });
 }
 

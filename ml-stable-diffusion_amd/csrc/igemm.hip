@@ -2675,6 +2675,18 @@ bool conv_plan_is_wstream(const ConvDesc& d0) {
   return choose_plan(d, a).tile == 9;
 }
 
+// Does the compiled-in plan table hold a row for this shape - a plan that was measured in a step?
+bool conv_plan_is_tuned(const ConvDesc& d) {
+  if (!conv_fast_path_ok(d)) return false;
+  const IgemmArgs a = make_args(d);
+  const int kind = conv_kind(d);
+  for (int i = 0; i < kNumTuned; ++i) {
+    const TunedConv& t = kTuned[i];
+    if (t.kind == kind && t.ksize == a.ksize && t.stride == a.stride && t.up == a.up && t.ctot == a.Ctot && t.n == a.N && t.m == a.M) return true;
+  }
+  return false;
+}
+
 size_t conv_workspace_bytes(const ConvDesc& d) {
   if (!conv_fast_path_ok(d)) return 0;
   IgemmArgs a = make_args(d);

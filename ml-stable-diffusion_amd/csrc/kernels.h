@@ -114,6 +114,7 @@ bool conv_fast_path_ok(const ConvDesc& d);
 bool conv_gn_loader_ok(const ConvDesc& d);   // gnf_* on a 3x3 conv (gnf_groups set): the halo kernel can normalise this input in its loader
 // tuning hook: plan (tile 1-6, staging 0-5, splitk) forced on every conv that admits it; tile 0 = off
 void conv_tune_set_candidate(int tile, int staging, int splitk);
+bool conv_plan_is_tuned(const ConvDesc& d);   // tuned_convs.inc has a row for this shape
 int conv_plan_table_set(const char* text);   // rows of tuned_convs.inc format; returns the number of plans read
 
 // wstream.hip: the small-M weight-streaming kernel (plan tile 9) and the group-organised slab combine
@@ -141,10 +142,15 @@ void launch_bvgemm_retile(const half_t* w, half_t* wt, int N, int K, bool geglu,
 void launch_bvgemm(const ConvDesc& d, int variant, hipStream_t s);   // variant 1-4 (bvgemm.hip), 0 = the library's choice
 bool bvgemm_wanted(const ConvDesc& d);                                // the library's rule for taking plan tile 11 on its own
 
-// smgemm.hip: small-M single-source 1x1 GEMM, whole-LDS ring, epilogue from the accumulators (plan tile 12)
+// smgemm.hip: small-M 1x1 GEMM (one source, or two concatenated along K), whole-LDS ring, epilogue from the accumulators (plan tile 12)
 bool smgemm_shape_ok(const ConvDesc& d, int variant);                 // variant 1 / 2: 32- / 64-row tiles, 0: by M
 bool smgemm_wanted(const ConvDesc& d);                                // the library's rule for taking plan tile 12 on its own
 void launch_smgemm(const ConvDesc& d, int variant, hipStream_t s);
+
+// wfold.hip: two back-to-back linear maps folded into one - merged [N][K + J] = [fp16(Wp W2) | Wp], bm = bp + Wp b2 (Wp [N][J],
+// W2 [J][K]; fp32 accumulation in a fixed order, once per handle: UNet::transformer_block's merged tail)
+void launch_wfold(const half_t* wp, const float* bp, const half_t* w2, const float* b2, half_t* merged, float* bm, int N, int J, int K,
+                  hipStream_t s);
 
 // smgeglu.hip: GEGLU projection (with or without the LayerNorm fold) on BM x 80 tiles, one workgroup per CU, whole-LDS ring, weights
 // as uploaded (plan tile 13)

@@ -1,5 +1,7 @@
-// Small-M single-source 1x1 GEMM (plan tile 12): the transformer projections of the 640- and 1280-channel levels
+// Small-M 1x1 GEMM (plan tile 12): the transformer projections of the 640- and 1280-channel levels
 // (unet.py:533-551 proj_in / proj_out, :62-118 to_out, :594-617 ff.net.2; plain epilogue: bias, optional residual).
+// One activation source, or two concatenated along K (the merged transformer tail [Wp W2 | Wp] [g | h2], wfold.hip): the weight
+// rows run along the whole K, the activation pieces change their source at ring stage C0 / 64.
 //
 // At M <= 2048 these GEMMs are neither FLOP- nor byte-bound on igemm_kernel's 64 x 64 tile: 160 workgroups leave 96 CUs idle, the
 // general im2col loader does integer divisions before its first DMA, a 3- / 4-stage ring keeps only 48-64 KB in flight per CU,
@@ -31,12 +33,14 @@ constexpr int SM_NW = SM_BN / 16;      // waves: one 16-column strip each
 constexpr int SM_LDS = 160 * 1024;
 
 struct SmArgs {
-  const half_t* x;      // [M][K]
+  const half_t* x;      // [M][ldx0]: K stages [0, nk0)
+  const half_t* x1;     // [M][ldx1]: K stages [nk0, nk) (single source: nk0 == nk, never read)
   const half_t* w;      // [N][K]
   const float* bias;    // [N]; has_bias == 0: any readable float[N] (the loads keep their count)
   const half_t* res;    // [M][res_ld]; has_res == 0: any readable half[N] with res_ld = 0
   half_t* out;          // [M][N]
   int K, N, nk, res_ld;
+  int nk0, ldx0, ldx1;
   int has_bias, has_res;
   unsigned per_xcd;     // workgroups of one XCD's contiguous tile run (grid % 8 == 0)
   unsigned fast_div;    // tiles along the fast dimension (>= 2)
@@ -81,8 +85,21 @@ __global__ __launch_bounds__(64 * SM_NW, 1) void smgemm_kernel(SmArgs a) {
     const int chunk = (lane & 7) ^ ((r >> 1) & 7);        // logical chunk at physical slot lane & 7
     int rx = r - SM_BN;
     if (rx >= BM) rx -= BM;                               // the padding pieces repeat activation rows
-    src[j] = (r < SM_BN ? a.w + (size_t)(n_blk + r) * a.K : a.x + (size_t)(m_blk + rx) * a.K) + chunk * 8;
+    src[j] = (r < SM_BN ? a.w + (size_t)(n_blk + r) * a.K : a.x + (size_t)(m_blk + rx) * a.ldx0) + chunk * 8;
   }
+  // second source: the activation pieces (j >= SM_BN / 8 / SM_NW: the first 80 staged rows are weights, whole pieces of them)
+  // restart on x1 when ring stage nk0 is issued - a wave-uniform compare per stage, vector work once per kernel
+  static_assert(SM_BN % (8 * SM_NW) == 0, "a piece is all weights or all activations, by j alone");
+  auto switch_source = [&]() {
+#pragma unroll
+    for (int j = SM_BN / (8 * SM_NW); j < PPW; ++j) {
+      const int r = (wave + SM_NW * j) * 8 + (lane >> 3);
+      const int chunk = (lane & 7) ^ ((r >> 1) & 7);
+      int rx = r - SM_BN;
+      if (rx >= BM) rx -= BM;
+      src[j] = a.x1 + (size_t)(m_blk + rx) * a.ldx1 + chunk * 8;
+    }
+  };
   // ring stage idx (< nk) into slot idx % NST
   auto issue = [&](int idx) {
     char* st = smem + (idx % NST) * C::STAGE + wave * 1024;   // wave-uniform piece base (M0)
@@ -135,7 +152,10 @@ __global__ __launch_bounds__(64 * SM_NW, 1) void smgemm_kernel(SmArgs a) {
       for (int i = 0; i < TM; ++i) xf[kk][i] = *reinterpret_cast<const half8*>(st + (SM_BN + 16 * i) * 128 + foff[kk]);
     }
     __builtin_amdgcn_sched_barrier(0);   // reads first, then the next DMA, then the MFMAs
-    if (rel + NST - 1 < a.nk) issue(rel + NST - 1);
+    if (rel + NST - 1 < a.nk) {
+      if (rel + NST - 1 == a.nk0) switch_source();   // (nk0 >= NST: never in the prologue, smgemm_shape_ok)
+      issue(rel + NST - 1);
+    }
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
@@ -173,6 +193,8 @@ __global__ __launch_bounds__(64 * SM_NW, 1) void smgemm_kernel(SmArgs a) {
   }
 }
 
+int sm_nst(int bm) { return bm == 32 ? SmCfg<32>::NST : SmCfg<64>::NST; }
+
 int sm_bm(const ConvDesc& d, int variant) {   // variant 1 / 2: BM = 32 / 64; 0: by M
   if (variant == 1) return 32;
   if (variant == 2) return 64;
@@ -182,12 +204,14 @@ int sm_bm(const ConvDesc& d, int variant) {   // variant 1 / 2: BM = 32 / 64; 0:
 }  // namespace
 
 bool smgemm_shape_ok(const ConvDesc& d, int variant) {
-  if (!(d.ksize == 1 && d.stride == 1 && d.up == 1 && !d.x1 && d.out_mode == kOutHalf && !d.ln_colsum && !d.out_t && !d.temb &&
+  if (!(d.ksize == 1 && d.stride == 1 && d.up == 1 && d.out_mode == kOutHalf && !d.ln_colsum && !d.out_t && !d.temb &&
         d.q_cols == 0 && !d.gnf_partial && d.n_twins == 0 && !d.debug && variant >= 0 && variant <= 2))
     return false;
   const long M = (long)d.B * d.Ho * d.Wo;
   const int bm = sm_bm(d, variant);
   const long mt = M / bm, nt = d.N / SM_BN;
+  // a second source starts on a stage boundary, behind the prologue's NST - 1 stages (the kernel switches inside the K loop only)
+  if (d.x1 && !(d.C1 % SM_BK == 0 && d.C1 >= SM_BK && d.C0 / SM_BK >= sm_nst(bm))) return false;
   return d.C0 % SM_BK == 0 && d.C0 >= SM_BK && d.N % SM_BN == 0 && M % bm == 0 && mt >= 2 && nt >= 2 && (mt * nt) % 8 == 0 &&
          mt * nt <= 65535;
 }
@@ -195,22 +219,26 @@ bool smgemm_shape_ok(const ConvDesc& d, int variant) {
 // the library's rule: the shapes whose grid fills the chip once (M <= 2048; larger M has enough tiles for igemm.hip's kernels).
 // Launches that must also leave GroupNorm statistics of their output (d.gn_partial) stay on igemm_kernel's epilogue, and so do
 // K > 2560: 80 serial K stages per workgroup lose to the 4-way split-K plan of 5120 -> 1280 at M = 512 (32.3 vs 28.3 us in sequence,
-// profiles/r07_smgemm_op_ab.txt).
+// profiles/r07_smgemm_op_ab.txt).  Two sources (the merged transformer tail): K = C0 + C1 <= 3200, the 32x32 level's 2560 + 640.
 bool smgemm_wanted(const ConvDesc& d) {
-  if (!smgemm_shape_ok(d, 0) || d.gn_partial || d.C0 > 2560) return false;
+  static const int k2_max = tune_env_int("SD_SMGEMM_K2_MAX", 3200);   // (with SD_TUNE: 6400 sends the 16x16 level's merged tail here, A/B)
+  if (!smgemm_shape_ok(d, 0) || d.gn_partial || (d.x1 ? d.C0 + d.C1 > k2_max : d.C0 > 2560)) return false;
   const long M = (long)d.B * d.Ho * d.Wo;
   const long tiles = M / sm_bm(d, 0) * (d.N / SM_BN);
   return M >= 256 && M <= 2048 && tiles >= 192 && tiles <= 256;
 }
 
 void launch_smgemm(const ConvDesc& d, int variant, hipStream_t s) {
-  SD_REQUIRE(smgemm_shape_ok(d, variant), kInvalidArgument, "plan tile 12 (smgemm.hip): not a single-source 1x1 GEMM it tiles (C0=%d N=%d)",
-             d.C0, d.N);
-  const int M = d.B * d.Ho * d.Wo, K = d.C0;
+  SD_REQUIRE(smgemm_shape_ok(d, variant), kInvalidArgument, "plan tile 12 (smgemm.hip): not a 1x1 GEMM it tiles (C0=%d C1=%d N=%d)",
+             d.C0, d.x1 ? d.C1 : 0, d.N);
+  const int M = d.B * d.Ho * d.Wo, K = d.C0 + (d.x1 ? d.C1 : 0);
   const int bm = sm_bm(d, variant);
   const unsigned mt = M / bm, nt = d.N / SM_BN, nwg = mt * nt;
   SmArgs a;
   a.x = d.x0;
+  a.x1 = d.x1 ? d.x1 : d.x0;
+  a.ldx0 = d.C0;
+  a.ldx1 = d.x1 ? d.C1 : d.C0;
   a.w = d.w;
   a.bias = d.bias ? d.bias : reinterpret_cast<const float*>(d.w);   // K >= 64: the weights hold more than N floats
   a.res = d.res ? d.res : d.w;
@@ -218,6 +246,7 @@ void launch_smgemm(const ConvDesc& d, int variant, hipStream_t s) {
   a.K = K;
   a.N = d.N;
   a.nk = K / SM_BK;
+  a.nk0 = d.C0 / SM_BK;
   a.res_ld = d.res ? d.N : 0;
   a.has_bias = d.bias != nullptr;
   a.has_res = d.res != nullptr;
@@ -232,7 +261,7 @@ void launch_smgemm(const ConvDesc& d, int variant, hipStream_t s) {
   a.fast_magic = (unsigned)((1ull << 32) / a.fast_div + 1);
   static const bool log_plans = tune_env_set("SD_LOG_CONVS");
   if (log_plans)
-    fprintf(stderr, "[sd conv] k1 s1 up1 C0=%d C1=0 M=%d N=%d K=%d mode=%d tile=12 bm=%d n_fast=%d\n", d.C0, M, d.N, K, d.out_mode, bm,
+    fprintf(stderr, "[sd conv] k1 s1 up1 C0=%d C1=%d M=%d N=%d K=%d mode=%d tile=12 bm=%d n_fast=%d\n", d.C0, d.x1 ? d.C1 : 0, M, d.N, K, d.out_mode, bm,
             a.n_fast);
   if (bm == 32) {
     auto k = smgemm_kernel<32>;

@@ -8,6 +8,13 @@
 // round 5: the weight-streaming kernel of wstream.hip (tile 9; staging 4 = four waves per workgroup, else eight) on the 8x8 level
 {0, 3, 1, 1, 1280, 1280, 128, 9, 0, 1},
 {0, 3, 1, 1, 2560, 1280, 128, 9, 0, 1},
+// round 9: the merged transformer tail [Wp W2 | Wp] [g | h2] (K = 5120 + 1280, two sources) keeps the plan of the 5120 -> 1280 GEMM it
+// replaces with a fifth split: 20 K steps per split as measured there, four splits on g and one on h2 (the source boundary is a
+// split boundary); accepted with the merge itself by the step A/B of profiles/r09_tail_merge_step_ab.txt; ten other plans (4 / 10
+// splits, the other tiles, a 3-stage ring) all lost to these end to end (tools/tune_e2e.py, same file)
+{0, 1, 1, 1, 6400, 1280, 512, 1, 3, 5},
+{0, 1, 1, 1, 6400, 1280, 128, 3, 3, 5},
+{0, 1, 1, 1, 6400, 1280, 1152, 2, 6, 2},  // SDXL-base 96x96: the merged tail on the plan of the 5120 -> 1280 GEMM it replaces (tools/tune_e2e.py, 15.188 -> 15.182 ms; five other plans lost)
 {0, 1, 1, 1, 5120, 1280, 512, 1, 3, 4},  // r6 re-tune on the final library (tools/tune_e2e.py, 4.397 -> 4.377 ms with the 640 -> 640 conv row below; was 2, 6, 2)
 {3, 1, 1, 1, 320, 960, 8192, 1, 8, 1},  // r4: 2-stage pipelined ring accepted end to end (tools/tune_e2e.py, 4.761 -> 4.698 ms; was tile 3 staging 6)
 {0, 1, 1, 1, 1280, 320, 8192, 3, 6, 1},

@@ -901,6 +901,63 @@ Tensor UNet::transformer_block(std::vector<Op>& ops, const std::string& b, const
     *tail_done = true;
     return out;
   }
+  // The other levels: the same tail as ONE GEMM over the K-concatenation [g | h2] with the folded weights [Wp W2 | Wp] and bias
+  // Wp b2 + bp (wfold.hip; both fixed for the life of the handle): h3 = W2 g + b2 + h2 has no other reader, so one launch and the
+  // write and read of h3 leave the step, at the same FLOPs and weight bytes.  The two source matrices only pass through a
+  // temporary buffer.  Only where the merged GEMM runs a plan that was measured in a step against the two launches it replaces -
+  // the two-source rule of smgemm.hip or a row of tuned_convs.inc (SD2.1-base's three levels, SDXL-base 768x768); any other shape
+  // keeps the two launches and their own tuned plans.  SD_TAIL_MERGE=0 (with SD_TUNE): the two GEMM launches everywhere (A/B),
+  // SD_TAIL_MERGE=2: the merge on every shape of the general rule (for measuring a new one).
+  static const int merge_mode = tune_env_int("SD_TAIL_MERGE", 1);
+  bool merge = proj_out && tres && tail_done && merge_mode != 0 && !f32_ && g.C == 4 * C && C % 64 == 0 && h.M() <= 2048;
+  if (merge && merge_mode != 2) {
+    ConvDesc md;
+    md.x0 = g.p;
+    md.C0 = 4 * C;
+    md.x1 = h2.p;
+    md.C1 = C;
+    md.B = h.B;
+    md.Hi = md.Ho = h.H;
+    md.Wi = md.Wo = h.W;
+    md.N = C;
+    merge = smgemm_wanted(md) || conv_plan_is_tuned(md);
+  }
+  if (merge) {
+    const int K1 = 4 * C;
+    const HostTensor& t2 = ws_->get(b + ".ff.net.2.weight");
+    const HostTensor& tp = ws_->get(*proj_out + ".weight");
+    const HostTensor& tb2 = ws_->get(b + ".ff.net.2.bias");
+    const HostTensor& tbp = ws_->get(*proj_out + ".bias");
+    SD_REQUIRE(t2.numel() == (size_t)C * K1 && tp.numel() == (size_t)C * C && (int)tb2.numel() == C && (int)tbp.numel() == C, kInvalidArgument,
+               "%s: ff.net.2 / proj_out parameter shapes", b.c_str());
+    // staging buffer, freed below: [b2 | bp] fp32, then [W2 | Wp] fp16 as the two-launch form uploads them
+    std::vector<float> hb(2 * (size_t)C);
+    std::vector<half_t> hw((size_t)C * K1 + (size_t)C * C);
+    for (int i = 0; i < C; ++i) hb[i] = tb2.data[i], hb[C + i] = tbp.data[i];
+    for (size_t i = 0; i < t2.numel(); ++i) hw[i] = (half_t)t2.data[i];
+    for (size_t i = 0; i < tp.numel(); ++i) hw[t2.numel() + i] = (half_t)tp.data[i];
+    half_t* wm = arena_.alloc_n<half_t>((size_t)C * (K1 + C));
+    float* bm = arena_.alloc_n<float>(C);
+    char* tmp = nullptr;
+    const size_t b_bytes = hb.size() * sizeof(float), w_bytes = hw.size() * sizeof(half_t);
+    SD_HIP(hipMalloc(reinterpret_cast<void**>(&tmp), b_bytes + w_bytes));
+    try {
+      SD_HIP(hipMemcpy(tmp, hb.data(), b_bytes, hipMemcpyHostToDevice));
+      SD_HIP(hipMemcpy(tmp + b_bytes, hw.data(), w_bytes, hipMemcpyHostToDevice));
+      const float* db = reinterpret_cast<const float*>(tmp);
+      const half_t* dw = reinterpret_cast<const half_t*>(tmp + b_bytes);
+      launch_wfold(dw + (size_t)C * K1, db + C, dw, db, wm, bm, C, C, K1, stream_);
+      SD_HIP(hipStreamSynchronize(stream_));
+    } catch (...) {
+      (void)hipFree(tmp);
+      throw;
+    }
+    SD_HIP(hipFree(tmp));
+    Tensor out = conv_w(ops, b + ".ff.net.2 + residual + proj_out + residual", wm, bm, g, &h2, C, 1, 1, 1, nullptr, tres->p, kOutHalf, 0, false);
+    ops.back().flop = 2.0 * h.M() * (double)C * K1 + 2.0 * h.M() * (double)C * C;   // the algorithmic count of the two maps
+    *tail_done = true;
+    return out;
+  }
   return conv(ops, b + ".ff.net.2", g, nullptr, C, 1, 1, 1, true, nullptr, h2.p);
 }
 

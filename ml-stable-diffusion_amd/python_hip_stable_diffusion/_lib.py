@@ -99,6 +99,7 @@ SYMBOLS = [
                                             C.POINTER(_I), _I, _FP]),
     ("sd_op_cross_attention_fused", _I, [_P, _FP, _FP, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _I, _FP]),
     ("sd_op_ffn_out_proj", _I, [_P, _P, _FP, _P, _P, _FP, _P, _P, _FP, _I, _I, _I, _I, _I, _I, _FP]),
+    ("sd_op_fold_linear", _I, [_P, _FP, _P, _FP, _P, _FP, _I, _I, _I]),
     ("sd_op_cross_attention_block", _I, [_P, _FP, _FP, _P, _P, _P, _P, _FP, _P, _P, _FP, _P, _I, _I, _I, _I, _F, _I, _I, _FP]),
     ("sd_op_geglu", _I, [_P, _P, _FP, _P, _I, _I, _I, _I, _FP]),
     ("sd_op_geglu_ln", _I, [_P, _FP, _FP, _P, _FP, _P, _I, _I, _I, C.c_float, _I, _I, _FP]),
@@ -334,8 +335,9 @@ def cross_attention_block(x, ln_weight, ln_bias, wq, k, v, wo, bo, heads, eps=1e
 
 
 def ffn_out_proj(g, w1, b1, res1, w2, b2, res2, groups=0, fused=True, iters=1):
-    """res2 + proj_out(res1 + ff.net.2(g) + b1) + b2 - the tail of a SpatialTransformer; fused=True runs it as ONE launch (C = 320,
-    S % 32 == 0).  g (B,4C,1,S), res1 / res2 (B,C,1,S) f16, w1 (C,4C), w2 (C,C) f16, b1 / b2 (C) f32.  groups > 0: also returns the
+    """res2 + proj_out(res1 + ff.net.2(g) + b1) + b2 - the tail of a SpatialTransformer; fused=True (1) runs it as ONE launch (C = 320,
+    S % 32 == 0), fused=False (0) as the two GEMMs; fused = 2 .. 5: folded weights and ONE two-source GEMM (2 the library's plan, 3 the
+    tiled igemm kernels, 4 / 5 smgemm.hip with 32- / 64-row tiles; ValueError for a shape the forced kernel does not tile).  g (B,4C,1,S), res1 / res2 (B,C,1,S) f16, w1 (C,4C), w2 (C,C) f16, b1 / b2 (C) f32.  groups > 0: also returns the
     GroupNorm statistics the launch left for its consumer, folded: (B, groups, 2) = (sum, sum of squares).  Returns (out, gn_sums or None, ms)."""
     g, res1, res2, w1, w2 = f16(g), f16(res1), f16(res2), f16(w1), f16(w2)
     B, Cn, _, S = res1.shape
@@ -348,6 +350,19 @@ def ffn_out_proj(g, w1, b1, res1, w2, b2, res2, groups=0, fused=True, iters=1):
     check(lib().sd_op_ffn_out_proj(ptr(g), ptr(w1), fptr(b1), ptr(res1), ptr(w2), fptr(b2), ptr(res2), ptr(out), fptr(sums), B, Cn, S, groups,
                                    int(fused), iters, C.byref(ms)))
     return out, sums, ms.value
+
+
+def fold_linear(wp, bp, w2, b2):
+    """The weight fold of the merged tail on its own: (fp16(wp @ w2), bp + wp @ b2).  wp (N, J), w2 (J, K) f16, bp (N), b2 (J) f32."""
+    wp, w2, bp, b2 = f16(wp), f16(w2), f32(bp), f32(b2)
+    N, J = wp.shape
+    K = w2.shape[1]
+    if w2.shape[0] != J or bp.shape != (N,) or b2.shape != (J,):
+        raise ValueError("fold_linear: inconsistent shapes")
+    wm = np.empty((N, K), np.float16)
+    bm = np.empty(N, np.float32)
+    check(lib().sd_op_fold_linear(ptr(wp), fptr(bp), ptr(w2), fptr(b2), ptr(wm), fptr(bm), N, J, K))
+    return wm, bm
 
 
 def cross_attention_fused(x, ln_weight, ln_bias, wq, k, v, heads, eps=1e-5, nst=0, iters=1):
