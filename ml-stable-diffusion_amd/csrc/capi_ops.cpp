@@ -1,0 +1,925 @@
+// Operator-level sd_op_* entry points of libsdmi355 (include/sd_mi355x.h): each drives one kernel, or one short launch sequence of
+// the UNet graph, from host tensors in the reference's layouts, so that a test can pin it against the oracle.  The weights go
+// through the layout rules of weight_prep.h - the ones the UNet builder applies - before they reach the device.
+//
+// Plan codes of the entry points (A/B testing and tuning tools; the header describes them for callers):
+//   conv `tile` (sd_op_conv2d, _groupnorm, _groupnorm_proj, _groupnorm_conv3x3): plan tile = tile % 10, staging = tile / 10
+//     tile    0 the library's plan, 1 128x128, 2 128x64, 3 64x64, 4 64x128, 7 the 3x3 halo kernel, 9 wstream.hip (needs w_tiled)
+//     staging 0 LDS-DMA 2-stage, 1 HBM -> VGPR -> LDS, 2 LDS-DMA 3-stage ring, ...; 12 / 13 (codes 12x / 13x) igemm_kernel's
+//             in-workgroup split-K rings
+//     sd_op_conv2d alone: 110-116 plan tile 11 (bvgemm.hip: its own choice / variants 1-6, needs w_bv),
+//                         140-142 plan tile 12 (smgemm.hip: tile height by M / 32 rows / 64 rows)
+//   sd_op_geglu_ln `kernel`: 0 the library's plan, 1 the tiled igemm / gemm_pipe kernels, 2 plan tile 10 (wsgemm.hip),
+//     2 + 10 n ablation build n of that kernel, 3-9 plan tile 11 (bvgemm.hip: its own choice / variants 1-6),
+//     100 plan tile 13 (smgeglu.hip) with the tile height by the grid size, 101 / 102 its 128- / 256-row tiles,
+//     110-112 the same through the phase-clock build, which prints its table
+//   sd_op_qkv_ln `kernel`: 0 the library's plan, 1 the tiled kernels, 2 plan tile 10 (wsgemm.hip), 3 plan tile 11 (bvgemm.hip:
+//     its own choice), 4 + v its variant v + 1
+//   sd_op_ffn_out_proj `fused`: 0 two 1x1 GEMMs, 1 one launch (xattn_out.hip ffn_proj), 2-5 the merged tail (wfold.hip, then ONE
+//     two-source GEMM): 2 the library's plan, 3 igemm_kernel's 64x64 tile, 4 / 5 smgemm.hip's 32- / 64-row tiles
+//   sd_op_attention `variant`: 0 default dispatch, 1 never the software-pipelined d = 64 kernel (attention8.hip), 2 that kernel with
+//     pre-scaled q, 100 + u its balanced form with u units per workgroup (0: the launch's own split)
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstring>
+#include <initializer_list>
+
+#include "capi_util.h"
+#include "weight_prep.h"
+
+namespace sd {
+namespace {
+
+const half_t* f16(const void* p) { return reinterpret_cast<const half_t*>(p); }
+
+// (B, C, H, W) f16 on the host -> [B][H][W][C] on the device
+half_t* upload_nhwc(Scratch& sc, const void* x, int B, int C, int H, int W) {
+  const half_t* src = f16(x);
+  std::vector<half_t> t((size_t)B * C * H * W);
+  for (int b = 0; b < B; ++b)
+    for (int c = 0; c < C; ++c)
+      for (int p = 0; p < H * W; ++p) t[((size_t)b * H * W + p) * C + c] = src[((size_t)b * C + c) * H * W + p];
+  return sc.dev<half_t>(t.size(), t.data());
+}
+// BC1S (B, C, 1, S) -> token-major [B * S][C]: NCHW with H = 1, W = S
+half_t* upload_tokens(Scratch& sc, const void* x, int B, int C, int S) { return upload_nhwc(sc, x, B, C, 1, S); }
+
+// (B, C, 1, Sk) -> V^T [B][C][ldv], rows zero-padded; perm: the middle 4-key blocks of every 16 keys swapped (AttnDesc::vt_perm)
+half_t* upload_vt(Scratch& sc, const void* v, int B, int C, int Sk, int ldv, bool perm) {
+  const half_t* src = f16(v);
+  std::vector<half_t> t((size_t)B * C * ldv, (half_t)0);
+  for (size_t r = 0; r < (size_t)B * C; ++r)
+    for (int s = 0; s < Sk; ++s) {
+      const int o = s & 15;
+      t[r * ldv + (perm && o >= 4 && o < 12 ? s + (o < 8 ? 4 : -4) : s)] = src[r * Sk + s];
+    }
+  return sc.dev<half_t>(t.size(), t.data());
+}
+
+// device [B][H][W][C] -> (B, C, H, W) f16 host buffer
+void download_nchw(const half_t* dev, void* out, int B, int C, int H, int W) {
+  std::vector<half_t> t((size_t)B * C * H * W);
+  SD_HIP(hipMemcpy(t.data(), dev, t.size() * 2, hipMemcpyDeviceToHost));
+  half_t* dst = reinterpret_cast<half_t*>(out);
+  for (int b = 0; b < B; ++b)
+    for (int c = 0; c < C; ++c)
+      for (int p = 0; p < H * W; ++p) dst[((size_t)b * C + c) * H * W + p] = t[((size_t)b * H * W + p) * C + c];
+}
+void download_tokens(const half_t* dev, void* out, int B, int C, int S) { download_nchw(dev, out, B, C, 1, S); }
+
+// [Cout][Cin][k][k] f16 -> [Cout][k][k][Cin] on the device
+half_t* upload_conv_weight(Scratch& sc, const void* w, int cout, int cin, int k) {
+  std::vector<half_t> t((size_t)cout * cin * k * k);
+  retile_ohwi(f16(w), cout, cin, k, false, t.data());
+  return sc.dev<half_t>(t.size(), t.data());
+}
+
+// a projection [cout][cin] f16 with the LayerNorm in front of it folded in (gamma == beta == NULL: none to fold)
+struct FoldedProj {
+  half_t* w;
+  float *bias, *colsum;
+};
+FoldedProj upload_ln_folded(Scratch& sc, const void* w, const float* bias, const float* gamma, const float* beta, int cout, int cin,
+                            bool geglu) {
+  std::vector<half_t> wf((size_t)cout * cin);
+  std::vector<float> bf(cout), cs(cout);
+  fold_layernorm_rows(f16(w), bias, gamma, beta, cout, cin, 0, geglu, wf.data(), cs.data(), bf.data());
+  return {sc.dev<half_t>(wf.size(), wf.data()), sc.dev<float>(cout, bf.data()), sc.dev<float>(cout, cs.data())};
+}
+
+// GroupNorm partial buffer, poisoned: a consumer must only read what the producer wrote
+float* poisoned_gn_partial(Scratch& sc, int B, int HW, int groups) {
+  std::vector<float> poison(groupnorm_scratch_floats(B, HW, groups), 1.0e30f);
+  return sc.dev<float>(poison.size(), poison.data());
+}
+
+// split-K workspace large enough for every one of these launches
+ConvWorkspace workspace_for(Scratch& sc, std::initializer_list<ConvDesc> descs) {
+  ConvWorkspace ws;
+  for (const ConvDesc& d : descs) ws.partial_bytes = std::max(ws.partial_bytes, conv_workspace_bytes(d));
+  if (ws.partial_bytes) ws.partial = reinterpret_cast<float*>(sc.dev<char>(ws.partial_bytes));
+  return ws;
+}
+
+// stride-1 conv that keeps the image size (ksize 1: a GEMM over the pixels)
+ConvDesc conv_desc(const half_t* in, int cin, const half_t* w, const float* bias, const half_t* res, half_t* out, int B, int H, int W,
+                   int N, int ksize = 1) {
+  ConvDesc d;
+  d.x0 = in; d.C0 = cin; d.w = w; d.bias = bias; d.res = res; d.out = out;
+  d.B = B; d.Hi = H; d.Wi = W; d.Ho = H; d.Wo = W;
+  d.ksize = ksize; d.N = N;
+  return d;
+}
+// 1x1 GEMM over [B][1][S] tokens
+ConvDesc token_gemm(const half_t* in, int cin, const half_t* w, const float* bias, const half_t* res, half_t* out, int B, int S, int N) {
+  return conv_desc(in, cin, w, bias, res, out, B, 1, S, N);
+}
+
+// conv `tile` code -> plan tile + staging (table at the top); gemm_codes: the 1x1-GEMM ranges sd_op_conv2d alone accepts
+void apply_tile_code(ConvDesc& d, int code, bool gemm_codes = false) {
+  d.tile = code % 10;
+  d.staging = code / 10;
+  if (gemm_codes && code >= 110 && code <= 116) d.tile = 11, d.staging = code - 110;
+  if (gemm_codes && code >= 140 && code <= 142) d.tile = 12, d.staging = code - 140;
+}
+
+// the pre-tiled weight copies a forced plan reads: tile 9 w_tiled (wstream.hip), tile 10 w_ws (wsgemm.hip), tile 11 w_bv (bvgemm.hip)
+void tile_for_wstream(Scratch& sc, ConvDesc& d, const char* refusal) {
+  SD_REQUIRE(wstream_shape_ok(d), kInvalidArgument, "%s", refusal);
+  half_t* wtd = sc.dev<half_t>(wstream_tiled_halves(d.N, d.C0, d.ksize));
+  launch_wstream_retile(d.w, wtd, d.N, d.C0, d.ksize, sc.stream);
+  d.w_tiled = wtd;
+}
+void tile_for_wsgemm(Scratch& sc, ConvDesc& d) {
+  half_t* wtd = sc.dev<half_t>(wsgemm_tiled_halves(d.N));
+  launch_wsgemm_retile(d.w, wtd, d.N, d.out_mode == kOutGeglu, sc.stream);
+  d.w_ws = wtd;
+}
+void tile_for_bvgemm(Scratch& sc, ConvDesc& d, const char* refusal) {
+  SD_REQUIRE(bvgemm_shape_ok(d), kInvalidArgument, "%s", refusal);
+  half_t* wtd = sc.dev<half_t>(bvgemm_tiled_halves(d.N, d.C0));
+  launch_bvgemm_retile(d.w, wtd, d.N, d.C0, d.out_mode == kOutGeglu, sc.stream);
+  d.w_bv = wtd;
+}
+
+// The producer of the conv2d_groupnorm* entries: a k x k stride-1 conv (+ bias, + residual) that writes its output to a fresh
+// buffer (d.out) under the tile code's plan, without split-K
+ConvDesc producer_conv(Scratch& sc, const void* x, const void* w, const float* bias, const void* res, int B, int Cin, int H, int W,
+                       int Cout, int ksize, int tile) {
+  ConvDesc d = conv_desc(upload_nhwc(sc, x, B, Cin, H, W), Cin, upload_conv_weight(sc, w, Cout, Cin, ksize),
+                         bias ? sc.dev<float>(Cout, bias) : nullptr, res ? upload_nhwc(sc, res, B, Cout, H, W) : nullptr,
+                         sc.dev<half_t>((size_t)B * H * W * Cout), B, H, W, Cout, ksize);
+  apply_tile_code(d, tile);
+  d.splitk = 1;
+  return d;
+}
+
+// the consumer of a folded GroupNorm reads the producer's raw output and its statistics entries
+void fold_groupnorm(ConvDesc& d, const half_t* x, const float* partial, const float* gamma, const float* beta, float eps, int groups,
+                    int entries) {
+  d.x0 = x;
+  d.gnf_partial = partial;
+  d.gnf_gamma = gamma;
+  d.gnf_beta = beta;
+  d.gnf_eps = eps;
+  d.gnf_groups = groups;
+  d.gnf_entries = entries;
+}
+
+// LayerNorm-folded q|k|v GEMM: columns [0, 2C) to qk (queries scaled by q_scale), the V columns token-transposed to vt [B][C][HW]
+ConvDesc qkv_desc(const half_t* in, const FoldedProj& f, float ln_eps, half_t* qk, half_t* vt, int B, int H, int W, int C, float q_scale,
+                  int vt_perm) {
+  ConvDesc d = conv_desc(in, C, f.w, f.bias, nullptr, qk, B, H, W, 3 * C);
+  d.ln_colsum = f.colsum;
+  d.ln_eps = ln_eps;
+  d.out_t = vt;
+  d.n_trans = 2 * C;
+  d.ldT = H * W;
+  d.vt_perm = vt_perm ? 1 : 0;
+  d.q_scale = q_scale;
+  d.q_cols = C;
+  return d;
+}
+
+}  // namespace
+}  // namespace sd
+
+using namespace sd;
+
+extern "C" {
+
+int sd_op_attention(int impl, const void* q, const void* k, const void* v, void* out, int B, int heads, int d,
+                    int Sq, int Sk, int variant, int iters, float* ms) {
+  return guarded([&] {
+    SD_REQUIRE(q && k && v && out, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(impl >= 0 && impl <= 2, kInvalidArgument, "unknown attention implementation %d", impl);
+    SD_REQUIRE(B > 0 && heads > 0 && d > 0 && Sq > 0 && Sk > 0, kInvalidArgument, "empty attention problem");
+    Scratch sc;
+    const int C = heads * d;
+    const int ldv = (Sk + 7) / 8 * 8;
+    // the software-pipelined d = 64 kernel reads V^T in its own key order (AttnDesc::vt_perm)
+    const bool perm = variant != 1 && attention8_shape_ok(d, Sq, Sk);
+    AttnDesc a;
+    a.q = upload_tokens(sc, q, B, C, Sq);
+    a.k = upload_tokens(sc, k, B, C, Sk);
+    a.vt = upload_vt(sc, v, B, C, Sk, ldv, perm);
+    half_t* o = sc.dev<half_t>((size_t)B * Sq * C);
+    a.out = o;
+    a.B = B; a.heads = heads; a.d = d; a.Sq = Sq; a.Sk = Sk;
+    a.ldq = C; a.ldk = C; a.ldv = ldv; a.ldo = C;
+    a.impl = impl;
+    a.variant = variant;
+    a.vt_perm = perm ? 1 : 0;
+    if (variant == 2) {   // the caller multiplied d^-0.5 * log2(e) into q before rounding it to fp16 (what the UNet's q|k|v GEMM does)
+      SD_REQUIRE(perm, kInvalidArgument, "attention variant 2 (pre-scaled q) needs attention8's shape (d %d Sq %d Sk %d)", d, Sq, Sk);
+      a.q_prescaled = 1;
+    }
+    if (variant >= 100) {   // attention8's balanced form, variant - 100 units per workgroup (0: the launch's own split)
+      SD_REQUIRE(perm, kInvalidArgument, "attention variant %d (balanced form) needs attention8's shape (d %d Sq %d Sk %d)", variant, d, Sq, Sk);
+      a.variant = 0;
+      a.sk_force = 1;
+      a.sk_upw = variant - 100;
+    }
+    {
+      size_t pb = 0;
+      int nc = 0;
+      if (perm && attention8_sk_scratch(a, &pb, &nc)) {
+        a.sk_part = reinterpret_cast<float*>(sc.dev<char>(pb));
+        a.sk_part_bytes = pb;
+        a.sk_cnt = sc.dev<unsigned>(nc);
+        a.sk_cnt_n = nc;
+        SD_HIP(hipMemset(a.sk_cnt, 0, (size_t)nc * sizeof(unsigned)));
+      } else {
+        SD_REQUIRE(variant < 100, kInvalidArgument, "attention variant %d: the balanced form cannot run this shape", variant);
+      }
+    }
+    sc.timed(iters, ms, [&] { launch_attention(a, sc.stream); });
+    download_tokens(o, out, B, C, Sq);
+  });
+}
+
+int sd_op_layernorm(const void* x, const float* weight, const float* bias, void* out, int B, int C, int S, float eps,
+                    int iters, float* ms) {
+  return guarded([&] {
+    SD_REQUIRE(x && weight && bias && out, kInvalidArgument, "NULL argument");
+    Scratch sc;
+    half_t* dx = upload_tokens(sc, x, B, C, S);
+    half_t* dy = sc.dev<half_t>((size_t)B * S * C);
+    float* dw = sc.dev<float>(C, weight);
+    float* db = sc.dev<float>(C, bias);
+    sc.timed(iters, ms, [&] { launch_layernorm(dx, dw, db, dy, B * S, C, eps, sc.stream); });
+    download_tokens(dy, out, B, C, S);
+  });
+}
+
+int sd_op_groupnorm(const void* x, const float* weight, const float* bias, void* out, int B, int C, int H, int W,
+                    int groups, float eps, int silu, int iters, float* ms) {
+  return guarded([&] {
+    SD_REQUIRE(x && weight && bias && out, kInvalidArgument, "NULL argument");
+    Scratch sc;
+    half_t* dx = upload_nhwc(sc, x, B, C, H, W);
+    half_t* dy = sc.dev<half_t>((size_t)B * H * W * C);
+    float* dw = sc.dev<float>(C, weight);
+    float* db = sc.dev<float>(C, bias);
+    float* partial = sc.dev<float>(groupnorm_scratch_floats(B, H * W, groups));
+    sc.timed(iters, ms, [&] {
+      launch_groupnorm(dx, C, nullptr, 0, partial, dw, db, dy, B, H * W, groups, eps, silu, sc.stream);
+    });
+    download_nchw(dy, out, B, C, H, W);
+  });
+}
+
+int sd_op_groupnorm_shortcut(const void* x0, const void* x1, const float* gn_weight, const float* gn_bias, const void* w, const float* bias,
+                             void* out_gn, void* out_sc, int B, int C0, int C1, int H, int W, int N, int groups, float eps, int silu,
+                             int side, int iters, float* ms) {
+  return guarded([&] {
+    SD_REQUIRE(x0 && gn_weight && gn_bias && w && out_gn && out_sc, kInvalidArgument, "NULL argument");
+    if (!x1) C1 = 0;
+    const int C = C0 + C1;
+    Scratch sc;
+    half_t* d0 = upload_nhwc(sc, x0, B, C0, H, W);
+    half_t* d1 = x1 ? upload_nhwc(sc, x1, B, C1, H, W) : nullptr;
+    half_t* dy = sc.dev<half_t>((size_t)B * H * W * C);
+    half_t* ds = sc.dev<half_t>((size_t)B * H * W * N);
+    float* dgw = sc.dev<float>(C, gn_weight);
+    float* dgb = sc.dev<float>(C, gn_bias);
+    float* partial = sc.dev<float>(groupnorm_scratch_floats(B, H * W, groups));
+    // conv_shortcut: a 1x1 conv over the channel concat (x0 | x1), weights [N][C] as they are
+    ConvDesc d = conv_desc(d0, C0, sc.dev<half_t>((size_t)N * C, f16(w)), bias ? sc.dev<float>(N, bias) : nullptr, nullptr, ds, B, H, W, N);
+    d.x1 = d1;
+    d.C1 = C1;
+    SD_REQUIRE(conv_fast_path_ok(d), kInvalidArgument, "groupnorm_shortcut: C0=%d C1=%d N=%d not MFMA-tileable", C0, C1, N);
+    SD_REQUIRE(!side || gn_side_gemm_ok(d), kUnsupported, "groupnorm_shortcut: the GEMM cannot ride in the GroupNorm launch (M=%d)", B * H * W);
+    ConvWorkspace ws = workspace_for(sc, {d});
+    sc.timed(iters, ms, [&] {
+      if (side) {
+        launch_groupnorm(d0, C0, d1, C1, partial, dgw, dgb, dy, B, H * W, groups, eps, silu, sc.stream, 0, &d);
+      } else {
+        launch_groupnorm(d0, C0, d1, C1, partial, dgw, dgb, dy, B, H * W, groups, eps, silu, sc.stream);
+        launch_conv(d, ws, sc.stream);
+      }
+    });
+    download_nchw(dy, out_gn, B, C, H, W);
+    download_nchw(ds, out_sc, B, N, H, W);
+  });
+}
+
+int sd_op_conv2d(const void* x, const void* w, const float* bias, const void* res, void* out, int B, int Cin, int H,
+                 int W, int Cout, int ksize, int stride, int upsample, int tile, int splitk, int force_generic,
+                 int iters, float* ms) {
+  return guarded([&] {
+    SD_REQUIRE(x && w && out, kInvalidArgument, "NULL argument");
+    SD_REQUIRE((ksize == 1 || ksize == 3) && (stride == 1 || stride == 2) && (upsample == 0 || upsample == 1),
+               kInvalidArgument, "conv2d: ksize %d stride %d upsample %d not on the path", ksize, stride, upsample);
+    Scratch sc;
+    const int up = upsample ? 2 : 1, pad = ksize / 2;
+    const int Ho = (H * up + 2 * pad - ksize) / stride + 1, Wo = (W * up + 2 * pad - ksize) / stride + 1;
+    ConvDesc d;
+    d.x0 = upload_nhwc(sc, x, B, Cin, H, W);
+    d.C0 = Cin;
+    d.w = upload_conv_weight(sc, w, Cout, Cin, ksize);
+    d.bias = bias ? sc.dev<float>(Cout, bias) : nullptr;
+    if (res) d.res = upload_nhwc(sc, res, B, Cout, Ho, Wo);
+    half_t* dout = sc.dev<half_t>((size_t)B * Ho * Wo * Cout);
+    d.out = dout;
+    d.B = B; d.Hi = H; d.Wi = W; d.Ho = Ho; d.Wo = Wo;
+    d.ksize = ksize; d.stride = stride; d.up = up; d.N = Cout;
+    apply_tile_code(d, tile, true);
+    d.splitk = splitk;
+    d.debug = force_generic >= 2 ? force_generic - 1 : 0;   // 2: loads only, 3: compute only (ablation)
+    if (d.debug & 4) d.prof = sc.dev<long long>(8);
+    const bool fast = force_generic != 1 && conv_fast_path_ok(d);
+    ConvWorkspace ws;
+    if (fast && d.tile == 9) tile_for_wstream(sc, d, "conv2d: shape not eligible for plan tile 9 (wstream.hip)");
+    if (fast && d.tile == 11) tile_for_bvgemm(sc, d, "conv2d: shape not eligible for plan tile 11 (bvgemm.hip)");
+    if (fast && d.tile != 11 && d.tile != 12) ws = workspace_for(sc, {d});
+    // N <= 8 (conv_out of the UNet / the VAE): the small-N kernels the handles use, unless the direct kernel was asked for
+    const bool small_n = !fast && force_generic == 0 && Cout <= 8 && Cin % 8 == 0 && ksize == 3 && stride == 1 && !res;
+    sc.timed(iters, ms, [&] {
+      if (fast)
+        launch_conv(d, ws, sc.stream);
+      else if (small_n)
+        launch_conv_small_n(d, nullptr, sc.stream);
+      else
+        launch_conv_generic(d, 0, sc.stream);
+    });
+    if (d.prof) {
+      long long t[8];
+      SD_HIP(hipMemcpy(t, d.prof, sizeof(t), hipMemcpyDeviceToHost));
+      fprintf(stderr, "[sd prof] block0: prologue %lld, k-loop %lld, epilogue %lld shader cycles; total %lld cycles = %lld ticks of the 100 MHz wall clock\n",
+              t[1] - t[0], t[2] - t[1], t[3] - t[2], t[3] - t[0], t[4]);
+    }
+    download_nchw(dout, out, B, Cout, Ho, Wo);
+  });
+}
+
+int sd_op_conv2d_groupnorm(const void* x, const void* w, const float* bias, const void* res, const float* gn_weight,
+                           const float* gn_bias, void* conv_out, void* out, int B, int Cin, int H, int W, int Cout, int ksize,
+                           int groups, float eps, int silu, int tile, int producer_stats, int* entries, int iters, float* ms) {
+  return guarded([&] {
+    SD_REQUIRE(x && w && gn_weight && gn_bias && out, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(ksize == 1 || ksize == 3, kInvalidArgument, "conv2d_groupnorm: ksize %d", ksize);
+    Scratch sc;
+    ConvDesc d = producer_conv(sc, x, w, bias, res, B, Cin, H, W, Cout, ksize, tile);
+    half_t* dconv = d.out;
+    half_t* dy = sc.dev<half_t>((size_t)B * H * W * Cout);
+    const bool fast = conv_fast_path_ok(d);   // else: conv_in's 4-channel MFMA kernel / the direct kernels
+    float* partial = poisoned_gn_partial(sc, B, H * W, groups);
+    if (producer_stats == 1) {
+      d.gn_partial = partial;
+      d.gn_groups = groups;
+    }
+    float* dgw = sc.dev<float>(Cout, gn_weight);
+    float* dgb = sc.dev<float>(Cout, gn_bias);
+    if (fast && d.tile == 9) tile_for_wstream(sc, d, "conv2d_groupnorm: shape not eligible for plan tile 9");
+    if (producer_stats == 2) {   // the GroupNorm as a twin of the conv's slab combine: no GroupNorm launch
+      SD_REQUIRE(fast, kInvalidArgument, "conv2d_groupnorm: GroupNorm twins need the MFMA path");
+      d.n_twins = 1;
+      d.twin[0].y = dy;
+      d.twin[0].ld = Cout;
+      d.twin[0].c_off = 0;
+      d.twin[0].cpg = Cout / groups;
+      d.twin[0].gamma = dgw;
+      d.twin[0].beta = dgb;
+      d.twin[0].eps = eps;
+      d.twin[0].silu = silu;
+      SD_REQUIRE(Cout % groups == 0 && reduce_twin_ok(H * W, Cout, 1, d.twin), kInvalidArgument,
+                 "conv2d_groupnorm: shape not eligible for a GroupNorm twin (HW=%d C=%d groups=%d)", H * W, Cout, groups);
+    }
+    ConvWorkspace ws;
+    if (fast) ws = workspace_for(sc, {d});
+    int n_entries = 0;
+    sc.timed(iters, ms, [&] {
+      n_entries = fast ? launch_conv(d, ws, sc.stream) : launch_conv_generic(d, 0, sc.stream);
+      if (producer_stats != 2)
+        launch_groupnorm(dconv, Cout, nullptr, 0, partial, dgw, dgb, dy, B, H * W, groups, eps, silu, sc.stream, n_entries);
+    });
+    if (entries) *entries = n_entries;
+    if (conv_out) download_nchw(dconv, conv_out, B, Cout, H, W);
+    download_nchw(dy, out, B, Cout, H, W);
+  });
+}
+
+int sd_op_conv2d_groupnorm_proj(const void* x, const void* w, const float* bias, const void* res, const float* gn_weight,
+                                const float* gn_bias, const void* proj_w, const float* proj_bias, void* conv_out, void* out, int B,
+                                int Cin, int H, int W, int Cout, int ksize, int Nproj, int groups, float eps, int fold, int tile,
+                                int* entries, int iters, float* ms) {
+  return guarded([&] {
+    SD_REQUIRE(x && w && gn_weight && gn_bias && proj_w && out, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(ksize == 1 || ksize == 3, kInvalidArgument, "conv2d_groupnorm_proj: ksize %d", ksize);
+    Scratch sc;
+    ConvDesc d = producer_conv(sc, x, w, bias, res, B, Cin, H, W, Cout, ksize, tile);
+    half_t* dconv = d.out;
+    half_t* dnorm = sc.dev<half_t>((size_t)B * H * W * Cout);
+    half_t* dy = sc.dev<half_t>((size_t)B * H * W * Nproj);
+    SD_REQUIRE(conv_fast_path_ok(d), kInvalidArgument, "conv2d_groupnorm_proj: the producer must run on the MFMA path");
+    float* partial = poisoned_gn_partial(sc, B, H * W, groups);
+    d.gn_partial = partial;
+    d.gn_groups = groups;
+    float* dgw = sc.dev<float>(Cout, gn_weight);
+    float* dgb = sc.dev<float>(Cout, gn_bias);
+    // the 1x1 projection over the conv's output
+    ConvDesc pd = conv_desc(nullptr, Cout, sc.dev<half_t>((size_t)Nproj * Cout, f16(proj_w)), proj_bias ? sc.dev<float>(Nproj, proj_bias) : nullptr,
+                            nullptr, dy, B, H, W, Nproj);
+    SD_REQUIRE(conv_fast_path_ok(pd), kInvalidArgument, "conv2d_groupnorm_proj: the projection must run on the MFMA path");
+    ConvWorkspace ws = workspace_for(sc, {d, pd});
+    int n_entries = 0;
+    sc.timed(iters, ms, [&] {
+      n_entries = launch_conv(d, ws, sc.stream);
+      ConvDesc pp = pd;
+      if (fold && n_entries >= 1 && n_entries <= 128) {
+        fold_groupnorm(pp, dconv, partial, dgw, dgb, eps, groups, n_entries);
+      } else {
+        launch_groupnorm(dconv, Cout, nullptr, 0, partial, dgw, dgb, dnorm, B, H * W, groups, eps, 0, sc.stream, n_entries);
+        pp.x0 = dnorm;
+      }
+      launch_conv(pp, ws, sc.stream);
+    });
+    if (entries) *entries = (fold && n_entries >= 1 && n_entries <= 128) ? n_entries : 0;
+    if (conv_out) download_nchw(dconv, conv_out, B, Cout, H, W);
+    download_nchw(dy, out, B, Nproj, H, W);
+  });
+}
+
+int sd_op_conv2d_groupnorm_conv3x3(const void* x, const void* w, const float* bias, const void* res, const float* gn_weight,
+                                   const float* gn_bias, const void* w2, const float* bias2, const void* res2, void* conv_out, void* out,
+                                   int B, int Cin, int H, int W, int Cout, int ksize, int N2, int groups, float eps, int silu, int fold,
+                                   int tile, int staging2, int* entries, int iters, float* ms) {
+  return guarded([&] {
+    SD_REQUIRE(x && w && gn_weight && gn_bias && w2 && out, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(ksize == 1 || ksize == 3, kInvalidArgument, "conv2d_groupnorm_conv3x3: ksize %d", ksize);
+    Scratch sc;
+    ConvDesc d = producer_conv(sc, x, w, bias, res, B, Cin, H, W, Cout, ksize, tile);
+    half_t* dconv = d.out;
+    half_t* dnorm = sc.dev<half_t>((size_t)B * H * W * Cout);
+    half_t* dy = sc.dev<half_t>((size_t)B * H * W * N2);
+    SD_REQUIRE(conv_fast_path_ok(d), kInvalidArgument, "conv2d_groupnorm_conv3x3: the producer must run on the MFMA path");
+    float* partial = poisoned_gn_partial(sc, B, H * W, groups);
+    d.gn_partial = partial;
+    d.gn_groups = groups;
+    float* dgw = sc.dev<float>(Cout, gn_weight);
+    float* dgb = sc.dev<float>(Cout, gn_bias);
+    // the 3x3 conv over the normalised tensor
+    ConvDesc cd = conv_desc(nullptr, Cout, upload_conv_weight(sc, w2, N2, Cout, 3), bias2 ? sc.dev<float>(N2, bias2) : nullptr,
+                            res2 ? upload_nhwc(sc, res2, B, N2, H, W) : nullptr, dy, B, H, W, N2, 3);
+    cd.staging = staging2;
+    cd.gnf_groups = groups;
+    SD_REQUIRE(conv_fast_path_ok(cd), kInvalidArgument, "conv2d_groupnorm_conv3x3: the second conv must run on the MFMA path");
+    const bool can_fold = fold && silu && conv_gn_loader_ok(cd);   // (the loader always applies SiLU: every such GroupNorm of the graph has one)
+    SD_REQUIRE(!fold || can_fold, kUnsupported, "conv2d_groupnorm_conv3x3: the halo loader cannot normalise C=%d groups=%d @%dx%d", Cout, groups, H, W);
+    cd.gnf_groups = 0;
+    ConvWorkspace ws = workspace_for(sc, {d, cd});
+    int n_entries = 0;
+    sc.timed(iters, ms, [&] {
+      n_entries = launch_conv(d, ws, sc.stream);
+      ConvDesc cc = cd;
+      if (fold && n_entries >= 1 && n_entries <= 128) {
+        fold_groupnorm(cc, dconv, partial, dgw, dgb, eps, groups, n_entries);
+        cc.gnf_silu = silu ? 1 : 0;
+      } else {
+        launch_groupnorm(dconv, Cout, nullptr, 0, partial, dgw, dgb, dnorm, B, H * W, groups, eps, silu ? 1 : 0, sc.stream, n_entries);
+        cc.x0 = dnorm;
+      }
+      launch_conv(cc, ws, sc.stream);
+    });
+    if (entries) *entries = (fold && n_entries >= 1 && n_entries <= 128) ? n_entries : 0;
+    if (conv_out) download_nchw(dconv, conv_out, B, Cout, H, W);
+    download_nchw(dy, out, B, N2, H, W);
+  });
+}
+
+int sd_op_cross_attention_fused(const void* x, const float* ln_weight, const float* ln_bias, const void* wq, const void* k,
+                                const void* v, void* out, int B, int heads, int Sq, int Sk, float eps, int nst, int iters,
+                                float* ms) {
+  return guarded([&] {
+    SD_REQUIRE(x && ln_weight && ln_bias && wq && k && v && out, kInvalidArgument, "NULL argument");
+    const int C = heads * 64;
+    SD_REQUIRE(B > 0 && heads > 0 && xattn_fused_ok(C, heads, Sq, Sk), kUnsupported,
+               "cross_attention_fused: heads %d x 64 channels, Sq %d, Sk %d (<= 96)", heads, Sq, Sk);
+    Scratch sc;
+    const int ldv = (Sk + 7) / 8 * 8;
+    const FoldedProj fq = upload_ln_folded(sc, wq, nullptr, ln_weight, ln_bias, C, C, false);
+    XAttnDesc d;
+    d.x = upload_tokens(sc, x, B, C, Sq);
+    d.wq = fq.w;
+    d.bias = fq.bias;
+    d.colsum = fq.colsum;
+    d.k = upload_tokens(sc, k, B, C, Sk);
+    d.vt = upload_vt(sc, v, B, C, Sk, ldv, false);
+    half_t* o = sc.dev<half_t>((size_t)B * Sq * C);
+    d.out = o;
+    d.M = B * Sq; d.C = C; d.S = Sq; d.L = Sk; d.ldv = ldv; d.heads = heads;
+    d.ln_eps = eps;
+    d.nst = nst;
+    sc.timed(iters, ms, [&] { launch_xattn_fused(d, sc.stream); });
+    download_tokens(o, out, B, C, Sq);
+  });
+}
+
+int sd_op_cross_attention_block(const void* x, const float* ln_weight, const float* ln_bias, const void* wq, const void* k, const void* v,
+                                const void* wo, const float* bo, const void* a1, const void* wo1, const float* bo1, void* out, int B, int heads,
+                                int Sq, int Sk, float eps, int fused, int iters, float* ms) {
+  return guarded([&] {
+    SD_REQUIRE(x && ln_weight && ln_bias && wq && k && v && wo && bo && out, kInvalidArgument, "NULL argument");
+    const bool pre = a1 != nullptr;
+    SD_REQUIRE(!pre || (wo1 && bo1), kInvalidArgument, "cross_attention_block: a1 needs wo1 and bo1");
+    const int C = heads * 64;
+    SD_REQUIRE(B > 0 && heads > 0 && xattn_fused_ok(C, heads, Sq, Sk), kUnsupported,
+               "cross_attention_block: heads %d x 64 channels, Sq %d, Sk %d (<= 96)", heads, Sq, Sk);
+    SD_REQUIRE(!fused || (xattn_out_ok(C, heads, Sq, Sk) && (!pre || heads == 5)), kUnsupported,
+               "cross_attention_block: the one-launch form takes 5 or 10 heads (with a1: 5) and Sq %% 32 == 0 (heads %d, Sq %d)", heads, Sq);
+    Scratch sc;
+    const int ldv = (Sk + 7) / 8 * 8;
+    half_t* dx = upload_tokens(sc, x, B, C, Sq);
+    half_t* da1 = pre ? upload_tokens(sc, a1, B, C, Sq) : nullptr;
+    const FoldedProj fq = upload_ln_folded(sc, wq, nullptr, ln_weight, ln_bias, C, C, false);
+    half_t* dk = upload_tokens(sc, k, B, C, Sk);
+    half_t* dvt = upload_vt(sc, v, B, C, Sk, ldv, false);
+    half_t* dwo = sc.dev<half_t>((size_t)C * C, f16(wo));
+    float* dbo = sc.dev<float>(C, bo);
+    half_t* dwo1 = pre ? sc.dev<half_t>((size_t)C * C, f16(wo1)) : nullptr;
+    float* dbo1 = pre ? sc.dev<float>(C, bo1) : nullptr;
+    half_t* dh1 = sc.dev<half_t>((size_t)B * Sq * C);
+    half_t* da2 = sc.dev<half_t>((size_t)B * Sq * C);
+    half_t* o = sc.dev<half_t>((size_t)B * Sq * C);
+    if (fused) {
+      half_t* wq_t = sc.dev<half_t>((size_t)C * C);
+      half_t* wo_t = sc.dev<half_t>((size_t)C * C);
+      launch_xattn_out_retile(fq.w, wq_t, C, sc.stream);
+      launch_xattn_out_retile(dwo, wo_t, C, sc.stream);
+      XAttnOutDesc d;
+      d.x = pre ? da1 : dx; d.wq_t = wq_t; d.q_bias = fq.bias; d.q_colsum = fq.colsum; d.k = dk; d.vt = dvt; d.wo_t = wo_t; d.o_bias = dbo; d.out = o;
+      d.M = B * Sq; d.C = C; d.S = Sq; d.L = Sk; d.ldv = ldv; d.heads = heads; d.ln_eps = eps;
+      if (pre) {
+        half_t* wo1_t = sc.dev<half_t>((size_t)C * C);
+        launch_xattn_out_retile(dwo1, wo1_t, C, sc.stream);
+        d.h0 = dx; d.wo1_t = wo1_t; d.o1_bias = dbo1;
+      }
+      sc.timed(iters, ms, [&] { launch_xattn_out(d, sc.stream); });
+    } else {
+      auto gemm_res = [&](const half_t* in, const half_t* w, const float* bias, const half_t* res, half_t* dst) {   // 1x1 GEMM + residual
+        ConvDesc cd = token_gemm(in, C, w, bias, res, dst, B, Sq, C);
+        SD_REQUIRE(conv_fast_path_ok(cd), kInvalidArgument, "cross_attention_block: to_out off the MFMA path");
+        return cd;
+      };
+      const half_t* h1 = pre ? dh1 : dx;
+      XAttnDesc d;
+      d.x = h1; d.wq = fq.w; d.bias = fq.bias; d.colsum = fq.colsum; d.k = dk; d.vt = dvt; d.out = da2;
+      d.M = B * Sq; d.C = C; d.S = Sq; d.L = Sk; d.ldv = ldv; d.heads = heads; d.ln_eps = eps;
+      ConvDesc c1 = gemm_res(da1 ? da1 : dx, dwo1 ? dwo1 : dwo, dbo1 ? dbo1 : dbo, dx, dh1);   // (only launched with a1)
+      ConvDesc c2 = gemm_res(da2, dwo, dbo, h1, o);
+      ConvWorkspace ws = workspace_for(sc, {c1, c2});
+      sc.timed(iters, ms, [&] {
+        if (pre) launch_conv(c1, ws, sc.stream);
+        launch_xattn_fused(d, sc.stream);
+        launch_conv(c2, ws, sc.stream);
+      });
+    }
+    download_tokens(o, out, B, C, Sq);
+  });
+}
+
+int sd_op_ffn_out_proj(const void* g, const void* w1, const float* b1, const void* res1, const void* w2, const float* b2, const void* res2,
+                       void* out, float* gn_sums, int B, int C, int S, int groups, int fused, int iters, float* ms) {
+  return guarded([&] {
+    SD_REQUIRE(g && w1 && b1 && res1 && w2 && b2 && res2 && out, kInvalidArgument, "NULL argument");
+    const int K1 = 4 * C, M = B * S;
+    SD_REQUIRE(B > 0 && C % 64 == 0 && S > 0, kInvalidArgument, "ffn_out_proj: B=%d C=%d S=%d", B, C, S);
+    SD_REQUIRE(fused >= 0 && fused <= 5, kInvalidArgument, "ffn_out_proj: fused code %d", fused);
+    SD_REQUIRE(fused != 1 || ffn_proj_ok(C, K1, M, S), kUnsupported, "ffn_out_proj: the one-launch form takes C = 320 and S %% 32 == 0 (C=%d S=%d)", C, S);
+    SD_REQUIRE(!gn_sums || (groups >= 1 && C % groups == 0), kInvalidArgument, "ffn_out_proj: groups %d", groups);
+    Scratch sc;
+    half_t* dg = upload_tokens(sc, g, B, K1, S);
+    half_t* dr1 = upload_tokens(sc, res1, B, C, S);
+    half_t* dr2 = upload_tokens(sc, res2, B, C, S);
+    half_t* dw1 = sc.dev<half_t>((size_t)C * K1, f16(w1));
+    half_t* dw2 = sc.dev<half_t>((size_t)C * C, f16(w2));
+    float* db1 = sc.dev<float>(C, b1);
+    float* db2 = sc.dev<float>(C, b2);
+    half_t* dh3 = sc.dev<half_t>((size_t)M * C);
+    half_t* o = sc.dev<half_t>((size_t)M * C);
+    const size_t pf = gn_sums ? groupnorm_scratch_floats(B, S, groups) : 0;
+    float* partial = gn_sums ? poisoned_gn_partial(sc, B, S, groups) : nullptr;   // only what the producer wrote may be folded
+    int n_entries = 0;
+    if (fused >= 2) {   // the merged tail: weight fold (once per handle, outside the timed region), then ONE two-source GEMM
+      half_t* wm = sc.dev<half_t>((size_t)C * (K1 + C));
+      float* bm = sc.dev<float>(C);
+      launch_wfold(dw2, db2, dw1, db1, wm, bm, C, C, K1, sc.stream);
+      ConvDesc cd = token_gemm(dg, K1, wm, bm, dr2, o, B, S, C);
+      cd.x1 = dr1;
+      cd.C1 = C;
+      cd.gn_partial = partial;
+      cd.gn_groups = groups;
+      SD_REQUIRE(conv_fast_path_ok(cd), kInvalidArgument, "ffn_out_proj: off the MFMA path");
+      if (fused == 3) cd.tile = 3;
+      if (fused >= 4) cd.tile = 12, cd.staging = fused - 3;
+      ConvWorkspace ws = workspace_for(sc, {cd});
+      sc.timed(iters, ms, [&] { n_entries = launch_conv(cd, ws, sc.stream); });
+    } else if (fused) {
+      half_t* w1_t = sc.dev<half_t>((size_t)C * K1);
+      half_t* w2_t = sc.dev<half_t>((size_t)C * C);
+      launch_xattn_out_retile_nk(dw1, w1_t, C, K1, sc.stream);
+      launch_xattn_out_retile_nk(dw2, w2_t, C, C, sc.stream);
+      FfnProjDesc d;
+      d.g = dg; d.w1_t = w1_t; d.b1 = db1; d.res1 = dr1; d.w2_t = w2_t; d.b2 = db2; d.res2 = dr2; d.out = o;
+      d.gn_partial = partial; d.gn_groups = groups; d.M = M; d.C = C; d.K1 = K1; d.S = S;
+      sc.timed(iters, ms, [&] { n_entries = launch_ffn_proj(d, sc.stream); });
+    } else {
+      ConvDesc c1 = token_gemm(dg, K1, dw1, db1, dr1, dh3, B, S, C);
+      ConvDesc c2 = token_gemm(dh3, C, dw2, db2, dr2, o, B, S, C);
+      SD_REQUIRE(conv_fast_path_ok(c1) && conv_fast_path_ok(c2), kInvalidArgument, "ffn_out_proj: off the MFMA path");
+      c2.gn_partial = partial;
+      c2.gn_groups = groups;
+      ConvWorkspace ws = workspace_for(sc, {c1, c2});
+      sc.timed(iters, ms, [&] {
+        launch_conv(c1, ws, sc.stream);
+        n_entries = launch_conv(c2, ws, sc.stream);
+      });
+    }
+    download_tokens(o, out, B, C, S);
+    if (gn_sums) {   // the producer's entries folded on the host: (sum, sumsq) per (sample, group); -1 entries: none written
+      std::vector<float> hp(pf);
+      SD_HIP(hipMemcpy(hp.data(), partial, pf * sizeof(float), hipMemcpyDeviceToHost));
+      for (int b = 0; b < B; ++b)
+        for (int gi = 0; gi < groups; ++gi) {
+          double s1 = 0.0, s2 = 0.0;
+          for (int e = 0; e < n_entries; ++e) {
+            s1 += hp[(((size_t)b * groups + gi) * kGnMaxSlabs + e) * 2];
+            s2 += hp[(((size_t)b * groups + gi) * kGnMaxSlabs + e) * 2 + 1];
+          }
+          gn_sums[((size_t)b * groups + gi) * 2] = n_entries ? (float)s1 : NAN;
+          gn_sums[((size_t)b * groups + gi) * 2 + 1] = n_entries ? (float)s2 : NAN;
+        }
+    }
+  });
+}
+
+int sd_op_fold_linear(const void* wp, const float* bp, const void* w2, const float* b2, void* wm_out, float* bm_out, int N, int J, int K) {
+  return guarded([&] {
+    SD_REQUIRE(wp && bp && w2 && b2 && wm_out && bm_out && N > 0 && J > 0 && K > 0, kInvalidArgument, "fold_linear: N=%d J=%d K=%d", N, J, K);
+    Scratch sc;
+    half_t* dwp = sc.dev<half_t>((size_t)N * J, f16(wp));
+    half_t* dw2 = sc.dev<half_t>((size_t)J * K, f16(w2));
+    float* dbp = sc.dev<float>(N, bp);
+    float* db2 = sc.dev<float>(J, b2);
+    half_t* merged = sc.dev<half_t>((size_t)N * (K + J));
+    float* bm = sc.dev<float>(N);
+    launch_wfold(dwp, dbp, dw2, db2, merged, bm, N, J, K, sc.stream);
+    SD_HIP(hipStreamSynchronize(sc.stream));
+    SD_HIP(hipMemcpy2D(wm_out, (size_t)K * 2, merged, (size_t)(K + J) * 2, (size_t)K * 2, N, hipMemcpyDeviceToHost));
+    SD_HIP(hipMemcpy(bm_out, bm, (size_t)N * sizeof(float), hipMemcpyDeviceToHost));
+    // the copied block behind the folded columns must be Wp itself
+    std::vector<half_t> tail((size_t)N * J);
+    SD_HIP(hipMemcpy2D(tail.data(), (size_t)J * 2, merged + K, (size_t)(K + J) * 2, (size_t)J * 2, N, hipMemcpyDeviceToHost));
+    SD_REQUIRE(std::memcmp(tail.data(), wp, tail.size() * 2) == 0, kInternal, "fold_linear: the Wp columns of the merged matrix differ from Wp");
+  });
+}
+
+int sd_op_geglu(const void* x, const void* w, const float* bias, void* out, int M, int C, int N2, int iters, float* ms) {
+  return guarded([&] {
+    SD_REQUIRE(x && w && out && N2 % 2 == 0, kInvalidArgument, "bad GEGLU arguments");
+    Scratch sc;
+    const int half_n = N2 / 2;
+    SD_REQUIRE(half_n % 32 == 0, kUnsupported, "GEGLU needs (N/2) %% 32 == 0");
+    std::vector<half_t> wt((size_t)N2 * C);
+    retile_ohwi(f16(w), N2, C, 1, true, wt.data());
+    std::vector<float> bt(N2, 0.f);
+    if (bias)
+      for (int o = 0; o < N2; ++o) bt[geglu_row(o, N2)] = bias[o];
+    half_t* dout = sc.dev<half_t>((size_t)M * half_n);
+    ConvDesc d = token_gemm(sc.dev<half_t>((size_t)M * C, f16(x)), C, sc.dev<half_t>(wt.size(), wt.data()),
+                            bias ? sc.dev<float>(N2, bt.data()) : nullptr, nullptr, dout, 1, M, N2);
+    d.out_mode = kOutGeglu;
+    const bool fast = conv_fast_path_ok(d);
+    ConvWorkspace ws;
+    sc.timed(iters, ms, [&] {
+      if (fast)
+        launch_conv(d, ws, sc.stream);
+      else
+        launch_conv_generic(d, 0, sc.stream);
+    });
+    SD_HIP(hipMemcpy(out, dout, (size_t)M * half_n * 2, hipMemcpyDeviceToHost));
+  });
+}
+
+// GEGLU projection with the LayerNorm in front of it folded in (unet.py:583-591 norm3 -> :609-617 ff.net.0.proj) by the rule the
+// UNet builder folds it with (fold_layernorm_rows): x (M, C) f16 un-normalised rows, ln_weight / ln_bias (C) f32 or both NULL (plain
+// GEGLU), w (N2, C) f16 [values | gates], bias (N2) f32 or NULL -> out (M, N2 / 2) f16.
+int sd_op_geglu_ln(const void* x, const float* ln_weight, const float* ln_bias, const void* w, const float* bias, void* out, int M, int C,
+                   int N2, float eps, int kernel, int iters, float* ms) {
+  return guarded([&] {
+    const bool smgeglu = kernel >= 100 && kernel <= 112 && kernel % 10 <= 2;   // 100-102, 110-112: plan tile 13 (smgeglu.hip)
+    const int sg_variant = smgeglu ? kernel % 10 : 0;                          // tile height by grid size / 128 rows / 256 rows
+    const bool sg_clock = smgeglu && kernel >= 110;
+    if (smgeglu) kernel = 0;
+    const int abl = kernel / 10;   // kernel = 2 + 10 * n: ablation build n of the weight-stationary kernel (measurement tools only)
+    kernel %= 10;
+    SD_REQUIRE(x && w && out && N2 % 64 == 0 && (ln_weight == nullptr) == (ln_bias == nullptr) && kernel >= 0 && kernel <= 9 &&
+                   (abl == 0 || kernel == 2), kInvalidArgument, "bad GEGLU arguments");
+    Scratch sc;
+    const int half_n = N2 / 2;
+    const FoldedProj f = upload_ln_folded(sc, w, bias, ln_weight, ln_bias, N2, C, true);
+    half_t* dout = sc.dev<half_t>((size_t)M * half_n);
+    ConvDesc d = token_gemm(sc.dev<half_t>((size_t)M * C, f16(x)), C, f.w, f.bias, nullptr, dout, 1, M, N2);
+    if (ln_weight) d.ln_colsum = f.colsum;
+    d.ln_eps = eps;
+    d.out_mode = kOutGeglu;
+    SD_REQUIRE(!smgeglu || smgeglu_shape_ok(d, sg_variant), kInvalidArgument,
+               "GEGLU shape not eligible for plan tile 13 (smgeglu.hip): M=%d C=%d N2=%d", M, C, N2);
+    SD_REQUIRE(conv_fast_path_ok(d), kUnsupported, "GEGLU shape off the MFMA path (C=%d N2=%d)", C, N2);
+    if (kernel != 1 && kernel < 3 && !smgeglu && wsgemm_shape_ok(d)) tile_for_wsgemm(sc, d);
+    if (kernel == 2) d.tile = 10;
+    size_t sg_prof = 0;
+    if (smgeglu) {
+      d.tile = 13;
+      d.staging = sg_variant;
+      if (sg_clock) {
+        sg_prof = smgeglu_prof_entries(d, d.staging);
+        d.prof = sc.dev<long long>(sg_prof);
+      }
+    } else if (kernel >= 3) {
+      tile_for_bvgemm(sc, d, "GEGLU shape not eligible for plan tile 11 (bvgemm.hip)");
+      d.w_ws = nullptr;
+      d.tile = 11;
+      d.staging = kernel - 3;
+    }
+    d.debug = abl;
+    if (abl == 5) d.prof = sc.dev<long long>(64);
+    ConvWorkspace ws;
+    sc.timed(iters, ms, [&] { launch_conv(d, ws, sc.stream); });
+    if (sg_prof) {   // every wave's stamps of the last launch: cycles from kernel entry to the end of each phase
+      std::vector<long long> t(sg_prof);
+      SD_HIP(hipMemcpy(t.data(), d.prof, sg_prof * sizeof(long long), hipMemcpyDeviceToHost));
+      static const char* const phase[5] = {"first ring stages + epilogue operands issued", "first stage landed (counted wait + barrier)",
+                                           "K loop done", "row statistics exchanged", "last store issued"};
+      const size_t waves = sg_prof / 8;
+      fprintf(stderr, "[sd prof] smgeglu M=%d K=%d N=%d kernel=%d: %zu waves, shader-clock cycles since the wave's kernel entry (min / mean / max)\n",
+              M, C, N2, 110 + sg_variant, waves);
+      for (int k = 1; k <= 5; ++k) {
+        long long lo = LLONG_MAX, hi = 0;
+        double sum = 0.0;
+        for (size_t wv = 0; wv < waves; ++wv) {
+          const long long dt = t[wv * 8 + k] - t[wv * 8];
+          lo = std::min(lo, dt);
+          hi = std::max(hi, dt);
+          sum += (double)dt;
+        }
+        fprintf(stderr, "[sd prof]   %-46s %8lld %10.0f %8lld\n", phase[k - 1], lo, sum / (double)waves, hi);
+      }
+    } else if (d.prof) {   // workgroup (0, 0), thread 0: shader-clock stamps of its first pipeline iterations
+      long long t[64];
+      SD_HIP(hipMemcpy(t, d.prof, sizeof(t), hipMemcpyDeviceToHost));
+      for (int i = 0; i < 6; ++i)
+        fprintf(stderr, "[sd prof] wsgemm iteration %d: barrier wait %lld, DMA issue + store %lld, statistics %lld, MFMA || epilogue %lld cycles\n",
+                i + 1, t[i * 8 + 1] - t[i * 8], t[i * 8 + 2] - t[i * 8 + 1], t[i * 8 + 3] - t[i * 8 + 2], t[i * 8 + 4] - t[i * 8 + 3]);
+    }
+    SD_HIP(hipMemcpy(out, dout, (size_t)M * half_n * 2, hipMemcpyDeviceToHost));
+  });
+}
+
+// Fused q|k|v projection of self-attention with norm1 folded in (unet.py:583-586 norm1 -> :74-84 to_q / to_k / to_v as ONE GEMM, as the
+// UNet graph runs it): x (B * HW, C) f16 un-normalised tokens, ln_weight / ln_bias (C) f32, w (3C, C) f16 = [Wq | Wk | Wv] (no bias)
+// -> out_qk (B * HW, 2C) f16 (the queries multiplied by q_scale on the fp32 accumulator), out_vt (B, C, HW) f16 = V^T, with
+// vt_perm in attention8's key order (AttnDesc::vt_perm).
+int sd_op_qkv_ln(const void* x, const float* ln_weight, const float* ln_bias, const void* w, void* out_qk, void* out_vt, int B, int HW, int C,
+                 float eps, float q_scale, int vt_perm, int kernel, int iters, float* ms) {
+  return guarded([&] {
+    SD_REQUIRE(x && ln_weight && ln_bias && w && out_qk && out_vt && B >= 1 && HW >= 1 && C % 64 == 0 && kernel >= 0 && kernel <= 9,
+               kInvalidArgument, "bad q|k|v arguments");
+    Scratch sc;
+    const int N = 3 * C, M = B * HW;
+    const FoldedProj f = upload_ln_folded(sc, w, nullptr, ln_weight, ln_bias, N, C, false);
+    half_t* dqk = sc.dev<half_t>((size_t)M * 2 * C);
+    half_t* dvt = sc.dev<half_t>((size_t)B * C * HW);
+    ConvDesc d = qkv_desc(sc.dev<half_t>((size_t)M * C, f16(x)), f, eps, dqk, dvt, B, 1, HW, C, q_scale, vt_perm);
+    SD_REQUIRE(conv_fast_path_ok(d), kUnsupported, "q|k|v shape off the MFMA path (C=%d)", C);
+    if (kernel == 2 || (kernel == 0 && wsgemm_wanted(d))) {   // the weight-stationary kernel (wsgemm.hip, plan tile 10)
+      SD_REQUIRE(wsgemm_shape_ok(d), kInvalidArgument, "q|k|v shape not eligible for plan tile 10 (wsgemm.hip)");
+      tile_for_wsgemm(sc, d);
+      if (kernel == 2) d.tile = 10;
+    } else if (kernel >= 3 || (kernel == 0 && bvgemm_wanted(d))) {
+      tile_for_bvgemm(sc, d, "q|k|v shape not eligible for plan tile 11 (bvgemm.hip)");
+      if (kernel >= 3) {
+        d.tile = 11;
+        d.staging = kernel - 3;
+      }
+    }
+    ConvWorkspace ws;
+    sc.timed(iters, ms, [&] { launch_conv(d, ws, sc.stream); });
+    SD_HIP(hipMemcpy(out_qk, dqk, (size_t)M * 2 * C * 2, hipMemcpyDeviceToHost));
+    SD_HIP(hipMemcpy(out_vt, dvt, (size_t)B * C * HW * 2, hipMemcpyDeviceToHost));
+  });
+}
+
+// The head of a SpatialTransformer (unet.py:553-556 norm -> proj_in, :583-586 norm1 -> :74-84 fused to_q | to_k | to_v) behind a 1x1 conv
+// that produces its input x = conv(x_in) and - like the resnet conv in front of it in the UNet - leaves the GroupNorm statistics of x in
+// its epilogue.  fused = 1: ONE launch (xattn_out.hip gn_proj_qkv_kernel; 2 / 3: its 64- / 32-token form); 0: GroupNorm launch, proj_in GEMM,
+// LayerNorm-folded q|k|v GEMM.
+// x_in (B, C, H, W) f16 NCHW; conv_w (C, C); gn_* (C) f32; proj_w (C, C), proj_bias (C); ln_* (C); wqkv (3C, C) -> out_h (B * HW, C),
+// out_qk (B * HW, 2C), out_vt (B, C, HW), all f16.  *entries = the producer's partial entries per (sample, group) the fused launch folded.
+int sd_op_gn_proj_qkv(const void* x_in, const void* conv_w, const float* gn_weight, const float* gn_bias, const void* proj_w,
+                      const float* proj_bias, const float* ln_weight, const float* ln_bias, const void* wqkv, void* out_h, void* out_qk,
+                      void* out_vt, int B, int H, int W, int C, int groups, float gn_eps, float ln_eps, float q_scale, int vt_perm, int fused,
+                      int* entries, int iters, float* ms) {
+  return guarded([&] {
+    SD_REQUIRE(x_in && conv_w && gn_weight && gn_bias && proj_w && proj_bias && ln_weight && ln_bias && wqkv && out_h && out_qk && out_vt,
+               kInvalidArgument, "NULL argument");
+    const int HW = H * W, M = B * HW, N = 3 * C;
+    SD_REQUIRE(gn_proj_qkv_ok(C, C / 64, HW, M, HW, groups), kInvalidArgument, "gn_proj_qkv: C=%d HW=%d groups=%d", C, HW, groups);
+    Scratch sc;
+    half_t* dx = sc.dev<half_t>((size_t)M * C);
+    // the producer
+    ConvDesc d = conv_desc(upload_nhwc(sc, x_in, B, C, H, W), C, sc.dev<half_t>((size_t)C * C, f16(conv_w)), nullptr, nullptr, dx, B, H, W, C);
+    d.splitk = 1;
+    float* partial = poisoned_gn_partial(sc, B, HW, groups);
+    d.gn_partial = partial;
+    d.gn_groups = groups;
+    float* dgw = sc.dev<float>(C, gn_weight);
+    float* dgb = sc.dev<float>(C, gn_bias);
+    const FoldedProj fq = upload_ln_folded(sc, wqkv, nullptr, ln_weight, ln_bias, N, C, false);   // LayerNorm fold of the fused q|k|v
+    half_t* dwp = sc.dev<half_t>((size_t)C * C, f16(proj_w));
+    float* dpb = sc.dev<float>(C, proj_bias);
+    half_t* dnorm = sc.dev<half_t>((size_t)M * C);
+    half_t* dh = sc.dev<half_t>((size_t)M * C);
+    half_t* dqk = sc.dev<half_t>((size_t)M * 2 * C);
+    half_t* dvt = sc.dev<half_t>((size_t)B * C * HW);
+    half_t* dwp_t = sc.dev<half_t>((size_t)C * C);
+    half_t* dwq_t = sc.dev<half_t>((size_t)N * C);
+    launch_xattn_out_retile_nk(dwp, dwp_t, C, C, sc.stream);
+    launch_xattn_out_retile_nk(fq.w, dwq_t, N, C, sc.stream);
+    ConvDesc pd = conv_desc(dnorm, C, dwp, dpb, nullptr, dh, B, H, W, C);                      // proj_in of the three-launch path
+    ConvDesc qd = qkv_desc(dh, fq, ln_eps, dqk, dvt, B, H, W, C, q_scale, vt_perm);            // fused q|k|v of the three-launch path
+    SD_REQUIRE(conv_fast_path_ok(d) && conv_fast_path_ok(pd) && conv_fast_path_ok(qd), kInvalidArgument, "gn_proj_qkv: off the MFMA path");
+    ConvWorkspace ws = workspace_for(sc, {d, pd, qd});
+    int n_entries = 0;
+    static const bool want_clk = tune_env_set("SD_GQ_CLOCK");   // phase clock of the one-launch kernel, printed to stderr
+    const size_t n_clk = (size_t)(M / 32) * 5 * 16;
+    long long* dclk = want_clk && fused ? sc.dev<long long>(n_clk) : nullptr;
+    sc.timed(iters, ms, [&] {
+      n_entries = launch_conv(d, ws, sc.stream);
+      const bool have = n_entries >= 1 && n_entries <= 128;
+      if (fused) {
+        GnProjQkvDesc g;
+        g.clk = dclk;
+        g.tok = fused == 2 ? 64 : (fused == 3 ? 32 : 0);   // operator tests: the 64- / 32-token form whatever the launch's rule says
+        g.x = dx;
+        if (have) {
+          g.gn_partial = partial; g.gn_gamma = dgw; g.gn_beta = dgb; g.gn_entries = n_entries;
+        } else {   // no producer statistics: the GroupNorm launch, then the fused launch on the normalised tensor
+          launch_groupnorm(dx, C, nullptr, 0, partial, dgw, dgb, dnorm, B, HW, groups, gn_eps, 0, sc.stream, n_entries);
+          g.x = dnorm;
+        }
+        g.gn_groups = groups; g.gn_eps = gn_eps;
+        g.wp_t = dwp_t; g.p_bias = dpb; g.h = dh;
+        g.wqkv_t = dwq_t; g.qkv_bias = fq.bias; g.qkv_colsum = fq.colsum; g.ln_eps = ln_eps;
+        g.qk = dqk; g.vt = dvt; g.M = M; g.C = C; g.S = HW; g.ldT = HW; g.vt_perm = vt_perm != 0; g.q_scale = q_scale;
+        launch_gn_proj_qkv(g, sc.stream);
+      } else {
+        launch_groupnorm(dx, C, nullptr, 0, partial, dgw, dgb, dnorm, B, HW, groups, gn_eps, 0, sc.stream, n_entries);
+        launch_conv(pd, ws, sc.stream);
+        launch_conv(qd, ws, sc.stream);
+      }
+    });
+    if (entries) *entries = (fused && n_entries >= 1 && n_entries <= 128) ? n_entries : 0;
+    if (dclk) {
+      std::vector<long long> hc(n_clk);
+      SD_HIP(hipMemcpy(hc.data(), dclk, n_clk * sizeof(long long), hipMemcpyDeviceToHost));
+      static const char* names[13] = {"start -> group statistics folded", "-> constants in LDS", "-> normalised tile in LDS", "-> proj_in MFMAs issued",
+                                      "-> h tile in LDS", "-> q MFMAs", "-> q stored", "-> k MFMAs", "-> k stored", "-> v MFMAs", "-> V^T stored", "", ""};
+      const size_t nw = n_clk / 16;
+      double total = 0;
+      for (int ph = 1; ph <= 11; ++ph) {
+        double sum = 0, mx = 0;
+        for (size_t w = 0; w < nw; ++w) {
+          const double dlt = (double)(hc[w * 16 + ph] - hc[w * 16 + ph - 1]);
+          sum += dlt;
+          mx = std::max(mx, dlt);
+        }
+        total += sum / nw;
+        fprintf(stderr, "gn_proj_qkv phase %2d  mean %8.0f  max %8.0f cycles   %s\n", ph, sum / nw, mx, names[ph - 1]);
+      }
+      fprintf(stderr, "gn_proj_qkv mean wave %8.0f cycles (%zu waves; the XCDs' counters are not synchronised: no launch-wide span)\n", total, nw);
+    }
+    SD_HIP(hipMemcpy(out_h, dh, (size_t)M * C * 2, hipMemcpyDeviceToHost));
+    SD_HIP(hipMemcpy(out_qk, dqk, (size_t)M * 2 * C * 2, hipMemcpyDeviceToHost));
+    SD_HIP(hipMemcpy(out_vt, dvt, (size_t)B * C * HW * 2, hipMemcpyDeviceToHost));
+  });
+}
+
+int sd_op_timestep_embedding(const float* t, float* out, int n, int dim, int flip_sin_to_cos, float freq_shift) {
+  return guarded([&] {
+    SD_REQUIRE(t && out && n > 0 && dim > 0 && dim % 2 == 0, kInvalidArgument, "bad arguments");
+    SD_REQUIRE(flip_sin_to_cos == 1, kUnsupported, "flip_sin_to_cos=False is not on the path");
+    Scratch sc;
+    float* dt = sc.dev<float>(n, t);
+    float* dout = sc.dev<float>((size_t)n * dim);
+    std::vector<float> f = timestep_freq_table(dim, freq_shift);
+    float* df = sc.dev<float>(f.size(), f.data());
+    launch_timestep_embedding(dt, df, dout, n, dim, sc.stream);
+    SD_HIP(hipStreamSynchronize(sc.stream));
+    SD_HIP(hipMemcpy(out, dout, (size_t)n * dim * sizeof(float), hipMemcpyDeviceToHost));
+  });
+}
+
+}  // extern "C"

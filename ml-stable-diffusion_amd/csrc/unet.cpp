@@ -13,6 +13,7 @@
 //    when encoder_hidden_states changes, not every step (SURVEY.md Appendix E obs. 3); all 22
 //    time_emb_proj(SiLU(emb)) (unet.py:477) are one batched GEMV per step.
 #include "unet.h"
+#include "weight_prep.h"
 
 #ifndef SD_GN_QKV_DEFAULT
 #define SD_GN_QKV_DEFAULT 1   // the one-launch head of a SpatialTransformer (UNet::transformer); 0 = the three launches it replaces
@@ -105,19 +106,7 @@ half_t* UNet::upload_conv_weight(const std::string& name, int cout, int cin, int
   SD_REQUIRE(t.numel() == expect, kInvalidArgument, "%s.weight has %zu elements, expected %zu (%d,%d,%d,%d)",
              name.c_str(), t.numel(), expect, cout, cin, k, k);
   std::vector<half_t> host(expect);
-  const int kk = k * k;
-  for (int o = 0; o < cout; ++o) {
-    int dst_o = o;
-    if (geglu) {
-      const int half_n = cout / 2;
-      const bool gate = o >= half_n;
-      const int j = gate ? o - half_n : o;
-      dst_o = (j / 32) * 64 + (gate ? 32 : 0) + (j % 32);
-    }
-    for (int c = 0; c < cin; ++c)
-      for (int t2 = 0; t2 < kk; ++t2)
-        host[((size_t)dst_o * kk + t2) * cin + c] = (half_t)t.data[((size_t)o * cin + c) * kk + t2];
-  }
+  retile_ohwi(t.data.data(), cout, cin, k, geglu, host.data());
   half_t* d = arena_.alloc_n<half_t>(expect);
   SD_HIP(hipMemcpy(d, host.data(), expect * sizeof(half_t), hipMemcpyHostToDevice));
   return d;
@@ -127,14 +116,8 @@ float* UNet::upload_vec(const std::string& name, int n, bool geglu) {
   const HostTensor& t = ws_->get(name);
   SD_REQUIRE((int)t.numel() == n, kInvalidArgument, "%s has %zu elements, expected %d", name.c_str(), t.numel(), n);
   std::vector<float> host(t.data);
-  if (geglu) {
-    const int half_n = n / 2;
-    for (int o = 0; o < n; ++o) {
-      const bool gate = o >= half_n;
-      const int j = gate ? o - half_n : o;
-      host[(j / 32) * 64 + (gate ? 32 : 0) + (j % 32)] = t.data[o];
-    }
-  }
+  if (geglu)
+    for (int o = 0; o < n; ++o) host[geglu_row(o, n)] = t.data[o];
   float* d = arena_.alloc_n<float>(n);
   SD_HIP(hipMemcpy(d, host.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice));
   return d;
@@ -153,10 +136,7 @@ Tensor UNet::conv(std::vector<Op>& ops, const std::string& name, const Tensor& x
     const size_t expect = (size_t)cout * cin * k * k;
     SD_REQUIRE(!geglu && t.numel() == expect, kInvalidArgument, "%s.weight has %zu elements, expected %zu", name.c_str(), t.numel(), expect);
     std::vector<float> host(expect);
-    const int kk = k * k;
-    for (int o = 0; o < cout; ++o)
-      for (int c = 0; c < cin; ++c)
-        for (int t2 = 0; t2 < kk; ++t2) host[((size_t)o * kk + t2) * cin + c] = t.data[((size_t)o * cin + c) * kk + t2];
+    retile_ohwi(t.data.data(), cout, cin, k, false, host.data());
     float* d = arena_.alloc_n<float>(expect);
     SD_HIP(hipMemcpy(d, host.data(), expect * sizeof(float), hipMemcpyHostToDevice));
     w_f32_pending_ = true;   // consumed by conv_w's fp32 branch (ConvF32Desc::w_kind 1)
@@ -200,25 +180,8 @@ UNet::LnFold UNet::fold_layernorm(const std::string& ln, const std::vector<std::
     SD_REQUIRE(t.numel() == (size_t)cout_each * cin, kInvalidArgument, "%s.weight: bad shape", names[i].c_str());
     const HostTensor* tb = ws_->has(names[i] + ".bias") ? &ws_->get(names[i] + ".bias") : nullptr;
     SD_REQUIRE(!tb || (int)tb->numel() == cout_each, kInvalidArgument, "%s.bias: bad shape", names[i].c_str());
-    for (int o = 0; o < cout_each; ++o) {
-      int dst = i * cout_each + o;
-      if (geglu) {   // same value/gate interleave as upload_conv_weight
-        const int half_n = cout_each / 2;
-        const bool gate = o >= half_n;
-        const int j = gate ? o - half_n : o;
-        dst = (j / 32) * 64 + (gate ? 32 : 0) + (j % 32);
-      }
-      double cs = 0.0, bb = tb ? (double)tb->data[o] : 0.0;
-      for (int c = 0; c < cin; ++c) {
-        const float wv = t.data[(size_t)o * cin + c];
-        const half_t h = (half_t)(wv * g.data[c]);
-        w[(size_t)dst * cin + c] = h;
-        cs += (double)(float)h;          // column sum of what the MFMA actually multiplies
-        bb += (double)wv * (double)be.data[c];
-      }
-      colsum[dst] = (float)cs;
-      bias[dst] = (float)bb;
-    }
+    fold_layernorm_rows(t.data.data(), tb ? tb->data.data() : nullptr, g.data.data(), be.data.data(), cout_each, cin, i * cout_each,
+                        geglu, w.data(), colsum.data(), bias.data());
   }
   LnFold f;
   f.w = arena_.alloc_n<half_t>(w.size());
