@@ -363,6 +363,18 @@ int sd_op_gn_proj_qkv(const void* x_in, const void* conv_w, const float* gn_weig
                       int* entries, int iters, float* ms);
 /* unet.py:703-728 */
 int sd_op_timestep_embedding(const float* t, float* out, int n, int dim, int flip_sin_to_cos, float freq_shift);
+/* Which plan does the library give a conv / 1x1 GEMM of this shape?  Host only, read only: needs no GPU and launches nothing.
+ * The descriptor as plain ints: C0 (+ C1 > 0: a second, channel-concatenated source) -> N over B x Ho x Wo outputs, up = 1 / 2 (nearest
+ * upsample in the gather), out_mode 0 plain, 1 token-transposed, 2 GEGLU; flags: 1 LayerNorm fold, 2 timestep embedding, 4 residual,
+ * 8 GroupNorm statistics wanted from the epilogue, 16 bias, 32 explicit zero padding (the stride-2 downsample of the VAE encoder);
+ * n_trans > 0: fused q|k|v with that many row-major columns; n_twins: GroupNorm twins written by the slab combine; gnf_groups > 0:
+ * GroupNorm of the input folded into the launch; tile / staging / splitk: a forced plan (0 = the library's); copies: which pre-tiled
+ * weight copies exist (1 wstream, 2 wsgemm, 4 bvgemm; -1 = the ones the library's handle would hold).
+ * plan[7] = plan tile (1-4 igemm tiles, 7 halo conv, 9 wstream, 10 wsgemm, 11 bvgemm, 12 smgemm, 13 smgeglu, -1 off the MFMA path),
+ * staging, resolved split-K, slab (0 / 1), then the copies a handle must hold for this conv: wstream, wsgemm, bvgemm (0 / 1 each).
+ * *workspace_bytes: the slab workspace this launch needs. */
+int sd_op_conv_plan(int ksize, int stride, int up, int C0, int C1, int N, int B, int Ho, int Wo, int out_mode, int flags, int n_trans,
+                    int n_twins, int gnf_groups, int tile, int staging, int splitk, int copies, int* plan, unsigned long long* workspace_bytes);
 /* numpy legacy stream: np.random.seed(seed); np.random.randn(n) (pipeline.py:331,:726;
  * NumPyRandomSource.swift:28-102).  Host-side, bit-exact. */
 int sd_numpy_randn(uint32_t seed, double* out, size_t n);

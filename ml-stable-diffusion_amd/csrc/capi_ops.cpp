@@ -26,6 +26,7 @@
 #include <initializer_list>
 
 #include "capi_util.h"
+#include "conv_plan.h"
 #include "weight_prep.h"
 
 namespace sd {
@@ -305,6 +306,8 @@ int sd_op_groupnorm_shortcut(const void* x0, const void* x1, const float* gn_wei
   });
 }
 
+// tile = 0 and splitk = 0 mirror a handle: the entry holds the pre-tiled weight copies conv_plan_copies names, so the launch runs the
+// plan a UNet's conv of this shape runs (plan tiles 9 / 11 included; sd_op_conv_plan says which).  A forced tile holds its own copy only.
 int sd_op_conv2d(const void* x, const void* w, const float* bias, const void* res, void* out, int B, int Cin, int H,
                  int W, int Cout, int ksize, int stride, int upsample, int tile, int splitk, int force_generic,
                  int iters, float* ms) {
@@ -331,8 +334,10 @@ int sd_op_conv2d(const void* x, const void* w, const float* bias, const void* re
     if (d.debug & 4) d.prof = sc.dev<long long>(8);
     const bool fast = force_generic != 1 && conv_fast_path_ok(d);
     ConvWorkspace ws;
-    if (fast && d.tile == 9) tile_for_wstream(sc, d, "conv2d: shape not eligible for plan tile 9 (wstream.hip)");
-    if (fast && d.tile == 11) tile_for_bvgemm(sc, d, "conv2d: shape not eligible for plan tile 11 (bvgemm.hip)");
+    // the pre-tiled weight copies: what a forced plan reads, else exactly what the planner names for the library's own plan
+    const ConvWeightCopies copies = (fast && tile == 0 && splitk == 0 && !d.debug) ? conv_plan_copies(d) : ConvWeightCopies{false, false, false};
+    if (fast && (d.tile == 9 || copies.wstream)) tile_for_wstream(sc, d, "conv2d: shape not eligible for plan tile 9 (wstream.hip)");
+    if (fast && (d.tile == 11 || copies.bvgemm)) tile_for_bvgemm(sc, d, "conv2d: shape not eligible for plan tile 11 (bvgemm.hip)");
     if (fast && d.tile != 11 && d.tile != 12) ws = workspace_for(sc, {d});
     // N <= 8 (conv_out of the UNet / the VAE): the small-N kernels the handles use, unless the direct kernel was asked for
     const bool small_n = !fast && force_generic == 0 && Cout <= 8 && Cin % 8 == 0 && ksize == 3 && stride == 1 && !res;
@@ -728,7 +733,8 @@ int sd_op_geglu_ln(const void* x, const float* ln_weight, const float* ln_bias, 
     SD_REQUIRE(!smgeglu || smgeglu_shape_ok(d, sg_variant), kInvalidArgument,
                "GEGLU shape not eligible for plan tile 13 (smgeglu.hip): M=%d C=%d N2=%d", M, C, N2);
     SD_REQUIRE(conv_fast_path_ok(d), kUnsupported, "GEGLU shape off the MFMA path (C=%d N2=%d)", C, N2);
-    if (kernel != 1 && kernel < 3 && !smgeglu && wsgemm_shape_ok(d)) tile_for_wsgemm(sc, d);
+    // the wsgemm copy: where plan tile 10 is forced (kernel 2), else exactly where the planner names it for the library's own plan
+    if (!smgeglu && (kernel == 2 ? wsgemm_shape_ok(d) : kernel == 0 && conv_plan_copies(d).wsgemm)) tile_for_wsgemm(sc, d);
     if (kernel == 2) d.tile = 10;
     size_t sg_prof = 0;
     if (smgeglu) {
@@ -794,11 +800,12 @@ int sd_op_qkv_ln(const void* x, const float* ln_weight, const float* ln_bias, co
     half_t* dvt = sc.dev<half_t>((size_t)B * C * HW);
     ConvDesc d = qkv_desc(sc.dev<half_t>((size_t)M * C, f16(x)), f, eps, dqk, dvt, B, 1, HW, C, q_scale, vt_perm);
     SD_REQUIRE(conv_fast_path_ok(d), kUnsupported, "q|k|v shape off the MFMA path (C=%d)", C);
-    if (kernel == 2 || (kernel == 0 && wsgemm_wanted(d))) {   // the weight-stationary kernel (wsgemm.hip, plan tile 10)
+    const ConvWeightCopies copies = conv_plan_copies(d);   // what the library's own plan (kernel 0) reads
+    if (kernel == 2 || (kernel == 0 && copies.wsgemm)) {   // the weight-stationary kernel (wsgemm.hip, plan tile 10)
       SD_REQUIRE(wsgemm_shape_ok(d), kInvalidArgument, "q|k|v shape not eligible for plan tile 10 (wsgemm.hip)");
       tile_for_wsgemm(sc, d);
       if (kernel == 2) d.tile = 10;
-    } else if (kernel >= 3 || (kernel == 0 && bvgemm_wanted(d))) {
+    } else if (kernel >= 3 || (kernel == 0 && copies.bvgemm)) {
       tile_for_bvgemm(sc, d, "q|k|v shape not eligible for plan tile 11 (bvgemm.hip)");
       if (kernel >= 3) {
         d.tile = 11;
@@ -904,6 +911,48 @@ int sd_op_gn_proj_qkv(const void* x_in, const void* conv_w, const float* gn_weig
     SD_HIP(hipMemcpy(out_h, dh, (size_t)M * C * 2, hipMemcpyDeviceToHost));
     SD_HIP(hipMemcpy(out_qk, dqk, (size_t)M * 2 * C * 2, hipMemcpyDeviceToHost));
     SD_HIP(hipMemcpy(out_vt, dvt, (size_t)B * C * HW * 2, hipMemcpyDeviceToHost));
+  });
+}
+
+// Which plan does a conv / 1x1 GEMM of this shape get (conv_plan.h)?  Host only: no GPU, nothing launched.
+int sd_op_conv_plan(int ksize, int stride, int up, int C0, int C1, int N, int B, int Ho, int Wo, int out_mode, int flags, int n_trans,
+                    int n_twins, int gnf_groups, int tile, int staging, int splitk, int copies, int* plan, unsigned long long* workspace_bytes) {
+  return guarded([&] {
+    SD_REQUIRE(plan && workspace_bytes && ksize >= 1 && stride >= 1 && up >= 1 && C0 >= 1 && C1 >= 0 && N >= 1 && B >= 1 && Ho >= 1 && Wo >= 1 &&
+                   n_trans >= 0 && n_twins >= 0 && n_twins <= 2 && gnf_groups >= 0 && copies >= -1 && copies <= 7,
+               kInvalidArgument, "bad conv_plan arguments");
+    static const float present[4] = {};   // the planner only tests these pointers
+    const half_t* ph = reinterpret_cast<const half_t*>(present);
+    ConvDesc d;
+    d.x0 = d.w = ph;
+    d.C0 = C0;
+    if (C1 > 0) d.x1 = ph, d.C1 = C1;
+    d.B = B; d.Ho = Ho; d.Wo = Wo; d.Hi = Ho * stride / up; d.Wi = Wo * stride / up;
+    d.ksize = ksize; d.stride = stride; d.up = up; d.N = N; d.out_mode = out_mode;
+    if (flags & 1) d.ln_colsum = present;
+    if (flags & 2) d.temb = present;
+    if (flags & 4) d.res = ph;
+    if (flags & 8) d.gn_partial = const_cast<float*>(present), d.gn_groups = 32;
+    if (flags & 16) d.bias = present;
+    if (flags & 32) d.pad = 0;
+    if (n_trans > 0) d.out_t = const_cast<half_t*>(ph), d.n_trans = n_trans, d.ldT = Ho * Wo;
+    d.n_twins = n_twins;
+    if (gnf_groups > 0) {   // GroupNorm of the input folded into this launch, as the UNet's resnets / transformers ask for it
+      d.gnf_partial = d.gnf_gamma = d.gnf_beta = present;
+      d.gnf_groups = gnf_groups;
+      d.gnf_entries = 1;
+      d.gnf_silu = ksize == 3 ? 1 : 0;
+    }
+    d.tile = tile; d.staging = staging; d.splitk = splitk;
+    const ConvWeightCopies c = conv_plan_copies(d);
+    if (copies < 0) copies = (c.wstream ? 1 : 0) | (c.wsgemm ? 2 : 0) | (c.bvgemm ? 4 : 0);   // what a handle of the library holds
+    if (copies & 1) d.w_tiled = ph;
+    if (copies & 2) d.w_ws = ph;
+    if (copies & 4) d.w_bv = ph;
+    const ConvPlan p = conv_plan(d);
+    plan[0] = p.tile; plan[1] = p.staging; plan[2] = p.splitk; plan[3] = p.slab ? 1 : 0;
+    plan[4] = c.wstream ? 1 : 0; plan[5] = c.wsgemm ? 1 : 0; plan[6] = c.bvgemm ? 1 : 0;
+    *workspace_bytes = p.workspace_bytes;
   });
 }
 

@@ -40,6 +40,7 @@ struct Scratch {
   hipEvent_t e0 = nullptr, e1 = nullptr;
   Scratch() {
     require_device();
+    device_zero_chunk();   // the conv launches only read it
     SD_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     SD_HIP(hipEventCreate(&e0));
     SD_HIP(hipEventCreate(&e1));

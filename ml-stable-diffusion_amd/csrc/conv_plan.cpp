@@ -1,0 +1,399 @@
+// The conv / GEMM planner (conv_plan.h).  No kernel and no HIP call in this file.
+#include "conv_plan.h"
+
+#include <algorithm>
+#include <cstring>
+
+namespace sd {
+
+namespace {
+
+constexpr int BK = kConvBK;
+
+// the sizes the rules below are written in (IgemmArgs carries the same numbers to the kernels: igemm_device.h make_args)
+struct Dims {
+  int Ctot, M, N, K, HoWo, nk_total, tiles_x, tiles_y;
+};
+Dims dims_of(const ConvDesc& d) {
+  Dims a;
+  a.Ctot = d.C0 + (d.x1 ? d.C1 : 0);
+  a.M = d.B * d.Ho * d.Wo;
+  a.N = d.N;
+  a.K = d.ksize * d.ksize * a.Ctot;
+  a.HoWo = d.Ho * d.Wo;
+  a.nk_total = a.K / BK;
+  a.tiles_x = cdiv(d.Wo, 16);   // halo kernels: stride 1, so output = (upsampled) input extent
+  a.tiles_y = cdiv(d.Ho, 8);
+  return a;
+}
+
+// The A/B switches of the plan, each read here and nowhere else (SD_TUNE only: sd_common.h tune_env_int).
+//   SD_WSTREAM=0 takes plan tile 9 out of every plan; SD_WSGEMM / SD_BVGEMM / SD_SMGEMM / SD_SMGEGLU=0 keep the library's own rule
+//   from taking tiles 10 / 11 / 12 / 13 (a forced tile still runs); SD_REDUCE_STATS=1: GroupNorm statistics from the slab combine
+//   (measured: the step loses 0.25 ms with it, LAB_NOTES.md r5 - off unless asked for)
+struct Switches {
+  bool wstream, wsgemm, bvgemm, smgemm, smgeglu, reduce_stats, tuning;
+};
+const Switches& switches() {
+  static const Switches s = {tune_env_int("SD_WSTREAM", 1) != 0, tune_env_int("SD_WSGEMM", 1) != 0, tune_env_int("SD_BVGEMM", 1) != 0,
+                             tune_env_int("SD_SMGEMM", 1) != 0, tune_env_int("SD_SMGEGLU", 1) != 0, tune_env_int("SD_REDUCE_STATS", 0) != 0,
+                             getenv("SD_TUNE") != nullptr};
+  return s;
+}
+
+struct Plan {
+  int tile;     // 1: 128x128, 2: 128x64, 3: 64x64, 4: 64x128
+  int splitk;
+  int staging = 0;   // from the tuned table (tile / 10): 0 two-stage LDS-DMA, 2 / 3 = 3- / 4-stage ring
+};
+
+// the LayerNorm fold needs whole rows per workgroup, the fused q|k|v epilogue has no slab path
+bool can_split(const ConvDesc& d) { return d.out_mode == kOutHalf && !d.ln_colsum && !d.out_t; }
+// the weight-streaming kernel can take this conv: its pre-tiled weights exist and the shape is its own (SD_WSTREAM: tile_ok)
+bool can_stream(const ConvDesc& d) { return d.w_tiled != nullptr && can_split(d) && wstream_shape_ok(d); }
+// fp32 slabs of a launch: one per split, one when only `slab` (weight stream, GroupNorm twins) asks for the slab path
+size_t slab_bytes(const Dims& a, int splits, bool slab) { return (splits > 1 || slab) ? (size_t)splits * a.M * a.N * sizeof(float) : 0; }
+
+// Heuristic (overridden per shape by the measured table in tuned_convs.inc when present):
+// prefer the biggest tile whose grid, multiplied by the split-K it can afford (>= 16 K-tiles per
+// split), still gives every CU work (>= ~1.5 workgroups per CU); deep-K small-M layers (8x8 /
+// 16x16 levels stream weights: SURVEY.md 7.3(1)) end up split, shallow 1x1 GEMMs end up on the
+// small tile with many workgroups.
+// kind: 0 plain epilogue (bias / timestep embedding / residual), 1 LayerNorm-folded, 2 GEGLU (LayerNorm-folded or
+// not), 3 fused q|k|v (LayerNorm-folded, V columns leave transposed).  staging: see launch_tile.
+struct TunedConv { int kind, ksize, stride, up, ctot, n, m, tile, staging, splitk; };
+#if __has_include("tuned_convs.inc")
+static const TunedConv kTuned[] = {
+#include "tuned_convs.inc"
+};
+static const int kNumTuned = sizeof(kTuned) / sizeof(kTuned[0]);
+#else
+static const TunedConv* kTuned = nullptr;
+static const int kNumTuned = 0;
+#endif
+
+// SD_PLAN_TABLE=<file>: rows "{kind, ksize, stride, up, Ctot, N, M, tile, staging, splitk}" (the format of
+// tuned_convs.inc) read at first use and consulted BEFORE the compiled-in table - how tools/tune_plans.py
+// validates a freshly measured table in the same GPU session without a rebuild.
+bool parse_plan_row(const char* line, TunedConv& r) {
+  return sscanf(line, " {%d, %d, %d, %d, %d, %d, %d, %d, %d, %d}", &r.kind, &r.ksize, &r.stride, &r.up, &r.ctot, &r.n, &r.m, &r.tile,
+                &r.staging, &r.splitk) == 10;
+}
+std::vector<TunedConv>& runtime_table() {
+  static std::vector<TunedConv> table = [] {
+    std::vector<TunedConv> t;
+    const char* path = tune_env_set("SD_PLAN_TABLE") ? getenv("SD_PLAN_TABLE") : nullptr;
+    if (!path) return t;
+    FILE* f = fopen(path, "r");
+    if (!f) {
+      fprintf(stderr, "[sd] SD_PLAN_TABLE=%s cannot be opened - ignored\n", path);
+      return t;
+    }
+    char line[512];
+    while (fgets(line, sizeof(line), f)) {
+      TunedConv r;
+      if (parse_plan_row(line, r)) t.push_back(r);
+    }
+    fclose(f);
+    fprintf(stderr, "[sd] SD_PLAN_TABLE=%s: %zu plans\n", path, t.size());
+    return t;
+  }();
+  return table;
+}
+
+// measurement hook (sd_tune_set_candidate): while tile != 0 every conv whose constraints allow it runs this plan,
+// so one profiled forward evaluates a candidate on every layer shape at once, in sequence (tools/tune_plans.py)
+struct TuneCandidate { int tile = 0, staging = 0, splitk = 0; };
+TuneCandidate g_tune;
+
+int conv_kind(const ConvDesc& d) {
+  if (d.out_t) return 3;
+  if (d.out_mode == kOutGeglu) return 2;
+  return d.ln_colsum ? 1 : 0;
+}
+
+// the table match: a row is for this descriptor's shape key (choose_plan adds "and its tile is admissible")
+bool table_match(const TunedConv& t, const ConvDesc& d, const Dims& a) {
+  return t.kind == conv_kind(d) && t.ksize == d.ksize && t.stride == d.stride && t.up == d.up && t.ctot == a.Ctot && t.n == a.N && t.m == a.M;
+}
+
+Plan choose_plan(const ConvDesc& d, const Dims& a) {
+  Plan p{d.tile, d.splitk};
+  p.staging = d.staging;
+  const bool geglu = d.out_mode == kOutGeglu;
+  const bool split_ok = can_split(d);
+  // plan tiles: 1 = 128x128, 2 = 128x64, 3 = 64x64, 4 = 64x128 (igemm_kernel / gemm_pipe_kernel), 7 = the halo conv.  Codes 5 / 6
+  // (round 2's first halo kernel) and 8 / 9 (256x128 / 256x256 GEMM tiles, measured in round 3 and selected nowhere) were removed
+  // in round 4: a caller or table row that names them gets the heuristic.
+  auto is_halo = [](int c) { return c == 7; };
+  // plan tile 9 = the weight-streaming kernel of wstream.hip (needs the pre-tiled weights; staging 4 = four waves per workgroup,
+  // anything else eight; its slab count follows from the wave count).  SD_WSTREAM=0 (with SD_TUNE) takes it out of every plan: A/B.
+  auto tile_ok = [&](int c) {
+    if (c == 9) return switches().wstream && can_stream(d);
+    if (!((c >= 1 && c <= 4) || c == 7)) return false;
+    if (is_halo(c)) return halo_ks_ok(d) && !d.ln_colsum && !d.out_t && !geglu;
+    int bm, bn;
+    tile_dims(c, bm, bn);
+    if (geglu && c != 1 && c != 4) return false;       // GEGLU value/gate pairs need 64 n-columns per wave
+    if (d.out_t && d.n_trans % bn != 0) return false;  // the q|k / v boundary must be a tile boundary
+    return true;
+  };
+  if (!tile_ok(p.tile)) p.tile = 0;
+  auto blocks_of = [&](int c) {
+    int bm, bn;
+    tile_dims(c, bm, bn);
+    const long mt = is_halo(c) ? (long)d.B * a.tiles_x * a.tiles_y : cdiv(a.M, bm);
+    return mt * cdiv(a.N, bn);
+  };
+  auto ksteps = [&](int c) { return is_halo(c) ? a.Ctot / BK : a.nk_total; };   // split-K granularity
+  auto max_split = [&](int c) {
+    // a split costs a dependent reduce launch (~6 us): worth it only while each split still runs >= 16 K
+    // steps (measured: 20-step 1x1 GEMMs lose 2.5 us when split in two, 180-step 3x3 convs peak at 8 splits)
+    const int per_min = is_halo(c) ? 2 : 16;     // halo splits whole 64-channel chunks (9 K steps each)
+    int s = 1;
+    while (split_ok && s < 16 && ksteps(c) / (s * 2) >= per_min) s *= 2;
+    return s;
+  };
+  const bool pinned = p.tile != 0 || p.splitk != 0 || p.staging != 0;   // the caller chose (operator-level A/B tests)
+  if (!pinned && g_tune.tile != 0 && tile_ok(g_tune.tile)) {
+    p.tile = g_tune.tile;
+    p.staging = g_tune.staging;
+    p.splitk = g_tune.splitk;
+  } else if (!pinned) {
+    auto match = [&](const TunedConv& t) { return table_match(t, d, a) && tile_ok(t.tile); };
+    const TunedConv* hit = nullptr;
+    for (const TunedConv& t : runtime_table())
+      if (!hit && match(t)) hit = &t;
+    for (int i = 0; i < kNumTuned && !hit; ++i)
+      if (match(kTuned[i])) hit = &kTuned[i];
+    if (hit) {
+      p.tile = hit->tile;
+      p.staging = hit->staging;
+      p.splitk = hit->splitk;
+    }
+  }
+  // (measured and dropped, round 3: sending every untuned 1x1 GEMM with M >= 8192 to the software-pipelined kernel's 128x64
+  // tile - 10-25 % faster stand-alone at UNet batch 16 - made the batch-16 step 1.3 % and the batch-4 step 0.6 % SLOWER in
+  // sequence; the pipelined kernel is only used where tools/tune_e2e.py accepted it end to end)
+  // 8x8 level at any small batch: a 3x3 conv there is a weight stream (wstream.hip), whatever the table says for M = 128
+  if (p.tile == 0 && tile_ok(9) && d.ksize == 3 && a.HoWo <= 64 && a.M <= 256) p.tile = 9;
+  if (p.tile == 9) {
+    p.splitk = 1;   // (the slab count follows from the wave count: conv_plan)
+    return p;
+  }
+  if (p.tile == 0 && tile_ok(7)) {
+    // no measured plan for this shape: the K-split halo kernel with the 4-stage ring won every 3x3 / stride-1 shape that was
+    // tuned (SD2.1-base, SDXL-base, SD1.5: tuned_convs.inc); split-K below as for the other kernels
+    p.tile = 7;
+    if (p.staging == 0) p.staging = 3;
+  }
+  if (p.tile == 0) {
+    p.tile = 3;
+    for (int c : {1, 2, 4, 3}) {
+      if (!tile_ok(c)) continue;
+      if (blocks_of(c) * max_split(c) >= 384 || c == 3) { p.tile = c; break; }
+    }
+    if (!tile_ok(p.tile)) p.tile = 4;
+  }
+  if (p.splitk == 0) {
+    p.splitk = 1;
+    const int ms = max_split(p.tile);
+    const long want = p.tile == 7 ? 192 : 384;   // the pipelined halo kernel is at its best from ~160 workgroups (1 per CU)
+    while (blocks_of(p.tile) * p.splitk < want && p.splitk < ms) p.splitk *= 2;
+  }
+  if (!split_ok) p.splitk = 1;
+  if (p.splitk > ksteps(p.tile)) p.splitk = ksteps(p.tile);
+  if (p.splitk < 1) p.splitk = 1;
+  return p;
+}
+
+// Would the plan of this conv be the weight-streaming kernel (plan tile 9) if its fragment-major weight copy existed?  The ONE
+// predicate the copy is allocated by (a second, looser copy of this rule left ~430 MB of copies per handle that no
+// kernel reads).
+bool plan_is_wstream(const ConvDesc& d0) {
+  if (!wstream_shape_ok(d0)) return false;
+  ConvDesc d = d0;
+  static const half_t present = 0;
+  d.w_tiled = &present;   // choose_plan only tests the pointer
+  return choose_plan(d, dims_of(d)).tile == 9;
+}
+
+}  // namespace
+
+// the K-split halo kernel also folds the nearest-x2 upsample into its gather and takes 8-pixel-wide images (half of each
+// 8x16 tile is then padding: the 8x8 level streams weights, MFMA work is not what bounds it)
+bool halo_ks_ok(const ConvDesc& d) {
+  const int c1 = d.x1 ? d.C1 : 0;
+  return d.ksize == 3 && d.stride == 1 && (d.up == 1 || d.up == 2) && d.pad < 0 && d.out_mode == kOutHalf && d.Wo >= 8 && d.Ho >= 8 &&
+         d.C0 % BK == 0 && c1 % BK == 0 && d.N % 4 == 0;
+}
+
+bool gemm_pipe_ok(int ksize, int stride, int up, int M, int N, int K, int C0, int C1) {
+  const size_t lim = (size_t)1 << 31;
+  return ksize == 1 && stride == 1 && up == 1 && (size_t)M * std::max(C0, C1) * 2 < lim && (size_t)N * K * 2 < lim;
+}
+
+void tile_dims(int tile, int& bm, int& bn) {
+  switch (tile) {
+    case 7: bm = 128; bn = 64; break;    // halo conv (8x16-pixel tile), K-split waves + register double buffering
+    case 1: bm = 128; bn = 128; break;
+    case 2: bm = 128; bn = 64; break;
+    case 3: bm = 64; bn = 64; break;
+    default: bm = 64; bn = 128; break;
+  }
+}
+
+bool conv_fast_path_ok(const ConvDesc& d) {
+  const int c1 = d.x1 ? d.C1 : 0;
+  if (d.C0 % BK != 0 || c1 % BK != 0) return false;
+  if (d.N % 4 != 0) return false;
+  if (d.out_mode == kOutGeglu && d.N % 64 != 0) return false;
+  if (!(d.ksize == 1 || d.ksize == 3)) return false;
+  if (!(d.up == 1 || d.up == 2)) return false;
+  return true;
+}
+
+ConvPlan conv_plan(const ConvDesc& d) {
+  if (!conv_fast_path_ok(d)) return ConvPlan{-1, 0, 1, false, 0};
+  const Switches& sw = switches();
+  // the library's own rules for tiles 10-13 apply where nothing else was asked for (a tuner candidate in force also keeps them off)
+  const bool free_choice = d.tile == 0 && d.splitk == 0 && d.staging == 0 && g_tune.tile == 0;
+  // plan tile 10: the weight-stationary GEGLU kernel (wsgemm.hip) wherever its pre-tiled weights exist
+  if (d.w_ws && wsgemm_shape_ok(d) && (d.tile == 10 || (sw.wsgemm && free_choice && wsgemm_wanted(d)))) return ConvPlan{10, 0, 1, false, 0};
+  SD_REQUIRE(d.tile != 10, kInvalidArgument, "plan tile 10 (wsgemm.hip) needs the pre-tiled weights and an eligible GEGLU shape");
+  // plan tile 11: weights global -> VGPR (bvgemm.hip), on the library's rule or forced (staging 1 - 4 then force a variant)
+  if (sw.bvgemm && d.w_bv && free_choice && bvgemm_wanted(d)) return ConvPlan{11, 0, 1, false, 0};
+  if (d.tile == 11) {
+    SD_REQUIRE(d.w_bv && bvgemm_shape_ok(d), kInvalidArgument, "plan tile 11 (bvgemm.hip) needs the pre-tiled weights and an eligible 1x1 shape");
+    return ConvPlan{11, d.staging, 1, false, 0};
+  }
+  // plan tiles 12 (smgemm.hip) / 13 (smgeglu.hip): staging 1 / 2 of a forced plan force a tile height (the launchers check its shape)
+  if (d.tile == 12 || (sw.smgemm && free_choice && smgemm_wanted(d))) return ConvPlan{12, d.tile == 12 ? d.staging : 0, 1, false, 0};
+  if (d.tile == 13 || (sw.smgeglu && free_choice && smgeglu_wanted(d))) return ConvPlan{13, d.tile == 13 ? d.staging : 0, 1, false, 0};
+
+  const Dims a = dims_of(d);
+  Plan p = choose_plan(d, a);
+  const bool twins = d.n_twins > 0;
+  if (d.gnf_partial && d.ksize == 3) {   // GroupNorm(+SiLU) applied in the halo loader of the K-split 3x3 kernel (GNL)
+    SD_REQUIRE(conv_gn_loader_ok(d) && d.gnf_silu == 1 && d.gnf_gamma && d.gnf_beta && d.gnf_entries >= 1 && d.gnf_entries <= 128 && !twins, kInvalidArgument,
+               "GroupNorm in the conv loader: Ctot=%d groups=%d entries=%d up=%d", a.Ctot, d.gnf_groups, d.gnf_entries, d.up);
+    p.tile = 7;
+    if (p.staging != 2 && p.staging != 3) p.staging = 3;
+    p.splitk = 1;
+  } else if (d.gnf_partial) {   // GroupNorm folded into this 1x1 GEMM: gemm_pipe_kernel's 64 x 64 tile (the only GNF instantiation)
+    SD_REQUIRE(d.ksize == 1 && d.stride == 1 && !d.x1 && d.out_mode == kOutHalf && !d.ln_colsum && !d.out_t && !twins &&
+                   gemm_pipe_ok(d.ksize, d.stride, d.up, a.M, a.N, a.K, d.C0, 0) &&
+                   d.gnf_gamma && d.gnf_beta && d.gnf_groups >= 1 && d.gnf_groups <= 32 && a.K % d.gnf_groups == 0 && a.K <= 2048 &&
+                   d.gnf_entries >= 1 && d.gnf_entries <= 128 && a.HoWo % 64 == 0,
+               kInvalidArgument, "GroupNorm fold: K=%d groups=%d entries=%d HoWo=%d", a.K, d.gnf_groups, d.gnf_entries, a.HoWo);
+    p.tile = 3;
+    if (p.staging != 6 && p.staging != 7 && p.staging != 8) p.staging = 6;
+    p.splitk = 1;
+  }
+  ConvPlan r{p.tile, p.staging, 1, true, 0};
+  if (p.tile == 9) {   // weight-streaming kernel: one slab per nw input-channel slices, always through the combine
+    r.splitk = wstream_splits(d, p.staging == 4 ? 4 : 8);
+  } else {             // no empty splits
+    const int steps = p.tile == 7 ? a.Ctot / BK : a.nk_total;
+    r.splitk = cdiv(steps, cdiv(steps, p.splitk));
+    r.slab = r.splitk > 1 || twins;
+  }
+  r.workspace_bytes = slab_bytes(a, r.splitk, r.slab);
+  return r;
+}
+
+// Workspace a handle reserves for this conv at build time.  The descriptor may still change before it is launched - the GroupNorm
+// hook attaches statistics or twins, a tuner candidate or a run-time table row changes the split - so this is the split-K plan of
+// the tiled kernels with head room, an upper bound of conv_plan(d).workspace_bytes for every plan the descriptor can later get:
+//   - under SD_TUNE (tools/tune_plans.py), room for the 16 splits of any candidate of the sweep;
+//   - with the weight-stream copy present, its slab count at four waves per workgroup (the most slabs it writes);
+//   - the unresolved split-K (the launch may use fewer splits), one slab when only the GroupNorm twins ask for it.
+size_t conv_workspace_bytes(const ConvDesc& d) {
+  if (!conv_fast_path_ok(d)) return 0;
+  const Dims a = dims_of(d);
+  const Plan p = choose_plan(d, a);
+  int splits = (switches().tuning && can_split(d)) ? std::max(p.splitk, 16) : p.splitk;
+  if (can_stream(d)) splits = std::max(splits, wstream_splits(d, 4));
+  return slab_bytes(a, splits, d.n_twins > 0 || can_stream(d));
+}
+
+ConvWeightCopies conv_plan_copies(const ConvDesc& d0) {
+  ConvWeightCopies c{false, false, false};
+  if (!conv_fast_path_ok(d0)) return c;
+  ConvDesc d = d0;
+  d.w_tiled = d.w_ws = d.w_bv = nullptr;
+  const Switches& sw = switches();
+  const int k = d.ksize, M = d.B * d.Ho * d.Wo;
+  // small-M layers: the weight-streaming kernel (plan tile 9) needs the fragment-major copy of the weights
+  // (SD_TUNE: every shape a plan sweep may send there; production: exactly the convs whose plan IS tile 9)
+  const bool ws_candidate = sw.tuning ? ((k == 3 && M <= 512) || (k == 1 && M <= 128)) : plan_is_wstream(d);
+  c.wstream = sw.wstream && wstream_shape_ok(d) && ws_candidate;
+  // widest-M GEGLU projection (K = 320): the weight-stationary kernel reads its own fragment-major copy (wsgemm.hip)
+  c.wsgemm = sw.wsgemm && wsgemm_wanted(d);
+  // large-M 1x1 GEMMs: weights global -> VGPR (bvgemm.hip) reads its own fragment-major copy; tile 10 comes first in conv_plan
+  c.bvgemm = sw.bvgemm && !c.wsgemm && bvgemm_wanted(d);
+  return c;
+}
+
+// Does the compiled-in plan table hold a row for this shape - a plan that was measured in a step?
+bool conv_plan_is_tuned(const ConvDesc& d) {
+  if (!conv_fast_path_ok(d)) return false;
+  const Dims a = dims_of(d);
+  for (int i = 0; i < kNumTuned; ++i)
+    if (table_match(kTuned[i], d, a)) return true;
+  return false;
+}
+
+// sd_tune_set_plan_table: replace the run-time table by the rows of `text` (tuned_convs.inc format, one per line) - how
+// tools/tune_e2e.py tries one plan after another against the graph replay time of the whole step in ONE process
+int conv_plan_table_set(const char* text) {
+  std::vector<TunedConv>& t = runtime_table();
+  t.clear();
+  if (!text) return 0;
+  const char* p = text;
+  while (*p) {
+    const char* e = strchr(p, '\n');
+    std::string line(p, e ? (size_t)(e - p) : strlen(p));
+    TunedConv r;
+    if (parse_plan_row(line.c_str(), r)) t.push_back(r);
+    if (!e) break;
+    p = e + 1;
+  }
+  return (int)t.size();
+}
+
+void conv_tune_set_candidate(int tile, int staging, int splitk) {
+  g_tune.tile = tile;
+  g_tune.staging = staging;
+  g_tune.splitk = splitk;
+}
+
+void conv_plan_log(const ConvDesc& d, const ConvPlan& p, int bm, int n_fast) {
+  static const bool on = tune_env_set("SD_LOG_CONVS");
+  if (!on) return;
+  const Dims a = dims_of(d);
+  const int c1 = d.x1 ? d.C1 : 0;
+  if (p.tile == 9)
+    fprintf(stderr, "[sd conv] k%d up%d C0=%d C1=%d M=%d N=%d K=%d tile=9 nw=%d slabs=%d twins=%d\n", d.ksize, d.up, d.C0, c1, a.M, a.N, a.K,
+            p.staging == 4 ? 4 : 8, p.splitk, d.n_twins);
+  else if (p.tile == 12 || p.tile == 13)
+    fprintf(stderr, "[sd conv] k1 s1 up1 C0=%d C1=%d M=%d N=%d K=%d mode=%d tile=%d bm=%d n_fast=%d\n", d.C0, c1, a.M, a.N, a.K, d.out_mode, p.tile, bm,
+            n_fast);
+  else
+    fprintf(stderr, "[sd conv] k%d s%d up%d C0=%d C1=%d M=%d N=%d K=%d mode=%d tile=%d splitk=%d\n", d.ksize, d.stride, d.up, d.C0, c1, a.M, a.N,
+            a.K, d.out_mode, p.tile, p.splitk);
+}
+
+bool choose_tile_order(double a_bytes, double w_bytes, double nbm, double nbn, bool ab_switch) {
+  const double l2 = 3.5e6;   // what one 4-MB L2 keeps of an operand next to the other one's stream
+  const double m_fast_cost = w_bytes + a_bytes * (a_bytes <= l2 ? std::min(8.0, nbn) : nbn);
+  const double n_fast_cost = a_bytes + w_bytes * (w_bytes <= l2 ? std::min(8.0, nbm) : nbm);
+  static const int forced = tune_env_int("SD_TILE_ORDER", -1);   // A/B switch: 0 / 1 / 2
+  if (ab_switch && forced == 2) return nbn > 1 && a_bytes * (nbn - 1) > 7.0 * w_bytes;
+  if (ab_switch && forced >= 0) return forced != 0;
+  return nbn > 1 && n_fast_cost < m_fast_cost;
+}
+
+bool conv_reduce_stats_on() { return switches().reduce_stats; }
+
+}  // namespace sd

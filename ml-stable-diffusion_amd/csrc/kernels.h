@@ -7,7 +7,7 @@
 namespace sd {
 
 // ---------------------------------------------------------------------------------------------
-// K4/K5: implicit-GEMM convolution / 1x1 GEMM on MFMA (igemm.hip)
+// K4/K5: implicit-GEMM convolution / 1x1 GEMM on MFMA (igemm.hip, conv3x3_halo.hip, conv_small.hip; the plan: conv_plan.h)
 //   out[m][n] = epilogue( sum_k X[m][k] * W[n][k] ),  k = tap*(C0+C1) + c
 // ---------------------------------------------------------------------------------------------
 enum OutMode : int {
@@ -106,8 +106,11 @@ struct ConvWorkspace {
   size_t partial_bytes = 0;
 };
 
-// Returns the workspace bytes this conv needs with its current heuristic (for planning).
+// Workspace bytes a handle reserves for this conv at build time: an upper bound of what any plan it can later get needs (conv_plan.cpp).
 size_t conv_workspace_bytes(const ConvDesc& d);
+// 256 B of device zeros, the source of padding rows of the conv kernels: allocated by the first call.  Every handle constructor
+// (and the operator entry points' Scratch) calls it, so it is never first called under graph capture; launches only read it.
+const half_t* device_zero_chunk();
 // returns the number of GroupNorm partial entries per (sample, group) written to d.gn_partial (0: none)
 int launch_conv(const ConvDesc& d, const ConvWorkspace& ws, hipStream_t s);
 bool conv_fast_path_ok(const ConvDesc& d);
@@ -118,7 +121,6 @@ bool conv_plan_is_tuned(const ConvDesc& d);   // tuned_convs.inc has a row for t
 int conv_plan_table_set(const char* text);   // rows of tuned_convs.inc format; returns the number of plans read
 
 // wstream.hip: the small-M weight-streaming kernel (plan tile 9) and the group-organised slab combine
-bool conv_plan_is_wstream(const ConvDesc& d);            // choose_plan would take plan tile 9 given the pre-tiled weights
 bool wstream_shape_ok(const ConvDesc& d);                 // shape admits plan tile 9 (d.w_tiled not looked at)
 int wstream_splits(const ConvDesc& d, int nw);            // slabs launch_wstream writes with nw waves per workgroup
 size_t wstream_tiled_halves(int N, int Ctot, int ksize);
@@ -164,7 +166,7 @@ size_t smgeglu_prof_entries(const ConvDesc& d, int variant);          // this ma
 // over between the XCDs' L2s, ns per dependent load from HBM / from the caches
 void run_calibration(int device, float* out);
 
-// direct conv for tiny / odd shapes (any Cin, any N): fp32 accumulate, one thread per output
+// conv_small.hip: direct conv for tiny / odd shapes (any Cin, any N): fp32 accumulate, one thread per output
 int launch_conv_generic(const ConvDesc& d, int act_silu_out, hipStream_t s);   // returns like launch_conv
 
 // N <= 8 outputs, K % 8 == 0: one wavefront per output pixel.  out_nchw_f32: write float

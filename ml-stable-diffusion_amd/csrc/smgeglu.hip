@@ -20,6 +20,7 @@
 // PROF instantiation (ConvDesc::prof): every wave leaves six shader-clock stamps (sd_op_geglu_ln prints the table).
 #include <algorithm>
 
+#include "conv_plan.h"
 #include "kernels.h"
 #include "sm_ring.h"
 
@@ -397,17 +398,11 @@ void launch_smgeglu(const ConvDesc& d, int variant, hipStream_t s) {
   a.lnf = d.ln_colsum != nullptr;
   a.ln_eps = d.ln_eps;
   a.per_xcd = nwg / 8;
-  // tile order by the bytes each pulls into the 8 XCD L2s (smgemm.hip, igemm.hip choose_tile_order)
-  const double a_bytes = 2.0 * M * K, w_bytes = 2.0 * d.N * K, l2 = 3.5e6;
-  const double m_fast_cost = w_bytes + a_bytes * (a_bytes <= l2 ? std::min(8.0, (double)nt) : (double)nt);
-  const double n_fast_cost = a_bytes + w_bytes * (w_bytes <= l2 ? std::min(8.0, (double)mt) : (double)mt);
-  a.n_fast = n_fast_cost < m_fast_cost;
+  // tile order by the bytes each pulls into the 8 XCD L2s (as smgemm.hip: no A/B switch here)
+  a.n_fast = choose_tile_order(2.0 * M * K, 2.0 * d.N * K, (double)mt, (double)nt, false);
   a.fast_div = a.n_fast ? nt : mt;
   a.fast_magic = (unsigned)((1ull << 32) / a.fast_div + 1);
-  static const bool log_plans = tune_env_set("SD_LOG_CONVS");
-  if (log_plans)
-    fprintf(stderr, "[sd conv] k1 s1 up1 C0=%d C1=0 M=%d N=%d K=%d mode=%d tile=13 bm=%d n_fast=%d\n", d.C0, M, d.N, K, d.out_mode, bm,
-            a.n_fast);
+  conv_plan_log(d, ConvPlan{13, variant, 1, false, 0}, bm, a.n_fast);
   if (bm == 128) {
     if (d.prof) sg_launch<128, true>(a, nwg, s);
     else sg_launch<128, false>(a, nwg, s);

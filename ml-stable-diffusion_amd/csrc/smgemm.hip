@@ -20,6 +20,7 @@
 //     one output row; no LDS, no barrier.
 #include <algorithm>
 
+#include "conv_plan.h"
 #include "kernels.h"
 #include "sm_ring.h"
 
@@ -45,7 +46,7 @@ struct SmArgs {
   unsigned per_xcd;     // workgroups of one XCD's contiguous tile run (grid % 8 == 0)
   unsigned fast_div;    // tiles along the fast dimension (>= 2)
   unsigned fast_magic;  // floor(2^32 / fast_div) + 1: mulhi(t, magic) == t / fast_div for t * fast_div < 2^32
-  int n_fast;           // 1: consecutive tiles share an activation panel, 0: a weight panel (igemm.hip IgemmArgs::n_fast)
+  int n_fast;           // 1: consecutive tiles share an activation panel, 0: a weight panel (igemm_device.h IgemmArgs::n_fast)
 };
 
 template <int BM>
@@ -251,18 +252,12 @@ void launch_smgemm(const ConvDesc& d, int variant, hipStream_t s) {
   a.has_bias = d.bias != nullptr;
   a.has_res = d.res != nullptr;
   a.per_xcd = nwg / 8;
-  // tile order by the bytes each pulls into the 8 XCD L2s (igemm.hip choose_tile_order): m fastest streams every weight panel once
-  // and the activations once per XCD; n fastest the other way round
-  const double a_bytes = 2.0 * M * K, w_bytes = 2.0 * d.N * K, l2 = 3.5e6;
-  const double m_fast_cost = w_bytes + a_bytes * (a_bytes <= l2 ? std::min(8.0, (double)nt) : (double)nt);
-  const double n_fast_cost = a_bytes + w_bytes * (w_bytes <= l2 ? std::min(8.0, (double)mt) : (double)mt);
-  a.n_fast = n_fast_cost < m_fast_cost;
+  // tile order by the bytes each pulls into the 8 XCD L2s: m fastest streams every weight panel once and the activations once per
+  // XCD; n fastest the other way round (no A/B switch here)
+  a.n_fast = choose_tile_order(2.0 * M * K, 2.0 * d.N * K, (double)mt, (double)nt, false);
   a.fast_div = a.n_fast ? nt : mt;
   a.fast_magic = (unsigned)((1ull << 32) / a.fast_div + 1);
-  static const bool log_plans = tune_env_set("SD_LOG_CONVS");
-  if (log_plans)
-    fprintf(stderr, "[sd conv] k1 s1 up1 C0=%d C1=%d M=%d N=%d K=%d mode=%d tile=12 bm=%d n_fast=%d\n", d.C0, d.x1 ? d.C1 : 0, M, d.N, K, d.out_mode, bm,
-            a.n_fast);
+  conv_plan_log(d, ConvPlan{12, variant, 1, false, 0}, bm, a.n_fast);
   if (bm == 32) {
     auto k = smgemm_kernel<32>;
     constexpr size_t lds = (size_t)SmCfg<32>::NST * SmCfg<32>::STAGE;

@@ -60,6 +60,7 @@ TextEncoder::TextEncoder(const sd_text_encoder_config& cfg, const WeightStore& w
   SD_REQUIRE(device >= 0 && device < ndev, kInvalidArgument, "device %d out of range (%d visible)", device, ndev);
   SD_HIP(hipSetDevice(device));
   SD_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
+  device_zero_chunk();   // the GEMM launches only read it (never first allocated under graph capture)
   const float eps = cfg.layer_norm_eps > 0 ? cfg.layer_norm_eps : 1e-5f;
   const std::string tm = ws.has("text_model.embeddings.token_embedding.weight") ? "text_model." : "";
   half_t* tok = upload_matrix(ws, tm + "embeddings.token_embedding.weight", cfg.vocab_size, D);

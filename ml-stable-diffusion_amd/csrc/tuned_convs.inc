@@ -1,4 +1,4 @@
-// Plan table: {kind, ksize, stride, up, Ctot, N, M, tile, staging, splitk}  (kind / staging: igemm.hip choose_plan,
+// Plan table: {kind, ksize, stride, up, Ctot, N, M, tile, staging, splitk}  (kind / staging: conv_plan.cpp choose_plan,
 // launch_tile).  Measured IN SEQUENCE on MI355X by tools/tune_plans.py (per-op HIP events of the eager SD2.1-base
 // CFG-batch-2 step, caches as cold as in the step): entries beat the previous plan by more than 3 %.
 // other BASELINE configs (tools/gpu_r2_q.sh): shapes that SD2.1-base does not have

@@ -13,6 +13,7 @@
 //    when encoder_hidden_states changes, not every step (SURVEY.md Appendix E obs. 3); all 22
 //    time_emb_proj(SiLU(emb)) (unet.py:477) are one batched GEMV per step.
 #include "unet.h"
+#include "conv_plan.h"
 #include "weight_prep.h"
 
 #ifndef SD_GN_QKV_DEFAULT
@@ -42,6 +43,7 @@ UNet::UNet(const sd_unet_config& cfg, const WeightStore& ws, int device) : cfg_(
   SD_REQUIRE(device >= 0 && device < ndev, kInvalidArgument, "device %d out of range (%d visible)", device, ndev);
   SD_HIP(hipSetDevice(device));
   SD_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
+  device_zero_chunk();   // the conv launches only read it (never first allocated under graph capture)
   if (tune_env_int("SD_SIDE_TIME", 0) != 0) {
     SD_HIP(hipStreamCreateWithFlags(&side_, hipStreamNonBlocking));
     SD_HIP(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming));
@@ -299,33 +301,23 @@ Tensor UNet::conv_w(std::vector<Op>& ops, const std::string& name, const half_t*
     return dd;
   };
   if (conv_fast_path_ok(d) && !silu_out) {
-    // small-M layers: the weight-streaming kernel (plan tile 9) needs the fragment-major copy of the weights
-    static const int ws_mode = tune_env_int("SD_WSTREAM", 1);
-    const int Mrows = x.B * d.Ho * d.Wo;
-    // (SD_TUNE: every shape a plan sweep may send there; production: exactly the convs whose plan IS tile 9)
-    static const bool tuning = getenv("SD_TUNE") != nullptr;
-    const bool ws_candidate = tuning ? ((k == 3 && Mrows <= 512) || (k == 1 && Mrows <= 128)) : conv_plan_is_wstream(d);
-    if (ws_mode != 0 && !ex && wstream_shape_ok(d) && ws_candidate) {
+    // the pre-tiled (fragment-major) weight copies the plan of this conv reads: exactly what the planner names
+    const ConvWeightCopies copies = conv_plan_copies(d);
+    if (copies.wstream && !ex) {   // small-M layers: the weight-streaming kernel (plan tile 9; never a LayerNorm-fold / q|k|v op)
       const int cin_t = x.C + (x2 ? x2->C : 0);
       half_t* wt = arena_.alloc_n<half_t>(wstream_tiled_halves(cout, cin_t, k));
       launch_wstream_retile(w, wt, cout, cin_t, k, stream_);
       d.w_tiled = wt;
     }
-    {   // widest-M GEGLU projection (K = 320): the weight-stationary kernel reads its own fragment-major copy (wsgemm.hip)
-      static const bool wsg_on = tune_env_int("SD_WSGEMM", 1) != 0;
-      if (wsg_on && wsgemm_wanted(d)) {
-        half_t* wt = arena_.alloc_n<half_t>(wsgemm_tiled_halves(cout));
-        launch_wsgemm_retile(w, wt, cout, geglu, stream_);
-        d.w_ws = wt;
-      }
+    if (copies.wsgemm) {    // widest-M GEGLU projection (K = 320): the weight-stationary kernel (wsgemm.hip, plan tile 10)
+      half_t* wt = arena_.alloc_n<half_t>(wsgemm_tiled_halves(cout));
+      launch_wsgemm_retile(w, wt, cout, geglu, stream_);
+      d.w_ws = wt;
     }
-    {   // large-M 1x1 GEMMs: weights global -> VGPR (bvgemm.hip) reads its own fragment-major copy
-      static const bool bv_on = tune_env_int("SD_BVGEMM", 1) != 0;
-      if (bv_on && !d.w_ws && bvgemm_wanted(d)) {
-        half_t* wt = arena_.alloc_n<half_t>(bvgemm_tiled_halves(cout, x.C));
-        launch_bvgemm_retile(w, wt, cout, x.C, geglu, stream_);
-        d.w_bv = wt;
-      }
+    if (copies.bvgemm) {    // large-M 1x1 GEMMs: weights global -> VGPR (bvgemm.hip, plan tile 11)
+      half_t* wt = arena_.alloc_n<half_t>(bvgemm_tiled_halves(cout, x.C));
+      launch_bvgemm_retile(w, wt, cout, x.C, geglu, stream_);
+      d.w_bv = wt;
     }
     if (hook) {
       hook->twin_capable = !ex && d.Ho * d.Wo <= 256;

@@ -9,7 +9,7 @@ namespace sd {
 
 // GEGLU (ff.net.0.proj, unet.py:613-617): destination row of output row o of an n-row [values | gates] matrix.  Value and gate
 // channels interleave in blocks of 32, so the GEMM epilogue multiplies them in registers (the device-side twin of this rule is
-// conv_generic_kernel's, igemm.hip).
+// conv_generic_kernel's, conv_small.hip).
 inline int geglu_row(int o, int n) {
   const int half_n = n / 2;
   const bool gate = o >= half_n;

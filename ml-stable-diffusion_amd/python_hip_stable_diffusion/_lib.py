@@ -107,6 +107,7 @@ SYMBOLS = [
     ("sd_op_gn_proj_qkv", _I, [_P, _P, _FP, _FP, _P, _FP, _FP, _FP, _P, _P, _P, _P, _I, _I, _I, _I, _I, C.c_float, C.c_float, C.c_float, _I, _I,
                                C.POINTER(C.c_int), _I, _FP]),
     ("sd_op_timestep_embedding", _I, [_FP, _FP, _I, _I, _I, _F]),
+    ("sd_op_conv_plan", _I, [_I] * 18 + [C.POINTER(C.c_int), C.POINTER(C.c_ulonglong)]),
     ("sd_numpy_randn", _I, [C.c_uint32, C.POINTER(C.c_double), C.c_size_t]),
     ("sd_torch_randn", _I, [C.c_uint32, C.POINTER(C.c_double), C.c_size_t]),
     ("sd_philox_randn", _I, [C.c_uint64, C.c_uint32, C.POINTER(C.c_double), C.c_size_t]),
@@ -439,6 +440,20 @@ def gn_proj_qkv(x_in, conv_w, gn_weight, gn_bias, proj_w, proj_bias, ln_weight, 
                                   fptr(f32(ln_weight)), fptr(f32(ln_bias)), ptr(wqkv), ptr(h), ptr(qk), ptr(vt), B, H, W, Cn, groups, gn_eps,
                                   ln_eps, q_scale, int(vt_perm), int(fused), C.byref(entries), iters, C.byref(ms)))
     return h, qk, vt, entries.value, ms.value
+
+
+def conv_plan(ksize, stride, up, C0, C1, N, B, Ho, Wo, out_mode=0, flags=0, n_trans=0, n_twins=0, gnf_groups=0, tile=0, staging=0, splitk=0,
+              copies=-1):
+    """The plan the library gives a conv / 1x1 GEMM of this shape (sd_op_conv_plan: host only, no GPU).  flags: 1 LayerNorm fold, 2 timestep
+    embedding, 4 residual, 8 GroupNorm statistics, 16 bias, 32 explicit zero padding; copies: bit set of the pre-tiled weight copies that
+    exist (1 wstream, 2 wsgemm, 4 bvgemm), -1 = the ones the library's handle holds.  Returns a dict: tile, staging, splitk, slab,
+    workspace_bytes, copies (wstream, wsgemm, bvgemm)."""
+    plan = (C.c_int * 7)()
+    ws = C.c_ulonglong(0)
+    check(lib().sd_op_conv_plan(ksize, stride, up, C0, C1, N, B, Ho, Wo, out_mode, flags, n_trans, n_twins, gnf_groups, tile, staging, splitk,
+                                copies, plan, C.byref(ws)))
+    return {"tile": plan[0], "staging": plan[1], "splitk": plan[2], "slab": bool(plan[3]), "workspace_bytes": int(ws.value),
+            "copies": (bool(plan[4]), bool(plan[5]), bool(plan[6]))}
 
 
 def timestep_embedding(t, dim, flip_sin_to_cos=True, freq_shift=0.0):

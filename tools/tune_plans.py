@@ -91,7 +91,7 @@ for key, b_ms in sorted(base.items(), key=lambda kv: -kv[1]):
     total_best += b_ms
     report[key] = {"base_ms": b_ms, "best_ms": b_ms, "plan": None}
 with open(out_table, "w") as f:
-    f.write("// Plan table: {kind, ksize, stride, up, Ctot, N, M, tile, staging, splitk}  (kind / staging: igemm.hip choose_plan,\n"
+    f.write("// Plan table: {kind, ksize, stride, up, Ctot, N, M, tile, staging, splitk}  (kind / staging: conv_plan.cpp choose_plan,\n"
             "// launch_tile).  Measured IN SEQUENCE on MI355X by tools/tune_plans.py (per-op HIP events of the eager\n"
             "// CFG-batch-%d step of %s at %dx%d latents, caches as cold as in the step): entries beat the previous plan by > 3 %%.\n"
             % (B, WHICH, HW, HW))
