@@ -398,6 +398,49 @@ int sd_calibrate(int device, float* out9);
  * layout matches what the kernels assume). */
 int sd_selftest_mfma(void);
 
+/* ------------------------------------------------------------------------------------------
+ * Safety checker: diffusers' StableDiffusionSafetyChecker (transformers' CLIPVisionModel ViT-L/14, visual_projection and
+ * the concept head) as the reference converts it (torch2coreml.py:1119-1309, the head's vectorised forward :1177-1209) and
+ * runs it on every generated image (pipeline.py:286-311, step 9 at :578; SafetyChecker.swift; `disableSafety` of the Swift
+ * configuration).  Static batch like every model.  Weights use the key names diffusers writes
+ * (vision_model.vision_model.embeddings.* / .pre_layrnorm.* (sic) / .encoder.layers.N.* / .post_layernorm.*,
+ * visual_projection.weight, concept_embeds, special_care_embeds, concept_embeds_weights, special_care_embeds_weights);
+ * a single `vision_model.` prefix is accepted too.  A missing key is SD_ERR_NOT_FOUND, a wrong shape or bad config
+ * SD_ERR_INVALID_ARGUMENT, a head dim other than 64 SD_ERR_UNSUPPORTED - all before any device work.
+ * `filtered_images` (torch2coreml.py:1203-1207) is deliberately NOT part of this ABI: the images are on the host at that
+ * point (pipeline.py:286-311), blackening a flagged one is a host memset, done by the Python wrapper.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct sd_safety_checker_config {
+  int32_t batch, image_size /*224*/, patch_size /*14*/, hidden_size, intermediate_size,
+          num_hidden_layers, num_attention_heads, projection_dim, num_concepts /*17*/,
+          num_special /*3*/, hidden_act /*0 quick_gelu, 1 gelu*/;
+  float layer_norm_eps;
+  int32_t use_graph;
+} sd_safety_checker_config;
+typedef struct sd_safety_checker sd_safety_checker;
+/* replaces the load of the converted safety_checker model (pipeline.py:650-656 in get_coreml_pipe; SafetyChecker.swift:21-33) */
+int sd_safety_checker_create(const sd_safety_checker_config* cfg, const sd_weights* w, int device, sd_safety_checker** out);
+void sd_safety_checker_destroy(sd_safety_checker* c);
+size_t sd_safety_checker_device_bytes(const sd_safety_checker* c);
+/* replaces `safety_checker(clip_input=, images=, adjustment=)` (pipeline.py:293-304; SafetyChecker.swift:55-99 isSafe).
+ * clip_input (B,3,I,I) f16 (a device pointer with SD_FLAG_DEVICE_PTRS); outputs f32 on the host, each may be NULL: has_nsfw (B)
+ * 0 / 1, concept_scores (B,num_concepts), image_embeds (B,projection_dim), last_hidden_state (B,S,hidden) BEFORE
+ * post_layernorm (transformers' meaning of the name) */
+int sd_safety_checker_run(sd_safety_checker* c, const void* clip_input, float adjustment, float* has_nsfw,
+                          float* concept_scores, float* image_embeds, float* last_hidden_state, int flags);
+/* Measurement hook (no reference counterpart): HIP-event milliseconds of the launch list of the last sd_safety_checker_run - the
+ * graph replay, or the eager launches - without the copies in front of and behind it; 0 before the first run. */
+float sd_safety_checker_last_ms(const sd_safety_checker* c);
+/* operator-level entries, same conventions as the other sd_op_*.
+ * CLIPAttention of the vision tower (no mask), head dim 64 only (else SD_ERR_UNSUPPORTED): qkv (B*S, 3*heads*d) f16 rows
+ * [q | k | v] as the stacked projection writes them -> out (B*S, heads*d) f16; any S >= 1. */
+int sd_op_vit_attention(const void* qkv, void* out, int B, int S, int heads, int d, int iters, float* ms);
+/* the concept head (torch2coreml.py:1177-1209), all f32: image_embeds (B,P), concept_embeds (n_concepts,P), special_embeds
+ * (n_special,P), thresholds concept_w / special_w -> has_nsfw (B) 0 / 1, concept_scores (B,n_concepts) */
+int sd_op_safety_head(const float* image_embeds, const float* concept_embeds, const float* special_embeds,
+                      const float* concept_w, const float* special_w, float adjustment, int B, int P,
+                      int n_concepts, int n_special, float* has_nsfw, float* concept_scores);
+
 #ifdef __cplusplus
 }
 #endif

@@ -971,4 +971,51 @@ int sd_op_timestep_embedding(const float* t, float* out, int n, int dim, int fli
   });
 }
 
+// The safety checker's attention (vit.hip) on the layout its handle feeds it: qkv (B * S, 3 * heads * d) f16 rows [q | k | v] ->
+// out (B * S, heads * d) f16.  The device output sits in front of a guard of 64 rows; both are filled with NaN patterns before the
+// launch, and a launch that wrote into the guard fails the call.
+int sd_op_vit_attention(const void* qkv, void* out, int B, int S, int heads, int d, int iters, float* ms) {
+  return guarded([&] {
+    SD_REQUIRE(qkv && out, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(B > 0 && S > 0 && heads > 0 && d > 0, kInvalidArgument, "empty attention problem");
+    SD_REQUIRE(vit_attention_ok(d), kUnsupported, "vit_attention: head dim %d (the kernel is built for 64)", d);
+    Scratch sc;
+    const int D = heads * d;
+    const size_t n = (size_t)B * S * D, guard = (size_t)64 * D;
+    half_t* dq = sc.dev<half_t>((size_t)B * S * 3 * D, f16(qkv));
+    half_t* dout = sc.dev<half_t>(n + guard);
+    SD_HIP(hipMemset(dout, 0xff, (n + guard) * sizeof(half_t)));   // 0xffff: a NaN
+    sc.timed(iters, ms, [&] { launch_vit_attention(dq, dout, B, S, heads, d, sc.stream); });
+    SD_HIP(hipStreamSynchronize(sc.stream));
+    std::vector<uint16_t> g(guard);
+    SD_HIP(hipMemcpy(g.data(), dout + n, guard * sizeof(half_t), hipMemcpyDeviceToHost));
+    for (uint16_t v : g) SD_REQUIRE(v == 0xffff, kInternal, "vit_attention wrote behind its %d output rows", B * S);
+    SD_HIP(hipMemcpy(out, dout, n * sizeof(half_t), hipMemcpyDeviceToHost));
+  });
+}
+
+// The safety checker's concept head (vit.hip safety_head_kernel) on host fp32 arrays
+int sd_op_safety_head(const float* image_embeds, const float* concept_embeds, const float* special_embeds, const float* concept_w,
+                      const float* special_w, float adjustment, int B, int P, int n_concepts, int n_special, float* has_nsfw,
+                      float* concept_scores) {
+  return guarded([&] {
+    SD_REQUIRE(image_embeds && concept_embeds && concept_w && has_nsfw && concept_scores, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(B > 0 && P > 0 && n_concepts > 0 && n_special >= 0 && (n_special == 0 || (special_embeds && special_w)), kInvalidArgument,
+               "safety_head: B=%d P=%d concepts=%d special=%d", B, P, n_concepts, n_special);
+    Scratch sc;
+    float* di = sc.dev<float>((size_t)B * P, image_embeds);
+    float* dc = sc.dev<float>((size_t)n_concepts * P, concept_embeds);
+    float* dcw = sc.dev<float>(n_concepts, concept_w);
+    float* ds = n_special ? sc.dev<float>((size_t)n_special * P, special_embeds) : nullptr;
+    float* dsw = n_special ? sc.dev<float>(n_special, special_w) : nullptr;
+    float* dadj = sc.dev<float>(1, &adjustment);
+    float* dflag = sc.dev<float>(B);
+    float* dscore = sc.dev<float>((size_t)B * n_concepts);
+    launch_safety_head(di, dc, ds, dcw, dsw, dadj, B, P, n_concepts, n_special, dflag, dscore, sc.stream);
+    SD_HIP(hipStreamSynchronize(sc.stream));
+    SD_HIP(hipMemcpy(has_nsfw, dflag, (size_t)B * sizeof(float), hipMemcpyDeviceToHost));
+    SD_HIP(hipMemcpy(concept_scores, dscore, (size_t)B * n_concepts * sizeof(float), hipMemcpyDeviceToHost));
+  });
+}
+
 }  // extern "C"

@@ -317,6 +317,27 @@ int launch_ffn_proj(const FfnProjDesc& d, hipStream_t s);
 void launch_xattn_out_retile_nk(const half_t* w, half_t* wt, int N, int K, hipStream_t s);   // [N][K] row-major -> fragment-major
 
 // ---------------------------------------------------------------------------------------------
+// CLIP towers: what the text encoder and the safety checker's vision tower share (clip.hip), and the vision tower's own kernels (vit.hip)
+// ---------------------------------------------------------------------------------------------
+// in-place MLP activation over n halves: 0 = quick_gelu x * sigmoid(1.702 x), 1 = exact-erf gelu
+void launch_clip_act(half_t* x, size_t n, int act, hipStream_t s);
+// Non-causal attention over the stacked projection's rows: qkv [B * S][3 * heads * d] = [q | k | v] -> out [B * S][heads * d], one
+// workgroup per (batch, head, 64 queries), any S >= 1, d^-0.5 applied in fp32 inside; d must be 64 (else kUnsupported)
+bool vit_attention_ok(int d);
+void launch_vit_attention(const half_t* qkv, half_t* out, int B, int S, int heads, int d, hipStream_t s);
+// img (B, 3, I, I) NCHW -> rows [B * (I / p)^2][Kp], column c * p * p + py * p + px (the flattened conv weight's order), columns
+// [3 p p, Kp) zero: the patch-embedding conv becomes a 1x1 GEMM over these rows
+void launch_vit_patch_rows(const half_t* img, half_t* rows, int B, int I, int p, int Kp, hipStream_t s);
+// x [B][S][D]: row 0 = cls + pos[0], row 1 + j = patch[b][j] + pos[1 + j]   (patch [B][S - 1][D], cls [D], pos [S][D])
+void launch_vit_tokens(const half_t* patch, const half_t* cls, const half_t* pos, half_t* x, int B, int S, int D, hipStream_t s);
+// The safety checker's concept head, fp32 (vit.hip safety_head_kernel): image_embeds [B][P], concept_embeds [n_concepts][P],
+// special_embeds [n_special][P], thresholds concept_w / special_w, adjustment = ONE float in device memory (a handle changes it between
+// replays of its captured graph) -> has_nsfw [B] (0 / 1), concept_scores [B][n_concepts]
+void launch_safety_head(const float* image_embeds, const float* concept_embeds, const float* special_embeds, const float* concept_w,
+                        const float* special_w, const float* adjustment, int B, int P, int n_concepts, int n_special, float* has_nsfw,
+                        float* concept_scores, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------
 // K6/K7: norms (norm.hip)
 // ---------------------------------------------------------------------------------------------
 // y[m][:] = (x[m][:]-mean)*rstd * w + b over the channel dim (LayerNormANE, layer_norm.py:51-80)

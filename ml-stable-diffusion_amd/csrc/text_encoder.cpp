@@ -14,7 +14,6 @@ namespace sd {
 
 void launch_clip_embed(const int* ids, const half_t* tok, const half_t* pos, half_t* x, int S, int D, int vocab, hipStream_t s);
 void launch_clip_attention(const half_t* qkv, half_t* out, int S, int D, int heads, hipStream_t s);
-void launch_clip_act(half_t* x, size_t n, int act, hipStream_t s);
 
 class TextEncoder {
  public:

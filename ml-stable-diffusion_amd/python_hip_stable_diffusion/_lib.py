@@ -53,6 +53,14 @@ class UNetIO(C.Structure):
     ]
 
 
+class SafetyCheckerConfig(C.Structure):
+    """sd_safety_checker_config: thirteen 4-byte members, no padding."""
+    _fields_ = [("batch", C.c_int32), ("image_size", C.c_int32), ("patch_size", C.c_int32), ("hidden_size", C.c_int32),
+                ("intermediate_size", C.c_int32), ("num_hidden_layers", C.c_int32), ("num_attention_heads", C.c_int32),
+                ("projection_dim", C.c_int32), ("num_concepts", C.c_int32), ("num_special", C.c_int32), ("hidden_act", C.c_int32),
+                ("layer_norm_eps", C.c_float), ("use_graph", C.c_int32)]
+
+
 _lib = None
 
 # every symbol include/sd_mi355x.h declares: (name, restype, argtypes)
@@ -113,6 +121,13 @@ SYMBOLS = [
     ("sd_philox_randn", _I, [C.c_uint64, C.c_uint32, C.POINTER(C.c_double), C.c_size_t]),
     ("sd_calibrate", _I, [_I, _FP]),
     ("sd_selftest_mfma", _I, []),
+    ("sd_safety_checker_create", _I, [C.POINTER(SafetyCheckerConfig), _P, _I, C.POINTER(_P)]),
+    ("sd_safety_checker_destroy", None, [_P]),
+    ("sd_safety_checker_device_bytes", C.c_size_t, [_P]),
+    ("sd_safety_checker_last_ms", C.c_float, [_P]),
+    ("sd_safety_checker_run", _I, [_P, _P, _F, _FP, _FP, _FP, _FP, _I]),
+    ("sd_op_vit_attention", _I, [_P, _P, _I, _I, _I, _I, _I, _FP]),
+    ("sd_op_safety_head", _I, [_FP, _FP, _FP, _FP, _FP, _F, _I, _I, _I, _I, _FP, _FP]),
 ]
 
 
@@ -183,6 +198,40 @@ def attention(impl, q, k, v, heads, dim_head, variant=0, iters=1):
     check(lib().sd_op_attention(ATTENTION_IMPLEMENTATIONS[impl], ptr(q), ptr(k), ptr(v), ptr(out), B, heads,
                                 dim_head, Sq, Sk, variant, iters, C.byref(ms)))
     return out, ms.value
+
+
+def vit_attention(qkv, heads, dim_head=64, out=None, iters=1):
+    """Non-causal attention of the safety checker's vision tower (csrc/vit.hip).  qkv (B, S, 3 * heads * dim_head) f16, rows
+    [q | k | v] as the stacked projection writes them -> (B, S, heads * dim_head) f16, ms.  ``out``: a C-contiguous float16 buffer of
+    at least B * S * heads * dim_head elements to write into (tests put a guard behind it)."""
+    qkv = f16(qkv)
+    if qkv.ndim != 3 or qkv.shape[2] != 3 * heads * dim_head:
+        raise ValueError("vit_attention: qkv must be (B, S, 3 * heads * dim_head)")
+    B, S, _ = qkv.shape
+    n = B * S * heads * dim_head
+    if out is None:
+        out = np.empty(n, np.float16)
+    if out.dtype != np.float16 or not out.flags.c_contiguous or out.size < n:
+        raise ValueError("vit_attention: out must be a C-contiguous float16 buffer of at least B * S * heads * dim_head elements")
+    ms = C.c_float(0)
+    check(lib().sd_op_vit_attention(ptr(qkv), ptr(out), B, S, heads, dim_head, iters, C.byref(ms)))
+    return out.reshape(-1)[:n].reshape(B, S, heads * dim_head), ms.value
+
+
+def safety_head(image_embeds, concept_embeds, special_embeds, concept_w, special_w, adjustment=0.0):
+    """The safety checker's concept head (torch2coreml.py:1177-1209) in fp32 on the GPU.  Returns (has_nsfw (B,) bool,
+    concept_scores (B, n_concepts) f32)."""
+    image_embeds, concept_embeds, special_embeds = f32(image_embeds), f32(concept_embeds), f32(special_embeds)
+    concept_w, special_w = f32(concept_w), f32(special_w)
+    B, P = image_embeds.shape
+    nc, ns = concept_embeds.shape[0], special_embeds.shape[0]
+    if concept_embeds.shape != (nc, P) or special_embeds.shape != (ns, P) or concept_w.shape != (nc,) or special_w.shape != (ns,):
+        raise ValueError("safety_head: inconsistent shapes")
+    flags = np.empty(B, np.float32)
+    scores = np.empty((B, nc), np.float32)
+    check(lib().sd_op_safety_head(fptr(image_embeds), fptr(concept_embeds), fptr(special_embeds), fptr(concept_w), fptr(special_w),
+                                  float(adjustment), B, P, nc, ns, fptr(flags), fptr(scores)))
+    return flags > 0.5, scores
 
 
 def layernorm(x, weight, bias, eps=1e-5, iters=1):

@@ -58,6 +58,8 @@ class HipStableDiffusionPipeline:
         self.aesthetic_score, self.negative_aesthetic_score = aesthetic_score, negative_aesthetic_score
         if safety_checker is None:
             logger.warning("safety checker disabled for %s", type(self).__name__)
+        elif feature_extractor is None:                                              # pipeline.py:288 needs it
+            raise ValueError("a safety checker needs the checkpoint's feature extractor (CLIPImageProcessor) for its input")
         # static shapes come from the model, like the reference (pipeline.py:104-117)
         self.unet.in_channels = self.unet.expected_inputs["sample"]["shape"][1]
         latent_h, latent_w = self.unet.expected_inputs["sample"]["shape"][2:]
@@ -126,10 +128,26 @@ class HipStableDiffusionPipeline:
             total = out if total is None else {k: total[k] + v for k, v in out.items()}
         return {k: v.astype(np.float16) for k, v in total.items()}
 
+    # ---- pipeline.py:286-311 ---------------------------------------------------------------
     def run_safety_checker(self, image):
         if self.safety_checker is None:
             return image, None
-        raise NotImplementedError("safety checker is outside the MI355X hot path (SURVEY.md section 8)")
+        clip_input = self.feature_extractor(self.numpy_to_pil(image), return_tensors="np").pixel_values.astype(np.float16)
+        sb = self.safety_checker.expected_inputs["clip_input"]["shape"][0]
+        # the checker handle has a static batch like every model (pipeline.py:112-114): feed it in slices
+        if image.shape[0] % sb:
+            raise ValueError(f"{image.shape[0]} images do not fill the safety checker's static batch of {sb}")
+        outs = [self.safety_checker(clip_input=np.ascontiguousarray(clip_input[i:i + sb]),
+                                    images=np.ascontiguousarray(image[i:i + sb]).astype(np.float16),
+                                    adjustment=np.array([0.]).astype(np.float16))    # defaults to 0 in the original pipeline
+                for i in range(0, image.shape[0], sb)]
+        has_nsfw = np.concatenate([np.asarray(o["has_nsfw_concepts"]).reshape(-1) for o in outs])
+        # filtered_images without the detour through the checker's float16 input: unflagged images stay bit for bit what the
+        # VAE produced, flagged ones are zeroed like the model's output
+        filtered = image.copy()
+        filtered[has_nsfw.astype(bool)] = 0
+        logger.info("Generated image has nsfw concept=%s", bool(has_nsfw.any()))
+        return filtered, has_nsfw
 
     # ---- pipeline.py:313-320 ---------------------------------------------------------------
     def decode_latents(self, latents):
@@ -346,10 +364,10 @@ class HipStableDiffusionPipeline:
                     callback(i, t, latents)
 
         if output_type == "latent" or self.vae_decoder is None:
-            image = latents
+            image, has_nsfw = latents, None                  # the checker looks at images only
         else:
             image = self.decode_latents(latents)
-        image, has_nsfw = self.run_safety_checker(image)
+            image, has_nsfw = self.run_safety_checker(image)
         if output_type == "pil" and image.ndim == 4 and image.shape[-1] == 3:
             image = self.numpy_to_pil(image)
         if not return_dict:
@@ -407,7 +425,7 @@ def checkpoint_scheduler_config(model_dir):
 def get_hip_pipe(model_dir, model_version, compute_unit="ALL", scheduler_override=None, controlnet_models=None,
                  force_zeros_for_empty_prompt=True, sources=None, attention_implementation="SPLIT_EINSUM",
                  num_images=1, guidance_scale=7.5, unet_batch_one=False, latent_size=None, device=0,
-                 refiner_dir=None, tokenizer_factory=None, text_encoder_factory=None, vae_dtype=None):
+                 refiner_dir=None, tokenizer_factory=None, text_encoder_factory=None, vae_dtype=None, disable_safety=False):
     """``get_coreml_pipe`` (pipeline.py:607-697) without the conversion step: ``model_dir`` is a diffusers
     checkpoint directory (``unet/``, ``vae/``, ``text_encoder/``, ``tokenizer/``, ``scheduler/`` [,
     ``text_encoder_2/``, ``tokenizer_2/``]) instead of a folder of ``.mlpackage`` files; ControlNets are
@@ -415,7 +433,9 @@ def get_hip_pipe(model_dir, model_version, compute_unit="ALL", scheduler_overrid
     (pipeline.py:112-114) are fixed here: UNet batch = (2 if guidance_scale > 1 else 1) * num_images.
     ``vae_dtype``: compute precision of the VAE decoder; default = the reference's conversion rule (torch2coreml.py:570-578):
     float32 for an SDXL checkpoint's own VAE (it overflows fp16), float16 otherwise; pass ``np.float16`` for an
-    fp16-safe replacement VAE (``--custom-vae-version``)."""
+    fp16-safe replacement VAE (``--custom-vae-version``).
+    ``disable_safety``: do not load ``model_dir/safety_checker/`` (pipeline.py:650-656; ``disableSafety`` of the Swift
+    configuration); a checkpoint directory without one runs unchecked either way."""
     if not os.path.isdir(model_dir):
         raise FileNotFoundError(f"{model_dir} not found (coreml_model.py:176-178)")
     from . import text_encoder as te
@@ -471,6 +491,12 @@ def get_hip_pipe(model_dir, model_version, compute_unit="ALL", scheduler_overrid
     else:
         kwargs["tokenizer"] = make_tok(os.path.join(model_dir, "tokenizer"))
         kwargs["text_encoder"] = make_enc(os.path.join(model_dir, "text_encoder"))
+    if not disable_safety and os.path.isdir(os.path.join(model_dir, "safety_checker")):
+        from .safety_checker import HipSafetyChecker, load_feature_extractor
+        kwargs["feature_extractor"] = load_feature_extractor(os.path.join(model_dir, "feature_extractor"))
+        kwargs["safety_checker"] = HipSafetyChecker.from_pretrained(
+            os.path.join(model_dir, "safety_checker"), batch=1, device=device,
+            image_height=lat * VAE_DECODER_UPSAMPLE_FACTOR, image_width=kwargs["unet"].latent_width * VAE_DECODER_UPSAMPLE_FACTOR)
     logger.info("Initializing HIP pipe for image generation")
     return HipStableDiffusionPipeline(scheduler=scheduler, **kwargs)
 
@@ -532,6 +558,8 @@ def build_parser():
                         help="Accepted for compatibility and ignored (there is no conversion step).")
     parser.add_argument("--attention-implementation", choices=tuple(_lib.ATTENTION_IMPLEMENTATIONS), default="SPLIT_EINSUM",
                         help="Attention schedule of the UNet kernels (a conversion-time flag in the reference).")
+    parser.add_argument("--disable-safety", action="store_true",
+                        help="Do not run the checkpoint's safety checker on the generated images (swift CLI --disable-safety).")
     parser.add_argument("--refiner", default=None, help="SDXL: diffusers directory of the refiner checkpoint")
     parser.add_argument("--rng", choices=("numpy", "torch", "nvidia"), default="numpy",
                         help="Seed-exact random source of the initial latents (swift/StableDiffusionCLI/main.swift --rng): "
@@ -553,7 +581,8 @@ def main(args):
     pipe = get_hip_pipe(args.i, args.model_version, args.compute_unit, scheduler_override=scheduler,
                         controlnet_models=args.controlnet, force_zeros_for_empty_prompt=force_zeros,
                         sources=args.model_sources, attention_implementation=args.attention_implementation,
-                        guidance_scale=args.guidance_scale, unet_batch_one=args.unet_batch_one, refiner_dir=args.refiner)
+                        guidance_scale=args.guidance_scale, unet_batch_one=args.unet_batch_one, refiner_dir=args.refiner,
+                        disable_safety=getattr(args, "disable_safety", False))
     controlnet_cond = None
     if args.controlnet:
         controlnet_cond = [prepare_controlnet_cond(args.controlnet_inputs[i], pipe.height, pipe.width)
