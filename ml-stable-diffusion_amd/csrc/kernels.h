@@ -321,6 +321,9 @@ void launch_xattn_out_retile_nk(const half_t* w, half_t* wt, int N, int K, hipSt
 // ---------------------------------------------------------------------------------------------
 // in-place MLP activation over n halves: 0 = quick_gelu x * sigmoid(1.702 x), 1 = exact-erf gelu
 void launch_clip_act(half_t* x, size_t n, int act, hipStream_t s);
+// the text encoder's own two (clip.hip): x[s] = tok[ids[s]] + pos[s], and causal attention over qkv [S][3 D] -> out [S][D]
+void launch_clip_embed(const int* ids, const half_t* tok, const half_t* pos, half_t* x, int S, int D, int vocab, hipStream_t s);
+void launch_clip_attention(const half_t* qkv, half_t* out, int S, int D, int heads, hipStream_t s);
 // Non-causal attention over the stacked projection's rows: qkv [B * S][3 * heads * d] = [q | k | v] -> out [B * S][heads * d], one
 // workgroup per (batch, head, 64 queries), any S >= 1, d^-0.5 applied in fp32 inside; d must be 64 (else kUnsupported)
 bool vit_attention_ok(int d);

@@ -37,13 +37,7 @@ UNet::UNet(const sd_unet_config& cfg, const WeightStore& ws, int device) : cfg_(
   SD_REQUIRE(cfg.batch >= 1 && cfg.height >= 1 && cfg.width >= 1, kInvalidArgument, "bad batch/size");
   SD_REQUIRE(cfg.norm_num_groups >= 1 && cfg.norm_num_groups <= 64, kUnsupported, "norm_num_groups=%d",
              cfg.norm_num_groups);
-  int ndev = 0;
-  SD_HIP(hipGetDeviceCount(&ndev));
-  SD_REQUIRE(ndev > 0, kHipError, "no HIP device visible: libsdmi355 has no CPU fallback");
-  SD_REQUIRE(device >= 0 && device < ndev, kInvalidArgument, "device %d out of range (%d visible)", device, ndev);
-  SD_HIP(hipSetDevice(device));
-  SD_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-  device_zero_chunk();   // the conv launches only read it (never first allocated under graph capture)
+  stream_ = open_device(device);
   if (tune_env_int("SD_SIDE_TIME", 0) != 0) {
     SD_HIP(hipStreamCreateWithFlags(&side_, hipStreamNonBlocking));
     SD_HIP(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming));
@@ -1484,7 +1478,7 @@ void UNet::run_vae_graph() {
     if (!graph_) {
       run_ops(main_ops_);
       SD_HIP(hipStreamSynchronize(stream_));
-      graph_ = capture([&] { run_ops(main_ops_); });
+      graph_ = capture_graph(stream_, [&] { run_ops(main_ops_); });
     }
     SD_HIP(hipGraphLaunch(graph_, stream_));
   } else {
@@ -1631,26 +1625,6 @@ void UNet::run_ops_on(const std::vector<Op>& ops, hipStream_t s) {
     if (poison) launch_lds_poison(s);
     op(s);
   }
-}
-
-// Stream capture that cannot leave the stream in capture mode: an op that throws between Begin and
-// End (SD_HIP / SD_REQUIRE inside a launch) ends and discards the capture before the error travels on.
-hipGraphExec_t UNet::capture(const std::function<void()>& body) {
-  SD_HIP(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
-  hipGraph_t g = nullptr;
-  try {
-    body();
-  } catch (...) {
-    (void)hipStreamEndCapture(stream_, &g);
-    if (g) (void)hipGraphDestroy(g);
-    throw;
-  }
-  SD_HIP(hipStreamEndCapture(stream_, &g));
-  hipGraphExec_t exec = nullptr;
-  const hipError_t e = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(g);
-  SD_REQUIRE(e == hipSuccess, kHipError, "hipGraphInstantiate failed: %s", hipGetErrorString(e));
-  return exec;
 }
 
 namespace {
@@ -1863,7 +1837,7 @@ void UNet::ensure_graph() {
   // first run eagerly (sets kernel attributes, warms code objects), then capture
   run_forward_ops();
   SD_HIP(hipStreamSynchronize(stream_));
-  graph_ = capture([&] { run_forward_ops(); });
+  graph_ = capture_graph(stream_, [&] { run_forward_ops(); });
 }
 
 void UNet::forward(const sd_unet_io& io) {
@@ -2061,7 +2035,7 @@ void UNet::denoise_loop(const sd_unet_io& io, float* latents, int n_images, int 
         run_time_and_main();
         SD_HIP(hipStreamSynchronize(stream_));
       }
-      loop_graph_ = capture(step_ops);
+      loop_graph_ = capture_graph(stream_, step_ops);
       loop_graph_key_ = full_key;
     }
   }

@@ -1,11 +1,8 @@
 // Host-side builder/executor of the UNet (and ControlNet) launch graph.
 // Spec: python_coreml_stable_diffusion/unet.py:798-1152, controlnet.py:49-250.
 #pragma once
-#include <functional>
-
 #include "../../include/sd_mi355x.h"
-#include "kernels.h"
-#include "weights.h"
+#include "launch_list.h"
 
 namespace sd {
 
@@ -58,17 +55,6 @@ struct PreQkv {
   half_t* vt = nullptr;    // [B][C][round_up(S, 8)]
   bool vt_perm = false;    // V^T in attention8's key order
   bool q_pre = false;      // queries carry d^-0.5 * log2(e)
-};
-
-// One entry of a handle's launch list: the launch closure plus what the per-op profile reports about it.
-struct Op {
-  std::function<void(hipStream_t)> fn;
-  std::string label;   // "<kind> <shape> <checkpoint name>"
-  double flop = 0;     // algorithmic FLOP (2 per MAC) of MFMA ops, 0 for bandwidth ops
-  Op() = default;
-  template <class F, class = std::enable_if_t<!std::is_same<std::decay_t<F>, Op>::value>>
-  Op(F&& f) : fn(std::forward<F>(f)) {}
-  void operator()(hipStream_t s) const { fn(s); }
 };
 
 struct OpTime {
@@ -171,7 +157,6 @@ class UNet {
   void set_context_from(const half_t* ehs_dev, hipStream_t s);
   void run_attached();
   void invalidate_graphs();
-  hipGraphExec_t capture(const std::function<void()>& body);
   void run_forward_ops();
   void run_time_and_main();   // time_ops_ (optionally on the forked side stream) + main_ops_
   void run_main(bool with_time);   // main_ops_ [behind time_ops_] with the joins of the forked time path / ControlNets in place

@@ -61,6 +61,15 @@ class SafetyCheckerConfig(C.Structure):
                 ("layer_norm_eps", C.c_float), ("use_graph", C.c_int32)]
 
 
+class TextEncoderConfig(C.Structure):
+    _fields_ = [("vocab_size", C.c_int32), ("hidden_size", C.c_int32), ("intermediate_size", C.c_int32),
+                ("num_hidden_layers", C.c_int32), ("num_attention_heads", C.c_int32),
+                ("max_position_embeddings", C.c_int32), ("hidden_act", C.c_int32), ("projection_dim", C.c_int32),
+                ("layer_norm_eps", C.c_float), ("use_graph", C.c_int32)]
+
+
+ACTS = {"quick_gelu": 0, "gelu": 1}      # hidden_act of the two CLIP towers' configs (launch_clip_act)
+
 _lib = None
 
 # every symbol include/sd_mi355x.h declares: (name, restype, argtypes)
@@ -162,6 +171,55 @@ def check(status):
     if status != 0:
         msg = lib().sd_last_error().decode("utf-8", "replace")
         raise _EXC.get(status, RuntimeError)(msg)
+
+
+class Handle:
+    """Owner of one library handle ``_h``, freed by the entry point ``_destroy`` names."""
+    _destroy = None
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(lib(), self._destroy)(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def verify_inputs(expected, **kwargs):
+    """coreml_model.py:97-116: TypeError for a wrong type / dtype / shape, ValueError for an unknown or missing keyword."""
+    for k, v in kwargs.items():
+        if k not in expected:
+            raise ValueError(f"Received unexpected input kwarg: {k}")
+        if not isinstance(v, np.ndarray):
+            raise TypeError(f"Expected numpy.ndarray, got {v} for input: {k}")
+        if v.dtype != expected[k]["dtype"]:
+            raise TypeError(f"Expected dtype {expected[k]['dtype']}, got {v.dtype} for input: {k}")
+        if v.shape != expected[k]["shape"]:
+            raise TypeError(f"Expected shape {expected[k]['shape']}, got {v.shape} for input: {k}")
+    missing = [k for k in expected if k not in kwargs]
+    if missing:
+        raise ValueError(f"Missing input kwargs: {missing}")
+
+
+class Model(Handle):
+    """A model runner behind the CoreMLModel interface: ``expected_inputs`` is what ``__call__`` accepts."""
+
+    def _verify_inputs(self, **kwargs):
+        verify_inputs(self.expected_inputs, **kwargs)
+
+
+def checkpoint_file(folder):
+    """The .safetensors file of one model folder of a diffusers checkpoint, the fp16 variant first."""
+    if not os.path.isdir(folder):
+        raise FileNotFoundError(f"{folder} not found (coreml_model.py:176-178)")
+    for name in ("model.fp16.safetensors", "model.safetensors"):
+        if os.path.exists(os.path.join(folder, name)):
+            return os.path.join(folder, name)
+    raise FileNotFoundError(f"no .safetensors checkpoint under {folder}")
 
 
 def ptr(a):

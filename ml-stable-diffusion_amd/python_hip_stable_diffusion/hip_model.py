@@ -10,6 +10,7 @@ Core ML models declare (torch2coreml.py:135).  Behind it sits ``libsdmi355.so`` 
 for a .mlpackage (pipeline.py:112-114).  The attention implementation, a conversion-time flag
 in the reference (torch2coreml.py:1678-1685 -> unet.py:39), is a per-handle run-time switch.
 """
+import contextlib
 import ctypes as C
 import logging
 import time
@@ -92,8 +93,9 @@ def _fill(arr, values):
         arr[i] = int(v)
 
 
-class Weights:
+class Weights(_lib.Handle):
     """Owns an ``sd_weights`` store (checkpoint tensors keyed by diffusers names)."""
+    _destroy = "sd_weights_destroy"
 
     def __init__(self, tensors=None, safetensors_path=None, prefix=None):
         self._h = C.c_void_p()
@@ -118,20 +120,24 @@ class Weights:
     def __len__(self):
         return _lib.lib().sd_weights_count(self._h)
 
-    def close(self):
-        if self._h:
-            _lib.lib().sd_weights_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
+    @classmethod
+    @contextlib.contextmanager
+    def lend(cls, weights):
+        """``weights`` as a store for one ``create`` call: a ``Weights`` passes through and stays open; a .safetensors path
+        or a {name: array} dict is loaded into a store that is closed behind the call."""
+        if isinstance(weights, cls):
+            yield weights
+            return
+        store = cls(safetensors_path=weights) if isinstance(weights, (str, bytes)) else cls(tensors=weights)
         try:
-            self.close()
-        except Exception:
-            pass
+            yield store
+        finally:
+            store.close()
 
 
-class HipModel:
+class HipModel(_lib.Model):
     """UNet / control-UNet / ControlNet on one MI355X behind the CoreMLModel interface."""
+    _destroy = "sd_unet_destroy"
 
     def __init__(self, config, weights, kind="unet", batch=2, latent_height=None, latent_width=None,
                  attention_implementation="SPLIT_EINSUM", device=0, use_graph=True, context_len=77):
@@ -175,15 +181,9 @@ class HipModel:
         c.attention_impl = _lib.ATTENTION_IMPLEMENTATIONS[attention_implementation]
         c.use_graph = int(use_graph)
         self._cfg_struct = c
-        own = not isinstance(weights, Weights)
-        wstore = weights if not own else (Weights(safetensors_path=weights) if isinstance(weights, (str, bytes))
-                                          else Weights(tensors=weights))
         self._h = C.c_void_p()
-        try:
-            _lib.check(_lib.lib().sd_unet_create(C.byref(c), wstore._h, device, C.byref(self._h)))
-        finally:
-            if own:
-                wstore.close()
+        with Weights.lend(weights) as store:
+            _lib.check(_lib.lib().sd_unet_create(C.byref(c), store._h, device, C.byref(self._h)))
         self.batch, self.latent_height, self.latent_width = batch, h, w
         self.attention_implementation = attention_implementation
         self.num_residuals = _lib.lib().sd_unet_num_residuals(self._h)
@@ -219,24 +219,6 @@ class HipModel:
                 shapes.append((batch, boc[i], h, w))
         shapes.append((batch, boc[-1], h, w))
         return shapes
-
-    # coreml_model.py:97-116
-    def _verify_inputs(self, **kwargs):
-        for k, v in kwargs.items():
-            if k in self.expected_inputs:
-                if not isinstance(v, np.ndarray):
-                    raise TypeError(f"Expected numpy.ndarray, got {v} for input: {k}")
-                expected_dtype = self.expected_inputs[k]["dtype"]
-                if not v.dtype == expected_dtype:
-                    raise TypeError(f"Expected dtype {expected_dtype}, got {v.dtype} for input: {k}")
-                expected_shape = self.expected_inputs[k]["shape"]
-                if not v.shape == expected_shape:
-                    raise TypeError(f"Expected shape {expected_shape}, got {v.shape} for input: {k}")
-            else:
-                raise ValueError(f"Received unexpected input kwarg: {k}")
-        missing = [k for k in self.expected_inputs if k not in kwargs]
-        if missing:
-            raise ValueError(f"Missing input kwargs: {missing}")
 
     def _io(self, kwargs, keep):
         io = _lib.UNetIO()
@@ -300,18 +282,7 @@ class HipModel:
             raise ValueError("denoise_loop needs a UNet handle")
         loop_inputs = {k: v for k, v in self.expected_inputs.items()
                        if k not in ("sample", "timestep") and not k.startswith("additional_residual_")}
-        for k, v in kwargs.items():
-            if k not in loop_inputs:
-                raise ValueError(f"Received unexpected input kwarg: {k}")
-            if not isinstance(v, np.ndarray):
-                raise TypeError(f"Expected numpy.ndarray, got {v} for input: {k}")
-            if v.dtype != loop_inputs[k]["dtype"]:
-                raise TypeError(f"Expected dtype {loop_inputs[k]['dtype']}, got {v.dtype} for input: {k}")
-            if v.shape != loop_inputs[k]["shape"]:
-                raise TypeError(f"Expected shape {loop_inputs[k]['shape']}, got {v.shape} for input: {k}")
-        missing = [k for k in loop_inputs if k not in kwargs]
-        if missing:
-            raise ValueError(f"Missing input kwargs: {missing}")
+        _lib.verify_inputs(loop_inputs, **kwargs)
         if self._cfg_struct.support_controlnet and not self._attached:
             raise ValueError("this UNet consumes ControlNet residuals: attach_controlnets() first, or step through "
                              "__call__ with additional_residual_* inputs")
@@ -391,20 +362,12 @@ class HipModel:
         return _lib.lib().sd_unet_device_bytes(self._h)
 
     def close(self):
-        if getattr(self, "_h", None):
-            if getattr(self, "_attached", None):
-                try:
-                    self.attach_controlnets([])
-                except Exception:
-                    pass
-            _lib.lib().sd_unet_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        if getattr(self, "_h", None) and getattr(self, "_attached", None):
+            try:
+                self.attach_controlnets([])
+            except Exception:
+                pass
+        super().close()
 
 
 def _profile(handle, iters):
@@ -426,13 +389,14 @@ VAE_CONFIGS = {   # public AutoencoderKL config of SD 1.x / 2.x (decoder side)
 VAE_CONFIGS["runwayml/stable-diffusion-v1-5"] = VAE_CONFIGS["stabilityai/stable-diffusion-2-1-base"]
 
 
-class HipVaeDecoder:
+class HipVaeDecoder(_lib.Model):
     """``vae_decoder`` model runner: ``decoder(post_quant_conv(z))`` (torch2coreml.py:584-594) behind
     the CoreMLModel interface: ``expected_inputs["z"]`` (pipeline.py:315) and
     ``model(z=...)["image"]`` in [-1, 1] (pipeline.py:316), NCHW fp32.
     ``dtype`` is the model's declared input dtype AND its compute precision, as in the reference's conversion
     (torch2coreml.py:570-578): ``np.float16`` = the MFMA kernels (fp16 storage, fp32 accumulation); ``np.float32`` = fp32
     activations and arithmetic end to end (``compute_fp32``), what the stock SDXL VAE needs."""
+    _destroy = "sd_unet_destroy"
 
     def __init__(self, config, weights, batch=1, latent_height=64, latent_width=64, device=0, use_graph=True,
                  dtype=np.float16):
@@ -453,22 +417,14 @@ class HipVaeDecoder:
             raise ValueError(f"VAE dtype must be float16 or float32, got {dtype}")
         c.compute_fp32 = int(np.dtype(dtype) == np.float32)
         self.compute_dtype = np.dtype(dtype)
-        own = not isinstance(weights, Weights)
-        wstore = weights if not own else (Weights(safetensors_path=weights) if isinstance(weights, (str, bytes))
-                                          else Weights(tensors=weights))
         self._h = C.c_void_p()
-        try:
-            _lib.check(_lib.lib().sd_vae_decoder_create(C.byref(c), wstore._h, device, C.byref(self._h)))
-        finally:
-            if own:
-                wstore.close()
+        with Weights.lend(weights) as store:
+            _lib.check(_lib.lib().sd_vae_decoder_create(C.byref(c), store._h, device, C.byref(self._h)))
         self.batch, self.latent_height, self.latent_width = batch, latent_height, latent_width
         up = 2 ** (len(boc) - 1)
         self.image_shape = (batch, config["out_channels"], latent_height * up, latent_width * up)
         self.expected_inputs = {"z": {"shape": (batch, config["latent_channels"], latent_height, latent_width),
                                       "dtype": np.dtype(dtype)}}
-
-    _verify_inputs = HipModel._verify_inputs
 
     def __call__(self, **kwargs):
         self._verify_inputs(**kwargs)
@@ -490,22 +446,12 @@ class HipVaeDecoder:
     def device_bytes(self):
         return _lib.lib().sd_unet_device_bytes(self._h)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib.lib().sd_unet_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class HipVaeEncoder:
+class HipVaeEncoder(_lib.Model):
     """``vae_encoder`` model runner: ``quant_conv(encoder(x))`` (torch2coreml.py:739-749) behind the CoreMLModel
     interface: ``model(x=...)["latent"]`` = the posterior moments (B, 2*latent_channels, H/8, W/8) fp32,
     [mean | logvar]; sampling and the scale factor stay with the caller (Encoder.swift:48-90)."""
+    _destroy = "sd_unet_destroy"
 
     def __init__(self, config, weights, batch=1, height=512, width=512, device=0, use_graph=True, dtype=np.float16):
         if isinstance(config, str):
@@ -525,20 +471,12 @@ class HipVaeEncoder:
             raise ValueError(f"VAE dtype must be float16 or float32, got {dtype}")
         c.compute_fp32 = int(np.dtype(dtype) == np.float32)   # torch2coreml.py:726-733: the SDXL encoder is float32 too
         self.compute_dtype = np.dtype(dtype)
-        own = not isinstance(weights, Weights)
-        wstore = weights if not own else (Weights(safetensors_path=weights) if isinstance(weights, (str, bytes))
-                                          else Weights(tensors=weights))
         self._h = C.c_void_p()
-        try:
-            _lib.check(_lib.lib().sd_vae_encoder_create(C.byref(c), wstore._h, device, C.byref(self._h)))
-        finally:
-            if own:
-                wstore.close()
+        with Weights.lend(weights) as store:
+            _lib.check(_lib.lib().sd_vae_encoder_create(C.byref(c), store._h, device, C.byref(self._h)))
         down = 2 ** (len(boc) - 1)
         self.latent_shape = (batch, 2 * config["latent_channels"], height // down, width // down)
         self.expected_inputs = {"x": {"shape": (batch, 3, height, width), "dtype": np.dtype(dtype)}}
-
-    _verify_inputs = HipModel._verify_inputs
 
     def __call__(self, **kwargs):
         self._verify_inputs(**kwargs)
@@ -550,14 +488,3 @@ class HipVaeEncoder:
     @property
     def device_bytes(self):
         return _lib.lib().sd_unet_device_bytes(self._h)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib.lib().sd_unet_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -14,9 +14,9 @@ import os
 import numpy as np
 
 from . import _lib
+from ._lib import verify_inputs  # noqa: F401  (this module's name for it)
 from .hip_model import Weights
 
-_ACTS = {"quick_gelu": 0, "gelu": 1}
 # openai/clip-vit-large-patch14's vision tower: what every Stable Diffusion 1.x safety checker is
 VIT_L_14 = dict(hidden_size=1024, intermediate_size=4096, num_hidden_layers=24, num_attention_heads=16, image_size=224, patch_size=14,
                 projection_dim=768, hidden_act="quick_gelu", layer_norm_eps=1e-5)
@@ -70,27 +70,13 @@ def expected_inputs(batch, image_size, image_height, image_width):
             "adjustment": {"shape": (1,), "dtype": f16}}
 
 
-def verify_inputs(expected, **kwargs):
-    """coreml_model.py:97-116: TypeError for a wrong type / dtype / shape, ValueError for an unknown or missing keyword."""
-    for k, v in kwargs.items():
-        if k not in expected:
-            raise ValueError(f"Received unexpected input kwarg: {k}")
-        if not isinstance(v, np.ndarray):
-            raise TypeError(f"Expected numpy.ndarray, got {v} for input: {k}")
-        if v.dtype != expected[k]["dtype"]:
-            raise TypeError(f"Expected dtype {expected[k]['dtype']}, got {v.dtype} for input: {k}")
-        if v.shape != expected[k]["shape"]:
-            raise TypeError(f"Expected shape {expected[k]['shape']}, got {v.shape} for input: {k}")
-    missing = [k for k in expected if k not in kwargs]
-    if missing:
-        raise ValueError(f"Missing input kwargs: {missing}")
+class HipSafetyChecker(_lib.Model):
+    _destroy = "sd_safety_checker_destroy"
 
-
-class HipSafetyChecker:
     def __init__(self, config, weights, batch=1, device=0, use_graph=True, image_height=512, image_width=512):
         vc = vision_config(config)
         act = vc["hidden_act"]
-        if act not in _ACTS:
+        if act not in _lib.ACTS:
             raise NotImplementedError(f"hidden_act {act!r} (CLIP vision towers use quick_gelu or gelu)")
         if int(batch) < 1:
             raise ValueError(f"batch must be >= 1, got {batch}")
@@ -107,47 +93,32 @@ class HipSafetyChecker:
         c.hidden_size, c.intermediate_size = int(vc["hidden_size"]), int(vc["intermediate_size"])
         c.num_hidden_layers, c.num_attention_heads = int(vc["num_hidden_layers"]), int(vc["num_attention_heads"])
         c.projection_dim, c.num_concepts, c.num_special = int(vc["projection_dim"]), vc["num_concepts"], vc["num_special"]
-        c.hidden_act = _ACTS[act]
+        c.hidden_act = _lib.ACTS[act]
         c.layer_norm_eps = float(vc["layer_norm_eps"])
         c.use_graph = int(bool(use_graph))
         self._cfg_struct = c
         self.batch, self.image_size = c.batch, c.image_size
         self.seq_len = (c.image_size // max(1, c.patch_size)) ** 2 + 1
         self.expected_inputs = expected_inputs(c.batch, c.image_size, image_height, image_width)
-        own = not isinstance(weights, Weights)
-        wstore = weights if not own else (Weights(safetensors_path=weights) if isinstance(weights, (str, bytes))
-                                          else Weights(tensors=weights))
         self._h = C.c_void_p()
-        try:
-            _lib.check(_lib.lib().sd_safety_checker_create(C.byref(c), wstore._h, device, C.byref(self._h)))
-        finally:
-            if own:
-                wstore.close()
+        with Weights.lend(weights) as store:
+            _lib.check(_lib.lib().sd_safety_checker_create(C.byref(c), store._h, device, C.byref(self._h)))
 
     @classmethod
     def from_pretrained(cls, folder, **kw):
-        if not os.path.isdir(folder):
-            raise FileNotFoundError(f"{folder} not found (coreml_model.py:176-178)")
+        path = _lib.checkpoint_file(folder)
         cfg = {}
         if os.path.exists(os.path.join(folder, "config.json")):
             with open(os.path.join(folder, "config.json")) as f:
                 cfg = json.load(f)
-        for name in ("model.fp16.safetensors", "model.safetensors"):
-            path = os.path.join(folder, name)
-            if os.path.exists(path):
-                from safetensors import safe_open
-                with safe_open(path, framework="np") as f:              # the head's sizes are the checkpoint's
-                    keys = set(f.keys())
-                    cfg = dict(cfg)
-                    if "concept_embeds" in keys:
-                        cfg.setdefault("num_concepts", f.get_slice("concept_embeds").get_shape()[0])
-                    if "special_care_embeds" in keys:
-                        cfg.setdefault("num_special", f.get_slice("special_care_embeds").get_shape()[0])
-                return cls(cfg, path, **kw)
-        raise FileNotFoundError(f"no .safetensors checkpoint under {folder}")
-
-    def _verify_inputs(self, **kwargs):
-        verify_inputs(self.expected_inputs, **kwargs)
+        from safetensors import safe_open
+        with safe_open(path, framework="np") as f:                      # the head's sizes are the checkpoint's
+            keys = set(f.keys())
+            if "concept_embeds" in keys:
+                cfg.setdefault("num_concepts", f.get_slice("concept_embeds").get_shape()[0])
+            if "special_care_embeds" in keys:
+                cfg.setdefault("num_special", f.get_slice("special_care_embeds").get_shape()[0])
+        return cls(cfg, path, **kw)
 
     def run(self, clip_input, adjustment=0.0, want_hidden=False):
         """The device part: (has_nsfw (B,) bool, concept_scores (B, n) f32, image_embeds (B, P) f32[, last_hidden_state
@@ -176,14 +147,3 @@ class HipSafetyChecker:
 
     def device_bytes(self):
         return _lib.lib().sd_safety_checker_device_bytes(self._h)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib.lib().sd_safety_checker_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

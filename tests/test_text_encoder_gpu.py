@@ -50,6 +50,43 @@ def test_text_encoder_matches_oracle(name, xl):
     enc.close()
 
 
+def test_graph_replay_is_bit_identical_to_eager_launches():
+    """The graph handle against a handle that launches eagerly, on alternating prompts: a replay reads the new ids and the
+    new eos_index, and hidden_states[-2] (xl=True) comes out of the captured list as it does out of the eager one."""
+    cfg = clip_ref.CONFIGS["mini-l"]
+    sd16 = weights.make_state_dict(clip_ref.param_shapes(cfg), seed=7, dtype=np.float16, gain=2.0)
+    rows = [_ids(cfg, 3, 9).astype(np.float32), _ids(cfg, 4, 76).astype(np.float32)]
+    eager = HipTextEncoder(cfg, sd16, xl=True, use_graph=False)
+    want = [eager(input_ids=ids) for ids in rows]
+    eager.close()
+    assert all(np.isfinite(a).all() for w in want for a in w.values())
+    assert not np.array_equal(want[0]["hidden_embeds"], want[1]["hidden_embeds"])
+    assert not np.array_equal(want[0]["pooled_outputs"], want[1]["pooled_outputs"])
+    graph = HipTextEncoder(cfg, sd16, xl=True, use_graph=True)
+    for i in range(11):                                   # call 0 launches eagerly and captures, calls 1-10 replay
+        got = graph(input_ids=rows[i % 2])
+        for key in ("hidden_embeds", "pooled_outputs"):
+            assert np.isfinite(got[key]).all()
+            assert np.array_equal(got[key], want[i % 2][key]), f"call {i}: {key} differs from the eager handle"
+    graph.close()
+
+
+def test_single_layer_encoder_returns_the_embeddings_as_penultimate_state():
+    """num_hidden_layers = 1: hidden_states[-2] is the input of the only layer, the embeddings."""
+    cfg = dict(clip_ref.CONFIGS["mini-l"], num_hidden_layers=1)
+    sd16 = weights.make_state_dict(clip_ref.param_shapes(cfg), seed=7, dtype=np.float16, gain=2.0)
+    sd = weights.to_torch({k: v.astype(np.float32) for k, v in sd16.items()})
+    enc = HipTextEncoder(cfg, sd16, xl=True)
+    ids = _ids(cfg, 3, 9)
+    out = enc(input_ids=ids.astype(np.float32))
+    enc.close()
+    ref = clip_ref.text_encoder_forward(sd, cfg, torch.from_numpy(ids))
+    p = psnr.compute_psnr(out["hidden_embeds"], ref["hidden_embeds"].numpy())
+    assert p >= 50.0, f"hidden_embeds: PSNR {p:.1f} dB"
+    pp = psnr.compute_psnr(out["pooled_outputs"], ref["pooler_output"].numpy())
+    assert pp >= 45.0, f"pooled: PSNR {pp:.1f} dB"
+
+
 def _bytes_to_unicode():
     bs = list(range(ord("!"), ord("~") + 1)) + list(range(ord("\xa1"), ord("\xac") + 1)) + list(range(ord("\xae"), ord("\xff") + 1))
     cs, n = bs[:], 0
