@@ -270,6 +270,23 @@ int sd_op_groupnorm_shortcut(const void* x0, const void* x1, const float* gn_wei
 int sd_op_conv2d(const void* x, const void* w, const float* bias, const void* res, void* out, int B, int Cin, int H,
                  int W, int Cout, int ksize, int stride, int upsample, int tile, int splitk, int force_generic,
                  int iters, float* ms);
+/* sd_op_conv2d plus what the UNet / VAE builders set on their convs (a testing entry: tile, splitk, force_generic, iters, ms as above):
+ *   x1, C1        second source (B, C1, H, W) f16 or NULL: the conv runs over the channel concat (x | x1) (the up blocks' torch.cat,
+ *                 unet.py:213-216); w is then (Cout, Cin + C1, k, k)
+ *   temb          (B, Cout) f32 or NULL: the resnet's time_emb_proj row, added to every pixel of its sample (unet.py:477).  On the
+ *                 device it is a column block of a wider, otherwise poisoned row buffer, as the UNet keeps it
+ *   pad_mode      0: padding k/2; 1: the VAE encoder's Downsample2D(padding=0) - F.pad(x, (0, 1, 0, 1)), then a pad-0 conv
+ *                 (k = 3, stride 2, no upsample; Ho = (H - 2) / 2 + 1)
+ *   twin_groups   > 0: the slab combine also writes GroupNorm(twin_groups groups, twin_gamma / twin_beta (Cout) f32, twin_eps)
+ *                 (+ SiLU with twin_silu) of the result to out_twin (B, Cout, Ho, Wo) f16 - no GroupNorm launch (the low-res
+ *                 conv1 -> norm2 path); refused where the combine cannot hold whole (sample, group) slices
+ *   plan_out[4]   the plan the launch ran: tile (1-4 igemm.hip, 7 conv3x3_halo.hip, 9 wstream.hip, 11 bvgemm.hip, 12 smgemm.hip),
+ *                 staging, resolved split-K, 1 if the output left through fp32 slabs; all -1: the direct (non-MFMA) kernels
+ * res / out are (B, Cout, Ho, Wo). */
+int sd_op_conv2d_ex(const void* x, const void* x1, const void* w, const float* bias, const float* temb, const void* res, void* out, int B,
+                    int Cin, int C1, int H, int W, int Cout, int ksize, int stride, int upsample, int pad_mode, int twin_groups,
+                    const float* twin_gamma, const float* twin_beta, float twin_eps, int twin_silu, void* out_twin, int tile, int splitk,
+                    int force_generic, int* plan_out, int iters, float* ms);
 /* The same conv followed by torch.nn.GroupNorm (+ SiLU) of its output (unet.py:470-489 conv -> norm -> SiLU; stride 1, no
  * upsample): with producer_stats = 1 the GroupNorm statistics come out of the conv kernel's own epilogue (one launch less per
  * GroupNorm), with 0 from the GroupNorm's own statistics pass.  *entries (may be NULL) returns the number of partial

@@ -3,12 +3,14 @@
 // through the layout rules of weight_prep.h - the ones the UNet builder applies - before they reach the device.
 //
 // Plan codes of the entry points (A/B testing and tuning tools; the header describes them for callers):
-//   conv `tile` (sd_op_conv2d, _groupnorm, _groupnorm_proj, _groupnorm_conv3x3): plan tile = tile % 10, staging = tile / 10
+//   conv `tile` (sd_op_conv2d, _conv2d_ex, _groupnorm, _groupnorm_proj, _groupnorm_conv3x3): plan tile = tile % 10, staging = tile / 10
 //     tile    0 the library's plan, 1 128x128, 2 128x64, 3 64x64, 4 64x128, 7 the 3x3 halo kernel, 9 wstream.hip (needs w_tiled)
 //     staging 0 LDS-DMA 2-stage, 1 HBM -> VGPR -> LDS, 2 LDS-DMA 3-stage ring, ...; 12 / 13 (codes 12x / 13x) igemm_kernel's
 //             in-workgroup split-K rings
-//     sd_op_conv2d alone: 110-116 plan tile 11 (bvgemm.hip: its own choice / variants 1-6, needs w_bv),
-//                         140-142 plan tile 12 (smgemm.hip: tile height by M / 32 rows / 64 rows)
+//     sd_op_conv2d / sd_op_conv2d_ex alone: 110-116 plan tile 11 (bvgemm.hip: its own choice / variants 1-6, needs w_bv),
+//                                           140-142 plan tile 12 (smgemm.hip: tile height by M / 32 rows / 64 rows)
+//     sd_op_conv2d_ex is sd_op_conv2d with the ConvDesc fields the UNet / VAE builders set on top (second source, timestep embedding,
+//     the encoder's explicit padding, one GroupNorm twin) and reads the plan that ran back: plan_out = {tile, staging, splitk, slab}
 //   sd_op_geglu_ln `kernel`: 0 the library's plan, 1 the tiled igemm / gemm_pipe kernels, 2 plan tile 10 (wsgemm.hip),
 //     2 + 10 n ablation build n of that kernel, 3-9 plan tile 11 (bvgemm.hip: its own choice / variants 1-6),
 //     100 plan tile 13 (smgeglu.hip) with the tile height by the grid size, 101 / 102 its 128- / 256-row tiles,
@@ -126,10 +128,11 @@ void apply_tile_code(ConvDesc& d, int code, bool gemm_codes = false) {
 }
 
 // the pre-tiled weight copies a forced plan reads: tile 9 w_tiled (wstream.hip), tile 10 w_ws (wsgemm.hip), tile 11 w_bv (bvgemm.hip)
+int concat_channels(const ConvDesc& d) { return d.C0 + (d.x1 ? d.C1 : 0); }
 void tile_for_wstream(Scratch& sc, ConvDesc& d, const char* refusal) {
   SD_REQUIRE(wstream_shape_ok(d), kInvalidArgument, "%s", refusal);
-  half_t* wtd = sc.dev<half_t>(wstream_tiled_halves(d.N, d.C0, d.ksize));
-  launch_wstream_retile(d.w, wtd, d.N, d.C0, d.ksize, sc.stream);
+  half_t* wtd = sc.dev<half_t>(wstream_tiled_halves(d.N, concat_channels(d), d.ksize));
+  launch_wstream_retile(d.w, wtd, d.N, concat_channels(d), d.ksize, sc.stream);
   d.w_tiled = wtd;
 }
 void tile_for_wsgemm(Scratch& sc, ConvDesc& d) {
@@ -139,9 +142,119 @@ void tile_for_wsgemm(Scratch& sc, ConvDesc& d) {
 }
 void tile_for_bvgemm(Scratch& sc, ConvDesc& d, const char* refusal) {
   SD_REQUIRE(bvgemm_shape_ok(d), kInvalidArgument, "%s", refusal);
-  half_t* wtd = sc.dev<half_t>(bvgemm_tiled_halves(d.N, d.C0));
-  launch_bvgemm_retile(d.w, wtd, d.N, d.C0, d.out_mode == kOutGeglu, sc.stream);
+  half_t* wtd = sc.dev<half_t>(bvgemm_tiled_halves(d.N, concat_channels(d)));
+  launch_bvgemm_retile(d.w, wtd, d.N, concat_channels(d), d.out_mode == kOutGeglu, sc.stream);
   d.w_bv = wtd;
+}
+
+// What sd_op_conv2d_ex sets on top of sd_op_conv2d (header); default-constructed: sd_op_conv2d itself.
+struct ConvOpExtra {
+  const void* x1 = nullptr;   // second source (B, C1, H, W) f16
+  int C1 = 0;
+  const float* temb = nullptr;   // (B, Cout) f32
+  int pad_mode = 0;              // 1: the VAE encoder's F.pad(x, (0, 1, 0, 1)) + pad-0 stride-2 conv
+  int twin_groups = 0;           // > 0: one GroupNorm twin over exactly this output
+  const float *twin_gamma = nullptr, *twin_beta = nullptr;
+  float twin_eps = 1e-5f;
+  int twin_silu = 0;
+  void* out_twin = nullptr;
+  int* plan_out = nullptr;       // {tile, staging, splitk, slab} of the plan that ran; -1: the direct kernels
+};
+
+// (B, N) f32 rows on the device as the UNet keeps its time_emb_proj outputs: a column block of a wider row buffer, every other float
+// of which is poisoned - a kernel that reads a neighbouring column or another row's padding leaves garbage, not a near miss
+constexpr int kOpTembOffset = 4, kOpTembTail = 8;
+const float* upload_temb_rows(Scratch& sc, const float* temb, int B, int N, int* stride) {
+  const int ld = kOpTembOffset + (N + 3) / 4 * 4 + kOpTembTail;
+  std::vector<float> rows((size_t)B * ld, 1.0e30f);
+  for (int b = 0; b < B; ++b) std::copy(temb + (size_t)b * N, temb + (size_t)(b + 1) * N, rows.begin() + (size_t)b * ld + kOpTembOffset);
+  *stride = ld;
+  return sc.dev<float>(rows.size(), rows.data()) + kOpTembOffset;
+}
+
+// the body of sd_op_conv2d / sd_op_conv2d_ex
+void conv2d_op(const void* x, const void* w, const float* bias, const void* res, void* out, int B, int Cin, int H, int W, int Cout,
+               int ksize, int stride, int upsample, int tile, int splitk, int force_generic, int iters, float* ms, const ConvOpExtra& e) {
+  SD_REQUIRE(x && w && out, kInvalidArgument, "NULL argument");
+  SD_REQUIRE((ksize == 1 || ksize == 3) && (stride == 1 || stride == 2) && (upsample == 0 || upsample == 1),
+             kInvalidArgument, "conv2d: ksize %d stride %d upsample %d not on the path", ksize, stride, upsample);
+  SD_REQUIRE(e.C1 >= 0 && (e.C1 == 0 || e.x1), kInvalidArgument, "conv2d: C1 = %d needs the second source x1", e.C1);
+  SD_REQUIRE(e.pad_mode == 0 || (e.pad_mode == 1 && ksize == 3 && stride == 2 && !upsample), kInvalidArgument,
+             "conv2d: pad_mode %d (1 = the (0,1,0,1) padding of a 3x3 / stride-2 conv without upsample; ksize %d stride %d upsample %d)",
+             e.pad_mode, ksize, stride, upsample);
+  SD_REQUIRE(e.twin_groups == 0 || (e.twin_groups > 0 && e.twin_gamma && e.twin_beta && e.out_twin), kInvalidArgument,
+             "conv2d: a GroupNorm twin needs twin_gamma, twin_beta and out_twin (twin_groups %d)", e.twin_groups);
+  Scratch sc;
+  const int up = upsample ? 2 : 1, pad = ksize / 2;
+  // pad_mode 1: one row / column of zeros behind the image only (the sizes of UNet::conv_w)
+  const int Ho = e.pad_mode ? (H * up + 1 - ksize) / stride + 1 : (H * up + 2 * pad - ksize) / stride + 1;
+  const int Wo = e.pad_mode ? (W * up + 1 - ksize) / stride + 1 : (W * up + 2 * pad - ksize) / stride + 1;
+  SD_REQUIRE(Ho >= 1 && Wo >= 1, kInvalidArgument, "conv2d: empty output (%dx%d)", Ho, Wo);
+  ConvDesc d;
+  d.x0 = upload_nhwc(sc, x, B, Cin, H, W);
+  d.C0 = Cin;
+  if (e.C1 > 0) {
+    d.x1 = upload_nhwc(sc, e.x1, B, e.C1, H, W);
+    d.C1 = e.C1;
+  }
+  d.w = upload_conv_weight(sc, w, Cout, Cin + e.C1, ksize);
+  d.bias = bias ? sc.dev<float>(Cout, bias) : nullptr;
+  if (e.temb) d.temb = upload_temb_rows(sc, e.temb, B, Cout, &d.temb_stride);
+  if (res) d.res = upload_nhwc(sc, res, B, Cout, Ho, Wo);
+  half_t* dout = sc.dev<half_t>((size_t)B * Ho * Wo * Cout);
+  d.out = dout;
+  d.B = B; d.Hi = H; d.Wi = W; d.Ho = Ho; d.Wo = Wo;
+  d.ksize = ksize; d.stride = stride; d.up = up; d.N = Cout;
+  if (e.pad_mode) d.pad = 0;
+  apply_tile_code(d, tile, true);
+  d.splitk = splitk;
+  d.debug = force_generic >= 2 ? force_generic - 1 : 0;   // 2: loads only, 3: compute only (ablation)
+  if (d.debug & 4) d.prof = sc.dev<long long>(8);
+  const bool fast = force_generic != 1 && conv_fast_path_ok(d);
+  half_t* dtwin = nullptr;
+  if (e.twin_groups) {   // the GroupNorm as a twin of the conv's slab combine (sd_op_conv2d_groupnorm's producer_stats = 2)
+    SD_REQUIRE(fast, kInvalidArgument, "conv2d: GroupNorm twins need the MFMA path");
+    dtwin = sc.dev<half_t>((size_t)B * Ho * Wo * Cout);
+    d.n_twins = 1;
+    d.twin[0].y = dtwin;
+    d.twin[0].ld = Cout;
+    d.twin[0].c_off = 0;
+    d.twin[0].cpg = Cout / e.twin_groups;
+    d.twin[0].gamma = sc.dev<float>(Cout, e.twin_gamma);
+    d.twin[0].beta = sc.dev<float>(Cout, e.twin_beta);
+    d.twin[0].eps = e.twin_eps;
+    d.twin[0].silu = e.twin_silu;
+    SD_REQUIRE(Cout % e.twin_groups == 0 && reduce_twin_ok(Ho * Wo, Cout, 1, d.twin), kInvalidArgument,
+               "conv2d: shape not eligible for a GroupNorm twin (HW=%d C=%d groups=%d)", Ho * Wo, Cout, e.twin_groups);
+  }
+  ConvWorkspace ws;
+  // the pre-tiled weight copies: what a forced plan reads, else exactly what the planner names for the library's own plan
+  const ConvWeightCopies copies = (fast && tile == 0 && splitk == 0 && !d.debug) ? conv_plan_copies(d) : ConvWeightCopies{false, false, false};
+  if (fast && (d.tile == 9 || copies.wstream)) tile_for_wstream(sc, d, "conv2d: shape not eligible for plan tile 9 (wstream.hip)");
+  if (fast && (d.tile == 11 || copies.bvgemm)) tile_for_bvgemm(sc, d, "conv2d: shape not eligible for plan tile 11 (bvgemm.hip)");
+  if (fast && d.tile != 11 && d.tile != 12) ws = workspace_for(sc, {d});
+  // N <= 8 (conv_out of the UNet / the VAE): the small-N kernels the handles use, unless the direct kernel was asked for
+  const bool small_n = !fast && force_generic == 0 && Cout <= 8 && Cin % 8 == 0 && ksize == 3 && stride == 1 && !res && !d.x1 && !d.temb && !e.pad_mode;
+  if (e.plan_out) {   // the plan launch_conv is about to resolve for this descriptor
+    const ConvPlan p = fast ? conv_plan(d) : ConvPlan{-1, -1, -1, false, 0};
+    e.plan_out[0] = p.tile; e.plan_out[1] = p.staging; e.plan_out[2] = p.splitk; e.plan_out[3] = fast ? (p.slab ? 1 : 0) : -1;
+  }
+  sc.timed(iters, ms, [&] {
+    if (fast)
+      launch_conv(d, ws, sc.stream);
+    else if (small_n)
+      launch_conv_small_n(d, nullptr, sc.stream);
+    else
+      launch_conv_generic(d, 0, sc.stream);
+  });
+  if (d.prof) {
+    long long t[8];
+    SD_HIP(hipMemcpy(t, d.prof, sizeof(t), hipMemcpyDeviceToHost));
+    fprintf(stderr, "[sd prof] block0: prologue %lld, k-loop %lld, epilogue %lld shader cycles; total %lld cycles = %lld ticks of the 100 MHz wall clock\n",
+            t[1] - t[0], t[2] - t[1], t[3] - t[2], t[3] - t[0], t[4]);
+  }
+  download_nchw(dout, out, B, Cout, Ho, Wo);
+  if (dtwin) download_nchw(dtwin, e.out_twin, B, Cout, Ho, Wo);
 }
 
 // The producer of the conv2d_groupnorm* entries: a k x k stride-1 conv (+ bias, + residual) that writes its output to a fresh
@@ -311,51 +424,21 @@ int sd_op_groupnorm_shortcut(const void* x0, const void* x1, const float* gn_wei
 int sd_op_conv2d(const void* x, const void* w, const float* bias, const void* res, void* out, int B, int Cin, int H,
                  int W, int Cout, int ksize, int stride, int upsample, int tile, int splitk, int force_generic,
                  int iters, float* ms) {
+  return guarded([&] { conv2d_op(x, w, bias, res, out, B, Cin, H, W, Cout, ksize, stride, upsample, tile, splitk, force_generic, iters, ms, ConvOpExtra{}); });
+}
+
+int sd_op_conv2d_ex(const void* x, const void* x1, const void* w, const float* bias, const float* temb, const void* res, void* out, int B,
+                    int Cin, int C1, int H, int W, int Cout, int ksize, int stride, int upsample, int pad_mode, int twin_groups,
+                    const float* twin_gamma, const float* twin_beta, float twin_eps, int twin_silu, void* out_twin, int tile, int splitk,
+                    int force_generic, int* plan_out, int iters, float* ms) {
   return guarded([&] {
-    SD_REQUIRE(x && w && out, kInvalidArgument, "NULL argument");
-    SD_REQUIRE((ksize == 1 || ksize == 3) && (stride == 1 || stride == 2) && (upsample == 0 || upsample == 1),
-               kInvalidArgument, "conv2d: ksize %d stride %d upsample %d not on the path", ksize, stride, upsample);
-    Scratch sc;
-    const int up = upsample ? 2 : 1, pad = ksize / 2;
-    const int Ho = (H * up + 2 * pad - ksize) / stride + 1, Wo = (W * up + 2 * pad - ksize) / stride + 1;
-    ConvDesc d;
-    d.x0 = upload_nhwc(sc, x, B, Cin, H, W);
-    d.C0 = Cin;
-    d.w = upload_conv_weight(sc, w, Cout, Cin, ksize);
-    d.bias = bias ? sc.dev<float>(Cout, bias) : nullptr;
-    if (res) d.res = upload_nhwc(sc, res, B, Cout, Ho, Wo);
-    half_t* dout = sc.dev<half_t>((size_t)B * Ho * Wo * Cout);
-    d.out = dout;
-    d.B = B; d.Hi = H; d.Wi = W; d.Ho = Ho; d.Wo = Wo;
-    d.ksize = ksize; d.stride = stride; d.up = up; d.N = Cout;
-    apply_tile_code(d, tile, true);
-    d.splitk = splitk;
-    d.debug = force_generic >= 2 ? force_generic - 1 : 0;   // 2: loads only, 3: compute only (ablation)
-    if (d.debug & 4) d.prof = sc.dev<long long>(8);
-    const bool fast = force_generic != 1 && conv_fast_path_ok(d);
-    ConvWorkspace ws;
-    // the pre-tiled weight copies: what a forced plan reads, else exactly what the planner names for the library's own plan
-    const ConvWeightCopies copies = (fast && tile == 0 && splitk == 0 && !d.debug) ? conv_plan_copies(d) : ConvWeightCopies{false, false, false};
-    if (fast && (d.tile == 9 || copies.wstream)) tile_for_wstream(sc, d, "conv2d: shape not eligible for plan tile 9 (wstream.hip)");
-    if (fast && (d.tile == 11 || copies.bvgemm)) tile_for_bvgemm(sc, d, "conv2d: shape not eligible for plan tile 11 (bvgemm.hip)");
-    if (fast && d.tile != 11 && d.tile != 12) ws = workspace_for(sc, {d});
-    // N <= 8 (conv_out of the UNet / the VAE): the small-N kernels the handles use, unless the direct kernel was asked for
-    const bool small_n = !fast && force_generic == 0 && Cout <= 8 && Cin % 8 == 0 && ksize == 3 && stride == 1 && !res;
-    sc.timed(iters, ms, [&] {
-      if (fast)
-        launch_conv(d, ws, sc.stream);
-      else if (small_n)
-        launch_conv_small_n(d, nullptr, sc.stream);
-      else
-        launch_conv_generic(d, 0, sc.stream);
-    });
-    if (d.prof) {
-      long long t[8];
-      SD_HIP(hipMemcpy(t, d.prof, sizeof(t), hipMemcpyDeviceToHost));
-      fprintf(stderr, "[sd prof] block0: prologue %lld, k-loop %lld, epilogue %lld shader cycles; total %lld cycles = %lld ticks of the 100 MHz wall clock\n",
-              t[1] - t[0], t[2] - t[1], t[3] - t[2], t[3] - t[0], t[4]);
-    }
-    download_nchw(dout, out, B, Cout, Ho, Wo);
+    SD_REQUIRE(plan_out, kInvalidArgument, "NULL argument");
+    ConvOpExtra e;
+    e.x1 = x1; e.C1 = C1; e.temb = temb; e.pad_mode = pad_mode;
+    e.twin_groups = twin_groups; e.twin_gamma = twin_gamma; e.twin_beta = twin_beta; e.twin_eps = twin_eps; e.twin_silu = twin_silu;
+    e.out_twin = out_twin;
+    e.plan_out = plan_out;
+    conv2d_op(x, w, bias, res, out, B, Cin, H, W, Cout, ksize, stride, upsample, tile, splitk, force_generic, iters, ms, e);
   });
 }
 

@@ -110,6 +110,8 @@ SYMBOLS = [
     ("sd_op_groupnorm", _I, [_P, _FP, _FP, _P, _I, _I, _I, _I, _I, _F, _I, _I, _FP]),
     ("sd_op_groupnorm_shortcut", _I, [_P, _P, _FP, _FP, _P, _FP, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _I, _I, _I, _FP]),
     ("sd_op_conv2d", _I, [_P, _P, _FP, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _FP]),
+    ("sd_op_conv2d_ex", _I, [_P, _P, _P, _FP, _FP, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _FP, _FP, _F, _I, _P, _I, _I, _I,
+                             C.POINTER(_I), _I, _FP]),
     ("sd_op_conv2d_groupnorm", _I, [_P, _P, _FP, _P, _FP, _FP, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _I, _I, _I, C.POINTER(_I), _I, _FP]),
     ("sd_op_conv2d_groupnorm_proj", _I, [_P, _P, _FP, _P, _FP, _FP, _P, _FP, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _I, C.POINTER(_I), _I, _FP]),
     ("sd_op_conv2d_groupnorm_conv3x3", _I, [_P, _P, _FP, _P, _FP, _FP, _P, _FP, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _I, _I, _I,
@@ -328,6 +330,40 @@ def conv2d(x, w, bias=None, res=None, stride=1, upsample=False, tile=0, splitk=0
     check(lib().sd_op_conv2d(ptr(x), ptr(w), fptr(bias), ptr(res), ptr(out), B, Cin, H, W, Cout, k, stride,
                              int(upsample), tile, splitk, int(force_generic), iters, C.byref(ms)))
     return out, ms.value
+
+
+def conv2d_ex(x, w, bias=None, res=None, x1=None, temb=None, stride=1, upsample=False, pad_mode=0, twin=None, tile=0, splitk=0,
+              force_generic=False, iters=1):
+    """conv2d with a second source x1 (channel concat), a time-embedding row temb (B, Cout), the VAE encoder's (0,1,0,1) padding
+    (pad_mode=1) and one GroupNorm twin of the output: twin = (groups, gamma, beta, eps, silu).  Returns (out, twin output or None,
+    plan, ms); plan = [tile, staging, splitk, slab] of the launch, all -1 for the direct kernels."""
+    x, w = f16(x), f16(w)
+    x1 = None if x1 is None else f16(x1)
+    B, Cin, H, W = x.shape
+    C1 = 0 if x1 is None else x1.shape[1]
+    Cout, Ctot, k, k2 = w.shape
+    if Ctot != Cin + C1 or k != k2 or (x1 is not None and x1.shape != (B, C1, H, W)):
+        raise ValueError("conv2d_ex: weight / second source shape does not match input")
+    up = 2 if upsample else 1
+    pad = k // 2
+    Ho = (H * up + (1 if pad_mode else 2 * pad) - k) // stride + 1
+    Wo = (W * up + (1 if pad_mode else 2 * pad) - k) // stride + 1
+    bias = None if bias is None else f32(bias)
+    res = None if res is None else f16(res)
+    temb = None if temb is None else f32(temb)
+    if (temb is not None and temb.shape != (B, Cout)) or (res is not None and res.shape != (B, Cout, Ho, Wo)):
+        raise ValueError("conv2d_ex: temb must be (B, Cout), res (B, Cout, Ho, Wo)")
+    groups, gamma, beta, eps, silu = (0, None, None, 0.0, False) if twin is None else twin
+    gamma = None if gamma is None else f32(gamma)
+    beta = None if beta is None else f32(beta)
+    out = np.empty((B, Cout, Ho, Wo), np.float16)
+    out_twin = None if twin is None else np.empty_like(out)
+    plan = (C.c_int * 4)()
+    ms = C.c_float(0)
+    check(lib().sd_op_conv2d_ex(ptr(x), ptr(x1), ptr(w), fptr(bias), fptr(temb), ptr(res), ptr(out), B, Cin, C1, H, W, Cout, k, stride,
+                                int(upsample), pad_mode, groups, fptr(gamma), fptr(beta), eps, int(silu), ptr(out_twin), tile, splitk,
+                                int(force_generic), plan, iters, C.byref(ms)))
+    return out, out_twin, list(plan), ms.value
 
 
 def groupnorm_shortcut(x0, x1, gn_weight, gn_bias, w, bias=None, groups=32, eps=1e-5, silu=True, side=True, iters=1):
