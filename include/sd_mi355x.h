@@ -210,6 +210,17 @@ int sd_vae_decode(sd_unet* vae, const void* z, sd_dtype z_dtype, float* image, i
  * moments: (B, 8, H/8, W/8) f32 = [mean | logvar]. */
 int sd_vae_encoder_create(const sd_unet_config* cfg, const sd_weights* w, int device, sd_unet** out);
 int sd_vae_encode(sd_unet* vae, const void* x, sd_dtype x_dtype, float* moments, int flags);
+/* Image-to-image start: the n_images noised starting latents of ONE starting image in one call - what generateLatentSamples
+ * (StableDiffusionPipeline.swift:361-379, StableDiffusionXLPipeline.swift:365-381) gets from Encoder.encode (Encoder.swift:48-92:
+ * posterior sample of the moments, logvar clamped to [-30, 20], times the scale factor) and Scheduler.addNoise
+ * (Scheduler.swift:83-102).  Runs the encoder's launch list, then one element-wise fp32 kernel on the same stream; the moments
+ * never reach the host:
+ *     z = (mean + exp(0.5 * clamp(logvar, -30, 20)) * eps) * scale_factor;   latents[i] = sa * z + sb * noise[i]
+ * The handle must have batch 1.  x as for sd_vae_encode; eps (Cz, H/8, W/8), noise and latents (n_images, Cz, H/8, W/8) f32;
+ * eps / noise are standard normals drawn by the caller (sd_numpy_randn, ...), (sa, sb) the scheduler's add-noise coefficients
+ * at the first timestep of the truncated schedule.  Host pointers unless SD_FLAG_DEVICE_PTRS. */
+int sd_vae_encode_latents(sd_unet* vae_encoder, const void* x, sd_dtype x_dtype, const float* eps, const float* noise, int n_images,
+                          float scale_factor, float sa, float sb, float* latents, int flags);
 
 /* ------------------------------------------------------------------------------------------
  * CLIP text encoder(s): transformers' CLIPTextModel / CLIPTextModelWithProjection as the reference
@@ -380,6 +391,10 @@ int sd_op_gn_proj_qkv(const void* x_in, const void* conv_w, const float* gn_weig
                       int* entries, int iters, float* ms);
 /* unet.py:703-728 */
 int sd_op_timestep_embedding(const float* t, float* out, int n, int dim, int flip_sin_to_cos, float freq_shift);
+/* The kernel behind sd_vae_encode_latents alone (Encoder.swift:68-89 + Scheduler.swift:83-102): moments (2 * Cz, h, w) f32 =
+ * [mean | logvar], eps (Cz, h, w), noise and out (n_images, Cz, h, w) f32. */
+int sd_op_posterior_noise(const float* moments, const float* eps, const float* noise, float* out, int Cz, int h, int w, int n_images,
+                          float scale_factor, float sa, float sb, int iters, float* ms);
 /* Which plan does the library give a conv / 1x1 GEMM of this shape?  Host only, read only: needs no GPU and launches nothing.
  * The descriptor as plain ints: C0 (+ C1 > 0: a second, channel-concatenated source) -> N over B x Ho x Wo outputs, up = 1 / 2 (nearest
  * upsample in the gather), out_mode 0 plain, 1 token-transposed, 2 GEGLU; flags: 1 LayerNorm fold, 2 timestep embedding, 4 residual,

@@ -176,6 +176,15 @@ int sd_vae_encode(sd_unet* vae, const void* x, sd_dtype x_dtype, float* moments,
     vae->impl->vae_encode(x, x_dtype == SD_F32, moments, flags);
   });
 }
+int sd_vae_encode_latents(sd_unet* vae, const void* x, sd_dtype x_dtype, const float* eps, const float* noise, int n_images,
+                          float scale_factor, float sa, float sb, float* latents, int flags) {
+  return guarded([&] {
+    SD_REQUIRE(vae && x && eps && noise && latents, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(n_images >= 1, kInvalidArgument, "encode_latents: n_images = %d", n_images);
+    SD_REQUIRE(vae->impl->config().is_vae_decoder == 2, kInvalidArgument, "handle is not a VAE encoder");
+    vae->impl->vae_encode_latents(x, x_dtype == SD_F32, eps, noise, n_images, scale_factor, sa, sb, latents, flags);
+  });
+}
 int sd_vae_decode(sd_unet* vae, const void* z, sd_dtype z_dtype, float* image, int flags) {
   return guarded([&] {
     SD_REQUIRE(vae && z && image, kInvalidArgument, "NULL argument");

@@ -1054,6 +1054,29 @@ int sd_op_timestep_embedding(const float* t, float* out, int n, int dim, int fli
   });
 }
 
+// The image-to-image start on its own (misc.hip posterior_noise_kernel): moments (2 * Cz, h, w) f32 = [mean | logvar] of one image,
+// eps (Cz, h, w), noise / out (n_images, Cz, h, w) f32.  The device output sits in front of a poisoned guard that a launch must leave alone.
+int sd_op_posterior_noise(const float* moments, const float* eps, const float* noise, float* out, int Cz, int h, int w, int n_images,
+                          float scale_factor, float sa, float sb, int iters, float* ms) {
+  return guarded([&] {
+    SD_REQUIRE(moments && eps && noise && out, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(Cz > 0 && h > 0 && w > 0 && n_images > 0, kInvalidArgument, "posterior_noise: Cz=%d h=%d w=%d n_images=%d", Cz, h, w, n_images);
+    Scratch sc;
+    const size_t n = (size_t)Cz * h * w, total = (size_t)n_images * n, guard = 256;
+    float* dm = sc.dev<float>(2 * n, moments);
+    float* de = sc.dev<float>(n, eps);
+    float* dn = sc.dev<float>(total, noise);
+    float* dout = sc.dev<float>(total + guard);
+    SD_HIP(hipMemset(dout, 0xff, (total + guard) * sizeof(float)));   // 0xffffffff: a NaN
+    sc.timed(iters, ms, [&] { launch_posterior_noise(dm, de, dn, dout, n, n_images, scale_factor, sa, sb, sc.stream); });
+    SD_HIP(hipStreamSynchronize(sc.stream));
+    std::vector<uint32_t> g(guard);
+    SD_HIP(hipMemcpy(g.data(), dout + total, guard * sizeof(float), hipMemcpyDeviceToHost));
+    for (uint32_t v : g) SD_REQUIRE(v == 0xffffffffu, kInternal, "posterior_noise wrote behind its %zu outputs", total);
+    SD_HIP(hipMemcpy(out, dout, total * sizeof(float), hipMemcpyDeviceToHost));
+  });
+}
+
 // The safety checker's attention (vit.hip) on the layout its handle feeds it: qkv (B * S, 3 * heads * d) f16 rows [q | k | v] ->
 // out (B * S, heads * d) f16.  The device output sits in front of a guard of 64 rows; both are filled with NaN patterns before the
 // launch, and a launch that wrote into the guard fails the call.

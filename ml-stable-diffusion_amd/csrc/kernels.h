@@ -435,6 +435,12 @@ void launch_loop_prep(const float* latents, half_t* sample, float* tbuf, LoopTab
 void launch_cfg_sched_step(const float* noise_pred, float* latents, float* eps_hist, LoopTables t, float guidance,
                            int Bimg, int CHW, int cfg, int hist, hipStream_t s);
 
+// Image-to-image start (Encoder.swift:68-89 + Scheduler.swift:83-102) as one element-wise fp32 launch: moments = the encoder's
+// [mean | logvar] NCHW fp32 of ONE image (2 * n floats, n = Cz * h * w); std = exp(0.5 * clamp(logvar, -30, 20));
+// z = (mean + std * eps) * scale;  out[i] = sa * z + sb * noise[i] for the n_images (n floats each) of noise / out
+void launch_posterior_noise(const float* moments, const float* eps, const float* noise, float* out, size_t n, int n_images,
+                            float scale, float sa, float sb, hipStream_t s);
+
 void launch_lds_poison(hipStream_t s);   // debug (SD_POISON_LDS): NaN patterns into every CU's LDS
 void launch_count_nonfinite_half(const void* p, size_t bytes, unsigned long long* out, hipStream_t s);   // debug scan (SD_NAN_TRACE)
 

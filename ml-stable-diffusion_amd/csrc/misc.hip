@@ -2,6 +2,7 @@
 // MLPs, layout conversions at the 4-channel model boundary, and the device-resident
 // classifier-free-guidance + scheduler step (pipeline.py:500-573 without host round trips).
 #include <cmath>
+#include <cstdint>
 
 #include "kernels.h"
 
@@ -276,6 +277,47 @@ __global__ __launch_bounds__(256) void cfg_sched_step_kernel(const float* __rest
   }
 }
 
+// Image-to-image start: the posterior sample of the VAE encoder's moments (Encoder.swift:68-77: logvar clamped to [-30, 20],
+// std = exp(0.5 * logvar)), the scale factor (:78-89) and the scheduler's addNoise (Scheduler.swift:83-102) in one pass.  The
+// arithmetic is spelled out in fmaf / products so that the vector and the scalar form round alike: std * eps + mean in one
+// rounding, times scale, then sa * z + (sb * noise).  expf is the accurate library function (the std spans e^-15 .. e^10).
+__device__ __forceinline__ float posterior_latent(float mean, float logvar, float eps, float scale) {
+  const float lv = fminf(fmaxf(logvar, -30.0f), 20.0f);
+  return fmaf(expf(0.5f * lv), eps, mean) * scale;
+}
+// moments [mean (n) | logvar (n)], eps (n), noise / out (n_images, n).  VEC: n % 4 == 0 and every pointer 16-byte aligned - one
+// 16-byte load / store per lane and tensor; else one float per lane (any n, any alignment).  Grid-stride: any grid is in bounds.
+template <bool VEC>
+__global__ __launch_bounds__(256) void posterior_noise_kernel(const float* __restrict__ moments, const float* __restrict__ eps,
+                                                               const float* __restrict__ noise, float* __restrict__ out, size_t n,
+                                                               int n_images, float scale, float sa, float sb) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  if (VEC) {
+    const size_t n4 = n / 4;
+    const floatx4* mean4 = reinterpret_cast<const floatx4*>(moments);
+    const floatx4* logvar4 = reinterpret_cast<const floatx4*>(moments + n);
+    const floatx4* eps4 = reinterpret_cast<const floatx4*>(eps);
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+      const floatx4 m = mean4[i], lv = logvar4[i], e = eps4[i];
+      floatx4 z;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) z[k] = posterior_latent(m[k], lv[k], e[k], scale);
+      for (int b = 0; b < n_images; ++b) {
+        const floatx4 nz = reinterpret_cast<const floatx4*>(noise + (size_t)b * n)[i];
+        floatx4 o;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[k] = fmaf(sa, z[k], sb * nz[k]);
+        reinterpret_cast<floatx4*>(out + (size_t)b * n)[i] = o;
+      }
+    }
+  } else {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+      const float z = posterior_latent(moments[i], moments[n + i], eps[i], scale);
+      for (int b = 0; b < n_images; ++b) out[(size_t)b * n + i] = fmaf(sa, z, sb * noise[(size_t)b * n + i]);
+    }
+  }
+}
+
 inline int grid_for(size_t n) { return (int)std::min<size_t>((n + 255) / 256, 2048); }
 
 }  // namespace
@@ -368,6 +410,20 @@ void launch_cfg_sched_step(const float* noise_pred, float* latents, float* eps_h
   const size_t n = (size_t)Bimg * CHW;
   hipLaunchKernelGGL(cfg_sched_step_kernel, dim3(std::min(grid_for(n), 64)), dim3(256), 0, s, noise_pred, latents,
                      eps_hist, t, guidance, Bimg, CHW, cfg, hist);
+  SD_HIP(hipGetLastError());
+}
+
+void launch_posterior_noise(const float* moments, const float* eps, const float* noise, float* out, size_t n, int n_images,
+                            float scale, float sa, float sb, hipStream_t s) {
+  SD_REQUIRE(n >= 1 && n_images >= 1, kInvalidArgument, "posterior_noise: %zu elements x %d images", n, n_images);
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(moments) | reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(noise) |
+                         reinterpret_cast<uintptr_t>(out);
+  if (n % 4 == 0 && bits % 16 == 0)
+    hipLaunchKernelGGL(posterior_noise_kernel<true>, dim3(grid_for(n / 4)), dim3(256), 0, s, moments, eps, noise, out, n, n_images,
+                       scale, sa, sb);
+  else
+    hipLaunchKernelGGL(posterior_noise_kernel<false>, dim3(grid_for(n)), dim3(256), 0, s, moments, eps, noise, out, n, n_images,
+                       scale, sa, sb);
   SD_HIP(hipGetLastError());
 }
 

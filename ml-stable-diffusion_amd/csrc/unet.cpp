@@ -1576,6 +1576,40 @@ void UNet::vae_encode(const void* x, int x_is_f32, float* moments, int flags) {
   have_inputs_ = true;
 }
 
+// generateLatentSamples + Encoder.encode + Scheduler.addNoise (StableDiffusionPipeline.swift:361-379, Encoder.swift:68-89,
+// Scheduler.swift:83-102) behind the encoder graph: the moments stay in image_, one more launch on the same stream turns them
+// into the n_images noised starting latents.  The random numbers (eps, noise) are the host's, as everywhere in the library.
+void UNet::vae_encode_latents(const void* x, int x_is_f32, const float* eps, const float* noise, int n_images, float scale_factor,
+                              float sa, float sb, float* latents, int flags) {
+  SD_REQUIRE(cfg_.is_vae_decoder == 2, kInvalidArgument, "handle is not a VAE encoder");
+  SD_REQUIRE(cfg_.batch == 1 && cfg_.out_channels % 2 == 0, kInvalidArgument,
+             "encode_latents: the encoder handle must have batch 1 (one starting image feeds every latent), got %d", cfg_.batch);
+  SD_HIP(hipSetDevice(device_));
+  const bool dev = (flags & SD_FLAG_DEVICE_PTRS) != 0;
+  const hipMemcpyKind in_kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  const size_t n = image_elems_ / 2;   // Cz * h * w
+  if (enc_images_cap_ < n_images) {
+    enc_eps_ = enc_eps_ ? enc_eps_ : arena_.alloc_n<float>(n);
+    enc_noise_ = arena_.alloc_n<float>((size_t)n_images * n);
+    enc_latents_ = arena_.alloc_n<float>((size_t)n_images * n);
+    enc_images_cap_ = n_images;
+  }
+  const size_t nx = (size_t)3 * cfg_.height * cfg_.width;
+  if ((x_is_f32 != 0) != (vae_in_f32_ != 0)) {   // the captured boundary kernel bakes the input dtype in
+    vae_in_f32_ = x_is_f32 ? 1 : 0;
+    invalidate_graphs();
+  }
+  SD_HIP(hipMemcpyAsync(in_x_, x, nx * (x_is_f32 ? 4 : 2), in_kind, stream_));
+  SD_HIP(hipMemcpyAsync(enc_eps_, eps, n * sizeof(float), in_kind, stream_));
+  SD_HIP(hipMemcpyAsync(enc_noise_, noise, (size_t)n_images * n * sizeof(float), in_kind, stream_));
+  run_vae_graph();
+  launch_posterior_noise(image_, enc_eps_, enc_noise_, enc_latents_, n, n_images, scale_factor, sa, sb, stream_);
+  SD_HIP(hipMemcpyAsync(latents, enc_latents_, (size_t)n_images * n * sizeof(float),
+                        dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream_));
+  SD_HIP(hipStreamSynchronize(stream_));
+  have_inputs_ = true;
+}
+
 void UNet::invalidate_graphs() {
   if (graph_) { (void)hipGraphExecDestroy(graph_); graph_ = nullptr; }
   if (loop_graph_) { (void)hipGraphExecDestroy(loop_graph_); loop_graph_ = nullptr; }

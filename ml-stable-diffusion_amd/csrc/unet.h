@@ -84,6 +84,9 @@ class UNet {
   void set_attention(int impl);
   void vae_decode(const void* z, int z_is_f32, float* image, int flags);
   void vae_encode(const void* x, int x_is_f32, float* moments, int flags);
+  // image-to-image start: the encoder's launch list, then launch_posterior_noise on the moments where the list leaves them
+  void vae_encode_latents(const void* x, int x_is_f32, const float* eps, const float* noise, int n_images, float scale_factor,
+                          float sa, float sb, float* latents, int flags);
   int num_residuals() const { return (int)res_shapes_.size(); }
   size_t device_bytes() const { return arena_.bytes(); }
   const sd_unet_config& config() const { return cfg_; }
@@ -217,6 +220,8 @@ class UNet {
   float* image_ = nullptr;          // VAE: decoded image NCHW f32 (encoder: the moments NCHW f32)
   void* in_x_ = nullptr;            // VAE encoder: input image NCHW (f16 or f32)
   int vae_in_f32_ = 0;
+  float *enc_eps_ = nullptr, *enc_noise_ = nullptr, *enc_latents_ = nullptr;   // vae_encode_latents: (n), (images, n), (images, n)
+  int enc_images_cap_ = 0;
   size_t image_elems_ = 0;
   std::vector<float*> res_out_;     // ControlNet outputs NCHW f32
   std::vector<Tensor> cn_out_;      // ControlNet outputs NHWC f16

@@ -101,6 +101,7 @@ SYMBOLS = [
     ("sd_vae_decode", _I, [_P, _P, _I, _FP, _I]),
     ("sd_vae_encoder_create", _I, [C.POINTER(UNetConfig), _P, _I, C.POINTER(_P)]),
     ("sd_vae_encode", _I, [_P, _P, _I, _FP, _I]),
+    ("sd_vae_encode_latents", _I, [_P, _P, _I, _FP, _FP, _I, _F, _F, _F, _FP, _I]),
     ("sd_text_encoder_create", _I, [_P, _P, _I, C.POINTER(_P)]),
     ("sd_text_encoder_destroy", None, [_P]),
     ("sd_text_encoder_device_bytes", C.c_size_t, [_P]),
@@ -126,6 +127,7 @@ SYMBOLS = [
     ("sd_op_gn_proj_qkv", _I, [_P, _P, _FP, _FP, _P, _FP, _FP, _FP, _P, _P, _P, _P, _I, _I, _I, _I, _I, C.c_float, C.c_float, C.c_float, _I, _I,
                                C.POINTER(C.c_int), _I, _FP]),
     ("sd_op_timestep_embedding", _I, [_FP, _FP, _I, _I, _I, _F]),
+    ("sd_op_posterior_noise", _I, [_FP, _FP, _FP, _FP, _I, _I, _I, _I, _F, _F, _F, _I, _FP]),
     ("sd_op_conv_plan", _I, [_I] * 18 + [C.POINTER(C.c_int), C.POINTER(C.c_ulonglong)]),
     ("sd_numpy_randn", _I, [C.c_uint32, C.POINTER(C.c_double), C.c_size_t]),
     ("sd_torch_randn", _I, [C.c_uint32, C.POINTER(C.c_double), C.c_size_t]),
@@ -604,6 +606,23 @@ def timestep_embedding(t, dim, flip_sin_to_cos=True, freq_shift=0.0):
     out = np.empty((t.shape[0], dim), np.float32)
     check(lib().sd_op_timestep_embedding(fptr(t), fptr(out), t.shape[0], dim, int(flip_sin_to_cos), freq_shift))
     return out
+
+
+def posterior_noise(moments, eps, noise, scale_factor, sa, sb, iters=1):
+    """The image-to-image start as one launch (csrc/misc.hip posterior_noise_kernel; Encoder.swift:68-89 + Scheduler.swift:83-102):
+    moments (2*Cz, h, w) or (1, 2*Cz, h, w) f32 = [mean | logvar], eps (Cz, h, w), noise (n_images, Cz, h, w) f32 ->
+    (sa * (mean + exp(0.5 * clamp(logvar, -30, 20)) * eps) * scale_factor + sb * noise[i], ms)."""
+    moments, eps, noise = f32(moments), f32(eps), f32(noise)
+    if noise.ndim != 4:
+        raise ValueError("posterior_noise: noise must be (n_images, Cz, h, w)")
+    n_images, Cz, h, w = noise.shape
+    if moments.size != 2 * Cz * h * w or moments.shape[-3:] != (2 * Cz, h, w) or eps.shape[-3:] != (Cz, h, w) or eps.size != Cz * h * w:
+        raise ValueError("posterior_noise: moments must be (2*Cz, h, w) and eps (Cz, h, w) for noise (n_images, Cz, h, w)")
+    out = np.empty_like(noise)
+    ms = C.c_float(0)
+    check(lib().sd_op_posterior_noise(fptr(moments), fptr(eps), fptr(noise), fptr(out), Cz, h, w, n_images, float(scale_factor), float(sa),
+                                      float(sb), iters, C.byref(ms)))
+    return out, ms.value
 
 
 def numpy_randn(seed, n):

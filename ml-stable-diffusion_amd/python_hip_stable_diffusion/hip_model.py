@@ -485,6 +485,31 @@ class HipVaeEncoder(_lib.Model):
         _lib.check(_lib.lib().sd_vae_encode(self._h, _lib.ptr(x), 1 if x.dtype == np.float32 else 0, _lib.fptr(out), 0))
         return {"latent": out}
 
+    def encode_latents(self, x, eps, noise, scale_factor, sa, sb):
+        """The noised starting latents of image-to-image in one call (``sd_vae_encode_latents``): the encoder, then on the device
+        ``sa * (mean + std * eps) * scale_factor + sb * noise[i]`` (Encoder.swift:68-89, Scheduler.swift:83-102).  x as for
+        ``__call__`` (batch 1: one starting image feeds every latent), eps (Cz, h, w) and noise (n_images, Cz, h, w) float32
+        standard normals -> (n_images, Cz, h, w) float32."""
+        self._verify_inputs(x=x)
+        _, c2, h, w = self.latent_shape
+        if self.latent_shape[0] != 1:
+            raise ValueError(f"encode_latents needs an encoder handle of batch 1, this one has batch {self.latent_shape[0]}")
+        for name, v in (("eps", eps), ("noise", noise)):
+            if not isinstance(v, np.ndarray):
+                raise TypeError(f"Expected numpy.ndarray, got {v} for input: {name}")
+            if v.dtype != np.float32:
+                raise TypeError(f"Expected dtype float32, got {v.dtype} for input: {name}")
+        if eps.shape != (c2 // 2, h, w):
+            raise TypeError(f"Expected shape {(c2 // 2, h, w)}, got {eps.shape} for input: eps")
+        if noise.ndim != 4 or noise.shape[0] < 1 or noise.shape[1:] != (c2 // 2, h, w):
+            raise TypeError(f"Expected shape {('n_images', c2 // 2, h, w)}, got {noise.shape} for input: noise")
+        x, eps, noise = np.ascontiguousarray(x), np.ascontiguousarray(eps), np.ascontiguousarray(noise)
+        out = np.empty(noise.shape, np.float32)
+        _lib.check(_lib.lib().sd_vae_encode_latents(self._h, _lib.ptr(x), 1 if x.dtype == np.float32 else 0, _lib.fptr(eps),
+                                                    _lib.fptr(noise), noise.shape[0], float(scale_factor), float(sa), float(sb),
+                                                    _lib.fptr(out), 0))
+        return out
+
     @property
     def device_bytes(self):
         return _lib.lib().sd_unet_device_bytes(self._h)

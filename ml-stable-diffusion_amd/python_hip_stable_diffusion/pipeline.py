@@ -20,6 +20,10 @@ tensor hand-offs to the model runners; ``get_hip_pipe`` / ``main`` mirror ``get_
   * ``seed`` is an argument (the reference seeds numpy globally in ``main``, pipeline.py:726) and
     the initial latents come from the bit-exact numpy legacy stream implemented in the library
     (``sd_numpy_randn``), so results do not depend on global RNG state;
+  * image-to-image, the Swift pipeline's ``startingImage`` / ``strength`` (StableDiffusionPipeline.Configuration.swift:22-26,
+    :74-80; StableDiffusionPipeline.swift:242-262, :361-379; CLI ``--image`` / ``--strength``): the starting image goes through a
+    VAE encoder handle, its posterior sample is noised to the first timestep of the truncated schedule on the device
+    (``HipVaeEncoder.encode_latents``) and the loop runs over the schedule's tail;
   * ``--attention-implementation`` is a run-time flag of ``main`` (a conversion-time flag in the
     reference, torch2coreml.py:1678-1685).
 """
@@ -44,10 +48,11 @@ class HipStableDiffusionPipeline:
     def __init__(self, text_encoder, unet, vae_decoder, scheduler, tokenizer, controlnet=None, xl=False,
                  force_zeros_for_empty_prompt=True, feature_extractor=None, safety_checker=None,
                  text_encoder_2=None, tokenizer_2=None, vae_scaling_factor=None, unet_refiner=None,
-                 refiner_start=0.8, aesthetic_score=6.0, negative_aesthetic_score=2.5):
+                 refiner_start=0.8, aesthetic_score=6.0, negative_aesthetic_score=2.5, vae_encoder=None):
         self.text_encoder, self.text_encoder_2 = text_encoder, text_encoder_2
         self.tokenizer, self.tokenizer_2 = tokenizer, tokenizer_2
         self.unet, self.vae_decoder, self.scheduler = unet, vae_decoder, scheduler
+        self.vae_encoder = vae_encoder                       # image-to-image only (Encoder.swift); None: text-to-image only
         self.controlnet = controlnet
         self.xl = xl
         self.force_zeros_for_empty_prompt = force_zeros_for_empty_prompt
@@ -184,6 +189,50 @@ class HipStableDiffusionPipeline:
             raise ValueError(f"Unexpected latents shape, got {latents.shape}, expected {shape}")
         return latents * np.float32(self.scheduler.init_noise_sigma)
 
+    def prepare_image_latents(self, starting_image, strength, num_inference_steps, batch_size, num_channels_latents,
+                              latents=None, seed=None, rng="numpy"):
+        """Image-to-image start (generateLatentSamples, StableDiffusionPipeline.swift:361-379): truncates the schedule
+        (``scheduler.set_timesteps(n, strength)``) and returns the ``batch_size`` starting latents, float32 - the posterior sample
+        of the encoded image times the scale factor (Encoder.swift:48-92), noised to the first timestep of the tail
+        (Scheduler.swift:83-102).  Draw order of the reference: unit-variance noise for every latent first (user ``latents`` take
+        their place), then the posterior normals from the same source.  ``rng="numpy"``: one continued stream
+        (NumPyRandomSource.swift:86-117: normalShapedArray is consecutive nextNormal draws).  ``rng="nvidia"``: every array and
+        every single nextNormal is one Philox launch with its own offset (NvRandomSource.swift:65-90): image i is offset i, the
+        j-th posterior normal offset batch_size + j.  ``rng="torch"``: the posterior draws continue the generator behind the
+        vectorised array draw (TorchRandomSource.swift:94-150), which ``sd_torch_randn`` does not export - NotImplementedError.
+        The noise is NOT scaled by ``init_noise_sigma``: the add-noise coefficients carry the level."""
+        if self.vae_encoder is None:                                               # startingImageProvidedWithoutEncoder
+            raise ValueError("a starting image needs a VAE encoder: build the pipeline with vae_encoder=...")
+        if rng not in ("numpy", "torch", "nvidia"):
+            raise ValueError(f"rng must be 'numpy', 'torch' or 'nvidia', got {rng!r}")
+        if rng == "torch" and seed is not None:
+            raise NotImplementedError("image-to-image with rng='torch': the posterior normals continue torch's CPU generator behind "
+                                      "the latents' array draw, and sd_torch_randn exports whole arrays from a fresh seed only")
+        enc = self.vae_encoder.expected_inputs["x"]
+        x = np.asarray(starting_image)
+        if x.ndim == 3:
+            x = x[None]
+        if x.shape != tuple(enc["shape"]) or enc["shape"][0] != 1:                 # Encoder.swift:57-60 sampleInputShapeNotCorrect
+            raise ValueError(f"Unexpected starting image shape, got {np.asarray(starting_image).shape}, expected "
+                             f"{tuple(enc['shape'][1:])} (the encoder handle has batch {enc['shape'][0]}, must be 1)")
+        shape = (batch_size, num_channels_latents, self.height // 8, self.width // 8)
+        n_noise, n_post = int(np.prod(shape)), int(np.prod(shape[1:]))
+        if latents is not None and latents.shape != shape:
+            raise ValueError(f"Unexpected latents shape, got {latents.shape}, expected {shape}")
+        if rng == "nvidia" and seed is not None:
+            noise = latents if latents is not None else np.stack(
+                [_lib.philox_randn(int(seed), n_post, offset=i).reshape(shape[1:]) for i in range(batch_size)])
+            eps = np.array([_lib.philox_randn(int(seed), 1, offset=batch_size + j)[0] for j in range(n_post)]).reshape(shape[1:])
+        else:
+            stream = (np.random.randn(n_noise + n_post) if seed is None            # reference behaviour: numpy's global stream
+                      else _lib.numpy_randn(int(seed), n_noise + n_post))
+            noise = stream[:n_noise].reshape(shape) if latents is None else latents
+            eps = stream[n_noise:].reshape(shape[1:])
+        self.scheduler.set_timesteps(num_inference_steps, strength)
+        sa, sb = self.scheduler.add_noise_coefficients()
+        return self.vae_encoder.encode_latents(np.ascontiguousarray(x.astype(enc["dtype"])), eps.astype(np.float32),
+                                               np.ascontiguousarray(noise, dtype=np.float32), self.vae_scaling_factor, sa, sb)
+
     def prepare_control_cond(self, controlnet_cond, do_classifier_free_guidance, batch_size, num_images_per_prompt):
         out = []
         for cond in controlnet_cond:                                              # pipeline.py:346-357
@@ -240,8 +289,17 @@ class HipStableDiffusionPipeline:
     def __call__(self, prompt, height=512, width=512, num_inference_steps=50, guidance_scale=7.5, negative_prompt=None,
                  num_images_per_prompt=1, eta=0.0, latents=None, output_type="np", return_dict=True, callback=None,
                  callback_steps=1, controlnet_cond=None, original_size=None, crops_coords_top_left=(0, 0),
-                 target_size=None, unet_batch_one=False, seed=None, device_loop=True, rng="numpy", **kwargs):
+                 target_size=None, unet_batch_one=False, seed=None, device_loop=True, rng="numpy", starting_image=None,
+                 strength=1.0, **kwargs):
+        """``starting_image`` (3, H, W) or (1, 3, H, W) in [-1, 1] with ``strength`` < 1.0: image-to-image - the fraction
+        ``strength`` of the schedule runs, from the encoded image noised to its first timestep; without an image, or with
+        ``strength`` >= 1.0, text-to-image (mode rule of StableDiffusionPipeline.Configuration.swift:74-80)."""
         self.check_inputs(prompt, height, width, callback_steps)
+        if not strength > 0:
+            raise ValueError(f"`strength` has to be positive (a fraction of the schedule in (0, 1]) but is {strength}")
+        image_to_image = starting_image is not None and strength < 1.0            # Configuration.swift:74-80
+        if image_to_image and self.vae_encoder is None:                            # startingImageProvidedWithoutEncoder
+            raise ValueError("a starting image needs a VAE encoder: build the pipeline with vae_encoder=...")
         height, width = self.height, self.width
         original_size = original_size or (height, width)
         target_size = target_size or (height, width)
@@ -268,9 +326,14 @@ class HipStableDiffusionPipeline:
             extra = self._xl_kwargs(self.unet, pooled, original_size, crops_coords_top_left, target_size, do_cfg, n_img,
                                     is_refiner)
 
-        self.scheduler.set_timesteps(num_inference_steps)
-        timesteps = self.scheduler.timesteps
-        latents = self.prepare_latents(n_img, self.unet.in_channels, height, width, latents, seed, rng)
+        if image_to_image:
+            latents = self.prepare_image_latents(starting_image, strength, num_inference_steps, n_img, self.unet.in_channels,
+                                                 latents, seed, rng)
+        else:
+            self.scheduler.set_timesteps(num_inference_steps)
+            latents = self.prepare_latents(n_img, self.unet.in_channels, height, width, latents, seed, rng)
+        timesteps = self.scheduler.timesteps                 # image-to-image: the tail of the schedule (Scheduler.swift:109-114)
+        init_latents = latents
         if controlnet_cond:
             controlnet_cond = self.prepare_control_cond(controlnet_cond, do_cfg, batch_size, num_images_per_prompt)
         extra_step_kwargs = self.prepare_extra_step_kwargs(eta)
@@ -280,7 +343,7 @@ class HipStableDiffusionPipeline:
         if self.unet_refiner is not None:
             if not self.xl:
                 raise ValueError("unet_refiner needs an SDXL pipeline (xl=True)")
-            swap = int(float(len(timesteps)) * self.refiner_start)                 # ...XLPipeline.swift:206
+            swap = int(float(len(timesteps)) * self.refiner_start)                 # ...XLPipeline.swift:203-206 (truncated count)
             if swap < len(timesteps):
                 r_emb, r_pooled = self._encode_prompt(prompt, None, do_cfg, negative_prompt, None, for_refiner=True)
                 r_emb = self._per_image(r_emb, batch_size, num_images_per_prompt, cfg_mul)
@@ -372,7 +435,8 @@ class HipStableDiffusionPipeline:
             image = self.numpy_to_pil(image)
         if not return_dict:
             return image, has_nsfw
-        return PipelineOutput(images=image, nsfw_content_detected=has_nsfw, step_ms=step_ms, latents=latents)
+        return PipelineOutput(images=image, nsfw_content_detected=has_nsfw, step_ms=step_ms, latents=latents,
+                              init_latents=init_latents)
 
     @staticmethod
     def numpy_to_pil(images):
@@ -425,7 +489,8 @@ def checkpoint_scheduler_config(model_dir):
 def get_hip_pipe(model_dir, model_version, compute_unit="ALL", scheduler_override=None, controlnet_models=None,
                  force_zeros_for_empty_prompt=True, sources=None, attention_implementation="SPLIT_EINSUM",
                  num_images=1, guidance_scale=7.5, unet_batch_one=False, latent_size=None, device=0,
-                 refiner_dir=None, tokenizer_factory=None, text_encoder_factory=None, vae_dtype=None, disable_safety=False):
+                 refiner_dir=None, tokenizer_factory=None, text_encoder_factory=None, vae_dtype=None, disable_safety=False,
+                 vae_encoder=False):
     """``get_coreml_pipe`` (pipeline.py:607-697) without the conversion step: ``model_dir`` is a diffusers
     checkpoint directory (``unet/``, ``vae/``, ``text_encoder/``, ``tokenizer/``, ``scheduler/`` [,
     ``text_encoder_2/``, ``tokenizer_2/``]) instead of a folder of ``.mlpackage`` files; ControlNets are
@@ -435,11 +500,13 @@ def get_hip_pipe(model_dir, model_version, compute_unit="ALL", scheduler_overrid
     float32 for an SDXL checkpoint's own VAE (it overflows fp16), float16 otherwise; pass ``np.float16`` for an
     fp16-safe replacement VAE (``--custom-vae-version``).
     ``disable_safety``: do not load ``model_dir/safety_checker/`` (pipeline.py:650-656; ``disableSafety`` of the Swift
-    configuration); a checkpoint directory without one runs unchecked either way."""
+    configuration); a checkpoint directory without one runs unchecked either way.
+    ``vae_encoder``: also build the VAE encoder from ``vae/`` (image-to-image, ``pipe(..., starting_image=, strength=)``), in the
+    decoder's precision; off by default, so a text-to-image pipeline holds no more device memory than before."""
     if not os.path.isdir(model_dir):
         raise FileNotFoundError(f"{model_dir} not found (coreml_model.py:176-178)")
     from . import text_encoder as te
-    from .hip_model import HipModel, HipVaeDecoder
+    from .hip_model import HipModel, HipVaeDecoder, HipVaeEncoder
     xl = "xl" in model_version
     do_cfg = guidance_scale > 1.0
     batch = 1 if (unet_batch_one and do_cfg) else (2 if do_cfg else 1) * num_images
@@ -471,12 +538,15 @@ def get_hip_pipe(model_dir, model_version, compute_unit="ALL", scheduler_overrid
     kwargs["controlnet"] = ([load_unet(d, kind="controlnet") for d in controlnet_models] if controlnet_models else None)
     vcfg = _read_json(os.path.join(model_dir, "vae", "config.json"))
     lat = kwargs["unet"].latent_height
-    kwargs["vae_decoder"] = HipVaeDecoder(
-        dict(latent_channels=vcfg.get("latent_channels", 4), out_channels=vcfg.get("out_channels", 3),
-             block_out_channels=tuple(vcfg["block_out_channels"]), layers_per_block=vcfg.get("layers_per_block", 2)),
-        _find_weights(os.path.join(model_dir, "vae")), batch=1, latent_height=lat,
-        latent_width=kwargs["unet"].latent_width, device=device,
-        dtype=np.dtype(vae_dtype) if vae_dtype is not None else (np.float32 if xl else np.float16))
+    vae_cfg = dict(latent_channels=vcfg.get("latent_channels", 4), out_channels=vcfg.get("out_channels", 3),
+                   block_out_channels=tuple(vcfg["block_out_channels"]), layers_per_block=vcfg.get("layers_per_block", 2))
+    vae_dtype = np.dtype(vae_dtype) if vae_dtype is not None else np.dtype(np.float32 if xl else np.float16)
+    kwargs["vae_decoder"] = HipVaeDecoder(vae_cfg, _find_weights(os.path.join(model_dir, "vae")), batch=1, latent_height=lat,
+                                          latent_width=kwargs["unet"].latent_width, device=device, dtype=vae_dtype)
+    if vae_encoder:                                                                # Encoder.swift: one starting image, batch 1
+        down = 2 ** (len(vae_cfg["block_out_channels"]) - 1)
+        kwargs["vae_encoder"] = HipVaeEncoder(vae_cfg, _find_weights(os.path.join(model_dir, "vae")), batch=1, height=lat * down,
+                                              width=kwargs["unet"].latent_width * down, device=device, dtype=vae_dtype)
     kwargs["vae_scaling_factor"] = vcfg.get("scaling_factor")
     make_tok = tokenizer_factory or te.load_tokenizer
     make_enc = text_encoder_factory or (lambda folder, **kw: te.HipTextEncoder.from_pretrained(folder, device=device, **kw))
@@ -522,6 +592,15 @@ def prepare_controlnet_cond(image_path, height, width):
     return np.array(image).transpose(2, 0, 1) / 255.0
 
 
+def prepare_starting_image(image_path, height, width):
+    """The starting image of image-to-image: RGB, LANCZOS resize to the model size, CHW float32 in [-1, 1]
+    (``planarRGBShapedArray(minValue: -1, maxValue: 1)``, Encoder.swift:56)."""
+    from PIL import Image
+    image = Image.open(image_path).convert("RGB")
+    image = image.resize((width, height), resample=Image.LANCZOS)
+    return (np.array(image).transpose(2, 0, 1).astype(np.float32) / np.float32(255.0)) * np.float32(2.0) - np.float32(1.0)
+
+
 def build_parser():
     """The reference's flags with their names and defaults (pipeline.py:785-855) plus the run-time
     ``--attention-implementation`` (torch2coreml.py:1678-1685)."""
@@ -565,6 +644,8 @@ def build_parser():
                         help="Seed-exact random source of the initial latents (swift/StableDiffusionCLI/main.swift --rng): "
                              "numpy = np.random.seed + randn (this pipeline's and the reference's default), torch = torch's CPU "
                              "generator, nvidia = torch's CUDA generator (Philox)")
+    parser.add_argument("--image", default=None, help="Path to starting image.")          # swift/StableDiffusionCLI/main.swift:45-49
+    parser.add_argument("--strength", default=0.5, type=float, help="Strength for image2image.")
     return parser
 
 
@@ -582,15 +663,18 @@ def main(args):
                         controlnet_models=args.controlnet, force_zeros_for_empty_prompt=force_zeros,
                         sources=args.model_sources, attention_implementation=args.attention_implementation,
                         guidance_scale=args.guidance_scale, unet_batch_one=args.unet_batch_one, refiner_dir=args.refiner,
-                        disable_safety=getattr(args, "disable_safety", False))
+                        disable_safety=getattr(args, "disable_safety", False), vae_encoder=bool(getattr(args, "image", None)))
     controlnet_cond = None
     if args.controlnet:
         controlnet_cond = [prepare_controlnet_cond(args.controlnet_inputs[i], pipe.height, pipe.width)
                            for i, _ in enumerate(args.controlnet)]
+    i2i = {}
+    if getattr(args, "image", None):
+        i2i = dict(starting_image=prepare_starting_image(args.image, pipe.height, pipe.width), strength=args.strength)
     logger.info("Beginning image generation.")
     image = pipe(prompt=args.prompt, height=pipe.height, width=pipe.width, num_inference_steps=args.num_inference_steps,
                  guidance_scale=args.guidance_scale, controlnet_cond=controlnet_cond, negative_prompt=args.negative_prompt,
-                 unet_batch_one=args.unet_batch_one, seed=args.seed, output_type="pil", rng=getattr(args, "rng", "numpy"))
+                 unet_batch_one=args.unet_batch_one, seed=args.seed, output_type="pil", rng=getattr(args, "rng", "numpy"), **i2i)
     out_path = get_image_path(args)
     logger.info("Saving generated image to %s", out_path)
     image["images"][0].save(out_path)
