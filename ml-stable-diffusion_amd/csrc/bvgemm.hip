@@ -61,7 +61,7 @@ __device__ __forceinline__ float bv_gelu_erf(float x) {   // igemm.hip gelu_erf 
 // MFMA row n of strip `strip` (the accumulator register of lane half hi = (n >> 2) & 1 that holds it is r = 4 (n >> 3) + (n & 3))
 // -> row of the device weight matrix.  Plain: a lane ends up with the 16 consecutive output channels 32 strip + 16 hi + r.
 // GEGLU: wsgemm.hip's order - registers 0-3 | 8-11 the values, 4-7 | 12-15 the gates of the 8 consecutive channels
-// 16 strip + 8 hi + {0..3 | 4..7}; device rows are 32 values | 32 gates per 64 (UNet::upload_conv_weight).
+// 16 strip + 8 hi + {0..3 | 4..7}; device rows are 32 values | 32 gates per 64 (Net::upload_conv_weight).
 __host__ __device__ inline int bv_row(int strip, int n, bool geglu) {
   const int hi = (n >> 2) & 1, grp = n >> 3, e = n & 3;
   if (!geglu) return strip * 32 + 16 * hi + 4 * grp + e;
@@ -467,7 +467,7 @@ void launch_bvgemm(const ConvDesc& d, int variant, hipStream_t s) {
   SD_HIP(hipGetLastError());
 }
 
-// The library's own rule (launch_conv / UNet::conv_w): where the stand-alone table shows this kernel ahead of the tiled ones -
+// The library's own rule (launch_conv / Net::conv_w): where the stand-alone table shows this kernel ahead of the tiled ones -
 // 8 192 rows and more, K of at least 640 (K = 320 GEGLU belongs to wsgemm.hip)
 bool bvgemm_wanted(const ConvDesc& d) {
   if (!bvgemm_shape_ok(d)) return false;

@@ -12,6 +12,38 @@ int selftest_mfma();   // selftest.hip
 
 using namespace sd;
 
+namespace {
+// One handle type, three kinds (cfg.is_vae_decoder: 0 UNet / ControlNet, 1 VAE decoder, 2 VAE encoder): created here ...
+void create_handle(const sd_unet_config* cfg, const sd_weights* w, int device, sd_unet** out, int vae_kind = -1) {
+  SD_REQUIRE(cfg && w && out, kInvalidArgument, "NULL argument");
+  require_device();
+  sd_unet_config c = *cfg;
+  if (vae_kind >= 0) {
+    c.is_vae_decoder = vae_kind;
+    c.is_controlnet = 0;
+  }
+  SD_REQUIRE(!c.compute_fp32 || c.is_vae_decoder, kUnsupported,
+             "compute_fp32 is the VAE graphs' option (torch2coreml.py:570-578, :726-733); the UNet kernels store fp16");
+  auto h = std::make_unique<sd_unet>();
+  if (c.is_vae_decoder)
+    h->impl = std::make_unique<Vae>(c, w->store, device);
+  else
+    h->impl = std::make_unique<UNet>(c, w->store, device);
+  *out = h.release();
+}
+// ... and told apart here: `refusal` is what a VAE handle hears from an entry point of the UNet / ControlNet
+UNet& unet_of(sd_unet* u, const char* refusal) {
+  UNet* p = dynamic_cast<UNet*>(u->impl.get());
+  SD_REQUIRE(p, kInvalidArgument, "%s", refusal);
+  return *p;
+}
+Vae& vae_of(sd_unet* u, int kind) {
+  Vae* p = dynamic_cast<Vae*>(u->impl.get());
+  SD_REQUIRE(p && p->config().is_vae_decoder == kind, kInvalidArgument, "handle is not a VAE %s", kind == 2 ? "encoder" : "decoder");
+  return *p;
+}
+}  // namespace
+
 extern "C" {
 
 const char* sd_last_error(void) { return g_last_error.c_str(); }
@@ -49,13 +81,7 @@ int sd_weights_count(const sd_weights* w) { return w ? (int)w->store.size() : 0;
 void sd_weights_destroy(sd_weights* w) { delete w; }
 
 int sd_unet_create(const sd_unet_config* cfg, const sd_weights* w, int device, sd_unet** out) {
-  return guarded([&] {
-    SD_REQUIRE(cfg && w && out, kInvalidArgument, "NULL argument");
-    require_device();
-    auto h = std::make_unique<sd_unet>();
-    h->impl = std::make_unique<UNet>(*cfg, w->store, device);
-    *out = h.release();
-  });
+  return guarded([&] { create_handle(cfg, w, device, out); });
 }
 void sd_unet_destroy(sd_unet* u) { delete u; }
 int sd_unet_set_attention(sd_unet* u, int impl) {
@@ -79,13 +105,16 @@ int sd_tune_set_plan_table(const char* rows, sd_unet* u, int* n_plans) {
     if (u) u->impl->drop_graphs();   // the captured launches bake the old plans in
   });
 }
-int sd_unet_num_residuals(const sd_unet* u) { return u ? u->impl->num_residuals() : 0; }
+int sd_unet_num_residuals(const sd_unet* u) {
+  const UNet* p = u ? dynamic_cast<const UNet*>(u->impl.get()) : nullptr;
+  return p ? p->num_residuals() : 0;
+}
 size_t sd_unet_device_bytes(const sd_unet* u) { return u ? u->impl->device_bytes() : 0; }
 
 int sd_unet_forward(sd_unet* u, const sd_unet_io* io) {
   return guarded([&] {
     SD_REQUIRE(u && io, kInvalidArgument, "NULL argument");
-    u->impl->forward(*io);
+    unet_of(u, "handle is a VAE decoder: use sd_vae_decode").forward(*io);
   });
 }
 int sd_unet_time_forward(sd_unet* u, int warmup, int iters, float* ms_per_iter) {
@@ -99,8 +128,8 @@ int sd_unet_denoise_loop(sd_unet* u, const sd_unet_io* io, float* latents, int n
                          float guidance_scale, float* history_io, float* ms_per_step) {
   return guarded([&] {
     SD_REQUIRE(u && io && latents && timesteps && coef, kInvalidArgument, "NULL argument");
-    u->impl->denoise_loop(*io, latents, n_images, n_steps, timesteps, coef, sample_scale, history, guidance_scale,
-                          history_io, ms_per_step);
+    unet_of(u, "denoise_loop needs a UNet handle")
+        .denoise_loop(*io, latents, n_images, n_steps, timesteps, coef, sample_scale, history, guidance_scale, history_io, ms_per_step);
   });
 }
 
@@ -130,50 +159,33 @@ int sd_unet_profile(sd_unet* u, int iters, int cap, float* ms, double* flop, cha
 int sd_unet_attach_controlnets(sd_unet* u, sd_unet* const* controlnets, int n) {
   return guarded([&] {
     SD_REQUIRE(u && n >= 0 && (n == 0 || controlnets), kInvalidArgument, "NULL argument");
+    UNet& unet = unet_of(u, "attach_controlnets needs a UNet handle");
     std::vector<UNet*> v;
     for (int i = 0; i < n; ++i) {
       SD_REQUIRE(controlnets[i], kInvalidArgument, "controlnets[%d] is NULL", i);
-      v.push_back(controlnets[i]->impl.get());
+      v.push_back(dynamic_cast<UNet*>(controlnets[i]->impl.get()));   // null for a VAE handle: refused there as "not a ControlNet"
     }
-    u->impl->attach_controlnets(v);
+    unet.attach_controlnets(v);
   });
 }
 
 int sd_controlnet_set_cond(sd_unet* cn, const void* controlnet_cond, int flags) {
   return guarded([&] {
     SD_REQUIRE(cn && controlnet_cond, kInvalidArgument, "NULL argument");
-    cn->impl->set_controlnet_cond(controlnet_cond, flags);
+    unet_of(cn, "set_controlnet_cond needs a ControlNet handle").set_controlnet_cond(controlnet_cond, flags);
   });
 }
 
 int sd_vae_decoder_create(const sd_unet_config* cfg, const sd_weights* w, int device, sd_unet** out) {
-  return guarded([&] {
-    SD_REQUIRE(cfg && w && out, kInvalidArgument, "NULL argument");
-    require_device();
-    sd_unet_config c = *cfg;
-    c.is_vae_decoder = 1;
-    c.is_controlnet = 0;
-    auto h = std::make_unique<sd_unet>();
-    h->impl = std::make_unique<UNet>(c, w->store, device);
-    *out = h.release();
-  });
+  return guarded([&] { create_handle(cfg, w, device, out, 1); });
 }
 int sd_vae_encoder_create(const sd_unet_config* cfg, const sd_weights* w, int device, sd_unet** out) {
-  return guarded([&] {
-    SD_REQUIRE(cfg && w && out, kInvalidArgument, "NULL argument");
-    require_device();
-    sd_unet_config c = *cfg;
-    c.is_vae_decoder = 2;
-    c.is_controlnet = 0;
-    auto h = std::make_unique<sd_unet>();
-    h->impl = std::make_unique<UNet>(c, w->store, device);
-    *out = h.release();
-  });
+  return guarded([&] { create_handle(cfg, w, device, out, 2); });
 }
 int sd_vae_encode(sd_unet* vae, const void* x, sd_dtype x_dtype, float* moments, int flags) {
   return guarded([&] {
     SD_REQUIRE(vae && x && moments, kInvalidArgument, "NULL argument");
-    vae->impl->vae_encode(x, x_dtype == SD_F32, moments, flags);
+    vae_of(vae, 2).encode(x, x_dtype == SD_F32, moments, flags);
   });
 }
 int sd_vae_encode_latents(sd_unet* vae, const void* x, sd_dtype x_dtype, const float* eps, const float* noise, int n_images,
@@ -181,14 +193,13 @@ int sd_vae_encode_latents(sd_unet* vae, const void* x, sd_dtype x_dtype, const f
   return guarded([&] {
     SD_REQUIRE(vae && x && eps && noise && latents, kInvalidArgument, "NULL argument");
     SD_REQUIRE(n_images >= 1, kInvalidArgument, "encode_latents: n_images = %d", n_images);
-    SD_REQUIRE(vae->impl->config().is_vae_decoder == 2, kInvalidArgument, "handle is not a VAE encoder");
-    vae->impl->vae_encode_latents(x, x_dtype == SD_F32, eps, noise, n_images, scale_factor, sa, sb, latents, flags);
+    vae_of(vae, 2).encode_latents(x, x_dtype == SD_F32, eps, noise, n_images, scale_factor, sa, sb, latents, flags);
   });
 }
 int sd_vae_decode(sd_unet* vae, const void* z, sd_dtype z_dtype, float* image, int flags) {
   return guarded([&] {
     SD_REQUIRE(vae && z && image, kInvalidArgument, "NULL argument");
-    vae->impl->vae_decode(z, z_dtype == SD_F32, image, flags);
+    vae_of(vae, 1).decode(z, z_dtype == SD_F32, image, flags);
   });
 }
 

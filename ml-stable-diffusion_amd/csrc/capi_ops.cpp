@@ -186,7 +186,7 @@ void conv2d_op(const void* x, const void* w, const float* bias, const void* res,
              "conv2d: a GroupNorm twin needs twin_gamma, twin_beta and out_twin (twin_groups %d)", e.twin_groups);
   Scratch sc;
   const int up = upsample ? 2 : 1, pad = ksize / 2;
-  // pad_mode 1: one row / column of zeros behind the image only (the sizes of UNet::conv_w)
+  // pad_mode 1: one row / column of zeros behind the image only (the sizes of Net::conv_w)
   const int Ho = e.pad_mode ? (H * up + 1 - ksize) / stride + 1 : (H * up + 2 * pad - ksize) / stride + 1;
   const int Wo = e.pad_mode ? (W * up + 1 - ksize) / stride + 1 : (W * up + 2 * pad - ksize) / stride + 1;
   SD_REQUIRE(Ho >= 1 && Wo >= 1, kInvalidArgument, "conv2d: empty output (%dx%d)", Ho, Wo);

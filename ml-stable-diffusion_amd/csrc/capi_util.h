@@ -4,6 +4,7 @@
 #include <algorithm>
 
 #include "unet.h"
+#include "vae.h"
 
 namespace sd {
 extern thread_local std::string g_last_error;

@@ -1,7 +1,7 @@
 // What a model handle owns that is not model-specific: its device and stream, the arena, the launch list, the conv / GEMM
 // workspace and the captured graph - and the three things every handle does the same way: open a device, capture a graph,
-// upload checkpoint rows.  The text encoder and the safety checker are LaunchLists; the UNet shares Op, open_device and
-// capture_graph and keeps its own op lists.
+// upload checkpoint rows.  The text encoder and the safety checker are LaunchLists; the UNet / ControlNet and VAE handles hold one
+// in their common base (net.h: `ops` is their main list, `graph` one captured forward) and walk it through Net::run_ops_on.
 #pragma once
 #include <functional>
 

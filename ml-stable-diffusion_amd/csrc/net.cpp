@@ -1,0 +1,464 @@
+// Builders and executor shared by the UNet / ControlNet and VAE handles (net.h).
+//  * static shapes like the reference's Core ML models (pipeline.py:112-114): everything is allocated once, each tensor owns
+//    its bytes (288 GB HBM), so a forward is a pure launch list and is captured into one HIP graph.
+//  * channels-last activations, fp16 (or fp32 on a compute_fp32 VAE handle: each op has its two forms as two functions, chosen
+//    once at the top of conv / group_norm); weights re-laid-out at load to [Cout][ky][kx][Cin].
+#include "net.h"
+
+#include <algorithm>
+
+#include "conv_plan.h"
+#include "weight_prep.h"
+
+namespace sd {
+
+Net::Net(const sd_unet_config& cfg, const WeightStore& ws, int device) : cfg_(cfg), ws_(&ws), f32_(cfg.compute_fp32 != 0) {
+  SD_REQUIRE(cfg.n_levels >= 1 && cfg.n_levels <= SD_MAX_LEVELS, kInvalidArgument, "n_levels=%d", cfg.n_levels);
+  SD_REQUIRE(cfg.batch >= 1 && cfg.height >= 1 && cfg.width >= 1, kInvalidArgument, "bad batch/size");
+  SD_REQUIRE(cfg.norm_num_groups >= 1 && cfg.norm_num_groups <= 64, kUnsupported, "norm_num_groups=%d",
+             cfg.norm_num_groups);
+  open(device);
+}
+
+void Net::seal() {
+  ll_.seal();
+  ws_ = nullptr;
+}
+
+Tensor Net::new_tensor(int B, int H, int W, int C) {
+  Tensor t;
+  t.B = B;
+  t.H = H;
+  t.W = W;
+  t.C = C;
+  t.p = ll_.arena.alloc_n<half_t>(t.numel() * (f32_ ? 2 : 1));   // compute_fp32: the same bookkeeping over float elements
+  return t;
+}
+
+// [Cout][Cin][k][k] (or Linear [Cout][Cin]) -> [Cout][k][k][Cin] fp16.  GEGLU (ff.net.0.proj,
+// unet.py:613-617): rows re-ordered so value/gate channels interleave in blocks of 32 and the
+// GEMM epilogue can multiply them in registers.
+half_t* Net::upload_conv_weight(const std::string& name, int cout, int cin, int k, bool geglu) {
+  const HostTensor& t = ws_->get(name + ".weight");
+  const size_t expect = (size_t)cout * cin * k * k;
+  SD_REQUIRE(t.numel() == expect, kInvalidArgument, "%s.weight has %zu elements, expected %zu (%d,%d,%d,%d)",
+             name.c_str(), t.numel(), expect, cout, cin, k, k);
+  std::vector<half_t> host(expect);
+  retile_ohwi(t.data.data(), cout, cin, k, geglu, host.data());
+  half_t* d = ll_.arena.alloc_n<half_t>(expect);
+  SD_HIP(hipMemcpy(d, host.data(), expect * sizeof(half_t), hipMemcpyHostToDevice));
+  return d;
+}
+
+float* Net::upload_vec(const std::string& name, int n, bool geglu) {
+  const HostTensor& t = ws_->get(name);
+  SD_REQUIRE((int)t.numel() == n, kInvalidArgument, "%s has %zu elements, expected %d", name.c_str(), t.numel(), n);
+  std::vector<float> host(t.data);
+  if (geglu)
+    for (int o = 0; o < n; ++o) host[geglu_row(o, n)] = t.data[o];
+  float* d = ll_.arena.alloc_n<float>(n);
+  SD_HIP(hipMemcpy(d, host.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+  return d;
+}
+
+namespace {
+// output size of a conv over x, and its ConvDesc / ConvF32Desc pad field (-1: ksize / 2 on every side)
+struct ConvGeom {
+  int Ho, Wo, pad;
+};
+ConvGeom conv_geom(const std::string& name, const Tensor& x, const ConvArgs& a) {
+  const int Hup = x.H * a.up, Wup = x.W * a.up, pad = a.k / 2;
+  if (a.pad >= 0) {   // diffusers Downsample2D(padding=0): F.pad(x, (0, 1, 0, 1)) then a pad-0 stride-2 conv
+    SD_REQUIRE(a.pad == 0 && a.stride == 2 && a.k == 3, kUnsupported, "%s: explicit padding %d", name.c_str(), a.pad);
+    return {(Hup + 1 - a.k) / a.stride + 1, (Wup + 1 - a.k) / a.stride + 1, 0};
+  }
+  return {(Hup + 2 * pad - a.k) / a.stride + 1, (Wup + 2 * pad - a.k) / a.stride + 1, -1};
+}
+}  // namespace
+
+Tensor Net::conv(std::vector<Op>& ops, const std::string& name, const Tensor& x, const ConvArgs& a) {
+  if (f32_) return conv_f32(ops, name, x, a);
+  const int cin = x.C + (a.x2 ? a.x2->C : 0);
+  const bool geglu = a.out_mode == kOutGeglu;
+  const float* b = a.bias ? upload_vec(name + ".bias", a.cout, geglu) : nullptr;
+  const half_t* w = upload_conv_weight(name, a.cout, cin, a.k, geglu);
+  return conv_w(ops, name, w, b, x, a);
+}
+
+// fp32 compute path (torch2coreml.py:570-578 converts an SDXL checkpoint's own VAE with FLOAT32 precision): the weights stay
+// fp32 too - an fp32 checkpoint is not rounded to fp16 on the way in - in the [N][taps][Cin] layout of the fp16 path
+Tensor Net::conv_f32(std::vector<Op>& ops, const std::string& name, const Tensor& x, const ConvArgs& a) {
+  const int cout = a.cout, k = a.k;
+  const float* b = a.bias ? upload_vec(name + ".bias", cout) : nullptr;
+  const HostTensor& t = ws_->get(name + ".weight");
+  const size_t expect = (size_t)cout * x.C * k * k;
+  SD_REQUIRE(t.numel() == expect, kInvalidArgument, "%s.weight has %zu elements, expected %zu", name.c_str(), t.numel(), expect);
+  SD_REQUIRE(!a.x2 && !a.temb && !a.ln_colsum && a.out_mode == kOutHalf && !a.silu_out, kInternal, "%s: not a VAE conv", name.c_str());
+  std::vector<float> host(expect);
+  retile_ohwi(t.data.data(), cout, x.C, k, false, host.data());
+  float* w = ll_.arena.alloc_n<float>(expect);
+  SD_HIP(hipMemcpy(w, host.data(), expect * sizeof(float), hipMemcpyHostToDevice));
+  const ConvGeom g = conv_geom(name, x, a);
+  Tensor out = new_tensor(x.B, g.Ho, g.Wo, cout);
+  ConvF32Desc fd;
+  fd.x = x.f();
+  fd.w = w;
+  fd.w_kind = 1;
+  fd.bias = b;
+  fd.res = reinterpret_cast<const float*>(a.res);
+  fd.out = out.f();
+  fd.B = x.B; fd.Hi = x.H; fd.Wi = x.W; fd.Cin = x.C; fd.Ho = g.Ho; fd.Wo = g.Wo; fd.N = cout;
+  fd.ksize = k; fd.stride = a.stride; fd.up = a.up; fd.pad = g.pad;
+  ops.push_back([fd](hipStream_t s) { launch_conv_f32(fd, s); });
+  char buf[256];
+  snprintf(buf, sizeof(buf), "conv%dx%d fp32 %d->%d @%dx%d %s", k, k, x.C, cout, g.Ho, g.Wo, name.c_str());
+  ops.back().label = buf;
+  ops.back().flop = 2.0 * x.B * g.Ho * g.Wo * (double)cout * x.C * k * k;
+  return out;
+}
+
+Tensor Net::conv_w(std::vector<Op>& ops, const std::string& name, const half_t* w, const float* bias, const Tensor& x, const ConvArgs& a) {
+  const Tensor* x2 = a.x2;
+  const int cout = a.cout, k = a.k;
+  const bool geglu = a.out_mode == kOutGeglu, ln = a.ln_colsum != nullptr;
+  ConvDesc d;
+  d.x0 = x.p;
+  d.C0 = x.C;
+  if (x2) {
+    SD_REQUIRE(x2->B == x.B && x2->H == x.H && x2->W == x.W, kInternal, "%s: concat shape mismatch", name.c_str());
+    d.x1 = x2->p;
+    d.C1 = x2->C;
+  }
+  d.w = w;
+  d.bias = bias;
+  d.temb = a.temb;
+  d.temb_stride = kTembCap;
+  d.res = a.res;
+  d.B = x.B;
+  d.Hi = x.H;
+  d.Wi = x.W;
+  const ConvGeom g = conv_geom(name, x, a);
+  d.Ho = g.Ho;
+  d.Wo = g.Wo;
+  d.pad = g.pad;
+  d.ksize = k;
+  d.stride = a.stride;
+  d.up = a.up;
+  d.N = cout;
+  d.out_mode = a.out_mode;
+  d.ldT = a.ldT;
+  d.ln_colsum = a.ln_colsum;
+  if (ln) {
+    d.vt_perm = a.vt_perm ? 1 : 0;
+    d.q_scale = a.q_scale;
+    d.q_cols = a.q_cols;
+  }
+  Tensor out;
+  if (ln && a.n_trans > 0) {   // fused q|k|v: [M][n_trans] row-major + V^T [B][cout - n_trans][ldT]
+    out = new_tensor(x.B, d.Ho, d.Wo, a.n_trans);
+    *a.vt_out = ll_.arena.alloc_n<half_t>((size_t)x.B * (cout - a.n_trans) * a.ldT);
+    d.out_t = *a.vt_out;
+    d.n_trans = a.n_trans;
+  } else if (a.out_mode == kOutHalfT) {
+    out.B = x.B; out.H = 1; out.W = a.ldT; out.C = cout;   // [B][cout][ldT]
+    out.p = ll_.arena.alloc_n<half_t>((size_t)x.B * cout * a.ldT);
+  } else {
+    out = new_tensor(x.B, d.Ho, d.Wo, geglu ? cout / 2 : cout);
+  }
+  d.out = out.p;
+  SD_REQUIRE(!ln || (conv_fast_path_ok(d) && !a.silu_out), kInternal, "%s: LayerNorm fold / fused q|k|v off the MFMA path",
+             name.c_str());
+  // a GroupNorm built later over exactly this tensor may ask for its statistics from this op's epilogue (GnHook)
+  std::shared_ptr<GnHook> hook;
+  if (a.out_mode == kOutHalf && !(ln && a.n_trans > 0)) {
+    hook = std::make_shared<GnHook>();
+    out.gn = hook;
+    hook->ops_pos = (int)ops.size();
+    hook->ops_list = &ops;
+  }
+  auto with_hook = [hook](const ConvDesc& d0) {
+    ConvDesc dd = d0;
+    if (hook) {
+      dd.gn_partial = hook->partial;
+      dd.gn_groups = hook->groups;
+    }
+    return dd;
+  };
+  const int cin = x.C + (x2 ? x2->C : 0);
+  if (conv_fast_path_ok(d) && !a.silu_out) {
+    // the pre-tiled (fragment-major) weight copies the plan of this conv reads: exactly what the planner names
+    const ConvWeightCopies copies = conv_plan_copies(d);
+    if (copies.wstream && !ln) {   // small-M layers: the weight-streaming kernel (plan tile 9; never a LayerNorm-fold / q|k|v op)
+      half_t* wt = ll_.arena.alloc_n<half_t>(wstream_tiled_halves(cout, cin, k));
+      launch_wstream_retile(w, wt, cout, cin, k, ll_.stream);
+      d.w_tiled = wt;
+    }
+    if (copies.wsgemm) {    // widest-M GEGLU projection (K = 320): the weight-stationary kernel (wsgemm.hip, plan tile 10)
+      half_t* wt = ll_.arena.alloc_n<half_t>(wsgemm_tiled_halves(cout));
+      launch_wsgemm_retile(w, wt, cout, geglu, ll_.stream);
+      d.w_ws = wt;
+    }
+    if (copies.bvgemm) {    // large-M 1x1 GEMMs: weights global -> VGPR (bvgemm.hip, plan tile 11)
+      half_t* wt = ll_.arena.alloc_n<half_t>(bvgemm_tiled_halves(cout, x.C));
+      launch_bvgemm_retile(w, wt, cout, x.C, geglu, ll_.stream);
+      d.w_bv = wt;
+    }
+    ll_.ws_need = std::max(ll_.ws_need, conv_workspace_bytes(d));
+    ops.push_back([this, d, hook, with_hook](hipStream_t s) {
+      const int n = launch_conv(with_hook(d), ll_.ws_conv, s);
+      if (hook) hook->produced(n);
+    });
+  } else {
+    const int so = a.silu_out ? 1 : 0;
+    ops.push_back([d, so, hook, with_hook](hipStream_t s) {
+      const int n = launch_conv_generic(with_hook(d), so, s);
+      if (hook) hook->produced(n);
+    });
+  }
+  char buf[320];
+  // trailing "#kind,ksize,stride,up,Ctot,N,M" is the plan-table key of this op (tools/tune_plans.py)
+  const int kind = d.out_t ? 3 : (geglu ? 2 : (ln ? 1 : 0));
+  snprintf(buf, sizeof(buf), "%s%s %d->%d @%dx%d M=%d K=%d %s #%d,%d,%d,%d,%d,%d,%d", k == 3 ? "conv3x3" : (geglu ? "geglu1x1" : "gemm1x1"),
+           ln ? "+ln" : "", cin, cout, d.Ho, d.Wo, x.B * d.Ho * d.Wo, cin * k * k, name.c_str(), kind, k, a.stride, a.up, cin, cout,
+           x.B * d.Ho * d.Wo);
+  ops.back().label = buf;
+  ops.back().flop = 2.0 * x.B * d.Ho * d.Wo * (double)cout * cin * k * k;
+  return out;
+}
+
+void Net::conv_small_n(std::vector<Op>& ops, const std::string& name, const Tensor& x, int cout, half_t* out_nhwc, float* out_nchw) {
+  ConvDesc d;
+  d.x0 = x.p;
+  d.C0 = x.C;
+  d.w = upload_conv_weight(name, cout, x.C, 3, false);
+  d.bias = upload_vec(name + ".bias", cout);
+  d.out = out_nhwc;
+  d.B = x.B; d.Hi = x.H; d.Wi = x.W; d.Ho = x.H; d.Wo = x.W;
+  d.ksize = 3; d.stride = 1; d.up = 1; d.N = cout;
+  if (f32_) {
+    ConvF32Desc fd;
+    fd.x = x.f(); fd.w = d.w; fd.bias = d.bias;
+    fd.out = out_nhwc ? reinterpret_cast<float*>(out_nhwc) : new_tensor(x.B, x.H, x.W, cout).f();
+    fd.B = x.B; fd.Hi = x.H; fd.Wi = x.W; fd.Cin = x.C; fd.Ho = x.H; fd.Wo = x.W; fd.N = cout; fd.ksize = 3;
+    ops.push_back([=](hipStream_t s) {
+      launch_conv_f32(fd, s);
+      if (out_nchw) launch_nhwc_to_nchw_f32f32(fd.out, out_nchw, fd.B, fd.N, fd.Ho, fd.Wo, s);
+    });
+  } else {
+    ops.push_back([=](hipStream_t s) { launch_conv_small_n(d, out_nchw, s); });
+  }
+  ops.back().label = "conv3x3 small-N " + name + (out_nchw ? " -> fp32 NCHW" : "");
+  ops.back().flop = 2.0 * x.M() * (double)cout * x.C * 9;
+}
+
+Tensor Net::group_norm_f32(std::vector<Op>& ops, const std::string& name, const Tensor& x, float eps, bool silu) {
+  const int C = x.C, G = cfg_.norm_num_groups;
+  void* scratch = ll_.arena.alloc(groupnorm_f32_scratch_bytes(x.B, G));
+  const float* gamma = upload_vec(name + ".weight", C);
+  const float* beta = upload_vec(name + ".bias", C);
+  Tensor y = new_tensor(x.B, x.H, x.W, C);
+  const float* xp = x.f();
+  float* yp = y.f();
+  const int B = x.B, HW = x.H * x.W, si = silu ? 1 : 0;
+  ops.push_back([=](hipStream_t s) { launch_groupnorm_f32(xp, scratch, gamma, beta, yp, B, HW, C, G, eps, si, s); });
+  ops.back().label = "groupnorm fp32 C=" + std::to_string(C) + " @" + std::to_string(x.H) + "x" + std::to_string(x.W) + " " + name;
+  return y;
+}
+
+Tensor Net::group_norm(std::vector<Op>& ops, const std::string& name, const Tensor& x, const Tensor* x2, float eps,
+                       bool silu, const ConvDesc* side, const std::string& side_label, double side_flop) {
+  SD_REQUIRE(!side || !f32_, kInternal, "%s: side GEMM on the fp32 path", name.c_str());
+  const int C = x.C + (x2 ? x2->C : 0);
+  const int G = cfg_.norm_num_groups;
+  SD_REQUIRE(C % G == 0, kUnsupported, "%s: %d channels not divisible by %d groups", name.c_str(), C, G);
+  if (f32_) {
+    SD_REQUIRE(!x2, kInternal, "%s: concat GroupNorm on the fp32 path", name.c_str());
+    return group_norm_f32(ops, name, x, eps, silu);
+  }
+  const float* gamma = upload_vec(name + ".weight", C);
+  const float* beta = upload_vec(name + ".bias", C);
+  Tensor y = new_tensor(x.B, x.H, x.W, C);
+  float* partial = ll_.arena.alloc_n<float>(groupnorm_scratch_floats(x.B, x.H * x.W, G));
+  const half_t* p0 = x.p;
+  const half_t* p1 = x2 ? x2->p : nullptr;
+  const int C0 = x.C, C1 = x2 ? x2->C : 0, B = x.B, HW = x.H * x.W, si = silu ? 1 : 0;
+  half_t* yp = y.p;
+  // single-source GroupNorm that would need its own statistics launch: ask the op that produced x for them
+  std::shared_ptr<GnHook> hook;
+  if (!x2 && x.gn && !x.gn->partial && groupnorm_wants_producer_stats(HW, C, G)) {
+    // (`entries` is handed over at launch time - the producer must run first, in the same launch list)
+    SD_REQUIRE(x.gn->ops_list == &ops && x.gn->ops_pos >= 0 && x.gn->ops_pos < (int)ops.size(), kInternal,
+               "%s: GroupNorm producer statistics need the producing op earlier in the same launch list", name.c_str());
+    hook = x.gn;
+    hook->partial = partial;
+    hook->groups = G;
+  }
+  const std::string label = "groupnorm C=" + std::to_string(C) + " @" + std::to_string(x.H) + "x" + std::to_string(x.W) + " " + name;
+  if (side) {
+    const ConvDesc sd = *side;
+    ops.push_back([=](hipStream_t s) {
+      launch_groupnorm(p0, C0, p1, C1, partial, gamma, beta, yp, B, HW, G, eps, si, s, hook ? hook->consume() : 0, &sd);
+    });
+    ops.back().label = label + " || " + side_label;
+    ops.back().flop = side_flop;
+    return y;
+  }
+  ops.push_back([=](hipStream_t s) {
+    launch_groupnorm(p0, C0, p1, C1, partial, gamma, beta, yp, B, HW, G, eps, si, s, hook ? hook->consume() : 0);
+  });
+  ops.back().label = label;
+  return y;
+}
+
+// unet.py:470-489
+Tensor Net::resnet(std::vector<Op>& ops, const std::string& p, const Tensor& x, const Tensor* x2, int cout, const float* temb) {
+  const int cin = x.C + (x2 ? x2->C : 0);
+  // conv_shortcut(x) does not depend on norm1 -> conv1 -> norm2: it rides in norm1's launch (one grid: the GroupNorm's blocks, then
+  // the GEMM's tiles - igemm.hip gn_*_side_kernel) instead of a launch of its own.  SD_GN_SIDE=0 (with SD_TUNE): separate launches (A/B).
+  static const int side_mode = tune_env_int("SD_GN_SIDE", 1);
+  const half_t* side_out = nullptr;
+  Tensor t0;
+  if (cin != cout && side_mode != 0 && !f32_) {
+    ConvDesc sd;
+    sd.x0 = x.p;
+    sd.C0 = x.C;
+    if (x2) {
+      sd.x1 = x2->p;
+      sd.C1 = x2->C;
+    }
+    sd.B = x.B;
+    sd.Hi = sd.Ho = x.H;
+    sd.Wi = sd.Wo = x.W;
+    sd.N = cout;
+    if (gn_side_gemm_ok(sd)) {
+      sd.w = upload_conv_weight(p + ".conv_shortcut", cout, cin, 1, false);
+      sd.bias = upload_vec(p + ".conv_shortcut.bias", cout);
+      Tensor sc = new_tensor(x.B, x.H, x.W, cout);
+      sd.out = sc.p;
+      side_out = sc.p;
+      char buf[256];
+      snprintf(buf, sizeof(buf), "gemm1x1 %d->%d @%dx%d M=%d K=%d %s.conv_shortcut", cin, cout, x.H, x.W, x.M(), cin, p.c_str());
+      t0 = group_norm(ops, p + ".norm1", x, x2, cfg_.norm_eps, true, &sd, buf, 2.0 * x.M() * (double)cout * cin);
+    }
+  }
+  if (!side_out) t0 = group_norm(ops, p + ".norm1", x, x2, cfg_.norm_eps, true);
+  Tensor h = conv(ops, p + ".conv1", t0, {.cout = cout, .k = 3, .temb = temb});
+  Tensor t1 = group_norm(ops, p + ".norm2", h, nullptr, cfg_.norm_eps, true);
+  const half_t* shortcut;
+  if (side_out) {
+    shortcut = side_out;
+  } else if (cin != cout) {
+    shortcut = conv(ops, p + ".conv_shortcut", x, {.x2 = x2, .cout = cout}).p;
+  } else {
+    SD_REQUIRE(x2 == nullptr, kInternal, "%s: concat input with identity shortcut", p.c_str());
+    shortcut = x.p;
+  }
+  return conv(ops, p + ".conv2", t1, {.cout = cout, .k = 3, .res = shortcut});
+}
+
+void Net::invalidate_graphs() {
+  if (ll_.graph) { (void)hipGraphExecDestroy(ll_.graph); ll_.graph = nullptr; }
+}
+
+void Net::set_attention(int impl) {
+  SD_REQUIRE(impl >= 0 && impl <= 2, kInvalidArgument, "attention impl %d", impl);
+  if (impl != cfg_.attention_impl) {
+    cfg_.attention_impl = impl;
+    invalidate_graphs();
+  }
+}
+
+void Net::run_ops_on(const std::vector<Op>& ops, hipStream_t s) {
+  // SD_NAN_TRACE=1 (with SD_TUNE; eager launches only): after every op the whole arena is scanned for fp16 Inf / NaN patterns and the op
+  // after which their number changes is named on stderr (fp32 regions give false positives - read the list with the op in mind).
+  static const bool trace = tune_env_set("SD_NAN_TRACE");
+  if (trace) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) {
+      unsigned long long* d = nullptr;
+      SD_HIP(hipMalloc(&d, sizeof(unsigned long long)));
+      auto scan = [&]() {
+        SD_HIP(hipMemsetAsync(d, 0, sizeof(unsigned long long), s));
+        const Arena& ar = ll_.arena;
+        for (size_t i = 0; i < ar.chunks().size(); ++i) launch_count_nonfinite_half(ar.chunks()[i], ar.chunk_bytes()[i], d, s);
+        unsigned long long h = 0;
+        SD_HIP(hipMemcpyAsync(&h, d, sizeof(h), hipMemcpyDeviceToHost, s));
+        SD_HIP(hipStreamSynchronize(s));
+        return h;
+      };
+      unsigned long long last = scan();
+      fprintf(stderr, "nan-trace: %llu non-finite fp16 patterns in the arena before the list\n", last);
+      for (auto& op : ops) {
+        op(s);
+        const unsigned long long now = scan();
+        if (now != last) fprintf(stderr, "nan-trace: %llu -> %llu after  %s\n", last, now, op.label.c_str());
+        last = now;
+      }
+      (void)hipFree(d);
+      return;
+    }
+  }
+  static const bool poison = tune_env_set("SD_POISON_LDS");   // debug: NaN patterns into every CU's LDS in front of every op
+  for (auto& op : ops) {
+    if (poison) launch_lds_poison(s);
+    op(s);
+  }
+}
+
+void Net::run_forward() {
+  if (!cfg_.use_graph) return run_eager();
+  if (!ll_.graph) {
+    // first run eagerly (sets kernel attributes, warms code objects), then capture
+    run_eager();
+    SD_HIP(hipStreamSynchronize(ll_.stream));
+    ll_.graph = capture_graph(ll_.stream, [&] { run_eager(); });
+  }
+  SD_HIP(hipGraphLaunch(ll_.graph, ll_.stream));
+}
+
+float Net::time_forward(int warmup, int iters) {
+  SD_HIP(hipSetDevice(ll_.device));
+  SD_REQUIRE(have_inputs_, kInvalidArgument, "time_forward: call sd_unet_forward once first");
+  SD_REQUIRE(iters >= 1, kInvalidArgument, "iters must be >= 1");
+  for (int i = 0; i < warmup; ++i) run_forward();
+  EventList ev(2);
+  SD_HIP(hipEventRecord(ev[0], ll_.stream));
+  for (int i = 0; i < iters; ++i) run_forward();
+  SD_HIP(hipEventRecord(ev[1], ll_.stream));
+  SD_HIP(hipEventSynchronize(ev[1]));
+  float ms = 0.f;
+  SD_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
+  return ms / (float)iters;
+}
+
+std::vector<OpTime> Net::profile(int iters) {
+  SD_HIP(hipSetDevice(ll_.device));
+  SD_REQUIRE(have_inputs_, kInvalidArgument, "profile: call sd_unet_forward / sd_vae_decode once first");
+  SD_REQUIRE(iters >= 1 && iters <= 100, kInvalidArgument, "iters must be in 1..100");
+  hipStream_t stream = ll_.stream;
+  std::vector<const Op*> seq;
+  for (const auto* list : forward_lists())
+    for (const Op& op : *list) seq.push_back(&op);
+  const size_t n = seq.size();
+  std::vector<std::vector<float>> t(n, std::vector<float>((size_t)iters));
+  for (const Op* op : seq) (*op)(stream);   // warm (kernel attributes, code objects)
+  SD_HIP(hipStreamSynchronize(stream));
+  EventList ev(n + 1);
+  for (int it = 0; it < iters; ++it) {
+    SD_HIP(hipEventRecord(ev[0], stream));
+    for (size_t i = 0; i < n; ++i) {
+      (*seq[i])(stream);
+      SD_HIP(hipEventRecord(ev[i + 1], stream));
+    }
+    SD_HIP(hipEventSynchronize(ev[n]));
+    for (size_t i = 0; i < n; ++i) SD_HIP(hipEventElapsedTime(&t[i][(size_t)it], ev[i], ev[i + 1]));
+  }
+  std::vector<OpTime> out;
+  for (size_t i = 0; i < n; ++i) {
+    std::sort(t[i].begin(), t[i].end());
+    out.push_back({seq[i]->label.empty() ? std::string("op") : seq[i]->label, seq[i]->flop, t[i][(size_t)iters / 2]});
+  }
+  return out;
+}
+
+}  // namespace sd

@@ -1,0 +1,152 @@
+// What the UNet / ControlNet handle (unet.h) and the VAE handles (vae.h) share: one LaunchList for the device, stream, arena,
+// conv workspace, main op list and its graph; the conv / GroupNorm / ResNet block builders in fp16 and fp32; and the executor
+// (eager lists, the captured forward, per-forward timing and the per-op profile).
+#pragma once
+#include "../../include/sd_mi355x.h"
+#include "launch_list.h"
+
+namespace sd {
+
+constexpr int kTembCap = 65536;      // floats per batch row for the batched time_emb_proj outputs
+inline int round_up(int x, int a) { return (x + a - 1) / a * a; }
+
+// Link between a conv / GEMM op and the GroupNorm that consumes its output: the GroupNorm (built later) asks the
+// producer to leave per-tile (sum, sumsq) partials of the tensor in `partial`; at launch time the producer reports how
+// many entries per (sample, group) its plan wrote (0: none - split-K, ragged tiles - the GroupNorm runs its own pass).
+// `entries` is written by the producer's launch closure (produced()) and taken by the GroupNorm's (consume()): the GroupNorm op
+// sits behind its producer in the launch list (Net::group_norm asserts the positions at build time: ops_pos of the producer <
+// its own), and at LAUNCH time a consumer that runs without its producer having run since the last consumption - an op timed on
+// its own, a list walked out of order - gets 0 entries, i.e. runs its own statistics pass: stale partials are never folded.
+struct GnHook {
+  float* partial = nullptr;
+  int groups = 0;
+  int entries = 0;
+  bool fresh = false;            // produced() since the last consume()
+  void produced(int n) {
+    entries = n;
+    fresh = true;
+  }
+  int consume() {
+    const int n = fresh ? entries : 0;
+    fresh = false;
+    return n;
+  }
+  int ops_pos = -1;              // index of the producing op in its launch list
+  const void* ops_list = nullptr;
+};
+
+struct Tensor {
+  half_t* p = nullptr;          // fp32 handle (Net::f32_): the same bookkeeping over float elements, read through f()
+  int B = 0, H = 0, W = 0, C = 0;
+  std::shared_ptr<GnHook> gn;   // set on conv / GEMM outputs
+  int M() const { return B * H * W; }
+  size_t numel() const { return (size_t)B * H * W * C; }
+  float* f() const { return reinterpret_cast<float*>(p); }
+};
+
+struct OpTime {
+  std::string label;
+  double flop;
+  float ms;
+};
+
+// Arguments of Net::conv / conv_w by name; only cout is required.
+struct ConvArgs {
+  const Tensor* x2 = nullptr;    // second source: channel concat that is never materialised
+  int cout = 0;
+  int k = 1, stride = 1, up = 1;
+  bool bias = true;              // conv: <name>.bias exists in the checkpoint (conv_w takes its bias pointer)
+  const float* temb = nullptr;   // time_emb_proj row added per output channel
+  const half_t* res = nullptr;   // residual added in the epilogue
+  int out_mode = kOutHalf;
+  int ldT = 0;                   // kOutHalfT / fused q|k|v: tokens per transposed row
+  bool silu_out = false;
+  int pad = -1;                  // 0: diffusers Downsample2D(padding=0), F.pad(x, (0, 1, 0, 1)) then a pad-0 stride-2 conv
+  // conv_w only - LayerNorm fold (ln_colsum set) and, with it, the fused q|k|v split (n_trans > 0: columns >= n_trans leave
+  // token-transposed in *vt_out, [B][cout - n_trans][ldT])
+  const float* ln_colsum = nullptr;
+  int n_trans = 0;
+  half_t** vt_out = nullptr;
+  bool vt_perm = false;          // V^T in attention8's key order (AttnDesc::vt_perm)
+  float q_scale = 1.f;           // fused q|k|v: the first q_cols columns leave pre-scaled for attention8 (ConvDesc::q_scale)
+  int q_cols = 0;
+};
+
+class Net {
+ public:
+  virtual ~Net() { close(); }
+  Net(const Net&) = delete;
+  float time_forward(int warmup, int iters);
+  // HIP-event time of every op of one forward, in launch order (eager launches, cold caches between
+  // dependent kernels exactly as inside the graph); median over `iters` passes
+  std::vector<OpTime> profile(int iters);
+  virtual void set_attention(int impl);
+  void drop_graphs() { invalidate_graphs(); }   // measurement hook: the next forward re-captures (sd_tune_set_plan_table)
+  size_t device_bytes() const { return ll_.arena.bytes(); }
+  const sd_unet_config& config() const { return cfg_; }
+
+ protected:
+  Net(const sd_unet_config& cfg, const WeightStore& ws, int device);   // checks the shared config fields, then open()
+  void open(int device) { ll_.open(device); }
+  void seal();    // end of construction: the conv workspace, uploads complete, the weight store is not read again
+  void close() { ll_.close(); }
+
+  // ---- build ----
+  Tensor new_tensor(int B, int H, int W, int C);
+  half_t* upload_conv_weight(const std::string& name, int cout, int cin, int k, bool geglu);
+  float* upload_vec(const std::string& name, int n, bool geglu = false);
+  // conv uploads <name>.weight / .bias and emits the op; conv_w (fp16 only) takes device pointers
+  Tensor conv(std::vector<Op>& ops, const std::string& name, const Tensor& x, const ConvArgs& a);
+  Tensor conv_w(std::vector<Op>& ops, const std::string& name, const half_t* w, const float* bias, const Tensor& x, const ConvArgs& a);
+  // 3x3 conv to N <= 8 channels, one wavefront per pixel (conv_small.hip): fp32 NCHW into out_nchw (a model's boundary), else
+  // fp16 NHWC into out_nhwc.  An fp32 handle runs the fp32 conv into out_nhwc (or a tensor of its own) and transposes.
+  void conv_small_n(std::vector<Op>& ops, const std::string& name, const Tensor& x, int cout, half_t* out_nhwc, float* out_nchw);
+  // side (round 5): an independent 1x1 GEMM launched in the SAME grid as the GroupNorm's apply / single-launch kernel
+  // (launch_groupnorm); side_label / side_flop describe it in the per-op profile
+  Tensor group_norm(std::vector<Op>& ops, const std::string& name, const Tensor& x, const Tensor* x2, float eps,
+                    bool silu, const ConvDesc* side = nullptr, const std::string& side_label = std::string(), double side_flop = 0);
+  // temb: this resnet's row of time_emb_proj outputs (the UNet registers it), null without a time embedding (VAE)
+  Tensor resnet(std::vector<Op>& ops, const std::string& p, const Tensor& x, const Tensor* x2, int cout, const float* temb);
+
+  // ---- run ----
+  void run_ops(const std::vector<Op>& ops) { run_ops_on(ops, ll_.stream); }
+  void run_ops_on(const std::vector<Op>& ops, hipStream_t s);
+  virtual void run_eager() { run_ops(ll_.ops); }   // one forward between the boundary copies, launch by launch
+  void run_forward();                              // the same as one graph replay when cfg.use_graph (captured on first use)
+  virtual void invalidate_graphs();
+  // the op lists of one forward in launch order, for profile()
+  virtual std::vector<const std::vector<Op>*> forward_lists() const { return {&ll_.ops}; }
+
+  sd_unet_config cfg_;
+  const WeightStore* ws_ = nullptr;   // only valid during construction
+  bool f32_ = false;                  // VAE handle with cfg.compute_fp32: fp32 activations on the vae_f32.hip kernels
+  LaunchList ll_;                     // ll_.ops is the main list, ll_.graph one captured forward
+  bool have_inputs_ = false;
+
+ private:
+  Tensor conv_f32(std::vector<Op>& ops, const std::string& name, const Tensor& x, const ConvArgs& a);
+  Tensor group_norm_f32(std::vector<Op>& ops, const std::string& name, const Tensor& x, float eps, bool silu);
+};
+
+// hipEvents that are destroyed on every exit path
+struct EventList {
+  std::vector<hipEvent_t> ev;
+  explicit EventList(size_t n) {
+    ev.reserve(n);
+    for (size_t i = 0; i < n; ++i) {
+      hipEvent_t e = nullptr;
+      SD_HIP(hipEventCreate(&e));
+      ev.push_back(e);
+    }
+  }
+  ~EventList() {
+    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+  }
+  hipEvent_t operator[](size_t i) const { return ev[i]; }
+};
+
+}  // namespace sd
+
+struct sd_unet {
+  std::unique_ptr<sd::Net> impl;
+};

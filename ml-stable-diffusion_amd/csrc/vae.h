@@ -1,0 +1,34 @@
+// Host-side builder/executor of the VAE decoder and encoder launch graphs (diffusers AutoencoderKL), fp16 or fp32.
+// Spec: torch2coreml.py:584-594 (decoder), :739-749 (encoder); Encoder.swift:48-90.
+#pragma once
+#include "net.h"
+
+namespace sd {
+
+class Vae : public Net {
+ public:
+  Vae(const sd_unet_config& cfg, const WeightStore& ws, int device);   // cfg.is_vae_decoder: 1 decoder, 2 encoder
+
+  void decode(const void* z, int z_is_f32, float* image, int flags);
+  void encode(const void* x, int x_is_f32, float* moments, int flags);
+  // image-to-image start: the encoder's launch list, then launch_posterior_noise on the moments where the list leaves them
+  void encode_latents(const void* x, int x_is_f32, const float* eps, const float* noise, int n_images, float scale_factor,
+                      float sa, float sb, float* latents, int flags);
+
+ private:
+  void build_decoder();
+  void build_encoder();
+  Tensor attention(std::vector<Op>& ops, const std::string& p, const Tensor& h);
+  void upload_image(const void* x, int x_is_f32, hipMemcpyKind kind);
+
+  float* in_z_ = nullptr;           // decoder: latent input NCHW f32
+  half_t* z_half_ = nullptr;
+  float* image_ = nullptr;          // decoded image NCHW f32 (encoder: the moments NCHW f32)
+  size_t image_elems_ = 0;
+  void* in_x_ = nullptr;            // encoder: input image NCHW (f16 or f32)
+  int vae_in_f32_ = 0;
+  float *enc_eps_ = nullptr, *enc_noise_ = nullptr, *enc_latents_ = nullptr;   // encode_latents: (n), (images, n), (images, n)
+  int enc_images_cap_ = 0;
+};
+
+}  // namespace sd
