@@ -60,7 +60,26 @@ int sd_weights_add(sd_weights* w, const char* name, const void* data, sd_dtype d
 /* parse a .safetensors file (F16 / F32 / BF16 tensors); `prefix` (may be NULL) is stripped */
 int sd_weights_load_safetensors(sd_weights* w, const char* path, const char* prefix);
 int sd_weights_count(const sd_weights* w);
+/* tensor `index` (0 .. count - 1, in name order): its name (NUL-terminated, cut to name_bytes) and shape (at most 8 dims) */
+int sd_weights_tensor_info(const sd_weights* w, int index, char* name, int name_bytes, int64_t* shape8, int* ndim);
 void sd_weights_destroy(sd_weights* w);
+/* Palettized weights: the reference's conversion-time compression (torch2coreml.py:182-229 --quantize-nbits,
+ * mixed_bit_compression_apply.py) with the semantics of its fake_palettize at one group per tensor
+ * (mixed_bit_compression_pre_analysis.py:139-156): one LUT of 2^nbits fp16 entries per tensor, uint8 indices, and the tensor every
+ * model sees is lut[indices].  nbits is 1, 2, 4, 6 or 8 (anything else SD_ERR_INVALID_ARGUMENT, checked first).
+ * sd_weights_palettize clusters the stored tensor `name` (SD_ERR_NOT_FOUND when absent), its values rounded to fp16 first, by EXACT
+ * 1-D k-means - dynamic programming over the sorted distinct values, deterministic - and replaces its data by lut[indices]; the LUT
+ * is ascending; *sq_err (may be NULL) = sum of squared differences between the fp16-rounded values and lut[indices].  A tensor with
+ * no more than 2^nbits distinct values is reproduced exactly.
+ * sd_weights_add_palettized stores a palette computed elsewhere: lut 2^nbits f16, indices one uint8 per element (an index
+ * >= 2^nbits is SD_ERR_INVALID_ARGUMENT).  sd_weights_palette_bits: the tensor's nbits, 0 when it has no palette.
+ * sd_weights_read_palette copies out what the store holds (each output may be NULL): lut 2^nbits f16, indices, and the tensor's
+ * values as f32 (values alone also works for a tensor without a palette). */
+int sd_weights_palettize(sd_weights* w, const char* name, int nbits, double* sq_err);
+int sd_weights_add_palettized(sd_weights* w, const char* name, const void* lut, int nbits, const uint8_t* indices, const int64_t* shape,
+                              int ndim);
+int sd_weights_palette_bits(const sd_weights* w, const char* name);
+int sd_weights_read_palette(const sd_weights* w, const char* name, void* lut, uint8_t* indices, float* values);
 
 /* ------------------------------------------------------------------------------------------
  * UNet / ControlNet.  Config mirrors UNet2DConditionModel.__init__ (unet.py:801-833) with the
@@ -109,6 +128,13 @@ int sd_unet_set_attention(sd_unet* u, int impl);
 int sd_unet_num_residuals(const sd_unet* u); /* controlnet.py:191-197 */
 /* bytes of HBM held by the handle (weights + activations) */
 size_t sd_unet_device_bytes(const sd_unet* u);
+/* bytes the handle's tensors occupy inside that memory: the sum of its 256-byte-aligned allocations (sd_unet_device_bytes counts the
+ * whole 256-MiB chunks they were carved from) */
+size_t sd_unet_arena_used_bytes(const sd_unet* u);
+/* Palettes of the handle's weights: *n_palettized tensors of its weight store arrived with a palette; *n_streamed convolutions read
+ * theirs on the device - the small-M weight-stream convs (plan tile 14), which hold only the index bit stream and the LUT, no fp16
+ * copy; *stream_bytes = the bytes of those streams and LUTs.  Every other palettized tensor was uploaded as fp16 lut[indices]. */
+int sd_unet_palette_info(const sd_unet* u, int* n_palettized, int* n_streamed, size_t* stream_bytes);
 
 #define SD_FLAG_DEVICE_PTRS 1 /* all data pointers are device pointers on the handle's GPU */
 
@@ -298,6 +324,20 @@ int sd_op_conv2d_ex(const void* x, const void* x1, const void* w, const float* b
                     int Cin, int C1, int H, int W, int Cout, int ksize, int stride, int upsample, int pad_mode, int twin_groups,
                     const float* twin_gamma, const float* twin_beta, float twin_eps, int twin_silu, void* out_twin, int tile, int splitk,
                     int force_generic, int* plan_out, int iters, float* ms);
+/* The small-M weight-stream conv from PALETTIZED weights (plan tile 14): w = lut[indices], lut 2^nbits f16 (nbits 1, 2, 4, 6, 8),
+ * indices (Cout, Cin + C1, k, k) uint8; x1 / C1, bias, res, upsample, plan_out, iters, ms as sd_op_conv2d_ex; nw = waves per workgroup
+ * (4 or 8, 0 = 8).  Stride 1, padding k / 2.  The result is bit-identical to sd_op_conv2d_ex(tile = 9, or 49 for four waves) on the
+ * fp16 weights lut[indices].  A shape the weight stream does not take (wstream.hip: k 3 on 8- or 16-pixel-wide images or k 1,
+ * channel counts multiples of 64 in and 32 out) is SD_ERR_INVALID_ARGUMENT. */
+int sd_op_conv2d_palettized(const void* x, const void* x1, const void* lut, int nbits, const uint8_t* indices, const float* bias,
+                            const void* res, void* out, int B, int Cin, int C1, int H, int W, int Cout, int ksize, int upsample, int nw,
+                            int* plan_out, int iters, float* ms);
+/* The index bit stream that entry and the UNet builder put on the device (host only, no GPU): indices (Cout, Ctot, k, k) uint8 ->
+ * stream; *bytes = its size, stream may be NULL to ask for the size alone.  Per 32-row strip, 32-channel slice and lane, the
+ * 16 * k * k indices of the lane in MFMA fragment order (fragment j, element e: row strip * 32 + (lane & 31), channel slice * 32 +
+ * (j & 1) * 16 + (lane >> 5) * 8 + e, tap j >> 1) as little-endian nbits-wide fields, padded to whole 16-byte words, word q at
+ * [strip][slice][q][lane][16 B]. */
+int sd_op_palette_pack(const uint8_t* indices, int Cout, int Ctot, int ksize, int nbits, uint8_t* stream, size_t* bytes);
 /* The same conv followed by torch.nn.GroupNorm (+ SiLU) of its output (unet.py:470-489 conv -> norm -> SiLU; stride 1, no
  * upsample): with producer_stats = 1 the GroupNorm statistics come out of the conv kernel's own epilogue (one launch less per
  * GroupNorm), with 0 from the GroupNorm's own statistics pass.  *entries (may be NULL) returns the number of partial

@@ -78,6 +78,46 @@ int sd_weights_load_safetensors(sd_weights* w, const char* path, const char* pre
   });
 }
 int sd_weights_count(const sd_weights* w) { return w ? (int)w->store.size() : 0; }
+int sd_weights_tensor_info(const sd_weights* w, int index, char* name, int name_bytes, int64_t* shape8, int* ndim) {
+  return guarded([&] {
+    SD_REQUIRE(w && name && name_bytes > 1 && shape8 && ndim, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(index >= 0 && (size_t)index < w->store.size(), kInvalidArgument, "tensor index %d of %zu", index, w->store.size());
+    auto it = w->store.tensors().begin();
+    std::advance(it, index);
+    std::snprintf(name, (size_t)name_bytes, "%s", it->first.c_str());
+    *ndim = (int)it->second.shape.size();
+    std::copy(it->second.shape.begin(), it->second.shape.end(), shape8);
+  });
+}
+int sd_weights_palettize(sd_weights* w, const char* name, int nbits, double* sq_err) {
+  return guarded([&] {
+    SD_REQUIRE(w && name, kInvalidArgument, "NULL argument");
+    const double e = w->store.palettize(name, nbits);
+    if (sq_err) *sq_err = e;
+  });
+}
+int sd_weights_add_palettized(sd_weights* w, const char* name, const void* lut, int nbits, const uint8_t* indices, const int64_t* shape,
+                              int ndim) {
+  return guarded([&] {
+    SD_REQUIRE(w && name && lut && indices && (shape || ndim == 0), kInvalidArgument, "NULL argument");
+    w->store.add_palettized(name, lut, nbits, indices, shape, ndim);
+  });
+}
+int sd_weights_palette_bits(const sd_weights* w, const char* name) {
+  const Palette* p = (w && name) ? w->store.palette(name) : nullptr;
+  return p ? p->nbits : 0;
+}
+int sd_weights_read_palette(const sd_weights* w, const char* name, void* lut, uint8_t* indices, float* values) {
+  return guarded([&] {
+    SD_REQUIRE(w && name, kInvalidArgument, "NULL argument");
+    const HostTensor& t = w->store.get(name);
+    const Palette* p = w->store.palette(name);
+    SD_REQUIRE(p || (!lut && !indices), kInvalidArgument, "tensor '%s' has no palette", name);
+    if (lut) std::copy(p->lut.begin(), p->lut.end(), reinterpret_cast<uint16_t*>(lut));
+    if (indices) std::copy(p->indices.begin(), p->indices.end(), indices);
+    if (values) std::copy(t.data.begin(), t.data.end(), values);
+  });
+}
 void sd_weights_destroy(sd_weights* w) { delete w; }
 
 int sd_unet_create(const sd_unet_config* cfg, const sd_weights* w, int device, sd_unet** out) {
@@ -110,6 +150,13 @@ int sd_unet_num_residuals(const sd_unet* u) {
   return p ? p->num_residuals() : 0;
 }
 size_t sd_unet_device_bytes(const sd_unet* u) { return u ? u->impl->device_bytes() : 0; }
+size_t sd_unet_arena_used_bytes(const sd_unet* u) { return u ? u->impl->arena_used_bytes() : 0; }
+int sd_unet_palette_info(const sd_unet* u, int* n_palettized, int* n_streamed, size_t* stream_bytes) {
+  return guarded([&] {
+    SD_REQUIRE(u && n_palettized && n_streamed && stream_bytes, kInvalidArgument, "NULL argument");
+    u->impl->palette_info(n_palettized, n_streamed, stream_bytes);
+  });
+}
 
 int sd_unet_forward(sd_unet* u, const sd_unet_io* io) {
   return guarded([&] {

@@ -159,7 +159,29 @@ struct ConvOpExtra {
   int twin_silu = 0;
   void* out_twin = nullptr;
   int* plan_out = nullptr;       // {tile, staging, splitk, slab} of the plan that ran; -1: the direct kernels
+  // sd_op_conv2d_palettized: the weights are pal_lut[pal_indices] (w is NULL) and stay palettized on the device (plan tile 14)
+  const void* pal_lut = nullptr;         // 2^pal_bits f16
+  const uint8_t* pal_indices = nullptr;  // (Cout, Cin + C1, k, k)
+  int pal_bits = 0, pal_waves = 0;       // waves per workgroup: 4, else 8
 };
+
+// the palettized weights of a descriptor as the UNet builder uploads them (Net::conv): the packed index stream and the padded LUT
+void upload_palette(Scratch& sc, ConvDesc& d, const void* lut, int nbits, const uint8_t* indices, int waves) {
+  const int ctot = concat_channels(d);
+  const size_t n_el = (size_t)d.N * ctot * d.ksize * d.ksize;
+  for (size_t i = 0; i < n_el; ++i)
+    SD_REQUIRE(indices[i] < (1u << nbits), kInvalidArgument, "palettized conv: index %u at element %zu, the palette has %d entries",
+               (unsigned)indices[i], i, 1 << nbits);
+  std::vector<uint8_t> stream(wstream_pal_bytes(d.N, ctot, d.ksize, nbits));
+  wstream_pal_pack(indices, d.N, ctot, d.ksize, nbits, stream.data());
+  std::vector<half_t> lut_pad(kPalLutHalves, (half_t)0);
+  std::copy(f16(lut), f16(lut) + (1 << nbits), lut_pad.begin());
+  d.w_pal = sc.dev<uint8_t>(stream.size(), stream.data());
+  d.pal_lut = sc.dev<half_t>(lut_pad.size(), lut_pad.data());
+  d.pal_bits = nbits;
+  d.tile = 14;
+  d.staging = waves == 4 ? 4 : 0;
+}
 
 // (B, N) f32 rows on the device as the UNet keeps its time_emb_proj outputs: a column block of a wider row buffer, every other float
 // of which is poisoned - a kernel that reads a neighbouring column or another row's padding leaves garbage, not a near miss
@@ -175,7 +197,7 @@ const float* upload_temb_rows(Scratch& sc, const float* temb, int B, int N, int*
 // the body of sd_op_conv2d / sd_op_conv2d_ex
 void conv2d_op(const void* x, const void* w, const float* bias, const void* res, void* out, int B, int Cin, int H, int W, int Cout,
                int ksize, int stride, int upsample, int tile, int splitk, int force_generic, int iters, float* ms, const ConvOpExtra& e) {
-  SD_REQUIRE(x && w && out, kInvalidArgument, "NULL argument");
+  SD_REQUIRE(x && (w || e.pal_indices) && out, kInvalidArgument, "NULL argument");
   SD_REQUIRE((ksize == 1 || ksize == 3) && (stride == 1 || stride == 2) && (upsample == 0 || upsample == 1),
              kInvalidArgument, "conv2d: ksize %d stride %d upsample %d not on the path", ksize, stride, upsample);
   SD_REQUIRE(e.C1 >= 0 && (e.C1 == 0 || e.x1), kInvalidArgument, "conv2d: C1 = %d needs the second source x1", e.C1);
@@ -197,7 +219,7 @@ void conv2d_op(const void* x, const void* w, const float* bias, const void* res,
     d.x1 = upload_nhwc(sc, e.x1, B, e.C1, H, W);
     d.C1 = e.C1;
   }
-  d.w = upload_conv_weight(sc, w, Cout, Cin + e.C1, ksize);
+  if (!e.pal_indices) d.w = upload_conv_weight(sc, w, Cout, Cin + e.C1, ksize);
   d.bias = bias ? sc.dev<float>(Cout, bias) : nullptr;
   if (e.temb) d.temb = upload_temb_rows(sc, e.temb, B, Cout, &d.temb_stride);
   if (res) d.res = upload_nhwc(sc, res, B, Cout, Ho, Wo);
@@ -211,6 +233,11 @@ void conv2d_op(const void* x, const void* w, const float* bias, const void* res,
   d.debug = force_generic >= 2 ? force_generic - 1 : 0;   // 2: loads only, 3: compute only (ablation)
   if (d.debug & 4) d.prof = sc.dev<long long>(8);
   const bool fast = force_generic != 1 && conv_fast_path_ok(d);
+  if (e.pal_indices) {
+    SD_REQUIRE(fast && wstream_shape_ok(d), kInvalidArgument, "conv2d_palettized: shape not eligible for plan tile 14 (wstream.hip: k=%d C0=%d C1=%d N=%d %dx%d)",
+               ksize, Cin, e.C1, Cout, Ho, Wo);
+    upload_palette(sc, d, e.pal_lut, e.pal_bits, e.pal_indices, e.pal_waves);
+  }
   half_t* dtwin = nullptr;
   if (e.twin_groups) {   // the GroupNorm as a twin of the conv's slab combine (sd_op_conv2d_groupnorm's producer_stats = 2)
     SD_REQUIRE(fast, kInvalidArgument, "conv2d: GroupNorm twins need the MFMA path");
@@ -229,7 +256,7 @@ void conv2d_op(const void* x, const void* w, const float* bias, const void* res,
   }
   ConvWorkspace ws;
   // the pre-tiled weight copies: what a forced plan reads, else exactly what the planner names for the library's own plan
-  const ConvWeightCopies copies = (fast && tile == 0 && splitk == 0 && !d.debug) ? conv_plan_copies(d) : ConvWeightCopies{false, false, false};
+  const ConvWeightCopies copies = (fast && tile == 0 && splitk == 0 && !d.debug && !d.w_pal) ? conv_plan_copies(d) : ConvWeightCopies{false, false, false};
   if (fast && (d.tile == 9 || copies.wstream)) tile_for_wstream(sc, d, "conv2d: shape not eligible for plan tile 9 (wstream.hip)");
   if (fast && (d.tile == 11 || copies.bvgemm)) tile_for_bvgemm(sc, d, "conv2d: shape not eligible for plan tile 11 (bvgemm.hip)");
   if (fast && d.tile != 11 && d.tile != 12) ws = workspace_for(sc, {d});
@@ -439,6 +466,32 @@ int sd_op_conv2d_ex(const void* x, const void* x1, const void* w, const float* b
     e.out_twin = out_twin;
     e.plan_out = plan_out;
     conv2d_op(x, w, bias, res, out, B, Cin, H, W, Cout, ksize, stride, upsample, tile, splitk, force_generic, iters, ms, e);
+  });
+}
+
+int sd_op_conv2d_palettized(const void* x, const void* x1, const void* lut, int nbits, const uint8_t* indices, const float* bias,
+                            const void* res, void* out, int B, int Cin, int C1, int H, int W, int Cout, int ksize, int upsample, int nw,
+                            int* plan_out, int iters, float* ms) {
+  return guarded([&] {
+    SD_REQUIRE(lut && indices, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(palette_bits_ok(nbits), kInvalidArgument, "conv2d_palettized: nbits = %d, not one of 1, 2, 4, 6, 8", nbits);
+    SD_REQUIRE(nw == 0 || nw == 4 || nw == 8, kInvalidArgument, "conv2d_palettized: nw = %d, not 0, 4 or 8", nw);
+    SD_REQUIRE(B > 0 && Cin > 0 && C1 >= 0 && Cout > 0 && H > 0 && W > 0, kInvalidArgument, "conv2d_palettized: empty problem");
+    ConvOpExtra e;
+    e.x1 = x1; e.C1 = C1;
+    e.plan_out = plan_out;
+    e.pal_lut = lut; e.pal_indices = indices; e.pal_bits = nbits; e.pal_waves = nw;
+    conv2d_op(x, nullptr, bias, res, out, B, Cin, H, W, Cout, ksize, 1, upsample, 0, 0, 0, iters, ms, e);
+  });
+}
+
+int sd_op_palette_pack(const uint8_t* indices, int Cout, int Ctot, int ksize, int nbits, uint8_t* stream, size_t* bytes) {
+  return guarded([&] {
+    SD_REQUIRE(indices && bytes, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(palette_bits_ok(nbits) && (ksize == 1 || ksize == 3) && Cout > 0 && Ctot > 0 && Cout % 32 == 0 && Ctot % 32 == 0, kInvalidArgument,
+               "palette_pack: nbits %d ksize %d Cout %d Ctot %d", nbits, ksize, Cout, Ctot);
+    *bytes = wstream_pal_bytes(Cout, Ctot, ksize, nbits);
+    if (stream) wstream_pal_pack(indices, Cout, Ctot, ksize, nbits, stream);
   });
 }
 

@@ -51,6 +51,8 @@ struct Plan {
 bool can_split(const ConvDesc& d) { return d.out_mode == kOutHalf && !d.ln_colsum && !d.out_t; }
 // the weight-streaming kernel can take this conv: its pre-tiled weights exist and the shape is its own (SD_WSTREAM: tile_ok)
 bool can_stream(const ConvDesc& d) { return d.w_tiled != nullptr && can_split(d) && wstream_shape_ok(d); }
+// a palettized descriptor (plan tile 14): pinned to the palettized weight stream, it holds no fp16 weights to run anything else on
+bool pal_stream(const ConvDesc& d) { return d.w_pal != nullptr; }
 // fp32 slabs of a launch: one per split, one when only `slab` (weight stream, GroupNorm twins) asks for the slab path
 size_t slab_bytes(const Dims& a, int splits, bool slab) { return (splits > 1 || slab) ? (size_t)splits * a.M * a.N * sizeof(float) : 0; }
 
@@ -255,6 +257,14 @@ bool conv_fast_path_ok(const ConvDesc& d) {
 
 ConvPlan conv_plan(const ConvDesc& d) {
   if (!conv_fast_path_ok(d)) return ConvPlan{-1, 0, 1, false, 0};
+  if (pal_stream(d)) {   // in front of the tuner candidate, the tables and every rule: nothing moves it
+    SD_REQUIRE(d.pal_lut && can_split(d) && wstream_shape_ok(d), kInvalidArgument,
+               "plan tile 14 (wstream.hip, palettized) needs the index stream, the LUT and a shape of the weight stream");
+    ConvPlan r{14, d.staging, 1, true, 0};   // staging as on tile 9: 4 = four waves per workgroup, anything else eight
+    r.splitk = wstream_splits(d, d.staging == 4 ? 4 : 8);
+    r.workspace_bytes = slab_bytes(dims_of(d), r.splitk, true);
+    return r;
+  }
   const Switches& sw = switches();
   // the library's own rules for tiles 10-13 apply where nothing else was asked for (a tuner candidate in force also keeps them off)
   const bool free_choice = d.tile == 0 && d.splitk == 0 && d.staging == 0 && g_tune.tile == 0;
@@ -313,8 +323,9 @@ size_t conv_workspace_bytes(const ConvDesc& d) {
   const Dims a = dims_of(d);
   const Plan p = choose_plan(d, a);
   int splits = (switches().tuning && can_split(d)) ? std::max(p.splitk, 16) : p.splitk;
-  if (can_stream(d)) splits = std::max(splits, wstream_splits(d, 4));
-  return slab_bytes(a, splits, d.n_twins > 0 || can_stream(d));
+  const bool stream = can_stream(d) || (pal_stream(d) && can_split(d) && wstream_shape_ok(d));   // tile 14 as tile 9
+  if (stream) splits = std::max(splits, wstream_splits(d, 4));
+  return slab_bytes(a, splits, d.n_twins > 0 || stream);
 }
 
 ConvWeightCopies conv_plan_copies(const ConvDesc& d0) {
@@ -333,6 +344,20 @@ ConvWeightCopies conv_plan_copies(const ConvDesc& d0) {
   // large-M 1x1 GEMMs: weights global -> VGPR (bvgemm.hip) reads its own fragment-major copy; tile 10 comes first in conv_plan
   c.bvgemm = sw.bvgemm && !c.wsgemm && bvgemm_wanted(d);
   return c;
+}
+
+// Build-time question of a handle that holds a PALETTE for this conv's weights: would the conv run on the weight stream (plan tile
+// 9) if its fp16 copies were uploaded - the plan conv_plan gives it with the fragment-major copy present - and with how many waves
+// per workgroup?  0: no (the tensor is then uploaded de-palettized); 4 / 8: tile 14 with that wave count, i.e. tile 9's slab count.
+int conv_plan_pal_waves(const ConvDesc& d0) {
+  if (!conv_fast_path_ok(d0) || !switches().wstream || d0.ln_colsum || !plan_is_wstream(d0)) return 0;
+  ConvDesc d = d0;
+  static const half_t present = 0;
+  d.w_tiled = &present;   // conv_plan only tests the pointer
+  d.w_ws = d.w_bv = nullptr;
+  d.w_pal = nullptr;
+  const ConvPlan p = conv_plan(d);
+  return p.tile == 9 ? (p.staging == 4 ? 4 : 8) : 0;
 }
 
 // Does the compiled-in plan table hold a row for this shape - a plan that was measured in a step?
@@ -373,9 +398,9 @@ void conv_plan_log(const ConvDesc& d, const ConvPlan& p, int bm, int n_fast) {
   if (!on) return;
   const Dims a = dims_of(d);
   const int c1 = d.x1 ? d.C1 : 0;
-  if (p.tile == 9)
-    fprintf(stderr, "[sd conv] k%d up%d C0=%d C1=%d M=%d N=%d K=%d tile=9 nw=%d slabs=%d twins=%d\n", d.ksize, d.up, d.C0, c1, a.M, a.N, a.K,
-            p.staging == 4 ? 4 : 8, p.splitk, d.n_twins);
+  if (p.tile == 9 || p.tile == 14)
+    fprintf(stderr, "[sd conv] k%d up%d C0=%d C1=%d M=%d N=%d K=%d tile=%d nw=%d slabs=%d twins=%d bits=%d\n", d.ksize, d.up, d.C0, c1, a.M, a.N,
+            a.K, p.tile, p.staging == 4 ? 4 : 8, p.splitk, d.n_twins, p.tile == 14 ? d.pal_bits : 16);
   else if (p.tile == 12 || p.tile == 13)
     fprintf(stderr, "[sd conv] k1 s1 up1 C0=%d C1=%d M=%d N=%d K=%d mode=%d tile=%d bm=%d n_fast=%d\n", d.C0, c1, a.M, a.N, a.K, d.out_mode, p.tile, bm,
             n_fast);

@@ -8,8 +8,8 @@ namespace sd {
 
 struct ConvPlan {
   int tile;        // 1: 128x128, 2: 128x64, 3: 64x64, 4: 64x128 (igemm.hip), 7: the K-split halo conv (conv3x3_halo.hip), 9: wstream.hip,
-                   // 10: wsgemm.hip, 11: bvgemm.hip, 12: smgemm.hip, 13: smgeglu.hip; -1 = not on the MFMA path (launch_conv_generic)
-  int staging;     // ring code (tiles 1-4, 7: launch_tile / launch_halo_ks), wave-count code (9: 4 = four waves, else eight), variant (11, 12, 13)
+                   // 10: wsgemm.hip, 11: bvgemm.hip, 12: smgemm.hip, 13: smgeglu.hip, 14: wstream.hip from palettized weights; -1 = not on the MFMA path (launch_conv_generic)
+  int staging;     // ring code (tiles 1-4, 7: launch_tile / launch_halo_ks), wave-count code (9, 14: 4 = four waves, else eight), variant (11, 12, 13)
   int splitk;      // resolved: what the launch runs, no empty splits (halo: over 64-channel chunks; tile 9: the slab count)
   bool slab;       // the output leaves through fp32 slabs (split-K, weight stream, GroupNorm twins)
   size_t workspace_bytes;   // exactly what this launch needs of ConvWorkspace::partial
@@ -23,6 +23,11 @@ struct ConvWeightCopies {
   bool wstream, wsgemm, bvgemm;
 };
 ConvWeightCopies conv_plan_copies(const ConvDesc& d);
+
+// A handle that holds a palette for this conv's weights asks at build time: 4 / 8 = run it from the index stream (plan tile 14) with
+// that many waves per workgroup - the conv's plan with fp16 copies would be the weight stream with that wave count; 0 = upload the
+// de-palettized tensor and run as ever.  d.w / w_tiled / w_pal are not looked at.
+int conv_plan_pal_waves(const ConvDesc& d);
 
 // the SD_LOG_CONVS line of a launch (bm / n_fast: what smgemm.hip / smgeglu.hip add to theirs)
 void conv_plan_log(const ConvDesc& d, const ConvPlan& p, int bm = 0, int n_fast = 0);

@@ -1172,13 +1172,15 @@ int launch_conv(const ConvDesc& d, const ConvWorkspace& ws, hipStream_t s) {
   SD_REQUIRE(!twins || (d.out_mode == kOutHalf && !d.ln_colsum && !d.out_t && !d.debug && reduce_twin_ok(a.HoWo, a.N, d.n_twins, d.twin)),
              kInvalidArgument, "GroupNorm twins need a plain fp16 output and whole (sample, group) slices (HoWo=%d N=%d)", a.HoWo, a.N);
   const bool have_ws = !p.slab || (ws.partial && ws.partial_bytes >= p.workspace_bytes);
-  if (p.tile == 9) SD_REQUIRE(have_ws, kInternal, "wstream workspace too small (%zu < %zu)", ws.partial_bytes, p.workspace_bytes);
+  if (p.tile == 9 || p.tile == 14) SD_REQUIRE(have_ws, kInternal, "wstream workspace too small (%zu < %zu)", ws.partial_bytes, p.workspace_bytes);
   SD_REQUIRE(have_ws, kInternal, "split-K workspace too small (%zu < %zu)", ws.partial_bytes, p.workspace_bytes);
   conv_plan_log(d, p);
   int gn_entries = 0;
   if (p.tile == 9) {
     // weight-streaming kernel: slabs, then the group-organised combine (with the consumer's GroupNorm twins) or the plain one
     launch_wstream(d, ws.partial, p.staging == 4 ? 4 : 8, s);
+  } else if (p.tile == 14) {   // the same slabs from palettized weights, then the same combine
+    launch_wstream_pal(d, ws.partial, p.staging == 4 ? 4 : 8, s);
   } else if (p.tile == 7) {
     gn_entries = launch_halo_ks(d, p, ws.partial, s);
   } else {

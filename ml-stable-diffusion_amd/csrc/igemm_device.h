@@ -468,7 +468,7 @@ IgemmArgs planned_args(const ConvDesc& d, const ConvPlan& p, float* partial) {
   a.slab = p.slab ? 1 : 0;
   a.partial = p.slab ? partial : nullptr;
   // (the weight stream has its own arguments: these then only feed the slab combine; the halo kernel splits whole 64-channel chunks)
-  if (p.tile != 9) a.nk_per_split = cdiv(p.tile == 7 ? a.Ctot / BK : a.nk_total, p.splitk);
+  if (p.tile != 9 && p.tile != 14) a.nk_per_split = cdiv(p.tile == 7 ? a.Ctot / BK : a.nk_total, p.splitk);
   return a;
 }
 

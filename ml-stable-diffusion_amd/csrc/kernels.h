@@ -87,6 +87,12 @@ struct ConvDesc {
   int gnf_silu = 0;
   // weights in the fragment-major layout of wstream.hip (launch_wstream_retile), or null: plan tile 9 needs them
   const half_t* w_tiled = nullptr;
+  // palettized weights (plan tile 14, wstream.hip wstream_pal_kernel): the bit stream of weight_prep.h wstream_pal_pack, the
+  // tensor's LUT padded to kPalLutHalves fp16 entries, and the index width (1, 2, 4, 6, 8).  A descriptor that carries them is
+  // pinned: it has no fp16 weights (w == w_tiled == nullptr), so no table row or tuner candidate can move it
+  const uint8_t* w_pal = nullptr;
+  const half_t* pal_lut = nullptr;
+  int pal_bits = 0;
   // weights in the fragment-major layout of wsgemm.hip (launch_wsgemm_retile), or null: the weight-stationary GEGLU kernel
   // (plan tile 10) needs them; launch_conv takes that kernel whenever they are there and no other plan was forced
   const half_t* w_ws = nullptr;
@@ -126,6 +132,10 @@ int wstream_splits(const ConvDesc& d, int nw);            // slabs launch_wstrea
 size_t wstream_tiled_halves(int N, int Ctot, int ksize);
 void launch_wstream_retile(const half_t* w, half_t* wt, int N, int Ctot, int ksize, hipStream_t s);
 int launch_wstream(const ConvDesc& d, float* partial, int nw, hipStream_t s);
+// the same launch from palettized weights (d.w_pal / pal_lut / pal_bits): every weight is looked up in the LUT in front of the same
+// MFMAs in the same order, so the slabs are bit-identical to launch_wstream's on the de-palettized weights
+constexpr int kPalLutHalves = 256;
+int launch_wstream_pal(const ConvDesc& d, float* partial, int nw, hipStream_t s);
 bool reduce_twin_ok(int HW, int N, int n_twins, const GnTwin* tw);
 void launch_reduce_twin(const float* partial, int S, int M, int N, int HW, const float* bias, const float* temb, int temb_stride,
                         const half_t* res, half_t* out, int n_twins, const GnTwin* tw, hipStream_t s);

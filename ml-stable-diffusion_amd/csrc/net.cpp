@@ -12,7 +12,8 @@
 
 namespace sd {
 
-Net::Net(const sd_unet_config& cfg, const WeightStore& ws, int device) : cfg_(cfg), ws_(&ws), f32_(cfg.compute_fp32 != 0) {
+Net::Net(const sd_unet_config& cfg, const WeightStore& ws, int device)
+    : cfg_(cfg), ws_(&ws), f32_(cfg.compute_fp32 != 0), pal_tensors_((int)ws.palettes()) {
   SD_REQUIRE(cfg.n_levels >= 1 && cfg.n_levels <= SD_MAX_LEVELS, kInvalidArgument, "n_levels=%d", cfg.n_levels);
   SD_REQUIRE(cfg.batch >= 1 && cfg.height >= 1 && cfg.width >= 1, kInvalidArgument, "bad batch/size");
   SD_REQUIRE(cfg.norm_num_groups >= 1 && cfg.norm_num_groups <= 64, kUnsupported, "norm_num_groups=%d",
@@ -81,6 +82,30 @@ Tensor Net::conv(std::vector<Op>& ops, const std::string& name, const Tensor& x,
   const int cin = x.C + (a.x2 ? a.x2->C : 0);
   const bool geglu = a.out_mode == kOutGeglu;
   const float* b = a.bias ? upload_vec(name + ".bias", a.cout, geglu) : nullptr;
+  // A palettized tensor whose conv would run on the weight stream stays palettized on the device: the handle uploads the index
+  // stream and the LUT and neither fp16 copy (plan tile 14).  Every other palettized tensor is uploaded as lut[indices].
+  const Palette* pal = ws_->palette(name + ".weight");
+  const int pal_waves = (pal && !a.silu_out && !a.ln_colsum) ? conv_plan_pal_waves(conv_shape(name, x, a)) : 0;
+  if (pal_waves) {
+    const HostTensor& t = ws_->get(name + ".weight");
+    const size_t expect = (size_t)a.cout * cin * a.k * a.k;
+    SD_REQUIRE(t.numel() == expect && pal->indices.size() == expect, kInvalidArgument, "%s.weight has %zu elements, expected %zu (%d,%d,%d,%d)",
+               name.c_str(), t.numel(), expect, a.cout, cin, a.k, a.k);
+    std::vector<uint8_t> stream(wstream_pal_bytes(a.cout, cin, a.k, pal->nbits));
+    wstream_pal_pack(pal->indices.data(), a.cout, cin, a.k, pal->nbits, stream.data());
+    uint8_t* ds = ll_.arena.alloc_n<uint8_t>(stream.size());
+    SD_HIP(hipMemcpy(ds, stream.data(), stream.size(), hipMemcpyHostToDevice));
+    half_t* dl = ll_.arena.alloc_n<half_t>(kPalLutHalves);   // zero-initialised: the entries behind 2^nbits stay 0
+    SD_HIP(hipMemcpy(dl, pal->lut.data(), pal->lut.size() * sizeof(half_t), hipMemcpyHostToDevice));
+    ++pal_streamed_;
+    pal_stream_bytes_ += stream.size() + kPalLutHalves * sizeof(half_t);
+    ConvArgs ap = a;
+    ap.pal_stream = ds;
+    ap.pal_lut = dl;
+    ap.pal_bits = pal->nbits;
+    ap.pal_waves = pal_waves;
+    return conv_w(ops, name, nullptr, b, x, ap);
+  }
   const half_t* w = upload_conv_weight(name, a.cout, cin, a.k, geglu);
   return conv_w(ops, name, w, b, x, a);
 }
@@ -117,10 +142,10 @@ Tensor Net::conv_f32(std::vector<Op>& ops, const std::string& name, const Tensor
   return out;
 }
 
-Tensor Net::conv_w(std::vector<Op>& ops, const std::string& name, const half_t* w, const float* bias, const Tensor& x, const ConvArgs& a) {
+// the shape, sources and epilogue fields of a conv's descriptor: everything the planner looks at, no weights, no output
+ConvDesc Net::conv_shape(const std::string& name, const Tensor& x, const ConvArgs& a) const {
   const Tensor* x2 = a.x2;
-  const int cout = a.cout, k = a.k;
-  const bool geglu = a.out_mode == kOutGeglu, ln = a.ln_colsum != nullptr;
+  const bool ln = a.ln_colsum != nullptr;
   ConvDesc d;
   d.x0 = x.p;
   d.C0 = x.C;
@@ -129,8 +154,6 @@ Tensor Net::conv_w(std::vector<Op>& ops, const std::string& name, const half_t* 
     d.x1 = x2->p;
     d.C1 = x2->C;
   }
-  d.w = w;
-  d.bias = bias;
   d.temb = a.temb;
   d.temb_stride = kTembCap;
   d.res = a.res;
@@ -141,10 +164,10 @@ Tensor Net::conv_w(std::vector<Op>& ops, const std::string& name, const half_t* 
   d.Ho = g.Ho;
   d.Wo = g.Wo;
   d.pad = g.pad;
-  d.ksize = k;
+  d.ksize = a.k;
   d.stride = a.stride;
   d.up = a.up;
-  d.N = cout;
+  d.N = a.cout;
   d.out_mode = a.out_mode;
   d.ldT = a.ldT;
   d.ln_colsum = a.ln_colsum;
@@ -152,6 +175,23 @@ Tensor Net::conv_w(std::vector<Op>& ops, const std::string& name, const half_t* 
     d.vt_perm = a.vt_perm ? 1 : 0;
     d.q_scale = a.q_scale;
     d.q_cols = a.q_cols;
+  }
+  return d;
+}
+
+Tensor Net::conv_w(std::vector<Op>& ops, const std::string& name, const half_t* w, const float* bias, const Tensor& x, const ConvArgs& a) {
+  const Tensor* x2 = a.x2;
+  const int cout = a.cout, k = a.k;
+  const bool geglu = a.out_mode == kOutGeglu, ln = a.ln_colsum != nullptr;
+  ConvDesc d = conv_shape(name, x, a);
+  d.w = w;
+  d.bias = bias;
+  d.w_pal = a.pal_stream;
+  d.pal_lut = a.pal_lut;
+  d.pal_bits = a.pal_bits;
+  if (a.pal_stream) {   // pinned to the palettized weight stream (plan tile 14) with the wave count Net::conv read off the plan
+    d.tile = 14;
+    d.staging = a.pal_waves == 4 ? 4 : 0;
   }
   Tensor out;
   if (ln && a.n_trans > 0) {   // fused q|k|v: [M][n_trans] row-major + V^T [B][cout - n_trans][ldT]
@@ -187,7 +227,7 @@ Tensor Net::conv_w(std::vector<Op>& ops, const std::string& name, const half_t* 
   const int cin = x.C + (x2 ? x2->C : 0);
   if (conv_fast_path_ok(d) && !a.silu_out) {
     // the pre-tiled (fragment-major) weight copies the plan of this conv reads: exactly what the planner names
-    const ConvWeightCopies copies = conv_plan_copies(d);
+    const ConvWeightCopies copies = d.w_pal ? ConvWeightCopies{false, false, false} : conv_plan_copies(d);
     if (copies.wstream && !ln) {   // small-M layers: the weight-streaming kernel (plan tile 9; never a LayerNorm-fold / q|k|v op)
       half_t* wt = ll_.arena.alloc_n<half_t>(wstream_tiled_halves(cout, cin, k));
       launch_wstream_retile(w, wt, cout, cin, k, ll_.stream);
@@ -218,8 +258,10 @@ Tensor Net::conv_w(std::vector<Op>& ops, const std::string& name, const half_t* 
   char buf[320];
   // trailing "#kind,ksize,stride,up,Ctot,N,M" is the plan-table key of this op (tools/tune_plans.py)
   const int kind = d.out_t ? 3 : (geglu ? 2 : (ln ? 1 : 0));
-  snprintf(buf, sizeof(buf), "%s%s %d->%d @%dx%d M=%d K=%d %s #%d,%d,%d,%d,%d,%d,%d", k == 3 ? "conv3x3" : (geglu ? "geglu1x1" : "gemm1x1"),
-           ln ? "+ln" : "", cin, cout, d.Ho, d.Wo, x.B * d.Ho * d.Wo, cin * k * k, name.c_str(), kind, k, a.stride, a.up, cin, cout,
+  // ("+pal<bits>": the op reads its weights from their palette, plan tile 14)
+  const std::string palmark = d.w_pal ? "+pal" + std::to_string(d.pal_bits) : std::string();
+  snprintf(buf, sizeof(buf), "%s%s%s %d->%d @%dx%d M=%d K=%d %s #%d,%d,%d,%d,%d,%d,%d", k == 3 ? "conv3x3" : (geglu ? "geglu1x1" : "gemm1x1"),
+           ln ? "+ln" : "", palmark.c_str(), cin, cout, d.Ho, d.Wo, x.B * d.Ho * d.Wo, cin * k * k, name.c_str(), kind, k, a.stride, a.up, cin, cout,
            x.B * d.Ho * d.Wo);
   ops.back().label = buf;
   ops.back().flop = 2.0 * x.B * d.Ho * d.Wo * (double)cout * cin * k * k;

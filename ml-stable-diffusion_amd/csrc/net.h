@@ -70,6 +70,11 @@ struct ConvArgs {
   bool vt_perm = false;          // V^T in attention8's key order (AttnDesc::vt_perm)
   float q_scale = 1.f;           // fused q|k|v: the first q_cols columns leave pre-scaled for attention8 (ConvDesc::q_scale)
   int q_cols = 0;
+  // conv_w only, set by Net::conv for a palettized tensor that stays palettized on the device (ConvDesc::w_pal / pal_lut / pal_bits;
+  // w is then null): the op is pinned to plan tile 14 with pal_waves (4 / 8) waves per workgroup
+  const uint8_t* pal_stream = nullptr;
+  const half_t* pal_lut = nullptr;
+  int pal_bits = 0, pal_waves = 0;
 };
 
 class Net {
@@ -83,6 +88,14 @@ class Net {
   virtual void set_attention(int impl);
   void drop_graphs() { invalidate_graphs(); }   // measurement hook: the next forward re-captures (sd_tune_set_plan_table)
   size_t device_bytes() const { return ll_.arena.bytes(); }
+  size_t arena_used_bytes() const { return ll_.arena.used(); }
+  // palettes: tensors of the weight store that arrived with one, convs that read theirs on the device (plan tile 14), and the bytes
+  // of those convs' index streams and LUTs
+  void palette_info(int* n_palettized, int* n_streamed, size_t* stream_bytes) const {
+    *n_palettized = pal_tensors_;
+    *n_streamed = pal_streamed_;
+    *stream_bytes = pal_stream_bytes_;
+  }
   const sd_unet_config& config() const { return cfg_; }
 
  protected:
@@ -124,6 +137,9 @@ class Net {
   bool have_inputs_ = false;
 
  private:
+  ConvDesc conv_shape(const std::string& name, const Tensor& x, const ConvArgs& a) const;
+  int pal_tensors_ = 0, pal_streamed_ = 0;
+  size_t pal_stream_bytes_ = 0;
   Tensor conv_f32(std::vector<Op>& ops, const std::string& name, const Tensor& x, const ConvArgs& a);
   Tensor group_norm_f32(std::vector<Op>& ops, const std::string& name, const Tensor& x, float eps, bool silu);
 };

@@ -86,13 +86,14 @@ class Arena {
   template <typename T>
   T* alloc_n(size_t n) { return reinterpret_cast<T*>(alloc(n * sizeof(T))); }
   size_t bytes() const { return total_; }
+  size_t used() const { return used_; }   // the sum of the (256-B aligned) allocations, without the unused tail of any chunk
   const std::vector<void*>& chunks() const { return chunks_; }       // (debug scans: SD_NAN_TRACE)
   const std::vector<size_t>& chunk_bytes() const { return sizes_; }
 
  private:
   std::vector<void*> chunks_;
   std::vector<size_t> sizes_;
-  size_t cap_ = 0, cur_ = 0, total_ = 0;
+  size_t cap_ = 0, cur_ = 0, total_ = 0, used_ = 0;
 };
 
 template <typename T>
@@ -118,6 +119,8 @@ inline bool tune_env_set(const char* name) {
   return on && getenv(name) != nullptr;
 }
 
+// index widths of a palettized tensor (weights.h Palette; wstream.hip instantiates one kernel per width)
+inline bool palette_bits_ok(int nbits) { return nbits == 1 || nbits == 2 || nbits == 4 || nbits == 6 || nbits == 8; }
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 

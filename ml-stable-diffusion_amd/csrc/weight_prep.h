@@ -1,7 +1,10 @@
 // Host-side weight layout rules, stated once: the UNet builder (unet.cpp) and the operator entry points (capi_ops.cpp) both
 // call these, so an operator test checks the layout the step runs.  Plain host C++: no HIP call, no allocation.
 #pragma once
+#include <algorithm>
 #include <cstddef>
+#include <cstdint>
+#include <vector>
 
 #include "sd_common.h"
 
@@ -48,6 +51,45 @@ void fold_layernorm_rows(const W* w, const float* bias, const float* gamma, cons
     colsum[dst] = (float)cs;
     bias_out[dst] = (float)bb;
   }
+}
+
+// The palettized weight stream of wstream.hip (plan tile 14).  A lane of the (strip, slice) wave owns NF = 2 * taps fragments of 8
+// weights - fragment j, element e: output row strip * 32 + (lane & 31), input channel slice * 32 + (j & 1) * 16 + (lane >> 5) * 8 + e,
+// tap j >> 1 (the order of wstream_retile_kernel).  Its NF * 8 palette indices, in that order, form one little-endian bit stream of
+// nbits-wide fields (field f at bits [f * nbits, (f + 1) * nbits)), padded to whole 16-byte words; word q of every lane lies at
+// [strip][slice][q][lane][16 B], so each load instruction of the kernel is one coalesced 1-KB wave load.
+inline int wstream_pal_words(int taps, int nbits) { return (2 * taps * 8 * nbits + 127) / 128; }
+inline size_t wstream_pal_bytes(int N, int Ctot, int ksize, int nbits) {
+  return (size_t)(N / 32) * (Ctot / 32) * wstream_pal_words(ksize * ksize, nbits) * 64 * 16;
+}
+// indices [N][Ctot][k][k] (the checkpoint's order) -> the stream; dst holds wstream_pal_bytes(...) bytes
+inline void wstream_pal_pack(const uint8_t* indices, int N, int Ctot, int ksize, int nbits, uint8_t* dst) {
+  const int taps = ksize * ksize, nslices = Ctot / 32, Q = wstream_pal_words(taps, nbits), nf = 2 * taps;
+  std::vector<uint8_t> lane_bytes((size_t)Q * 16 + 8);   // one lane's stream (+ room for the last window's spill)
+  for (int strip = 0; strip < N / 32; ++strip)
+    for (int slice = 0; slice < nslices; ++slice)
+      for (int lane = 0; lane < 64; ++lane) {
+        const int n = strip * 32 + (lane & 31);
+        std::fill(lane_bytes.begin(), lane_bytes.end(), (uint8_t)0);
+        uint64_t window = 0;   // bits not yet stored, little-endian; fewer than 8 of them between fields
+        int held = 0;
+        size_t at = 0;
+        for (int j = 0; j < nf; ++j) {
+          const uint8_t* src = indices + ((size_t)n * Ctot + slice * 32 + (j & 1) * 16 + (lane >> 5) * 8) * taps + (j >> 1);
+          for (int e = 0; e < 8; ++e) {
+            window |= (uint64_t)src[(size_t)e * taps] << held;
+            held += nbits;
+            while (held >= 8) {
+              lane_bytes[at++] = (uint8_t)window;
+              window >>= 8;
+              held -= 8;
+            }
+          }
+        }
+        if (held) lane_bytes[at++] = (uint8_t)window;
+        for (int q = 0; q < Q; ++q)
+          std::copy(lane_bytes.begin() + q * 16, lane_bytes.begin() + (q + 1) * 16, dst + ((((size_t)strip * nslices + slice) * Q + q) * 64 + lane) * 16);
+      }
 }
 
 }  // namespace sd

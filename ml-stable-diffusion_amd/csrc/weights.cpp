@@ -1,5 +1,6 @@
 #include "weights.h"
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstring>
 #include <fstream>
@@ -38,6 +39,7 @@ void* Arena::alloc(size_t bytes) {
   }
   char* p = reinterpret_cast<char*>(chunks_.back()) + cur_;
   cur_ += bytes;
+  used_ += bytes;
   return p;
 }
 
@@ -72,6 +74,149 @@ void WeightStore::add(const std::string& name, const void* data, int dtype, cons
     fail(kInvalidArgument, "weights.add(%s): unknown dtype %d", name.c_str(), dtype);
   }
   map_[name] = std::move(t);
+  pal_.erase(name);   // plain values replace whatever palette the name had
+}
+
+// ---- palettes --------------------------------------------------------------------------------
+static inline uint16_t float_to_half_bits(float f) {
+  const _Float16 v = (_Float16)f;
+  uint16_t h;
+  std::memcpy(&h, &v, 2);
+  return h;
+}
+
+const Palette* WeightStore::palette(const std::string& name) const {
+  auto it = pal_.find(name);
+  return it == pal_.end() ? nullptr : &it->second;
+}
+
+namespace {
+// Optimal partition of n sorted weighted points into k contiguous ranges (least sum of squared distances to the range means).
+// dp[m][j] = min_i dp[m-1][i-1] + cost(i, j); the arg min is monotone in j, so a layer is filled by divide and conquer:
+// O(k n log n) cost evaluations, each O(1) from float64 prefix sums of count, count * v, count * v^2.  No random start, no
+// iteration: the result is the optimum and the same on every run.
+struct RangeCost {
+  std::vector<double> s0, s1, s2;   // prefix sums, entry i = points [0, i)
+  double operator()(int i, int j) const {   // points [i, j], inclusive
+    const double c = s0[j + 1] - s0[i], a = s1[j + 1] - s1[i], q = s2[j + 1] - s2[i];
+    const double e = q - a * a / c;
+    return e > 0.0 ? e : 0.0;
+  }
+  double mean(int i, int j) const { return (s1[j + 1] - s1[i]) / (s0[j + 1] - s0[i]); }
+};
+
+void dp_layer(const RangeCost& cost, const std::vector<double>& prev, std::vector<double>& cur, std::vector<int32_t>& arg, int m, int jlo,
+              int jhi, int ilo, int ihi) {
+  if (jlo > jhi) return;
+  const int j = (jlo + jhi) / 2;
+  double best = 1e300;
+  int bi = -1;
+  // range m (0-based) starts at i >= m (m ranges of at least one point in front of it) and ends at j
+  for (int i = std::max(ilo, m), hi = std::min(ihi, j); i <= hi; ++i) {
+    const double v = prev[i - 1] + cost(i, j);
+    if (v < best) {
+      best = v;
+      bi = i;
+    }
+  }
+  cur[j] = best;
+  arg[j] = bi;
+  dp_layer(cost, prev, cur, arg, m, jlo, j - 1, ilo, bi);
+  dp_layer(cost, prev, cur, arg, m, j + 1, jhi, bi, ihi);
+}
+}  // namespace
+
+double WeightStore::palettize(const std::string& name, int nbits) {
+  SD_REQUIRE(palette_bits_ok(nbits), kInvalidArgument, "palettize(%s): nbits = %d, not one of 1, 2, 4, 6, 8", name.c_str(), nbits);
+  auto it = map_.find(name);
+  if (it == map_.end()) fail(kNotFound, "palettize: the store has no tensor '%s'", name.c_str());
+  HostTensor& t = it->second;
+  const size_t n_el = t.numel();
+  const int k = 1 << nbits;
+  // histogram of the fp16-rounded values (the reference clusters weight.astype(float16)); -0 counts as +0
+  std::vector<uint16_t> hb(n_el);
+  std::vector<uint32_t> count(65536, 0);
+  for (size_t e = 0; e < n_el; ++e) {
+    uint16_t h = float_to_half_bits(t.data[e]);
+    SD_REQUIRE((h & 0x7c00) != 0x7c00, kInvalidArgument, "palettize(%s): element %zu is not finite in fp16", name.c_str(), e);
+    if (h == 0x8000) h = 0;
+    hb[e] = h;
+    ++count[h];
+  }
+  // distinct values in ascending order: negative patterns downwards, then the non-negative ones upwards
+  std::vector<uint16_t> vals;
+  for (int h = 0xfbff; h > 0x8000; --h)
+    if (count[h]) vals.push_back((uint16_t)h);
+  for (int h = 0; h < 0x7c00; ++h)
+    if (count[h]) vals.push_back((uint16_t)h);
+  const int n = (int)vals.size();
+  Palette p;
+  p.nbits = nbits;
+  p.lut.assign(k, 0);
+  std::vector<int> cluster_of(65536, 0);
+  if (n <= k) {   // every distinct value gets its own entry (the last one repeated): exact
+    for (int i = 0; i < k; ++i) p.lut[i] = n ? vals[std::min(i, n - 1)] : 0;
+    for (int i = 0; i < n; ++i) cluster_of[vals[i]] = i;
+  } else {
+    RangeCost cost;
+    cost.s0.assign(n + 1, 0.0);
+    cost.s1.assign(n + 1, 0.0);
+    cost.s2.assign(n + 1, 0.0);
+    for (int i = 0; i < n; ++i) {
+      const double v = (double)half_bits_to_float(vals[i]), c = (double)count[vals[i]];
+      cost.s0[i + 1] = cost.s0[i] + c;
+      cost.s1[i + 1] = cost.s1[i] + c * v;
+      cost.s2[i + 1] = cost.s2[i] + c * v * v;
+    }
+    std::vector<double> prev(n), cur(n);
+    std::vector<std::vector<int32_t>> arg(k, std::vector<int32_t>(n, 0));
+    for (int j = 0; j < n; ++j) prev[j] = cost(0, j);
+    for (int m = 1; m < k; ++m) {
+      std::fill(cur.begin(), cur.end(), 1e300);
+      dp_layer(cost, prev, cur, arg[m], m, m, n - 1, m, n - 1);
+      prev.swap(cur);
+    }
+    int j = n - 1;
+    for (int m = k - 1; m >= 0; --m) {   // walk the range starts back from the last point
+      const int i = m == 0 ? 0 : arg[m][j];
+      p.lut[m] = float_to_half_bits((float)cost.mean(i, j));
+      for (int q = i; q <= j; ++q) cluster_of[vals[q]] = m;
+      j = i - 1;
+    }
+  }
+  p.indices.resize(n_el);
+  double err = 0.0;
+  for (size_t e = 0; e < n_el; ++e) {
+    const int c = cluster_of[hb[e]];
+    const float v = half_bits_to_float(p.lut[c]);
+    const double dlt = (double)half_bits_to_float(hb[e]) - (double)v;
+    err += dlt * dlt;
+    p.indices[e] = (uint8_t)c;
+    t.data[e] = v;
+  }
+  pal_[name] = std::move(p);
+  return err;
+}
+
+void WeightStore::add_palettized(const std::string& name, const void* lut_f16, int nbits, const uint8_t* indices, const int64_t* shape,
+                                 int ndim) {
+  SD_REQUIRE(palette_bits_ok(nbits), kInvalidArgument, "add_palettized(%s): nbits = %d, not one of 1, 2, 4, 6, 8", name.c_str(), nbits);
+  SD_REQUIRE(lut_f16 && indices && ndim >= 0 && ndim <= 8, kInvalidArgument, "add_palettized(%s): bad arguments", name.c_str());
+  Palette p;
+  p.nbits = nbits;
+  const uint16_t* l = reinterpret_cast<const uint16_t*>(lut_f16);
+  p.lut.assign(l, l + (1 << nbits));
+  HostTensor t;
+  t.shape.assign(shape, shape + ndim);
+  const size_t n_el = t.numel();
+  for (size_t e = 0; e < n_el; ++e)
+    SD_REQUIRE(indices[e] < (1u << nbits), kInvalidArgument, "add_palettized(%s): index %u at element %zu, the palette has %d entries",
+               name.c_str(), (unsigned)indices[e], e, 1 << nbits);
+  p.indices.assign(indices, indices + n_el);
+  t.data.resize(n_el);
+  for (size_t e = 0; e < n_el; ++e) t.data[e] = half_bits_to_float(p.lut[indices[e]]);
+  map_[name] = std::move(t);
+  pal_[name] = std::move(p);
 }
 
 // Public SD 1.x / 2.x VAE checkpoints keep the deprecated attention names (query / key / value /

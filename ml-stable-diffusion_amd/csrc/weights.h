@@ -16,6 +16,15 @@ struct HostTensor {
   }
 };
 
+// A palettized tensor (the reference's fake_palettize with one group, mixed_bit_compression_pre_analysis.py:139-156): the tensor
+// the model sees is lut[indices].  The HostTensor beside it already holds those values, so every consumer of the store reads the
+// de-palettized weights unchanged; only the weight-stream conv (wstream.hip, plan tile 14) keeps the indices on the device.
+struct Palette {
+  int nbits = 0;                  // 1, 2, 4, 6 or 8
+  std::vector<uint16_t> lut;      // 2^nbits fp16 bit patterns, ascending where palettize() made them
+  std::vector<uint8_t> indices;   // one per element, in the tensor's own order
+};
+
 class WeightStore {
  public:
   void add(const std::string& name, const void* data, int dtype /*0 f16, 1 f32, 2 bf16*/,
@@ -25,9 +34,17 @@ class WeightStore {
   const HostTensor* find(const std::string& name) const;  // nullptr when absent (deprecated VAE attention names accepted)
   bool has(const std::string& name) const { return find(name) != nullptr; }
   size_t size() const { return map_.size(); }
+  // Exact 1-D k-means (dynamic programming over the sorted distinct fp16 values) of the stored tensor into 2^nbits entries; the
+  // tensor's data becomes lut[indices].  Returns the squared error against the fp16-rounded values it clustered.
+  double palettize(const std::string& name, int nbits);
+  void add_palettized(const std::string& name, const void* lut_f16, int nbits, const uint8_t* indices, const int64_t* shape, int ndim);
+  const Palette* palette(const std::string& name) const;   // nullptr: the tensor has none
+  size_t palettes() const { return pal_.size(); }
+  const std::map<std::string, HostTensor>& tensors() const { return map_; }   // name order
 
  private:
   std::map<std::string, HostTensor> map_;
+  std::map<std::string, Palette> pal_;
 };
 
 }  // namespace sd

@@ -84,11 +84,18 @@ SYMBOLS = [
     ("sd_weights_load_safetensors", _I, [_P, C.c_char_p, C.c_char_p]),
     ("sd_weights_count", _I, [_P]),
     ("sd_weights_destroy", None, [_P]),
+    ("sd_weights_tensor_info", _I, [_P, _I, C.c_char_p, _I, C.POINTER(C.c_int64), C.POINTER(_I)]),
+    ("sd_weights_palettize", _I, [_P, C.c_char_p, _I, C.POINTER(C.c_double)]),
+    ("sd_weights_add_palettized", _I, [_P, C.c_char_p, _P, _I, _P, C.POINTER(C.c_int64), _I]),
+    ("sd_weights_palette_bits", _I, [_P, C.c_char_p]),
+    ("sd_weights_read_palette", _I, [_P, C.c_char_p, _P, _P, _FP]),
     ("sd_unet_create", _I, [C.POINTER(UNetConfig), _P, _I, C.POINTER(_P)]),
     ("sd_unet_destroy", None, [_P]),
     ("sd_unet_set_attention", _I, [_P, _I]),
     ("sd_unet_num_residuals", _I, [_P]),
     ("sd_unet_device_bytes", C.c_size_t, [_P]),
+    ("sd_unet_arena_used_bytes", C.c_size_t, [_P]),
+    ("sd_unet_palette_info", _I, [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(C.c_size_t)]),
     ("sd_unet_forward", _I, [_P, C.POINTER(UNetIO)]),
     ("sd_unet_time_forward", _I, [_P, _I, _I, _FP]),
     ("sd_unet_denoise_loop", _I, [_P, C.POINTER(UNetIO), _FP, _I, _I, _FP, _FP, _FP, _I, _F, _FP, _FP]),
@@ -113,6 +120,8 @@ SYMBOLS = [
     ("sd_op_conv2d", _I, [_P, _P, _FP, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _FP]),
     ("sd_op_conv2d_ex", _I, [_P, _P, _P, _FP, _FP, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _FP, _FP, _F, _I, _P, _I, _I, _I,
                              C.POINTER(_I), _I, _FP]),
+    ("sd_op_conv2d_palettized", _I, [_P, _P, _P, _I, _P, _FP, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_I), _I, _FP]),
+    ("sd_op_palette_pack", _I, [_P, _I, _I, _I, _I, _P, C.POINTER(C.c_size_t)]),
     ("sd_op_conv2d_groupnorm", _I, [_P, _P, _FP, _P, _FP, _FP, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _I, _I, _I, C.POINTER(_I), _I, _FP]),
     ("sd_op_conv2d_groupnorm_proj", _I, [_P, _P, _FP, _P, _FP, _FP, _P, _FP, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _I, C.POINTER(_I), _I, _FP]),
     ("sd_op_conv2d_groupnorm_conv3x3", _I, [_P, _P, _FP, _P, _FP, _FP, _P, _FP, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _I, _I, _I,
@@ -366,6 +375,54 @@ def conv2d_ex(x, w, bias=None, res=None, x1=None, temb=None, stride=1, upsample=
                                 int(upsample), pad_mode, groups, fptr(gamma), fptr(beta), eps, int(silu), ptr(out_twin), tile, splitk,
                                 int(force_generic), plan, iters, C.byref(ms)))
     return out, out_twin, list(plan), ms.value
+
+
+def conv2d_palettized(x, lut, indices, nbits, bias=None, res=None, x1=None, upsample=False, nw=0, out=None, iters=1):
+    """The weight-stream conv from palettized weights (sd_op_conv2d_palettized, plan tile 14): w = lut[indices], lut (2^nbits,) f16,
+    indices (Cout, Cin + C1, k, k) uint8.  ``out``: a C-contiguous float16 buffer of at least B * Cout * Ho * Wo elements to write
+    into (tests put guards behind it).  Returns (out (B, Cout, Ho, Wo), plan, ms)."""
+    x, lut = f16(x), f16(lut)
+    indices = np.ascontiguousarray(indices, dtype=np.uint8)
+    x1 = None if x1 is None else f16(x1)
+    B, Cin, H, W = x.shape
+    C1 = 0 if x1 is None else x1.shape[1]
+    if indices.ndim != 4:
+        raise ValueError("conv2d_palettized: indices must be (Cout, Cin + C1, k, k)")
+    Cout, Ctot, k, k2 = indices.shape
+    if Ctot != Cin + C1 or k != k2 or (x1 is not None and x1.shape != (B, C1, H, W)):
+        raise ValueError("conv2d_palettized: indices / second source shape does not match input")
+    if nbits not in (1, 2, 4, 6, 8) or lut.shape != (1 << nbits,):
+        raise ValueError("conv2d_palettized: nbits must be 1, 2, 4, 6 or 8 and lut hold 2 ** nbits entries")
+    up = 2 if upsample else 1
+    Ho, Wo = H * up, W * up
+    bias = None if bias is None else f32(bias)
+    res = None if res is None else f16(res)
+    if res is not None and res.shape != (B, Cout, Ho, Wo):
+        raise ValueError("conv2d_palettized: res must be (B, Cout, Ho, Wo)")
+    n = B * Cout * Ho * Wo
+    if out is None:
+        out = np.empty(n, np.float16)
+    if out.dtype != np.float16 or not out.flags.c_contiguous or out.size < n:
+        raise ValueError("conv2d_palettized: out must be a C-contiguous float16 buffer of at least B * Cout * Ho * Wo elements")
+    plan = (C.c_int * 4)()
+    ms = C.c_float(0)
+    check(lib().sd_op_conv2d_palettized(ptr(x), ptr(x1), ptr(lut), nbits, ptr(indices), fptr(bias), ptr(res), ptr(out), B, Cin, C1, H, W,
+                                        Cout, k, int(upsample), nw, plan, iters, C.byref(ms)))
+    return out.reshape(-1)[:n].reshape(B, Cout, Ho, Wo), list(plan), ms.value
+
+
+def palette_pack(indices, nbits):
+    """The index bit stream of the palettized weight-stream conv (sd_op_palette_pack; host only): indices (Cout, Ctot, k, k) uint8
+    -> uint8 array [Cout / 32][Ctot / 32][words][64 lanes][16 bytes]."""
+    indices = np.ascontiguousarray(indices, dtype=np.uint8)
+    Cout, Ctot, k, k2 = indices.shape
+    if k != k2:
+        raise ValueError("palette_pack: indices must be (Cout, Ctot, k, k)")
+    n = C.c_size_t(0)
+    check(lib().sd_op_palette_pack(ptr(indices), Cout, Ctot, k, nbits, None, C.byref(n)))
+    stream = np.zeros(n.value, np.uint8)
+    check(lib().sd_op_palette_pack(ptr(indices), Cout, Ctot, k, nbits, ptr(stream), C.byref(n)))
+    return stream.reshape(Cout // 32, Ctot // 32, -1, 64, 16)
 
 
 def groupnorm_shortcut(x0, x1, gn_weight, gn_bias, w, bias=None, groups=32, eps=1e-5, silu=True, side=True, iters=1):

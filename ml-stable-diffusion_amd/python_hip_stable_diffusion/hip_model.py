@@ -99,6 +99,7 @@ class Weights(_lib.Handle):
 
     def __init__(self, tensors=None, safetensors_path=None, prefix=None):
         self._h = C.c_void_p()
+        self._shapes = None
         _lib.check(_lib.lib().sd_weights_create(C.byref(self._h)))
         if safetensors_path is not None:
             _lib.check(_lib.lib().sd_weights_load_safetensors(
@@ -116,9 +117,68 @@ class Weights(_lib.Handle):
         t = np.ascontiguousarray(t)
         shape = (C.c_int64 * max(1, t.ndim))(*t.shape)
         _lib.check(_lib.lib().sd_weights_add(self._h, name.encode(), _lib.ptr(t), dt, shape, t.ndim))
+        self._shapes = None
 
     def __len__(self):
         return _lib.lib().sd_weights_count(self._h)
+
+    def shapes(self):
+        """{name: shape} of every tensor of the store (listed once, kept until a tensor is added)."""
+        if self._shapes is not None:
+            return self._shapes
+        out = {}
+        name = C.create_string_buffer(512)
+        shape = (C.c_int64 * 8)()
+        ndim = C.c_int(0)
+        for i in range(len(self)):
+            _lib.check(_lib.lib().sd_weights_tensor_info(self._h, i, name, len(name), shape, C.byref(ndim)))
+            out[name.value.decode()] = tuple(int(shape[j]) for j in range(ndim.value))
+        self._shapes = out
+        return out
+
+    # ---- palettes (sd_mi355x.h "Palettized weights") ----
+    def palettize(self, name, nbits):
+        """Cluster tensor ``name`` into a LUT of 2 ** nbits fp16 entries (exact 1-D k-means) and replace it by lut[indices]; returns
+        the squared error against the fp16-rounded tensor.  ValueError: nbits not in {1, 2, 4, 6, 8}; KeyError: unknown name."""
+        err = C.c_double(0)
+        status = _lib.lib().sd_weights_palettize(self._h, name.encode(), int(nbits), C.byref(err))
+        if status == -2:
+            raise KeyError(name)
+        _lib.check(status)
+        return err.value
+
+    def add_palettized(self, name, lut, indices, nbits):
+        """Store a palette computed elsewhere: lut (2 ** nbits,) float16, indices uint8 of the tensor's shape; the tensor is
+        lut[indices]."""
+        lut = np.ascontiguousarray(lut, dtype=np.float16)
+        indices = np.ascontiguousarray(indices, dtype=np.uint8)
+        if nbits in (1, 2, 4, 6, 8) and lut.shape != (1 << nbits,):
+            raise ValueError(f"add_palettized: the LUT of a {nbits}-bit palette has {1 << nbits} entries, got {lut.shape}")
+        shape = (C.c_int64 * max(1, indices.ndim))(*indices.shape)
+        _lib.check(_lib.lib().sd_weights_add_palettized(self._h, name.encode(), _lib.ptr(lut), int(nbits), _lib.ptr(indices), shape,
+                                                        indices.ndim))
+        self._shapes = None
+
+    def palette_bits(self, name):
+        """Index width of the tensor's palette, 0 when it has none."""
+        return _lib.lib().sd_weights_palette_bits(self._h, name.encode())
+
+    def read(self, name):
+        """The stored tensor as float32 (for a palettized tensor: lut[indices])."""
+        shape = self.shapes()[name]
+        values = np.empty(shape, np.float32)
+        _lib.check(_lib.lib().sd_weights_read_palette(self._h, name.encode(), None, None, _lib.fptr(values)))
+        return values
+
+    def read_palette(self, name):
+        """(lut (2 ** nbits,) float16, indices uint8 of the tensor's shape) of a palettized tensor."""
+        nbits = self.palette_bits(name)
+        if not nbits:
+            raise ValueError(f"tensor {name!r} has no palette")
+        lut = np.empty(1 << nbits, np.float16)
+        indices = np.empty(self.shapes()[name], np.uint8)
+        _lib.check(_lib.lib().sd_weights_read_palette(self._h, name.encode(), _lib.ptr(lut), _lib.ptr(indices), None))
+        return lut, indices
 
     @classmethod
     @contextlib.contextmanager
@@ -140,7 +200,8 @@ class HipModel(_lib.Model):
     _destroy = "sd_unet_destroy"
 
     def __init__(self, config, weights, kind="unet", batch=2, latent_height=None, latent_width=None,
-                 attention_implementation="SPLIT_EINSUM", device=0, use_graph=True, context_len=77):
+                 attention_implementation="SPLIT_EINSUM", device=0, use_graph=True, context_len=77, quantize_nbits=None,
+                 palettization_recipe=None, recipe_strict=True):
         if kind not in ("unet", "controlnet"):
             raise ValueError(f"kind must be 'unet' or 'controlnet', got {kind!r}")
         if attention_implementation not in _lib.ATTENTION_IMPLEMENTATIONS:
@@ -182,7 +243,16 @@ class HipModel(_lib.Model):
         c.use_graph = int(use_graph)
         self._cfg_struct = c
         self._h = C.c_void_p()
+        if quantize_nbits is not None and palettization_recipe is not None:
+            raise ValueError("quantize_nbits and palettization_recipe are two ways to say the same thing: give one")
+        if quantize_nbits is not None and quantize_nbits not in (1, 2, 4, 6, 8):
+            raise ValueError(f"--quantize-nbits must be one of 1, 2, 4, 6, 8, got {quantize_nbits!r}")
         with Weights.lend(weights) as store:
+            if quantize_nbits is not None or palettization_recipe is not None:
+                # (torch2coreml.py:182-229 quantize_weights / mixed_bit_compression_apply.py: at conversion time there, at load time here;
+                # a store the caller lent stays palettized, as a converted model does)
+                from . import palettize
+                palettize.apply(store, nbits=quantize_nbits, recipe=palettization_recipe, strict=recipe_strict)
             _lib.check(_lib.lib().sd_unet_create(C.byref(c), store._h, device, C.byref(self._h)))
         self.batch, self.latent_height, self.latent_width = batch, h, w
         self.attention_implementation = attention_implementation
@@ -360,6 +430,18 @@ class HipModel(_lib.Model):
     @property
     def device_bytes(self):
         return _lib.lib().sd_unet_device_bytes(self._h)
+
+    @property
+    def arena_used_bytes(self):
+        """Bytes the handle's tensors occupy inside ``device_bytes`` (which counts whole 256-MiB chunks)."""
+        return _lib.lib().sd_unet_arena_used_bytes(self._h)
+
+    def palette_info(self):
+        """(tensors that arrived with a palette, convs that read theirs on the device - plan tile 14 -, bytes of those convs' index
+        streams and LUTs)."""
+        n_pal, n_str, nbytes = C.c_int(0), C.c_int(0), C.c_size_t(0)
+        _lib.check(_lib.lib().sd_unet_palette_info(self._h, C.byref(n_pal), C.byref(n_str), C.byref(nbytes)))
+        return n_pal.value, n_str.value, nbytes.value
 
     def close(self):
         if getattr(self, "_h", None) and getattr(self, "_attached", None):

@@ -490,7 +490,7 @@ def get_hip_pipe(model_dir, model_version, compute_unit="ALL", scheduler_overrid
                  force_zeros_for_empty_prompt=True, sources=None, attention_implementation="SPLIT_EINSUM",
                  num_images=1, guidance_scale=7.5, unet_batch_one=False, latent_size=None, device=0,
                  refiner_dir=None, tokenizer_factory=None, text_encoder_factory=None, vae_dtype=None, disable_safety=False,
-                 vae_encoder=False):
+                 vae_encoder=False, quantize_nbits=None, palettization_recipe=None):
     """``get_coreml_pipe`` (pipeline.py:607-697) without the conversion step: ``model_dir`` is a diffusers
     checkpoint directory (``unet/``, ``vae/``, ``text_encoder/``, ``tokenizer/``, ``scheduler/`` [,
     ``text_encoder_2/``, ``tokenizer_2/``]) instead of a folder of ``.mlpackage`` files; ControlNets are
@@ -502,7 +502,12 @@ def get_hip_pipe(model_dir, model_version, compute_unit="ALL", scheduler_overrid
     ``disable_safety``: do not load ``model_dir/safety_checker/`` (pipeline.py:650-656; ``disableSafety`` of the Swift
     configuration); a checkpoint directory without one runs unchecked either way.
     ``vae_encoder``: also build the VAE encoder from ``vae/`` (image-to-image, ``pipe(..., starting_image=, strength=)``), in the
-    decoder's precision; off by default, so a text-to-image pipeline holds no more device memory than before."""
+    decoder's precision; off by default, so a text-to-image pipeline holds no more device memory than before.
+    ``quantize_nbits`` (1, 2, 4, 6, 8) / ``palettization_recipe`` ({module: nbits}, ``palettize.load_recipe``): palettize the UNet,
+    the refiner UNet and the ControlNets at load time (torch2coreml.py:182-229 ``quantize_weights`` names exactly these models;
+    mixed_bit_compression_apply.py); the text encoder, the VAE and the safety checker stay as they are.  A recipe is the UNet's: a
+    module of it that the UNet lacks raises ``KeyError``; the ControlNets and the refiner take the modules they share with it (a
+    ControlNet has the UNet's down and mid blocks) and leave the rest of their weights fp16."""
     if not os.path.isdir(model_dir):
         raise FileNotFoundError(f"{model_dir} not found (coreml_model.py:176-178)")
     from . import text_encoder as te
@@ -525,17 +530,18 @@ def get_hip_pipe(model_dir, model_version, compute_unit="ALL", scheduler_overrid
             logger.warning("Overriding scheduler in pipeline: Override=%s", name)
         scheduler = SCHEDULER_MAP[name].from_config(sc_cfg)
 
-    def load_unet(folder, kind="unet", support_controlnet=False):
+    def load_unet(folder, kind="unet", support_controlnet=False, recipe_strict=True):
         cfg = dict(_read_json(os.path.join(folder, "config.json")))
         cfg["support_controlnet"] = support_controlnet
         size = latent_size or cfg.get("sample_size", 64)
         return HipModel(cfg, _find_weights(folder), kind=kind, batch=batch, latent_height=size, latent_width=size,
-                        attention_implementation=attention_implementation, device=device)
+                        attention_implementation=attention_implementation, device=device, quantize_nbits=quantize_nbits,
+                        palettization_recipe=palettization_recipe, recipe_strict=recipe_strict)
 
     kwargs = dict(xl=xl, force_zeros_for_empty_prompt=force_zeros_for_empty_prompt, safety_checker=None)
     logger.info("Loading models in HBM from %s", model_dir)
     kwargs["unet"] = load_unet(os.path.join(model_dir, "unet"), support_controlnet=bool(controlnet_models))
-    kwargs["controlnet"] = ([load_unet(d, kind="controlnet") for d in controlnet_models] if controlnet_models else None)
+    kwargs["controlnet"] = ([load_unet(d, kind="controlnet", recipe_strict=False) for d in controlnet_models] if controlnet_models else None)
     vcfg = _read_json(os.path.join(model_dir, "vae", "config.json"))
     lat = kwargs["unet"].latent_height
     vae_cfg = dict(latent_channels=vcfg.get("latent_channels", 4), out_channels=vcfg.get("out_channels", 3),
@@ -557,7 +563,7 @@ def get_hip_pipe(model_dir, model_version, compute_unit="ALL", scheduler_overrid
         kwargs["tokenizer_2"] = make_tok(os.path.join(model_dir, "tokenizer_2"))
         kwargs["text_encoder_2"] = make_enc(os.path.join(model_dir, "text_encoder_2"), xl=True)
         if refiner_dir:
-            kwargs["unet_refiner"] = load_unet(os.path.join(refiner_dir, "unet"))
+            kwargs["unet_refiner"] = load_unet(os.path.join(refiner_dir, "unet"), recipe_strict=False)
     else:
         kwargs["tokenizer"] = make_tok(os.path.join(model_dir, "tokenizer"))
         kwargs["text_encoder"] = make_enc(os.path.join(model_dir, "text_encoder"))
@@ -646,6 +652,13 @@ def build_parser():
                              "generator, nvidia = torch's CUDA generator (Philox)")
     parser.add_argument("--image", default=None, help="Path to starting image.")          # swift/StableDiffusionCLI/main.swift:45-49
     parser.add_argument("--strength", default=0.5, type=float, help="Strength for image2image.")
+    parser.add_argument("--quantize-nbits", default=None, choices=(1, 2, 4, 6, 8), type=int,       # torch2coreml.py:1705
+                        help="If specified, the UNet / refiner / ControlNet weights are palettized to this many bits at load time "
+                             "(k-means LUT per tensor; the conversion-time flag of torch2coreml.py)")
+    parser.add_argument("--pre-analysis-json-path", default=None,                                # mixed_bit_compression_apply.py
+                        help="The JSON file generated by mixed_bit_compression_pre_analysis.py: per-layer palettization recipes")
+    parser.add_argument("--selected-recipe", default=None,
+                        help="The string key into --pre-analysis-json-path's dict that picks the recipe to apply")
     return parser
 
 
@@ -659,11 +672,18 @@ def main(args):
     idx = os.path.join(args.i, "model_index.json")
     if xl and os.path.exists(idx):
         force_zeros = bool(_read_json(idx).get("force_zeros_for_empty_prompt", False))
+    recipe = None
+    if getattr(args, "pre_analysis_json_path", None) or getattr(args, "selected_recipe", None):
+        if not (args.pre_analysis_json_path and args.selected_recipe) or getattr(args, "quantize_nbits", None) is not None:
+            raise ValueError("--pre-analysis-json-path and --selected-recipe go together, and not with --quantize-nbits")
+        from .palettize import load_recipe
+        recipe = load_recipe(args.pre_analysis_json_path, args.selected_recipe)
     pipe = get_hip_pipe(args.i, args.model_version, args.compute_unit, scheduler_override=scheduler,
                         controlnet_models=args.controlnet, force_zeros_for_empty_prompt=force_zeros,
                         sources=args.model_sources, attention_implementation=args.attention_implementation,
                         guidance_scale=args.guidance_scale, unet_batch_one=args.unet_batch_one, refiner_dir=args.refiner,
-                        disable_safety=getattr(args, "disable_safety", False), vae_encoder=bool(getattr(args, "image", None)))
+                        disable_safety=getattr(args, "disable_safety", False), vae_encoder=bool(getattr(args, "image", None)),
+                        quantize_nbits=getattr(args, "quantize_nbits", None), palettization_recipe=recipe)
     controlnet_cond = None
     if args.controlnet:
         controlnet_cond = [prepare_controlnet_cond(args.controlnet_inputs[i], pipe.height, pipe.width)
