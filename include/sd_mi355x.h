@@ -132,8 +132,9 @@ size_t sd_unet_device_bytes(const sd_unet* u);
  * whole 256-MiB chunks they were carved from) */
 size_t sd_unet_arena_used_bytes(const sd_unet* u);
 /* Palettes of the handle's weights: *n_palettized tensors of its weight store arrived with a palette; *n_streamed convolutions read
- * theirs on the device - the small-M weight-stream convs (plan tile 14), which hold only the index bit stream and the LUT, no fp16
- * copy; *stream_bytes = the bytes of those streams and LUTs.  Every other palettized tensor was uploaded as fp16 lut[indices]. */
+ * theirs on the device - the small-M weight-stream convs (plan tile 14) and the small-M 1x1 projections proj_in / attn1.to_out.0 /
+ * attn2.to_out.0 whose plan is smgemm.hip (plan tile 15), which hold only the index bit stream and the LUT, no fp16 copy;
+ * *stream_bytes = the bytes of those streams and LUTs.  Every other palettized tensor was uploaded as fp16 lut[indices]. */
 int sd_unet_palette_info(const sd_unet* u, int* n_palettized, int* n_streamed, size_t* stream_bytes);
 
 #define SD_FLAG_DEVICE_PTRS 1 /* all data pointers are device pointers on the handle's GPU */
@@ -338,6 +339,20 @@ int sd_op_conv2d_palettized(const void* x, const void* x1, const void* lut, int 
  * (j & 1) * 16 + (lane >> 5) * 8 + e, tap j >> 1) as little-endian nbits-wide fields, padded to whole 16-byte words, word q at
  * [strip][slice][q][lane][16 B]. */
 int sd_op_palette_pack(const uint8_t* indices, int Cout, int Ctot, int ksize, int nbits, uint8_t* stream, size_t* bytes);
+/* smgemm.hip from PALETTIZED weights (plan tile 15): w = lut[indices], indices (Cout, Cin) uint8; x (B,Cin,H,W), res/out (B,Cout,H,W) f16 NCHW;
+ * bm 0 / 32 / 64 (0: by M as tile 12). Bit-identical to sd_op_conv2d(tile 141 / 142) on the fp16 weights lut[indices].
+ * plan_out[4] = {15, 1|2, 1, 0}.  Checked on the host in this order, before any device work, each SD_ERR_INVALID_ARGUMENT: nbits not in
+ * {1, 2, 4, 6, 8}; bm not in {0, 32, 64}; NULL or empty arguments; an index >= 2^nbits (the message names `index N` and its element); a
+ * shape the small-M GEMM does not tile (Cin % 64, Cout % 80, M = B*H*W % bm, at least 2 x 2 tiles, their number a multiple of 8). */
+int sd_op_gemm_palettized(const void* x, const void* lut, int nbits, const uint8_t* indices, const float* bias, const void* res, void* out,
+                          int B, int Cin, int H, int W, int Cout, int bm, int* plan_out, int iters, float* ms);
+/* The index bit stream that entry and the UNet builder put on the device (host only, no GPU): indices (Cout, K) uint8, Cout % 16 == 0,
+ * K % 64 == 0 -> *bytes = (Cout / 16) * groups * nbits * 1024 with groups = ceil(K / 512); stream may be NULL (size query).  The wave of
+ * 16-row strip n / 16 consumes K in stages of 64, in groups of 8 stages; lane l = 16 g + r16 owns, per stage s and sub-step kk = 0, 1, the
+ * indices of W[16 strip + r16][64 s + 32 kk + 8 g + e], e = 0..7.  Its 128 indices of a group, in the order (s, kk, e), are
+ * little-endian nbits-wide fields (field f at bits [f * nbits, (f + 1) * nbits)) filling exactly nbits 16-byte words; word q lies at
+ * [strip][group][q][lane][16 B].  Fields of stages beyond K / 64 in the last group are zero. */
+int sd_op_palette_pack_gemm(const uint8_t* indices, int Cout, int K, int nbits, uint8_t* stream, size_t* bytes);
 /* The same conv followed by torch.nn.GroupNorm (+ SiLU) of its output (unet.py:470-489 conv -> norm -> SiLU; stride 1, no
  * upsample): with producer_stats = 1 the GroupNorm statistics come out of the conv kernel's own epilogue (one launch less per
  * GroupNorm), with 0 from the GroupNorm's own statistics pass.  *entries (may be NULL) returns the number of partial
@@ -442,7 +457,8 @@ int sd_op_posterior_noise(const float* moments, const float* eps, const float* n
  * n_trans > 0: fused q|k|v with that many row-major columns; n_twins: GroupNorm twins written by the slab combine; gnf_groups > 0:
  * GroupNorm of the input folded into the launch; tile / staging / splitk: a forced plan (0 = the library's); copies: which pre-tiled
  * weight copies exist (1 wstream, 2 wsgemm, 4 bvgemm; -1 = the ones the library's handle would hold).
- * plan[7] = plan tile (1-4 igemm tiles, 7 halo conv, 9 wstream, 10 wsgemm, 11 bvgemm, 12 smgemm, 13 smgeglu, -1 off the MFMA path),
+ * plan[7] = plan tile (1-4 igemm tiles, 7 halo conv, 9 wstream, 10 wsgemm, 11 bvgemm, 12 smgemm, 13 smgeglu, -1 off the MFMA path; the
+ * palettized tiles 14 / 15 need a palette and are never an answer here: a handle takes 15 exactly where this says 12, sd_op_gemm_palettized),
  * staging, resolved split-K, slab (0 / 1), then the copies a handle must hold for this conv: wstream, wsgemm, bvgemm (0 / 1 each).
  * *workspace_bytes: the slab workspace this launch needs. */
 int sd_op_conv_plan(int ksize, int stride, int up, int C0, int C1, int N, int B, int Ho, int Wo, int out_mode, int flags, int n_trans,

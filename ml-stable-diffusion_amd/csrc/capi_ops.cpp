@@ -9,6 +9,7 @@
 //             in-workgroup split-K rings
 //     sd_op_conv2d / sd_op_conv2d_ex alone: 110-116 plan tile 11 (bvgemm.hip: its own choice / variants 1-6, needs w_bv),
 //                                           140-142 plan tile 12 (smgemm.hip: tile height by M / 32 rows / 64 rows)
+//     (plan tiles 14 / 15 read palettized weights: sd_op_conv2d_palettized / sd_op_gemm_palettized)
 //     sd_op_conv2d_ex is sd_op_conv2d with the ConvDesc fields the UNet / VAE builders set on top (second source, timestep embedding,
 //     the encoder's explicit padding, one GroupNorm twin) and reads the plan that ran back: plan_out = {tile, staging, splitk, slab}
 //   sd_op_geglu_ln `kernel`: 0 the library's plan, 1 the tiled igemm / gemm_pipe kernels, 2 plan tile 10 (wsgemm.hip),
@@ -492,6 +493,60 @@ int sd_op_palette_pack(const uint8_t* indices, int Cout, int Ctot, int ksize, in
                "palette_pack: nbits %d ksize %d Cout %d Ctot %d", nbits, ksize, Cout, Ctot);
     *bytes = wstream_pal_bytes(Cout, Ctot, ksize, nbits);
     if (stream) wstream_pal_pack(indices, Cout, Ctot, ksize, nbits, stream);
+  });
+}
+
+// Every check runs on the host in front of the first device call (Scratch), in the order the header lists them.
+int sd_op_gemm_palettized(const void* x, const void* lut, int nbits, const uint8_t* indices, const float* bias, const void* res, void* out,
+                          int B, int Cin, int H, int W, int Cout, int bm, int* plan_out, int iters, float* ms) {
+  return guarded([&] {
+    SD_REQUIRE(palette_bits_ok(nbits), kInvalidArgument, "gemm_palettized: nbits = %d, not one of 1, 2, 4, 6, 8", nbits);
+    SD_REQUIRE(bm == 0 || bm == 32 || bm == 64, kInvalidArgument, "gemm_palettized: bm = %d, not 0, 32 or 64", bm);
+    SD_REQUIRE(x && lut && indices && out && plan_out, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, kInvalidArgument, "gemm_palettized: empty problem");
+    const size_t n_el = (size_t)Cout * Cin;
+    for (size_t i = 0; i < n_el; ++i)
+      SD_REQUIRE(indices[i] < (1u << nbits), kInvalidArgument, "gemm_palettized: index %u at element %zu, the palette has %d entries",
+                 (unsigned)indices[i], i, 1 << nbits);
+    ConvDesc d;
+    d.C0 = Cin;
+    d.B = B; d.Hi = H; d.Wi = W; d.Ho = H; d.Wo = W;
+    d.N = Cout;
+    const int variant = bm == 32 ? 1 : (bm == 64 ? 2 : 0);
+    SD_REQUIRE(conv_fast_path_ok(d) && smgemm_shape_ok(d, variant), kInvalidArgument,
+               "gemm_palettized: shape not eligible for plan tile 15 (smgemm.hip: Cin=%d Cout=%d M=%d bm=%d - Cin a multiple of 64, Cout of 80, M of the "
+               "tile height, at least 2 x 2 tiles and a multiple of 8 of them)", Cin, Cout, B * H * W, bm);
+    Scratch sc;
+    d.x0 = upload_nhwc(sc, x, B, Cin, H, W);
+    d.bias = bias ? sc.dev<float>(Cout, bias) : nullptr;
+    if (res) d.res = upload_nhwc(sc, res, B, Cout, H, W);
+    half_t* dout = sc.dev<half_t>((size_t)B * H * W * Cout);
+    d.out = dout;
+    std::vector<uint8_t> stream(smgemm_pal_bytes(Cout, Cin, nbits));
+    smgemm_pal_pack(indices, Cout, Cin, nbits, stream.data());
+    std::vector<half_t> lut_pad(kPalLutHalves, (half_t)0);
+    std::copy(f16(lut), f16(lut) + (1 << nbits), lut_pad.begin());
+    d.w_pal = sc.dev<uint8_t>(stream.size(), stream.data());
+    d.pal_lut = sc.dev<half_t>(lut_pad.size(), lut_pad.data());
+    d.pal_bits = nbits;
+    d.pal_gemm = true;
+    d.tile = 15;
+    d.staging = variant;
+    const ConvPlan p = conv_plan(d);
+    plan_out[0] = p.tile; plan_out[1] = p.staging; plan_out[2] = p.splitk; plan_out[3] = p.slab ? 1 : 0;
+    ConvWorkspace ws;
+    sc.timed(iters, ms, [&] { launch_conv(d, ws, sc.stream); });
+    download_nchw(dout, out, B, Cout, H, W);
+  });
+}
+
+int sd_op_palette_pack_gemm(const uint8_t* indices, int Cout, int K, int nbits, uint8_t* stream, size_t* bytes) {
+  return guarded([&] {
+    SD_REQUIRE(indices && bytes, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(palette_bits_ok(nbits) && Cout > 0 && K > 0 && Cout % 16 == 0 && K % 64 == 0, kInvalidArgument,
+               "palette_pack_gemm: nbits %d Cout %d K %d", nbits, Cout, K);
+    *bytes = smgemm_pal_bytes(Cout, K, nbits);
+    if (stream) smgemm_pal_pack(indices, Cout, K, nbits, stream);
   });
 }
 

@@ -52,7 +52,9 @@ bool can_split(const ConvDesc& d) { return d.out_mode == kOutHalf && !d.ln_colsu
 // the weight-streaming kernel can take this conv: its pre-tiled weights exist and the shape is its own (SD_WSTREAM: tile_ok)
 bool can_stream(const ConvDesc& d) { return d.w_tiled != nullptr && can_split(d) && wstream_shape_ok(d); }
 // a palettized descriptor (plan tile 14): pinned to the palettized weight stream, it holds no fp16 weights to run anything else on
-bool pal_stream(const ConvDesc& d) { return d.w_pal != nullptr; }
+bool pal_stream(const ConvDesc& d) { return d.w_pal != nullptr && !d.pal_gemm; }
+// the same for the small-M 1x1 GEMM (plan tile 15): the descriptor carries the stream of smgemm_pal_pack
+bool pal_gemm(const ConvDesc& d) { return d.w_pal != nullptr && d.pal_gemm; }
 // fp32 slabs of a launch: one per split, one when only `slab` (weight stream, GroupNorm twins) asks for the slab path
 size_t slab_bytes(const Dims& a, int splits, bool slab) { return (splits > 1 || slab) ? (size_t)splits * a.M * a.N * sizeof(float) : 0; }
 
@@ -265,6 +267,11 @@ ConvPlan conv_plan(const ConvDesc& d) {
     r.workspace_bytes = slab_bytes(dims_of(d), r.splitk, true);
     return r;
   }
+  if (pal_gemm(d)) {   // pinned like tile 14; staging 1 / 2 = 32- / 64-row tiles (0: by M, resolved here), no workspace
+    SD_REQUIRE(d.pal_lut && palette_bits_ok(d.pal_bits) && !d.x1 && d.staging >= 0 && d.staging <= 2 && smgemm_shape_ok(d, d.staging), kInvalidArgument,
+               "plan tile 15 (smgemm.hip, palettized) needs the index stream, the LUT and a single-source shape of the small-M GEMM");
+    return ConvPlan{15, smgemm_bm(d, d.staging) == 32 ? 1 : 2, 1, false, 0};
+  }
   const Switches& sw = switches();
   // the library's own rules for tiles 10-13 apply where nothing else was asked for (a tuner candidate in force also keeps them off)
   const bool free_choice = d.tile == 0 && d.splitk == 0 && d.staging == 0 && g_tune.tile == 0;
@@ -319,7 +326,7 @@ ConvPlan conv_plan(const ConvDesc& d) {
 //   - with the weight-stream copy present, its slab count at four waves per workgroup (the most slabs it writes);
 //   - the unresolved split-K (the launch may use fewer splits), one slab when only the GroupNorm twins ask for it.
 size_t conv_workspace_bytes(const ConvDesc& d) {
-  if (!conv_fast_path_ok(d)) return 0;
+  if (!conv_fast_path_ok(d) || pal_gemm(d)) return 0;   // (tile 15: no slabs)
   const Dims a = dims_of(d);
   const Plan p = choose_plan(d, a);
   int splits = (switches().tuning && can_split(d)) ? std::max(p.splitk, 16) : p.splitk;
@@ -358,6 +365,24 @@ int conv_plan_pal_waves(const ConvDesc& d0) {
   d.w_pal = nullptr;
   const ConvPlan p = conv_plan(d);
   return p.tile == 9 ? (p.staging == 4 ? 4 : 8) : 0;
+}
+
+// The same question for plan tile 15: would this conv, uploaded as fp16 with the copies a handle would hold, get plan tile 12 by the
+// library's own rule?  conv_plan itself answers (one predicate: SD_SMGEMM=0, a tuner candidate, a forced plan, GroupNorm statistics
+// asked of it or a shape smgemm_wanted refuses all give another tile there); 32 / 64 = the tile height tile 12 would run.
+int conv_plan_pal_gemm(const ConvDesc& d0) {
+  if (!conv_fast_path_ok(d0) || !switches().smgemm || d0.ln_colsum || d0.x1) return 0;
+  ConvDesc d = d0;
+  d.w_pal = nullptr;
+  d.pal_gemm = false;
+  d.w_tiled = d.w_ws = d.w_bv = nullptr;
+  static const half_t present = 0;   // conv_plan only tests the pointers
+  const ConvWeightCopies c = conv_plan_copies(d);
+  if (c.wstream) d.w_tiled = &present;
+  if (c.wsgemm) d.w_ws = &present;
+  if (c.bvgemm) d.w_bv = &present;
+  const ConvPlan p = conv_plan(d);
+  return p.tile == 12 ? smgemm_bm(d, p.staging) : 0;
 }
 
 // Does the compiled-in plan table hold a row for this shape - a plan that was measured in a step?
@@ -404,6 +429,9 @@ void conv_plan_log(const ConvDesc& d, const ConvPlan& p, int bm, int n_fast) {
   else if (p.tile == 12 || p.tile == 13)
     fprintf(stderr, "[sd conv] k1 s1 up1 C0=%d C1=%d M=%d N=%d K=%d mode=%d tile=%d bm=%d n_fast=%d\n", d.C0, c1, a.M, a.N, a.K, d.out_mode, p.tile, bm,
             n_fast);
+  else if (p.tile == 15)
+    fprintf(stderr, "[sd conv] k1 s1 up1 C0=%d C1=%d M=%d N=%d K=%d mode=%d tile=%d bm=%d n_fast=%d bits=%d\n", d.C0, c1, a.M, a.N, a.K, d.out_mode,
+            p.tile, bm, n_fast, d.pal_bits);
   else
     fprintf(stderr, "[sd conv] k%d s%d up%d C0=%d C1=%d M=%d N=%d K=%d mode=%d tile=%d splitk=%d\n", d.ksize, d.stride, d.up, d.C0, c1, a.M, a.N,
             a.K, d.out_mode, p.tile, p.splitk);

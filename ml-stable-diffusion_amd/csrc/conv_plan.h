@@ -8,8 +8,10 @@ namespace sd {
 
 struct ConvPlan {
   int tile;        // 1: 128x128, 2: 128x64, 3: 64x64, 4: 64x128 (igemm.hip), 7: the K-split halo conv (conv3x3_halo.hip), 9: wstream.hip,
-                   // 10: wsgemm.hip, 11: bvgemm.hip, 12: smgemm.hip, 13: smgeglu.hip, 14: wstream.hip from palettized weights; -1 = not on the MFMA path (launch_conv_generic)
-  int staging;     // ring code (tiles 1-4, 7: launch_tile / launch_halo_ks), wave-count code (9, 14: 4 = four waves, else eight), variant (11, 12, 13)
+                   // 10: wsgemm.hip, 11: bvgemm.hip, 12: smgemm.hip, 13: smgeglu.hip, 14: wstream.hip from palettized weights,
+                   // 15: smgemm.hip from palettized weights; -1 = not on the MFMA path (launch_conv_generic)
+  int staging;     // ring code (tiles 1-4, 7: launch_tile / launch_halo_ks), wave-count code (9, 14: 4 = four waves, else eight), variant (11, 12, 13),
+                   // tile height (15: 1 / 2 = 32 / 64 rows)
   int splitk;      // resolved: what the launch runs, no empty splits (halo: over 64-channel chunks; tile 9: the slab count)
   bool slab;       // the output leaves through fp32 slabs (split-K, weight stream, GroupNorm twins)
   size_t workspace_bytes;   // exactly what this launch needs of ConvWorkspace::partial
@@ -28,6 +30,10 @@ ConvWeightCopies conv_plan_copies(const ConvDesc& d);
 // that many waves per workgroup - the conv's plan with fp16 copies would be the weight stream with that wave count; 0 = upload the
 // de-palettized tensor and run as ever.  d.w / w_tiled / w_pal are not looked at.
 int conv_plan_pal_waves(const ConvDesc& d);
+// The same question for the small-M 1x1 GEMM (plan tile 15): 32 / 64 = this conv, uploaded as fp16 with the copies a handle would hold,
+// would get plan tile 12 by the library's own rule with that tile height - run it from the index stream of smgemm_pal_pack instead;
+// 0 = no (SD_SMGEMM=0, two sources, a LayerNorm fold, any other plan): upload the de-palettized tensor.
+int conv_plan_pal_gemm(const ConvDesc& d);
 
 // the SD_LOG_CONVS line of a launch (bm / n_fast: what smgemm.hip / smgeglu.hip add to theirs)
 void conv_plan_log(const ConvDesc& d, const ConvPlan& p, int bm = 0, int n_fast = 0);

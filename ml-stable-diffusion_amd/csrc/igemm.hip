@@ -1165,6 +1165,7 @@ int launch_conv(const ConvDesc& d, const ConvWorkspace& ws, hipStream_t s) {
     case 11: launch_bvgemm(d, p.staging, s); return 0;
     case 12: launch_smgemm(d, p.staging, s); return 0;
     case 13: launch_smgeglu(d, p.staging, s); return 0;
+    case 15: launch_smgemm_pal(d, p.staging, s); return 0;   // (d.gn_partial set: no statistics, 0 entries - the GroupNorm runs its own pass)
     default: break;
   }
   IgemmArgs a = planned_args(d, p, ws.partial);

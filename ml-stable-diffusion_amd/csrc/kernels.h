@@ -93,6 +93,9 @@ struct ConvDesc {
   const uint8_t* w_pal = nullptr;
   const half_t* pal_lut = nullptr;
   int pal_bits = 0;
+  // pal_gemm: w_pal is the bit stream of weight_prep.h smgemm_pal_pack instead and the descriptor is pinned to plan tile 15
+  // (smgemm.hip smgemm_pal_kernel; staging 1 / 2 = 32- / 64-row tiles, 0 = by M as tile 12)
+  bool pal_gemm = false;
   // weights in the fragment-major layout of wsgemm.hip (launch_wsgemm_retile), or null: the weight-stationary GEGLU kernel
   // (plan tile 10) needs them; launch_conv takes that kernel whenever they are there and no other plan was forced
   const half_t* w_ws = nullptr;
@@ -158,6 +161,11 @@ bool bvgemm_wanted(const ConvDesc& d);                                // the lib
 bool smgemm_shape_ok(const ConvDesc& d, int variant);                 // variant 1 / 2: 32- / 64-row tiles, 0: by M
 bool smgemm_wanted(const ConvDesc& d);                                // the library's rule for taking plan tile 12 on its own
 void launch_smgemm(const ConvDesc& d, int variant, hipStream_t s);
+int smgemm_bm(const ConvDesc& d, int variant);                        // the tile height launch_smgemm / launch_smgemm_pal run: 32 or 64
+// the same GEMM from palettized weights (plan tile 15: d.w_pal in the layout of weight_prep.h smgemm_pal_pack, d.pal_lut, d.pal_bits):
+// the weights are decoded from the LUT into the fragments of the same MFMAs in the same order, the epilogue is launch_smgemm's, so
+// the output is bit-identical to launch_smgemm's on the fp16 weights lut[indices].  One source only.
+void launch_smgemm_pal(const ConvDesc& d, int variant, hipStream_t s);
 
 // wfold.hip: two back-to-back linear maps folded into one - merged [N][K + J] = [fp16(Wp W2) | Wp], bm = bp + Wp b2 (Wp [N][J],
 // W2 [J][K]; fp32 accumulation in a fixed order, once per handle: UNet::transformer_block's merged tail)

@@ -82,17 +82,21 @@ Tensor Net::conv(std::vector<Op>& ops, const std::string& name, const Tensor& x,
   const int cin = x.C + (a.x2 ? a.x2->C : 0);
   const bool geglu = a.out_mode == kOutGeglu;
   const float* b = a.bias ? upload_vec(name + ".bias", a.cout, geglu) : nullptr;
-  // A palettized tensor whose conv would run on the weight stream stays palettized on the device: the handle uploads the index
-  // stream and the LUT and neither fp16 copy (plan tile 14).  Every other palettized tensor is uploaded as lut[indices].
+  // A palettized tensor stays palettized on the device where a kernel reads palettes: the handle uploads the index stream and the LUT
+  // and no fp16 copy.  In this order: the weight stream (plan tile 14) where the conv's plan would be tile 9; else, where the call site
+  // opted in (ConvArgs::pal_gemm), the small-M GEMM (plan tile 15) where its plan would be tile 12; else lut[indices] as fp16.
   const Palette* pal = ws_->palette(name + ".weight");
-  const int pal_waves = (pal && !a.silu_out && !a.ln_colsum) ? conv_plan_pal_waves(conv_shape(name, x, a)) : 0;
-  if (pal_waves) {
+  const bool pal_ok = pal && !a.silu_out && !a.ln_colsum;
+  const int pal_waves = pal_ok ? conv_plan_pal_waves(conv_shape(name, x, a)) : 0;
+  const int pal_bm = (pal_ok && !pal_waves && a.pal_gemm && a.k == 1 && !a.x2 && a.out_mode == kOutHalf) ? conv_plan_pal_gemm(conv_shape(name, x, a)) : 0;
+  if (pal_waves || pal_bm) {
     const HostTensor& t = ws_->get(name + ".weight");
     const size_t expect = (size_t)a.cout * cin * a.k * a.k;
     SD_REQUIRE(t.numel() == expect && pal->indices.size() == expect, kInvalidArgument, "%s.weight has %zu elements, expected %zu (%d,%d,%d,%d)",
                name.c_str(), t.numel(), expect, a.cout, cin, a.k, a.k);
-    std::vector<uint8_t> stream(wstream_pal_bytes(a.cout, cin, a.k, pal->nbits));
-    wstream_pal_pack(pal->indices.data(), a.cout, cin, a.k, pal->nbits, stream.data());
+    std::vector<uint8_t> stream(pal_waves ? wstream_pal_bytes(a.cout, cin, a.k, pal->nbits) : smgemm_pal_bytes(a.cout, cin, pal->nbits));
+    if (pal_waves) wstream_pal_pack(pal->indices.data(), a.cout, cin, a.k, pal->nbits, stream.data());
+    else smgemm_pal_pack(pal->indices.data(), a.cout, cin, pal->nbits, stream.data());
     uint8_t* ds = ll_.arena.alloc_n<uint8_t>(stream.size());
     SD_HIP(hipMemcpy(ds, stream.data(), stream.size(), hipMemcpyHostToDevice));
     half_t* dl = ll_.arena.alloc_n<half_t>(kPalLutHalves);   // zero-initialised: the entries behind 2^nbits stay 0
@@ -104,6 +108,7 @@ Tensor Net::conv(std::vector<Op>& ops, const std::string& name, const Tensor& x,
     ap.pal_lut = dl;
     ap.pal_bits = pal->nbits;
     ap.pal_waves = pal_waves;
+    ap.pal_bm = pal_bm;
     return conv_w(ops, name, nullptr, b, x, ap);
   }
   const half_t* w = upload_conv_weight(name, a.cout, cin, a.k, geglu);
@@ -189,7 +194,11 @@ Tensor Net::conv_w(std::vector<Op>& ops, const std::string& name, const half_t* 
   d.w_pal = a.pal_stream;
   d.pal_lut = a.pal_lut;
   d.pal_bits = a.pal_bits;
-  if (a.pal_stream) {   // pinned to the palettized weight stream (plan tile 14) with the wave count Net::conv read off the plan
+  if (a.pal_stream && a.pal_bm) {   // pinned to the palettized small-M GEMM (plan tile 15) with the tile height Net::conv read off the plan
+    d.pal_gemm = true;
+    d.tile = 15;
+    d.staging = a.pal_bm == 32 ? 1 : 2;
+  } else if (a.pal_stream) {   // pinned to the palettized weight stream (plan tile 14) with the wave count Net::conv read off the plan
     d.tile = 14;
     d.staging = a.pal_waves == 4 ? 4 : 0;
   }
@@ -258,7 +267,7 @@ Tensor Net::conv_w(std::vector<Op>& ops, const std::string& name, const half_t* 
   char buf[320];
   // trailing "#kind,ksize,stride,up,Ctot,N,M" is the plan-table key of this op (tools/tune_plans.py)
   const int kind = d.out_t ? 3 : (geglu ? 2 : (ln ? 1 : 0));
-  // ("+pal<bits>": the op reads its weights from their palette, plan tile 14)
+  // ("+pal<bits>": the op reads its weights from their palette, plan tile 14 or 15)
   const std::string palmark = d.w_pal ? "+pal" + std::to_string(d.pal_bits) : std::string();
   snprintf(buf, sizeof(buf), "%s%s%s %d->%d @%dx%d M=%d K=%d %s #%d,%d,%d,%d,%d,%d,%d", k == 3 ? "conv3x3" : (geglu ? "geglu1x1" : "gemm1x1"),
            ln ? "+ln" : "", palmark.c_str(), cin, cout, d.Ho, d.Wo, x.B * d.Ho * d.Wo, cin * k * k, name.c_str(), kind, k, a.stride, a.up, cin, cout,

@@ -75,6 +75,12 @@ struct ConvArgs {
   const uint8_t* pal_stream = nullptr;
   const half_t* pal_lut = nullptr;
   int pal_bits = 0, pal_waves = 0;
+  // conv: the call site opts in to keeping a palettized 1x1 projection on the device as plan tile 15 (smgemm.hip from the index stream).
+  // A pinned op cannot move to igemm_kernel when a later GroupNorm asks for epilogue statistics, so only call sites whose output
+  // feeds no GroupNorm set it (proj_in and the two to_out.0 of a transformer block feed LayerNorms).  conv_w: pal_bm = 32 / 64, the
+  // tile height Net::conv read off the plan (pal_stream is then the stream of smgemm_pal_pack)
+  bool pal_gemm = false;
+  int pal_bm = 0;
 };
 
 class Net {
@@ -89,8 +95,8 @@ class Net {
   void drop_graphs() { invalidate_graphs(); }   // measurement hook: the next forward re-captures (sd_tune_set_plan_table)
   size_t device_bytes() const { return ll_.arena.bytes(); }
   size_t arena_used_bytes() const { return ll_.arena.used(); }
-  // palettes: tensors of the weight store that arrived with one, convs that read theirs on the device (plan tile 14), and the bytes
-  // of those convs' index streams and LUTs
+  // palettes: tensors of the weight store that arrived with one, convs that read theirs on the device (plan tiles 14 and 15), and
+  // the bytes of those convs' index streams and LUTs
   void palette_info(int* n_palettized, int* n_streamed, size_t* stream_bytes) const {
     *n_palettized = pal_tensors_;
     *n_streamed = pal_streamed_;

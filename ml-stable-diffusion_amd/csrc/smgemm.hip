@@ -19,10 +19,12 @@
 //   * epilogue from the accumulators: fp16 pairs of two 16-row blocks meet through v_permlane16_swap, every lane stores 16 B of
 //     one output row; no LDS, no barrier.
 #include <algorithm>
+#include <utility>
 
 #include "conv_plan.h"
 #include "kernels.h"
 #include "sm_ring.h"
+#include "weight_prep.h"
 
 namespace sd {
 
@@ -194,6 +196,284 @@ __global__ __launch_bounds__(64 * SM_NW, 1) void smgemm_kernel(SmArgs a) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The same GEMM from PALETTIZED weights (plan tile 15).  Geometry, MFMAs, their order per accumulator block (ascending K64 stage, then
+// kk = 0, 1), tile order and epilogue are smgemm_kernel's, so the output is bit-identical to smgemm_kernel<BM> on lut[indices].  What
+// differs is where the weight fragment comes from:
+//   * no fp16 weight exists anywhere.  Lane (g, r16) of wave w owns the bit stream of its palette indices (weight_prep.h
+//     smgemm_pal_pack: NBITS coalesced 16-B words per GROUP of 8 stages), keeps the current group's words in registers and turns every
+//     index into one 2-byte LDS read of the LUT, placed in the low or high half of a fragment register.  Field positions are
+//     compile-time constants (the 8 stages of a group are unrolled); the two fragments of stage s + 1 are decoded beside the MFMAs of
+//     stage s (register double buffer wf[2]);
+//   * the index words arrive by LDS-DMA too: one 1-KB piece per word into the wave's own two group buffers, from where the lane
+//     takes its 16 B back with one ds_read_b128 per word and group.  They were ordinary loads first; hipcc then waits vmcnt(0) in front
+//     of EVERY use of a word register while LDS-DMA is in flight (seen in the assembly: one full drain of the ring per stage), and
+//     the loads cannot be hidden from it without inline assembly.  As pieces they are counted by hand with everything else;
+//   * the LUT (zero-padded to kPalLutHalves) is ONE COPY PER WAVE, brought by two 4-byte LDS-DMA pieces of the wave itself in front of
+//     everything else: no barrier and no register pass of its own - the counted wait for stage 0 retires it (pieces retire in
+//     order), and a workgroup copy would make five waves share its two pieces unevenly;
+//   * the ring holds the BM activation rows only: NST = 16 / 8 stages of K64 (BM = 32 / 64), BM / 8 pieces of 1 KB each.  Five waves
+//     issue PPW = 1 / 2 pieces per stage; the 1 / 2 pieces beyond BM / 8 repeat activation rows into a dump slot behind the ring that
+//     nothing reads, so every wave issues the same number of pieces and one immediate serves all.
+// Order of the LDS-DMA pieces of a wave (they share vmcnt and retire in order; the only ordinary loads, bias and residual rows, come
+// first and are used behind the loop):
+//     [LUT: 2] [W_0 -> buffer 0: NBITS] [W_1 -> buffer 1: NBITS] [stages 0 .. NST - 2]                          prologue
+//     step rel = 8 j + t:  wait for stage rel -> [t == 0: W_(j+2) -> buffer j & 1] [stage rel + NST - 1, if < nk]
+// (W_i: the words of group min(i, groups - 1) - behind the last group it is loaded again, so the count is the same at every step).
+// Group j + 1 moves from its buffer to registers in step 8 j + 7: W_(j+1) is older than stage 8 j + 7 (issued in step 8 (j - 1) in
+// front of stage 8 (j - 1) + NST - 1 <= 8 j + 7), whose wait that step has passed; group 0 in step 0.  Buffer j & 1 is re-filled in
+// step 8 j behind an lgkmcnt(0): the reads that emptied it are done.
+// Younger than stage rel at the wait of step rel are the `ahead` = min(NST - 2, nk - 1 - rel) stages behind it and every batch W
+// issued in a step 8 u < rel with rel <= 8 u + NST - 2 (the last stage issued in front of it):
+//     u = j:      0 < t <= NST - 2
+//     u = j - 1:  j > 0 and t + 8 <= NST - 2         (u = j - 2: t + 16 <= NST - 2, never for NST <= 17)
+//     vmcnt immediate = PPW * ahead + NBITS * (number of those batches).
+// t is a compile-time constant of the unrolled group body, j > 0 its `FIRST = false` instantiation.
+struct SmPalArgs {
+  const half_t* x;      // [M][K]
+  const uint8_t* pal;   // [N / 16][groups][NBITS][64 lanes][16 B]
+  const half_t* lut;    // kPalLutHalves entries
+  const float* bias;    // as SmArgs
+  const half_t* res;
+  half_t* out;
+  int K, N, nk, ngroups, res_ld;
+  int has_bias, has_res;
+  unsigned per_xcd, fast_div, fast_magic;
+  int n_fast;
+};
+
+template <int BM, int NBITS>
+struct SmPalCfg {
+  static constexpr int PIECES = BM / 8;                          // 1-KiB pieces of real activation rows per stage
+  static constexpr int PPW = (PIECES + SM_NW - 1) / SM_NW;       // pieces per wave per stage
+  static constexpr int PAD = SM_NW * PPW - PIECES;               // padding pieces per stage: into the dump slots
+  static constexpr int STAGE = PIECES * 1024;
+  static constexpr int NST = 512 / BM;                           // 64 KB of ring
+  static constexpr int G = kSmPalGroup;
+  static constexpr int DUMP = NST * STAGE;                       // byte offsets behind the ring
+  static constexpr int LUT = DUMP + PAD * 1024;                  // SM_NW copies
+  static constexpr int WORDS = LUT + SM_NW * kPalLutHalves * 2;  // per wave: two group buffers of NBITS KB
+  static constexpr int LDS = WORDS + SM_NW * 2 * NBITS * 1024;
+  static constexpr int TM = BM / 16;
+  // index-word batches younger than stage 8 j + t at its wait (header comment)
+  static constexpr int batches(int t, bool first) { return ((t > 0 && t <= NST - 2) ? 1 : 0) + ((!first && t + G <= NST - 2) ? 1 : 0); }
+  static_assert(BM % 32 == 0 && LDS <= SM_LDS, "tile");
+  static_assert(G == 8 && NST >= G && NST <= 2 * G, "the batch count above, and group j + 1 landed by step 8 j + 7");
+  static_assert(PPW * (NST - 2) + 2 * NBITS <= 63, "vmcnt range");
+};
+
+typedef unsigned sm_uintx4 __attribute__((ext_vector_type(4)));
+
+template <int... I, typename F>
+__device__ __forceinline__ void sm_static_for(std::integer_sequence<int, I...>, F&& f) {
+  (f(std::integral_constant<int, I>{}), ...);
+}
+
+template <int BM, int NBITS>
+__global__ __launch_bounds__(64 * SM_NW, 1) void smgemm_pal_kernel(SmPalArgs a) {
+  using C = SmPalCfg<BM, NBITS>;
+  constexpr int NST = C::NST, PPW = C::PPW, TM = C::TM, Q = NBITS, G = C::G;
+  constexpr unsigned MASK = (1u << NBITS) - 1u;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+
+  const unsigned t_id = (blockIdx.x & 7u) * a.per_xcd + (blockIdx.x >> 3);
+  const unsigned slow = __umulhi(t_id, a.fast_magic);
+  const unsigned fast = t_id - slow * a.fast_div;
+  const int m_blk = (int)(a.n_fast ? slow : fast) * BM;
+  const int n_blk = (int)(a.n_fast ? fast : slow) * SM_BN;
+  const int g = lane >> 4, r16 = lane & 15;
+
+  // ---- epilogue operands first (nothing in the K loop counts them), in the store layout as in smgemm_kernel ----
+  const floatx4 bias4 = *reinterpret_cast<const floatx4*>(a.bias + n_blk + 16 * wave + 4 * g);
+  half8 resv[TM / 2];
+#pragma unroll
+  for (int p = 0; p < TM / 2; ++p)
+    resv[p] = *reinterpret_cast<const half8*>(a.res + (size_t)(m_blk + 32 * p + 16 * (g & 1) + r16) * a.res_ld + n_blk + 16 * wave +
+                                              8 * (g >> 1));
+  __builtin_amdgcn_sched_barrier(0);
+  // ---- this wave's copy of the LUT: 2 x (64 lanes x 4 B) by LDS-DMA ----
+  char* const lut_lds = smem + C::LUT + wave * (kPalLutHalves * 2);
+#pragma unroll
+  for (int h = 0; h < 2; ++h)
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a.lut + h * 128 + lane * 2),
+                                     (__attribute__((address_space(3))) void*)(lut_lds + h * 256), 4, 0, 0);
+  const unsigned short* const lutp = reinterpret_cast<const unsigned short*>(lut_lds);
+  // ---- index words: batch W_i = group min(i, groups - 1) into this wave's buffer i & 1 ----
+  char* const wbuf = smem + C::WORDS + wave * (2 * Q * 1024);
+  const sm_uintx4* const wbase = reinterpret_cast<const sm_uintx4*>(a.pal) + (size_t)(n_blk / 16 + wave) * a.ngroups * (Q * 64) + lane;
+  auto issue_words = [&](int i) __attribute__((always_inline)) {
+    const sm_uintx4* p = wbase + (size_t)min(i, a.ngroups - 1) * (Q * 64);
+    char* dst = wbuf + (i & 1) * (Q * 1024);
+#pragma unroll
+    for (int q = 0; q < Q; ++q)
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(p + q * 64),
+                                       (__attribute__((address_space(3))) void*)(dst + q * 1024), 16, 0, 0);
+  };
+  auto read_words = [&](sm_uintx4(&wq)[Q], int grp) __attribute__((always_inline)) {
+    const char* srcw = wbuf + (grp & 1) * (Q * 1024) + lane * 16;
+#pragma unroll
+    for (int q = 0; q < Q; ++q) wq[q] = *reinterpret_cast<const sm_uintx4*>(srcw + q * 1024);
+  };
+  issue_words(0);
+  issue_words(1);
+
+  // ---- activation staging: piece wave + 5 j of every stage; pieces >= BM / 8 repeat rows into their dump slot ----
+  const half_t* src[PPW];
+#pragma unroll
+  for (int j = 0; j < PPW; ++j) {
+    const int p = wave + SM_NW * j;
+    const int pr = p >= C::PIECES ? p - C::PIECES : p;
+    const int r = pr * 8 + (lane >> 3);                   // activation row of the tile
+    const int chunk = (lane & 7) ^ ((r >> 1) & 7);        // logical chunk at physical slot lane & 7
+    src[j] = a.x + (size_t)(m_blk + r) * a.K + chunk * 8;
+  }
+  auto issue = [&](int idx) __attribute__((always_inline)) {
+#pragma unroll
+    for (int j = 0; j < PPW; ++j) {
+      const int p = wave + SM_NW * j;                     // wave-uniform
+      char* dst = p >= C::PIECES ? smem + C::DUMP + (p - C::PIECES) * 1024 : smem + (idx % NST) * C::STAGE + p * 1024;
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src[j],
+                                       (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+      src[j] += SM_BK;
+    }
+  };
+#pragma unroll
+  for (int p = 0; p < NST - 1; ++p)
+    if (p < a.nk) issue(p);
+  __builtin_amdgcn_sched_barrier(0);
+
+  int foff[2];
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk) foff[kk] = r16 * 128 + (((4 * kk + g) ^ ((r16 >> 1) & 7)) * 16);
+
+  floatx4 acc[TM];
+#pragma unroll
+  for (int i = 0; i < TM; ++i) acc[i] = floatx4{0.f, 0.f, 0.f, 0.f};
+
+  // the two weight fragments of stage t of a group: field f = (2 t + kk) * 8 + e of the lane's stream; a field that straddles a dword
+  // is one funnel shift (wstream.hip decode_tap)
+  auto decode = [&](half8(&wf)[2], const sm_uintx4(&wq)[Q], auto tc) __attribute__((always_inline)) {
+    constexpr int t = decltype(tc)::value;
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      sm_uintx4 pk = {0u, 0u, 0u, 0u};
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int bit = ((t * 2 + kk) * 8 + e) * NBITS, dw = bit >> 5, sh = bit & 31;
+        const unsigned lo = wq[dw >> 2][dw & 3];
+        unsigned idx;
+        if (sh + NBITS <= 32) {
+          idx = (lo >> sh) & MASK;
+        } else {
+          const int dn = dw + 1;   // (inside the group's words: the field ends in it)
+          idx = __builtin_amdgcn_alignbit(wq[dn >> 2][dn & 3], lo, sh) & MASK;
+        }
+        const unsigned v = lutp[idx];
+        pk[e >> 1] = (e & 1) ? (pk[e >> 1] | (v << 16)) : v;
+      }
+      wf[kk] = __builtin_bit_cast(half8, pk);
+    }
+  };
+
+  half8 wf[2][2];   // [stage parity][kk]
+  // one group of 8 stages: `cur` holds its words, `nxt` receives the next group's in its last stage
+  auto run_group = [&](auto first_c, sm_uintx4(&cur)[Q], sm_uintx4(&nxt)[Q], int grp) __attribute__((always_inline)) {
+    constexpr bool FIRST = decltype(first_c)::value;
+    sm_static_for(std::make_integer_sequence<int, G>{}, [&](auto tc) __attribute__((always_inline)) {
+      constexpr int t = decltype(tc)::value;
+      const int rel = grp * G + t;
+      if (rel < a.nk) {   // (the same for every wave of every workgroup)
+        sm_wait<PPW, Q * C::batches(t, FIRST), NST - 2>(min(NST - 2, a.nk - 1 - rel));
+        if constexpr (FIRST && t == 0) {   // group 0 and stage 0's fragments: the wait has retired the LUT and W_0, which are older
+          read_words(cur, 0);
+          decode(wf[0], cur, std::integral_constant<int, 0>{});
+        }
+        const char* st = smem + (rel % NST) * C::STAGE;
+        half8 xf[2][TM];
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+          for (int i = 0; i < TM; ++i) xf[kk][i] = *reinterpret_cast<const half8*>(st + 16 * i * 128 + foff[kk]);
+        __builtin_amdgcn_sched_barrier(0);   // reads first, then the next DMA, then decode and MFMAs
+        if constexpr (t == 0) {
+          __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): the reads that moved this group out of its buffer are done
+          __builtin_amdgcn_sched_barrier(0);
+          issue_words(grp + 2);
+        }
+        if (rel + NST - 1 < a.nk) issue(rel + NST - 1);
+        __builtin_amdgcn_sched_barrier(0);
+        // stage rel + 1's fragments beside this stage's MFMAs.  Unconditional, so that both stay in one block: behind the last stage
+        // it decodes zero padding fields, or the re-loaded last group, into fragments no MFMA consumes
+        if constexpr (t == G - 1) {
+          read_words(nxt, grp + 1);
+          decode(wf[0], nxt, std::integral_constant<int, 0>{});
+        } else {
+          decode(wf[(t + 1) & 1], cur, std::integral_constant<int, t + 1>{});
+        }
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+          for (int i = 0; i < TM; ++i) acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[t & 1][kk], xf[kk][i], acc[i], 0, 0, 0);
+      }
+    });
+  };
+  sm_uintx4 wa[Q], wb[Q];
+  run_group(std::true_type{}, wa, wb, 0);
+  for (int grp = 1; grp < a.ngroups; grp += 2) {
+    run_group(std::false_type{}, wb, wa, grp);
+    if (grp + 1 < a.ngroups) run_group(std::false_type{}, wa, wb, grp + 1);
+  }
+
+  // ---- epilogue: smgemm_kernel's ----
+  const floatx4 bv = a.has_bias ? bias4 : floatx4{0.f, 0.f, 0.f, 0.f};
+  const int n = n_blk + 16 * wave + 8 * (g >> 1);
+#pragma unroll
+  for (int p = 0; p < TM / 2; ++p) {
+    unsigned lo[2], hi[2];
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      const floatx4 v = acc[2 * p + b];
+      const half2v h01 = {(half_t)(v[0] + bv[0]), (half_t)(v[1] + bv[1])};
+      const half2v h23 = {(half_t)(v[2] + bv[2]), (half_t)(v[3] + bv[3])};
+      lo[b] = __builtin_bit_cast(unsigned, h01);
+      hi[b] = __builtin_bit_cast(unsigned, h23);
+    }
+    const auto s0 = __builtin_amdgcn_permlane16_swap(lo[0], lo[1], false, false);
+    const auto s1 = __builtin_amdgcn_permlane16_swap(hi[0], hi[1], false, false);
+    const unsigned d0 = s0[0], d1 = s1[0], d2 = s0[1], d3 = s1[1];
+    half8 o = __builtin_bit_cast(half8, (sm_uintx4){d0, d1, d2, d3});
+    if (a.has_res) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = (half_t)((float)o[e] + (float)resv[p][e]);
+    }
+    const int m = m_blk + 32 * p + 16 * (g & 1) + r16;
+    out_store(reinterpret_cast<half8*>(a.out + (size_t)m * a.N + n), o);
+  }
+}
+
+template <int BM, int NBITS>
+void launch_sm_pal(const SmPalArgs& a, unsigned nwg, hipStream_t s) {
+  auto k = smgemm_pal_kernel<BM, NBITS>;
+  constexpr size_t lds = SmPalCfg<BM, NBITS>::LDS;
+  static DynLdsOnce once;
+  once.set(k, lds);
+  hipLaunchKernelGGL(k, dim3(nwg), dim3(64 * SM_NW), lds, s, a);
+}
+
+template <int BM>
+void launch_sm_pal_bits(const SmPalArgs& a, int nbits, unsigned nwg, hipStream_t s) {
+  switch (nbits) {
+    case 1: launch_sm_pal<BM, 1>(a, nwg, s); break;
+    case 2: launch_sm_pal<BM, 2>(a, nwg, s); break;
+    case 4: launch_sm_pal<BM, 4>(a, nwg, s); break;
+    case 6: launch_sm_pal<BM, 6>(a, nwg, s); break;
+    case 8: launch_sm_pal<BM, 8>(a, nwg, s); break;
+    default: fail(kInternal, "palettized smgemm: no kernel for %d-bit indices", nbits);
+  }
+}
+
 int sm_nst(int bm) { return bm == 32 ? SmCfg<32>::NST : SmCfg<64>::NST; }
 
 int sm_bm(const ConvDesc& d, int variant) {   // variant 1 / 2: BM = 32 / 64; 0: by M
@@ -228,6 +508,8 @@ bool smgemm_wanted(const ConvDesc& d) {
   const long tiles = M / sm_bm(d, 0) * (d.N / SM_BN);
   return M >= 256 && M <= 2048 && tiles >= 192 && tiles <= 256;
 }
+
+int smgemm_bm(const ConvDesc& d, int variant) { return sm_bm(d, variant); }
 
 void launch_smgemm(const ConvDesc& d, int variant, hipStream_t s) {
   SD_REQUIRE(smgemm_shape_ok(d, variant), kInvalidArgument, "plan tile 12 (smgemm.hip): not a 1x1 GEMM it tiles (C0=%d C1=%d N=%d)",
@@ -271,6 +553,38 @@ void launch_smgemm(const ConvDesc& d, int variant, hipStream_t s) {
     once.set(k, lds);
     hipLaunchKernelGGL(k, dim3(nwg), dim3(64 * SM_NW), lds, s, a);
   }
+  SD_HIP(hipGetLastError());
+}
+
+void launch_smgemm_pal(const ConvDesc& d, int variant, hipStream_t s) {
+  SD_REQUIRE(smgemm_shape_ok(d, variant) && !d.x1 && d.w_pal && d.pal_gemm && d.pal_lut && palette_bits_ok(d.pal_bits), kInvalidArgument,
+             "plan tile 15 (smgemm.hip, palettized): not a single-source 1x1 GEMM it tiles, or no palette (C0=%d C1=%d N=%d M=%d bits=%d)", d.C0,
+             d.x1 ? d.C1 : 0, d.N, d.B * d.Ho * d.Wo, d.pal_bits);
+  const int M = d.B * d.Ho * d.Wo, K = d.C0;
+  const int bm = sm_bm(d, variant);
+  const unsigned mt = M / bm, nt = d.N / SM_BN, nwg = mt * nt;
+  SmPalArgs a;
+  a.x = d.x0;
+  a.pal = d.w_pal;
+  a.lut = d.pal_lut;
+  // (no bias / residual: any readable memory keeps the loads - the stream holds at least 64 N bytes)
+  a.bias = d.bias ? d.bias : reinterpret_cast<const float*>(d.w_pal);
+  a.res = d.res ? d.res : reinterpret_cast<const half_t*>(d.w_pal);
+  a.out = d.out;
+  a.K = K;
+  a.N = d.N;
+  a.nk = K / SM_BK;
+  a.ngroups = smgemm_pal_groups(K);
+  a.res_ld = d.res ? d.N : 0;
+  a.has_bias = d.bias != nullptr;
+  a.has_res = d.res != nullptr;
+  a.per_xcd = nwg / 8;
+  a.n_fast = choose_tile_order(2.0 * M * K, 2.0 * d.N * K, (double)mt, (double)nt, false);   // tile 12's order, from the fp16 sizes
+  a.fast_div = a.n_fast ? nt : mt;
+  a.fast_magic = (unsigned)((1ull << 32) / a.fast_div + 1);
+  conv_plan_log(d, ConvPlan{15, bm == 32 ? 1 : 2, 1, false, 0}, bm, a.n_fast);
+  if (bm == 32) launch_sm_pal_bits<32>(a, d.pal_bits, nwg, s);
+  else launch_sm_pal_bits<64>(a, d.pal_bits, nwg, s);
   SD_HIP(hipGetLastError());
 }
 

@@ -223,7 +223,7 @@ Tensor UNet::transformer_block(std::vector<Op>& ops, const std::string& b, const
                          (heads == 5 || xo_mode == 2);
   const bool xo_pre = xo_branch && xo_mode == 3 && heads == 5;
   Tensor h1;
-  if (!xo_pre) h1 = conv(ops, b + ".attn1.to_out.0", a1, {.cout = C, .res = h.p});
+  if (!xo_pre) h1 = conv(ops, b + ".attn1.to_out.0", a1, {.cout = C, .res = h.p, .pal_gemm = true});
   // --- cross attention: K / V^T of the prompt are computed by ctx_ops_ when the prompt changes
   const int ldvc = round_up(L, 8);
   Tensor k2 = conv(ctx_ops_, b + ".attn2.to_k", ctx_, {.cout = C, .bias = false});
@@ -310,7 +310,7 @@ Tensor UNet::transformer_block(std::vector<Op>& ops, const std::string& b, const
     }
     a2 = attention(ops, q2, k2.p, vt2.p, heads, S, L, C, ldvc, C);
   }
-  if (!branch_done) h2 = conv(ops, b + ".attn2.to_out.0", a2, {.cout = C, .res = h1.p});
+  if (!branch_done) h2 = conv(ops, b + ".attn2.to_out.0", a2, {.cout = C, .res = h1.p, .pal_gemm = true});
   // --- GEGLU feed-forward (norm3 folded the same way)
   Tensor g;
   if (can_fold_ln(h2, 8 * C, true)) {
@@ -496,7 +496,7 @@ Tensor UNet::transformer(std::vector<Op>& ops, const std::string& p, const Tenso
     ops.back().flop = 8.0 * x.M() * (double)C * C;
   } else {
     Tensor t0 = group_norm(ops, p + ".norm", x, nullptr, 1e-6f, false);
-    h = conv(ops, p + ".proj_in", t0, {.cout = x.C});
+    h = conv(ops, p + ".proj_in", t0, {.cout = x.C, .pal_gemm = true});
   }
   bool tail_done = false;
   const std::string proj_name = p + ".proj_out";

@@ -92,4 +92,43 @@ inline void wstream_pal_pack(const uint8_t* indices, int N, int Ctot, int ksize,
       }
 }
 
+// The palettized weight stream of smgemm.hip (plan tile 15), indices [N][K] (a 1x1 conv / Linear), N % 16 == 0, K % 64 == 0.  The wave
+// of 16-column strip n / 16 consumes K in stages of 64; lane l = 16 g + r16 multiplies, in stage s and sub-step kk (0, 1), the eight
+// weights W[16 strip + r16][64 s + 32 kk + 8 g + e], e = 0..7: 16 indices per lane per stage.  Stages are cut into GROUPS of
+// kSmPalGroup = 8 (the last group is padded with zero fields that no MFMA consumes); a lane's 128 indices of a group, in the order
+// (s, kk, e), form one little-endian bit stream of nbits-wide fields (field f at bits [f * nbits, (f + 1) * nbits)): exactly nbits
+// 16-byte words.  Word q of every lane lies at [strip][group][q][lane][16 B], so each load instruction of the kernel is one coalesced
+// 1-KB wave load.
+constexpr int kSmPalGroup = 8;
+inline int smgemm_pal_groups(int K) { return (K / 64 + kSmPalGroup - 1) / kSmPalGroup; }
+inline size_t smgemm_pal_bytes(int N, int K, int nbits) { return (size_t)(N / 16) * smgemm_pal_groups(K) * nbits * 64 * 16; }
+// dst holds smgemm_pal_bytes(...) bytes
+inline void smgemm_pal_pack(const uint8_t* indices, int N, int K, int nbits, uint8_t* dst) {
+  const int groups = smgemm_pal_groups(K), nk = K / 64;
+  std::vector<uint8_t> lane_bytes((size_t)nbits * 16);
+  for (int strip = 0; strip < N / 16; ++strip)
+    for (int grp = 0; grp < groups; ++grp)
+      for (int lane = 0; lane < 64; ++lane) {
+        const uint8_t* row = indices + (size_t)(strip * 16 + (lane & 15)) * K + (lane >> 4) * 8;
+        std::fill(lane_bytes.begin(), lane_bytes.end(), (uint8_t)0);
+        uint64_t window = 0;   // bits not yet stored, little-endian; fewer than 8 of them between fields
+        int held = 0;
+        size_t at = 0;
+        for (int f = 0; f < kSmPalGroup * 16; ++f) {
+          const int s = grp * kSmPalGroup + (f >> 4), kk = (f >> 3) & 1, e = f & 7;
+          const uint64_t v = s < nk ? row[s * 64 + kk * 32 + e] : 0;
+          window |= v << held;
+          held += nbits;
+          while (held >= 8) {
+            lane_bytes[at++] = (uint8_t)window;
+            window >>= 8;
+            held -= 8;
+          }
+        }   // (128 fields of nbits bits: a whole number of bytes, nothing held)
+        for (int q = 0; q < nbits; ++q)
+          std::copy(lane_bytes.begin() + q * 16, lane_bytes.begin() + (q + 1) * 16,
+                    dst + ((((size_t)strip * groups + grp) * nbits + q) * 64 + lane) * 16);
+      }
+}
+
 }  // namespace sd

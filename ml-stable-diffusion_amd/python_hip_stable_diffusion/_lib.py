@@ -122,6 +122,8 @@ SYMBOLS = [
                              C.POINTER(_I), _I, _FP]),
     ("sd_op_conv2d_palettized", _I, [_P, _P, _P, _I, _P, _FP, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_I), _I, _FP]),
     ("sd_op_palette_pack", _I, [_P, _I, _I, _I, _I, _P, C.POINTER(C.c_size_t)]),
+    ("sd_op_gemm_palettized", _I, [_P, _P, _I, _P, _FP, _P, _P, _I, _I, _I, _I, _I, _I, C.POINTER(_I), _I, _FP]),
+    ("sd_op_palette_pack_gemm", _I, [_P, _I, _I, _I, _P, C.POINTER(C.c_size_t)]),
     ("sd_op_conv2d_groupnorm", _I, [_P, _P, _FP, _P, _FP, _FP, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _I, _I, _I, C.POINTER(_I), _I, _FP]),
     ("sd_op_conv2d_groupnorm_proj", _I, [_P, _P, _FP, _P, _FP, _FP, _P, _FP, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _I, C.POINTER(_I), _I, _FP]),
     ("sd_op_conv2d_groupnorm_conv3x3", _I, [_P, _P, _FP, _P, _FP, _FP, _P, _FP, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _I, _I, _I,
@@ -423,6 +425,49 @@ def palette_pack(indices, nbits):
     stream = np.zeros(n.value, np.uint8)
     check(lib().sd_op_palette_pack(ptr(indices), Cout, Ctot, k, nbits, ptr(stream), C.byref(n)))
     return stream.reshape(Cout // 32, Ctot // 32, -1, 64, 16)
+
+
+def gemm_palettized(x, lut, indices, nbits, bias=None, res=None, bm=0, out=None, iters=1):
+    """The small-M 1x1 GEMM from palettized weights (sd_op_gemm_palettized, plan tile 15): w = lut[indices], lut (2^nbits,) f16, indices
+    (Cout, Cin) uint8, x (B, Cin, H, W); bm 0 / 32 / 64 = the tile height (0: by M).  ``out``: a C-contiguous float16 buffer of at
+    least B * Cout * H * W elements to write into (tests put guards behind it).  What the library checks - nbits, bm, index range, shape
+    - it refuses itself (ValueError, no GPU needed).  Returns (out (B, Cout, H, W), plan, ms)."""
+    x, lut = f16(x), f16(lut)
+    indices = np.ascontiguousarray(indices, dtype=np.uint8)
+    if x.ndim != 4 or indices.ndim != 2 or indices.shape[1] != x.shape[1]:
+        raise ValueError("gemm_palettized: x must be (B, Cin, H, W) and indices (Cout, Cin)")
+    B, Cin, H, W = x.shape
+    Cout = indices.shape[0]
+    if nbits in (1, 2, 4, 6, 8) and lut.shape != (1 << nbits,):
+        raise ValueError("gemm_palettized: lut must hold 2 ** nbits entries")
+    bias = None if bias is None else f32(bias)
+    res = None if res is None else f16(res)
+    if (bias is not None and bias.shape != (Cout,)) or (res is not None and res.shape != (B, Cout, H, W)):
+        raise ValueError("gemm_palettized: bias must be (Cout,), res (B, Cout, H, W)")
+    n = B * Cout * H * W
+    if out is None:
+        out = np.empty(n, np.float16)
+    if out.dtype != np.float16 or not out.flags.c_contiguous or out.size < n:
+        raise ValueError("gemm_palettized: out must be a C-contiguous float16 buffer of at least B * Cout * H * W elements")
+    plan = (C.c_int * 4)()
+    ms = C.c_float(0)
+    check(lib().sd_op_gemm_palettized(ptr(x), ptr(lut), nbits, ptr(indices), fptr(bias), ptr(res), ptr(out), B, Cin, H, W, Cout, bm, plan,
+                                      iters, C.byref(ms)))
+    return out.reshape(-1)[:n].reshape(B, Cout, H, W), list(plan), ms.value
+
+
+def palette_pack_gemm(indices, nbits):
+    """The index bit stream of the palettized small-M GEMM (sd_op_palette_pack_gemm; host only): indices (Cout, K) uint8 -> uint8 array
+    [Cout / 16][ceil(K / 512) groups][nbits words][64 lanes][16 bytes]."""
+    indices = np.ascontiguousarray(indices, dtype=np.uint8)
+    if indices.ndim != 2:
+        raise ValueError("palette_pack_gemm: indices must be (Cout, K)")
+    Cout, K = indices.shape
+    n = C.c_size_t(0)
+    check(lib().sd_op_palette_pack_gemm(ptr(indices), Cout, K, nbits, None, C.byref(n)))
+    stream = np.zeros(n.value, np.uint8)
+    check(lib().sd_op_palette_pack_gemm(ptr(indices), Cout, K, nbits, ptr(stream), C.byref(n)))
+    return stream.reshape(Cout // 16, -1, nbits, 64, 16)
 
 
 def groupnorm_shortcut(x0, x1, gn_weight, gn_bias, w, bias=None, groups=32, eps=1e-5, silu=True, side=True, iters=1):
