@@ -166,22 +166,14 @@ struct ConvOpExtra {
   int pal_bits = 0, pal_waves = 0;       // waves per workgroup: 4, else 8
 };
 
-// the palettized weights of a descriptor as the UNet builder uploads them (Net::conv): the packed index stream and the padded LUT
-void upload_palette(Scratch& sc, ConvDesc& d, const void* lut, int nbits, const uint8_t* indices, int waves) {
-  const int ctot = concat_channels(d);
-  const size_t n_el = (size_t)d.N * ctot * d.ksize * d.ksize;
-  for (size_t i = 0; i < n_el; ++i)
-    SD_REQUIRE(indices[i] < (1u << nbits), kInvalidArgument, "palettized conv: index %u at element %zu, the palette has %d entries",
-               (unsigned)indices[i], i, 1 << nbits);
-  std::vector<uint8_t> stream(wstream_pal_bytes(d.N, ctot, d.ksize, nbits));
-  wstream_pal_pack(indices, d.N, ctot, d.ksize, nbits, stream.data());
-  std::vector<half_t> lut_pad(kPalLutHalves, (half_t)0);
-  std::copy(f16(lut), f16(lut) + (1 << nbits), lut_pad.begin());
-  d.w_pal = sc.dev<uint8_t>(stream.size(), stream.data());
-  d.pal_lut = sc.dev<half_t>(lut_pad.size(), lut_pad.data());
+// the palettized weights of a descriptor as the UNet builder uploads them (Net::conv): the packed index stream - smgemm.hip's for
+// `gemm`, else wstream.hip's - and the padded LUT
+void upload_palette(Scratch& sc, ConvDesc& d, const char* what, const void* lut, int nbits, const uint8_t* indices, bool gemm) {
+  const PaletteHostCopy h = palette_host_copy(what, f16(lut), nbits, indices, d.N, concat_channels(d), d.ksize, gemm);
+  d.w_pal = sc.dev<uint8_t>(h.stream.size(), h.stream.data());
+  d.pal_lut = sc.dev<half_t>(h.lut.size(), h.lut.data());
   d.pal_bits = nbits;
-  d.tile = 14;
-  d.staging = waves == 4 ? 4 : 0;
+  d.pal_gemm = gemm;
 }
 
 // (B, N) f32 rows on the device as the UNet keeps its time_emb_proj outputs: a column block of a wider row buffer, every other float
@@ -237,7 +229,9 @@ void conv2d_op(const void* x, const void* w, const float* bias, const void* res,
   if (e.pal_indices) {
     SD_REQUIRE(fast && wstream_shape_ok(d), kInvalidArgument, "conv2d_palettized: shape not eligible for plan tile 14 (wstream.hip: k=%d C0=%d C1=%d N=%d %dx%d)",
                ksize, Cin, e.C1, Cout, Ho, Wo);
-    upload_palette(sc, d, e.pal_lut, e.pal_bits, e.pal_indices, e.pal_waves);
+    upload_palette(sc, d, "palettized conv", e.pal_lut, e.pal_bits, e.pal_indices, false);
+    d.tile = 14;
+    d.staging = e.pal_waves == 4 ? 4 : 0;
   }
   half_t* dtwin = nullptr;
   if (e.twin_groups) {   // the GroupNorm as a twin of the conv's slab combine (sd_op_conv2d_groupnorm's producer_stats = 2)
@@ -504,10 +498,7 @@ int sd_op_gemm_palettized(const void* x, const void* lut, int nbits, const uint8
     SD_REQUIRE(bm == 0 || bm == 32 || bm == 64, kInvalidArgument, "gemm_palettized: bm = %d, not 0, 32 or 64", bm);
     SD_REQUIRE(x && lut && indices && out && plan_out, kInvalidArgument, "NULL argument");
     SD_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, kInvalidArgument, "gemm_palettized: empty problem");
-    const size_t n_el = (size_t)Cout * Cin;
-    for (size_t i = 0; i < n_el; ++i)
-      SD_REQUIRE(indices[i] < (1u << nbits), kInvalidArgument, "gemm_palettized: index %u at element %zu, the palette has %d entries",
-                 (unsigned)indices[i], i, 1 << nbits);
+    palette_check_indices("gemm_palettized", indices, (size_t)Cout * Cin, nbits);   // (in front of the shape: the header's order)
     ConvDesc d;
     d.C0 = Cin;
     d.B = B; d.Hi = H; d.Wi = W; d.Ho = H; d.Wo = W;
@@ -522,14 +513,7 @@ int sd_op_gemm_palettized(const void* x, const void* lut, int nbits, const uint8
     if (res) d.res = upload_nhwc(sc, res, B, Cout, H, W);
     half_t* dout = sc.dev<half_t>((size_t)B * H * W * Cout);
     d.out = dout;
-    std::vector<uint8_t> stream(smgemm_pal_bytes(Cout, Cin, nbits));
-    smgemm_pal_pack(indices, Cout, Cin, nbits, stream.data());
-    std::vector<half_t> lut_pad(kPalLutHalves, (half_t)0);
-    std::copy(f16(lut), f16(lut) + (1 << nbits), lut_pad.begin());
-    d.w_pal = sc.dev<uint8_t>(stream.size(), stream.data());
-    d.pal_lut = sc.dev<half_t>(lut_pad.size(), lut_pad.data());
-    d.pal_bits = nbits;
-    d.pal_gemm = true;
+    upload_palette(sc, d, "gemm_palettized", lut, nbits, indices, true);
     d.tile = 15;
     d.staging = variant;
     const ConvPlan p = conv_plan(d);

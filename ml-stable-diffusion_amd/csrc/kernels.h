@@ -87,7 +87,7 @@ struct ConvDesc {
   int gnf_silu = 0;
   // weights in the fragment-major layout of wstream.hip (launch_wstream_retile), or null: plan tile 9 needs them
   const half_t* w_tiled = nullptr;
-  // palettized weights (plan tile 14, wstream.hip wstream_pal_kernel): the bit stream of weight_prep.h wstream_pal_pack, the
+  // palettized weights (plan tile 14, wstream.hip wstream_kernel with NBITS > 0): the bit stream of weight_prep.h wstream_pal_pack, the
   // tensor's LUT padded to kPalLutHalves fp16 entries, and the index width (1, 2, 4, 6, 8).  A descriptor that carries them is
   // pinned: it has no fp16 weights (w == w_tiled == nullptr), so no table row or tuner candidate can move it
   const uint8_t* w_pal = nullptr;
@@ -137,7 +137,6 @@ void launch_wstream_retile(const half_t* w, half_t* wt, int N, int Ctot, int ksi
 int launch_wstream(const ConvDesc& d, float* partial, int nw, hipStream_t s);
 // the same launch from palettized weights (d.w_pal / pal_lut / pal_bits): every weight is looked up in the LUT in front of the same
 // MFMAs in the same order, so the slabs are bit-identical to launch_wstream's on the de-palettized weights
-constexpr int kPalLutHalves = 256;
 int launch_wstream_pal(const ConvDesc& d, float* partial, int nw, hipStream_t s);
 bool reduce_twin_ok(int HW, int N, int n_twins, const GnTwin* tw);
 void launch_reduce_twin(const float* partial, int S, int M, int N, int HW, const float* bias, const float* temb, int temb_stride,

@@ -94,15 +94,16 @@ Tensor Net::conv(std::vector<Op>& ops, const std::string& name, const Tensor& x,
     const size_t expect = (size_t)a.cout * cin * a.k * a.k;
     SD_REQUIRE(t.numel() == expect && pal->indices.size() == expect, kInvalidArgument, "%s.weight has %zu elements, expected %zu (%d,%d,%d,%d)",
                name.c_str(), t.numel(), expect, a.cout, cin, a.k, a.k);
-    std::vector<uint8_t> stream(pal_waves ? wstream_pal_bytes(a.cout, cin, a.k, pal->nbits) : smgemm_pal_bytes(a.cout, cin, pal->nbits));
-    if (pal_waves) wstream_pal_pack(pal->indices.data(), a.cout, cin, a.k, pal->nbits, stream.data());
-    else smgemm_pal_pack(pal->indices.data(), a.cout, cin, pal->nbits, stream.data());
-    uint8_t* ds = ll_.arena.alloc_n<uint8_t>(stream.size());
-    SD_HIP(hipMemcpy(ds, stream.data(), stream.size(), hipMemcpyHostToDevice));
-    half_t* dl = ll_.arena.alloc_n<half_t>(kPalLutHalves);   // zero-initialised: the entries behind 2^nbits stay 0
-    SD_HIP(hipMemcpy(dl, pal->lut.data(), pal->lut.size() * sizeof(half_t), hipMemcpyHostToDevice));
+    SD_REQUIRE(palette_bits_ok(pal->nbits) && pal->lut.size() == (size_t)1 << pal->nbits, kInternal, "%s.weight: a palette of %zu entries for %d bits",
+               name.c_str(), pal->lut.size(), pal->nbits);
+    const PaletteHostCopy h = palette_host_copy((name + ".weight").c_str(), reinterpret_cast<const half_t*>(pal->lut.data()), pal->nbits,
+                                                pal->indices.data(), a.cout, cin, a.k, !pal_waves);
+    uint8_t* ds = ll_.arena.alloc_n<uint8_t>(h.stream.size());
+    SD_HIP(hipMemcpy(ds, h.stream.data(), h.stream.size(), hipMemcpyHostToDevice));
+    half_t* dl = ll_.arena.alloc_n<half_t>(h.lut.size());
+    SD_HIP(hipMemcpy(dl, h.lut.data(), h.lut.size() * sizeof(half_t), hipMemcpyHostToDevice));
     ++pal_streamed_;
-    pal_stream_bytes_ += stream.size() + kPalLutHalves * sizeof(half_t);
+    pal_stream_bytes_ += h.stream.size() + h.lut.size() * sizeof(half_t);
     ConvArgs ap = a;
     ap.pal_stream = ds;
     ap.pal_lut = dl;

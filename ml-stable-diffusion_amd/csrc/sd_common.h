@@ -20,6 +20,7 @@ typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 typedef _Float16 half2v __attribute__((ext_vector_type(2)));
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef float floatx4 __attribute__((ext_vector_type(4)));
+typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
 
 // Output stores of the step's kernels.  -DSD_SC1_STORES (experiment, round 6): write-through (sc1) instead of plain stores, so that
 // a kernel's results leave the XCD's L2 while it runs instead of at its end-of-kernel release (MI355X_MICROARCH.md "boundary":
@@ -119,8 +120,10 @@ inline bool tune_env_set(const char* name) {
   return on && getenv(name) != nullptr;
 }
 
-// index widths of a palettized tensor (weights.h Palette; wstream.hip instantiates one kernel per width)
+// index widths of a palettized tensor (weights.h Palette; wstream.hip and smgemm.hip instantiate one kernel per width), and the
+// entries of the zero-padded LUT a kernel copies: 2^8
 inline bool palette_bits_ok(int nbits) { return nbits == 1 || nbits == 2 || nbits == 4 || nbits == 6 || nbits == 8; }
+constexpr int kPalLutHalves = 256;
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 

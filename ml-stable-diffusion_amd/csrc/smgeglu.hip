@@ -23,6 +23,7 @@
 #include "conv_plan.h"
 #include "kernels.h"
 #include "sm_ring.h"
+#include "sm_tile.h"
 
 namespace sd {
 
@@ -46,10 +47,7 @@ struct SgArgs {
   int K, nk, ldo;
   int has_bias, lnf;
   float ln_eps;
-  unsigned per_xcd;      // workgroups of one XCD's contiguous tile run (grid % 8 == 0)
-  unsigned fast_div;     // tiles along the fast dimension (>= 2)
-  unsigned fast_magic;   // floor(2^32 / fast_div) + 1 (smgemm.hip)
-  int n_fast;            // 1: consecutive tiles share an activation panel, 0: a weight panel
+  SmTileOrder order;
 };
 
 template <int BM>
@@ -97,12 +95,9 @@ __global__ __launch_bounds__(64 * SG_NW, 1) void smgeglu_kernel(SgArgs a) {
   const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
   const int u = wave % SG_UNITS, h = wave / SG_UNITS;   // column unit, row half
 
-  // XCD-aware tile order (block b runs on XCD b % 8): XCD x walks tiles [x * per_xcd, (x + 1) * per_xcd)
-  const unsigned t = (blockIdx.x & 7u) * a.per_xcd + (blockIdx.x >> 3);
-  const unsigned slow = __umulhi(t, a.fast_magic);
-  const unsigned fast = t - slow * a.fast_div;
-  const int m_blk = (int)(a.n_fast ? slow : fast) * BM;
-  const int u_blk = (int)(a.n_fast ? fast : slow) * SG_UNITS;   // first 16-column unit of the tile
+  int m_tile, n_tile;
+  sm_tile_coords(a.order, m_tile, n_tile);
+  const int m_blk = m_tile * BM, u_blk = n_tile * SG_UNITS;   // first row, first 16-column unit of the tile
 
   // ---- staging: piece wave + 10 j of every stage (the last j only on the first FULL waves), one 16-B chunk of one staged row per
   // lane.  Staged weight row r: unit r / 32, value (r & 16 == 0) or gate row r & 15 ----
@@ -285,7 +280,7 @@ __global__ __launch_bounds__(64 * SG_NW, 1) void smgeglu_kernel(SgArgs a) {
   }
   if constexpr (PROF) stamp[4] = clock64();
 
-  // ---- epilogue: tile_epilogue's arithmetic in fp32, one rounding to fp16, blocks (2p, 2p + 1) paired by v_permlane16_swap ----
+  // ---- epilogue: tile_epilogue's arithmetic in fp32, one rounding to fp16, blocks (2p, 2p + 1) paired by sm_swap16 ----
   const floatx4 zero4 = {0.f, 0.f, 0.f, 0.f};
   const floatx4 bv = a.has_bias ? bias_v : zero4, bg = a.has_bias ? bias_g : zero4;
   const int n = (u_blk + u) * 16 + 8 * (g >> 1);
@@ -313,13 +308,7 @@ __global__ __launch_bounds__(64 * SG_NW, 1) void smgeglu_kernel(SgArgs a) {
       lo[b] = __builtin_bit_cast(unsigned, h01);
       hi[b] = __builtin_bit_cast(unsigned, h23);
     }
-    // the odd 16-lane rows of block 2p trade with the even rows of block 2p + 1: afterwards lane (g, r16) holds columns
-    // 8 (g >> 1) .. + 7 of row 16 (2p + (g & 1)) + r16, the first four in the `vdst` results (smgemm.hip)
-    const auto s0 = __builtin_amdgcn_permlane16_swap(lo[0], lo[1], false, false);
-    const auto s1 = __builtin_amdgcn_permlane16_swap(hi[0], hi[1], false, false);
-    const unsigned d0 = s0[0], d1 = s1[0], d2 = s0[1], d3 = s1[1];   // scalars first (igemm.hip xor32_sum)
-    typedef unsigned u4 __attribute__((ext_vector_type(4)));
-    const half8 o8 = __builtin_bit_cast(half8, (u4){d0, d1, d2, d3});
+    const half8 o8 = sm_swap16(lo[0], lo[1], hi[0], hi[1]);
     const int m = m_blk + h * (BM / 2) + 32 * p + 16 * (g & 1) + r16;
     out_store(reinterpret_cast<half8*>(a.out + (size_t)m * a.ldo + n), o8);
   }
@@ -397,12 +386,8 @@ void launch_smgeglu(const ConvDesc& d, int variant, hipStream_t s) {
   a.has_bias = d.bias != nullptr;
   a.lnf = d.ln_colsum != nullptr;
   a.ln_eps = d.ln_eps;
-  a.per_xcd = nwg / 8;
-  // tile order by the bytes each pulls into the 8 XCD L2s (as smgemm.hip: no A/B switch here)
-  a.n_fast = choose_tile_order(2.0 * M * K, 2.0 * d.N * K, (double)mt, (double)nt, false);
-  a.fast_div = a.n_fast ? nt : mt;
-  a.fast_magic = (unsigned)((1ull << 32) / a.fast_div + 1);
-  conv_plan_log(d, ConvPlan{13, variant, 1, false, 0}, bm, a.n_fast);
+  a.order = sm_tile_order(M, d.N, K, mt, nt);
+  conv_plan_log(d, ConvPlan{13, variant, 1, false, 0}, bm, a.order.n_fast);
   if (bm == 128) {
     if (d.prof) sg_launch<128, true>(a, nwg, s);
     else sg_launch<128, false>(a, nwg, s);

@@ -23,7 +23,9 @@
 
 #include "conv_plan.h"
 #include "kernels.h"
+#include "pal_decode.h"
 #include "sm_ring.h"
+#include "sm_tile.h"
 #include "weight_prep.h"
 
 namespace sd {
@@ -45,10 +47,7 @@ struct SmArgs {
   int K, N, nk, res_ld;
   int nk0, ldx0, ldx1;
   int has_bias, has_res;
-  unsigned per_xcd;     // workgroups of one XCD's contiguous tile run (grid % 8 == 0)
-  unsigned fast_div;    // tiles along the fast dimension (>= 2)
-  unsigned fast_magic;  // floor(2^32 / fast_div) + 1: mulhi(t, magic) == t / fast_div for t * fast_div < 2^32
-  int n_fast;           // 1: consecutive tiles share an activation panel, 0: a weight panel (igemm_device.h IgemmArgs::n_fast)
+  SmTileOrder order;
 };
 
 template <int BM>
@@ -73,12 +72,9 @@ __global__ __launch_bounds__(64 * SM_NW, 1) void smgemm_kernel(SmArgs a) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
 
-  // XCD-aware tile order (block b runs on XCD b % 8): XCD x walks tiles [x * per_xcd, (x + 1) * per_xcd)
-  const unsigned t = (blockIdx.x & 7u) * a.per_xcd + (blockIdx.x >> 3);
-  const unsigned slow = __umulhi(t, a.fast_magic);
-  const unsigned fast = t - slow * a.fast_div;
-  const int m_blk = (int)(a.n_fast ? slow : fast) * BM;
-  const int n_blk = (int)(a.n_fast ? fast : slow) * SM_BN;
+  int m_tile, n_tile;
+  sm_tile_coords(a.order, m_tile, n_tile);
+  const int m_blk = m_tile * BM, n_blk = n_tile * SM_BN;
 
   // ---- staging: piece wave + 5 j of every stage, one 16-B chunk of one staged row per lane ----
   const half_t* src[PPW];
@@ -166,7 +162,7 @@ __global__ __launch_bounds__(64 * SM_NW, 1) void smgemm_kernel(SmArgs a) {
         acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[kk], xf[kk][i], acc[i], 0, 0, 0);
   }
 
-  // ---- epilogue: bias in fp32, one rounding to fp16, blocks (2p, 2p + 1) paired by v_permlane16_swap -> 16 B per lane ----
+  // ---- epilogue: bias in fp32, one rounding to fp16, blocks (2p, 2p + 1) paired by sm_swap16 -> 16 B of one output row per lane ----
   const floatx4 bv = a.has_bias ? bias4 : floatx4{0.f, 0.f, 0.f, 0.f};
   const int n = n_blk + 16 * wave + 8 * (g >> 1);
 #pragma unroll
@@ -180,13 +176,7 @@ __global__ __launch_bounds__(64 * SM_NW, 1) void smgemm_kernel(SmArgs a) {
       lo[b] = __builtin_bit_cast(unsigned, h01);
       hi[b] = __builtin_bit_cast(unsigned, h23);
     }
-    // the odd 16-lane rows of block 2p trade with the even rows of block 2p + 1: afterwards lane (g, r16) holds columns
-    // 8 (g >> 1) .. + 7 of row 16 (2p + (g & 1)) + r16, the first four in the `vdst` results
-    const auto s0 = __builtin_amdgcn_permlane16_swap(lo[0], lo[1], false, false);
-    const auto s1 = __builtin_amdgcn_permlane16_swap(hi[0], hi[1], false, false);
-    const unsigned d0 = s0[0], d1 = s1[0], d2 = s0[1], d3 = s1[1];   // scalars first (igemm.hip xor32_sum)
-    typedef unsigned u4 __attribute__((ext_vector_type(4)));
-    half8 o = __builtin_bit_cast(half8, (u4){d0, d1, d2, d3});
+    half8 o = sm_swap16(lo[0], lo[1], hi[0], hi[1]);
     if (a.has_res) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) o[e] = (half_t)((float)o[e] + (float)resv[p][e]);
@@ -197,9 +187,10 @@ __global__ __launch_bounds__(64 * SM_NW, 1) void smgemm_kernel(SmArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// The same GEMM from PALETTIZED weights (plan tile 15).  Geometry, MFMAs, their order per accumulator block (ascending K64 stage, then
-// kk = 0, 1), tile order and epilogue are smgemm_kernel's, so the output is bit-identical to smgemm_kernel<BM> on lut[indices].  What
-// differs is where the weight fragment comes from:
+// The second kernel of this file: the same GEMM from PALETTIZED weights (plan tile 15).  Geometry, MFMAs, their order per accumulator
+// block (ascending K64 stage, then kk = 0, 1), tile order (sm_tile.h) and epilogue are smgemm_kernel's, so the output is bit-identical
+// to smgemm_kernel<BM> on lut[indices].  The K loop is its own - another ring, other wait arithmetic - because of where the weight
+// fragment comes from:
 //   * no fp16 weight exists anywhere.  Lane (g, r16) of wave w owns the bit stream of its palette indices (weight_prep.h
 //     smgemm_pal_pack: NBITS coalesced 16-B words per GROUP of 8 stages), keeps the current group's words in registers and turns every
 //     index into one 2-byte LDS read of the LUT, placed in the low or high half of a fragment register.  Field positions are
@@ -238,8 +229,7 @@ struct SmPalArgs {
   half_t* out;
   int K, N, nk, ngroups, res_ld;
   int has_bias, has_res;
-  unsigned per_xcd, fast_div, fast_magic;
-  int n_fast;
+  SmTileOrder order;
 };
 
 template <int BM, int NBITS>
@@ -262,8 +252,6 @@ struct SmPalCfg {
   static_assert(PPW * (NST - 2) + 2 * NBITS <= 63, "vmcnt range");
 };
 
-typedef unsigned sm_uintx4 __attribute__((ext_vector_type(4)));
-
 template <int... I, typename F>
 __device__ __forceinline__ void sm_static_for(std::integer_sequence<int, I...>, F&& f) {
   (f(std::integral_constant<int, I>{}), ...);
@@ -273,16 +261,13 @@ template <int BM, int NBITS>
 __global__ __launch_bounds__(64 * SM_NW, 1) void smgemm_pal_kernel(SmPalArgs a) {
   using C = SmPalCfg<BM, NBITS>;
   constexpr int NST = C::NST, PPW = C::PPW, TM = C::TM, Q = NBITS, G = C::G;
-  constexpr unsigned MASK = (1u << NBITS) - 1u;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
 
-  const unsigned t_id = (blockIdx.x & 7u) * a.per_xcd + (blockIdx.x >> 3);
-  const unsigned slow = __umulhi(t_id, a.fast_magic);
-  const unsigned fast = t_id - slow * a.fast_div;
-  const int m_blk = (int)(a.n_fast ? slow : fast) * BM;
-  const int n_blk = (int)(a.n_fast ? fast : slow) * SM_BN;
+  int m_tile, n_tile;
+  sm_tile_coords(a.order, m_tile, n_tile);
+  const int m_blk = m_tile * BM, n_blk = n_tile * SM_BN;
   const int g = lane >> 4, r16 = lane & 15;
 
   // ---- epilogue operands first (nothing in the K loop counts them), in the store layout as in smgemm_kernel ----
@@ -302,19 +287,19 @@ __global__ __launch_bounds__(64 * SM_NW, 1) void smgemm_pal_kernel(SmPalArgs a) 
   const unsigned short* const lutp = reinterpret_cast<const unsigned short*>(lut_lds);
   // ---- index words: batch W_i = group min(i, groups - 1) into this wave's buffer i & 1 ----
   char* const wbuf = smem + C::WORDS + wave * (2 * Q * 1024);
-  const sm_uintx4* const wbase = reinterpret_cast<const sm_uintx4*>(a.pal) + (size_t)(n_blk / 16 + wave) * a.ngroups * (Q * 64) + lane;
+  const uintx4* const wbase = reinterpret_cast<const uintx4*>(a.pal) + (size_t)(n_blk / 16 + wave) * a.ngroups * (Q * 64) + lane;
   auto issue_words = [&](int i) __attribute__((always_inline)) {
-    const sm_uintx4* p = wbase + (size_t)min(i, a.ngroups - 1) * (Q * 64);
+    const uintx4* p = wbase + (size_t)min(i, a.ngroups - 1) * (Q * 64);
     char* dst = wbuf + (i & 1) * (Q * 1024);
 #pragma unroll
     for (int q = 0; q < Q; ++q)
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(p + q * 64),
                                        (__attribute__((address_space(3))) void*)(dst + q * 1024), 16, 0, 0);
   };
-  auto read_words = [&](sm_uintx4(&wq)[Q], int grp) __attribute__((always_inline)) {
+  auto read_words = [&](uintx4(&wq)[Q], int grp) __attribute__((always_inline)) {
     const char* srcw = wbuf + (grp & 1) * (Q * 1024) + lane * 16;
 #pragma unroll
-    for (int q = 0; q < Q; ++q) wq[q] = *reinterpret_cast<const sm_uintx4*>(srcw + q * 1024);
+    for (int q = 0; q < Q; ++q) wq[q] = *reinterpret_cast<const uintx4*>(srcw + q * 1024);
   };
   issue_words(0);
   issue_words(1);
@@ -352,34 +337,16 @@ __global__ __launch_bounds__(64 * SM_NW, 1) void smgemm_pal_kernel(SmPalArgs a) 
 #pragma unroll
   for (int i = 0; i < TM; ++i) acc[i] = floatx4{0.f, 0.f, 0.f, 0.f};
 
-  // the two weight fragments of stage t of a group: field f = (2 t + kk) * 8 + e of the lane's stream; a field that straddles a dword
-  // is one funnel shift (wstream.hip decode_tap)
-  auto decode = [&](half8(&wf)[2], const sm_uintx4(&wq)[Q], auto tc) __attribute__((always_inline)) {
+  // the two weight fragments of stage t of a group: fragments 2 t, 2 t + 1 of the lane's stream (pal_decode.h)
+  auto decode = [&](half8(&wf)[2], const uintx4(&wq)[Q], auto tc) __attribute__((always_inline)) {
     constexpr int t = decltype(tc)::value;
 #pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      sm_uintx4 pk = {0u, 0u, 0u, 0u};
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const int bit = ((t * 2 + kk) * 8 + e) * NBITS, dw = bit >> 5, sh = bit & 31;
-        const unsigned lo = wq[dw >> 2][dw & 3];
-        unsigned idx;
-        if (sh + NBITS <= 32) {
-          idx = (lo >> sh) & MASK;
-        } else {
-          const int dn = dw + 1;   // (inside the group's words: the field ends in it)
-          idx = __builtin_amdgcn_alignbit(wq[dn >> 2][dn & 3], lo, sh) & MASK;
-        }
-        const unsigned v = lutp[idx];
-        pk[e >> 1] = (e & 1) ? (pk[e >> 1] | (v << 16)) : v;
-      }
-      wf[kk] = __builtin_bit_cast(half8, pk);
-    }
+    for (int kk = 0; kk < 2; ++kk) wf[kk] = pal_decode<NBITS>(wq, t * 2 + kk, lutp);
   };
 
   half8 wf[2][2];   // [stage parity][kk]
   // one group of 8 stages: `cur` holds its words, `nxt` receives the next group's in its last stage
-  auto run_group = [&](auto first_c, sm_uintx4(&cur)[Q], sm_uintx4(&nxt)[Q], int grp) __attribute__((always_inline)) {
+  auto run_group = [&](auto first_c, uintx4(&cur)[Q], uintx4(&nxt)[Q], int grp) __attribute__((always_inline)) {
     constexpr bool FIRST = decltype(first_c)::value;
     sm_static_for(std::make_integer_sequence<int, G>{}, [&](auto tc) __attribute__((always_inline)) {
       constexpr int t = decltype(tc)::value;
@@ -419,7 +386,7 @@ __global__ __launch_bounds__(64 * SM_NW, 1) void smgemm_pal_kernel(SmPalArgs a) 
       }
     });
   };
-  sm_uintx4 wa[Q], wb[Q];
+  uintx4 wa[Q], wb[Q];
   run_group(std::true_type{}, wa, wb, 0);
   for (int grp = 1; grp < a.ngroups; grp += 2) {
     run_group(std::false_type{}, wb, wa, grp);
@@ -431,7 +398,7 @@ __global__ __launch_bounds__(64 * SM_NW, 1) void smgemm_pal_kernel(SmPalArgs a) 
   const int n = n_blk + 16 * wave + 8 * (g >> 1);
 #pragma unroll
   for (int p = 0; p < TM / 2; ++p) {
-    unsigned lo[2], hi[2];
+    unsigned lo[2], hi[2];   // [block 2p | block 2p + 1] x {columns 4 g, 4 g + 1 | 4 g + 2, 4 g + 3}
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
       const floatx4 v = acc[2 * p + b];
@@ -440,10 +407,7 @@ __global__ __launch_bounds__(64 * SM_NW, 1) void smgemm_pal_kernel(SmPalArgs a) 
       lo[b] = __builtin_bit_cast(unsigned, h01);
       hi[b] = __builtin_bit_cast(unsigned, h23);
     }
-    const auto s0 = __builtin_amdgcn_permlane16_swap(lo[0], lo[1], false, false);
-    const auto s1 = __builtin_amdgcn_permlane16_swap(hi[0], hi[1], false, false);
-    const unsigned d0 = s0[0], d1 = s1[0], d2 = s0[1], d3 = s1[1];
-    half8 o = __builtin_bit_cast(half8, (sm_uintx4){d0, d1, d2, d3});
+    half8 o = sm_swap16(lo[0], lo[1], hi[0], hi[1]);
     if (a.has_res) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) o[e] = (half_t)((float)o[e] + (float)resv[p][e]);
@@ -453,25 +417,42 @@ __global__ __launch_bounds__(64 * SM_NW, 1) void smgemm_pal_kernel(SmPalArgs a) 
   }
 }
 
-template <int BM, int NBITS>
-void launch_sm_pal(const SmPalArgs& a, unsigned nwg, hipStream_t s) {
-  auto k = smgemm_pal_kernel<BM, NBITS>;
-  constexpr size_t lds = SmPalCfg<BM, NBITS>::LDS;
-  static DynLdsOnce once;
-  once.set(k, lds);
-  hipLaunchKernelGGL(k, dim3(nwg), dim3(64 * SM_NW), lds, s, a);
+// one workgroup per tile: 8 XCD runs of per_xcd tiles
+template <class K, class A>
+void launch_sm(K kernel, size_t lds, DynLdsOnce& once, const A& a, hipStream_t s) {
+  once.set(kernel, lds);
+  hipLaunchKernelGGL(kernel, dim3(8 * a.order.per_xcd), dim3(64 * SM_NW), lds, s, a);
 }
 
 template <int BM>
-void launch_sm_pal_bits(const SmPalArgs& a, int nbits, unsigned nwg, hipStream_t s) {
-  switch (nbits) {
-    case 1: launch_sm_pal<BM, 1>(a, nwg, s); break;
-    case 2: launch_sm_pal<BM, 2>(a, nwg, s); break;
-    case 4: launch_sm_pal<BM, 4>(a, nwg, s); break;
-    case 6: launch_sm_pal<BM, 6>(a, nwg, s); break;
-    case 8: launch_sm_pal<BM, 8>(a, nwg, s); break;
-    default: fail(kInternal, "palettized smgemm: no kernel for %d-bit indices", nbits);
-  }
+void launch_sm_fp16(const SmArgs& a, hipStream_t s) {
+  static DynLdsOnce once;
+  launch_sm(smgemm_kernel<BM>, (size_t)SmCfg<BM>::NST * SmCfg<BM>::STAGE, once, a, s);
+}
+
+template <int BM, int NBITS>
+void launch_sm_pal(const SmPalArgs& a, hipStream_t s) {
+  static DynLdsOnce once;
+  launch_sm(smgemm_pal_kernel<BM, NBITS>, SmPalCfg<BM, NBITS>::LDS, once, a, s);
+}
+
+// what SmArgs and SmPalArgs share, for the single source d.x0 of K channels; `dummy`: readable memory of at least N floats that stands
+// in for an absent bias / residual row (the loads keep their count).  Returns the tile order's n_fast for the plan log.
+template <class A>
+int sm_common_args(A& a, const ConvDesc& d, int K, int bm, const void* dummy) {
+  const int M = d.B * d.Ho * d.Wo;
+  a.x = d.x0;
+  a.bias = d.bias ? d.bias : static_cast<const float*>(dummy);
+  a.res = d.res ? d.res : static_cast<const half_t*>(dummy);
+  a.out = d.out;
+  a.K = K;
+  a.N = d.N;
+  a.nk = K / SM_BK;
+  a.res_ld = d.res ? d.N : 0;
+  a.has_bias = d.bias != nullptr;
+  a.has_res = d.res != nullptr;
+  a.order = sm_tile_order(M, d.N, K, M / bm, d.N / SM_BN);
+  return a.order.n_fast;
 }
 
 int sm_nst(int bm) { return bm == 32 ? SmCfg<32>::NST : SmCfg<64>::NST; }
@@ -514,45 +495,17 @@ int smgemm_bm(const ConvDesc& d, int variant) { return sm_bm(d, variant); }
 void launch_smgemm(const ConvDesc& d, int variant, hipStream_t s) {
   SD_REQUIRE(smgemm_shape_ok(d, variant), kInvalidArgument, "plan tile 12 (smgemm.hip): not a 1x1 GEMM it tiles (C0=%d C1=%d N=%d)",
              d.C0, d.x1 ? d.C1 : 0, d.N);
-  const int M = d.B * d.Ho * d.Wo, K = d.C0 + (d.x1 ? d.C1 : 0);
   const int bm = sm_bm(d, variant);
-  const unsigned mt = M / bm, nt = d.N / SM_BN, nwg = mt * nt;
   SmArgs a;
-  a.x = d.x0;
+  const int n_fast = sm_common_args(a, d, d.C0 + (d.x1 ? d.C1 : 0), bm, d.w);   // K >= 64: the weights hold more than N floats
   a.x1 = d.x1 ? d.x1 : d.x0;
   a.ldx0 = d.C0;
   a.ldx1 = d.x1 ? d.C1 : d.C0;
   a.w = d.w;
-  a.bias = d.bias ? d.bias : reinterpret_cast<const float*>(d.w);   // K >= 64: the weights hold more than N floats
-  a.res = d.res ? d.res : d.w;
-  a.out = d.out;
-  a.K = K;
-  a.N = d.N;
-  a.nk = K / SM_BK;
   a.nk0 = d.C0 / SM_BK;
-  a.res_ld = d.res ? d.N : 0;
-  a.has_bias = d.bias != nullptr;
-  a.has_res = d.res != nullptr;
-  a.per_xcd = nwg / 8;
-  // tile order by the bytes each pulls into the 8 XCD L2s: m fastest streams every weight panel once and the activations once per
-  // XCD; n fastest the other way round (no A/B switch here)
-  a.n_fast = choose_tile_order(2.0 * M * K, 2.0 * d.N * K, (double)mt, (double)nt, false);
-  a.fast_div = a.n_fast ? nt : mt;
-  a.fast_magic = (unsigned)((1ull << 32) / a.fast_div + 1);
-  conv_plan_log(d, ConvPlan{12, variant, 1, false, 0}, bm, a.n_fast);
-  if (bm == 32) {
-    auto k = smgemm_kernel<32>;
-    constexpr size_t lds = (size_t)SmCfg<32>::NST * SmCfg<32>::STAGE;
-    static DynLdsOnce once;
-    once.set(k, lds);
-    hipLaunchKernelGGL(k, dim3(nwg), dim3(64 * SM_NW), lds, s, a);
-  } else {
-    auto k = smgemm_kernel<64>;
-    constexpr size_t lds = (size_t)SmCfg<64>::NST * SmCfg<64>::STAGE;
-    static DynLdsOnce once;
-    once.set(k, lds);
-    hipLaunchKernelGGL(k, dim3(nwg), dim3(64 * SM_NW), lds, s, a);
-  }
+  conv_plan_log(d, ConvPlan{12, variant, 1, false, 0}, bm, n_fast);
+  if (bm == 32) launch_sm_fp16<32>(a, s);
+  else launch_sm_fp16<64>(a, s);
   SD_HIP(hipGetLastError());
 }
 
@@ -560,31 +513,17 @@ void launch_smgemm_pal(const ConvDesc& d, int variant, hipStream_t s) {
   SD_REQUIRE(smgemm_shape_ok(d, variant) && !d.x1 && d.w_pal && d.pal_gemm && d.pal_lut && palette_bits_ok(d.pal_bits), kInvalidArgument,
              "plan tile 15 (smgemm.hip, palettized): not a single-source 1x1 GEMM it tiles, or no palette (C0=%d C1=%d N=%d M=%d bits=%d)", d.C0,
              d.x1 ? d.C1 : 0, d.N, d.B * d.Ho * d.Wo, d.pal_bits);
-  const int M = d.B * d.Ho * d.Wo, K = d.C0;
   const int bm = sm_bm(d, variant);
-  const unsigned mt = M / bm, nt = d.N / SM_BN, nwg = mt * nt;
   SmPalArgs a;
-  a.x = d.x0;
+  const int n_fast = sm_common_args(a, d, d.C0, bm, d.w_pal);   // the stream holds at least 64 N bytes; tile 12's order, from the fp16 sizes
   a.pal = d.w_pal;
   a.lut = d.pal_lut;
-  // (no bias / residual: any readable memory keeps the loads - the stream holds at least 64 N bytes)
-  a.bias = d.bias ? d.bias : reinterpret_cast<const float*>(d.w_pal);
-  a.res = d.res ? d.res : reinterpret_cast<const half_t*>(d.w_pal);
-  a.out = d.out;
-  a.K = K;
-  a.N = d.N;
-  a.nk = K / SM_BK;
-  a.ngroups = smgemm_pal_groups(K);
-  a.res_ld = d.res ? d.N : 0;
-  a.has_bias = d.bias != nullptr;
-  a.has_res = d.res != nullptr;
-  a.per_xcd = nwg / 8;
-  a.n_fast = choose_tile_order(2.0 * M * K, 2.0 * d.N * K, (double)mt, (double)nt, false);   // tile 12's order, from the fp16 sizes
-  a.fast_div = a.n_fast ? nt : mt;
-  a.fast_magic = (unsigned)((1ull << 32) / a.fast_div + 1);
-  conv_plan_log(d, ConvPlan{15, bm == 32 ? 1 : 2, 1, false, 0}, bm, a.n_fast);
-  if (bm == 32) launch_sm_pal_bits<32>(a, d.pal_bits, nwg, s);
-  else launch_sm_pal_bits<64>(a, d.pal_bits, nwg, s);
+  a.ngroups = smgemm_pal_groups(d.C0);
+  conv_plan_log(d, ConvPlan{15, bm == 32 ? 1 : 2, 1, false, 0}, bm, n_fast);
+  pal_dispatch_bits(d.pal_bits, "palettized smgemm", [&](auto nb) {
+    if (bm == 32) launch_sm_pal<32, decltype(nb)::value>(a, s);
+    else launch_sm_pal<64, decltype(nb)::value>(a, s);
+  });
   SD_HIP(hipGetLastError());
 }
 

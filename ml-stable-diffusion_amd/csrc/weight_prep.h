@@ -53,11 +53,41 @@ void fold_layernorm_rows(const W* w, const float* bias, const float* gamma, cons
   }
 }
 
+// One lane's share of a palettized weight stream (wstream.hip plan tile 14, smgemm.hip plan tile 15; decoded by pal_decode.h): a
+// little-endian bit stream of nbits-wide fields (field f at bits [f * nbits, (f + 1) * nbits)), padded to whole 16-byte words.
+// Word q of every lane of a wave lies together - [q][lane][16 B] - so each load instruction of a kernel is one coalesced 1-KB wave load.
+struct PalLaneWriter {
+  int nbits;
+  std::vector<uint8_t> bytes;   // the lane's words (+ room for the last window's spill)
+  uint64_t window = 0;          // bits not yet stored, little-endian; fewer than 8 of them between fields
+  int held = 0;
+  size_t at = 0;
+  PalLaneWriter(int nbits_, int words) : nbits(nbits_), bytes((size_t)words * 16 + 8, (uint8_t)0) {}
+  void put(uint64_t index) {
+    window |= index << held;
+    held += nbits;
+    while (held >= 8) {
+      bytes[at++] = (uint8_t)window;
+      window >>= 8;
+      held -= 8;
+    }
+  }
+  // the lane's words into its wave's block of the stream (words x 64 lanes x 16 B), and a fresh lane
+  void flush(uint8_t* wave_block, int lane) {
+    if (held) bytes[at++] = (uint8_t)window;
+    for (size_t q = 0; (q + 1) * 16 + 8 <= bytes.size(); ++q)
+      std::copy(bytes.begin() + q * 16, bytes.begin() + (q + 1) * 16, wave_block + (q * 64 + lane) * 16);
+    std::fill(bytes.begin(), bytes.end(), (uint8_t)0);
+    window = 0;
+    held = 0;
+    at = 0;
+  }
+};
+
 // The palettized weight stream of wstream.hip (plan tile 14).  A lane of the (strip, slice) wave owns NF = 2 * taps fragments of 8
 // weights - fragment j, element e: output row strip * 32 + (lane & 31), input channel slice * 32 + (j & 1) * 16 + (lane >> 5) * 8 + e,
-// tap j >> 1 (the order of wstream_retile_kernel).  Its NF * 8 palette indices, in that order, form one little-endian bit stream of
-// nbits-wide fields (field f at bits [f * nbits, (f + 1) * nbits)), padded to whole 16-byte words; word q of every lane lies at
-// [strip][slice][q][lane][16 B], so each load instruction of the kernel is one coalesced 1-KB wave load.
+// tap j >> 1 (the order of wstream_retile_kernel).  Its NF * 8 palette indices, in that order, are the lane's stream; the wave's block
+// lies at [strip][slice].
 inline int wstream_pal_words(int taps, int nbits) { return (2 * taps * 8 * nbits + 127) / 128; }
 inline size_t wstream_pal_bytes(int N, int Ctot, int ksize, int nbits) {
   return (size_t)(N / 32) * (Ctot / 32) * wstream_pal_words(ksize * ksize, nbits) * 64 * 16;
@@ -65,30 +95,16 @@ inline size_t wstream_pal_bytes(int N, int Ctot, int ksize, int nbits) {
 // indices [N][Ctot][k][k] (the checkpoint's order) -> the stream; dst holds wstream_pal_bytes(...) bytes
 inline void wstream_pal_pack(const uint8_t* indices, int N, int Ctot, int ksize, int nbits, uint8_t* dst) {
   const int taps = ksize * ksize, nslices = Ctot / 32, Q = wstream_pal_words(taps, nbits), nf = 2 * taps;
-  std::vector<uint8_t> lane_bytes((size_t)Q * 16 + 8);   // one lane's stream (+ room for the last window's spill)
+  PalLaneWriter w(nbits, Q);
   for (int strip = 0; strip < N / 32; ++strip)
     for (int slice = 0; slice < nslices; ++slice)
       for (int lane = 0; lane < 64; ++lane) {
         const int n = strip * 32 + (lane & 31);
-        std::fill(lane_bytes.begin(), lane_bytes.end(), (uint8_t)0);
-        uint64_t window = 0;   // bits not yet stored, little-endian; fewer than 8 of them between fields
-        int held = 0;
-        size_t at = 0;
         for (int j = 0; j < nf; ++j) {
           const uint8_t* src = indices + ((size_t)n * Ctot + slice * 32 + (j & 1) * 16 + (lane >> 5) * 8) * taps + (j >> 1);
-          for (int e = 0; e < 8; ++e) {
-            window |= (uint64_t)src[(size_t)e * taps] << held;
-            held += nbits;
-            while (held >= 8) {
-              lane_bytes[at++] = (uint8_t)window;
-              window >>= 8;
-              held -= 8;
-            }
-          }
+          for (int e = 0; e < 8; ++e) w.put(src[(size_t)e * taps]);
         }
-        if (held) lane_bytes[at++] = (uint8_t)window;
-        for (int q = 0; q < Q; ++q)
-          std::copy(lane_bytes.begin() + q * 16, lane_bytes.begin() + (q + 1) * 16, dst + ((((size_t)strip * nslices + slice) * Q + q) * 64 + lane) * 16);
+        w.flush(dst + ((size_t)strip * nslices + slice) * Q * 1024, lane);
       }
 }
 
@@ -96,39 +112,48 @@ inline void wstream_pal_pack(const uint8_t* indices, int N, int Ctot, int ksize,
 // of 16-column strip n / 16 consumes K in stages of 64; lane l = 16 g + r16 multiplies, in stage s and sub-step kk (0, 1), the eight
 // weights W[16 strip + r16][64 s + 32 kk + 8 g + e], e = 0..7: 16 indices per lane per stage.  Stages are cut into GROUPS of
 // kSmPalGroup = 8 (the last group is padded with zero fields that no MFMA consumes); a lane's 128 indices of a group, in the order
-// (s, kk, e), form one little-endian bit stream of nbits-wide fields (field f at bits [f * nbits, (f + 1) * nbits)): exactly nbits
-// 16-byte words.  Word q of every lane lies at [strip][group][q][lane][16 B], so each load instruction of the kernel is one coalesced
-// 1-KB wave load.
+// (s, kk, e), are its stream: exactly nbits words.  The wave's block lies at [strip][group].
 constexpr int kSmPalGroup = 8;
 inline int smgemm_pal_groups(int K) { return (K / 64 + kSmPalGroup - 1) / kSmPalGroup; }
 inline size_t smgemm_pal_bytes(int N, int K, int nbits) { return (size_t)(N / 16) * smgemm_pal_groups(K) * nbits * 64 * 16; }
 // dst holds smgemm_pal_bytes(...) bytes
 inline void smgemm_pal_pack(const uint8_t* indices, int N, int K, int nbits, uint8_t* dst) {
   const int groups = smgemm_pal_groups(K), nk = K / 64;
-  std::vector<uint8_t> lane_bytes((size_t)nbits * 16);
+  PalLaneWriter w(nbits, nbits);
   for (int strip = 0; strip < N / 16; ++strip)
     for (int grp = 0; grp < groups; ++grp)
       for (int lane = 0; lane < 64; ++lane) {
         const uint8_t* row = indices + (size_t)(strip * 16 + (lane & 15)) * K + (lane >> 4) * 8;
-        std::fill(lane_bytes.begin(), lane_bytes.end(), (uint8_t)0);
-        uint64_t window = 0;   // bits not yet stored, little-endian; fewer than 8 of them between fields
-        int held = 0;
-        size_t at = 0;
         for (int f = 0; f < kSmPalGroup * 16; ++f) {
           const int s = grp * kSmPalGroup + (f >> 4), kk = (f >> 3) & 1, e = f & 7;
-          const uint64_t v = s < nk ? row[s * 64 + kk * 32 + e] : 0;
-          window |= v << held;
-          held += nbits;
-          while (held >= 8) {
-            lane_bytes[at++] = (uint8_t)window;
-            window >>= 8;
-            held -= 8;
-          }
-        }   // (128 fields of nbits bits: a whole number of bytes, nothing held)
-        for (int q = 0; q < nbits; ++q)
-          std::copy(lane_bytes.begin() + q * 16, lane_bytes.begin() + (q + 1) * 16,
-                    dst + ((((size_t)strip * groups + grp) * nbits + q) * 64 + lane) * 16);
+          w.put(s < nk ? row[s * 64 + kk * 32 + e] : 0);
+        }
+        w.flush(dst + ((size_t)strip * groups + grp) * nbits * 1024, lane);
       }
+}
+
+// What every upload of a palettized tensor starts from (the operator entry points of capi_ops.cpp, Net::conv): indices inside the
+// palette, the packed stream - smgemm.hip's for `gemm` (indices [N][Ctot], ksize 1), else wstream.hip's - and the LUT zero-padded to
+// the kPalLutHalves entries the kernels copy.  The caller has checked the shape against the layout and owns the device memory.
+inline void palette_check_indices(const char* what, const uint8_t* indices, size_t n, int nbits) {
+  for (size_t i = 0; i < n; ++i)
+    SD_REQUIRE(indices[i] < (1u << nbits), kInvalidArgument, "%s: index %u at element %zu, the palette has %d entries", what,
+               (unsigned)indices[i], i, 1 << nbits);
+}
+struct PaletteHostCopy {
+  std::vector<uint8_t> stream;
+  std::vector<half_t> lut;
+};
+inline PaletteHostCopy palette_host_copy(const char* what, const half_t* lut, int nbits, const uint8_t* indices, int N, int Ctot, int ksize,
+                                         bool gemm) {
+  palette_check_indices(what, indices, (size_t)N * Ctot * ksize * ksize, nbits);
+  PaletteHostCopy h;
+  h.stream.resize(gemm ? smgemm_pal_bytes(N, Ctot, nbits) : wstream_pal_bytes(N, Ctot, ksize, nbits));
+  if (gemm) smgemm_pal_pack(indices, N, Ctot, nbits, h.stream.data());
+  else wstream_pal_pack(indices, N, Ctot, ksize, nbits, h.stream.data());
+  h.lut.assign(kPalLutHalves, (half_t)0);
+  std::copy(lut, lut + (1 << nbits), h.lut.begin());
+  return h;
 }
 
 }  // namespace sd

@@ -11,6 +11,16 @@
 //                         MFMAs as the fragments land (the compiler's in-order vmcnt waits).  The NW waves of a workgroup
 //                         are NW K-slices of the same strip and are summed through LDS once; K-splits across workgroups leave
 //                         fp32 slabs like every split-K kernel of the library.
+//                         TWO WEIGHT SOURCES, one body (template parameter NBITS): the fp16 fragments above (NBITS = 0, plan
+//                         tile 9), or PALETTIZED weights (NBITS = 1 / 2 / 4 / 6 / 8, plan tile 14): a lane loads the bit stream
+//                         of its NF * 8 palette indices instead (weight_prep.h wstream_pal_pack: Q coalesced 16-B words instead
+//                         of NF fragments), the wave keeps the tensor's LUT in its own LDS behind its halo slice, and every
+//                         weight is one 2-byte LDS read into the low or high half of a fragment register (pal_decode.h); the
+//                         two fragments of tap t + 1 are decoded while the MFMAs of tap t issue.  Everything else - halo
+//                         addressing, staging, the MFMAs and their order per accumulator (tap-major, h = 0, 1), the slab sum
+//                         and the slab store - is the same text, so the slabs of tile 14 are bit-identical to tile 9's on
+//                         lut[indices].  Within either source the order of memory operations is fixed: activations first, then
+//                         weights or indices (the compiler's in-order vmcnt waits count on it).
 //   reduce_twin_kernel  - the slab combine, organised per (sample, GroupNorm group): it adds bias / timestep embedding /
 //                         residual, stores the fp16 tensor AND - because a workgroup holds whole (sample, group) slices in
 //                         registers - the GroupNorm(+SiLU) of it that the consuming resnet / SpatialTransformer asks for
@@ -18,6 +28,7 @@
 //                         boundaries fall on the tensor boundary (torch.cat of :213-216): the "twin" goes to its column range
 //                         of the concatenated operand.  The separate GroupNorm launch and its round trip disappear.
 #include "kernels.h"
+#include "pal_decode.h"
 
 namespace sd {
 
@@ -190,33 +201,41 @@ __global__ __launch_bounds__(NT) void reduce_twin_kernel(TwinArgs a) {
 struct WsArgs {
   const half_t* x0;
   const half_t* x1;
-  const half_t* wt;   // pre-tiled weights: [N / 32][nslices][TAPS][2][64 lanes][8 halves]
+  const half_t* wt;   // fp16 source: pre-tiled weights [N / 32][nslices][TAPS][2][64 lanes][8 halves]
   float* partial;     // [S][M][N]
   int C0, C1, nslices;
   int B, Hi, Wi, H, W, ush;   // source image, output (= upsampled source) image, log2 of the nearest upsample factor
   int M, N;
+  const uint8_t* pal;   // palettized source: the index streams [N / 32][nslices][Q][64 lanes][16 B]
+  const half_t* lut;    //   and the tensor's LUT: kPalLutHalves entries (its 2^NBITS, zero-padded)
 };
 
 constexpr int WS_REGION = 16384;   // per-wave LDS: the 32-channel halo slice (<= 200 pixels x 80 B), later its 128 x 32 fp32 tile
 constexpr int WS_ROWB = 80;        // 64 B of channels + 16 B pad: the 16 lanes of a ds_read_b128 group hit distinct banks
+typedef unsigned uintx2 __attribute__((ext_vector_type(2)));
+constexpr int ws_region(int nbits) { return WS_REGION + (nbits ? kPalLutHalves * 2 : 0); }   // palettized: + the wave's copy of the LUT
 
 // NW waves; TAPS 9 (3x3, stride 1, pad 1) or 1 (1x1); WW = image width of the 3x3 form (8: a 128-pixel block is two 8-row
-// sub-tiles, 16: one), ignored for TAPS == 1.  grid (N / 32, ceil(nslices / NW), ceil(M / 128)).
-template <int NW, int TAPS, int WW>
+// sub-tiles, 16: one), ignored for TAPS == 1; NBITS = 0: fp16 weights (a.wt), else the index width of palettized ones (a.pal, a.lut).
+// grid (N / 32, ceil(nslices / NW), ceil(M / 128)).
+template <int NW, int TAPS, int WW, int NBITS>
 __global__ __launch_bounds__(NW * 64) void wstream_kernel(WsArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr bool PAL = NBITS > 0;
+  constexpr int REGION = ws_region(NBITS);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int strip = blockIdx.x, split = blockIdx.y, zb = blockIdx.z;
   const int slice = split * NW + wave;
   const bool live = slice < a.nslices;   // wave-uniform
-  char* const region = smem + wave * WS_REGION;
+  char* const region = smem + wave * REGION;
 
   constexpr int NSUB = TAPS == 9 ? 16 / WW : 1;          // 8-row sub-tiles per block
   constexpr int HW_ = WW + 2, HPS = 10 * HW_;            // halo row length, halo pixels per sub-tile
   constexpr int HP = TAPS == 9 ? NSUB * HPS : 128;       // pixels staged per wave
   constexpr int NL = (HP + 15) / 16;                     // 16-pixel load groups
   constexpr int NF = TAPS * 2;                           // weight fragments per wave
+  constexpr int Q = PAL ? (NF * 8 * NBITS + 127) / 128 : 1;   // 16-B words of a lane's index stream
 
   floatx16 acc[4];
 #pragma unroll
@@ -253,17 +272,29 @@ __global__ __launch_bounds__(NW * 64) void wstream_kernel(WsArgs a) {
       const half8 z = {0, 0, 0, 0, 0, 0, 0, 0};
       xa[i] = ok ? *reinterpret_cast<const half8*>(xs + pix * Cs + coff + piece * 8) : z;
     }
-    // ---- the whole weight slice of this wave: NF fully coalesced 1-KB fragments, all in flight ----
-    const half_t* wp = a.wt + (((size_t)strip * a.nslices + slice) * NF * 64 + lane) * 8;
-    half8 bf[NF];
+    // ---- the whole weight slice of this wave, all in flight: NF fully coalesced 1-KB fragments, or the LUT (8 B per lane: the
+    // padded 512 B) and the Q coalesced 1-KB words of the index stream ----
+    half8 bf[PAL ? 1 : NF];
+    uintx4 wq[Q];
+    uintx2 lv;
+    if constexpr (PAL) {
+      lv = *reinterpret_cast<const uintx2*>(a.lut + lane * 4);
+      const uintx4* sp = reinterpret_cast<const uintx4*>(a.pal) + ((size_t)strip * a.nslices + slice) * (Q * 64) + lane;
 #pragma unroll
-    for (int j = 0; j < NF; ++j) bf[j] = __builtin_nontemporal_load(reinterpret_cast<const half8*>(wp + (size_t)j * 512));
-    // ---- halo slice -> this wave's LDS region (only this wave reads it: no barrier) ----
+      for (int q = 0; q < Q; ++q) wq[q] = __builtin_nontemporal_load(sp + q * 64);
+    } else {
+      const half_t* wp = a.wt + (((size_t)strip * a.nslices + slice) * NF * 64 + lane) * 8;
+#pragma unroll
+      for (int j = 0; j < NF; ++j) bf[j] = __builtin_nontemporal_load(reinterpret_cast<const half8*>(wp + (size_t)j * 512));
+    }
+    // ---- halo slice (and LUT) -> this wave's LDS region (only this wave reads it: no barrier) ----
 #pragma unroll
     for (int i = 0; i < NL; ++i) {
       const int px = i * 16 + (lane >> 2);
       if (px < HP) *reinterpret_cast<half8*>(region + px * WS_ROWB + piece * 16) = xa[i];
     }
+    if constexpr (PAL) *reinterpret_cast<uintx2*>(region + WS_REGION + lane * 8) = lv;
+    const unsigned short* const lutp = reinterpret_cast<const unsigned short*>(region + WS_REGION);
     // ---- fragments: lane (m = lane & 31, hi = lane >> 5) of pixel tile i reads 16 B of its pixel's row under the tap shift ----
     int hb[4];
 #pragma unroll
@@ -286,17 +317,30 @@ __global__ __launch_bounds__(NW * 64) void wstream_kernel(WsArgs a) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) xf[h * 4 + i] = *reinterpret_cast<const half8*>(region + hb[i] + toff + h * 32);
     };
-    half8 xfa[8], xfb[8];
+    // palettized: the two weight fragments of tap t + 1 are decoded beside them (fragments 2 tap, 2 tap + 1 of the lane's stream:
+    // compile-time field positions once the tap loop is unrolled)
+    auto decode_tap = [&](half8 (&wf)[2], int tap) {
+#pragma unroll
+      for (int h = 0; h < 2; ++h) wf[h] = pal_decode<NBITS>(wq, tap * 2 + h, lutp);
+    };
+    half8 xfa[8], xfb[8], wfa[2], wfb[2];
     read_tap(xfa, 0);
+    if constexpr (PAL) decode_tap(wfa, 0);
 #pragma unroll
     for (int tap = 0; tap < TAPS; ++tap) {
       half8(&cur)[8] = (tap & 1) ? xfb : xfa;
       half8(&nxt)[8] = (tap & 1) ? xfa : xfb;
-      if (tap + 1 < TAPS) read_tap(nxt, tap + 1);
+      half8(&wcur)[2] = (tap & 1) ? wfb : wfa;
+      half8(&wnxt)[2] = (tap & 1) ? wfa : wfb;
+      if (tap + 1 < TAPS) {
+        read_tap(nxt, tap + 1);
+        if constexpr (PAL) decode_tap(wnxt, tap + 1);
+      }
 #pragma unroll
       for (int h = 0; h < 2; ++h)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bf[tap * 2 + h], cur[h * 4 + i], acc[i], 0, 0, 0);
+        for (int i = 0; i < 4; ++i)
+          acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(PAL ? wcur[h] : bf[PAL ? 0 : tap * 2 + h], cur[h * 4 + i], acc[i], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
     }
   }
@@ -320,7 +364,7 @@ __global__ __launch_bounds__(NW * 64) void wstream_kernel(WsArgs a) {
     const int id = (((ml >> 5) * 4 + (pc >> 1)) * 64) + (pc & 1) * 32 + (ml & 31);
     floatx4 s = reinterpret_cast<const floatx4*>(smem)[id];
 #pragma unroll
-    for (int w = 1; w < NW; ++w) s += reinterpret_cast<const floatx4*>(smem + w * WS_REGION)[id];
+    for (int w = 1; w < NW; ++w) s += reinterpret_cast<const floatx4*>(smem + w * REGION)[id];
     const int m = zb * 128 + ml, n = strip * 32 + 4 * pc;
     if (m < a.M) out_store(reinterpret_cast<floatx4*>(a.partial + ((size_t)split * a.M + m) * a.N + n), s);
   }
@@ -344,211 +388,29 @@ __global__ __launch_bounds__(256) void wstream_retile_kernel(const half_t* __res
   }
 }
 
-template <int NW, int TAPS, int WW>
+template <int NW, int TAPS, int WW, int NBITS>
 void launch_ws(const WsArgs& a, int splits, hipStream_t s) {
-  auto k = wstream_kernel<NW, TAPS, WW>;
-  const size_t lds = (size_t)NW * WS_REGION;
+  auto k = wstream_kernel<NW, TAPS, WW, NBITS>;
+  const size_t lds = (size_t)NW * ws_region(NBITS);
   static DynLdsOnce once;
   once.set(k, lds);
   hipLaunchKernelGGL(k, dim3(a.N / 32, splits, cdiv(a.M, 128)), dim3(NW * 64), lds, s, a);
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// The same launch from PALETTIZED weights (plan tile 14): a lane loads the bit stream of its NF * 8 palette indices (weight_prep.h
-// wstream_pal_pack: Q coalesced 16-B words instead of NF), the wave keeps the tensor's LUT in its own LDS behind its halo slice, and
-// every weight is one 2-byte LDS read into the low or high half of a fragment register.  The two fragments of tap t + 1 are
-// decoded while the MFMAs of tap t issue; the MFMAs, their order per accumulator (tap-major, h = 0, 1), the slab sum and the slab
-// store are wstream_kernel's, so the slabs are bit-identical to its slabs on lut[indices].
-struct WsPalArgs {
-  WsArgs ws;            // (ws.wt unused)
-  const uint8_t* pal;   // [N / 32][nslices][Q][64 lanes][16 B]
-  const half_t* lut;    // kPalLutHalves entries (the tensor's 2^NBITS, zero-padded)
-};
-
-constexpr int WS_PAL_REGION = WS_REGION + kPalLutHalves * 2;   // + the wave's copy of the LUT
-typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
-typedef unsigned uintx2 __attribute__((ext_vector_type(2)));
-
-template <int NW, int TAPS, int WW, int NBITS>
-__global__ __launch_bounds__(NW * 64) void wstream_pal_kernel(WsPalArgs pa) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const WsArgs& a = pa.ws;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int strip = blockIdx.x, split = blockIdx.y, zb = blockIdx.z;
-  const int slice = split * NW + wave;
-  const bool live = slice < a.nslices;   // wave-uniform
-  char* const region = smem + wave * WS_PAL_REGION;
-
-  constexpr int NSUB = TAPS == 9 ? 16 / WW : 1;
-  constexpr int HW_ = WW + 2, HPS = 10 * HW_;
-  constexpr int HP = TAPS == 9 ? NSUB * HPS : 128;
-  constexpr int NL = (HP + 15) / 16;
-  constexpr int NF = TAPS * 2;
-  constexpr int Q = (NF * 8 * NBITS + 127) / 128;        // 16-B words of a lane's index stream
-  constexpr unsigned MASK = (1u << NBITS) - 1u;
-
-  floatx16 acc[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-
-  if (live) {
-    // ---- activations first, as in wstream_kernel ----
-    const int c = slice * 32;
-    const bool second = c >= a.C0;
-    const half_t* xs = second ? a.x1 : a.x0;
-    const int Cs = second ? a.C1 : a.C0, coff = second ? c - a.C0 : c;
-    const int piece = lane & 3;
-    half8 xa[NL];
-#pragma unroll
-    for (int i = 0; i < NL; ++i) {
-      const int px = i * 16 + (lane >> 2);
-      bool ok;
-      size_t pix;
-      if constexpr (TAPS == 9) {
-        const int sub = px / HPS, r = px - sub * HPS;
-        const int hy = r / HW_, hx = r - hy * HW_;
-        const int sg = zb * NSUB + sub, tpi = a.H >> 3;
-        const int b = sg / tpi, y0 = (sg - b * tpi) * 8;
-        const int iy = y0 + hy - 1, ix = hx - 1;
-        ok = px < HP && b < a.B && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
-        pix = ((size_t)b * a.Hi + (iy >> a.ush)) * a.Wi + (ix >> a.ush);
-      } else {
-        const int m = zb * 128 + px;
-        ok = m < a.M;
-        pix = (size_t)m;
-      }
-      const half8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-      xa[i] = ok ? *reinterpret_cast<const half8*>(xs + pix * Cs + coff + piece * 8) : z;
-    }
-    // ---- the LUT (8 B per lane: the padded 512 B) and this wave's whole index stream: Q coalesced 1-KB loads, all in flight ----
-    const uintx2 lv = *reinterpret_cast<const uintx2*>(pa.lut + lane * 4);
-    const uintx4* sp = reinterpret_cast<const uintx4*>(pa.pal) + ((size_t)strip * a.nslices + slice) * (Q * 64) + lane;
-    uintx4 wq[Q];
-#pragma unroll
-    for (int q = 0; q < Q; ++q) wq[q] = __builtin_nontemporal_load(sp + q * 64);
-    // ---- halo slice and LUT -> this wave's LDS region (only this wave reads them: no barrier) ----
-#pragma unroll
-    for (int i = 0; i < NL; ++i) {
-      const int px = i * 16 + (lane >> 2);
-      if (px < HP) *reinterpret_cast<half8*>(region + px * WS_ROWB + piece * 16) = xa[i];
-    }
-    *reinterpret_cast<uintx2*>(region + WS_REGION + lane * 8) = lv;
-    const unsigned short* const lutp = reinterpret_cast<const unsigned short*>(region + WS_REGION);
-    int hb[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int ml = i * 32 + (lane & 31);
-      if constexpr (TAPS == 9) {
-        const int sub = ml / (8 * WW), rem = ml - sub * (8 * WW);
-        const int y = rem / WW, x = rem - y * WW;
-        hb[i] = (sub * HPS + y * HW_ + x) * WS_ROWB + (lane >> 5) * 16;
-      } else {
-        hb[i] = ml * WS_ROWB + (lane >> 5) * 16;
-      }
-    }
-    auto read_tap = [&](half8 (&xf)[8], int tap) {
-      const int toff = TAPS == 9 ? ((tap / 3) * HW_ + (tap % 3)) * WS_ROWB : 0;
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) xf[h * 4 + i] = *reinterpret_cast<const half8*>(region + hb[i] + toff + h * 32);
-    };
-    // the two weight fragments of a tap: field f = (2 tap + h) * 8 + e of the lane's stream; positions are compile-time constants
-    // once the tap loop is unrolled, a field that straddles a dword is one funnel shift
-    auto decode_tap = [&](half8 (&wf)[2], int tap) {
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        uintx4 pk = {0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const int bit = ((tap * 2 + h) * 8 + e) * NBITS, dw = bit >> 5, sh = bit & 31;
-          const unsigned lo = wq[dw >> 2][dw & 3];
-          unsigned idx;
-          if (sh + NBITS <= 32) {
-            idx = (lo >> sh) & MASK;
-          } else {
-            const int dn = dw + 1;   // (inside the stream: the field ends in it)
-            idx = __builtin_amdgcn_alignbit(wq[dn >> 2][dn & 3], lo, sh) & MASK;
-          }
-          const unsigned v = lutp[idx];
-          pk[e >> 1] = (e & 1) ? (pk[e >> 1] | (v << 16)) : v;
-        }
-        wf[h] = __builtin_bit_cast(half8, pk);
-      }
-    };
-    half8 xfa[8], xfb[8], wfa[2], wfb[2];
-    read_tap(xfa, 0);
-    decode_tap(wfa, 0);
-#pragma unroll
-    for (int tap = 0; tap < TAPS; ++tap) {
-      half8(&cur)[8] = (tap & 1) ? xfb : xfa;
-      half8(&nxt)[8] = (tap & 1) ? xfa : xfb;
-      half8(&wcur)[2] = (tap & 1) ? wfb : wfa;
-      half8(&wnxt)[2] = (tap & 1) ? wfa : wfb;
-      if (tap + 1 < TAPS) {
-        read_tap(nxt, tap + 1);
-        decode_tap(wnxt, tap + 1);
-      }
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wcur[h], cur[h * 4 + i], acc[i], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-  // ---- sum the NW K-slices through LDS and store the slab: wstream_kernel's, over this kernel's region stride ----
-  {
-    floatx4* rg = reinterpret_cast<floatx4*>(region);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) rg[(i * 4 + q) * 64 + lane] = floatx4{acc[i][4 * q], acc[i][4 * q + 1], acc[i][4 * q + 2], acc[i][4 * q + 3]};
-  }
-  __syncthreads();
-  constexpr int PER = 1024 / (NW * 64);
-#pragma unroll
-  for (int it = 0; it < PER; ++it) {
-    const int e = it * (NW * 64) + tid;
-    const int ml = e >> 3, pc = e & 7;
-    const int id = (((ml >> 5) * 4 + (pc >> 1)) * 64) + (pc & 1) * 32 + (ml & 31);
-    floatx4 s = reinterpret_cast<const floatx4*>(smem)[id];
-#pragma unroll
-    for (int w = 1; w < NW; ++w) s += reinterpret_cast<const floatx4*>(smem + w * WS_PAL_REGION)[id];
-    const int m = zb * 128 + ml, n = strip * 32 + 4 * pc;
-    if (m < a.M) out_store(reinterpret_cast<floatx4*>(a.partial + ((size_t)split * a.M + m) * a.N + n), s);
-  }
-}
-
-template <int NW, int TAPS, int WW, int NBITS>
-void launch_ws_pal(const WsPalArgs& a, int splits, hipStream_t s) {
-  auto k = wstream_pal_kernel<NW, TAPS, WW, NBITS>;
-  const size_t lds = (size_t)NW * WS_PAL_REGION;
-  static DynLdsOnce once;
-  once.set(k, lds);
-  hipLaunchKernelGGL(k, dim3(a.ws.N / 32, splits, cdiv(a.ws.M, 128)), dim3(NW * 64), lds, s, a);
-}
-
 template <int NW, int TAPS, int WW>
-void launch_ws_pal_bits(const WsPalArgs& a, int nbits, int splits, hipStream_t s) {
-  switch (nbits) {
-    case 1: launch_ws_pal<NW, TAPS, WW, 1>(a, splits, s); break;
-    case 2: launch_ws_pal<NW, TAPS, WW, 2>(a, splits, s); break;
-    case 4: launch_ws_pal<NW, TAPS, WW, 4>(a, splits, s); break;
-    case 6: launch_ws_pal<NW, TAPS, WW, 6>(a, splits, s); break;
-    case 8: launch_ws_pal<NW, TAPS, WW, 8>(a, splits, s); break;
-    default: fail(kInternal, "palettized wstream: no kernel for %d-bit indices", nbits);
-  }
+void launch_ws_source(const WsArgs& a, int nbits, int splits, hipStream_t s) {   // nbits 0: the fp16 stream
+  if (nbits == 0) launch_ws<NW, TAPS, WW, 0>(a, splits, s);
+  else pal_dispatch_bits(nbits, "palettized wstream", [&](auto nb) { launch_ws<NW, TAPS, WW, decltype(nb)::value>(a, splits, s); });
 }
 
-// the arguments both launchers share (a.wt: the fp16 stream, null on a palettized descriptor)
+// (a.wt: null on a palettized descriptor, a.pal / a.lut on an fp16 one)
 WsArgs ws_args(const ConvDesc& d, float* partial) {
   WsArgs a{};
   a.x0 = d.x0;
   a.x1 = d.x1;
   a.wt = d.w_tiled;
+  a.pal = d.w_pal;
+  a.lut = d.pal_lut;
   a.partial = partial;
   a.C0 = d.C0;
   a.C1 = d.x1 ? d.C1 : 0;
@@ -562,6 +424,28 @@ WsArgs ws_args(const ConvDesc& d, float* partial) {
   a.M = d.B * d.Ho * d.Wo;
   a.N = d.N;
   return a;
+}
+
+// slabs [splits][M][N] of the conv into `partial` from the descriptor's fp16 (nbits 0) or palettized stream; nw = waves (K slices)
+// per workgroup, 4 or 8.  Returns the slab count.
+int launch_ws_conv(const ConvDesc& d, float* partial, int nbits, int nw, hipStream_t s) {
+  const WsArgs a = ws_args(d, partial);
+  if (nw != 4) nw = 8;
+  const int splits = cdiv(a.nslices, nw);
+  if (d.ksize == 3) {
+    if (d.Wo == 8) {
+      if (nw == 4) launch_ws_source<4, 9, 8>(a, nbits, splits, s);
+      else launch_ws_source<8, 9, 8>(a, nbits, splits, s);
+    } else {
+      if (nw == 4) launch_ws_source<4, 9, 16>(a, nbits, splits, s);
+      else launch_ws_source<8, 9, 16>(a, nbits, splits, s);
+    }
+  } else {
+    if (nw == 4) launch_ws_source<4, 1, 8>(a, nbits, splits, s);
+    else launch_ws_source<8, 1, 8>(a, nbits, splits, s);
+  }
+  SD_HIP(hipGetLastError());
+  return splits;
 }
 
 }  // namespace
@@ -588,50 +472,17 @@ void launch_wstream_retile(const half_t* w, half_t* wt, int N, int Ctot, int ksi
   SD_HIP(hipGetLastError());
 }
 
-// slabs [splits][M][N] of the conv into `partial`; nw = waves (K slices) per workgroup, 4 or 8.  Returns the slab count.
 int launch_wstream(const ConvDesc& d, float* partial, int nw, hipStream_t s) {
   SD_REQUIRE(wstream_shape_ok(d) && d.w_tiled, kInvalidArgument, "wstream: shape not eligible (k=%d C0=%d C1=%d N=%d %dx%d)", d.ksize, d.C0,
              d.C1, d.N, d.Ho, d.Wo);
-  const WsArgs a = ws_args(d, partial);
-  if (nw != 4) nw = 8;
-  const int splits = cdiv(a.nslices, nw);
-  if (d.ksize == 3) {
-    if (d.Wo == 8) {
-      if (nw == 4) launch_ws<4, 9, 8>(a, splits, s);
-      else launch_ws<8, 9, 8>(a, splits, s);
-    } else {
-      if (nw == 4) launch_ws<4, 9, 16>(a, splits, s);
-      else launch_ws<8, 9, 16>(a, splits, s);
-    }
-  } else {
-    if (nw == 4) launch_ws<4, 1, 8>(a, splits, s);
-    else launch_ws<8, 1, 8>(a, splits, s);
-  }
-  SD_HIP(hipGetLastError());
-  return splits;
+  return launch_ws_conv(d, partial, 0, nw, s);
 }
 
 int launch_wstream_pal(const ConvDesc& d, float* partial, int nw, hipStream_t s) {
   SD_REQUIRE(wstream_shape_ok(d) && d.w_pal && d.pal_lut && palette_bits_ok(d.pal_bits),
              kInvalidArgument, "palettized wstream: shape not eligible or no palette (k=%d C0=%d C1=%d N=%d %dx%d bits=%d)", d.ksize, d.C0, d.C1,
              d.N, d.Ho, d.Wo, d.pal_bits);
-  const WsPalArgs a{ws_args(d, partial), d.w_pal, d.pal_lut};
-  if (nw != 4) nw = 8;
-  const int splits = cdiv(a.ws.nslices, nw);
-  if (d.ksize == 3) {
-    if (d.Wo == 8) {
-      if (nw == 4) launch_ws_pal_bits<4, 9, 8>(a, d.pal_bits, splits, s);
-      else launch_ws_pal_bits<8, 9, 8>(a, d.pal_bits, splits, s);
-    } else {
-      if (nw == 4) launch_ws_pal_bits<4, 9, 16>(a, d.pal_bits, splits, s);
-      else launch_ws_pal_bits<8, 9, 16>(a, d.pal_bits, splits, s);
-    }
-  } else {
-    if (nw == 4) launch_ws_pal_bits<4, 1, 8>(a, d.pal_bits, splits, s);
-    else launch_ws_pal_bits<8, 1, 8>(a, d.pal_bits, splits, s);
-  }
-  SD_HIP(hipGetLastError());
-  return splits;
+  return launch_ws_conv(d, partial, d.pal_bits, nw, s);
 }
 
 bool reduce_twin_ok(int HW, int N, int n_twins, const GnTwin* tw) {

@@ -413,6 +413,15 @@ def conv2d_palettized(x, lut, indices, nbits, bias=None, res=None, x1=None, upsa
     return out.reshape(-1)[:n].reshape(B, Cout, Ho, Wo), list(plan), ms.value
 
 
+def _packed(pack, *args):
+    """The byte stream of a host-only packer: one call for its size (stream = NULL), one to fill it."""
+    n = C.c_size_t(0)
+    check(pack(*args, None, C.byref(n)))
+    stream = np.zeros(n.value, np.uint8)
+    check(pack(*args, ptr(stream), C.byref(n)))
+    return stream
+
+
 def palette_pack(indices, nbits):
     """The index bit stream of the palettized weight-stream conv (sd_op_palette_pack; host only): indices (Cout, Ctot, k, k) uint8
     -> uint8 array [Cout / 32][Ctot / 32][words][64 lanes][16 bytes]."""
@@ -420,11 +429,7 @@ def palette_pack(indices, nbits):
     Cout, Ctot, k, k2 = indices.shape
     if k != k2:
         raise ValueError("palette_pack: indices must be (Cout, Ctot, k, k)")
-    n = C.c_size_t(0)
-    check(lib().sd_op_palette_pack(ptr(indices), Cout, Ctot, k, nbits, None, C.byref(n)))
-    stream = np.zeros(n.value, np.uint8)
-    check(lib().sd_op_palette_pack(ptr(indices), Cout, Ctot, k, nbits, ptr(stream), C.byref(n)))
-    return stream.reshape(Cout // 32, Ctot // 32, -1, 64, 16)
+    return _packed(lib().sd_op_palette_pack, ptr(indices), Cout, Ctot, k, nbits).reshape(Cout // 32, Ctot // 32, -1, 64, 16)
 
 
 def gemm_palettized(x, lut, indices, nbits, bias=None, res=None, bm=0, out=None, iters=1):
@@ -463,11 +468,7 @@ def palette_pack_gemm(indices, nbits):
     if indices.ndim != 2:
         raise ValueError("palette_pack_gemm: indices must be (Cout, K)")
     Cout, K = indices.shape
-    n = C.c_size_t(0)
-    check(lib().sd_op_palette_pack_gemm(ptr(indices), Cout, K, nbits, None, C.byref(n)))
-    stream = np.zeros(n.value, np.uint8)
-    check(lib().sd_op_palette_pack_gemm(ptr(indices), Cout, K, nbits, ptr(stream), C.byref(n)))
-    return stream.reshape(Cout // 16, -1, nbits, 64, 16)
+    return _packed(lib().sd_op_palette_pack_gemm, ptr(indices), Cout, K, nbits).reshape(Cout // 16, -1, nbits, 64, 16)
 
 
 def groupnorm_shortcut(x0, x1, gn_weight, gn_bias, w, bias=None, groups=32, eps=1e-5, silu=True, side=True, iters=1):
