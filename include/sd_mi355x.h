@@ -208,6 +208,34 @@ int sd_unet_denoise_loop(sd_unet* u, const sd_unet_io* io, float* latents, int n
                          const float* timesteps, const float* coef, const float* sample_scale, int history,
                          float guidance_scale, float* history_io, float* ms_per_step);
 
+/* Progress handler of the device-resident loop: what sample(configuration:progressHandler:) hands its handler as PipelineProgress
+ * after every step (StableDiffusionPipeline.swift:205-210, :332-349, :411-426) and pipeline.py:570-573 its `callback(i, t, latents)`.
+ * step: index into `timesteps`; n_steps: their count (PNDM's doubled entry counts, as Swift's timeSteps.count does); latents: the
+ * latents after that step, (n_images, C, H, W) f32; denoised: the scheduler's de-noised estimate of that step (Swift's
+ * `modelOutputs.last`, the previews of useDenoisedIntermediates, StableDiffusionPipeline.Configuration.swift:43-44), or NULL when
+ * the loop got no `pred`.  Both are host buffers of the handle, valid during the call only.  Returning 0 stops the generation, as
+ * the Swift handler's `false` does. */
+typedef int (*sd_progress_fn)(void* user, int step, int n_steps, const float* latents, const float* denoised);
+/* sd_unet_denoise_loop with that handler; sd_unet_denoise_loop is this entry with pred = NULL, every = 1, fn = NULL.
+ * `pred` (may be NULL): n_steps x 8 f32 rows [pa, pb, ph0, ph1, ph2, 0, 0, 0] of the scheduler's de-noised table; with it every step
+ * also writes  denoised = pa*x + pb*eps + sum_{j<history} ph[j]*hist[j]  from the x, eps and hist[] its update reads (one more fp32
+ * store of the latents per step; the latents, the history and the step count are bit for bit those of a loop without it).
+ * After step i with i % every == 0 (the rule of pipeline.py:570; every >= 1) the latents [and `denoised`] are copied to the host, the
+ * handle's stream is drained and fn runs on the calling thread.  fn returning 0 stops the loop: `latents` receives the latents after
+ * step i, `history_io` is written as at a normal end, *steps_done = i + 1 (n_steps after a full run), the status is SD_OK and only
+ * ms_per_step[0 .. i] are filled.  ms_per_step[i] covers step i's device work only, neither the snapshot copy nor the handler.
+ * Inside the handler this handle's stream is idle, so other handles may be driven (the VAE decoder for a preview); every entry
+ * that would run or reconfigure THIS handle - sd_unet_forward, sd_unet_time_forward, sd_unet_profile, sd_unet_denoise_loop[_progress]
+ * (a refusal of either names sd_unet_denoise_loop_progress, the one entry behind both), sd_unet_set_attention,
+ * sd_unet_attach_controlnets, sd_tune_set_plan_table - returns SD_ERR_INVALID_ARGUMENT before any device work and leaves the loop
+ * undisturbed; the read-only queries (sd_unet_num_residuals, sd_unet_device_bytes, sd_unet_arena_used_bytes, sd_unet_palette_info)
+ * answer as always; destroying the handle there is undefined.  steps_done may be NULL only when fn is. */
+int sd_unet_denoise_loop_progress(sd_unet* u, const sd_unet_io* io, float* latents, int n_images, int n_steps,
+                                  const float* timesteps, const float* coef, const float* sample_scale, int history,
+                                  float guidance_scale, float* history_io, float* ms_per_step,
+                                  const float* pred /* n_steps x 8 or NULL */, int every,
+                                  sd_progress_fn fn, void* user, int* steps_done);
+
 /* ControlNet residuals on the device (replaces the host round trip of pipeline.py:259-284 / :519-529
  * and ControlNet.swift:64-118): `u` (built with support_controlnet) runs the n <= 3 attached
  * ControlNet handles on its own stream before every forward - same sample / timestep /
@@ -450,6 +478,14 @@ int sd_op_timestep_embedding(const float* t, float* out, int n, int dim, int fli
  * [mean | logvar], eps (Cz, h, w), noise and out (n_images, Cz, h, w) f32. */
 int sd_op_posterior_noise(const float* moments, const float* eps, const float* noise, float* out, int Cz, int h, int w, int n_images,
                           float scale_factor, float sa, float sb, int iters, float* ms);
+/* One launch of the loop's step kernel (csrc/misc.hip cfg_sched_step_kernel; pipeline.py:561-569, the update rule documented at
+ * sd_unet_denoise_loop) on host arrays: noise_pred (cfg * n_images, n) f32, rows [uncond..., cond...]; latents (n_images, n) in/out;
+ * hist (history, n_images, n) in/out, or NULL with history = 0; coef: one row of 8; pred: one row of 8 or NULL; step_noise
+ * (n_images, n) or NULL; cfg 1 or 2; history 0..3; denoised (n_images, n) out, needed exactly when pred is given.  *step_after:
+ * the device step counter behind the launch (it starts at 0, so 1); the arrival ticket must be back at 0, else SD_ERR_INTERNAL.
+ * Every device output sits in front of a poisoned guard that the launch must leave alone. */
+int sd_op_sched_step(const float* noise_pred, float* latents, float* hist, const float* coef, const float* pred, const float* step_noise,
+                     float guidance, int cfg, int history, int n_images, int n, float* denoised, int* step_after);
 /* Which plan does the library give a conv / 1x1 GEMM of this shape?  Host only, read only: needs no GPU and launches nothing.
  * The descriptor as plain ints: C0 (+ C1 > 0: a second, channel-concatenated source) -> N over B x Ho x Wo outputs, up = 1 / 2 (nearest
  * upsample in the gather), out_mode 0 plain, 1 token-transposed, 2 GEGLU; flags: 1 LayerNorm fold, 2 timestep embedding, 4 residual,

@@ -37,6 +37,14 @@ UNet& unet_of(sd_unet* u, const char* refusal) {
   SD_REQUIRE(p, kInvalidArgument, "%s", refusal);
   return *p;
 }
+// A handle whose device loop is inside its caller's progress handler (sd_unet_denoise_loop_progress) takes no other call: refused
+// here, before any device work, and the loop goes on undisturbed.
+void require_idle(const sd_unet* u, const char* entry) {
+  const UNet* p = u ? dynamic_cast<const UNet*>(u->impl.get()) : nullptr;
+  SD_REQUIRE(!p || !p->in_progress_handler(), kInvalidArgument,
+             "%s: this handle is running sd_unet_denoise_loop_progress and is inside its progress handler; the handler may drive "
+             "other handles only", entry);
+}
 Vae& vae_of(sd_unet* u, int kind) {
   Vae* p = dynamic_cast<Vae*>(u->impl.get());
   SD_REQUIRE(p && p->config().is_vae_decoder == kind, kInvalidArgument, "handle is not a VAE %s", kind == 2 ? "encoder" : "decoder");
@@ -127,6 +135,7 @@ void sd_unet_destroy(sd_unet* u) { delete u; }
 int sd_unet_set_attention(sd_unet* u, int impl) {
   return guarded([&] {
     SD_REQUIRE(u, kInvalidArgument, "NULL handle");
+    require_idle(u, "sd_unet_set_attention");
     u->impl->set_attention(impl);
   });
 }
@@ -140,6 +149,7 @@ static void require_tune_env() {
 int sd_tune_set_plan_table(const char* rows, sd_unet* u, int* n_plans) {
   return guarded([&] {
     require_tune_env();
+    require_idle(u, "sd_tune_set_plan_table");
     const int n = conv_plan_table_set(rows);
     if (n_plans) *n_plans = n;
     if (u) u->impl->drop_graphs();   // the captured launches bake the old plans in
@@ -161,23 +171,37 @@ int sd_unet_palette_info(const sd_unet* u, int* n_palettized, int* n_streamed, s
 int sd_unet_forward(sd_unet* u, const sd_unet_io* io) {
   return guarded([&] {
     SD_REQUIRE(u && io, kInvalidArgument, "NULL argument");
+    require_idle(u, "sd_unet_forward");
     unet_of(u, "handle is a VAE decoder: use sd_vae_decode").forward(*io);
   });
 }
 int sd_unet_time_forward(sd_unet* u, int warmup, int iters, float* ms_per_iter) {
   return guarded([&] {
     SD_REQUIRE(u && ms_per_iter, kInvalidArgument, "NULL argument");
+    require_idle(u, "sd_unet_time_forward");
     *ms_per_iter = u->impl->time_forward(warmup, iters);
+  });
+}
+int sd_unet_denoise_loop_progress(sd_unet* u, const sd_unet_io* io, float* latents, int n_images, int n_steps,
+                                  const float* timesteps, const float* coef, const float* sample_scale, int history,
+                                  float guidance_scale, float* history_io, float* ms_per_step, const float* pred, int every,
+                                  sd_progress_fn fn, void* user, int* steps_done) {
+  return guarded([&] {
+    SD_REQUIRE(every >= 1, kInvalidArgument, "denoise_loop: every = %d: the handler runs after the steps i with i %% every == 0, every >= 1",
+               every);
+    SD_REQUIRE(!fn || steps_done, kInvalidArgument, "denoise_loop: a progress handler may stop the loop, so steps_done must not be NULL");
+    SD_REQUIRE(u && io && latents && timesteps && coef, kInvalidArgument, "NULL argument");
+    require_idle(u, "sd_unet_denoise_loop_progress");
+    unet_of(u, "denoise_loop needs a UNet handle")
+        .denoise_loop(*io, latents, n_images, n_steps, timesteps, coef, sample_scale, history, guidance_scale, history_io, ms_per_step,
+                      pred, every, fn, user, steps_done);
   });
 }
 int sd_unet_denoise_loop(sd_unet* u, const sd_unet_io* io, float* latents, int n_images, int n_steps,
                          const float* timesteps, const float* coef, const float* sample_scale, int history,
                          float guidance_scale, float* history_io, float* ms_per_step) {
-  return guarded([&] {
-    SD_REQUIRE(u && io && latents && timesteps && coef, kInvalidArgument, "NULL argument");
-    unet_of(u, "denoise_loop needs a UNet handle")
-        .denoise_loop(*io, latents, n_images, n_steps, timesteps, coef, sample_scale, history, guidance_scale, history_io, ms_per_step);
-  });
+  return sd_unet_denoise_loop_progress(u, io, latents, n_images, n_steps, timesteps, coef, sample_scale, history, guidance_scale,
+                                       history_io, ms_per_step, nullptr, 1, nullptr, nullptr, nullptr);
 }
 
 int sd_tune_set_candidate(int tile, int staging, int splitk) {
@@ -193,6 +217,7 @@ int sd_unet_profile(sd_unet* u, int iters, int cap, float* ms, double* flop, cha
   return guarded([&] {
     SD_REQUIRE(u && n_ops && cap >= 0 && (cap == 0 || (ms && flop && labels && label_bytes > 1)), kInvalidArgument,
                "NULL argument");
+    require_idle(u, "sd_unet_profile");
     const std::vector<OpTime> t = u->impl->profile(iters);
     *n_ops = (int)t.size();
     for (int i = 0; i < (int)t.size() && i < cap; ++i) {
@@ -206,6 +231,7 @@ int sd_unet_profile(sd_unet* u, int iters, int cap, float* ms, double* flop, cha
 int sd_unet_attach_controlnets(sd_unet* u, sd_unet* const* controlnets, int n) {
   return guarded([&] {
     SD_REQUIRE(u && n >= 0 && (n == 0 || controlnets), kInvalidArgument, "NULL argument");
+    require_idle(u, "sd_unet_attach_controlnets");
     UNet& unet = unet_of(u, "attach_controlnets needs a UNet handle");
     std::vector<UNet*> v;
     for (int i = 0; i < n; ++i) {

@@ -1169,6 +1169,58 @@ int sd_op_posterior_noise(const float* moments, const float* eps, const float* n
   });
 }
 
+// One launch of cfg_sched_step_kernel (misc.hip) the way the loop launches it, from a zeroed step counter and ticket; the one-row
+// tables sit at step 0.  Latents, history and the de-noised tap's output each sit in front of a poisoned guard.
+int sd_op_sched_step(const float* noise_pred, float* latents, float* hist, const float* coef, const float* pred, const float* step_noise,
+                     float guidance, int cfg, int history, int n_images, int n, float* denoised, int* step_after) {
+  return guarded([&] {
+    SD_REQUIRE(noise_pred && latents && coef && step_after, kInvalidArgument, "NULL argument");
+    SD_REQUIRE((cfg == 1 || cfg == 2) && history >= 0 && history <= 3 && n_images > 0 && n > 0, kInvalidArgument,
+               "sched_step: cfg=%d history=%d n_images=%d n=%d", cfg, history, n_images, n);
+    SD_REQUIRE((history == 0 || hist) && (pred != nullptr) == (denoised != nullptr), kInvalidArgument,
+               "sched_step: history > 0 needs hist, and pred and denoised go together");
+    Scratch sc;
+    const size_t total = (size_t)n_images * n, guard = 256;
+    auto guarded_buf = [&](const float* host, size_t count) {
+      float* d = sc.dev<float>(count + guard);
+      SD_HIP(hipMemset(d, 0xff, (count + guard) * sizeof(float)));   // 0xffffffff: a NaN
+      if (host) SD_HIP(hipMemcpy(d, host, count * sizeof(float), hipMemcpyHostToDevice));
+      return d;
+    };
+    auto check_guard = [&](const float* d, size_t count, const char* what) {
+      std::vector<uint32_t> g(guard);
+      SD_HIP(hipMemcpy(g.data(), d + count, guard * sizeof(float), hipMemcpyDeviceToHost));
+      for (uint32_t v : g) SD_REQUIRE(v == 0xffffffffu, kInternal, "sched_step wrote behind its %zu %s", count, what);
+    };
+    float* dnp = sc.dev<float>((size_t)cfg * total, noise_pred);
+    float* dlat = guarded_buf(latents, total);
+    float* dhist = history ? guarded_buf(hist, (size_t)history * total) : nullptr;
+    float* dden = pred ? guarded_buf(nullptr, total) : nullptr;
+    int* dstep = sc.dev<int>(2);   // zeroed: [0] the step counter, [1] the ticket
+    LoopTables tab{};
+    tab.coef = sc.dev<float>(8, coef);
+    tab.step = dstep;
+    tab.ticket = reinterpret_cast<unsigned*>(dstep + 1);
+    if (step_noise) tab.noise_tab = sc.dev<float>(total, step_noise);
+    if (pred) {
+      tab.pred = sc.dev<float>(8, pred);
+      tab.denoised = dden;
+    }
+    launch_cfg_sched_step(dnp, dlat, dhist, tab, guidance, n_images, n, cfg, history, sc.stream);
+    SD_HIP(hipStreamSynchronize(sc.stream));
+    check_guard(dlat, total, "latents");
+    if (dhist) check_guard(dhist, (size_t)history * total, "history entries");
+    if (dden) check_guard(dden, total, "de-noised latents");
+    int st[2];
+    SD_HIP(hipMemcpy(st, dstep, sizeof(st), hipMemcpyDeviceToHost));
+    SD_REQUIRE(st[1] == 0, kInternal, "sched_step left its arrival ticket at %d", st[1]);
+    *step_after = st[0];
+    SD_HIP(hipMemcpy(latents, dlat, total * sizeof(float), hipMemcpyDeviceToHost));
+    if (dhist) SD_HIP(hipMemcpy(hist, dhist, (size_t)history * total * sizeof(float), hipMemcpyDeviceToHost));
+    if (dden) SD_HIP(hipMemcpy(denoised, dden, total * sizeof(float), hipMemcpyDeviceToHost));
+  });
+}
+
 // The safety checker's attention (vit.hip) on the layout its handle feeds it: qkv (B * S, 3 * heads * d) f16 rows [q | k | v] ->
 // out (B * S, heads * d) f16.  The device output sits in front of a guard of 64 rows; both are filled with NaN patterns before the
 // launch, and a launch that wrote into the guard fails the call.

@@ -444,11 +444,16 @@ struct LoopTables {
   int temb_rows, temb_ld, temb_n;
   // ancestral samplers: [n_steps][Bimg * CHW] noise (already scaled by sigma_up) added to the latents after step `step`, or null
   const float* noise_tab = nullptr;
+  // de-noised tap (progress previews, StableDiffusionPipeline.swift:332 `modelOutputs.last`): with `denoised` set, the step kernel also
+  // writes pa*x + pb*eps + sum_j ph[j]*hist[j] of the values its update reads; pred [n_steps][8]: pa, pb, ph0..ph2, 0, 0, 0.  Both or neither.
+  const float* pred = nullptr;
+  float* denoised = nullptr;   // fp32, the latents' layout
 };
 // latents fp32 NCHW [Bimg][4][H][W] -> UNet sample fp16 NHWC [cfg*Bimg][H][W][4], timestep buffer
 void launch_loop_prep(const float* latents, half_t* sample, float* tbuf, LoopTables t, int Bimg, int C, int H,
                       int W, int cfg, hipStream_t s);
 // eps = u + g*(c-u) (pipeline.py:561-562); m = a*x + b*eps; latents = cx*x + cm*m + sum ch_j * hist_j; step++
+// [t.denoised = pa*x + pb*eps + sum ph_j * hist_j, from the values before the update]
 void launch_cfg_sched_step(const float* noise_pred, float* latents, float* eps_hist, LoopTables t, float guidance,
                            int Bimg, int CHW, int cfg, int hist, hipStream_t s);
 

@@ -239,6 +239,9 @@ __global__ void loop_prep_kernel(const float* __restrict__ latents, half_t* __re
 // evaluation of the PLMS warm-up, Scheduler.swift:228-236).  The workgroup that arrives last at the ticket
 // advances the device step counter (every workgroup read it before arriving), so the step needs no second
 // launch; the ticket only orders that one store, the arithmetic stays atomics-free and deterministic.
+// De-noised tap (t.denoised != null; the previews of StableDiffusionPipeline.swift:332-349): one more linear form of the same x,
+// eps and history, stored to its own buffer from inside a run-time branch - the update's own expressions are untouched, so the
+// latents, the history and the step counter come out bit for bit as without it.
 __global__ __launch_bounds__(256) void cfg_sched_step_kernel(const float* __restrict__ noise_pred,
                                                               float* __restrict__ latents, float* __restrict__ eps_hist,
                                                               LoopTables t, float guidance, int Bimg, int CHW, int cfg,
@@ -255,6 +258,14 @@ __global__ __launch_bounds__(256) void cfg_sched_step_kernel(const float* __rest
       eps = eps + guidance * (c - eps);
     }
     const float x0 = latents[idx];
+    if (t.denoised) {   // reads the history before this step's push below; every lane touches its own idx only
+      const float* pr = t.pred + (size_t)step * 8;
+      // spelled the way m below is contracted (one product rounded, then one fma): where the row is m's own (a, b) - DPM-Solver++ -
+      // the estimate is m bit for bit (tests/test_progress_gpu.py holds the two together)
+      float d = fmaf(pr[0], x0, pr[1] * eps);
+      for (int j = 0; j < hist; ++j) d = fmaf(pr[2 + j], eps_hist[(size_t)j * total + idx], d);
+      t.denoised[idx] = d;
+    }
     const float m = ma * x0 + mb * eps;
     float x = cx * x0 + cm * m;
     // history slot j holds the converted model output of j+1 pushes ago

@@ -973,9 +973,12 @@ void UNet::forward(const sd_unet_io& io) {
 
 // pipeline.py:500-573 on the device: per step {duplicate latents + fp16 cast, [ControlNets,] UNet, CFG
 // combine, scheduler update}; the host only replays one graph per step.
+// Progress (StableDiffusionPipeline.swift:332-349, pipeline.py:570-573): between two replays, after every `every`-th step, the
+// latents [and the de-noised tap's output] are copied to host buffers of this handle, the stream is drained and `fn` runs on the
+// calling thread; fn returning 0 ends the loop behind that step.
 void UNet::denoise_loop(const sd_unet_io& io, float* latents, int n_images, int n_steps, const float* timesteps,
                         const float* coef, const float* sample_scale, int history, float guidance, float* history_io,
-                        float* ms_per_step) {
+                        float* ms_per_step, const float* pred, int every, sd_progress_fn fn, void* user, int* steps_done) {
   SD_HIP(hipSetDevice(ll_.device));
   SD_REQUIRE(!cfg_.is_controlnet, kInvalidArgument, "denoise_loop needs a UNet handle");
   const int cfgmul = guidance > 1.0f ? 2 : 1;   // pipeline.py:443
@@ -1061,6 +1064,18 @@ void UNet::denoise_loop(const sd_unet_io& io, float* latents, int n_images, int 
     SD_HIP(hipMemcpyAsync(noise_tab_, io.step_noise, need * sizeof(float), hipMemcpyHostToDevice, ll_.stream));
     tab.noise_tab = noise_tab_;
   }
+  const bool tap = pred != nullptr;
+  if (tap) {   // the de-noised tap: its table and its output exist from the first call that asks for them
+    if (pred_cap_ < n_steps) {
+      pred_cap_ = std::max(n_steps, 1024);
+      tab_pred_ = ll_.arena.alloc_n<float>((size_t)pred_cap_ * 8);
+      if (!denoised_) denoised_ = ll_.arena.alloc_n<float>((size_t)cfg_.batch * C * H * W);
+      if (loop_graph_) { (void)hipGraphExecDestroy(loop_graph_); loop_graph_ = nullptr; }   // the addresses are baked in
+    }
+    SD_HIP(hipMemcpyAsync(tab_pred_, pred, (size_t)n_steps * 8 * sizeof(float), hipMemcpyHostToDevice, ll_.stream));
+    tab.pred = tab_pred_;
+    tab.denoised = denoised_;
+  }
   auto step_ops = [&]() {
     launch_loop_prep(latents_, x_in_.p, tbuf_, tab, n_images, C, H, W, cfgmul, ll_.stream);
     run_attached();
@@ -1068,9 +1083,13 @@ void UNet::denoise_loop(const sd_unet_io& io, float* latents, int n_images, int 
     launch_cfg_sched_step(noise_pred_, latents_, eps_hist_, tab, guidance, n_images, C * H * W, cfgmul, history,
                           ll_.stream);
   };
-  const int key = n_images * 128 + (io.step_noise ? 64 : 0) + (hoist ? 32 : 0) + history * 4 + (cfgmul - 1) * 2 + (sample_scale ? 1 : 0);
+  const int key = n_images * 128 + (io.step_noise ? 64 : 0) + (hoist ? 32 : 0) + (tap ? 16 : 0) + history * 4 + (cfgmul - 1) * 2 +
+                  (sample_scale ? 1 : 0);
+  // ms_per_step: without a handler step i runs from event i to event i + 1; with one every step has its own pair (2i, 2i + 1), so
+  // that neither the snapshot copy nor the handler counts
+  const bool pairs = fn != nullptr;
   std::unique_ptr<EventList> ev;
-  if (ms_per_step) ev = std::make_unique<EventList>((size_t)n_steps + 1);
+  if (ms_per_step) ev = std::make_unique<EventList>(pairs ? (size_t)n_steps * 2 : (size_t)n_steps + 1);
   if (cfg_.use_graph) {
     // guidance is baked into the captured kernel arguments -> key the graph on its bit pattern too
     int gbits;
@@ -1088,14 +1107,39 @@ void UNet::denoise_loop(const sd_unet_io& io, float* latents, int n_images, int 
       loop_graph_key_ = full_key;
     }
   }
+  if (fn) {
+    snap_latents_.resize(lat_n);
+    if (tap) snap_denoised_.resize(lat_n);
+  }
+  int done = n_steps;
   for (int i = 0; i < n_steps; ++i) {
-    if (ms_per_step) SD_HIP(hipEventRecord((*ev)[i], ll_.stream));
+    if (ms_per_step && (pairs || i == 0)) SD_HIP(hipEventRecord((*ev)[pairs ? 2 * i : 0], ll_.stream));
     if (cfg_.use_graph)
       SD_HIP(hipGraphLaunch(loop_graph_, ll_.stream));
     else
       step_ops();
+    if (ms_per_step) SD_HIP(hipEventRecord((*ev)[pairs ? 2 * i + 1 : i + 1], ll_.stream));
+    if (fn && i % every == 0) {   // pipeline.py:570
+      SD_HIP(hipMemcpyAsync(snap_latents_.data(), latents_, lat_n * sizeof(float), hipMemcpyDeviceToHost, ll_.stream));
+      if (tap) SD_HIP(hipMemcpyAsync(snap_denoised_.data(), denoised_, lat_n * sizeof(float), hipMemcpyDeviceToHost, ll_.stream));
+      SD_HIP(hipStreamSynchronize(ll_.stream));
+      struct Flag {   // the stream is idle: the handler may drive other handles, this one refuses (capi.cpp require_idle)
+        bool& f;
+        explicit Flag(bool& b) : f(b) { f = true; }
+        ~Flag() { f = false; }
+      };
+      int go;
+      {
+        Flag inside(in_handler_);
+        go = fn(user, i, n_steps, snap_latents_.data(), tap ? snap_denoised_.data() : nullptr);
+      }
+      SD_HIP(hipSetDevice(ll_.device));   // the handler may have worked on another device
+      if (!go) {
+        done = i + 1;
+        break;
+      }
+    }
   }
-  if (ms_per_step) SD_HIP(hipEventRecord((*ev)[n_steps], ll_.stream));
   SD_HIP(hipMemcpyAsync(latents, latents_, lat_n * sizeof(float), hipMemcpyDeviceToHost, ll_.stream));
   if (history_io && history > 0)
     for (int j = 0; j < history; ++j)
@@ -1103,7 +1147,9 @@ void UNet::denoise_loop(const sd_unet_io& io, float* latents, int n_images, int 
                             hipMemcpyDeviceToHost, ll_.stream));
   SD_HIP(hipStreamSynchronize(ll_.stream));
   if (ms_per_step)
-    for (int i = 0; i < n_steps; ++i) SD_HIP(hipEventElapsedTime(&ms_per_step[i], (*ev)[i], (*ev)[i + 1]));
+    for (int i = 0; i < done; ++i)
+      SD_HIP(hipEventElapsedTime(&ms_per_step[i], (*ev)[pairs ? 2 * i : i], (*ev)[pairs ? 2 * i + 1 : i + 1]));
+  if (steps_done) *steps_done = done;
 }
 
 }  // namespace sd

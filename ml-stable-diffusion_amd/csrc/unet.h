@@ -19,9 +19,13 @@ class UNet : public Net {
   ~UNet() override;
 
   void forward(const sd_unet_io& io);
+  // pred / every / fn / user / steps_done: the progress handler of sd_unet_denoise_loop_progress (include/sd_mi355x.h); fn == null:
+  // sd_unet_denoise_loop
   void denoise_loop(const sd_unet_io& io, float* latents, int n_images, int n_steps, const float* timesteps,
                     const float* coef, const float* sample_scale, int history, float guidance, float* history_io,
-                    float* ms_per_step);
+                    float* ms_per_step, const float* pred = nullptr, int every = 1, sd_progress_fn fn = nullptr,
+                    void* user = nullptr, int* steps_done = nullptr);
+  bool in_progress_handler() const { return in_handler_; }   // the loop is inside its caller's handler: the handle takes no other call
   // device-resident ControlNet hand-off (pipeline.py:259-284, unet.py:1009-1022): this UNet reads the
   // residual tensors of the attached ControlNet handles straight from HBM and sums them on the device
   void attach_controlnets(const std::vector<UNet*>& cns);
@@ -135,6 +139,13 @@ class UNet : public Net {
   int tab_cap_ = 0;
   float* noise_tab_ = nullptr;      // ancestral samplers: per-step noise of the current call
   size_t noise_cap_ = 0;            // in floats
+  // progress handler: the de-noised tap's table and output (allocated by the first call that gives `pred`), the host snapshots
+  // the handler reads, and the flag that refuses re-entry while it runs
+  float* tab_pred_ = nullptr;       // [pred_cap_][8]
+  int pred_cap_ = 0;
+  float* denoised_ = nullptr;
+  std::vector<float> snap_latents_, snap_denoised_;
+  bool in_handler_ = false;
 };
 
 }  // namespace sd

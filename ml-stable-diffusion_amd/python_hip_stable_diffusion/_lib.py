@@ -70,6 +70,9 @@ class TextEncoderConfig(C.Structure):
 
 ACTS = {"quick_gelu": 0, "gelu": 1}      # hidden_act of the two CLIP towers' configs (launch_clip_act)
 
+# sd_progress_fn: int (*)(void* user, int step, int n_steps, const float* latents, const float* denoised)
+PROGRESS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float))
+
 _lib = None
 
 # every symbol include/sd_mi355x.h declares: (name, restype, argtypes)
@@ -99,6 +102,9 @@ SYMBOLS = [
     ("sd_unet_forward", _I, [_P, C.POINTER(UNetIO)]),
     ("sd_unet_time_forward", _I, [_P, _I, _I, _FP]),
     ("sd_unet_denoise_loop", _I, [_P, C.POINTER(UNetIO), _FP, _I, _I, _FP, _FP, _FP, _I, _F, _FP, _FP]),
+    # (the handler travels as a plain pointer: C.cast(PROGRESS_FN(f), C.c_void_p), NULL for none)
+    ("sd_unet_denoise_loop_progress", _I, [_P, C.POINTER(UNetIO), _FP, _I, _I, _FP, _FP, _FP, _I, _F, _FP, _FP, _FP, _I, _P, _P,
+                                           C.POINTER(_I)]),
     ("sd_tune_set_candidate", _I, [_I, _I, _I]),
     ("sd_tune_set_plan_table", _I, [C.c_char_p, C.c_void_p, C.POINTER(C.c_int)]),
     ("sd_unet_profile", _I, [_P, _I, _I, _FP, C.POINTER(C.c_double), C.c_char_p, _I, C.POINTER(_I)]),
@@ -139,6 +145,7 @@ SYMBOLS = [
                                C.POINTER(C.c_int), _I, _FP]),
     ("sd_op_timestep_embedding", _I, [_FP, _FP, _I, _I, _I, _F]),
     ("sd_op_posterior_noise", _I, [_FP, _FP, _FP, _FP, _I, _I, _I, _I, _F, _F, _F, _I, _FP]),
+    ("sd_op_sched_step", _I, [_FP, _FP, _FP, _FP, _FP, _FP, _F, _I, _I, _I, _I, _FP, C.POINTER(_I)]),
     ("sd_op_conv_plan", _I, [_I] * 18 + [C.POINTER(C.c_int), C.POINTER(C.c_ulonglong)]),
     ("sd_numpy_randn", _I, [C.c_uint32, C.POINTER(C.c_double), C.c_size_t]),
     ("sd_torch_randn", _I, [C.c_uint32, C.POINTER(C.c_double), C.c_size_t]),
@@ -726,6 +733,30 @@ def posterior_noise(moments, eps, noise, scale_factor, sa, sb, iters=1):
     check(lib().sd_op_posterior_noise(fptr(moments), fptr(eps), fptr(noise), fptr(out), Cz, h, w, n_images, float(scale_factor), float(sa),
                                       float(sb), iters, C.byref(ms)))
     return out, ms.value
+
+
+def sched_step(noise_pred, latents, coef, guidance=1.0, hist=None, pred=None, step_noise=None):
+    """One launch of the loop's step kernel (csrc/misc.hip cfg_sched_step_kernel; sd_op_sched_step): noise_pred (cfg * n_images, n),
+    latents (n_images, n), hist (history, n_images, n) or None, coef (8,), pred (8,) or None, step_noise (n_images, n) or None, all
+    f32; cfg = noise_pred rows / latents rows.  Returns (latents, hist or None, denoised or None, step counter behind the launch)."""
+    noise_pred, lat, coef = f32(noise_pred), f32(latents).copy(), f32(coef)
+    if lat.ndim != 2 or noise_pred.ndim != 2 or noise_pred.shape[1] != lat.shape[1] or noise_pred.shape[0] % lat.shape[0] or coef.shape != (8,):
+        raise ValueError("sched_step: noise_pred must be (cfg * n_images, n), latents (n_images, n) and coef (8,)")
+    n_images, n = lat.shape
+    cfg = noise_pred.shape[0] // n_images
+    history = 0 if hist is None else len(hist)
+    hs = None if hist is None else f32(hist).copy()
+    if hs is not None and hs.shape != (history, n_images, n):
+        raise ValueError("sched_step: hist must be (history, n_images, n)")
+    pr = None if pred is None else f32(pred)
+    sn = None if step_noise is None else f32(step_noise)
+    if (pr is not None and pr.shape != (8,)) or (sn is not None and sn.shape != lat.shape):
+        raise ValueError("sched_step: pred must be (8,) and step_noise (n_images, n)")
+    den = None if pr is None else np.empty_like(lat)
+    step = C.c_int(-1)
+    check(lib().sd_op_sched_step(fptr(noise_pred), fptr(lat), fptr(hs), fptr(coef), fptr(pr), fptr(sn), float(guidance), cfg, history,
+                                 n_images, n, fptr(den), C.byref(step)))
+    return lat, hs, den, step.value
 
 
 def numpy_randn(seed, n):

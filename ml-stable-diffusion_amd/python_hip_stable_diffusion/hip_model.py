@@ -340,14 +340,22 @@ class HipModel(_lib.Model):
         return ms.value
 
     def denoise_loop(self, latents, timesteps, coef, guidance_scale, history=0, sample_scale=None, history_state=None,
-                     step_noise=None, **kwargs):
+                     step_noise=None, progress=None, progress_steps=1, pred=None, **kwargs):
         """Device-resident pipeline.py:500-573.  latents (n_img, C, H, W) float32 -> final latents,
         per-step HIP-event milliseconds.  ``kwargs`` are the loop-invariant model inputs
         (encoder_hidden_states, SDXL time_ids / text_embeds), validated like ``__call__`` validates them
         (coreml_model.py:97-116).  ``history_state`` (history, n_img, C, H, W) float32 carries the
         scheduler's multistep history in and out (updated in place) when a loop continues on another
         handle (SDXL base -> refiner).  ``step_noise`` (len(timesteps), n_img, C, H, W) float32: added to the latents at
-        the end of step i - the ancestral samplers' fresh noise, already scaled by sigma_up."""
+        the end of step i - the ancestral samplers' fresh noise, already scaled by sigma_up.
+        ``progress(step, n_steps, latents, denoised)``: called between two steps of the device loop (``sd_unet_denoise_loop_progress``;
+        StableDiffusionPipeline.swift:332-349) after every step with ``step % progress_steps == 0`` (pipeline.py:570), with copies of
+        the latents after that step and - when ``pred`` (len(timesteps), 8), the scheduler's ``denoised_table()``, is given - of its
+        de-noised estimate, else None.  A falsy return other than None stops the loop; an exception in the handler stops it too and is
+        raised again here once the library call has returned.  ``ms`` then holds the steps that ran - as many as after a full run when
+        the stop comes behind the LAST step, so a caller that must know that the handler said stop keeps its verdict itself (the
+        pipeline does).  The handler may drive other
+        handles (a VAE decoder for a preview), not this one (ValueError)."""
         if self.kind != "unet":
             raise ValueError("denoise_loop needs a UNet handle")
         loop_inputs = {k: v for k, v in self.expected_inputs.items()
@@ -387,11 +395,35 @@ class HipModel(_lib.Model):
                 raise ValueError(f"step_noise must have shape {(len(ts),) + lat.shape}, got {sn.shape}")
             keep.append(sn)
             io.step_noise = sn.ctypes.data
+        pr = None
+        if pred is not None:
+            pr = np.ascontiguousarray(pred, dtype=np.float32)
+            if pr.shape != (len(ts), 8):
+                raise ValueError(f"pred must have shape {(len(ts), 8)}, got {pr.shape}")
+        if isinstance(progress_steps, bool) or not isinstance(progress_steps, (int, np.integer)) or progress_steps < 1:
+            raise ValueError(f"`progress_steps` has to be a positive integer but is {progress_steps}")
         ms = np.zeros(len(ts), np.float32)
-        _lib.check(_lib.lib().sd_unet_denoise_loop(self._h, C.byref(io), _lib.fptr(lat), lat.shape[0], len(ts),
-                                                   _lib.fptr(ts), _lib.fptr(cf), _lib.fptr(sc), int(history),
-                                                   float(guidance_scale), _lib.fptr(hs), _lib.fptr(ms)))
-        return lat, ms
+        raised = []
+
+        def trampoline(_user, step, n_steps, lat_p, den_p):
+            try:
+                snap = np.ctypeslib.as_array(lat_p, shape=lat.shape).copy()
+                den = np.ctypeslib.as_array(den_p, shape=lat.shape).copy() if den_p else None
+                go = progress(step, n_steps, snap, den)
+                return 1 if (go is None or go) else 0
+            except BaseException as e:   # an exception cannot unwind through the library: stop the loop, raise behind the call
+                raised.append(e)
+                return 0
+
+        fn = _lib.PROGRESS_FN(trampoline) if progress is not None else None      # alive until the call has returned
+        done = C.c_int(len(ts))
+        _lib.check(_lib.lib().sd_unet_denoise_loop_progress(
+            self._h, C.byref(io), _lib.fptr(lat), lat.shape[0], len(ts), _lib.fptr(ts), _lib.fptr(cf), _lib.fptr(sc), int(history),
+            float(guidance_scale), _lib.fptr(hs), _lib.fptr(ms), _lib.fptr(pr), int(progress_steps),
+            None if fn is None else C.cast(fn, C.c_void_p), None, C.byref(done)))
+        if raised:
+            raise raised[0]
+        return lat, ms[:done.value]
 
     def profile(self, iters=5):
         """[(label, flop, ms)] for every launch-list entry of one forward, in launch order (sd_unet_profile)."""

@@ -24,6 +24,11 @@ tensor hand-offs to the model runners; ``get_hip_pipe`` / ``main`` mirror ``get_
     :74-80; StableDiffusionPipeline.swift:242-262, :361-379; CLI ``--image`` / ``--strength``): the starting image goes through a
     VAE encoder handle, its posterior sample is noised to the first timestep of the truncated schedule on the device
     (``HipVaeEncoder.encode_latents``) and the loop runs over the schedule's tail;
+  * a progress handler, the Swift pipeline's ``sample(configuration:progressHandler:)`` (StableDiffusionPipeline.swift:205-210,
+    :332-349, :411-426; ``useDenoisedIntermediates`` Configuration.swift:43-44; CLI ``--save-every``, StableDiffusionCLI/main.swift:57-63,
+    :260-263): ``progress_handler(PipelineProgress)`` runs after every ``progress_steps``-th step, gets the latents or the scheduler's
+    de-noised estimate with lazily decoded preview images, and stops the generation by returning False.  Unlike ``callback`` it
+    keeps the loop device-resident: the handler runs between two graph replays of ``sd_unet_denoise_loop_progress``;
   * ``--attention-implementation`` is a run-time flag of ``main`` (a conversion-time flag in the
     reference, torch2coreml.py:1678-1685).
 """
@@ -42,6 +47,28 @@ from .schedulers import SCHEDULER_MAP, get_available_schedulers  # noqa: F401  (
 logger = logging.getLogger(__name__)
 VAE_DECODER_UPSAMPLE_FACTOR = 8          # pipeline.py:108
 VAE_SCALING_FACTOR = 0.18215             # pipeline.py:314 (SD 1.x / 2.x); SDXL 0.13025 (main.swift:124)
+
+
+class PipelineProgress:
+    """What the progress handler receives after a step (``PipelineProgress``, StableDiffusionPipeline.swift:411-426): ``pipeline``,
+    ``prompt``, ``step`` (index into the timestep list, over both stages with a refiner), ``step_count`` (the list's length: PNDM's
+    doubled entry counts, like Swift's ``timeSteps.count``), ``current_latent_samples`` (n_images, C, H, W) float32 - the de-noised
+    estimate with ``use_denoised_intermediates``, else the latents - and ``current_images``, decoded from them on first access
+    (``decodeToImages``: the VAE decoder, then the safety checker) in the call's ``output_type``."""
+
+    def __init__(self, pipeline, prompt, step, step_count, current_latent_samples, output_type="np"):
+        self.pipeline, self.prompt, self.step, self.step_count = pipeline, prompt, step, step_count
+        self.current_latent_samples = current_latent_samples
+        self._output_type, self._images = output_type, None
+
+    @property
+    def current_images(self):
+        if self._images is None:
+            if self.pipeline.vae_decoder is None:
+                raise ValueError("current_images needs a pipeline with a VAE decoder")
+            image, _ = self.pipeline.run_safety_checker(self.pipeline.decode_latents(self.current_latent_samples))
+            self._images = self.pipeline.numpy_to_pil(image) if self._output_type == "pil" else image
+        return self._images
 
 
 class HipStableDiffusionPipeline:
@@ -290,11 +317,16 @@ class HipStableDiffusionPipeline:
                  num_images_per_prompt=1, eta=0.0, latents=None, output_type="np", return_dict=True, callback=None,
                  callback_steps=1, controlnet_cond=None, original_size=None, crops_coords_top_left=(0, 0),
                  target_size=None, unet_batch_one=False, seed=None, device_loop=True, rng="numpy", starting_image=None,
-                 strength=1.0, **kwargs):
-        """``starting_image`` (3, H, W) or (1, 3, H, W) in [-1, 1] with ``strength`` < 1.0: image-to-image - the fraction
+                 strength=1.0, progress_handler=None, progress_steps=1, use_denoised_intermediates=False, **kwargs):
+        """``progress_handler(PipelineProgress)``: called after every step i with ``i % progress_steps == 0``; a falsy return other
+        than None stops the generation (``images == []``, ``cancelled=True``, ``latents`` at the stop); it does not move the loop off
+        the device.  ``use_denoised_intermediates``: its ``current_latent_samples`` are the scheduler's de-noised estimate.
+        ``starting_image`` (3, H, W) or (1, 3, H, W) in [-1, 1] with ``strength`` < 1.0: image-to-image - the fraction
         ``strength`` of the schedule runs, from the encoded image noised to its first timestep; without an image, or with
         ``strength`` >= 1.0, text-to-image (mode rule of StableDiffusionPipeline.Configuration.swift:74-80)."""
         self.check_inputs(prompt, height, width, callback_steps)
+        if isinstance(progress_steps, bool) or not isinstance(progress_steps, (int, np.integer)) or progress_steps <= 0:
+            raise ValueError(f"`progress_steps` has to be a positive integer but is {progress_steps}")
         if not strength > 0:
             raise ValueError(f"`strength` has to be positive (a fraction of the schedule in (0, 1]) but is {strength}")
         image_to_image = starting_image is not None and strength < 1.0            # Configuration.swift:74-80
@@ -371,6 +403,24 @@ class HipStableDiffusionPipeline:
             reasons.append("eta != 0")
         fused = not reasons
         step_ms = None
+        cancelled = False
+        pred = None
+        if progress_handler is not None and use_denoised_intermediates:
+            if not hasattr(self.scheduler, "denoised_table"):
+                raise NotImplementedError(f"{type(self.scheduler).__name__} exports no de-noised table (use_denoised_intermediates)")
+            pred = self.scheduler.denoised_table()
+
+        stopped = []                                        # the handler said stop: kept here, since a stop behind a stage's LAST step
+                                                            # leaves as many step times as a full run (denoise_loop's return)
+
+        def report(i, lat_i, den_i):
+            """the handler's verdict on step i of the timestep list: True = go on"""
+            go = progress_handler(PipelineProgress(self, prompt, i, len(timesteps), den_i if use_denoised_intermediates else lat_i,
+                                                   output_type))
+            if not (go is None or bool(go)):
+                stopped.append(i)
+            return not stopped
+
         if fused:
             if not controlnet_cond and getattr(self.unet, "_attached", None):
                 # a previous call attached ControlNets: without conditioning images this call must not run them with the
@@ -389,16 +439,30 @@ class HipStableDiffusionPipeline:
             noise = self.scheduler.step_noise(lat.shape) if hasattr(self.scheduler, "step_noise") else None   # ancestral samplers
             step_ms = []
             for model, emb, kw, first, last in stages:
+                pkw = {}
+                if progress_handler is not None:
+                    # `step` runs over both stages; the library thins by the stage's own index, which agrees where the stage starts
+                    # on a multiple of progress_steps - else it reports every step and the thinning happens here
+                    every = progress_steps if first % progress_steps == 0 else 1
+                    pkw = dict(progress_steps=every, pred=None if pred is None else pred[first:last],
+                               progress=lambda k, _n, lat_k, den_k, first=first: ((first + k) % progress_steps != 0
+                                                                                  or report(first + k, lat_k, den_k)))
                 lat, ms = model.denoise_loop(lat, ts[first:last], coef[first:last], guidance_scale, history=hist,
                                              sample_scale=None if scale is None else scale[first:last],
                                              history_state=state, step_noise=None if noise is None else noise[first:last],
-                                             encoder_hidden_states=emb.astype(np.float16), **kw)
+                                             encoder_hidden_states=emb.astype(np.float16), **pkw, **kw)
                 step_ms.append(ms)
+                if stopped:                                  # the handler stopped this stage: a later one does not run
+                    cancelled = True
+                    break
             latents, step_ms = lat, np.concatenate(step_ms)
         else:
             logger.info("stepping the denoising loop through the host boundary (%s)", "; ".join(reasons))
             if getattr(self.unet, "_attached", None):
                 self.unet.attach_controlnets([])           # host-stepped ControlNet residuals travel like the reference's
+            if pred is not None:                            # the de-noised estimate on the host: the tap of cfg_sched_step_kernel in numpy
+                _, dn_coef, dn_hist = self.scheduler.device_tables()
+                m_hist = [np.zeros(latents.shape, np.float32) for _ in range(dn_hist)]
             for i, t in enumerate(timesteps):                                      # pipeline.py:500-573
                 model, emb, kw, _, _ = next(s for s in stages if s[3] <= i < s[4])
                 x = np.concatenate([latents] * 2) if do_cfg else latents
@@ -422,10 +486,27 @@ class HipStableDiffusionPipeline:
                     noise_uncond, noise_text = halves
                 if do_cfg:
                     noise_pred = noise_uncond + guidance_scale * (noise_text - noise_uncond)
+                denoised = None
+                if pred is not None:
+                    x32, out32 = latents.astype(np.float32), np.asarray(noise_pred, np.float32)
+                    denoised = pred[i, 0] * x32 + pred[i, 1] * out32
+                    for j in range(dn_hist):
+                        denoised = denoised + pred[i, 2 + j] * m_hist[j]
+                    if dn_hist and dn_coef[i, 7] == 0:      # this step's converted output enters the history behind the tap
+                        m_hist = [dn_coef[i, 5] * x32 + dn_coef[i, 6] * out32] + m_hist[:-1]
                 latents = self.scheduler.step(noise_pred, t, latents.astype(np.float32), **extra_step_kwargs).prev_sample
                 if callback is not None and i % callback_steps == 0:
                     callback(i, t, latents)
+                if progress_handler is not None and i % progress_steps == 0:
+                    if not report(i, np.array(latents, np.float32), denoised):
+                        cancelled = True
+                        break
 
+        if cancelled:                                        # Swift returns [] (StableDiffusionPipeline.swift:343-346)
+            if not return_dict:
+                return [], None
+            return PipelineOutput(images=[], nsfw_content_detected=None, step_ms=step_ms, latents=latents, init_latents=init_latents,
+                                  cancelled=True)
         if output_type == "latent" or self.vae_decoder is None:
             image, has_nsfw = latents, None                  # the checker looks at images only
         else:
@@ -436,7 +517,7 @@ class HipStableDiffusionPipeline:
         if not return_dict:
             return image, has_nsfw
         return PipelineOutput(images=image, nsfw_content_detected=has_nsfw, step_ms=step_ms, latents=latents,
-                              init_latents=init_latents)
+                              init_latents=init_latents, cancelled=False)
 
     @staticmethod
     def numpy_to_pil(images):
@@ -652,6 +733,9 @@ def build_parser():
                              "generator, nvidia = torch's CUDA generator (Philox)")
     parser.add_argument("--image", default=None, help="Path to starting image.")          # swift/StableDiffusionCLI/main.swift:45-49
     parser.add_argument("--strength", default=0.5, type=float, help="Strength for image2image.")
+    parser.add_argument("--save-every", default=0, type=int,                                      # swift/StableDiffusionCLI/main.swift:57-63
+                        help="Save the preview image of every n-th step next to the final image, as <final name>.step<i>.png; "
+                             "0 = the final image only")
     parser.add_argument("--quantize-nbits", default=None, choices=(1, 2, 4, 6, 8), type=int,       # torch2coreml.py:1705
                         help="If specified, the UNet / refiner / ControlNet weights are palettized to this many bits at load time "
                              "(k-means LUT per tensor; the conversion-time flag of torch2coreml.py)")
@@ -691,11 +775,26 @@ def main(args):
     i2i = {}
     if getattr(args, "image", None):
         i2i = dict(starting_image=prepare_starting_image(args.image, pipe.height, pipe.width), strength=args.strength)
+    out_path = get_image_path(args)
+    progress = {}
+    save_every = getattr(args, "save_every", 0) or 0
+    if save_every < 0:
+        raise ValueError(f"--save-every has to be 0 or a positive step count but is {save_every}")
+    if save_every:                                                                 # StableDiffusionCLI/main.swift:260-263
+        stem = os.path.splitext(out_path)[0]
+
+        def save_previews(p):
+            logger.info("Step %d of %d", p.step, p.step_count)
+            if p.step % save_every == 0:
+                p.current_images[0].save(f"{stem}.step{p.step}.png")
+            return True
+
+        progress = dict(progress_handler=save_previews)
     logger.info("Beginning image generation.")
     image = pipe(prompt=args.prompt, height=pipe.height, width=pipe.width, num_inference_steps=args.num_inference_steps,
                  guidance_scale=args.guidance_scale, controlnet_cond=controlnet_cond, negative_prompt=args.negative_prompt,
-                 unet_batch_one=args.unet_batch_one, seed=args.seed, output_type="pil", rng=getattr(args, "rng", "numpy"), **i2i)
-    out_path = get_image_path(args)
+                 unet_batch_one=args.unet_batch_one, seed=args.seed, output_type="pil", rng=getattr(args, "rng", "numpy"), **i2i,
+                 **progress)
     logger.info("Saving generated image to %s", out_path)
     image["images"][0].save(out_path)
     return out_path
