@@ -499,6 +499,13 @@ int sd_op_sched_step(const float* noise_pred, float* latents, float* hist, const
  * *workspace_bytes: the slab workspace this launch needs. */
 int sd_op_conv_plan(int ksize, int stride, int up, int C0, int C1, int N, int B, int Ho, int Wo, int out_mode, int flags, int n_trans,
                     int n_twins, int gnf_groups, int tile, int staging, int splitk, int copies, int* plan, unsigned long long* workspace_bytes);
+/* No reference counterpart.  The same question with the same 18 descriptor arguments, answered with the kernel that launches: one
+ * NUL-terminated line in text[text_bytes] (64 bytes hold every answer) in the format of csrc/conv_plan.h conv_plan_kernel_name, e.g.
+ * "igemm 64x64 ring4 kg2", "gemm_pipe 128x64 ring3", "halo_ks ring6", "wstream waves8", "bvgemm v3", "smgemm bm32", "generic":
+ * kernel family, tile, the ring depth that runs after the fall-back to one that fits the LDS, in-workgroup K groups, register
+ * staging, wave count, variant - what the (tile, staging) codes of sd_op_conv_plan mean for this descriptor.  Host only. */
+int sd_op_conv_plan_kernel(int ksize, int stride, int up, int C0, int C1, int N, int B, int Ho, int Wo, int out_mode, int flags, int n_trans,
+                           int n_twins, int gnf_groups, int tile, int staging, int splitk, int copies, char* text, int text_bytes);
 /* numpy legacy stream: np.random.seed(seed); np.random.randn(n) (pipeline.py:331,:726;
  * NumPyRandomSource.swift:28-102).  Host-side, bit-exact. */
 int sd_numpy_randn(uint32_t seed, double* out, size_t n);

@@ -16,6 +16,7 @@
 //   * epilogue through an LDS tile, whole rows out (bias, LayerNorm fold, residual, or value * gelu(gate) for GEGLU rows in the
 //     lane order of wsgemm.hip).
 // One workgroup of 8 waves per CU (2 per SIMD), like the 256 x 256 8-phase template of the CDNA guide; plain HIP, no inline asm.
+#include "conv_plan.h"
 #include "kernels.h"
 
 #include <type_traits>
@@ -415,9 +416,10 @@ int bvgemm_auto_variant(const ConvDesc& d) {
   return 1;
 }
 
-void launch_bvgemm(const ConvDesc& d, int variant, hipStream_t s) {
-  SD_REQUIRE(bvgemm_shape_ok(d) && d.w_bv, kInvalidArgument, "bvgemm: shape not eligible (C0=%d N=%d mode=%d)", d.C0, d.N, d.out_mode);
-  if (variant < 1 || variant > 6) variant = bvgemm_auto_variant(d);
+void launch_bvgemm(const ConvDesc& d, const ConvPlan& p, hipStream_t s) {
+  const int variant = p.variant;
+  SD_REQUIRE(bvgemm_shape_ok(d) && d.w_bv && variant >= 1 && variant <= 6, kInvalidArgument, "bvgemm: shape not eligible (C0=%d N=%d mode=%d)", d.C0, d.N,
+             d.out_mode);
   const int tcols = (variant == 5 || variant == 6) ? 64 : (variant == 4 ? 128 : 256);   // columns per workgroup
   SD_REQUIRE(d.N % tcols == 0, kInvalidArgument, "bvgemm variant %d does not tile N=%d", variant, d.N);
   SD_REQUIRE(!d.out_t || (tcols >= 128 && d.n_trans % tcols == 0), kInvalidArgument,

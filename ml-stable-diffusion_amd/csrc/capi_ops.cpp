@@ -5,8 +5,8 @@
 // Plan codes of the entry points (A/B testing and tuning tools; the header describes them for callers):
 //   conv `tile` (sd_op_conv2d, _conv2d_ex, _groupnorm, _groupnorm_proj, _groupnorm_conv3x3): plan tile = tile % 10, staging = tile / 10
 //     tile    0 the library's plan, 1 128x128, 2 128x64, 3 64x64, 4 64x128, 7 the 3x3 halo kernel, 9 wstream.hip (needs w_tiled)
-//     staging 0 LDS-DMA 2-stage, 1 HBM -> VGPR -> LDS, 2 LDS-DMA 3-stage ring, ...; 12 / 13 (codes 12x / 13x) igemm_kernel's
-//             in-workgroup split-K rings
+//     staging the code that goes with the tile (ring depth, register staging, the pipelined kernel, in-workgroup split-K, wave count):
+//             decoded by decode_plan (conv_plan.cpp) and nowhere else; sd_op_conv_plan_kernel names the kernel a pair launches
 //     sd_op_conv2d / sd_op_conv2d_ex alone: 110-116 plan tile 11 (bvgemm.hip: its own choice / variants 1-6, needs w_bv),
 //                                           140-142 plan tile 12 (smgemm.hip: tile height by M / 32 rows / 64 rows)
 //     (plan tiles 14 / 15 read palettized weights: sd_op_conv2d_palettized / sd_op_gemm_palettized)
@@ -231,7 +231,7 @@ void conv2d_op(const void* x, const void* w, const float* bias, const void* res,
                ksize, Cin, e.C1, Cout, Ho, Wo);
     upload_palette(sc, d, "palettized conv", e.pal_lut, e.pal_bits, e.pal_indices, false);
     d.tile = 14;
-    d.staging = e.pal_waves == 4 ? 4 : 0;
+    d.staging = conv_plan_waves_code(e.pal_waves);
   }
   half_t* dtwin = nullptr;
   if (e.twin_groups) {   // the GroupNorm as a twin of the conv's slab combine (sd_op_conv2d_groupnorm's producer_stats = 2)
@@ -1089,45 +1089,66 @@ int sd_op_gn_proj_qkv(const void* x_in, const void* conv_w, const float* gn_weig
   });
 }
 
+// the descriptor sd_op_conv_plan / sd_op_conv_plan_kernel ask about and its plan; c: the copies a handle of the library holds for it
+static ConvPlan query_conv_plan(int ksize, int stride, int up, int C0, int C1, int N, int B, int Ho, int Wo, int out_mode, int flags, int n_trans,
+                                int n_twins, int gnf_groups, int tile, int staging, int splitk, int copies, ConvWeightCopies& c) {
+  SD_REQUIRE(ksize >= 1 && stride >= 1 && up >= 1 && C0 >= 1 && C1 >= 0 && N >= 1 && B >= 1 && Ho >= 1 && Wo >= 1 &&
+                 n_trans >= 0 && n_twins >= 0 && n_twins <= 2 && gnf_groups >= 0 && copies >= -1 && copies <= 7,
+             kInvalidArgument, "bad conv_plan arguments");
+  static const float present[4] = {};   // the planner only tests these pointers
+  const half_t* ph = reinterpret_cast<const half_t*>(present);
+  ConvDesc d;
+  d.x0 = d.w = ph;
+  d.C0 = C0;
+  if (C1 > 0) d.x1 = ph, d.C1 = C1;
+  d.B = B; d.Ho = Ho; d.Wo = Wo; d.Hi = Ho * stride / up; d.Wi = Wo * stride / up;
+  d.ksize = ksize; d.stride = stride; d.up = up; d.N = N; d.out_mode = out_mode;
+  if (flags & 1) d.ln_colsum = present;
+  if (flags & 2) d.temb = present;
+  if (flags & 4) d.res = ph;
+  if (flags & 8) d.gn_partial = const_cast<float*>(present), d.gn_groups = 32;
+  if (flags & 16) d.bias = present;
+  if (flags & 32) d.pad = 0;
+  if (n_trans > 0) d.out_t = const_cast<half_t*>(ph), d.n_trans = n_trans, d.ldT = Ho * Wo;
+  d.n_twins = n_twins;
+  if (gnf_groups > 0) {   // GroupNorm of the input folded into this launch, as the UNet's resnets / transformers ask for it
+    d.gnf_partial = d.gnf_gamma = d.gnf_beta = present;
+    d.gnf_groups = gnf_groups;
+    d.gnf_entries = 1;
+    d.gnf_silu = ksize == 3 ? 1 : 0;
+  }
+  d.tile = tile; d.staging = staging; d.splitk = splitk;
+  c = conv_plan_copies(d);
+  if (copies < 0) copies = (c.wstream ? 1 : 0) | (c.wsgemm ? 2 : 0) | (c.bvgemm ? 4 : 0);   // what a handle of the library holds
+  if (copies & 1) d.w_tiled = ph;
+  if (copies & 2) d.w_ws = ph;
+  if (copies & 4) d.w_bv = ph;
+  return conv_plan(d);
+}
+
 // Which plan does a conv / 1x1 GEMM of this shape get (conv_plan.h)?  Host only: no GPU, nothing launched.
 int sd_op_conv_plan(int ksize, int stride, int up, int C0, int C1, int N, int B, int Ho, int Wo, int out_mode, int flags, int n_trans,
                     int n_twins, int gnf_groups, int tile, int staging, int splitk, int copies, int* plan, unsigned long long* workspace_bytes) {
   return guarded([&] {
-    SD_REQUIRE(plan && workspace_bytes && ksize >= 1 && stride >= 1 && up >= 1 && C0 >= 1 && C1 >= 0 && N >= 1 && B >= 1 && Ho >= 1 && Wo >= 1 &&
-                   n_trans >= 0 && n_twins >= 0 && n_twins <= 2 && gnf_groups >= 0 && copies >= -1 && copies <= 7,
-               kInvalidArgument, "bad conv_plan arguments");
-    static const float present[4] = {};   // the planner only tests these pointers
-    const half_t* ph = reinterpret_cast<const half_t*>(present);
-    ConvDesc d;
-    d.x0 = d.w = ph;
-    d.C0 = C0;
-    if (C1 > 0) d.x1 = ph, d.C1 = C1;
-    d.B = B; d.Ho = Ho; d.Wo = Wo; d.Hi = Ho * stride / up; d.Wi = Wo * stride / up;
-    d.ksize = ksize; d.stride = stride; d.up = up; d.N = N; d.out_mode = out_mode;
-    if (flags & 1) d.ln_colsum = present;
-    if (flags & 2) d.temb = present;
-    if (flags & 4) d.res = ph;
-    if (flags & 8) d.gn_partial = const_cast<float*>(present), d.gn_groups = 32;
-    if (flags & 16) d.bias = present;
-    if (flags & 32) d.pad = 0;
-    if (n_trans > 0) d.out_t = const_cast<half_t*>(ph), d.n_trans = n_trans, d.ldT = Ho * Wo;
-    d.n_twins = n_twins;
-    if (gnf_groups > 0) {   // GroupNorm of the input folded into this launch, as the UNet's resnets / transformers ask for it
-      d.gnf_partial = d.gnf_gamma = d.gnf_beta = present;
-      d.gnf_groups = gnf_groups;
-      d.gnf_entries = 1;
-      d.gnf_silu = ksize == 3 ? 1 : 0;
-    }
-    d.tile = tile; d.staging = staging; d.splitk = splitk;
-    const ConvWeightCopies c = conv_plan_copies(d);
-    if (copies < 0) copies = (c.wstream ? 1 : 0) | (c.wsgemm ? 2 : 0) | (c.bvgemm ? 4 : 0);   // what a handle of the library holds
-    if (copies & 1) d.w_tiled = ph;
-    if (copies & 2) d.w_ws = ph;
-    if (copies & 4) d.w_bv = ph;
-    const ConvPlan p = conv_plan(d);
+    SD_REQUIRE(plan && workspace_bytes, kInvalidArgument, "bad conv_plan arguments");
+    ConvWeightCopies c;
+    const ConvPlan p = query_conv_plan(ksize, stride, up, C0, C1, N, B, Ho, Wo, out_mode, flags, n_trans, n_twins, gnf_groups, tile, staging, splitk, copies, c);
     plan[0] = p.tile; plan[1] = p.staging; plan[2] = p.splitk; plan[3] = p.slab ? 1 : 0;
     plan[4] = c.wstream ? 1 : 0; plan[5] = c.wsgemm ? 1 : 0; plan[6] = c.bvgemm ? 1 : 0;
     *workspace_bytes = p.workspace_bytes;
+  });
+}
+
+// The same question, answered with the kernel that launches: conv_plan_kernel_name (conv_plan.h) of the plan, NUL-terminated into text
+int sd_op_conv_plan_kernel(int ksize, int stride, int up, int C0, int C1, int N, int B, int Ho, int Wo, int out_mode, int flags, int n_trans,
+                           int n_twins, int gnf_groups, int tile, int staging, int splitk, int copies, char* text, int text_bytes) {
+  return guarded([&] {
+    SD_REQUIRE(text && text_bytes >= 1, kInvalidArgument, "bad conv_plan_kernel arguments");
+    ConvWeightCopies c;
+    const std::string name = conv_plan_kernel_name(
+        query_conv_plan(ksize, stride, up, C0, C1, N, B, Ho, Wo, out_mode, flags, n_trans, n_twins, gnf_groups, tile, staging, splitk, copies, c));
+    SD_REQUIRE((int)name.size() < text_bytes, kInvalidArgument, "conv_plan_kernel: the text buffer holds %d bytes, the line needs %zu", text_bytes, name.size() + 1);
+    memcpy(text, name.c_str(), name.size() + 1);
   });
 }
 

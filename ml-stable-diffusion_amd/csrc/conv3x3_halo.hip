@@ -18,7 +18,7 @@ namespace {
 // 5 / 6 - lost to the K-split kernel below on every shape of every model and was removed in round 4; its ablation is
 // profiles/r02_ablate_halo.txt.)
 // ---------------------------------------------------------------------------------------------
-constexpr int HALO_W = 18, HALO_ROWS = 180, HALO_PIECES = 23, HALO_LDS_ROWS = 184, HALO_PPW = 6;
+constexpr int HALO_W = 18, HALO_ROWS = 180, HALO_PIECES = 23, HALO_LDS_ROWS = kHaloLdsRows, HALO_PPW = 6;
 
 constexpr int halo_mod9(int t) { return ((t % 9) + 9) % 9; }
 // halo pieces of the NEXT chunk a wave issues in tap step `tap`.  Plain kernel: one per step in steps 0-5.  GNL (GroupNorm in the
@@ -29,10 +29,7 @@ constexpr int halo_x_issued(int tap) {
   const int t = halo_mod9(tap);
   return GNL ? (t == 0 ? 2 : (t <= 4 ? 1 : 0)) : (t < HALO_PPW ? 1 : 0);
 }
-// D = stages of the weight ring (D - 1 tap steps of weights in flight; 2 = the round-1 double buffer).
-constexpr size_t halo_lds_bytes(int bn, int d) {
-  return ((size_t)2 * HALO_LDS_ROWS * BK + (size_t)d * bn * BK) * sizeof(half_t) + bn * sizeof(float);
-}
+// D = stages of the weight ring (D - 1 tap steps of weights in flight; 2 = the round-1 double buffer): halo_lds_bytes (conv_plan.h)
 
 // ---------------------------------------------------------------------------------------------
 // Software-pipelined, K-split variant of the halo kernel (plan tile 7).  Measured on the kernel above
@@ -579,27 +576,20 @@ __global__ __launch_bounds__(256, halo_lds_bytes(64, D) <= 80 * 1024 ? 2 : 1) vo
 
 #undef HALO_SRC
 
-// staging (the table's ring code): 0 = 2 weight stages (two workgroups per CU), 2 / 3 = 3 / 4 stages, 4 / 5 = 6 / 8 stages
-// GNL: the [3][Ctot] fp16 GroupNorm table takes the place of the epilogue constants behind the ring (conv3x3_halo_ks_kernel)
-constexpr size_t halo_gnl_lds_cap = 160 * 1024;
-inline size_t halo_gnl_lds_bytes(int d, int ctot) {
-  const size_t k_loop = halo_lds_bytes(64, d) - 64 * sizeof(float) + (((size_t)6 * ctot + 15) & ~(size_t)15);
-  const size_t epilogue = 32 * 1024 + 128 * (64 + 8) * 2 + 64 * sizeof(float);
-  return std::max(k_loop, epilogue);
-}
+// 2 weight stages: two workgroups per CU.  GNL: halo_gnl_lds_bytes (conv_plan.h)
 template <int D, int DBG = 0, bool GNL = false>
 void launch_halo_ks_d(const IgemmArgs& a, hipStream_t s) {
   const size_t lds = GNL ? halo_gnl_lds_bytes(D, a.Ctot) : halo_lds_bytes(64, D);
-  static_assert(halo_lds_bytes(64, D) <= 160 * 1024, "LDS");
+  static_assert(halo_lds_bytes(64, D) <= kLdsBudget, "LDS");
   auto k = conv3x3_halo_ks_kernel<D, DBG, GNL>;
   static DynLdsOnce once;
-  once.set(k, GNL ? halo_gnl_lds_cap : lds);   // GNL: the table grows with Ctot - allow the full LDS once
+  once.set(k, GNL ? kLdsBudget : lds);   // GNL: the table grows with Ctot - allow the full LDS once
   dim3 grid(a.B * a.tiles_x * a.tiles_y * cdiv(a.N, 64), a.splitk);
   hipLaunchKernelGGL(k, grid, dim3(256), lds, s, a);
 }
 
-// ring code 0 / 2 / 3 / 4 / 5 = 2 / 3 / 4 / 6 / 8 weight stages
-void launch_halo_ks_ring(const IgemmArgs& a, int staging, hipStream_t s) {
+// stages: the ring depth the plan resolved (GroupNorm in the loader: 3 / 4 only, the table must fit - decode_plan)
+void launch_halo_ks_ring(const IgemmArgs& a, int stages, hipStream_t s) {
   if (a.debug >= 32) {   // ablation builds of the 4-stage kernel: debug = 32 + DBG bits
     switch (a.debug - 32) {
       case 1: launch_halo_ks_d<4, 1>(a, s); return;
@@ -614,16 +604,16 @@ void launch_halo_ks_ring(const IgemmArgs& a, int staging, hipStream_t s) {
       default: break;
     }
   }
-  if (a.gnf_partial) {   // GroupNorm in the loader: rings of 3 / 4 stages only (launch_conv checked the shape)
-    if (staging >= 3 && halo_gnl_lds_bytes(4, a.Ctot) <= halo_gnl_lds_cap) launch_halo_ks_d<4, 0, true>(a, s);
-    else launch_halo_ks_d<3, 0, true>(a, s);
-    return;
+  const bool gnl = a.gnf_partial != nullptr;
+  switch (stages) {
+    case 2: if (!gnl) return launch_halo_ks_d<2>(a, s); break;
+    case 3: return gnl ? launch_halo_ks_d<3, 0, true>(a, s) : launch_halo_ks_d<3>(a, s);
+    case 4: return gnl ? launch_halo_ks_d<4, 0, true>(a, s) : launch_halo_ks_d<4>(a, s);
+    case 6: if (!gnl) return launch_halo_ks_d<6>(a, s); break;
+    case 8: if (!gnl) return launch_halo_ks_d<8>(a, s); break;
+    default: break;
   }
-  if (staging >= 5) { launch_halo_ks_d<8>(a, s); return; }
-  if (staging >= 4) { launch_halo_ks_d<6>(a, s); return; }
-  if (staging >= 3) { launch_halo_ks_d<4>(a, s); return; }
-  if (staging >= 2) { launch_halo_ks_d<3>(a, s); return; }
-  launch_halo_ks_d<2>(a, s);
+  SD_REQUIRE(false, kInternal, "halo conv: no kernel with a ring of %d stages (GroupNorm loader %d)", stages, gnl ? 1 : 0);
 }
 
 }  // namespace
@@ -634,16 +624,16 @@ bool conv_gn_loader_ok(const ConvDesc& d) {
   const int ctot = d.C0 + c1;
   return d.ksize == 3 && d.stride == 1 && d.up == 1 && halo_ks_ok(d) && !d.ln_colsum && !d.out_t && d.out_mode == kOutHalf && !d.debug &&
          d.gnf_groups >= 1 && d.gnf_groups <= 32 && ctot % d.gnf_groups == 0 && ctot <= 2048 && d.Hi == d.Ho && d.Wi == d.Wo &&
-         halo_gnl_lds_bytes(3, ctot) <= halo_gnl_lds_cap;
+         halo_gnl_lds_bytes(3, ctot) <= kLdsBudget;
 }
 
 // plan tile 7.  Returns the GroupNorm partial entries per (sample, group) the epilogue wrote (setup_gn_stats).
 int launch_halo_ks(const ConvDesc& d, const ConvPlan& p, float* partial, hipStream_t s) {
   IgemmArgs a = planned_args(d, p, partial);
-  set_tile_order(a, 7);
+  set_tile_order(a, p.bm, p.bn, true);
   const int gn_entries = setup_gn_stats(d, a, 0);
   a.nk_total = a.Ctot / BK;   // the kernel walks 64-channel chunks
-  launch_halo_ks_ring(a, p.staging, s);
+  launch_halo_ks_ring(a, p.stages, s);
   return gn_entries;
 }
 

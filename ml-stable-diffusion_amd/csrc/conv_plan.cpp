@@ -44,7 +44,7 @@ const Switches& switches() {
 struct Plan {
   int tile;     // 1: 128x128, 2: 128x64, 3: 64x64, 4: 64x128
   int splitk;
-  int staging = 0;   // from the tuned table (tile / 10): 0 two-stage LDS-DMA, 2 / 3 = 3- / 4-stage ring
+  int staging = 0;   // the code beside the tile (decode_plan)
 };
 
 // the LayerNorm fold needs whole rows per workgroup, the fused q|k|v epilogue has no slab path
@@ -55,6 +55,8 @@ bool can_stream(const ConvDesc& d) { return d.w_tiled != nullptr && can_split(d)
 bool pal_stream(const ConvDesc& d) { return d.w_pal != nullptr && !d.pal_gemm; }
 // the same for the small-M 1x1 GEMM (plan tile 15): the descriptor carries the stream of smgemm_pal_pack
 bool pal_gemm(const ConvDesc& d) { return d.w_pal != nullptr && d.pal_gemm; }
+// tiles 9 / 14: the code's wave count (decode_plan)
+int wstream_waves(int code) { return code == 4 ? 4 : 8; }
 // fp32 slabs of a launch: one per split, one when only `slab` (weight stream, GroupNorm twins) asks for the slab path
 size_t slab_bytes(const Dims& a, int splits, bool slab) { return (splits > 1 || slab) ? (size_t)splits * a.M * a.N * sizeof(float) : 0; }
 
@@ -64,7 +66,7 @@ size_t slab_bytes(const Dims& a, int splits, bool slab) { return (splits > 1 || 
 // 16x16 levels stream weights: SURVEY.md 7.3(1)) end up split, shallow 1x1 GEMMs end up on the
 // small tile with many workgroups.
 // kind: 0 plain epilogue (bias / timestep embedding / residual), 1 LayerNorm-folded, 2 GEGLU (LayerNorm-folded or
-// not), 3 fused q|k|v (LayerNorm-folded, V columns leave transposed).  staging: see launch_tile.
+// not), 3 fused q|k|v (LayerNorm-folded, V columns leave transposed).  staging: see decode_plan.
 struct TunedConv { int kind, ksize, stride, up, ctot, n, m, tile, staging, splitk; };
 #if __has_include("tuned_convs.inc")
 static const TunedConv kTuned[] = {
@@ -110,6 +112,16 @@ std::vector<TunedConv>& runtime_table() {
 struct TuneCandidate { int tile = 0, staging = 0, splitk = 0; };
 TuneCandidate g_tune;
 
+void tile_dims(int tile, int& bm, int& bn) {
+  switch (tile) {
+    case 7: bm = 128; bn = 64; break;    // halo conv (8x16-pixel tile), K-split waves + register double buffering
+    case 1: bm = 128; bn = 128; break;
+    case 2: bm = 128; bn = 64; break;
+    case 3: bm = 64; bn = 64; break;
+    default: bm = 64; bn = 128; break;
+  }
+}
+
 int conv_kind(const ConvDesc& d) {
   if (d.out_t) return 3;
   if (d.out_mode == kOutGeglu) return 2;
@@ -130,8 +142,8 @@ Plan choose_plan(const ConvDesc& d, const Dims& a) {
   // (round 2's first halo kernel) and 8 / 9 (256x128 / 256x256 GEMM tiles, measured in round 3 and selected nowhere) were removed
   // in round 4: a caller or table row that names them gets the heuristic.
   auto is_halo = [](int c) { return c == 7; };
-  // plan tile 9 = the weight-streaming kernel of wstream.hip (needs the pre-tiled weights; staging 4 = four waves per workgroup,
-  // anything else eight; its slab count follows from the wave count).  SD_WSTREAM=0 (with SD_TUNE) takes it out of every plan: A/B.
+  // plan tile 9 = the weight-streaming kernel of wstream.hip (needs the pre-tiled weights; its slab count follows from the wave
+  // count its code names).  SD_WSTREAM=0 (with SD_TUNE) takes it out of every plan: A/B.
   auto tile_ok = [&](int c) {
     if (c == 9) return switches().wstream && can_stream(d);
     if (!((c >= 1 && c <= 4) || c == 7)) return false;
@@ -237,16 +249,6 @@ bool gemm_pipe_ok(int ksize, int stride, int up, int M, int N, int K, int C0, in
   return ksize == 1 && stride == 1 && up == 1 && (size_t)M * std::max(C0, C1) * 2 < lim && (size_t)N * K * 2 < lim;
 }
 
-void tile_dims(int tile, int& bm, int& bn) {
-  switch (tile) {
-    case 7: bm = 128; bn = 64; break;    // halo conv (8x16-pixel tile), K-split waves + register double buffering
-    case 1: bm = 128; bn = 128; break;
-    case 2: bm = 128; bn = 64; break;
-    case 3: bm = 64; bn = 64; break;
-    default: bm = 64; bn = 128; break;
-  }
-}
-
 bool conv_fast_path_ok(const ConvDesc& d) {
   const int c1 = d.x1 ? d.C1 : 0;
   if (d.C0 % BK != 0 || c1 % BK != 0) return false;
@@ -257,20 +259,23 @@ bool conv_fast_path_ok(const ConvDesc& d) {
   return true;
 }
 
-ConvPlan conv_plan(const ConvDesc& d) {
+namespace {
+
+// the plan in the wire format: tile, code, resolved split-K, slab, workspace
+ConvPlan plan_codes(const ConvDesc& d) {
   if (!conv_fast_path_ok(d)) return ConvPlan{-1, 0, 1, false, 0};
   if (pal_stream(d)) {   // in front of the tuner candidate, the tables and every rule: nothing moves it
     SD_REQUIRE(d.pal_lut && can_split(d) && wstream_shape_ok(d), kInvalidArgument,
                "plan tile 14 (wstream.hip, palettized) needs the index stream, the LUT and a shape of the weight stream");
-    ConvPlan r{14, d.staging, 1, true, 0};   // staging as on tile 9: 4 = four waves per workgroup, anything else eight
-    r.splitk = wstream_splits(d, d.staging == 4 ? 4 : 8);
+    ConvPlan r{14, d.staging, 1, true, 0};   // the code of tile 9
+    r.splitk = wstream_splits(d, wstream_waves(d.staging));
     r.workspace_bytes = slab_bytes(dims_of(d), r.splitk, true);
     return r;
   }
-  if (pal_gemm(d)) {   // pinned like tile 14; staging 1 / 2 = 32- / 64-row tiles (0: by M, resolved here), no workspace
+  if (pal_gemm(d)) {   // pinned like tile 14; the code of tile 12 in, the resolved tile height out; no workspace
     SD_REQUIRE(d.pal_lut && palette_bits_ok(d.pal_bits) && !d.x1 && d.staging >= 0 && d.staging <= 2 && smgemm_shape_ok(d, d.staging), kInvalidArgument,
                "plan tile 15 (smgemm.hip, palettized) needs the index stream, the LUT and a single-source shape of the small-M GEMM");
-    return ConvPlan{15, smgemm_bm(d, d.staging) == 32 ? 1 : 2, 1, false, 0};
+    return ConvPlan{15, conv_plan_bm_code(smgemm_bm(d, d.staging)), 1, false, 0};
   }
   const Switches& sw = switches();
   // the library's own rules for tiles 10-13 apply where nothing else was asked for (a tuner candidate in force also keeps them off)
@@ -278,13 +283,13 @@ ConvPlan conv_plan(const ConvDesc& d) {
   // plan tile 10: the weight-stationary GEGLU kernel (wsgemm.hip) wherever its pre-tiled weights exist
   if (d.w_ws && wsgemm_shape_ok(d) && (d.tile == 10 || (sw.wsgemm && free_choice && wsgemm_wanted(d)))) return ConvPlan{10, 0, 1, false, 0};
   SD_REQUIRE(d.tile != 10, kInvalidArgument, "plan tile 10 (wsgemm.hip) needs the pre-tiled weights and an eligible GEGLU shape");
-  // plan tile 11: weights global -> VGPR (bvgemm.hip), on the library's rule or forced (staging 1 - 4 then force a variant)
+  // plan tile 11: weights global -> VGPR (bvgemm.hip), on the library's rule or forced (the code then forces a variant)
   if (sw.bvgemm && d.w_bv && free_choice && bvgemm_wanted(d)) return ConvPlan{11, 0, 1, false, 0};
   if (d.tile == 11) {
     SD_REQUIRE(d.w_bv && bvgemm_shape_ok(d), kInvalidArgument, "plan tile 11 (bvgemm.hip) needs the pre-tiled weights and an eligible 1x1 shape");
     return ConvPlan{11, d.staging, 1, false, 0};
   }
-  // plan tiles 12 (smgemm.hip) / 13 (smgeglu.hip): staging 1 / 2 of a forced plan force a tile height (the launchers check its shape)
+  // plan tiles 12 (smgemm.hip) / 13 (smgeglu.hip): the code of a forced plan forces a tile height (the launchers check its shape)
   if (d.tile == 12 || (sw.smgemm && free_choice && smgemm_wanted(d))) return ConvPlan{12, d.tile == 12 ? d.staging : 0, 1, false, 0};
   if (d.tile == 13 || (sw.smgeglu && free_choice && smgeglu_wanted(d))) return ConvPlan{13, d.tile == 13 ? d.staging : 0, 1, false, 0};
 
@@ -309,7 +314,7 @@ ConvPlan conv_plan(const ConvDesc& d) {
   }
   ConvPlan r{p.tile, p.staging, 1, true, 0};
   if (p.tile == 9) {   // weight-streaming kernel: one slab per nw input-channel slices, always through the combine
-    r.splitk = wstream_splits(d, p.staging == 4 ? 4 : 8);
+    r.splitk = wstream_splits(d, wstream_waves(p.staging));
   } else {             // no empty splits
     const int steps = p.tile == 7 ? a.Ctot / BK : a.nk_total;
     r.splitk = cdiv(steps, cdiv(steps, p.splitk));
@@ -317,6 +322,106 @@ ConvPlan conv_plan(const ConvDesc& d) {
   }
   r.workspace_bytes = slab_bytes(a, r.splitk, r.slab);
   return r;
+}
+
+// THE decode of the wire format: what (tile, staging) launch for this descriptor.  Every per-family meaning of `staging` is here.
+//   tiles 1-4: 0 = 2 stages, 1 = register staging, 2 / 3 / 4 / 5 = ring of 3 / 4 / 6 / 8 stages; 6 / 7 / 8 = gemm_pipe_kernel with 3 / 4 / 2
+//              stages where gemm_pipe_ok, else as 3; 12 / 13 = the 3- / 4-stage ring with in-workgroup split-K (two K groups) where the
+//              epilogue is the plain one, a split runs >= 4 K steps and two rings fit, else as 2 / 3.  A ring that does not fit the LDS
+//              runs as the deepest shallower one that does.  The LayerNorm fold has no register staging (1 as 0); the token-transposed
+//              output (kOutHalfT) has register staging and rings of 2 / 3 stages only.
+//   tile 7:    0 / 2 / 3 / 4 / 5 = 2 / 3 / 4 / 6 / 8 weight stages; GroupNorm in the loader: 4 stages from code 3 where its table fits, else 3
+//   tiles 9 / 14: 4 = four waves per workgroup, anything else eight      tile 11: 1-6 = the variant, anything else the library's choice
+//   tiles 12 / 15 / 13: 1 / 2 = the lower / higher tile (32 / 64, 128 / 256 rows), 0 = by the shape
+void decode_plan(const ConvDesc& d, ConvPlan& p) {
+  const Dims a = dims_of(d);
+  int code = p.staging;
+  switch (p.tile) {
+    case -1: p.kernel = ConvKernel::Generic; return;
+    case 9: case 14:
+      p.kernel = p.tile == 9 ? ConvKernel::Wstream : ConvKernel::WstreamPal;
+      p.waves = wstream_waves(code);
+      return;
+    case 10: p.kernel = ConvKernel::Wsgemm; return;
+    case 11:
+      p.kernel = ConvKernel::Bvgemm;
+      p.variant = code >= 1 && code <= 6 ? code : bvgemm_auto_variant(d);
+      return;
+    case 12: case 15:
+      p.kernel = p.tile == 12 ? ConvKernel::Smgemm : ConvKernel::SmgemmPal;
+      p.bm = code >= 0 && code <= 2 ? smgemm_bm(d, code) : 0;   // (0: no such tile - the launcher refuses it)
+      return;
+    case 13:
+      p.kernel = ConvKernel::Smgeglu;
+      p.bm = code >= 0 && code <= 2 ? smgeglu_bm(d, code) : 0;
+      return;
+    default: break;
+  }
+  tile_dims(p.tile, p.bm, p.bn);
+  if (p.tile == 7) {
+    p.kernel = ConvKernel::HaloKs;
+    if (d.gnf_partial) p.stages = code >= 3 && halo_gnl_lds_bytes(4, a.Ctot) <= kLdsBudget ? 4 : 3;
+    else p.stages = code >= 5 ? 8 : code == 4 ? 6 : code == 3 ? 4 : code == 2 ? 3 : 2;
+    return;
+  }
+  p.kernel = ConvKernel::Igemm;
+  p.stages = 2;
+  const bool lnf = d.ln_colsum != nullptr;
+  auto fits = [&](int nst, int kgroups = 1) { return ring_fits(p.bm, p.bn, nst, kgroups); };
+  if (lnf && code == 1) code = 0;
+  if (code == 1) {
+    p.reg_staged = true;
+    return;
+  }
+  if (!lnf && d.out_mode == kOutHalfT) {
+    if (code >= 2) p.stages = 3;
+    return;
+  }
+  if (code == 12 || code == 13) {
+    const bool two_groups = !lnf && cdiv(a.nk_total, p.splitk) >= 4;
+    if (two_groups && code == 13 && fits(4, 2)) p.stages = 4, p.kgroups = 2;
+    else if (two_groups && fits(3, 2)) p.stages = 3, p.kgroups = 2;
+    if (p.kgroups == 2) return;
+    code -= 10;
+  }
+  // (a GroupNorm-folded 1x1 arrives here as tile 3 with code 6 / 7 / 8 and gemm_pipe_ok checked: gemm_pipe_kernel's GNF instantiation)
+  if (code >= 6 && code <= 8 && gemm_pipe_ok(d.ksize, d.stride, d.up, a.M, a.N, a.K, d.C0, d.x1 ? d.C1 : 0)) {
+    p.kernel = ConvKernel::GemmPipe;
+    p.stages = code == 8 ? 2 : (code == 7 && fits(4)) ? 4 : 3;
+    return;
+  }
+  if (code >= 6) code = 3;
+  const int asked = code >= 5 ? 8 : code == 4 ? 6 : code == 3 ? 4 : code == 2 ? 3 : 2;
+  for (int nst : {8, 6, 4, 3, 2})
+    if (nst <= asked && fits(nst)) {
+      p.stages = nst;
+      return;
+    }
+}
+
+}  // namespace
+
+ConvPlan conv_plan(const ConvDesc& d) {
+  ConvPlan p = plan_codes(d);
+  decode_plan(d, p);
+  return p;
+}
+
+std::string conv_plan_kernel_name(const ConvPlan& p) {
+  const std::string tile = std::to_string(p.bm) + "x" + std::to_string(p.bn), ring = " ring" + std::to_string(p.stages);
+  switch (p.kernel) {
+    case ConvKernel::Igemm: return "igemm " + tile + ring + (p.kgroups == 2 ? " kg2" : "") + (p.reg_staged ? " regs" : "");
+    case ConvKernel::GemmPipe: return "gemm_pipe " + tile + ring;
+    case ConvKernel::HaloKs: return "halo_ks" + ring;
+    case ConvKernel::Wstream: return "wstream waves" + std::to_string(p.waves);
+    case ConvKernel::WstreamPal: return "wstream_pal waves" + std::to_string(p.waves);
+    case ConvKernel::Wsgemm: return "wsgemm";
+    case ConvKernel::Bvgemm: return "bvgemm v" + std::to_string(p.variant);
+    case ConvKernel::Smgemm: return "smgemm bm" + std::to_string(p.bm);
+    case ConvKernel::SmgemmPal: return "smgemm_pal bm" + std::to_string(p.bm);
+    case ConvKernel::Smgeglu: return "smgeglu bm" + std::to_string(p.bm);
+    default: return "generic";
+  }
 }
 
 // Workspace a handle reserves for this conv at build time.  The descriptor may still change before it is launched - the GroupNorm
@@ -364,7 +469,7 @@ int conv_plan_pal_waves(const ConvDesc& d0) {
   d.w_ws = d.w_bv = nullptr;
   d.w_pal = nullptr;
   const ConvPlan p = conv_plan(d);
-  return p.tile == 9 ? (p.staging == 4 ? 4 : 8) : 0;
+  return p.kernel == ConvKernel::Wstream ? p.waves : 0;
 }
 
 // The same question for plan tile 15: would this conv, uploaded as fp16 with the copies a handle would hold, get plan tile 12 by the
@@ -382,7 +487,7 @@ int conv_plan_pal_gemm(const ConvDesc& d0) {
   if (c.wsgemm) d.w_ws = &present;
   if (c.bvgemm) d.w_bv = &present;
   const ConvPlan p = conv_plan(d);
-  return p.tile == 12 ? smgemm_bm(d, p.staging) : 0;
+  return p.kernel == ConvKernel::Smgemm ? p.bm : 0;
 }
 
 // Does the compiled-in plan table hold a row for this shape - a plan that was measured in a step?
@@ -418,20 +523,20 @@ void conv_tune_set_candidate(int tile, int staging, int splitk) {
   g_tune.splitk = splitk;
 }
 
-void conv_plan_log(const ConvDesc& d, const ConvPlan& p, int bm, int n_fast) {
+void conv_plan_log(const ConvDesc& d, const ConvPlan& p, int n_fast) {
   static const bool on = tune_env_set("SD_LOG_CONVS");
   if (!on) return;
   const Dims a = dims_of(d);
   const int c1 = d.x1 ? d.C1 : 0;
   if (p.tile == 9 || p.tile == 14)
     fprintf(stderr, "[sd conv] k%d up%d C0=%d C1=%d M=%d N=%d K=%d tile=%d nw=%d slabs=%d twins=%d bits=%d\n", d.ksize, d.up, d.C0, c1, a.M, a.N,
-            a.K, p.tile, p.staging == 4 ? 4 : 8, p.splitk, d.n_twins, p.tile == 14 ? d.pal_bits : 16);
+            a.K, p.tile, p.waves, p.splitk, d.n_twins, p.tile == 14 ? d.pal_bits : 16);
   else if (p.tile == 12 || p.tile == 13)
-    fprintf(stderr, "[sd conv] k1 s1 up1 C0=%d C1=%d M=%d N=%d K=%d mode=%d tile=%d bm=%d n_fast=%d\n", d.C0, c1, a.M, a.N, a.K, d.out_mode, p.tile, bm,
+    fprintf(stderr, "[sd conv] k1 s1 up1 C0=%d C1=%d M=%d N=%d K=%d mode=%d tile=%d bm=%d n_fast=%d\n", d.C0, c1, a.M, a.N, a.K, d.out_mode, p.tile, p.bm,
             n_fast);
   else if (p.tile == 15)
     fprintf(stderr, "[sd conv] k1 s1 up1 C0=%d C1=%d M=%d N=%d K=%d mode=%d tile=%d bm=%d n_fast=%d bits=%d\n", d.C0, c1, a.M, a.N, a.K, d.out_mode,
-            p.tile, bm, n_fast, d.pal_bits);
+            p.tile, p.bm, n_fast, d.pal_bits);
   else
     fprintf(stderr, "[sd conv] k%d s%d up%d C0=%d C1=%d M=%d N=%d K=%d mode=%d tile=%d splitk=%d\n", d.ksize, d.stride, d.up, d.C0, c1, a.M, a.N,
             a.K, d.out_mode, p.tile, p.splitk);

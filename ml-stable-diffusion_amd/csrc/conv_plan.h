@@ -2,19 +2,33 @@
 // workspace, and which pre-tiled weight copies its handle must hold.  Host code only (conv_plan.cpp makes no HIP call), so the
 // CPU suite pins it row by row (tests/test_conv_plan.py through sd_op_conv_plan).
 #pragma once
+#include <string>
+
 #include "kernels.h"
 
 namespace sd {
 
+// the kernel a plan launches (tile -1 / 1-4 / 7 / 9 / 14 / 10 / 11 / 12 / 15 / 13 of the wire format below)
+enum class ConvKernel { Generic, Igemm, GemmPipe, HaloKs, Wstream, WstreamPal, Wsgemm, Bvgemm, Smgemm, SmgemmPal, Smgeglu };
+
 struct ConvPlan {
+  // The wire format: what ConvDesc::tile / staging pins, tuned_convs.inc rows, SD_PLAN_TABLE and sd_tune_set_candidate say and what
+  // sd_op_conv_plan, plan_out and SD_LOG_CONVS report.  Read by decode_plan (conv_plan.cpp) and by nothing else.
   int tile;        // 1: 128x128, 2: 128x64, 3: 64x64, 4: 64x128 (igemm.hip), 7: the K-split halo conv (conv3x3_halo.hip), 9: wstream.hip,
                    // 10: wsgemm.hip, 11: bvgemm.hip, 12: smgemm.hip, 13: smgeglu.hip, 14: wstream.hip from palettized weights,
                    // 15: smgemm.hip from palettized weights; -1 = not on the MFMA path (launch_conv_generic)
-  int staging;     // ring code (tiles 1-4, 7: launch_tile / launch_halo_ks), wave-count code (9, 14: 4 = four waves, else eight), variant (11, 12, 13),
-                   // tile height (15: 1 / 2 = 32 / 64 rows)
+  int staging;     // per-family code: decode_plan
   int splitk;      // resolved: what the launch runs, no empty splits (halo: over 64-channel chunks; tile 9: the slab count)
   bool slab;       // the output leaves through fp32 slabs (split-K, weight stream, GroupNorm twins)
   size_t workspace_bytes;   // exactly what this launch needs of ConvWorkspace::partial
+  // What the codes mean for this descriptor, resolved once by conv_plan(): all a launcher reads.
+  ConvKernel kernel = ConvKernel::Generic;
+  int bm = 0, bn = 0;        // Igemm / GemmPipe / HaloKs (128 x 64, as its tile counts): tile rows x columns; Smgemm* / Smgeglu: bm, tile rows
+  int stages = 0;            // Igemm / GemmPipe / HaloKs: the ring depth that runs, after the fall-back to one that fits the LDS
+  int kgroups = 1;           // Igemm: 2 = in-workgroup split-K, two K groups of four waves with a ring each
+  bool reg_staged = false;   // Igemm: A / B travel HBM -> VGPR -> LDS (the A/B reference form), two stages
+  int waves = 0;             // Wstream*: waves (K slices) per workgroup, 4 or 8
+  int variant = 0;           // Bvgemm: 1-6 (bvgemm.hip), the library's choice already made
 };
 // Pure function of the descriptor, the tuner candidate, the run-time table and the environment switches.  Raises the checks
 // that belong to the plan (a forced tile the shape does not admit, the GroupNorm-loader / GroupNorm-fold shapes).
@@ -35,8 +49,19 @@ int conv_plan_pal_waves(const ConvDesc& d);
 // 0 = no (SD_SMGEMM=0, two sources, a LayerNorm fold, any other plan): upload the de-palettized tensor.
 int conv_plan_pal_gemm(const ConvDesc& d);
 
-// the SD_LOG_CONVS line of a launch (bm / n_fast: what smgemm.hip / smgeglu.hip add to theirs)
-void conv_plan_log(const ConvDesc& d, const ConvPlan& p, int bm = 0, int n_fast = 0);
+// the SD_LOG_CONVS line of a launch (n_fast: what smgemm.hip / smgeglu.hip add to theirs)
+void conv_plan_log(const ConvDesc& d, const ConvPlan& p, int n_fast = 0);
+
+// The pins of a descriptor that runs from a palette (ConvDesc::staging of plan tiles 14 / 15), written as codes: the inverse of
+// decode_plan for what conv_plan_pal_waves / conv_plan_pal_gemm answered.
+inline int conv_plan_waves_code(int waves) { return waves == 4 ? 4 : 0; }
+inline int conv_plan_bm_code(int bm) { return bm == 32 ? 1 : 2; }
+
+// What launches, as one line (sd_op_conv_plan_kernel): the kernel's name, then only the fields that kernel has -
+//   "igemm <bm>x<bn> ring<stages>[ kg2][ regs]"    "gemm_pipe <bm>x<bn> ring<stages>"    "halo_ks ring<stages>"
+//   "wstream waves<n>"   "wstream_pal waves<n>"    "wsgemm"    "bvgemm v<variant>"
+//   "smgemm bm<bm>"      "smgemm_pal bm<bm>"       "smgeglu bm<bm>"                      "generic"
+std::string conv_plan_kernel_name(const ConvPlan& p);
 
 // Tile order inside an XCD's run of workgroup ids, from an estimate of the bytes each order pulls through the fabric into the 8 XCD L2s:
 //   m fastest: every weight panel once; the activations once per XCD when they fit an L2, else once per n-tile
@@ -52,6 +77,22 @@ bool conv_reduce_stats_on();   // SD_REDUCE_STATS: the slab combine also leaves 
 constexpr int kConvBK = 64;   // K step (halves) of the MFMA kernels
 bool halo_ks_ok(const ConvDesc& d);
 bool gemm_pipe_ok(int ksize, int stride, int up, int M, int N, int K, int C0, int C1);
-void tile_dims(int tile, int& bm, int& bn);
+
+// LDS budgets, stated once: decode_plan picks the ring that runs by them, the launchers assert them per instantiation.
+constexpr size_t kLdsBudget = 160 * 1024;
+// igemm_kernel / gemm_pipe_kernel: kgroups rings of nst stages of a bm x bn tile's A and B rows, then [2][bn] floats of epilogue constants
+constexpr size_t ring_bytes(int bm, int bn, int nst) { return (size_t)nst * (bm + bn) * kConvBK * sizeof(half_t); }
+constexpr bool ring_fits(int bm, int bn, int nst, int kgroups = 1) { return kgroups * ring_bytes(bm, bn, nst) + 2 * bn * sizeof(float) <= kLdsBudget; }
+// conv3x3_halo_ks_kernel: two halo buffers, d stages of bn weight rows, [bn] floats of epilogue constants
+constexpr int kHaloLdsRows = 184;
+constexpr size_t halo_lds_bytes(int bn, int d) {
+  return ((size_t)2 * kHaloLdsRows * kConvBK + (size_t)d * bn * kConvBK) * sizeof(half_t) + bn * sizeof(float);
+}
+// the same with GroupNorm in the loader: the [3][ctot] fp16 GroupNorm table takes the place of the epilogue constants behind the ring
+constexpr size_t halo_gnl_lds_bytes(int d, int ctot) {
+  const size_t k_loop = halo_lds_bytes(64, d) - 64 * sizeof(float) + (((size_t)6 * ctot + 15) & ~(size_t)15);
+  const size_t epilogue = 32 * 1024 + 128 * (64 + 8) * 2 + 64 * sizeof(float);
+  return k_loop > epilogue ? k_loop : epilogue;
+}
 
 }  // namespace sd

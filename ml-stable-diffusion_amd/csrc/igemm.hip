@@ -960,7 +960,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_stats_kernel(IgemmArgs a, i
 template <int BM, int BN, int WGM, int WGN, bool TRANS, bool GLDS, int NST, bool LNF = false, int KG = 1>
 void launch_variant(const IgemmArgs& a, hipStream_t s) {
   const size_t lds = (size_t)KG * NST * (BM + BN) * (GLDS ? BK : LDS_ROW) * sizeof(half_t) + 2 * BN * sizeof(float);
-  static_assert((size_t)KG * NST * (BM + BN) * BK * sizeof(half_t) + 2 * BN * sizeof(float) <= 160 * 1024, "LDS");
+  static_assert(ring_fits(BM, BN, NST, KG), "LDS");
   static_assert((size_t)BN * (BM + 8) <= (size_t)NST * (BM + BN) * (GLDS ? BK : LDS_ROW), "transposed staging fits");
   static_assert((size_t)BM * (BN + 8) * 2 + 16 + (kGnScratchFloats + 2 * BN) * sizeof(float) <=
                     (size_t)NST * (BM + BN) * (GLDS ? BK : LDS_ROW) * sizeof(half_t),
@@ -993,19 +993,7 @@ bool launch_debug_mode(const IgemmArgs& a, int dbg, hipStream_t s) {
   }
 }
 
-// staging: 0 = LDS-DMA 2 stages, 1 = register staging (A/B reference), 2 / 3 / 4 / 5 = LDS-DMA ring of
-// 3 / 4 / 6 / 8 stages (a ring that would not fit the 160 KB of LDS falls back to the deepest one that does),
-constexpr size_t kLdsBudget = 160 * 1024;
-template <int BM, int BN>
-constexpr size_t ring_bytes(int nst) {
-  return (size_t)nst * (BM + BN) * BK * sizeof(half_t);
-}
-template <int BM, int BN>
-constexpr bool ring_fits(int nst) {
-  return (size_t)nst * (BM + BN) * BK * sizeof(half_t) + 2 * BN * sizeof(float) <= kLdsBudget;
-}
-// staging 6 / 7 / 8: the software-pipelined 1x1 GEMM kernel with a ring of 3 / 4 / 2 stages (1x1, stride 1, non-transposed
-// output; 32-bit buffer offsets); anything else that asks for them runs the 4-stage ring of igemm_kernel
+// the software-pipelined 1x1 GEMM kernel with a ring of D stages (1x1, stride 1, non-transposed output; 32-bit buffer offsets)
 template <int BM, int BN, int WGM, int WGN, int D, bool LNF>
 void launch_pipe_dbg(const IgemmArgs& a, hipStream_t s) {   // ablation builds (a.debug = 64 + bits)
   constexpr size_t lds = (size_t)D * (BM + BN) * BK * sizeof(half_t) + 2 * BN * sizeof(float);
@@ -1024,7 +1012,7 @@ void launch_pipe_dbg(const IgemmArgs& a, hipStream_t s) {   // ablation builds (
 template <int BM, int BN, int WGM, int WGN, int D, bool LNF>
 void launch_pipe(const IgemmArgs& a, hipStream_t s) {
   constexpr size_t lds = (size_t)D * (BM + BN) * BK * sizeof(half_t) + 2 * BN * sizeof(float);
-  static_assert(lds <= kLdsBudget, "LDS");
+  static_assert(ring_fits(BM, BN, D), "LDS");
   static_assert((size_t)BM * (BN + 8) * 2 + 16 + (kGnScratchFloats + 2 * BN) * sizeof(float) <= (size_t)D * (BM + BN) * BK * sizeof(half_t),
                 "staged tile + GroupNorm statistics scratch fit the K-loop buffers");
   static_assert((size_t)BN * (BM + 8) <= (size_t)D * (BM + BN) * BK, "transposed staging fits");
@@ -1050,60 +1038,45 @@ void launch_pipe(const IgemmArgs& a, hipStream_t s) {
   once.set(k, lds);
   hipLaunchKernelGGL(k, grid, dim3(256), lds, s, a);
 }
-template <int BM, int BN, int WGM, int WGN, bool LNF>
-void launch_ring(const IgemmArgs& a, int staging, hipStream_t s) {
-  // staging 12 / 13: igemm_kernel's 3- / 4-stage ring with the in-workgroup split-K (two K groups of four waves, KG = 2) where two
-  // rings fit the LDS and the epilogue is the plain one; anything else that names them gets the same ring without it
-  if (staging == 12 || staging == 13) {
-    if constexpr (!LNF) {
-      if (a.nk_per_split >= 4) {
-        if (staging == 13) {
-          if constexpr (2 * ring_bytes<BM, BN>(4) + 2 * BN * sizeof(float) <= kLdsBudget) { launch_variant<BM, BN, WGM, WGN, false, true, 4, false, 2>(a, s); return; }
-        }
-        if constexpr (2 * ring_bytes<BM, BN>(3) + 2 * BN * sizeof(float) <= kLdsBudget) { launch_variant<BM, BN, WGM, WGN, false, true, 3, false, 2>(a, s); return; }
-      }
+// The instantiation the plan names (decode_plan resolved kernel, ring depth and K groups against the same ring_fits as the guards
+// here): igemm_kernel's LDS-DMA ring of 2 / 3 / 4 / 6 / 8 stages, the same with two K groups of four waves (3 / 4 stages, plain
+// epilogue), or gemm_pipe_kernel's ring of 2 / 3 / 4 stages.  false: no such kernel.
+template <int BM, int BN, bool LNF, int NST>
+bool launch_ring_depth(const IgemmArgs& a, const ConvPlan& p, hipStream_t s) {
+  if constexpr (ring_fits(BM, BN, NST)) {
+    if (p.kernel == ConvKernel::GemmPipe) {
+      if constexpr (NST <= 4) { launch_pipe<BM, BN, 2, 2, NST, LNF>(a, s); return true; }
+    } else if (p.kgroups == 2) {
+      if constexpr (!LNF && (NST == 3 || NST == 4) && ring_fits(BM, BN, NST, 2)) { launch_variant<BM, BN, 2, 2, false, true, NST, false, 2>(a, s); return true; }
+    } else {
+      launch_variant<BM, BN, 2, 2, false, true, NST, LNF>(a, s);
+      return true;
     }
-    staging -= 10;
   }
-  if (staging == 8 && gemm_pipe_ok(a)) {   // 2-stage ring, two workgroups per CU (three on 128 x 64): profiles/r03_exp_pipe_d2.txt
-    launch_pipe<BM, BN, WGM, WGN, 2, LNF>(a, s);
-    return;
+  return false;
+}
+template <int BM, int BN, bool LNF>
+bool launch_ring(const IgemmArgs& a, const ConvPlan& p, hipStream_t s) {
+  switch (p.stages) {
+    case 2: return launch_ring_depth<BM, BN, LNF, 2>(a, p, s);
+    case 3: return launch_ring_depth<BM, BN, LNF, 3>(a, p, s);
+    case 4: return launch_ring_depth<BM, BN, LNF, 4>(a, p, s);
+    case 6: return launch_ring_depth<BM, BN, LNF, 6>(a, p, s);
+    case 8: return launch_ring_depth<BM, BN, LNF, 8>(a, p, s);
+    default: return false;
   }
-  if ((staging == 6 || staging == 7) && gemm_pipe_ok(a)) {
-    if (staging == 7) {
-      if constexpr (ring_fits<BM, BN>(4)) { launch_pipe<BM, BN, WGM, WGN, 4, LNF>(a, s); return; }
-    }
-    launch_pipe<BM, BN, WGM, WGN, 3, LNF>(a, s);
-    return;
-  }
-  if (staging >= 6) staging = 3;
-  if (staging >= 5) {
-    if constexpr (ring_fits<BM, BN>(8)) { launch_variant<BM, BN, WGM, WGN, false, true, 8, LNF>(a, s); return; }
-  }
-  if (staging >= 4) {
-    if constexpr (ring_fits<BM, BN>(6)) { launch_variant<BM, BN, WGM, WGN, false, true, 6, LNF>(a, s); return; }
-  }
-  if (staging >= 3) {
-    if constexpr (ring_fits<BM, BN>(4)) { launch_variant<BM, BN, WGM, WGN, false, true, 4, LNF>(a, s); return; }
-  }
-  if (staging >= 2) { launch_variant<BM, BN, WGM, WGN, false, true, 3, LNF>(a, s); return; }
-  launch_variant<BM, BN, WGM, WGN, false, true, 2, LNF>(a, s);
 }
 
-template <int BM, int BN, int WGM, int WGN>
-void launch_tile(const IgemmArgs& a, bool trans, int staging, hipStream_t s) {
-  if (a.ln_colsum) {   // LayerNorm-folded 1x1 GEMM
-    launch_ring<BM, BN, WGM, WGN, true>(a, staging == 1 ? 0 : staging, s);
-    return;
-  }
-  if (trans) {
-    if (staging == 1) launch_variant<BM, BN, WGM, WGN, true, false, 2>(a, s);
-    else if (staging >= 2) launch_variant<BM, BN, WGM, WGN, true, true, 3>(a, s);
-    else launch_variant<BM, BN, WGM, WGN, true, true, 2>(a, s);
-  } else {
-    if (staging == 1) launch_variant<BM, BN, WGM, WGN, false, false, 2>(a, s);
-    else launch_ring<BM, BN, WGM, WGN, false>(a, staging, s);
-  }
+template <int BM, int BN>
+void launch_tile(const IgemmArgs& a, const ConvPlan& p, bool trans, hipStream_t s) {
+  bool ok = true;
+  if (a.ln_colsum) ok = !p.reg_staged && launch_ring<BM, BN, true>(a, p, s);   // LayerNorm-folded 1x1 GEMM
+  else if (trans && p.reg_staged) launch_variant<BM, BN, 2, 2, true, false, 2>(a, s);
+  else if (trans && p.stages == 3) launch_variant<BM, BN, 2, 2, true, true, 3>(a, s);
+  else if (trans) launch_variant<BM, BN, 2, 2, true, true, 2>(a, s);
+  else if (p.reg_staged) launch_variant<BM, BN, 2, 2, false, false, 2>(a, s);
+  else ok = launch_ring<BM, BN, false>(a, p, s);
+  SD_REQUIRE(ok, kInternal, "no %dx%d kernel for plan '%s'", BM, BN, conv_plan_kernel_name(p).c_str());
 }
 
 // slab combine of a split-K / weight-streaming launch: plain, or - when the consumer is a GroupNorm over <= 256 pixels per sample -
@@ -1160,12 +1133,12 @@ int launch_conv(const ConvDesc& d, const ConvWorkspace& ws, hipStream_t s) {
   SD_REQUIRE(!d.vt_perm || (d.out_t && (d.Ho * d.Wo) % 16 == 0), kInvalidArgument, "permuted V^T needs the fused q|k|v epilogue and HoWo %% 16 == 0");
   SD_REQUIRE(d.q_cols == 0 || (d.out_t && d.q_cols % 4 == 0 && d.q_cols <= d.n_trans), kInvalidArgument, "pre-scaled queries need the fused q|k|v epilogue (q_cols %d)", d.q_cols);
   const ConvPlan p = conv_plan(d);
-  switch (p.tile) {   // the kernels with their own argument blocks
-    case 10: launch_wsgemm(d, s); return 0;
-    case 11: launch_bvgemm(d, p.staging, s); return 0;
-    case 12: launch_smgemm(d, p.staging, s); return 0;
-    case 13: launch_smgeglu(d, p.staging, s); return 0;
-    case 15: launch_smgemm_pal(d, p.staging, s); return 0;   // (d.gn_partial set: no statistics, 0 entries - the GroupNorm runs its own pass)
+  switch (p.kernel) {   // the kernels with their own argument blocks
+    case ConvKernel::Wsgemm: launch_wsgemm(d, s); return 0;
+    case ConvKernel::Bvgemm: launch_bvgemm(d, p, s); return 0;
+    case ConvKernel::Smgemm: launch_smgemm(d, p, s); return 0;
+    case ConvKernel::Smgeglu: launch_smgeglu(d, p, s); return 0;
+    case ConvKernel::SmgemmPal: launch_smgemm_pal(d, p, s); return 0;   // (d.gn_partial set: no statistics, 0 entries - the GroupNorm runs its own pass)
     default: break;
   }
   IgemmArgs a = planned_args(d, p, ws.partial);
@@ -1173,36 +1146,35 @@ int launch_conv(const ConvDesc& d, const ConvWorkspace& ws, hipStream_t s) {
   SD_REQUIRE(!twins || (d.out_mode == kOutHalf && !d.ln_colsum && !d.out_t && !d.debug && reduce_twin_ok(a.HoWo, a.N, d.n_twins, d.twin)),
              kInvalidArgument, "GroupNorm twins need a plain fp16 output and whole (sample, group) slices (HoWo=%d N=%d)", a.HoWo, a.N);
   const bool have_ws = !p.slab || (ws.partial && ws.partial_bytes >= p.workspace_bytes);
-  if (p.tile == 9 || p.tile == 14) SD_REQUIRE(have_ws, kInternal, "wstream workspace too small (%zu < %zu)", ws.partial_bytes, p.workspace_bytes);
+  if (p.kernel == ConvKernel::Wstream || p.kernel == ConvKernel::WstreamPal) SD_REQUIRE(have_ws, kInternal, "wstream workspace too small (%zu < %zu)", ws.partial_bytes, p.workspace_bytes);
   SD_REQUIRE(have_ws, kInternal, "split-K workspace too small (%zu < %zu)", ws.partial_bytes, p.workspace_bytes);
   conv_plan_log(d, p);
   int gn_entries = 0;
-  if (p.tile == 9) {
-    // weight-streaming kernel: slabs, then the group-organised combine (with the consumer's GroupNorm twins) or the plain one
-    launch_wstream(d, ws.partial, p.staging == 4 ? 4 : 8, s);
-  } else if (p.tile == 14) {   // the same slabs from palettized weights, then the same combine
-    launch_wstream_pal(d, ws.partial, p.staging == 4 ? 4 : 8, s);
-  } else if (p.tile == 7) {
-    gn_entries = launch_halo_ks(d, p, ws.partial, s);
-  } else {
-    const bool trans = d.out_mode == kOutHalfT;
-    set_tile_order(a, p.tile);
-    if (d.debug && d.debug < 64) {   // ablation builds exist for two tiles only (tools/prof_conv.py)
-      const bool ok = p.tile == 1 ? launch_debug_mode<128, 128>(a, d.debug, s) : launch_debug_mode<64, 64>(a, d.debug, s);
-      SD_REQUIRE(ok && !trans, kInvalidArgument, "no ablation kernel for debug mode %d", d.debug);
-      return 0;
+  switch (p.kernel) {
+    case ConvKernel::Wstream:      // weight-streaming kernel: slabs, then the group-organised combine (with the consumer's GroupNorm twins) or the plain one
+      launch_wstream(d, ws.partial, p.waves, s);
+      break;
+    case ConvKernel::WstreamPal:   // the same slabs from palettized weights, then the same combine
+      launch_wstream_pal(d, ws.partial, p.waves, s);
+      break;
+    case ConvKernel::HaloKs: gn_entries = launch_halo_ks(d, p, ws.partial, s); break;
+    case ConvKernel::Igemm:
+    case ConvKernel::GemmPipe: {
+      const bool trans = d.out_mode == kOutHalfT;
+      set_tile_order(a, p.bm, p.bn);
+      if (d.debug && d.debug < 64) {   // ablation builds exist for two tiles only (tools/prof_conv.py)
+        const bool ok = p.bm == 128 && p.bn == 128 ? launch_debug_mode<128, 128>(a, d.debug, s) : launch_debug_mode<64, 64>(a, d.debug, s);
+        SD_REQUIRE(ok && !trans, kInvalidArgument, "no ablation kernel for debug mode %d", d.debug);
+        return 0;
+      }
+      if (!trans) gn_entries = setup_gn_stats(d, a, p.bm);
+      if (p.bm == 128 && p.bn == 128) launch_tile<128, 128>(a, p, trans, s);
+      else if (p.bm == 128) launch_tile<128, 64>(a, p, trans, s);
+      else if (p.bn == 64) launch_tile<64, 64>(a, p, trans, s);
+      else launch_tile<64, 128>(a, p, trans, s);
+      break;
     }
-    if (!trans) {
-      int bm, bn;
-      tile_dims(p.tile >= 1 && p.tile <= 3 ? p.tile : 4, bm, bn);
-      gn_entries = setup_gn_stats(d, a, bm);
-    }
-    switch (p.tile) {
-      case 1: launch_tile<128, 128, 2, 2>(a, trans, p.staging, s); break;
-      case 2: launch_tile<128, 64, 2, 2>(a, trans, p.staging, s); break;
-      case 3: launch_tile<64, 64, 2, 2>(a, trans, p.staging, s); break;
-      default: launch_tile<64, 128, 2, 2>(a, trans, p.staging, s); break;
-    }
+    default: SD_REQUIRE(false, kInternal, "launch_conv: plan '%s' has no launcher here", conv_plan_kernel_name(p).c_str());
   }
   if (twins) {
     launch_reduce_twin(a.partial, a.splitk, a.M, a.N, a.HoWo, a.bias, a.temb, a.temb_stride, a.res, a.out, d.n_twins, d.twin, s);
@@ -1229,7 +1201,7 @@ IgemmArgs side_args(const ConvDesc& d) {
   IgemmArgs a = make_args(d);
   a.splitk = 1;
   a.slab = 0;
-  set_tile_order(a, 3);
+  set_tile_order(a, 64, 64);
   return a;
 }
 constexpr size_t kSideLds = (size_t)kSideD * (64 + 64) * BK * sizeof(half_t) + 2 * 64 * sizeof(float);

@@ -451,12 +451,10 @@ IgemmArgs make_args(const ConvDesc& d) {
   return a;
 }
 
-// tile order (IgemmArgs::n_fast) from the operand sizes: choose_tile_order (conv_plan.h)
-void set_tile_order(IgemmArgs& a, int tile) {
-  int bm, bn;
-  tile_dims(tile, bm, bn);
+// tile order (IgemmArgs::n_fast) from the operand sizes: choose_tile_order (conv_plan.h).  halo: m-tiles are the 8x16-pixel tiles
+void set_tile_order(IgemmArgs& a, int bm, int bn, bool halo = false) {
   const double nbn = (double)cdiv(a.N, bn);
-  const double nbm = tile == 7 ? (double)a.B * a.tiles_x * a.tiles_y : (double)cdiv(a.M, bm);
+  const double nbm = halo ? (double)a.B * a.tiles_x * a.tiles_y : (double)cdiv(a.M, bm);
   a.n_fast = choose_tile_order(2.0 * a.B * a.Hi * a.Wi * a.Ctot, 2.0 * a.N * a.K, nbm, nbn, true);
 }
 
@@ -468,11 +466,10 @@ IgemmArgs planned_args(const ConvDesc& d, const ConvPlan& p, float* partial) {
   a.slab = p.slab ? 1 : 0;
   a.partial = p.slab ? partial : nullptr;
   // (the weight stream has its own arguments: these then only feed the slab combine; the halo kernel splits whole 64-channel chunks)
-  if (p.tile != 9 && p.tile != 14) a.nk_per_split = cdiv(p.tile == 7 ? a.Ctot / BK : a.nk_total, p.splitk);
+  if (p.kernel != ConvKernel::Wstream && p.kernel != ConvKernel::WstreamPal)
+    a.nk_per_split = cdiv(p.kernel == ConvKernel::HaloKs ? a.Ctot / BK : a.nk_total, p.splitk);
   return a;
 }
-
-bool gemm_pipe_ok(const IgemmArgs& a) { return ::sd::gemm_pipe_ok(a.ksize, a.stride, a.up, a.M, a.N, a.K, a.C0, a.C1); }
 
 // GroupNorm statistics from the epilogue: fills a.gn_* and returns the entries per (sample, group) the launch will write,
 // or 0 when this launch cannot produce them (bm: rows per m-tile of an igemm tile, 0 for the 8x16-pixel halo tiles)

@@ -47,11 +47,11 @@ struct ConvDesc {
   int out_mode = kOutHalf;
   int ldT = 0;                  // kOutHalfT: padded token stride
   // tuning overrides (0 = heuristic)
-  int tile = 0;                 // 1: 128x128  2: 128x64  3: 64x64 4: 64x128
+  int tile = 0;                 // plan tile pinned by the caller (ConvPlan::tile, conv_plan.h)
   int splitk = 0;
   long long* prof = nullptr;    // debug bit 2: device buffer of 8 timestamps
   int debug = 0;                // ablation hooks for tools/microbench (results are garbage when != 0)
-  int staging = 0;              // 0: LDS-DMA 2-stage, 1: HBM->VGPR->LDS (A/B reference), 2: LDS-DMA 3-stage ring
+  int staging = 0;              // the code that goes with the tile: its meaning per kernel family is decode_plan's (conv_plan.cpp)
   // LayerNorm folded into this 1x1 GEMM (x is the UN-normalised input): w = W*gamma, bias = b + W.beta,
   // ln_colsum[n] = sum_k w[n][k]; the kernel derives mean / rstd of each row from its own A tiles
   const float* ln_colsum = nullptr;
@@ -94,7 +94,7 @@ struct ConvDesc {
   const half_t* pal_lut = nullptr;
   int pal_bits = 0;
   // pal_gemm: w_pal is the bit stream of weight_prep.h smgemm_pal_pack instead and the descriptor is pinned to plan tile 15
-  // (smgemm.hip smgemm_pal_kernel; staging 1 / 2 = 32- / 64-row tiles, 0 = by M as tile 12)
+  // (smgemm.hip smgemm_pal_kernel; staging = conv_plan_bm_code of the tile height, 0 = by M as tile 12)
   bool pal_gemm = false;
   // weights in the fragment-major layout of wsgemm.hip (launch_wsgemm_retile), or null: the weight-stationary GEGLU kernel
   // (plan tile 10) needs them; launch_conv takes that kernel whenever they are there and no other plan was forced
@@ -122,9 +122,10 @@ size_t conv_workspace_bytes(const ConvDesc& d);
 const half_t* device_zero_chunk();
 // returns the number of GroupNorm partial entries per (sample, group) written to d.gn_partial (0: none)
 int launch_conv(const ConvDesc& d, const ConvWorkspace& ws, hipStream_t s);
+struct ConvPlan;   // conv_plan.h: what launch_conv resolved; the launchers of the kernel files below read their fields of it
 bool conv_fast_path_ok(const ConvDesc& d);
 bool conv_gn_loader_ok(const ConvDesc& d);   // gnf_* on a 3x3 conv (gnf_groups set): the halo kernel can normalise this input in its loader
-// tuning hook: plan (tile 1-6, staging 0-5, splitk) forced on every conv that admits it; tile 0 = off
+// tuning hook: plan (tile, staging, splitk in the codes of ConvPlan) forced on every conv that admits it; tile 0 = off
 void conv_tune_set_candidate(int tile, int staging, int splitk);
 bool conv_plan_is_tuned(const ConvDesc& d);   // tuned_convs.inc has a row for this shape
 int conv_plan_table_set(const char* text);   // rows of tuned_convs.inc format; returns the number of plans read
@@ -134,7 +135,7 @@ bool wstream_shape_ok(const ConvDesc& d);                 // shape admits plan t
 int wstream_splits(const ConvDesc& d, int nw);            // slabs launch_wstream writes with nw waves per workgroup
 size_t wstream_tiled_halves(int N, int Ctot, int ksize);
 void launch_wstream_retile(const half_t* w, half_t* wt, int N, int Ctot, int ksize, hipStream_t s);
-int launch_wstream(const ConvDesc& d, float* partial, int nw, hipStream_t s);
+int launch_wstream(const ConvDesc& d, float* partial, int nw, hipStream_t s);   // nw: ConvPlan::waves
 // the same launch from palettized weights (d.w_pal / pal_lut / pal_bits): every weight is looked up in the LUT in front of the same
 // MFMAs in the same order, so the slabs are bit-identical to launch_wstream's on the de-palettized weights
 int launch_wstream_pal(const ConvDesc& d, float* partial, int nw, hipStream_t s);
@@ -153,18 +154,19 @@ void launch_wsgemm(const ConvDesc& d, hipStream_t s);
 bool bvgemm_shape_ok(const ConvDesc& d);
 size_t bvgemm_tiled_halves(int N, int K);
 void launch_bvgemm_retile(const half_t* w, half_t* wt, int N, int K, bool geglu, hipStream_t s);
-void launch_bvgemm(const ConvDesc& d, int variant, hipStream_t s);   // variant 1-4 (bvgemm.hip), 0 = the library's choice
+void launch_bvgemm(const ConvDesc& d, const ConvPlan& p, hipStream_t s);   // p.variant 1-6 (bvgemm.hip)
+int bvgemm_auto_variant(const ConvDesc& d);                           // the library's choice of a variant (the planner resolves it)
 bool bvgemm_wanted(const ConvDesc& d);                                // the library's rule for taking plan tile 11 on its own
 
 // smgemm.hip: small-M 1x1 GEMM (one source, or two concatenated along K), whole-LDS ring, epilogue from the accumulators (plan tile 12)
 bool smgemm_shape_ok(const ConvDesc& d, int variant);                 // variant 1 / 2: 32- / 64-row tiles, 0: by M
 bool smgemm_wanted(const ConvDesc& d);                                // the library's rule for taking plan tile 12 on its own
-void launch_smgemm(const ConvDesc& d, int variant, hipStream_t s);
-int smgemm_bm(const ConvDesc& d, int variant);                        // the tile height launch_smgemm / launch_smgemm_pal run: 32 or 64
+void launch_smgemm(const ConvDesc& d, const ConvPlan& p, hipStream_t s);   // p.bm: 32- or 64-row tiles
+int smgemm_bm(const ConvDesc& d, int variant);                        // the tile height of a variant: 32 or 64 (the planner resolves it)
 // the same GEMM from palettized weights (plan tile 15: d.w_pal in the layout of weight_prep.h smgemm_pal_pack, d.pal_lut, d.pal_bits):
 // the weights are decoded from the LUT into the fragments of the same MFMAs in the same order, the epilogue is launch_smgemm's, so
 // the output is bit-identical to launch_smgemm's on the fp16 weights lut[indices].  One source only.
-void launch_smgemm_pal(const ConvDesc& d, int variant, hipStream_t s);
+void launch_smgemm_pal(const ConvDesc& d, const ConvPlan& p, hipStream_t s);
 
 // wfold.hip: two back-to-back linear maps folded into one - merged [N][K + J] = [fp16(Wp W2) | Wp], bm = bp + Wp b2 (Wp [N][J],
 // W2 [J][K]; fp32 accumulation in a fixed order, once per handle: UNet::transformer_block's merged tail)
@@ -175,7 +177,8 @@ void launch_wfold(const half_t* wp, const float* bp, const half_t* w2, const flo
 // as uploaded (plan tile 13)
 bool smgeglu_shape_ok(const ConvDesc& d, int variant);                // variant 1 / 2: 128- / 256-row tiles, 0: by the grid size
 bool smgeglu_wanted(const ConvDesc& d);                               // the library's rule for taking plan tile 13 on its own
-void launch_smgeglu(const ConvDesc& d, int variant, hipStream_t s);   // d.prof set: the phase-clock build, which fills
+int smgeglu_bm(const ConvDesc& d, int variant);                       // the tile height of a variant: 128 or 256 (the planner resolves it)
+void launch_smgeglu(const ConvDesc& d, const ConvPlan& p, hipStream_t s);   // p.bm; d.prof set: the phase-clock build, which fills
 size_t smgeglu_prof_entries(const ConvDesc& d, int variant);          // this many long long: [workgroup][10 waves][8], six stamps used
 
 // calib.hip: box calibration for bench.py - out[0..6] = copy GB/s, dense MFMA TFLOP/s, us per launch of a 323-launch empty

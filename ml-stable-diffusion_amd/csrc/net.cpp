@@ -198,10 +198,10 @@ Tensor Net::conv_w(std::vector<Op>& ops, const std::string& name, const half_t* 
   if (a.pal_stream && a.pal_bm) {   // pinned to the palettized small-M GEMM (plan tile 15) with the tile height Net::conv read off the plan
     d.pal_gemm = true;
     d.tile = 15;
-    d.staging = a.pal_bm == 32 ? 1 : 2;
+    d.staging = conv_plan_bm_code(a.pal_bm);
   } else if (a.pal_stream) {   // pinned to the palettized weight stream (plan tile 14) with the wave count Net::conv read off the plan
     d.tile = 14;
-    d.staging = a.pal_waves == 4 ? 4 : 0;
+    d.staging = conv_plan_waves_code(a.pal_waves);
   }
   Tensor out;
   if (ln && a.n_trans > 0) {   // fused q|k|v: [M][n_trans] row-major + V^T [B][cout - n_trans][ldT]

@@ -338,24 +338,27 @@ void sg_launch(const SgArgs& a, unsigned nwg, hipStream_t s) {
   hipLaunchKernelGGL(k, dim3(nwg), dim3(64 * SG_NW), SgCfg<BM>::LDS, s, a);
 }
 
+// a GEGLU projection the kernel tiles with bm-row tiles
+bool sg_tiles(const ConvDesc& d, int bm) {
+  if (!(d.ksize == 1 && d.stride == 1 && d.up == 1 && !d.x1 && d.out_mode == kOutGeglu && !d.out_t && !d.temb && !d.res &&
+        d.q_cols == 0 && !d.gnf_partial && !d.gn_partial && d.n_twins == 0 && !d.debug && (!d.ln_colsum || d.bias) && (bm == 128 || bm == 256)))
+    return false;
+  const long M = (long)d.B * d.Ho * d.Wo;
+  const long mt = M / bm, nt = d.N / SG_WROWS;
+  return d.C0 % SG_BK == 0 && d.C0 >= SG_BK && d.N % SG_WROWS == 0 && d.N % 64 == 0 && M % bm == 0 && mt >= 2 && nt >= 2 &&
+         (mt * nt) % 8 == 0 && mt * nt <= 65535;
+}
+
 }  // namespace
+
+int smgeglu_bm(const ConvDesc& d, int variant) { return sg_bm(d, variant); }
 
 size_t smgeglu_prof_entries(const ConvDesc& d, int variant) {
   const long M = (long)d.B * d.Ho * d.Wo;
   return (size_t)(M / sg_bm(d, variant) * (d.N / SG_WROWS)) * SG_NW * SG_STAMPS;
 }
 
-bool smgeglu_shape_ok(const ConvDesc& d, int variant) {
-  if (!(d.ksize == 1 && d.stride == 1 && d.up == 1 && !d.x1 && d.out_mode == kOutGeglu && !d.out_t && !d.temb && !d.res &&
-        d.q_cols == 0 && !d.gnf_partial && !d.gn_partial && d.n_twins == 0 && !d.debug && (!d.ln_colsum || d.bias) && variant >= 0 &&
-        variant <= 2))
-    return false;
-  const long M = (long)d.B * d.Ho * d.Wo;
-  const int bm = sg_bm(d, variant);
-  const long mt = M / bm, nt = d.N / SG_WROWS;
-  return d.C0 % SG_BK == 0 && d.C0 >= SG_BK && d.N % SG_WROWS == 0 && d.N % 64 == 0 && M % bm == 0 && mt >= 2 && nt >= 2 &&
-         (mt * nt) % 8 == 0 && mt * nt <= 65535;
-}
+bool smgeglu_shape_ok(const ConvDesc& d, int variant) { return variant >= 0 && variant <= 2 && sg_tiles(d, sg_bm(d, variant)); }
 
 // the library's rule: GEGLU projections whose grid of BM x 80 tiles fills the chip once (192-256 workgroups): SD2.1's 1280 -> 10240
 // at M = 512 and 640 -> 5120 at M = 2048.  Everything else - the M = 128 level (64 tiles), the 64 x 64 level (wsgemm.hip), SDXL's and
@@ -367,11 +370,11 @@ bool smgeglu_wanted(const ConvDesc& d) {
   return tiles >= 192 && tiles <= 256;
 }
 
-void launch_smgeglu(const ConvDesc& d, int variant, hipStream_t s) {
-  SD_REQUIRE(smgeglu_shape_ok(d, variant), kInvalidArgument,
+void launch_smgeglu(const ConvDesc& d, const ConvPlan& p, hipStream_t s) {
+  SD_REQUIRE(sg_tiles(d, p.bm), kInvalidArgument,
              "plan tile 13 (smgeglu.hip): not a single-source 1x1 GEGLU projection it tiles (C0=%d N=%d M=%d)", d.C0, d.N, d.B * d.Ho * d.Wo);
   const int M = d.B * d.Ho * d.Wo, K = d.C0;
-  const int bm = sg_bm(d, variant);
+  const int bm = p.bm;
   const unsigned mt = M / bm, nt = d.N / SG_WROWS, nwg = mt * nt;
   SgArgs a;
   a.x = d.x0;
@@ -387,7 +390,7 @@ void launch_smgeglu(const ConvDesc& d, int variant, hipStream_t s) {
   a.lnf = d.ln_colsum != nullptr;
   a.ln_eps = d.ln_eps;
   a.order = sm_tile_order(M, d.N, K, mt, nt);
-  conv_plan_log(d, ConvPlan{13, variant, 1, false, 0}, bm, a.order.n_fast);
+  conv_plan_log(d, p, a.order.n_fast);
   if (bm == 128) {
     if (d.prof) sg_launch<128, true>(a, nwg, s);
     else sg_launch<128, false>(a, nwg, s);

@@ -463,20 +463,22 @@ int sm_bm(const ConvDesc& d, int variant) {   // variant 1 / 2: BM = 32 / 64; 0:
   return (long)d.B * d.Ho * d.Wo <= 1024 ? 32 : 64;
 }
 
-}  // namespace
-
-bool smgemm_shape_ok(const ConvDesc& d, int variant) {
+// a 1x1 GEMM the kernels tile with bm-row tiles
+bool sm_tiles(const ConvDesc& d, int bm) {
   if (!(d.ksize == 1 && d.stride == 1 && d.up == 1 && d.out_mode == kOutHalf && !d.ln_colsum && !d.out_t && !d.temb &&
-        d.q_cols == 0 && !d.gnf_partial && d.n_twins == 0 && !d.debug && variant >= 0 && variant <= 2))
+        d.q_cols == 0 && !d.gnf_partial && d.n_twins == 0 && !d.debug && (bm == 32 || bm == 64)))
     return false;
   const long M = (long)d.B * d.Ho * d.Wo;
-  const int bm = sm_bm(d, variant);
   const long mt = M / bm, nt = d.N / SM_BN;
   // a second source starts on a stage boundary, behind the prologue's NST - 1 stages (the kernel switches inside the K loop only)
   if (d.x1 && !(d.C1 % SM_BK == 0 && d.C1 >= SM_BK && d.C0 / SM_BK >= sm_nst(bm))) return false;
   return d.C0 % SM_BK == 0 && d.C0 >= SM_BK && d.N % SM_BN == 0 && M % bm == 0 && mt >= 2 && nt >= 2 && (mt * nt) % 8 == 0 &&
          mt * nt <= 65535;
 }
+
+}  // namespace
+
+bool smgemm_shape_ok(const ConvDesc& d, int variant) { return variant >= 0 && variant <= 2 && sm_tiles(d, sm_bm(d, variant)); }
 
 // the library's rule: the shapes whose grid fills the chip once (M <= 2048; larger M has enough tiles for igemm.hip's kernels).
 // Launches that must also leave GroupNorm statistics of their output (d.gn_partial) stay on igemm_kernel's epilogue, and so do
@@ -492,10 +494,10 @@ bool smgemm_wanted(const ConvDesc& d) {
 
 int smgemm_bm(const ConvDesc& d, int variant) { return sm_bm(d, variant); }
 
-void launch_smgemm(const ConvDesc& d, int variant, hipStream_t s) {
-  SD_REQUIRE(smgemm_shape_ok(d, variant), kInvalidArgument, "plan tile 12 (smgemm.hip): not a 1x1 GEMM it tiles (C0=%d C1=%d N=%d)",
+void launch_smgemm(const ConvDesc& d, const ConvPlan& p, hipStream_t s) {
+  SD_REQUIRE(sm_tiles(d, p.bm), kInvalidArgument, "plan tile 12 (smgemm.hip): not a 1x1 GEMM it tiles (C0=%d C1=%d N=%d)",
              d.C0, d.x1 ? d.C1 : 0, d.N);
-  const int bm = sm_bm(d, variant);
+  const int bm = p.bm;
   SmArgs a;
   const int n_fast = sm_common_args(a, d, d.C0 + (d.x1 ? d.C1 : 0), bm, d.w);   // K >= 64: the weights hold more than N floats
   a.x1 = d.x1 ? d.x1 : d.x0;
@@ -503,23 +505,23 @@ void launch_smgemm(const ConvDesc& d, int variant, hipStream_t s) {
   a.ldx1 = d.x1 ? d.C1 : d.C0;
   a.w = d.w;
   a.nk0 = d.C0 / SM_BK;
-  conv_plan_log(d, ConvPlan{12, variant, 1, false, 0}, bm, n_fast);
+  conv_plan_log(d, p, n_fast);
   if (bm == 32) launch_sm_fp16<32>(a, s);
   else launch_sm_fp16<64>(a, s);
   SD_HIP(hipGetLastError());
 }
 
-void launch_smgemm_pal(const ConvDesc& d, int variant, hipStream_t s) {
-  SD_REQUIRE(smgemm_shape_ok(d, variant) && !d.x1 && d.w_pal && d.pal_gemm && d.pal_lut && palette_bits_ok(d.pal_bits), kInvalidArgument,
+void launch_smgemm_pal(const ConvDesc& d, const ConvPlan& p, hipStream_t s) {
+  SD_REQUIRE(sm_tiles(d, p.bm) && !d.x1 && d.w_pal && d.pal_gemm && d.pal_lut && palette_bits_ok(d.pal_bits), kInvalidArgument,
              "plan tile 15 (smgemm.hip, palettized): not a single-source 1x1 GEMM it tiles, or no palette (C0=%d C1=%d N=%d M=%d bits=%d)", d.C0,
              d.x1 ? d.C1 : 0, d.N, d.B * d.Ho * d.Wo, d.pal_bits);
-  const int bm = sm_bm(d, variant);
+  const int bm = p.bm;
   SmPalArgs a;
   const int n_fast = sm_common_args(a, d, d.C0, bm, d.w_pal);   // the stream holds at least 64 N bytes; tile 12's order, from the fp16 sizes
   a.pal = d.w_pal;
   a.lut = d.pal_lut;
   a.ngroups = smgemm_pal_groups(d.C0);
-  conv_plan_log(d, ConvPlan{15, bm == 32 ? 1 : 2, 1, false, 0}, bm, n_fast);
+  conv_plan_log(d, p, n_fast);
   pal_dispatch_bits(d.pal_bits, "palettized smgemm", [&](auto nb) {
     if (bm == 32) launch_sm_pal<32, decltype(nb)::value>(a, s);
     else launch_sm_pal<64, decltype(nb)::value>(a, s);

@@ -1,11 +1,11 @@
-// Plan table: {kind, ksize, stride, up, Ctot, N, M, tile, staging, splitk}  (kind / staging: conv_plan.cpp choose_plan,
-// launch_tile).  Measured IN SEQUENCE on MI355X by tools/tune_plans.py (per-op HIP events of the eager SD2.1-base
+// Plan table: {kind, ksize, stride, up, Ctot, N, M, tile, staging, splitk}  (kind: conv_plan.cpp choose_plan; staging:
+// conv_plan.cpp decode_plan).  Measured IN SEQUENCE on MI355X by tools/tune_plans.py (per-op HIP events of the eager SD2.1-base
 // CFG-batch-2 step, caches as cold as in the step): entries beat the previous plan by more than 3 %.
 // other BASELINE configs (tools/gpu_r2_q.sh): shapes that SD2.1-base does not have
-// round 3: the software-pipelined 1x1 GEMM kernel (staging 6 = gemm_pipe_kernel, 3-stage ring), accepted END TO END by
+// round 3: the software-pipelined 1x1 GEMM kernel (gemm_pipe_kernel, first with its 3-stage ring), accepted END TO END by
 // tools/tune_e2e.py on the SD2.1-base CFG-batch-2 step (5.886 -> 5.751 ms on the tuning box, profiles/r03_tune_e2e_pipe.log);
 // listed first: the first matching row wins
-// round 5: the weight-streaming kernel of wstream.hip (tile 9; staging 4 = four waves per workgroup, else eight) on the 8x8 level
+// round 5: the weight-streaming kernel of wstream.hip (tile 9; its code names the waves per workgroup) on the 8x8 level
 {0, 3, 1, 1, 1280, 1280, 128, 9, 0, 1},
 {0, 3, 1, 1, 2560, 1280, 128, 9, 0, 1},
 // round 9: the merged transformer tail [Wp W2 | Wp] [g | h2] (K = 5120 + 1280, two sources) keeps the plan of the 5120 -> 1280 GEMM it

@@ -429,8 +429,8 @@ WsArgs ws_args(const ConvDesc& d, float* partial) {
 // slabs [splits][M][N] of the conv into `partial` from the descriptor's fp16 (nbits 0) or palettized stream; nw = waves (K slices)
 // per workgroup, 4 or 8.  Returns the slab count.
 int launch_ws_conv(const ConvDesc& d, float* partial, int nbits, int nw, hipStream_t s) {
+  SD_REQUIRE(nw == 4 || nw == 8, kInternal, "wstream: %d waves per workgroup", nw);
   const WsArgs a = ws_args(d, partial);
-  if (nw != 4) nw = 8;
   const int splits = cdiv(a.nslices, nw);
   if (d.ksize == 3) {
     if (d.Wo == 8) {

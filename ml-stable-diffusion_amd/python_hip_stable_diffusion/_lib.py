@@ -147,6 +147,7 @@ SYMBOLS = [
     ("sd_op_posterior_noise", _I, [_FP, _FP, _FP, _FP, _I, _I, _I, _I, _F, _F, _F, _I, _FP]),
     ("sd_op_sched_step", _I, [_FP, _FP, _FP, _FP, _FP, _FP, _F, _I, _I, _I, _I, _FP, C.POINTER(_I)]),
     ("sd_op_conv_plan", _I, [_I] * 18 + [C.POINTER(C.c_int), C.POINTER(C.c_ulonglong)]),
+    ("sd_op_conv_plan_kernel", _I, [_I] * 18 + [C.c_char_p, _I]),
     ("sd_numpy_randn", _I, [C.c_uint32, C.POINTER(C.c_double), C.c_size_t]),
     ("sd_torch_randn", _I, [C.c_uint32, C.POINTER(C.c_double), C.c_size_t]),
     ("sd_philox_randn", _I, [C.c_uint64, C.c_uint32, C.POINTER(C.c_double), C.c_size_t]),
@@ -702,13 +703,15 @@ def conv_plan(ksize, stride, up, C0, C1, N, B, Ho, Wo, out_mode=0, flags=0, n_tr
     """The plan the library gives a conv / 1x1 GEMM of this shape (sd_op_conv_plan: host only, no GPU).  flags: 1 LayerNorm fold, 2 timestep
     embedding, 4 residual, 8 GroupNorm statistics, 16 bias, 32 explicit zero padding; copies: bit set of the pre-tiled weight copies that
     exist (1 wstream, 2 wsgemm, 4 bvgemm), -1 = the ones the library's handle holds.  Returns a dict: tile, staging, splitk, slab,
-    workspace_bytes, copies (wstream, wsgemm, bvgemm)."""
+    workspace_bytes, copies (wstream, wsgemm, bvgemm), kernel (sd_op_conv_plan_kernel: the line that names what launches)."""
     plan = (C.c_int * 7)()
     ws = C.c_ulonglong(0)
-    check(lib().sd_op_conv_plan(ksize, stride, up, C0, C1, N, B, Ho, Wo, out_mode, flags, n_trans, n_twins, gnf_groups, tile, staging, splitk,
-                                copies, plan, C.byref(ws)))
+    desc = (ksize, stride, up, C0, C1, N, B, Ho, Wo, out_mode, flags, n_trans, n_twins, gnf_groups, tile, staging, splitk, copies)
+    check(lib().sd_op_conv_plan(*desc, plan, C.byref(ws)))
+    text = C.create_string_buffer(64)
+    check(lib().sd_op_conv_plan_kernel(*desc, text, len(text)))
     return {"tile": plan[0], "staging": plan[1], "splitk": plan[2], "slab": bool(plan[3]), "workspace_bytes": int(ws.value),
-            "copies": (bool(plan[4]), bool(plan[5]), bool(plan[6]))}
+            "copies": (bool(plan[4]), bool(plan[5]), bool(plan[6])), "kernel": text.value.decode()}
 
 
 def timestep_embedding(t, dim, flip_sin_to_cos=True, freq_shift=0.0):

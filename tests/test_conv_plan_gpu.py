@@ -15,7 +15,15 @@ SHAPES = [
     (3, 128, 128, 2, 16, 16, (7,), False),          # the K-split halo kernel
     (3, 1280, 1280, 2, 8, 8, (9,), True),           # M = 128: the weight stream (slabs + combine)
     (1, 2560, 640, 1, 16, 16, (1, 2, 3, 4), True),  # deep K, small M: split-K and the slab combine
+    # the software-pipelined ring (gemm_pipe_kernel), which the table's codes 6 / 8 name.  The table's 1280 -> 320 row at M = 8192
+    # (tile 3, code 6) is not what a handle runs there: with its pre-tiled copy the shape is bvgemm.hip's by the library's rule, which
+    # comes before the table - so that shape pins plan tile 11, and the table's 1280 -> 1280 row at M = 1152 the 3-stage pipelined ring
+    (1, 1280, 320, 2, 64, 64, (11,), False),
+    (1, 1280, 1280, 2, 24, 24, (3,), False),
+    (1, 320, 320, 2, 64, 64, (3,), False),          # the table's only plain 1x1 row with code 8: the 2-stage pipelined ring
 ]
+# what launches for the rows that were added for a kernel, not a tile
+KERNELS = {(1280, 320, 8192): "bvgemm v6", (1280, 1280, 1152): "gemm_pipe 64x64 ring3", (320, 320, 8192): "gemm_pipe 64x64 ring2"}
 
 
 def tile_code(plan):
@@ -36,6 +44,7 @@ def test_query_reports_the_plan_the_launch_runs(k, cin, cout, B, H, W, tiles, sp
     bias = rs.randn(cout).astype(np.float32)
     plan = _lib.conv_plan(k, 1, 1, cin, 0, cout, B, H, W, flags=16)
     assert plan["tile"] in tiles, plan
+    assert plan["kernel"] == KERNELS.get((cin, cout, B * H * W), plan["kernel"]), plan
     assert (plan["splitk"] > 1) == split and plan["slab"] == split, plan
     assert (plan["workspace_bytes"] > 0) == split
     free, _ = _lib.conv2d(x, w, bias=bias)
