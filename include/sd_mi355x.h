@@ -133,8 +133,10 @@ size_t sd_unet_device_bytes(const sd_unet* u);
 size_t sd_unet_arena_used_bytes(const sd_unet* u);
 /* Palettes of the handle's weights: *n_palettized tensors of its weight store arrived with a palette; *n_streamed convolutions read
  * theirs on the device - the small-M weight-stream convs (plan tile 14) and the small-M 1x1 projections proj_in / attn1.to_out.0 /
- * attn2.to_out.0 whose plan is smgemm.hip (plan tile 15), which hold only the index bit stream and the LUT, no fp16 copy;
- * *stream_bytes = the bytes of those streams and LUTs.  Every other palettized tensor was uploaded as fp16 lut[indices]. */
+ * attn2.to_out.0 whose plan is smgemm.hip (plan tile 15) and the GEGLU projections ff.net.0.proj whose plan is smgeglu.hip on
+ * 128-row tiles (plan tile 16; beside stream and LUT they hold norm3.weight as fp32 where the LayerNorm is folded in), which hold only
+ * the index bit stream and the LUT, no fp16 copy; *stream_bytes = the bytes of those streams and LUTs.  Every other palettized tensor
+ * (q|k|v, attn2.to_q, the merged transformer tail, GEGLU projections on 256-row tiles) was uploaded as fp16 lut[indices]. */
 int sd_unet_palette_info(const sd_unet* u, int* n_palettized, int* n_streamed, size_t* stream_bytes);
 
 #define SD_FLAG_DEVICE_PTRS 1 /* all data pointers are device pointers on the handle's GPU */
@@ -381,6 +383,26 @@ int sd_op_gemm_palettized(const void* x, const void* lut, int nbits, const uint8
  * little-endian nbits-wide fields (field f at bits [f * nbits, (f + 1) * nbits)) filling exactly nbits 16-byte words; word q lies at
  * [strip][group][q][lane][16 B].  Fields of stages beyond K / 64 in the last group are zero. */
 int sd_op_palette_pack_gemm(const uint8_t* indices, int Cout, int K, int nbits, uint8_t* stream, size_t* bytes);
+/* smgeglu.hip from PALETTIZED weights (plan tile 16): the GEGLU projection of sd_op_geglu_ln with w = lut[indices], indices (N2, C) uint8
+ * in the checkpoint's row order [values | gates]; x (M, C) f16, ln_weight / ln_bias (C) f32 or both NULL (plain GEGLU), bias (N2) f32 or
+ * NULL -> out (M, N2 / 2) f16.  With the LayerNorm the kernel multiplies every LUT value by ln_weight (fp32 product, one rounding to
+ * fp16) as the host fold does.  Bit-identical to sd_op_geglu_ln(kernel = 101) on the fp16 weights lut[indices].  bm 0 / 128 / 256
+ * (0: by the grid as tile 13); only 128-row tiles are built, so bm = 256 - or bm = 0 on a shape tile 13 would give 256 rows - is
+ * refused.  plan_out[4] = {16, 1, 1, 0}.  Checked on the host in this order, before any device work, each SD_ERR_INVALID_ARGUMENT:
+ * nbits not in {1, 2, 4, 6, 8}; bm not in {0, 128, 256}; NULL or empty arguments; exactly one of ln_weight / ln_bias given; an index >=
+ * 2^nbits (the message names `index N` and its element); a shape the kernel does not tile (C % 64, C <= 2560, N2 % 160, M % 128, at
+ * least 2 x 2 tiles, their number a multiple of 8, 128-row tiles). */
+int sd_op_geglu_palettized(const void* x, const float* ln_weight, const float* ln_bias, const void* lut, int nbits, const uint8_t* indices,
+                           const float* bias, void* out, int M, int C, int N2, float eps, int bm, int* plan_out, int iters, float* ms);
+/* The index bit stream that entry and the UNet builder put on the device (host only, no GPU): indices (N2, K) uint8 in the
+ * checkpoint's row order, N2 % 32 == 0, K % 64 == 0 -> *bytes = (N2 / 16) * groups * nbits * 1024 with groups = ceil(K / 512); stream
+ * may be NULL (size query).  It is the stream of sd_op_palette_pack_gemm over 16-row strips in the order the kernel stages them: strip
+ * 2 U + v holds the checkpoint rows v * N2 / 2 + 16 U + r16, r16 = 0..15 - the value (v = 0) or gate (v = 1) rows of output columns
+ * 16 U .. 16 U + 15.  Per strip as there: K in stages of 64, groups of 8 stages; lane l = 16 g + r16 owns, per stage s and sub-step
+ * kk = 0, 1, the indices of row r16 of the strip at columns 64 s + 32 kk + 8 g + e, e = 0..7; its 128 indices of a group, in the order
+ * (s, kk, e), are little-endian nbits-wide fields (field f at bits [f * nbits, (f + 1) * nbits)) filling exactly nbits 16-byte words;
+ * word q lies at [strip][group][q][lane][16 B].  Fields of stages beyond K / 64 in the last group are zero. */
+int sd_op_palette_pack_geglu(const uint8_t* indices, int N2, int K, int nbits, uint8_t* stream, size_t* bytes);
 /* The same conv followed by torch.nn.GroupNorm (+ SiLU) of its output (unet.py:470-489 conv -> norm -> SiLU; stride 1, no
  * upsample): with producer_stats = 1 the GroupNorm statistics come out of the conv kernel's own epilogue (one launch less per
  * GroupNorm), with 0 from the GroupNorm's own statistics pass.  *entries (may be NULL) returns the number of partial
@@ -494,7 +516,8 @@ int sd_op_sched_step(const float* noise_pred, float* latents, float* hist, const
  * GroupNorm of the input folded into the launch; tile / staging / splitk: a forced plan (0 = the library's); copies: which pre-tiled
  * weight copies exist (1 wstream, 2 wsgemm, 4 bvgemm; -1 = the ones the library's handle would hold).
  * plan[7] = plan tile (1-4 igemm tiles, 7 halo conv, 9 wstream, 10 wsgemm, 11 bvgemm, 12 smgemm, 13 smgeglu, -1 off the MFMA path; the
- * palettized tiles 14 / 15 need a palette and are never an answer here: a handle takes 15 exactly where this says 12, sd_op_gemm_palettized),
+ * palettized tiles 14 / 15 / 16 need a palette and are never an answer here: a handle takes 15 exactly where this says 12
+ * (sd_op_gemm_palettized) and 16 where this says 13 with 128-row tiles (sd_op_geglu_palettized)),
  * staging, resolved split-K, slab (0 / 1), then the copies a handle must hold for this conv: wstream, wsgemm, bvgemm (0 / 1 each).
  * *workspace_bytes: the slab workspace this launch needs. */
 int sd_op_conv_plan(int ksize, int stride, int up, int C0, int C1, int N, int B, int Ho, int Wo, int out_mode, int flags, int n_trans,

@@ -166,14 +166,15 @@ struct ConvOpExtra {
   int pal_bits = 0, pal_waves = 0;       // waves per workgroup: 4, else 8
 };
 
-// the palettized weights of a descriptor as the UNet builder uploads them (Net::conv): the packed index stream - smgemm.hip's for
-// `gemm`, else wstream.hip's - and the padded LUT
-void upload_palette(Scratch& sc, ConvDesc& d, const char* what, const void* lut, int nbits, const uint8_t* indices, bool gemm) {
-  const PaletteHostCopy h = palette_host_copy(what, f16(lut), nbits, indices, d.N, concat_channels(d), d.ksize, gemm);
+// the palettized weights of a descriptor as the UNet builder uploads them (Net::conv, Net::upload_pal_geglu): the packed index stream
+// of the layout and the padded LUT
+void upload_palette(Scratch& sc, ConvDesc& d, const char* what, const void* lut, int nbits, const uint8_t* indices, PalLayout layout) {
+  const PaletteHostCopy h = palette_host_copy(what, f16(lut), nbits, indices, d.N, concat_channels(d), d.ksize, layout);
   d.w_pal = sc.dev<uint8_t>(h.stream.size(), h.stream.data());
   d.pal_lut = sc.dev<half_t>(h.lut.size(), h.lut.data());
   d.pal_bits = nbits;
-  d.pal_gemm = gemm;
+  d.pal_gemm = layout == PalLayout::Gemm;
+  d.pal_geglu = layout == PalLayout::Geglu;
 }
 
 // (B, N) f32 rows on the device as the UNet keeps its time_emb_proj outputs: a column block of a wider row buffer, every other float
@@ -229,7 +230,7 @@ void conv2d_op(const void* x, const void* w, const float* bias, const void* res,
   if (e.pal_indices) {
     SD_REQUIRE(fast && wstream_shape_ok(d), kInvalidArgument, "conv2d_palettized: shape not eligible for plan tile 14 (wstream.hip: k=%d C0=%d C1=%d N=%d %dx%d)",
                ksize, Cin, e.C1, Cout, Ho, Wo);
-    upload_palette(sc, d, "palettized conv", e.pal_lut, e.pal_bits, e.pal_indices, false);
+    upload_palette(sc, d, "palettized conv", e.pal_lut, e.pal_bits, e.pal_indices, PalLayout::Wstream);
     d.tile = 14;
     d.staging = conv_plan_waves_code(e.pal_waves);
   }
@@ -513,7 +514,7 @@ int sd_op_gemm_palettized(const void* x, const void* lut, int nbits, const uint8
     if (res) d.res = upload_nhwc(sc, res, B, Cout, H, W);
     half_t* dout = sc.dev<half_t>((size_t)B * H * W * Cout);
     d.out = dout;
-    upload_palette(sc, d, "gemm_palettized", lut, nbits, indices, true);
+    upload_palette(sc, d, "gemm_palettized", lut, nbits, indices, PalLayout::Gemm);
     d.tile = 15;
     d.staging = variant;
     const ConvPlan p = conv_plan(d);
@@ -956,6 +957,61 @@ int sd_op_geglu_ln(const void* x, const float* ln_weight, const float* ln_bias, 
                 i + 1, t[i * 8 + 1] - t[i * 8], t[i * 8 + 2] - t[i * 8 + 1], t[i * 8 + 3] - t[i * 8 + 2], t[i * 8 + 4] - t[i * 8 + 3]);
     }
     SD_HIP(hipMemcpy(out, dout, (size_t)M * half_n * 2, hipMemcpyDeviceToHost));
+  });
+}
+
+// The same projection from PALETTIZED weights (plan tile 16).  Every check runs on the host in front of the first device call
+// (Scratch), in the order the header lists them.  colsum and the folded bias come from lut[indices] by fold_layernorm_rows, as
+// sd_op_geglu_ln computes them; the folded fp16 matrix is a host temporary.
+int sd_op_geglu_palettized(const void* x, const float* ln_weight, const float* ln_bias, const void* lut, int nbits, const uint8_t* indices,
+                           const float* bias, void* out, int M, int C, int N2, float eps, int bm, int* plan_out, int iters, float* ms) {
+  return guarded([&] {
+    SD_REQUIRE(palette_bits_ok(nbits), kInvalidArgument, "geglu_palettized: nbits = %d, not one of 1, 2, 4, 6, 8", nbits);
+    SD_REQUIRE(bm == 0 || bm == 128 || bm == 256, kInvalidArgument, "geglu_palettized: bm = %d, not 0, 128 or 256", bm);
+    SD_REQUIRE(x && lut && indices && out && plan_out, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(M > 0 && C > 0 && N2 > 0, kInvalidArgument, "geglu_palettized: empty problem");
+    SD_REQUIRE((ln_weight == nullptr) == (ln_bias == nullptr), kInvalidArgument, "geglu_palettized: ln_weight and ln_bias go together");
+    palette_check_indices("geglu_palettized", indices, (size_t)N2 * C, nbits);   // (in front of the shape: the header's order)
+    static const float present = 0.f;   // the planner only tests the pointers
+    ConvDesc d = token_gemm(nullptr, C, nullptr, &present, nullptr, nullptr, 1, M, N2);
+    if (ln_weight) d.ln_colsum = &present;
+    d.ln_eps = eps;
+    d.out_mode = kOutGeglu;
+    const int variant = bm == 128 ? 1 : (bm == 256 ? 2 : 0);
+    SD_REQUIRE(conv_fast_path_ok(d) && smgeglu_pal_shape_ok(d, variant), kInvalidArgument,
+               "geglu_palettized: shape not eligible for plan tile 16 (smgeglu.hip: M=%d C=%d N2=%d bm=%d - 128-row tiles only (256 is not "
+               "built), C a multiple of 64 up to 2560, N2 of 160, M of 128, at least 2 x 2 tiles and a multiple of 8 of them)", M, C, N2, bm);
+    std::vector<half_t> w((size_t)N2 * C), wf(w.size());
+    for (size_t i = 0; i < w.size(); ++i) w[i] = f16(lut)[indices[i]];
+    std::vector<float> bf(N2), cs(N2);
+    fold_layernorm_rows(w.data(), bias, ln_weight, ln_bias, N2, C, 0, true, wf.data(), cs.data(), bf.data());
+    Scratch sc;
+    half_t* dout = sc.dev<half_t>((size_t)M * (N2 / 2));
+    d.x0 = sc.dev<half_t>((size_t)M * C, f16(x));
+    d.out = dout;
+    d.bias = sc.dev<float>(N2, bf.data());
+    if (ln_weight) {
+      d.ln_colsum = sc.dev<float>(N2, cs.data());
+      d.ln_gamma = sc.dev<float>(C, ln_weight);
+    }
+    upload_palette(sc, d, "geglu_palettized", lut, nbits, indices, PalLayout::Geglu);
+    d.tile = 16;
+    d.staging = variant;
+    const ConvPlan p = conv_plan(d);
+    plan_out[0] = p.tile; plan_out[1] = p.staging; plan_out[2] = p.splitk; plan_out[3] = p.slab ? 1 : 0;
+    ConvWorkspace ws;
+    sc.timed(iters, ms, [&] { launch_conv(d, ws, sc.stream); });
+    SD_HIP(hipMemcpy(out, dout, (size_t)M * (N2 / 2) * 2, hipMemcpyDeviceToHost));
+  });
+}
+
+int sd_op_palette_pack_geglu(const uint8_t* indices, int N2, int K, int nbits, uint8_t* stream, size_t* bytes) {
+  return guarded([&] {
+    SD_REQUIRE(indices && bytes, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(palette_bits_ok(nbits) && N2 > 0 && K > 0 && N2 % 32 == 0 && K % 64 == 0, kInvalidArgument,
+               "palette_pack_geglu: nbits %d N2 %d K %d", nbits, N2, K);
+    *bytes = smgemm_pal_bytes(N2, K, nbits);
+    if (stream) smgeglu_pal_pack(indices, N2, K, nbits, stream);
   });
 }
 

@@ -52,9 +52,11 @@ bool can_split(const ConvDesc& d) { return d.out_mode == kOutHalf && !d.ln_colsu
 // the weight-streaming kernel can take this conv: its pre-tiled weights exist and the shape is its own (SD_WSTREAM: tile_ok)
 bool can_stream(const ConvDesc& d) { return d.w_tiled != nullptr && can_split(d) && wstream_shape_ok(d); }
 // a palettized descriptor (plan tile 14): pinned to the palettized weight stream, it holds no fp16 weights to run anything else on
-bool pal_stream(const ConvDesc& d) { return d.w_pal != nullptr && !d.pal_gemm; }
+bool pal_stream(const ConvDesc& d) { return d.w_pal != nullptr && !d.pal_gemm && !d.pal_geglu; }
 // the same for the small-M 1x1 GEMM (plan tile 15): the descriptor carries the stream of smgemm_pal_pack
 bool pal_gemm(const ConvDesc& d) { return d.w_pal != nullptr && d.pal_gemm; }
+// and for the GEGLU projection (plan tile 16): the stream of smgeglu_pal_pack
+bool pal_geglu(const ConvDesc& d) { return d.w_pal != nullptr && d.pal_geglu; }
 // tiles 9 / 14: the code's wave count (decode_plan)
 int wstream_waves(int code) { return code == 4 ? 4 : 8; }
 // fp32 slabs of a launch: one per split, one when only `slab` (weight stream, GroupNorm twins) asks for the slab path
@@ -277,6 +279,14 @@ ConvPlan plan_codes(const ConvDesc& d) {
                "plan tile 15 (smgemm.hip, palettized) needs the index stream, the LUT and a single-source shape of the small-M GEMM");
     return ConvPlan{15, conv_plan_bm_code(smgemm_bm(d, d.staging)), 1, false, 0};
   }
+  if (pal_geglu(d)) {   // pinned likewise; the code of tile 13 in, the resolved tile height out (128 rows: code 1; 256 is not built)
+    SD_REQUIRE(d.pal_lut && palette_bits_ok(d.pal_bits) && !d.pal_gemm && (d.ln_gamma != nullptr) == (d.ln_colsum != nullptr) &&
+                   smgeglu_pal_shape_ok(d, d.staging),
+               kInvalidArgument,
+               "plan tile 16 (smgeglu.hip, palettized) needs the index stream, the LUT, the norm weight with the LayerNorm fold and a shape of "
+               "the GEGLU kernel with 128-row tiles");
+    return ConvPlan{16, 1, 1, false, 0};
+  }
   const Switches& sw = switches();
   // the library's own rules for tiles 10-13 apply where nothing else was asked for (a tuner candidate in force also keeps them off)
   const bool free_choice = d.tile == 0 && d.splitk == 0 && d.staging == 0 && g_tune.tile == 0;
@@ -332,7 +342,7 @@ ConvPlan plan_codes(const ConvDesc& d) {
 //              output (kOutHalfT) has register staging and rings of 2 / 3 stages only.
 //   tile 7:    0 / 2 / 3 / 4 / 5 = 2 / 3 / 4 / 6 / 8 weight stages; GroupNorm in the loader: 4 stages from code 3 where its table fits, else 3
 //   tiles 9 / 14: 4 = four waves per workgroup, anything else eight      tile 11: 1-6 = the variant, anything else the library's choice
-//   tiles 12 / 15 / 13: 1 / 2 = the lower / higher tile (32 / 64, 128 / 256 rows), 0 = by the shape
+//   tiles 12 / 15 / 13 / 16: 1 / 2 = the lower / higher tile (32 / 64, 128 / 256 rows), 0 = by the shape
 void decode_plan(const ConvDesc& d, ConvPlan& p) {
   const Dims a = dims_of(d);
   int code = p.staging;
@@ -351,8 +361,8 @@ void decode_plan(const ConvDesc& d, ConvPlan& p) {
       p.kernel = p.tile == 12 ? ConvKernel::Smgemm : ConvKernel::SmgemmPal;
       p.bm = code >= 0 && code <= 2 ? smgemm_bm(d, code) : 0;   // (0: no such tile - the launcher refuses it)
       return;
-    case 13:
-      p.kernel = ConvKernel::Smgeglu;
+    case 13: case 16:
+      p.kernel = p.tile == 13 ? ConvKernel::Smgeglu : ConvKernel::SmgegluPal;
       p.bm = code >= 0 && code <= 2 ? smgeglu_bm(d, code) : 0;
       return;
     default: break;
@@ -420,6 +430,7 @@ std::string conv_plan_kernel_name(const ConvPlan& p) {
     case ConvKernel::Smgemm: return "smgemm bm" + std::to_string(p.bm);
     case ConvKernel::SmgemmPal: return "smgemm_pal bm" + std::to_string(p.bm);
     case ConvKernel::Smgeglu: return "smgeglu bm" + std::to_string(p.bm);
+    case ConvKernel::SmgegluPal: return "smgeglu_pal bm" + std::to_string(p.bm);
     default: return "generic";
   }
 }
@@ -431,7 +442,7 @@ std::string conv_plan_kernel_name(const ConvPlan& p) {
 //   - with the weight-stream copy present, its slab count at four waves per workgroup (the most slabs it writes);
 //   - the unresolved split-K (the launch may use fewer splits), one slab when only the GroupNorm twins ask for it.
 size_t conv_workspace_bytes(const ConvDesc& d) {
-  if (!conv_fast_path_ok(d) || pal_gemm(d)) return 0;   // (tile 15: no slabs)
+  if (!conv_fast_path_ok(d) || pal_gemm(d) || pal_geglu(d)) return 0;   // (tiles 15 / 16: no slabs)
   const Dims a = dims_of(d);
   const Plan p = choose_plan(d, a);
   int splits = (switches().tuning && can_split(d)) ? std::max(p.splitk, 16) : p.splitk;
@@ -490,6 +501,23 @@ int conv_plan_pal_gemm(const ConvDesc& d0) {
   return p.kernel == ConvKernel::Smgemm ? p.bm : 0;
 }
 
+// And for plan tile 16: tile 13 by the library's own rule (SD_SMGEGLU=0, a tuner candidate or a forced plan give another tile), on the
+// 128-row tiles the palettized kernel has.
+int conv_plan_pal_geglu(const ConvDesc& d0) {
+  if (!conv_fast_path_ok(d0) || !switches().smgeglu || d0.x1 || d0.out_mode != kOutGeglu) return 0;
+  ConvDesc d = d0;
+  d.w_pal = nullptr;
+  d.pal_gemm = d.pal_geglu = false;
+  d.w_tiled = d.w_ws = d.w_bv = nullptr;
+  static const half_t present = 0;   // conv_plan only tests the pointers
+  const ConvWeightCopies c = conv_plan_copies(d);
+  if (c.wstream) d.w_tiled = &present;
+  if (c.wsgemm) d.w_ws = &present;
+  if (c.bvgemm) d.w_bv = &present;
+  const ConvPlan p = conv_plan(d);
+  return p.kernel == ConvKernel::Smgeglu && smgeglu_pal_shape_ok(d, 0) ? p.bm : 0;
+}
+
 // Does the compiled-in plan table hold a row for this shape - a plan that was measured in a step?
 bool conv_plan_is_tuned(const ConvDesc& d) {
   if (!conv_fast_path_ok(d)) return false;
@@ -534,7 +562,7 @@ void conv_plan_log(const ConvDesc& d, const ConvPlan& p, int n_fast) {
   else if (p.tile == 12 || p.tile == 13)
     fprintf(stderr, "[sd conv] k1 s1 up1 C0=%d C1=%d M=%d N=%d K=%d mode=%d tile=%d bm=%d n_fast=%d\n", d.C0, c1, a.M, a.N, a.K, d.out_mode, p.tile, p.bm,
             n_fast);
-  else if (p.tile == 15)
+  else if (p.tile == 15 || p.tile == 16)
     fprintf(stderr, "[sd conv] k1 s1 up1 C0=%d C1=%d M=%d N=%d K=%d mode=%d tile=%d bm=%d n_fast=%d bits=%d\n", d.C0, c1, a.M, a.N, a.K, d.out_mode,
             p.tile, p.bm, n_fast, d.pal_bits);
   else

@@ -8,8 +8,8 @@
 
 namespace sd {
 
-// the kernel a plan launches (tile -1 / 1-4 / 7 / 9 / 14 / 10 / 11 / 12 / 15 / 13 of the wire format below)
-enum class ConvKernel { Generic, Igemm, GemmPipe, HaloKs, Wstream, WstreamPal, Wsgemm, Bvgemm, Smgemm, SmgemmPal, Smgeglu };
+// the kernel a plan launches (tile -1 / 1-4 / 7 / 9 / 14 / 10 / 11 / 12 / 15 / 13 / 16 of the wire format below)
+enum class ConvKernel { Generic, Igemm, GemmPipe, HaloKs, Wstream, WstreamPal, Wsgemm, Bvgemm, Smgemm, SmgemmPal, Smgeglu, SmgegluPal };
 
 struct ConvPlan {
   // The wire format: what ConvDesc::tile / staging pins, tuned_convs.inc rows, SD_PLAN_TABLE and sd_tune_set_candidate say and what
@@ -48,6 +48,9 @@ int conv_plan_pal_waves(const ConvDesc& d);
 // would get plan tile 12 by the library's own rule with that tile height - run it from the index stream of smgemm_pal_pack instead;
 // 0 = no (SD_SMGEMM=0, two sources, a LayerNorm fold, any other plan): upload the de-palettized tensor.
 int conv_plan_pal_gemm(const ConvDesc& d);
+// The same question for the GEGLU projection (plan tile 16): the tile height when this conv, uploaded as fp16 with the copies a handle
+// would hold, gets plan tile 13 by the library's own rule AND the palettized kernel has that tile height (128); else 0.
+int conv_plan_pal_geglu(const ConvDesc& d);
 
 // the SD_LOG_CONVS line of a launch (n_fast: what smgemm.hip / smgeglu.hip add to theirs)
 void conv_plan_log(const ConvDesc& d, const ConvPlan& p, int n_fast = 0);

@@ -1138,6 +1138,7 @@ int launch_conv(const ConvDesc& d, const ConvWorkspace& ws, hipStream_t s) {
     case ConvKernel::Bvgemm: launch_bvgemm(d, p, s); return 0;
     case ConvKernel::Smgemm: launch_smgemm(d, p, s); return 0;
     case ConvKernel::Smgeglu: launch_smgeglu(d, p, s); return 0;
+    case ConvKernel::SmgegluPal: launch_smgeglu_pal(d, p, s); return 0;
     case ConvKernel::SmgemmPal: launch_smgemm_pal(d, p, s); return 0;   // (d.gn_partial set: no statistics, 0 entries - the GroupNorm runs its own pass)
     default: break;
   }

@@ -96,6 +96,11 @@ struct ConvDesc {
   // pal_gemm: w_pal is the bit stream of weight_prep.h smgemm_pal_pack instead and the descriptor is pinned to plan tile 15
   // (smgemm.hip smgemm_pal_kernel; staging = conv_plan_bm_code of the tile height, 0 = by M as tile 12)
   bool pal_gemm = false;
+  // pal_geglu: w_pal is the bit stream of weight_prep.h smgeglu_pal_pack and the descriptor is pinned to plan tile 16 (smgeglu.hip
+  // smgeglu_pal_kernel; staging = the code of tile 13).  With the LayerNorm fold (ln_colsum set) ln_gamma is the fp32 norm weight [C0]:
+  // the kernel multiplies every LUT value by it as fold_layernorm_rows does on the host; without the fold it is null
+  bool pal_geglu = false;
+  const float* ln_gamma = nullptr;
   // weights in the fragment-major layout of wsgemm.hip (launch_wsgemm_retile), or null: the weight-stationary GEGLU kernel
   // (plan tile 10) needs them; launch_conv takes that kernel whenever they are there and no other plan was forced
   const half_t* w_ws = nullptr;
@@ -180,6 +185,11 @@ bool smgeglu_wanted(const ConvDesc& d);                               // the lib
 int smgeglu_bm(const ConvDesc& d, int variant);                       // the tile height of a variant: 128 or 256 (the planner resolves it)
 void launch_smgeglu(const ConvDesc& d, const ConvPlan& p, hipStream_t s);   // p.bm; d.prof set: the phase-clock build, which fills
 size_t smgeglu_prof_entries(const ConvDesc& d, int variant);          // this many long long: [workgroup][10 waves][8], six stamps used
+// the same launch from palettized weights (plan tile 16: d.w_pal in the layout of weight_prep.h smgeglu_pal_pack, d.pal_lut, d.pal_bits,
+// d.ln_gamma with the fold): LUT value times norm weight decoded into the weight rows of the same stages in front of the same MFMAs,
+// so the output is bit-identical to launch_smgeglu's on the folded fp16 weights.  128-row tiles only, C0 <= 2560, no phase clocks.
+bool smgeglu_pal_shape_ok(const ConvDesc& d, int variant);            // variant 0 / 1 resolving to 128-row tiles
+void launch_smgeglu_pal(const ConvDesc& d, const ConvPlan& p, hipStream_t s);
 
 // calib.hip: box calibration for bench.py - out[0..6] = copy GB/s, dense MFMA TFLOP/s, us per launch of a 323-launch empty
 // graph, us per launch of a 323-launch chain of short kernels on cold operands, us per launch of a 323-launch chain handing 8 MB

@@ -87,6 +87,13 @@ Tensor Net::conv(std::vector<Op>& ops, const std::string& name, const Tensor& x,
   // opted in (ConvArgs::pal_gemm), the small-M GEMM (plan tile 15) where its plan would be tile 12; else lut[indices] as fp16.
   const Palette* pal = ws_->palette(name + ".weight");
   const bool pal_ok = pal && !a.silu_out && !a.ln_colsum;
+  if (pal_ok && a.pal_geglu) {   // a plain GEGLU projection behind its LayerNorm launch (plan tile 16)
+    if (const int bm = pal_geglu_bm(name, x, a, false)) {
+      ConvArgs ap = a;
+      upload_pal_geglu(name, std::string(), cin, bm, ap);
+      return conv_w(ops, name, nullptr, b, x, ap);
+    }
+  }
   const int pal_waves = pal_ok ? conv_plan_pal_waves(conv_shape(name, x, a)) : 0;
   const int pal_bm = (pal_ok && !pal_waves && a.pal_gemm && a.k == 1 && !a.x2 && a.out_mode == kOutHalf) ? conv_plan_pal_gemm(conv_shape(name, x, a)) : 0;
   if (pal_waves || pal_bm) {
@@ -97,7 +104,7 @@ Tensor Net::conv(std::vector<Op>& ops, const std::string& name, const Tensor& x,
     SD_REQUIRE(palette_bits_ok(pal->nbits) && pal->lut.size() == (size_t)1 << pal->nbits, kInternal, "%s.weight: a palette of %zu entries for %d bits",
                name.c_str(), pal->lut.size(), pal->nbits);
     const PaletteHostCopy h = palette_host_copy((name + ".weight").c_str(), reinterpret_cast<const half_t*>(pal->lut.data()), pal->nbits,
-                                                pal->indices.data(), a.cout, cin, a.k, !pal_waves);
+                                                pal->indices.data(), a.cout, cin, a.k, pal_waves ? PalLayout::Wstream : PalLayout::Gemm);
     uint8_t* ds = ll_.arena.alloc_n<uint8_t>(h.stream.size());
     SD_HIP(hipMemcpy(ds, h.stream.data(), h.stream.size(), hipMemcpyHostToDevice));
     half_t* dl = ll_.arena.alloc_n<half_t>(h.lut.size());
@@ -114,6 +121,37 @@ Tensor Net::conv(std::vector<Op>& ops, const std::string& name, const Tensor& x,
   }
   const half_t* w = upload_conv_weight(name, a.cout, cin, a.k, geglu);
   return conv_w(ops, name, w, b, x, a);
+}
+
+int Net::pal_geglu_bm(const std::string& name, const Tensor& x, const ConvArgs& a, bool ln) const {
+  if (f32_ || !ws_->palette(name + ".weight") || a.x2 || a.k != 1 || a.out_mode != kOutGeglu || a.silu_out) return 0;
+  ConvDesc d = conv_shape(name, x, a);
+  static const float present = 0.f;   // the planner only tests the pointers
+  if (ln) d.ln_colsum = d.bias = &present;
+  return conv_plan_pal_geglu(d);
+}
+
+void Net::upload_pal_geglu(const std::string& name, const std::string& ln_name, int cin, int bm, ConvArgs& a) {
+  const Palette* pal = ws_->palette(name + ".weight");
+  const size_t expect = (size_t)a.cout * cin;
+  SD_REQUIRE(pal && ws_->get(name + ".weight").numel() == expect && pal->indices.size() == expect, kInvalidArgument,
+             "%s.weight: expected a palette of %zu indices (%d,%d)", name.c_str(), expect, a.cout, cin);
+  SD_REQUIRE(palette_bits_ok(pal->nbits) && pal->lut.size() == (size_t)1 << pal->nbits, kInternal, "%s.weight: a palette of %zu entries for %d bits",
+             name.c_str(), pal->lut.size(), pal->nbits);
+  const PaletteHostCopy h = palette_host_copy((name + ".weight").c_str(), reinterpret_cast<const half_t*>(pal->lut.data()), pal->nbits,
+                                              pal->indices.data(), a.cout, cin, 1, PalLayout::Geglu);
+  uint8_t* ds = ll_.arena.alloc_n<uint8_t>(h.stream.size());
+  SD_HIP(hipMemcpy(ds, h.stream.data(), h.stream.size(), hipMemcpyHostToDevice));
+  half_t* dl = ll_.arena.alloc_n<half_t>(h.lut.size());
+  SD_HIP(hipMemcpy(dl, h.lut.data(), h.lut.size() * sizeof(half_t), hipMemcpyHostToDevice));
+  ++pal_streamed_;
+  pal_stream_bytes_ += h.stream.size() + h.lut.size() * sizeof(half_t);
+  a.pal_stream = ds;
+  a.pal_lut = dl;
+  a.pal_bits = pal->nbits;
+  a.pal_geglu = true;
+  a.pal_bm = bm;
+  a.ln_gamma = ln_name.empty() ? nullptr : upload_vec(ln_name + ".weight", cin);
 }
 
 // fp32 compute path (torch2coreml.py:570-578 converts an SDXL checkpoint's own VAE with FLOAT32 precision): the weights stay
@@ -195,7 +233,12 @@ Tensor Net::conv_w(std::vector<Op>& ops, const std::string& name, const half_t* 
   d.w_pal = a.pal_stream;
   d.pal_lut = a.pal_lut;
   d.pal_bits = a.pal_bits;
-  if (a.pal_stream && a.pal_bm) {   // pinned to the palettized small-M GEMM (plan tile 15) with the tile height Net::conv read off the plan
+  if (a.pal_stream && a.pal_geglu) {   // pinned to the palettized GEGLU kernel (plan tile 16); the code of tile 13 for the tile height
+    d.pal_geglu = true;
+    d.ln_gamma = a.ln_gamma;
+    d.tile = 16;
+    d.staging = a.pal_bm == 128 ? 1 : 2;
+  } else if (a.pal_stream && a.pal_bm) {   // pinned to the palettized small-M GEMM (plan tile 15) with the tile height Net::conv read off the plan
     d.pal_gemm = true;
     d.tile = 15;
     d.staging = conv_plan_bm_code(a.pal_bm);
@@ -268,10 +311,11 @@ Tensor Net::conv_w(std::vector<Op>& ops, const std::string& name, const half_t* 
   char buf[320];
   // trailing "#kind,ksize,stride,up,Ctot,N,M" is the plan-table key of this op (tools/tune_plans.py)
   const int kind = d.out_t ? 3 : (geglu ? 2 : (ln ? 1 : 0));
-  // ("+pal<bits>": the op reads its weights from their palette, plan tile 14 or 15)
+  // ("+pal<bits>": the op reads its weights from their palette, plan tile 14 or 15; plan tile 16 is "geglu+pal<bits>[+ln]")
   const std::string palmark = d.w_pal ? "+pal" + std::to_string(d.pal_bits) : std::string();
-  snprintf(buf, sizeof(buf), "%s%s%s %d->%d @%dx%d M=%d K=%d %s #%d,%d,%d,%d,%d,%d,%d", k == 3 ? "conv3x3" : (geglu ? "geglu1x1" : "gemm1x1"),
-           ln ? "+ln" : "", palmark.c_str(), cin, cout, d.Ho, d.Wo, x.B * d.Ho * d.Wo, cin * k * k, name.c_str(), kind, k, a.stride, a.up, cin, cout,
+  const std::string lnmark = ln ? "+ln" : "";
+  snprintf(buf, sizeof(buf), "%s%s%s %d->%d @%dx%d M=%d K=%d %s #%d,%d,%d,%d,%d,%d,%d", k == 3 ? "conv3x3" : (geglu ? (d.pal_geglu ? "geglu" : "geglu1x1") : "gemm1x1"),
+           (d.pal_geglu ? palmark : lnmark).c_str(), (d.pal_geglu ? lnmark : palmark).c_str(), cin, cout, d.Ho, d.Wo, x.B * d.Ho * d.Wo, cin * k * k, name.c_str(), kind, k, a.stride, a.up, cin, cout,
            x.B * d.Ho * d.Wo);
   ops.back().label = buf;
   ops.back().flop = 2.0 * x.B * d.Ho * d.Wo * (double)cout * cin * k * k;

@@ -81,6 +81,10 @@ struct ConvArgs {
   // tile height Net::conv read off the plan (pal_stream is then the stream of smgemm_pal_pack)
   bool pal_gemm = false;
   int pal_bm = 0;
+  // conv: the same opt-in for a GEGLU projection (plan tile 16, smgeglu.hip from the index stream).  conv_w: pal_stream is the stream of
+  // smgeglu_pal_pack, pal_bm = 128, ln_gamma the fp32 norm weight on the device when ln_colsum is set (Net::upload_pal_geglu fills them)
+  bool pal_geglu = false;
+  const float* ln_gamma = nullptr;
 };
 
 class Net {
@@ -95,7 +99,7 @@ class Net {
   void drop_graphs() { invalidate_graphs(); }   // measurement hook: the next forward re-captures (sd_tune_set_plan_table)
   size_t device_bytes() const { return ll_.arena.bytes(); }
   size_t arena_used_bytes() const { return ll_.arena.used(); }
-  // palettes: tensors of the weight store that arrived with one, convs that read theirs on the device (plan tiles 14 and 15), and
+  // palettes: tensors of the weight store that arrived with one, convs that read theirs on the device (plan tiles 14, 15 and 16), and
   // the bytes of those convs' index streams and LUTs
   void palette_info(int* n_palettized, int* n_streamed, size_t* stream_bytes) const {
     *n_palettized = pal_tensors_;
@@ -117,6 +121,11 @@ class Net {
   // conv uploads <name>.weight / .bias and emits the op; conv_w (fp16 only) takes device pointers
   Tensor conv(std::vector<Op>& ops, const std::string& name, const Tensor& x, const ConvArgs& a);
   Tensor conv_w(std::vector<Op>& ops, const std::string& name, const half_t* w, const float* bias, const Tensor& x, const ConvArgs& a);
+  // A palettized GEGLU projection that stays palettized (plan tile 16): the tile height (128) when <name>.weight has a palette and its
+  // fp16 plan - with the LayerNorm fold for `ln` - would be tile 13 on the tiles the palettized kernel has, else 0; and the upload of
+  // stream and LUT (and norm weight `ln_name`.weight, with the fold) into the arguments conv_w takes
+  int pal_geglu_bm(const std::string& name, const Tensor& x, const ConvArgs& a, bool ln) const;
+  void upload_pal_geglu(const std::string& name, const std::string& ln_name, int cin, int bm, ConvArgs& a);
   // 3x3 conv to N <= 8 channels, one wavefront per pixel (conv_small.hip): fp32 NCHW into out_nchw (a model's boundary), else
   // fp16 NHWC into out_nhwc.  An fp32 handle runs the fp32 conv into out_nhwc (or a tensor of its own) and transposes.
   void conv_small_n(std::vector<Op>& ops, const std::string& name, const Tensor& x, int cout, half_t* out_nhwc, float* out_nchw);

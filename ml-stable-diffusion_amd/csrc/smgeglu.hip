@@ -18,12 +18,17 @@
 //     accumulators with the arithmetic of igemm.hip tile_epilogue, fp16 pairs of two row blocks meet through v_permlane16_swap,
 //     every lane stores 16 B of one output row.
 // PROF instantiation (ConvDesc::prof): every wave leaves six shader-clock stamps (sd_op_geglu_ln prints the table).
+// NBITS > 0 instantiations (plan tile 16, smgeglu_pal_kernel): the same launch from palettized weights - the comment above SgPalArgs.
 #include <algorithm>
+#include <type_traits>
+#include <utility>
 
 #include "conv_plan.h"
 #include "kernels.h"
+#include "pal_decode.h"
 #include "sm_ring.h"
 #include "sm_tile.h"
+#include "weight_prep.h"
 
 namespace sd {
 
@@ -53,6 +58,7 @@ struct SgArgs {
 template <int BM>
 struct SgCfg {
   static constexpr int ROWS = SG_WROWS + BM;                   // staged rows per stage: weights, then activations
+  static constexpr int PIECE0 = 0;                             // first staged piece that travels by LDS-DMA
   static constexpr int PIECES = ROWS / 8;                      // 1-KiB LDS-DMA pieces (8 rows x 128 B) per stage
   static constexpr int PPW = (PIECES + SG_NW - 1) / SG_NW;     // pieces per wave per stage: the first FULL waves; the others one less
   static constexpr int FULL = PIECES - SG_NW * (PPW - 1);
@@ -62,10 +68,83 @@ struct SgCfg {
   static constexpr int SB = TM / 4;                            // blocks whose statistics a wave of units 0-3 carries
   static constexpr int EPI = 4;                                // epilogue loads per lane: bias and colsum of value / gate rows
   static constexpr size_t LDS = (size_t)NST * STAGE + BM * 8;
+  static constexpr int LUT = 0, GAMMA = 0, WORDS = 0, HQ = 1;  // (palettized kernel only)
   static_assert(BM % 128 == 0 && ROWS % 8 == 0 && PPW >= 2 && FULL >= 1 && FULL <= SG_NW, "tile");
   static_assert(NST >= 3 && LDS <= SG_LDS, "ring");
   static_assert(PPW * (NST - 2) + EPI <= 63, "vmcnt range");
 };
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The same launch from PALETTIZED weights (plan tile 16): smgeglu_pal_kernel<BM, NBITS>.  Tile, waves, MFMAs and their order per
+// accumulator block (ascending K64 stage, then kk = 0, 1), tile order, row statistics and epilogue are one text, so the output is
+// bit-identical to smgeglu_kernel on the folded fp16 weights.  Only the source of a stage's 160 weight rows changes:
+//   * no fp16 weight exists in global memory.  The stream is smgemm_pal_pack's (weight_prep.h smgeglu_pal_pack: one 16-row strip
+//     per wave, groups of 8 stages, NBITS 16-B words per lane and group).  The tile's 160 staged rows are ten strips; wave w decodes
+//     strip w of stage rel + 1 beside the MFMAs of stage rel - per weight one field of its bit stream (pal_decode.h), one 2-byte
+//     LDS read of the LUT and, with the LayerNorm fold, w' = (half)((float)lut_value * gamma[k]): one fp32 product, one
+//     round-to-nearest-even, fold_layernorm_rows' expression - and writes its two 16-B chunks per row to `strip base + foff[kk]`
+//     of the stage's slot, the address the MFMA loop reads.  Decode and product are paid once per workgroup, not once per row half;
+//   * the slot of stage rel + 1 last held stage rel + 1 - NST, which every wave left before the barrier at the end of stage
+//     rel - 1 (NST >= 2); the lgkmcnt(0) in front of the barrier at the end of stage rel publishes the writes;
+//   * the ring's DMA pieces are the BM activation rows only: 16 pieces over ten waves, the first FULL = 6 waves issue two per stage,
+//     the others one (the rule of the fp16 kernel with other numbers).  The stage layout is unchanged, 36 KB x NST = 3;
+//   * index words, LUT and gamma arrive by LDS-DMA, counted by hand: the LUT (2 pieces of 256 B: waves 0, 1) and gamma (one 256-B
+//     piece per K64 stage, piece p by wave p % 10; K <= kSgPalMaxK = 2560: 10 KB) once per workgroup in front of everything else, the
+//     index words through a transit buffer per wave of HALF a group: HQ = max(1, NBITS / 2) words (stages 4 i .. 4 i + 3 begin on a
+//     word boundary for every width but 1 bit, whose single word is brought for both halves).  From there a lane takes its 16 B
+//     per word into registers when stage 4 i is the next to decode.  LDS: 108 KB ring + 1 KB statistics + 0.5 KB LUT + 10 KB gamma
+//     + 10 HQ KB transit = 159.5 KB at 8 bits;
+//   * BM = 256 is not built: its stage is 52 KB, and the ring of three the K loop's pipelining and wait ladder are written for
+//     (SgCfg: NST >= 3) leaves 2 KB of the 160 beside the statistics, against 10.5 KB of LUT and gamma and up to 40 KB of transit.
+//     Those launches (640 -> 5120 at M = 2048) stay on fp16; plan tile 16 refuses bm = 256.
+// Order of a wave's LDS-DMA pieces (they retire in order; the only ordinary loads, bias and colsum, come first and are used behind the
+// loop), P = 2 (wave < FULL) or 1 activation pieces per stage:
+//     [LUT] [gamma] [H_0] [stages 0 .. min(NST - 1, nk) - 1]      -> wait A: vmcnt(P min(NST - 1, nk)) + barrier: LUT, gamma, H_0
+//     H_0 -> registers, stage 0 decoded into slot 0, lgkmcnt(0)   -> wait for stage 0 (+ barrier)
+//     [H_1, if nk > 1] [stage NST - 1, if < nk]
+//     end of stage rel (rel + 1 < nk): lgkmcnt(0), wait for stage rel + 1 (+ barrier), [H_((rel + 1) / 4 + 1), if 4 | rel + 1]
+//                                      [stage rel + NST, if < nk]
+// (H_i: the words of half-group min(i, last)).  H_(j+1) is issued at the end of stage 4 j - 1 (j = 0: behind the wait for stage 0) in
+// front of stage 4 j - 1 + NST and moves to registers at the top of stage 4 j + 3, behind the wait for stage 4 j + 3 > 4 j + 2, which
+// is younger; the transit buffer is free again behind the lgkmcnt(0) at the end of that stage.  Younger than stage s at its wait
+// are the `ahead` = min(NST - 2, nk - 1 - s) stages behind it and batch H_(j+1) when 4 j < s < 4 j - 1 + NST:
+//     vmcnt immediate = P * ahead + HQ * [s % 4 in 1 .. NST - 2]        (NST = 3: s % 4 == 1)
+// tests/test_palettize_geglu.py replays this order for every K / 64 from 1 to 44 and finds each immediate equal to the count.
+constexpr int kSgPalMaxK = 2560;
+
+struct SgPalArgs : SgArgs {   // (w unused)
+  const uint8_t* pal;    // [N / 16 strips][groups][NBITS][64 lanes][16 B], strips in the order of smgeglu_pal_pack
+  const half_t* lut;     // kPalLutHalves entries
+  const float* gamma;    // [K] fp32 LayerNorm weight; lnf == 0: not read
+  int nhalf;             // half-groups of a strip's stream: 2 * groups
+};
+template <int BM, int NBITS>
+struct SgPalCfg {
+  static constexpr int ROWS = SG_WROWS + BM;                   // the stage layout of SgCfg; the weight rows are written by the waves
+  static constexpr int PIECE0 = SG_WROWS / 8;
+  static constexpr int PIECES = BM / 8;
+  static constexpr int PPW = (PIECES + SG_NW - 1) / SG_NW;
+  static constexpr int FULL = PIECES - SG_NW * (PPW - 1);
+  static constexpr int STAGE = ROWS / 8 * 1024;
+  static constexpr int NST = 3;
+  static constexpr int TM = BM / 32;
+  static constexpr int SB = TM / 4;
+  static constexpr int HQ = NBITS >= 2 ? NBITS / 2 : 1;        // index words per half-group of 4 stages
+  static constexpr int EPI = 0;                                // (the epilogue loads come first: no wait counts them)
+  static constexpr int STAT = NST * STAGE;                     // byte offsets behind the ring
+  static constexpr int LUT = STAT + BM * 8;
+  static constexpr int GAMMA = LUT + kPalLutHalves * 2;
+  static constexpr int WORDS = GAMMA + kSgPalMaxK * 4;
+  static constexpr size_t LDS = (size_t)WORDS + SG_NW * HQ * 1024;
+  static_assert(BM == 128 && PPW == 2 && FULL >= 1 && FULL <= SG_NW, "tile");
+  static_assert(LDS <= SG_LDS, "ring");
+  static_assert(PPW * (NST - 1) + HQ <= 63, "vmcnt range");
+};
+
+template <int... I, typename F>
+__device__ __forceinline__ void sg_static_for(std::integer_sequence<int, I...>, F&& f) {
+  (f(std::integral_constant<int, I>{}), ...);
+}
 
 __device__ __forceinline__ float sg_gelu_erf(float x) {   // igemm.hip gelu_erf (Abramowitz-Stegun 7.1.26)
   const float z = x * 0.70710678118654752f;
@@ -84,9 +163,11 @@ __device__ __forceinline__ float sg_gelu_erf(float x) {   // igemm.hip gelu_erf 
 // first weight row of 16-column unit U of the output: its 16 value rows; the gate rows are 32 further on
 __device__ __forceinline__ int sg_unit_row(int U) { return 64 * (U >> 1) + 16 * (U & 1); }
 
-template <int BM, bool PROF>
-__global__ __launch_bounds__(64 * SG_NW, 1) void smgeglu_kernel(SgArgs a) {
-  using C = SgCfg<BM>;
+// One body for both launches: NBITS == 0 is the fp16 kernel (weights by LDS-DMA), NBITS > 0 the palettized one (smgeglu_pal_kernel).
+template <int BM, bool PROF, int NBITS = 0>
+__global__ __launch_bounds__(64 * SG_NW, 1) void smgeglu_kernel(std::conditional_t<(NBITS > 0), SgPalArgs, SgArgs> a) {
+  constexpr bool PAL = NBITS > 0;
+  using C = std::conditional_t<PAL, SgPalCfg<BM, PAL ? NBITS : 1>, SgCfg<BM>>;
   constexpr int NST = C::NST, PPW = C::PPW, TM = C::TM, SB = C::SB;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   long long stamp[6] = {};
@@ -108,6 +189,7 @@ __global__ __launch_bounds__(64 * SG_NW, 1) void smgeglu_kernel(SgArgs a) {
   for (int j = 0; j < PPW; ++j) {
     int p = wave + SG_NW * j;
     if (p >= C::PIECES) p -= C::PIECES;                   // (never issued: keeps the address in range)
+    if constexpr (PAL) p += C::PIECE0;                    // (the activation pieces only)
     pdst[j] = p * 1024;
     const int r = p * 8 + (lane >> 3);                    // staged row
     const int chunk = (lane & 7) ^ ((r >> 1) & 7);        // logical chunk at physical slot lane & 7
@@ -126,11 +208,14 @@ __global__ __launch_bounds__(64 * SG_NW, 1) void smgeglu_kernel(SgArgs a) {
     }
   };
 
+  // fp16: the epilogue operands right behind the first ring stages: bias and colsum of this lane's four value and four gate rows
+  // (absent: a readable dummy, so that every launch counts the same loads).  Palettized: in front of every LDS-DMA piece, so that
+  // no wait of the K loop counts them
+  if constexpr (!PAL) {
 #pragma unroll
-  for (int p = 0; p < NST - 1; ++p)
-    if (p < a.nk) issue(p);
-  // the epilogue operands right behind the first ring stages: bias and colsum of this lane's four value and four gate rows
-  // (absent: a readable dummy, so that every launch counts the same loads)
+    for (int p = 0; p < NST - 1; ++p)
+      if (p < a.nk) issue(p);
+  }
   const int g = lane >> 4, r16 = lane & 15;
   const int vrow = sg_unit_row(u_blk + u) + 4 * g;
   __builtin_amdgcn_sched_barrier(0);
@@ -140,6 +225,38 @@ __global__ __launch_bounds__(64 * SG_NW, 1) void smgeglu_kernel(SgArgs a) {
   const floatx4 cs_g = *reinterpret_cast<const floatx4*>(a.colsum + vrow + 32);
   __builtin_amdgcn_sched_barrier(0);
   if constexpr (PROF) stamp[1] = clock64();
+
+  // ---- palettized: LUT and gamma for the workgroup, this wave's index words (header comment) ----
+  const unsigned short* const lutp = reinterpret_cast<const unsigned short*>(smem + (PAL ? C::LUT : 0));
+  const float* const gam = reinterpret_cast<const float*>(smem + (PAL ? C::GAMMA : 0));
+  char* const wbuf = smem + (PAL ? C::WORDS + wave * (C::HQ * 1024) : 0);
+  // half-group min(i, last) into the transit buffer
+  auto issue_half = [&](int i) __attribute__((always_inline)) {
+    if constexpr (PAL) {
+      i = min(i, a.nhalf - 1);
+      const uintx4* p = reinterpret_cast<const uintx4*>(a.pal) + ((size_t)(2 * u_blk + wave) * (a.nhalf >> 1) + (i >> 1)) * (NBITS * 64) +
+                        (NBITS >= 2 ? (i & 1) * (C::HQ * 64) : 0) + lane;
+#pragma unroll
+      for (int q = 0; q < C::HQ; ++q)
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(p + q * 64),
+                                         (__attribute__((address_space(3))) void*)(wbuf + q * 1024), 16, 0, 0);
+    }
+  };
+  if constexpr (PAL) {
+    if (wave < 2)
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a.lut + wave * 128 + lane * 2),
+                                       (__attribute__((address_space(3))) void*)(smem + C::LUT + wave * 256), 4, 0, 0);
+    if (a.lnf) {
+      for (int p = wave; p < a.nk; p += SG_NW)
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a.gamma + p * SG_BK + lane),
+                                         (__attribute__((address_space(3))) void*)(smem + C::GAMMA + p * (SG_BK * 4)), 4, 0, 0);
+    }
+    issue_half(0);
+#pragma unroll
+    for (int p = 0; p < NST - 1; ++p)
+      if (p < a.nk) issue(p);
+    __builtin_amdgcn_sched_barrier(0);
+  }
 
   // fragment offsets inside a stage: row (16-row block base + r16), logical chunk 4 kk + g; every block base is a multiple of 16,
   // so the swizzle of the row is (r16 >> 1) & 7
@@ -180,6 +297,17 @@ __global__ __launch_bounds__(64 * SG_NW, 1) void smgeglu_kernel(SgArgs a) {
   // loads - are in flight; the barrier then says so for every wave
   auto wait_stage = [&](int s) {
     const int ahead = min(NST - 2, a.nk - 1 - s);
+    if constexpr (PAL) {   // no epilogue loads to count; the index batch issued behind the wait for stage s - 1 when s % 4 == 1
+      static_assert(!PAL || NST == 3, "the batch is younger than stages 4 j + 1 .. 4 j + NST - 2");
+      if (full) {
+        if ((s & 3) == 1) sm_wait<PPW, C::HQ, NST - 2>(ahead);
+        else sm_wait<PPW, 0, NST - 2>(ahead);
+      } else {
+        if ((s & 3) == 1) sm_wait<PPW - 1, C::HQ, NST - 2>(ahead);
+        else sm_wait<PPW - 1, 0, NST - 2>(ahead);
+      }
+      return;
+    }
     if (full) {
       if (s <= NST - 2) sm_wait<PPW, C::EPI, NST - 2>(ahead);
       else sm_wait<PPW, 0, NST - 2>(ahead);
@@ -189,8 +317,50 @@ __global__ __launch_bounds__(64 * SG_NW, 1) void smgeglu_kernel(SgArgs a) {
     }
   };
 
+  // ---- palettized: the current half-group's words, and stage s's strip of this wave decoded into its slot ----
+  uintx4 cur[PAL ? C::HQ : 1];
+  auto read_words = [&]() __attribute__((always_inline)) {
+    if constexpr (PAL) {
+#pragma unroll
+      for (int q = 0; q < C::HQ; ++q) cur[q] = *reinterpret_cast<const uintx4*>(wbuf + q * 1024 + lane * 16);
+    }
+  };
+  auto decode_stage = [&](int s, char* st) __attribute__((always_inline)) {
+    if constexpr (PAL) {
+      char* const strip = st + 16 * wave * 128;   // staged strip `wave`: unit wave / 2, value or gate rows
+      const float* const gs = gam + s * SG_BK + 8 * g;
+      // the stage's place in the words held: a compile-time fragment number per case (no variable shift in pal_decode)
+      sg_static_for(std::make_integer_sequence<int, 8>{}, [&](auto tc) __attribute__((always_inline)) {
+        constexpr int T = decltype(tc)::value;
+        if ((s & 7) == T) {
+#pragma unroll
+          for (int kk = 0; kk < 2; ++kk) {
+            half8 f = pal_decode<NBITS>(cur, (NBITS >= 2 ? 2 * (T & 3) : 2 * T) + kk, lutp);
+            if (a.lnf) {
+              const floatx4 g0 = *reinterpret_cast<const floatx4*>(gs + 32 * kk);
+              const floatx4 g1 = *reinterpret_cast<const floatx4*>(gs + 32 * kk + 4);
+#pragma unroll
+              for (int e = 0; e < 8; ++e) f[e] = (half_t)((float)f[e] * (e < 4 ? g0[e & 3] : g1[e & 3]));
+            }
+            *reinterpret_cast<half8*>(strip + foff[kk]) = f;
+          }
+        }
+      });
+    }
+  };
+  if constexpr (PAL) {
+    // wait A: LUT, gamma and H_0 are older than the stages issued; the barrier publishes the workgroup's LUT and gamma
+    if (full) sm_wait<PPW, 0, NST - 1>(min(NST - 1, a.nk));
+    else sm_wait<PPW - 1, 0, NST - 1>(min(NST - 1, a.nk));
+    read_words();
+    decode_stage(0, smem);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  }
   wait_stage(0);
   if constexpr (PROF) stamp[2] = clock64();
+  if constexpr (PAL) {
+    if (a.nk > 1) issue_half(1);
+  }
   if (NST - 1 < a.nk) issue(NST - 1);
   read_w(smem, wv, wg);
   read_q(smem, 0);
@@ -199,6 +369,13 @@ __global__ __launch_bounds__(64 * SG_NW, 1) void smgeglu_kernel(SgArgs a) {
   for (int rel = 0; rel < a.nk; ++rel) {
     const char* st = smem + slot * C::STAGE;
     const int nslot = slot + 1 == NST ? 0 : slot + 1;
+    if constexpr (PAL) {
+      if (rel + 1 < a.nk) {   // the next stage's weight rows; its half-group has landed (header comment)
+        if (((rel + 1) & 3) == 0) read_words();
+        decode_stage(rel + 1, smem + nslot * C::STAGE);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
       const int kk = q / NG;
@@ -208,6 +385,9 @@ __global__ __launch_bounds__(64 * SG_NW, 1) void smgeglu_kernel(SgArgs a) {
         // wave: stage rel + NST may overwrite this stage's slot
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         wait_stage(rel + 1);
+        if constexpr (PAL) {
+          if (((rel + 1) & 3) == 0) issue_half(((rel + 1) >> 2) + 1);
+        }
         if (rel + NST < a.nk) issue(slot);
       }
       // the quarter's first MFMA, then the next quarter's reads, then the rest: hipcc waits for ALL outstanding LDS reads in front
@@ -249,6 +429,7 @@ __global__ __launch_bounds__(64 * SG_NW, 1) void smgeglu_kernel(SgArgs a) {
     slot = nslot;
   }
   if constexpr (PROF) stamp[3] = clock64();
+  if constexpr (PAL) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // a last index batch may still be on its way to the LDS
 
   // ---- row statistics: the four K-chunk groups of a row meet by lane shuffles, (ln_a, ln_b) of the tile's rows through LDS ----
   float ln_a[TM], ln_b[TM];
@@ -322,6 +503,9 @@ __global__ __launch_bounds__(64 * SG_NW, 1) void smgeglu_kernel(SgArgs a) {
   }
 }
 
+template <int BM, int NBITS>
+constexpr auto smgeglu_pal_kernel = smgeglu_kernel<BM, false, NBITS>;
+
 // variant 1 / 2: BM = 128 / 256; 0: the smaller tile height whose grid is at most one round of 256 CUs
 int sg_bm(const ConvDesc& d, int variant) {
   if (variant == 1) return 128;
@@ -370,16 +554,15 @@ bool smgeglu_wanted(const ConvDesc& d) {
   return tiles >= 192 && tiles <= 256;
 }
 
-void launch_smgeglu(const ConvDesc& d, const ConvPlan& p, hipStream_t s) {
-  SD_REQUIRE(sg_tiles(d, p.bm), kInvalidArgument,
-             "plan tile 13 (smgeglu.hip): not a single-source 1x1 GEGLU projection it tiles (C0=%d N=%d M=%d)", d.C0, d.N, d.B * d.Ho * d.Wo);
+namespace {
+
+// the launch arguments both kernels share; `dummy`: readable memory of at least N floats that stands in for an absent bias / colsum
+SgArgs sg_common_args(const ConvDesc& d, int bm, const void* dummy) {
   const int M = d.B * d.Ho * d.Wo, K = d.C0;
-  const int bm = p.bm;
-  const unsigned mt = M / bm, nt = d.N / SG_WROWS, nwg = mt * nt;
   SgArgs a;
   a.x = d.x0;
   a.w = d.w;
-  a.bias = d.bias ? d.bias : reinterpret_cast<const float*>(d.w);   // K >= 64: the weights hold more than N floats
+  a.bias = d.bias ? d.bias : static_cast<const float*>(dummy);
   a.colsum = d.ln_colsum ? d.ln_colsum : a.bias;
   a.out = d.out;
   a.prof = d.prof;
@@ -389,7 +572,47 @@ void launch_smgeglu(const ConvDesc& d, const ConvPlan& p, hipStream_t s) {
   a.has_bias = d.bias != nullptr;
   a.lnf = d.ln_colsum != nullptr;
   a.ln_eps = d.ln_eps;
-  a.order = sm_tile_order(M, d.N, K, mt, nt);
+  a.order = sm_tile_order(M, d.N, K, M / bm, d.N / SG_WROWS);   // (palettized too: from the fp16 operand sizes)
+  return a;
+}
+
+}  // namespace
+
+bool smgeglu_pal_shape_ok(const ConvDesc& d, int variant) {
+  return variant >= 0 && variant <= 2 && sg_bm(d, variant) == 128 && sg_tiles(d, 128) && d.C0 <= kSgPalMaxK && !d.prof;
+}
+
+void launch_smgeglu_pal(const ConvDesc& d, const ConvPlan& p, hipStream_t s) {
+  SD_REQUIRE(p.bm == 128 && sg_tiles(d, p.bm) && d.C0 <= kSgPalMaxK && !d.prof && d.w_pal && d.pal_geglu && d.pal_lut && palette_bits_ok(d.pal_bits) &&
+                 (d.ln_gamma != nullptr) == (d.ln_colsum != nullptr),
+             kInvalidArgument,
+             "plan tile 16 (smgeglu.hip, palettized): not a 1x1 GEGLU projection it tiles with 128-row tiles, or no palette / norm weight "
+             "(C0=%d N=%d M=%d bm=%d bits=%d)", d.C0, d.N, d.B * d.Ho * d.Wo, p.bm, d.pal_bits);
+  SgPalArgs a;
+  static_cast<SgArgs&>(a) = sg_common_args(d, p.bm, d.w_pal);   // the stream holds at least 64 N bytes
+  a.pal = d.w_pal;
+  a.lut = d.pal_lut;
+  a.gamma = d.ln_gamma;
+  a.nhalf = 2 * smgemm_pal_groups(d.C0);
+  const unsigned nwg = (unsigned)(d.B * d.Ho * d.Wo / p.bm) * (d.N / SG_WROWS);
+  conv_plan_log(d, p, a.order.n_fast);
+  pal_dispatch_bits(d.pal_bits, "palettized smgeglu", [&](auto nb) {
+    constexpr int NB = decltype(nb)::value;
+    constexpr size_t lds = SgPalCfg<128, NB>::LDS;
+    auto k = smgeglu_pal_kernel<128, NB>;
+    static DynLdsOnce once;
+    once.set(k, lds);
+    hipLaunchKernelGGL(k, dim3(nwg), dim3(64 * SG_NW), lds, s, a);
+  });
+  SD_HIP(hipGetLastError());
+}
+
+void launch_smgeglu(const ConvDesc& d, const ConvPlan& p, hipStream_t s) {
+  SD_REQUIRE(sg_tiles(d, p.bm), kInvalidArgument,
+             "plan tile 13 (smgeglu.hip): not a single-source 1x1 GEGLU projection it tiles (C0=%d N=%d M=%d)", d.C0, d.N, d.B * d.Ho * d.Wo);
+  const int bm = p.bm;
+  const unsigned nwg = (unsigned)(d.B * d.Ho * d.Wo / bm) * (d.N / SG_WROWS);
+  const SgArgs a = sg_common_args(d, bm, d.w);   // K >= 64: the weights hold more than N floats
   conv_plan_log(d, p, a.order.n_fast);
   if (bm == 128) {
     if (d.prof) sg_launch<128, true>(a, nwg, s);

@@ -68,7 +68,7 @@ Tensor UNet::conv_stacked(std::vector<Op>& ops, const std::vector<std::string>& 
 // GEMM runs on the raw rows and applies the row statistics in its epilogue (igemm LNF kernels), so
 // the separate LayerNorm launch, its HBM round trip and the fp16 rounding of LN(x) all disappear.
 UNet::LnFold UNet::fold_layernorm(const std::string& ln, const std::vector<std::string>& names, int cin, int cout_each,
-                                  bool geglu) {
+                                  bool geglu, bool upload_w) {
   const HostTensor& g = ws_->get(ln + ".weight");
   const HostTensor& be = ws_->get(ln + ".bias");
   SD_REQUIRE((int)g.numel() == cin && (int)be.numel() == cin, kInvalidArgument, "%s: expected %d channels", ln.c_str(),
@@ -86,10 +86,10 @@ UNet::LnFold UNet::fold_layernorm(const std::string& ln, const std::vector<std::
                         geglu, w.data(), colsum.data(), bias.data());
   }
   LnFold f;
-  f.w = ll_.arena.alloc_n<half_t>(w.size());
+  f.w = upload_w ? ll_.arena.alloc_n<half_t>(w.size()) : nullptr;
   f.colsum = ll_.arena.alloc_n<float>(ntot);
   f.bias = ll_.arena.alloc_n<float>(ntot);
-  SD_HIP(hipMemcpy(f.w, w.data(), w.size() * sizeof(half_t), hipMemcpyHostToDevice));
+  if (upload_w) SD_HIP(hipMemcpy(f.w, w.data(), w.size() * sizeof(half_t), hipMemcpyHostToDevice));
   SD_HIP(hipMemcpy(f.colsum, colsum.data(), ntot * sizeof(float), hipMemcpyHostToDevice));
   SD_HIP(hipMemcpy(f.bias, bias.data(), ntot * sizeof(float), hipMemcpyHostToDevice));
   return f;
@@ -313,12 +313,18 @@ Tensor UNet::transformer_block(std::vector<Op>& ops, const std::string& b, const
   if (!branch_done) h2 = conv(ops, b + ".attn2.to_out.0", a2, {.cout = C, .res = h1.p, .pal_gemm = true});
   // --- GEGLU feed-forward (norm3 folded the same way)
   Tensor g;
+  // A palettized ff.net.0.proj whose plan is smgeglu.hip on 128-row tiles stays palettized (plan tile 16): stream, LUT and - with the
+  // fold - norm3.weight go up, colsum and the folded bias come from lut[indices] as ever, no fp16 matrix is uploaded
   if (can_fold_ln(h2, 8 * C, true)) {
-    LnFold f = fold_layernorm(b + ".norm3", {b + ".ff.net.0.proj"}, C, 8 * C, true);
-    g = conv_w(ops, b + ".ff.net.0.proj", f.w, f.bias, h2, {.cout = 8 * C, .out_mode = kOutGeglu, .ln_colsum = f.colsum});
+    ConvArgs ga{.cout = 8 * C, .out_mode = kOutGeglu};
+    const int pal_bm = pal_geglu_bm(b + ".ff.net.0.proj", h2, ga, true);
+    LnFold f = fold_layernorm(b + ".norm3", {b + ".ff.net.0.proj"}, C, 8 * C, true, pal_bm == 0);
+    ga.ln_colsum = f.colsum;
+    if (pal_bm) upload_pal_geglu(b + ".ff.net.0.proj", b + ".norm3", C, pal_bm, ga);
+    g = conv_w(ops, b + ".ff.net.0.proj", f.w, f.bias, h2, ga);
   } else {
     Tensor n3 = layer_norm(ops, b + ".norm3", h2);
-    g = conv(ops, b + ".ff.net.0.proj", n3, {.cout = 8 * C, .out_mode = kOutGeglu});
+    g = conv(ops, b + ".ff.net.0.proj", n3, {.cout = 8 * C, .out_mode = kOutGeglu, .pal_geglu = true});
   }
   // the tail of the SpatialTransformer - ff.net.2 + residual -> proj_out + residual - as ONE launch at the 320-channel level
   // (ffn_proj_kernel: the intermediate never goes to HBM, the output's GroupNorm statistics for the next resnet come out of it);

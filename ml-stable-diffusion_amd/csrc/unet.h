@@ -43,8 +43,9 @@ class UNet : public Net {
     float* colsum;
     float* bias;
   };
+  // upload_w = false: the folded fp16 matrix stays a host temporary (f.w null): the projection runs from its palette
   LnFold fold_layernorm(const std::string& ln, const std::vector<std::string>& names, int cin, int cout_each,
-                        bool geglu);
+                        bool geglu, bool upload_w = true);
   bool can_fold_ln(const Tensor& x, int cout, bool geglu) const;
   Tensor conv_stacked(std::vector<Op>& ops, const std::vector<std::string>& names, const Tensor& x, int cout_each);
   Tensor layer_norm(std::vector<Op>& ops, const std::string& name, const Tensor& x);

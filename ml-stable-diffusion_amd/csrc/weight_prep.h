@@ -132,9 +132,28 @@ inline void smgemm_pal_pack(const uint8_t* indices, int N, int K, int nbits, uin
       }
 }
 
+// The palettized weight stream of smgeglu.hip (plan tile 16), indices [N2][K] of ff.net.0.proj in the checkpoint's row order (rows
+// 0 .. N2 / 2 - 1 the values, the rest the gates), N2 % 32 == 0, K % 64 == 0.  The stream is smgemm_pal_pack's - strips of 16 rows,
+// groups of 8 stages, nbits words of [64 lanes][16 B] per strip and group, lane 16 g + r16 holding row r16's indices of columns
+// 64 s + 32 kk + 8 g + e in the order (s, kk, e) - over 16-row strips in the order the kernel's tile stages them: strip 2 U + v holds
+// the checkpoint rows v * N2 / 2 + 16 U + (0 .. 15) - the 16 value (v = 0) or gate (v = 1) rows of the output's 16-column unit U
+// (geglu_row puts them at rows 64 (U / 2) + 16 (U % 2) + 32 v of the fp16 upload).  A tile of 80 output columns reads the ten
+// consecutive strips 10 n_tile .. 10 n_tile + 9, one per wave.  Bytes: smgemm_pal_bytes(N2, K, nbits).
+inline void smgeglu_pal_pack(const uint8_t* indices, int N2, int K, int nbits, uint8_t* dst) {
+  std::vector<uint8_t> rows((size_t)N2 * K);
+  for (int strip = 0; strip < N2 / 16; ++strip)
+    for (int i = 0; i < 16; ++i) {
+      const int o = (strip & 1) * (N2 / 2) + 16 * (strip >> 1) + i;   // checkpoint row
+      // the same row through the upload's interleave: where the fp16 kernel reads it
+      SD_REQUIRE(geglu_row(o, N2) == 64 * (strip >> 2) + 16 * ((strip >> 1) & 1) + 32 * (strip & 1) + i, kInternal, "GEGLU strip order");
+      std::copy(indices + (size_t)o * K, indices + (size_t)(o + 1) * K, rows.begin() + ((size_t)strip * 16 + i) * K);
+    }
+  smgemm_pal_pack(rows.data(), N2, K, nbits, dst);
+}
+
 // What every upload of a palettized tensor starts from (the operator entry points of capi_ops.cpp, Net::conv): indices inside the
-// palette, the packed stream - smgemm.hip's for `gemm` (indices [N][Ctot], ksize 1), else wstream.hip's - and the LUT zero-padded to
-// the kPalLutHalves entries the kernels copy.  The caller has checked the shape against the layout and owns the device memory.
+// palette, the packed stream of the layout - wstream.hip's, smgemm.hip's or smgeglu.hip's (the latter two: indices [N][Ctot], ksize 1)
+// - and the LUT zero-padded to the kPalLutHalves entries the kernels copy.  The caller has checked the shape against the layout and owns the device memory.
 inline void palette_check_indices(const char* what, const uint8_t* indices, size_t n, int nbits) {
   for (size_t i = 0; i < n; ++i)
     SD_REQUIRE(indices[i] < (1u << nbits), kInvalidArgument, "%s: index %u at element %zu, the palette has %d entries", what,
@@ -144,12 +163,14 @@ struct PaletteHostCopy {
   std::vector<uint8_t> stream;
   std::vector<half_t> lut;
 };
+enum class PalLayout { Wstream, Gemm, Geglu };
 inline PaletteHostCopy palette_host_copy(const char* what, const half_t* lut, int nbits, const uint8_t* indices, int N, int Ctot, int ksize,
-                                         bool gemm) {
+                                         PalLayout layout) {
   palette_check_indices(what, indices, (size_t)N * Ctot * ksize * ksize, nbits);
   PaletteHostCopy h;
-  h.stream.resize(gemm ? smgemm_pal_bytes(N, Ctot, nbits) : wstream_pal_bytes(N, Ctot, ksize, nbits));
-  if (gemm) smgemm_pal_pack(indices, N, Ctot, nbits, h.stream.data());
+  h.stream.resize(layout == PalLayout::Wstream ? wstream_pal_bytes(N, Ctot, ksize, nbits) : smgemm_pal_bytes(N, Ctot, nbits));
+  if (layout == PalLayout::Gemm) smgemm_pal_pack(indices, N, Ctot, nbits, h.stream.data());
+  else if (layout == PalLayout::Geglu) smgeglu_pal_pack(indices, N, Ctot, nbits, h.stream.data());
   else wstream_pal_pack(indices, N, Ctot, ksize, nbits, h.stream.data());
   h.lut.assign(kPalLutHalves, (half_t)0);
   std::copy(lut, lut + (1 << nbits), h.lut.begin());

@@ -130,6 +130,8 @@ SYMBOLS = [
     ("sd_op_palette_pack", _I, [_P, _I, _I, _I, _I, _P, C.POINTER(C.c_size_t)]),
     ("sd_op_gemm_palettized", _I, [_P, _P, _I, _P, _FP, _P, _P, _I, _I, _I, _I, _I, _I, C.POINTER(_I), _I, _FP]),
     ("sd_op_palette_pack_gemm", _I, [_P, _I, _I, _I, _P, C.POINTER(C.c_size_t)]),
+    ("sd_op_geglu_palettized", _I, [_P, _FP, _FP, _P, _I, _P, _FP, _P, _I, _I, _I, C.c_float, _I, C.POINTER(_I), _I, _FP]),
+    ("sd_op_palette_pack_geglu", _I, [_P, _I, _I, _I, _P, C.POINTER(C.c_size_t)]),
     ("sd_op_conv2d_groupnorm", _I, [_P, _P, _FP, _P, _FP, _FP, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _I, _I, _I, C.POINTER(_I), _I, _FP]),
     ("sd_op_conv2d_groupnorm_proj", _I, [_P, _P, _FP, _P, _FP, _FP, _P, _FP, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _I, C.POINTER(_I), _I, _FP]),
     ("sd_op_conv2d_groupnorm_conv3x3", _I, [_P, _P, _FP, _P, _FP, _FP, _P, _FP, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _I, _I, _I,
@@ -477,6 +479,47 @@ def palette_pack_gemm(indices, nbits):
         raise ValueError("palette_pack_gemm: indices must be (Cout, K)")
     Cout, K = indices.shape
     return _packed(lib().sd_op_palette_pack_gemm, ptr(indices), Cout, K, nbits).reshape(Cout // 16, -1, nbits, 64, 16)
+
+
+def geglu_palettized(x, lut, indices, nbits, bias=None, ln_weight=None, ln_bias=None, eps=1e-5, bm=0, out=None, iters=1):
+    """The GEGLU projection of smgeglu.hip from palettized weights (sd_op_geglu_palettized, plan tile 16): w = lut[indices], lut
+    (2^nbits,) f16, indices (N2, C) uint8 in the checkpoint's row order [values | gates], x (M, C); ln_weight / ln_bias (C,) or both
+    None (plain GEGLU); bm 0 / 128 / 256 = the tile height (0: by the grid; only 128-row tiles are built).  ``out``: a C-contiguous
+    float16 buffer of at least M * N2 / 2 elements to write into (tests put guards behind it).  What the library checks - nbits, bm,
+    the LayerNorm pair, index range, shape - it refuses itself (ValueError, no GPU needed).  Returns (out (M, N2 / 2), plan, ms)."""
+    x, lut = f16(x), f16(lut)
+    indices = np.ascontiguousarray(indices, dtype=np.uint8)
+    if x.ndim != 2 or indices.ndim != 2 or indices.shape[1] != x.shape[1]:
+        raise ValueError("geglu_palettized: x must be (M, C) and indices (N2, C)")
+    M, Cn = x.shape
+    N2 = indices.shape[0]
+    if nbits in (1, 2, 4, 6, 8) and lut.shape != (1 << nbits,):
+        raise ValueError("geglu_palettized: lut must hold 2 ** nbits entries")
+    bias = None if bias is None else f32(bias)
+    ln_weight = None if ln_weight is None else f32(ln_weight)
+    ln_bias = None if ln_bias is None else f32(ln_bias)
+    if (bias is not None and bias.shape != (N2,)) or any(v is not None and v.shape != (Cn,) for v in (ln_weight, ln_bias)):
+        raise ValueError("geglu_palettized: bias must be (N2,), ln_weight / ln_bias (C,)")
+    n = M * (N2 // 2)
+    if out is None:
+        out = np.empty(n, np.float16)
+    if out.dtype != np.float16 or not out.flags.c_contiguous or out.size < n:
+        raise ValueError("geglu_palettized: out must be a C-contiguous float16 buffer of at least M * N2 / 2 elements")
+    plan = (C.c_int * 4)()
+    ms = C.c_float(0)
+    check(lib().sd_op_geglu_palettized(ptr(x), fptr(ln_weight), fptr(ln_bias), ptr(lut), nbits, ptr(indices), fptr(bias), ptr(out), M, Cn,
+                                       N2, eps, bm, plan, iters, C.byref(ms)))
+    return out.reshape(-1)[:n].reshape(M, N2 // 2), list(plan), ms.value
+
+
+def palette_pack_geglu(indices, nbits):
+    """The index bit stream of the palettized GEGLU projection (sd_op_palette_pack_geglu; host only): indices (N2, K) uint8 in the
+    checkpoint's row order -> uint8 array [N2 / 16 strips][ceil(K / 512) groups][nbits words][64 lanes][16 bytes]."""
+    indices = np.ascontiguousarray(indices, dtype=np.uint8)
+    if indices.ndim != 2:
+        raise ValueError("palette_pack_geglu: indices must be (N2, K)")
+    N2, K = indices.shape
+    return _packed(lib().sd_op_palette_pack_geglu, ptr(indices), N2, K, nbits).reshape(N2 // 16, -1, nbits, 64, 16)
 
 
 def groupnorm_shortcut(x0, x1, gn_weight, gn_bias, w, bias=None, groups=32, eps=1e-5, silu=True, side=True, iters=1):
