@@ -595,6 +595,47 @@ int sd_op_safety_head(const float* image_embeds, const float* concept_embeds, co
                       const float* concept_w, const float* special_w, float adjustment, int B, int P,
                       int n_concepts, int n_special, float* has_nsfw, float* concept_scores);
 
+/* ------------------------------------------------------------------------------------------
+ * Image post-processing on the device: from the decoder's last conv to the 8-bit image and the safety verdict without a detour
+ * through the host.  Replaces, bit for bit, what the reference does in numpy, PIL and transformers' CLIPImageProcessor between its two
+ * models (pipeline.py:286-320: decode_latents' clip and transpose, numpy_to_pil, the feature extractor's 8-bit bicubic resize, centre
+ * crop, rescale and normalise, the cast to fp16); Decoder.swift:40-68 (the decoder returns an 8-bit image), SafetyChecker.swift:55-99
+ * (the checker takes the image and resizes and normalises it itself).
+ *   quantise   q = rint(clamp(x * 0.5f + 0.5f, 0, 1) * 255.0f), round-half-to-even, uint8 (B, H, W, 3)
+ *   resize     Pillow's 8-bit Image.resize(BICUBIC): two separable passes, horizontal first, the intermediate image rounded to uint8,
+ *              22-bit fixed-point coefficients (sd_op_resample_coeffs); a pass whose size does not change is the identity
+ *   crop       centre crop to S x S, S = the checker's image_size: top = (resize_h - S) / 2, left = (resize_w - S) / 2
+ *   normalise  ((float)u / 255.0f - image_mean[c]) / image_std[c] in fp32, both divisions IEEE-rounded, then fp16 (RNE), (B, 3, S, S)
+ * ------------------------------------------------------------------------------------------ */
+/* The geometry and constants of CLIPImageProcessor as the checkpoint's preprocessor_config.json resolves them for this image size
+ * (pipeline.py:288-291): the size the image is resized to before the crop, and the fp32 roundings of image_mean / image_std. */
+typedef struct sd_image_post {
+  int32_t resize_h, resize_w;
+  float image_mean[3], image_std[3];
+} sd_image_post;
+/* replaces decode_latents + numpy_to_pil + the feature extractor + `safety_checker(...)` + filtered_images (pipeline.py:286-320,
+ * torch2coreml.py:1203-1207; Decoder.swift:40-68 decode, SafetyChecker.swift:55-99 isSafe).  Runs the decoder like sd_vae_decode,
+ * then the two kernels on the decoder's stream, feeds `checker` from device memory in slices of its static batch and zeroes the
+ * flagged images in `image` and `rgb8`.  z / flags as in sd_vae_decode; image (B,3,H,W) f32 in [-1, 1] and rgb8 (B,H,W,3) follow
+ * `flags` like `image` there; has_nsfw (B) 0 / 1 and concept_scores (B,num_concepts) are host memory as in sd_safety_checker_run.
+ * image, rgb8 and checker (with post, has_nsfw, concept_scores) may each be NULL; a checker needs `post`.  With no checker this is
+ * Decoder.swift's 8-bit output alone.  SD_ERR_INVALID_ARGUMENT before any device work: a decoder batch that is no multiple of the
+ * checker's, handles on different devices, resize_h / resize_w below S; SD_ERR_UNSUPPORTED: an odd S, or a downscale so steep that a
+ * tile's source rows exceed 64 KB of LDS. */
+int sd_vae_decode_images(sd_unet* vae, const void* z, sd_dtype z_dtype, float* image, uint8_t* rgb8, sd_safety_checker* checker,
+                         const sd_image_post* post, float adjustment, float* has_nsfw, float* concept_scores, int flags);
+/* operator-level entries, same conventions as the other sd_op_*.
+ * Pillow's coefficient tables of one axis, in_size -> out_size samples (the resize inside CLIPImageProcessor, pipeline.py:288-291).
+ * Host only.  *ksize = taps per output sample; bounds (out_size, 2) = [first source index, tap count]; coeffs (out_size, *ksize),
+ * zeros behind a row's taps.  A NULL table pointer is a size query: *ksize alone. */
+int sd_op_resample_coeffs(int in_size, int out_size, int* ksize, int32_t* bounds, int32_t* coeffs);
+/* numpy_to_pil's quantisation (pipeline.py:313-320 decode_latents + numpy_to_pil; Decoder.swift:40-68): image (B,3,H,W) f32 -> rgb8 (B,H,W,3) */
+int sd_op_image_rgb8(const float* image, uint8_t* rgb8, int B, int H, int W, int iters, float* ms);
+/* CLIPImageProcessor on 8-bit images (pipeline.py:288-291; SafetyChecker.swift:55-99): rgb8 (B,H,W,3) -> clip_input (B,3,S,S) f16
+ * through a resize to rh x rw; mean3 / std3: three floats each */
+int sd_op_clip_input(const uint8_t* rgb8, void* clip_input, int B, int H, int W, int rh, int rw, int S, const float* mean3,
+                     const float* std3, int iters, float* ms);
+
 #ifdef __cplusplus
 }
 #endif

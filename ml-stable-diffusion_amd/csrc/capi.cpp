@@ -5,6 +5,7 @@
 #include <cstdlib>
 
 #include "capi_util.h"
+#include "safety_checker.h"
 
 namespace sd {
 int selftest_mfma();   // selftest.hip
@@ -273,6 +274,15 @@ int sd_vae_decode(sd_unet* vae, const void* z, sd_dtype z_dtype, float* image, i
   return guarded([&] {
     SD_REQUIRE(vae && z && image, kInvalidArgument, "NULL argument");
     vae_of(vae, 1).decode(z, z_dtype == SD_F32, image, flags);
+  });
+}
+
+int sd_vae_decode_images(sd_unet* vae, const void* z, sd_dtype z_dtype, float* image, uint8_t* rgb8, sd_safety_checker* checker,
+                         const sd_image_post* post, float adjustment, float* has_nsfw, float* concept_scores, int flags) {
+  return guarded([&] {
+    SD_REQUIRE(vae && z, kInvalidArgument, "NULL argument");
+    vae_of(vae, 1).decode_images(z, z_dtype == SD_F32, image, rgb8, checker ? checker->impl.get() : nullptr, post, adjustment, has_nsfw,
+                                 concept_scores, flags);
   });
 }
 

@@ -1298,6 +1298,71 @@ int sd_op_sched_step(const float* noise_pred, float* latents, float* hist, const
   });
 }
 
+// Pillow's 8-bit bicubic coefficients of one axis (imgpost.hip resample_coeffs; host only): bounds (out_size, 2) = [xmin, n], coeffs
+// (out_size, *ksize), zeros behind the n taps of a row.  A NULL table pointer: the size query, *ksize alone.
+int sd_op_resample_coeffs(int in_size, int out_size, int* ksize, int32_t* bounds, int32_t* coeffs) {
+  return guarded([&] {
+    SD_REQUIRE(ksize, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(in_size >= 1 && out_size >= 1 && in_size <= (1 << 20) && out_size <= (1 << 20), kInvalidArgument, "resample_coeffs: %d -> %d",
+               in_size, out_size);
+    *ksize = resample_ksize(in_size, out_size);
+    if (bounds && coeffs) resample_coeffs(in_size, out_size, bounds, coeffs);
+  });
+}
+
+// imgpost.hip image_rgb8_kernel on host arrays: image (B, 3, H, W) f32 -> rgb8 (B, H, W, 3).  The device output sits in front of a
+// guard; both are filled with 0xa5 before the launch, and a launch that wrote into the guard fails the call.
+int sd_op_image_rgb8(const float* image, uint8_t* rgb8, int B, int H, int W, int iters, float* ms) {
+  return guarded([&] {
+    SD_REQUIRE(image && rgb8, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(B > 0 && H > 0 && W > 0, kInvalidArgument, "image_rgb8: B=%d H=%d W=%d", B, H, W);
+    Scratch sc;
+    const size_t n = (size_t)B * H * W * 3, guard = 4096;
+    float* din = sc.dev<float>(n, image);
+    uint8_t* dout = sc.dev<uint8_t>(n + guard);
+    SD_HIP(hipMemset(dout, 0xa5, n + guard));
+    sc.timed(iters, ms, [&] { launch_image_rgb8(din, dout, B, H, W, sc.stream); });
+    SD_HIP(hipStreamSynchronize(sc.stream));
+    std::vector<uint8_t> g(guard);
+    SD_HIP(hipMemcpy(g.data(), dout + n, guard, hipMemcpyDeviceToHost));
+    for (uint8_t v : g) SD_REQUIRE(v == 0xa5, kInternal, "image_rgb8 wrote behind its %zu output bytes", n);
+    SD_HIP(hipMemcpy(rgb8, dout, n, hipMemcpyDeviceToHost));
+  });
+}
+
+// imgpost.hip clip_input_kernel on host arrays: rgb8 (B, H, W, 3) -> clip_input (B, 3, S, S) f16.  The geometry is checked and the
+// tables are built on the host before any device work.  The device output sits in front of a guard; both are filled with NaN patterns
+// before the launch, and a launch that wrote into the guard fails the call.
+int sd_op_clip_input(const uint8_t* rgb8, void* clip_input, int B, int H, int W, int rh, int rw, int S, const float* mean3, const float* std3,
+                     int iters, float* ms) {
+  return guarded([&] {
+    SD_REQUIRE(rgb8 && clip_input && mean3 && std3, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(B > 0, kInvalidArgument, "clip_input: B=%d", B);
+    const ClipInputPlan plan = plan_clip_input(H, W, rh, rw, S);
+    ClipInputDesc d{};
+    for (int c = 0; c < 3; ++c) {
+      SD_REQUIRE(std3[c] != 0.f, kInvalidArgument, "clip_input: std[%d] is 0", c);
+      d.mean[c] = mean3[c], d.std[c] = std3[c];
+    }
+    Scratch sc;
+    d.hbounds = sc.dev<int32_t>(plan.hbounds.size(), plan.hbounds.data());
+    d.hcoeffs = sc.dev<int32_t>(plan.hcoeffs.size(), plan.hcoeffs.data());
+    d.vbounds = sc.dev<int32_t>(plan.vbounds.size(), plan.vbounds.data());
+    d.vcoeffs = sc.dev<int32_t>(plan.vcoeffs.size(), plan.vcoeffs.data());
+    d.H = H, d.W = W, d.S = S, d.top = (rh - S) / 2, d.left = (rw - S) / 2, d.ksh = plan.ksh, d.ksv = plan.ksv;
+    const size_t n = (size_t)B * 3 * S * S, guard = 4096;
+    uint8_t* din = sc.dev<uint8_t>((size_t)B * H * W * 3, rgb8);
+    half_t* dout = sc.dev<half_t>(n + guard);
+    SD_HIP(hipMemset(dout, 0xff, (n + guard) * sizeof(half_t)));   // 0xffff: a NaN
+    sc.timed(iters, ms, [&] { launch_clip_input(din, dout, B, d, plan.lds_bytes, sc.stream); });
+    SD_HIP(hipStreamSynchronize(sc.stream));
+    std::vector<uint16_t> g(guard);
+    SD_HIP(hipMemcpy(g.data(), dout + n, guard * sizeof(half_t), hipMemcpyDeviceToHost));
+    for (uint16_t v : g) SD_REQUIRE(v == 0xffff, kInternal, "clip_input wrote behind its %zu outputs", n);
+    SD_HIP(hipMemcpy(clip_input, dout, n * sizeof(half_t), hipMemcpyDeviceToHost));
+  });
+}
+
 // The safety checker's attention (vit.hip) on the layout its handle feeds it: qkv (B * S, 3 * heads * d) f16 rows [q | k | v] ->
 // out (B * S, heads * d) f16.  The device output sits in front of a guard of 64 rows; both are filled with NaN patterns before the
 // launch, and a launch that wrote into the guard fails the call.

@@ -476,6 +476,33 @@ void launch_cfg_sched_step(const float* noise_pred, float* latents, float* eps_h
 void launch_posterior_noise(const float* moments, const float* eps, const float* noise, float* out, size_t n, int n_images,
                             float scale, float sa, float sb, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------------
+// Image post-processing behind the VAE decoder (imgpost.hip; pipeline.py:286-320, Decoder.swift:40-68, SafetyChecker.swift:55-99)
+// ---------------------------------------------------------------------------------------------
+// image (B, 3, H, W) fp32 in [-1, 1] -> rgb8 (B, H, W, 3): (np.clip(image / 2 + 0.5, 0, 1) * 255).round().astype("uint8") bit for bit
+void launch_image_rgb8(const float* image, uint8_t* rgb8, int B, int H, int W, hipStream_t s);
+// Pillow's 8-bit bicubic resize coefficients of one axis (host): ksize taps per output sample; bounds (out, 2) = [xmin, n],
+// coeffs (out, ksize) fixed point with kResampleBits fraction bits, zeros behind the n taps of a row
+constexpr int kResampleBits = 22;
+int resample_ksize(int in_size, int out_size);
+void resample_coeffs(int in_size, int out_size, int32_t* bounds, int32_t* coeffs);
+// rgb8 (B, H, W, 3) -> clip_input (B, 3, S, S) fp16: resize to rh x rw (two passes, horizontal first, the intermediate image uint8),
+// centre crop to S x S, ((float)u / 255.0f - mean[c]) / std[c] with both divisions IEEE-rounded, rounded to fp16.
+// The tables of a geometry on the host (plan_clip_input: checks the geometry and the LDS it needs; no device work) ...
+struct ClipInputPlan {
+  int H = 0, W = 0, rh = 0, rw = 0, S = 0, ksh = 0, ksv = 0;
+  std::vector<int32_t> hbounds, hcoeffs, vbounds, vcoeffs;
+  size_t lds_bytes = 0;
+};
+ClipInputPlan plan_clip_input(int H, int W, int rh, int rw, int S);
+// ... and what a launch reads: the same tables in device memory
+struct ClipInputDesc {
+  const int32_t *hbounds, *hcoeffs, *vbounds, *vcoeffs;
+  int H, W, S, top, left, ksh, ksv;
+  float mean[3], std[3];
+};
+void launch_clip_input(const uint8_t* rgb8, half_t* out, int B, const ClipInputDesc& d, size_t lds_bytes, hipStream_t s);
+
 void launch_lds_poison(hipStream_t s);   // debug (SD_POISON_LDS): NaN patterns into every CU's LDS
 void launch_count_nonfinite_half(const void* p, size_t bytes, unsigned long long* out, hipStream_t s);   // debug scan (SD_NAN_TRACE)
 

@@ -6,6 +6,7 @@
 #include <cmath>
 
 #include "conv_plan.h"
+#include "safety_checker.h"
 
 namespace sd {
 
@@ -122,11 +123,8 @@ void Vae::build_decoder() {
   conv_small_n(ops, "decoder.conv_out", t, cfg_.out_channels, nullptr, image_);
 }
 
-// pipeline.py:313-320 hands z = latents / scaling_factor (fp16 or fp32); returns image in [-1, 1]
-void Vae::decode(const void* z, int z_is_f32, float* image, int flags) {
-  SD_HIP(hipSetDevice(ll_.device));
+void Vae::upload_latents(const void* z, int z_is_f32, bool dev) {
   hipStream_t stream = ll_.stream;
-  const bool dev = (flags & SD_FLAG_DEVICE_PTRS) != 0;
   const size_t n = (size_t)cfg_.batch * cfg_.in_channels * cfg_.height * cfg_.width;
   if (z_is_f32) {
     SD_HIP(hipMemcpyAsync(in_z_, z, n * 4, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
@@ -135,9 +133,96 @@ void Vae::decode(const void* z, int z_is_f32, float* image, int flags) {
     SD_HIP(hipMemcpyAsync(z_half_, z, n * 2, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
     launch_half_to_float(z_half_, in_z_, n, stream);
   }
+}
+
+// pipeline.py:313-320 hands z = latents / scaling_factor (fp16 or fp32); returns image in [-1, 1]
+void Vae::decode(const void* z, int z_is_f32, float* image, int flags) {
+  SD_HIP(hipSetDevice(ll_.device));
+  hipStream_t stream = ll_.stream;
+  const bool dev = (flags & SD_FLAG_DEVICE_PTRS) != 0;
+  upload_latents(z, z_is_f32, dev);
   run_forward();
   SD_HIP(hipMemcpyAsync(image, image_, image_elems_ * sizeof(float),
                         dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
+  SD_HIP(hipStreamSynchronize(stream));
+  have_inputs_ = true;
+}
+
+// pipeline.py:286-320 behind the decoder's launch list, without the detour through the host: numpy_to_pil's quantisation, then - with a
+// checker - CLIPImageProcessor's resize / crop / normalise, the checker itself (SafetyChecker::run on device pointers, in slices of its
+// static batch) and filtered_images (torch2coreml.py:1203-1207): the flagged images zeroed in both outputs.
+void Vae::decode_images(const void* z, int z_is_f32, float* image, uint8_t* rgb8, SafetyChecker* checker, const sd_image_post* post,
+                        float adjustment, float* has_nsfw, float* concept_scores, int flags) {
+  const int B = cfg_.batch, C = cfg_.out_channels;
+  const int H = cfg_.height << (cfg_.n_levels - 1), W = cfg_.width << (cfg_.n_levels - 1);   // n_levels - 1 upsamplers
+  SD_REQUIRE((flags & ~SD_FLAG_DEVICE_PTRS) == 0, kInvalidArgument, "unknown flags %d", flags);
+  SD_REQUIRE(C == 3 && image_elems_ == (size_t)B * 3 * H * W, kUnsupported, "decode_images: the decoder writes %zu floats, 8-bit RGB needs %d x 3 x %d x %d",
+             image_elems_, B, H, W);
+  // everything that can be refused is refused here, before any device work
+  ClipInputPlan plan;
+  int cb = 0, S = 0, NC = 0;
+  if (checker) {
+    const sd_safety_checker_config& cc = checker->config();
+    cb = cc.batch, S = cc.image_size, NC = cc.num_concepts;
+    SD_REQUIRE(post != nullptr, kInvalidArgument, "decode_images: a checker needs the sd_image_post that describes its input");
+    SD_REQUIRE(B % cb == 0, kInvalidArgument, "decode_images: the decoder's batch %d is no multiple of the safety checker's %d", B, cb);
+    SD_REQUIRE(checker->device_index() == ll_.device, kInvalidArgument, "decode_images: the decoder is on device %d, the safety checker on %d",
+               ll_.device, checker->device_index());
+    for (int c = 0; c < 3; ++c)
+      SD_REQUIRE(post->image_std[c] != 0.f, kInvalidArgument, "decode_images: image_std[%d] is 0", c);
+    if (post->resize_h != post_rh_ || post->resize_w != post_rw_ || S != post_S_) plan = plan_clip_input(H, W, post->resize_h, post->resize_w, S);
+  }
+  SD_HIP(hipSetDevice(ll_.device));
+  hipStream_t stream = ll_.stream;
+  const bool dev = (flags & SD_FLAG_DEVICE_PTRS) != 0;
+  const hipMemcpyKind out_kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  const size_t px = (size_t)H * W;
+  upload_latents(z, z_is_f32, dev);
+  run_forward();
+  if (rgb8 || checker) {
+    if (!rgb8_) rgb8_ = ll_.arena.alloc_n<uint8_t>((size_t)B * px * 3);
+    launch_image_rgb8(image_, rgb8_, B, H, W, stream);
+  }
+  if (checker) {
+    if (plan.S) {   // a new geometry: its tables into the arena
+      auto up = [&](const std::vector<int32_t>& v) {
+        int32_t* d = ll_.arena.alloc_n<int32_t>(v.size());
+        SD_HIP(hipMemcpyAsync(d, v.data(), v.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+        return d;
+      };
+      post_desc_.hbounds = up(plan.hbounds), post_desc_.hcoeffs = up(plan.hcoeffs);
+      post_desc_.vbounds = up(plan.vbounds), post_desc_.vcoeffs = up(plan.vcoeffs);
+      SD_HIP(hipStreamSynchronize(stream));   // `plan` lives on this frame
+      post_desc_.H = H, post_desc_.W = W, post_desc_.S = S;
+      post_desc_.top = (plan.rh - S) / 2, post_desc_.left = (plan.rw - S) / 2;
+      post_desc_.ksh = plan.ksh, post_desc_.ksv = plan.ksv;
+      post_lds_ = plan.lds_bytes;
+      post_rh_ = plan.rh, post_rw_ = plan.rw, post_S_ = S;
+    }
+    const size_t per_image = (size_t)3 * S * S;
+    if (clip_input_cap_ < B * per_image) {
+      clip_input_ = ll_.arena.alloc_n<half_t>(B * per_image);
+      clip_input_cap_ = B * per_image;
+    }
+    ClipInputDesc d = post_desc_;
+    for (int c = 0; c < 3; ++c) d.mean[c] = post->image_mean[c], d.std[c] = post->image_std[c];
+    launch_clip_input(rgb8_, clip_input_, B, d, post_lds_, stream);
+    SD_HIP(hipStreamSynchronize(stream));   // the checker runs on its own stream
+    std::vector<float> verdict(B);
+    for (int i = 0; i < B; i += cb)
+      checker->run(clip_input_ + i * per_image, adjustment, verdict.data() + i, concept_scores ? concept_scores + (size_t)i * NC : nullptr,
+                   nullptr, nullptr, SD_FLAG_DEVICE_PTRS);
+    SD_HIP(hipSetDevice(ll_.device));
+    for (int i = 0; i < B; ++i) {
+      if (has_nsfw) has_nsfw[i] = verdict[i];
+      if (verdict[i] > 0.5f) {   // the next forward rewrites image_, so zeroing it in place loses nothing
+        if (image) SD_HIP(hipMemsetAsync(image_ + i * px * 3, 0, px * 3 * sizeof(float), stream));
+        if (rgb8) SD_HIP(hipMemsetAsync(rgb8_ + i * px * 3, 0, px * 3, stream));
+      }
+    }
+  }
+  if (image) SD_HIP(hipMemcpyAsync(image, image_, image_elems_ * sizeof(float), out_kind, stream));
+  if (rgb8) SD_HIP(hipMemcpyAsync(rgb8, rgb8_, (size_t)B * px * 3, out_kind, stream));
   SD_HIP(hipStreamSynchronize(stream));
   have_inputs_ = true;
 }

@@ -61,6 +61,11 @@ class SafetyCheckerConfig(C.Structure):
                 ("layer_norm_eps", C.c_float), ("use_graph", C.c_int32)]
 
 
+class ImagePost(C.Structure):
+    """sd_image_post: what CLIPImageProcessor resolves to for one image size (safety_checker.image_post builds it)."""
+    _fields_ = [("resize_h", C.c_int32), ("resize_w", C.c_int32), ("image_mean", C.c_float * 3), ("image_std", C.c_float * 3)]
+
+
 class TextEncoderConfig(C.Structure):
     _fields_ = [("vocab_size", C.c_int32), ("hidden_size", C.c_int32), ("intermediate_size", C.c_int32),
                 ("num_hidden_layers", C.c_int32), ("num_attention_heads", C.c_int32),
@@ -162,6 +167,10 @@ SYMBOLS = [
     ("sd_safety_checker_run", _I, [_P, _P, _F, _FP, _FP, _FP, _FP, _I]),
     ("sd_op_vit_attention", _I, [_P, _P, _I, _I, _I, _I, _I, _FP]),
     ("sd_op_safety_head", _I, [_FP, _FP, _FP, _FP, _FP, _F, _I, _I, _I, _I, _FP, _FP]),
+    ("sd_vae_decode_images", _I, [_P, _P, _I, _FP, _P, _P, C.POINTER(ImagePost), _F, _FP, _FP, _I]),
+    ("sd_op_resample_coeffs", _I, [_I, _I, C.POINTER(_I), _P, _P]),
+    ("sd_op_image_rgb8", _I, [_FP, _P, _I, _I, _I, _I, _FP]),
+    ("sd_op_clip_input", _I, [_P, _P, _I, _I, _I, _I, _I, _I, _FP, _FP, _I, _FP]),
 ]
 
 
@@ -315,6 +324,50 @@ def safety_head(image_embeds, concept_embeds, special_embeds, concept_w, special
     check(lib().sd_op_safety_head(fptr(image_embeds), fptr(concept_embeds), fptr(special_embeds), fptr(concept_w), fptr(special_w),
                                   float(adjustment), B, P, nc, ns, fptr(flags), fptr(scores)))
     return flags > 0.5, scores
+
+
+def resample_coeffs(in_size, out_size):
+    """Pillow's 8-bit bicubic coefficient tables of one axis (sd_op_resample_coeffs; host only): (ksize, bounds (out_size, 2) int32 =
+    [xmin, n], coeffs (out_size, ksize) int32 with 22 fraction bits, zeros behind the n taps of a row)."""
+    ksize = C.c_int(0)
+    check(lib().sd_op_resample_coeffs(int(in_size), int(out_size), C.byref(ksize), None, None))
+    bounds = np.zeros((out_size, 2), np.int32)
+    coeffs = np.zeros((out_size, ksize.value), np.int32)
+    check(lib().sd_op_resample_coeffs(int(in_size), int(out_size), C.byref(ksize), ptr(bounds), ptr(coeffs)))
+    return ksize.value, bounds, coeffs
+
+
+def image_rgb8(image, iters=1):
+    """numpy_to_pil's quantisation on the GPU (csrc/imgpost.hip image_rgb8_kernel): image (B, 3, H, W) f32 in [-1, 1] ->
+    ((np.clip(image / 2 + 0.5, 0, 1) * 255).round().astype("uint8") as (B, H, W, 3), ms)."""
+    image = f32(image)
+    if image.ndim != 4 or image.shape[1] != 3:
+        raise ValueError("image_rgb8: image must be (B, 3, H, W)")
+    B, _, H, W = image.shape
+    out = np.empty((B, H, W, 3), np.uint8)
+    ms = C.c_float(0)
+    check(lib().sd_op_image_rgb8(fptr(image), ptr(out), B, H, W, iters, C.byref(ms)))
+    return out, ms.value
+
+
+def clip_input(rgb8, rh, rw, S, mean, std, out=None, iters=1):
+    """CLIPImageProcessor on the GPU (csrc/imgpost.hip clip_input_kernel): rgb8 (B, H, W, 3) uint8 -> Pillow's 8-bit bicubic resize to
+    (rh, rw), centre crop to S x S, (u / 255 - mean) / std in fp32, as (clip_input (B, 3, S, S) f16, ms).  ``out``: a C-contiguous
+    float16 buffer of at least B * 3 * S * S elements to write into (tests put a guard behind it).  A geometry the kernel does not
+    express is refused by the library before any device work (ValueError / NotImplementedError)."""
+    rgb8 = np.ascontiguousarray(rgb8, dtype=np.uint8)
+    mean, std = f32(mean), f32(std)
+    if rgb8.ndim != 4 or rgb8.shape[3] != 3 or mean.shape != (3,) or std.shape != (3,):
+        raise ValueError("clip_input: rgb8 must be (B, H, W, 3), mean and std three floats each")
+    B, H, W, _ = rgb8.shape
+    n = B * 3 * S * S
+    if out is None:
+        out = np.empty(n, np.float16)
+    if out.dtype != np.float16 or not out.flags.c_contiguous or out.size < n:
+        raise ValueError("clip_input: out must be a C-contiguous float16 buffer of at least B * 3 * S * S elements")
+    ms = C.c_float(0)
+    check(lib().sd_op_clip_input(ptr(rgb8), ptr(out), B, H, W, int(rh), int(rw), int(S), fptr(mean), fptr(std), iters, C.byref(ms)))
+    return out.reshape(-1)[:n].reshape(B, 3, S, S), ms.value
 
 
 def layernorm(x, weight, bias, eps=1e-5, iters=1):

@@ -548,6 +548,30 @@ class HipVaeDecoder(_lib.Model):
                                             _lib.fptr(image), 0))
         return {"image": image}
 
+    def decode_images(self, z, safety_checker=None, image_post=None, adjustment=0.0, want_image=True, want_rgb8=True):
+        """The decoder, then the image post-processing and the safety checker without leaving the device (sd_vae_decode_images;
+        pipeline.py:286-320): returns ``{"image"`` (B, 3, H, W) f32 in [-1, 1] ``, "rgb8"`` (B, H, W, 3) uint8 - what
+        ``numpy_to_pil`` makes of it - ``, "has_nsfw_concepts"`` (B,) bool ``, "concept_scores"`` (B, n) f32 ``}``; an output that was
+        not asked for (``want_image`` / ``want_rgb8`` False, no ``safety_checker``) is None.  The flagged images come back zeroed in
+        ``image`` and ``rgb8``.  ``safety_checker``: a ``HipSafetyChecker`` whose static batch divides this decoder's, on the same
+        device; it needs ``image_post`` (``safety_checker.image_post(...)``: the checkpoint's CLIPImageProcessor for this image size)."""
+        self._verify_inputs(z=z)
+        z = np.ascontiguousarray(z)
+        if safety_checker is not None and not isinstance(image_post, _lib.ImagePost):
+            raise ValueError("decode_images: a safety checker needs image_post (safety_checker.image_post(...))")
+        B, _, H, W = self.image_shape
+        image = np.empty(self.image_shape, np.float32) if want_image else None
+        rgb8 = np.empty((B, H, W, 3), np.uint8) if want_rgb8 else None
+        flags = scores = None
+        if safety_checker is not None:
+            flags = np.empty(B, np.float32)
+            scores = np.empty((B, safety_checker._cfg_struct.num_concepts), np.float32)
+        _lib.check(_lib.lib().sd_vae_decode_images(
+            self._h, _lib.ptr(z), 1 if z.dtype == np.float32 else 0, _lib.fptr(image), _lib.ptr(rgb8),
+            safety_checker._h if safety_checker is not None else None, C.byref(image_post) if safety_checker is not None else None,
+            float(adjustment), _lib.fptr(flags), _lib.fptr(scores), 0))
+        return {"image": image, "rgb8": rgb8, "has_nsfw_concepts": None if flags is None else flags > 0.5, "concept_scores": scores}
+
     def profile(self, iters=5):
         return _profile(self._h, iters)
 

@@ -29,6 +29,9 @@ tensor hand-offs to the model runners; ``get_hip_pipe`` / ``main`` mirror ``get_
     :260-263): ``progress_handler(PipelineProgress)`` runs after every ``progress_steps``-th step, gets the latents or the scheduler's
     de-noised estimate with lazily decoded preview images, and stops the generation by returning False.  Unlike ``callback`` it
     keeps the loop device-resident: the handler runs between two graph replays of ``sd_unet_denoise_loop_progress``;
+  * ``device_postprocess`` (CLI ``--device-postprocess``; off by default): the final decode and every preview go from the
+    decoder's last conv to the 8-bit image and the safety verdict on the device (``sd_vae_decode_images``, csrc/imgpost.hip) instead of
+    through numpy, PIL and CLIPImageProcessor on the host (pipeline.py:286-320); the results are bit for bit the host route's;
   * ``--attention-implementation`` is a run-time flag of ``main`` (a conversion-time flag in the
     reference, torch2coreml.py:1678-1685).
 """
@@ -66,8 +69,11 @@ class PipelineProgress:
         if self._images is None:
             if self.pipeline.vae_decoder is None:
                 raise ValueError("current_images needs a pipeline with a VAE decoder")
-            image, _ = self.pipeline.run_safety_checker(self.pipeline.decode_latents(self.current_latent_samples))
-            self._images = self.pipeline.numpy_to_pil(image) if self._output_type == "pil" else image
+            if self.pipeline.device_postprocess:
+                self._images, _ = self.pipeline.decode_images_on_device(self.current_latent_samples, self._output_type)
+            else:
+                image, _ = self.pipeline.run_safety_checker(self.pipeline.decode_latents(self.current_latent_samples))
+                self._images = self.pipeline.numpy_to_pil(image) if self._output_type == "pil" else image
         return self._images
 
 
@@ -75,7 +81,7 @@ class HipStableDiffusionPipeline:
     def __init__(self, text_encoder, unet, vae_decoder, scheduler, tokenizer, controlnet=None, xl=False,
                  force_zeros_for_empty_prompt=True, feature_extractor=None, safety_checker=None,
                  text_encoder_2=None, tokenizer_2=None, vae_scaling_factor=None, unet_refiner=None,
-                 refiner_start=0.8, aesthetic_score=6.0, negative_aesthetic_score=2.5, vae_encoder=None):
+                 refiner_start=0.8, aesthetic_score=6.0, negative_aesthetic_score=2.5, vae_encoder=None, device_postprocess=False):
         self.text_encoder, self.text_encoder_2 = text_encoder, text_encoder_2
         self.tokenizer, self.tokenizer_2 = tokenizer, tokenizer_2
         self.unet, self.vae_decoder, self.scheduler = unet, vae_decoder, scheduler
@@ -98,6 +104,25 @@ class HipStableDiffusionPipeline:
         self.height = latent_h * VAE_DECODER_UPSAMPLE_FACTOR
         self.width = latent_w * VAE_DECODER_UPSAMPLE_FACTOR
         logger.info("Stable Diffusion configured to generate %dx%d images", self.height, self.width)
+        self.device_postprocess, self._image_post = bool(device_postprocess), None
+        if self.device_postprocess:
+            self._image_post = self._check_device_postprocess()
+
+    def _check_device_postprocess(self):
+        """``device_postprocess`` drives library handles: anything else is refused here, not worked around later."""
+        from .hip_model import HipVaeDecoder
+        from .safety_checker import HipSafetyChecker, image_post
+        if not isinstance(self.vae_decoder, HipVaeDecoder):
+            raise ValueError(f"device_postprocess needs a HipVaeDecoder handle, got {type(self.vae_decoder).__name__}")
+        if self.safety_checker is None:
+            return None
+        if not isinstance(self.safety_checker, HipSafetyChecker):
+            raise ValueError(f"device_postprocess needs a HipSafetyChecker handle (or no checker), got {type(self.safety_checker).__name__}")
+        if self.vae_decoder.batch % self.safety_checker.batch:
+            raise ValueError(f"device_postprocess: the VAE decoder's static batch of {self.vae_decoder.batch} is no multiple of the "
+                             f"safety checker's {self.safety_checker.batch}")
+        _, _, h, w = self.vae_decoder.image_shape
+        return image_post(self.feature_extractor, h, w, self.safety_checker.image_size)
 
     # ---- pipeline.py:123-257 ---------------------------------------------------------------
     def _encode_prompt(self, prompt, prompt_2=None, do_classifier_free_guidance=True, negative_prompt=None,
@@ -193,6 +218,31 @@ class HipStableDiffusionPipeline:
                                 for i in range(0, latents.shape[0], vb)])
         image = np.clip(image / 2 + 0.5, 0, 1)
         return image.transpose((0, 2, 3, 1))
+
+    def decode_images_on_device(self, latents, output_type):
+        """decode_latents + run_safety_checker (+ numpy_to_pil) through ``HipVaeDecoder.decode_images``: (images, has_nsfw).
+        ``output_type="pil"``: PIL images straight from the device's 8-bit image, no fp32 read-back; else the float images (n, H, W, 3)
+        in [0, 1], computed from the decoder's output as decode_latents does.  Flagged images are black either way."""
+        latents = 1 / self.vae_scaling_factor * latents
+        dtype = self.vae_decoder.expected_inputs["z"]["dtype"]
+        vb = self.vae_decoder.expected_inputs["z"]["shape"][0]
+        if latents.shape[0] % vb:
+            raise ValueError(f"{latents.shape[0]} latents do not fill the VAE decoder's static batch of {vb}")
+        pil = output_type == "pil"
+        outs = [self.vae_decoder.decode_images(np.ascontiguousarray(latents[i:i + vb]).astype(dtype), self.safety_checker,
+                                               self._image_post, want_image=not pil, want_rgb8=pil)
+                for i in range(0, latents.shape[0], vb)]
+        has_nsfw = None
+        if self.safety_checker is not None:
+            has_nsfw = np.concatenate([o["has_nsfw_concepts"] for o in outs])
+            logger.info("Generated image has nsfw concept=%s", bool(has_nsfw.any()))
+        if pil:
+            from PIL import Image
+            return [Image.fromarray(im) for o in outs for im in o["rgb8"]], has_nsfw
+        image = np.clip(np.concatenate([o["image"] for o in outs]) / 2 + 0.5, 0, 1).transpose((0, 2, 3, 1))
+        if has_nsfw is not None:
+            image[has_nsfw] = 0                              # the library zeroed them in [-1, 1], which is mid-grey here
+        return image, has_nsfw
 
     # ---- pipeline.py:322-344 ---------------------------------------------------------------
     def prepare_latents(self, batch_size, num_channels_latents, height, width, latents=None, seed=None, rng="numpy"):
@@ -509,10 +559,12 @@ class HipStableDiffusionPipeline:
                                   cancelled=True)
         if output_type == "latent" or self.vae_decoder is None:
             image, has_nsfw = latents, None                  # the checker looks at images only
+        elif self.device_postprocess:
+            image, has_nsfw = self.decode_images_on_device(latents, output_type)
         else:
             image = self.decode_latents(latents)
             image, has_nsfw = self.run_safety_checker(image)
-        if output_type == "pil" and image.ndim == 4 and image.shape[-1] == 3:
+        if output_type == "pil" and not isinstance(image, list) and image.ndim == 4 and image.shape[-1] == 3:
             image = self.numpy_to_pil(image)
         if not return_dict:
             return image, has_nsfw
@@ -571,7 +623,7 @@ def get_hip_pipe(model_dir, model_version, compute_unit="ALL", scheduler_overrid
                  force_zeros_for_empty_prompt=True, sources=None, attention_implementation="SPLIT_EINSUM",
                  num_images=1, guidance_scale=7.5, unet_batch_one=False, latent_size=None, device=0,
                  refiner_dir=None, tokenizer_factory=None, text_encoder_factory=None, vae_dtype=None, disable_safety=False,
-                 vae_encoder=False, quantize_nbits=None, palettization_recipe=None):
+                 vae_encoder=False, quantize_nbits=None, palettization_recipe=None, device_postprocess=False):
     """``get_coreml_pipe`` (pipeline.py:607-697) without the conversion step: ``model_dir`` is a diffusers
     checkpoint directory (``unet/``, ``vae/``, ``text_encoder/``, ``tokenizer/``, ``scheduler/`` [,
     ``text_encoder_2/``, ``tokenizer_2/``]) instead of a folder of ``.mlpackage`` files; ControlNets are
@@ -588,7 +640,8 @@ def get_hip_pipe(model_dir, model_version, compute_unit="ALL", scheduler_overrid
     the refiner UNet and the ControlNets at load time (torch2coreml.py:182-229 ``quantize_weights`` names exactly these models;
     mixed_bit_compression_apply.py); the text encoder, the VAE and the safety checker stay as they are.  A recipe is the UNet's: a
     module of it that the UNet lacks raises ``KeyError``; the ControlNets and the refiner take the modules they share with it (a
-    ControlNet has the UNet's down and mid blocks) and leave the rest of their weights fp16."""
+    ControlNet has the UNet's down and mid blocks) and leave the rest of their weights fp16.
+    ``device_postprocess``: the 8-bit image and the safety checker's input are made on the device (``HipStableDiffusionPipeline``)."""
     if not os.path.isdir(model_dir):
         raise FileNotFoundError(f"{model_dir} not found (coreml_model.py:176-178)")
     from . import text_encoder as te
@@ -655,7 +708,7 @@ def get_hip_pipe(model_dir, model_version, compute_unit="ALL", scheduler_overrid
             os.path.join(model_dir, "safety_checker"), batch=1, device=device,
             image_height=lat * VAE_DECODER_UPSAMPLE_FACTOR, image_width=kwargs["unet"].latent_width * VAE_DECODER_UPSAMPLE_FACTOR)
     logger.info("Initializing HIP pipe for image generation")
-    return HipStableDiffusionPipeline(scheduler=scheduler, **kwargs)
+    return HipStableDiffusionPipeline(scheduler=scheduler, device_postprocess=device_postprocess, **kwargs)
 
 
 def get_image_path(args, **override_kwargs):
@@ -736,6 +789,9 @@ def build_parser():
     parser.add_argument("--save-every", default=0, type=int,                                      # swift/StableDiffusionCLI/main.swift:57-63
                         help="Save the preview image of every n-th step next to the final image, as <final name>.step<i>.png; "
                              "0 = the final image only")
+    parser.add_argument("--device-postprocess", action="store_true",
+                        help="Make the 8-bit image and the safety checker's input on the GPU, behind the VAE decoder, instead of in "
+                             "numpy / PIL / CLIPImageProcessor on the host; same images and verdicts, bit for bit.")
     parser.add_argument("--quantize-nbits", default=None, choices=(1, 2, 4, 6, 8), type=int,       # torch2coreml.py:1705
                         help="If specified, the UNet / refiner / ControlNet weights are palettized to this many bits at load time "
                              "(k-means LUT per tensor; the conversion-time flag of torch2coreml.py)")
@@ -767,7 +823,8 @@ def main(args):
                         sources=args.model_sources, attention_implementation=args.attention_implementation,
                         guidance_scale=args.guidance_scale, unet_batch_one=args.unet_batch_one, refiner_dir=args.refiner,
                         disable_safety=getattr(args, "disable_safety", False), vae_encoder=bool(getattr(args, "image", None)),
-                        quantize_nbits=getattr(args, "quantize_nbits", None), palettization_recipe=recipe)
+                        quantize_nbits=getattr(args, "quantize_nbits", None), palettization_recipe=recipe,
+                        device_postprocess=getattr(args, "device_postprocess", False))
     controlnet_cond = None
     if args.controlnet:
         controlnet_cond = [prepare_controlnet_cond(args.controlnet_inputs[i], pipe.height, pipe.width)

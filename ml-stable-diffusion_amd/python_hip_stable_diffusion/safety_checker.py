@@ -51,6 +51,58 @@ def load_feature_extractor(folder):
     return CLIPImageProcessor(**{k: cfg[k] for k in keys if k in cfg})
 
 
+def image_post(feature_extractor, height, width, image_size):
+    """``_lib.ImagePost`` for images of ``height`` x ``width`` and a checker of ``image_size``: the size CLIPImageProcessor resizes
+    them to (``{"shortest_edge": s}`` or a legacy integer: the short side becomes s, the long side ``int(s * long / short)``;
+    ``{"height", "width"}``: those) and the fp32 roundings of its ``image_mean`` / ``image_std``.  A processor the device kernels
+    (csrc/imgpost.hip) do not express is refused with ValueError, not worked around: a resample filter other than BICUBIC, any of
+    do_resize / do_center_crop / do_rescale / do_normalize off, a rescale factor other than 1 / 255, a crop size other than the
+    checker's input, a resized image smaller than the crop (transformers would zero-pad)."""
+    fe = feature_extractor
+    for flag in ("do_resize", "do_center_crop", "do_rescale", "do_normalize"):
+        if not getattr(fe, flag, False):
+            raise ValueError(f"device post-processing needs a feature extractor with {flag}=True")
+    if int(getattr(fe, "resample", 0) or 0) != 3:
+        raise ValueError(f"device post-processing implements PIL's BICUBIC (resample=3), the feature extractor has {fe.resample!r}")
+    if float(fe.rescale_factor) != 1 / 255:
+        raise ValueError(f"device post-processing rescales by 1/255, the feature extractor by {fe.rescale_factor!r}")
+
+    def size_dict(v):
+        if v is None or isinstance(v, (int, np.integer)):
+            return v
+        return {k: v[k] for k in ("shortest_edge", "height", "width", "longest_edge", "max_height", "max_width") if v.get(k) is not None}
+
+    S = int(image_size)
+    crop = size_dict(fe.crop_size)
+    if isinstance(crop, (int, np.integer)):
+        crop = {"height": int(crop), "width": int(crop)}
+    if crop != {"height": S, "width": S}:
+        raise ValueError(f"the feature extractor crops to {crop}, the safety checker takes {S}x{S} images")
+    size = size_dict(fe.size)
+    height, width = int(height), int(width)
+    if isinstance(size, (int, np.integer)):
+        size = {"shortest_edge": int(size)}
+    if set(size) == {"shortest_edge"}:
+        s = int(size["shortest_edge"])
+        short, long = (width, height) if width <= height else (height, width)
+        new_long = int(s * long / short)
+        rh, rw = (new_long, s) if width <= height else (s, new_long)
+    elif set(size) == {"height", "width"}:
+        rh, rw = int(size["height"]), int(size["width"])
+    else:
+        raise ValueError(f"device post-processing resolves size={{'shortest_edge'}} or {{'height', 'width'}}, the feature extractor has {size}")
+    if rh < S or rw < S:
+        raise ValueError(f"the feature extractor resizes {height}x{width} images to {rh}x{rw}, smaller than the {S}x{S} crop "
+                         "(transformers would zero-pad)")
+    mean, std = np.asarray(fe.image_mean, np.float32), np.asarray(fe.image_std, np.float32)
+    if mean.shape != (3,) or std.shape != (3,) or not (std != 0).all():
+        raise ValueError("device post-processing needs three image_mean and three non-zero image_std values")
+    post = _lib.ImagePost()
+    post.resize_h, post.resize_w = rh, rw
+    post.image_mean[:], post.image_std[:] = [float(v) for v in mean], [float(v) for v in std]
+    return post
+
+
 def blacken(images, has_nsfw):
     """``filtered_images``: a copy of ``images`` (B, H, W, 3) with every flagged image zeroed (torch2coreml.py:1203-1207)."""
     images = np.asarray(images)
