@@ -278,6 +278,13 @@ int sd_vae_encode(sd_unet* vae, const void* x, sd_dtype x_dtype, float* moments,
  * at the first timestep of the truncated schedule.  Host pointers unless SD_FLAG_DEVICE_PTRS. */
 int sd_vae_encode_latents(sd_unet* vae_encoder, const void* x, sd_dtype x_dtype, const float* eps, const float* noise, int n_images,
                           float scale_factor, float sa, float sb, float* latents, int flags);
+/* operator-level entry, same conventions as the other sd_op_* (host pointers, iters, ms): the single-head mid-block attention of
+ * AutoencoderKL, out = softmax(q k^T / sqrt(C)) v with head dim = C over S = h * w tokens, as ONE streaming launch with no S x S
+ * buffer - diffusers' mid-block attention inside the reference's VAE wrappers (torch2coreml.py:584-594 decoder, :739-749 encoder;
+ * Decoder.swift, Encoder.swift).  q / k / v / out: (B*S, C) f16 token-major rows, as the 1x1 projections write them; any S >= 1.
+ * Checked on the host before any device work, in this order: NULL arguments or B, S, C < 1 -> SD_ERR_INVALID_ARGUMENT; C not in
+ * {64, 128, 256, 512} -> SD_ERR_UNSUPPORTED.  fp16 VAE handles run this kernel where H*W > 8192 or H*W % 64 != 0. */
+int sd_op_vae_attention(const void* q, const void* k, const void* v, void* out, int B, int S, int C, int iters, float* ms);
 
 /* ------------------------------------------------------------------------------------------
  * CLIP text encoder(s): transformers' CLIPTextModel / CLIPTextModelWithProjection as the reference

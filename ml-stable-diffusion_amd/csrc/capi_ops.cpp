@@ -1386,6 +1386,31 @@ int sd_op_vit_attention(const void* qkv, void* out, int B, int S, int heads, int
   });
 }
 
+// The VAE's mid-block attention (vae_attention.hip) on the layout its handle feeds it: q / k / v (B * S, C) f16 -> out (B * S, C) f16.
+// Everything that can be refused is refused before any device work.  The device output sits in front of a guard of 64 rows; both are
+// filled with NaN patterns before the launch, and a launch that wrote into the guard fails the call.
+int sd_op_vae_attention(const void* q, const void* k, const void* v, void* out, int B, int S, int C, int iters, float* ms) {
+  return guarded([&] {
+    SD_REQUIRE(q && k && v && out, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(B > 0 && S > 0 && C > 0, kInvalidArgument, "empty attention problem");
+    SD_REQUIRE(vae_attention_ok(C), kUnsupported, "vae_attention: head dim %d (the kernel is built for 64, 128, 256 and 512)", C);
+    SD_REQUIRE(B <= 65535, kInvalidArgument, "vae_attention: B=%d", B);
+    Scratch sc;
+    const size_t n = (size_t)B * S * C, guard = (size_t)64 * C;
+    half_t* dq = sc.dev<half_t>(n, f16(q));
+    half_t* dk = sc.dev<half_t>(n, f16(k));
+    half_t* dv = sc.dev<half_t>(n, f16(v));
+    half_t* dout = sc.dev<half_t>(n + guard);
+    SD_HIP(hipMemset(dout, 0xff, (n + guard) * sizeof(half_t)));   // 0xffff: a NaN
+    sc.timed(iters, ms, [&] { launch_vae_attention(dq, dk, dv, dout, B, S, C, sc.stream); });
+    SD_HIP(hipStreamSynchronize(sc.stream));
+    std::vector<uint16_t> g(guard);
+    SD_HIP(hipMemcpy(g.data(), dout + n, guard * sizeof(half_t), hipMemcpyDeviceToHost));
+    for (uint16_t x : g) SD_REQUIRE(x == 0xffff, kInternal, "vae_attention wrote behind its %d output rows", B * S);
+    SD_HIP(hipMemcpy(out, dout, n * sizeof(half_t), hipMemcpyDeviceToHost));
+  });
+}
+
 // The safety checker's concept head (vit.hip safety_head_kernel) on host fp32 arrays
 int sd_op_safety_head(const float* image_embeds, const float* concept_embeds, const float* special_embeds, const float* concept_w,
                       const float* special_w, float adjustment, int B, int P, int n_concepts, int n_special, float* has_nsfw,

@@ -358,6 +358,11 @@ void launch_clip_attention(const half_t* qkv, half_t* out, int S, int D, int hea
 // workgroup per (batch, head, 64 queries), any S >= 1, d^-0.5 applied in fp32 inside; d must be 64 (else kUnsupported)
 bool vit_attention_ok(int d);
 void launch_vit_attention(const half_t* qkv, half_t* out, int B, int S, int heads, int d, hipStream_t s);
+// AutoencoderKL mid-block attention (vae_attention.hip): one head of width C over S tokens, q / k / v / out [B * S][C] token-major, one
+// workgroup per (batch, 64 queries), keys streamed through LDS, no S x S buffer; any S >= 1, C^-0.5 applied in fp32 inside; C must be
+// 64, 128, 256 or 512 (else kUnsupported)
+bool vae_attention_ok(int C);
+void launch_vae_attention(const half_t* q, const half_t* k, const half_t* v, half_t* out, int B, int S, int C, hipStream_t s);
 // img (B, 3, I, I) NCHW -> rows [B * (I / p)^2][Kp], column c * p * p + py * p + px (the flattened conv weight's order), columns
 // [3 p p, Kp) zero: the patch-embedding conv becomes a 1x1 GEMM over these rows
 void launch_vit_patch_rows(const half_t* img, half_t* rows, int B, int I, int p, int Kp, hipStream_t s);

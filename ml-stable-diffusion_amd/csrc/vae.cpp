@@ -19,8 +19,12 @@ Vae::Vae(const sd_unet_config& cfg, const WeightStore& ws, int device) : Net(cfg
   seal();
 }
 
-// AutoencoderKL mid-block attention: single head over H*W tokens, d = C (too wide for the streaming kernel's
-// register budget): scores and P are materialised per image (S x S fp16) through the GEMM kernel.
+// AutoencoderKL mid-block attention: single head over S = H*W tokens, head dim = C (512 for every SD / SDXL VAE).  Two fp16 routes:
+//   S <= 8192 and S % 64 == 0   scores and P materialised per image (S x S fp16) through the GEMM kernel and the row softmax,
+//                               three launches per image - every size the benchmarks and goldens were recorded at
+//   any other S                 vae_attention.hip: one streaming launch for the whole batch, no score matrix and no V^T copy
+//                               (768^2 / 1024^2 images: S = 9216 / 16384; 480^2: S = 3600)
+// fp32 handles keep the materialised fp32 steps at any S.
 Tensor Vae::attention(std::vector<Op>& ops, const std::string& p, const Tensor& h) {
   const int B = h.B, H = h.H, W = h.W, C = h.C, S = H * W;
   Tensor t0 = group_norm(ops, p + ".group_norm", h, nullptr, 1e-6f, false);
@@ -54,10 +58,18 @@ Tensor Vae::attention(std::vector<Op>& ops, const std::string& p, const Tensor& 
     }
     return conv(ops, p + ".to_out.0", a, {.cout = C, .res = h.p});
   }
-  const int ldv = round_up(S, 8);
-  Tensor vt = conv(ops, p + ".to_v", t0, {.cout = C, .out_mode = kOutHalfT, .ldT = ldv});
-  SD_REQUIRE(C % 64 == 0 && S % 64 == 0, kUnsupported, "VAE attention needs C %% 64 == 0 and H*W %% 64 == 0");
-  SD_REQUIRE(ldv == S, kUnsupported, "VAE attention needs H*W %% 8 == 0");
+  if (S > 8192 || S % 64 != 0) {   // what the materialised route cannot take: the streaming kernel, one op for the whole batch
+    SD_REQUIRE(vae_attention_ok(C), kUnsupported,
+               "VAE attention over %d tokens: mid-block width %d (the streaming kernel is built for head dims 64, 128, 256 and 512)", S, C);
+    Tensor v = conv(ops, p + ".to_v", t0, {.cout = C});
+    Tensor a = new_tensor(B, H, W, C);
+    ops.push_back([=](hipStream_t s) { launch_vae_attention(q.p, k.p, v.p, a.p, B, S, C, s); });
+    ops.back().label = "VAE attention: streaming QK^T + softmax + PV, one launch, S=" + std::to_string(S);
+    ops.back().flop = 4.0 * (double)S * S * C * B;
+    return conv(ops, p + ".to_out.0", a, {.cout = C, .res = h.p});
+  }
+  SD_REQUIRE(C % 64 == 0, kUnsupported, "VAE attention needs C %% 64 == 0");
+  Tensor vt = conv(ops, p + ".to_v", t0, {.cout = C, .out_mode = kOutHalfT, .ldT = S});
   half_t* scores = ll_.arena.alloc_n<half_t>((size_t)S * S);
   Tensor a = new_tensor(B, H, W, C);
   for (int b = 0; b < B; ++b) {
@@ -65,7 +77,7 @@ Tensor Vae::attention(std::vector<Op>& ops, const std::string& p, const Tensor& 
     d1.x0 = q.p + (size_t)b * S * C; d1.C0 = C; d1.w = k.p + (size_t)b * S * C;
     d1.out = scores; d1.B = 1; d1.Hi = 1; d1.Wi = S; d1.Ho = 1; d1.Wo = S; d1.N = S;
     ConvDesc d2;   // out[q][c] = sum_k P[q][k] V^T[c][k]
-    d2.x0 = scores; d2.C0 = S; d2.w = vt.p + (size_t)b * C * ldv;
+    d2.x0 = scores; d2.C0 = S; d2.w = vt.p + (size_t)b * C * S;
     d2.out = a.p + (size_t)b * S * C; d2.B = 1; d2.Hi = 1; d2.Wi = S; d2.Ho = 1; d2.Wo = S; d2.N = C;
     ll_.ws_need = std::max(ll_.ws_need, std::max(conv_workspace_bytes(d1), conv_workspace_bytes(d2)));
     ops.push_back([this, d1, d2, scores, S, scale](hipStream_t s) {

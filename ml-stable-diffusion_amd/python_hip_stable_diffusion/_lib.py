@@ -167,6 +167,7 @@ SYMBOLS = [
     ("sd_safety_checker_run", _I, [_P, _P, _F, _FP, _FP, _FP, _FP, _I]),
     ("sd_op_vit_attention", _I, [_P, _P, _I, _I, _I, _I, _I, _FP]),
     ("sd_op_safety_head", _I, [_FP, _FP, _FP, _FP, _FP, _F, _I, _I, _I, _I, _FP, _FP]),
+    ("sd_op_vae_attention", _I, [_P, _P, _P, _P, _I, _I, _I, _I, _FP]),
     ("sd_vae_decode_images", _I, [_P, _P, _I, _FP, _P, _P, C.POINTER(ImagePost), _F, _FP, _FP, _I]),
     ("sd_op_resample_coeffs", _I, [_I, _I, C.POINTER(_I), _P, _P]),
     ("sd_op_image_rgb8", _I, [_FP, _P, _I, _I, _I, _I, _FP]),
@@ -308,6 +309,24 @@ def vit_attention(qkv, heads, dim_head=64, out=None, iters=1):
     ms = C.c_float(0)
     check(lib().sd_op_vit_attention(ptr(qkv), ptr(out), B, S, heads, dim_head, iters, C.byref(ms)))
     return out.reshape(-1)[:n].reshape(B, S, heads * dim_head), ms.value
+
+
+def vae_attention(q, k, v, out=None, iters=1):
+    """Single-head mid-block attention of the VAE (csrc/vae_attention.hip): softmax(q k^T / sqrt(C)) v as one streaming launch.
+    q, k, v (B, S, C) f16 token-major, C in {64, 128, 256, 512} (else NotImplementedError from the library) -> (B, S, C) f16, ms.
+    ``out``: a C-contiguous float16 buffer of at least B * S * C elements to write into (tests put a guard behind it)."""
+    q, k, v = f16(q), f16(k), f16(v)
+    if q.ndim != 3 or k.shape != q.shape or v.shape != q.shape:
+        raise ValueError("vae_attention: q, k and v must share one (B, S, C) shape")
+    B, S, Cn = q.shape
+    n = B * S * Cn
+    if out is None:
+        out = np.empty(n, np.float16)
+    if out.dtype != np.float16 or not out.flags.c_contiguous or out.size < n:
+        raise ValueError("vae_attention: out must be a C-contiguous float16 buffer of at least B * S * C elements")
+    ms = C.c_float(0)
+    check(lib().sd_op_vae_attention(ptr(q), ptr(k), ptr(v), ptr(out), B, S, Cn, iters, C.byref(ms)))
+    return out.reshape(-1)[:n].reshape(B, S, Cn), ms.value
 
 
 def safety_head(image_embeds, concept_embeds, special_embeds, concept_w, special_w, adjustment=0.0):
