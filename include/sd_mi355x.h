@@ -80,6 +80,24 @@ int sd_weights_add_palettized(sd_weights* w, const char* name, const void* lut, 
                               int ndim);
 int sd_weights_palette_bits(const sd_weights* w, const char* name);
 int sd_weights_read_palette(const sd_weights* w, const char* name, void* lut, uint8_t* indices, float* values);
+/* W8A8 post-training quantization: replaces activation_quantization.py:141-203 (quantize_cumulative_config + the calibration that
+ * feeds it) with its scheme - symmetric int8, one scale per OUTPUT CHANNEL for a conv's weights, one scale per TENSOR for the
+ * activations it reads.  Parity with coremltools' quantizer is unpinned (coremltools is not part of this code base's test bed).
+ *   weights      s_w[n] = absmax_n / 127 (an all-zero row: 1), q = clip(rint(w / s_w[n]), -127, 127): fp32 division, ties to even
+ *   activations  s_a = act_absmax / 127 over ALL sources of the conv (both halves of a skip concat);
+ *                x_q = clip(rint(fp32(x) * fp32(1 / s_a)), -127, 127) in the kernel; NaN -> 0, +-inf -> +-127
+ *   output       fp32(int32 sum) * fp32(s_a * s_w[n]), then bias / time embedding / residual as for any conv
+ * sd_weights_quantize_w8a8 MARKS the conv weight `name` (SD_ERR_NOT_FOUND when absent): the store keeps q, s_w and act_absmax beside
+ * the untouched values; *sq_err (may be NULL) = sum (w - q s_w)^2.  SD_ERR_INVALID_ARGUMENT: a tensor that is not (Cout, Cin, k, k),
+ * a tensor that carries a palette (and sd_weights_palettize refuses a marked tensor), act_absmax not a positive finite number, a
+ * non-finite weight.  A UNet handle built from the store runs a marked conv from int8 (wstream.hip, plan tile 17) exactly where
+ * its plan would be the weight stream (plan tile 9); any other marked conv runs fp16 as before - the reference's skipped layers.
+ * sd_weights_w8a8_info: 1 when `name` is marked (*act_scale, may be NULL, = s_a), else 0.
+ * sd_weights_observe_activations(on): handles created from the store while it is on put an absmax observer in front of every conv
+ * that plan tile 17 could take (sd_unet_activation_ranges) - calibration on the device. */
+int sd_weights_quantize_w8a8(sd_weights* w, const char* name, float act_absmax, double* sq_err);
+int sd_weights_w8a8_info(const sd_weights* w, const char* name, float* act_scale);
+int sd_weights_observe_activations(sd_weights* w, int on);
 
 /* ------------------------------------------------------------------------------------------
  * UNet / ControlNet.  Config mirrors UNet2DConditionModel.__init__ (unet.py:801-833) with the
@@ -138,6 +156,19 @@ size_t sd_unet_arena_used_bytes(const sd_unet* u);
  * the index bit stream and the LUT, no fp16 copy; *stream_bytes = the bytes of those streams and LUTs.  Every other palettized tensor
  * (q|k|v, attn2.to_q, the merged transformer tail, GEGLU projections on 256-row tiles) was uploaded as fp16 lut[indices]. */
 int sd_unet_palette_info(const sd_unet* u, int* n_palettized, int* n_streamed, size_t* stream_bytes);
+/* W8A8 (activation_quantization.py:141-203; sd_weights_quantize_w8a8): *n_marked tensors of the handle's weight store arrived with a
+ * mark; *n_applied convolutions run from int8 (plan tile 17) and hold the int8 stream and one fp32 scale per output channel, no fp16
+ * copy; *bytes = the bytes of those streams and scale vectors.  n_marked - n_applied marked convs stayed fp16. */
+int sd_unet_w8a8_info(const sd_unet* u, int* n_marked, int* n_applied, size_t* bytes);
+/* Which convs those are: returns n_applied (>= 0) or an error code (< 0); index >= 0 fills `name` with the weight tensor of the
+ * index-th of them in build order (SD_ERR_INVALID_ARGUMENT when there is no such conv), index < 0 asks for the count alone. */
+int sd_unet_w8a8_layer(const sd_unet* u, int index, char* name, int name_bytes);
+/* The activation observers of a handle created from an observing store (sd_weights_observe_activations), in launch order.  Returns
+ * their number (>= 0) or an error code (< 0).  index >= 0 (SD_ERR_INVALID_ARGUMENT when there is no such slot): `name` = the conv's
+ * weight tensor (NUL-terminated, cut to name_bytes), *absmax = max |x| over the conv's source tensor(s) of every forward since the
+ * handle was created (an element-wise maximum: NaN elements are skipped).  index < 0: the count alone.  Synchronises the handle's
+ * stream.  The observers are ordinary launches of the forward (captured into its graph); they write nothing the model reads. */
+int sd_unet_activation_ranges(sd_unet* u, int index, char* name, int name_bytes, float* absmax);
 
 #define SD_FLAG_DEVICE_PTRS 1 /* all data pointers are device pointers on the handle's GPU */
 
@@ -376,6 +407,23 @@ int sd_op_conv2d_palettized(const void* x, const void* x1, const void* lut, int 
  * (j & 1) * 16 + (lane >> 5) * 8 + e, tap j >> 1) as little-endian nbits-wide fields, padded to whole 16-byte words, word q at
  * [strip][slice][q][lane][16 B]. */
 int sd_op_palette_pack(const uint8_t* indices, int Cout, int Ctot, int ksize, int nbits, uint8_t* stream, size_t* bytes);
+/* The small-M weight-stream conv in W8A8 (plan tile 17; activation_quantization.py:141-203, semantics at sd_weights_quantize_w8a8):
+ * wq (Cout, Cin + C1, k, k) int8, w_scale (Cout) f32, act_absmax the range of x (and x1); x1 / C1, bias, res, upsample, nw, plan_out,
+ * iters, ms as sd_op_conv2d_palettized.  plan_out = {17, 4 for four waves else 0, slabs, 1}.  Checked on the host in this order,
+ * before any device work, each SD_ERR_INVALID_ARGUMENT: NULL arguments; nw not in {0, 4, 8}; an empty problem; ksize / upsample off the
+ * path; a shape the weight stream does not take; act_absmax not a positive finite number; a w_scale that is not; a weight of -128. */
+int sd_op_conv2d_w8a8(const void* x, const void* x1, const int8_t* wq, const float* w_scale, float act_absmax, const float* bias,
+                      const void* res, void* out, int B, int Cin, int C1, int H, int W, int Cout, int ksize, int upsample, int nw,
+                      int* plan_out, int iters, float* ms);
+/* The int8 stream that entry and the UNet builder put on the device (host only): wq (Cout, Ctot, k, k) int8 -> stream
+ * [Cout / 32][Ctot / 32][k * k][64 lanes][16 B]: lane l of (strip, slice, tap) holds row strip * 32 + (l & 31), channels slice * 32 +
+ * (l >> 5) * 16 + (0 .. 15).  *bytes = its size (Cout * Ctot * k * k); stream may be NULL to ask for the size alone. */
+int sd_op_w8a8_pack(const int8_t* wq, int Cout, int Ctot, int ksize, int8_t* stream, size_t* bytes);
+/* The host weight quantizer of sd_weights_quantize_w8a8 on its own: w (Cout, per_row) f32 -> q (Cout, per_row) int8, w_scale (Cout)
+ * f32, *sq_err (may be NULL).  A non-finite weight is SD_ERR_INVALID_ARGUMENT. */
+int sd_op_quantize_weight(const float* w, int Cout, size_t per_row, int8_t* q, float* w_scale, double* sq_err);
+/* max |x| over n f16 values on the device (the observers' kernel, misc.hip): exactly the fp32 value of the largest magnitude. */
+int sd_op_absmax(const void* x, size_t n, float* absmax);
 /* smgemm.hip from PALETTIZED weights (plan tile 15): w = lut[indices], indices (Cout, Cin) uint8; x (B,Cin,H,W), res/out (B,Cout,H,W) f16 NCHW;
  * bm 0 / 32 / 64 (0: by M as tile 12). Bit-identical to sd_op_conv2d(tile 141 / 142) on the fp16 weights lut[indices].
  * plan_out[4] = {15, 1|2, 1, 0}.  Checked on the host in this order, before any device work, each SD_ERR_INVALID_ARGUMENT: nbits not in
@@ -524,7 +572,9 @@ int sd_op_sched_step(const float* noise_pred, float* latents, float* hist, const
  * weight copies exist (1 wstream, 2 wsgemm, 4 bvgemm; -1 = the ones the library's handle would hold).
  * plan[7] = plan tile (1-4 igemm tiles, 7 halo conv, 9 wstream, 10 wsgemm, 11 bvgemm, 12 smgemm, 13 smgeglu, -1 off the MFMA path; the
  * palettized tiles 14 / 15 / 16 need a palette and are never an answer here: a handle takes 15 exactly where this says 12
- * (sd_op_gemm_palettized) and 16 where this says 13 with 128-row tiles (sd_op_geglu_palettized)),
+ * (sd_op_gemm_palettized) and 16 where this says 13 with 128-row tiles (sd_op_geglu_palettized); tile = 17 asks for a W8A8
+ * descriptor - the answer is 17 with the slab count of its wave code (staging 4: four waves, else eight), or SD_ERR_INVALID_ARGUMENT for
+ * a shape the weight stream does not take; a handle takes 17 exactly where this says 9 and the tensor carries a W8A8 mark),
  * staging, resolved split-K, slab (0 / 1), then the copies a handle must hold for this conv: wstream, wsgemm, bvgemm (0 / 1 each).
  * *workspace_bytes: the slab workspace this launch needs. */
 int sd_op_conv_plan(int ksize, int stride, int up, int C0, int C1, int N, int B, int Ho, int Wo, int out_mode, int flags, int n_trans,
@@ -556,7 +606,7 @@ int sd_philox_randn(uint64_t seed, uint32_t offset, double* out, size_t n);
  * on the slow ones: the figure `value_normalised` is built on.  Nine floats.  Allocates and frees 2 GiB of device memory; synchronous. */
 int sd_calibrate(int device, float* out9);
 /* MFMA fragment layout self-check used by the build/smoke tests (returns 0 when the hardware
- * layout matches what the kernels assume). */
+ * layout matches what the kernels assume; bit 0 the f16 MFMA, bits 1 / 2 the cross-lane exchanges, bit 3 the int8 MFMA of W8A8). */
 int sd_selftest_mfma(void);
 
 /* ------------------------------------------------------------------------------------------

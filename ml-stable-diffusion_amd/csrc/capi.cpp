@@ -127,6 +127,24 @@ int sd_weights_read_palette(const sd_weights* w, const char* name, void* lut, ui
     if (values) std::copy(t.data.begin(), t.data.end(), values);
   });
 }
+int sd_weights_quantize_w8a8(sd_weights* w, const char* name, float act_absmax, double* sq_err) {
+  return guarded([&] {
+    SD_REQUIRE(w && name, kInvalidArgument, "NULL argument");
+    const double e = w->store.quantize_w8a8(name, act_absmax);
+    if (sq_err) *sq_err = e;
+  });
+}
+int sd_weights_w8a8_info(const sd_weights* w, const char* name, float* act_scale) {
+  const W8A8Mark* m = (w && name) ? w->store.w8a8(name) : nullptr;
+  if (m && act_scale) *act_scale = m->act_absmax / 127.0f;
+  return m ? 1 : 0;
+}
+int sd_weights_observe_activations(sd_weights* w, int on) {
+  return guarded([&] {
+    SD_REQUIRE(w, kInvalidArgument, "NULL argument");
+    w->store.set_observe(on != 0);
+  });
+}
 void sd_weights_destroy(sd_weights* w) { delete w; }
 
 int sd_unet_create(const sd_unet_config* cfg, const sd_weights* w, int device, sd_unet** out) {
@@ -167,6 +185,41 @@ int sd_unet_palette_info(const sd_unet* u, int* n_palettized, int* n_streamed, s
     SD_REQUIRE(u && n_palettized && n_streamed && stream_bytes, kInvalidArgument, "NULL argument");
     u->impl->palette_info(n_palettized, n_streamed, stream_bytes);
   });
+}
+
+int sd_unet_w8a8_info(const sd_unet* u, int* n_marked, int* n_applied, size_t* bytes) {
+  return guarded([&] {
+    SD_REQUIRE(u && n_marked && n_applied && bytes, kInvalidArgument, "NULL argument");
+    u->impl->w8a8_info(n_marked, n_applied, bytes);
+  });
+}
+int sd_unet_w8a8_layer(const sd_unet* u, int index, char* name, int name_bytes) {
+  int n = 0;
+  const int st = guarded([&] {
+    SD_REQUIRE(u, kInvalidArgument, "NULL handle");
+    const std::vector<std::string>& names = u->impl->w8a8_applied();
+    n = (int)names.size();
+    SD_REQUIRE(index < n && (index < 0 || (name && name_bytes > 1)), kInvalidArgument, "W8A8 layer %d of %d", index, n);
+    if (index >= 0) std::snprintf(name, (size_t)name_bytes, "%s", names[(size_t)index].c_str());
+  });
+  return st != kOk ? st : n;
+}
+int sd_unet_activation_ranges(sd_unet* u, int index, char* name, int name_bytes, float* absmax) {
+  int n = 0;
+  const int st = guarded([&] {
+    SD_REQUIRE(u, kInvalidArgument, "NULL handle");
+    SD_REQUIRE(index < 0 || (name && name_bytes > 1 && absmax), kInvalidArgument, "NULL argument");
+    require_idle(u, "sd_unet_activation_ranges");
+    std::string s;
+    float v = 0.f;
+    n = u->impl->activation_range(index, &s, &v);
+    SD_REQUIRE(index < n, kInvalidArgument, "activation range %d of %d", index, n);
+    if (index >= 0) {
+      std::snprintf(name, (size_t)name_bytes, "%s", s.c_str());
+      *absmax = v;
+    }
+  });
+  return st != kOk ? st : n;
 }
 
 int sd_unet_forward(sd_unet* u, const sd_unet_io* io) {

@@ -9,7 +9,7 @@
 //             decoded by decode_plan (conv_plan.cpp) and nowhere else; sd_op_conv_plan_kernel names the kernel a pair launches
 //     sd_op_conv2d / sd_op_conv2d_ex alone: 110-116 plan tile 11 (bvgemm.hip: its own choice / variants 1-6, needs w_bv),
 //                                           140-142 plan tile 12 (smgemm.hip: tile height by M / 32 rows / 64 rows)
-//     (plan tiles 14 / 15 read palettized weights: sd_op_conv2d_palettized / sd_op_gemm_palettized)
+//     (plan tiles 14 / 15 read palettized weights: sd_op_conv2d_palettized / sd_op_gemm_palettized; plan tile 17 int8 ones: sd_op_conv2d_w8a8)
 //     sd_op_conv2d_ex is sd_op_conv2d with the ConvDesc fields the UNet / VAE builders set on top (second source, timestep embedding,
 //     the encoder's explicit padding, one GroupNorm twin) and reads the plan that ran back: plan_out = {tile, staging, splitk, slab}
 //   sd_op_geglu_ln `kernel`: 0 the library's plan, 1 the tiled igemm / gemm_pipe kernels, 2 plan tile 10 (wsgemm.hip),
@@ -164,6 +164,10 @@ struct ConvOpExtra {
   const void* pal_lut = nullptr;         // 2^pal_bits f16
   const uint8_t* pal_indices = nullptr;  // (Cout, Cin + C1, k, k)
   int pal_bits = 0, pal_waves = 0;       // waves per workgroup: 4, else 8
+  // sd_op_conv2d_w8a8: the weights are i8_q * i8_w_scale[n] (w is NULL), the activations are quantized with act_absmax / 127 (plan tile 17)
+  const int8_t* i8_q = nullptr;          // (Cout, Cin + C1, k, k)
+  const float* i8_w_scale = nullptr;     // (Cout,)
+  float i8_act_absmax = 0.f;
 };
 
 // the palettized weights of a descriptor as the UNet builder uploads them (Net::conv, Net::upload_pal_geglu): the packed index stream
@@ -191,7 +195,7 @@ const float* upload_temb_rows(Scratch& sc, const float* temb, int B, int N, int*
 // the body of sd_op_conv2d / sd_op_conv2d_ex
 void conv2d_op(const void* x, const void* w, const float* bias, const void* res, void* out, int B, int Cin, int H, int W, int Cout,
                int ksize, int stride, int upsample, int tile, int splitk, int force_generic, int iters, float* ms, const ConvOpExtra& e) {
-  SD_REQUIRE(x && (w || e.pal_indices) && out, kInvalidArgument, "NULL argument");
+  SD_REQUIRE(x && (w || e.pal_indices || e.i8_q) && out, kInvalidArgument, "NULL argument");
   SD_REQUIRE((ksize == 1 || ksize == 3) && (stride == 1 || stride == 2) && (upsample == 0 || upsample == 1),
              kInvalidArgument, "conv2d: ksize %d stride %d upsample %d not on the path", ksize, stride, upsample);
   SD_REQUIRE(e.C1 >= 0 && (e.C1 == 0 || e.x1), kInvalidArgument, "conv2d: C1 = %d needs the second source x1", e.C1);
@@ -213,7 +217,7 @@ void conv2d_op(const void* x, const void* w, const float* bias, const void* res,
     d.x1 = upload_nhwc(sc, e.x1, B, e.C1, H, W);
     d.C1 = e.C1;
   }
-  if (!e.pal_indices) d.w = upload_conv_weight(sc, w, Cout, Cin + e.C1, ksize);
+  if (!e.pal_indices && !e.i8_q) d.w = upload_conv_weight(sc, w, Cout, Cin + e.C1, ksize);
   d.bias = bias ? sc.dev<float>(Cout, bias) : nullptr;
   if (e.temb) d.temb = upload_temb_rows(sc, e.temb, B, Cout, &d.temb_stride);
   if (res) d.res = upload_nhwc(sc, res, B, Cout, Ho, Wo);
@@ -234,6 +238,14 @@ void conv2d_op(const void* x, const void* w, const float* bias, const void* res,
     d.tile = 14;
     d.staging = conv_plan_waves_code(e.pal_waves);
   }
+  if (e.i8_q) {   // (shape and values were checked on the host by the entry point)
+    const W8A8HostCopy h = w8a8_host_copy("conv2d_w8a8", e.i8_q, e.i8_w_scale, e.i8_act_absmax, Cout, Cin + e.C1, ksize);
+    d.w_i8 = sc.dev<int8_t>(h.stream.size(), h.stream.data());
+    d.i8_scale = sc.dev<float>(h.cs.size(), h.cs.data());
+    d.i8_inv_s = h.inv_s;
+    d.tile = 17;
+    d.staging = conv_plan_waves_code(e.pal_waves);
+  }
   half_t* dtwin = nullptr;
   if (e.twin_groups) {   // the GroupNorm as a twin of the conv's slab combine (sd_op_conv2d_groupnorm's producer_stats = 2)
     SD_REQUIRE(fast, kInvalidArgument, "conv2d: GroupNorm twins need the MFMA path");
@@ -252,7 +264,7 @@ void conv2d_op(const void* x, const void* w, const float* bias, const void* res,
   }
   ConvWorkspace ws;
   // the pre-tiled weight copies: what a forced plan reads, else exactly what the planner names for the library's own plan
-  const ConvWeightCopies copies = (fast && tile == 0 && splitk == 0 && !d.debug && !d.w_pal) ? conv_plan_copies(d) : ConvWeightCopies{false, false, false};
+  const ConvWeightCopies copies = (fast && tile == 0 && splitk == 0 && !d.debug && !d.w_pal && !d.w_i8) ? conv_plan_copies(d) : ConvWeightCopies{false, false, false};
   if (fast && (d.tile == 9 || copies.wstream)) tile_for_wstream(sc, d, "conv2d: shape not eligible for plan tile 9 (wstream.hip)");
   if (fast && (d.tile == 11 || copies.bvgemm)) tile_for_bvgemm(sc, d, "conv2d: shape not eligible for plan tile 11 (bvgemm.hip)");
   if (fast && d.tile != 11 && d.tile != 12) ws = workspace_for(sc, {d});
@@ -478,6 +490,63 @@ int sd_op_conv2d_palettized(const void* x, const void* x1, const void* lut, int 
     e.plan_out = plan_out;
     e.pal_lut = lut; e.pal_indices = indices; e.pal_bits = nbits; e.pal_waves = nw;
     conv2d_op(x, nullptr, bias, res, out, B, Cin, H, W, Cout, ksize, 1, upsample, 0, 0, 0, iters, ms, e);
+  });
+}
+
+// Every check runs on the host in front of the first device call (Scratch), in the order the header lists them.
+int sd_op_conv2d_w8a8(const void* x, const void* x1, const int8_t* wq, const float* w_scale, float act_absmax, const float* bias,
+                      const void* res, void* out, int B, int Cin, int C1, int H, int W, int Cout, int ksize, int upsample, int nw,
+                      int* plan_out, int iters, float* ms) {
+  return guarded([&] {
+    SD_REQUIRE(x && wq && w_scale && out, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(nw == 0 || nw == 4 || nw == 8, kInvalidArgument, "conv2d_w8a8: nw = %d, not 0, 4 or 8", nw);
+    SD_REQUIRE(B > 0 && Cin > 0 && C1 >= 0 && Cout > 0 && H > 0 && W > 0 && (C1 == 0 || x1), kInvalidArgument, "conv2d_w8a8: empty problem");
+    SD_REQUIRE((ksize == 1 || ksize == 3) && (upsample == 0 || upsample == 1), kInvalidArgument, "conv2d_w8a8: ksize %d upsample %d", ksize, upsample);
+    ConvDesc d;   // the shape alone: what the planner's predicates look at
+    d.C0 = Cin;
+    if (C1 > 0) d.x1 = f16(x1), d.C1 = C1;
+    d.B = B; d.Hi = H; d.Wi = W; d.Ho = H * (upsample ? 2 : 1); d.Wo = W * (upsample ? 2 : 1);
+    d.ksize = ksize; d.up = upsample ? 2 : 1; d.N = Cout;
+    SD_REQUIRE(conv_fast_path_ok(d) && wstream_shape_ok(d), kInvalidArgument,
+               "conv2d_w8a8: shape not eligible for plan tile 17 (wstream.hip: k=%d C0=%d C1=%d N=%d %dx%d)", ksize, Cin, C1, Cout, d.Ho, d.Wo);
+    // act_absmax, then w_scale, then the weight values (-128 is outside the symmetric range)
+    (void)w8a8_host_copy("conv2d_w8a8", wq, w_scale, act_absmax, Cout, Cin + C1, ksize);
+    ConvOpExtra e;
+    e.x1 = x1; e.C1 = C1;
+    e.plan_out = plan_out;
+    e.i8_q = wq; e.i8_w_scale = w_scale; e.i8_act_absmax = act_absmax; e.pal_waves = nw;
+    conv2d_op(x, nullptr, bias, res, out, B, Cin, H, W, Cout, ksize, 1, upsample, 0, 0, 0, iters, ms, e);
+  });
+}
+
+int sd_op_w8a8_pack(const int8_t* wq, int Cout, int Ctot, int ksize, int8_t* stream, size_t* bytes) {
+  return guarded([&] {
+    SD_REQUIRE(wq && bytes, kInvalidArgument, "NULL argument");
+    SD_REQUIRE((ksize == 1 || ksize == 3) && Cout > 0 && Ctot > 0 && Cout % 32 == 0 && Ctot % 32 == 0, kInvalidArgument,
+               "w8a8_pack: ksize %d Cout %d Ctot %d", ksize, Cout, Ctot);
+    *bytes = wstream_i8_bytes(Cout, Ctot, ksize);
+    if (stream) wstream_i8_pack(wq, Cout, Ctot, ksize, stream);
+  });
+}
+
+int sd_op_quantize_weight(const float* w, int Cout, size_t per_row, int8_t* q, float* w_scale, double* sq_err) {
+  return guarded([&] {
+    SD_REQUIRE(w && q && w_scale && Cout > 0 && per_row > 0, kInvalidArgument, "quantize_weight: NULL argument or empty tensor");
+    const double e = w8a8_quantize_weight(w, Cout, per_row, q, w_scale);
+    if (sq_err) *sq_err = e;
+  });
+}
+
+int sd_op_absmax(const void* x, size_t n, float* absmax) {
+  return guarded([&] {
+    SD_REQUIRE(x && n > 0 && absmax, kInvalidArgument, "absmax: NULL argument or empty tensor");
+    Scratch sc;
+    const half_t* dx = sc.dev<half_t>(n, f16(x));
+    const float zero = 0.f;
+    float* slot = sc.dev<float>(1, &zero);
+    launch_absmax_half(dx, n, nullptr, 0, slot, sc.stream);
+    SD_HIP(hipStreamSynchronize(sc.stream));
+    SD_HIP(hipMemcpy(absmax, slot, sizeof(float), hipMemcpyDeviceToHost));
   });
 }
 
@@ -1174,6 +1243,12 @@ static ConvPlan query_conv_plan(int ksize, int stride, int up, int C0, int C1, i
     d.gnf_silu = ksize == 3 ? 1 : 0;
   }
   d.tile = tile; d.staging = staging; d.splitk = splitk;
+  if (tile == 17) {   // a W8A8 descriptor carries its int8 stream and scales (the planner only tests the pointers)
+    d.w = nullptr;
+    d.w_i8 = reinterpret_cast<const int8_t*>(present);
+    d.i8_scale = present;
+    d.i8_inv_s = 1.f;
+  }
   c = conv_plan_copies(d);
   if (copies < 0) copies = (c.wstream ? 1 : 0) | (c.wsgemm ? 2 : 0) | (c.bvgemm ? 4 : 0);   // what a handle of the library holds
   if (copies & 1) d.w_tiled = ph;

@@ -53,11 +53,13 @@ bool can_split(const ConvDesc& d) { return d.out_mode == kOutHalf && !d.ln_colsu
 bool can_stream(const ConvDesc& d) { return d.w_tiled != nullptr && can_split(d) && wstream_shape_ok(d); }
 // a palettized descriptor (plan tile 14): pinned to the palettized weight stream, it holds no fp16 weights to run anything else on
 bool pal_stream(const ConvDesc& d) { return d.w_pal != nullptr && !d.pal_gemm && !d.pal_geglu; }
+// a W8A8 descriptor (plan tile 17): pinned to the int8 weight stream likewise
+bool i8_stream(const ConvDesc& d) { return d.w_i8 != nullptr; }
 // the same for the small-M 1x1 GEMM (plan tile 15): the descriptor carries the stream of smgemm_pal_pack
 bool pal_gemm(const ConvDesc& d) { return d.w_pal != nullptr && d.pal_gemm; }
 // and for the GEGLU projection (plan tile 16): the stream of smgeglu_pal_pack
 bool pal_geglu(const ConvDesc& d) { return d.w_pal != nullptr && d.pal_geglu; }
-// tiles 9 / 14: the code's wave count (decode_plan)
+// tiles 9 / 14 / 17: the code's wave count (decode_plan)
 int wstream_waves(int code) { return code == 4 ? 4 : 8; }
 // fp32 slabs of a launch: one per split, one when only `slab` (weight stream, GroupNorm twins) asks for the slab path
 size_t slab_bytes(const Dims& a, int splits, bool slab) { return (splits > 1 || slab) ? (size_t)splits * a.M * a.N * sizeof(float) : 0; }
@@ -274,6 +276,14 @@ ConvPlan plan_codes(const ConvDesc& d) {
     r.workspace_bytes = slab_bytes(dims_of(d), r.splitk, true);
     return r;
   }
+  if (i8_stream(d)) {   // pinned in the same place, for the same reason
+    SD_REQUIRE(d.i8_scale && !d.w_pal && can_split(d) && wstream_shape_ok(d), kInvalidArgument,
+               "plan tile 17 (wstream.hip, int8) needs the int8 stream, the scales and a shape of the weight stream");
+    ConvPlan r{17, d.staging, 1, true, 0};   // the code of tile 9
+    r.splitk = wstream_splits(d, wstream_waves(d.staging));
+    r.workspace_bytes = slab_bytes(dims_of(d), r.splitk, true);
+    return r;
+  }
   if (pal_gemm(d)) {   // pinned like tile 14; the code of tile 12 in, the resolved tile height out; no workspace
     SD_REQUIRE(d.pal_lut && palette_bits_ok(d.pal_bits) && !d.x1 && d.staging >= 0 && d.staging <= 2 && smgemm_shape_ok(d, d.staging), kInvalidArgument,
                "plan tile 15 (smgemm.hip, palettized) needs the index stream, the LUT and a single-source shape of the small-M GEMM");
@@ -341,15 +351,15 @@ ConvPlan plan_codes(const ConvDesc& d) {
 //              runs as the deepest shallower one that does.  The LayerNorm fold has no register staging (1 as 0); the token-transposed
 //              output (kOutHalfT) has register staging and rings of 2 / 3 stages only.
 //   tile 7:    0 / 2 / 3 / 4 / 5 = 2 / 3 / 4 / 6 / 8 weight stages; GroupNorm in the loader: 4 stages from code 3 where its table fits, else 3
-//   tiles 9 / 14: 4 = four waves per workgroup, anything else eight      tile 11: 1-6 = the variant, anything else the library's choice
+//   tiles 9 / 14 / 17: 4 = four waves per workgroup, anything else eight      tile 11: 1-6 = the variant, anything else the library's choice
 //   tiles 12 / 15 / 13 / 16: 1 / 2 = the lower / higher tile (32 / 64, 128 / 256 rows), 0 = by the shape
 void decode_plan(const ConvDesc& d, ConvPlan& p) {
   const Dims a = dims_of(d);
   int code = p.staging;
   switch (p.tile) {
     case -1: p.kernel = ConvKernel::Generic; return;
-    case 9: case 14:
-      p.kernel = p.tile == 9 ? ConvKernel::Wstream : ConvKernel::WstreamPal;
+    case 9: case 14: case 17:
+      p.kernel = p.tile == 9 ? ConvKernel::Wstream : p.tile == 14 ? ConvKernel::WstreamPal : ConvKernel::WstreamI8;
       p.waves = wstream_waves(code);
       return;
     case 10: p.kernel = ConvKernel::Wsgemm; return;
@@ -425,6 +435,7 @@ std::string conv_plan_kernel_name(const ConvPlan& p) {
     case ConvKernel::HaloKs: return "halo_ks" + ring;
     case ConvKernel::Wstream: return "wstream waves" + std::to_string(p.waves);
     case ConvKernel::WstreamPal: return "wstream_pal waves" + std::to_string(p.waves);
+    case ConvKernel::WstreamI8: return "wstream_i8 waves" + std::to_string(p.waves);
     case ConvKernel::Wsgemm: return "wsgemm";
     case ConvKernel::Bvgemm: return "bvgemm v" + std::to_string(p.variant);
     case ConvKernel::Smgemm: return "smgemm bm" + std::to_string(p.bm);
@@ -446,7 +457,7 @@ size_t conv_workspace_bytes(const ConvDesc& d) {
   const Dims a = dims_of(d);
   const Plan p = choose_plan(d, a);
   int splits = (switches().tuning && can_split(d)) ? std::max(p.splitk, 16) : p.splitk;
-  const bool stream = can_stream(d) || (pal_stream(d) && can_split(d) && wstream_shape_ok(d));   // tile 14 as tile 9
+  const bool stream = can_stream(d) || ((pal_stream(d) || i8_stream(d)) && can_split(d) && wstream_shape_ok(d));   // tiles 14 / 17 as tile 9
   if (stream) splits = std::max(splits, wstream_splits(d, 4));
   return slab_bytes(a, splits, d.n_twins > 0 || stream);
 }
@@ -479,6 +490,7 @@ int conv_plan_pal_waves(const ConvDesc& d0) {
   d.w_tiled = &present;   // conv_plan only tests the pointer
   d.w_ws = d.w_bv = nullptr;
   d.w_pal = nullptr;
+  d.w_i8 = nullptr;
   const ConvPlan p = conv_plan(d);
   return p.kernel == ConvKernel::Wstream ? p.waves : 0;
 }
@@ -556,9 +568,9 @@ void conv_plan_log(const ConvDesc& d, const ConvPlan& p, int n_fast) {
   if (!on) return;
   const Dims a = dims_of(d);
   const int c1 = d.x1 ? d.C1 : 0;
-  if (p.tile == 9 || p.tile == 14)
+  if (p.tile == 9 || p.tile == 14 || p.tile == 17)
     fprintf(stderr, "[sd conv] k%d up%d C0=%d C1=%d M=%d N=%d K=%d tile=%d nw=%d slabs=%d twins=%d bits=%d\n", d.ksize, d.up, d.C0, c1, a.M, a.N,
-            a.K, p.tile, p.waves, p.splitk, d.n_twins, p.tile == 14 ? d.pal_bits : 16);
+            a.K, p.tile, p.waves, p.splitk, d.n_twins, p.tile == 14 ? d.pal_bits : p.tile == 17 ? 8 : 16);
   else if (p.tile == 12 || p.tile == 13)
     fprintf(stderr, "[sd conv] k1 s1 up1 C0=%d C1=%d M=%d N=%d K=%d mode=%d tile=%d bm=%d n_fast=%d\n", d.C0, c1, a.M, a.N, a.K, d.out_mode, p.tile, p.bm,
             n_fast);

@@ -8,15 +8,16 @@
 
 namespace sd {
 
-// the kernel a plan launches (tile -1 / 1-4 / 7 / 9 / 14 / 10 / 11 / 12 / 15 / 13 / 16 of the wire format below)
-enum class ConvKernel { Generic, Igemm, GemmPipe, HaloKs, Wstream, WstreamPal, Wsgemm, Bvgemm, Smgemm, SmgemmPal, Smgeglu, SmgegluPal };
+// the kernel a plan launches (tile -1 / 1-4 / 7 / 9 / 14 / 17 / 10 / 11 / 12 / 15 / 13 / 16 of the wire format below)
+enum class ConvKernel { Generic, Igemm, GemmPipe, HaloKs, Wstream, WstreamPal, WstreamI8, Wsgemm, Bvgemm, Smgemm, SmgemmPal, Smgeglu, SmgegluPal };
 
 struct ConvPlan {
   // The wire format: what ConvDesc::tile / staging pins, tuned_convs.inc rows, SD_PLAN_TABLE and sd_tune_set_candidate say and what
   // sd_op_conv_plan, plan_out and SD_LOG_CONVS report.  Read by decode_plan (conv_plan.cpp) and by nothing else.
   int tile;        // 1: 128x128, 2: 128x64, 3: 64x64, 4: 64x128 (igemm.hip), 7: the K-split halo conv (conv3x3_halo.hip), 9: wstream.hip,
                    // 10: wsgemm.hip, 11: bvgemm.hip, 12: smgemm.hip, 13: smgeglu.hip, 14: wstream.hip from palettized weights,
-                   // 15: smgemm.hip from palettized weights; -1 = not on the MFMA path (launch_conv_generic)
+                   // 15: smgemm.hip from palettized weights, 17: wstream.hip from int8 weights and activations (W8A8);
+                   // -1 = not on the MFMA path (launch_conv_generic)
   int staging;     // per-family code: decode_plan
   int splitk;      // resolved: what the launch runs, no empty splits (halo: over 64-channel chunks; tile 9: the slab count)
   bool slab;       // the output leaves through fp32 slabs (split-K, weight stream, GroupNorm twins)
@@ -44,6 +45,8 @@ ConvWeightCopies conv_plan_copies(const ConvDesc& d);
 // that many waves per workgroup - the conv's plan with fp16 copies would be the weight stream with that wave count; 0 = upload the
 // de-palettized tensor and run as ever.  d.w / w_tiled / w_pal are not looked at.
 int conv_plan_pal_waves(const ConvDesc& d);
+// A handle that holds W8A8 marks for this conv's weights asks the same question for plan tile 17: the one predicate of tile 14.
+inline int conv_plan_i8_waves(const ConvDesc& d) { return conv_plan_pal_waves(d); }
 // The same question for the small-M 1x1 GEMM (plan tile 15): 32 / 64 = this conv, uploaded as fp16 with the copies a handle would hold,
 // would get plan tile 12 by the library's own rule with that tile height - run it from the index stream of smgemm_pal_pack instead;
 // 0 = no (SD_SMGEMM=0, two sources, a LayerNorm fold, any other plan): upload the de-palettized tensor.
@@ -62,7 +65,7 @@ inline int conv_plan_bm_code(int bm) { return bm == 32 ? 1 : 2; }
 
 // What launches, as one line (sd_op_conv_plan_kernel): the kernel's name, then only the fields that kernel has -
 //   "igemm <bm>x<bn> ring<stages>[ kg2][ regs]"    "gemm_pipe <bm>x<bn> ring<stages>"    "halo_ks ring<stages>"
-//   "wstream waves<n>"   "wstream_pal waves<n>"    "wsgemm"    "bvgemm v<variant>"
+//   "wstream waves<n>"   "wstream_pal waves<n>"    "wstream_i8 waves<n>"                 "wsgemm"    "bvgemm v<variant>"
 //   "smgemm bm<bm>"      "smgemm_pal bm<bm>"       "smgeglu bm<bm>"                      "generic"
 std::string conv_plan_kernel_name(const ConvPlan& p);
 

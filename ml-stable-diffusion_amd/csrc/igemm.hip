@@ -1147,7 +1147,7 @@ int launch_conv(const ConvDesc& d, const ConvWorkspace& ws, hipStream_t s) {
   SD_REQUIRE(!twins || (d.out_mode == kOutHalf && !d.ln_colsum && !d.out_t && !d.debug && reduce_twin_ok(a.HoWo, a.N, d.n_twins, d.twin)),
              kInvalidArgument, "GroupNorm twins need a plain fp16 output and whole (sample, group) slices (HoWo=%d N=%d)", a.HoWo, a.N);
   const bool have_ws = !p.slab || (ws.partial && ws.partial_bytes >= p.workspace_bytes);
-  if (p.kernel == ConvKernel::Wstream || p.kernel == ConvKernel::WstreamPal) SD_REQUIRE(have_ws, kInternal, "wstream workspace too small (%zu < %zu)", ws.partial_bytes, p.workspace_bytes);
+  if (p.kernel == ConvKernel::Wstream || p.kernel == ConvKernel::WstreamPal || p.kernel == ConvKernel::WstreamI8) SD_REQUIRE(have_ws, kInternal, "wstream workspace too small (%zu < %zu)", ws.partial_bytes, p.workspace_bytes);
   SD_REQUIRE(have_ws, kInternal, "split-K workspace too small (%zu < %zu)", ws.partial_bytes, p.workspace_bytes);
   conv_plan_log(d, p);
   int gn_entries = 0;
@@ -1157,6 +1157,9 @@ int launch_conv(const ConvDesc& d, const ConvWorkspace& ws, hipStream_t s) {
       break;
     case ConvKernel::WstreamPal:   // the same slabs from palettized weights, then the same combine
       launch_wstream_pal(d, ws.partial, p.waves, s);
+      break;
+    case ConvKernel::WstreamI8:    // int8 weights and activations: exact int32 sums scaled into the same slabs, then the same combine
+      launch_wstream_i8(d, ws.partial, p.waves, s);
       break;
     case ConvKernel::HaloKs: gn_entries = launch_halo_ks(d, p, ws.partial, s); break;
     case ConvKernel::Igemm:

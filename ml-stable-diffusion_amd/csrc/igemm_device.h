@@ -466,7 +466,7 @@ IgemmArgs planned_args(const ConvDesc& d, const ConvPlan& p, float* partial) {
   a.slab = p.slab ? 1 : 0;
   a.partial = p.slab ? partial : nullptr;
   // (the weight stream has its own arguments: these then only feed the slab combine; the halo kernel splits whole 64-channel chunks)
-  if (p.kernel != ConvKernel::Wstream && p.kernel != ConvKernel::WstreamPal)
+  if (p.kernel != ConvKernel::Wstream && p.kernel != ConvKernel::WstreamPal && p.kernel != ConvKernel::WstreamI8)
     a.nk_per_split = cdiv(p.kernel == ConvKernel::HaloKs ? a.Ctot / BK : a.nk_total, p.splitk);
   return a;
 }

@@ -101,6 +101,12 @@ struct ConvDesc {
   // the kernel multiplies every LUT value by it as fold_layernorm_rows does on the host; without the fold it is null
   bool pal_geglu = false;
   const float* ln_gamma = nullptr;
+  // W8A8 (plan tile 17, wstream.hip wstream_kernel with NBITS = kWsI8): the int8 stream of weight_prep.h wstream_i8_pack, the output
+  // scale per column i8_scale[n] = fp32(s_a * s_w[n]) and i8_inv_s = fp32(1 / s_a), the factor the kernel quantizes its activations
+  // by.  A descriptor that carries them is pinned like a palettized one: it has no fp16 weights
+  const int8_t* w_i8 = nullptr;
+  const float* i8_scale = nullptr;
+  float i8_inv_s = 0.f;
   // weights in the fragment-major layout of wsgemm.hip (launch_wsgemm_retile), or null: the weight-stationary GEGLU kernel
   // (plan tile 10) needs them; launch_conv takes that kernel whenever they are there and no other plan was forced
   const half_t* w_ws = nullptr;
@@ -144,6 +150,9 @@ int launch_wstream(const ConvDesc& d, float* partial, int nw, hipStream_t s);   
 // the same launch from palettized weights (d.w_pal / pal_lut / pal_bits): every weight is looked up in the LUT in front of the same
 // MFMAs in the same order, so the slabs are bit-identical to launch_wstream's on the de-palettized weights
 int launch_wstream_pal(const ConvDesc& d, float* partial, int nw, hipStream_t s);
+// the same launch from int8 weights and activations quantized in the loader (d.w_i8 / i8_scale / i8_inv_s, plan tile 17): exact int32
+// sums over a workgroup's slices, scaled per column into the same fp32 slabs
+int launch_wstream_i8(const ConvDesc& d, float* partial, int nw, hipStream_t s);
 bool reduce_twin_ok(int HW, int N, int n_twins, const GnTwin* tw);
 void launch_reduce_twin(const float* partial, int S, int M, int N, int HW, const float* bias, const float* temb, int temb_stride,
                         const half_t* res, half_t* out, int n_twins, const GnTwin* tw, hipStream_t s);
@@ -507,6 +516,10 @@ struct ClipInputDesc {
   float mean[3], std[3];
 };
 void launch_clip_input(const uint8_t* rgb8, half_t* out, int B, const ClipInputDesc& d, size_t lds_bytes, hipStream_t s);
+
+// max |x| over x0 [n0] (and x1 [n1], or null) folded into *slot (a non-negative fp32, atomicMax on its bit pattern): the running
+// maximum since the slot was zeroed - the activation observers of a calibrating handle (W8A8) and sd_op_absmax
+void launch_absmax_half(const half_t* x0, size_t n0, const half_t* x1, size_t n1, float* slot, hipStream_t s);
 
 void launch_lds_poison(hipStream_t s);   // debug (SD_POISON_LDS): NaN patterns into every CU's LDS
 void launch_count_nonfinite_half(const void* p, size_t bytes, unsigned long long* out, hipStream_t s);   // debug scan (SD_NAN_TRACE)

@@ -474,4 +474,33 @@ void launch_count_nonfinite_half(const void* p, size_t bytes, unsigned long long
   SD_HIP(hipGetLastError());
 }
 
+// Activation calibration (W8A8, activation_quantization.py:141-203): max |x| over one or two fp16 tensors, folded into *slot - the bit
+// pattern of a non-negative fp32, whose unsigned order is its numeric order, so the running maximum is one atomicMax per wave.  NaN
+// elements are skipped (fmaxf keeps the other operand); +-inf gives +inf.  Grid-stride, eight halves per load where the size allows.
+__global__ __launch_bounds__(256) void absmax_half_kernel(const half_t* __restrict__ x0, size_t n0, const half_t* __restrict__ x1, size_t n1,
+                                                          unsigned* __restrict__ slot) {
+  float m = 0.f;
+  const size_t step = (size_t)gridDim.x * blockDim.x, t0 = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  for (int src = 0; src < 2; ++src) {
+    const half_t* x = src ? x1 : x0;
+    const size_t n = src ? n1 : n0, n8 = n / 8;
+    if (!x) continue;
+    for (size_t i = t0; i < n8; i += step) {
+      const half8 v = *reinterpret_cast<const half8*>(x + i * 8);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) m = fmaxf(m, fabsf((float)v[e]));
+    }
+    for (size_t i = n8 * 8 + t0; i < n; i += step) m = fmaxf(m, fabsf((float)x[i]));
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+  if ((threadIdx.x & 63) == 0 && m > 0.f) atomicMax(slot, __float_as_uint(m));
+}
+void launch_absmax_half(const half_t* x0, size_t n0, const half_t* x1, size_t n1, float* slot, hipStream_t s) {
+  const size_t n = std::max(n0, x1 ? n1 : 0);
+  const unsigned blocks = (unsigned)std::min<size_t>((n / 8 + 255) / 256 + 1, 256);
+  hipLaunchKernelGGL(absmax_half_kernel, dim3(blocks), dim3(256), 0, s, x0, n0, x1, x1 ? n1 : 0, reinterpret_cast<unsigned*>(slot));
+  SD_HIP(hipGetLastError());
+}
+
 }  // namespace sd

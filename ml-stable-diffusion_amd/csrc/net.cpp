@@ -13,7 +13,7 @@
 namespace sd {
 
 Net::Net(const sd_unet_config& cfg, const WeightStore& ws, int device)
-    : cfg_(cfg), ws_(&ws), f32_(cfg.compute_fp32 != 0), pal_tensors_((int)ws.palettes()) {
+    : cfg_(cfg), ws_(&ws), f32_(cfg.compute_fp32 != 0), pal_tensors_((int)ws.palettes()), i8_marked_((int)ws.w8a8_marks()) {
   SD_REQUIRE(cfg.n_levels >= 1 && cfg.n_levels <= SD_MAX_LEVELS, kInvalidArgument, "n_levels=%d", cfg.n_levels);
   SD_REQUIRE(cfg.batch >= 1 && cfg.height >= 1 && cfg.width >= 1, kInvalidArgument, "bad batch/size");
   SD_REQUIRE(cfg.norm_num_groups >= 1 && cfg.norm_num_groups <= 64, kUnsupported, "norm_num_groups=%d",
@@ -119,8 +119,50 @@ Tensor Net::conv(std::vector<Op>& ops, const std::string& name, const Tensor& x,
     ap.pal_bm = pal_bm;
     return conv_w(ops, name, nullptr, b, x, ap);
   }
+  // W8A8 (the store's marks, WeightStore::quantize_w8a8): plan tile 17 exactly where the conv's plan would be tile 9 - the predicate of
+  // tile 14.  Such a layer uploads the int8 stream and cs and no fp16 copy; a marked layer with any other plan runs fp16 as ever (the
+  // reference's "skipped layer").  An observing store (calibration) puts an absmax op over the conv's source(s) in front of every
+  // conv tile 17 could take: an ordinary member of the launch list that writes one slot nothing else reads.
+  const W8A8Mark* i8 = ws_->w8a8(name + ".weight");
+  const int i8_waves = ((i8 || ws_->observe()) && !pal && !a.silu_out && !a.ln_colsum) ? conv_plan_i8_waves(conv_shape(name, x, a)) : 0;
+  if (ws_->observe() && i8_waves) {
+    float* slot = ll_.arena.alloc_n<float>(1);   // (the arena is zeroed: the running maximum starts at 0)
+    observed_.push_back({name + ".weight", slot});
+    const half_t *p0 = x.p, *p1 = a.x2 ? a.x2->p : nullptr;
+    const size_t n0 = x.numel(), n1 = a.x2 ? a.x2->numel() : 0;
+    ops.push_back([=](hipStream_t s) { launch_absmax_half(p0, n0, p1, n1, slot, s); });
+    ops.back().label = "absmax " + name;
+  }
+  if (i8 && i8_waves) {
+    const size_t expect = (size_t)a.cout * cin * a.k * a.k;
+    SD_REQUIRE(ws_->get(name + ".weight").numel() == expect && i8->q.size() == expect && i8->w_scale.size() == (size_t)a.cout, kInvalidArgument,
+               "%s.weight: expected %zu W8A8 values (%d,%d,%d,%d)", name.c_str(), expect, a.cout, cin, a.k, a.k);
+    const W8A8HostCopy h = w8a8_host_copy((name + ".weight").c_str(), i8->q.data(), i8->w_scale.data(), i8->act_absmax, a.cout, cin, a.k);
+    int8_t* ds = ll_.arena.alloc_n<int8_t>(h.stream.size());
+    SD_HIP(hipMemcpy(ds, h.stream.data(), h.stream.size(), hipMemcpyHostToDevice));
+    float* dcs = ll_.arena.alloc_n<float>(h.cs.size());
+    SD_HIP(hipMemcpy(dcs, h.cs.data(), h.cs.size() * sizeof(float), hipMemcpyHostToDevice));
+    ++i8_applied_;
+    i8_bytes_ += h.stream.size() + h.cs.size() * sizeof(float);
+    i8_names_.push_back(name + ".weight");
+    ConvArgs ai = a;
+    ai.i8_stream = ds;
+    ai.i8_scale = dcs;
+    ai.i8_inv_s = h.inv_s;
+    ai.i8_waves = i8_waves;
+    return conv_w(ops, name, nullptr, b, x, ai);
+  }
   const half_t* w = upload_conv_weight(name, a.cout, cin, a.k, geglu);
   return conv_w(ops, name, w, b, x, a);
+}
+
+int Net::activation_range(int index, std::string* name, float* absmax) {
+  if (index < 0 || index >= (int)observed_.size()) return (int)observed_.size();
+  SD_HIP(hipSetDevice(ll_.device));
+  SD_HIP(hipStreamSynchronize(ll_.stream));
+  SD_HIP(hipMemcpy(absmax, observed_[(size_t)index].second, sizeof(float), hipMemcpyDeviceToHost));
+  *name = observed_[(size_t)index].first;
+  return (int)observed_.size();
 }
 
 int Net::pal_geglu_bm(const std::string& name, const Tensor& x, const ConvArgs& a, bool ln) const {
@@ -245,6 +287,12 @@ Tensor Net::conv_w(std::vector<Op>& ops, const std::string& name, const half_t* 
   } else if (a.pal_stream) {   // pinned to the palettized weight stream (plan tile 14) with the wave count Net::conv read off the plan
     d.tile = 14;
     d.staging = conv_plan_waves_code(a.pal_waves);
+  } else if (a.i8_stream) {    // pinned to the int8 weight stream (plan tile 17) likewise
+    d.w_i8 = a.i8_stream;
+    d.i8_scale = a.i8_scale;
+    d.i8_inv_s = a.i8_inv_s;
+    d.tile = 17;
+    d.staging = conv_plan_waves_code(a.i8_waves);
   }
   Tensor out;
   if (ln && a.n_trans > 0) {   // fused q|k|v: [M][n_trans] row-major + V^T [B][cout - n_trans][ldT]
@@ -280,7 +328,7 @@ Tensor Net::conv_w(std::vector<Op>& ops, const std::string& name, const half_t* 
   const int cin = x.C + (x2 ? x2->C : 0);
   if (conv_fast_path_ok(d) && !a.silu_out) {
     // the pre-tiled (fragment-major) weight copies the plan of this conv reads: exactly what the planner names
-    const ConvWeightCopies copies = d.w_pal ? ConvWeightCopies{false, false, false} : conv_plan_copies(d);
+    const ConvWeightCopies copies = (d.w_pal || d.w_i8) ? ConvWeightCopies{false, false, false} : conv_plan_copies(d);
     if (copies.wstream && !ln) {   // small-M layers: the weight-streaming kernel (plan tile 9; never a LayerNorm-fold / q|k|v op)
       half_t* wt = ll_.arena.alloc_n<half_t>(wstream_tiled_halves(cout, cin, k));
       launch_wstream_retile(w, wt, cout, cin, k, ll_.stream);
@@ -312,7 +360,8 @@ Tensor Net::conv_w(std::vector<Op>& ops, const std::string& name, const half_t* 
   // trailing "#kind,ksize,stride,up,Ctot,N,M" is the plan-table key of this op (tools/tune_plans.py)
   const int kind = d.out_t ? 3 : (geglu ? 2 : (ln ? 1 : 0));
   // ("+pal<bits>": the op reads its weights from their palette, plan tile 14 or 15; plan tile 16 is "geglu+pal<bits>[+ln]")
-  const std::string palmark = d.w_pal ? "+pal" + std::to_string(d.pal_bits) : std::string();
+  // ("+w8a8": the op runs from int8 weights and quantizes its activations, plan tile 17)
+  const std::string palmark = d.w_pal ? "+pal" + std::to_string(d.pal_bits) : d.w_i8 ? std::string("+w8a8") : std::string();
   const std::string lnmark = ln ? "+ln" : "";
   snprintf(buf, sizeof(buf), "%s%s%s %d->%d @%dx%d M=%d K=%d %s #%d,%d,%d,%d,%d,%d,%d", k == 3 ? "conv3x3" : (geglu ? (d.pal_geglu ? "geglu" : "geglu1x1") : "gemm1x1"),
            (d.pal_geglu ? palmark : lnmark).c_str(), (d.pal_geglu ? lnmark : palmark).c_str(), cin, cout, d.Ho, d.Wo, x.B * d.Ho * d.Wo, cin * k * k, name.c_str(), kind, k, a.stride, a.up, cin, cout,

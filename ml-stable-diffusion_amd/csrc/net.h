@@ -85,6 +85,12 @@ struct ConvArgs {
   // smgeglu_pal_pack, pal_bm = 128, ln_gamma the fp32 norm weight on the device when ln_colsum is set (Net::upload_pal_geglu fills them)
   bool pal_geglu = false;
   const float* ln_gamma = nullptr;
+  // conv_w only, set by Net::conv for a W8A8-marked tensor whose conv runs from int8 (ConvDesc::w_i8 / i8_scale / i8_inv_s; w is then
+  // null): the op is pinned to plan tile 17 with i8_waves (4 / 8) waves per workgroup
+  const int8_t* i8_stream = nullptr;
+  const float* i8_scale = nullptr;
+  float i8_inv_s = 0.f;
+  int i8_waves = 0;
 };
 
 class Net {
@@ -106,6 +112,17 @@ class Net {
     *n_streamed = pal_streamed_;
     *stream_bytes = pal_stream_bytes_;
   }
+  // W8A8: tensors of the weight store that arrived with a mark, convs that run from int8 (plan tile 17), and the bytes of those convs'
+  // int8 streams and scale vectors
+  void w8a8_info(int* n_marked, int* n_applied, size_t* bytes) const {
+    *n_marked = i8_marked_;
+    *n_applied = i8_applied_;
+    *bytes = i8_bytes_;
+  }
+  // the activation observers of a handle built from an observing store, in launch order: fills slot `index` (name of the conv's weight
+  // tensor, running max |x| of its source(s) since creation) when it exists; returns the number of slots
+  int activation_range(int index, std::string* name, float* absmax);
+  const std::vector<std::string>& w8a8_applied() const { return i8_names_; }   // weight tensors of the convs that run from int8, in build order
   const sd_unet_config& config() const { return cfg_; }
 
  protected:
@@ -155,6 +172,10 @@ class Net {
   ConvDesc conv_shape(const std::string& name, const Tensor& x, const ConvArgs& a) const;
   int pal_tensors_ = 0, pal_streamed_ = 0;
   size_t pal_stream_bytes_ = 0;
+  int i8_marked_ = 0, i8_applied_ = 0;
+  size_t i8_bytes_ = 0;
+  std::vector<std::pair<std::string, float*>> observed_;
+  std::vector<std::string> i8_names_;
   Tensor conv_f32(std::vector<Op>& ops, const std::string& name, const Tensor& x, const ConvArgs& a);
   Tensor group_norm_f32(std::vector<Op>& ops, const std::string& name, const Tensor& x, float eps, bool silu);
 };

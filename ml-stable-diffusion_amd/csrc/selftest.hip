@@ -6,6 +6,10 @@
 //   bit 1  the DPP butterfly (quad_perm xor1, xor2, row_half_mirror, row_mirror) + the
 //          v_permlane16_swap xor-16 step used for the ORIGINAL-attention row reductions
 //   bit 2  the v_permlane32_swap xor-32 exchange of the SPLIT_EINSUM softmax
+//   bit 3  v_mfma_i32_32x32x32_i8 (the W8A8 weight stream, wstream.hip): 16 int8 per lane and operand,
+//          A: lane l holds A[i=l&31][k=16*(l>>5)+e], B: B[k=16*(l>>5)+e][j=l&31], e = 0..15 (byte e of the four registers),
+//          D as above.  Checked with A = identity against an asymmetric B (D must be B: the k of every (lane, byte) is
+//          then read off directly) and with asymmetric data on both sides
 // Asymmetric integer data so a transposed or permuted mapping cannot pass by accident.
 #include "kernels.h"
 
@@ -25,6 +29,29 @@ __global__ void mfma_probe(const half_t* __restrict__ A, const half_t* __restric
 #pragma unroll
   for (int r = 0; r < 16; ++r) c[r] = 0.f;
   c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int i = (r & 3) + 8 * (r >> 2) + 4 * (l >> 5), j = l & 31;
+    D[i * 32 + j] = c[r];
+  }
+}
+
+typedef int intx4 __attribute__((ext_vector_type(4)));
+typedef int intx16 __attribute__((ext_vector_type(16)));
+
+__global__ void mfma_i8_probe(const int8_t* __restrict__ A, const int8_t* __restrict__ B, int* __restrict__ D) {
+  const int l = threadIdx.x;
+  intx4 a = {0, 0, 0, 0}, b = {0, 0, 0, 0};
+#pragma unroll
+  for (int e = 0; e < 16; ++e) {
+    const int k = 16 * (l >> 5) + e;
+    a[e >> 2] |= (int)((unsigned)(unsigned char)A[(l & 31) * 32 + k] << (8 * (e & 3)));   // A[32][32] row-major
+    b[e >> 2] |= (int)((unsigned)(unsigned char)B[k * 32 + (l & 31)] << (8 * (e & 3)));   // B[32][32] row-major
+  }
+  intx16 c;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) c[r] = 0;
+  c = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, c, 0, 0, 0);
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int i = (r & 3) + 8 * (r >> 2) + 4 * (l >> 5), j = l & 31;
@@ -150,6 +177,40 @@ int selftest_mfma() {
     }
   }
   if (bad) result |= 4;
+  {   // bit 3: the int8 form, A = identity first, then asymmetric data on both sides
+    int8_t hA8[32 * 32], hB8[32 * 32], *dA8, *dB8;
+    int ref8[32 * 32], got8[32 * 32], *dD8;
+    SD_HIP(hipMalloc(&dA8, sizeof(hA8)));
+    SD_HIP(hipMalloc(&dB8, sizeof(hB8)));
+    SD_HIP(hipMalloc(&dD8, sizeof(got8)));
+    for (int k = 0; k < 32; ++k)
+      for (int j = 0; j < 32; ++j) hB8[k * 32 + j] = (int8_t)((k * 37 + j * 11) % 255 - 127);   // -127 .. 127, no row or column alike
+    bad = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+      for (int i = 0; i < 32; ++i)
+        for (int k = 0; k < 32; ++k) hA8[i * 32 + k] = pass == 0 ? (int8_t)(i == k) : (int8_t)((i * 29 + k * 53) % 255 - 127);
+      for (int i = 0; i < 32; ++i)
+        for (int j = 0; j < 32; ++j) {
+          int sum = 0;
+          for (int k = 0; k < 32; ++k) sum += (int)hA8[i * 32 + k] * (int)hB8[k * 32 + j];
+          ref8[i * 32 + j] = sum;
+        }
+      SD_HIP(hipMemcpy(dA8, hA8, sizeof(hA8), hipMemcpyHostToDevice));
+      SD_HIP(hipMemcpy(dB8, hB8, sizeof(hB8), hipMemcpyHostToDevice));
+      hipLaunchKernelGGL(mfma_i8_probe, dim3(1), dim3(64), 0, 0, dA8, dB8, dD8);
+      SD_HIP(hipDeviceSynchronize());
+      SD_HIP(hipMemcpy(got8, dD8, sizeof(got8), hipMemcpyDeviceToHost));
+      for (int i = 0; i < 32 * 32; ++i)
+        if (got8[i] != ref8[i]) {
+          if (bad < 8) fprintf(stderr, "[sd selftest] mfma i8 (pass %d) D[%d][%d] = %d, expected %d\n", pass, i / 32, i % 32, got8[i], ref8[i]);
+          ++bad;
+        }
+    }
+    if (bad) result |= 8;
+    (void)hipFree(dA8);
+    (void)hipFree(dB8);
+    (void)hipFree(dD8);
+  }
   (void)hipFree(dA);
   (void)hipFree(dB);
   (void)hipFree(dD);

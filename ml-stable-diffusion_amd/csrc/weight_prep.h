@@ -2,6 +2,7 @@
 // call these, so an operator test checks the layout the step runs.  Plain host C++: no HIP call, no allocation.
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <vector>
@@ -106,6 +107,72 @@ inline void wstream_pal_pack(const uint8_t* indices, int N, int Ctot, int ksize,
         }
         w.flush(dst + ((size_t)strip * nslices + slice) * Q * 1024, lane);
       }
+}
+
+// W8A8 (plan tile 17, wstream.hip's int8 source; the reference's quantize_cumulative_config, activation_quantization.py:141-203:
+// symmetric, per-output-channel weights, per-tensor activations - parity with coremltools' quantizer unpinned).
+// The weight quantizer, w [N][per_row] fp32 (a conv's (Cout, Ctot, k, k) row by row): s_w[n] = absmax_n / 127 (an all-zero row: 1),
+// q = clip(rint(w / s_w[n]), -127, 127) - fp32 division, round to nearest even (the default rounding mode; nearbyintf raises no
+// inexact flag).  Every element must be finite (kInvalidArgument).  Returns the squared error sum (w - q * s_w)^2 in float64.
+inline double w8a8_quantize_weight(const float* w, int N, size_t per_row, int8_t* q, float* scale) {
+  double err = 0.0;
+  for (int n = 0; n < N; ++n) {
+    const float* row = w + (size_t)n * per_row;
+    float amax = 0.f;
+    for (size_t i = 0; i < per_row; ++i) {
+      SD_REQUIRE(std::isfinite(row[i]), kInvalidArgument, "w8a8 quantizer: row %d element %zu is not finite", n, i);
+      amax = std::max(amax, std::fabs(row[i]));
+    }
+    const float s = amax > 0.f ? amax / 127.0f : 1.0f;
+    scale[n] = s;
+    for (size_t i = 0; i < per_row; ++i) {
+      const float r = std::min(std::max(std::nearbyintf(row[i] / s), -127.0f), 127.0f);
+      q[(size_t)n * per_row + i] = (int8_t)r;
+      const double dlt = (double)row[i] - (double)r * (double)s;
+      err += dlt * dlt;
+    }
+  }
+  return err;
+}
+// The int8 weight stream of wstream.hip: [N / 32][Ctot / 32][taps][64 lanes][16 B].  Lane l of the (strip, slice) wave holds, for tap
+// t, the 16 weights of output row strip * 32 + (l & 31), input channels slice * 32 + (l >> 5) * 16 + (0 .. 15): one operand of
+// v_mfma_i32_32x32x32_i8, loaded as one coalesced 1-KB wave load.  q [N][Ctot][k][k] (the checkpoint's order); dst holds N * Ctot * k * k bytes.
+inline size_t wstream_i8_bytes(int N, int Ctot, int ksize) { return (size_t)N * Ctot * ksize * ksize; }
+inline void wstream_i8_pack(const int8_t* q, int N, int Ctot, int ksize, int8_t* dst) {
+  const int taps = ksize * ksize, nslices = Ctot / 32;
+  for (int strip = 0; strip < N / 32; ++strip)
+    for (int slice = 0; slice < nslices; ++slice)
+      for (int t = 0; t < taps; ++t)
+        for (int lane = 0; lane < 64; ++lane) {
+          const int8_t* src = q + ((size_t)(strip * 32 + (lane & 31)) * Ctot + slice * 32 + (lane >> 5) * 16) * taps + t;
+          int8_t* out = dst + ((((size_t)strip * nslices + slice) * taps + t) * 64 + lane) * 16;
+          for (int e = 0; e < 16; ++e) out[e] = src[(size_t)e * taps];
+        }
+}
+// What an upload of a W8A8 conv starts from (sd_op_conv2d_w8a8, Net::conv): no value of -128 (the symmetric scheme has none), finite
+// positive scales, the packed stream, cs[n] = fp32(s_a * s_w[n]) with s_a = act_absmax / 127, and inv_s = fp32(1 / s_a).
+struct W8A8HostCopy {
+  std::vector<int8_t> stream;
+  std::vector<float> cs;
+  float inv_s = 0.f;
+};
+inline bool w8a8_absmax_ok(float act_absmax) { return std::isfinite(act_absmax) && act_absmax > 0.f; }
+inline W8A8HostCopy w8a8_host_copy(const char* what, const int8_t* q, const float* w_scale, float act_absmax, int N, int Ctot, int ksize) {
+  SD_REQUIRE(w8a8_absmax_ok(act_absmax), kInvalidArgument, "%s: act_absmax = %g, not a positive finite number", what, (double)act_absmax);
+  const size_t n_el = wstream_i8_bytes(N, Ctot, ksize);
+  for (size_t i = 0; i < n_el; ++i) SD_REQUIRE(q[i] != -128, kInvalidArgument, "%s: weight value -128 at element %zu, the symmetric range is [-127, 127]", what, i);
+  W8A8HostCopy h;
+  const float s_a = act_absmax / 127.0f;
+  h.inv_s = 1.0f / s_a;
+  SD_REQUIRE(std::isfinite(h.inv_s) && h.inv_s > 0.f, kInvalidArgument, "%s: act_absmax = %g has no finite inverse scale", what, (double)act_absmax);
+  h.cs.resize(N);
+  for (int n = 0; n < N; ++n) {
+    SD_REQUIRE(std::isfinite(w_scale[n]) && w_scale[n] > 0.f, kInvalidArgument, "%s: w_scale[%d] = %g, not a positive finite number", what, n, (double)w_scale[n]);
+    h.cs[n] = s_a * w_scale[n];
+  }
+  h.stream.resize(n_el);
+  wstream_i8_pack(q, N, Ctot, ksize, h.stream.data());
+  return h;
 }
 
 // The palettized weight stream of smgemm.hip (plan tile 15), indices [N][K] (a 1x1 conv / Linear), N % 16 == 0, K % 64 == 0.  The wave

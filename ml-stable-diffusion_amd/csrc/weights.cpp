@@ -1,5 +1,7 @@
 #include "weights.h"
 
+#include "weight_prep.h"
+
 #include <algorithm>
 #include <cstdarg>
 #include <cstring>
@@ -75,6 +77,32 @@ void WeightStore::add(const std::string& name, const void* data, int dtype, cons
   }
   map_[name] = std::move(t);
   pal_.erase(name);   // plain values replace whatever palette the name had
+  i8_.erase(name);    // ... and whatever W8A8 mark
+}
+
+// ---- W8A8 marks ------------------------------------------------------------------------------
+const W8A8Mark* WeightStore::w8a8(const std::string& name) const {
+  auto it = i8_.find(name);
+  return it == i8_.end() ? nullptr : &it->second;
+}
+
+double WeightStore::quantize_w8a8(const std::string& name, float act_absmax) {
+  auto it = map_.find(name);
+  if (it == map_.end()) fail(kNotFound, "quantize_w8a8: the store has no tensor '%s'", name.c_str());
+  const HostTensor& t = it->second;
+  SD_REQUIRE(t.shape.size() == 4 && t.shape[2] == t.shape[3] && t.numel() > 0, kInvalidArgument,
+             "quantize_w8a8(%s): not a conv weight (Cout, Cin, k, k)", name.c_str());
+  SD_REQUIRE(!pal_.count(name), kInvalidArgument, "quantize_w8a8(%s): the tensor carries a palette; a tensor is palettized or W8A8, not both",
+             name.c_str());
+  SD_REQUIRE(w8a8_absmax_ok(act_absmax), kInvalidArgument, "quantize_w8a8(%s): act_absmax = %g, not a positive finite number", name.c_str(),
+             (double)act_absmax);
+  W8A8Mark m;
+  m.act_absmax = act_absmax;
+  m.q.resize(t.numel());
+  m.w_scale.resize((size_t)t.shape[0]);
+  const double err = w8a8_quantize_weight(t.data.data(), (int)t.shape[0], t.numel() / (size_t)t.shape[0], m.q.data(), m.w_scale.data());
+  i8_[name] = std::move(m);
+  return err;
 }
 
 // ---- palettes --------------------------------------------------------------------------------
@@ -130,6 +158,7 @@ double WeightStore::palettize(const std::string& name, int nbits) {
   SD_REQUIRE(palette_bits_ok(nbits), kInvalidArgument, "palettize(%s): nbits = %d, not one of 1, 2, 4, 6, 8", name.c_str(), nbits);
   auto it = map_.find(name);
   if (it == map_.end()) fail(kNotFound, "palettize: the store has no tensor '%s'", name.c_str());
+  SD_REQUIRE(!i8_.count(name), kInvalidArgument, "palettize(%s): the tensor carries a W8A8 mark; a tensor is palettized or W8A8, not both", name.c_str());
   HostTensor& t = it->second;
   const size_t n_el = t.numel();
   const int k = 1 << nbits;
@@ -217,6 +246,7 @@ void WeightStore::add_palettized(const std::string& name, const void* lut_f16, i
   for (size_t e = 0; e < n_el; ++e) t.data[e] = half_bits_to_float(p.lut[indices[e]]);
   map_[name] = std::move(t);
   pal_[name] = std::move(p);
+  i8_.erase(name);   // new values: a W8A8 mark of the old ones is gone
 }
 
 // Public SD 1.x / 2.x VAE checkpoints keep the deprecated attention names (query / key / value /

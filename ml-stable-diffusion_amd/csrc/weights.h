@@ -25,8 +25,26 @@ struct Palette {
   std::vector<uint8_t> indices;   // one per element, in the tensor's own order
 };
 
+// A W8A8 mark on a conv weight (the reference's quantize_cumulative_config, activation_quantization.py:141-203: symmetric int8,
+// one scale per output channel for the weights, one per tensor for the activations the conv reads; parity with coremltools'
+// quantizer unpinned).  The HostTensor beside it keeps the untouched values: a handle runs the conv from `q` only where its plan is
+// the weight stream (wstream.hip, plan tile 17), every other consumer reads fp16 as ever - the reference's "skipped layer".
+struct W8A8Mark {
+  std::vector<int8_t> q;        // one per element, in the tensor's own order, -127 .. 127
+  std::vector<float> w_scale;   // [Cout]
+  float act_absmax = 0.f;       // s_a = act_absmax / 127
+};
+
 class WeightStore {
  public:
+  // marks the 4-D tensor `name` (kNotFound when absent; kInvalidArgument: not (Cout, Cin, k, k), a palette on it, act_absmax not a
+  // positive finite number, a non-finite weight); returns the squared weight error
+  double quantize_w8a8(const std::string& name, float act_absmax);
+  const W8A8Mark* w8a8(const std::string& name) const;   // nullptr: no mark
+  size_t w8a8_marks() const { return i8_.size(); }
+  // handles built from this store put an absmax observer in front of every conv plan tile 17 could take
+  void set_observe(bool on) { observe_ = on; }
+  bool observe() const { return observe_; }
   void add(const std::string& name, const void* data, int dtype /*0 f16, 1 f32, 2 bf16*/,
            const int64_t* shape, int ndim);
   void load_safetensors(const std::string& path, const std::string& prefix);
@@ -45,6 +63,8 @@ class WeightStore {
  private:
   std::map<std::string, HostTensor> map_;
   std::map<std::string, Palette> pal_;
+  std::map<std::string, W8A8Mark> i8_;
+  bool observe_ = false;
 };
 
 }  // namespace sd

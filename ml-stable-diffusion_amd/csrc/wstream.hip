@@ -21,6 +21,15 @@
 //                         and the slab store - is the same text, so the slabs of tile 14 are bit-identical to tile 9's on
 //                         lut[indices].  Within either source the order of memory operations is fixed: activations first, then
 //                         weights or indices (the compiler's in-order vmcnt waits count on it).
+//                         A THIRD SOURCE (NBITS = kWsI8, plan tile 17): W8A8 - int8 weights with one fp32 scale per output
+//                         channel and int8 activations with one scale per layer (the reference's quantize_cumulative_config,
+//                         activation_quantization.py:141-203: symmetric, per-tensor activations, per-channel weights; parity with
+//                         coremltools' quantizer unpinned).  The weights arrive as they are multiplied - one coalesced 16-B load
+//                         per lane per tap (weight_prep.h wstream_i8_pack), no decode - the fp16 activations are quantized in
+//                         registers between their load and the LDS store, x_q = clip(rint(fp32(x) * inv_s), -127, 127) with NaN
+//                         -> 0 and +-inf -> +-127, and one v_mfma_i32_32x32x32_i8 per pixel tile per tap takes all 32 input
+//                         channels.  The NW slices are summed in int32 (exact, order-free: 8 x 288 x 127^2 < 2^31), converted
+//                         once and multiplied by cs[n] = fp32(s_a * s_w[n]); the fp32 slabs leave as ever.
 //   reduce_twin_kernel  - the slab combine, organised per (sample, GroupNorm group): it adds bias / timestep embedding /
 //                         residual, stores the fp16 tensor AND - because a workgroup holds whole (sample, group) slices in
 //                         registers - the GroupNorm(+SiLU) of it that the consuming resnet / SpatialTransformer asks for
@@ -29,6 +38,9 @@
 //                         of the concatenated operand.  The separate GroupNorm launch and its round trip disappear.
 #include "kernels.h"
 #include "pal_decode.h"
+
+#include <cmath>
+#include <type_traits>
 
 namespace sd {
 
@@ -208,20 +220,62 @@ struct WsArgs {
   int M, N;
   const uint8_t* pal;   // palettized source: the index streams [N / 32][nslices][Q][64 lanes][16 B]
   const half_t* lut;    //   and the tensor's LUT: kPalLutHalves entries (its 2^NBITS, zero-padded)
+  const int8_t* w8;     // int8 source: pre-tiled weights [N / 32][nslices][TAPS][64 lanes][16 B]
+  const float* cs;      //   [N] output scale s_a * s_w[n]
+  float inv_s;          //   1 / s_a
 };
 
 constexpr int WS_REGION = 16384;   // per-wave LDS: the 32-channel halo slice (<= 200 pixels x 80 B), later its 128 x 32 fp32 tile
 constexpr int WS_ROWB = 80;        // 64 B of channels + 16 B pad: the 16 lanes of a ds_read_b128 group hit distinct banks
 typedef unsigned uintx2 __attribute__((ext_vector_type(2)));
-constexpr int ws_region(int nbits) { return WS_REGION + (nbits ? kPalLutHalves * 2 : 0); }   // palettized: + the wave's copy of the LUT
+constexpr int ws_region(int nbits) { return WS_REGION + (nbits > 0 ? kPalLutHalves * 2 : 0); }   // palettized: + the wave's copy of the LUT
+constexpr int kWsI8 = -8;          // NBITS of the int8 source
+typedef int intx4 __attribute__((ext_vector_type(4)));
+typedef int intx16 __attribute__((ext_vector_type(16)));
+
+// The int8 source's LDS image of a wave's halo slice: 32 B (32 int8 channels) per pixel, NO per-pixel pad, halo rows PITCH pixels
+// apart, and the two 16-B halves of a pixel swapped where bit `g` of the pixel is set.  By the LDS bank rules (256-B bank row = 16
+// slots of 16 B; a ds_read_b128 is served in the lane groups {0-3,12-15,20-27}, {4-11,16-19,28-31} and the same + 32, and only lanes
+// of one group conflict): a group lies inside one 32-lane half, so its 16 lanes read the SAME half (hi) of 16 pixels and land on slot
+// (2 * pixel + (hi ^ g)) mod 16.  W = 8, 3x3: lanes m = 0..31 are pixels (y, x) = (m >> 3, m & 7) at halo pixel y * PITCH + x; with
+// PITCH = 12 the first group's pixels are {0-3}, {16-19}, {28-31}, {36-39}: mod 8 {0-3}, {0-3}, {4-7}, {4-7} - every residue twice,
+// once on an even and once on an odd halo row - so g = halo row & 1 gives 16 distinct slots (the second group: {4-7}, {12-15},
+// {24-27}, {40-43} -> {4-7}, {4-7}, {0-3}, {0-3}, likewise).  PITCH = 10, the halo's own width, puts four pixels of a group on one
+// residue (0, 14, 24, 30 -> 0, 6, 0, 6): 2-way at best with one swap bit.  A tap shift adds one constant to every pixel and flips g in
+// every lane or in none, so every tap is conflict-free.  W = 16: a group holds x = 0-3, 12-15 of one row and 4-11 of the next, all
+// eight residues once per row, g = row & 1 again, any pitch (18).  1x1: pixel = m, residues {0-3}, {4-7} (m = 12-15), {4-7}, {0-3}
+// (m = 20-27) - g = bit 4 of m separates the pairs.
+template <int TAPS, int WW>
+struct WsI8Image {
+  static constexpr int PITCH = TAPS == 9 ? (WW == 8 ? 12 : WW + 2) : 0;
+  static constexpr int SUB = 10 * PITCH;   // pixels of a sub-tile's image
+  // byte address of 16-B half `half` of pixel (sub-tile, halo row, halo column) / of row ml of the 1x1 form
+  static __device__ __forceinline__ int at(int sub, int hy, int hx, int half) { return ((sub * 10 + hy) * PITCH + hx) * 32 + ((half ^ hy) & 1) * 16; }
+  static __device__ __forceinline__ int at1(int ml, int half) { return ml * 32 + ((half ^ (ml >> 4)) & 1) * 16; }
+};
+static_assert(2 * WsI8Image<9, 8>::SUB * 32 <= WS_REGION && WsI8Image<9, 16>::SUB * 32 <= WS_REGION, "int8 halo image larger than a wave's region");
+
+// x_q = clip(rint(fp32(x) * inv_s), -127, 127): one product, v_rndne_f32, a clamp.  NaN -> 0 (it compares false with everything, the
+// select keeps 0); +-inf -> +-127 (the clamp saturates them like any large value).  Eight channels -> 8 bytes.
+__device__ __forceinline__ uintx2 ws_quantize8(const half8& x, float inv_s) {
+  unsigned b[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const float v = __builtin_rintf((float)x[e] * inv_s);
+    const float c = v == v ? fminf(fmaxf(v, -127.f), 127.f) : 0.f;
+    b[e] = (unsigned)(int)c & 0xffu;
+  }
+  return uintx2{b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24), b[4] | (b[5] << 8) | (b[6] << 16) | (b[7] << 24)};
+}
 
 // NW waves; TAPS 9 (3x3, stride 1, pad 1) or 1 (1x1); WW = image width of the 3x3 form (8: a 128-pixel block is two 8-row
-// sub-tiles, 16: one), ignored for TAPS == 1; NBITS = 0: fp16 weights (a.wt), else the index width of palettized ones (a.pal, a.lut).
+// sub-tiles, 16: one), ignored for TAPS == 1; NBITS = 0: fp16 weights (a.wt), > 0: the index width of palettized ones (a.pal, a.lut),
+// kWsI8: int8 weights and activations (a.w8, a.cs, a.inv_s).
 // grid (N / 32, ceil(nslices / NW), ceil(M / 128)).
 template <int NW, int TAPS, int WW, int NBITS>
 __global__ __launch_bounds__(NW * 64) void wstream_kernel(WsArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr bool PAL = NBITS > 0;
+  constexpr bool PAL = NBITS > 0, I8 = NBITS == kWsI8;
   constexpr int REGION = ws_region(NBITS);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -237,11 +291,11 @@ __global__ __launch_bounds__(NW * 64) void wstream_kernel(WsArgs a) {
   constexpr int NF = TAPS * 2;                           // weight fragments per wave
   constexpr int Q = PAL ? (NF * 8 * NBITS + 127) / 128 : 1;   // 16-B words of a lane's index stream
 
-  floatx16 acc[4];
+  typename std::conditional<I8, intx16, floatx16>::type acc[4];   // int8: exact int32 sums
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+    for (int r = 0; r < 16; ++r) acc[i][r] = 0;
 
   if (live) {
     // ---- activations first (they are waited for first; loads of one wave return in order) ----
@@ -274,10 +328,15 @@ __global__ __launch_bounds__(NW * 64) void wstream_kernel(WsArgs a) {
     }
     // ---- the whole weight slice of this wave, all in flight: NF fully coalesced 1-KB fragments, or the LUT (8 B per lane: the
     // padded 512 B) and the Q coalesced 1-KB words of the index stream ----
-    half8 bf[PAL ? 1 : NF];
+    half8 bf[PAL || I8 ? 1 : NF];
     uintx4 wq[Q];
     uintx2 lv;
-    if constexpr (PAL) {
+    intx4 bw[I8 ? TAPS : 1];   // int8: one 16-B fragment per tap - this lane's output row, 16 input channels
+    if constexpr (I8) {
+      const intx4* wp = reinterpret_cast<const intx4*>(a.w8) + ((size_t)strip * a.nslices + slice) * (TAPS * 64) + lane;
+#pragma unroll
+      for (int t = 0; t < TAPS; ++t) bw[t] = __builtin_nontemporal_load(wp + t * 64);
+    } else if constexpr (PAL) {
       lv = *reinterpret_cast<const uintx2*>(a.lut + lane * 4);
       const uintx4* sp = reinterpret_cast<const uintx4*>(a.pal) + ((size_t)strip * a.nslices + slice) * (Q * 64) + lane;
 #pragma unroll
@@ -287,70 +346,118 @@ __global__ __launch_bounds__(NW * 64) void wstream_kernel(WsArgs a) {
 #pragma unroll
       for (int j = 0; j < NF; ++j) bf[j] = __builtin_nontemporal_load(reinterpret_cast<const half8*>(wp + (size_t)j * 512));
     }
-    // ---- halo slice (and LUT) -> this wave's LDS region (only this wave reads it: no barrier) ----
+    if constexpr (I8) {
+      // ---- halo slice, quantized in registers, -> this wave's LDS region in the image of WsI8Image ----
+      using Img = WsI8Image<TAPS, WW>;
+      const float inv_s = a.inv_s;
 #pragma unroll
-    for (int i = 0; i < NL; ++i) {
-      const int px = i * 16 + (lane >> 2);
-      if (px < HP) *reinterpret_cast<half8*>(region + px * WS_ROWB + piece * 16) = xa[i];
-    }
-    if constexpr (PAL) *reinterpret_cast<uintx2*>(region + WS_REGION + lane * 8) = lv;
-    const unsigned short* const lutp = reinterpret_cast<const unsigned short*>(region + WS_REGION);
-    // ---- fragments: lane (m = lane & 31, hi = lane >> 5) of pixel tile i reads 16 B of its pixel's row under the tap shift ----
-    int hb[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int ml = i * 32 + (lane & 31);
-      if constexpr (TAPS == 9) {
-        const int sub = ml / (8 * WW), rem = ml - sub * (8 * WW);
-        const int y = rem / WW, x = rem - y * WW;
-        hb[i] = (sub * HPS + y * HW_ + x) * WS_ROWB + (lane >> 5) * 16;
-      } else {
-        hb[i] = ml * WS_ROWB + (lane >> 5) * 16;
+      for (int i = 0; i < NL; ++i) {
+        const int px = i * 16 + (lane >> 2);
+        int at;
+        if constexpr (TAPS == 9) {
+          const int sub = px / HPS, r = px - sub * HPS;
+          const int hy = r / HW_, hx = r - hy * HW_;
+          at = Img::at(sub, hy, hx, piece >> 1);
+        } else {
+          at = Img::at1(px, piece >> 1);
+        }
+        if (px < HP) *reinterpret_cast<uintx2*>(region + at + (piece & 1) * 8) = ws_quantize8(xa[i], inv_s);
       }
-    }
-    // fragments of tap t+1 are read while the MFMAs of tap t issue (register double buffer; the first version read two
-    // fragments, waited, issued two MFMAs: the LDS latency was exposed 36 times per wave)
-    auto read_tap = [&](half8 (&xf)[8], int tap) {
-      const int toff = TAPS == 9 ? ((tap / 3) * HW_ + (tap % 3)) * WS_ROWB : 0;
+      // ---- fragments: lane (m = lane & 31, hi = lane >> 5) of pixel tile i reads the 16 channels hi * 16 .. of its pixel under the tap shift ----
+      int hb[4];
 #pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) xf[h * 4 + i] = *reinterpret_cast<const half8*>(region + hb[i] + toff + h * 32);
-    };
-    // palettized: the two weight fragments of tap t + 1 are decoded beside them (fragments 2 tap, 2 tap + 1 of the lane's stream:
-    // compile-time field positions once the tap loop is unrolled)
-    auto decode_tap = [&](half8 (&wf)[2], int tap) {
-#pragma unroll
-      for (int h = 0; h < 2; ++h) wf[h] = pal_decode<NBITS>(wq, tap * 2 + h, lutp);
-    };
-    half8 xfa[8], xfb[8], wfa[2], wfb[2];
-    read_tap(xfa, 0);
-    if constexpr (PAL) decode_tap(wfa, 0);
-#pragma unroll
-    for (int tap = 0; tap < TAPS; ++tap) {
-      half8(&cur)[8] = (tap & 1) ? xfb : xfa;
-      half8(&nxt)[8] = (tap & 1) ? xfa : xfb;
-      half8(&wcur)[2] = (tap & 1) ? wfb : wfa;
-      half8(&wnxt)[2] = (tap & 1) ? wfa : wfb;
-      if (tap + 1 < TAPS) {
-        read_tap(nxt, tap + 1);
-        if constexpr (PAL) decode_tap(wnxt, tap + 1);
+      for (int i = 0; i < 4; ++i) {
+        const int ml = i * 32 + (lane & 31);
+        if constexpr (TAPS == 9) {
+          const int sub = ml / (8 * WW), rem = ml - sub * (8 * WW);
+          hb[i] = Img::at(sub, rem / WW, rem % WW, lane >> 5);
+        } else {
+          hb[i] = Img::at1(ml, lane >> 5);
+        }
       }
+      auto read_tap = [&](intx4 (&xf)[4], int tap) {   // (a tap one halo row down flips the swap bit of every lane)
+        const int toff = TAPS == 9 ? ((tap / 3) * Img::PITCH + (tap % 3)) * 32 : 0, flip = TAPS == 9 ? ((tap / 3) & 1) * 16 : 0;
 #pragma unroll
-      for (int h = 0; h < 2; ++h)
+        for (int i = 0; i < 4; ++i) xf[i] = *reinterpret_cast<const intx4*>(region + ((hb[i] + toff) ^ flip));
+      };
+      intx4 xfa[4], xfb[4];
+      read_tap(xfa, 0);
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
-          acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(PAL ? wcur[h] : bf[PAL ? 0 : tap * 2 + h], cur[h * 4 + i], acc[i], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
+      for (int tap = 0; tap < TAPS; ++tap) {
+        intx4(&cur)[4] = (tap & 1) ? xfb : xfa;
+        intx4(&nxt)[4] = (tap & 1) ? xfa : xfb;
+        if (tap + 1 < TAPS) read_tap(nxt, tap + 1);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[i] = __builtin_amdgcn_mfma_i32_32x32x32_i8(bw[tap], cur[i], acc[i], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    } else {
+      // ---- halo slice (and LUT) -> this wave's LDS region (only this wave reads it: no barrier) ----
+#pragma unroll
+      for (int i = 0; i < NL; ++i) {
+        const int px = i * 16 + (lane >> 2);
+        if (px < HP) *reinterpret_cast<half8*>(region + px * WS_ROWB + piece * 16) = xa[i];
+      }
+      if constexpr (PAL) *reinterpret_cast<uintx2*>(region + WS_REGION + lane * 8) = lv;
+      const unsigned short* const lutp = reinterpret_cast<const unsigned short*>(region + WS_REGION);
+      // ---- fragments: lane (m = lane & 31, hi = lane >> 5) of pixel tile i reads 16 B of its pixel's row under the tap shift ----
+      int hb[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int ml = i * 32 + (lane & 31);
+        if constexpr (TAPS == 9) {
+          const int sub = ml / (8 * WW), rem = ml - sub * (8 * WW);
+          const int y = rem / WW, x = rem - y * WW;
+          hb[i] = (sub * HPS + y * HW_ + x) * WS_ROWB + (lane >> 5) * 16;
+        } else {
+          hb[i] = ml * WS_ROWB + (lane >> 5) * 16;
+        }
+      }
+      // fragments of tap t+1 are read while the MFMAs of tap t issue (register double buffer; the first version read two
+      // fragments, waited, issued two MFMAs: the LDS latency was exposed 36 times per wave)
+      auto read_tap = [&](half8 (&xf)[8], int tap) {
+        const int toff = TAPS == 9 ? ((tap / 3) * HW_ + (tap % 3)) * WS_ROWB : 0;
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) xf[h * 4 + i] = *reinterpret_cast<const half8*>(region + hb[i] + toff + h * 32);
+      };
+      // palettized: the two weight fragments of tap t + 1 are decoded beside them (fragments 2 tap, 2 tap + 1 of the lane's stream:
+      // compile-time field positions once the tap loop is unrolled)
+      auto decode_tap = [&](half8 (&wf)[2], int tap) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) wf[h] = pal_decode<NBITS>(wq, tap * 2 + h, lutp);
+      };
+      half8 xfa[8], xfb[8], wfa[2], wfb[2];
+      read_tap(xfa, 0);
+      if constexpr (PAL) decode_tap(wfa, 0);
+#pragma unroll
+      for (int tap = 0; tap < TAPS; ++tap) {
+        half8(&cur)[8] = (tap & 1) ? xfb : xfa;
+        half8(&nxt)[8] = (tap & 1) ? xfa : xfb;
+        half8(&wcur)[2] = (tap & 1) ? wfb : wfa;
+        half8(&wnxt)[2] = (tap & 1) ? wfa : wfb;
+        if (tap + 1 < TAPS) {
+          read_tap(nxt, tap + 1);
+          if constexpr (PAL) decode_tap(wnxt, tap + 1);
+        }
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(PAL ? wcur[h] : bf[PAL ? 0 : tap * 2 + h], cur[h * 4 + i], acc[i], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+      }
     }
   }
   // ---- sum the NW K-slices through LDS (each wave's own region, its fragment reads are behind it) ----
   {
-    floatx4* rg = reinterpret_cast<floatx4*>(region);
+    typedef typename std::conditional<I8, intx4, floatx4>::type V4;
+    V4* rg = reinterpret_cast<V4*>(region);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-      for (int q = 0; q < 4; ++q) rg[(i * 4 + q) * 64 + lane] = floatx4{acc[i][4 * q], acc[i][4 * q + 1], acc[i][4 * q + 2], acc[i][4 * q + 3]};
+      for (int q = 0; q < 4; ++q) rg[(i * 4 + q) * 64 + lane] = V4{acc[i][4 * q], acc[i][4 * q + 1], acc[i][4 * q + 2], acc[i][4 * q + 3]};
   }
   __syncthreads();
   // The tile is 128 rows x 128 B of fp32: thread -> (row, 16-B piece) so that eight lanes write one whole 128-B line (the
@@ -362,10 +469,19 @@ __global__ __launch_bounds__(NW * 64) void wstream_kernel(WsArgs a) {
     const int e = it * (NW * 64) + tid;               // row-major: e = ml * 8 + piece
     const int ml = e >> 3, pc = e & 7;
     const int id = (((ml >> 5) * 4 + (pc >> 1)) * 64) + (pc & 1) * 32 + (ml & 31);
-    floatx4 s = reinterpret_cast<const floatx4*>(smem)[id];
-#pragma unroll
-    for (int w = 1; w < NW; ++w) s += reinterpret_cast<const floatx4*>(smem + w * REGION)[id];
     const int m = zb * 128 + ml, n = strip * 32 + 4 * pc;
+    floatx4 s;
+    if constexpr (I8) {   // the int32 sum of the slices, one conversion, one multiply by the column's scale
+      intx4 si = reinterpret_cast<const intx4*>(smem)[id];
+#pragma unroll
+      for (int w = 1; w < NW; ++w) si += reinterpret_cast<const intx4*>(smem + w * REGION)[id];
+      const floatx4 cs = *reinterpret_cast<const floatx4*>(a.cs + n);
+      s = floatx4{(float)si[0] * cs[0], (float)si[1] * cs[1], (float)si[2] * cs[2], (float)si[3] * cs[3]};
+    } else {
+      s = reinterpret_cast<const floatx4*>(smem)[id];
+#pragma unroll
+      for (int w = 1; w < NW; ++w) s += reinterpret_cast<const floatx4*>(smem + w * REGION)[id];
+    }
     if (m < a.M) out_store(reinterpret_cast<floatx4*>(a.partial + ((size_t)split * a.M + m) * a.N + n), s);
   }
 }
@@ -400,6 +516,7 @@ void launch_ws(const WsArgs& a, int splits, hipStream_t s) {
 template <int NW, int TAPS, int WW>
 void launch_ws_source(const WsArgs& a, int nbits, int splits, hipStream_t s) {   // nbits 0: the fp16 stream
   if (nbits == 0) launch_ws<NW, TAPS, WW, 0>(a, splits, s);
+  else if (nbits == kWsI8) launch_ws<NW, TAPS, WW, kWsI8>(a, splits, s);
   else pal_dispatch_bits(nbits, "palettized wstream", [&](auto nb) { launch_ws<NW, TAPS, WW, decltype(nb)::value>(a, splits, s); });
 }
 
@@ -411,6 +528,9 @@ WsArgs ws_args(const ConvDesc& d, float* partial) {
   a.wt = d.w_tiled;
   a.pal = d.w_pal;
   a.lut = d.pal_lut;
+  a.w8 = d.w_i8;
+  a.cs = d.i8_scale;
+  a.inv_s = d.i8_inv_s;
   a.partial = partial;
   a.C0 = d.C0;
   a.C1 = d.x1 ? d.C1 : 0;
@@ -483,6 +603,12 @@ int launch_wstream_pal(const ConvDesc& d, float* partial, int nw, hipStream_t s)
              kInvalidArgument, "palettized wstream: shape not eligible or no palette (k=%d C0=%d C1=%d N=%d %dx%d bits=%d)", d.ksize, d.C0, d.C1,
              d.N, d.Ho, d.Wo, d.pal_bits);
   return launch_ws_conv(d, partial, d.pal_bits, nw, s);
+}
+
+int launch_wstream_i8(const ConvDesc& d, float* partial, int nw, hipStream_t s) {
+  SD_REQUIRE(wstream_shape_ok(d) && d.w_i8 && d.i8_scale && d.i8_inv_s > 0.f && std::isfinite(d.i8_inv_s), kInvalidArgument,
+             "int8 wstream: shape not eligible or no int8 weights (k=%d C0=%d C1=%d N=%d %dx%d)", d.ksize, d.C0, d.C1, d.N, d.Ho, d.Wo);
+  return launch_ws_conv(d, partial, kWsI8, nw, s);
 }
 
 bool reduce_twin_ok(int HW, int N, int n_twins, const GnTwin* tw) {

@@ -97,6 +97,16 @@ SYMBOLS = [
     ("sd_weights_add_palettized", _I, [_P, C.c_char_p, _P, _I, _P, C.POINTER(C.c_int64), _I]),
     ("sd_weights_palette_bits", _I, [_P, C.c_char_p]),
     ("sd_weights_read_palette", _I, [_P, C.c_char_p, _P, _P, _FP]),
+    ("sd_weights_quantize_w8a8", _I, [_P, C.c_char_p, _F, C.POINTER(C.c_double)]),
+    ("sd_weights_w8a8_info", _I, [_P, C.c_char_p, _FP]),
+    ("sd_weights_observe_activations", _I, [_P, _I]),
+    ("sd_unet_w8a8_info", _I, [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(C.c_size_t)]),
+    ("sd_unet_w8a8_layer", _I, [_P, _I, C.c_char_p, _I]),
+    ("sd_unet_activation_ranges", _I, [_P, _I, C.c_char_p, _I, _FP]),
+    ("sd_op_conv2d_w8a8", _I, [_P, _P, _P, _FP, _F, _FP, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_I), _I, _FP]),
+    ("sd_op_w8a8_pack", _I, [_P, _I, _I, _I, _P, C.POINTER(C.c_size_t)]),
+    ("sd_op_quantize_weight", _I, [_FP, _I, C.c_size_t, _P, _FP, C.POINTER(C.c_double)]),
+    ("sd_op_absmax", _I, [_P, C.c_size_t, _FP]),
     ("sd_unet_create", _I, [C.POINTER(UNetConfig), _P, _I, C.POINTER(_P)]),
     ("sd_unet_destroy", None, [_P]),
     ("sd_unet_set_attention", _I, [_P, _I]),
@@ -493,6 +503,69 @@ def conv2d_palettized(x, lut, indices, nbits, bias=None, res=None, x1=None, upsa
     check(lib().sd_op_conv2d_palettized(ptr(x), ptr(x1), ptr(lut), nbits, ptr(indices), fptr(bias), ptr(res), ptr(out), B, Cin, C1, H, W,
                                         Cout, k, int(upsample), nw, plan, iters, C.byref(ms)))
     return out.reshape(-1)[:n].reshape(B, Cout, Ho, Wo), list(plan), ms.value
+
+
+def conv2d_w8a8(x, wq, w_scale, act_absmax, bias=None, res=None, x1=None, upsample=False, nw=0, out=None, iters=1):
+    """The weight-stream conv in W8A8 (sd_op_conv2d_w8a8, plan tile 17): wq (Cout, Cin + C1, k, k) int8, w_scale (Cout,) f32,
+    act_absmax the range of x (and x1); the rest as conv2d_palettized.  Returns (out (B, Cout, Ho, Wo), plan, ms)."""
+    x = f16(x)
+    wq = np.ascontiguousarray(wq, dtype=np.int8)
+    w_scale = f32(w_scale)
+    x1 = None if x1 is None else f16(x1)
+    B, Cin, H, W = x.shape
+    C1 = 0 if x1 is None else x1.shape[1]
+    if wq.ndim != 4:
+        raise ValueError("conv2d_w8a8: wq must be (Cout, Cin + C1, k, k)")
+    Cout, Ctot, k, k2 = wq.shape
+    if Ctot != Cin + C1 or k != k2 or (x1 is not None and x1.shape != (B, C1, H, W)) or w_scale.shape != (Cout,):
+        raise ValueError("conv2d_w8a8: wq / w_scale / second source shape does not match input")
+    up = 2 if upsample else 1
+    Ho, Wo = H * up, W * up
+    bias = None if bias is None else f32(bias)
+    res = None if res is None else f16(res)
+    if res is not None and res.shape != (B, Cout, Ho, Wo):
+        raise ValueError("conv2d_w8a8: res must be (B, Cout, Ho, Wo)")
+    n = B * Cout * Ho * Wo
+    if out is None:
+        out = np.empty(n, np.float16)
+    if out.dtype != np.float16 or not out.flags.c_contiguous or out.size < n:
+        raise ValueError("conv2d_w8a8: out must be a C-contiguous float16 buffer of at least B * Cout * Ho * Wo elements")
+    plan = (C.c_int * 4)()
+    ms = C.c_float(0)
+    check(lib().sd_op_conv2d_w8a8(ptr(x), ptr(x1), ptr(wq), fptr(w_scale), float(act_absmax), fptr(bias), ptr(res), ptr(out), B, Cin, C1,
+                                  H, W, Cout, k, int(upsample), nw, plan, iters, C.byref(ms)))
+    return out.reshape(-1)[:n].reshape(B, Cout, Ho, Wo), list(plan), ms.value
+
+
+def w8a8_pack(wq):
+    """The int8 stream of the W8A8 weight-stream conv (sd_op_w8a8_pack; host only): wq (Cout, Ctot, k, k) int8 -> int8 array
+    [Cout / 32][Ctot / 32][k * k][64 lanes][16 bytes]."""
+    wq = np.ascontiguousarray(wq, dtype=np.int8)
+    Cout, Ctot, k, k2 = wq.shape
+    if k != k2:
+        raise ValueError("w8a8_pack: wq must be (Cout, Ctot, k, k)")
+    return _packed(lib().sd_op_w8a8_pack, ptr(wq), Cout, Ctot, k).view(np.int8).reshape(Cout // 32, Ctot // 32, k * k, 64, 16)
+
+
+def quantize_weight(w):
+    """The host weight quantizer of W8A8 (sd_op_quantize_weight): w (Cout, ...) f32 -> (q int8 of w's shape, w_scale (Cout,) f32,
+    squared error)."""
+    w = f32(w)
+    if w.ndim < 2 or w.size == 0:
+        raise ValueError("quantize_weight: w must be (Cout, ...)")
+    q = np.empty(w.shape, np.int8)
+    scale = np.empty(w.shape[0], np.float32)
+    err = C.c_double(0)
+    check(lib().sd_op_quantize_weight(fptr(w), w.shape[0], w.size // w.shape[0], ptr(q), fptr(scale), C.byref(err)))
+    return q, scale, err.value
+
+
+def absmax(x):
+    """max |x| of an f16 array on the device (sd_op_absmax: the activation observers' kernel), as an fp32 number."""
+    x = f16(x)
+    r = C.c_float(0)
+    check(lib().sd_op_absmax(ptr(x), x.size, C.byref(r)))
+    return np.float32(r.value)
 
 
 def _packed(pack, *args):

@@ -1,0 +1,82 @@
+"""W8A8 post-training quantization of the UNet at load time.
+
+The reference (``python_coreml_stable_diffusion/activation_quantization.py``) records calibration inputs
+(``--generate-calibration-data``), then quantizes the torch UNet with coremltools' ``LinearQuantizer`` under
+``quantize_cumulative_config`` (:141-203): symmetric int8, per-output-channel weights, per-tensor activations
+(``--quantize-pytorch``).  Here the same scheme runs inside the library: the weight store MARKS a conv weight with its int8
+values, its per-channel scales and the range of the activations the conv reads (``sd_weights_quantize_w8a8``), and a handle runs
+a marked conv from int8 on ``v_mfma_i32_32x32x32_i8`` wherever its plan is the weight stream (``wstream.hip``, plan tile 17);
+every other marked conv stays fp16 - the reference's skipped layers.  Parity with coremltools' quantizer is NOT pinned
+(coremltools is not a dependency of this project): the scales are plain absmax / 127, not the result of its calibration.
+
+Calibration happens on the device: ``HipModel(..., observe_activations=True)`` puts an absmax observer in front of every conv
+that could run from int8; after any number of forwards ``.activation_ranges()`` is the recipe's raw material.
+
+A recipe is JSON ``{layer: act_absmax}``, ``layer`` the conv's module name (its weight tensor without ``.weight``).
+
+Scope: the UNet.  The refiner, the ControlNets and the layer-wise PSNR sensitivity search (:384-413) are out of scope: recipes
+come from ranges, every observed layer unless ``skip`` names it.
+"""
+import json
+import logging
+import math
+
+logger = logging.getLogger(__name__)
+
+_SUFFIX = ".weight"
+
+
+def layer_of(tensor_name):
+    """``down_blocks.1.resnets.0.conv1.weight`` -> ``down_blocks.1.resnets.0.conv1``"""
+    return tensor_name[:-len(_SUFFIX)] if tensor_name.endswith(_SUFFIX) else tensor_name
+
+
+def recipe_from_ranges(ranges, skip=()):
+    """{layer: act_absmax} from ``HipModel.activation_ranges()``.  ``skip``: layers to leave fp16 (what the reference's sensitivity
+    search would drop).  A layer whose observed range is 0 (never run, or all-zero input) has no scale and raises ``ValueError``."""
+    skip = {layer_of(s) for s in skip}
+    recipe = {}
+    for layer, absmax in ranges.items():
+        layer = layer_of(layer)
+        if layer in skip:
+            continue
+        recipe[layer] = _checked(layer, absmax)
+    return recipe
+
+
+def _checked(layer, absmax):
+    absmax = float(absmax)
+    if not (math.isfinite(absmax) and absmax > 0.0):
+        raise ValueError(f"activation range of {layer!r} is {absmax!r}: a W8A8 layer needs a positive finite act_absmax")
+    return absmax
+
+
+def save_recipe(recipe, path):
+    with open(path, "w") as f:
+        json.dump({layer_of(k): _checked(k, v) for k, v in recipe.items()}, f, indent=1, sort_keys=True)
+
+
+def load_recipe(path_or_dict):
+    """A recipe file (or an already parsed dict) -> {layer: act_absmax}, values checked."""
+    if isinstance(path_or_dict, dict):
+        raw = path_or_dict
+    else:
+        with open(path_or_dict) as f:
+            raw = json.load(f)
+    if not isinstance(raw, dict):
+        raise ValueError("an activation-quantization recipe is a JSON object {layer: act_absmax}")
+    return {layer_of(str(k)): _checked(k, v) for k, v in raw.items()}
+
+
+def apply(weights, recipe):
+    """Mark the layers of ``recipe`` in a ``Weights`` store; returns {layer: squared weight error}.  ``KeyError``: a layer the
+    checkpoint does not have (nothing is marked then); ``ValueError``: a layer whose tensor carries a palette, or is no conv weight."""
+    recipe = load_recipe(recipe)
+    names = weights.shapes()
+    for layer in recipe:
+        if layer + _SUFFIX not in names:
+            raise KeyError(f"activation-quantization recipe: layer {layer!r} is not in the checkpoint (no tensor {layer + _SUFFIX!r})")
+        if weights.palette_bits(layer + _SUFFIX):
+            raise ValueError(f"{layer!r} is palettized (quantize_nbits / palettization recipe) AND named by the activation-quantization "
+                             "recipe: a tensor is one or the other")
+    return {layer: weights.quantize_w8a8(layer + _SUFFIX, absmax) for layer, absmax in recipe.items()}

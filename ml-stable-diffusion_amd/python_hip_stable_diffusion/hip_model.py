@@ -180,6 +180,26 @@ class Weights(_lib.Handle):
         _lib.check(_lib.lib().sd_weights_read_palette(self._h, name.encode(), _lib.ptr(lut), _lib.ptr(indices), None))
         return lut, indices
 
+    # ---- W8A8 marks (sd_mi355x.h "W8A8 post-training quantization") ----
+    def quantize_w8a8(self, name, act_absmax):
+        """Mark conv weight ``name`` for W8A8 with the range of the activations its conv reads; returns the squared weight error.
+        KeyError: unknown name; ValueError: not a conv weight, a palettized tensor, act_absmax not positive and finite."""
+        err = C.c_double(0)
+        status = _lib.lib().sd_weights_quantize_w8a8(self._h, name.encode(), float(act_absmax), C.byref(err))
+        if status == -2:
+            raise KeyError(name)
+        _lib.check(status)
+        return err.value
+
+    def w8a8_info(self, name):
+        """The activation scale s_a = act_absmax / 127 of a marked tensor, None when it has no mark."""
+        s = C.c_float(0)
+        return float(s.value) if _lib.lib().sd_weights_w8a8_info(self._h, name.encode(), C.byref(s)) else None
+
+    def observe_activations(self, on=True):
+        """Handles created from the store while this is on carry the activation observers (calibration)."""
+        _lib.check(_lib.lib().sd_weights_observe_activations(self._h, int(bool(on))))
+
     @classmethod
     @contextlib.contextmanager
     def lend(cls, weights):
@@ -201,9 +221,13 @@ class HipModel(_lib.Model):
 
     def __init__(self, config, weights, kind="unet", batch=2, latent_height=None, latent_width=None,
                  attention_implementation="SPLIT_EINSUM", device=0, use_graph=True, context_len=77, quantize_nbits=None,
-                 palettization_recipe=None, recipe_strict=True):
+                 palettization_recipe=None, recipe_strict=True, activation_quantization=None, observe_activations=False):
         if kind not in ("unet", "controlnet"):
             raise ValueError(f"kind must be 'unet' or 'controlnet', got {kind!r}")
+        if (activation_quantization is not None or observe_activations) and kind != "unet":
+            raise ValueError("activation quantization (W8A8) covers the UNet only: ControlNets are out of scope")
+        if activation_quantization is not None and observe_activations:
+            raise ValueError("observe_activations calibrates the fp16 model: give it or an activation_quantization recipe, not both")
         if attention_implementation not in _lib.ATTENTION_IMPLEMENTATIONS:
             raise ValueError(f"--attention-implementation must be one of {list(_lib.ATTENTION_IMPLEMENTATIONS)}")
         start = time.time()
@@ -253,7 +277,26 @@ class HipModel(_lib.Model):
                 # a store the caller lent stays palettized, as a converted model does)
                 from . import palettize
                 palettize.apply(store, nbits=quantize_nbits, recipe=palettization_recipe, strict=recipe_strict)
-            _lib.check(_lib.lib().sd_unet_create(C.byref(c), store._h, device, C.byref(self._h)))
+            self.activation_quantization = None
+            if activation_quantization is not None:
+                # (activation_quantization.py:141-203 --quantize-pytorch: at load time here; raises on an unknown layer and on a
+                # tensor the palettization above covers, before any device work)
+                from . import activation_quantization as aq
+                self.activation_quantization = aq.load_recipe(activation_quantization)
+                aq.apply(store, self.activation_quantization)
+            if observe_activations:
+                store.observe_activations(True)
+            try:
+                _lib.check(_lib.lib().sd_unet_create(C.byref(c), store._h, device, C.byref(self._h)))
+            finally:
+                if observe_activations:
+                    store.observe_activations(False)   # a lent store goes back as it came
+        if self.activation_quantization is not None:
+            applied = set(self.w8a8_layers())
+            stayed = sorted(set(self.activation_quantization) - applied)
+            logger.info("W8A8: %d of %d recipe layers run from int8 (plan tile 17)", len(applied), len(self.activation_quantization))
+            if stayed:
+                logger.info("W8A8: these layers stay fp16 (their plan is not the weight stream): %s", ", ".join(stayed))
         self.batch, self.latent_height, self.latent_width = batch, h, w
         self.attention_implementation = attention_implementation
         self.num_residuals = _lib.lib().sd_unet_num_residuals(self._h)
@@ -474,6 +517,42 @@ class HipModel(_lib.Model):
         n_pal, n_str, nbytes = C.c_int(0), C.c_int(0), C.c_size_t(0)
         _lib.check(_lib.lib().sd_unet_palette_info(self._h, C.byref(n_pal), C.byref(n_str), C.byref(nbytes)))
         return n_pal.value, n_str.value, nbytes.value
+
+    def w8a8_info(self):
+        """(tensors that arrived with a W8A8 mark, convs that run from int8 - plan tile 17 -, bytes of those convs' int8 streams and
+        scale vectors).  marked - applied convs stayed fp16."""
+        n_marked, n_applied, nbytes = C.c_int(0), C.c_int(0), C.c_size_t(0)
+        _lib.check(_lib.lib().sd_unet_w8a8_info(self._h, C.byref(n_marked), C.byref(n_applied), C.byref(nbytes)))
+        return n_marked.value, n_applied.value, nbytes.value
+
+    def w8a8_layers(self):
+        """Module names of the convs that run from int8, in build order."""
+        n = _lib.lib().sd_unet_w8a8_layer(self._h, -1, None, 0)
+        if n < 0:
+            _lib.check(n)
+        name = C.create_string_buffer(512)
+        out = []
+        for i in range(n):
+            if _lib.lib().sd_unet_w8a8_layer(self._h, i, name, len(name)) < 0:
+                _lib.check(-1)
+            out.append(name.value.decode()[:-len(".weight")])
+        return out
+
+    def activation_ranges(self):
+        """{layer: max |x| over the conv's input(s) of every forward so far} of a handle built with ``observe_activations=True``
+        (empty otherwise): the calibration of ``activation_quantization.recipe_from_ranges``."""
+        n = _lib.lib().sd_unet_activation_ranges(self._h, -1, None, 0, None)
+        if n < 0:
+            _lib.check(n)
+        name = C.create_string_buffer(512)
+        v = C.c_float(0)
+        out = {}
+        for i in range(n):
+            st = _lib.lib().sd_unet_activation_ranges(self._h, i, name, len(name), C.byref(v))
+            if st < 0:
+                _lib.check(st)
+            out[name.value.decode()[:-len(".weight")]] = float(v.value)
+        return out
 
     def close(self):
         if getattr(self, "_h", None) and getattr(self, "_attached", None):

@@ -623,7 +623,8 @@ def get_hip_pipe(model_dir, model_version, compute_unit="ALL", scheduler_overrid
                  force_zeros_for_empty_prompt=True, sources=None, attention_implementation="SPLIT_EINSUM",
                  num_images=1, guidance_scale=7.5, unet_batch_one=False, latent_size=None, device=0,
                  refiner_dir=None, tokenizer_factory=None, text_encoder_factory=None, vae_dtype=None, disable_safety=False,
-                 vae_encoder=False, quantize_nbits=None, palettization_recipe=None, device_postprocess=False):
+                 vae_encoder=False, quantize_nbits=None, palettization_recipe=None, device_postprocess=False,
+                 activation_quantization=None, observe_activations=False):
     """``get_coreml_pipe`` (pipeline.py:607-697) without the conversion step: ``model_dir`` is a diffusers
     checkpoint directory (``unet/``, ``vae/``, ``text_encoder/``, ``tokenizer/``, ``scheduler/`` [,
     ``text_encoder_2/``, ``tokenizer_2/``]) instead of a folder of ``.mlpackage`` files; ControlNets are
@@ -641,7 +642,11 @@ def get_hip_pipe(model_dir, model_version, compute_unit="ALL", scheduler_overrid
     mixed_bit_compression_apply.py); the text encoder, the VAE and the safety checker stay as they are.  A recipe is the UNet's: a
     module of it that the UNet lacks raises ``KeyError``; the ControlNets and the refiner take the modules they share with it (a
     ControlNet has the UNet's down and mid blocks) and leave the rest of their weights fp16.
-    ``device_postprocess``: the 8-bit image and the safety checker's input are made on the device (``HipStableDiffusionPipeline``)."""
+    ``device_postprocess``: the 8-bit image and the safety checker's input are made on the device (``HipStableDiffusionPipeline``).
+    ``activation_quantization``: a W8A8 recipe, a path or a dict {layer: act_absmax} (``activation_quantization.load_recipe``), applied
+    to the UNet alone (activation_quantization.py:141-203 ``--quantize-pytorch``; the refiner and the ControlNets stay as they are;
+    parity with coremltools' quantizer unpinned).  ``observe_activations``: the UNet carries the calibration observers
+    (``pipe.unet.activation_ranges()`` after a generation; ``--calibrate-activations``)."""
     if not os.path.isdir(model_dir):
         raise FileNotFoundError(f"{model_dir} not found (coreml_model.py:176-178)")
     from . import text_encoder as te
@@ -664,17 +669,18 @@ def get_hip_pipe(model_dir, model_version, compute_unit="ALL", scheduler_overrid
             logger.warning("Overriding scheduler in pipeline: Override=%s", name)
         scheduler = SCHEDULER_MAP[name].from_config(sc_cfg)
 
-    def load_unet(folder, kind="unet", support_controlnet=False, recipe_strict=True):
+    def load_unet(folder, kind="unet", support_controlnet=False, recipe_strict=True, **w8a8):
         cfg = dict(_read_json(os.path.join(folder, "config.json")))
         cfg["support_controlnet"] = support_controlnet
         size = latent_size or cfg.get("sample_size", 64)
         return HipModel(cfg, _find_weights(folder), kind=kind, batch=batch, latent_height=size, latent_width=size,
                         attention_implementation=attention_implementation, device=device, quantize_nbits=quantize_nbits,
-                        palettization_recipe=palettization_recipe, recipe_strict=recipe_strict)
+                        palettization_recipe=palettization_recipe, recipe_strict=recipe_strict, **w8a8)
 
     kwargs = dict(xl=xl, force_zeros_for_empty_prompt=force_zeros_for_empty_prompt, safety_checker=None)
     logger.info("Loading models in HBM from %s", model_dir)
-    kwargs["unet"] = load_unet(os.path.join(model_dir, "unet"), support_controlnet=bool(controlnet_models))
+    kwargs["unet"] = load_unet(os.path.join(model_dir, "unet"), support_controlnet=bool(controlnet_models),
+                               activation_quantization=activation_quantization, observe_activations=observe_activations)
     kwargs["controlnet"] = ([load_unet(d, kind="controlnet", recipe_strict=False) for d in controlnet_models] if controlnet_models else None)
     vcfg = _read_json(os.path.join(model_dir, "vae", "config.json"))
     lat = kwargs["unet"].latent_height
@@ -799,6 +805,12 @@ def build_parser():
                         help="The JSON file generated by mixed_bit_compression_pre_analysis.py: per-layer palettization recipes")
     parser.add_argument("--selected-recipe", default=None,
                         help="The string key into --pre-analysis-json-path's dict that picks the recipe to apply")
+    parser.add_argument("--activation-quantization-recipe", default=None,                        # activation_quantization.py --quantize-pytorch
+                        help="A W8A8 recipe (JSON {layer: act_absmax}, written by --calibrate-activations): the UNet convs it names run "
+                             "from int8 weights and activations where their kernel is the weight stream")
+    parser.add_argument("--calibrate-activations", default=None,                                 # activation_quantization.py --generate-calibration-data
+                        help="Run the requested generation on a UNet that records the range of every quantizable conv's input and write "
+                             "the W8A8 recipe to this file")
     return parser
 
 
@@ -818,13 +830,17 @@ def main(args):
             raise ValueError("--pre-analysis-json-path and --selected-recipe go together, and not with --quantize-nbits")
         from .palettize import load_recipe
         recipe = load_recipe(args.pre_analysis_json_path, args.selected_recipe)
+    aq_recipe, calibrate = getattr(args, "activation_quantization_recipe", None), getattr(args, "calibrate_activations", None)
+    if aq_recipe and calibrate:
+        raise ValueError("--calibrate-activations writes a recipe from the fp16 model; it does not go with --activation-quantization-recipe")
     pipe = get_hip_pipe(args.i, args.model_version, args.compute_unit, scheduler_override=scheduler,
                         controlnet_models=args.controlnet, force_zeros_for_empty_prompt=force_zeros,
                         sources=args.model_sources, attention_implementation=args.attention_implementation,
                         guidance_scale=args.guidance_scale, unet_batch_one=args.unet_batch_one, refiner_dir=args.refiner,
                         disable_safety=getattr(args, "disable_safety", False), vae_encoder=bool(getattr(args, "image", None)),
                         quantize_nbits=getattr(args, "quantize_nbits", None), palettization_recipe=recipe,
-                        device_postprocess=getattr(args, "device_postprocess", False))
+                        device_postprocess=getattr(args, "device_postprocess", False), activation_quantization=aq_recipe,
+                        observe_activations=bool(calibrate))
     controlnet_cond = None
     if args.controlnet:
         controlnet_cond = [prepare_controlnet_cond(args.controlnet_inputs[i], pipe.height, pipe.width)
@@ -854,6 +870,10 @@ def main(args):
                  **progress)
     logger.info("Saving generated image to %s", out_path)
     image["images"][0].save(out_path)
+    if calibrate:
+        from . import activation_quantization as aq
+        aq.save_recipe(aq.recipe_from_ranges(pipe.unet.activation_ranges()), calibrate)
+        logger.info("Saved the activation-quantization recipe to %s", calibrate)
     return out_path
 
 
