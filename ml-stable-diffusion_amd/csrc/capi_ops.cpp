@@ -148,6 +148,17 @@ void tile_for_bvgemm(Scratch& sc, ConvDesc& d, const char* refusal) {
   d.w_bv = wtd;
 }
 
+// compressed weights as an entry point receives them on the host: a palette lut[indices] or W8A8 values q * w_scale[n]
+struct HostWeights {
+  WeightSource kind = WeightSource::Fp16;
+  const void* lut = nullptr;          // palettes: 2^bits f16
+  const uint8_t* indices = nullptr;   // (Cout, Cin + C1, k, k)
+  int bits = 0;
+  const int8_t* q = nullptr;          // W8A8: (Cout, Cin + C1, k, k)
+  const float* w_scale = nullptr;     // (Cout,)
+  float act_absmax = 0.f;             // the activations are quantized with act_absmax / 127
+};
+
 // What sd_op_conv2d_ex sets on top of sd_op_conv2d (header); default-constructed: sd_op_conv2d itself.
 struct ConvOpExtra {
   const void* x1 = nullptr;   // second source (B, C1, H, W) f16
@@ -160,25 +171,19 @@ struct ConvOpExtra {
   int twin_silu = 0;
   void* out_twin = nullptr;
   int* plan_out = nullptr;       // {tile, staging, splitk, slab} of the plan that ran; -1: the direct kernels
-  // sd_op_conv2d_palettized: the weights are pal_lut[pal_indices] (w is NULL) and stay palettized on the device (plan tile 14)
-  const void* pal_lut = nullptr;         // 2^pal_bits f16
-  const uint8_t* pal_indices = nullptr;  // (Cout, Cin + C1, k, k)
-  int pal_bits = 0, pal_waves = 0;       // waves per workgroup: 4, else 8
-  // sd_op_conv2d_w8a8: the weights are i8_q * i8_w_scale[n] (w is NULL), the activations are quantized with act_absmax / 127 (plan tile 17)
-  const int8_t* i8_q = nullptr;          // (Cout, Cin + C1, k, k)
-  const float* i8_w_scale = nullptr;     // (Cout,)
-  float i8_act_absmax = 0.f;
+  HostWeights cw;                // sd_op_conv2d_palettized / sd_op_conv2d_w8a8: the weights arrive compressed (w is NULL)
+  int nw = 0;                    // ... with this many waves per workgroup: 4, else 8
 };
 
-// the palettized weights of a descriptor as the UNet builder uploads them (Net::conv, Net::upload_pal_geglu): the packed index stream
-// of the layout and the padded LUT
-void upload_palette(Scratch& sc, ConvDesc& d, const char* what, const void* lut, int nbits, const uint8_t* indices, PalLayout layout) {
-  const PaletteHostCopy h = palette_host_copy(what, f16(lut), nbits, indices, d.N, concat_channels(d), d.ksize, layout);
-  d.w_pal = sc.dev<uint8_t>(h.stream.size(), h.stream.data());
-  d.pal_lut = sc.dev<half_t>(h.lut.size(), h.lut.data());
-  d.pal_bits = nbits;
-  d.pal_gemm = layout == PalLayout::Gemm;
-  d.pal_geglu = layout == PalLayout::Geglu;
+// The compressed weights of a descriptor as the UNet builder uploads them (Net::upload_compressed) - the packed stream of the kind
+// with its LUT / scales - and the kind's pin by the caller's n (conv_plan_pin: waves per workgroup or tile height)
+void upload_compressed(Scratch& sc, ConvDesc& d, const char* what, const HostWeights& h, int n) {
+  auto up = [&sc](const auto* host, size_t count) { return sc.dev(count, host); };
+  d.cw = h.kind == WeightSource::I8Wstream ? upload_w8a8(up, what, h.q, h.w_scale, h.act_absmax, d.N, concat_channels(d), d.ksize)
+                                           : upload_palettized(up, h.kind, what, f16(h.lut), h.bits, h.indices, d.N, concat_channels(d), d.ksize);
+  const WeightPin pin = conv_plan_pin(h.kind, n);
+  d.tile = pin.tile;
+  d.staging = pin.staging;
 }
 
 // (B, N) f32 rows on the device as the UNet keeps its time_emb_proj outputs: a column block of a wider row buffer, every other float
@@ -195,7 +200,7 @@ const float* upload_temb_rows(Scratch& sc, const float* temb, int B, int N, int*
 // the body of sd_op_conv2d / sd_op_conv2d_ex
 void conv2d_op(const void* x, const void* w, const float* bias, const void* res, void* out, int B, int Cin, int H, int W, int Cout,
                int ksize, int stride, int upsample, int tile, int splitk, int force_generic, int iters, float* ms, const ConvOpExtra& e) {
-  SD_REQUIRE(x && (w || e.pal_indices || e.i8_q) && out, kInvalidArgument, "NULL argument");
+  SD_REQUIRE(x && (w || e.cw.indices || e.cw.q) && out, kInvalidArgument, "NULL argument");
   SD_REQUIRE((ksize == 1 || ksize == 3) && (stride == 1 || stride == 2) && (upsample == 0 || upsample == 1),
              kInvalidArgument, "conv2d: ksize %d stride %d upsample %d not on the path", ksize, stride, upsample);
   SD_REQUIRE(e.C1 >= 0 && (e.C1 == 0 || e.x1), kInvalidArgument, "conv2d: C1 = %d needs the second source x1", e.C1);
@@ -217,7 +222,7 @@ void conv2d_op(const void* x, const void* w, const float* bias, const void* res,
     d.x1 = upload_nhwc(sc, e.x1, B, e.C1, H, W);
     d.C1 = e.C1;
   }
-  if (!e.pal_indices && !e.i8_q) d.w = upload_conv_weight(sc, w, Cout, Cin + e.C1, ksize);
+  if (e.cw.kind == WeightSource::Fp16) d.w = upload_conv_weight(sc, w, Cout, Cin + e.C1, ksize);
   d.bias = bias ? sc.dev<float>(Cout, bias) : nullptr;
   if (e.temb) d.temb = upload_temb_rows(sc, e.temb, B, Cout, &d.temb_stride);
   if (res) d.res = upload_nhwc(sc, res, B, Cout, Ho, Wo);
@@ -231,21 +236,11 @@ void conv2d_op(const void* x, const void* w, const float* bias, const void* res,
   d.debug = force_generic >= 2 ? force_generic - 1 : 0;   // 2: loads only, 3: compute only (ablation)
   if (d.debug & 4) d.prof = sc.dev<long long>(8);
   const bool fast = force_generic != 1 && conv_fast_path_ok(d);
-  if (e.pal_indices) {
+  if (e.cw.kind == WeightSource::PalWstream)
     SD_REQUIRE(fast && wstream_shape_ok(d), kInvalidArgument, "conv2d_palettized: shape not eligible for plan tile 14 (wstream.hip: k=%d C0=%d C1=%d N=%d %dx%d)",
                ksize, Cin, e.C1, Cout, Ho, Wo);
-    upload_palette(sc, d, "palettized conv", e.pal_lut, e.pal_bits, e.pal_indices, PalLayout::Wstream);
-    d.tile = 14;
-    d.staging = conv_plan_waves_code(e.pal_waves);
-  }
-  if (e.i8_q) {   // (shape and values were checked on the host by the entry point)
-    const W8A8HostCopy h = w8a8_host_copy("conv2d_w8a8", e.i8_q, e.i8_w_scale, e.i8_act_absmax, Cout, Cin + e.C1, ksize);
-    d.w_i8 = sc.dev<int8_t>(h.stream.size(), h.stream.data());
-    d.i8_scale = sc.dev<float>(h.cs.size(), h.cs.data());
-    d.i8_inv_s = h.inv_s;
-    d.tile = 17;
-    d.staging = conv_plan_waves_code(e.pal_waves);
-  }
+  // (W8A8: shape and values were checked on the host by the entry point)
+  if (e.cw.kind != WeightSource::Fp16) upload_compressed(sc, d, e.cw.kind == WeightSource::PalWstream ? "palettized conv" : "conv2d_w8a8", e.cw, e.nw);
   half_t* dtwin = nullptr;
   if (e.twin_groups) {   // the GroupNorm as a twin of the conv's slab combine (sd_op_conv2d_groupnorm's producer_stats = 2)
     SD_REQUIRE(fast, kInvalidArgument, "conv2d: GroupNorm twins need the MFMA path");
@@ -264,7 +259,7 @@ void conv2d_op(const void* x, const void* w, const float* bias, const void* res,
   }
   ConvWorkspace ws;
   // the pre-tiled weight copies: what a forced plan reads, else exactly what the planner names for the library's own plan
-  const ConvWeightCopies copies = (fast && tile == 0 && splitk == 0 && !d.debug && !d.w_pal && !d.w_i8) ? conv_plan_copies(d) : ConvWeightCopies{false, false, false};
+  const ConvWeightCopies copies = (fast && tile == 0 && splitk == 0 && !d.debug && d.cw.kind == WeightSource::Fp16) ? conv_plan_copies(d) : ConvWeightCopies{false, false, false};
   if (fast && (d.tile == 9 || copies.wstream)) tile_for_wstream(sc, d, "conv2d: shape not eligible for plan tile 9 (wstream.hip)");
   if (fast && (d.tile == 11 || copies.bvgemm)) tile_for_bvgemm(sc, d, "conv2d: shape not eligible for plan tile 11 (bvgemm.hip)");
   if (fast && d.tile != 11 && d.tile != 12) ws = workspace_for(sc, {d});
@@ -488,7 +483,8 @@ int sd_op_conv2d_palettized(const void* x, const void* x1, const void* lut, int 
     ConvOpExtra e;
     e.x1 = x1; e.C1 = C1;
     e.plan_out = plan_out;
-    e.pal_lut = lut; e.pal_indices = indices; e.pal_bits = nbits; e.pal_waves = nw;
+    e.cw.kind = WeightSource::PalWstream; e.cw.lut = lut; e.cw.indices = indices; e.cw.bits = nbits;
+    e.nw = nw;
     conv2d_op(x, nullptr, bias, res, out, B, Cin, H, W, Cout, ksize, 1, upsample, 0, 0, 0, iters, ms, e);
   });
 }
@@ -514,7 +510,8 @@ int sd_op_conv2d_w8a8(const void* x, const void* x1, const int8_t* wq, const flo
     ConvOpExtra e;
     e.x1 = x1; e.C1 = C1;
     e.plan_out = plan_out;
-    e.i8_q = wq; e.i8_w_scale = w_scale; e.i8_act_absmax = act_absmax; e.pal_waves = nw;
+    e.cw.kind = WeightSource::I8Wstream; e.cw.q = wq; e.cw.w_scale = w_scale; e.cw.act_absmax = act_absmax;
+    e.nw = nw;
     conv2d_op(x, nullptr, bias, res, out, B, Cin, H, W, Cout, ksize, 1, upsample, 0, 0, 0, iters, ms, e);
   });
 }
@@ -573,8 +570,7 @@ int sd_op_gemm_palettized(const void* x, const void* lut, int nbits, const uint8
     d.C0 = Cin;
     d.B = B; d.Hi = H; d.Wi = W; d.Ho = H; d.Wo = W;
     d.N = Cout;
-    const int variant = bm == 32 ? 1 : (bm == 64 ? 2 : 0);
-    SD_REQUIRE(conv_fast_path_ok(d) && smgemm_shape_ok(d, variant), kInvalidArgument,
+    SD_REQUIRE(conv_fast_path_ok(d) && smgemm_shape_ok(d, conv_plan_pin(WeightSource::PalGemm, bm).staging), kInvalidArgument,
                "gemm_palettized: shape not eligible for plan tile 15 (smgemm.hip: Cin=%d Cout=%d M=%d bm=%d - Cin a multiple of 64, Cout of 80, M of the "
                "tile height, at least 2 x 2 tiles and a multiple of 8 of them)", Cin, Cout, B * H * W, bm);
     Scratch sc;
@@ -583,9 +579,9 @@ int sd_op_gemm_palettized(const void* x, const void* lut, int nbits, const uint8
     if (res) d.res = upload_nhwc(sc, res, B, Cout, H, W);
     half_t* dout = sc.dev<half_t>((size_t)B * H * W * Cout);
     d.out = dout;
-    upload_palette(sc, d, "gemm_palettized", lut, nbits, indices, PalLayout::Gemm);
-    d.tile = 15;
-    d.staging = variant;
+    HostWeights h;
+    h.kind = WeightSource::PalGemm; h.lut = lut; h.indices = indices; h.bits = nbits;
+    upload_compressed(sc, d, "gemm_palettized", h, bm);
     const ConvPlan p = conv_plan(d);
     plan_out[0] = p.tile; plan_out[1] = p.staging; plan_out[2] = p.splitk; plan_out[3] = p.slab ? 1 : 0;
     ConvWorkspace ws;
@@ -1046,8 +1042,7 @@ int sd_op_geglu_palettized(const void* x, const float* ln_weight, const float* l
     if (ln_weight) d.ln_colsum = &present;
     d.ln_eps = eps;
     d.out_mode = kOutGeglu;
-    const int variant = bm == 128 ? 1 : (bm == 256 ? 2 : 0);
-    SD_REQUIRE(conv_fast_path_ok(d) && smgeglu_pal_shape_ok(d, variant), kInvalidArgument,
+    SD_REQUIRE(conv_fast_path_ok(d) && smgeglu_pal_shape_ok(d, conv_plan_pin(WeightSource::PalGeglu, bm).staging), kInvalidArgument,
                "geglu_palettized: shape not eligible for plan tile 16 (smgeglu.hip: M=%d C=%d N2=%d bm=%d - 128-row tiles only (256 is not "
                "built), C a multiple of 64 up to 2560, N2 of 160, M of 128, at least 2 x 2 tiles and a multiple of 8 of them)", M, C, N2, bm);
     std::vector<half_t> w((size_t)N2 * C), wf(w.size());
@@ -1059,13 +1054,13 @@ int sd_op_geglu_palettized(const void* x, const float* ln_weight, const float* l
     d.x0 = sc.dev<half_t>((size_t)M * C, f16(x));
     d.out = dout;
     d.bias = sc.dev<float>(N2, bf.data());
+    HostWeights h;
+    h.kind = WeightSource::PalGeglu; h.lut = lut; h.indices = indices; h.bits = nbits;
+    upload_compressed(sc, d, "geglu_palettized", h, bm);
     if (ln_weight) {
       d.ln_colsum = sc.dev<float>(N2, cs.data());
-      d.ln_gamma = sc.dev<float>(C, ln_weight);
+      d.cw.ln_gamma = sc.dev<float>(C, ln_weight);
     }
-    upload_palette(sc, d, "geglu_palettized", lut, nbits, indices, PalLayout::Geglu);
-    d.tile = 16;
-    d.staging = variant;
     const ConvPlan p = conv_plan(d);
     plan_out[0] = p.tile; plan_out[1] = p.staging; plan_out[2] = p.splitk; plan_out[3] = p.slab ? 1 : 0;
     ConvWorkspace ws;
@@ -1245,9 +1240,9 @@ static ConvPlan query_conv_plan(int ksize, int stride, int up, int C0, int C1, i
   d.tile = tile; d.staging = staging; d.splitk = splitk;
   if (tile == 17) {   // a W8A8 descriptor carries its int8 stream and scales (the planner only tests the pointers)
     d.w = nullptr;
-    d.w_i8 = reinterpret_cast<const int8_t*>(present);
-    d.i8_scale = present;
-    d.i8_inv_s = 1.f;
+    d.cw.kind = WeightSource::I8Wstream;
+    d.cw.stream = d.cw.scale = present;
+    d.cw.inv_s = 1.f;
   }
   c = conv_plan_copies(d);
   if (copies < 0) copies = (c.wstream ? 1 : 0) | (c.wsgemm ? 2 : 0) | (c.bvgemm ? 4 : 0);   // what a handle of the library holds

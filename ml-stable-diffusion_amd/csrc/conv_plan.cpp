@@ -51,14 +51,13 @@ struct Plan {
 bool can_split(const ConvDesc& d) { return d.out_mode == kOutHalf && !d.ln_colsum && !d.out_t; }
 // the weight-streaming kernel can take this conv: its pre-tiled weights exist and the shape is its own (SD_WSTREAM: tile_ok)
 bool can_stream(const ConvDesc& d) { return d.w_tiled != nullptr && can_split(d) && wstream_shape_ok(d); }
-// a palettized descriptor (plan tile 14): pinned to the palettized weight stream, it holds no fp16 weights to run anything else on
-bool pal_stream(const ConvDesc& d) { return d.w_pal != nullptr && !d.pal_gemm && !d.pal_geglu; }
-// a W8A8 descriptor (plan tile 17): pinned to the int8 weight stream likewise
-bool i8_stream(const ConvDesc& d) { return d.w_i8 != nullptr; }
-// the same for the small-M 1x1 GEMM (plan tile 15): the descriptor carries the stream of smgemm_pal_pack
-bool pal_gemm(const ConvDesc& d) { return d.w_pal != nullptr && d.pal_gemm; }
-// and for the GEGLU projection (plan tile 16): the stream of smgeglu_pal_pack
-bool pal_geglu(const ConvDesc& d) { return d.w_pal != nullptr && d.pal_geglu; }
+// a descriptor with a compressed weight source (ConvDesc::cw) is pinned to the source's kernel: it holds no fp16 weights to run anything
+// else on.  Plan tiles 14 / 17: the palettized / int8 weight stream
+bool pal_stream(const ConvDesc& d) { return d.cw.kind == WeightSource::PalWstream; }
+bool i8_stream(const ConvDesc& d) { return d.cw.kind == WeightSource::I8Wstream; }
+// plan tile 15: the small-M 1x1 GEMM;  plan tile 16: the GEGLU projection
+bool pal_gemm(const ConvDesc& d) { return d.cw.kind == WeightSource::PalGemm; }
+bool pal_geglu(const ConvDesc& d) { return d.cw.kind == WeightSource::PalGeglu; }
 // tiles 9 / 14 / 17: the code's wave count (decode_plan)
 int wstream_waves(int code) { return code == 4 ? 4 : 8; }
 // fp32 slabs of a launch: one per split, one when only `slab` (weight stream, GroupNorm twins) asks for the slab path
@@ -268,34 +267,31 @@ namespace {
 // the plan in the wire format: tile, code, resolved split-K, slab, workspace
 ConvPlan plan_codes(const ConvDesc& d) {
   if (!conv_fast_path_ok(d)) return ConvPlan{-1, 0, 1, false, 0};
-  if (pal_stream(d)) {   // in front of the tuner candidate, the tables and every rule: nothing moves it
-    SD_REQUIRE(d.pal_lut && can_split(d) && wstream_shape_ok(d), kInvalidArgument,
-               "plan tile 14 (wstream.hip, palettized) needs the index stream, the LUT and a shape of the weight stream");
-    ConvPlan r{14, d.staging, 1, true, 0};   // the code of tile 9
-    r.splitk = wstream_splits(d, wstream_waves(d.staging));
-    r.workspace_bytes = slab_bytes(dims_of(d), r.splitk, true);
-    return r;
-  }
-  if (i8_stream(d)) {   // pinned in the same place, for the same reason
-    SD_REQUIRE(d.i8_scale && !d.w_pal && can_split(d) && wstream_shape_ok(d), kInvalidArgument,
-               "plan tile 17 (wstream.hip, int8) needs the int8 stream, the scales and a shape of the weight stream");
-    ConvPlan r{17, d.staging, 1, true, 0};   // the code of tile 9
-    r.splitk = wstream_splits(d, wstream_waves(d.staging));
-    r.workspace_bytes = slab_bytes(dims_of(d), r.splitk, true);
-    return r;
-  }
-  if (pal_gemm(d)) {   // pinned like tile 14; the code of tile 12 in, the resolved tile height out; no workspace
-    SD_REQUIRE(d.pal_lut && palette_bits_ok(d.pal_bits) && !d.x1 && d.staging >= 0 && d.staging <= 2 && smgemm_shape_ok(d, d.staging), kInvalidArgument,
-               "plan tile 15 (smgemm.hip, palettized) needs the index stream, the LUT and a single-source shape of the small-M GEMM");
-    return ConvPlan{15, conv_plan_bm_code(smgemm_bm(d, d.staging)), 1, false, 0};
-  }
-  if (pal_geglu(d)) {   // pinned likewise; the code of tile 13 in, the resolved tile height out (128 rows: code 1; 256 is not built)
-    SD_REQUIRE(d.pal_lut && palette_bits_ok(d.pal_bits) && !d.pal_gemm && (d.ln_gamma != nullptr) == (d.ln_colsum != nullptr) &&
-                   smgeglu_pal_shape_ok(d, d.staging),
-               kInvalidArgument,
-               "plan tile 16 (smgeglu.hip, palettized) needs the index stream, the LUT, the norm weight with the LayerNorm fold and a shape of "
-               "the GEGLU kernel with 128-row tiles");
-    return ConvPlan{16, 1, 1, false, 0};
+  // a compressed weight source, in front of the tuner candidate, the tables and every rule: nothing moves it
+  const CompressedWeights& cw = d.cw;
+  switch (cw.kind) {
+    case WeightSource::Fp16: break;
+    case WeightSource::PalWstream:
+    case WeightSource::I8Wstream: {   // the code of tile 9
+      const bool i8 = i8_stream(d);
+      SD_REQUIRE(cw.stream && (i8 ? cw.scale != nullptr : cw.lut != nullptr) && can_split(d) && wstream_shape_ok(d), kInvalidArgument, "%s",
+                 i8 ? "plan tile 17 (wstream.hip, int8) needs the int8 stream, the scales and a shape of the weight stream"
+                    : "plan tile 14 (wstream.hip, palettized) needs the index stream, the LUT and a shape of the weight stream");
+      ConvPlan r{i8 ? 17 : 14, d.staging, 1, true, 0};
+      r.splitk = wstream_splits(d, wstream_waves(d.staging));
+      r.workspace_bytes = slab_bytes(dims_of(d), r.splitk, true);
+      return r;
+    }
+    case WeightSource::PalGemm:   // the code of tile 12 in, the resolved tile height out; no workspace
+      SD_REQUIRE(cw.stream && cw.lut && palette_bits_ok(cw.bits) && !d.x1 && d.staging >= 0 && d.staging <= 2 && smgemm_shape_ok(d, d.staging), kInvalidArgument,
+                 "plan tile 15 (smgemm.hip, palettized) needs the index stream, the LUT and a single-source shape of the small-M GEMM");
+      return ConvPlan{15, smgemm_bm(d, d.staging) == 32 ? 1 : 2, 1, false, 0};
+    case WeightSource::PalGeglu:   // the code of tile 13 in, the resolved tile height out (128 rows: code 1; 256 is not built)
+      SD_REQUIRE(cw.stream && cw.lut && palette_bits_ok(cw.bits) && (cw.ln_gamma != nullptr) == (d.ln_colsum != nullptr) && smgeglu_pal_shape_ok(d, d.staging),
+                 kInvalidArgument,
+                 "plan tile 16 (smgeglu.hip, palettized) needs the index stream, the LUT, the norm weight with the LayerNorm fold and a shape of "
+                 "the GEGLU kernel with 128-row tiles");
+      return ConvPlan{16, 1, 1, false, 0};
   }
   const Switches& sw = switches();
   // the library's own rules for tiles 10-13 apply where nothing else was asked for (a tuner candidate in force also keeps them off)
@@ -480,54 +476,49 @@ ConvWeightCopies conv_plan_copies(const ConvDesc& d0) {
   return c;
 }
 
-// Build-time question of a handle that holds a PALETTE for this conv's weights: would the conv run on the weight stream (plan tile
-// 9) if its fp16 copies were uploaded - the plan conv_plan gives it with the fragment-major copy present - and with how many waves
-// per workgroup?  0: no (the tensor is then uploaded de-palettized); 4 / 8: tile 14 with that wave count, i.e. tile 9's slab count.
-int conv_plan_pal_waves(const ConvDesc& d0) {
-  if (!conv_fast_path_ok(d0) || !switches().wstream || d0.ln_colsum || !plan_is_wstream(d0)) return 0;
-  ConvDesc d = d0;
+namespace {
+// the plan of this conv run from fp16 with the pre-tiled copies `c` present (conv_plan only tests the pointers)
+ConvPlan fp16_plan(const ConvDesc& d0, const ConvWeightCopies& c) {
   static const half_t present = 0;
-  d.w_tiled = &present;   // conv_plan only tests the pointer
-  d.w_ws = d.w_bv = nullptr;
-  d.w_pal = nullptr;
-  d.w_i8 = nullptr;
-  const ConvPlan p = conv_plan(d);
-  return p.kernel == ConvKernel::Wstream ? p.waves : 0;
+  ConvDesc d = d0;
+  d.cw = CompressedWeights{};
+  d.w_tiled = c.wstream ? &present : nullptr;
+  d.w_ws = c.wsgemm ? &present : nullptr;
+  d.w_bv = c.bvgemm ? &present : nullptr;
+  return conv_plan(d);
+}
+}  // namespace
+
+WeightPin conv_plan_pin(WeightSource kind, int n) {
+  switch (kind) {
+    case WeightSource::PalWstream: return {kind, 14, n == 4 ? 4 : 0};
+    case WeightSource::I8Wstream: return {kind, 17, n == 4 ? 4 : 0};
+    case WeightSource::PalGemm: return {kind, 15, n == 32 ? 1 : n == 64 ? 2 : 0};
+    case WeightSource::PalGeglu: return {kind, 16, n == 128 ? 1 : n == 256 ? 2 : 0};
+    default: return {};
+  }
 }
 
-// The same question for plan tile 15: would this conv, uploaded as fp16 with the copies a handle would hold, get plan tile 12 by the
-// library's own rule?  conv_plan itself answers (one predicate: SD_SMGEMM=0, a tuner candidate, a forced plan, GroupNorm statistics
-// asked of it or a shape smgemm_wanted refuses all give another tile there); 32 / 64 = the tile height tile 12 would run.
-int conv_plan_pal_gemm(const ConvDesc& d0) {
-  if (!conv_fast_path_ok(d0) || !switches().smgemm || d0.ln_colsum || d0.x1) return 0;
-  ConvDesc d = d0;
-  d.w_pal = nullptr;
-  d.pal_gemm = false;
-  d.w_tiled = d.w_ws = d.w_bv = nullptr;
-  static const half_t present = 0;   // conv_plan only tests the pointers
-  const ConvWeightCopies c = conv_plan_copies(d);
-  if (c.wstream) d.w_tiled = &present;
-  if (c.wsgemm) d.w_ws = &present;
-  if (c.bvgemm) d.w_bv = &present;
-  const ConvPlan p = conv_plan(d);
-  return p.kernel == ConvKernel::Smgemm ? p.bm : 0;
-}
-
-// And for plan tile 16: tile 13 by the library's own rule (SD_SMGEGLU=0, a tuner candidate or a forced plan give another tile), on the
-// 128-row tiles the palettized kernel has.
-int conv_plan_pal_geglu(const ConvDesc& d0) {
-  if (!conv_fast_path_ok(d0) || !switches().smgeglu || d0.x1 || d0.out_mode != kOutGeglu) return 0;
-  ConvDesc d = d0;
-  d.w_pal = nullptr;
-  d.pal_gemm = d.pal_geglu = false;
-  d.w_tiled = d.w_ws = d.w_bv = nullptr;
-  static const half_t present = 0;   // conv_plan only tests the pointers
-  const ConvWeightCopies c = conv_plan_copies(d);
-  if (c.wstream) d.w_tiled = &present;
-  if (c.wsgemm) d.w_ws = &present;
-  if (c.bvgemm) d.w_bv = &present;
-  const ConvPlan p = conv_plan(d);
-  return p.kernel == ConvKernel::Smgeglu && smgeglu_pal_shape_ok(d, 0) ? p.bm : 0;
+// conv_plan itself answers each question (one predicate: an A/B switch, a tuner candidate, a forced plan, GroupNorm statistics asked
+// of the conv or a shape the twin's own rule refuses all give another kernel there).
+WeightPin conv_plan_weights(const ConvDesc& d, StoredWeights held, bool opt_in) {
+  if (held == StoredWeights::Fp16 || !conv_fast_path_ok(d)) return {};
+  const Switches& sw = switches();
+  const bool palette = held == StoredWeights::Palette, one_by_one = opt_in && palette && d.ksize == 1 && !d.x1;
+  if (one_by_one && d.out_mode == kOutGeglu && sw.smgeglu) {   // tile 13, on the 128-row tiles the palettized kernel has
+    const ConvPlan p = fp16_plan(d, conv_plan_copies(d));
+    if (p.kernel == ConvKernel::Smgeglu && smgeglu_pal_shape_ok(d, 0)) return conv_plan_pin(WeightSource::PalGeglu, p.bm);
+  }
+  // tile 9 with the fragment-major copy present: its wave count, i.e. its slab count
+  if (sw.wstream && !d.ln_colsum && plan_is_wstream(d)) {
+    const ConvPlan p = fp16_plan(d, {true, false, false});
+    if (p.kernel == ConvKernel::Wstream) return conv_plan_pin(palette ? WeightSource::PalWstream : WeightSource::I8Wstream, p.waves);
+  }
+  if (one_by_one && d.out_mode == kOutHalf && sw.smgemm && !d.ln_colsum) {   // tile 12
+    const ConvPlan p = fp16_plan(d, conv_plan_copies(d));
+    if (p.kernel == ConvKernel::Smgemm) return conv_plan_pin(WeightSource::PalGemm, p.bm);
+  }
+  return {};
 }
 
 // Does the compiled-in plan table hold a row for this shape - a plan that was measured in a step?
@@ -570,13 +561,13 @@ void conv_plan_log(const ConvDesc& d, const ConvPlan& p, int n_fast) {
   const int c1 = d.x1 ? d.C1 : 0;
   if (p.tile == 9 || p.tile == 14 || p.tile == 17)
     fprintf(stderr, "[sd conv] k%d up%d C0=%d C1=%d M=%d N=%d K=%d tile=%d nw=%d slabs=%d twins=%d bits=%d\n", d.ksize, d.up, d.C0, c1, a.M, a.N,
-            a.K, p.tile, p.waves, p.splitk, d.n_twins, p.tile == 14 ? d.pal_bits : p.tile == 17 ? 8 : 16);
+            a.K, p.tile, p.waves, p.splitk, d.n_twins, p.tile == 14 ? d.cw.bits : p.tile == 17 ? 8 : 16);
   else if (p.tile == 12 || p.tile == 13)
     fprintf(stderr, "[sd conv] k1 s1 up1 C0=%d C1=%d M=%d N=%d K=%d mode=%d tile=%d bm=%d n_fast=%d\n", d.C0, c1, a.M, a.N, a.K, d.out_mode, p.tile, p.bm,
             n_fast);
   else if (p.tile == 15 || p.tile == 16)
     fprintf(stderr, "[sd conv] k1 s1 up1 C0=%d C1=%d M=%d N=%d K=%d mode=%d tile=%d bm=%d n_fast=%d bits=%d\n", d.C0, c1, a.M, a.N, a.K, d.out_mode,
-            p.tile, p.bm, n_fast, d.pal_bits);
+            p.tile, p.bm, n_fast, d.cw.bits);
   else
     fprintf(stderr, "[sd conv] k%d s%d up%d C0=%d C1=%d M=%d N=%d K=%d mode=%d tile=%d splitk=%d\n", d.ksize, d.stride, d.up, d.C0, c1, a.M, a.N,
             a.K, d.out_mode, p.tile, p.splitk);

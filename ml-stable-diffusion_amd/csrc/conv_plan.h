@@ -41,27 +41,27 @@ struct ConvWeightCopies {
 };
 ConvWeightCopies conv_plan_copies(const ConvDesc& d);
 
-// A handle that holds a palette for this conv's weights asks at build time: 4 / 8 = run it from the index stream (plan tile 14) with
-// that many waves per workgroup - the conv's plan with fp16 copies would be the weight stream with that wave count; 0 = upload the
-// de-palettized tensor and run as ever.  d.w / w_tiled / w_pal are not looked at.
-int conv_plan_pal_waves(const ConvDesc& d);
-// A handle that holds W8A8 marks for this conv's weights asks the same question for plan tile 17: the one predicate of tile 14.
-inline int conv_plan_i8_waves(const ConvDesc& d) { return conv_plan_pal_waves(d); }
-// The same question for the small-M 1x1 GEMM (plan tile 15): 32 / 64 = this conv, uploaded as fp16 with the copies a handle would hold,
-// would get plan tile 12 by the library's own rule with that tile height - run it from the index stream of smgemm_pal_pack instead;
-// 0 = no (SD_SMGEMM=0, two sources, a LayerNorm fold, any other plan): upload the de-palettized tensor.
-int conv_plan_pal_gemm(const ConvDesc& d);
-// The same question for the GEGLU projection (plan tile 16): the tile height when this conv, uploaded as fp16 with the copies a handle
-// would hold, gets plan tile 13 by the library's own rule AND the palettized kernel has that tile height (128); else 0.
-int conv_plan_pal_geglu(const ConvDesc& d);
+// The build-time question of whoever holds a compressed form of this conv's weights: does a kernel read that form on the device?
+// d is the conv as it would run from fp16 (d.w / the copies / d.cw are not looked at), `held` what the weight store holds for the
+// tensor, `opt_in` the call site's consent to a pinned 1x1 / GEGLU kernel (a pinned op cannot move to igemm_kernel when a later
+// GroupNorm asks for epilogue statistics).  The answer is the source kind with its pin in wire-format codes (ConvDesc::tile /
+// staging), or Fp16: upload the de-compressed tensor and run as ever.  A kind is taken exactly where the plan of the fp16 conv, with
+// the copies a handle would hold, is the kind's fp16 twin by the library's own rule, with the twin's wave count / tile height:
+//   Palette: opted-in GEGLU (tile 16 for tile 13 on the 128-row tiles the palettized kernel has), then the weight stream (tile 14 for
+//            tile 9), then the opted-in single-source small-M GEMM (tile 15 for tile 12)
+//   W8A8:    the weight stream (tile 17) by tile 14's predicate; an observing store asks this without holding a mark
+enum class StoredWeights { Fp16, Palette, W8A8 };
+struct WeightPin {
+  WeightSource kind = WeightSource::Fp16;
+  int tile = 0, staging = 0;
+};
+WeightPin conv_plan_weights(const ConvDesc& d, StoredWeights held, bool opt_in);
+// The pin of a kind by the caller's own choice (the operator entry points): n = waves per workgroup (4, anything else eight) of the
+// weight-stream kinds, the tile height of the others (32 / 64, 128 / 256; 0 = by the shape)
+WeightPin conv_plan_pin(WeightSource kind, int n);
 
 // the SD_LOG_CONVS line of a launch (n_fast: what smgemm.hip / smgeglu.hip add to theirs)
 void conv_plan_log(const ConvDesc& d, const ConvPlan& p, int n_fast = 0);
-
-// The pins of a descriptor that runs from a palette (ConvDesc::staging of plan tiles 14 / 15), written as codes: the inverse of
-// decode_plan for what conv_plan_pal_waves / conv_plan_pal_gemm answered.
-inline int conv_plan_waves_code(int waves) { return waves == 4 ? 4 : 0; }
-inline int conv_plan_bm_code(int bm) { return bm == 32 ? 1 : 2; }
 
 // What launches, as one line (sd_op_conv_plan_kernel): the kernel's name, then only the fields that kernel has -
 //   "igemm <bm>x<bn> ring<stages>[ kg2][ regs]"    "gemm_pipe <bm>x<bn> ring<stages>"    "halo_ks ring<stages>"

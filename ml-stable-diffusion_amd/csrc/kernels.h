@@ -29,6 +29,32 @@ struct GnTwin {
   int silu = 0;
 };
 
+// What a conv reads its weights from.  Fp16: ConvDesc::w and its pre-tiled copies.  Every other kind is ONE packed stream on the device
+// (the weight_prep.h rule of the kind) that a kernel decodes in front of the MFMAs of its fp16 twin; a descriptor that carries one holds
+// no fp16 weights (w == w_tiled == nullptr) and is pinned to the kind's plan tile, so no table row or tuner candidate can move it:
+//   PalWstream  tile 14, wstream.hip  wstream_kernel NBITS > 0   stream of wstream_pal_pack   staging: tile 9's code
+//   PalGemm     tile 15, smgemm.hip   smgemm_pal_kernel          stream of smgemm_pal_pack    staging: tile 12's code (0 = by M)
+//   PalGeglu    tile 16, smgeglu.hip  smgeglu_pal_kernel         stream of smgeglu_pal_pack   staging: tile 13's code
+//   I8Wstream   tile 17, wstream.hip  wstream_kernel NBITS = kWsI8 (W8A8)   stream of wstream_i8_pack   staging: tile 9's code
+enum class WeightSource { Fp16, PalWstream, PalGemm, PalGeglu, I8Wstream };
+struct CompressedWeights {
+  WeightSource kind = WeightSource::Fp16;
+  const void* stream = nullptr;
+  // palettes: the tensor's LUT padded to kPalLutHalves fp16 entries and the index width (1, 2, 4, 6, 8)
+  const half_t* lut = nullptr;
+  int bits = 0;
+  // PalGeglu with the LayerNorm fold (ConvDesc::ln_colsum set): the fp32 norm weight [C0] - the kernel multiplies every LUT value by it
+  // as fold_layernorm_rows does on the host; null without the fold
+  const float* ln_gamma = nullptr;
+  // I8Wstream: the output scale per column scale[n] = fp32(s_a * s_w[n]) and inv_s = fp32(1 / s_a), the factor the kernel quantizes
+  // its activations by
+  const float* scale = nullptr;
+  float inv_s = 0.f;
+  bool palettized() const { return kind == WeightSource::PalWstream || kind == WeightSource::PalGemm || kind == WeightSource::PalGeglu; }
+  const uint8_t* pal() const { return palettized() ? static_cast<const uint8_t*>(stream) : nullptr; }
+  const int8_t* i8() const { return kind == WeightSource::I8Wstream ? static_cast<const int8_t*>(stream) : nullptr; }
+};
+
 struct ConvDesc {
   const half_t* x0 = nullptr;   // [B][Hi][Wi][C0]
   const half_t* x1 = nullptr;   // optional second source (channel concat), [B][Hi][Wi][C1]
@@ -87,26 +113,8 @@ struct ConvDesc {
   int gnf_silu = 0;
   // weights in the fragment-major layout of wstream.hip (launch_wstream_retile), or null: plan tile 9 needs them
   const half_t* w_tiled = nullptr;
-  // palettized weights (plan tile 14, wstream.hip wstream_kernel with NBITS > 0): the bit stream of weight_prep.h wstream_pal_pack, the
-  // tensor's LUT padded to kPalLutHalves fp16 entries, and the index width (1, 2, 4, 6, 8).  A descriptor that carries them is
-  // pinned: it has no fp16 weights (w == w_tiled == nullptr), so no table row or tuner candidate can move it
-  const uint8_t* w_pal = nullptr;
-  const half_t* pal_lut = nullptr;
-  int pal_bits = 0;
-  // pal_gemm: w_pal is the bit stream of weight_prep.h smgemm_pal_pack instead and the descriptor is pinned to plan tile 15
-  // (smgemm.hip smgemm_pal_kernel; staging = conv_plan_bm_code of the tile height, 0 = by M as tile 12)
-  bool pal_gemm = false;
-  // pal_geglu: w_pal is the bit stream of weight_prep.h smgeglu_pal_pack and the descriptor is pinned to plan tile 16 (smgeglu.hip
-  // smgeglu_pal_kernel; staging = the code of tile 13).  With the LayerNorm fold (ln_colsum set) ln_gamma is the fp32 norm weight [C0]:
-  // the kernel multiplies every LUT value by it as fold_layernorm_rows does on the host; without the fold it is null
-  bool pal_geglu = false;
-  const float* ln_gamma = nullptr;
-  // W8A8 (plan tile 17, wstream.hip wstream_kernel with NBITS = kWsI8): the int8 stream of weight_prep.h wstream_i8_pack, the output
-  // scale per column i8_scale[n] = fp32(s_a * s_w[n]) and i8_inv_s = fp32(1 / s_a), the factor the kernel quantizes its activations
-  // by.  A descriptor that carries them is pinned like a palettized one: it has no fp16 weights
-  const int8_t* w_i8 = nullptr;
-  const float* i8_scale = nullptr;
-  float i8_inv_s = 0.f;
+  // what the conv reads its weights from when not from the fp16 matrices (CompressedWeights above); kind Fp16 = w and its copies
+  CompressedWeights cw;
   // weights in the fragment-major layout of wsgemm.hip (launch_wsgemm_retile), or null: the weight-stationary GEGLU kernel
   // (plan tile 10) needs them; launch_conv takes that kernel whenever they are there and no other plan was forced
   const half_t* w_ws = nullptr;
@@ -147,10 +155,10 @@ int wstream_splits(const ConvDesc& d, int nw);            // slabs launch_wstrea
 size_t wstream_tiled_halves(int N, int Ctot, int ksize);
 void launch_wstream_retile(const half_t* w, half_t* wt, int N, int Ctot, int ksize, hipStream_t s);
 int launch_wstream(const ConvDesc& d, float* partial, int nw, hipStream_t s);   // nw: ConvPlan::waves
-// the same launch from palettized weights (d.w_pal / pal_lut / pal_bits): every weight is looked up in the LUT in front of the same
+// the same launch from palettized weights (d.cw of kind PalWstream): every weight is looked up in the LUT in front of the same
 // MFMAs in the same order, so the slabs are bit-identical to launch_wstream's on the de-palettized weights
 int launch_wstream_pal(const ConvDesc& d, float* partial, int nw, hipStream_t s);
-// the same launch from int8 weights and activations quantized in the loader (d.w_i8 / i8_scale / i8_inv_s, plan tile 17): exact int32
+// the same launch from int8 weights and activations quantized in the loader (d.cw of kind I8Wstream, plan tile 17): exact int32
 // sums over a workgroup's slices, scaled per column into the same fp32 slabs
 int launch_wstream_i8(const ConvDesc& d, float* partial, int nw, hipStream_t s);
 bool reduce_twin_ok(int HW, int N, int n_twins, const GnTwin* tw);
@@ -177,7 +185,7 @@ bool smgemm_shape_ok(const ConvDesc& d, int variant);                 // variant
 bool smgemm_wanted(const ConvDesc& d);                                // the library's rule for taking plan tile 12 on its own
 void launch_smgemm(const ConvDesc& d, const ConvPlan& p, hipStream_t s);   // p.bm: 32- or 64-row tiles
 int smgemm_bm(const ConvDesc& d, int variant);                        // the tile height of a variant: 32 or 64 (the planner resolves it)
-// the same GEMM from palettized weights (plan tile 15: d.w_pal in the layout of weight_prep.h smgemm_pal_pack, d.pal_lut, d.pal_bits):
+// the same GEMM from palettized weights (plan tile 15: d.cw of kind PalGemm):
 // the weights are decoded from the LUT into the fragments of the same MFMAs in the same order, the epilogue is launch_smgemm's, so
 // the output is bit-identical to launch_smgemm's on the fp16 weights lut[indices].  One source only.
 void launch_smgemm_pal(const ConvDesc& d, const ConvPlan& p, hipStream_t s);
@@ -194,9 +202,8 @@ bool smgeglu_wanted(const ConvDesc& d);                               // the lib
 int smgeglu_bm(const ConvDesc& d, int variant);                       // the tile height of a variant: 128 or 256 (the planner resolves it)
 void launch_smgeglu(const ConvDesc& d, const ConvPlan& p, hipStream_t s);   // p.bm; d.prof set: the phase-clock build, which fills
 size_t smgeglu_prof_entries(const ConvDesc& d, int variant);          // this many long long: [workgroup][10 waves][8], six stamps used
-// the same launch from palettized weights (plan tile 16: d.w_pal in the layout of weight_prep.h smgeglu_pal_pack, d.pal_lut, d.pal_bits,
-// d.ln_gamma with the fold): LUT value times norm weight decoded into the weight rows of the same stages in front of the same MFMAs,
-// so the output is bit-identical to launch_smgeglu's on the folded fp16 weights.  128-row tiles only, C0 <= 2560, no phase clocks.
+// the same launch from palettized weights (plan tile 16: d.cw of kind PalGeglu, ln_gamma with the fold): LUT value times norm weight
+// decoded into the weight rows of the same stages in front of the same MFMAs, so the output is bit-identical to launch_smgeglu's on the folded fp16 weights.  128-row tiles only, C0 <= 2560, no phase clocks.
 bool smgeglu_pal_shape_ok(const ConvDesc& d, int variant);            // variant 0 / 1 resolving to 128-row tiles
 void launch_smgeglu_pal(const ConvDesc& d, const ConvPlan& p, hipStream_t s);
 

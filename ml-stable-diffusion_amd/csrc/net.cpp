@@ -6,6 +6,7 @@
 #include "net.h"
 
 #include <algorithm>
+#include <type_traits>
 
 #include "conv_plan.h"
 #include "weight_prep.h"
@@ -77,55 +78,19 @@ ConvGeom conv_geom(const std::string& name, const Tensor& x, const ConvArgs& a) 
 }
 }  // namespace
 
+// A tensor the store holds compressed stays compressed on the device where a kernel reads that form (conv_plan_weights): the handle
+// uploads the packed stream with its LUT / scales and no fp16 copy.  Everywhere else a palettized tensor goes up as lut[indices] and
+// a W8A8-marked one as fp16 (the reference's "skipped layer").
 Tensor Net::conv(std::vector<Op>& ops, const std::string& name, const Tensor& x, const ConvArgs& a) {
   if (f32_) return conv_f32(ops, name, x, a);
   const int cin = x.C + (a.x2 ? a.x2->C : 0);
   const bool geglu = a.out_mode == kOutGeglu;
   const float* b = a.bias ? upload_vec(name + ".bias", a.cout, geglu) : nullptr;
-  // A palettized tensor stays palettized on the device where a kernel reads palettes: the handle uploads the index stream and the LUT
-  // and no fp16 copy.  In this order: the weight stream (plan tile 14) where the conv's plan would be tile 9; else, where the call site
-  // opted in (ConvArgs::pal_gemm), the small-M GEMM (plan tile 15) where its plan would be tile 12; else lut[indices] as fp16.
-  const Palette* pal = ws_->palette(name + ".weight");
-  const bool pal_ok = pal && !a.silu_out && !a.ln_colsum;
-  if (pal_ok && a.pal_geglu) {   // a plain GEGLU projection behind its LayerNorm launch (plan tile 16)
-    if (const int bm = pal_geglu_bm(name, x, a, false)) {
-      ConvArgs ap = a;
-      upload_pal_geglu(name, std::string(), cin, bm, ap);
-      return conv_w(ops, name, nullptr, b, x, ap);
-    }
-  }
-  const int pal_waves = pal_ok ? conv_plan_pal_waves(conv_shape(name, x, a)) : 0;
-  const int pal_bm = (pal_ok && !pal_waves && a.pal_gemm && a.k == 1 && !a.x2 && a.out_mode == kOutHalf) ? conv_plan_pal_gemm(conv_shape(name, x, a)) : 0;
-  if (pal_waves || pal_bm) {
-    const HostTensor& t = ws_->get(name + ".weight");
-    const size_t expect = (size_t)a.cout * cin * a.k * a.k;
-    SD_REQUIRE(t.numel() == expect && pal->indices.size() == expect, kInvalidArgument, "%s.weight has %zu elements, expected %zu (%d,%d,%d,%d)",
-               name.c_str(), t.numel(), expect, a.cout, cin, a.k, a.k);
-    SD_REQUIRE(palette_bits_ok(pal->nbits) && pal->lut.size() == (size_t)1 << pal->nbits, kInternal, "%s.weight: a palette of %zu entries for %d bits",
-               name.c_str(), pal->lut.size(), pal->nbits);
-    const PaletteHostCopy h = palette_host_copy((name + ".weight").c_str(), reinterpret_cast<const half_t*>(pal->lut.data()), pal->nbits,
-                                                pal->indices.data(), a.cout, cin, a.k, pal_waves ? PalLayout::Wstream : PalLayout::Gemm);
-    uint8_t* ds = ll_.arena.alloc_n<uint8_t>(h.stream.size());
-    SD_HIP(hipMemcpy(ds, h.stream.data(), h.stream.size(), hipMemcpyHostToDevice));
-    half_t* dl = ll_.arena.alloc_n<half_t>(h.lut.size());
-    SD_HIP(hipMemcpy(dl, h.lut.data(), h.lut.size() * sizeof(half_t), hipMemcpyHostToDevice));
-    ++pal_streamed_;
-    pal_stream_bytes_ += h.stream.size() + h.lut.size() * sizeof(half_t);
-    ConvArgs ap = a;
-    ap.pal_stream = ds;
-    ap.pal_lut = dl;
-    ap.pal_bits = pal->nbits;
-    ap.pal_waves = pal_waves;
-    ap.pal_bm = pal_bm;
-    return conv_w(ops, name, nullptr, b, x, ap);
-  }
-  // W8A8 (the store's marks, WeightStore::quantize_w8a8): plan tile 17 exactly where the conv's plan would be tile 9 - the predicate of
-  // tile 14.  Such a layer uploads the int8 stream and cs and no fp16 copy; a marked layer with any other plan runs fp16 as ever (the
-  // reference's "skipped layer").  An observing store (calibration) puts an absmax op over the conv's source(s) in front of every
-  // conv tile 17 could take: an ordinary member of the launch list that writes one slot nothing else reads.
-  const W8A8Mark* i8 = ws_->w8a8(name + ".weight");
-  const int i8_waves = ((i8 || ws_->observe()) && !pal && !a.silu_out && !a.ln_colsum) ? conv_plan_i8_waves(conv_shape(name, x, a)) : 0;
-  if (ws_->observe() && i8_waves) {
+  const WeightPin pin = weight_plan(name, x, a, false);
+  // An observing store (calibration) puts an absmax op over the conv's source(s) in front of every conv the int8 weight stream could
+  // take: an ordinary member of the launch list that writes one slot nothing else reads.
+  if (ws_->observe() && !ws_->palette(name + ".weight") && !a.silu_out &&
+      conv_plan_weights(conv_shape(name, x, a), StoredWeights::W8A8, false).kind == WeightSource::I8Wstream) {
     float* slot = ll_.arena.alloc_n<float>(1);   // (the arena is zeroed: the running maximum starts at 0)
     observed_.push_back({name + ".weight", slot});
     const half_t *p0 = x.p, *p1 = a.x2 ? a.x2->p : nullptr;
@@ -133,27 +98,52 @@ Tensor Net::conv(std::vector<Op>& ops, const std::string& name, const Tensor& x,
     ops.push_back([=](hipStream_t s) { launch_absmax_half(p0, n0, p1, n1, slot, s); });
     ops.back().label = "absmax " + name;
   }
-  if (i8 && i8_waves) {
-    const size_t expect = (size_t)a.cout * cin * a.k * a.k;
-    SD_REQUIRE(ws_->get(name + ".weight").numel() == expect && i8->q.size() == expect && i8->w_scale.size() == (size_t)a.cout, kInvalidArgument,
-               "%s.weight: expected %zu W8A8 values (%d,%d,%d,%d)", name.c_str(), expect, a.cout, cin, a.k, a.k);
-    const W8A8HostCopy h = w8a8_host_copy((name + ".weight").c_str(), i8->q.data(), i8->w_scale.data(), i8->act_absmax, a.cout, cin, a.k);
-    int8_t* ds = ll_.arena.alloc_n<int8_t>(h.stream.size());
-    SD_HIP(hipMemcpy(ds, h.stream.data(), h.stream.size(), hipMemcpyHostToDevice));
-    float* dcs = ll_.arena.alloc_n<float>(h.cs.size());
-    SD_HIP(hipMemcpy(dcs, h.cs.data(), h.cs.size() * sizeof(float), hipMemcpyHostToDevice));
+  if (pin.kind != WeightSource::Fp16) return conv_w(ops, name, upload_compressed(name, pin, cin, a), b, x, a);
+  return conv_w(ops, name, upload_conv_weight(name, a.cout, cin, a.k, geglu), b, x, a);
+}
+
+WeightPin Net::weight_plan(const std::string& name, const Tensor& x, const ConvArgs& a, bool ln) const {
+  if (f32_ || a.silu_out) return {};
+  const StoredWeights held = ws_->palette(name + ".weight") ? StoredWeights::Palette
+                             : ws_->w8a8(name + ".weight")  ? StoredWeights::W8A8
+                                                            : StoredWeights::Fp16;
+  ConvDesc d = conv_shape(name, x, a);
+  static const float present = 0.f;   // the planner only tests the pointers
+  if (ln) d.ln_colsum = d.bias = &present;
+  return conv_plan_weights(d, held, a.keep_compressed);
+}
+
+ConvWeights Net::upload_compressed(const std::string& name, const WeightPin& pin, int cin, const ConvArgs& a, const std::string& ln_name) {
+  const std::string wname = name + ".weight";
+  const size_t expect = (size_t)a.cout * cin * a.k * a.k;
+  auto up = [this](const auto* host, size_t n) {
+    auto* d = ll_.arena.alloc_n<std::remove_cv_t<std::remove_pointer_t<decltype(host)>>>(n);
+    SD_HIP(hipMemcpy(d, host, n * sizeof(*host), hipMemcpyHostToDevice));
+    return d;
+  };
+  size_t bytes = 0;
+  CompressedWeights cw;
+  if (pin.kind == WeightSource::I8Wstream) {
+    const W8A8Mark* i8 = ws_->w8a8(wname);
+    SD_REQUIRE(i8 && ws_->get(wname).numel() == expect && i8->q.size() == expect && i8->w_scale.size() == (size_t)a.cout, kInvalidArgument,
+               "%s: expected %zu W8A8 values (%d,%d,%d,%d)", wname.c_str(), expect, a.cout, cin, a.k, a.k);
+    cw = upload_w8a8(up, wname.c_str(), i8->q.data(), i8->w_scale.data(), i8->act_absmax, a.cout, cin, a.k, &bytes);
     ++i8_applied_;
-    i8_bytes_ += h.stream.size() + h.cs.size() * sizeof(float);
-    i8_names_.push_back(name + ".weight");
-    ConvArgs ai = a;
-    ai.i8_stream = ds;
-    ai.i8_scale = dcs;
-    ai.i8_inv_s = h.inv_s;
-    ai.i8_waves = i8_waves;
-    return conv_w(ops, name, nullptr, b, x, ai);
+    i8_bytes_ += bytes;
+    i8_names_.push_back(wname);
+  } else {
+    const Palette* pal = ws_->palette(wname);
+    SD_REQUIRE(pal && ws_->get(wname).numel() == expect && pal->indices.size() == expect, kInvalidArgument,
+               "%s has %zu elements, expected %zu (%d,%d,%d,%d)", wname.c_str(), ws_->get(wname).numel(), expect, a.cout, cin, a.k, a.k);
+    SD_REQUIRE(palette_bits_ok(pal->nbits) && pal->lut.size() == (size_t)1 << pal->nbits, kInternal, "%s: a palette of %zu entries for %d bits",
+               wname.c_str(), pal->lut.size(), pal->nbits);
+    cw = upload_palettized(up, pin.kind, wname.c_str(), reinterpret_cast<const half_t*>(pal->lut.data()), pal->nbits, pal->indices.data(), a.cout,
+                           cin, a.k, &bytes);
+    if (!ln_name.empty()) cw.ln_gamma = upload_vec(ln_name + ".weight", cin);
+    ++pal_streamed_;
+    pal_stream_bytes_ += bytes;
   }
-  const half_t* w = upload_conv_weight(name, a.cout, cin, a.k, geglu);
-  return conv_w(ops, name, w, b, x, a);
+  return ConvWeights(cw, pin);
 }
 
 int Net::activation_range(int index, std::string* name, float* absmax) {
@@ -163,37 +153,6 @@ int Net::activation_range(int index, std::string* name, float* absmax) {
   SD_HIP(hipMemcpy(absmax, observed_[(size_t)index].second, sizeof(float), hipMemcpyDeviceToHost));
   *name = observed_[(size_t)index].first;
   return (int)observed_.size();
-}
-
-int Net::pal_geglu_bm(const std::string& name, const Tensor& x, const ConvArgs& a, bool ln) const {
-  if (f32_ || !ws_->palette(name + ".weight") || a.x2 || a.k != 1 || a.out_mode != kOutGeglu || a.silu_out) return 0;
-  ConvDesc d = conv_shape(name, x, a);
-  static const float present = 0.f;   // the planner only tests the pointers
-  if (ln) d.ln_colsum = d.bias = &present;
-  return conv_plan_pal_geglu(d);
-}
-
-void Net::upload_pal_geglu(const std::string& name, const std::string& ln_name, int cin, int bm, ConvArgs& a) {
-  const Palette* pal = ws_->palette(name + ".weight");
-  const size_t expect = (size_t)a.cout * cin;
-  SD_REQUIRE(pal && ws_->get(name + ".weight").numel() == expect && pal->indices.size() == expect, kInvalidArgument,
-             "%s.weight: expected a palette of %zu indices (%d,%d)", name.c_str(), expect, a.cout, cin);
-  SD_REQUIRE(palette_bits_ok(pal->nbits) && pal->lut.size() == (size_t)1 << pal->nbits, kInternal, "%s.weight: a palette of %zu entries for %d bits",
-             name.c_str(), pal->lut.size(), pal->nbits);
-  const PaletteHostCopy h = palette_host_copy((name + ".weight").c_str(), reinterpret_cast<const half_t*>(pal->lut.data()), pal->nbits,
-                                              pal->indices.data(), a.cout, cin, 1, PalLayout::Geglu);
-  uint8_t* ds = ll_.arena.alloc_n<uint8_t>(h.stream.size());
-  SD_HIP(hipMemcpy(ds, h.stream.data(), h.stream.size(), hipMemcpyHostToDevice));
-  half_t* dl = ll_.arena.alloc_n<half_t>(h.lut.size());
-  SD_HIP(hipMemcpy(dl, h.lut.data(), h.lut.size() * sizeof(half_t), hipMemcpyHostToDevice));
-  ++pal_streamed_;
-  pal_stream_bytes_ += h.stream.size() + h.lut.size() * sizeof(half_t);
-  a.pal_stream = ds;
-  a.pal_lut = dl;
-  a.pal_bits = pal->nbits;
-  a.pal_geglu = true;
-  a.pal_bm = bm;
-  a.ln_gamma = ln_name.empty() ? nullptr : upload_vec(ln_name + ".weight", cin);
 }
 
 // fp32 compute path (torch2coreml.py:570-578 converts an SDXL checkpoint's own VAE with FLOAT32 precision): the weights stay
@@ -265,35 +224,17 @@ ConvDesc Net::conv_shape(const std::string& name, const Tensor& x, const ConvArg
   return d;
 }
 
-Tensor Net::conv_w(std::vector<Op>& ops, const std::string& name, const half_t* w, const float* bias, const Tensor& x, const ConvArgs& a) {
+Tensor Net::conv_w(std::vector<Op>& ops, const std::string& name, const ConvWeights& weights, const float* bias, const Tensor& x, const ConvArgs& a) {
   const Tensor* x2 = a.x2;
   const int cout = a.cout, k = a.k;
   const bool geglu = a.out_mode == kOutGeglu, ln = a.ln_colsum != nullptr;
+  const half_t* w = weights.w;
   ConvDesc d = conv_shape(name, x, a);
   d.w = w;
   d.bias = bias;
-  d.w_pal = a.pal_stream;
-  d.pal_lut = a.pal_lut;
-  d.pal_bits = a.pal_bits;
-  if (a.pal_stream && a.pal_geglu) {   // pinned to the palettized GEGLU kernel (plan tile 16); the code of tile 13 for the tile height
-    d.pal_geglu = true;
-    d.ln_gamma = a.ln_gamma;
-    d.tile = 16;
-    d.staging = a.pal_bm == 128 ? 1 : 2;
-  } else if (a.pal_stream && a.pal_bm) {   // pinned to the palettized small-M GEMM (plan tile 15) with the tile height Net::conv read off the plan
-    d.pal_gemm = true;
-    d.tile = 15;
-    d.staging = conv_plan_bm_code(a.pal_bm);
-  } else if (a.pal_stream) {   // pinned to the palettized weight stream (plan tile 14) with the wave count Net::conv read off the plan
-    d.tile = 14;
-    d.staging = conv_plan_waves_code(a.pal_waves);
-  } else if (a.i8_stream) {    // pinned to the int8 weight stream (plan tile 17) likewise
-    d.w_i8 = a.i8_stream;
-    d.i8_scale = a.i8_scale;
-    d.i8_inv_s = a.i8_inv_s;
-    d.tile = 17;
-    d.staging = conv_plan_waves_code(a.i8_waves);
-  }
+  d.cw = weights.cw;   // a compressed source comes with its pin (all zero beside an fp16 matrix)
+  d.tile = weights.pin.tile;
+  d.staging = weights.pin.staging;
   Tensor out;
   if (ln && a.n_trans > 0) {   // fused q|k|v: [M][n_trans] row-major + V^T [B][cout - n_trans][ldT]
     out = new_tensor(x.B, d.Ho, d.Wo, a.n_trans);
@@ -328,7 +269,7 @@ Tensor Net::conv_w(std::vector<Op>& ops, const std::string& name, const half_t* 
   const int cin = x.C + (x2 ? x2->C : 0);
   if (conv_fast_path_ok(d) && !a.silu_out) {
     // the pre-tiled (fragment-major) weight copies the plan of this conv reads: exactly what the planner names
-    const ConvWeightCopies copies = (d.w_pal || d.w_i8) ? ConvWeightCopies{false, false, false} : conv_plan_copies(d);
+    const ConvWeightCopies copies = d.cw.kind != WeightSource::Fp16 ? ConvWeightCopies{false, false, false} : conv_plan_copies(d);
     if (copies.wstream && !ln) {   // small-M layers: the weight-streaming kernel (plan tile 9; never a LayerNorm-fold / q|k|v op)
       half_t* wt = ll_.arena.alloc_n<half_t>(wstream_tiled_halves(cout, cin, k));
       launch_wstream_retile(w, wt, cout, cin, k, ll_.stream);
@@ -359,13 +300,14 @@ Tensor Net::conv_w(std::vector<Op>& ops, const std::string& name, const half_t* 
   char buf[320];
   // trailing "#kind,ksize,stride,up,Ctot,N,M" is the plan-table key of this op (tools/tune_plans.py)
   const int kind = d.out_t ? 3 : (geglu ? 2 : (ln ? 1 : 0));
-  // ("+pal<bits>": the op reads its weights from their palette, plan tile 14 or 15; plan tile 16 is "geglu+pal<bits>[+ln]")
-  // ("+w8a8": the op runs from int8 weights and quantizes its activations, plan tile 17)
-  const std::string palmark = d.w_pal ? "+pal" + std::to_string(d.pal_bits) : d.w_i8 ? std::string("+w8a8") : std::string();
-  const std::string lnmark = ln ? "+ln" : "";
-  snprintf(buf, sizeof(buf), "%s%s%s %d->%d @%dx%d M=%d K=%d %s #%d,%d,%d,%d,%d,%d,%d", k == 3 ? "conv3x3" : (geglu ? (d.pal_geglu ? "geglu" : "geglu1x1") : "gemm1x1"),
-           (d.pal_geglu ? palmark : lnmark).c_str(), (d.pal_geglu ? lnmark : palmark).c_str(), cin, cout, d.Ho, d.Wo, x.B * d.Ho * d.Wo, cin * k * k, name.c_str(), kind, k, a.stride, a.up, cin, cout,
-           x.B * d.Ho * d.Wo);
+  // the weight source in the label: "[+ln]+pal<bits>" from a palette (plan tile 14 or 15), "geglu+pal<bits>[+ln]" for plan tile 16,
+  // "+w8a8" from int8 weights and quantized activations (plan tile 17)
+  const WeightSource src = d.cw.kind;
+  const std::string lnmark = ln ? "+ln" : "", palmark = "+pal" + std::to_string(d.cw.bits);
+  const std::string mark = src == WeightSource::PalGeglu ? palmark + lnmark : lnmark + (src == WeightSource::I8Wstream ? "+w8a8" : src != WeightSource::Fp16 ? palmark : "");
+  snprintf(buf, sizeof(buf), "%s%s %d->%d @%dx%d M=%d K=%d %s #%d,%d,%d,%d,%d,%d,%d",
+           k == 3 ? "conv3x3" : (geglu ? (src == WeightSource::PalGeglu ? "geglu" : "geglu1x1") : "gemm1x1"), mark.c_str(), cin, cout, d.Ho, d.Wo,
+           x.B * d.Ho * d.Wo, cin * k * k, name.c_str(), kind, k, a.stride, a.up, cin, cout, x.B * d.Ho * d.Wo);
   ops.back().label = buf;
   ops.back().flop = 2.0 * x.B * d.Ho * d.Wo * (double)cout * cin * k * k;
   return out;

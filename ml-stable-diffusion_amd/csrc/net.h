@@ -3,6 +3,7 @@
 // (eager lists, the captured forward, per-forward timing and the per-op profile).
 #pragma once
 #include "../../include/sd_mi355x.h"
+#include "conv_plan.h"
 #include "launch_list.h"
 
 namespace sd {
@@ -70,27 +71,20 @@ struct ConvArgs {
   bool vt_perm = false;          // V^T in attention8's key order (AttnDesc::vt_perm)
   float q_scale = 1.f;           // fused q|k|v: the first q_cols columns leave pre-scaled for attention8 (ConvDesc::q_scale)
   int q_cols = 0;
-  // conv_w only, set by Net::conv for a palettized tensor that stays palettized on the device (ConvDesc::w_pal / pal_lut / pal_bits;
-  // w is then null): the op is pinned to plan tile 14 with pal_waves (4 / 8) waves per workgroup
-  const uint8_t* pal_stream = nullptr;
-  const half_t* pal_lut = nullptr;
-  int pal_bits = 0, pal_waves = 0;
-  // conv: the call site opts in to keeping a palettized 1x1 projection on the device as plan tile 15 (smgemm.hip from the index stream).
-  // A pinned op cannot move to igemm_kernel when a later GroupNorm asks for epilogue statistics, so only call sites whose output
-  // feeds no GroupNorm set it (proj_in and the two to_out.0 of a transformer block feed LayerNorms).  conv_w: pal_bm = 32 / 64, the
-  // tile height Net::conv read off the plan (pal_stream is then the stream of smgemm_pal_pack)
-  bool pal_gemm = false;
-  int pal_bm = 0;
-  // conv: the same opt-in for a GEGLU projection (plan tile 16, smgeglu.hip from the index stream).  conv_w: pal_stream is the stream of
-  // smgeglu_pal_pack, pal_bm = 128, ln_gamma the fp32 norm weight on the device when ln_colsum is set (Net::upload_pal_geglu fills them)
-  bool pal_geglu = false;
-  const float* ln_gamma = nullptr;
-  // conv_w only, set by Net::conv for a W8A8-marked tensor whose conv runs from int8 (ConvDesc::w_i8 / i8_scale / i8_inv_s; w is then
-  // null): the op is pinned to plan tile 17 with i8_waves (4 / 8) waves per workgroup
-  const int8_t* i8_stream = nullptr;
-  const float* i8_scale = nullptr;
-  float i8_inv_s = 0.f;
-  int i8_waves = 0;
+  // The call site opts in to keeping a palettized 1x1 projection / GEGLU projection (out_mode says which) on the device as a pinned
+  // plan tile 15 / 16 (conv_plan_weights).  A pinned op cannot move to igemm_kernel when a later GroupNorm asks for epilogue
+  // statistics, so only call sites whose output feeds no GroupNorm set it (proj_in, the two to_out.0 and ff.net.0.proj of a transformer
+  // block feed LayerNorms or GEMMs).
+  bool keep_compressed = false;
+};
+
+// The weights conv_w runs from: an fp16 matrix on the device, or a compressed source with its pin (Net::upload_compressed)
+struct ConvWeights {
+  const half_t* w = nullptr;
+  CompressedWeights cw;
+  WeightPin pin;
+  ConvWeights(const half_t* fp16) : w(fp16) {}
+  ConvWeights(const CompressedWeights& c, const WeightPin& p) : cw(c), pin(p) {}
 };
 
 class Net {
@@ -137,12 +131,13 @@ class Net {
   float* upload_vec(const std::string& name, int n, bool geglu = false);
   // conv uploads <name>.weight / .bias and emits the op; conv_w (fp16 only) takes device pointers
   Tensor conv(std::vector<Op>& ops, const std::string& name, const Tensor& x, const ConvArgs& a);
-  Tensor conv_w(std::vector<Op>& ops, const std::string& name, const half_t* w, const float* bias, const Tensor& x, const ConvArgs& a);
-  // A palettized GEGLU projection that stays palettized (plan tile 16): the tile height (128) when <name>.weight has a palette and its
-  // fp16 plan - with the LayerNorm fold for `ln` - would be tile 13 on the tiles the palettized kernel has, else 0; and the upload of
-  // stream and LUT (and norm weight `ln_name`.weight, with the fold) into the arguments conv_w takes
-  int pal_geglu_bm(const std::string& name, const Tensor& x, const ConvArgs& a, bool ln) const;
-  void upload_pal_geglu(const std::string& name, const std::string& ln_name, int cin, int bm, ConvArgs& a);
+  Tensor conv_w(std::vector<Op>& ops, const std::string& name, const ConvWeights& w, const float* bias, const Tensor& x, const ConvArgs& a);
+  // What the conv of <name>.weight reads its weights from: the planner's answer (conv_plan_weights) for what the store holds for the
+  // tensor - a palette, a W8A8 mark - with the LayerNorm fold for `ln` (asked before fold_layernorm, which then skips the fp16 upload).
+  // upload_compressed then uploads a compressed answer (the palette's stream and LUT and, with the fold, `ln_name`.weight; the int8
+  // stream and scales) and keeps the handle's counters; an Fp16 answer goes through upload_conv_weight as ever
+  WeightPin weight_plan(const std::string& name, const Tensor& x, const ConvArgs& a, bool ln) const;
+  ConvWeights upload_compressed(const std::string& name, const WeightPin& pin, int cin, const ConvArgs& a, const std::string& ln_name = std::string());
   // 3x3 conv to N <= 8 channels, one wavefront per pixel (conv_small.hip): fp32 NCHW into out_nchw (a model's boundary), else
   // fp16 NHWC into out_nhwc.  An fp32 handle runs the fp32 conv into out_nhwc (or a tensor of its own) and transposes.
   void conv_small_n(std::vector<Op>& ops, const std::string& name, const Tensor& x, int cout, half_t* out_nhwc, float* out_nchw);

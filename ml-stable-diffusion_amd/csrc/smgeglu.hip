@@ -583,20 +583,20 @@ bool smgeglu_pal_shape_ok(const ConvDesc& d, int variant) {
 }
 
 void launch_smgeglu_pal(const ConvDesc& d, const ConvPlan& p, hipStream_t s) {
-  SD_REQUIRE(p.bm == 128 && sg_tiles(d, p.bm) && d.C0 <= kSgPalMaxK && !d.prof && d.w_pal && d.pal_geglu && d.pal_lut && palette_bits_ok(d.pal_bits) &&
-                 (d.ln_gamma != nullptr) == (d.ln_colsum != nullptr),
+  SD_REQUIRE(p.bm == 128 && sg_tiles(d, p.bm) && d.C0 <= kSgPalMaxK && !d.prof && d.cw.kind == WeightSource::PalGeglu && d.cw.stream && d.cw.lut &&
+                 palette_bits_ok(d.cw.bits) && (d.cw.ln_gamma != nullptr) == (d.ln_colsum != nullptr),
              kInvalidArgument,
              "plan tile 16 (smgeglu.hip, palettized): not a 1x1 GEGLU projection it tiles with 128-row tiles, or no palette / norm weight "
-             "(C0=%d N=%d M=%d bm=%d bits=%d)", d.C0, d.N, d.B * d.Ho * d.Wo, p.bm, d.pal_bits);
+             "(C0=%d N=%d M=%d bm=%d bits=%d)", d.C0, d.N, d.B * d.Ho * d.Wo, p.bm, d.cw.bits);
   SgPalArgs a;
-  static_cast<SgArgs&>(a) = sg_common_args(d, p.bm, d.w_pal);   // the stream holds at least 64 N bytes
-  a.pal = d.w_pal;
-  a.lut = d.pal_lut;
-  a.gamma = d.ln_gamma;
+  static_cast<SgArgs&>(a) = sg_common_args(d, p.bm, d.cw.pal());   // the stream holds at least 64 N bytes
+  a.pal = d.cw.pal();
+  a.lut = d.cw.lut;
+  a.gamma = d.cw.ln_gamma;
   a.nhalf = 2 * smgemm_pal_groups(d.C0);
   const unsigned nwg = (unsigned)(d.B * d.Ho * d.Wo / p.bm) * (d.N / SG_WROWS);
   conv_plan_log(d, p, a.order.n_fast);
-  pal_dispatch_bits(d.pal_bits, "palettized smgeglu", [&](auto nb) {
+  pal_dispatch_bits(d.cw.bits, "palettized smgeglu", [&](auto nb) {
     constexpr int NB = decltype(nb)::value;
     constexpr size_t lds = SgPalCfg<128, NB>::LDS;
     auto k = smgeglu_pal_kernel<128, NB>;

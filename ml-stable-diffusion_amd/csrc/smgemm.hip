@@ -512,17 +512,17 @@ void launch_smgemm(const ConvDesc& d, const ConvPlan& p, hipStream_t s) {
 }
 
 void launch_smgemm_pal(const ConvDesc& d, const ConvPlan& p, hipStream_t s) {
-  SD_REQUIRE(sm_tiles(d, p.bm) && !d.x1 && d.w_pal && d.pal_gemm && d.pal_lut && palette_bits_ok(d.pal_bits), kInvalidArgument,
+  SD_REQUIRE(sm_tiles(d, p.bm) && !d.x1 && d.cw.kind == WeightSource::PalGemm && d.cw.stream && d.cw.lut && palette_bits_ok(d.cw.bits), kInvalidArgument,
              "plan tile 15 (smgemm.hip, palettized): not a single-source 1x1 GEMM it tiles, or no palette (C0=%d C1=%d N=%d M=%d bits=%d)", d.C0,
-             d.x1 ? d.C1 : 0, d.N, d.B * d.Ho * d.Wo, d.pal_bits);
+             d.x1 ? d.C1 : 0, d.N, d.B * d.Ho * d.Wo, d.cw.bits);
   const int bm = p.bm;
   SmPalArgs a;
-  const int n_fast = sm_common_args(a, d, d.C0, bm, d.w_pal);   // the stream holds at least 64 N bytes; tile 12's order, from the fp16 sizes
-  a.pal = d.w_pal;
-  a.lut = d.pal_lut;
+  const int n_fast = sm_common_args(a, d, d.C0, bm, d.cw.pal());   // the stream holds at least 64 N bytes; tile 12's order, from the fp16 sizes
+  a.pal = d.cw.pal();
+  a.lut = d.cw.lut;
   a.ngroups = smgemm_pal_groups(d.C0);
   conv_plan_log(d, p, n_fast);
-  pal_dispatch_bits(d.pal_bits, "palettized smgemm", [&](auto nb) {
+  pal_dispatch_bits(d.cw.bits, "palettized smgemm", [&](auto nb) {
     if (bm == 32) launch_sm_pal<32, decltype(nb)::value>(a, s);
     else launch_sm_pal<64, decltype(nb)::value>(a, s);
   });

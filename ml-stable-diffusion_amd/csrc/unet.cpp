@@ -223,7 +223,7 @@ Tensor UNet::transformer_block(std::vector<Op>& ops, const std::string& b, const
                          (heads == 5 || xo_mode == 2);
   const bool xo_pre = xo_branch && xo_mode == 3 && heads == 5;
   Tensor h1;
-  if (!xo_pre) h1 = conv(ops, b + ".attn1.to_out.0", a1, {.cout = C, .res = h.p, .pal_gemm = true});
+  if (!xo_pre) h1 = conv(ops, b + ".attn1.to_out.0", a1, {.cout = C, .res = h.p, .keep_compressed = true});
   // --- cross attention: K / V^T of the prompt are computed by ctx_ops_ when the prompt changes
   const int ldvc = round_up(L, 8);
   Tensor k2 = conv(ctx_ops_, b + ".attn2.to_k", ctx_, {.cout = C, .bias = false});
@@ -310,21 +310,21 @@ Tensor UNet::transformer_block(std::vector<Op>& ops, const std::string& b, const
     }
     a2 = attention(ops, q2, k2.p, vt2.p, heads, S, L, C, ldvc, C);
   }
-  if (!branch_done) h2 = conv(ops, b + ".attn2.to_out.0", a2, {.cout = C, .res = h1.p, .pal_gemm = true});
+  if (!branch_done) h2 = conv(ops, b + ".attn2.to_out.0", a2, {.cout = C, .res = h1.p, .keep_compressed = true});
   // --- GEGLU feed-forward (norm3 folded the same way)
   Tensor g;
   // A palettized ff.net.0.proj whose plan is smgeglu.hip on 128-row tiles stays palettized (plan tile 16): stream, LUT and - with the
   // fold - norm3.weight go up, colsum and the folded bias come from lut[indices] as ever, no fp16 matrix is uploaded
   if (can_fold_ln(h2, 8 * C, true)) {
-    ConvArgs ga{.cout = 8 * C, .out_mode = kOutGeglu};
-    const int pal_bm = pal_geglu_bm(b + ".ff.net.0.proj", h2, ga, true);
-    LnFold f = fold_layernorm(b + ".norm3", {b + ".ff.net.0.proj"}, C, 8 * C, true, pal_bm == 0);
+    ConvArgs ga{.cout = 8 * C, .out_mode = kOutGeglu, .keep_compressed = true};
+    const WeightPin pin = weight_plan(b + ".ff.net.0.proj", h2, ga, true);
+    const bool fp16 = pin.kind == WeightSource::Fp16;
+    LnFold f = fold_layernorm(b + ".norm3", {b + ".ff.net.0.proj"}, C, 8 * C, true, fp16);
     ga.ln_colsum = f.colsum;
-    if (pal_bm) upload_pal_geglu(b + ".ff.net.0.proj", b + ".norm3", C, pal_bm, ga);
-    g = conv_w(ops, b + ".ff.net.0.proj", f.w, f.bias, h2, ga);
+    g = conv_w(ops, b + ".ff.net.0.proj", fp16 ? ConvWeights(f.w) : upload_compressed(b + ".ff.net.0.proj", pin, C, ga, b + ".norm3"), f.bias, h2, ga);
   } else {
     Tensor n3 = layer_norm(ops, b + ".norm3", h2);
-    g = conv(ops, b + ".ff.net.0.proj", n3, {.cout = 8 * C, .out_mode = kOutGeglu, .pal_geglu = true});
+    g = conv(ops, b + ".ff.net.0.proj", n3, {.cout = 8 * C, .out_mode = kOutGeglu, .keep_compressed = true});
   }
   // the tail of the SpatialTransformer - ff.net.2 + residual -> proj_out + residual - as ONE launch at the 320-channel level
   // (ffn_proj_kernel: the intermediate never goes to HBM, the output's GroupNorm statistics for the next resnet come out of it);
@@ -502,7 +502,7 @@ Tensor UNet::transformer(std::vector<Op>& ops, const std::string& p, const Tenso
     ops.back().flop = 8.0 * x.M() * (double)C * C;
   } else {
     Tensor t0 = group_norm(ops, p + ".norm", x, nullptr, 1e-6f, false);
-    h = conv(ops, p + ".proj_in", t0, {.cout = x.C, .pal_gemm = true});
+    h = conv(ops, p + ".proj_in", t0, {.cout = x.C, .keep_compressed = true});
   }
   bool tail_done = false;
   const std::string proj_name = p + ".proj_out";

@@ -7,7 +7,7 @@
 #include <cstdint>
 #include <vector>
 
-#include "sd_common.h"
+#include "kernels.h"
 
 namespace sd {
 
@@ -230,18 +230,45 @@ struct PaletteHostCopy {
   std::vector<uint8_t> stream;
   std::vector<half_t> lut;
 };
-enum class PalLayout { Wstream, Gemm, Geglu };
 inline PaletteHostCopy palette_host_copy(const char* what, const half_t* lut, int nbits, const uint8_t* indices, int N, int Ctot, int ksize,
-                                         PalLayout layout) {
+                                         WeightSource kind) {   // one of the three palettized kinds
   palette_check_indices(what, indices, (size_t)N * Ctot * ksize * ksize, nbits);
   PaletteHostCopy h;
-  h.stream.resize(layout == PalLayout::Wstream ? wstream_pal_bytes(N, Ctot, ksize, nbits) : smgemm_pal_bytes(N, Ctot, nbits));
-  if (layout == PalLayout::Gemm) smgemm_pal_pack(indices, N, Ctot, nbits, h.stream.data());
-  else if (layout == PalLayout::Geglu) smgeglu_pal_pack(indices, N, Ctot, nbits, h.stream.data());
+  h.stream.resize(kind == WeightSource::PalWstream ? wstream_pal_bytes(N, Ctot, ksize, nbits) : smgemm_pal_bytes(N, Ctot, nbits));
+  if (kind == WeightSource::PalGemm) smgemm_pal_pack(indices, N, Ctot, nbits, h.stream.data());
+  else if (kind == WeightSource::PalGeglu) smgeglu_pal_pack(indices, N, Ctot, nbits, h.stream.data());
   else wstream_pal_pack(indices, N, Ctot, ksize, nbits, h.stream.data());
   h.lut.assign(kPalLutHalves, (half_t)0);
   std::copy(lut, lut + (1 << nbits), h.lut.begin());
   return h;
+}
+
+// The one upload of a compressed weight source, per host-copy type: host copy -> device stream + LUT / scales -> the descriptor's
+// source (ConvDesc::cw).  `up(host, n)` returns a device copy of n elements from memory the caller owns (a handle's arena, an operator
+// entry point's scratch); *bytes, when asked for, gets what went up.
+template <class Up>
+CompressedWeights upload_palettized(Up&& up, WeightSource kind, const char* what, const half_t* lut, int nbits, const uint8_t* indices, int N,
+                                    int Ctot, int ksize, size_t* bytes = nullptr) {
+  const PaletteHostCopy h = palette_host_copy(what, lut, nbits, indices, N, Ctot, ksize, kind);
+  CompressedWeights c;
+  c.kind = kind;
+  c.stream = up(h.stream.data(), h.stream.size());
+  c.lut = up(h.lut.data(), h.lut.size());
+  c.bits = nbits;
+  if (bytes) *bytes = h.stream.size() + h.lut.size() * sizeof(half_t);
+  return c;
+}
+template <class Up>
+CompressedWeights upload_w8a8(Up&& up, const char* what, const int8_t* q, const float* w_scale, float act_absmax, int N, int Ctot, int ksize,
+                              size_t* bytes = nullptr) {
+  const W8A8HostCopy h = w8a8_host_copy(what, q, w_scale, act_absmax, N, Ctot, ksize);
+  CompressedWeights c;
+  c.kind = WeightSource::I8Wstream;
+  c.stream = up(h.stream.data(), h.stream.size());
+  c.scale = up(h.cs.data(), h.cs.size());
+  c.inv_s = h.inv_s;
+  if (bytes) *bytes = h.stream.size() + h.cs.size() * sizeof(float);
+  return c;
 }
 
 }  // namespace sd

@@ -526,11 +526,11 @@ WsArgs ws_args(const ConvDesc& d, float* partial) {
   a.x0 = d.x0;
   a.x1 = d.x1;
   a.wt = d.w_tiled;
-  a.pal = d.w_pal;
-  a.lut = d.pal_lut;
-  a.w8 = d.w_i8;
-  a.cs = d.i8_scale;
-  a.inv_s = d.i8_inv_s;
+  a.pal = d.cw.pal();
+  a.lut = d.cw.lut;
+  a.w8 = d.cw.i8();
+  a.cs = d.cw.scale;
+  a.inv_s = d.cw.inv_s;
   a.partial = partial;
   a.C0 = d.C0;
   a.C1 = d.x1 ? d.C1 : 0;
@@ -599,14 +599,14 @@ int launch_wstream(const ConvDesc& d, float* partial, int nw, hipStream_t s) {
 }
 
 int launch_wstream_pal(const ConvDesc& d, float* partial, int nw, hipStream_t s) {
-  SD_REQUIRE(wstream_shape_ok(d) && d.w_pal && d.pal_lut && palette_bits_ok(d.pal_bits),
+  SD_REQUIRE(wstream_shape_ok(d) && d.cw.kind == WeightSource::PalWstream && d.cw.stream && d.cw.lut && palette_bits_ok(d.cw.bits),
              kInvalidArgument, "palettized wstream: shape not eligible or no palette (k=%d C0=%d C1=%d N=%d %dx%d bits=%d)", d.ksize, d.C0, d.C1,
-             d.N, d.Ho, d.Wo, d.pal_bits);
-  return launch_ws_conv(d, partial, d.pal_bits, nw, s);
+             d.N, d.Ho, d.Wo, d.cw.bits);
+  return launch_ws_conv(d, partial, d.cw.bits, nw, s);
 }
 
 int launch_wstream_i8(const ConvDesc& d, float* partial, int nw, hipStream_t s) {
-  SD_REQUIRE(wstream_shape_ok(d) && d.w_i8 && d.i8_scale && d.i8_inv_s > 0.f && std::isfinite(d.i8_inv_s), kInvalidArgument,
+  SD_REQUIRE(wstream_shape_ok(d) && d.cw.i8() && d.cw.scale && d.cw.inv_s > 0.f && std::isfinite(d.cw.inv_s), kInvalidArgument,
              "int8 wstream: shape not eligible or no int8 weights (k=%d C0=%d C1=%d N=%d %dx%d)", d.ksize, d.C0, d.C1, d.N, d.Ho, d.Wo);
   return launch_ws_conv(d, partial, kWsI8, nw, s);
 }
