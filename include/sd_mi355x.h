@@ -108,7 +108,8 @@ int sd_weights_observe_activations(sd_weights* w, int on);
 typedef struct sd_unet_config {
   int32_t batch;                 /* UNet batch (2 = classifier-free guidance for one image)          */
   int32_t in_channels, out_channels;
-  int32_t height, width;         /* latent size (image / 8)                                          */
+  int32_t height, width;         /* latent size (image / 8); a UNet needs both to divide by
+                                    2^(n_levels - 1), else SD_ERR_INVALID_ARGUMENT at create         */
   int32_t n_levels;
   int32_t block_out_channels[SD_MAX_LEVELS];
   int32_t down_cross_attn[SD_MAX_LEVELS];   /* 1: CrossAttnDownBlock2D, 0: DownBlock2D               */

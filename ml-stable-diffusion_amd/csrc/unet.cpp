@@ -27,7 +27,23 @@
 
 namespace sd {
 
-UNet::UNet(const sd_unet_config& cfg, const WeightStore& ws, int device) : Net(cfg, ws, device) {
+namespace {
+
+// A UNet's up path doubles the image once per level and concatenates it with the skip of the same level (unet.py:213-216, :498-500):
+// the latent size must divide by 2^(levels - 1), or the stride-2 convs round up and the concat meets two sizes.  Checked before the
+// base class opens the device.  (A ControlNet has no up path: any size its downsamplers take.)
+const sd_unet_config& checked_size(const sd_unet_config& cfg) {
+  if (!cfg.is_controlnet && cfg.n_levels >= 1 && cfg.n_levels <= SD_MAX_LEVELS) {
+    const int q = 1 << (cfg.n_levels - 1);
+    SD_REQUIRE(cfg.height % q == 0 && cfg.width % q == 0, kInvalidArgument,
+               "latent size %dx%d: a UNet of %d levels needs height and width that divide by %d", cfg.height, cfg.width, cfg.n_levels, q);
+  }
+  return cfg;
+}
+
+}  // namespace
+
+UNet::UNet(const sd_unet_config& cfg, const WeightStore& ws, int device) : Net(checked_size(cfg), ws, device) {
   if (cfg_.support_controlnet && !cfg_.is_controlnet && tune_env_int("SD_CN_CONCURRENT", 1) != 0) {
     SD_HIP(hipStreamCreateWithFlags(&cn_stream_, hipStreamNonBlocking));
     SD_HIP(hipEventCreateWithFlags(&ev_cn_fork_, hipEventDisableTiming));

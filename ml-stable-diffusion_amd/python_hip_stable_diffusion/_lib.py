@@ -430,6 +430,8 @@ def conv2d(x, w, bias=None, res=None, stride=1, upsample=False, tile=0, splitk=0
     Wo = (W * up + 2 * pad - k) // stride + 1
     bias = None if bias is None else f32(bias)
     res = None if res is None else f16(res)
+    if res is not None and res.shape != (B, Cout, Ho, Wo):   # the library reads B * Cout * Ho * Wo halves behind the pointer
+        raise ValueError(f"conv2d: res must be (B, Cout, Ho, Wo) = {(B, Cout, Ho, Wo)}, got {res.shape}")
     out = np.empty((B, Cout, Ho, Wo), np.float16)
     ms = C.c_float(0)
     check(lib().sd_op_conv2d(ptr(x), ptr(w), fptr(bias), ptr(res), ptr(out), B, Cin, H, W, Cout, k, stride,

@@ -4,7 +4,8 @@ array_equal, at the operator, on a whole handle and through the pipeline.
 
 Shapes: the MFMA path of launch_conv takes input channel counts that are multiples of 64 (conv_fast_path_ok), so the operator cases
 use the smallest such shapes that still reach each form of the kernel: two slices with six dead waves, a ragged last workgroup of
-slices, three K splits, a second source, the upsample gather, the 16-pixel-wide form, ragged and multi-block M of the 1x1 form."""
+slices, three K splits, a second source, the upsample gather, the 16-pixel-wide form, ragged and multi-block M of the 1x1 form, and
+three images with H != W (a block that is one image, blocks that straddle images with a half-empty last one, one sub-tile per image)."""
 import json
 import os
 import re
@@ -33,6 +34,10 @@ CASES = {
     "3x3 W=16": (2, 64, 0, 16, 16, 32, 3, False, 8),
     "1x1 M=72": (1, 64, 0, 8, 9, 32, 1, False, 8),
     "1x1 M=200 two M blocks": (2, 64, 0, 10, 10, 32, 1, False, 4),
+    # H != W: the loader finds image and row of each 8-row sub-tile from H / 8 sub-tiles per image
+    "3x3 16x8 a block is one image": (2, 64, 0, 16, 8, 32, 3, False, 8),
+    "3x3 24x8 batch 3 blocks straddle images": (3, 64, 0, 24, 8, 32, 3, False, 4),
+    "3x3 8x16 one sub-tile per image": (2, 64, 0, 8, 16, 32, 3, False, 8),
 }
 
 

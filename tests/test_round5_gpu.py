@@ -1,6 +1,7 @@
 """Round-5 kernels through the C ABI against fp32 torch:
   * the small-M weight-streaming conv kernel (wstream.hip, plan tile 9): 3x3 stride-1 convs of the 8x8 / 16x16 levels incl. the
-    nearest-x2 upsample gather, 1x1 GEMMs, dead K-slice waves, odd batch (unet.py:435-468, :496-500);
+    nearest-x2 upsample gather, 1x1 GEMMs, dead K-slice waves, odd batch (unet.py:435-468, :496-500), and the images with H != W that
+    its shape predicate admits (8 or 16 wide, any multiple of 8 high: the low levels of a 1024x512 image);
   * GroupNorm(+SiLU) written by the conv's own slab combine ("twin", reduce_twin_kernel) instead of a GroupNorm launch
     (unet.py:430-451, :472-481, :528-531).
 Tolerances as tests/test_ops_gpu.py: PSNR >= 60 dB, max |err| <= 4e-3 * max|ref| + 1e-3 (fp16 I/O, fp32 accumulate)."""
@@ -52,7 +53,31 @@ WS_CASES = [  # (B, Cin, H, W, Cout, k, upsample)
     (2, 128, 8, 8, 96, 1, False),       # 1x1
     (2, 1280, 8, 8, 1280, 1, False),    # proj_in / to_out of the mid block
     (5, 64, 4, 4, 32, 1, False),        # 1x1: M = 80 < 128 (masked rows)
+    # H != W: the loader finds image b and first row y0 of each 8-row sub-tile from tpi = H / 8 sub-tiles per image
+    (2, 64, 16, 8, 64, 3, False),       # a 128-pixel block is exactly one 16x8 image
+    (1, 96, 24, 8, 32, 3, False),       # three sub-tiles: the last block is half empty; 3 input slices: dead waves
+    (3, 64, 24, 8, 64, 3, False),       # nine sub-tiles: blocks straddle images (sub-tile 0 of image b+1 must not read image b's rows)
+    (2, 64, 8, 16, 96, 3, False),       # 16 wide, one sub-tile per image
+    (1, 128, 32, 16, 64, 3, False),     # tpi = 4
+    (2, 64, 24, 16, 32, 3, False),      # tpi = 3
+    (2, 64, 8, 4, 64, 3, True),         # upsample: 8x4 source, 16x8 output
+    (1, 64, 4, 8, 64, 3, True),         # upsample: 4x8 source, 8x16 output
+    (2, 64, 12, 8, 32, 3, True),        # upsample: 12x8 source, 24x16 output
+    (3, 64, 24, 8, 64, 1, False),       # 1x1, M = 576: ragged 128-row blocks
+    # The two 96-channel cases above never reach the streaming kernel: the MFMA path takes input channel counts that are multiples
+    # of 64 (conv_fast_path_ok), sd_op_conv2d runs the direct kernel for the rest whatever tile is asked for, and the test now says
+    # so (plan -1).  These two have the dead waves and ragged slice groups those cases were written for: six 32-channel slices are
+    # two dead waves of eight, and a second group of four with two live waves
+    (1, 192, 8, 8, 32, 3, False),       # odd batch: the second sub-tile masked
+    (1, 192, 24, 8, 32, 3, False),      # three sub-tiles: the last block is half empty
 ]
+
+
+def signed_input(rs, b, c, h, w_):
+    """noise + 0.5 b + 0.1 y: every image and every row carries its own offset, so a sub-tile read from the wrong image or the wrong
+    row cannot pass"""
+    sig = 0.5 * np.arange(b).reshape(b, 1, 1, 1) + 0.1 * np.arange(h).reshape(1, 1, h, 1)
+    return h16(rs.randn(b, c, h, w_) + sig)
 
 
 @pytest.mark.parametrize("case", WS_CASES, ids=lambda c: "x".join(map(str, c)))
@@ -60,14 +85,19 @@ WS_CASES = [  # (B, Cin, H, W, Cout, k, upsample)
 def test_weight_streaming_conv_matches_torch(case, tile):
     b, cin, h, w_, cout, k, up = case
     rs = np.random.RandomState(cin + cout + h + k)
-    x = h16(rs.randn(b, cin, h, w_))
+    x = signed_input(rs, b, cin, h, w_)
     w = h16(rs.randn(cout, cin, k, k) / np.sqrt(cin * k * k))
     bias = (0.1 * rs.randn(cout)).astype(np.float32)
     ho = h * (2 if up else 1)
     res = h16(rs.randn(b, cout, ho, ho * w_ // h))
     ref = conv_ref(x, w, bias, res, up).numpy()
-    out, _ = _lib.conv2d(x, w, bias, res, upsample=up, tile=tile)
+    out, _, plan, _ = _lib.conv2d_ex(x, w, bias, res, upsample=up, tile=tile)
+    # the kernel that ran: the stream with 8 or 4 waves, one slab per group of slices - or, off the MFMA path, the direct kernel
+    on_mfma_path = cin % 64 == 0
+    assert plan == ([9, tile // 10, -(-(cin // 32) // (4 if tile == 49 else 8)), 1] if on_mfma_path else [-1, -1, -1, -1]), plan
     close(out, ref, f"wstream conv {case} tile {tile}")
+    same, _ = _lib.conv2d(x, w, bias, res, upsample=up, tile=tile)
+    assert np.array_equal(out, same), "sd_op_conv2d_ex without its extras is sd_op_conv2d"
     again, _ = _lib.conv2d(x, w, bias, res, upsample=up, tile=tile, iters=3)
     assert np.array_equal(out, again), "replays must be bit-identical (fixed-order slab sums)"
     # the same conv on the tiled kernels of igemm.hip: two kernels, one answer
@@ -84,28 +114,70 @@ def test_weight_streaming_rejects_ineligible_shapes():
     x = h16(rs.randn(1, 64, 8, 8))
     with pytest.raises(ValueError):
         _lib.conv2d(x, w, stride=2, tile=9)     # stride 2
+    with pytest.raises(ValueError):
+        _lib.conv2d(h16(rs.randn(1, 64, 16, 12)), w, tile=9)   # 16x12: the width is neither 8 nor 16
+    with pytest.raises(ValueError):
+        _lib.conv2d(h16(rs.randn(1, 64, 12, 8)), w, tile=9)    # 12x8: the height is no multiple of the 8-row sub-tile
+    # an 8x8 source upsampled "to 16x8" does not exist: nearest x2 gives 16x16, and a 16x8 residual says the caller meant otherwise.
+    # The wrapper refuses before the library is called (it would read the residual as 16x16: past the end of the array)
+    with pytest.raises(ValueError, match="res"):
+        _lib.conv2d(x, w, None, h16(rs.randn(1, 64, 16, 8)), upsample=True, tile=9)
 
 
-TWIN_CASES = [  # (B, Cin, HW, Cout, k, silu, tile)
-    (2, 128, 8, 1280, 3, True, 0),      # 40-channel groups, default plan forced onto the slab path
-    (2, 128, 8, 1280, 3, True, 9),      # ... behind the weight-streaming kernel
-    (2, 1280, 8, 1280, 3, True, 9),     # full-size resnet conv of the 8x8 level
-    (2, 64, 16, 640, 3, True, 0),       # 20-channel groups at 16x16
-    (2, 64, 16, 1280, 3, False, 9),     # SpatialTransformer norm (no SiLU) at 16x16: 10 items per thread
-    (1, 64, 16, 2560, 1, True, 0),      # 80-channel groups: 20 items per thread
-    (2, 256, 8, 1280, 1, False, 0),     # proj_out-like 1x1 GEMM forced onto the slab path
-    (2, 64, 4, 256, 3, True, 0),        # 8-channel groups, 4x4 image
+@pytest.mark.parametrize("c1", [32, 64])
+def test_weight_streaming_conv_two_sources_and_temb_at_16x8(c1):
+    """A resnet conv1 of an up block at a 16x8 level (unet.py:213-216 concat, :478-481 + temb): the second source's slices and the
+    time-embedding row on the streaming kernel where a 128-pixel block is one whole image.  C1 = 64 runs there.  C1 = 32 does not:
+    wstream_shape_ok admits it, but the MFMA path of sd_op_conv2d_ex takes sources that are multiples of 64 channels
+    (conv_fast_path_ok), so the direct kernel answers whatever tile is asked for - the plan says so, and the parity checks still hold."""
+    b, c0, h, w_, cout = 2, 64, 16, 8, 64
+    rs = np.random.RandomState(1608 + c1)
+    x0, x1 = signed_input(rs, b, c0, h, w_), signed_input(rs, b, c1, h, w_)
+    w = h16(rs.randn(cout, c0 + c1, 3, 3) / np.sqrt((c0 + c1) * 9))
+    bias = (0.1 * rs.randn(cout)).astype(np.float32)
+    temb = rs.randn(b, cout).astype(np.float32)
+    res = h16(rs.randn(b, cout, h, w_))
+    ref = conv_ref(np.concatenate([x0, x1], axis=1), w, bias, res, False).numpy() + temb[:, :, None, None]
+    out, _, plan, _ = _lib.conv2d_ex(x0, w, bias, res, x1=x1, temb=temb, tile=9)
+    assert plan == ([9, 0, 1, 1] if c1 == 64 else [-1, -1, -1, -1]), plan
+    close(out, ref, "wstream conv, two sources + temb, 16x8")
+    again, _, _, _ = _lib.conv2d_ex(x0, w, bias, res, x1=x1, temb=temb, tile=9, iters=3)
+    assert np.array_equal(out, again)
+    base, _, _, _ = _lib.conv2d_ex(x0, w, bias, res, x1=x1, temb=temb)
+    close(out, base.astype(np.float32), "wstream vs the library's own plan, two sources + temb, 16x8", min_psnr=65.0)
+
+
+TWIN_CASES = [  # (B, Cin, (H, W), Cout, k, silu, tile)
+    (2, 128, (8, 8), 1280, 3, True, 0),      # 40-channel groups, default plan forced onto the slab path
+    (2, 128, (8, 8), 1280, 3, True, 9),      # ... behind the weight-streaming kernel
+    (2, 1280, (8, 8), 1280, 3, True, 9),     # full-size resnet conv of the 8x8 level
+    (2, 64, (16, 16), 640, 3, True, 0),      # 20-channel groups at 16x16
+    (2, 64, (16, 16), 1280, 3, False, 9),    # SpatialTransformer norm (no SiLU) at 16x16: 10 items per thread
+    (1, 64, (16, 16), 2560, 1, True, 0),     # 80-channel groups: 20 items per thread
+    (2, 256, (8, 8), 1280, 1, False, 0),     # proj_out-like 1x1 GEMM forced onto the slab path
+    (2, 64, (4, 4), 256, 3, True, 0),        # 8-channel groups, 4x4 image
+    # H != W: the combine indexes by HW alone (HW = 128, 128, 192, 32 - it had only seen 16, 64 and 256)
+    (2, 64, (16, 8), 640, 3, True, 9),       # HW = 128 behind the weight-streaming kernel
+    (2, 128, (8, 16), 1280, 3, True, 9),     # HW = 128, 16 wide
+    (1, 64, (24, 8), 256, 3, False, 0),      # HW = 192: no power of two
+    (2, 64, (8, 4), 1280, 1, True, 0),       # HW = 32
 ]
 
 
-@pytest.mark.parametrize("case", TWIN_CASES, ids=lambda c: "x".join(map(str, c)))
+def twin_id(c):
+    """square cases keep the ids they had when the tuple carried one HW"""
+    h, w_ = c[2]
+    return "x".join(map(str, c[:2] + ((h,) if h == w_ else (f"{h}by{w_}",)) + c[3:]))
+
+
+@pytest.mark.parametrize("case", TWIN_CASES, ids=twin_id)
 def test_groupnorm_twin_of_the_slab_combine(case):
-    b, cin, hw, cout, k, silu, tile = case
-    rs = np.random.RandomState(cin + cout + hw)
-    x = h16(rs.randn(b, cin, hw, hw))
+    b, cin, (hh, ww), cout, k, silu, tile = case
+    rs = np.random.RandomState(cin + cout + hh + (0 if hh == ww else 3 * ww))
+    x = h16(rs.randn(b, cin, hh, ww))
     w = h16(rs.randn(cout, cin, k, k) / np.sqrt(cin * k * k))
     bias = (0.1 * rs.randn(cout)).astype(np.float32) + 0.3
-    res = h16(rs.randn(b, cout, hw, hw) * 0.5 + 0.2)
+    res = h16(rs.randn(b, cout, hh, ww) * 0.5 + 0.2)
     gw = (1.0 + 0.2 * rs.randn(cout)).astype(np.float32)
     gb = (0.2 * rs.randn(cout)).astype(np.float32)
     eps = 1e-5
@@ -132,6 +204,15 @@ def test_groupnorm_twin_rejects_what_it_cannot_hold():
     g = np.ones(64, np.float32)
     with pytest.raises(ValueError):   # 32x32 = 1024 pixels per (sample, group) slice: more than a workgroup keeps in registers
         _lib.conv2d_groupnorm(x, w, g, g, groups=32, producer_stats=2)
+    # reduce_twin_ok: HW * (channels per group) / 4 <= 5120 items per workgroup
+    x = h16(rs.randn(1, 64, 32, 16))
+    g = np.ones(2560, np.float32)
+    with pytest.raises(ValueError):   # 32x16 with 80-channel groups: 512 * 20 = 10240 items
+        _lib.conv2d_groupnorm(x, h16(rs.randn(2560, 64, 1, 1) * 0.1), g, g, groups=32, producer_stats=2)
+    x = h16(rs.randn(1, 64, 32, 8))
+    g = np.ones(2688, np.float32)
+    with pytest.raises(ValueError):   # 32x8 with 84-channel groups: 256 * 21 = 5376 items, the first count past the bound at HW = 256
+        _lib.conv2d_groupnorm(x, h16(rs.randn(2688, 64, 1, 1) * 0.1), g, g, groups=32, producer_stats=2)
 
 
 STATS_CASES = [  # (B, Cin, HW, Cout, k, tile, entries expected)

@@ -4,8 +4,9 @@ integers, so with power-of-two scales the whole operator is exact and compared b
 float64 fake-quant reference whose integer part is the kernel's by construction.  Then the absmax observers, a calibrated handle
 against a fake-quantizing oracle, and the two CLI flags.
 
-Shapes: the eight geometries of tests/test_palettize_gpu.py (the forms of wstream_kernel: dead waves, a ragged last workgroup of
-slices, three K splits, a second source, the upsample gather, the 16-pixel-wide form, ragged and multi-block M of the 1x1 form)."""
+Shapes: the geometries of tests/test_palettize_gpu.py (the forms of wstream_kernel: dead waves, a ragged last workgroup of
+slices, three K splits, a second source, the upsample gather, the 16-pixel-wide form, ragged and multi-block M of the 1x1 form, and
+the H != W images 16x8, 24x8 at batch 3 and 8x16)."""
 import json
 import os
 import re
