@@ -90,11 +90,14 @@ int sd_weights_read_palette(const sd_weights* w, const char* name, void* lut, ui
  * sd_weights_quantize_w8a8 MARKS the conv weight `name` (SD_ERR_NOT_FOUND when absent): the store keeps q, s_w and act_absmax beside
  * the untouched values; *sq_err (may be NULL) = sum (w - q s_w)^2.  SD_ERR_INVALID_ARGUMENT: a tensor that is not (Cout, Cin, k, k),
  * a tensor that carries a palette (and sd_weights_palettize refuses a marked tensor), act_absmax not a positive finite number, a
- * non-finite weight.  A UNet handle built from the store runs a marked conv from int8 (wstream.hip, plan tile 17) exactly where
- * its plan would be the weight stream (plan tile 9); any other marked conv runs fp16 as before - the reference's skipped layers.
+ * non-finite weight.  A UNet handle built from the store runs a marked conv from int8 exactly where its plan would be the weight
+ * stream (plan tile 9 -> wstream.hip, plan tile 17) or the 3x3 / stride-1 halo conv with at most 14 784 input channels (plan tile 7
+ * -> conv3x3_halo_i8.hip, plan tile 18, with tile 7's ring and split-K) - the same function of its inputs in both; any other marked
+ * conv (1x1, stride 2, channel counts off the tiles) runs fp16 as before - the reference's skipped layers.
  * sd_weights_w8a8_info: 1 when `name` is marked (*act_scale, may be NULL, = s_a), else 0.
  * sd_weights_observe_activations(on): handles created from the store while it is on put an absmax observer in front of every conv
- * that plan tile 17 could take (sd_unet_activation_ranges) - calibration on the device. */
+ * that plan tile 17 could take (on = 1) or that plan tile 17 or 18 could take (on = 2) (sd_unet_activation_ranges) - calibration on
+ * the device.  0 = off; any other value is SD_ERR_INVALID_ARGUMENT. */
 int sd_weights_quantize_w8a8(sd_weights* w, const char* name, float act_absmax, double* sq_err);
 int sd_weights_w8a8_info(const sd_weights* w, const char* name, float* act_scale);
 int sd_weights_observe_activations(sd_weights* w, int on);
@@ -158,8 +161,9 @@ size_t sd_unet_arena_used_bytes(const sd_unet* u);
  * (q|k|v, attn2.to_q, the merged transformer tail, GEGLU projections on 256-row tiles) was uploaded as fp16 lut[indices]. */
 int sd_unet_palette_info(const sd_unet* u, int* n_palettized, int* n_streamed, size_t* stream_bytes);
 /* W8A8 (activation_quantization.py:141-203; sd_weights_quantize_w8a8): *n_marked tensors of the handle's weight store arrived with a
- * mark; *n_applied convolutions run from int8 (plan tile 17) and hold the int8 stream and one fp32 scale per output channel, no fp16
- * copy; *bytes = the bytes of those streams and scale vectors.  n_marked - n_applied marked convs stayed fp16. */
+ * mark; *n_applied convolutions run from int8 (plan tiles 17 and 18) and hold the int8 weights in their kernel's layout and one fp32
+ * scale per output channel, no fp16 copy; *bytes = the bytes of those weights and scale vectors.  n_marked - n_applied marked convs
+ * stayed fp16. */
 int sd_unet_w8a8_info(const sd_unet* u, int* n_marked, int* n_applied, size_t* bytes);
 /* Which convs those are: returns n_applied (>= 0) or an error code (< 0); index >= 0 fills `name` with the weight tensor of the
  * index-th of them in build order (SD_ERR_INVALID_ARGUMENT when there is no such conv), index < 0 asks for the count alone. */
@@ -387,7 +391,8 @@ int sd_op_conv2d(const void* x, const void* w, const float* bias, const void* re
  *   twin_groups   > 0: the slab combine also writes GroupNorm(twin_groups groups, twin_gamma / twin_beta (Cout) f32, twin_eps)
  *                 (+ SiLU with twin_silu) of the result to out_twin (B, Cout, Ho, Wo) f16 - no GroupNorm launch (the low-res
  *                 conv1 -> norm2 path); refused where the combine cannot hold whole (sample, group) slices
- *   plan_out[4]   the plan the launch ran: tile (1-4 igemm.hip, 7 conv3x3_halo.hip, 9 wstream.hip, 11 bvgemm.hip, 12 smgemm.hip),
+ *   plan_out[4]   the plan the launch ran: tile (1-4 igemm.hip, 7 conv3x3_halo.hip, 9 wstream.hip, 11 bvgemm.hip, 12 smgemm.hip; the
+ *                 entries of the compressed sources report theirs: 14 / 15 / 16 palettized, 17 / 18 W8A8),
  *                 staging, resolved split-K, 1 if the output left through fp32 slabs; all -1: the direct (non-MFMA) kernels
  * res / out are (B, Cout, Ho, Wo). */
 int sd_op_conv2d_ex(const void* x, const void* x1, const void* w, const float* bias, const float* temb, const void* res, void* out, int B,
@@ -420,6 +425,21 @@ int sd_op_conv2d_w8a8(const void* x, const void* x1, const int8_t* wq, const flo
  * [Cout / 32][Ctot / 32][k * k][64 lanes][16 B]: lane l of (strip, slice, tap) holds row strip * 32 + (l & 31), channels slice * 32 +
  * (l >> 5) * 16 + (0 .. 15).  *bytes = its size (Cout * Ctot * k * k); stream may be NULL to ask for the size alone. */
 int sd_op_w8a8_pack(const int8_t* wq, int Cout, int Ctot, int ksize, int8_t* stream, size_t* bytes);
+/* The 3x3 / stride-1 halo conv in W8A8 (plan tile 18, conv3x3_halo_i8.hip; semantics at sd_weights_quantize_w8a8 - the same function
+ * of its inputs as sd_op_conv2d_w8a8): wq (Cout, Cin + C1, 3, 3) int8, w_scale (Cout) f32, act_absmax the range of x (and x1); x1 / C1,
+ * bias, temb, res, upsample, iters, ms as sd_op_conv2d_ex; staging = plan tile 7's ring code (0 / 2 / 3: 2 / 3 / 4 weight stages; 4 / 5
+ * run the 4-stage ring), splitk = split-K over 64-channel chunks (0 = the library's rule for tile 7).
+ * plan_out = {18, ring code, resolved split-K, slab}.  Checked on the host in this order, before any device work, each
+ * SD_ERR_INVALID_ARGUMENT: NULL arguments; an empty problem; upsample / staging / splitk off their ranges; a shape the halo conv does not
+ * take (channel counts multiples of 64 in and 4 out, an image of at least 8 x 8 outputs); more than 14 784 input channels (the int32
+ * sums must stay exact: 127 * 127 * 9 * Ctot < 2^31); act_absmax not a positive finite number; a w_scale that is not; a weight of -128. */
+int sd_op_conv2d_w8a8_halo(const void* x, const void* x1, const int8_t* wq, const float* w_scale, float act_absmax, const float* bias,
+                           const float* temb, const void* res, void* out, int B, int Cin, int C1, int H, int W, int Cout, int upsample,
+                           int staging, int splitk, int* plan_out, int iters, float* ms);
+/* The int8 weights that entry and the UNet builder put on the device (host only): wq (Cout, Ctot, 3, 3) int8 -> packed (Cout, 9, Ctot),
+ * tap-major - the K order of the fp16 halo conv at one byte per weight, so a (row, tap, 64-channel chunk) is 64 contiguous bytes.
+ * Ctot a multiple of 64.  *bytes = its size (Cout * Ctot * 9); packed may be NULL to ask for the size alone. */
+int sd_op_w8a8_pack_halo(const int8_t* wq, int Cout, int Ctot, int8_t* packed, size_t* bytes);
 /* The host weight quantizer of sd_weights_quantize_w8a8 on its own: w (Cout, per_row) f32 -> q (Cout, per_row) int8, w_scale (Cout)
  * f32, *sq_err (may be NULL).  A non-finite weight is SD_ERR_INVALID_ARGUMENT. */
 int sd_op_quantize_weight(const float* w, int Cout, size_t per_row, int8_t* q, float* w_scale, double* sq_err);
@@ -575,14 +595,17 @@ int sd_op_sched_step(const float* noise_pred, float* latents, float* hist, const
  * palettized tiles 14 / 15 / 16 need a palette and are never an answer here: a handle takes 15 exactly where this says 12
  * (sd_op_gemm_palettized) and 16 where this says 13 with 128-row tiles (sd_op_geglu_palettized); tile = 17 asks for a W8A8
  * descriptor - the answer is 17 with the slab count of its wave code (staging 4: four waves, else eight), or SD_ERR_INVALID_ARGUMENT for
- * a shape the weight stream does not take; a handle takes 17 exactly where this says 9 and the tensor carries a W8A8 mark),
+ * a shape the weight stream does not take; a handle takes 17 exactly where this says 9 and the tensor carries a W8A8 mark; tile = 18
+ * asks for a W8A8 descriptor of the halo conv - the answer is 18 with tile 7's ring code, split-K and workspace for the same staging /
+ * splitk, or SD_ERR_INVALID_ARGUMENT naming plan tile 18 for a shape it does not take; a handle takes 18 exactly where this says 7
+ * without gnf_groups, Ctot <= 14 784 and the tensor carries a W8A8 mark),
  * staging, resolved split-K, slab (0 / 1), then the copies a handle must hold for this conv: wstream, wsgemm, bvgemm (0 / 1 each).
  * *workspace_bytes: the slab workspace this launch needs. */
 int sd_op_conv_plan(int ksize, int stride, int up, int C0, int C1, int N, int B, int Ho, int Wo, int out_mode, int flags, int n_trans,
                     int n_twins, int gnf_groups, int tile, int staging, int splitk, int copies, int* plan, unsigned long long* workspace_bytes);
 /* No reference counterpart.  The same question with the same 18 descriptor arguments, answered with the kernel that launches: one
  * NUL-terminated line in text[text_bytes] (64 bytes hold every answer) in the format of csrc/conv_plan.h conv_plan_kernel_name, e.g.
- * "igemm 64x64 ring4 kg2", "gemm_pipe 128x64 ring3", "halo_ks ring6", "wstream waves8", "bvgemm v3", "smgemm bm32", "generic":
+ * "igemm 64x64 ring4 kg2", "gemm_pipe 128x64 ring3", "halo_ks ring6", "halo_i8 ring4", "wstream waves8", "bvgemm v3", "smgemm bm32", "generic":
  * kernel family, tile, the ring depth that runs after the fall-back to one that fits the LDS, in-workgroup K groups, register
  * staging, wave count, variant - what the (tile, staging) codes of sd_op_conv_plan mean for this descriptor.  Host only. */
 int sd_op_conv_plan_kernel(int ksize, int stride, int up, int C0, int C1, int N, int B, int Ho, int Wo, int out_mode, int flags, int n_trans,

@@ -142,7 +142,8 @@ int sd_weights_w8a8_info(const sd_weights* w, const char* name, float* act_scale
 int sd_weights_observe_activations(sd_weights* w, int on) {
   return guarded([&] {
     SD_REQUIRE(w, kInvalidArgument, "NULL argument");
-    w->store.set_observe(on != 0);
+    SD_REQUIRE(on >= 0 && on <= 2, kInvalidArgument, "sd_weights_observe_activations: level %d (0 off, 1 weight-stream convs, 2 every W8A8-eligible conv)", on);
+    w->store.set_observe(on);
   });
 }
 void sd_weights_destroy(sd_weights* w) { delete w; }

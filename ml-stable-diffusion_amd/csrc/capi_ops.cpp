@@ -172,14 +172,14 @@ struct ConvOpExtra {
   void* out_twin = nullptr;
   int* plan_out = nullptr;       // {tile, staging, splitk, slab} of the plan that ran; -1: the direct kernels
   HostWeights cw;                // sd_op_conv2d_palettized / sd_op_conv2d_w8a8: the weights arrive compressed (w is NULL)
-  int nw = 0;                    // ... with this many waves per workgroup: 4, else 8
+  int nw = 0;                    // ... with this many waves per workgroup: 4, else 8 (sd_op_conv2d_w8a8_halo: tile 7's ring code)
 };
 
 // The compressed weights of a descriptor as the UNet builder uploads them (Net::upload_compressed) - the packed stream of the kind
 // with its LUT / scales - and the kind's pin by the caller's n (conv_plan_pin: waves per workgroup or tile height)
 void upload_compressed(Scratch& sc, ConvDesc& d, const char* what, const HostWeights& h, int n) {
   auto up = [&sc](const auto* host, size_t count) { return sc.dev(count, host); };
-  d.cw = h.kind == WeightSource::I8Wstream ? upload_w8a8(up, what, h.q, h.w_scale, h.act_absmax, d.N, concat_channels(d), d.ksize)
+  d.cw = h.q ? upload_w8a8(up, h.kind, what, h.q, h.w_scale, h.act_absmax, d.N, concat_channels(d), d.ksize)
                                            : upload_palettized(up, h.kind, what, f16(h.lut), h.bits, h.indices, d.N, concat_channels(d), d.ksize);
   const WeightPin pin = conv_plan_pin(h.kind, n);
   d.tile = pin.tile;
@@ -240,7 +240,8 @@ void conv2d_op(const void* x, const void* w, const float* bias, const void* res,
     SD_REQUIRE(fast && wstream_shape_ok(d), kInvalidArgument, "conv2d_palettized: shape not eligible for plan tile 14 (wstream.hip: k=%d C0=%d C1=%d N=%d %dx%d)",
                ksize, Cin, e.C1, Cout, Ho, Wo);
   // (W8A8: shape and values were checked on the host by the entry point)
-  if (e.cw.kind != WeightSource::Fp16) upload_compressed(sc, d, e.cw.kind == WeightSource::PalWstream ? "palettized conv" : "conv2d_w8a8", e.cw, e.nw);
+  if (e.cw.kind != WeightSource::Fp16)
+    upload_compressed(sc, d, e.cw.kind == WeightSource::PalWstream ? "palettized conv" : e.cw.kind == WeightSource::I8Halo ? "conv2d_w8a8_halo" : "conv2d_w8a8", e.cw, e.nw);
   half_t* dtwin = nullptr;
   if (e.twin_groups) {   // the GroupNorm as a twin of the conv's slab combine (sd_op_conv2d_groupnorm's producer_stats = 2)
     SD_REQUIRE(fast, kInvalidArgument, "conv2d: GroupNorm twins need the MFMA path");
@@ -513,6 +514,45 @@ int sd_op_conv2d_w8a8(const void* x, const void* x1, const int8_t* wq, const flo
     e.cw.kind = WeightSource::I8Wstream; e.cw.q = wq; e.cw.w_scale = w_scale; e.cw.act_absmax = act_absmax;
     e.nw = nw;
     conv2d_op(x, nullptr, bias, res, out, B, Cin, H, W, Cout, ksize, 1, upsample, 0, 0, 0, iters, ms, e);
+  });
+}
+
+// Every check runs on the host in front of the first device call (Scratch), in the order the header lists them.
+int sd_op_conv2d_w8a8_halo(const void* x, const void* x1, const int8_t* wq, const float* w_scale, float act_absmax, const float* bias, const float* temb,
+                           const void* res, void* out, int B, int Cin, int C1, int H, int W, int Cout, int upsample, int staging, int splitk, int* plan_out,
+                           int iters, float* ms) {
+  return guarded([&] {
+    SD_REQUIRE(x && wq && w_scale && out, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(B > 0 && Cin > 0 && C1 >= 0 && Cout > 0 && H > 0 && W > 0 && (C1 == 0 || x1), kInvalidArgument, "conv2d_w8a8_halo: empty problem");
+    SD_REQUIRE((upsample == 0 || upsample == 1) && staging >= 0 && staging <= 5 && staging != 1 && splitk >= 0, kInvalidArgument,
+               "conv2d_w8a8_halo: upsample %d staging %d (plan tile 7's ring codes 0, 2-5) splitk %d", upsample, staging, splitk);
+    ConvDesc d;   // the shape alone: what the planner's predicates look at
+    d.C0 = Cin;
+    if (C1 > 0) d.x1 = f16(x1), d.C1 = C1;
+    d.B = B; d.Hi = H; d.Wi = W; d.Ho = H * (upsample ? 2 : 1); d.Wo = W * (upsample ? 2 : 1);
+    d.ksize = 3; d.up = upsample ? 2 : 1; d.N = Cout;
+    SD_REQUIRE(conv_fast_path_ok(d) && halo_ks_ok(d), kInvalidArgument,
+               "conv2d_w8a8_halo: shape not eligible for plan tile 18 (conv3x3_halo_i8.hip: C0=%d C1=%d N=%d %dx%d)", Cin, C1, Cout, d.Ho, d.Wo);
+    SD_REQUIRE(Cin + C1 <= kHaloI8MaxCtot, kInvalidArgument, "conv2d_w8a8_halo: %d input channels, the exact int32 sums of plan tile 18 hold up to %d",
+               Cin + C1, kHaloI8MaxCtot);
+    // act_absmax, then w_scale, then the weight values (-128 is outside the symmetric range)
+    (void)w8a8_host_copy("conv2d_w8a8_halo", wq, w_scale, act_absmax, Cout, Cin + C1, 3, WeightSource::I8Halo);
+    ConvOpExtra e;
+    e.x1 = x1; e.C1 = C1;
+    e.temb = temb;
+    e.plan_out = plan_out;
+    e.cw.kind = WeightSource::I8Halo; e.cw.q = wq; e.cw.w_scale = w_scale; e.cw.act_absmax = act_absmax;
+    e.nw = staging;
+    conv2d_op(x, nullptr, bias, res, out, B, Cin, H, W, Cout, 3, 1, upsample, 0, splitk, 0, iters, ms, e);
+  });
+}
+
+int sd_op_w8a8_pack_halo(const int8_t* wq, int Cout, int Ctot, int8_t* packed, size_t* bytes) {
+  return guarded([&] {
+    SD_REQUIRE(wq && bytes, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(Cout > 0 && Ctot > 0 && Ctot % 64 == 0, kInvalidArgument, "w8a8_pack_halo: Cout %d Ctot %d", Cout, Ctot);
+    *bytes = (size_t)Cout * Ctot * 9;
+    if (packed) halo_i8_pack(wq, Cout, Ctot, 3, packed);
   });
 }
 
@@ -1241,6 +1281,12 @@ static ConvPlan query_conv_plan(int ksize, int stride, int up, int C0, int C1, i
   if (tile == 17) {   // a W8A8 descriptor carries its int8 stream and scales (the planner only tests the pointers)
     d.w = nullptr;
     d.cw.kind = WeightSource::I8Wstream;
+    d.cw.stream = d.cw.scale = present;
+    d.cw.inv_s = 1.f;
+  }
+  if (tile == 18) {   // ... and so does one of the int8 halo conv
+    d.w = nullptr;
+    d.cw.kind = WeightSource::I8Halo;
     d.cw.stream = d.cw.scale = present;
     d.cw.inv_s = 1.f;
   }

@@ -55,6 +55,11 @@ bool can_stream(const ConvDesc& d) { return d.w_tiled != nullptr && can_split(d)
 // else on.  Plan tiles 14 / 17: the palettized / int8 weight stream
 bool pal_stream(const ConvDesc& d) { return d.cw.kind == WeightSource::PalWstream; }
 bool i8_stream(const ConvDesc& d) { return d.cw.kind == WeightSource::I8Wstream; }
+// plan tile 18: the int8 halo conv - tile 7's shapes without the GroupNorm loader, inside the int32 bound
+bool i8_halo(const ConvDesc& d) { return d.cw.kind == WeightSource::I8Halo; }
+bool halo_i8_ok(const ConvDesc& d) {
+  return halo_ks_ok(d) && can_split(d) && !d.gnf_partial && !d.debug && d.C0 + (d.x1 ? d.C1 : 0) <= kHaloI8MaxCtot;
+}
 // plan tile 15: the small-M 1x1 GEMM;  plan tile 16: the GEGLU projection
 bool pal_gemm(const ConvDesc& d) { return d.cw.kind == WeightSource::PalGemm; }
 bool pal_geglu(const ConvDesc& d) { return d.cw.kind == WeightSource::PalGeglu; }
@@ -173,7 +178,9 @@ Plan choose_plan(const ConvDesc& d, const Dims& a) {
     while (split_ok && s < 16 && ksteps(c) / (s * 2) >= per_min) s *= 2;
     return s;
   };
-  const bool pinned = p.tile != 0 || p.splitk != 0 || p.staging != 0;   // the caller chose (operator-level A/B tests)
+  // the caller chose (operator-level A/B tests); an int8 halo conv is tile 7's plan whatever a table row or a tuner candidate says
+  const bool pinned = p.tile != 0 || p.splitk != 0 || p.staging != 0 || i8_halo(d);
+  if (i8_halo(d)) p.tile = 7;
   if (!pinned && g_tune.tile != 0 && tile_ok(g_tune.tile)) {
     p.tile = g_tune.tile;
     p.staging = g_tune.staging;
@@ -266,9 +273,14 @@ namespace {
 
 // the plan in the wire format: tile, code, resolved split-K, slab, workspace
 ConvPlan plan_codes(const ConvDesc& d) {
+  const CompressedWeights& cw = d.cw;
+  // (an int8 halo descriptor off the MFMA path has no direct kernel to fall to: refused like every other shape tile 18 does not take)
+  if (i8_halo(d))
+    SD_REQUIRE(conv_fast_path_ok(d) && cw.stream && cw.scale && halo_i8_ok(d), kInvalidArgument,
+               "plan tile 18 (conv3x3_halo_i8.hip, int8) needs the int8 weights, the scales and a 3x3 / stride-1 shape of the halo conv with "
+               "at most %d input channels (k=%d stride=%d up=%d C0=%d C1=%d N=%d)", kHaloI8MaxCtot, d.ksize, d.stride, d.up, d.C0, d.x1 ? d.C1 : 0, d.N);
   if (!conv_fast_path_ok(d)) return ConvPlan{-1, 0, 1, false, 0};
   // a compressed weight source, in front of the tuner candidate, the tables and every rule: nothing moves it
-  const CompressedWeights& cw = d.cw;
   switch (cw.kind) {
     case WeightSource::Fp16: break;
     case WeightSource::PalWstream:
@@ -280,6 +292,16 @@ ConvPlan plan_codes(const ConvDesc& d) {
       ConvPlan r{i8 ? 17 : 14, d.staging, 1, true, 0};
       r.splitk = wstream_splits(d, wstream_waves(d.staging));
       r.workspace_bytes = slab_bytes(dims_of(d), r.splitk, true);
+      return r;
+    }
+    case WeightSource::I8Halo: {   // tile 7's ring code, split-K rule and slab arithmetic (checked above)
+      const Dims a = dims_of(d);
+      const Plan p = choose_plan(d, a);
+      ConvPlan r{18, p.staging, 1, true, 0};
+      const int steps = a.Ctot / BK;
+      r.splitk = cdiv(steps, cdiv(steps, p.splitk));
+      r.slab = r.splitk > 1 || d.n_twins > 0;
+      r.workspace_bytes = slab_bytes(a, r.splitk, r.slab);
       return r;
     }
     case WeightSource::PalGemm:   // the code of tile 12 in, the resolved tile height out; no workspace
@@ -347,6 +369,7 @@ ConvPlan plan_codes(const ConvDesc& d) {
 //              runs as the deepest shallower one that does.  The LayerNorm fold has no register staging (1 as 0); the token-transposed
 //              output (kOutHalfT) has register staging and rings of 2 / 3 stages only.
 //   tile 7:    0 / 2 / 3 / 4 / 5 = 2 / 3 / 4 / 6 / 8 weight stages; GroupNorm in the loader: 4 stages from code 3 where its table fits, else 3
+//   tile 18:   tile 7's codes; the int8 kernel has rings of 2 / 3 / 4 stages, a deeper code runs the 4-stage one
 //   tiles 9 / 14 / 17: 4 = four waves per workgroup, anything else eight      tile 11: 1-6 = the variant, anything else the library's choice
 //   tiles 12 / 15 / 13 / 16: 1 / 2 = the lower / higher tile (32 / 64, 128 / 256 rows), 0 = by the shape
 void decode_plan(const ConvDesc& d, ConvPlan& p) {
@@ -372,6 +395,12 @@ void decode_plan(const ConvDesc& d, ConvPlan& p) {
       p.bm = code >= 0 && code <= 2 ? smgeglu_bm(d, code) : 0;
       return;
     default: break;
+  }
+  if (p.tile == 18) {
+    tile_dims(7, p.bm, p.bn);
+    p.kernel = ConvKernel::HaloI8;
+    p.stages = code >= 3 ? 4 : code == 2 ? 3 : 2;
+    return;
   }
   tile_dims(p.tile, p.bm, p.bn);
   if (p.tile == 7) {
@@ -429,6 +458,7 @@ std::string conv_plan_kernel_name(const ConvPlan& p) {
     case ConvKernel::Igemm: return "igemm " + tile + ring + (p.kgroups == 2 ? " kg2" : "") + (p.reg_staged ? " regs" : "");
     case ConvKernel::GemmPipe: return "gemm_pipe " + tile + ring;
     case ConvKernel::HaloKs: return "halo_ks" + ring;
+    case ConvKernel::HaloI8: return "halo_i8" + ring;
     case ConvKernel::Wstream: return "wstream waves" + std::to_string(p.waves);
     case ConvKernel::WstreamPal: return "wstream_pal waves" + std::to_string(p.waves);
     case ConvKernel::WstreamI8: return "wstream_i8 waves" + std::to_string(p.waves);
@@ -493,6 +523,7 @@ WeightPin conv_plan_pin(WeightSource kind, int n) {
   switch (kind) {
     case WeightSource::PalWstream: return {kind, 14, n == 4 ? 4 : 0};
     case WeightSource::I8Wstream: return {kind, 17, n == 4 ? 4 : 0};
+    case WeightSource::I8Halo: return {kind, 18, n};   // n: tile 7's ring code as it is
     case WeightSource::PalGemm: return {kind, 15, n == 32 ? 1 : n == 64 ? 2 : 0};
     case WeightSource::PalGeglu: return {kind, 16, n == 128 ? 1 : n == 256 ? 2 : 0};
     default: return {};
@@ -517,6 +548,14 @@ WeightPin conv_plan_weights(const ConvDesc& d, StoredWeights held, bool opt_in) 
   if (one_by_one && d.out_mode == kOutHalf && sw.smgemm && !d.ln_colsum) {   // tile 12
     const ConvPlan p = fp16_plan(d, conv_plan_copies(d));
     if (p.kernel == ConvKernel::Smgemm) return conv_plan_pin(WeightSource::PalGemm, p.bm);
+  }
+  if (held == StoredWeights::W8A8 && halo_i8_ok(d)) {   // tile 7 without the GroupNorm loader: its ring code and resolved split-K
+    const ConvPlan p = fp16_plan(d, conv_plan_copies(d));
+    if (p.kernel == ConvKernel::HaloKs) {
+      WeightPin pin = conv_plan_pin(WeightSource::I8Halo, p.staging);
+      pin.splitk = p.splitk;
+      return pin;
+    }
   }
   return {};
 }
@@ -568,6 +607,9 @@ void conv_plan_log(const ConvDesc& d, const ConvPlan& p, int n_fast) {
   else if (p.tile == 15 || p.tile == 16)
     fprintf(stderr, "[sd conv] k1 s1 up1 C0=%d C1=%d M=%d N=%d K=%d mode=%d tile=%d bm=%d n_fast=%d bits=%d\n", d.C0, c1, a.M, a.N, a.K, d.out_mode,
             p.tile, p.bm, n_fast, d.cw.bits);
+  else if (p.tile == 18)
+    fprintf(stderr, "[sd conv] k%d s%d up%d C0=%d C1=%d M=%d N=%d K=%d mode=%d tile=%d splitk=%d bits=8\n", d.ksize, d.stride, d.up, d.C0, c1, a.M, a.N,
+            a.K, d.out_mode, p.tile, p.splitk);
   else
     fprintf(stderr, "[sd conv] k%d s%d up%d C0=%d C1=%d M=%d N=%d K=%d mode=%d tile=%d splitk=%d\n", d.ksize, d.stride, d.up, d.C0, c1, a.M, a.N,
             a.K, d.out_mode, p.tile, p.splitk);

@@ -8,15 +8,16 @@
 
 namespace sd {
 
-// the kernel a plan launches (tile -1 / 1-4 / 7 / 9 / 14 / 17 / 10 / 11 / 12 / 15 / 13 / 16 of the wire format below)
-enum class ConvKernel { Generic, Igemm, GemmPipe, HaloKs, Wstream, WstreamPal, WstreamI8, Wsgemm, Bvgemm, Smgemm, SmgemmPal, Smgeglu, SmgegluPal };
+// the kernel a plan launches (tile -1 / 1-4 / 7 / 18 / 9 / 14 / 17 / 10 / 11 / 12 / 15 / 13 / 16 of the wire format below)
+enum class ConvKernel { Generic, Igemm, GemmPipe, HaloKs, HaloI8, Wstream, WstreamPal, WstreamI8, Wsgemm, Bvgemm, Smgemm, SmgemmPal, Smgeglu, SmgegluPal };
 
 struct ConvPlan {
   // The wire format: what ConvDesc::tile / staging pins, tuned_convs.inc rows, SD_PLAN_TABLE and sd_tune_set_candidate say and what
   // sd_op_conv_plan, plan_out and SD_LOG_CONVS report.  Read by decode_plan (conv_plan.cpp) and by nothing else.
   int tile;        // 1: 128x128, 2: 128x64, 3: 64x64, 4: 64x128 (igemm.hip), 7: the K-split halo conv (conv3x3_halo.hip), 9: wstream.hip,
                    // 10: wsgemm.hip, 11: bvgemm.hip, 12: smgemm.hip, 13: smgeglu.hip, 14: wstream.hip from palettized weights,
-                   // 15: smgemm.hip from palettized weights, 17: wstream.hip from int8 weights and activations (W8A8);
+                   // 15: smgemm.hip from palettized weights, 17: wstream.hip from int8 weights and activations (W8A8),
+                   // 18: the halo conv from int8 weights and activations (conv3x3_halo_i8.hip; never the library's own answer);
                    // -1 = not on the MFMA path (launch_conv_generic)
   int staging;     // per-family code: decode_plan
   int splitk;      // resolved: what the launch runs, no empty splits (halo: over 64-channel chunks; tile 9: the slab count)
@@ -24,8 +25,8 @@ struct ConvPlan {
   size_t workspace_bytes;   // exactly what this launch needs of ConvWorkspace::partial
   // What the codes mean for this descriptor, resolved once by conv_plan(): all a launcher reads.
   ConvKernel kernel = ConvKernel::Generic;
-  int bm = 0, bn = 0;        // Igemm / GemmPipe / HaloKs (128 x 64, as its tile counts): tile rows x columns; Smgemm* / Smgeglu: bm, tile rows
-  int stages = 0;            // Igemm / GemmPipe / HaloKs: the ring depth that runs, after the fall-back to one that fits the LDS
+  int bm = 0, bn = 0;        // Igemm / GemmPipe / HaloKs / HaloI8 (128 x 64, as its tile counts): tile rows x columns; Smgemm* / Smgeglu: bm, tile rows
+  int stages = 0;            // Igemm / GemmPipe / HaloKs / HaloI8: the ring depth that runs, after the fall-back to one that fits the LDS
   int kgroups = 1;           // Igemm: 2 = in-workgroup split-K, two K groups of four waves with a ring each
   bool reg_staged = false;   // Igemm: A / B travel HBM -> VGPR -> LDS (the A/B reference form), two stages
   int waves = 0;             // Wstream*: waves (K slices) per workgroup, 4 or 8
@@ -49,11 +50,13 @@ ConvWeightCopies conv_plan_copies(const ConvDesc& d);
 // the copies a handle would hold, is the kind's fp16 twin by the library's own rule, with the twin's wave count / tile height:
 //   Palette: opted-in GEGLU (tile 16 for tile 13 on the 128-row tiles the palettized kernel has), then the weight stream (tile 14 for
 //            tile 9), then the opted-in single-source small-M GEMM (tile 15 for tile 12)
-//   W8A8:    the weight stream (tile 17) by tile 14's predicate; an observing store asks this without holding a mark
+//   W8A8:    the weight stream (tile 17) by tile 14's predicate, then the halo conv (tile 18 for tile 7 without the GroupNorm loader,
+//            with that plan's ring code and split-K; Ctot <= kHaloI8MaxCtot); an observing store asks this without holding a mark
 enum class StoredWeights { Fp16, Palette, W8A8 };
 struct WeightPin {
   WeightSource kind = WeightSource::Fp16;
   int tile = 0, staging = 0;
+  int splitk = 0;   // I8Halo: the fp16 plan's resolved split-K (ConvDesc::splitk); 0 for the other kinds
 };
 WeightPin conv_plan_weights(const ConvDesc& d, StoredWeights held, bool opt_in);
 // The pin of a kind by the caller's own choice (the operator entry points): n = waves per workgroup (4, anything else eight) of the
@@ -64,7 +67,7 @@ WeightPin conv_plan_pin(WeightSource kind, int n);
 void conv_plan_log(const ConvDesc& d, const ConvPlan& p, int n_fast = 0);
 
 // What launches, as one line (sd_op_conv_plan_kernel): the kernel's name, then only the fields that kernel has -
-//   "igemm <bm>x<bn> ring<stages>[ kg2][ regs]"    "gemm_pipe <bm>x<bn> ring<stages>"    "halo_ks ring<stages>"
+//   "igemm <bm>x<bn> ring<stages>[ kg2][ regs]"    "gemm_pipe <bm>x<bn> ring<stages>"    "halo_ks ring<stages>"    "halo_i8 ring<stages>"
 //   "wstream waves<n>"   "wstream_pal waves<n>"    "wstream_i8 waves<n>"                 "wsgemm"    "bvgemm v<variant>"
 //   "smgemm bm<bm>"      "smgemm_pal bm<bm>"       "smgeglu bm<bm>"                      "generic"
 std::string conv_plan_kernel_name(const ConvPlan& p);
@@ -100,5 +103,15 @@ constexpr size_t halo_gnl_lds_bytes(int d, int ctot) {
   const size_t epilogue = 32 * 1024 + 128 * (64 + 8) * 2 + 64 * sizeof(float);
   return k_loop > epilogue ? k_loop : epilogue;
 }
+// conv3x3_halo_i8_kernel: one fp16 staging buffer of tile 7's halo rows, two int8 halo images (64 B per pixel, halo rows kHaloI8Pitch
+// pixels apart, kHaloI8Rows pixels with the rows the last DMA piece carries past the halo), d stages of 64 int8 weight rows, [2][64]
+// floats of epilogue constants
+constexpr int kHaloI8Pitch = 20, kHaloI8Rows = 204;
+constexpr size_t halo_i8_lds_bytes(int d) {
+  return (size_t)kHaloLdsRows * kConvBK * sizeof(half_t) + (size_t)2 * kHaloI8Rows * kConvBK + (size_t)d * 64 * kConvBK + 2 * 64 * sizeof(float);
+}
+// exact int32 sums: 127 * 127 * 9 * Ctot < 2^31
+constexpr int kHaloI8MaxCtot = 14784;
+static_assert(127LL * 127 * 9 * kHaloI8MaxCtot < (1LL << 31) && 127LL * 127 * 9 * (kHaloI8MaxCtot + 64) >= (1LL << 31), "int32 bound of plan tile 18");
 
 }  // namespace sd

@@ -36,7 +36,8 @@ struct GnTwin {
 //   PalGemm     tile 15, smgemm.hip   smgemm_pal_kernel          stream of smgemm_pal_pack    staging: tile 12's code (0 = by M)
 //   PalGeglu    tile 16, smgeglu.hip  smgeglu_pal_kernel         stream of smgeglu_pal_pack   staging: tile 13's code
 //   I8Wstream   tile 17, wstream.hip  wstream_kernel NBITS = kWsI8 (W8A8)   stream of wstream_i8_pack   staging: tile 9's code
-enum class WeightSource { Fp16, PalWstream, PalGemm, PalGeglu, I8Wstream };
+//   I8Halo      tile 18, conv3x3_halo_i8.hip  conv3x3_halo_i8_kernel (W8A8)   stream of halo_i8_pack      staging: tile 7's code
+enum class WeightSource { Fp16, PalWstream, PalGemm, PalGeglu, I8Wstream, I8Halo };
 struct CompressedWeights {
   WeightSource kind = WeightSource::Fp16;
   const void* stream = nullptr;
@@ -46,13 +47,13 @@ struct CompressedWeights {
   // PalGeglu with the LayerNorm fold (ConvDesc::ln_colsum set): the fp32 norm weight [C0] - the kernel multiplies every LUT value by it
   // as fold_layernorm_rows does on the host; null without the fold
   const float* ln_gamma = nullptr;
-  // I8Wstream: the output scale per column scale[n] = fp32(s_a * s_w[n]) and inv_s = fp32(1 / s_a), the factor the kernel quantizes
+  // I8Wstream / I8Halo: the output scale per column scale[n] = fp32(s_a * s_w[n]) and inv_s = fp32(1 / s_a), the factor the kernel quantizes
   // its activations by
   const float* scale = nullptr;
   float inv_s = 0.f;
   bool palettized() const { return kind == WeightSource::PalWstream || kind == WeightSource::PalGemm || kind == WeightSource::PalGeglu; }
   const uint8_t* pal() const { return palettized() ? static_cast<const uint8_t*>(stream) : nullptr; }
-  const int8_t* i8() const { return kind == WeightSource::I8Wstream ? static_cast<const int8_t*>(stream) : nullptr; }
+  const int8_t* i8() const { return kind == WeightSource::I8Wstream || kind == WeightSource::I8Halo ? static_cast<const int8_t*>(stream) : nullptr; }
 };
 
 struct ConvDesc {

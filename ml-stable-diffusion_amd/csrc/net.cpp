@@ -88,9 +88,12 @@ Tensor Net::conv(std::vector<Op>& ops, const std::string& name, const Tensor& x,
   const float* b = a.bias ? upload_vec(name + ".bias", a.cout, geglu) : nullptr;
   const WeightPin pin = weight_plan(name, x, a, false);
   // An observing store (calibration) puts an absmax op over the conv's source(s) in front of every conv the int8 weight stream could
-  // take: an ordinary member of the launch list that writes one slot nothing else reads.
-  if (ws_->observe() && !ws_->palette(name + ".weight") && !a.silu_out &&
-      conv_plan_weights(conv_shape(name, x, a), StoredWeights::W8A8, false).kind == WeightSource::I8Wstream) {
+  // take (level 1) or either int8 kernel could (level 2: the halo conv too): an ordinary member of the launch list that writes one slot
+  // nothing else reads.
+  const WeightSource could = ws_->observe() && !ws_->palette(name + ".weight") && !a.silu_out
+                                 ? conv_plan_weights(conv_shape(name, x, a), StoredWeights::W8A8, false).kind
+                                 : WeightSource::Fp16;
+  if (could == WeightSource::I8Wstream || (could == WeightSource::I8Halo && ws_->observe() >= 2)) {
     float* slot = ll_.arena.alloc_n<float>(1);   // (the arena is zeroed: the running maximum starts at 0)
     observed_.push_back({name + ".weight", slot});
     const half_t *p0 = x.p, *p1 = a.x2 ? a.x2->p : nullptr;
@@ -123,11 +126,11 @@ ConvWeights Net::upload_compressed(const std::string& name, const WeightPin& pin
   };
   size_t bytes = 0;
   CompressedWeights cw;
-  if (pin.kind == WeightSource::I8Wstream) {
+  if (pin.kind == WeightSource::I8Wstream || pin.kind == WeightSource::I8Halo) {   // q in the kernel's layout, cs[n], inv_s: no fp16 copy
     const W8A8Mark* i8 = ws_->w8a8(wname);
     SD_REQUIRE(i8 && ws_->get(wname).numel() == expect && i8->q.size() == expect && i8->w_scale.size() == (size_t)a.cout, kInvalidArgument,
                "%s: expected %zu W8A8 values (%d,%d,%d,%d)", wname.c_str(), expect, a.cout, cin, a.k, a.k);
-    cw = upload_w8a8(up, wname.c_str(), i8->q.data(), i8->w_scale.data(), i8->act_absmax, a.cout, cin, a.k, &bytes);
+    cw = upload_w8a8(up, pin.kind, wname.c_str(), i8->q.data(), i8->w_scale.data(), i8->act_absmax, a.cout, cin, a.k, &bytes);
     ++i8_applied_;
     i8_bytes_ += bytes;
     i8_names_.push_back(wname);
@@ -235,6 +238,7 @@ Tensor Net::conv_w(std::vector<Op>& ops, const std::string& name, const ConvWeig
   d.cw = weights.cw;   // a compressed source comes with its pin (all zero beside an fp16 matrix)
   d.tile = weights.pin.tile;
   d.staging = weights.pin.staging;
+  d.splitk = weights.pin.splitk;
   Tensor out;
   if (ln && a.n_trans > 0) {   // fused q|k|v: [M][n_trans] row-major + V^T [B][cout - n_trans][ldT]
     out = new_tensor(x.B, d.Ho, d.Wo, a.n_trans);
@@ -301,10 +305,10 @@ Tensor Net::conv_w(std::vector<Op>& ops, const std::string& name, const ConvWeig
   // trailing "#kind,ksize,stride,up,Ctot,N,M" is the plan-table key of this op (tools/tune_plans.py)
   const int kind = d.out_t ? 3 : (geglu ? 2 : (ln ? 1 : 0));
   // the weight source in the label: "[+ln]+pal<bits>" from a palette (plan tile 14 or 15), "geglu+pal<bits>[+ln]" for plan tile 16,
-  // "+w8a8" from int8 weights and quantized activations (plan tile 17)
+  // "+w8a8" from int8 weights and quantized activations (plan tiles 17 / 18)
   const WeightSource src = d.cw.kind;
   const std::string lnmark = ln ? "+ln" : "", palmark = "+pal" + std::to_string(d.cw.bits);
-  const std::string mark = src == WeightSource::PalGeglu ? palmark + lnmark : lnmark + (src == WeightSource::I8Wstream ? "+w8a8" : src != WeightSource::Fp16 ? palmark : "");
+  const std::string mark = src == WeightSource::PalGeglu ? palmark + lnmark : lnmark + (d.cw.i8() ? "+w8a8" : src != WeightSource::Fp16 ? palmark : "");
   snprintf(buf, sizeof(buf), "%s%s %d->%d @%dx%d M=%d K=%d %s #%d,%d,%d,%d,%d,%d,%d",
            k == 3 ? "conv3x3" : (geglu ? (src == WeightSource::PalGeglu ? "geglu" : "geglu1x1") : "gemm1x1"), mark.c_str(), cin, cout, d.Ho, d.Wo,
            x.B * d.Ho * d.Wo, cin * k * k, name.c_str(), kind, k, a.stride, a.up, cin, cout, x.B * d.Ho * d.Wo);

@@ -149,18 +149,22 @@ inline void wstream_i8_pack(const int8_t* q, int N, int Ctot, int ksize, int8_t*
           for (int e = 0; e < 16; ++e) out[e] = src[(size_t)e * taps];
         }
 }
-// What an upload of a W8A8 conv starts from (sd_op_conv2d_w8a8, Net::conv): no value of -128 (the symmetric scheme has none), finite
-// positive scales, the packed stream, cs[n] = fp32(s_a * s_w[n]) with s_a = act_absmax / 127, and inv_s = fp32(1 / s_a).
+// The int8 weights of conv3x3_halo_i8.hip (plan tile 18): [N][k * k][Ctot], the fp16 halo kernel's K order (retile_ohwi) at one byte
+// per weight - a (n, tap, 64-channel chunk) row is 64 contiguous bytes, what one DMA lane quartet fetches.  q [N][Ctot][k][k] (the
+// checkpoint's order); dst holds N * Ctot * k * k bytes.
+inline void halo_i8_pack(const int8_t* q, int N, int Ctot, int ksize, int8_t* dst) { retile_ohwi(q, N, Ctot, ksize, false, dst); }
+// What an upload of a W8A8 conv starts from (sd_op_conv2d_w8a8 / _halo, Net::conv), checked in the order the header lists: act_absmax, finite
+// positive scales, no value of -128 (the symmetric scheme has none); the packed stream, cs[n] = fp32(s_a * s_w[n]) with s_a = act_absmax / 127, and inv_s = fp32(1 / s_a).
 struct W8A8HostCopy {
   std::vector<int8_t> stream;
   std::vector<float> cs;
   float inv_s = 0.f;
 };
 inline bool w8a8_absmax_ok(float act_absmax) { return std::isfinite(act_absmax) && act_absmax > 0.f; }
-inline W8A8HostCopy w8a8_host_copy(const char* what, const int8_t* q, const float* w_scale, float act_absmax, int N, int Ctot, int ksize) {
+inline W8A8HostCopy w8a8_host_copy(const char* what, const int8_t* q, const float* w_scale, float act_absmax, int N, int Ctot, int ksize,
+                                   WeightSource kind = WeightSource::I8Wstream) {   // one of the two int8 kinds
   SD_REQUIRE(w8a8_absmax_ok(act_absmax), kInvalidArgument, "%s: act_absmax = %g, not a positive finite number", what, (double)act_absmax);
   const size_t n_el = wstream_i8_bytes(N, Ctot, ksize);
-  for (size_t i = 0; i < n_el; ++i) SD_REQUIRE(q[i] != -128, kInvalidArgument, "%s: weight value -128 at element %zu, the symmetric range is [-127, 127]", what, i);
   W8A8HostCopy h;
   const float s_a = act_absmax / 127.0f;
   h.inv_s = 1.0f / s_a;
@@ -170,8 +174,10 @@ inline W8A8HostCopy w8a8_host_copy(const char* what, const int8_t* q, const floa
     SD_REQUIRE(std::isfinite(w_scale[n]) && w_scale[n] > 0.f, kInvalidArgument, "%s: w_scale[%d] = %g, not a positive finite number", what, n, (double)w_scale[n]);
     h.cs[n] = s_a * w_scale[n];
   }
+  for (size_t i = 0; i < n_el; ++i) SD_REQUIRE(q[i] != -128, kInvalidArgument, "%s: weight value -128 at element %zu, the symmetric range is [-127, 127]", what, i);
   h.stream.resize(n_el);
-  wstream_i8_pack(q, N, Ctot, ksize, h.stream.data());
+  if (kind == WeightSource::I8Halo) halo_i8_pack(q, N, Ctot, ksize, h.stream.data());
+  else wstream_i8_pack(q, N, Ctot, ksize, h.stream.data());
   return h;
 }
 
@@ -259,11 +265,11 @@ CompressedWeights upload_palettized(Up&& up, WeightSource kind, const char* what
   return c;
 }
 template <class Up>
-CompressedWeights upload_w8a8(Up&& up, const char* what, const int8_t* q, const float* w_scale, float act_absmax, int N, int Ctot, int ksize,
-                              size_t* bytes = nullptr) {
-  const W8A8HostCopy h = w8a8_host_copy(what, q, w_scale, act_absmax, N, Ctot, ksize);
+CompressedWeights upload_w8a8(Up&& up, WeightSource kind, const char* what, const int8_t* q, const float* w_scale, float act_absmax, int N, int Ctot,
+                              int ksize, size_t* bytes = nullptr) {
+  const W8A8HostCopy h = w8a8_host_copy(what, q, w_scale, act_absmax, N, Ctot, ksize, kind);
   CompressedWeights c;
-  c.kind = WeightSource::I8Wstream;
+  c.kind = kind;
   c.stream = up(h.stream.data(), h.stream.size());
   c.scale = up(h.cs.data(), h.cs.size());
   c.inv_s = h.inv_s;

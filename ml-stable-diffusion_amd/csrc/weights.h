@@ -43,8 +43,8 @@ class WeightStore {
   const W8A8Mark* w8a8(const std::string& name) const;   // nullptr: no mark
   size_t w8a8_marks() const { return i8_.size(); }
   // handles built from this store put an absmax observer in front of every conv plan tile 17 could take
-  void set_observe(bool on) { observe_ = on; }
-  bool observe() const { return observe_; }
+  void set_observe(int level) { observe_ = level; }   // 0 off, 1 the convs plan tile 17 could take, 2 also those of plan tile 18
+  int observe() const { return observe_; }
   void add(const std::string& name, const void* data, int dtype /*0 f16, 1 f32, 2 bf16*/,
            const int64_t* shape, int ndim);
   void load_safetensors(const std::string& path, const std::string& prefix);
@@ -64,7 +64,7 @@ class WeightStore {
   std::map<std::string, HostTensor> map_;
   std::map<std::string, Palette> pal_;
   std::map<std::string, W8A8Mark> i8_;
-  bool observe_ = false;
+  int observe_ = 0;
 };
 
 }  // namespace sd

@@ -38,6 +38,7 @@
 //                         of the concatenated operand.  The separate GroupNorm launch and its round trip disappear.
 #include "kernels.h"
 #include "pal_decode.h"
+#include "quantize8.h"   // ws_quantize8: the activation quantizer shared with conv3x3_halo_i8.hip
 
 #include <cmath>
 #include <type_traits>
@@ -227,11 +228,8 @@ struct WsArgs {
 
 constexpr int WS_REGION = 16384;   // per-wave LDS: the 32-channel halo slice (<= 200 pixels x 80 B), later its 128 x 32 fp32 tile
 constexpr int WS_ROWB = 80;        // 64 B of channels + 16 B pad: the 16 lanes of a ds_read_b128 group hit distinct banks
-typedef unsigned uintx2 __attribute__((ext_vector_type(2)));
 constexpr int ws_region(int nbits) { return WS_REGION + (nbits > 0 ? kPalLutHalves * 2 : 0); }   // palettized: + the wave's copy of the LUT
 constexpr int kWsI8 = -8;          // NBITS of the int8 source
-typedef int intx4 __attribute__((ext_vector_type(4)));
-typedef int intx16 __attribute__((ext_vector_type(16)));
 
 // The int8 source's LDS image of a wave's halo slice: 32 B (32 int8 channels) per pixel, NO per-pixel pad, halo rows PITCH pixels
 // apart, and the two 16-B halves of a pixel swapped where bit `g` of the pixel is set.  By the LDS bank rules (256-B bank row = 16
@@ -254,19 +252,6 @@ struct WsI8Image {
   static __device__ __forceinline__ int at1(int ml, int half) { return ml * 32 + ((half ^ (ml >> 4)) & 1) * 16; }
 };
 static_assert(2 * WsI8Image<9, 8>::SUB * 32 <= WS_REGION && WsI8Image<9, 16>::SUB * 32 <= WS_REGION, "int8 halo image larger than a wave's region");
-
-// x_q = clip(rint(fp32(x) * inv_s), -127, 127): one product, v_rndne_f32, a clamp.  NaN -> 0 (it compares false with everything, the
-// select keeps 0); +-inf -> +-127 (the clamp saturates them like any large value).  Eight channels -> 8 bytes.
-__device__ __forceinline__ uintx2 ws_quantize8(const half8& x, float inv_s) {
-  unsigned b[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const float v = __builtin_rintf((float)x[e] * inv_s);
-    const float c = v == v ? fminf(fmaxf(v, -127.f), 127.f) : 0.f;
-    b[e] = (unsigned)(int)c & 0xffu;
-  }
-  return uintx2{b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24), b[4] | (b[5] << 8) | (b[6] << 16) | (b[7] << 24)};
-}
 
 // NW waves; TAPS 9 (3x3, stride 1, pad 1) or 1 (1x1); WW = image width of the 3x3 form (8: a 128-pixel block is two 8-row
 // sub-tiles, 16: one), ignored for TAPS == 1; NBITS = 0: fp16 weights (a.wt), > 0: the index width of palettized ones (a.pal, a.lut),

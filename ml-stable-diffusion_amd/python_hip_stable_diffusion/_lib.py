@@ -105,6 +105,8 @@ SYMBOLS = [
     ("sd_unet_activation_ranges", _I, [_P, _I, C.c_char_p, _I, _FP]),
     ("sd_op_conv2d_w8a8", _I, [_P, _P, _P, _FP, _F, _FP, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_I), _I, _FP]),
     ("sd_op_w8a8_pack", _I, [_P, _I, _I, _I, _P, C.POINTER(C.c_size_t)]),
+    ("sd_op_conv2d_w8a8_halo", _I, [_P, _P, _P, _FP, _F, _FP, _FP, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_I), _I, _FP]),
+    ("sd_op_w8a8_pack_halo", _I, [_P, _I, _I, _P, C.POINTER(C.c_size_t)]),
     ("sd_op_quantize_weight", _I, [_FP, _I, C.c_size_t, _P, _FP, C.POINTER(C.c_double)]),
     ("sd_op_absmax", _I, [_P, C.c_size_t, _FP]),
     ("sd_unet_create", _I, [C.POINTER(UNetConfig), _P, _I, C.POINTER(_P)]),
@@ -537,6 +539,52 @@ def conv2d_w8a8(x, wq, w_scale, act_absmax, bias=None, res=None, x1=None, upsamp
     check(lib().sd_op_conv2d_w8a8(ptr(x), ptr(x1), ptr(wq), fptr(w_scale), float(act_absmax), fptr(bias), ptr(res), ptr(out), B, Cin, C1,
                                   H, W, Cout, k, int(upsample), nw, plan, iters, C.byref(ms)))
     return out.reshape(-1)[:n].reshape(B, Cout, Ho, Wo), list(plan), ms.value
+
+
+def conv2d_w8a8_halo(x, wq, w_scale, act_absmax, bias=None, temb=None, res=None, x1=None, upsample=False, staging=3, splitk=0, out=None,
+                     iters=1):
+    """The 3x3 / stride-1 halo conv in W8A8 (sd_op_conv2d_w8a8_halo, plan tile 18): wq (Cout, Cin + C1, 3, 3) int8, w_scale (Cout,) f32,
+    act_absmax the range of x (and x1); temb (B, Cout) f32; staging = plan tile 7's ring code (0 / 2 / 3 = 2 / 3 / 4 stages), splitk 0 =
+    the library's rule.  Returns (out (B, Cout, Ho, Wo), plan, ms)."""
+    x = f16(x)
+    wq = np.ascontiguousarray(wq, dtype=np.int8)
+    w_scale = f32(w_scale)
+    x1 = None if x1 is None else f16(x1)
+    B, Cin, H, W = x.shape
+    C1 = 0 if x1 is None else x1.shape[1]
+    if wq.ndim != 4 or wq.shape[2:] != (3, 3):
+        raise ValueError("conv2d_w8a8_halo: wq must be (Cout, Cin + C1, 3, 3)")
+    Cout, Ctot = wq.shape[:2]
+    if Ctot != Cin + C1 or (x1 is not None and x1.shape != (B, C1, H, W)) or w_scale.shape != (Cout,):
+        raise ValueError("conv2d_w8a8_halo: wq / w_scale / second source shape does not match input")
+    up = 2 if upsample else 1
+    Ho, Wo = H * up, W * up
+    bias = None if bias is None else f32(bias)
+    temb = None if temb is None else f32(temb)
+    res = None if res is None else f16(res)
+    if res is not None and res.shape != (B, Cout, Ho, Wo):
+        raise ValueError("conv2d_w8a8_halo: res must be (B, Cout, Ho, Wo)")
+    if temb is not None and temb.shape != (B, Cout):
+        raise ValueError("conv2d_w8a8_halo: temb must be (B, Cout)")
+    n = B * Cout * Ho * Wo
+    if out is None:
+        out = np.empty(n, np.float16)
+    if out.dtype != np.float16 or not out.flags.c_contiguous or out.size < n:
+        raise ValueError("conv2d_w8a8_halo: out must be a C-contiguous float16 buffer of at least B * Cout * Ho * Wo elements")
+    plan = (C.c_int * 4)()
+    ms = C.c_float(0)
+    check(lib().sd_op_conv2d_w8a8_halo(ptr(x), ptr(x1), ptr(wq), fptr(w_scale), float(act_absmax), fptr(bias), fptr(temb), ptr(res), ptr(out),
+                                       B, Cin, C1, H, W, Cout, int(upsample), staging, splitk, plan, iters, C.byref(ms)))
+    return out.reshape(-1)[:n].reshape(B, Cout, Ho, Wo), list(plan), ms.value
+
+
+def w8a8_pack_halo(wq):
+    """The int8 weights of the W8A8 halo conv (sd_op_w8a8_pack_halo; host only): wq (Cout, Ctot, 3, 3) int8 -> int8 (Cout, 9, Ctot)."""
+    wq = np.ascontiguousarray(wq, dtype=np.int8)
+    if wq.ndim != 4 or wq.shape[2:] != (3, 3):
+        raise ValueError("w8a8_pack_halo: wq must be (Cout, Ctot, 3, 3)")
+    Cout, Ctot = wq.shape[:2]
+    return _packed(lib().sd_op_w8a8_pack_halo, ptr(wq), Cout, Ctot).view(np.int8).reshape(Cout, 9, Ctot)
 
 
 def w8a8_pack(wq):

@@ -197,8 +197,9 @@ class Weights(_lib.Handle):
         return float(s.value) if _lib.lib().sd_weights_w8a8_info(self._h, name.encode(), C.byref(s)) else None
 
     def observe_activations(self, on=True):
-        """Handles created from the store while this is on carry the activation observers (calibration)."""
-        _lib.check(_lib.lib().sd_weights_observe_activations(self._h, int(bool(on))))
+        """Handles created from the store while this is on carry the activation observers (calibration): ``True`` in front of the
+        convs the int8 weight stream could take (plan tile 17), ``"all"`` in front of those of the int8 halo conv (plan tile 18) too."""
+        _lib.check(_lib.lib().sd_weights_observe_activations(self._h, observe_level(on)))
 
     @classmethod
     @contextlib.contextmanager
@@ -213,6 +214,15 @@ class Weights(_lib.Handle):
             yield store
         finally:
             store.close()
+
+
+def observe_level(on):
+    """observe_activations as the level of sd_weights_observe_activations: False 0, True 1, "all" 2."""
+    if isinstance(on, str):
+        if on != "all":
+            raise ValueError(f"observe_activations must be False, True or 'all', got {on!r}")
+        return 2
+    return int(bool(on))
 
 
 class HipModel(_lib.Model):
@@ -285,7 +295,7 @@ class HipModel(_lib.Model):
                 self.activation_quantization = aq.load_recipe(activation_quantization)
                 aq.apply(store, self.activation_quantization)
             if observe_activations:
-                store.observe_activations(True)
+                store.observe_activations(observe_activations)
             try:
                 _lib.check(_lib.lib().sd_unet_create(C.byref(c), store._h, device, C.byref(self._h)))
             finally:
@@ -294,9 +304,9 @@ class HipModel(_lib.Model):
         if self.activation_quantization is not None:
             applied = set(self.w8a8_layers())
             stayed = sorted(set(self.activation_quantization) - applied)
-            logger.info("W8A8: %d of %d recipe layers run from int8 (plan tile 17)", len(applied), len(self.activation_quantization))
+            logger.info("W8A8: %d of %d recipe layers run from int8 (plan tiles 17 / 18)", len(applied), len(self.activation_quantization))
             if stayed:
-                logger.info("W8A8: these layers stay fp16 (their plan is not the weight stream): %s", ", ".join(stayed))
+                logger.info("W8A8: these layers stay fp16 (their plan is neither the weight stream nor the halo conv): %s", ", ".join(stayed))
         self.batch, self.latent_height, self.latent_width = batch, h, w
         self.attention_implementation = attention_implementation
         self.num_residuals = _lib.lib().sd_unet_num_residuals(self._h)

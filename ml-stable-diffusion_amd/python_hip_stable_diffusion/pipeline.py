@@ -807,10 +807,13 @@ def build_parser():
                         help="The string key into --pre-analysis-json-path's dict that picks the recipe to apply")
     parser.add_argument("--activation-quantization-recipe", default=None,                        # activation_quantization.py --quantize-pytorch
                         help="A W8A8 recipe (JSON {layer: act_absmax}, written by --calibrate-activations): the UNet convs it names run "
-                             "from int8 weights and activations where their kernel is the weight stream")
+                             "from int8 weights and activations where their kernel is the weight stream or the 3x3 halo conv")
     parser.add_argument("--calibrate-activations", default=None,                                 # activation_quantization.py --generate-calibration-data
                         help="Run the requested generation on a UNet that records the range of every quantizable conv's input and write "
                              "the W8A8 recipe to this file")
+    parser.add_argument("--calibrate-scope", default="stream", choices=("stream", "all"),
+                        help="Which convs --calibrate-activations observes: 'stream' = those the int8 weight stream takes (the 8x8 level), "
+                             "'all' = also every 3x3 / stride-1 conv the int8 halo conv takes")
     return parser
 
 
@@ -840,7 +843,7 @@ def main(args):
                         disable_safety=getattr(args, "disable_safety", False), vae_encoder=bool(getattr(args, "image", None)),
                         quantize_nbits=getattr(args, "quantize_nbits", None), palettization_recipe=recipe,
                         device_postprocess=getattr(args, "device_postprocess", False), activation_quantization=aq_recipe,
-                        observe_activations=bool(calibrate))
+                        observe_activations=("all" if getattr(args, "calibrate_scope", "stream") == "all" else True) if calibrate else False)
     controlnet_cond = None
     if args.controlnet:
         controlnet_cond = [prepare_controlnet_cond(args.controlnet_inputs[i], pipe.height, pipe.width)
