@@ -92,15 +92,21 @@ int sd_weights_read_palette(const sd_weights* w, const char* name, void* lut, ui
  * a tensor that carries a palette (and sd_weights_palettize refuses a marked tensor), act_absmax not a positive finite number, a
  * non-finite weight.  A UNet handle built from the store runs a marked conv from int8 exactly where its plan would be the weight
  * stream (plan tile 9 -> wstream.hip, plan tile 17) or the 3x3 / stride-1 halo conv with at most 14 784 input channels (plan tile 7
- * -> conv3x3_halo_i8.hip, plan tile 18, with tile 7's ring and split-K) - the same function of its inputs in both; any other marked
- * conv (1x1, stride 2, channel counts off the tiles) runs fp16 as before - the reference's skipped layers.
+ * -> conv3x3_halo_i8.hip, plan tile 18, with tile 7's ring and split-K) or, at a call site that consents to a pinned 1x1 kernel
+ * (proj_in, attn1.to_out.0, attn2.to_out.0), the single-source small-M 1x1 GEMM (plan tile 12 -> smgemm_i8.hip, plan tile 19, with
+ * tile 12's tile height) - the same function of its inputs in all three; any other marked conv (LayerNorm-folded or two-source 1x1,
+ * GEGLU, stride 2, channel counts off the tiles) runs fp16 as before - the reference's skipped layers.
  * sd_weights_w8a8_info: 1 when `name` is marked (*act_scale, may be NULL, = s_a), else 0.
  * sd_weights_observe_activations(on): handles created from the store while it is on put an absmax observer in front of every conv
  * that plan tile 17 could take (on = 1) or that plan tile 17 or 18 could take (on = 2) (sd_unet_activation_ranges) - calibration on
- * the device.  0 = off; any other value is SD_ERR_INVALID_ARGUMENT. */
+ * the device.  0 = off; any other value is SD_ERR_INVALID_ARGUMENT.
+ * sd_weights_observe_gemms(on): a flag beside that level - while the store observes (on = 1 or 2 above), handles created from it also
+ * put an observer in front of every 1x1 projection plan tile 19 could take.  on = 0 / 1; any other value is SD_ERR_INVALID_ARGUMENT.
+ * With the flag off the observer sets are those of the two levels above. */
 int sd_weights_quantize_w8a8(sd_weights* w, const char* name, float act_absmax, double* sq_err);
 int sd_weights_w8a8_info(const sd_weights* w, const char* name, float* act_scale);
 int sd_weights_observe_activations(sd_weights* w, int on);
+int sd_weights_observe_gemms(sd_weights* w, int on);
 
 /* ------------------------------------------------------------------------------------------
  * UNet / ControlNet.  Config mirrors UNet2DConditionModel.__init__ (unet.py:801-833) with the
@@ -161,7 +167,7 @@ size_t sd_unet_arena_used_bytes(const sd_unet* u);
  * (q|k|v, attn2.to_q, the merged transformer tail, GEGLU projections on 256-row tiles) was uploaded as fp16 lut[indices]. */
 int sd_unet_palette_info(const sd_unet* u, int* n_palettized, int* n_streamed, size_t* stream_bytes);
 /* W8A8 (activation_quantization.py:141-203; sd_weights_quantize_w8a8): *n_marked tensors of the handle's weight store arrived with a
- * mark; *n_applied convolutions run from int8 (plan tiles 17 and 18) and hold the int8 weights in their kernel's layout and one fp32
+ * mark; *n_applied convolutions run from int8 (plan tiles 17, 18 and 19) and hold the int8 weights in their kernel's layout and one fp32
  * scale per output channel, no fp16 copy; *bytes = the bytes of those weights and scale vectors.  n_marked - n_applied marked convs
  * stayed fp16. */
 int sd_unet_w8a8_info(const sd_unet* u, int* n_marked, int* n_applied, size_t* bytes);
@@ -392,7 +398,7 @@ int sd_op_conv2d(const void* x, const void* w, const float* bias, const void* re
  *                 (+ SiLU with twin_silu) of the result to out_twin (B, Cout, Ho, Wo) f16 - no GroupNorm launch (the low-res
  *                 conv1 -> norm2 path); refused where the combine cannot hold whole (sample, group) slices
  *   plan_out[4]   the plan the launch ran: tile (1-4 igemm.hip, 7 conv3x3_halo.hip, 9 wstream.hip, 11 bvgemm.hip, 12 smgemm.hip; the
- *                 entries of the compressed sources report theirs: 14 / 15 / 16 palettized, 17 / 18 W8A8),
+ *                 entries of the compressed sources report theirs: 14 / 15 / 16 palettized, 17 / 18 / 19 W8A8),
  *                 staging, resolved split-K, 1 if the output left through fp32 slabs; all -1: the direct (non-MFMA) kernels
  * res / out are (B, Cout, Ho, Wo). */
 int sd_op_conv2d_ex(const void* x, const void* x1, const void* w, const float* bias, const float* temb, const void* res, void* out, int B,
@@ -440,6 +446,22 @@ int sd_op_conv2d_w8a8_halo(const void* x, const void* x1, const int8_t* wq, cons
  * tap-major - the K order of the fp16 halo conv at one byte per weight, so a (row, tap, 64-channel chunk) is 64 contiguous bytes.
  * Ctot a multiple of 64.  *bytes = its size (Cout * Ctot * 9); packed may be NULL to ask for the size alone. */
 int sd_op_w8a8_pack_halo(const int8_t* wq, int Cout, int Ctot, int8_t* packed, size_t* bytes);
+/* No reference counterpart as an operator; the layer it stands for is any Linear the reference's UNet writes as a 1x1 conv (unet.py:533-551
+ * proj_in, :62-118 to_out) under quantize_cumulative_config (activation_quantization.py:141-203).  The single-source small-M 1x1 GEMM in
+ * W8A8 (plan tile 19, smgemm_i8.hip; semantics at sd_weights_quantize_w8a8 - the same function of its inputs as sd_op_conv2d_w8a8:
+ * out = fp16(((float(int32 sum) * (act_absmax / 127 * w_scale[n])) + bias[n]) + res), one rounding): x (B, Cin, H, W) f16, wq (Cout, Cin)
+ * int8, w_scale (Cout) f32, act_absmax the range of x; bias (Cout) f32 / res (B, Cout, H, W) f16 may be NULL; bm = tile height 32 / 64,
+ * 0 = by M as plan tile 12; iters, ms as sd_op_conv2d_ex.  plan_out = {19, 1 | 2 (bm 32 | 64), 1, 0}.  Checked on the host in this order,
+ * before any device work, each SD_ERR_INVALID_ARGUMENT: bm not 0 / 32 / 64; NULL arguments or an empty problem; a shape plan tile 12 does
+ * not tile (Cin a multiple of 64, Cout of 80, M = B H W of the tile height, at least 2 x 2 tiles and a multiple of 8 of them), then
+ * Cin > 133120 (the int32 sums must stay exact: 127 * 127 * K < 2^31); act_absmax not a positive finite number; a w_scale that is not; a
+ * weight of -128. */
+int sd_op_gemm_w8a8(const void* x, const int8_t* wq, const float* w_scale, float act_absmax, const float* bias, const void* res, void* out, int B,
+                    int Cin, int H, int W, int Cout, int bm, int* plan_out, int iters, float* ms);
+/* The int8 weights that entry and the UNet builder put on the device (host only): wq (Cout, K) int8 -> packed (Cout, K) - the
+ * checkpoint's own order: a wave fetches 16 rows x 64 contiguous bytes per K stage and swizzles on the source address.  Cout a multiple
+ * of 16, K of 64.  *bytes = its size (Cout * K); packed may be NULL to ask for the size alone. */
+int sd_op_w8a8_pack_gemm(const int8_t* wq, int Cout, int K, int8_t* packed, size_t* bytes);
 /* The host weight quantizer of sd_weights_quantize_w8a8 on its own: w (Cout, per_row) f32 -> q (Cout, per_row) int8, w_scale (Cout)
  * f32, *sq_err (may be NULL).  A non-finite weight is SD_ERR_INVALID_ARGUMENT. */
 int sd_op_quantize_weight(const float* w, int Cout, size_t per_row, int8_t* q, float* w_scale, double* sq_err);
@@ -598,14 +620,17 @@ int sd_op_sched_step(const float* noise_pred, float* latents, float* hist, const
  * a shape the weight stream does not take; a handle takes 17 exactly where this says 9 and the tensor carries a W8A8 mark; tile = 18
  * asks for a W8A8 descriptor of the halo conv - the answer is 18 with tile 7's ring code, split-K and workspace for the same staging /
  * splitk, or SD_ERR_INVALID_ARGUMENT naming plan tile 18 for a shape it does not take; a handle takes 18 exactly where this says 7
- * without gnf_groups, Ctot <= 14 784 and the tensor carries a W8A8 mark),
+ * without gnf_groups, Ctot <= 14 784 and the tensor carries a W8A8 mark; tile = 19 asks for a W8A8 descriptor of the small-M 1x1 GEMM -
+ * the answer is 19 with the resolved tile height of the same staging (1 / 2 = 32 / 64 rows), split-K 1, no slab, no workspace, or
+ * SD_ERR_INVALID_ARGUMENT naming plan tile 19 for a shape it does not take; a handle takes 19 exactly where this says 12 for a
+ * single-source plain projection at a consenting call site and the tensor carries a W8A8 mark),
  * staging, resolved split-K, slab (0 / 1), then the copies a handle must hold for this conv: wstream, wsgemm, bvgemm (0 / 1 each).
  * *workspace_bytes: the slab workspace this launch needs. */
 int sd_op_conv_plan(int ksize, int stride, int up, int C0, int C1, int N, int B, int Ho, int Wo, int out_mode, int flags, int n_trans,
                     int n_twins, int gnf_groups, int tile, int staging, int splitk, int copies, int* plan, unsigned long long* workspace_bytes);
 /* No reference counterpart.  The same question with the same 18 descriptor arguments, answered with the kernel that launches: one
  * NUL-terminated line in text[text_bytes] (64 bytes hold every answer) in the format of csrc/conv_plan.h conv_plan_kernel_name, e.g.
- * "igemm 64x64 ring4 kg2", "gemm_pipe 128x64 ring3", "halo_ks ring6", "halo_i8 ring4", "wstream waves8", "bvgemm v3", "smgemm bm32", "generic":
+ * "igemm 64x64 ring4 kg2", "gemm_pipe 128x64 ring3", "halo_ks ring6", "halo_i8 ring4", "wstream waves8", "bvgemm v3", "smgemm bm32", "smgemm_i8 bm32", "generic":
  * kernel family, tile, the ring depth that runs after the fall-back to one that fits the LDS, in-workgroup K groups, register
  * staging, wave count, variant - what the (tile, staging) codes of sd_op_conv_plan mean for this descriptor.  Host only. */
 int sd_op_conv_plan_kernel(int ksize, int stride, int up, int C0, int C1, int N, int B, int Ho, int Wo, int out_mode, int flags, int n_trans,
@@ -630,7 +655,8 @@ int sd_philox_randn(uint64_t seed, uint32_t offset, double* out, size_t n);
  * on the slow ones: the figure `value_normalised` is built on.  Nine floats.  Allocates and frees 2 GiB of device memory; synchronous. */
 int sd_calibrate(int device, float* out9);
 /* MFMA fragment layout self-check used by the build/smoke tests (returns 0 when the hardware
- * layout matches what the kernels assume; bit 0 the f16 MFMA, bits 1 / 2 the cross-lane exchanges, bit 3 the int8 MFMA of W8A8). */
+ * layout matches what the kernels assume; bit 0 the f16 MFMA, bits 1 / 2 the cross-lane exchanges, bit 3 the 32x32x32 int8 MFMA of the W8A8
+ * convs, bit 4 the 16x16x64 int8 MFMA of the W8A8 small-M GEMM). */
 int sd_selftest_mfma(void);
 
 /* ------------------------------------------------------------------------------------------

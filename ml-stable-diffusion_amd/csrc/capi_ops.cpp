@@ -556,6 +556,50 @@ int sd_op_w8a8_pack_halo(const int8_t* wq, int Cout, int Ctot, int8_t* packed, s
   });
 }
 
+// Every check runs on the host in front of the first device call (Scratch), in the order the header lists them.
+int sd_op_gemm_w8a8(const void* x, const int8_t* wq, const float* w_scale, float act_absmax, const float* bias, const void* res, void* out, int B,
+                    int Cin, int H, int W, int Cout, int bm, int* plan_out, int iters, float* ms) {
+  return guarded([&] {
+    SD_REQUIRE(bm == 0 || bm == 32 || bm == 64, kInvalidArgument, "gemm_w8a8: bm = %d, not 0, 32 or 64", bm);
+    SD_REQUIRE(x && wq && w_scale && out && plan_out, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, kInvalidArgument, "gemm_w8a8: empty problem");
+    ConvDesc d;
+    d.C0 = Cin;
+    d.B = B; d.Hi = H; d.Wi = W; d.Ho = H; d.Wo = W;
+    d.N = Cout;
+    const int code = conv_plan_pin(WeightSource::I8Gemm, bm).staging;
+    SD_REQUIRE(conv_fast_path_ok(d) && smgemm_shape_ok(d, code), kInvalidArgument,
+               "gemm_w8a8: shape not eligible for plan tile 19 (smgemm_i8.hip: Cin=%d Cout=%d M=%d bm=%d - Cin a multiple of 64, Cout of 80, M of the "
+               "tile height, at least 2 x 2 tiles and a multiple of 8 of them)", Cin, Cout, B * H * W, bm);
+    SD_REQUIRE(smgemm_i8_shape_ok(d, code), kInvalidArgument, "gemm_w8a8: K = %d, the exact int32 sums of plan tile 19 hold up to %d", Cin, kSmI8MaxK);
+    // act_absmax, then w_scale, then the weight values (-128 is outside the symmetric range)
+    (void)w8a8_host_copy("gemm_w8a8", wq, w_scale, act_absmax, Cout, Cin, 1, WeightSource::I8Gemm);
+    Scratch sc;
+    d.x0 = upload_nhwc(sc, x, B, Cin, H, W);
+    d.bias = bias ? sc.dev<float>(Cout, bias) : nullptr;
+    if (res) d.res = upload_nhwc(sc, res, B, Cout, H, W);
+    half_t* dout = sc.dev<half_t>((size_t)B * H * W * Cout);
+    d.out = dout;
+    HostWeights h;
+    h.kind = WeightSource::I8Gemm; h.q = wq; h.w_scale = w_scale; h.act_absmax = act_absmax;
+    upload_compressed(sc, d, "gemm_w8a8", h, bm);
+    const ConvPlan p = conv_plan(d);
+    plan_out[0] = p.tile; plan_out[1] = p.staging; plan_out[2] = p.splitk; plan_out[3] = p.slab ? 1 : 0;
+    ConvWorkspace ws;
+    sc.timed(iters, ms, [&] { launch_conv(d, ws, sc.stream); });
+    download_nchw(dout, out, B, Cout, H, W);
+  });
+}
+
+int sd_op_w8a8_pack_gemm(const int8_t* wq, int Cout, int K, int8_t* packed, size_t* bytes) {
+  return guarded([&] {
+    SD_REQUIRE(wq && bytes, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(Cout > 0 && K > 0 && Cout % 16 == 0 && K % 64 == 0, kInvalidArgument, "w8a8_pack_gemm: Cout %d K %d", Cout, K);
+    *bytes = smgemm_i8_bytes(Cout, K);
+    if (packed) smgemm_i8_pack(wq, Cout, K, packed);
+  });
+}
+
 int sd_op_w8a8_pack(const int8_t* wq, int Cout, int Ctot, int ksize, int8_t* stream, size_t* bytes) {
   return guarded([&] {
     SD_REQUIRE(wq && bytes, kInvalidArgument, "NULL argument");
@@ -1287,6 +1331,12 @@ static ConvPlan query_conv_plan(int ksize, int stride, int up, int C0, int C1, i
   if (tile == 18) {   // ... and so does one of the int8 halo conv
     d.w = nullptr;
     d.cw.kind = WeightSource::I8Halo;
+    d.cw.stream = d.cw.scale = present;
+    d.cw.inv_s = 1.f;
+  }
+  if (tile == 19) {   // ... and one of the int8 small-M GEMM
+    d.w = nullptr;
+    d.cw.kind = WeightSource::I8Gemm;
     d.cw.stream = d.cw.scale = present;
     d.cw.inv_s = 1.f;
   }

@@ -63,6 +63,8 @@ bool halo_i8_ok(const ConvDesc& d) {
 // plan tile 15: the small-M 1x1 GEMM;  plan tile 16: the GEGLU projection
 bool pal_gemm(const ConvDesc& d) { return d.cw.kind == WeightSource::PalGemm; }
 bool pal_geglu(const ConvDesc& d) { return d.cw.kind == WeightSource::PalGeglu; }
+// plan tile 19: the small-M 1x1 GEMM from int8 weights and activations
+bool i8_gemm(const ConvDesc& d) { return d.cw.kind == WeightSource::I8Gemm; }
 // tiles 9 / 14 / 17: the code's wave count (decode_plan)
 int wstream_waves(int code) { return code == 4 ? 4 : 8; }
 // fp32 slabs of a launch: one per split, one when only `slab` (weight stream, GroupNorm twins) asks for the slab path
@@ -279,6 +281,11 @@ ConvPlan plan_codes(const ConvDesc& d) {
     SD_REQUIRE(conv_fast_path_ok(d) && cw.stream && cw.scale && halo_i8_ok(d), kInvalidArgument,
                "plan tile 18 (conv3x3_halo_i8.hip, int8) needs the int8 weights, the scales and a 3x3 / stride-1 shape of the halo conv with "
                "at most %d input channels (k=%d stride=%d up=%d C0=%d C1=%d N=%d)", kHaloI8MaxCtot, d.ksize, d.stride, d.up, d.C0, d.x1 ? d.C1 : 0, d.N);
+  // (nor has an int8 GEMM descriptor: tile 19 takes it or nobody does)
+  if (i8_gemm(d))
+    SD_REQUIRE(conv_fast_path_ok(d) && cw.stream && cw.scale && d.staging >= 0 && d.staging <= 2 && smgemm_i8_shape_ok(d, d.staging), kInvalidArgument,
+               "plan tile 19 (smgemm_i8.hip, int8) needs the int8 weights, the scales and a single-source shape of the small-M GEMM with K <= %d "
+               "(k=%d C0=%d C1=%d N=%d M=%d mode=%d)", kSmI8MaxK, d.ksize, d.C0, d.x1 ? d.C1 : 0, d.N, d.B * d.Ho * d.Wo, d.out_mode);
   if (!conv_fast_path_ok(d)) return ConvPlan{-1, 0, 1, false, 0};
   // a compressed weight source, in front of the tuner candidate, the tables and every rule: nothing moves it
   switch (cw.kind) {
@@ -308,6 +315,8 @@ ConvPlan plan_codes(const ConvDesc& d) {
       SD_REQUIRE(cw.stream && cw.lut && palette_bits_ok(cw.bits) && !d.x1 && d.staging >= 0 && d.staging <= 2 && smgemm_shape_ok(d, d.staging), kInvalidArgument,
                  "plan tile 15 (smgemm.hip, palettized) needs the index stream, the LUT and a single-source shape of the small-M GEMM");
       return ConvPlan{15, smgemm_bm(d, d.staging) == 32 ? 1 : 2, 1, false, 0};
+    case WeightSource::I8Gemm:   // the code of tile 12 in, the resolved tile height out; no split-K, no slab, no workspace (checked above)
+      return ConvPlan{19, smgemm_bm(d, d.staging) == 32 ? 1 : 2, 1, false, 0};
     case WeightSource::PalGeglu:   // the code of tile 13 in, the resolved tile height out (128 rows: code 1; 256 is not built)
       SD_REQUIRE(cw.stream && cw.lut && palette_bits_ok(cw.bits) && (cw.ln_gamma != nullptr) == (d.ln_colsum != nullptr) && smgeglu_pal_shape_ok(d, d.staging),
                  kInvalidArgument,
@@ -371,7 +380,7 @@ ConvPlan plan_codes(const ConvDesc& d) {
 //   tile 7:    0 / 2 / 3 / 4 / 5 = 2 / 3 / 4 / 6 / 8 weight stages; GroupNorm in the loader: 4 stages from code 3 where its table fits, else 3
 //   tile 18:   tile 7's codes; the int8 kernel has rings of 2 / 3 / 4 stages, a deeper code runs the 4-stage one
 //   tiles 9 / 14 / 17: 4 = four waves per workgroup, anything else eight      tile 11: 1-6 = the variant, anything else the library's choice
-//   tiles 12 / 15 / 13 / 16: 1 / 2 = the lower / higher tile (32 / 64, 128 / 256 rows), 0 = by the shape
+//   tiles 12 / 15 / 19 / 13 / 16: 1 / 2 = the lower / higher tile (32 / 64, 128 / 256 rows), 0 = by the shape
 void decode_plan(const ConvDesc& d, ConvPlan& p) {
   const Dims a = dims_of(d);
   int code = p.staging;
@@ -386,8 +395,8 @@ void decode_plan(const ConvDesc& d, ConvPlan& p) {
       p.kernel = ConvKernel::Bvgemm;
       p.variant = code >= 1 && code <= 6 ? code : bvgemm_auto_variant(d);
       return;
-    case 12: case 15:
-      p.kernel = p.tile == 12 ? ConvKernel::Smgemm : ConvKernel::SmgemmPal;
+    case 12: case 15: case 19:
+      p.kernel = p.tile == 12 ? ConvKernel::Smgemm : p.tile == 15 ? ConvKernel::SmgemmPal : ConvKernel::SmgemmI8;
       p.bm = code >= 0 && code <= 2 ? smgemm_bm(d, code) : 0;   // (0: no such tile - the launcher refuses it)
       return;
     case 13: case 16:
@@ -466,6 +475,7 @@ std::string conv_plan_kernel_name(const ConvPlan& p) {
     case ConvKernel::Bvgemm: return "bvgemm v" + std::to_string(p.variant);
     case ConvKernel::Smgemm: return "smgemm bm" + std::to_string(p.bm);
     case ConvKernel::SmgemmPal: return "smgemm_pal bm" + std::to_string(p.bm);
+    case ConvKernel::SmgemmI8: return "smgemm_i8 bm" + std::to_string(p.bm);
     case ConvKernel::Smgeglu: return "smgeglu bm" + std::to_string(p.bm);
     case ConvKernel::SmgegluPal: return "smgeglu_pal bm" + std::to_string(p.bm);
     default: return "generic";
@@ -479,7 +489,7 @@ std::string conv_plan_kernel_name(const ConvPlan& p) {
 //   - with the weight-stream copy present, its slab count at four waves per workgroup (the most slabs it writes);
 //   - the unresolved split-K (the launch may use fewer splits), one slab when only the GroupNorm twins ask for it.
 size_t conv_workspace_bytes(const ConvDesc& d) {
-  if (!conv_fast_path_ok(d) || pal_gemm(d) || pal_geglu(d)) return 0;   // (tiles 15 / 16: no slabs)
+  if (!conv_fast_path_ok(d) || pal_gemm(d) || pal_geglu(d) || i8_gemm(d)) return 0;   // (tiles 15 / 16 / 19: no slabs)
   const Dims a = dims_of(d);
   const Plan p = choose_plan(d, a);
   int splits = (switches().tuning && can_split(d)) ? std::max(p.splitk, 16) : p.splitk;
@@ -525,6 +535,7 @@ WeightPin conv_plan_pin(WeightSource kind, int n) {
     case WeightSource::I8Wstream: return {kind, 17, n == 4 ? 4 : 0};
     case WeightSource::I8Halo: return {kind, 18, n};   // n: tile 7's ring code as it is
     case WeightSource::PalGemm: return {kind, 15, n == 32 ? 1 : n == 64 ? 2 : 0};
+    case WeightSource::I8Gemm: return {kind, 19, n == 32 ? 1 : n == 64 ? 2 : 0};
     case WeightSource::PalGeglu: return {kind, 16, n == 128 ? 1 : n == 256 ? 2 : 0};
     default: return {};
   }
@@ -548,6 +559,10 @@ WeightPin conv_plan_weights(const ConvDesc& d, StoredWeights held, bool opt_in) 
   if (one_by_one && d.out_mode == kOutHalf && sw.smgemm && !d.ln_colsum) {   // tile 12
     const ConvPlan p = fp16_plan(d, conv_plan_copies(d));
     if (p.kernel == ConvKernel::Smgemm) return conv_plan_pin(WeightSource::PalGemm, p.bm);
+  }
+  if (opt_in && held == StoredWeights::W8A8 && d.ksize == 1 && !d.x1 && d.out_mode == kOutHalf && sw.smgemm && !d.ln_colsum) {   // tile 12, as above
+    const ConvPlan p = fp16_plan(d, conv_plan_copies(d));
+    if (p.kernel == ConvKernel::Smgemm && smgemm_i8_shape_ok(d, 0)) return conv_plan_pin(WeightSource::I8Gemm, p.bm);
   }
   if (held == StoredWeights::W8A8 && halo_i8_ok(d)) {   // tile 7 without the GroupNorm loader: its ring code and resolved split-K
     const ConvPlan p = fp16_plan(d, conv_plan_copies(d));
@@ -607,6 +622,9 @@ void conv_plan_log(const ConvDesc& d, const ConvPlan& p, int n_fast) {
   else if (p.tile == 15 || p.tile == 16)
     fprintf(stderr, "[sd conv] k1 s1 up1 C0=%d C1=%d M=%d N=%d K=%d mode=%d tile=%d bm=%d n_fast=%d bits=%d\n", d.C0, c1, a.M, a.N, a.K, d.out_mode,
             p.tile, p.bm, n_fast, d.cw.bits);
+  else if (p.tile == 19)
+    fprintf(stderr, "[sd conv] k1 s1 up1 C0=%d C1=%d M=%d N=%d K=%d mode=%d tile=%d bm=%d n_fast=%d bits=8\n", d.C0, c1, a.M, a.N, a.K, d.out_mode, p.tile,
+            p.bm, n_fast);
   else if (p.tile == 18)
     fprintf(stderr, "[sd conv] k%d s%d up%d C0=%d C1=%d M=%d N=%d K=%d mode=%d tile=%d splitk=%d bits=8\n", d.ksize, d.stride, d.up, d.C0, c1, a.M, a.N,
             a.K, d.out_mode, p.tile, p.splitk);

@@ -8,8 +8,8 @@
 
 namespace sd {
 
-// the kernel a plan launches (tile -1 / 1-4 / 7 / 18 / 9 / 14 / 17 / 10 / 11 / 12 / 15 / 13 / 16 of the wire format below)
-enum class ConvKernel { Generic, Igemm, GemmPipe, HaloKs, HaloI8, Wstream, WstreamPal, WstreamI8, Wsgemm, Bvgemm, Smgemm, SmgemmPal, Smgeglu, SmgegluPal };
+// the kernel a plan launches (tile -1 / 1-4 / 7 / 18 / 9 / 14 / 17 / 10 / 11 / 12 / 15 / 19 / 13 / 16 of the wire format below)
+enum class ConvKernel { Generic, Igemm, GemmPipe, HaloKs, HaloI8, Wstream, WstreamPal, WstreamI8, Wsgemm, Bvgemm, Smgemm, SmgemmPal, SmgemmI8, Smgeglu, SmgegluPal };
 
 struct ConvPlan {
   // The wire format: what ConvDesc::tile / staging pins, tuned_convs.inc rows, SD_PLAN_TABLE and sd_tune_set_candidate say and what
@@ -17,7 +17,8 @@ struct ConvPlan {
   int tile;        // 1: 128x128, 2: 128x64, 3: 64x64, 4: 64x128 (igemm.hip), 7: the K-split halo conv (conv3x3_halo.hip), 9: wstream.hip,
                    // 10: wsgemm.hip, 11: bvgemm.hip, 12: smgemm.hip, 13: smgeglu.hip, 14: wstream.hip from palettized weights,
                    // 15: smgemm.hip from palettized weights, 17: wstream.hip from int8 weights and activations (W8A8),
-                   // 18: the halo conv from int8 weights and activations (conv3x3_halo_i8.hip; never the library's own answer);
+                   // 18: the halo conv from int8 weights and activations (conv3x3_halo_i8.hip; never the library's own answer),
+                   // 19: the small-M GEMM from int8 weights and activations (smgemm_i8.hip, tile 12's tiles; never the library's own answer);
                    // -1 = not on the MFMA path (launch_conv_generic)
   int staging;     // per-family code: decode_plan
   int splitk;      // resolved: what the launch runs, no empty splits (halo: over 64-channel chunks; tile 9: the slab count)
@@ -51,7 +52,9 @@ ConvWeightCopies conv_plan_copies(const ConvDesc& d);
 //   Palette: opted-in GEGLU (tile 16 for tile 13 on the 128-row tiles the palettized kernel has), then the weight stream (tile 14 for
 //            tile 9), then the opted-in single-source small-M GEMM (tile 15 for tile 12)
 //   W8A8:    the weight stream (tile 17) by tile 14's predicate, then the halo conv (tile 18 for tile 7 without the GroupNorm loader,
-//            with that plan's ring code and split-K; Ctot <= kHaloI8MaxCtot); an observing store asks this without holding a mark
+//            with that plan's ring code and split-K; Ctot <= kHaloI8MaxCtot), then the opted-in single-source small-M GEMM (tile 19 for
+//            tile 12: tile 15's predicate; K <= kSmI8MaxK holds wherever tile 12 is the library's rule); an observing store asks this
+//            without holding a mark, with the call site's consent only when it observes the projections too
 enum class StoredWeights { Fp16, Palette, W8A8 };
 struct WeightPin {
   WeightSource kind = WeightSource::Fp16;
@@ -69,7 +72,7 @@ void conv_plan_log(const ConvDesc& d, const ConvPlan& p, int n_fast = 0);
 // What launches, as one line (sd_op_conv_plan_kernel): the kernel's name, then only the fields that kernel has -
 //   "igemm <bm>x<bn> ring<stages>[ kg2][ regs]"    "gemm_pipe <bm>x<bn> ring<stages>"    "halo_ks ring<stages>"    "halo_i8 ring<stages>"
 //   "wstream waves<n>"   "wstream_pal waves<n>"    "wstream_i8 waves<n>"                 "wsgemm"    "bvgemm v<variant>"
-//   "smgemm bm<bm>"      "smgemm_pal bm<bm>"       "smgeglu bm<bm>"                      "generic"
+//   "smgemm bm<bm>"      "smgemm_pal bm<bm>"       "smgemm_i8 bm<bm>"                    "smgeglu bm<bm>"    "generic"
 std::string conv_plan_kernel_name(const ConvPlan& p);
 
 // Tile order inside an XCD's run of workgroup ids, from an estimate of the bytes each order pulls through the fabric into the 8 XCD L2s:
@@ -113,5 +116,8 @@ constexpr size_t halo_i8_lds_bytes(int d) {
 // exact int32 sums: 127 * 127 * 9 * Ctot < 2^31
 constexpr int kHaloI8MaxCtot = 14784;
 static_assert(127LL * 127 * 9 * kHaloI8MaxCtot < (1LL << 31) && 127LL * 127 * 9 * (kHaloI8MaxCtot + 64) >= (1LL << 31), "int32 bound of plan tile 18");
+// smgemm_i8_kernel (plan tile 19) sums the whole K of a 1x1 GEMM in int32: 127 * 127 * K < 2^31, the last multiple of 64 that fits
+constexpr int kSmI8MaxK = 133120;
+static_assert(127LL * 127 * kSmI8MaxK < (1LL << 31) && 127LL * 127 * (kSmI8MaxK + 64) >= (1LL << 31), "int32 bound of plan tile 19");
 
 }  // namespace sd

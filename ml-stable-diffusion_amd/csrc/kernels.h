@@ -37,7 +37,8 @@ struct GnTwin {
 //   PalGeglu    tile 16, smgeglu.hip  smgeglu_pal_kernel         stream of smgeglu_pal_pack   staging: tile 13's code
 //   I8Wstream   tile 17, wstream.hip  wstream_kernel NBITS = kWsI8 (W8A8)   stream of wstream_i8_pack   staging: tile 9's code
 //   I8Halo      tile 18, conv3x3_halo_i8.hip  conv3x3_halo_i8_kernel (W8A8)   stream of halo_i8_pack      staging: tile 7's code
-enum class WeightSource { Fp16, PalWstream, PalGemm, PalGeglu, I8Wstream, I8Halo };
+//   I8Gemm      tile 19, smgemm_i8.hip        smgemm_i8_kernel (W8A8)         stream of smgemm_i8_pack    staging: tile 12's code (0 = by M)
+enum class WeightSource { Fp16, PalWstream, PalGemm, PalGeglu, I8Wstream, I8Halo, I8Gemm };
 struct CompressedWeights {
   WeightSource kind = WeightSource::Fp16;
   const void* stream = nullptr;
@@ -47,13 +48,14 @@ struct CompressedWeights {
   // PalGeglu with the LayerNorm fold (ConvDesc::ln_colsum set): the fp32 norm weight [C0] - the kernel multiplies every LUT value by it
   // as fold_layernorm_rows does on the host; null without the fold
   const float* ln_gamma = nullptr;
-  // I8Wstream / I8Halo: the output scale per column scale[n] = fp32(s_a * s_w[n]) and inv_s = fp32(1 / s_a), the factor the kernel quantizes
+  // I8Wstream / I8Halo / I8Gemm: the output scale per column scale[n] = fp32(s_a * s_w[n]) and inv_s = fp32(1 / s_a), the factor the kernel quantizes
   // its activations by
   const float* scale = nullptr;
   float inv_s = 0.f;
   bool palettized() const { return kind == WeightSource::PalWstream || kind == WeightSource::PalGemm || kind == WeightSource::PalGeglu; }
   const uint8_t* pal() const { return palettized() ? static_cast<const uint8_t*>(stream) : nullptr; }
-  const int8_t* i8() const { return kind == WeightSource::I8Wstream || kind == WeightSource::I8Halo ? static_cast<const int8_t*>(stream) : nullptr; }
+  bool int8() const { return kind == WeightSource::I8Wstream || kind == WeightSource::I8Halo || kind == WeightSource::I8Gemm; }
+  const int8_t* i8() const { return int8() ? static_cast<const int8_t*>(stream) : nullptr; }
 };
 
 struct ConvDesc {
@@ -190,6 +192,10 @@ int smgemm_bm(const ConvDesc& d, int variant);                        // the til
 // the weights are decoded from the LUT into the fragments of the same MFMAs in the same order, the epilogue is launch_smgemm's, so
 // the output is bit-identical to launch_smgemm's on the fp16 weights lut[indices].  One source only.
 void launch_smgemm_pal(const ConvDesc& d, const ConvPlan& p, hipStream_t s);
+// smgemm_i8.hip: the single-source GEMM on the same tiles from int8 weights and activations (W8A8, plan tile 19: d.cw of kind I8Gemm) -
+// the semantics of the int8 weight stream (plan tile 17), not tile 12's rounding; K <= kSmI8MaxK
+bool smgemm_i8_shape_ok(const ConvDesc& d, int variant);              // smgemm_shape_ok, one source, inside the int32 bound
+void launch_smgemm_i8(const ConvDesc& d, const ConvPlan& p, hipStream_t s);
 
 // wfold.hip: two back-to-back linear maps folded into one - merged [N][K + J] = [fp16(Wp W2) | Wp], bm = bp + Wp b2 (Wp [N][J],
 // W2 [J][K]; fp32 accumulation in a fixed order, once per handle: UNet::transformer_block's merged tail)

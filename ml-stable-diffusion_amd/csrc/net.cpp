@@ -88,12 +88,13 @@ Tensor Net::conv(std::vector<Op>& ops, const std::string& name, const Tensor& x,
   const float* b = a.bias ? upload_vec(name + ".bias", a.cout, geglu) : nullptr;
   const WeightPin pin = weight_plan(name, x, a, false);
   // An observing store (calibration) puts an absmax op over the conv's source(s) in front of every conv the int8 weight stream could
-  // take (level 1) or either int8 kernel could (level 2: the halo conv too): an ordinary member of the launch list that writes one slot
-  // nothing else reads.
+  // take (level 1) or either int8 conv kernel could (level 2: the halo conv too): an ordinary member of the launch list that writes one
+  // slot nothing else reads.  A store that also observes the projections (observe_gemms) asks with the call site's consent to a pinned
+  // 1x1 kernel, and the small-M int8 GEMM (plan tile 19) may be the answer; without that flag the question and the answer are unchanged.
   const WeightSource could = ws_->observe() && !ws_->palette(name + ".weight") && !a.silu_out
-                                 ? conv_plan_weights(conv_shape(name, x, a), StoredWeights::W8A8, false).kind
+                                 ? conv_plan_weights(conv_shape(name, x, a), StoredWeights::W8A8, ws_->observe_gemms() && a.keep_compressed).kind
                                  : WeightSource::Fp16;
-  if (could == WeightSource::I8Wstream || (could == WeightSource::I8Halo && ws_->observe() >= 2)) {
+  if (could == WeightSource::I8Wstream || (could == WeightSource::I8Halo && ws_->observe() >= 2) || could == WeightSource::I8Gemm) {
     float* slot = ll_.arena.alloc_n<float>(1);   // (the arena is zeroed: the running maximum starts at 0)
     observed_.push_back({name + ".weight", slot});
     const half_t *p0 = x.p, *p1 = a.x2 ? a.x2->p : nullptr;
@@ -126,7 +127,7 @@ ConvWeights Net::upload_compressed(const std::string& name, const WeightPin& pin
   };
   size_t bytes = 0;
   CompressedWeights cw;
-  if (pin.kind == WeightSource::I8Wstream || pin.kind == WeightSource::I8Halo) {   // q in the kernel's layout, cs[n], inv_s: no fp16 copy
+  if (pin.kind == WeightSource::I8Wstream || pin.kind == WeightSource::I8Halo || pin.kind == WeightSource::I8Gemm) {   // q in the kernel's layout, cs[n], inv_s: no fp16 copy
     const W8A8Mark* i8 = ws_->w8a8(wname);
     SD_REQUIRE(i8 && ws_->get(wname).numel() == expect && i8->q.size() == expect && i8->w_scale.size() == (size_t)a.cout, kInvalidArgument,
                "%s: expected %zu W8A8 values (%d,%d,%d,%d)", wname.c_str(), expect, a.cout, cin, a.k, a.k);
@@ -305,7 +306,7 @@ Tensor Net::conv_w(std::vector<Op>& ops, const std::string& name, const ConvWeig
   // trailing "#kind,ksize,stride,up,Ctot,N,M" is the plan-table key of this op (tools/tune_plans.py)
   const int kind = d.out_t ? 3 : (geglu ? 2 : (ln ? 1 : 0));
   // the weight source in the label: "[+ln]+pal<bits>" from a palette (plan tile 14 or 15), "geglu+pal<bits>[+ln]" for plan tile 16,
-  // "+w8a8" from int8 weights and quantized activations (plan tiles 17 / 18)
+  // "+w8a8" from int8 weights and quantized activations (plan tiles 17 / 18 / 19)
   const WeightSource src = d.cw.kind;
   const std::string lnmark = ln ? "+ln" : "", palmark = "+pal" + std::to_string(d.cw.bits);
   const std::string mark = src == WeightSource::PalGeglu ? palmark + lnmark : lnmark + (d.cw.i8() ? "+w8a8" : src != WeightSource::Fp16 ? palmark : "");

@@ -10,6 +10,11 @@
 //          A: lane l holds A[i=l&31][k=16*(l>>5)+e], B: B[k=16*(l>>5)+e][j=l&31], e = 0..15 (byte e of the four registers),
 //          D as above.  Checked with A = identity against an asymmetric B (D must be B: the k of every (lane, byte) is
 //          then read off directly) and with asymmetric data on both sides
+//   bit 4  v_mfma_i32_16x16x64_i8 (the W8A8 small-M GEMM, smgemm_i8.hip): 16 int8 per lane and operand,
+//          A: lane l holds A[i=l&15][k=16*(l>>4)+e], B: B[k=16*(l>>4)+e][j=l&15], e = 0..15 (byte e of the four registers),
+//          D: lane l reg r holds D[i=4*(l>>4)+r][j=l&15] (the 16x16 map of every dtype).  Checked like bit 3: A = the 16 x 64
+//          selector A[i][k] = (k == 16 q + i) for each quarter q of K against an asymmetric B (D must be rows 16 q .. of B), then
+//          asymmetric data on both sides
 // Asymmetric integer data so a transposed or permuted mapping cannot pass by accident.
 #include "kernels.h"
 
@@ -57,6 +62,21 @@ __global__ void mfma_i8_probe(const int8_t* __restrict__ A, const int8_t* __rest
     const int i = (r & 3) + 8 * (r >> 2) + 4 * (l >> 5), j = l & 31;
     D[i * 32 + j] = c[r];
   }
+}
+
+__global__ void mfma_i8_16_probe(const int8_t* __restrict__ A, const int8_t* __restrict__ B, int* __restrict__ D) {
+  const int l = threadIdx.x;
+  intx4 a = {0, 0, 0, 0}, b = {0, 0, 0, 0};
+#pragma unroll
+  for (int e = 0; e < 16; ++e) {
+    const int k = 16 * (l >> 4) + e;
+    a[e >> 2] |= (int)((unsigned)(unsigned char)A[(l & 15) * 64 + k] << (8 * (e & 3)));   // A[16][64] row-major
+    b[e >> 2] |= (int)((unsigned)(unsigned char)B[k * 16 + (l & 15)] << (8 * (e & 3)));   // B[64][16] row-major
+  }
+  intx4 c = {0, 0, 0, 0};
+  c = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, c, 0, 0, 0);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) D[(4 * (l >> 4) + r) * 16 + (l & 15)] = c[r];
 }
 
 template <int CTRL>
@@ -207,6 +227,40 @@ int selftest_mfma() {
         }
     }
     if (bad) result |= 8;
+    (void)hipFree(dA8);
+    (void)hipFree(dB8);
+    (void)hipFree(dD8);
+  }
+  {   // bit 4: the 16x16x64 int8 form - a selector of each quarter of K first (passes 0-3), then asymmetric data on both sides
+    int8_t hA8[16 * 64], hB8[64 * 16], *dA8, *dB8;
+    int ref8[16 * 16], got8[16 * 16], *dD8;
+    SD_HIP(hipMalloc(&dA8, sizeof(hA8)));
+    SD_HIP(hipMalloc(&dB8, sizeof(hB8)));
+    SD_HIP(hipMalloc(&dD8, sizeof(got8)));
+    for (int k = 0; k < 64; ++k)
+      for (int j = 0; j < 16; ++j) hB8[k * 16 + j] = (int8_t)((k * 37 + j * 11) % 255 - 127);   // -127 .. 127, no row or column alike
+    bad = 0;
+    for (int pass = 0; pass < 5; ++pass) {
+      for (int i = 0; i < 16; ++i)
+        for (int k = 0; k < 64; ++k) hA8[i * 64 + k] = pass < 4 ? (int8_t)(k == 16 * pass + i) : (int8_t)((i * 29 + k * 53) % 255 - 127);
+      for (int i = 0; i < 16; ++i)
+        for (int j = 0; j < 16; ++j) {
+          int sum = 0;
+          for (int k = 0; k < 64; ++k) sum += (int)hA8[i * 64 + k] * (int)hB8[k * 16 + j];
+          ref8[i * 16 + j] = sum;
+        }
+      SD_HIP(hipMemcpy(dA8, hA8, sizeof(hA8), hipMemcpyHostToDevice));
+      SD_HIP(hipMemcpy(dB8, hB8, sizeof(hB8), hipMemcpyHostToDevice));
+      hipLaunchKernelGGL(mfma_i8_16_probe, dim3(1), dim3(64), 0, 0, dA8, dB8, dD8);
+      SD_HIP(hipDeviceSynchronize());
+      SD_HIP(hipMemcpy(got8, dD8, sizeof(got8), hipMemcpyDeviceToHost));
+      for (int i = 0; i < 16 * 16; ++i)
+        if (got8[i] != ref8[i]) {
+          if (bad < 8) fprintf(stderr, "[sd selftest] mfma i8 16x16x64 (pass %d) D[%d][%d] = %d, expected %d\n", pass, i / 16, i % 16, got8[i], ref8[i]);
+          ++bad;
+        }
+    }
+    if (bad) result |= 16;
     (void)hipFree(dA8);
     (void)hipFree(dB8);
     (void)hipFree(dD8);

@@ -153,7 +153,12 @@ inline void wstream_i8_pack(const int8_t* q, int N, int Ctot, int ksize, int8_t*
 // per weight - a (n, tap, 64-channel chunk) row is 64 contiguous bytes, what one DMA lane quartet fetches.  q [N][Ctot][k][k] (the
 // checkpoint's order); dst holds N * Ctot * k * k bytes.
 inline void halo_i8_pack(const int8_t* q, int N, int Ctot, int ksize, int8_t* dst) { retile_ohwi(q, N, Ctot, ksize, false, dst); }
-// What an upload of a W8A8 conv starts from (sd_op_conv2d_w8a8 / _halo, Net::conv), checked in the order the header lists: act_absmax, finite
+// The int8 weights of smgemm_i8.hip (plan tile 19): [N][K], the checkpoint's own order of a 1x1 conv / Linear - wave w of a tile
+// fetches rows 16 w .. 16 w + 15 of a K64 stage as one 1-KB LDS-DMA piece, 16 rows x 64 contiguous bytes, and the swizzle of its LDS
+// image is applied on the source address.  The layout is stated here once: the function is a copy.  N % 16 == 0, K % 64 == 0.
+inline size_t smgemm_i8_bytes(int N, int K) { return (size_t)N * K; }
+inline void smgemm_i8_pack(const int8_t* q, int N, int K, int8_t* dst) { std::copy(q, q + smgemm_i8_bytes(N, K), dst); }
+// What an upload of a W8A8 conv starts from (sd_op_conv2d_w8a8 / _halo, sd_op_gemm_w8a8, Net::conv), checked in the order the header lists: act_absmax, finite
 // positive scales, no value of -128 (the symmetric scheme has none); the packed stream, cs[n] = fp32(s_a * s_w[n]) with s_a = act_absmax / 127, and inv_s = fp32(1 / s_a).
 struct W8A8HostCopy {
   std::vector<int8_t> stream;
@@ -162,7 +167,7 @@ struct W8A8HostCopy {
 };
 inline bool w8a8_absmax_ok(float act_absmax) { return std::isfinite(act_absmax) && act_absmax > 0.f; }
 inline W8A8HostCopy w8a8_host_copy(const char* what, const int8_t* q, const float* w_scale, float act_absmax, int N, int Ctot, int ksize,
-                                   WeightSource kind = WeightSource::I8Wstream) {   // one of the two int8 kinds
+                                   WeightSource kind = WeightSource::I8Wstream) {   // one of the three int8 kinds
   SD_REQUIRE(w8a8_absmax_ok(act_absmax), kInvalidArgument, "%s: act_absmax = %g, not a positive finite number", what, (double)act_absmax);
   const size_t n_el = wstream_i8_bytes(N, Ctot, ksize);
   W8A8HostCopy h;
@@ -177,6 +182,7 @@ inline W8A8HostCopy w8a8_host_copy(const char* what, const int8_t* q, const floa
   for (size_t i = 0; i < n_el; ++i) SD_REQUIRE(q[i] != -128, kInvalidArgument, "%s: weight value -128 at element %zu, the symmetric range is [-127, 127]", what, i);
   h.stream.resize(n_el);
   if (kind == WeightSource::I8Halo) halo_i8_pack(q, N, Ctot, ksize, h.stream.data());
+  else if (kind == WeightSource::I8Gemm) smgemm_i8_pack(q, N, Ctot, h.stream.data());   // (ksize 1)
   else wstream_i8_pack(q, N, Ctot, ksize, h.stream.data());
   return h;
 }

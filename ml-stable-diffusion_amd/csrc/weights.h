@@ -45,6 +45,9 @@ class WeightStore {
   // handles built from this store put an absmax observer in front of every conv plan tile 17 could take
   void set_observe(int level) { observe_ = level; }   // 0 off, 1 the convs plan tile 17 could take, 2 also those of plan tile 18
   int observe() const { return observe_; }
+  // ... and, while observing, in front of every projection plan tile 19 could take at a call site that consents to a pinned 1x1 kernel
+  void set_observe_gemms(bool on) { observe_gemms_ = on; }
+  bool observe_gemms() const { return observe_gemms_; }
   void add(const std::string& name, const void* data, int dtype /*0 f16, 1 f32, 2 bf16*/,
            const int64_t* shape, int ndim);
   void load_safetensors(const std::string& path, const std::string& prefix);
@@ -65,6 +68,7 @@ class WeightStore {
   std::map<std::string, Palette> pal_;
   std::map<std::string, W8A8Mark> i8_;
   int observe_ = 0;
+  bool observe_gemms_ = false;
 };
 
 }  // namespace sd

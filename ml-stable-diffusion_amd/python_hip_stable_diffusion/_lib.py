@@ -100,6 +100,7 @@ SYMBOLS = [
     ("sd_weights_quantize_w8a8", _I, [_P, C.c_char_p, _F, C.POINTER(C.c_double)]),
     ("sd_weights_w8a8_info", _I, [_P, C.c_char_p, _FP]),
     ("sd_weights_observe_activations", _I, [_P, _I]),
+    ("sd_weights_observe_gemms", _I, [_P, _I]),
     ("sd_unet_w8a8_info", _I, [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(C.c_size_t)]),
     ("sd_unet_w8a8_layer", _I, [_P, _I, C.c_char_p, _I]),
     ("sd_unet_activation_ranges", _I, [_P, _I, C.c_char_p, _I, _FP]),
@@ -107,6 +108,8 @@ SYMBOLS = [
     ("sd_op_w8a8_pack", _I, [_P, _I, _I, _I, _P, C.POINTER(C.c_size_t)]),
     ("sd_op_conv2d_w8a8_halo", _I, [_P, _P, _P, _FP, _F, _FP, _FP, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_I), _I, _FP]),
     ("sd_op_w8a8_pack_halo", _I, [_P, _I, _I, _P, C.POINTER(C.c_size_t)]),
+    ("sd_op_gemm_w8a8", _I, [_P, _P, _FP, _F, _FP, _P, _P, _I, _I, _I, _I, _I, _I, C.POINTER(_I), _I, _FP]),
+    ("sd_op_w8a8_pack_gemm", _I, [_P, _I, _I, _P, C.POINTER(C.c_size_t)]),
     ("sd_op_quantize_weight", _I, [_FP, _I, C.c_size_t, _P, _FP, C.POINTER(C.c_double)]),
     ("sd_op_absmax", _I, [_P, C.c_size_t, _FP]),
     ("sd_unet_create", _I, [C.POINTER(UNetConfig), _P, _I, C.POINTER(_P)]),
@@ -585,6 +588,44 @@ def w8a8_pack_halo(wq):
         raise ValueError("w8a8_pack_halo: wq must be (Cout, Ctot, 3, 3)")
     Cout, Ctot = wq.shape[:2]
     return _packed(lib().sd_op_w8a8_pack_halo, ptr(wq), Cout, Ctot).view(np.int8).reshape(Cout, 9, Ctot)
+
+
+def gemm_w8a8(x, wq, w_scale, act_absmax, bias=None, res=None, bm=0, out=None, iters=1):
+    """The single-source small-M 1x1 GEMM in W8A8 (sd_op_gemm_w8a8, plan tile 19): x (B, Cin, H, W), wq (Cout, Cin) int8, w_scale
+    (Cout,) f32, act_absmax the range of x; bm 0 / 32 / 64 = the tile height (0: by M).  ``out``: a C-contiguous float16 buffer of at
+    least B * Cout * H * W elements to write into (tests put guards behind it).  What the library checks - bm, shape, the int32 bound,
+    act_absmax, w_scale, a weight of -128 - it refuses itself (ValueError, no GPU needed).  Returns (out (B, Cout, H, W), plan, ms)."""
+    x = f16(x)
+    wq = np.ascontiguousarray(wq, dtype=np.int8)
+    w_scale = f32(w_scale)
+    if x.ndim != 4 or wq.ndim != 2 or wq.shape[1] != x.shape[1] or w_scale.shape != (wq.shape[0],):
+        raise ValueError("gemm_w8a8: x must be (B, Cin, H, W), wq (Cout, Cin) and w_scale (Cout,)")
+    B, Cin, H, W = x.shape
+    Cout = wq.shape[0]
+    bias = None if bias is None else f32(bias)
+    res = None if res is None else f16(res)
+    if (bias is not None and bias.shape != (Cout,)) or (res is not None and res.shape != (B, Cout, H, W)):
+        raise ValueError("gemm_w8a8: bias must be (Cout,), res (B, Cout, H, W)")
+    n = B * Cout * H * W
+    if out is None:
+        out = np.empty(n, np.float16)
+    if out.dtype != np.float16 or not out.flags.c_contiguous or out.size < n:
+        raise ValueError("gemm_w8a8: out must be a C-contiguous float16 buffer of at least B * Cout * H * W elements")
+    plan = (C.c_int * 4)()
+    ms = C.c_float(0)
+    check(lib().sd_op_gemm_w8a8(ptr(x), ptr(wq), fptr(w_scale), float(act_absmax), fptr(bias), ptr(res), ptr(out), B, Cin, H, W, Cout, bm, plan,
+                                iters, C.byref(ms)))
+    return out.reshape(-1)[:n].reshape(B, Cout, H, W), list(plan), ms.value
+
+
+def w8a8_pack_gemm(wq):
+    """The int8 weights of the W8A8 small-M GEMM (sd_op_w8a8_pack_gemm; host only): wq (Cout, K) int8 -> int8 (Cout, K), the
+    checkpoint's own order."""
+    wq = np.ascontiguousarray(wq, dtype=np.int8)
+    if wq.ndim != 2:
+        raise ValueError("w8a8_pack_gemm: wq must be (Cout, K)")
+    Cout, K = wq.shape
+    return _packed(lib().sd_op_w8a8_pack_gemm, ptr(wq), Cout, K).view(np.int8).reshape(Cout, K)
 
 
 def w8a8_pack(wq):

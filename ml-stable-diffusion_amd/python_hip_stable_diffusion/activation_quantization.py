@@ -6,11 +6,14 @@ The reference (``python_coreml_stable_diffusion/activation_quantization.py``) re
 (``--quantize-pytorch``).  Here the same scheme runs inside the library: the weight store MARKS a conv weight with its int8
 values, its per-channel scales and the range of the activations the conv reads (``sd_weights_quantize_w8a8``), and a handle runs
 a marked conv from int8 on ``v_mfma_i32_32x32x32_i8`` wherever its plan is the weight stream (``wstream.hip``, plan tile 17) or the
-3x3 / stride-1 halo conv (``conv3x3_halo_i8.hip``, plan tile 18); every other marked conv stays fp16 - the reference's skipped layers.  Parity with coremltools' quantizer is NOT pinned
+3x3 / stride-1 halo conv (``conv3x3_halo_i8.hip``, plan tile 18), and a marked plain 1x1 projection (``proj_in``, ``attn1.to_out.0``,
+``attn2.to_out.0`` of the 640- / 1280-channel levels) on ``v_mfma_i32_16x16x64_i8`` wherever its plan is the small-M GEMM
+(``smgemm_i8.hip``, plan tile 19); every other marked conv stays fp16 - the reference's skipped layers.  Parity with coremltools' quantizer is NOT pinned
 (coremltools is not a dependency of this project): the scales are plain absmax / 127, not the result of its calibration.
 
 Calibration happens on the device: ``HipModel(..., observe_activations=True)`` puts an absmax observer in front of every conv
-the int8 weight stream could take, ``observe_activations="all"`` in front of every conv that could run from int8; after any number of forwards ``.activation_ranges()`` is the recipe's raw material.
+the int8 weight stream could take, ``observe_activations="all"`` in front of every conv either int8 conv kernel could take, ``observe_activations="gemm"`` also in front of
+the projections plan tile 19 could take - every layer that could run from int8; after any number of forwards ``.activation_ranges()`` is the recipe's raw material.
 
 A recipe is JSON ``{layer: act_absmax}``, ``layer`` the conv's module name (its weight tensor without ``.weight``).
 

@@ -198,8 +198,10 @@ class Weights(_lib.Handle):
 
     def observe_activations(self, on=True):
         """Handles created from the store while this is on carry the activation observers (calibration): ``True`` in front of the
-        convs the int8 weight stream could take (plan tile 17), ``"all"`` in front of those of the int8 halo conv (plan tile 18) too."""
+        convs the int8 weight stream could take (plan tile 17), ``"all"`` in front of those of the int8 halo conv (plan tile 18) too,
+        ``"gemm"`` also in front of the plain 1x1 projections the int8 small-M GEMM could take (plan tile 19)."""
         _lib.check(_lib.lib().sd_weights_observe_activations(self._h, observe_level(on)))
+        _lib.check(_lib.lib().sd_weights_observe_gemms(self._h, int(on == "gemm")))
 
     @classmethod
     @contextlib.contextmanager
@@ -217,10 +219,11 @@ class Weights(_lib.Handle):
 
 
 def observe_level(on):
-    """observe_activations as the level of sd_weights_observe_activations: False 0, True 1, "all" 2."""
+    """observe_activations as the level of sd_weights_observe_activations: False 0, True 1, "all" 2; "gemm" is level 2 with the
+    projections' flag (sd_weights_observe_gemms) beside it."""
     if isinstance(on, str):
-        if on != "all":
-            raise ValueError(f"observe_activations must be False, True or 'all', got {on!r}")
+        if on not in ("all", "gemm"):
+            raise ValueError(f"observe_activations must be False, True, 'all' or 'gemm', got {on!r}")
         return 2
     return int(bool(on))
 
@@ -304,9 +307,9 @@ class HipModel(_lib.Model):
         if self.activation_quantization is not None:
             applied = set(self.w8a8_layers())
             stayed = sorted(set(self.activation_quantization) - applied)
-            logger.info("W8A8: %d of %d recipe layers run from int8 (plan tiles 17 / 18)", len(applied), len(self.activation_quantization))
+            logger.info("W8A8: %d of %d recipe layers run from int8 (plan tiles 17 / 18 / 19)", len(applied), len(self.activation_quantization))
             if stayed:
-                logger.info("W8A8: these layers stay fp16 (their plan is neither the weight stream nor the halo conv): %s", ", ".join(stayed))
+                logger.info("W8A8: these layers stay fp16 (their plan is none of the weight stream, the halo conv and the plain small-M projection): %s", ", ".join(stayed))
         self.batch, self.latent_height, self.latent_width = batch, h, w
         self.attention_implementation = attention_implementation
         self.num_residuals = _lib.lib().sd_unet_num_residuals(self._h)
