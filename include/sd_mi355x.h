@@ -94,19 +94,25 @@ int sd_weights_read_palette(const sd_weights* w, const char* name, void* lut, ui
  * stream (plan tile 9 -> wstream.hip, plan tile 17) or the 3x3 / stride-1 halo conv with at most 14 784 input channels (plan tile 7
  * -> conv3x3_halo_i8.hip, plan tile 18, with tile 7's ring and split-K) or, at a call site that consents to a pinned 1x1 kernel
  * (proj_in, attn1.to_out.0, attn2.to_out.0), the single-source small-M 1x1 GEMM (plan tile 12 -> smgemm_i8.hip, plan tile 19, with
- * tile 12's tile height) - the same function of its inputs in all three; any other marked conv (LayerNorm-folded or two-source 1x1,
- * GEGLU, stride 2, channel counts off the tiles) runs fp16 as before - the reference's skipped layers.
+ * tile 12's tile height) - the same function of its inputs in all three - or, for ff.net.0.proj, the GEGLU projection (plan tile 13 ->
+ * smgeglu_i8.hip, plan tile 20, at tile 13's tile height: norm3 is then not folded, one LayerNorm launch writes int8(norm3(x)) with
+ * act_absmax / 127 and the GEGLU reads it - sd_op_layernorm_q8 / sd_op_geglu_w8a8); any other marked conv (LayerNorm-folded q|k|v and
+ * to_q, two-source 1x1, GEGLUs off tile 13, stride 2, channel counts off the tiles) runs fp16 as before - the reference's skipped layers.
  * sd_weights_w8a8_info: 1 when `name` is marked (*act_scale, may be NULL, = s_a), else 0.
  * sd_weights_observe_activations(on): handles created from the store while it is on put an absmax observer in front of every conv
  * that plan tile 17 could take (on = 1) or that plan tile 17 or 18 could take (on = 2) (sd_unet_activation_ranges) - calibration on
  * the device.  0 = off; any other value is SD_ERR_INVALID_ARGUMENT.
  * sd_weights_observe_gemms(on): a flag beside that level - while the store observes (on = 1 or 2 above), handles created from it also
  * put an observer in front of every 1x1 projection plan tile 19 could take.  on = 0 / 1; any other value is SD_ERR_INVALID_ARGUMENT.
- * With the flag off the observer sets are those of the two levels above. */
+ * With the flag off the observer sets are those of the two levels above.
+ * sd_weights_observe_geglus(on): a second flag of the same kind (0 / 1, effective only while the store observes) - handles created from
+ * it also run, for every ff.net.0.proj plan tile 20 could take, a LayerNorm of the GEGLU's input into a scratch tensor and an observer
+ * over it, named by the projection's weight; the GEGLU itself runs folded in fp16 as without the flag, so the outputs do not change. */
 int sd_weights_quantize_w8a8(sd_weights* w, const char* name, float act_absmax, double* sq_err);
 int sd_weights_w8a8_info(const sd_weights* w, const char* name, float* act_scale);
 int sd_weights_observe_activations(sd_weights* w, int on);
 int sd_weights_observe_gemms(sd_weights* w, int on);
+int sd_weights_observe_geglus(sd_weights* w, int on);
 
 /* ------------------------------------------------------------------------------------------
  * UNet / ControlNet.  Config mirrors UNet2DConditionModel.__init__ (unet.py:801-833) with the
@@ -167,7 +173,7 @@ size_t sd_unet_arena_used_bytes(const sd_unet* u);
  * (q|k|v, attn2.to_q, the merged transformer tail, GEGLU projections on 256-row tiles) was uploaded as fp16 lut[indices]. */
 int sd_unet_palette_info(const sd_unet* u, int* n_palettized, int* n_streamed, size_t* stream_bytes);
 /* W8A8 (activation_quantization.py:141-203; sd_weights_quantize_w8a8): *n_marked tensors of the handle's weight store arrived with a
- * mark; *n_applied convolutions run from int8 (plan tiles 17, 18 and 19) and hold the int8 weights in their kernel's layout and one fp32
+ * mark; *n_applied convolutions run from int8 (plan tiles 17, 18, 19 and 20) and hold the int8 weights in their kernel's layout and one fp32
  * scale per output channel, no fp16 copy; *bytes = the bytes of those weights and scale vectors.  n_marked - n_applied marked convs
  * stayed fp16. */
 int sd_unet_w8a8_info(const sd_unet* u, int* n_marked, int* n_applied, size_t* bytes);
@@ -398,7 +404,7 @@ int sd_op_conv2d(const void* x, const void* w, const float* bias, const void* re
  *                 (+ SiLU with twin_silu) of the result to out_twin (B, Cout, Ho, Wo) f16 - no GroupNorm launch (the low-res
  *                 conv1 -> norm2 path); refused where the combine cannot hold whole (sample, group) slices
  *   plan_out[4]   the plan the launch ran: tile (1-4 igemm.hip, 7 conv3x3_halo.hip, 9 wstream.hip, 11 bvgemm.hip, 12 smgemm.hip; the
- *                 entries of the compressed sources report theirs: 14 / 15 / 16 palettized, 17 / 18 / 19 W8A8),
+ *                 entries of the compressed sources report theirs: 14 / 15 / 16 palettized, 17 / 18 / 19 / 20 W8A8),
  *                 staging, resolved split-K, 1 if the output left through fp32 slabs; all -1: the direct (non-MFMA) kernels
  * res / out are (B, Cout, Ho, Wo). */
 int sd_op_conv2d_ex(const void* x, const void* x1, const void* w, const float* bias, const float* temb, const void* res, void* out, int B,
@@ -462,6 +468,29 @@ int sd_op_gemm_w8a8(const void* x, const int8_t* wq, const float* w_scale, float
  * checkpoint's own order: a wave fetches 16 rows x 64 contiguous bytes per K stage and swizzles on the source address.  Cout a multiple
  * of 16, K of 64.  *bytes = its size (Cout * K); packed may be NULL to ask for the size alone. */
 int sd_op_w8a8_pack_gemm(const int8_t* wq, int Cout, int K, int8_t* packed, size_t* bytes);
+/* No reference counterpart as an operator; the pair stands for norm3 -> ff.net.0.proj (unet.py:583-591, :609-617) under
+ * quantize_cumulative_config (activation_quantization.py:141-203), which quantizes the OUTPUT of the LayerNorm and the un-folded weight.
+ * sd_op_layernorm_q8: x (M, C) f16 token-major -> xq (M, C) int8 = clip(rint(fp32(y) * (127 / act_absmax)), -127, 127), y the fp16 value
+ * sd_op_layernorm stores for that element (NaN -> 0, +-inf -> +-127); ln_weight / ln_bias (C) f32, or both NULL: y = x, a plain quantize.
+ * C a multiple of 8 up to 2048, act_absmax a positive finite number; one wavefront per row, 8-byte stores.
+ * sd_op_geglu_w8a8 (plan tile 20, smgeglu_i8.hip): xq (M, C) int8, wq (N2, C) int8 in the checkpoint's row order [values | gates], w_scale
+ * (N2) f32, act_absmax the range xq was quantized with, bias (N2) f32 or NULL -> out (M, N2 / 2) f16 = fp16(v * gelu_erf(g)) with
+ * v = (float(int32 sum over C) * (act_absmax / 127 * w_scale[n_v])) + bias[n_v], g the same on the gate row - each operation rounded to
+ * fp32 on its own, the ending that of sd_op_geglu_ln.  bm = tile height 128 / 256, 0 = by the grid as plan tile 13; iters, ms as
+ * sd_op_conv2d_ex.  plan_out = {20, 1 | 2 (bm 128 | 256), 1, 0}.  Checked on the host in this order, before any device work, each
+ * SD_ERR_INVALID_ARGUMENT: (1) bm not 0 / 128 / 256; (2) NULL arguments or an empty problem; (3) a shape plan tile 13 does not tile (C a
+ * multiple of 64, N2 of 160, M of the tile height, at least 2 x 2 tiles and a multiple of 8 of them); (4) C > 133120 (the int32 sums
+ * must stay exact); (5) act_absmax not a positive finite number; (6) a w_scale that is not; (7) a weight of -128; (8) an activation of
+ * -128. */
+int sd_op_layernorm_q8(const void* x, const float* ln_weight, const float* ln_bias, float act_absmax, float eps, int8_t* xq, int M, int C,
+                       int iters, float* ms);
+int sd_op_geglu_w8a8(const int8_t* xq, const int8_t* wq, const float* w_scale, float act_absmax, const float* bias, void* out, int M, int C,
+                     int N2, int bm, int* plan_out, int iters, float* ms);
+/* The int8 weights that entry and the UNet builder put on the device (host only): wq (N2, K) int8 [values | gates] -> packed
+ * [N2 / 16 strips][16 rows][K]: strip 2 U + v holds the checkpoint rows v * N2 / 2 + 16 U + (0 .. 15) - the value (v = 0) or gate
+ * (v = 1) rows of the output's 16-column unit U, every row whole - so a tile of 80 output columns stages ten consecutive strips.  N2 a
+ * multiple of 32, K of 64.  *bytes = its size (N2 * K); packed may be NULL to ask for the size alone. */
+int sd_op_w8a8_pack_geglu(const int8_t* wq, int N2, int K, int8_t* packed, size_t* bytes);
 /* The host weight quantizer of sd_weights_quantize_w8a8 on its own: w (Cout, per_row) f32 -> q (Cout, per_row) int8, w_scale (Cout)
  * f32, *sq_err (may be NULL).  A non-finite weight is SD_ERR_INVALID_ARGUMENT. */
 int sd_op_quantize_weight(const float* w, int Cout, size_t per_row, int8_t* q, float* w_scale, double* sq_err);
@@ -623,7 +652,10 @@ int sd_op_sched_step(const float* noise_pred, float* latents, float* hist, const
  * without gnf_groups, Ctot <= 14 784 and the tensor carries a W8A8 mark; tile = 19 asks for a W8A8 descriptor of the small-M 1x1 GEMM -
  * the answer is 19 with the resolved tile height of the same staging (1 / 2 = 32 / 64 rows), split-K 1, no slab, no workspace, or
  * SD_ERR_INVALID_ARGUMENT naming plan tile 19 for a shape it does not take; a handle takes 19 exactly where this says 12 for a
- * single-source plain projection at a consenting call site and the tensor carries a W8A8 mark),
+ * single-source plain projection at a consenting call site and the tensor carries a W8A8 mark; tile = 20 asks for a W8A8 descriptor of
+ * the GEGLU projection - the answer is 20 with the resolved tile height of the same staging (1 / 2 = 128 / 256 rows), split-K 1, no slab,
+ * no workspace, or SD_ERR_INVALID_ARGUMENT naming plan tile 20 for a shape it does not take (the LayerNorm fold, flags & 1, among
+ * them); a handle takes 20 exactly where this says 13 for ff.net.0.proj and the tensor carries a W8A8 mark),
  * staging, resolved split-K, slab (0 / 1), then the copies a handle must hold for this conv: wstream, wsgemm, bvgemm (0 / 1 each).
  * *workspace_bytes: the slab workspace this launch needs. */
 int sd_op_conv_plan(int ksize, int stride, int up, int C0, int C1, int N, int B, int Ho, int Wo, int out_mode, int flags, int n_trans,

@@ -600,6 +600,76 @@ int sd_op_w8a8_pack_gemm(const int8_t* wq, int Cout, int K, int8_t* packed, size
   });
 }
 
+// LayerNorm that leaves as int8 (the producer of plan tile 20's activations): x (M, C) f16 token-major, ln_weight / ln_bias (C) f32 or
+// both NULL (a plain quantize of x) -> xq (M, C) int8 with inv_s = 1 / (act_absmax / 127) as w8a8_host_copy computes it.
+int sd_op_layernorm_q8(const void* x, const float* ln_weight, const float* ln_bias, float act_absmax, float eps, int8_t* xq, int M, int C,
+                       int iters, float* ms) {
+  return guarded([&] {
+    SD_REQUIRE(x && xq, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(M > 0 && C > 0, kInvalidArgument, "layernorm_q8: empty problem");
+    SD_REQUIRE((ln_weight == nullptr) == (ln_bias == nullptr), kInvalidArgument, "layernorm_q8: ln_weight and ln_bias go together");
+    SD_REQUIRE(C % 8 == 0 && C <= 2048, kInvalidArgument, "layernorm_q8: C = %d, not a multiple of 8 up to 2048", C);
+    SD_REQUIRE(w8a8_absmax_ok(act_absmax), kInvalidArgument, "layernorm_q8: act_absmax = %g, not a positive finite number", (double)act_absmax);
+    const float inv_s = 1.0f / (act_absmax / 127.0f);
+    SD_REQUIRE(std::isfinite(inv_s) && inv_s > 0.f, kInvalidArgument, "layernorm_q8: act_absmax = %g has no finite inverse scale", (double)act_absmax);
+    Scratch sc;
+    const half_t* dx = sc.dev<half_t>((size_t)M * C, f16(x));
+    const float* dw = ln_weight ? sc.dev<float>(C, ln_weight) : nullptr;
+    const float* db = ln_bias ? sc.dev<float>(C, ln_bias) : nullptr;
+    int8_t* dq = sc.dev<int8_t>((size_t)M * C);
+    sc.timed(iters, ms, [&] { launch_layernorm_q8(dx, dw, db, dq, M, C, eps, inv_s, sc.stream); });
+    SD_HIP(hipMemcpy(xq, dq, (size_t)M * C, hipMemcpyDeviceToHost));
+  });
+}
+
+// The GEGLU projection in W8A8 (plan tile 20).  Every check runs on the host in front of the first device call (Scratch), in the order
+// the header lists them.  The bias goes up interleaved as the UNet builder uploads it (upload_vec(..., geglu)).
+int sd_op_geglu_w8a8(const int8_t* xq, const int8_t* wq, const float* w_scale, float act_absmax, const float* bias, void* out, int M, int C,
+                     int N2, int bm, int* plan_out, int iters, float* ms) {
+  return guarded([&] {
+    SD_REQUIRE(bm == 0 || bm == 128 || bm == 256, kInvalidArgument, "geglu_w8a8: bm = %d, not 0, 128 or 256", bm);
+    SD_REQUIRE(xq && wq && w_scale && out && plan_out, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(M > 0 && C > 0 && N2 > 0, kInvalidArgument, "geglu_w8a8: empty problem");
+    ConvDesc d = token_gemm(nullptr, C, nullptr, nullptr, nullptr, nullptr, 1, M, N2);
+    d.out_mode = kOutGeglu;
+    const int code = conv_plan_pin(WeightSource::I8Geglu, bm).staging;
+    SD_REQUIRE(conv_fast_path_ok(d) && smgeglu_shape_ok(d, code), kInvalidArgument,
+               "geglu_w8a8: shape not eligible for plan tile 20 (smgeglu_i8.hip: M=%d C=%d N2=%d bm=%d - C a multiple of 64, N2 of 160, M of the "
+               "tile height, at least 2 x 2 tiles and a multiple of 8 of them)", M, C, N2, bm);
+    SD_REQUIRE(smgeglu_i8_shape_ok(d, code), kInvalidArgument, "geglu_w8a8: K = %d, the exact int32 sums of plan tile 20 hold up to %d", C, kSmI8MaxK);
+    // act_absmax, then w_scale, then the weight values (-128 is outside the symmetric range), then the activations
+    (void)w8a8_host_copy("geglu_w8a8", wq, w_scale, act_absmax, N2, C, 1, WeightSource::I8Geglu);
+    for (size_t i = 0; i < (size_t)M * C; ++i)
+      SD_REQUIRE(xq[i] != -128, kInvalidArgument, "geglu_w8a8: activation value -128 at element %zu, the symmetric range is [-127, 127]", i);
+    Scratch sc;
+    d.x0_i8 = sc.dev<int8_t>((size_t)M * C, xq);
+    if (bias) {
+      std::vector<float> bi(N2);
+      for (int o = 0; o < N2; ++o) bi[geglu_row(o, N2)] = bias[o];
+      d.bias = sc.dev<float>(N2, bi.data());
+    }
+    half_t* dout = sc.dev<half_t>((size_t)M * (N2 / 2));
+    d.out = dout;
+    HostWeights h;
+    h.kind = WeightSource::I8Geglu; h.q = wq; h.w_scale = w_scale; h.act_absmax = act_absmax;
+    upload_compressed(sc, d, "geglu_w8a8", h, bm);
+    const ConvPlan p = conv_plan(d);
+    plan_out[0] = p.tile; plan_out[1] = p.staging; plan_out[2] = p.splitk; plan_out[3] = p.slab ? 1 : 0;
+    ConvWorkspace ws;
+    sc.timed(iters, ms, [&] { launch_conv(d, ws, sc.stream); });
+    SD_HIP(hipMemcpy(out, dout, (size_t)M * (N2 / 2) * 2, hipMemcpyDeviceToHost));
+  });
+}
+
+int sd_op_w8a8_pack_geglu(const int8_t* wq, int N2, int K, int8_t* packed, size_t* bytes) {
+  return guarded([&] {
+    SD_REQUIRE(wq && bytes, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(N2 > 0 && K > 0 && N2 % 32 == 0 && K % 64 == 0, kInvalidArgument, "w8a8_pack_geglu: N2 %d K %d", N2, K);
+    *bytes = smgeglu_i8_bytes(N2, K);
+    if (packed) smgeglu_i8_pack(wq, N2, K, packed);
+  });
+}
+
 int sd_op_w8a8_pack(const int8_t* wq, int Cout, int Ctot, int ksize, int8_t* stream, size_t* bytes) {
   return guarded([&] {
     SD_REQUIRE(wq && bytes, kInvalidArgument, "NULL argument");
@@ -1339,6 +1409,13 @@ static ConvPlan query_conv_plan(int ksize, int stride, int up, int C0, int C1, i
     d.cw.kind = WeightSource::I8Gemm;
     d.cw.stream = d.cw.scale = present;
     d.cw.inv_s = 1.f;
+  }
+  if (tile == 20) {   // ... and one of the int8 GEGLU projection, whose activations arrive as int8 too
+    d.w = nullptr;
+    d.cw.kind = WeightSource::I8Geglu;
+    d.cw.stream = d.cw.scale = present;
+    d.cw.inv_s = 1.f;
+    d.x0_i8 = reinterpret_cast<const int8_t*>(present);
   }
   c = conv_plan_copies(d);
   if (copies < 0) copies = (c.wstream ? 1 : 0) | (c.wsgemm ? 2 : 0) | (c.bvgemm ? 4 : 0);   // what a handle of the library holds

@@ -65,6 +65,8 @@ bool pal_gemm(const ConvDesc& d) { return d.cw.kind == WeightSource::PalGemm; }
 bool pal_geglu(const ConvDesc& d) { return d.cw.kind == WeightSource::PalGeglu; }
 // plan tile 19: the small-M 1x1 GEMM from int8 weights and activations
 bool i8_gemm(const ConvDesc& d) { return d.cw.kind == WeightSource::I8Gemm; }
+// plan tile 20: the GEGLU projection from int8 weights and int8 activations
+bool i8_geglu(const ConvDesc& d) { return d.cw.kind == WeightSource::I8Geglu; }
 // tiles 9 / 14 / 17: the code's wave count (decode_plan)
 int wstream_waves(int code) { return code == 4 ? 4 : 8; }
 // fp32 slabs of a launch: one per split, one when only `slab` (weight stream, GroupNorm twins) asks for the slab path
@@ -286,6 +288,11 @@ ConvPlan plan_codes(const ConvDesc& d) {
     SD_REQUIRE(conv_fast_path_ok(d) && cw.stream && cw.scale && d.staging >= 0 && d.staging <= 2 && smgemm_i8_shape_ok(d, d.staging), kInvalidArgument,
                "plan tile 19 (smgemm_i8.hip, int8) needs the int8 weights, the scales and a single-source shape of the small-M GEMM with K <= %d "
                "(k=%d C0=%d C1=%d N=%d M=%d mode=%d)", kSmI8MaxK, d.ksize, d.C0, d.x1 ? d.C1 : 0, d.N, d.B * d.Ho * d.Wo, d.out_mode);
+  // (nor has an int8 GEGLU descriptor: tile 20 takes it or nobody does)
+  if (i8_geglu(d))
+    SD_REQUIRE(conv_fast_path_ok(d) && cw.stream && cw.scale && d.staging >= 0 && d.staging <= 2 && smgeglu_i8_shape_ok(d, d.staging), kInvalidArgument,
+               "plan tile 20 (smgeglu_i8.hip, int8) needs the int8 weights, the scales and an un-folded shape of the GEGLU kernel with K <= %d "
+               "(k=%d C0=%d C1=%d N=%d M=%d mode=%d ln=%d)", kSmI8MaxK, d.ksize, d.C0, d.x1 ? d.C1 : 0, d.N, d.B * d.Ho * d.Wo, d.out_mode, d.ln_colsum ? 1 : 0);
   if (!conv_fast_path_ok(d)) return ConvPlan{-1, 0, 1, false, 0};
   // a compressed weight source, in front of the tuner candidate, the tables and every rule: nothing moves it
   switch (cw.kind) {
@@ -323,6 +330,8 @@ ConvPlan plan_codes(const ConvDesc& d) {
                  "plan tile 16 (smgeglu.hip, palettized) needs the index stream, the LUT, the norm weight with the LayerNorm fold and a shape of "
                  "the GEGLU kernel with 128-row tiles");
       return ConvPlan{16, 1, 1, false, 0};
+    case WeightSource::I8Geglu:   // the code of tile 13 in, the resolved tile height out; no split-K, no slab, no workspace (checked above)
+      return ConvPlan{20, smgeglu_bm(d, d.staging) == 128 ? 1 : 2, 1, false, 0};
   }
   const Switches& sw = switches();
   // the library's own rules for tiles 10-13 apply where nothing else was asked for (a tuner candidate in force also keeps them off)
@@ -380,7 +389,7 @@ ConvPlan plan_codes(const ConvDesc& d) {
 //   tile 7:    0 / 2 / 3 / 4 / 5 = 2 / 3 / 4 / 6 / 8 weight stages; GroupNorm in the loader: 4 stages from code 3 where its table fits, else 3
 //   tile 18:   tile 7's codes; the int8 kernel has rings of 2 / 3 / 4 stages, a deeper code runs the 4-stage one
 //   tiles 9 / 14 / 17: 4 = four waves per workgroup, anything else eight      tile 11: 1-6 = the variant, anything else the library's choice
-//   tiles 12 / 15 / 19 / 13 / 16: 1 / 2 = the lower / higher tile (32 / 64, 128 / 256 rows), 0 = by the shape
+//   tiles 12 / 15 / 19 / 13 / 16 / 20: 1 / 2 = the lower / higher tile (32 / 64, 128 / 256 rows), 0 = by the shape
 void decode_plan(const ConvDesc& d, ConvPlan& p) {
   const Dims a = dims_of(d);
   int code = p.staging;
@@ -399,8 +408,8 @@ void decode_plan(const ConvDesc& d, ConvPlan& p) {
       p.kernel = p.tile == 12 ? ConvKernel::Smgemm : p.tile == 15 ? ConvKernel::SmgemmPal : ConvKernel::SmgemmI8;
       p.bm = code >= 0 && code <= 2 ? smgemm_bm(d, code) : 0;   // (0: no such tile - the launcher refuses it)
       return;
-    case 13: case 16:
-      p.kernel = p.tile == 13 ? ConvKernel::Smgeglu : ConvKernel::SmgegluPal;
+    case 13: case 16: case 20:
+      p.kernel = p.tile == 13 ? ConvKernel::Smgeglu : p.tile == 16 ? ConvKernel::SmgegluPal : ConvKernel::SmgegluI8;
       p.bm = code >= 0 && code <= 2 ? smgeglu_bm(d, code) : 0;
       return;
     default: break;
@@ -478,6 +487,7 @@ std::string conv_plan_kernel_name(const ConvPlan& p) {
     case ConvKernel::SmgemmI8: return "smgemm_i8 bm" + std::to_string(p.bm);
     case ConvKernel::Smgeglu: return "smgeglu bm" + std::to_string(p.bm);
     case ConvKernel::SmgegluPal: return "smgeglu_pal bm" + std::to_string(p.bm);
+    case ConvKernel::SmgegluI8: return "smgeglu_i8 bm" + std::to_string(p.bm);
     default: return "generic";
   }
 }
@@ -489,7 +499,7 @@ std::string conv_plan_kernel_name(const ConvPlan& p) {
 //   - with the weight-stream copy present, its slab count at four waves per workgroup (the most slabs it writes);
 //   - the unresolved split-K (the launch may use fewer splits), one slab when only the GroupNorm twins ask for it.
 size_t conv_workspace_bytes(const ConvDesc& d) {
-  if (!conv_fast_path_ok(d) || pal_gemm(d) || pal_geglu(d) || i8_gemm(d)) return 0;   // (tiles 15 / 16 / 19: no slabs)
+  if (!conv_fast_path_ok(d) || pal_gemm(d) || pal_geglu(d) || i8_gemm(d) || i8_geglu(d)) return 0;   // (tiles 15 / 16 / 19 / 20: no slabs)
   const Dims a = dims_of(d);
   const Plan p = choose_plan(d, a);
   int splits = (switches().tuning && can_split(d)) ? std::max(p.splitk, 16) : p.splitk;
@@ -537,6 +547,7 @@ WeightPin conv_plan_pin(WeightSource kind, int n) {
     case WeightSource::PalGemm: return {kind, 15, n == 32 ? 1 : n == 64 ? 2 : 0};
     case WeightSource::I8Gemm: return {kind, 19, n == 32 ? 1 : n == 64 ? 2 : 0};
     case WeightSource::PalGeglu: return {kind, 16, n == 128 ? 1 : n == 256 ? 2 : 0};
+    case WeightSource::I8Geglu: return {kind, 20, n == 128 ? 1 : n == 256 ? 2 : 0};
     default: return {};
   }
 }
@@ -550,6 +561,14 @@ WeightPin conv_plan_weights(const ConvDesc& d, StoredWeights held, bool opt_in) 
   if (one_by_one && d.out_mode == kOutGeglu && sw.smgeglu) {   // tile 13, on the 128-row tiles the palettized kernel has
     const ConvPlan p = fp16_plan(d, conv_plan_copies(d));
     if (p.kernel == ConvKernel::Smgeglu && smgeglu_pal_shape_ok(d, 0)) return conv_plan_pin(WeightSource::PalGeglu, p.bm);
+  }
+  // tile 13 at either tile height, for the int8 kernel that reads the LayerNorm's int8 output: asked with the fold's fields (the fp16
+  // plan of the call site) or without them - the answer's descriptor never carries them
+  if (opt_in && held == StoredWeights::W8A8 && d.ksize == 1 && !d.x1 && d.out_mode == kOutGeglu && sw.smgeglu) {
+    const ConvPlan p = fp16_plan(d, conv_plan_copies(d));
+    ConvDesc plain = d;
+    plain.ln_colsum = nullptr;
+    if (p.kernel == ConvKernel::Smgeglu && smgeglu_i8_shape_ok(plain, p.bm == 128 ? 1 : 2)) return conv_plan_pin(WeightSource::I8Geglu, p.bm);
   }
   // tile 9 with the fragment-major copy present: its wave count, i.e. its slab count
   if (sw.wstream && !d.ln_colsum && plan_is_wstream(d)) {
@@ -622,7 +641,7 @@ void conv_plan_log(const ConvDesc& d, const ConvPlan& p, int n_fast) {
   else if (p.tile == 15 || p.tile == 16)
     fprintf(stderr, "[sd conv] k1 s1 up1 C0=%d C1=%d M=%d N=%d K=%d mode=%d tile=%d bm=%d n_fast=%d bits=%d\n", d.C0, c1, a.M, a.N, a.K, d.out_mode,
             p.tile, p.bm, n_fast, d.cw.bits);
-  else if (p.tile == 19)
+  else if (p.tile == 19 || p.tile == 20)
     fprintf(stderr, "[sd conv] k1 s1 up1 C0=%d C1=%d M=%d N=%d K=%d mode=%d tile=%d bm=%d n_fast=%d bits=8\n", d.C0, c1, a.M, a.N, a.K, d.out_mode, p.tile,
             p.bm, n_fast);
   else if (p.tile == 18)

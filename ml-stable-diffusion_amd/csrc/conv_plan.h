@@ -8,8 +8,8 @@
 
 namespace sd {
 
-// the kernel a plan launches (tile -1 / 1-4 / 7 / 18 / 9 / 14 / 17 / 10 / 11 / 12 / 15 / 19 / 13 / 16 of the wire format below)
-enum class ConvKernel { Generic, Igemm, GemmPipe, HaloKs, HaloI8, Wstream, WstreamPal, WstreamI8, Wsgemm, Bvgemm, Smgemm, SmgemmPal, SmgemmI8, Smgeglu, SmgegluPal };
+// the kernel a plan launches (tile -1 / 1-4 / 7 / 18 / 9 / 14 / 17 / 10 / 11 / 12 / 15 / 19 / 13 / 16 / 20 of the wire format below)
+enum class ConvKernel { Generic, Igemm, GemmPipe, HaloKs, HaloI8, Wstream, WstreamPal, WstreamI8, Wsgemm, Bvgemm, Smgemm, SmgemmPal, SmgemmI8, Smgeglu, SmgegluPal, SmgegluI8 };
 
 struct ConvPlan {
   // The wire format: what ConvDesc::tile / staging pins, tuned_convs.inc rows, SD_PLAN_TABLE and sd_tune_set_candidate say and what
@@ -18,7 +18,9 @@ struct ConvPlan {
                    // 10: wsgemm.hip, 11: bvgemm.hip, 12: smgemm.hip, 13: smgeglu.hip, 14: wstream.hip from palettized weights,
                    // 15: smgemm.hip from palettized weights, 17: wstream.hip from int8 weights and activations (W8A8),
                    // 18: the halo conv from int8 weights and activations (conv3x3_halo_i8.hip; never the library's own answer),
-                   // 19: the small-M GEMM from int8 weights and activations (smgemm_i8.hip, tile 12's tiles; never the library's own answer);
+                   // 19: the small-M GEMM from int8 weights and activations (smgemm_i8.hip, tile 12's tiles; never the library's own answer),
+                   // 20: the GEGLU projection from int8 weights and int8 activations written by the LayerNorm in front of it
+                   // (smgeglu_i8.hip, tile 13's tiles at both heights; never the library's own answer);
                    // -1 = not on the MFMA path (launch_conv_generic)
   int staging;     // per-family code: decode_plan
   int splitk;      // resolved: what the launch runs, no empty splits (halo: over 64-channel chunks; tile 9: the slab count)
@@ -54,7 +56,9 @@ ConvWeightCopies conv_plan_copies(const ConvDesc& d);
 //   W8A8:    the weight stream (tile 17) by tile 14's predicate, then the halo conv (tile 18 for tile 7 without the GroupNorm loader,
 //            with that plan's ring code and split-K; Ctot <= kHaloI8MaxCtot), then the opted-in single-source small-M GEMM (tile 19 for
 //            tile 12: tile 15's predicate; K <= kSmI8MaxK holds wherever tile 12 is the library's rule); an observing store asks this
-//            without holding a mark, with the call site's consent only when it observes the projections too
+//            without holding a mark, with the call site's consent only when it observes the projections too.  In front of all of
+//            them, as the palette branch does for tile 16: the opted-in GEGLU (tile 20 for tile 13 at the same tile height, both
+//            heights) - asked WITHOUT the LayerNorm fold's fields, which tile 20 does not take (the caller un-folds: UNet::transformer_block)
 enum class StoredWeights { Fp16, Palette, W8A8 };
 struct WeightPin {
   WeightSource kind = WeightSource::Fp16;
@@ -72,7 +76,8 @@ void conv_plan_log(const ConvDesc& d, const ConvPlan& p, int n_fast = 0);
 // What launches, as one line (sd_op_conv_plan_kernel): the kernel's name, then only the fields that kernel has -
 //   "igemm <bm>x<bn> ring<stages>[ kg2][ regs]"    "gemm_pipe <bm>x<bn> ring<stages>"    "halo_ks ring<stages>"    "halo_i8 ring<stages>"
 //   "wstream waves<n>"   "wstream_pal waves<n>"    "wstream_i8 waves<n>"                 "wsgemm"    "bvgemm v<variant>"
-//   "smgemm bm<bm>"      "smgemm_pal bm<bm>"       "smgemm_i8 bm<bm>"                    "smgeglu bm<bm>"    "generic"
+//   "smgemm bm<bm>"      "smgemm_pal bm<bm>"       "smgemm_i8 bm<bm>"                    "smgeglu bm<bm>"    "smgeglu_pal bm<bm>"
+//   "smgeglu_i8 bm<bm>"  "generic"
 std::string conv_plan_kernel_name(const ConvPlan& p);
 
 // Tile order inside an XCD's run of workgroup ids, from an estimate of the bytes each order pulls through the fabric into the 8 XCD L2s:
@@ -119,5 +124,6 @@ static_assert(127LL * 127 * 9 * kHaloI8MaxCtot < (1LL << 31) && 127LL * 127 * 9 
 // smgemm_i8_kernel (plan tile 19) sums the whole K of a 1x1 GEMM in int32: 127 * 127 * K < 2^31, the last multiple of 64 that fits
 constexpr int kSmI8MaxK = 133120;
 static_assert(127LL * 127 * kSmI8MaxK < (1LL << 31) && 127LL * 127 * (kSmI8MaxK + 64) >= (1LL << 31), "int32 bound of plan tile 19");
+// (smgeglu_i8_kernel, plan tile 20, sums the whole K of its 1x1 GEMM the same way: the same bound)
 
 }  // namespace sd

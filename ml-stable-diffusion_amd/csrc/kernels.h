@@ -38,7 +38,9 @@ struct GnTwin {
 //   I8Wstream   tile 17, wstream.hip  wstream_kernel NBITS = kWsI8 (W8A8)   stream of wstream_i8_pack   staging: tile 9's code
 //   I8Halo      tile 18, conv3x3_halo_i8.hip  conv3x3_halo_i8_kernel (W8A8)   stream of halo_i8_pack      staging: tile 7's code
 //   I8Gemm      tile 19, smgemm_i8.hip        smgemm_i8_kernel (W8A8)         stream of smgemm_i8_pack    staging: tile 12's code (0 = by M)
-enum class WeightSource { Fp16, PalWstream, PalGemm, PalGeglu, I8Wstream, I8Halo, I8Gemm };
+//   I8Geglu     tile 20, smgeglu_i8.hip       smgeglu_i8_kernel (W8A8)        stream of smgeglu_i8_pack   staging: tile 13's code (0 = by the grid);
+//               the activations arrive quantized (ConvDesc::x0_i8, written by launch_layernorm_q8)
+enum class WeightSource { Fp16, PalWstream, PalGemm, PalGeglu, I8Wstream, I8Halo, I8Gemm, I8Geglu };
 struct CompressedWeights {
   WeightSource kind = WeightSource::Fp16;
   const void* stream = nullptr;
@@ -48,19 +50,21 @@ struct CompressedWeights {
   // PalGeglu with the LayerNorm fold (ConvDesc::ln_colsum set): the fp32 norm weight [C0] - the kernel multiplies every LUT value by it
   // as fold_layernorm_rows does on the host; null without the fold
   const float* ln_gamma = nullptr;
-  // I8Wstream / I8Halo / I8Gemm: the output scale per column scale[n] = fp32(s_a * s_w[n]) and inv_s = fp32(1 / s_a), the factor the kernel quantizes
-  // its activations by
+  // I8Wstream / I8Halo / I8Gemm / I8Geglu: the output scale per column scale[n] = fp32(s_a * s_w[n]) (I8Geglu: rows in the interleaved
+  // order of the GEGLU upload, geglu_row) and inv_s = fp32(1 / s_a), the factor the kernel - for I8Geglu the LayerNorm in front of it -
+  // quantizes its activations by
   const float* scale = nullptr;
   float inv_s = 0.f;
   bool palettized() const { return kind == WeightSource::PalWstream || kind == WeightSource::PalGemm || kind == WeightSource::PalGeglu; }
   const uint8_t* pal() const { return palettized() ? static_cast<const uint8_t*>(stream) : nullptr; }
-  bool int8() const { return kind == WeightSource::I8Wstream || kind == WeightSource::I8Halo || kind == WeightSource::I8Gemm; }
+  bool int8() const { return kind == WeightSource::I8Wstream || kind == WeightSource::I8Halo || kind == WeightSource::I8Gemm || kind == WeightSource::I8Geglu; }
   const int8_t* i8() const { return int8() ? static_cast<const int8_t*>(stream) : nullptr; }
 };
 
 struct ConvDesc {
   const half_t* x0 = nullptr;   // [B][Hi][Wi][C0]
   const half_t* x1 = nullptr;   // optional second source (channel concat), [B][Hi][Wi][C1]
+  const int8_t* x0_i8 = nullptr;   // cw of kind I8Geglu: the source as int8 [M][C0], quantized by its producer (launch_layernorm_q8); x0 is not read
   int C0 = 0, C1 = 0;
   const half_t* w = nullptr;    // [N][K] K-major, K = ksize*ksize*(C0+C1), tap-major
   const float* bias = nullptr;  // [N] or null
@@ -213,6 +217,10 @@ size_t smgeglu_prof_entries(const ConvDesc& d, int variant);          // this ma
 // decoded into the weight rows of the same stages in front of the same MFMAs, so the output is bit-identical to launch_smgeglu's on the folded fp16 weights.  128-row tiles only, C0 <= 2560, no phase clocks.
 bool smgeglu_pal_shape_ok(const ConvDesc& d, int variant);            // variant 0 / 1 resolving to 128-row tiles
 void launch_smgeglu_pal(const ConvDesc& d, const ConvPlan& p, hipStream_t s);
+// smgeglu_i8.hip: the projection WITHOUT the fold on the same tiles from int8 weights and int8 activations (W8A8, plan tile 20: d.cw of
+// kind I8Geglu, d.x0_i8) - exact int32 sums, scale and bias in fp32, then tile 13's v * gelu_erf(g); both tile heights, K <= kSmI8MaxK
+bool smgeglu_i8_shape_ok(const ConvDesc& d, int variant);             // smgeglu_shape_ok, no fold, inside the int32 bound
+void launch_smgeglu_i8(const ConvDesc& d, const ConvPlan& p, hipStream_t s);
 
 // calib.hip: box calibration for bench.py - out[0..6] = copy GB/s, dense MFMA TFLOP/s, us per launch of a 323-launch empty
 // graph, us per launch of a 323-launch chain of short kernels on cold operands, us per launch of a 323-launch chain handing 8 MB
@@ -402,6 +410,9 @@ void launch_safety_head(const float* image_embeds, const float* concept_embeds, 
 // K6/K7: norms (norm.hip)
 // ---------------------------------------------------------------------------------------------
 // y[m][:] = (x[m][:]-mean)*rstd * w + b over the channel dim (LayerNormANE, layer_norm.py:51-80)
+// the same LayerNorm leaving as int8 [M][C]: xq = ws_quantize8(fp16 value launch_layernorm stores, inv_s) (quantize8.h); w == b == NULL:
+// xq = ws_quantize8(x, inv_s), nothing normalised.  Same shape rule; xq 8-byte aligned.
+void launch_layernorm_q8(const half_t* x, const float* w, const float* b, int8_t* xq, int M, int C, float eps, float inv_s, hipStream_t s);
 void launch_layernorm(const half_t* x, const float* w, const float* b, half_t* y, int M, int C, float eps,
                       hipStream_t s);
 // GroupNorm over NHWC with optional channel-concat second source: deterministic two-pass

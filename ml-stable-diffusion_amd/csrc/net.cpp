@@ -117,6 +117,23 @@ WeightPin Net::weight_plan(const std::string& name, const Tensor& x, const ConvA
   return conv_plan_weights(d, held, a.keep_compressed);
 }
 
+bool Net::observes_geglu(const std::string& name, const Tensor& x, const ConvArgs& a, bool ln) const {
+  if (f32_ || !ws_->observe() || !ws_->observe_geglus() || ws_->palette(name + ".weight") || a.out_mode != kOutGeglu) return false;
+  ConvDesc d = conv_shape(name, x, a);
+  static const float present = 0.f;   // the planner only tests the pointers
+  if (ln) d.ln_colsum = d.bias = &present;
+  return conv_plan_weights(d, StoredWeights::W8A8, a.keep_compressed).kind == WeightSource::I8Geglu;
+}
+
+void Net::observe_tensor(std::vector<Op>& ops, const std::string& name, const Tensor& t) {
+  float* slot = ll_.arena.alloc_n<float>(1);   // (the arena is zeroed: the running maximum starts at 0)
+  observed_.push_back({name + ".weight", slot});
+  const half_t* p0 = t.p;
+  const size_t n0 = t.numel();
+  ops.push_back([=](hipStream_t s) { launch_absmax_half(p0, n0, nullptr, 0, slot, s); });
+  ops.back().label = "absmax " + name;
+}
+
 ConvWeights Net::upload_compressed(const std::string& name, const WeightPin& pin, int cin, const ConvArgs& a, const std::string& ln_name) {
   const std::string wname = name + ".weight";
   const size_t expect = (size_t)a.cout * cin * a.k * a.k;
@@ -127,7 +144,8 @@ ConvWeights Net::upload_compressed(const std::string& name, const WeightPin& pin
   };
   size_t bytes = 0;
   CompressedWeights cw;
-  if (pin.kind == WeightSource::I8Wstream || pin.kind == WeightSource::I8Halo || pin.kind == WeightSource::I8Gemm) {   // q in the kernel's layout, cs[n], inv_s: no fp16 copy
+  if (pin.kind == WeightSource::I8Wstream || pin.kind == WeightSource::I8Halo || pin.kind == WeightSource::I8Gemm ||
+      pin.kind == WeightSource::I8Geglu) {   // q in the kernel's layout, cs[n], inv_s: no fp16 copy
     const W8A8Mark* i8 = ws_->w8a8(wname);
     SD_REQUIRE(i8 && ws_->get(wname).numel() == expect && i8->q.size() == expect && i8->w_scale.size() == (size_t)a.cout, kInvalidArgument,
                "%s: expected %zu W8A8 values (%d,%d,%d,%d)", wname.c_str(), expect, a.cout, cin, a.k, a.k);
@@ -220,6 +238,7 @@ ConvDesc Net::conv_shape(const std::string& name, const Tensor& x, const ConvArg
   d.out_mode = a.out_mode;
   d.ldT = a.ldT;
   d.ln_colsum = a.ln_colsum;
+  d.x0_i8 = a.x_i8;
   if (ln) {
     d.vt_perm = a.vt_perm ? 1 : 0;
     d.q_scale = a.q_scale;
@@ -306,7 +325,7 @@ Tensor Net::conv_w(std::vector<Op>& ops, const std::string& name, const ConvWeig
   // trailing "#kind,ksize,stride,up,Ctot,N,M" is the plan-table key of this op (tools/tune_plans.py)
   const int kind = d.out_t ? 3 : (geglu ? 2 : (ln ? 1 : 0));
   // the weight source in the label: "[+ln]+pal<bits>" from a palette (plan tile 14 or 15), "geglu+pal<bits>[+ln]" for plan tile 16,
-  // "+w8a8" from int8 weights and quantized activations (plan tiles 17 / 18 / 19)
+  // "+w8a8" from int8 weights and quantized activations (plan tiles 17 / 18 / 19 / 20)
   const WeightSource src = d.cw.kind;
   const std::string lnmark = ln ? "+ln" : "", palmark = "+pal" + std::to_string(d.cw.bits);
   const std::string mark = src == WeightSource::PalGeglu ? palmark + lnmark : lnmark + (d.cw.i8() ? "+w8a8" : src != WeightSource::Fp16 ? palmark : "");

@@ -76,6 +76,9 @@ struct ConvArgs {
   // statistics, so only call sites whose output feeds no GroupNorm set it (proj_in, the two to_out.0 and ff.net.0.proj of a transformer
   // block feed LayerNorms or GEMMs).
   bool keep_compressed = false;
+  // conv_w only - the source as int8 [M][C], written by a layernorm_q8 launch in front of this op (plan tile 20 reads nothing else; x
+  // still gives the shape)
+  const int8_t* x_i8 = nullptr;
 };
 
 // The weights conv_w runs from: an fp16 matrix on the device, or a compressed source with its pin (Net::upload_compressed)
@@ -138,6 +141,11 @@ class Net {
   // stream and scales) and keeps the handle's counters; an Fp16 answer goes through upload_conv_weight as ever
   WeightPin weight_plan(const std::string& name, const Tensor& x, const ConvArgs& a, bool ln) const;
   ConvWeights upload_compressed(const std::string& name, const WeightPin& pin, int cin, const ConvArgs& a, const std::string& ln_name = std::string());
+  // Calibration of the GEGLU projections (WeightStore::observe_geglus while the store observes): would a W8A8 mark on <name>.weight
+  // make this GEGLU run as plan tile 20?  Then the caller normalises the GEGLU's input into a scratch tensor and observe_tensor puts
+  // an absmax launch over it, into a slot named <name>.weight - two ordinary launches that write nothing the model reads.
+  bool observes_geglu(const std::string& name, const Tensor& x, const ConvArgs& a, bool ln) const;
+  void observe_tensor(std::vector<Op>& ops, const std::string& name, const Tensor& t);
   // 3x3 conv to N <= 8 channels, one wavefront per pixel (conv_small.hip): fp32 NCHW into out_nchw (a model's boundary), else
   // fp16 NHWC into out_nhwc.  An fp32 handle runs the fp32 conv into out_nhwc (or a tensor of its own) and transposes.
   void conv_small_n(std::vector<Op>& ops, const std::string& name, const Tensor& x, int cout, half_t* out_nhwc, float* out_nchw);

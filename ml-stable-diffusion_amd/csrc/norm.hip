@@ -16,6 +16,7 @@
 #include <cstdlib>
 
 #include "kernels.h"
+#include "quantize8.h"
 
 namespace sd {
 namespace {
@@ -29,9 +30,15 @@ __device__ __forceinline__ float wave_sum(float v) {
 // partial layout [B][G][kGnMaxSlabs][2] (kernels.h); entries >= the producer's count are ignored by the fold
 constexpr int LN_MAX_CHUNKS = 4;   // C <= 64 lanes * 4 chunks * 8 = 2048
 
-__global__ __launch_bounds__(256) void layernorm_kernel(const half_t* __restrict__ x, const float* __restrict__ w,
-                                                        const float* __restrict__ b, half_t* __restrict__ y, int M,
-                                                        int C, float eps) {
+// One token row per wavefront: mean, variance, affine and the one rounding to fp16 of LayerNormANE - the body of layernorm_kernel and
+// of layernorm_q8_kernel, which hands every finished 8-channel chunk (channel chunk ch of the row, fp16 values o) to `store`, so the
+// tensor the second one quantizes is bit for bit the tensor the first one writes.  PIN_F32: the fp32 value of the affine is pinned in a
+// register in front of its rounding to fp16.  layernorm_kernel rounds twice (v_pk_fma_f32, then v_cvt_pk_f16_f32) and its code stays
+// as it is; beside a quantizer hipcc fuses the same text into v_fma_mixlo_f16, ONE rounding of the exact fma, which differs from the
+// stored value in the last bit of about one element in 10^4 (seen on the device) - the pin keeps the two roundings.
+template <bool PIN_F32, class Store>
+__device__ __forceinline__ void layernorm_row(const half_t* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b, int M,
+                                              int C, float eps, Store&& store) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= M) return;
@@ -68,17 +75,42 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const half_t* __restrict
     }
   }
   const float rstd = rsqrtf(wave_sum(sq) / (float)C + eps);
-  half_t* yr = y + (size_t)row * C;
 #pragma unroll
   for (int i = 0; i < LN_MAX_CHUNKS; ++i) {
     const int ch = lane + 64 * i;
     if (ch < nchunk) {
       half8 o;
 #pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] = (half_t)((v[i][e] - mean) * rstd * w[ch * 8 + e] + b[ch * 8 + e]);
-      *reinterpret_cast<half8*>(yr + ch * 8) = o;
+      for (int e = 0; e < 8; ++e) {
+        float f = (v[i][e] - mean) * rstd * w[ch * 8 + e] + b[ch * 8 + e];
+        if constexpr (PIN_F32) asm volatile("" : "+v"(f));
+        o[e] = (half_t)f;
+      }
+      store(row, ch, o);
     }
   }
+}
+
+__global__ __launch_bounds__(256) void layernorm_kernel(const half_t* __restrict__ x, const float* __restrict__ w,
+                                                        const float* __restrict__ b, half_t* __restrict__ y, int M,
+                                                        int C, float eps) {
+  layernorm_row<false>(x, w, b, M, C, eps, [=](int row, int ch, const half8& o) { *reinterpret_cast<half8*>(y + (size_t)row * C + ch * 8) = o; });
+}
+
+// LayerNorm whose output leaves as int8 (W8A8, in front of plan tile 20): xq = ws_quantize8(y, inv_s), y the fp16 chunk layernorm_kernel
+// would store - 8 B per 8 channels, one vector store.  w == b == NULL: no normalisation, xq = ws_quantize8(x, inv_s).
+__global__ __launch_bounds__(256) void layernorm_q8_kernel(const half_t* __restrict__ x, const float* __restrict__ w,
+                                                           const float* __restrict__ b, int8_t* __restrict__ xq, int M, int C, float eps,
+                                                           float inv_s) {
+  auto store = [=](int row, int ch, const half8& o) { *reinterpret_cast<uintx2*>(xq + (size_t)row * C + ch * 8) = ws_quantize8(o, inv_s); };
+  if (w) {
+    layernorm_row<true>(x, w, b, M, C, eps, store);
+    return;
+  }
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= M) return;
+  for (int ch = lane; ch < (C >> 3); ch += 64) store(row, ch, *reinterpret_cast<const half8*>(x + (size_t)row * C + ch * 8));
 }
 
 // Pass 1, grid (pixel slabs, B): deterministic partial (sum, sumsq) per (sample, slab, group).
@@ -248,6 +280,14 @@ void launch_layernorm(const half_t* x, const float* w, const float* b, half_t* y
                       hipStream_t s) {
   SD_REQUIRE(C % 8 == 0 && C <= 64 * 8 * LN_MAX_CHUNKS, kUnsupported, "layernorm: C=%d (need C %% 8 == 0, C <= 2048)", C);
   hipLaunchKernelGGL(layernorm_kernel, dim3(cdiv(M, 4)), dim3(256), 0, s, x, w, b, y, M, C, eps);
+  SD_HIP(hipGetLastError());
+}
+
+void launch_layernorm_q8(const half_t* x, const float* w, const float* b, int8_t* xq, int M, int C, float eps, float inv_s, hipStream_t s) {
+  SD_REQUIRE(C % 8 == 0 && C <= 64 * 8 * LN_MAX_CHUNKS, kUnsupported, "layernorm_q8: C=%d (need C %% 8 == 0, C <= 2048)", C);
+  SD_REQUIRE((w == nullptr) == (b == nullptr) && reinterpret_cast<uintptr_t>(xq) % 8 == 0, kInvalidArgument,
+             "layernorm_q8: weight and bias go together, the int8 rows are stored 8 bytes at a time");
+  hipLaunchKernelGGL(layernorm_q8_kernel, dim3(cdiv(M, 4)), dim3(256), 0, s, x, w, b, xq, M, C, eps, inv_s);
   SD_HIP(hipGetLastError());
 }
 

@@ -331,9 +331,29 @@ Tensor UNet::transformer_block(std::vector<Op>& ops, const std::string& b, const
   Tensor g;
   // A palettized ff.net.0.proj whose plan is smgeglu.hip on 128-row tiles stays palettized (plan tile 16): stream, LUT and - with the
   // fold - norm3.weight go up, colsum and the folded bias come from lut[indices] as ever, no fp16 matrix is uploaded
-  if (can_fold_ln(h2, 8 * C, true)) {
-    ConvArgs ga{.cout = 8 * C, .out_mode = kOutGeglu, .keep_compressed = true};
-    const WeightPin pin = weight_plan(b + ".ff.net.0.proj", h2, ga, true);
+  // A W8A8-marked ff.net.0.proj whose fp16 plan is smgeglu.hip runs as plan tile 20, folded or not: norm3 is NOT folded - one
+  // layernorm_q8 launch writes int8(norm3(h2)), the tensor the reference calibrates and quantizes, and the GEGLU streams it with the raw
+  // bias.  An observing store (observe_geglus) leaves the GEGLU as it is and puts a LayerNorm + absmax pair over the same tensor.
+  const std::string gname = b + ".ff.net.0.proj";
+  const bool fold3 = can_fold_ln(h2, 8 * C, true);
+  ConvArgs ga{.cout = 8 * C, .out_mode = kOutGeglu, .keep_compressed = true};
+  const WeightPin gpin = weight_plan(gname, h2, ga, fold3);
+  if (observes_geglu(gname, h2, ga, fold3)) observe_tensor(ops, gname, layer_norm(ops, b + ".norm3", h2));
+  if (gpin.kind == WeightSource::I8Geglu) {
+    const ConvWeights gw = upload_compressed(gname, gpin, C, ga);
+    const float* gb = ws_->has(gname + ".bias") ? upload_vec(gname + ".bias", 8 * C, true) : nullptr;
+    const float* nw = upload_vec(b + ".norm3.weight", C);
+    const float* nb = upload_vec(b + ".norm3.bias", C);
+    const int M = h2.M();
+    int8_t* xq = ll_.arena.alloc_n<int8_t>((size_t)M * C);
+    const half_t* xp = h2.p;
+    const float inv_s = gw.cw.inv_s;
+    ops.push_back([=](hipStream_t s) { launch_layernorm_q8(xp, nw, nb, xq, M, C, 1e-5f, inv_s, s); });
+    ops.back().label = "layernorm_q8 " + b + ".norm3";
+    ga.x_i8 = xq;
+    g = conv_w(ops, gname, gw, gb, h2, ga);
+  } else if (fold3) {
+    const WeightPin pin = gpin;
     const bool fp16 = pin.kind == WeightSource::Fp16;
     LnFold f = fold_layernorm(b + ".norm3", {b + ".ff.net.0.proj"}, C, 8 * C, true, fp16);
     ga.ln_colsum = f.colsum;

@@ -158,6 +158,19 @@ inline void halo_i8_pack(const int8_t* q, int N, int Ctot, int ksize, int8_t* ds
 // image is applied on the source address.  The layout is stated here once: the function is a copy.  N % 16 == 0, K % 64 == 0.
 inline size_t smgemm_i8_bytes(int N, int K) { return (size_t)N * K; }
 inline void smgemm_i8_pack(const int8_t* q, int N, int K, int8_t* dst) { std::copy(q, q + smgemm_i8_bytes(N, K), dst); }
+// The int8 weights of smgeglu_i8.hip (plan tile 20), q [N2][K] of ff.net.0.proj in the checkpoint's row order (rows 0 .. N2 / 2 - 1 the
+// values, the rest the gates), N2 % 32 == 0, K % 64 == 0: [N2 / 16 strips][16 rows][K] - strip 2 U + v holds the checkpoint rows
+// v * N2 / 2 + 16 U + (0 .. 15), the 16 value (v = 0) or gate (v = 1) rows of the output's 16-column unit U: the strip order of
+// smgeglu_pal_pack at one byte per weight, rows whole.  A tile of 80 output columns reads the ten consecutive strips 10 n_tile ..
+// 10 n_tile + 9, each stage 64 contiguous bytes of every row.  Bytes: N2 * K.
+inline size_t smgeglu_i8_bytes(int N2, int K) { return (size_t)N2 * K; }
+inline void smgeglu_i8_pack(const int8_t* q, int N2, int K, int8_t* dst) {
+  for (int strip = 0; strip < N2 / 16; ++strip)
+    for (int i = 0; i < 16; ++i) {
+      const int o = (strip & 1) * (N2 / 2) + 16 * (strip >> 1) + i;   // checkpoint row
+      std::copy(q + (size_t)o * K, q + (size_t)(o + 1) * K, dst + ((size_t)strip * 16 + i) * K);
+    }
+}
 // What an upload of a W8A8 conv starts from (sd_op_conv2d_w8a8 / _halo, sd_op_gemm_w8a8, Net::conv), checked in the order the header lists: act_absmax, finite
 // positive scales, no value of -128 (the symmetric scheme has none); the packed stream, cs[n] = fp32(s_a * s_w[n]) with s_a = act_absmax / 127, and inv_s = fp32(1 / s_a).
 struct W8A8HostCopy {
@@ -167,22 +180,24 @@ struct W8A8HostCopy {
 };
 inline bool w8a8_absmax_ok(float act_absmax) { return std::isfinite(act_absmax) && act_absmax > 0.f; }
 inline W8A8HostCopy w8a8_host_copy(const char* what, const int8_t* q, const float* w_scale, float act_absmax, int N, int Ctot, int ksize,
-                                   WeightSource kind = WeightSource::I8Wstream) {   // one of the three int8 kinds
+                                   WeightSource kind = WeightSource::I8Wstream) {   // one of the four int8 kinds
   SD_REQUIRE(w8a8_absmax_ok(act_absmax), kInvalidArgument, "%s: act_absmax = %g, not a positive finite number", what, (double)act_absmax);
   const size_t n_el = wstream_i8_bytes(N, Ctot, ksize);
   W8A8HostCopy h;
   const float s_a = act_absmax / 127.0f;
   h.inv_s = 1.0f / s_a;
   SD_REQUIRE(std::isfinite(h.inv_s) && h.inv_s > 0.f, kInvalidArgument, "%s: act_absmax = %g has no finite inverse scale", what, (double)act_absmax);
+  SD_REQUIRE(kind != WeightSource::I8Geglu || N % 64 == 0, kInvalidArgument, "%s: %d GEGLU rows do not interleave in blocks of 32", what, N);
   h.cs.resize(N);
   for (int n = 0; n < N; ++n) {
     SD_REQUIRE(std::isfinite(w_scale[n]) && w_scale[n] > 0.f, kInvalidArgument, "%s: w_scale[%d] = %g, not a positive finite number", what, n, (double)w_scale[n]);
-    h.cs[n] = s_a * w_scale[n];
+    h.cs[kind == WeightSource::I8Geglu ? geglu_row(n, N) : n] = s_a * w_scale[n];   // (GEGLU: where the interleaved bias of row n lies)
   }
   for (size_t i = 0; i < n_el; ++i) SD_REQUIRE(q[i] != -128, kInvalidArgument, "%s: weight value -128 at element %zu, the symmetric range is [-127, 127]", what, i);
   h.stream.resize(n_el);
   if (kind == WeightSource::I8Halo) halo_i8_pack(q, N, Ctot, ksize, h.stream.data());
   else if (kind == WeightSource::I8Gemm) smgemm_i8_pack(q, N, Ctot, h.stream.data());   // (ksize 1)
+  else if (kind == WeightSource::I8Geglu) smgeglu_i8_pack(q, N, Ctot, h.stream.data());
   else wstream_i8_pack(q, N, Ctot, ksize, h.stream.data());
   return h;
 }

@@ -48,6 +48,9 @@ class WeightStore {
   // ... and, while observing, in front of every projection plan tile 19 could take at a call site that consents to a pinned 1x1 kernel
   void set_observe_gemms(bool on) { observe_gemms_ = on; }
   bool observe_gemms() const { return observe_gemms_; }
+  // ... and over the LayerNorm output in front of every GEGLU projection plan tile 20 could take (two launches beside the folded GEGLU)
+  void set_observe_geglus(bool on) { observe_geglus_ = on; }
+  bool observe_geglus() const { return observe_geglus_; }
   void add(const std::string& name, const void* data, int dtype /*0 f16, 1 f32, 2 bf16*/,
            const int64_t* shape, int ndim);
   void load_safetensors(const std::string& path, const std::string& prefix);
@@ -69,6 +72,7 @@ class WeightStore {
   std::map<std::string, W8A8Mark> i8_;
   int observe_ = 0;
   bool observe_gemms_ = false;
+  bool observe_geglus_ = false;
 };
 
 }  // namespace sd

@@ -101,6 +101,7 @@ SYMBOLS = [
     ("sd_weights_w8a8_info", _I, [_P, C.c_char_p, _FP]),
     ("sd_weights_observe_activations", _I, [_P, _I]),
     ("sd_weights_observe_gemms", _I, [_P, _I]),
+    ("sd_weights_observe_geglus", _I, [_P, _I]),
     ("sd_unet_w8a8_info", _I, [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(C.c_size_t)]),
     ("sd_unet_w8a8_layer", _I, [_P, _I, C.c_char_p, _I]),
     ("sd_unet_activation_ranges", _I, [_P, _I, C.c_char_p, _I, _FP]),
@@ -110,6 +111,9 @@ SYMBOLS = [
     ("sd_op_w8a8_pack_halo", _I, [_P, _I, _I, _P, C.POINTER(C.c_size_t)]),
     ("sd_op_gemm_w8a8", _I, [_P, _P, _FP, _F, _FP, _P, _P, _I, _I, _I, _I, _I, _I, C.POINTER(_I), _I, _FP]),
     ("sd_op_w8a8_pack_gemm", _I, [_P, _I, _I, _P, C.POINTER(C.c_size_t)]),
+    ("sd_op_layernorm_q8", _I, [_P, _FP, _FP, _F, _F, _P, _I, _I, _I, _FP]),
+    ("sd_op_geglu_w8a8", _I, [_P, _P, _FP, _F, _FP, _P, _I, _I, _I, _I, C.POINTER(_I), _I, _FP]),
+    ("sd_op_w8a8_pack_geglu", _I, [_P, _I, _I, _P, C.POINTER(C.c_size_t)]),
     ("sd_op_quantize_weight", _I, [_FP, _I, C.c_size_t, _P, _FP, C.POINTER(C.c_double)]),
     ("sd_op_absmax", _I, [_P, C.c_size_t, _FP]),
     ("sd_unet_create", _I, [C.POINTER(UNetConfig), _P, _I, C.POINTER(_P)]),
@@ -626,6 +630,63 @@ def w8a8_pack_gemm(wq):
         raise ValueError("w8a8_pack_gemm: wq must be (Cout, K)")
     Cout, K = wq.shape
     return _packed(lib().sd_op_w8a8_pack_gemm, ptr(wq), Cout, K).view(np.int8).reshape(Cout, K)
+
+
+def layernorm_q8(x, ln_weight, ln_bias, act_absmax, eps=1e-5, out=None, iters=1):
+    """LayerNorm that leaves as int8 (sd_op_layernorm_q8): x (M, C) float16 token-major, ln_weight / ln_bias (C,) f32 or both None (a
+    plain quantize of x), act_absmax the range the output is quantized with.  ``out``: a C-contiguous int8 buffer of at least M * C
+    elements to write into (tests put guards behind it).  Returns (xq (M, C) int8, ms)."""
+    x = f16(x)
+    if x.ndim != 2 or (ln_weight is None) != (ln_bias is None):
+        raise ValueError("layernorm_q8: x must be (M, C); ln_weight and ln_bias go together")
+    M, Cc = x.shape
+    ln_weight = None if ln_weight is None else f32(ln_weight)
+    ln_bias = None if ln_bias is None else f32(ln_bias)
+    if ln_weight is not None and (ln_weight.shape != (Cc,) or ln_bias.shape != (Cc,)):
+        raise ValueError("layernorm_q8: ln_weight and ln_bias must be (C,)")
+    if out is None:
+        out = np.empty(M * Cc, np.int8)
+    if out.dtype != np.int8 or not out.flags.c_contiguous or out.size < M * Cc:
+        raise ValueError("layernorm_q8: out must be a C-contiguous int8 buffer of at least M * C elements")
+    ms = C.c_float(0)
+    check(lib().sd_op_layernorm_q8(ptr(x), fptr(ln_weight), fptr(ln_bias), float(act_absmax), float(eps), ptr(out), M, Cc, iters, C.byref(ms)))
+    return out.reshape(-1)[:M * Cc].reshape(M, Cc), ms.value
+
+
+def geglu_w8a8(xq, wq, w_scale, act_absmax, bias=None, bm=0, out=None, iters=1):
+    """The GEGLU projection in W8A8 (sd_op_geglu_w8a8, plan tile 20): xq (M, C) int8, wq (N2, C) int8 in the checkpoint's row order
+    [values | gates], w_scale (N2,) f32, act_absmax the range xq was quantized with, bias (N2,) f32 or None; bm 0 / 128 / 256 = the tile
+    height (0: by the grid).  ``out``: a C-contiguous float16 buffer of at least M * N2 / 2 elements (tests put guards behind it).  What
+    the library checks it refuses itself (ValueError, no GPU needed).  Returns (out (M, N2 / 2), plan, ms)."""
+    xq = np.ascontiguousarray(xq, dtype=np.int8)
+    wq = np.ascontiguousarray(wq, dtype=np.int8)
+    w_scale = f32(w_scale)
+    if xq.ndim != 2 or wq.ndim != 2 or wq.shape[1] != xq.shape[1] or w_scale.shape != (wq.shape[0],):
+        raise ValueError("geglu_w8a8: xq must be (M, C), wq (N2, C) and w_scale (N2,)")
+    M, Cc = xq.shape
+    N2 = wq.shape[0]
+    bias = None if bias is None else f32(bias)
+    if bias is not None and bias.shape != (N2,):
+        raise ValueError("geglu_w8a8: bias must be (N2,)")
+    n = M * (N2 // 2)
+    if out is None:
+        out = np.empty(n, np.float16)
+    if out.dtype != np.float16 or not out.flags.c_contiguous or out.size < n:
+        raise ValueError("geglu_w8a8: out must be a C-contiguous float16 buffer of at least M * N2 / 2 elements")
+    plan = (C.c_int * 4)()
+    ms = C.c_float(0)
+    check(lib().sd_op_geglu_w8a8(ptr(xq), ptr(wq), fptr(w_scale), float(act_absmax), fptr(bias), ptr(out), M, Cc, N2, bm, plan, iters, C.byref(ms)))
+    return out.reshape(-1)[:n].reshape(M, N2 // 2), list(plan), ms.value
+
+
+def w8a8_pack_geglu(wq):
+    """The int8 weights of the W8A8 GEGLU projection (sd_op_w8a8_pack_geglu; host only): wq (N2, K) int8 [values | gates] -> int8
+    (N2 / 16, 16, K), strip 2 U + v = rows v * N2 / 2 + 16 U .. + 15."""
+    wq = np.ascontiguousarray(wq, dtype=np.int8)
+    if wq.ndim != 2:
+        raise ValueError("w8a8_pack_geglu: wq must be (N2, K)")
+    N2, K = wq.shape
+    return _packed(lib().sd_op_w8a8_pack_geglu, ptr(wq), N2, K).view(np.int8).reshape(N2 // 16, 16, K)
 
 
 def w8a8_pack(wq):

@@ -8,12 +8,16 @@ values, its per-channel scales and the range of the activations the conv reads (
 a marked conv from int8 on ``v_mfma_i32_32x32x32_i8`` wherever its plan is the weight stream (``wstream.hip``, plan tile 17) or the
 3x3 / stride-1 halo conv (``conv3x3_halo_i8.hip``, plan tile 18), and a marked plain 1x1 projection (``proj_in``, ``attn1.to_out.0``,
 ``attn2.to_out.0`` of the 640- / 1280-channel levels) on ``v_mfma_i32_16x16x64_i8`` wherever its plan is the small-M GEMM
-(``smgemm_i8.hip``, plan tile 19); every other marked conv stays fp16 - the reference's skipped layers.  Parity with coremltools' quantizer is NOT pinned
+(``smgemm_i8.hip``, plan tile 19), and a marked GEGLU projection (``ff.net.0.proj`` of those levels) on the same instruction wherever
+its plan is ``smgeglu.hip`` (``smgeglu_i8.hip``, plan tile 20): its ``norm3`` is then not folded into the weights - one LayerNorm launch
+writes ``int8(norm3(x))``, the tensor the reference calibrates, and the GEGLU reads it; every other marked conv stays fp16 - the reference's skipped layers.  Parity with coremltools' quantizer is NOT pinned
 (coremltools is not a dependency of this project): the scales are plain absmax / 127, not the result of its calibration.
 
 Calibration happens on the device: ``HipModel(..., observe_activations=True)`` puts an absmax observer in front of every conv
 the int8 weight stream could take, ``observe_activations="all"`` in front of every conv either int8 conv kernel could take, ``observe_activations="gemm"`` also in front of
-the projections plan tile 19 could take - every layer that could run from int8; after any number of forwards ``.activation_ranges()`` is the recipe's raw material.
+the projections plan tile 19 could take, ``observe_activations="geglu"`` also over the output of ``norm3`` in front of every GEGLU
+projection plan tile 20 could take (a LayerNorm and an absmax launch beside the folded fp16 GEGLU, whose output does not change) -
+every layer that could run from int8; after any number of forwards ``.activation_ranges()`` is the recipe's raw material.
 
 A recipe is JSON ``{layer: act_absmax}``, ``layer`` the conv's module name (its weight tensor without ``.weight``).
 
@@ -27,6 +31,9 @@ import math
 logger = logging.getLogger(__name__)
 
 _SUFFIX = ".weight"
+
+# ``--calibrate-scope`` -> ``observe_activations``: each scope observes the previous one's layers and its own
+CALIBRATION_SCOPES = {"stream": True, "all": "all", "gemm": "gemm", "geglu": "geglu"}
 
 
 def layer_of(tensor_name):

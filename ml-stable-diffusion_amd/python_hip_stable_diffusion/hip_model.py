@@ -199,9 +199,11 @@ class Weights(_lib.Handle):
     def observe_activations(self, on=True):
         """Handles created from the store while this is on carry the activation observers (calibration): ``True`` in front of the
         convs the int8 weight stream could take (plan tile 17), ``"all"`` in front of those of the int8 halo conv (plan tile 18) too,
-        ``"gemm"`` also in front of the plain 1x1 projections the int8 small-M GEMM could take (plan tile 19)."""
+        ``"gemm"`` also in front of the plain 1x1 projections the int8 small-M GEMM could take (plan tile 19), ``"geglu"`` also over
+        the LayerNorm output in front of every GEGLU projection the int8 GEGLU kernel could take (plan tile 20)."""
         _lib.check(_lib.lib().sd_weights_observe_activations(self._h, observe_level(on)))
-        _lib.check(_lib.lib().sd_weights_observe_gemms(self._h, int(on == "gemm")))
+        _lib.check(_lib.lib().sd_weights_observe_gemms(self._h, int(on in ("gemm", "geglu"))))
+        _lib.check(_lib.lib().sd_weights_observe_geglus(self._h, int(on == "geglu")))
 
     @classmethod
     @contextlib.contextmanager
@@ -220,10 +222,10 @@ class Weights(_lib.Handle):
 
 def observe_level(on):
     """observe_activations as the level of sd_weights_observe_activations: False 0, True 1, "all" 2; "gemm" is level 2 with the
-    projections' flag (sd_weights_observe_gemms) beside it."""
+    projections' flag (sd_weights_observe_gemms) beside it, "geglu" level 2 with that flag and the GEGLUs' (sd_weights_observe_geglus)."""
     if isinstance(on, str):
-        if on not in ("all", "gemm"):
-            raise ValueError(f"observe_activations must be False, True, 'all' or 'gemm', got {on!r}")
+        if on not in ("all", "gemm", "geglu"):
+            raise ValueError(f"observe_activations must be False, True, 'all', 'gemm' or 'geglu', got {on!r}")
         return 2
     return int(bool(on))
 

@@ -646,7 +646,7 @@ def get_hip_pipe(model_dir, model_version, compute_unit="ALL", scheduler_overrid
     ``activation_quantization``: a W8A8 recipe, a path or a dict {layer: act_absmax} (``activation_quantization.load_recipe``), applied
     to the UNet alone (activation_quantization.py:141-203 ``--quantize-pytorch``; the refiner and the ControlNets stay as they are;
     parity with coremltools' quantizer unpinned).  ``observe_activations``: the UNet carries the calibration observers
-    (``True``, ``"all"`` or ``"gemm"``: ``Weights.observe_activations``; ``pipe.unet.activation_ranges()`` after a generation;
+    (``True``, ``"all"``, ``"gemm"`` or ``"geglu"``: ``Weights.observe_activations``; ``pipe.unet.activation_ranges()`` after a generation;
     ``--calibrate-activations`` / ``--calibrate-scope``)."""
     if not os.path.isdir(model_dir):
         raise FileNotFoundError(f"{model_dir} not found (coreml_model.py:176-178)")
@@ -809,14 +809,16 @@ def build_parser():
     parser.add_argument("--activation-quantization-recipe", default=None,                        # activation_quantization.py --quantize-pytorch
                         help="A W8A8 recipe (JSON {layer: act_absmax}, written by --calibrate-activations): the UNet convs it names run "
                              "from int8 weights and activations where their kernel is the weight stream, the 3x3 halo conv or - for the plain 1x1 "
-                             "projections proj_in / attn1.to_out.0 / attn2.to_out.0 of the 640- and 1280-channel levels - the small-M GEMM")
+                             "projections proj_in / attn1.to_out.0 / attn2.to_out.0 of the 640- and 1280-channel levels - the small-M GEMM, "
+                             "or - for their ff.net.0.proj - the GEGLU kernel behind a LayerNorm that writes int8")
     parser.add_argument("--calibrate-activations", default=None,                                 # activation_quantization.py --generate-calibration-data
                         help="Run the requested generation on a UNet that records the range of every quantizable conv's input and write "
                              "the W8A8 recipe to this file")
-    parser.add_argument("--calibrate-scope", default="stream", choices=("stream", "all", "gemm"),
+    parser.add_argument("--calibrate-scope", default="stream", choices=("stream", "all", "gemm", "geglu"),
                         help="Which convs --calibrate-activations observes: 'stream' = those the int8 weight stream takes (the 8x8 level), "
                              "'all' = also every 3x3 / stride-1 conv the int8 halo conv takes, 'gemm' = also the plain 1x1 projections the "
-                             "int8 small-M GEMM takes")
+                             "int8 small-M GEMM takes, 'geglu' = also the GEGLU projections ff.net.0.proj the int8 GEGLU kernel takes (the "
+                             "output of their norm3)")
     return parser
 
 
@@ -846,7 +848,7 @@ def main(args):
                         disable_safety=getattr(args, "disable_safety", False), vae_encoder=bool(getattr(args, "image", None)),
                         quantize_nbits=getattr(args, "quantize_nbits", None), palettization_recipe=recipe,
                         device_postprocess=getattr(args, "device_postprocess", False), activation_quantization=aq_recipe,
-                        observe_activations={"all": "all", "gemm": "gemm"}.get(getattr(args, "calibrate_scope", "stream"), True) if calibrate else False)
+                        observe_activations={"all": "all", "gemm": "gemm", "geglu": "geglu"}.get(getattr(args, "calibrate_scope", "stream"), True) if calibrate else False)
     controlnet_cond = None
     if args.controlnet:
         controlnet_cond = [prepare_controlnet_cond(args.controlnet_inputs[i], pipe.height, pipe.width)
