@@ -775,6 +775,49 @@ int sd_op_image_rgb8(const float* image, uint8_t* rgb8, int B, int H, int W, int
 int sd_op_clip_input(const uint8_t* rgb8, void* clip_input, int B, int H, int W, int rh, int rw, int S, const float* mean3,
                      const float* std3, int iters, float* ms);
 
+/* ------------------------------------------------------------------------------------------
+ * Operator-level entries of the kernels that otherwise run only inside whole models: the fp32 VAE path, the VAE's fp16 row
+ * softmax, the time-embedding GEMV, the text encoder's own kernels and the copy kernels at the model boundaries.  Host tensors in
+ * the reference's layouts; every refusal (SD_ERR_INVALID_ARGUMENT, SD_ERR_UNSUPPORTED) comes before any device work; every device
+ * output sits in front of a guard of NaN patterns, and a launch that wrote into it fails the call (SD_ERR_INTERNAL).
+ * ------------------------------------------------------------------------------------------ */
+/* fp32 implicit-GEMM conv of an fp32 VAE handle: x (B,Cin,H,W) f32; w_kind 0: w f16 (N,Cin,k,k), 1: w f32 (N,Cin,k,k), 2: w f32
+ * (Cin,N) with ksize 1 only (attention's P.V); bias (N) / res (B,N,Ho,Wo) f32 or NULL; ksize 1 / 3, stride 1 / 2, upsample 0 / 1
+ * (nearest x2 in front), pad_mode as sd_op_conv2d_ex (1: the encoder's (0,1,0,1) padding) -> out (B,N,Ho,Wo) f32 */
+int sd_op_conv_f32(const float* x, const void* w, int w_kind, const float* bias, const float* res, float* out, int B, int Cin,
+                   int H, int W, int N, int ksize, int stride, int upsample, int pad_mode);
+/* fp32 GroupNorm (+ SiLU) of an fp32 VAE handle: x (B,C,H,W) f32, gamma / beta (C) -> out (B,C,H,W) f32; C % groups != 0 is
+ * SD_ERR_UNSUPPORTED */
+int sd_op_groupnorm_f32(const float* x, const float* gamma, const float* beta, float* out, int B, int C, int H, int W, int groups,
+                        float eps, int silu);
+/* softmax(scale * x) over each row of x (rows, cols), in place: fp32 = 0 the f16 kernel (cols % 8 == 0 and <= 8192, else
+ * SD_ERR_UNSUPPORTED), fp32 = 1 the f32 kernel (any cols) */
+int sd_op_row_softmax(void* x, int rows, int cols, float scale, int fp32);
+/* out[b][n] (+)= act_out(sum_k w[n][k] * act_in(x[b][k]) + bias[n]), act = SiLU where its flag is set: w (N,K) f16, bias (N) or
+ * NULL, x (B,K) f32, out (B,N) f32 (read first with `accumulate`); K % 8 == 0 and <= 3072, else SD_ERR_UNSUPPORTED */
+int sd_op_gemv(const void* w, const float* bias, const float* x, float* out, int B, int N, int K, int silu_in, int silu_out,
+               int accumulate);
+/* causal attention of the text encoder: qkv (S, 3 D) f16 rows [q | k | v] -> out (S, D) f16; S <= 80, head dim D / heads a
+ * multiple of 8 and <= 128, else SD_ERR_UNSUPPORTED */
+int sd_op_clip_attention(const void* qkv, void* out, int S, int D, int heads);
+/* out[s] = tok[clamp(ids[s], 0, vocab - 1)] + pos[s]: ids (S) int32, tok (vocab, D) / pos (S, D) f16 -> out (S, D) f16;
+ * D % 8 != 0 is SD_ERR_UNSUPPORTED */
+int sd_op_clip_embed(const int32_t* ids, const void* tok, const void* pos, void* out, int S, int D, int vocab);
+/* the CLIP MLP activation over n f16 values, in place: act 0 quick_gelu, 1 exact-erf gelu; n % 8 == 0 */
+int sd_op_clip_act(void* x, size_t n, int act);
+/* the copy kernels, src -> dst of B * C * H * W elements: kind 0 / 1 (B,C,H,W) f16 / f32 -> [B][H][W][C] f16; 2 / 3 the same to
+ * f32; 4 / 5 [B][H][W][C] f16 / f32 -> (B,C,H,W) f32; 6 (B,C,1,S) f16 -> [B][S][C] f16 (H = 1, W = S); 7 f16 -> f32 and
+ * 8 f32 -> f16 over the flat buffer */
+int sd_op_layout(int kind, const void* src, void* dst, int B, int C, int H, int W);
+/* out = srcs[0] + ... + srcs[nsrc - 1] over n f16 values, fp32 accumulation in source order, one rounding; 1 <= nsrc <= 4,
+ * n % 8 == 0; add = 1 (nsrc 2 only): the two-source add kernel instead */
+int sd_op_sum_half(const void* const* srcs, int nsrc, void* out, size_t n, int add);
+/* img (B,3,I,I) f16 -> rows (B (I/p)^2, Kp) f16: column c p p + py p + px of a patch's row, columns [3 p p, Kp) zero */
+int sd_op_vit_patch_rows(const void* img, void* rows, int B, int I, int p, int Kp);
+/* out[b][0] = cls + pos[0], out[b][1 + j] = patch[b][j] + pos[1 + j]: patch (B, S - 1, D), cls (D), pos (S, D) f16 -> out
+ * (B, S, D) f16; D % 8 != 0 or S < 2 is SD_ERR_UNSUPPORTED */
+int sd_op_vit_tokens(const void* patch, const void* cls, const void* pos, void* out, int B, int S, int D);
+
 #ifdef __cplusplus
 }
 #endif

@@ -327,6 +327,48 @@ ConvDesc qkv_desc(const half_t* in, const FoldedProj& f, float ln_eps, half_t* q
   return d;
 }
 
+// A device buffer of n elements in front of a guard of `guard` more, every byte 0xff (fp16 / fp32 NaN patterns), then the first n
+// elements of `host` copied in (NULL: the output stays poisoned too, so an element the launch skipped reads back as NaN)
+template <typename T>
+T* guarded_buf(Scratch& sc, size_t n, size_t guard, const T* host = nullptr) {
+  T* d = sc.dev<T>(n + guard);
+  SD_HIP(hipMemset(d, 0xff, (n + guard) * sizeof(T)));
+  SD_HIP(hipStreamSynchronize(nullptr));   // the fill runs on the null stream, which the scratch's non-blocking stream does not wait for
+  if (host) SD_HIP(hipMemcpy(d, host, n * sizeof(T), hipMemcpyHostToDevice));
+  return d;
+}
+// ... and the check behind the launch: the guard must still hold its pattern
+template <typename T>
+void check_guard(Scratch& sc, const T* d, size_t n, size_t guard, const char* what) {
+  SD_HIP(hipStreamSynchronize(sc.stream));
+  std::vector<uint8_t> g(guard * sizeof(T));
+  SD_HIP(hipMemcpy(g.data(), d + n, g.size(), hipMemcpyDeviceToHost));
+  for (uint8_t v : g) SD_REQUIRE(v == 0xff, kInternal, "%s wrote behind its %zu outputs", what, n);
+}
+constexpr size_t kOpGuard = 4096;   // elements
+
+// (B, C, HW) -> [B][HW][C] and back, on the host
+template <typename T>
+std::vector<T> host_nhwc(const T* src, int B, int C, int HW) {
+  std::vector<T> t((size_t)B * C * HW);
+  for (int b = 0; b < B; ++b)
+    for (int c = 0; c < C; ++c)
+      for (int p = 0; p < HW; ++p) t[((size_t)b * HW + p) * C + c] = src[((size_t)b * C + c) * HW + p];
+  return t;
+}
+template <typename T>
+void host_nchw(const std::vector<T>& t, T* dst, int B, int C, int HW) {
+  for (int b = 0; b < B; ++b)
+    for (int c = 0; c < C; ++c)
+      for (int p = 0; p < HW; ++p) dst[((size_t)b * C + c) * HW + p] = t[((size_t)b * HW + p) * C + c];
+}
+template <typename T>
+std::vector<T> download(const T* dev, size_t n) {
+  std::vector<T> t(n);
+  SD_HIP(hipMemcpy(t.data(), dev, n * sizeof(T), hipMemcpyDeviceToHost));
+  return t;
+}
+
 }  // namespace
 }  // namespace sd
 
@@ -1675,6 +1717,284 @@ int sd_op_safety_head(const float* image_embeds, const float* concept_embeds, co
     SD_HIP(hipStreamSynchronize(sc.stream));
     SD_HIP(hipMemcpy(has_nsfw, dflag, (size_t)B * sizeof(float), hipMemcpyDeviceToHost));
     SD_HIP(hipMemcpy(concept_scores, dscore, (size_t)B * n_concepts * sizeof(float), hipMemcpyDeviceToHost));
+  });
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The kernels that only whole models used to reach (vae_f32.hip, norm.hip row_softmax, misc.hip, clip.hip, vit.hip's two layout
+// kernels), one entry point each.  Everything that can be refused is refused before any device work; every device output sits in
+// front of a guard of NaN patterns that the launch must leave alone, and starts out poisoned itself.
+// ---------------------------------------------------------------------------------------------------------------------------
+// vae_f32.hip conv_f32_kernel as Net::conv_f32 / the fp32 attention drive it: x (B,Cin,H,W) f32; w_kind 0: w f16 (N,Cin,k,k), 1: w f32
+// (N,Cin,k,k) - both through retile_ohwi - 2: w f32 (K = Cin, N) as it stands, ksize 1 only (attention's V); bias (N) / res
+// (B,N,Ho,Wo) f32 or NULL; pad_mode as sd_op_conv2d_ex -> out (B,N,Ho,Wo) f32
+int sd_op_conv_f32(const float* x, const void* w, int w_kind, const float* bias, const float* res, float* out, int B, int Cin, int H, int W,
+                   int N, int ksize, int stride, int upsample, int pad_mode) {
+  return guarded([&] {
+    SD_REQUIRE(x && w && out, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(B > 0 && Cin > 0 && H > 0 && W > 0 && N > 0, kInvalidArgument, "conv_f32: B=%d Cin=%d H=%d W=%d N=%d", B, Cin, H, W, N);
+    SD_REQUIRE((ksize == 1 || ksize == 3) && (stride == 1 || stride == 2) && (upsample == 0 || upsample == 1), kInvalidArgument,
+               "conv_f32: ksize %d stride %d upsample %d not on the path", ksize, stride, upsample);
+    SD_REQUIRE(w_kind >= 0 && w_kind <= 2 && (w_kind != 2 || ksize == 1), kInvalidArgument, "conv_f32: w_kind %d with ksize %d (2 = [K][N], ksize 1 only)",
+               w_kind, ksize);
+    SD_REQUIRE(pad_mode == 0 || (pad_mode == 1 && ksize == 3 && stride == 2 && !upsample), kInvalidArgument,
+               "conv_f32: pad_mode %d (1 = the (0,1,0,1) padding of a 3x3 / stride-2 conv without upsample)", pad_mode);
+    const int up = upsample ? 2 : 1, pad = ksize / 2;
+    const int Ho = pad_mode ? (H * up + 1 - ksize) / stride + 1 : (H * up + 2 * pad - ksize) / stride + 1;
+    const int Wo = pad_mode ? (W * up + 1 - ksize) / stride + 1 : (W * up + 2 * pad - ksize) / stride + 1;
+    SD_REQUIRE(Ho >= 1 && Wo >= 1, kInvalidArgument, "conv_f32: empty output (%dx%d)", Ho, Wo);
+    const size_t nw = (size_t)N * Cin * ksize * ksize, nout = (size_t)B * Ho * Wo * N;
+    Scratch sc;
+    ConvF32Desc d;
+    const std::vector<float> xh = host_nhwc(x, B, Cin, H * W);
+    d.x = sc.dev<float>(xh.size(), xh.data());
+    if (w_kind == 0) {
+      std::vector<half_t> t(nw);
+      retile_ohwi(f16(w), N, Cin, ksize, false, t.data());
+      d.w = sc.dev<half_t>(nw, t.data());
+    } else if (w_kind == 1) {
+      std::vector<float> t(nw);
+      retile_ohwi(reinterpret_cast<const float*>(w), N, Cin, ksize, false, t.data());
+      d.w = sc.dev<float>(nw, t.data());
+    } else {
+      d.w = sc.dev<float>(nw, reinterpret_cast<const float*>(w));
+    }
+    d.w_kind = w_kind;
+    d.bias = bias ? sc.dev<float>(N, bias) : nullptr;
+    if (res) {
+      const std::vector<float> rh = host_nhwc(res, B, N, Ho * Wo);
+      d.res = sc.dev<float>(rh.size(), rh.data());
+    }
+    float* dout = guarded_buf<float>(sc, nout, kOpGuard);
+    d.out = dout;
+    d.B = B; d.Hi = H; d.Wi = W; d.Cin = Cin; d.Ho = Ho; d.Wo = Wo; d.N = N;
+    d.ksize = ksize; d.stride = stride; d.up = up;
+    if (pad_mode) d.pad = 0;
+    launch_conv_f32(d, sc.stream);
+    check_guard(sc, dout, nout, kOpGuard, "conv_f32");
+    host_nchw(download(dout, nout), out, B, N, Ho * Wo);
+  });
+}
+
+// vae_f32.hip groupnorm_f32_* (statistics, finalize, apply): x (B,C,H,W) f32, gamma / beta (C) -> out (B,C,H,W) f32.  The statistics
+// scratch starts out as NaN patterns: a slab entry that is read without having been written shows.
+int sd_op_groupnorm_f32(const float* x, const float* gamma, const float* beta, float* out, int B, int C, int H, int W, int groups, float eps,
+                        int silu) {
+  return guarded([&] {
+    SD_REQUIRE(x && gamma && beta && out, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && groups > 0, kInvalidArgument, "groupnorm_f32: B=%d C=%d H=%d W=%d groups=%d", B, C, H, W, groups);
+    SD_REQUIRE(C % groups == 0, kUnsupported, "groupnorm_f32: %d channels, %d groups", C, groups);
+    Scratch sc;
+    const size_t n = (size_t)B * C * H * W;
+    const std::vector<float> xh = host_nhwc(x, B, C, H * W);
+    float* dx = sc.dev<float>(n, xh.data());
+    const size_t sb = groupnorm_f32_scratch_bytes(B, groups);
+    char* scratch = sc.dev<char>(sb);
+    SD_HIP(hipMemset(scratch, 0xff, sb));
+    SD_HIP(hipStreamSynchronize(nullptr));
+    float* dg = sc.dev<float>(C, gamma);
+    float* db = sc.dev<float>(C, beta);
+    float* dout = guarded_buf<float>(sc, n, kOpGuard);
+    launch_groupnorm_f32(dx, scratch, dg, db, dout, B, H * W, C, groups, eps, silu ? 1 : 0, sc.stream);
+    check_guard(sc, dout, n, kOpGuard, "groupnorm_f32");
+    host_nchw(download(dout, n), out, B, C, H * W);
+  });
+}
+
+// softmax(scale * x) over each row of x (rows, cols), in place: fp32 = 0 norm.hip row_softmax_kernel on f16 (cols % 8 == 0, <= 8192,
+// else SD_ERR_UNSUPPORTED), fp32 = 1 vae_f32.hip row_softmax_f32_kernel on f32 (any cols)
+int sd_op_row_softmax(void* x, int rows, int cols, float scale, int fp32) {
+  return guarded([&] {
+    SD_REQUIRE(x, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(rows > 0 && cols > 0 && (fp32 == 0 || fp32 == 1), kInvalidArgument, "row_softmax: rows=%d cols=%d fp32=%d", rows, cols, fp32);
+    SD_REQUIRE(fp32 || (cols % 8 == 0 && cols <= 8192), kUnsupported, "row_softmax: cols=%d (need cols %% 8 == 0, <= 8192)", cols);
+    Scratch sc;
+    const size_t n = (size_t)rows * cols;
+    if (fp32) {
+      float* d = guarded_buf<float>(sc, n, kOpGuard, reinterpret_cast<const float*>(x));
+      launch_row_softmax_f32(d, rows, cols, scale, sc.stream);
+      check_guard(sc, d, n, kOpGuard, "row_softmax (fp32)");
+      SD_HIP(hipMemcpy(x, d, n * sizeof(float), hipMemcpyDeviceToHost));
+    } else {
+      half_t* d = guarded_buf<half_t>(sc, n, kOpGuard, f16(x));
+      launch_row_softmax(d, rows, cols, scale, sc.stream);
+      check_guard(sc, d, n, kOpGuard, "row_softmax");
+      SD_HIP(hipMemcpy(x, d, n * sizeof(half_t), hipMemcpyDeviceToHost));
+    }
+  });
+}
+
+// misc.hip gemv_kernel through launch_gemv: out[b][n] (+)= act_out(sum_k w[n][k] act_in(x[b][k]) + bias[n]); w (N,K) f16, bias (N) or
+// NULL, x (B,K) f32, out (B,N) f32 - read first when `accumulate`.  The rows sit on the device as the UNet keeps them: x with a row
+// stride of K + 8 floats behind a 4-float offset (16-byte aligned, as the kernel's 16-byte loads need), every other float 1e30; out
+// with a row stride of N + 5, the padding NaN patterns that must survive the launch.
+int sd_op_gemv(const void* w, const float* bias, const float* x, float* out, int B, int N, int K, int silu_in, int silu_out, int accumulate) {
+  return guarded([&] {
+    SD_REQUIRE(w && x && out, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(B > 0 && N > 0 && K > 0, kInvalidArgument, "gemv: B=%d N=%d K=%d", B, N, K);
+    SD_REQUIRE(K % 8 == 0 && K <= 3072, kUnsupported, "gemv: K=%d must be a multiple of 8 and <= 3072", K);
+    Scratch sc;
+    const int ldx = K + 8, ldo = N + 5, xoff = 4;
+    std::vector<float> xr((size_t)B * ldx + xoff, 1.0e30f);
+    for (int b = 0; b < B; ++b) std::copy(x + (size_t)b * K, x + (size_t)(b + 1) * K, xr.begin() + xoff + (size_t)b * ldx);
+    const float* dx = sc.dev<float>(xr.size(), xr.data()) + xoff;
+    half_t* dw = sc.dev<half_t>((size_t)N * K, f16(w));
+    float* db = bias ? sc.dev<float>(N, bias) : nullptr;
+    const size_t no = (size_t)B * ldo;
+    float* dout = guarded_buf<float>(sc, no, kOpGuard);
+    if (accumulate) SD_HIP(hipMemcpy2D(dout, ldo * sizeof(float), out, N * sizeof(float), N * sizeof(float), B, hipMemcpyHostToDevice));
+    launch_gemv(dw, db, dx, ldx, dout, ldo, B, N, K, silu_in ? 1 : 0, silu_out ? 1 : 0, accumulate ? 1 : 0, sc.stream);
+    check_guard(sc, dout, no, kOpGuard, "gemv");
+    const std::vector<float> t = download(dout, no);
+    for (int b = 0; b < B; ++b) {
+      for (int c = N; c < ldo; ++c) {
+        uint32_t bits;
+        memcpy(&bits, &t[(size_t)b * ldo + c], 4);
+        SD_REQUIRE(bits == 0xffffffffu, kInternal, "gemv wrote into the padding of output row %d", b);
+      }
+      std::copy(t.begin() + (size_t)b * ldo, t.begin() + (size_t)b * ldo + N, out + (size_t)b * N);
+    }
+  });
+}
+
+// clip.hip clip_attention_kernel: causal attention of the text encoder over the stacked projection's rows qkv (S, 3 D) f16 = [q | k | v]
+// -> out (S, D) f16; S <= 80, head dim D / heads a multiple of 8 and <= 128 (else SD_ERR_UNSUPPORTED)
+int sd_op_clip_attention(const void* qkv, void* out, int S, int D, int heads) {
+  return guarded([&] {
+    SD_REQUIRE(qkv && out, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(S > 0 && D > 0 && heads > 0 && D % heads == 0, kInvalidArgument, "clip_attention: S=%d D=%d heads=%d", S, D, heads);
+    SD_REQUIRE(S <= 80 && D / heads <= 128 && (D / heads) % 8 == 0, kUnsupported, "clip_attention: S=%d D=%d heads=%d", S, D, heads);
+    Scratch sc;
+    const size_t n = (size_t)S * D;
+    half_t* dq = sc.dev<half_t>(3 * n, f16(qkv));
+    half_t* dout = guarded_buf<half_t>(sc, n, kOpGuard);
+    launch_clip_attention(dq, dout, S, D, heads, sc.stream);
+    check_guard(sc, dout, n, kOpGuard, "clip_attention");
+    SD_HIP(hipMemcpy(out, dout, n * sizeof(half_t), hipMemcpyDeviceToHost));
+  });
+}
+
+// clip.hip clip_embed_kernel: out[s] = tok[clamp(ids[s], 0, vocab - 1)] + pos[s]; ids (S) int32, tok (vocab, D) / pos (S, D) f16 ->
+// out (S, D) f16; D % 8 == 0 (else SD_ERR_UNSUPPORTED)
+int sd_op_clip_embed(const int32_t* ids, const void* tok, const void* pos, void* out, int S, int D, int vocab) {
+  return guarded([&] {
+    SD_REQUIRE(ids && tok && pos && out, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(S > 0 && D > 0 && vocab > 0, kInvalidArgument, "clip_embed: S=%d D=%d vocab=%d", S, D, vocab);
+    SD_REQUIRE(D % 8 == 0, kUnsupported, "clip_embed: hidden size %d", D);
+    Scratch sc;
+    const size_t n = (size_t)S * D;
+    int* di = sc.dev<int>(S, ids);
+    half_t* dt = sc.dev<half_t>((size_t)vocab * D, f16(tok));
+    half_t* dp = sc.dev<half_t>(n, f16(pos));
+    half_t* dout = guarded_buf<half_t>(sc, n, kOpGuard);
+    launch_clip_embed(di, dt, dp, dout, S, D, vocab, sc.stream);
+    check_guard(sc, dout, n, kOpGuard, "clip_embed");
+    SD_HIP(hipMemcpy(out, dout, n * sizeof(half_t), hipMemcpyDeviceToHost));
+  });
+}
+
+// clip.hip clip_act_kernel, in place over n f16 values: act 0 quick_gelu, 1 exact-erf gelu; n % 8 == 0
+int sd_op_clip_act(void* x, size_t n, int act) {
+  return guarded([&] {
+    SD_REQUIRE(x, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(n > 0 && n % 8 == 0 && (act == 0 || act == 1), kInvalidArgument, "clip_act: n=%zu act=%d", n, act);
+    Scratch sc;
+    half_t* d = guarded_buf<half_t>(sc, n, kOpGuard, f16(x));
+    launch_clip_act(d, n, act, sc.stream);
+    check_guard(sc, d, n, kOpGuard, "clip_act");
+    SD_HIP(hipMemcpy(x, d, n * sizeof(half_t), hipMemcpyDeviceToHost));
+  });
+}
+
+// The copy kernels at the model boundaries, src -> dst of B * C * H * W elements each, behind one kind code:
+//   0 / 1  misc.hip nchw_to_nhwc_kernel       (B,C,H,W) f16 / f32 -> [B][H][W][C] f16
+//   2 / 3  vae_f32.hip nchw_to_nhwc_f32_kernel (B,C,H,W) f16 / f32 -> [B][H][W][C] f32
+//   4      misc.hip nhwc_to_nchw_f32_kernel    [B][H][W][C] f16 -> (B,C,H,W) f32
+//   5      vae_f32.hip nhwc_to_nchw_f32f32     [B][H][W][C] f32 -> (B,C,H,W) f32
+//   6      misc.hip bc1s_to_tokens_kernel      (B,C,1,S) f16 -> [B][S][C] f16   (H = 1, W = S)
+//   7 / 8  misc.hip half_to_float / float_to_half over the flat buffer
+int sd_op_layout(int kind, const void* src, void* dst, int B, int C, int H, int W) {
+  return guarded([&] {
+    SD_REQUIRE(src && dst, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(kind >= 0 && kind <= 8, kInvalidArgument, "layout: kind %d", kind);
+    SD_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && (kind != 6 || H == 1), kInvalidArgument, "layout: kind %d B=%d C=%d H=%d W=%d", kind, B, C, H, W);
+    Scratch sc;
+    const size_t n = (size_t)B * C * H * W;
+    const bool src_f32 = kind == 1 || kind == 3 || kind == 5 || kind == 8;
+    const bool dst_f32 = kind == 2 || kind == 3 || kind == 4 || kind == 5 || kind == 7;
+    const void* ds = src_f32 ? (const void*)sc.dev<float>(n, reinterpret_cast<const float*>(src)) : (const void*)sc.dev<half_t>(n, f16(src));
+    float* df = dst_f32 ? guarded_buf<float>(sc, n, kOpGuard) : nullptr;
+    half_t* dh = dst_f32 ? nullptr : guarded_buf<half_t>(sc, n, kOpGuard);
+    switch (kind) {
+      case 0: case 1: launch_nchw_to_nhwc(ds, src_f32, dh, B, C, H, W, sc.stream); break;
+      case 2: case 3: launch_nchw_to_nhwc_f32(ds, src_f32, df, B, C, H, W, sc.stream); break;
+      case 4: launch_nhwc_to_nchw_f32(f16(ds), df, B, C, H, W, sc.stream); break;
+      case 5: launch_nhwc_to_nchw_f32f32(reinterpret_cast<const float*>(ds), df, B, C, H, W, sc.stream); break;
+      case 6: launch_bc1s_to_tokens(f16(ds), dh, B, C, W, sc.stream); break;
+      case 7: launch_half_to_float(f16(ds), df, n, sc.stream); break;
+      default: launch_float_to_half(reinterpret_cast<const float*>(ds), dh, n, sc.stream); break;
+    }
+    if (dst_f32) {
+      check_guard(sc, df, n, kOpGuard, "layout");
+      SD_HIP(hipMemcpy(dst, df, n * sizeof(float), hipMemcpyDeviceToHost));
+    } else {
+      check_guard(sc, dh, n, kOpGuard, "layout");
+      SD_HIP(hipMemcpy(dst, dh, n * sizeof(half_t), hipMemcpyDeviceToHost));
+    }
+  });
+}
+
+// misc.hip sum_half_kernel: out = srcs[0] + ... + srcs[nsrc - 1] over n f16 values (1 <= nsrc <= 4, fp32 accumulation in source order,
+// one rounding); add = 1 (nsrc must be 2): add_half_kernel instead.  n % 8 == 0.
+int sd_op_sum_half(const void* const* srcs, int nsrc, void* out, size_t n, int add) {
+  return guarded([&] {
+    SD_REQUIRE(srcs && out, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(n > 0 && n % 8 == 0 && nsrc >= 1 && nsrc <= 4 && (add == 0 || (add == 1 && nsrc == 2)), kInvalidArgument,
+               "sum_half: n=%zu (a multiple of 8), %d sources (1-4; add_half: 2), add=%d", n, nsrc, add);
+    for (int i = 0; i < nsrc; ++i) SD_REQUIRE(srcs[i], kInvalidArgument, "NULL argument");
+    Scratch sc;
+    const half_t* ds[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int i = 0; i < nsrc; ++i) ds[i] = sc.dev<half_t>(n, f16(srcs[i]));
+    half_t* dout = guarded_buf<half_t>(sc, n, kOpGuard);
+    if (add)
+      launch_add_half(ds[0], ds[1], dout, n, sc.stream);
+    else
+      launch_sum_half(ds, nsrc, dout, n, sc.stream);
+    check_guard(sc, dout, n, kOpGuard, "sum_half");
+    SD_HIP(hipMemcpy(out, dout, n * sizeof(half_t), hipMemcpyDeviceToHost));
+  });
+}
+
+// vit.hip vit_patch_rows_kernel: img (B,3,I,I) f16 -> rows (B (I/p)^2, Kp) f16, columns [3 p p, Kp) zero
+int sd_op_vit_patch_rows(const void* img, void* rows, int B, int I, int p, int Kp) {
+  return guarded([&] {
+    SD_REQUIRE(img && rows, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(B > 0 && p >= 1 && I >= p && I % p == 0 && Kp >= 3 * p * p, kInvalidArgument, "vit_patch_rows: B=%d image %d patch %d row %d", B, I, p, Kp);
+    Scratch sc;
+    const size_t n = (size_t)B * (I / p) * (I / p) * Kp;
+    half_t* di = sc.dev<half_t>((size_t)B * 3 * I * I, f16(img));
+    half_t* dout = guarded_buf<half_t>(sc, n, kOpGuard);
+    launch_vit_patch_rows(di, dout, B, I, p, Kp, sc.stream);
+    check_guard(sc, dout, n, kOpGuard, "vit_patch_rows");
+    SD_HIP(hipMemcpy(rows, dout, n * sizeof(half_t), hipMemcpyDeviceToHost));
+  });
+}
+
+// vit.hip vit_tokens_kernel: patch (B, S - 1, D), cls (D), pos (S, D) f16 -> out (B, S, D) f16; D % 8 == 0, S >= 2 (else SD_ERR_UNSUPPORTED)
+int sd_op_vit_tokens(const void* patch, const void* cls, const void* pos, void* out, int B, int S, int D) {
+  return guarded([&] {
+    SD_REQUIRE(patch && cls && pos && out, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(B > 0 && S > 0 && D > 0, kInvalidArgument, "vit_tokens: B=%d S=%d D=%d", B, S, D);
+    SD_REQUIRE(D % 8 == 0 && S >= 2, kUnsupported, "vit_tokens: hidden size %d, %d tokens", D, S);
+    Scratch sc;
+    const size_t n = (size_t)B * S * D;
+    half_t* dp = sc.dev<half_t>((size_t)B * (S - 1) * D, f16(patch));
+    half_t* dc = sc.dev<half_t>(D, f16(cls));
+    half_t* de = sc.dev<half_t>((size_t)S * D, f16(pos));
+    half_t* dout = guarded_buf<half_t>(sc, n, kOpGuard);
+    launch_vit_tokens(dp, dc, de, dout, B, S, D, sc.stream);
+    check_guard(sc, dout, n, kOpGuard, "vit_tokens");
+    SD_HIP(hipMemcpy(out, dout, n * sizeof(half_t), hipMemcpyDeviceToHost));
   });
 }
 

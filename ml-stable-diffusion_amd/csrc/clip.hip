@@ -94,14 +94,16 @@ __global__ __launch_bounds__(256) void clip_attention_kernel(const half_t* __res
   }
 }
 
-// in-place MLP activation: 0 = quick_gelu x*sigmoid(1.702x) (CLIP ViT-L), 1 = exact-erf gelu (OpenCLIP)
+// in-place MLP activation: 0 = quick_gelu x*sigmoid(1.702x) (CLIP ViT-L), 1 = exact-erf gelu (OpenCLIP).  The gelu is spelled
+// x * Phi(x) = 0.5 x erfc(-x / sqrt 2): 1 + erf(x / sqrt 2) cancels for x < -3 (at x = -4.8 the fp32 sum keeps four bits, and the
+// result, a subnormal fp16, came out two units off)
 __global__ void clip_act_kernel(half_t* __restrict__ x, size_t n8, int act) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (size_t)gridDim.x * blockDim.x) {
     half8 v = reinterpret_cast<half8*>(x)[i];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       const float f = (float)v[e];
-      v[e] = (half_t)(act == 0 ? f / (1.0f + __expf(-1.702f * f)) : 0.5f * f * (1.0f + erff(f * 0.70710678118654752f)));
+      v[e] = (half_t)(act == 0 ? f / (1.0f + __expf(-1.702f * f)) : 0.5f * f * erfcf(-f * 0.70710678118654752f));
     }
     reinterpret_cast<half8*>(x)[i] = v;
   }

@@ -52,6 +52,19 @@ half_t* Net::upload_conv_weight(const std::string& name, int cout, int cin, int 
   return d;
 }
 
+// the same tensor in the same [Cout][k][k][Cin] layout, kept fp32: what the convs of a compute_fp32 handle read (ConvF32Desc::w_kind 1)
+float* Net::upload_conv_weight_f32(const std::string& name, int cout, int cin, int k) {
+  const HostTensor& t = ws_->get(name + ".weight");
+  const size_t expect = (size_t)cout * cin * k * k;
+  SD_REQUIRE(t.numel() == expect, kInvalidArgument, "%s.weight has %zu elements, expected %zu (%d,%d,%d,%d)", name.c_str(), t.numel(), expect,
+             cout, cin, k, k);
+  std::vector<float> host(expect);
+  retile_ohwi(t.data.data(), cout, cin, k, false, host.data());
+  float* d = ll_.arena.alloc_n<float>(expect);
+  SD_HIP(hipMemcpy(d, host.data(), expect * sizeof(float), hipMemcpyHostToDevice));
+  return d;
+}
+
 float* Net::upload_vec(const std::string& name, int n, bool geglu) {
   const HostTensor& t = ws_->get(name);
   SD_REQUIRE((int)t.numel() == n, kInvalidArgument, "%s has %zu elements, expected %d", name.c_str(), t.numel(), n);
@@ -182,14 +195,8 @@ int Net::activation_range(int index, std::string* name, float* absmax) {
 Tensor Net::conv_f32(std::vector<Op>& ops, const std::string& name, const Tensor& x, const ConvArgs& a) {
   const int cout = a.cout, k = a.k;
   const float* b = a.bias ? upload_vec(name + ".bias", cout) : nullptr;
-  const HostTensor& t = ws_->get(name + ".weight");
-  const size_t expect = (size_t)cout * x.C * k * k;
-  SD_REQUIRE(t.numel() == expect, kInvalidArgument, "%s.weight has %zu elements, expected %zu", name.c_str(), t.numel(), expect);
   SD_REQUIRE(!a.x2 && !a.temb && !a.ln_colsum && a.out_mode == kOutHalf && !a.silu_out, kInternal, "%s: not a VAE conv", name.c_str());
-  std::vector<float> host(expect);
-  retile_ohwi(t.data.data(), cout, x.C, k, false, host.data());
-  float* w = ll_.arena.alloc_n<float>(expect);
-  SD_HIP(hipMemcpy(w, host.data(), expect * sizeof(float), hipMemcpyHostToDevice));
+  const float* w = upload_conv_weight_f32(name, cout, x.C, k);
   const ConvGeom g = conv_geom(name, x, a);
   Tensor out = new_tensor(x.B, g.Ho, g.Wo, cout);
   ConvF32Desc fd;
@@ -338,17 +345,9 @@ Tensor Net::conv_w(std::vector<Op>& ops, const std::string& name, const ConvWeig
 }
 
 void Net::conv_small_n(std::vector<Op>& ops, const std::string& name, const Tensor& x, int cout, half_t* out_nhwc, float* out_nchw) {
-  ConvDesc d;
-  d.x0 = x.p;
-  d.C0 = x.C;
-  d.w = upload_conv_weight(name, cout, x.C, 3, false);
-  d.bias = upload_vec(name + ".bias", cout);
-  d.out = out_nhwc;
-  d.B = x.B; d.Hi = x.H; d.Wi = x.W; d.Ho = x.H; d.Wo = x.W;
-  d.ksize = 3; d.stride = 1; d.up = 1; d.N = cout;
-  if (f32_) {
+  if (f32_) {   // fp32 weights like every other conv of the handle (conv_f32): conv_out is not the one layer rounded to fp16
     ConvF32Desc fd;
-    fd.x = x.f(); fd.w = d.w; fd.bias = d.bias;
+    fd.x = x.f(); fd.w = upload_conv_weight_f32(name, cout, x.C, 3); fd.w_kind = 1; fd.bias = upload_vec(name + ".bias", cout);
     fd.out = out_nhwc ? reinterpret_cast<float*>(out_nhwc) : new_tensor(x.B, x.H, x.W, cout).f();
     fd.B = x.B; fd.Hi = x.H; fd.Wi = x.W; fd.Cin = x.C; fd.Ho = x.H; fd.Wo = x.W; fd.N = cout; fd.ksize = 3;
     ops.push_back([=](hipStream_t s) {
@@ -356,6 +355,14 @@ void Net::conv_small_n(std::vector<Op>& ops, const std::string& name, const Tens
       if (out_nchw) launch_nhwc_to_nchw_f32f32(fd.out, out_nchw, fd.B, fd.N, fd.Ho, fd.Wo, s);
     });
   } else {
+    ConvDesc d;
+    d.x0 = x.p;
+    d.C0 = x.C;
+    d.w = upload_conv_weight(name, cout, x.C, 3, false);
+    d.bias = upload_vec(name + ".bias", cout);
+    d.out = out_nhwc;
+    d.B = x.B; d.Hi = x.H; d.Wi = x.W; d.Ho = x.H; d.Wo = x.W;
+    d.ksize = 3; d.stride = 1; d.up = 1; d.N = cout;
     ops.push_back([=](hipStream_t s) { launch_conv_small_n(d, out_nchw, s); });
   }
   ops.back().label = "conv3x3 small-N " + name + (out_nchw ? " -> fp32 NCHW" : "");

@@ -131,6 +131,7 @@ class Net {
   // ---- build ----
   Tensor new_tensor(int B, int H, int W, int C);
   half_t* upload_conv_weight(const std::string& name, int cout, int cin, int k, bool geglu);
+  float* upload_conv_weight_f32(const std::string& name, int cout, int cin, int k);   // the same layout in fp32 (compute_fp32 handles)
   float* upload_vec(const std::string& name, int n, bool geglu = false);
   // conv uploads <name>.weight / .bias and emits the op; conv_w (fp16 only) takes device pointers
   Tensor conv(std::vector<Op>& ops, const std::string& name, const Tensor& x, const ConvArgs& a);

@@ -191,6 +191,17 @@ SYMBOLS = [
     ("sd_op_resample_coeffs", _I, [_I, _I, C.POINTER(_I), _P, _P]),
     ("sd_op_image_rgb8", _I, [_FP, _P, _I, _I, _I, _I, _FP]),
     ("sd_op_clip_input", _I, [_P, _P, _I, _I, _I, _I, _I, _I, _FP, _FP, _I, _FP]),
+    ("sd_op_conv_f32", _I, [_FP, _P, _I, _FP, _FP, _FP, _I, _I, _I, _I, _I, _I, _I, _I, _I]),
+    ("sd_op_groupnorm_f32", _I, [_FP, _FP, _FP, _FP, _I, _I, _I, _I, _I, _F, _I]),
+    ("sd_op_row_softmax", _I, [_P, _I, _I, _F, _I]),
+    ("sd_op_gemv", _I, [_P, _FP, _FP, _FP, _I, _I, _I, _I, _I, _I]),
+    ("sd_op_clip_attention", _I, [_P, _P, _I, _I, _I]),
+    ("sd_op_clip_embed", _I, [C.POINTER(C.c_int32), _P, _P, _P, _I, _I, _I]),
+    ("sd_op_clip_act", _I, [_P, C.c_size_t, _I]),
+    ("sd_op_layout", _I, [_I, _P, _P, _I, _I, _I, _I]),
+    ("sd_op_sum_half", _I, [C.POINTER(_P), _I, _P, C.c_size_t, _I]),
+    ("sd_op_vit_patch_rows", _I, [_P, _P, _I, _I, _I, _I]),
+    ("sd_op_vit_tokens", _I, [_P, _P, _P, _P, _I, _I, _I]),
 ]
 
 
@@ -1129,3 +1140,187 @@ def calibrate(device=0):
     return {"copy_gbs": round(out[0], 1), "mfma_tflops": round(out[1], 1), "empty_launch_us": round(out[2], 3),
             "chain_us": round(out[3], 3), "handover_us": round(out[4], 3), "latency_hbm_ns": round(out[5], 1),
             "latency_cache_ns": round(out[6], 1), "small_grid_us": round(out[7], 3), "cold_code_us": round(out[8], 3)}
+
+
+# ------------------------------------------------------------------------------------------------
+# the kernels that otherwise run only inside whole models (sd_mi355x.h, last section).  The wrappers check that the arrays fit
+# together (ValueError, before the library is called); what a kernel cannot do is the library's refusal (NotImplementedError).
+# ------------------------------------------------------------------------------------------------
+def conv_f32(x, w, bias=None, res=None, stride=1, upsample=False, pad_mode=0, w_kind=1):
+    """fp32 conv of an fp32 VAE handle (csrc/vae_f32.hip conv_f32_kernel).  x (B,Cin,H,W) f32; w_kind 0: w (N,Cin,k,k) rounded to f16,
+    1: w (N,Cin,k,k) f32, 2: w (Cin,N) f32, a 1x1 conv whose weights are stored [K][N]; bias (N), res (B,N,Ho,Wo) f32 or None;
+    pad_mode 1: the encoder's (0,1,0,1) padding (3x3, stride 2) -> (B,N,Ho,Wo) f32."""
+    if w_kind not in (0, 1, 2):
+        raise ValueError(f"conv_f32: w_kind {w_kind}")
+    x = f32(x)
+    w = f16(w) if w_kind == 0 else f32(w)
+    if x.ndim != 4:
+        raise ValueError("conv_f32: x must be (B, Cin, H, W)")
+    B, Cin, H, W = x.shape
+    if w_kind == 2:
+        if w.ndim != 2 or w.shape[0] != Cin:
+            raise ValueError("conv_f32: w_kind 2 takes w (Cin, N)")
+        N, k = w.shape[1], 1
+    else:
+        if w.ndim != 4 or w.shape[1] != Cin or w.shape[2] != w.shape[3] or w.shape[2] not in (1, 3):
+            raise ValueError("conv_f32: w must be (N, Cin, k, k) with k 1 or 3")
+        N, k = w.shape[0], w.shape[2]
+    if stride not in (1, 2) or pad_mode not in (0, 1) or (pad_mode == 1 and (k != 3 or stride != 2 or upsample)):
+        raise ValueError("conv_f32: stride 1 or 2; pad_mode 1 needs a 3x3 / stride-2 conv without upsample")
+    up = 2 if upsample else 1
+    extra = 1 if pad_mode else 2 * (k // 2)
+    Ho, Wo = (H * up + extra - k) // stride + 1, (W * up + extra - k) // stride + 1
+    if Ho < 1 or Wo < 1:
+        raise ValueError("conv_f32: empty output")
+    bias = None if bias is None else f32(bias)
+    res = None if res is None else f32(res)
+    if (bias is not None and bias.shape != (N,)) or (res is not None and res.shape != (B, N, Ho, Wo)):
+        raise ValueError("conv_f32: bias must be (N,), res (B, N, Ho, Wo)")
+    out = np.empty((B, N, Ho, Wo), np.float32)
+    check(lib().sd_op_conv_f32(fptr(x), ptr(w), w_kind, fptr(bias), fptr(res), fptr(out), B, Cin, H, W, N, k, stride, int(bool(upsample)),
+                               pad_mode))
+    return out
+
+
+def groupnorm_f32(x, gamma, beta, groups, eps=1e-6, silu=False):
+    """fp32 GroupNorm (+ SiLU) of an fp32 VAE handle (csrc/vae_f32.hip).  x (B,C,H,W) f32, gamma / beta (C,) -> (B,C,H,W) f32."""
+    x, gamma, beta = f32(x), f32(gamma), f32(beta)
+    if x.ndim != 4 or gamma.shape != (x.shape[1],) or beta.shape != gamma.shape or groups < 1:
+        raise ValueError("groupnorm_f32: x must be (B, C, H, W), gamma and beta (C,), groups >= 1")
+    B, Cn, H, W = x.shape
+    out = np.empty_like(x)
+    check(lib().sd_op_groupnorm_f32(fptr(x), fptr(gamma), fptr(beta), fptr(out), B, Cn, H, W, int(groups), float(eps), int(bool(silu))))
+    return out
+
+
+def row_softmax(x, scale=1.0):
+    """softmax(scale * x) over the last axis of x (rows, cols): a float16 array runs csrc/norm.hip row_softmax_kernel, a float32 one
+    csrc/vae_f32.hip row_softmax_f32_kernel.  Returns a new array of x's dtype."""
+    if not isinstance(x, np.ndarray) or x.dtype not in (np.float16, np.float32) or x.ndim != 2 or x.size == 0:
+        raise ValueError("row_softmax: x must be a non-empty (rows, cols) float16 or float32 array")
+    y = np.array(x, order="C", copy=True)
+    check(lib().sd_op_row_softmax(ptr(y), y.shape[0], y.shape[1], float(scale), int(y.dtype == np.float32)))
+    return y
+
+
+def gemv(w, bias, x, init=None, silu_in=False, silu_out=False):
+    """The time-embedding GEMV (csrc/misc.hip gemv_kernel): act_out(act_in(x) @ w.T + bias) [+ init].  w (N,K) f16, bias (N,) f32 or
+    None, x (B,K) f32, init (B,N) f32 or None (given: the launch accumulates onto it) -> (B,N) f32."""
+    w, x = f16(w), f32(x)
+    if w.ndim != 2 or x.ndim != 2 or x.shape[1] != w.shape[1]:
+        raise ValueError("gemv: w must be (N, K) and x (B, K)")
+    N, K = w.shape
+    B = x.shape[0]
+    bias = None if bias is None else f32(bias)
+    if bias is not None and bias.shape != (N,):
+        raise ValueError("gemv: bias must be (N,)")
+    if init is not None and np.shape(init) != (B, N):
+        raise ValueError("gemv: init must be (B, N)")
+    out = np.empty((B, N), np.float32) if init is None else np.array(init, dtype=np.float32, order="C", copy=True)
+    check(lib().sd_op_gemv(ptr(w), fptr(bias), fptr(x), fptr(out), B, N, K, int(bool(silu_in)), int(bool(silu_out)), int(init is not None)))
+    return out
+
+
+def clip_attention(qkv, heads):
+    """Causal attention of the text encoder (csrc/clip.hip): qkv (S, 3 D) f16 rows [q | k | v] -> (S, D) f16."""
+    qkv = f16(qkv)
+    if qkv.ndim != 2 or qkv.shape[1] % 3 or heads < 1 or (qkv.shape[1] // 3) % heads:
+        raise ValueError("clip_attention: qkv must be (S, 3 * heads * dim_head)")
+    S, D = qkv.shape[0], qkv.shape[1] // 3
+    out = np.empty((S, D), np.float16)
+    check(lib().sd_op_clip_attention(ptr(qkv), ptr(out), S, D, int(heads)))
+    return out
+
+
+def clip_embed(ids, tok, pos):
+    """Token + position embedding of the text encoder (csrc/clip.hip): ids (S,) int, tok (vocab, D), pos (S, D) f16 -> (S, D) f16;
+    ids outside [0, vocab) are clamped."""
+    ids = np.ascontiguousarray(ids, dtype=np.int32)
+    tok, pos = f16(tok), f16(pos)
+    if ids.ndim != 1 or tok.ndim != 2 or pos.shape != (ids.shape[0], tok.shape[1]):
+        raise ValueError("clip_embed: ids (S,), tok (vocab, D), pos (S, D)")
+    out = np.empty_like(pos)
+    check(lib().sd_op_clip_embed(ids.ctypes.data_as(C.POINTER(C.c_int32)), ptr(tok), ptr(pos), ptr(out), pos.shape[0], pos.shape[1],
+                                 tok.shape[0]))
+    return out
+
+
+def clip_act(x, act):
+    """The CLIP MLP activation (csrc/clip.hip clip_act_kernel) over a float16 array: act "quick_gelu" or "gelu"."""
+    if act not in ACTS:
+        raise ValueError(f"clip_act: unknown activation {act!r}")
+    y = np.array(x, dtype=np.float16, order="C", copy=True)
+    check(lib().sd_op_clip_act(ptr(y), y.size, ACTS[act]))
+    return y
+
+
+# sd_op_layout kinds by (operation, source dtype, destination dtype)
+_LAYOUTS = {("nchw_to_nhwc", "float16", "float16"): 0, ("nchw_to_nhwc", "float32", "float16"): 1,
+            ("nchw_to_nhwc", "float16", "float32"): 2, ("nchw_to_nhwc", "float32", "float32"): 3,
+            ("nhwc_to_nchw", "float16", "float32"): 4, ("nhwc_to_nchw", "float32", "float32"): 5,
+            ("bc1s_to_tokens", "float16", "float16"): 6, ("convert", "float16", "float32"): 7, ("convert", "float32", "float16"): 8}
+
+
+def layout(op, src, dst_dtype):
+    """The copy kernels at the model boundaries (csrc/misc.hip, csrc/vae_f32.hip).  op "nchw_to_nhwc": src (B,C,H,W) -> (B,H,W,C);
+    "nhwc_to_nchw": src (B,H,W,C) -> (B,C,H,W) float32; "bc1s_to_tokens": src (B,C,1,S) -> (B,S,C) float16; "convert": float16 <->
+    float32 of any array.  The pair of src.dtype and dst_dtype selects the kernel; a pair no kernel serves is a ValueError."""
+    if not isinstance(src, np.ndarray):
+        raise ValueError("layout: src must be a numpy array")
+    kind = _LAYOUTS.get((op, src.dtype.name, np.dtype(dst_dtype).name))
+    if kind is None:
+        raise ValueError(f"layout: no kernel for {op!r} from {src.dtype.name} to {np.dtype(dst_dtype).name}")
+    src = np.ascontiguousarray(src)
+    if op == "convert":
+        if src.size == 0:
+            raise ValueError("layout: empty array")
+        dims, shape = (1, 1, 1, src.size), src.shape
+    else:
+        if src.ndim != 4 or src.size == 0 or (op == "bc1s_to_tokens" and src.shape[2] != 1):
+            raise ValueError("layout: src must be a non-empty 4-d array ((B, C, 1, S) for bc1s_to_tokens)")
+        if op == "nhwc_to_nchw":
+            B, H, W, Cn = src.shape
+            shape = (B, Cn, H, W)
+        else:
+            B, Cn, H, W = src.shape
+            shape = (B, W, Cn) if op == "bc1s_to_tokens" else (B, H, W, Cn)
+        dims = (B, Cn, H, W)
+    dst = np.empty(shape, dst_dtype)
+    check(lib().sd_op_layout(kind, ptr(src), ptr(dst), *dims))
+    return dst
+
+
+def sum_half(srcs, add=False):
+    """Sum of 1 to 4 float16 arrays of one shape, fp32 accumulation in source order and one rounding (csrc/misc.hip sum_half_kernel);
+    add=True: the two-source add_half_kernel."""
+    srcs = [f16(a) for a in srcs]
+    if not srcs or any(a.shape != srcs[0].shape for a in srcs) or srcs[0].size == 0 or (add and len(srcs) != 2):
+        raise ValueError("sum_half: one or more non-empty arrays of one shape (add=True: exactly two)")
+    out = np.empty_like(srcs[0])
+    arr = (C.c_void_p * len(srcs))(*[a.ctypes.data for a in srcs])
+    check(lib().sd_op_sum_half(arr, len(srcs), ptr(out), out.size, int(bool(add))))
+    return out
+
+
+def vit_patch_rows(img, patch, row):
+    """Patch rows of the vision tower's embedding conv (csrc/vit.hip): img (B,3,I,I) f16 -> (B * (I / patch)^2, row) f16, the columns
+    behind 3 * patch * patch zero."""
+    img = f16(img)
+    if img.ndim != 4 or img.shape[1] != 3 or img.shape[2] != img.shape[3] or patch < 1 or img.shape[2] % patch or row < 3 * patch * patch:
+        raise ValueError("vit_patch_rows: img (B, 3, I, I), I a multiple of patch, row >= 3 * patch * patch")
+    B, I = img.shape[0], img.shape[2]
+    out = np.empty((B * (I // patch) ** 2, row), np.float16)
+    check(lib().sd_op_vit_patch_rows(ptr(img), ptr(out), B, I, int(patch), int(row)))
+    return out
+
+
+def vit_tokens(patch, cls, pos):
+    """Class token + position embeddings of the vision tower (csrc/vit.hip): patch (B, S - 1, D), cls (D,), pos (S, D) f16 ->
+    (B, S, D) f16."""
+    patch, cls, pos = f16(patch), f16(cls), f16(pos)
+    if patch.ndim != 3 or cls.shape != (patch.shape[2],) or pos.shape != (patch.shape[1] + 1, patch.shape[2]):
+        raise ValueError("vit_tokens: patch (B, S - 1, D), cls (D,), pos (S, D)")
+    B, S, D = patch.shape[0], patch.shape[1] + 1, patch.shape[2]
+    out = np.empty((B, S, D), np.float16)
+    check(lib().sd_op_vit_tokens(ptr(patch), ptr(cls), ptr(pos), ptr(out), B, S, D))
+    return out

@@ -89,3 +89,53 @@ def test_vae_fp32_handle_keeps_fp32_weights():
     sd16 = weights.to_torch({k: v.astype(np.float16).astype(np.float32) for k, v in sd32.items()})
     rounded = vae_ref.vae_decode(sd16, cfg, torch.from_numpy(z)).numpy()
     assert np.abs(rounded - ref).max() > 2e-4 * np.abs(ref).max()
+
+
+def _conv_out_checkpoint(shapes, prefix, seed, gain):
+    """An fp32 checkpoint whose conv_out.weight is 1e-5 * randn - fp16's subnormal range, where rounding a weight to fp16 costs
+    2^-25 absolute, 1.7e-3 of the weight's scale - and (the same values) with that one tensor rounded to fp16.  conv_out.bias is
+    zero and conv_norm_out's affine is scaled by 1e3, so that conv_out's own product carries the output: with the stock bias and
+    unit-scale activations the output is the bias to within 1e-3, and no rounding of the weights could reach _close32's bound."""
+    sd32 = dict(weights.make_state_dict(shapes, seed=seed, dtype=np.float32, gain=gain))
+    key = prefix + "conv_out.weight"
+    sd32[key] = (1e-5 * weights.seeded_normal(sd32[key].shape, seed + 2)).astype(np.float32)
+    sd32[prefix + "conv_out.bias"] = np.zeros_like(sd32[prefix + "conv_out.bias"])
+    for name in ("conv_norm_out.weight", "conv_norm_out.bias"):
+        sd32[prefix + name] = (sd32[prefix + name] * np.float32(1e3)).astype(np.float32)
+    rounded = dict(sd32)
+    rounded[key] = sd32[key].astype(np.float16).astype(np.float32)
+    assert not np.array_equal(rounded[key], sd32[key])
+    return sd32, rounded
+
+
+def _assert_rounding_conv_out_shows(ref, rounded, what):
+    """The precondition, on the oracle itself: conv_out.weight rounded to fp16 misses the fp32 result by >= 5 x _close32's bound."""
+    gap = float(np.abs(rounded - ref).max())
+    bound = 2e-4 * float(np.abs(ref).max()) + 1e-6
+    print(f"{what}: fp16-rounded conv_out.weight is {gap:.3e} away, {gap / bound:.1f} x the bound {bound:.3e}")
+    assert gap >= 5.0 * bound, f"{what}: rounding conv_out.weight moves the oracle by {gap:.3e}, under 5 x the bound {bound:.3e}"
+
+
+def test_vae_decoder_fp32_keeps_conv_out_weights_fp32():
+    """decoder.conv_out runs through Net::conv_small_n, not Net::conv: an fp32 handle must give it fp32 weights like every other conv."""
+    cfg = vae_ref.VAE_CONFIGS["mini"]
+    sd32, rounded = _conv_out_checkpoint(vae_ref.vae_decoder_param_shapes(cfg), "decoder.", 67, 1.6)
+    hw = 8
+    z = (weights.seeded_normal((1, 4, hw, hw), 68) / 0.18215).astype(np.float32)
+    ref = vae_ref.vae_decode(weights.to_torch(sd32), cfg, torch.from_numpy(z)).numpy()
+    _assert_rounding_conv_out_shows(ref, vae_ref.vae_decode(weights.to_torch(rounded), cfg, torch.from_numpy(z)).numpy(), "mini decoder")
+    vae = HipVaeDecoder(cfg, sd32, batch=1, latent_height=hw, latent_width=hw, dtype=np.float32)
+    _close32(vae(z=z)["image"], ref, "fp32 VAE decoder with a conv_out.weight in fp16's subnormal range")
+    vae.close()
+
+
+def test_vae_encoder_fp32_keeps_conv_out_weights_fp32():
+    cfg = vae_ref.VAE_CONFIGS["mini"]
+    sd32, rounded = _conv_out_checkpoint(vae_ref.vae_encoder_param_shapes(cfg), "encoder.", 71, 1.4)
+    hw = 40
+    x = np.tanh(weights.seeded_normal((1, 3, hw, hw), 72)).astype(np.float32)
+    ref = vae_ref.vae_encode(weights.to_torch(sd32), cfg, torch.from_numpy(x)).numpy()
+    _assert_rounding_conv_out_shows(ref, vae_ref.vae_encode(weights.to_torch(rounded), cfg, torch.from_numpy(x)).numpy(), "mini encoder")
+    enc = HipVaeEncoder(cfg, sd32, batch=1, height=hw, width=hw, dtype=np.float32)
+    _close32(enc(x=x)["latent"], ref, "fp32 VAE encoder with a conv_out.weight in fp16's subnormal range")
+    enc.close()
