@@ -452,6 +452,20 @@ int sd_op_conv2d_w8a8_halo(const void* x, const void* x1, const int8_t* wq, cons
  * tap-major - the K order of the fp16 halo conv at one byte per weight, so a (row, tap, 64-channel chunk) is 64 contiguous bytes.
  * Ctot a multiple of 64.  *bytes = its size (Cout * Ctot * 9); packed may be NULL to ask for the size alone. */
 int sd_op_w8a8_pack_halo(const int8_t* wq, int Cout, int Ctot, int8_t* packed, size_t* bytes);
+/* The upsampler conv (Upsample2D, unet.py:498-500: nearest x2, then a 3x3 / pad-1 conv) as four 2x2 convs on the low-res image, one per
+ * output phase (Y & 1, X & 1): plan tile 21, conv3x3_halo_sp.hip, 4/9 of the multiply-adds.  sd_op_subpixel_fold is the host-only fold
+ * a handle applies once: w (Cout, Cin, 3, 3) f16 (w_f32 = 0) or f32 (1) -> folded (4 phases p = 2a + b, Cout, 4 taps t = 2dy + dx, Cin)
+ * f16, tap t at low-res offset (a + dy - 1, b + dx - 1); every folded weight is the fp32 sum of its 1, 2 or 4 source weights in
+ * (ky, kx) order, rounded to f16 once.  *halves = 16 * Cout * Cin; folded may be NULL to ask for the size alone.
+ * sd_op_subpixel_refusal (host only): the first condition a conv of this shape misses for plan tile 21, "" when it is admitted.
+ * sd_op_conv2d_subpixel: x (B, Cin, H, W) f16, w (Cout, Cin, 3, 3) f16 folded as above, bias (Cout) f32 / res (B, Cout, 2H, 2W) f16
+ * or NULL -> out (B, Cout, 2H, 2W) f16; staging: plan tile 7's ring code (2: three stages, anything else four), splitk 0: the plan's
+ * rule; plan_out = {21, staging, splitk, slab}.  The device output starts as NaN patterns in front of a guard: SD_ERR_INTERNAL when
+ * the guard was written.  SD_ERR_INVALID_ARGUMENT naming the refusal for a shape tile 21 does not take. */
+int sd_op_subpixel_fold(const void* w, int w_f32, int Cout, int Cin, void* folded, size_t* halves);
+int sd_op_subpixel_refusal(int ksize, int stride, int up, int C0, int C1, int N, int B, int Hi, int Wi, int out_mode, char* text, int text_bytes);
+int sd_op_conv2d_subpixel(const void* x, const void* w, const float* bias, const void* res, void* out, int B, int Cin, int H, int W, int Cout,
+                          int splitk, int staging, int* plan_out, int iters, float* ms);
 /* No reference counterpart as an operator; the layer it stands for is any Linear the reference's UNet writes as a 1x1 conv (unet.py:533-551
  * proj_in, :62-118 to_out) under quantize_cumulative_config (activation_quantization.py:141-203).  The single-source small-M 1x1 GEMM in
  * W8A8 (plan tile 19, smgemm_i8.hip; semantics at sd_weights_quantize_w8a8 - the same function of its inputs as sd_op_conv2d_w8a8:
@@ -638,7 +652,8 @@ int sd_op_sched_step(const float* noise_pred, float* latents, float* hist, const
 /* Which plan does the library give a conv / 1x1 GEMM of this shape?  Host only, read only: needs no GPU and launches nothing.
  * The descriptor as plain ints: C0 (+ C1 > 0: a second, channel-concatenated source) -> N over B x Ho x Wo outputs, up = 1 / 2 (nearest
  * upsample in the gather), out_mode 0 plain, 1 token-transposed, 2 GEGLU; flags: 1 LayerNorm fold, 2 timestep embedding, 4 residual,
- * 8 GroupNorm statistics wanted from the epilogue, 16 bias, 32 explicit zero padding (the stride-2 downsample of the VAE encoder);
+ * 8 GroupNorm statistics wanted from the epilogue, 16 bias, 32 explicit zero padding (the stride-2 downsample of the VAE encoder),
+ * 64 the upsampler as four 2x2 phase convs (plan tile 21 or SD_ERR_INVALID_ARGUMENT naming the refusal; without it no answer changes);
  * n_trans > 0: fused q|k|v with that many row-major columns; n_twins: GroupNorm twins written by the slab combine; gnf_groups > 0:
  * GroupNorm of the input folded into the launch; tile / staging / splitk: a forced plan (0 = the library's); copies: which pre-tiled
  * weight copies exist (1 wstream, 2 wsgemm, 4 bvgemm; -1 = the ones the library's handle would hold).

@@ -598,6 +598,73 @@ int sd_op_w8a8_pack_halo(const int8_t* wq, int Cout, int Ctot, int8_t* packed, s
   });
 }
 
+// The fold of an upsampler's 3x3 weights into the four 2x2 phase matrices of plan tile 21 (weight_prep.h subpixel_fold).  Host only.
+int sd_op_subpixel_fold(const void* w, int w_f32, int Cout, int Cin, void* folded, size_t* halves) {
+  return guarded([&] {
+    SD_REQUIRE(w && halves, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(Cout > 0 && Cin > 0, kInvalidArgument, "subpixel_fold: Cout %d Cin %d", Cout, Cin);
+    *halves = subpixel_fold_halves(Cout, Cin);
+    if (!folded) return;
+    if (w_f32) subpixel_fold(reinterpret_cast<const float*>(w), Cout, Cin, reinterpret_cast<half_t*>(folded));
+    else subpixel_fold(f16(w), Cout, Cin, reinterpret_cast<half_t*>(folded));
+  });
+}
+
+// Why plan tile 21 refuses a conv of this shape ("" when it takes it): halo_sp_refusal (conv_plan.h).  Host only.
+int sd_op_subpixel_refusal(int ksize, int stride, int up, int C0, int C1, int N, int B, int Hi, int Wi, int out_mode, char* text, int text_bytes) {
+  return guarded([&] {
+    SD_REQUIRE(text && text_bytes >= 1, kInvalidArgument, "bad subpixel_refusal arguments");
+    static const half_t present = 0;   // the predicate only tests the pointer
+    ConvDesc d;
+    d.C0 = C0;
+    if (C1 > 0) d.x1 = &present, d.C1 = C1;
+    d.B = B; d.Hi = Hi; d.Wi = Wi;
+    d.Ho = stride > 0 ? Hi * up / stride : 0; d.Wo = stride > 0 ? Wi * up / stride : 0;
+    d.ksize = ksize; d.stride = stride; d.up = up; d.N = N; d.out_mode = out_mode;
+    const char* why = halo_sp_refusal(d);
+    const std::string line = why ? why : "";
+    SD_REQUIRE((int)line.size() < text_bytes, kInvalidArgument, "subpixel_refusal: the text buffer holds %d bytes, the line needs %zu", text_bytes, line.size() + 1);
+    memcpy(text, line.c_str(), line.size() + 1);
+  });
+}
+
+// Nearest-x2 upsample + 3x3 / pad-1 conv as plan tile 21: w (Cout, Cin, 3, 3) f16 is folded by subpixel_fold, as a handle folds it.
+// The output buffer starts as NaN patterns in front of a guard that must survive; staging: tile 7's ring code (2: three stages, else
+// four), splitk 0: the plan's rule.  plan_out = {tile, staging, splitk, slab}.
+int sd_op_conv2d_subpixel(const void* x, const void* w, const float* bias, const void* res, void* out, int B, int Cin, int H, int W, int Cout, int splitk,
+                          int staging, int* plan_out, int iters, float* ms) {
+  return guarded([&] {
+    SD_REQUIRE(x && w && out && plan_out, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0 && splitk >= 0 && staging >= 0 && staging <= 5 && staging != 1, kInvalidArgument,
+               "conv2d_subpixel: empty problem, splitk %d or staging %d (plan tile 7's ring codes 0, 2-5)", splitk, staging);
+    ConvDesc d;
+    d.C0 = Cin;
+    d.B = B; d.Hi = H; d.Wi = W; d.Ho = 2 * H; d.Wo = 2 * W;
+    d.ksize = 3; d.up = 2; d.N = Cout;
+    d.subpix = true;
+    d.staging = staging;
+    d.splitk = splitk;
+    SD_REQUIRE(conv_fast_path_ok(d) && halo_sp_ok(d), kInvalidArgument, "conv2d_subpixel: plan tile 21 (conv3x3_halo_sp.hip) does not take this shape: %s (Cin=%d Cout=%d %dx%d)",
+               halo_sp_refusal(d) ? halo_sp_refusal(d) : "off the MFMA path", Cin, Cout, H, W);
+    std::vector<half_t> folded(subpixel_fold_halves(Cout, Cin));
+    subpixel_fold(f16(w), Cout, Cin, folded.data());
+    Scratch sc;
+    d.x0 = upload_nhwc(sc, x, B, Cin, H, W);
+    d.w = sc.dev<half_t>(folded.size(), folded.data());
+    d.bias = bias ? sc.dev<float>(Cout, bias) : nullptr;
+    if (res) d.res = upload_nhwc(sc, res, B, Cout, d.Ho, d.Wo);
+    const size_t n_out = (size_t)B * d.Ho * d.Wo * Cout;
+    half_t* dout = guarded_buf<half_t>(sc, n_out, kOpGuard);
+    d.out = dout;
+    const ConvPlan p = conv_plan(d);
+    plan_out[0] = p.tile; plan_out[1] = p.staging; plan_out[2] = p.splitk; plan_out[3] = p.slab ? 1 : 0;
+    ConvWorkspace ws = workspace_for(sc, {d});
+    sc.timed(iters, ms, [&] { launch_conv(d, ws, sc.stream); });
+    check_guard(sc, dout, n_out, kOpGuard, "conv2d_subpixel");
+    download_nchw(dout, out, B, Cout, d.Ho, d.Wo);
+  });
+}
+
 // Every check runs on the host in front of the first device call (Scratch), in the order the header lists them.
 int sd_op_gemm_w8a8(const void* x, const int8_t* wq, const float* w_scale, float act_absmax, const float* bias, const void* res, void* out, int B,
                     int Cin, int H, int W, int Cout, int bm, int* plan_out, int iters, float* ms) {
@@ -1425,6 +1492,7 @@ static ConvPlan query_conv_plan(int ksize, int stride, int up, int C0, int C1, i
   if (flags & 8) d.gn_partial = const_cast<float*>(present), d.gn_groups = 32;
   if (flags & 16) d.bias = present;
   if (flags & 32) d.pad = 0;
+  if (flags & 64) d.subpix = true;   // the upsampler as four 2x2 phase convs: plan tile 21 or a refusal
   if (n_trans > 0) d.out_t = const_cast<half_t*>(ph), d.n_trans = n_trans, d.ldT = Ho * Wo;
   d.n_twins = n_twins;
   if (gnf_groups > 0) {   // GroupNorm of the input folded into this launch, as the UNet's resnets / transformers ask for it

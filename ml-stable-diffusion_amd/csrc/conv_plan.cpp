@@ -258,6 +258,47 @@ bool halo_ks_ok(const ConvDesc& d) {
          d.C0 % BK == 0 && c1 % BK == 0 && d.N % 4 == 0;
 }
 
+const char* halo_sp_refusal(const ConvDesc& d) {
+  if (d.x1) return "a second source";
+  if (d.ksize != 3) return "not a 3x3 conv";
+  if (d.stride != 1) return "stride is not 1";
+  if (d.up != 2) return "no nearest-x2 upsample (up is not 2)";
+  if (d.pad >= 0) return "explicit padding";
+  if (d.out_mode != kOutHalf) return "the output mode is not plain fp16 (GEGLU / transposed)";
+  if (d.ln_colsum || d.out_t) return "a LayerNorm fold / fused q|k|v epilogue";
+  if (d.Ho != 2 * d.Hi || d.Wo != 2 * d.Wi) return "the output is not twice the input";
+  if (d.Hi < 8) return "Hi < 8";
+  if (d.Wi < 8) return "Wi < 8";
+  if (d.C0 % BK != 0) return "C0 is no multiple of 64";
+  if (d.N % 4 != 0) return "N is no multiple of 4";
+  if (d.gnf_partial) return "GroupNorm in the loader";
+  if (d.n_twins > 0) return "GroupNorm twins";
+  if (d.cw.kind != WeightSource::Fp16) return "a compressed weight source";
+  if (d.debug) return "an ablation build";
+  const size_t lim = (size_t)1 << 31;
+  if ((size_t)d.B * d.Hi * d.Wi * d.C0 * 2 >= lim || (size_t)16 * d.N * d.C0 * 2 >= lim) return "an operand of 2 GiB or more";
+  return nullptr;
+}
+
+// Which upsampler shapes run as tile 21 on the library's own rule: those whose STEP measured faster with it than without (graph
+// replay, interleaved pairs with disjoint ranges; LAB_NOTES.md round 28), keyed like a tuned_convs.inc row by (Ctot, N, M of the output).
+bool subpixel_wanted(const ConvDesc& d) {
+  static const int mode = tune_env_int("SD_UP_SUBPIX", 1);
+  if (mode == 0 || !halo_sp_ok(d)) return false;
+  const int M = d.B * d.Ho * d.Wo;
+  static const int only_m = tune_env_int("SD_UP_SUBPIX_M", 0);   // mode 2 on the one shape with this many output pixels: a candidate's own A/B
+  if (mode >= 2) return only_m == 0 || only_m == M;
+  struct Shape { int ctot, n, m; };
+  static const Shape kMeasured[] = {
+      {1280, 1280, 2048},   // SD2.1-base up_blocks.1, 16x16 -> 32x32 at CFG batch 2: 65.4 -> 45.4 us in sequence
+      {640, 640, 8192},     // SD2.1-base up_blocks.2, 32x32 -> 64x64: 59.5 -> 39.4 us in sequence
+      // (1280 -> 1280, 8x8 -> 16x16, M = 512 is weight-stream-bound and reads 52 MB instead of 29.5: 27.8 -> 31.2 us in sequence, not taken)
+      {0, 0, 0}};   // (terminator; a row of zeros matches nothing)
+  for (const Shape& s : kMeasured)
+    if (s.ctot == d.C0 && s.n == d.N && s.m == M && s.ctot != 0) return true;
+  return false;
+}
+
 bool gemm_pipe_ok(int ksize, int stride, int up, int M, int N, int K, int C0, int C1) {
   const size_t lim = (size_t)1 << 31;
   return ksize == 1 && stride == 1 && up == 1 && (size_t)M * std::max(C0, C1) * 2 < lim && (size_t)N * K * 2 < lim;
@@ -274,6 +315,20 @@ bool conv_fast_path_ok(const ConvDesc& d) {
 }
 
 namespace {
+
+// resolved split-K of plan tile 21: tile 7's rule (workgroups for every CU, a split keeps >= 2 chunks) over its grid of
+// 4 phases x low-res tiles x n-tiles; whole 64-channel chunks, no empty splits
+int subpix_splits(const ConvDesc& d, const Dims& a) {
+  const int steps = a.Ctot / BK;
+  int s = d.splitk;
+  if (s == 0) {
+    const long blocks = 4L * d.B * cdiv(d.Wi, 16) * cdiv(d.Hi, 8) * cdiv(a.N, 64);
+    s = 1;
+    while (blocks * s < 192 && s < 16 && steps / (s * 2) >= 2) s *= 2;
+  }
+  s = std::min(std::max(s, 1), steps);
+  return cdiv(steps, cdiv(steps, s));
+}
 
 // the plan in the wire format: tile, code, resolved split-K, slab, workspace
 ConvPlan plan_codes(const ConvDesc& d) {
@@ -293,6 +348,18 @@ ConvPlan plan_codes(const ConvDesc& d) {
     SD_REQUIRE(conv_fast_path_ok(d) && cw.stream && cw.scale && d.staging >= 0 && d.staging <= 2 && smgeglu_i8_shape_ok(d, d.staging), kInvalidArgument,
                "plan tile 20 (smgeglu_i8.hip, int8) needs the int8 weights, the scales and an un-folded shape of the GEGLU kernel with K <= %d "
                "(k=%d C0=%d C1=%d N=%d M=%d mode=%d ln=%d)", kSmI8MaxK, d.ksize, d.C0, d.x1 ? d.C1 : 0, d.N, d.B * d.Ho * d.Wo, d.out_mode, d.ln_colsum ? 1 : 0);
+  // the sub-pixel upsampler holds the folded matrix and nothing else: tile 21 takes it or nobody does (no table row, no tuner candidate)
+  if (d.subpix) {
+    SD_REQUIRE(conv_fast_path_ok(d) && halo_sp_ok(d) && (d.tile == 0 || d.tile == 21), kInvalidArgument,
+               "plan tile 21 (conv3x3_halo_sp.hip) does not take this conv: %s (k=%d stride=%d up=%d C0=%d C1=%d N=%d %dx%d tile=%d)",
+               halo_sp_refusal(d) ? halo_sp_refusal(d) : "another tile is pinned", d.ksize, d.stride, d.up, d.C0, d.x1 ? d.C1 : 0, d.N, d.Hi, d.Wi, d.tile);
+    const Dims a = dims_of(d);
+    ConvPlan r{21, d.staging ? d.staging : 3, 1, false, 0};
+    r.splitk = subpix_splits(d, a);
+    r.slab = r.splitk > 1;
+    r.workspace_bytes = slab_bytes(a, r.splitk, r.slab);
+    return r;
+  }
   if (!conv_fast_path_ok(d)) return ConvPlan{-1, 0, 1, false, 0};
   // a compressed weight source, in front of the tuner candidate, the tables and every rule: nothing moves it
   switch (cw.kind) {
@@ -388,6 +455,7 @@ ConvPlan plan_codes(const ConvDesc& d) {
 //              output (kOutHalfT) has register staging and rings of 2 / 3 stages only.
 //   tile 7:    0 / 2 / 3 / 4 / 5 = 2 / 3 / 4 / 6 / 8 weight stages; GroupNorm in the loader: 4 stages from code 3 where its table fits, else 3
 //   tile 18:   tile 7's codes; the int8 kernel has rings of 2 / 3 / 4 stages, a deeper code runs the 4-stage one
+//   tile 21:   tile 7's codes; the sub-pixel kernel has rings of 3 / 4 stages: 2 = 3 stages, anything else 4
 //   tiles 9 / 14 / 17: 4 = four waves per workgroup, anything else eight      tile 11: 1-6 = the variant, anything else the library's choice
 //   tiles 12 / 15 / 19 / 13 / 16 / 20: 1 / 2 = the lower / higher tile (32 / 64, 128 / 256 rows), 0 = by the shape
 void decode_plan(const ConvDesc& d, ConvPlan& p) {
@@ -418,6 +486,12 @@ void decode_plan(const ConvDesc& d, ConvPlan& p) {
     tile_dims(7, p.bm, p.bn);
     p.kernel = ConvKernel::HaloI8;
     p.stages = code >= 3 ? 4 : code == 2 ? 3 : 2;
+    return;
+  }
+  if (p.tile == 21) {
+    tile_dims(7, p.bm, p.bn);
+    p.kernel = ConvKernel::HaloSubpix;
+    p.stages = code == 2 ? 3 : 4;
     return;
   }
   tile_dims(p.tile, p.bm, p.bn);
@@ -477,6 +551,7 @@ std::string conv_plan_kernel_name(const ConvPlan& p) {
     case ConvKernel::GemmPipe: return "gemm_pipe " + tile + ring;
     case ConvKernel::HaloKs: return "halo_ks" + ring;
     case ConvKernel::HaloI8: return "halo_i8" + ring;
+    case ConvKernel::HaloSubpix: return "conv3x3_halo_sp" + ring;
     case ConvKernel::Wstream: return "wstream waves" + std::to_string(p.waves);
     case ConvKernel::WstreamPal: return "wstream_pal waves" + std::to_string(p.waves);
     case ConvKernel::WstreamI8: return "wstream_i8 waves" + std::to_string(p.waves);
@@ -501,6 +576,7 @@ std::string conv_plan_kernel_name(const ConvPlan& p) {
 size_t conv_workspace_bytes(const ConvDesc& d) {
   if (!conv_fast_path_ok(d) || pal_gemm(d) || pal_geglu(d) || i8_gemm(d) || i8_geglu(d)) return 0;   // (tiles 15 / 16 / 19 / 20: no slabs)
   const Dims a = dims_of(d);
+  if (d.subpix) return halo_sp_ok(d) ? slab_bytes(a, subpix_splits(d, a), false) : 0;   // (tile 21: pinned, no candidate or table row moves its split)
   const Plan p = choose_plan(d, a);
   int splits = (switches().tuning && can_split(d)) ? std::max(p.splitk, 16) : p.splitk;
   const bool stream = can_stream(d) || ((pal_stream(d) || i8_stream(d)) && can_split(d) && wstream_shape_ok(d));   // tiles 14 / 17 as tile 9
@@ -510,7 +586,7 @@ size_t conv_workspace_bytes(const ConvDesc& d) {
 
 ConvWeightCopies conv_plan_copies(const ConvDesc& d0) {
   ConvWeightCopies c{false, false, false};
-  if (!conv_fast_path_ok(d0)) return c;
+  if (!conv_fast_path_ok(d0) || d0.subpix) return c;   // (tile 21 reads the folded matrix alone)
   ConvDesc d = d0;
   d.w_tiled = d.w_ws = d.w_bv = nullptr;
   const Switches& sw = switches();
@@ -647,6 +723,9 @@ void conv_plan_log(const ConvDesc& d, const ConvPlan& p, int n_fast) {
   else if (p.tile == 18)
     fprintf(stderr, "[sd conv] k%d s%d up%d C0=%d C1=%d M=%d N=%d K=%d mode=%d tile=%d splitk=%d bits=8\n", d.ksize, d.stride, d.up, d.C0, c1, a.M, a.N,
             a.K, d.out_mode, p.tile, p.splitk);
+  else if (p.tile == 21)
+    fprintf(stderr, "[sd conv] k%d s%d up%d C0=%d C1=%d M=%d N=%d K=%d mode=%d tile=%d splitk=%d subpix K'=%d\n", d.ksize, d.stride, d.up, d.C0, c1, a.M,
+            a.N, a.K, d.out_mode, p.tile, p.splitk, 4 * a.Ctot);
   else
     fprintf(stderr, "[sd conv] k%d s%d up%d C0=%d C1=%d M=%d N=%d K=%d mode=%d tile=%d splitk=%d\n", d.ksize, d.stride, d.up, d.C0, c1, a.M, a.N,
             a.K, d.out_mode, p.tile, p.splitk);

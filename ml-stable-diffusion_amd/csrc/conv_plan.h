@@ -8,8 +8,8 @@
 
 namespace sd {
 
-// the kernel a plan launches (tile -1 / 1-4 / 7 / 18 / 9 / 14 / 17 / 10 / 11 / 12 / 15 / 19 / 13 / 16 / 20 of the wire format below)
-enum class ConvKernel { Generic, Igemm, GemmPipe, HaloKs, HaloI8, Wstream, WstreamPal, WstreamI8, Wsgemm, Bvgemm, Smgemm, SmgemmPal, SmgemmI8, Smgeglu, SmgegluPal, SmgegluI8 };
+// the kernel a plan launches (tile -1 / 1-4 / 7 / 18 / 21 / 9 / 14 / 17 / 10 / 11 / 12 / 15 / 19 / 13 / 16 / 20 of the wire format below)
+enum class ConvKernel { Generic, Igemm, GemmPipe, HaloKs, HaloI8, HaloSubpix, Wstream, WstreamPal, WstreamI8, Wsgemm, Bvgemm, Smgemm, SmgemmPal, SmgemmI8, Smgeglu, SmgegluPal, SmgegluI8 };
 
 struct ConvPlan {
   // The wire format: what ConvDesc::tile / staging pins, tuned_convs.inc rows, SD_PLAN_TABLE and sd_tune_set_candidate say and what
@@ -21,6 +21,7 @@ struct ConvPlan {
                    // 19: the small-M GEMM from int8 weights and activations (smgemm_i8.hip, tile 12's tiles; never the library's own answer),
                    // 20: the GEGLU projection from int8 weights and int8 activations written by the LayerNorm in front of it
                    // (smgeglu_i8.hip, tile 13's tiles at both heights; never the library's own answer);
+                   // 21: the upsampler conv as four 2x2 phase convs on the low-res halo (conv3x3_halo_sp.hip; only with ConvDesc::subpix);
                    // -1 = not on the MFMA path (launch_conv_generic)
   int staging;     // per-family code: decode_plan
   int splitk;      // resolved: what the launch runs, no empty splits (halo: over 64-channel chunks; tile 9: the slab count)
@@ -29,7 +30,7 @@ struct ConvPlan {
   // What the codes mean for this descriptor, resolved once by conv_plan(): all a launcher reads.
   ConvKernel kernel = ConvKernel::Generic;
   int bm = 0, bn = 0;        // Igemm / GemmPipe / HaloKs / HaloI8 (128 x 64, as its tile counts): tile rows x columns; Smgemm* / Smgeglu: bm, tile rows
-  int stages = 0;            // Igemm / GemmPipe / HaloKs / HaloI8: the ring depth that runs, after the fall-back to one that fits the LDS
+  int stages = 0;            // Igemm / GemmPipe / HaloKs / HaloI8 / HaloSubpix: the ring depth that runs, after the fall-back to one that fits the LDS
   int kgroups = 1;           // Igemm: 2 = in-workgroup split-K, two K groups of four waves with a ring each
   bool reg_staged = false;   // Igemm: A / B travel HBM -> VGPR -> LDS (the A/B reference form), two stages
   int waves = 0;             // Wstream*: waves (K slices) per workgroup, 4 or 8
@@ -75,6 +76,7 @@ void conv_plan_log(const ConvDesc& d, const ConvPlan& p, int n_fast = 0);
 
 // What launches, as one line (sd_op_conv_plan_kernel): the kernel's name, then only the fields that kernel has -
 //   "igemm <bm>x<bn> ring<stages>[ kg2][ regs]"    "gemm_pipe <bm>x<bn> ring<stages>"    "halo_ks ring<stages>"    "halo_i8 ring<stages>"
+//   "conv3x3_halo_sp ring<stages>"
 //   "wstream waves<n>"   "wstream_pal waves<n>"    "wstream_i8 waves<n>"                 "wsgemm"    "bvgemm v<variant>"
 //   "smgemm bm<bm>"      "smgemm_pal bm<bm>"       "smgemm_i8 bm<bm>"                    "smgeglu bm<bm>"    "smgeglu_pal bm<bm>"
 //   "smgeglu_i8 bm<bm>"  "generic"
@@ -93,6 +95,14 @@ bool conv_reduce_stats_on();   // SD_REDUCE_STATS: the slab combine also leaves 
 // shape rules and tile geometry shared by the planner and the launchers
 constexpr int kConvBK = 64;   // K step (halves) of the MFMA kernels
 bool halo_ks_ok(const ConvDesc& d);
+// Plan tile 21 (ConvDesc::subpix): the general admissibility - halo_ks_ok's conditions on the LOW-RES image (3x3, stride 1, up 2,
+// kOutHalf, C0 % 64 == 0, N % 4 == 0, Hi >= 8, Wi >= 8), one source, fp16 weights, no GroupNorm loader, no twins, no LayerNorm fold /
+// q|k|v, 32-bit buffer offsets.  halo_sp_refusal names the first condition a descriptor misses, nullptr when it misses none.
+const char* halo_sp_refusal(const ConvDesc& d);
+inline bool halo_sp_ok(const ConvDesc& d) { return halo_sp_refusal(d) == nullptr; }
+// The shapes the library takes tile 21 for on its own: the list measured in a step, in the manner of conv_plan_is_tuned.
+// SD_UP_SUBPIX (with SD_TUNE): 0 = none, 1 = the list (the default), 2 = every shape halo_sp_ok admits (measuring, small handles).
+bool subpixel_wanted(const ConvDesc& d);
 bool gemm_pipe_ok(int ksize, int stride, int up, int M, int N, int K, int C0, int C1);
 
 // LDS budgets, stated once: decode_plan picks the ring that runs by them, the launchers assert them per instantiation.

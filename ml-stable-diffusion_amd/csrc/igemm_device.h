@@ -20,6 +20,8 @@ const half_t* zero_chunk();
 int launch_halo_ks(const ConvDesc& d, const ConvPlan& p, float* partial, hipStream_t s);
 // conv3x3_halo_i8.hip: the launch of plan tile 18 (d.cw of kind I8Halo), same return
 int launch_halo_i8(const ConvDesc& d, const ConvPlan& p, float* partial, hipStream_t s);
+// conv3x3_halo_sp.hip: the launch of plan tile 21 (d.subpix, d.w the folded matrix); writes no GroupNorm statistics (returns 0)
+int launch_halo_sp(const ConvDesc& d, const ConvPlan& p, float* partial, hipStream_t s);
 
 namespace {
 

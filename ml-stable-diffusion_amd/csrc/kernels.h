@@ -132,6 +132,10 @@ struct ConvDesc {
   // (needs Ho * Wo <= 256 and reduce_twin_ok; launch_conv forces the slab path whatever the plan's split-K)
   GnTwin twin[2];
   int n_twins = 0;
+  // The upsampler conv (ksize 3, stride 1, up 2, kOutHalf, one source, fp16 weights) as four 2x2 phase convs on the low-res image (plan
+  // tile 21, conv3x3_halo_sp.hip): w is then the folded matrix of weight_prep.h subpixel_fold, [4][N][4][C0], NOT the 3x3 matrix.
+  // Shapes: halo_sp_ok (conv_plan.h).  Without the flag nothing about a descriptor's plan changes.
+  bool subpix = false;
 };
 
 constexpr int kGnMaxSlabs = 256;   // entries per (sample, group) of a GroupNorm partial buffer

@@ -52,6 +52,18 @@ half_t* Net::upload_conv_weight(const std::string& name, int cout, int cin, int 
   return d;
 }
 
+// an upsampler's (Cout, Cin, 3, 3) tensor folded into the four 2x2 phase matrices of plan tile 21, [4][Cout][4][Cin] fp16 (subpixel_fold)
+half_t* Net::upload_subpixel_weight(const std::string& name, int cout, int cin) {
+  const HostTensor& t = ws_->get(name + ".weight");
+  const size_t expect = (size_t)cout * cin * 9;
+  SD_REQUIRE(t.numel() == expect, kInvalidArgument, "%s.weight has %zu elements, expected %zu (%d,%d,3,3)", name.c_str(), t.numel(), expect, cout, cin);
+  std::vector<half_t> host(subpixel_fold_halves(cout, cin));
+  subpixel_fold(t.data.data(), cout, cin, host.data());
+  half_t* d = ll_.arena.alloc_n<half_t>(host.size());
+  SD_HIP(hipMemcpy(d, host.data(), host.size() * sizeof(half_t), hipMemcpyHostToDevice));
+  return d;
+}
+
 // the same tensor in the same [Cout][k][k][Cin] layout, kept fp32: what the convs of a compute_fp32 handle read (ConvF32Desc::w_kind 1)
 float* Net::upload_conv_weight_f32(const std::string& name, int cout, int cin, int k) {
   const HostTensor& t = ws_->get(name + ".weight");
@@ -116,6 +128,10 @@ Tensor Net::conv(std::vector<Op>& ops, const std::string& name, const Tensor& x,
     ops.back().label = "absmax " + name;
   }
   if (pin.kind != WeightSource::Fp16) return conv_w(ops, name, upload_compressed(name, pin, cin, a), b, x, a);
+  // An opted-in upsampler whose weights run from fp16 (an observing store's do: the conv itself stays fp16) goes up folded, as four
+  // 2x2 phase convs on the low-res image, where the library's rule takes the shape: plan tile 21 instead of tile 7.  Every question
+  // above was asked with the unchanged up = 2 descriptor.
+  if (a.subpix && !a.silu_out && subpixel_wanted(conv_shape(name, x, a))) return conv_w(ops, name, ConvWeights(upload_subpixel_weight(name, a.cout, cin), true), b, x, a);
   return conv_w(ops, name, upload_conv_weight(name, a.cout, cin, a.k, geglu), b, x, a);
 }
 
@@ -266,6 +282,7 @@ Tensor Net::conv_w(std::vector<Op>& ops, const std::string& name, const ConvWeig
   d.tile = weights.pin.tile;
   d.staging = weights.pin.staging;
   d.splitk = weights.pin.splitk;
+  d.subpix = weights.subpix;
   Tensor out;
   if (ln && a.n_trans > 0) {   // fused q|k|v: [M][n_trans] row-major + V^T [B][cout - n_trans][ldT]
     out = new_tensor(x.B, d.Ho, d.Wo, a.n_trans);
@@ -335,7 +352,8 @@ Tensor Net::conv_w(std::vector<Op>& ops, const std::string& name, const ConvWeig
   // "+w8a8" from int8 weights and quantized activations (plan tiles 17 / 18 / 19 / 20)
   const WeightSource src = d.cw.kind;
   const std::string lnmark = ln ? "+ln" : "", palmark = "+pal" + std::to_string(d.cw.bits);
-  const std::string mark = src == WeightSource::PalGeglu ? palmark + lnmark : lnmark + (d.cw.i8() ? "+w8a8" : src != WeightSource::Fp16 ? palmark : "");
+  // "+subpix": the upsampler as four 2x2 phase convs (plan tile 21); flop below stays the algorithmic 9-tap count of the map it replaces
+  const std::string mark = d.subpix ? "+subpix" : src == WeightSource::PalGeglu ? palmark + lnmark : lnmark + (d.cw.i8() ? "+w8a8" : src != WeightSource::Fp16 ? palmark : "");
   snprintf(buf, sizeof(buf), "%s%s %d->%d @%dx%d M=%d K=%d %s #%d,%d,%d,%d,%d,%d,%d",
            k == 3 ? "conv3x3" : (geglu ? (src == WeightSource::PalGeglu ? "geglu" : "geglu1x1") : "gemm1x1"), mark.c_str(), cin, cout, d.Ho, d.Wo,
            x.B * d.Ho * d.Wo, cin * k * k, name.c_str(), kind, k, a.stride, a.up, cin, cout, x.B * d.Ho * d.Wo);

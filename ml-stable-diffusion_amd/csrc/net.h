@@ -76,6 +76,10 @@ struct ConvArgs {
   // statistics, so only call sites whose output feeds no GroupNorm set it (proj_in, the two to_out.0 and ff.net.0.proj of a transformer
   // block feed LayerNorms or GEMMs).
   bool keep_compressed = false;
+  // The call site opts in to running an upsampler conv (k 3, up 2) as four 2x2 phase convs on the low-res image (plan tile 21): the
+  // handle then uploads the folded matrix (weight_prep.h subpixel_fold, 16/9 of the bytes) INSTEAD of the 3x3 one.  Taken only where the
+  // weights run from fp16 and subpixel_wanted says so (Net::conv); a W8A8-marked or palettized upsampler runs what it ran without it.
+  bool subpix = false;
   // conv_w only - the source as int8 [M][C], written by a layernorm_q8 launch in front of this op (plan tile 20 reads nothing else; x
   // still gives the shape)
   const int8_t* x_i8 = nullptr;
@@ -86,7 +90,8 @@ struct ConvWeights {
   const half_t* w = nullptr;
   CompressedWeights cw;
   WeightPin pin;
-  ConvWeights(const half_t* fp16) : w(fp16) {}
+  bool subpix = false;   // w is the folded matrix of subpixel_fold: the conv runs as plan tile 21 (ConvDesc::subpix)
+  ConvWeights(const half_t* fp16, bool folded = false) : w(fp16), subpix(folded) {}
   ConvWeights(const CompressedWeights& c, const WeightPin& p) : cw(c), pin(p) {}
 };
 
@@ -132,6 +137,7 @@ class Net {
   Tensor new_tensor(int B, int H, int W, int C);
   half_t* upload_conv_weight(const std::string& name, int cout, int cin, int k, bool geglu);
   float* upload_conv_weight_f32(const std::string& name, int cout, int cin, int k);   // the same layout in fp32 (compute_fp32 handles)
+  half_t* upload_subpixel_weight(const std::string& name, int cout, int cin);         // a 3x3 upsampler's weights folded for plan tile 21
   float* upload_vec(const std::string& name, int n, bool geglu = false);
   // conv uploads <name>.weight / .bias and emits the op; conv_w (fp16 only) takes device pointers
   Tensor conv(std::vector<Op>& ops, const std::string& name, const Tensor& x, const ConvArgs& a);

@@ -771,8 +771,8 @@ void UNet::build_unet() {
           h = transformer(ll_.ops, p + ".attentions." + std::to_string(j), h, cfg_.attention_head_dim[lvl],
                           cfg_.transformer_layers_per_block[lvl]);
       }
-      if (i != n - 1)   // Upsample2D: nearest x2 fused into the conv's gather (unet.py:498-500)
-        h = conv(ll_.ops, p + ".upsamplers.0.conv", h, {.cout = cout, .k = 3, .up = 2});
+      if (i != n - 1)   // Upsample2D: nearest x2 fused into the conv's gather (unet.py:498-500), or folded into four 2x2 phase convs (plan tile 21)
+        h = conv(ll_.ops, p + ".upsamplers.0.conv", h, {.cout = cout, .k = 3, .up = 2, .subpix = true});
     }
     SD_REQUIRE(skips.empty(), kInternal, "skip stack not empty");
     // ---- conv_norm_out -> SiLU -> conv_out (unet.py:1044-1046), fp32 NCHW at the boundary ----

@@ -32,6 +32,39 @@ void retile_ohwi(const S* src, int cout, int cin, int k, bool geglu, D* dst) {
   }
 }
 
+// The upsampler conv as four 2x2 phase convs (conv3x3_halo_sp.hip, plan tile 21).  Nearest-x2 followed by a 3x3 / pad-1 conv equals,
+// for output phase (a, b) = (Y & 1, X & 1), a 2x2 conv over the low-res image whose tap (dy, dx) sits at low-res offset
+// (a + dy - 1, b + dx - 1) and carries the sum of the 3x3 weights that land on that low-res pixel:
+//   rows:  a = 0: dy 0 <- ky {0}, dy 1 <- ky {1, 2};   a = 1: dy 0 <- ky {0, 1}, dy 1 <- ky {2};   columns alike with b, dx, kx.
+// src [Cout][Cin][3][3] (the checkpoint's order) -> dst [4 phases p = 2a + b][Cout][4 taps t = 2dy + dx][Cin] fp16: a (phase, n) row
+// is K' = 4 Cin contiguous, tap-major then channel.  Each folded weight is the sum of its 1, 2 or 4 source values, added in fp32 in
+// the order (ky, kx) ascending and rounded to fp16 ONCE.  A sum outside the fp16 range is refused.
+inline size_t subpixel_fold_halves(int cout, int cin) { return (size_t)16 * cout * cin; }
+inline int subpixel_first(int phase_bit, int d) { return phase_bit == 0 ? d : 2 * d; }             // first source tap of fold position d
+inline int subpixel_count(int phase_bit, int d) { return (phase_bit == 0) == (d == 0) ? 1 : 2; }   // how many source taps it sums
+template <typename S>
+void subpixel_fold(const S* src, int cout, int cin, half_t* dst) {
+  SD_REQUIRE(src && dst && cout > 0 && cin > 0, kInvalidArgument, "subpixel_fold: Cout %d Cin %d", cout, cin);
+  for (int p = 0; p < 4; ++p) {
+    const int a = p >> 1, b = p & 1;
+    for (int o = 0; o < cout; ++o)
+      for (int t = 0; t < 4; ++t) {
+        const int dy = t >> 1, dx = t & 1;
+        const int ky0 = subpixel_first(a, dy), nky = subpixel_count(a, dy), kx0 = subpixel_first(b, dx), nkx = subpixel_count(b, dx);
+        half_t* row = dst + (((size_t)p * cout + o) * 4 + t) * cin;
+        for (int c = 0; c < cin; ++c) {
+          const S* w9 = src + ((size_t)o * cin + c) * 9;
+          float s = 0.f;
+          for (int ky = ky0; ky < ky0 + nky; ++ky)
+            for (int kx = kx0; kx < kx0 + nkx; ++kx) s += (float)w9[ky * 3 + kx];
+          SD_REQUIRE(std::fabs(s) <= 65504.0f, kInvalidArgument, "subpixel_fold: the folded weight of output %d input %d phase %d tap %d is %g, outside fp16",
+                     o, c, p, t, (double)s);   // (a NaN fails the comparison too)
+          row[c] = (half_t)s;
+        }
+      }
+  }
+}
+
 // LayerNorm folded into the projection behind it, one projection w [cout][cin] (+ bias or NULL):
 //   y = LN(x) . W^T + b  ==  rstd*(x . (W*gamma)^T) - rstd*mean*colsum(W*gamma) + (b + W.beta)
 // Writes rows row0 + o (geglu: geglu_row(o, cout)) of w_out [..][cin], colsum and bias_out.  gamma == beta == NULL: the weights

@@ -109,6 +109,9 @@ SYMBOLS = [
     ("sd_op_w8a8_pack", _I, [_P, _I, _I, _I, _P, C.POINTER(C.c_size_t)]),
     ("sd_op_conv2d_w8a8_halo", _I, [_P, _P, _P, _FP, _F, _FP, _FP, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_I), _I, _FP]),
     ("sd_op_w8a8_pack_halo", _I, [_P, _I, _I, _P, C.POINTER(C.c_size_t)]),
+    ("sd_op_subpixel_fold", _I, [_P, _I, _I, _I, _P, C.POINTER(C.c_size_t)]),
+    ("sd_op_subpixel_refusal", _I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.c_char_p, _I]),
+    ("sd_op_conv2d_subpixel", _I, [_P, _P, _FP, _P, _P, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_I), _I, _FP]),
     ("sd_op_gemm_w8a8", _I, [_P, _P, _FP, _F, _FP, _P, _P, _I, _I, _I, _I, _I, _I, C.POINTER(_I), _I, _FP]),
     ("sd_op_w8a8_pack_gemm", _I, [_P, _I, _I, _P, C.POINTER(C.c_size_t)]),
     ("sd_op_layernorm_q8", _I, [_P, _FP, _FP, _F, _F, _P, _I, _I, _I, _FP]),
@@ -457,6 +460,51 @@ def conv2d(x, w, bias=None, res=None, stride=1, upsample=False, tile=0, splitk=0
     check(lib().sd_op_conv2d(ptr(x), ptr(w), fptr(bias), ptr(res), ptr(out), B, Cin, H, W, Cout, k, stride,
                              int(upsample), tile, splitk, int(force_generic), iters, C.byref(ms)))
     return out, ms.value
+
+
+def subpixel_fold(w):
+    """The host fold of an upsampler's 3x3 weights into the four 2x2 phase matrices of plan tile 21 (sd_op_subpixel_fold; no GPU):
+    w (Cout, Cin, 3, 3) float16 or float32 -> (4, Cout, 4, Cin) float16, phase p = 2a + b, tap t = 2dy + dx at low-res offset
+    (a + dy - 1, b + dx - 1); fp32 sums in (ky, kx) order, one rounding."""
+    w = np.ascontiguousarray(w)
+    if w.dtype not in (np.float16, np.float32) or w.ndim != 4 or w.shape[2:] != (3, 3):
+        raise ValueError("subpixel_fold: w must be (Cout, Cin, 3, 3) float16 or float32")
+    Cout, Cin = w.shape[:2]
+    out = np.empty((4, Cout, 4, Cin), np.float16)
+    n = C.c_size_t(0)
+    check(lib().sd_op_subpixel_fold(ptr(w), int(w.dtype == np.float32), Cout, Cin, ptr(out), C.byref(n)))
+    assert n.value == out.size
+    return out
+
+
+def subpixel_refusal(C0, N, B, Hi, Wi, ksize=3, stride=1, up=2, C1=0, out_mode=0):
+    """Why plan tile 21 refuses a conv of this shape, "" when it takes it (sd_op_subpixel_refusal; no GPU)."""
+    text = C.create_string_buffer(128)
+    check(lib().sd_op_subpixel_refusal(ksize, stride, up, C0, C1, N, B, Hi, Wi, out_mode, text, len(text)))
+    return text.value.decode()
+
+
+def conv2d_subpixel(x, w, bias=None, res=None, splitk=0, staging=0, iters=1):
+    """Nearest-x2 upsample + 3x3 / pad-1 conv as four 2x2 phase convs on the low-res image (sd_op_conv2d_subpixel, plan tile 21):
+    x (B, Cin, H, W), w (Cout, Cin, 3, 3) -> (out (B, Cout, 2H, 2W) float16, plan [tile, staging, splitk, slab], ms).  staging: plan
+    tile 7's ring code (2 = three stages, else four); splitk 0 = the plan's rule."""
+    x, w = f16(x), f16(w)
+    B, Cin, H, W = x.shape
+    if w.ndim != 4 or w.shape[1:] != (Cin, 3, 3):
+        raise ValueError("conv2d_subpixel: w must be (Cout, Cin, 3, 3)")
+    Cout = w.shape[0]
+    bias = None if bias is None else f32(bias)
+    res = None if res is None else f16(res)
+    if bias is not None and bias.shape != (Cout,):
+        raise ValueError("conv2d_subpixel: bias must be (Cout,)")
+    if res is not None and res.shape != (B, Cout, 2 * H, 2 * W):
+        raise ValueError(f"conv2d_subpixel: res must be (B, Cout, 2H, 2W) = {(B, Cout, 2 * H, 2 * W)}, got {res.shape}")
+    out = np.empty((B, Cout, 2 * H, 2 * W), np.float16)
+    plan = (C.c_int * 4)()
+    ms = C.c_float(0)
+    check(lib().sd_op_conv2d_subpixel(ptr(x), ptr(w), fptr(bias), ptr(res), ptr(out), B, Cin, H, W, Cout, splitk, staging, plan, iters,
+                                      C.byref(ms)))
+    return out, list(plan), ms.value
 
 
 def conv2d_ex(x, w, bias=None, res=None, x1=None, temb=None, stride=1, upsample=False, pad_mode=0, twin=None, tile=0, splitk=0,
