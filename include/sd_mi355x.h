@@ -96,8 +96,14 @@ int sd_weights_read_palette(const sd_weights* w, const char* name, void* lut, ui
  * (proj_in, attn1.to_out.0, attn2.to_out.0), the single-source small-M 1x1 GEMM (plan tile 12 -> smgemm_i8.hip, plan tile 19, with
  * tile 12's tile height) - the same function of its inputs in all three - or, for ff.net.0.proj, the GEGLU projection (plan tile 13 ->
  * smgeglu_i8.hip, plan tile 20, at tile 13's tile height: norm3 is then not folded, one LayerNorm launch writes int8(norm3(x)) with
- * act_absmax / 127 and the GEGLU reads it - sd_op_layernorm_q8 / sd_op_geglu_w8a8); any other marked conv (LayerNorm-folded q|k|v and
- * to_q, two-source 1x1, GEGLUs off tile 13, stride 2, channel counts off the tiles) runs fp16 as before - the reference's skipped layers.
+ * act_absmax / 127 and the GEGLU reads it - sd_op_layernorm_q8 / sd_op_geglu_w8a8) - or, for attn1.to_q / to_k / to_v of a
+ * self-attention that runs them as one fused q|k|v launch, that launch (smqkv_i8.hip, plan tile 22: norm1 is then not folded, one
+ * LayerNorm launch writes int8(norm1(x)) and the launch reads it and the stacked int8 matrix - sd_op_qkv_w8a8) where ALL THREE tensors
+ * are marked with the SAME act_absmax (one int8 tensor carries one scale; the calibration below reports one value under the three
+ * names) and the shape is on tile 22's rule (C a multiple of 160 from 640 up, H * W a multiple of 16, whole 128- / 256-row tiles: the
+ * 640- and 1280-channel levels, not the 8 x 8 mid block); any other marked conv (one or two of the three, three ranges, the
+ * 320-channel level's one-launch head, attn2.to_q / to_k / to_v, the merged transformer tail, two-source 1x1, GEGLUs off tile 13,
+ * stride 2, channel counts off the tiles) runs fp16 as before - the reference's skipped layers.
  * sd_weights_w8a8_info: 1 when `name` is marked (*act_scale, may be NULL, = s_a), else 0.
  * sd_weights_observe_activations(on): handles created from the store while it is on put an absmax observer in front of every conv
  * that plan tile 17 could take (on = 1) or that plan tile 17 or 18 could take (on = 2) (sd_unet_activation_ranges) - calibration on
@@ -107,12 +113,16 @@ int sd_weights_read_palette(const sd_weights* w, const char* name, void* lut, ui
  * With the flag off the observer sets are those of the two levels above.
  * sd_weights_observe_geglus(on): a second flag of the same kind (0 / 1, effective only while the store observes) - handles created from
  * it also run, for every ff.net.0.proj plan tile 20 could take, a LayerNorm of the GEGLU's input into a scratch tensor and an observer
- * over it, named by the projection's weight; the GEGLU itself runs folded in fp16 as without the flag, so the outputs do not change. */
+ * over it, named by the projection's weight; the GEGLU itself runs folded in fp16 as without the flag, so the outputs do not change.
+ * sd_weights_observe_qkv(on): a third flag of the same kind (0 / 1, effective only while the store observes) - handles created from it
+ * also run, for every fused q|k|v launch plan tile 22 could take, a LayerNorm of norm1 into a scratch tensor and ONE observer over it,
+ * reported under the three weight names attn1.to_q / to_k / to_v with one value; the launch itself runs folded in fp16. */
 int sd_weights_quantize_w8a8(sd_weights* w, const char* name, float act_absmax, double* sq_err);
 int sd_weights_w8a8_info(const sd_weights* w, const char* name, float* act_scale);
 int sd_weights_observe_activations(sd_weights* w, int on);
 int sd_weights_observe_gemms(sd_weights* w, int on);
 int sd_weights_observe_geglus(sd_weights* w, int on);
+int sd_weights_observe_qkv(sd_weights* w, int on);
 
 /* ------------------------------------------------------------------------------------------
  * UNet / ControlNet.  Config mirrors UNet2DConditionModel.__init__ (unet.py:801-833) with the
@@ -173,9 +183,10 @@ size_t sd_unet_arena_used_bytes(const sd_unet* u);
  * (q|k|v, attn2.to_q, the merged transformer tail, GEGLU projections on 256-row tiles) was uploaded as fp16 lut[indices]. */
 int sd_unet_palette_info(const sd_unet* u, int* n_palettized, int* n_streamed, size_t* stream_bytes);
 /* W8A8 (activation_quantization.py:141-203; sd_weights_quantize_w8a8): *n_marked tensors of the handle's weight store arrived with a
- * mark; *n_applied convolutions run from int8 (plan tiles 17, 18, 19 and 20) and hold the int8 weights in their kernel's layout and one fp32
+ * mark; *n_applied convolutions run from int8 (plan tiles 17, 18, 19, 20 and 22) and hold the int8 weights in their kernel's layout and one fp32
  * scale per output channel, no fp16 copy; *bytes = the bytes of those weights and scale vectors.  n_marked - n_applied marked convs
- * stayed fp16. */
+ * stayed fp16.  A fused q|k|v launch on plan tile 22 counts its three tensors - sd_unet_w8a8_layer names them in the order to_q, to_k,
+ * to_v - and 3C * C + 4 * 3C bytes. */
 int sd_unet_w8a8_info(const sd_unet* u, int* n_marked, int* n_applied, size_t* bytes);
 /* Which convs those are: returns n_applied (>= 0) or an error code (< 0); index >= 0 fills `name` with the weight tensor of the
  * index-th of them in build order (SD_ERR_INVALID_ARGUMENT when there is no such conv), index < 0 asks for the count alone. */
@@ -404,7 +415,7 @@ int sd_op_conv2d(const void* x, const void* w, const float* bias, const void* re
  *                 (+ SiLU with twin_silu) of the result to out_twin (B, Cout, Ho, Wo) f16 - no GroupNorm launch (the low-res
  *                 conv1 -> norm2 path); refused where the combine cannot hold whole (sample, group) slices
  *   plan_out[4]   the plan the launch ran: tile (1-4 igemm.hip, 7 conv3x3_halo.hip, 9 wstream.hip, 11 bvgemm.hip, 12 smgemm.hip; the
- *                 entries of the compressed sources report theirs: 14 / 15 / 16 palettized, 17 / 18 / 19 / 20 W8A8),
+ *                 entries of the compressed sources report theirs: 14 / 15 / 16 palettized, 17 / 18 / 19 / 20 / 22 W8A8),
  *                 staging, resolved split-K, 1 if the output left through fp32 slabs; all -1: the direct (non-MFMA) kernels
  * res / out are (B, Cout, Ho, Wo). */
 int sd_op_conv2d_ex(const void* x, const void* x1, const void* w, const float* bias, const float* temb, const void* res, void* out, int B,
@@ -505,6 +516,27 @@ int sd_op_geglu_w8a8(const int8_t* xq, const int8_t* wq, const float* w_scale, f
  * (v = 1) rows of the output's 16-column unit U, every row whole - so a tile of 80 output columns stages ten consecutive strips.  N2 a
  * multiple of 32, K of 64.  *bytes = its size (N2 * K); packed may be NULL to ask for the size alone. */
 int sd_op_w8a8_pack_geglu(const int8_t* wq, int N2, int K, int8_t* packed, size_t* bytes);
+/* No reference counterpart as an operator; behind sd_op_layernorm_q8 it stands for norm1 -> attn1.to_q / to_k / to_v (unet.py:583-586 ->
+ * :74-84) under quantize_cumulative_config (activation_quantization.py:141-203), which quantizes the OUTPUT of the LayerNorm and the
+ * three un-folded weights.  sd_op_qkv_w8a8 (plan tile 22, smqkv_i8.hip): xq (B * HW, C) int8 token-major, wq (3C, C) int8 =
+ * [Wq | Wk | Wv] each in the checkpoint's row order, w_scale (3C) f32, act_absmax the range xq was quantized with, bias (3C) f32 or NULL
+ * -> what sd_op_qkv_ln hands to attention: out_qk (B * HW, 2C) f16 = q | k, out_vt (B, C, HW) f16 = V^T (vt_perm != 0: the two middle
+ * 4-token blocks of every 16 tokens swapped).  For output column n of token m, each operation rounded to fp32 on its own:
+ *   v = float(int32 sum over C of xq[m][k] * wq[n][k]) * fp32(fp32(act_absmax / 127) * w_scale[n]);  v = v + bias[n] with a bias;
+ *   v = v * q_scale for n < C unless q_scale == 1;  out = fp16(v), one rounding.
+ * bm = tile height 128 / 256, 0 = by the grid (128 rows while that grid stays within 256 workgroups); iters, ms as sd_op_conv2d_ex.
+ * plan_out = {22, 1 | 2 (bm 128 | 256), 1, 0}.  Checked on the host in this order, before any device work, each
+ * SD_ERR_INVALID_ARGUMENT: (1) bm not 0 / 128 / 256; (2) NULL arguments or an empty problem; (3) a shape off plan tile 22's rule (C a
+ * multiple of 160 and of 64, at least 640; HW a multiple of 16; B * HW a multiple of the tile height with at least 2 tile rows; a
+ * multiple of 8 tiles of bm x 160); (4) C > 133120 (the int32 sums must stay exact); (5) act_absmax not a positive finite number, or
+ * q_scale not finite; (6) a w_scale that is not a positive finite number; (7) a weight of -128; (8) an activation of -128. */
+int sd_op_qkv_w8a8(const int8_t* xq, const int8_t* wq, const float* w_scale, float act_absmax, const float* bias, void* out_qk, void* out_vt,
+                   int B, int HW, int C, float q_scale, int vt_perm, int bm, int* plan_out, int iters, float* ms);
+/* The int8 weights that entry and the UNet builder put on the device (host only): wq (3C, C) int8 = [Wq | Wk | Wv] -> packed
+ * [3C / 16 strips][16 rows][C]: strip t holds the stacked rows 16 t .. 16 t + 15, every row whole - a tile of 160 output columns stages
+ * the ten consecutive strips 10 n_tile .. 10 n_tile + 9.  C a multiple of 64.  *bytes = its size (3C * C); packed may be NULL to ask
+ * for the size alone. */
+int sd_op_w8a8_pack_qkv(const int8_t* wq, int C, int8_t* packed, size_t* bytes);
 /* The host weight quantizer of sd_weights_quantize_w8a8 on its own: w (Cout, per_row) f32 -> q (Cout, per_row) int8, w_scale (Cout)
  * f32, *sq_err (may be NULL).  A non-finite weight is SD_ERR_INVALID_ARGUMENT. */
 int sd_op_quantize_weight(const float* w, int Cout, size_t per_row, int8_t* q, float* w_scale, double* sq_err);
@@ -670,7 +702,11 @@ int sd_op_sched_step(const float* noise_pred, float* latents, float* hist, const
  * single-source plain projection at a consenting call site and the tensor carries a W8A8 mark; tile = 20 asks for a W8A8 descriptor of
  * the GEGLU projection - the answer is 20 with the resolved tile height of the same staging (1 / 2 = 128 / 256 rows), split-K 1, no slab,
  * no workspace, or SD_ERR_INVALID_ARGUMENT naming plan tile 20 for a shape it does not take (the LayerNorm fold, flags & 1, among
- * them); a handle takes 20 exactly where this says 13 for ff.net.0.proj and the tensor carries a W8A8 mark),
+ * them); a handle takes 20 exactly where this says 13 for ff.net.0.proj and the tensor carries a W8A8 mark; tile = 22 asks for a W8A8
+ * descriptor of the fused q|k|v projection (N = 3 C0, n_trans = 2 C0, no flags) - the answer is 22 with the resolved tile height of
+ * the same staging (1 / 2 = 128 / 256 rows, 0 = by the grid), split-K 1, no slab, no workspace, or SD_ERR_INVALID_ARGUMENT naming plan
+ * tile 22 for a shape off its rule (sd_op_qkv_w8a8); it has no fp16 twin: a handle takes 22 for every fused q|k|v launch on the rule
+ * whose three tensors carry W8A8 marks with one range),
  * staging, resolved split-K, slab (0 / 1), then the copies a handle must hold for this conv: wstream, wsgemm, bvgemm (0 / 1 each).
  * *workspace_bytes: the slab workspace this launch needs. */
 int sd_op_conv_plan(int ksize, int stride, int up, int C0, int C1, int N, int B, int Ho, int Wo, int out_mode, int flags, int n_trans,

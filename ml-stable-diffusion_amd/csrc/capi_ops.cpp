@@ -779,6 +779,67 @@ int sd_op_w8a8_pack_geglu(const int8_t* wq, int N2, int K, int8_t* packed, size_
   });
 }
 
+// The fused q|k|v projection of a self-attention in W8A8 (plan tile 22).  Every check runs on the host in front of the first device call
+// (Scratch), in the order the header lists them.  Both outputs live in front of a poisoned guard on the device (guarded_buf): an
+// element the launch skipped reads back as NaN, and a guard that changed is an internal error.
+int sd_op_qkv_w8a8(const int8_t* xq, const int8_t* wq, const float* w_scale, float act_absmax, const float* bias, void* out_qk, void* out_vt,
+                   int B, int HW, int C, float q_scale, int vt_perm, int bm, int* plan_out, int iters, float* ms) {
+  return guarded([&] {
+    SD_REQUIRE(bm == 0 || bm == 128 || bm == 256, kInvalidArgument, "qkv_w8a8: bm = %d, not 0, 128 or 256", bm);
+    SD_REQUIRE(xq && wq && w_scale && out_qk && out_vt && plan_out, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(B > 0 && HW > 0 && C > 0, kInvalidArgument, "qkv_w8a8: empty problem");
+    const int M = B * HW, N = 3 * C;
+    ConvDesc d = conv_desc(nullptr, C, nullptr, nullptr, nullptr, nullptr, B, 1, HW, N);
+    d.n_trans = 2 * C;
+    d.ldT = HW;                          // (the rule wants HW % 16 == 0: no padding columns, out_vt is (B, C, HW) as sd_op_qkv_ln's)
+    d.vt_perm = vt_perm ? 1 : 0;
+    d.q_scale = q_scale;
+    d.q_cols = q_scale != 1.f ? C : 0;  // (a factor of 1: the product is skipped)
+    const int code = conv_plan_pin(WeightSource::I8Qkv, bm).staging;
+    SD_REQUIRE(conv_fast_path_ok(d) && smqkv_i8_tiles(d, code), kInvalidArgument,
+               "qkv_w8a8: shape not eligible for plan tile 22 (smqkv_i8.hip: B=%d HW=%d C=%d bm=%d - C a multiple of 160 and of 64, at least 640, HW a "
+               "multiple of 16, B * HW of the tile height, at least 2 tile rows and a multiple of 8 tiles of 160 columns)", B, HW, C, bm);
+    SD_REQUIRE(smqkv_i8_shape_ok(d, code), kInvalidArgument, "qkv_w8a8: K = %d, the exact int32 sums of plan tile 22 hold up to %d", C, kSmI8MaxK);
+    // act_absmax and q_scale, then w_scale, then the weight values (-128 is outside the symmetric range), then the activations
+    SD_REQUIRE(w8a8_absmax_ok(act_absmax), kInvalidArgument, "qkv_w8a8: act_absmax = %g, not a positive finite number", (double)act_absmax);
+    SD_REQUIRE(std::isfinite(q_scale), kInvalidArgument, "qkv_w8a8: q_scale = %g, not finite", (double)q_scale);
+    (void)w8a8_host_copy("qkv_w8a8", wq, w_scale, act_absmax, N, C, 1, WeightSource::I8Qkv);
+    for (size_t i = 0; i < (size_t)M * C; ++i)
+      SD_REQUIRE(xq[i] != -128, kInvalidArgument, "qkv_w8a8: activation value -128 at element %zu, the symmetric range is [-127, 127]", i);
+    Scratch sc;
+    d.x0_i8 = sc.dev<int8_t>((size_t)M * C, xq);
+    if (bias) d.bias = sc.dev<float>(N, bias);
+    const size_t n_qk = (size_t)M * 2 * C, n_vt = (size_t)B * C * d.ldT, guard = 4096;
+    half_t* dqk = guarded_buf<half_t>(sc, n_qk, guard);
+    half_t* dvt = guarded_buf<half_t>(sc, n_vt, guard);
+    d.out = dqk;
+    d.out_t = dvt;
+    HostWeights h;
+    h.kind = WeightSource::I8Qkv; h.q = wq; h.w_scale = w_scale; h.act_absmax = act_absmax;
+    upload_compressed(sc, d, "qkv_w8a8", h, bm);
+    const ConvPlan p = conv_plan(d);
+    plan_out[0] = p.tile; plan_out[1] = p.staging; plan_out[2] = p.splitk; plan_out[3] = p.slab ? 1 : 0;
+    ConvWorkspace ws;
+    sc.timed(iters, ms, [&] { launch_conv(d, ws, sc.stream); });
+    SD_HIP(hipMemcpy(out_qk, dqk, n_qk * 2, hipMemcpyDeviceToHost));
+    SD_HIP(hipMemcpy(out_vt, dvt, n_vt * 2, hipMemcpyDeviceToHost));
+    std::vector<uint16_t> g(2 * guard);
+    SD_HIP(hipMemcpy(g.data(), dqk + n_qk, guard * 2, hipMemcpyDeviceToHost));
+    SD_HIP(hipMemcpy(g.data() + guard, dvt + n_vt, guard * 2, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < g.size(); ++i)
+      SD_REQUIRE(g[i] == 0xffff, kInternal, "qkv_w8a8: the guard behind %s was written (element %zu)", i < guard ? "out_qk" : "out_vt", i % guard);
+  });
+}
+
+int sd_op_w8a8_pack_qkv(const int8_t* wq, int C, int8_t* packed, size_t* bytes) {
+  return guarded([&] {
+    SD_REQUIRE(wq && bytes, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(C > 0 && C % 64 == 0, kInvalidArgument, "w8a8_pack_qkv: C %d, not a positive multiple of 64", C);
+    *bytes = smqkv_i8_bytes(3 * C, C);
+    if (packed) smqkv_i8_pack(wq, 3 * C, C, packed);
+  });
+}
+
 int sd_op_w8a8_pack(const int8_t* wq, int Cout, int Ctot, int ksize, int8_t* stream, size_t* bytes) {
   return guarded([&] {
     SD_REQUIRE(wq && bytes, kInvalidArgument, "NULL argument");
@@ -1523,6 +1584,13 @@ static ConvPlan query_conv_plan(int ksize, int stride, int up, int C0, int C1, i
   if (tile == 20) {   // ... and one of the int8 GEGLU projection, whose activations arrive as int8 too
     d.w = nullptr;
     d.cw.kind = WeightSource::I8Geglu;
+    d.cw.stream = d.cw.scale = present;
+    d.cw.inv_s = 1.f;
+    d.x0_i8 = reinterpret_cast<const int8_t*>(present);
+  }
+  if (tile == 22) {   // ... and one of the int8 q|k|v projection (asked with n_trans = 2 C0, as the fused q|k|v launch is)
+    d.w = nullptr;
+    d.cw.kind = WeightSource::I8Qkv;
     d.cw.stream = d.cw.scale = present;
     d.cw.inv_s = 1.f;
     d.x0_i8 = reinterpret_cast<const int8_t*>(present);

@@ -30,14 +30,15 @@ Dims dims_of(const ConvDesc& d) {
 // The A/B switches of the plan, each read here and nowhere else (SD_TUNE only: sd_common.h tune_env_int).
 //   SD_WSTREAM=0 takes plan tile 9 out of every plan; SD_WSGEMM / SD_BVGEMM / SD_SMGEMM / SD_SMGEGLU=0 keep the library's own rule
 //   from taking tiles 10 / 11 / 12 / 13 (a forced tile still runs); SD_REDUCE_STATS=1: GroupNorm statistics from the slab combine
-//   (measured: the step loses 0.25 ms with it, LAB_NOTES.md r5 - off unless asked for)
+//   (measured: the step loses 0.25 ms with it, LAB_NOTES.md r5 - off unless asked for); SD_QKV_I8=0 takes plan tile 22 out of every
+//   plan: a marked q|k|v launch stays the folded fp16 launch (conv_plan_weights), a pinned descriptor is refused
 struct Switches {
-  bool wstream, wsgemm, bvgemm, smgemm, smgeglu, reduce_stats, tuning;
+  bool wstream, wsgemm, bvgemm, smgemm, smgeglu, reduce_stats, tuning, qkv_i8;
 };
 const Switches& switches() {
   static const Switches s = {tune_env_int("SD_WSTREAM", 1) != 0, tune_env_int("SD_WSGEMM", 1) != 0, tune_env_int("SD_BVGEMM", 1) != 0,
                              tune_env_int("SD_SMGEMM", 1) != 0, tune_env_int("SD_SMGEGLU", 1) != 0, tune_env_int("SD_REDUCE_STATS", 0) != 0,
-                             getenv("SD_TUNE") != nullptr};
+                             getenv("SD_TUNE") != nullptr, tune_env_int("SD_QKV_I8", 1) != 0};
   return s;
 }
 
@@ -67,6 +68,8 @@ bool pal_geglu(const ConvDesc& d) { return d.cw.kind == WeightSource::PalGeglu; 
 bool i8_gemm(const ConvDesc& d) { return d.cw.kind == WeightSource::I8Gemm; }
 // plan tile 20: the GEGLU projection from int8 weights and int8 activations
 bool i8_geglu(const ConvDesc& d) { return d.cw.kind == WeightSource::I8Geglu; }
+// plan tile 22: the fused q|k|v projection from int8 weights and int8 activations
+bool i8_qkv(const ConvDesc& d) { return d.cw.kind == WeightSource::I8Qkv; }
 // tiles 9 / 14 / 17: the code's wave count (decode_plan)
 int wstream_waves(int code) { return code == 4 ? 4 : 8; }
 // fp32 slabs of a launch: one per split, one when only `slab` (weight stream, GroupNorm twins) asks for the slab path
@@ -314,6 +317,29 @@ bool conv_fast_path_ok(const ConvDesc& d) {
   return true;
 }
 
+// plan tile 22's tiles (the rule: conv_plan.h)
+int smqkv_i8_bm(const ConvDesc& d, int variant) {
+  if (variant == 1) return 128;
+  if (variant == 2) return 256;
+  const long M = (long)d.B * d.Ho * d.Wo;
+  return M % 128 == 0 && M / 128 * (d.N / kSmQkvCols) <= 256 ? 128 : 256;
+}
+bool smqkv_i8_shape_ok(const ConvDesc& d, int variant) { return smqkv_i8_tiles(d, variant) && d.C0 <= kSmI8MaxK; }
+bool smqkv_i8_tiles(const ConvDesc& d, int variant) {
+  if (variant < 0 || variant > 2) return false;
+  if (!(d.ksize == 1 && d.stride == 1 && d.up == 1 && !d.x1 && d.out_mode == kOutHalf && !d.ln_colsum && !d.temb && !d.res && !d.gnf_partial &&
+        !d.gn_partial && d.n_twins == 0 && !d.debug && !d.prof && !d.subpix))
+    return false;
+  const int C = d.C0;
+  if (!(C >= 640 && C % kSmQkvCols == 0 && C % 64 == 0 && d.N == 3 * C && d.n_trans == 2 * C && (d.q_cols == 0 || d.q_cols == C)))
+    return false;
+  const long S = (long)d.Ho * d.Wo, M = d.B * S;
+  if (!(S % 16 == 0 && d.ldT >= S && d.ldT % 8 == 0)) return false;
+  const int bm = smqkv_i8_bm(d, variant);
+  const long mt = M / bm, nt = d.N / kSmQkvCols;
+  return M % bm == 0 && mt >= 2 && (mt * nt) % 8 == 0 && mt * nt <= 65535;
+}
+
 namespace {
 
 // resolved split-K of plan tile 21: tile 7's rule (workgroups for every CU, a split keeps >= 2 chunks) over its grid of
@@ -348,6 +374,13 @@ ConvPlan plan_codes(const ConvDesc& d) {
     SD_REQUIRE(conv_fast_path_ok(d) && cw.stream && cw.scale && d.staging >= 0 && d.staging <= 2 && smgeglu_i8_shape_ok(d, d.staging), kInvalidArgument,
                "plan tile 20 (smgeglu_i8.hip, int8) needs the int8 weights, the scales and an un-folded shape of the GEGLU kernel with K <= %d "
                "(k=%d C0=%d C1=%d N=%d M=%d mode=%d ln=%d)", kSmI8MaxK, d.ksize, d.C0, d.x1 ? d.C1 : 0, d.N, d.B * d.Ho * d.Wo, d.out_mode, d.ln_colsum ? 1 : 0);
+  // (nor has an int8 q|k|v descriptor: tile 22 takes it or nobody does)
+  if (i8_qkv(d))
+    SD_REQUIRE(conv_fast_path_ok(d) && switches().qkv_i8 && cw.stream && cw.scale && d.staging >= 0 && d.staging <= 2 && smqkv_i8_shape_ok(d, d.staging),
+               kInvalidArgument,
+               "plan tile 22 (smqkv_i8.hip, int8) needs the int8 weights, the scales and an un-folded q|k|v shape of its tiles with K <= %d "
+               "(k=%d C0=%d C1=%d N=%d n_trans=%d M=%d S=%d mode=%d ln=%d%s)", kSmI8MaxK, d.ksize, d.C0, d.x1 ? d.C1 : 0, d.N, d.n_trans,
+               d.B * d.Ho * d.Wo, d.Ho * d.Wo, d.out_mode, d.ln_colsum ? 1 : 0, switches().qkv_i8 ? "" : "; SD_QKV_I8=0");
   // the sub-pixel upsampler holds the folded matrix and nothing else: tile 21 takes it or nobody does (no table row, no tuner candidate)
   if (d.subpix) {
     SD_REQUIRE(conv_fast_path_ok(d) && halo_sp_ok(d) && (d.tile == 0 || d.tile == 21), kInvalidArgument,
@@ -399,6 +432,8 @@ ConvPlan plan_codes(const ConvDesc& d) {
       return ConvPlan{16, 1, 1, false, 0};
     case WeightSource::I8Geglu:   // the code of tile 13 in, the resolved tile height out; no split-K, no slab, no workspace (checked above)
       return ConvPlan{20, smgeglu_bm(d, d.staging) == 128 ? 1 : 2, 1, false, 0};
+    case WeightSource::I8Qkv:   // the tile height's code in (0 = by the grid), the resolved one out; no split-K, no slab, no workspace (checked above)
+      return ConvPlan{22, smqkv_i8_bm(d, d.staging) == 128 ? 1 : 2, 1, false, 0};
   }
   const Switches& sw = switches();
   // the library's own rules for tiles 10-13 apply where nothing else was asked for (a tuner candidate in force also keeps them off)
@@ -457,7 +492,7 @@ ConvPlan plan_codes(const ConvDesc& d) {
 //   tile 18:   tile 7's codes; the int8 kernel has rings of 2 / 3 / 4 stages, a deeper code runs the 4-stage one
 //   tile 21:   tile 7's codes; the sub-pixel kernel has rings of 3 / 4 stages: 2 = 3 stages, anything else 4
 //   tiles 9 / 14 / 17: 4 = four waves per workgroup, anything else eight      tile 11: 1-6 = the variant, anything else the library's choice
-//   tiles 12 / 15 / 19 / 13 / 16 / 20: 1 / 2 = the lower / higher tile (32 / 64, 128 / 256 rows), 0 = by the shape
+//   tiles 12 / 15 / 19 / 13 / 16 / 20 / 22: 1 / 2 = the lower / higher tile (32 / 64, 128 / 256 rows), 0 = by the shape
 void decode_plan(const ConvDesc& d, ConvPlan& p) {
   const Dims a = dims_of(d);
   int code = p.staging;
@@ -479,6 +514,10 @@ void decode_plan(const ConvDesc& d, ConvPlan& p) {
     case 13: case 16: case 20:
       p.kernel = p.tile == 13 ? ConvKernel::Smgeglu : p.tile == 16 ? ConvKernel::SmgegluPal : ConvKernel::SmgegluI8;
       p.bm = code >= 0 && code <= 2 ? smgeglu_bm(d, code) : 0;
+      return;
+    case 22:
+      p.kernel = ConvKernel::SmqkvI8;
+      p.bm = code >= 0 && code <= 2 ? smqkv_i8_bm(d, code) : 0;
       return;
     default: break;
   }
@@ -563,6 +602,7 @@ std::string conv_plan_kernel_name(const ConvPlan& p) {
     case ConvKernel::Smgeglu: return "smgeglu bm" + std::to_string(p.bm);
     case ConvKernel::SmgegluPal: return "smgeglu_pal bm" + std::to_string(p.bm);
     case ConvKernel::SmgegluI8: return "smgeglu_i8 bm" + std::to_string(p.bm);
+    case ConvKernel::SmqkvI8: return "smqkv_i8 bm" + std::to_string(p.bm);
     default: return "generic";
   }
 }
@@ -574,7 +614,7 @@ std::string conv_plan_kernel_name(const ConvPlan& p) {
 //   - with the weight-stream copy present, its slab count at four waves per workgroup (the most slabs it writes);
 //   - the unresolved split-K (the launch may use fewer splits), one slab when only the GroupNorm twins ask for it.
 size_t conv_workspace_bytes(const ConvDesc& d) {
-  if (!conv_fast_path_ok(d) || pal_gemm(d) || pal_geglu(d) || i8_gemm(d) || i8_geglu(d)) return 0;   // (tiles 15 / 16 / 19 / 20: no slabs)
+  if (!conv_fast_path_ok(d) || pal_gemm(d) || pal_geglu(d) || i8_gemm(d) || i8_geglu(d) || i8_qkv(d)) return 0;   // (tiles 15 / 16 / 19 / 20 / 22: no slabs)
   const Dims a = dims_of(d);
   if (d.subpix) return halo_sp_ok(d) ? slab_bytes(a, subpix_splits(d, a), false) : 0;   // (tile 21: pinned, no candidate or table row moves its split)
   const Plan p = choose_plan(d, a);
@@ -624,6 +664,7 @@ WeightPin conv_plan_pin(WeightSource kind, int n) {
     case WeightSource::I8Gemm: return {kind, 19, n == 32 ? 1 : n == 64 ? 2 : 0};
     case WeightSource::PalGeglu: return {kind, 16, n == 128 ? 1 : n == 256 ? 2 : 0};
     case WeightSource::I8Geglu: return {kind, 20, n == 128 ? 1 : n == 256 ? 2 : 0};
+    case WeightSource::I8Qkv: return {kind, 22, n == 128 ? 1 : n == 256 ? 2 : 0};
     default: return {};
   }
 }
@@ -645,6 +686,14 @@ WeightPin conv_plan_weights(const ConvDesc& d, StoredWeights held, bool opt_in) 
     ConvDesc plain = d;
     plain.ln_colsum = nullptr;
     if (p.kernel == ConvKernel::Smgeglu && smgeglu_i8_shape_ok(plain, p.bm == 128 ? 1 : 2)) return conv_plan_pin(WeightSource::I8Geglu, p.bm);
+  }
+  // the fused q|k|v launch (V columns transposed), for the int8 kernel that reads norm1's int8 output: no fp16 twin to follow - the
+  // shape rule alone, asked of the descriptor without the fold's fields, at the height the grid gives
+  if (opt_in && held == StoredWeights::W8A8 && d.ksize == 1 && !d.x1 && d.out_mode == kOutHalf && d.n_trans > 0 && sw.qkv_i8) {
+    ConvDesc plain = d;
+    plain.ln_colsum = nullptr;
+    if (smqkv_i8_shape_ok(plain, 0)) return conv_plan_pin(WeightSource::I8Qkv, smqkv_i8_bm(plain, 0));
+    return {};
   }
   // tile 9 with the fragment-major copy present: its wave count, i.e. its slab count
   if (sw.wstream && !d.ln_colsum && plan_is_wstream(d)) {
@@ -717,7 +766,7 @@ void conv_plan_log(const ConvDesc& d, const ConvPlan& p, int n_fast) {
   else if (p.tile == 15 || p.tile == 16)
     fprintf(stderr, "[sd conv] k1 s1 up1 C0=%d C1=%d M=%d N=%d K=%d mode=%d tile=%d bm=%d n_fast=%d bits=%d\n", d.C0, c1, a.M, a.N, a.K, d.out_mode,
             p.tile, p.bm, n_fast, d.cw.bits);
-  else if (p.tile == 19 || p.tile == 20)
+  else if (p.tile == 19 || p.tile == 20 || p.tile == 22)
     fprintf(stderr, "[sd conv] k1 s1 up1 C0=%d C1=%d M=%d N=%d K=%d mode=%d tile=%d bm=%d n_fast=%d bits=8\n", d.C0, c1, a.M, a.N, a.K, d.out_mode, p.tile,
             p.bm, n_fast);
   else if (p.tile == 18)

@@ -8,8 +8,8 @@
 
 namespace sd {
 
-// the kernel a plan launches (tile -1 / 1-4 / 7 / 18 / 21 / 9 / 14 / 17 / 10 / 11 / 12 / 15 / 19 / 13 / 16 / 20 of the wire format below)
-enum class ConvKernel { Generic, Igemm, GemmPipe, HaloKs, HaloI8, HaloSubpix, Wstream, WstreamPal, WstreamI8, Wsgemm, Bvgemm, Smgemm, SmgemmPal, SmgemmI8, Smgeglu, SmgegluPal, SmgegluI8 };
+// the kernel a plan launches (tile -1 / 1-4 / 7 / 18 / 21 / 9 / 14 / 17 / 10 / 11 / 12 / 15 / 19 / 13 / 16 / 20 / 22 of the wire format below)
+enum class ConvKernel { Generic, Igemm, GemmPipe, HaloKs, HaloI8, HaloSubpix, Wstream, WstreamPal, WstreamI8, Wsgemm, Bvgemm, Smgemm, SmgemmPal, SmgemmI8, Smgeglu, SmgegluPal, SmgegluI8, SmqkvI8 };
 
 struct ConvPlan {
   // The wire format: what ConvDesc::tile / staging pins, tuned_convs.inc rows, SD_PLAN_TABLE and sd_tune_set_candidate say and what
@@ -22,6 +22,8 @@ struct ConvPlan {
                    // 20: the GEGLU projection from int8 weights and int8 activations written by the LayerNorm in front of it
                    // (smgeglu_i8.hip, tile 13's tiles at both heights; never the library's own answer);
                    // 21: the upsampler conv as four 2x2 phase convs on the low-res halo (conv3x3_halo_sp.hip; only with ConvDesc::subpix);
+                   // 22: the self-attention q|k|v projection from int8 weights and int8 activations written by the LayerNorm in front
+                   // of it (smqkv_i8.hip, BM x 160-column tiles at tile 20's two heights; never the library's own answer);
                    // -1 = not on the MFMA path (launch_conv_generic)
   int staging;     // per-family code: decode_plan
   int splitk;      // resolved: what the launch runs, no empty splits (halo: over 64-channel chunks; tile 9: the slab count)
@@ -29,7 +31,7 @@ struct ConvPlan {
   size_t workspace_bytes;   // exactly what this launch needs of ConvWorkspace::partial
   // What the codes mean for this descriptor, resolved once by conv_plan(): all a launcher reads.
   ConvKernel kernel = ConvKernel::Generic;
-  int bm = 0, bn = 0;        // Igemm / GemmPipe / HaloKs / HaloI8 (128 x 64, as its tile counts): tile rows x columns; Smgemm* / Smgeglu: bm, tile rows
+  int bm = 0, bn = 0;        // Igemm / GemmPipe / HaloKs / HaloI8 (128 x 64, as its tile counts): tile rows x columns; Smgemm* / Smgeglu* / SmqkvI8: bm, tile rows
   int stages = 0;            // Igemm / GemmPipe / HaloKs / HaloI8 / HaloSubpix: the ring depth that runs, after the fall-back to one that fits the LDS
   int kgroups = 1;           // Igemm: 2 = in-workgroup split-K, two K groups of four waves with a ring each
   bool reg_staged = false;   // Igemm: A / B travel HBM -> VGPR -> LDS (the A/B reference form), two stages
@@ -60,6 +62,9 @@ ConvWeightCopies conv_plan_copies(const ConvDesc& d);
 //            without holding a mark, with the call site's consent only when it observes the projections too.  In front of all of
 //            them, as the palette branch does for tile 16: the opted-in GEGLU (tile 20 for tile 13 at the same tile height, both
 //            heights) - asked WITHOUT the LayerNorm fold's fields, which tile 20 does not take (the caller un-folds: UNet::transformer_block)
+//            - and the opted-in fused q|k|v launch (tile 22, which has no fp16 twin: taken wherever smqkv_i8_shape_ok admits the
+//            un-folded descriptor, at the height smqkv_i8_bm resolves; `held` then speaks for all three tensors - the caller has
+//            checked that each carries a mark and that the marks share one range)
 enum class StoredWeights { Fp16, Palette, W8A8 };
 struct WeightPin {
   WeightSource kind = WeightSource::Fp16;
@@ -79,7 +84,7 @@ void conv_plan_log(const ConvDesc& d, const ConvPlan& p, int n_fast = 0);
 //   "conv3x3_halo_sp ring<stages>"
 //   "wstream waves<n>"   "wstream_pal waves<n>"    "wstream_i8 waves<n>"                 "wsgemm"    "bvgemm v<variant>"
 //   "smgemm bm<bm>"      "smgemm_pal bm<bm>"       "smgemm_i8 bm<bm>"                    "smgeglu bm<bm>"    "smgeglu_pal bm<bm>"
-//   "smgeglu_i8 bm<bm>"  "generic"
+//   "smgeglu_i8 bm<bm>"  "smqkv_i8 bm<bm>"        "generic"
 std::string conv_plan_kernel_name(const ConvPlan& p);
 
 // Tile order inside an XCD's run of workgroup ids, from an estimate of the bytes each order pulls through the fabric into the 8 XCD L2s:
@@ -134,6 +139,23 @@ static_assert(127LL * 127 * 9 * kHaloI8MaxCtot < (1LL << 31) && 127LL * 127 * 9 
 // smgemm_i8_kernel (plan tile 19) sums the whole K of a 1x1 GEMM in int32: 127 * 127 * K < 2^31, the last multiple of 64 that fits
 constexpr int kSmI8MaxK = 133120;
 static_assert(127LL * 127 * kSmI8MaxK < (1LL << 31) && 127LL * 127 * (kSmI8MaxK + 64) >= (1LL << 31), "int32 bound of plan tile 19");
-// (smgeglu_i8_kernel, plan tile 20, sums the whole K of its 1x1 GEMM the same way: the same bound)
+// (smgeglu_i8_kernel, plan tile 20, and smqkv_i8_kernel, plan tile 22, sum the whole K of their 1x1 GEMMs the same way: the same bound)
+
+// Plan tile 22 (smqkv_i8.hip): the fused q|k|v projection [Wq | Wk | Wv] (3C, C) of a self-attention from int8 weights and the int8
+// output of norm1 - BM x kSmQkvCols tiles, BM = 128 / 256 (variant 1 / 2; 0: by the grid, tile 13's rule - 128 rows while that grid
+// stays within one round of 256 workgroups).  The rule, host only:
+//   * a single-source 1x1 GEMM, kOutHalf, N = 3 C0 with the V columns leaving transposed (n_trans = 2 C0), no LayerNorm fold (the int8
+//     activations ARE the LayerNorm's output), no time embedding, residual, GroupNorm statistics, twins, phase clocks or debug hooks;
+//   * C0 >= 640 - the levels whose self-attention is a launch of its own; the 320-channel level's head is ONE launch
+//     (gn_proj_qkv_kernel), and a rule that admitted its width would have the observers and the accounting promise a layer no handle
+//     runs from int8 - C0 % kSmQkvCols == 0, so that a tile lies inside q, k or v and the boundaries fall on tile boundaries,
+//     C0 % 64 == 0 (whole K64 stages), C0 <= kSmI8MaxK;
+//   * S = Ho * Wo a multiple of 16: a lane's four V^T tokens and the 16-token blocks vt_perm permutes lie in one sample; ldT >= S, ldT % 8 == 0;
+//   * q_cols 0 (no q_scale) or C0 (the queries, whole tiles);
+//   * M % BM == 0, at least two tile rows, a tile count that is a multiple of 8 (the XCD runs of sm_tile.h) and at most 65535.
+constexpr int kSmQkvCols = 160;
+bool smqkv_i8_shape_ok(const ConvDesc& d, int variant);
+bool smqkv_i8_tiles(const ConvDesc& d, int variant);   // the rule without the int32 bound (an operator entry names that refusal on its own)
+int smqkv_i8_bm(const ConvDesc& d, int variant);   // the tile height of a variant: 128 or 256
 
 }  // namespace sd

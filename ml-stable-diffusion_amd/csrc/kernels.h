@@ -40,7 +40,9 @@ struct GnTwin {
 //   I8Gemm      tile 19, smgemm_i8.hip        smgemm_i8_kernel (W8A8)         stream of smgemm_i8_pack    staging: tile 12's code (0 = by M)
 //   I8Geglu     tile 20, smgeglu_i8.hip       smgeglu_i8_kernel (W8A8)        stream of smgeglu_i8_pack   staging: tile 13's code (0 = by the grid);
 //               the activations arrive quantized (ConvDesc::x0_i8, written by launch_layernorm_q8)
-enum class WeightSource { Fp16, PalWstream, PalGemm, PalGeglu, I8Wstream, I8Halo, I8Gemm, I8Geglu };
+//   I8Qkv       tile 22, smqkv_i8.hip         smqkv_i8_kernel (W8A8)          stream of smqkv_i8_pack     staging: 1 / 2 = 128- / 256-row tiles (0 = by the
+//               grid); the stacked [Wq | Wk | Wv] of a fused q|k|v launch, activations quantized by their producer as for I8Geglu
+enum class WeightSource { Fp16, PalWstream, PalGemm, PalGeglu, I8Wstream, I8Halo, I8Gemm, I8Geglu, I8Qkv };
 struct CompressedWeights {
   WeightSource kind = WeightSource::Fp16;
   const void* stream = nullptr;
@@ -50,21 +52,21 @@ struct CompressedWeights {
   // PalGeglu with the LayerNorm fold (ConvDesc::ln_colsum set): the fp32 norm weight [C0] - the kernel multiplies every LUT value by it
   // as fold_layernorm_rows does on the host; null without the fold
   const float* ln_gamma = nullptr;
-  // I8Wstream / I8Halo / I8Gemm / I8Geglu: the output scale per column scale[n] = fp32(s_a * s_w[n]) (I8Geglu: rows in the interleaved
-  // order of the GEGLU upload, geglu_row) and inv_s = fp32(1 / s_a), the factor the kernel - for I8Geglu the LayerNorm in front of it -
-  // quantizes its activations by
+  // I8Wstream / I8Halo / I8Gemm / I8Geglu / I8Qkv: the output scale per column scale[n] = fp32(s_a * s_w[n]) (I8Geglu: rows in the
+  // interleaved order of the GEGLU upload, geglu_row) and inv_s = fp32(1 / s_a), the factor the kernel - for I8Geglu / I8Qkv the
+  // LayerNorm in front of it - quantizes its activations by
   const float* scale = nullptr;
   float inv_s = 0.f;
   bool palettized() const { return kind == WeightSource::PalWstream || kind == WeightSource::PalGemm || kind == WeightSource::PalGeglu; }
   const uint8_t* pal() const { return palettized() ? static_cast<const uint8_t*>(stream) : nullptr; }
-  bool int8() const { return kind == WeightSource::I8Wstream || kind == WeightSource::I8Halo || kind == WeightSource::I8Gemm || kind == WeightSource::I8Geglu; }
+  bool int8() const { return kind == WeightSource::I8Wstream || kind == WeightSource::I8Halo || kind == WeightSource::I8Gemm || kind == WeightSource::I8Geglu || kind == WeightSource::I8Qkv; }
   const int8_t* i8() const { return int8() ? static_cast<const int8_t*>(stream) : nullptr; }
 };
 
 struct ConvDesc {
   const half_t* x0 = nullptr;   // [B][Hi][Wi][C0]
   const half_t* x1 = nullptr;   // optional second source (channel concat), [B][Hi][Wi][C1]
-  const int8_t* x0_i8 = nullptr;   // cw of kind I8Geglu: the source as int8 [M][C0], quantized by its producer (launch_layernorm_q8); x0 is not read
+  const int8_t* x0_i8 = nullptr;   // cw of kind I8Geglu / I8Qkv: the source as int8 [M][C0], quantized by its producer (launch_layernorm_q8); x0 is not read
   int C0 = 0, C1 = 0;
   const half_t* w = nullptr;    // [N][K] K-major, K = ksize*ksize*(C0+C1), tap-major
   const float* bias = nullptr;  // [N] or null
@@ -225,6 +227,10 @@ void launch_smgeglu_pal(const ConvDesc& d, const ConvPlan& p, hipStream_t s);
 // kind I8Geglu, d.x0_i8) - exact int32 sums, scale and bias in fp32, then tile 13's v * gelu_erf(g); both tile heights, K <= kSmI8MaxK
 bool smgeglu_i8_shape_ok(const ConvDesc& d, int variant);             // smgeglu_shape_ok, no fold, inside the int32 bound
 void launch_smgeglu_i8(const ConvDesc& d, const ConvPlan& p, hipStream_t s);
+// smqkv_i8.hip: the fused q|k|v projection of a self-attention from int8 weights and int8 activations (W8A8, plan tile 22: d.cw of kind
+// I8Qkv, d.x0_i8) - tile 20's K loop on BM x 160-column tiles, q | k to d.out [M][2 C0] (columns below q_cols times q_scale), V^T to
+// d.out_t [B][C0][ldT] (vt_perm: attention8's key order).  Shapes: smqkv_i8_shape_ok (conv_plan.h)
+void launch_smqkv_i8(const ConvDesc& d, const ConvPlan& p, hipStream_t s);
 
 // calib.hip: box calibration for bench.py - out[0..6] = copy GB/s, dense MFMA TFLOP/s, us per launch of a 323-launch empty
 // graph, us per launch of a 323-launch chain of short kernels on cold operands, us per launch of a 323-launch chain handing 8 MB

@@ -154,13 +154,76 @@ bool Net::observes_geglu(const std::string& name, const Tensor& x, const ConvArg
   return conv_plan_weights(d, StoredWeights::W8A8, a.keep_compressed).kind == WeightSource::I8Geglu;
 }
 
-void Net::observe_tensor(std::vector<Op>& ops, const std::string& name, const Tensor& t) {
+void Net::observe_tensor(std::vector<Op>& ops, const std::string& name, const Tensor& t, const std::vector<std::string>& report_as) {
   float* slot = ll_.arena.alloc_n<float>(1);   // (the arena is zeroed: the running maximum starts at 0)
-  observed_.push_back({name + ".weight", slot});
+  if (report_as.empty()) observed_.push_back({name + ".weight", slot});
+  for (const std::string& n : report_as) observed_.push_back({n + ".weight", slot});   // one observation under several names
   const half_t* p0 = t.p;
   const size_t n0 = t.numel();
   ops.push_back([=](hipStream_t s) { launch_absmax_half(p0, n0, nullptr, 0, slot, s); });
   ops.back().label = "absmax " + name;
+}
+
+// the un-folded descriptor of the fused q|k|v launch, as the planner is asked about it
+ConvDesc Net::qkv_shape(const std::string& name, const Tensor& x, const ConvArgs& a) const {
+  ConvArgs plain = a;
+  plain.ln_colsum = nullptr;
+  plain.x_i8 = nullptr;
+  ConvDesc d = conv_shape(name, x, plain);
+  static const half_t present = 0;   // the planner only tests the pointer
+  d.out_t = const_cast<half_t*>(&present);
+  d.n_trans = a.n_trans;
+  d.vt_perm = a.vt_perm ? 1 : 0;
+  d.q_scale = a.q_scale;
+  d.q_cols = a.q_cols;
+  return d;
+}
+
+WeightPin Net::qkv_plan(const std::string& name, const std::vector<std::string>& parts, const Tensor& x, const ConvArgs& a) const {
+  if (f32_ || a.silu_out || parts.empty()) return {};
+  const W8A8Mark* first = nullptr;
+  for (const std::string& p : parts) {   // every tensor marked, none palettized, one range: one int8 tensor carries one scale
+    const W8A8Mark* m = ws_->w8a8(p + ".weight");
+    if (!m || ws_->palette(p + ".weight")) return {};
+    if (!first) first = m;
+    if (m->act_absmax != first->act_absmax) return {};
+  }
+  return conv_plan_weights(qkv_shape(name, x, a), StoredWeights::W8A8, true);
+}
+
+bool Net::observes_qkv(const std::string& name, const std::vector<std::string>& parts, const Tensor& x, const ConvArgs& a) const {
+  if (f32_ || !ws_->observe() || !ws_->observe_qkv()) return false;
+  for (const std::string& p : parts)
+    if (ws_->palette(p + ".weight")) return false;
+  return conv_plan_weights(qkv_shape(name, x, a), StoredWeights::W8A8, true).kind == WeightSource::I8Qkv;
+}
+
+ConvWeights Net::upload_qkv_i8(const std::vector<std::string>& parts, const WeightPin& pin, int cin, int cout_each) {
+  const size_t per = (size_t)cout_each * cin;
+  std::vector<int8_t> q(parts.size() * per);
+  std::vector<float> w_scale(parts.size() * cout_each);
+  float act_absmax = 0.f;
+  for (size_t i = 0; i < parts.size(); ++i) {
+    const std::string wname = parts[i] + ".weight";
+    const W8A8Mark* i8 = ws_->w8a8(wname);
+    SD_REQUIRE(i8 && ws_->get(wname).numel() == per && i8->q.size() == per && i8->w_scale.size() == (size_t)cout_each, kInvalidArgument,
+               "%s: expected %zu W8A8 values (%d,%d,1,1)", wname.c_str(), per, cout_each, cin);
+    std::copy(i8->q.begin(), i8->q.end(), q.begin() + i * per);
+    std::copy(i8->w_scale.begin(), i8->w_scale.end(), w_scale.begin() + i * cout_each);
+    act_absmax = i8->act_absmax;   // (equal in all parts: qkv_plan)
+  }
+  auto up = [this](const auto* host, size_t n) {
+    auto* d = ll_.arena.alloc_n<std::remove_cv_t<std::remove_pointer_t<decltype(host)>>>(n);
+    SD_HIP(hipMemcpy(d, host, n * sizeof(*host), hipMemcpyHostToDevice));
+    return d;
+  };
+  size_t bytes = 0;
+  const CompressedWeights cw = upload_w8a8(up, pin.kind, (parts[0] + ".weight").c_str(), q.data(), w_scale.data(), act_absmax,
+                                           (int)parts.size() * cout_each, cin, 1, &bytes);
+  i8_applied_ += (int)parts.size();
+  i8_bytes_ += bytes;
+  for (const std::string& p : parts) i8_names_.push_back(p + ".weight");
+  return ConvWeights(cw, pin);
 }
 
 ConvWeights Net::upload_compressed(const std::string& name, const WeightPin& pin, int cin, const ConvArgs& a, const std::string& ln_name) {
@@ -262,7 +325,7 @@ ConvDesc Net::conv_shape(const std::string& name, const Tensor& x, const ConvArg
   d.ldT = a.ldT;
   d.ln_colsum = a.ln_colsum;
   d.x0_i8 = a.x_i8;
-  if (ln) {
+  if (ln || a.x_i8) {   // (the fused q|k|v launch, folded in fp16 or - plan tile 22 - reading norm1's int8 output)
     d.vt_perm = a.vt_perm ? 1 : 0;
     d.q_scale = a.q_scale;
     d.q_cols = a.q_cols;
@@ -284,7 +347,8 @@ Tensor Net::conv_w(std::vector<Op>& ops, const std::string& name, const ConvWeig
   d.splitk = weights.pin.splitk;
   d.subpix = weights.subpix;
   Tensor out;
-  if (ln && a.n_trans > 0) {   // fused q|k|v: [M][n_trans] row-major + V^T [B][cout - n_trans][ldT]
+  const bool qkv = (ln || a.x_i8) && a.n_trans > 0;
+  if (qkv) {   // fused q|k|v: [M][n_trans] row-major + V^T [B][cout - n_trans][ldT]
     out = new_tensor(x.B, d.Ho, d.Wo, a.n_trans);
     *a.vt_out = ll_.arena.alloc_n<half_t>((size_t)x.B * (cout - a.n_trans) * a.ldT);
     d.out_t = *a.vt_out;
@@ -300,7 +364,7 @@ Tensor Net::conv_w(std::vector<Op>& ops, const std::string& name, const ConvWeig
              name.c_str());
   // a GroupNorm built later over exactly this tensor may ask for its statistics from this op's epilogue (GnHook)
   std::shared_ptr<GnHook> hook;
-  if (a.out_mode == kOutHalf && !(ln && a.n_trans > 0)) {
+  if (a.out_mode == kOutHalf && !qkv) {
     hook = std::make_shared<GnHook>();
     out.gn = hook;
     hook->ops_pos = (int)ops.size();

@@ -80,8 +80,8 @@ struct ConvArgs {
   // handle then uploads the folded matrix (weight_prep.h subpixel_fold, 16/9 of the bytes) INSTEAD of the 3x3 one.  Taken only where the
   // weights run from fp16 and subpixel_wanted says so (Net::conv); a W8A8-marked or palettized upsampler runs what it ran without it.
   bool subpix = false;
-  // conv_w only - the source as int8 [M][C], written by a layernorm_q8 launch in front of this op (plan tile 20 reads nothing else; x
-  // still gives the shape)
+  // conv_w only - the source as int8 [M][C], written by a layernorm_q8 launch in front of this op (plan tiles 20 and 22 read nothing
+  // else; x still gives the shape).  With n_trans > 0 it is the fused q|k|v split without the fold (plan tile 22)
   const int8_t* x_i8 = nullptr;
 };
 
@@ -152,7 +152,17 @@ class Net {
   // make this GEGLU run as plan tile 20?  Then the caller normalises the GEGLU's input into a scratch tensor and observe_tensor puts
   // an absmax launch over it, into a slot named <name>.weight - two ordinary launches that write nothing the model reads.
   bool observes_geglu(const std::string& name, const Tensor& x, const ConvArgs& a, bool ln) const;
-  void observe_tensor(std::vector<Op>& ops, const std::string& name, const Tensor& t);
+  // (report_as: the weight names, without ".weight", the one slot is reported under - <name> alone when empty)
+  void observe_tensor(std::vector<Op>& ops, const std::string& name, const Tensor& t, const std::vector<std::string>& report_as = {});
+  // The fused q|k|v launch `name` over the projections `parts` (to_q, to_k, to_v) in W8A8: qkv_plan answers I8Qkv (plan tile 22) when
+  // every part carries a mark, none a palette, all marks share one act_absmax (one int8 tensor carries one scale) and the planner takes
+  // the un-folded shape (a: cout, ldT, n_trans, vt_perm, q_scale, q_cols of the launch) - else Fp16: the folded launch as ever.
+  // upload_qkv_i8 then uploads the stacked int8 matrix and scales, no fp16 copy, and counts every part as applied, in order.
+  // observes_qkv: the store observes them (WeightStore::observe_qkv) and a mark would make this launch plan tile 22 - the caller then
+  // puts a LayerNorm + observe_tensor pair beside the folded launch, reported under all parts.
+  WeightPin qkv_plan(const std::string& name, const std::vector<std::string>& parts, const Tensor& x, const ConvArgs& a) const;
+  bool observes_qkv(const std::string& name, const std::vector<std::string>& parts, const Tensor& x, const ConvArgs& a) const;
+  ConvWeights upload_qkv_i8(const std::vector<std::string>& parts, const WeightPin& pin, int cin, int cout_each);
   // 3x3 conv to N <= 8 channels, one wavefront per pixel (conv_small.hip): fp32 NCHW into out_nchw (a model's boundary), else
   // fp16 NHWC into out_nhwc.  An fp32 handle runs the fp32 conv into out_nhwc (or a tensor of its own) and transposes.
   void conv_small_n(std::vector<Op>& ops, const std::string& name, const Tensor& x, int cout, half_t* out_nhwc, float* out_nchw);
@@ -180,6 +190,7 @@ class Net {
 
  private:
   ConvDesc conv_shape(const std::string& name, const Tensor& x, const ConvArgs& a) const;
+  ConvDesc qkv_shape(const std::string& name, const Tensor& x, const ConvArgs& a) const;
   int pal_tensors_ = 0, pal_streamed_ = 0;
   size_t pal_stream_bytes_ = 0;
   int i8_marked_ = 0, i8_applied_ = 0;

@@ -214,13 +214,49 @@ Tensor UNet::transformer_block(std::vector<Op>& ops, const std::string& b, const
     vt_perm = pre->vt_perm;
     q_pre = pre->q_pre;
   } else if (can_fold_ln(h, 3 * C, false) && S % 8 == 0 && (2 * C) % 64 == 0) {
-    LnFold f = fold_layernorm(b + ".norm1", {b + ".attn1.to_q", b + ".attn1.to_k", b + ".attn1.to_v"}, C, C, false);
+    const std::string qname = b + ".attn1.to_qkv";
+    const std::vector<std::string> parts = {b + ".attn1.to_q", b + ".attn1.to_k", b + ".attn1.to_v"};
     vt_perm = attention8_shape_ok(C / heads, S, S) && S % 16 == 0;
     // attention8 takes the queries with d^-0.5 * log2(e) already in them: multiplied into the fp32 accumulator here
     q_pre = vt_perm;
-    qk = conv_w(ops, b + ".attn1.to_qkv", f.w, f.bias, h,
-                {.cout = 3 * C, .ldT = ldv, .ln_colsum = f.colsum, .n_trans = 2 * C, .vt_out = &vtp, .vt_perm = vt_perm,
-                 .q_scale = q_pre ? attention_q_prescale(C / heads) : 1.f, .q_cols = q_pre ? C : 0});
+    ConvArgs qa{.cout = 3 * C, .ldT = ldv, .n_trans = 2 * C, .vt_out = &vtp, .vt_perm = vt_perm,
+                .q_scale = q_pre ? attention_q_prescale(C / heads) : 1.f, .q_cols = q_pre ? C : 0};
+    // All three projections W8A8-marked with ONE range, on a shape plan tile 22 takes: norm1 is NOT folded - one layernorm_q8 launch
+    // writes int8(norm1(h)), the tensor the reference calibrates and quantizes for to_q, to_k and to_v alike, and the q|k|v launch
+    // streams it and the stacked int8 matrix (no fp16 copy).  Anything else - one or two marks, three ranges, a shape off the rule -
+    // keeps the folded fp16 launch.  An observing store (observe_qkv) leaves the launch as it is and puts a LayerNorm + absmax pair
+    // over the same tensor, reported under the three weight names.
+    const WeightPin qpin = qkv_plan(qname, parts, h, qa);
+    if (observes_qkv(qname, parts, h, qa)) observe_tensor(ops, qname, layer_norm(ops, b + ".norm1", h), parts);
+    if (qpin.kind == WeightSource::I8Qkv) {
+      const ConvWeights qw = upload_qkv_i8(parts, qpin, C, C);
+      float* qb = nullptr;   // (SD checkpoints have no bias on to_q / to_k / to_v; one that has goes up stacked, absent parts zero)
+      if (ws_->has(parts[0] + ".bias") || ws_->has(parts[1] + ".bias") || ws_->has(parts[2] + ".bias")) {
+        std::vector<float> hb((size_t)3 * C, 0.f);
+        for (int i = 0; i < 3; ++i)
+          if (ws_->has(parts[i] + ".bias")) {
+            const HostTensor& tb = ws_->get(parts[i] + ".bias");
+            SD_REQUIRE((int)tb.numel() == C, kInvalidArgument, "%s.bias: bad shape", parts[i].c_str());
+            std::copy(tb.data.begin(), tb.data.end(), hb.begin() + (size_t)i * C);
+          }
+        qb = ll_.arena.alloc_n<float>(hb.size());
+        SD_HIP(hipMemcpy(qb, hb.data(), hb.size() * sizeof(float), hipMemcpyHostToDevice));
+      }
+      const float* nw = upload_vec(b + ".norm1.weight", C);
+      const float* nb = upload_vec(b + ".norm1.bias", C);
+      const int M = h.M();
+      int8_t* xq = ll_.arena.alloc_n<int8_t>((size_t)M * C);
+      const half_t* xp = h.p;
+      const float inv_s = qw.cw.inv_s;
+      ops.push_back([=](hipStream_t s) { launch_layernorm_q8(xp, nw, nb, xq, M, C, 1e-5f, inv_s, s); });
+      ops.back().label = "layernorm_q8 " + b + ".norm1";
+      qa.x_i8 = xq;
+      qk = conv_w(ops, qname, qw, qb, h, qa);
+    } else {
+      LnFold f = fold_layernorm(b + ".norm1", parts, C, C, false);
+      qa.ln_colsum = f.colsum;
+      qk = conv_w(ops, qname, f.w, f.bias, h, qa);
+    }
   } else {
     Tensor n1 = layer_norm(ops, b + ".norm1", h);
     qk = conv_stacked(ops, {b + ".attn1.to_q", b + ".attn1.to_k"}, n1, C);   // [M][2C]: q | k

@@ -204,6 +204,13 @@ inline void smgeglu_i8_pack(const int8_t* q, int N2, int K, int8_t* dst) {
       std::copy(q + (size_t)o * K, q + (size_t)(o + 1) * K, dst + ((size_t)strip * 16 + i) * K);
     }
 }
+// The int8 weights of smqkv_i8.hip (plan tile 22), q [3C][K] = the stacked [Wq | Wk | Wv] of a self-attention, each in the checkpoint's
+// row order, 3C % 16 == 0, K % 64 == 0: [3C / 16 strips][16 rows][K] - strip t holds the stacked rows 16 t .. 16 t + 15, every row
+// whole.  A tile of 160 output columns stages the ten consecutive strips 10 n_tile .. 10 n_tile + 9, each stage 64 contiguous bytes of
+// every row; with C % 160 == 0 a tile's strips belong to one of the three matrices.  The layout is stated here once: the function is a
+// copy.  Bytes: 3C * K.
+inline size_t smqkv_i8_bytes(int N3, int K) { return (size_t)N3 * K; }
+inline void smqkv_i8_pack(const int8_t* q, int N3, int K, int8_t* dst) { std::copy(q, q + smqkv_i8_bytes(N3, K), dst); }
 // What an upload of a W8A8 conv starts from (sd_op_conv2d_w8a8 / _halo, sd_op_gemm_w8a8, Net::conv), checked in the order the header lists: act_absmax, finite
 // positive scales, no value of -128 (the symmetric scheme has none); the packed stream, cs[n] = fp32(s_a * s_w[n]) with s_a = act_absmax / 127, and inv_s = fp32(1 / s_a).
 struct W8A8HostCopy {
@@ -213,7 +220,7 @@ struct W8A8HostCopy {
 };
 inline bool w8a8_absmax_ok(float act_absmax) { return std::isfinite(act_absmax) && act_absmax > 0.f; }
 inline W8A8HostCopy w8a8_host_copy(const char* what, const int8_t* q, const float* w_scale, float act_absmax, int N, int Ctot, int ksize,
-                                   WeightSource kind = WeightSource::I8Wstream) {   // one of the four int8 kinds
+                                   WeightSource kind = WeightSource::I8Wstream) {   // one of the five int8 kinds
   SD_REQUIRE(w8a8_absmax_ok(act_absmax), kInvalidArgument, "%s: act_absmax = %g, not a positive finite number", what, (double)act_absmax);
   const size_t n_el = wstream_i8_bytes(N, Ctot, ksize);
   W8A8HostCopy h;
@@ -231,6 +238,7 @@ inline W8A8HostCopy w8a8_host_copy(const char* what, const int8_t* q, const floa
   if (kind == WeightSource::I8Halo) halo_i8_pack(q, N, Ctot, ksize, h.stream.data());
   else if (kind == WeightSource::I8Gemm) smgemm_i8_pack(q, N, Ctot, h.stream.data());   // (ksize 1)
   else if (kind == WeightSource::I8Geglu) smgeglu_i8_pack(q, N, Ctot, h.stream.data());
+  else if (kind == WeightSource::I8Qkv) smqkv_i8_pack(q, N, Ctot, h.stream.data());     // (ksize 1; N = 3C stacked rows)
   else wstream_i8_pack(q, N, Ctot, ksize, h.stream.data());
   return h;
 }

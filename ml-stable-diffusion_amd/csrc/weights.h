@@ -51,6 +51,9 @@ class WeightStore {
   // ... and over the LayerNorm output in front of every GEGLU projection plan tile 20 could take (two launches beside the folded GEGLU)
   void set_observe_geglus(bool on) { observe_geglus_ = on; }
   bool observe_geglus() const { return observe_geglus_; }
+  // ... and over the output of norm1 in front of every fused q|k|v launch plan tile 22 could take (the same two launches)
+  void set_observe_qkv(bool on) { observe_qkv_ = on; }
+  bool observe_qkv() const { return observe_qkv_; }
   void add(const std::string& name, const void* data, int dtype /*0 f16, 1 f32, 2 bf16*/,
            const int64_t* shape, int ndim);
   void load_safetensors(const std::string& path, const std::string& prefix);
@@ -73,6 +76,7 @@ class WeightStore {
   int observe_ = 0;
   bool observe_gemms_ = false;
   bool observe_geglus_ = false;
+  bool observe_qkv_ = false;
 };
 
 }  // namespace sd

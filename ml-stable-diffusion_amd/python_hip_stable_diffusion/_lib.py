@@ -102,6 +102,7 @@ SYMBOLS = [
     ("sd_weights_observe_activations", _I, [_P, _I]),
     ("sd_weights_observe_gemms", _I, [_P, _I]),
     ("sd_weights_observe_geglus", _I, [_P, _I]),
+    ("sd_weights_observe_qkv", _I, [_P, _I]),
     ("sd_unet_w8a8_info", _I, [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(C.c_size_t)]),
     ("sd_unet_w8a8_layer", _I, [_P, _I, C.c_char_p, _I]),
     ("sd_unet_activation_ranges", _I, [_P, _I, C.c_char_p, _I, _FP]),
@@ -117,6 +118,8 @@ SYMBOLS = [
     ("sd_op_layernorm_q8", _I, [_P, _FP, _FP, _F, _F, _P, _I, _I, _I, _FP]),
     ("sd_op_geglu_w8a8", _I, [_P, _P, _FP, _F, _FP, _P, _I, _I, _I, _I, C.POINTER(_I), _I, _FP]),
     ("sd_op_w8a8_pack_geglu", _I, [_P, _I, _I, _P, C.POINTER(C.c_size_t)]),
+    ("sd_op_qkv_w8a8", _I, [_P, _P, _FP, _F, _FP, _P, _P, _I, _I, _I, _F, _I, _I, C.POINTER(_I), _I, _FP]),
+    ("sd_op_w8a8_pack_qkv", _I, [_P, _I, _P, C.POINTER(C.c_size_t)]),
     ("sd_op_quantize_weight", _I, [_FP, _I, C.c_size_t, _P, _FP, C.POINTER(C.c_double)]),
     ("sd_op_absmax", _I, [_P, C.c_size_t, _FP]),
     ("sd_unet_create", _I, [C.POINTER(UNetConfig), _P, _I, C.POINTER(_P)]),
@@ -746,6 +749,49 @@ def w8a8_pack_geglu(wq):
         raise ValueError("w8a8_pack_geglu: wq must be (N2, K)")
     N2, K = wq.shape
     return _packed(lib().sd_op_w8a8_pack_geglu, ptr(wq), N2, K).view(np.int8).reshape(N2 // 16, 16, K)
+
+
+def qkv_w8a8(xq, wq, w_scale, act_absmax, batch, q_scale=1.0, vt_perm=True, bias=None, bm=0, out_qk=None, out_vt=None, iters=1):
+    """The fused q|k|v projection of a self-attention in W8A8 (sd_op_qkv_w8a8, plan tile 22; the int8 form of ``qkv_ln`` behind
+    ``layernorm_q8``: unet.py:583-586 -> :74-84 under quantize_cumulative_config): xq (batch * HW, C) int8, wq (3C, C) int8 =
+    [Wq | Wk | Wv], w_scale (3C,) f32, act_absmax the range xq was quantized with, bias (3C,) f32 or None; q_scale multiplies the
+    queries before the rounding (1: skipped), vt_perm = V^T in the d = 64 attention kernel's key order, bm 0 / 128 / 256 = the tile
+    height (0: by the grid).  ``out_qk`` / ``out_vt``: C-contiguous float16 buffers of at least batch * HW * 2C / batch * C * HW
+    elements (tests put guards behind them).  What the library checks it refuses itself (ValueError, no GPU needed).
+    Returns (out_qk (batch * HW, 2C), out_vt (batch, C, HW), plan, ms)."""
+    xq = np.ascontiguousarray(xq, dtype=np.int8)
+    wq = np.ascontiguousarray(wq, dtype=np.int8)
+    w_scale = f32(w_scale)
+    if xq.ndim != 2 or wq.ndim != 2 or wq.shape != (3 * xq.shape[1], xq.shape[1]) or w_scale.shape != (wq.shape[0],) or batch < 1 or xq.shape[0] % batch:
+        raise ValueError("qkv_w8a8: xq must be (batch * HW, C), wq (3C, C) and w_scale (3C,)")
+    M, Cc = xq.shape
+    HW = M // batch
+    bias = None if bias is None else f32(bias)
+    if bias is not None and bias.shape != (3 * Cc,):
+        raise ValueError("qkv_w8a8: bias must be (3C,)")
+    n_qk, n_vt = M * 2 * Cc, batch * Cc * HW
+    if out_qk is None:
+        out_qk = np.empty(n_qk, np.float16)
+    if out_vt is None:
+        out_vt = np.empty(n_vt, np.float16)
+    for buf, n in ((out_qk, n_qk), (out_vt, n_vt)):
+        if buf.dtype != np.float16 or not buf.flags.c_contiguous or buf.size < n:
+            raise ValueError("qkv_w8a8: out_qk / out_vt must be C-contiguous float16 buffers of at least M * 2C / batch * C * HW elements")
+    plan = (C.c_int * 4)()
+    ms = C.c_float(0)
+    check(lib().sd_op_qkv_w8a8(ptr(xq), ptr(wq), fptr(w_scale), float(act_absmax), fptr(bias), ptr(out_qk), ptr(out_vt), batch, HW, Cc,
+                               float(q_scale), int(bool(vt_perm)), bm, plan, iters, C.byref(ms)))
+    return out_qk.reshape(-1)[:n_qk].reshape(M, 2 * Cc), out_vt.reshape(-1)[:n_vt].reshape(batch, Cc, HW), list(plan), ms.value
+
+
+def w8a8_pack_qkv(wq):
+    """The int8 weights of the W8A8 q|k|v projection (sd_op_w8a8_pack_qkv; host only): wq (3C, C) int8 = [Wq | Wk | Wv] -> int8
+    (3C / 16, 16, C), strip t = the stacked rows 16 t .. 16 t + 15."""
+    wq = np.ascontiguousarray(wq, dtype=np.int8)
+    if wq.ndim != 2 or wq.shape[0] != 3 * wq.shape[1]:
+        raise ValueError("w8a8_pack_qkv: wq must be (3C, C)")
+    Cc = wq.shape[1]
+    return _packed(lib().sd_op_w8a8_pack_qkv, ptr(wq), Cc).view(np.int8).reshape(3 * Cc // 16, 16, Cc)
 
 
 def w8a8_pack(wq):

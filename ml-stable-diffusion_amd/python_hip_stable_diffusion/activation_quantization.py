@@ -10,13 +10,20 @@ a marked conv from int8 on ``v_mfma_i32_32x32x32_i8`` wherever its plan is the w
 ``attn2.to_out.0`` of the 640- / 1280-channel levels) on ``v_mfma_i32_16x16x64_i8`` wherever its plan is the small-M GEMM
 (``smgemm_i8.hip``, plan tile 19), and a marked GEGLU projection (``ff.net.0.proj`` of those levels) on the same instruction wherever
 its plan is ``smgeglu.hip`` (``smgeglu_i8.hip``, plan tile 20): its ``norm3`` is then not folded into the weights - one LayerNorm launch
-writes ``int8(norm3(x))``, the tensor the reference calibrates, and the GEGLU reads it; every other marked conv stays fp16 - the reference's skipped layers.  Parity with coremltools' quantizer is NOT pinned
+writes ``int8(norm3(x))``, the tensor the reference calibrates, and the GEGLU reads it, and the marked self-attention projections
+``attn1.to_q`` / ``to_k`` / ``to_v`` of those levels as ONE fused launch (``smqkv_i8.hip``, plan tile 22) behind a LayerNorm launch that
+writes ``int8(norm1(x))`` - when all three are named with the same range, which is what ``observe_activations="attn"`` reports; every
+other marked conv stays fp16 - the reference's skipped layers: one or two of the three q|k|v tensors or three different ranges, the
+8x8 mid block's and the 320-channel level's q|k|v, ``attn2.to_q`` (inside the fused cross-attention launch), the prompt-side
+``attn2.to_k`` / ``to_v``, the merged transformer tail, ``conv_shortcut`` s and stride-2 convs.  Parity with coremltools' quantizer is NOT pinned
 (coremltools is not a dependency of this project): the scales are plain absmax / 127, not the result of its calibration.
 
 Calibration happens on the device: ``HipModel(..., observe_activations=True)`` puts an absmax observer in front of every conv
 the int8 weight stream could take, ``observe_activations="all"`` in front of every conv either int8 conv kernel could take, ``observe_activations="gemm"`` also in front of
 the projections plan tile 19 could take, ``observe_activations="geglu"`` also over the output of ``norm3`` in front of every GEGLU
-projection plan tile 20 could take (a LayerNorm and an absmax launch beside the folded fp16 GEGLU, whose output does not change) -
+projection plan tile 20 could take (a LayerNorm and an absmax launch beside the folded fp16 GEGLU, whose output does not change),
+``observe_activations="attn"`` also over the output of ``norm1`` in front of every fused q|k|v launch plan tile 22 could take (the same
+two launches; the one range is reported under ``attn1.to_q``, ``to_k`` and ``to_v``) -
 every layer that could run from int8; after any number of forwards ``.activation_ranges()`` is the recipe's raw material.
 
 A recipe is JSON ``{layer: act_absmax}``, ``layer`` the conv's module name (its weight tensor without ``.weight``).
@@ -34,6 +41,13 @@ _SUFFIX = ".weight"
 
 # ``--calibrate-scope`` -> ``observe_activations``: each scope observes the previous one's layers and its own
 CALIBRATION_SCOPES = {"stream": True, "all": "all", "gemm": "gemm", "geglu": "geglu"}
+# the scopes added since, in a mapping of their own: "attn" observes what "geglu" does plus the self-attention q|k|v launches
+ATTENTION_SCOPES = {"attn": "attn"}
+
+
+def calibration_scopes():
+    """every ``--calibrate-scope`` -> ``observe_activations``, in the order each adds to the one before"""
+    return {**CALIBRATION_SCOPES, **ATTENTION_SCOPES}
 
 
 def layer_of(tensor_name):

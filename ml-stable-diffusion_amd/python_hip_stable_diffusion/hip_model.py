@@ -200,10 +200,13 @@ class Weights(_lib.Handle):
         """Handles created from the store while this is on carry the activation observers (calibration): ``True`` in front of the
         convs the int8 weight stream could take (plan tile 17), ``"all"`` in front of those of the int8 halo conv (plan tile 18) too,
         ``"gemm"`` also in front of the plain 1x1 projections the int8 small-M GEMM could take (plan tile 19), ``"geglu"`` also over
-        the LayerNorm output in front of every GEGLU projection the int8 GEGLU kernel could take (plan tile 20)."""
+        the LayerNorm output in front of every GEGLU projection the int8 GEGLU kernel could take (plan tile 20), ``"attn"`` also over
+        the output of ``norm1`` in front of every fused q|k|v launch the int8 q|k|v kernel could take (plan tile 22; one range,
+        reported under ``attn1.to_q``, ``to_k`` and ``to_v``)."""
         _lib.check(_lib.lib().sd_weights_observe_activations(self._h, observe_level(on)))
-        _lib.check(_lib.lib().sd_weights_observe_gemms(self._h, int(on in ("gemm", "geglu"))))
-        _lib.check(_lib.lib().sd_weights_observe_geglus(self._h, int(on == "geglu")))
+        _lib.check(_lib.lib().sd_weights_observe_gemms(self._h, int(on in ("gemm", "geglu", "attn"))))
+        _lib.check(_lib.lib().sd_weights_observe_geglus(self._h, int(on in ("geglu", "attn"))))
+        _lib.check(_lib.lib().sd_weights_observe_qkv(self._h, int(on == "attn")))
 
     @classmethod
     @contextlib.contextmanager
@@ -222,10 +225,11 @@ class Weights(_lib.Handle):
 
 def observe_level(on):
     """observe_activations as the level of sd_weights_observe_activations: False 0, True 1, "all" 2; "gemm" is level 2 with the
-    projections' flag (sd_weights_observe_gemms) beside it, "geglu" level 2 with that flag and the GEGLUs' (sd_weights_observe_geglus)."""
+    projections' flag (sd_weights_observe_gemms) beside it, "geglu" level 2 with that flag and the GEGLUs' (sd_weights_observe_geglus),
+    "attn" level 2 with those two and the self-attention q|k|v launches' (sd_weights_observe_qkv)."""
     if isinstance(on, str):
-        if on not in ("all", "gemm", "geglu"):
-            raise ValueError(f"observe_activations must be False, True, 'all', 'gemm' or 'geglu', got {on!r}")
+        if on not in ("all", "gemm", "geglu", "attn"):
+            raise ValueError(f"observe_activations must be False, True, 'all', 'gemm', 'geglu' or 'attn', got {on!r}")
         return 2
     return int(bool(on))
 
@@ -309,9 +313,10 @@ class HipModel(_lib.Model):
         if self.activation_quantization is not None:
             applied = set(self.w8a8_layers())
             stayed = sorted(set(self.activation_quantization) - applied)
-            logger.info("W8A8: %d of %d recipe layers run from int8 (plan tiles 17 / 18 / 19)", len(applied), len(self.activation_quantization))
+            logger.info("W8A8: %d of %d recipe layers run from int8 (plan tiles 17 / 18 / 19 / 20 / 22)", len(applied), len(self.activation_quantization))
             if stayed:
-                logger.info("W8A8: these layers stay fp16 (their plan is none of the weight stream, the halo conv and the plain small-M projection): %s", ", ".join(stayed))
+                logger.info("W8A8: these layers stay fp16 (their plan is none of the weight stream, the halo conv, the plain small-M projection, the "
+                            "GEGLU kernel and the fused self-attention q|k|v launch with its three tensors under one range): %s", ", ".join(stayed))
         self.batch, self.latent_height, self.latent_width = batch, h, w
         self.attention_implementation = attention_implementation
         self.num_residuals = _lib.lib().sd_unet_num_residuals(self._h)
