@@ -42,6 +42,8 @@ struct GnTwin {
 //               the activations arrive quantized (ConvDesc::x0_i8, written by launch_layernorm_q8)
 //   I8Qkv       tile 22, smqkv_i8.hip         smqkv_i8_kernel (W8A8)          stream of smqkv_i8_pack     staging: 1 / 2 = 128- / 256-row tiles (0 = by the
 //               grid); the stacked [Wq | Wk | Wv] of a fused q|k|v launch, activations quantized by their producer as for I8Geglu
+//   (tiles 19, 20, 22: LDS image, ladder, epilogue arithmetic and launch, and the ring geometry, issue and wait of tiles 20 and 22, are
+//   sm_i8_ring.h's)
 enum class WeightSource { Fp16, PalWstream, PalGemm, PalGeglu, I8Wstream, I8Halo, I8Gemm, I8Geglu, I8Qkv };
 struct CompressedWeights {
   WeightSource kind = WeightSource::Fp16;

@@ -7,7 +7,6 @@ namespace sd {
 
 namespace {
 
-typedef unsigned uintx2 __attribute__((ext_vector_type(2)));
 typedef int intx4 __attribute__((ext_vector_type(4)));
 typedef int intx16 __attribute__((ext_vector_type(16)));
 

@@ -21,6 +21,7 @@ typedef _Float16 half2v __attribute__((ext_vector_type(2)));
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
+typedef unsigned uintx2 __attribute__((ext_vector_type(2)));
 
 // Output stores of the step's kernels.  -DSD_SC1_STORES (experiment, round 6): write-through (sc1) instead of plain stores, so that
 // a kernel's results leave the XCD's L2 while it runs instead of at its end-of-kernel release (MI355X_MICROARCH.md "boundary":

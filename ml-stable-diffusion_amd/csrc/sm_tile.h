@@ -1,5 +1,6 @@
-// What the whole-LDS-ring kernels (smgemm.hip, smgeglu.hip) share around their K loops: the XCD-aware tile order - the host's four
-// numbers and the division-free prologue that reads them - and the register epilogue's lane exchange.  (sm_ring.h: the counted waits.)
+// What the whole-LDS-ring kernels (smgemm.hip, smgeglu.hip and their int8 forms) share around their K loops: the XCD-aware tile order -
+// the host's four numbers and the division-free prologue that reads them - and the register epilogue's rounding and lane exchange.
+// (sm_ring.h: the counted waits; sm_i8_ring.h: what only the int8 forms share.)
 // The device helpers take and return VALUES and hold no arithmetic the compiler re-associates with its surroundings: with those two
 // properties hipcc's code for the kernels is the code of the same text written in place (LAB_NOTES.md, "one body").
 #pragma once
@@ -45,5 +46,14 @@ __device__ __forceinline__ half8 sm_swap16(unsigned lo0, unsigned lo1, unsigned 
   const unsigned d0 = s0[0], d1 = s1[0], d2 = s0[1], d3 = s1[1];   // scalars first (igemm.hip xor32_sum)
   return __builtin_bit_cast(half8, (uintx4){d0, d1, d2, d3});
 }
+
+// ... from fp32: sm_round4 rounds the lane's four columns of one block to fp16 once, {lo | hi}, as soon as the block has them (where
+// the roundings stand decides hipcc's schedule of the epilogue); sm_pack16 exchanges the two blocks
+__device__ __forceinline__ uintx2 sm_round4(floatx4 v) {
+  const half2v h01 = {(half_t)v[0], (half_t)v[1]};
+  const half2v h23 = {(half_t)v[2], (half_t)v[3]};
+  return uintx2{__builtin_bit_cast(unsigned, h01), __builtin_bit_cast(unsigned, h23)};
+}
+__device__ __forceinline__ half8 sm_pack16(uintx2 b0, uintx2 b1) { return sm_swap16(b0[0], b1[0], b0[1], b1[1]); }
 
 }  // namespace sd

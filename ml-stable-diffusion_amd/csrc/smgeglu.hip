@@ -461,17 +461,17 @@ __global__ __launch_bounds__(64 * SG_NW, 1) void smgeglu_kernel(std::conditional
   }
   if constexpr (PROF) stamp[4] = clock64();
 
-  // ---- epilogue: tile_epilogue's arithmetic in fp32, one rounding to fp16, blocks (2p, 2p + 1) paired by sm_swap16 ----
+  // ---- epilogue: tile_epilogue's arithmetic in fp32, one rounding to fp16, blocks (2p, 2p + 1) paired by sm_pack16 ----
   const floatx4 zero4 = {0.f, 0.f, 0.f, 0.f};
   const floatx4 bv = a.has_bias ? bias_v : zero4, bg = a.has_bias ? bias_g : zero4;
   const int n = (u_blk + u) * 16 + 8 * (g >> 1);
 #pragma unroll
   for (int p = 0; p < TM / 2; ++p) {
-    unsigned lo[2], hi[2];   // [block 2p | block 2p + 1] x {columns 4 g, 4 g + 1 | 4 g + 2, 4 g + 3}
+    uintx2 ho[2];   // block 2p | block 2p + 1: columns 4 g .. 4 g + 3 in fp16
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
       const int i = 2 * p + b;
-      float o[4];
+      floatx4 o;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float v, gt;
@@ -484,12 +484,9 @@ __global__ __launch_bounds__(64 * SG_NW, 1) void smgeglu_kernel(std::conditional
         }
         o[e] = v * sg_gelu_erf(gt);
       }
-      const half2v h01 = {(half_t)o[0], (half_t)o[1]};
-      const half2v h23 = {(half_t)o[2], (half_t)o[3]};
-      lo[b] = __builtin_bit_cast(unsigned, h01);
-      hi[b] = __builtin_bit_cast(unsigned, h23);
+      ho[b] = sm_round4(o);
     }
-    const half8 o8 = sm_swap16(lo[0], lo[1], hi[0], hi[1]);
+    const half8 o8 = sm_pack16(ho[0], ho[1]);
     const int m = m_blk + h * (BM / 2) + 32 * p + 16 * (g & 1) + r16;
     out_store(reinterpret_cast<half8*>(a.out + (size_t)m * a.ldo + n), o8);
   }

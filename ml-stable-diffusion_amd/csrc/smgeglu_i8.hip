@@ -4,7 +4,8 @@
 // sm_swap16 with no LDS and no barrier - so tile order, tile counts and eligibility (smgeglu_shape_ok) are tile 13's.
 // The semantics are the int8 kernels' (sd_weights_quantize_w8a8 in sd_mi355x.h): int8 weights never -128, exact int32 sums over the WHOLE
 // K (127 * 127 * K < 2^31, kSmI8MaxK), one conversion to fp32, one product with cs[n] = fp32(s_a * s_w[n]), the bias added in fp32 - each
-// operation rounded on its own (sgi_affine, fp contract off) - and then tile 13's own ending, out = fp16(v * gelu_erf(g)).
+// operation rounded on its own (sm_i8_affine) - and then tile 13's own ending, out = fp16(v * gelu_erf(g)).
+// Stage, LDS image, piece distribution, issue, counted wait and the K loop's RAW / WAR and vmcnt arguments: sm_i8_ring.h.
 //
 // What differs from tile 13, and why:
 //   * THE ACTIVATIONS ARRIVE AS INT8.  The LayerNorm in front of ff.net.0.proj is not folded: layernorm_q8_kernel (norm.hip) writes
@@ -13,44 +14,23 @@
 //   * MFMA: v_mfma_i32_16x16x64_i8, ONE instruction per 16 x 16 block and K64 stage (tile 13: two K32 steps).  Operand / result layout:
 //     bit 4 of sd_selftest_mfma; A and B share the lane -> k map, the result layout is tile 13's.
 //   * WEIGHTS int8 in the order of smgeglu_i8_pack (weight_prep.h): 16-row strips, strip 2 U + v = the value (v = 0) / gate (v = 1) rows
-//     of the output's 16-column unit U, so a tile's 160 rows are ten consecutive strips.
-//   * STAGE = K64: [10 weight strips | BM / 16 activation strips], every strip ONE 1-KiB LDS-DMA piece of 16 rows x 64 B - 18 KB
-//     (BM = 128) / 26 KB (BM = 256), half of tile 13's.  K64 and not K128 (two MFMA steps per barrier): the kernel keeps tile 13's
-//     eligibility rule C % 64 == 0 with no tail stage, the ring gets twice the depth in stages for the same bytes in flight (8 / 6
-//     stages = 144 / 156 KB of the 160), and a barrier still covers 8 / 16 MFMAs of 16 x 16 x 64 per wave - the MFMA time of a tile-13
-//     K64 stage, whose barrier count this kernel therefore shares.  Not measured against a K128 build.
-//   * PIECES: 18 / 26 per stage over ten waves - piece wave + 10 j, the first FULL = 8 / 6 waves issue PPW = 2 / 3 per stage, the others
-//     one less; every wave counts its own vmcnt (two instances of the ladder behind a wave-uniform branch, as in tile 13).
-//   * LDS image of a piece [16 rows][4 x 16 B]: the 16-B chunk kc of row r at position kc ^ F((r >> 2) & 3), F = (0, 2, 3, 1), applied on
-//     the source address; a fragment read is lane (g, r16) -> row r16, chunk g.  This is the access pattern of tile 19's weight strips,
-//     and its argument holds (smgemm_i8.hip): a ds_read_b128 lane group covers every row residue mod 4 four times with two chunk values,
-//     and F sends them to 16 distinct 16-B slots of the 256-B bank row.  Weights and activations share piece shape and read pattern.
-//   * bias and cs of the lane's four value and four gate rows (the upload's interleaved order, geglu_row) are requested right behind
-//     the first NST - 1 ring stages and counted in the same vmcnt.
-// The K loop, step s (NST the ring depth), one barrier per stage:
-//     [wait: this wave's pieces of stage s have landed | lgkmcnt(0) | s_barrier]
-//     issue stage s + NST - 1 -> slot (s - 1) % NST;  read the two weight fragments and the TM activation fragments of stage s;  MFMAs
-//   * RAW: a stage is read behind the barrier that follows every wave's counted wait for its own pieces of it.
-//   * WAR: slot (s - 1) % NST held stage s - 1; every wave has its fragments of that stage in registers (the lgkmcnt(0) in front of the
-//     barrier of step s) before any wave issues into the slot behind that barrier.
-//   * counted wait of step s: issued are stages 0 .. min(s + NST - 2, nk - 1); younger than stage s are min(NST - 2, nk - 1 - s) stages
-//     of this wave's pieces and, while s <= NST - 2, the EPI epilogue loads.
+//     of the output's 16-column unit U, so a tile's 160 rows are ten consecutive strips and a wave's strip pair is one unit.
+//   * STAGE = K64, 18 KB (BM = 128) / 26 KB (BM = 256), half of tile 13's.  K64 and not K128 (two MFMA steps per barrier): the kernel
+//     keeps tile 13's eligibility rule C % 64 == 0 with no tail stage, the ring gets twice the depth in stages for the same bytes in
+//     flight, and a barrier still covers 8 / 16 MFMAs of 16 x 16 x 64 per wave - the MFMA time of a tile-13 K64 stage, whose barrier
+//     count this kernel therefore shares.  Not measured against a K128 build.
 #include "conv_plan.h"
 #include "igemm_device.h"
 #include "kernels.h"
 #include "quantize8.h"
-#include "sm_tile.h"
+#include "sm_i8_ring.h"
 #include "weight_prep.h"
 
 namespace sd {
 
 namespace {
 
-constexpr int SGI_BK = 64;                  // K bytes per ring stage and row
-constexpr int SGI_UNITS = 5;                // 16-column units side by side
-constexpr int SGI_WROWS = 32 * SGI_UNITS;   // weight rows per workgroup: 16 value + 16 gate rows per unit
-constexpr int SGI_NW = 2 * SGI_UNITS;       // waves: unit x row half
-constexpr int SGI_LDS = 160 * 1024;
+constexpr int SGG_UNITS = SM_I8_WROWS / 32;   // 16-column units side by side: 16 value + 16 gate rows each
 
 struct SgI8Args {
   const int8_t* xq;     // [M][K]
@@ -63,65 +43,21 @@ struct SgI8Args {
   SmTileOrder order;
 };
 
-template <int BM>
-struct SgI8Cfg {
-  static constexpr int PIECES = (SGI_WROWS + BM) / 16;          // 1-KiB LDS-DMA pieces (16 rows x 64 B) per stage: weights, then activations
-  static constexpr int PPW = (PIECES + SGI_NW - 1) / SGI_NW;    // pieces per wave per stage: the first FULL waves; the others one less
-  static constexpr int FULL = PIECES - SGI_NW * (PPW - 1);
-  static constexpr int STAGE = PIECES * 1024;
-  static constexpr int NST = SGI_LDS / STAGE;                   // ring depth: 8 / 6
-  static constexpr int TM = BM / 32;                            // 16-row blocks per wave (one row half)
-  static constexpr int EPI = 4;                                 // epilogue loads per lane: bias and cs of value / gate rows
-  static constexpr size_t LDS = (size_t)NST * STAGE;
-  static_assert(BM % 128 == 0 && PPW >= 2 && FULL >= 1 && FULL <= SGI_NW, "tile");
-  static_assert(NST >= 3 && LDS <= SGI_LDS, "ring");
-  static_assert(PPW * (NST - 2) + EPI <= 63, "vmcnt range");
-};
-
 // first row, in the upload's interleaved order, of 16-column unit U of the output: its 16 value rows; the gate rows are 32 further on
-__device__ __forceinline__ int sgi_unit_row(int U) { return 64 * (U >> 1) + 16 * (U & 1); }
-
-// position of the 16-B chunk kc in a 64-B row of row quad R = (row >> 2) & 3: kc ^ F(R), F = (0, 2, 3, 1) (an involution per row)
-__device__ __forceinline__ int sgi_swz(int kc, int row) { return kc ^ ((0x78 >> (2 * ((row >> 2) & 3))) & 3); }
-
-// counted wait + the LDS counter + raw barrier in one statement (no LDS access moves across)
-template <int N>
-__device__ __forceinline__ void sgi_wait_barrier() {
-  asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
-}
-template <int PPW, int E, int A>
-__device__ __forceinline__ void sgi_wait(int ahead) {   // (the immediate must be a literal, hence the ladder)
-  if constexpr (A > 0) {
-    if (ahead == A) {
-      sgi_wait_barrier<PPW * A + E>();
-      return;
-    }
-    sgi_wait<PPW, E, A - 1>(ahead);
-  } else {
-    sgi_wait_barrier<E>();
-  }
-}
-
-// the int8 epilogue's arithmetic for one accumulator, each operation rounded on its own (hipcc contracts a * b + c into an fma by default)
-__device__ __forceinline__ float sgi_affine(int acc, float cs, float bias, bool has_bias) {
-#pragma clang fp contract(off)
-  float v = (float)acc * cs;
-  if (has_bias) v = v + bias;
-  return v;
-}
+__device__ __forceinline__ int geglu_unit_row(int U) { return 64 * (U >> 1) + 16 * (U & 1); }
 
 template <int BM>
-__global__ __launch_bounds__(64 * SGI_NW, 1) void smgeglu_i8_kernel(SgI8Args a) {
-  using C = SgI8Cfg<BM>;
+__global__ __launch_bounds__(64 * SM_I8_NW, 1) void smgeglu_i8_kernel(SgI8Args a) {
+  using C = SmI8RingCfg<BM, 4>;   // EPI = 4: bias_v, bias_g, cs_v, cs_g below
   constexpr int NST = C::NST, PPW = C::PPW, TM = C::TM;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-  const int u = wave % SGI_UNITS, h = wave / SGI_UNITS;   // column unit, row half
+  const int u = wave % SGG_UNITS, h = wave / SGG_UNITS;   // column unit, row half
 
   int m_tile, n_tile;
   sm_tile_coords(a.order, m_tile, n_tile);
-  const int m_blk = m_tile * BM, u_blk = n_tile * SGI_UNITS;   // first row, first 16-column unit of the tile
+  const int m_blk = m_tile * BM, u_blk = n_tile * SGG_UNITS;   // first row, first 16-column unit of the tile
 
   // ---- staging: piece wave + 10 j of every stage (the last j only on the first FULL waves); lane = 4 row + position ----
   const bool full = wave < C::FULL;
@@ -129,33 +65,23 @@ __global__ __launch_bounds__(64 * SGI_NW, 1) void smgeglu_i8_kernel(SgI8Args a) 
   int pdst[PPW];
 #pragma unroll
   for (int j = 0; j < PPW; ++j) {
-    int p = wave + SGI_NW * j;
+    int p = wave + SM_I8_NW * j;
     if (p >= C::PIECES) p -= C::PIECES;                   // (never issued: keeps the address in range)
     pdst[j] = p * 1024;
     const int r = lane >> 2;
-    const int chunk = sgi_swz(lane & 3, r);               // logical chunk at physical position lane & 3
-    const int wp = SGI_WROWS / 16;                        // weight pieces: strips 2 u_blk .. 2 u_blk + 9
+    const int chunk = sm_i8_swz(lane & 3, r);             // logical chunk at physical position lane & 3
+    const int wp = SM_I8_WROWS / 16;                      // weight pieces: strips 2 u_blk .. 2 u_blk + 9
     src[j] = (p < wp ? a.w + ((size_t)(2 * u_blk + p) * 16 + r) * a.K : a.xq + (size_t)(m_blk + 16 * (p - wp) + r) * a.K) + chunk * 16;
   }
-  // ring stage into slot `slot`
-  auto issue = [&](int slot) __attribute__((always_inline)) {
-    char* st = smem + slot * C::STAGE;
-#pragma unroll
-    for (int j = 0; j < PPW; ++j) {
-      if (j == PPW - 1 && !full) break;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src[j],
-                                       (__attribute__((address_space(3))) void*)(st + pdst[j]), 16, 0, 0);
-      src[j] += SGI_BK;
-    }
-  };
+  const SmI8Ring<C> ring{smem, full, src, pdst};
 
 #pragma unroll
   for (int p = 0; p < NST - 1; ++p)
-    if (p < a.nk) issue(p);
+    if (p < a.nk) ring.issue(p);
   // the epilogue operands right behind the first ring stages: bias and cs of this lane's four value and four gate rows (bias absent: a
   // readable dummy, so that every launch counts the same loads)
   const int g = lane >> 4, r16 = lane & 15;
-  const int vrow = sgi_unit_row(u_blk + u) + 4 * g;
+  const int vrow = geglu_unit_row(u_blk + u) + 4 * g;
   __builtin_amdgcn_sched_barrier(0);
   const floatx4 bias_v = *reinterpret_cast<const floatx4*>(a.bias + vrow);
   const floatx4 bias_g = *reinterpret_cast<const floatx4*>(a.bias + vrow + 32);
@@ -164,29 +90,18 @@ __global__ __launch_bounds__(64 * SGI_NW, 1) void smgeglu_i8_kernel(SgI8Args a) 
   __builtin_amdgcn_sched_barrier(0);
 
   // fragment offset inside a piece: row r16, logical chunk g
-  const int foff = r16 * 64 + sgi_swz(g, r16) * 16;
+  const int foff = r16 * 64 + sm_i8_swz(g, r16) * 16;
   const int w_off = 2 * u * 1024;                                  // the unit's value strip; the gate strip is the next piece
-  const int x_off = (SGI_WROWS / 16 + h * TM) * 1024;              // the half's first row block
+  const int x_off = (SM_I8_WROWS / 16 + h * TM) * 1024;            // the half's first row block
 
   intx4 accv[TM], accg[TM];
 #pragma unroll
   for (int i = 0; i < TM; ++i) accv[i] = accg[i] = intx4{0, 0, 0, 0};
 
-  auto wait_stage = [&](int s) __attribute__((always_inline)) {
-    const int ahead = min(NST - 2, a.nk - 1 - s);
-    if (full) {
-      if (s <= NST - 2) sgi_wait<PPW, C::EPI, NST - 2>(ahead);
-      else sgi_wait<PPW, 0, NST - 2>(ahead);
-    } else {
-      if (s <= NST - 2) sgi_wait<PPW - 1, C::EPI, NST - 2>(ahead);
-      else sgi_wait<PPW - 1, 0, NST - 2>(ahead);
-    }
-  };
-
   int slot = 0;   // slot of stage s
   for (int s = 0; s < a.nk; ++s) {
-    wait_stage(s);
-    if (s + NST - 1 < a.nk) issue(slot == 0 ? NST - 1 : slot - 1);
+    ring.wait_stage(s, a.nk);
+    if (s + NST - 1 < a.nk) ring.issue(slot == 0 ? NST - 1 : slot - 1);
     const char* st = smem + slot * C::STAGE;
     const intx4 wv = *reinterpret_cast<const intx4*>(st + w_off + foff);
     const intx4 wg = *reinterpret_cast<const intx4*>(st + w_off + 1024 + foff);
@@ -201,40 +116,29 @@ __global__ __launch_bounds__(64 * SGI_NW, 1) void smgeglu_i8_kernel(SgI8Args a) 
     slot = slot + 1 == NST ? 0 : slot + 1;
   }
 
-  // ---- epilogue: int32 -> fp32, scale and bias (sgi_affine), then tile 13's ending: v * gelu_erf(g) in fp32, one rounding to fp16,
-  // blocks (2p, 2p + 1) paired by sm_swap16 -> 16 B of one output row per lane ----
+  // ---- epilogue: int32 -> fp32, scale and bias (sm_i8_affine), then tile 13's ending: v * gelu_erf(g) in fp32, one rounding to fp16,
+  // blocks (2p, 2p + 1) paired by sm_pack16 -> 16 B of one output row per lane ----
   const bool has_bias = a.has_bias != 0;
   const int n = (u_blk + u) * 16 + 8 * (g >> 1);
 #pragma unroll
   for (int p = 0; p < TM / 2; ++p) {
-    unsigned lo[2], hi[2];   // [block 2p | block 2p + 1] x {columns 4 g, 4 g + 1 | 4 g + 2, 4 g + 3}
+    uintx2 ho[2];   // block 2p | block 2p + 1: columns 4 g .. 4 g + 3 in fp16
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
       const int i = 2 * p + b;
-      float o[4];
+      floatx4 o;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float v = sgi_affine(accv[i][e], cs_v[e], bias_v[e], has_bias);
-        const float gt = sgi_affine(accg[i][e], cs_g[e], bias_g[e], has_bias);
+        const float v = sm_i8_affine(accv[i][e], cs_v[e], bias_v[e], has_bias);
+        const float gt = sm_i8_affine(accg[i][e], cs_g[e], bias_g[e], has_bias);
         o[e] = v * gelu_erf(gt);
       }
-      const half2v h01 = {(half_t)o[0], (half_t)o[1]};
-      const half2v h23 = {(half_t)o[2], (half_t)o[3]};
-      lo[b] = __builtin_bit_cast(unsigned, h01);
-      hi[b] = __builtin_bit_cast(unsigned, h23);
+      ho[b] = sm_round4(o);
     }
-    const half8 o8 = sm_swap16(lo[0], lo[1], hi[0], hi[1]);
+    const half8 o8 = sm_pack16(ho[0], ho[1]);
     const int m = m_blk + h * (BM / 2) + 32 * p + 16 * (g & 1) + r16;
     out_store(reinterpret_cast<half8*>(a.out + (size_t)m * a.ldo + n), o8);
   }
-}
-
-template <int BM>
-void launch_sgi(const SgI8Args& a, unsigned nwg, hipStream_t s) {
-  static DynLdsOnce once;
-  auto k = smgeglu_i8_kernel<BM>;
-  once.set(k, SgI8Cfg<BM>::LDS);
-  hipLaunchKernelGGL(k, dim3(nwg), dim3(64 * SGI_NW), SgI8Cfg<BM>::LDS, s, a);
 }
 
 }  // namespace
@@ -256,14 +160,14 @@ void launch_smgeglu_i8(const ConvDesc& d, const ConvPlan& p, hipStream_t s) {
   a.bias = d.bias ? d.bias : d.cw.scale;   // absent: the scales stand in, N floats (the loads keep their count)
   a.out = d.out;
   a.K = K;
-  a.nk = K / SGI_BK;
+  a.nk = K / SM_I8_BK;
   a.ldo = d.N / 2;
   a.has_bias = d.bias != nullptr;
-  a.order = sm_tile_order(M, d.N, K, M / bm, d.N / SGI_WROWS);   // tile 13's order, from the fp16 sizes
-  const unsigned nwg = (unsigned)(M / bm) * (d.N / SGI_WROWS);
+  a.order = sm_tile_order(M, d.N, K, M / bm, d.N / SM_I8_WROWS);   // tile 13's order, from the fp16 sizes
+  const unsigned nwg = (unsigned)(M / bm) * (d.N / SM_I8_WROWS);
   conv_plan_log(d, p, a.order.n_fast);
-  if (bm == 128) launch_sgi<128>(a, nwg, s);
-  else launch_sgi<256>(a, nwg, s);
+  if (bm == 128) sm_i8_launch<smgeglu_i8_kernel<128>>(a, nwg, SM_I8_NW, SmI8RingGeom<128>::LDS, s);
+  else sm_i8_launch<smgeglu_i8_kernel<256>>(a, nwg, SM_I8_NW, SmI8RingGeom<256>::LDS, s);
   SD_HIP(hipGetLastError());
 }
 

@@ -8,18 +8,13 @@
 //     out = fp16(((float(acc) * cs[n]) + bias[n]) + float(res[m][n]))
 // with ONE rounding to fp16: the residual meets the fp32 value.  That is the order of splitk_reduce_kernel behind a one-slab launch of
 // tile 17, so a shape both kernels take is bit-identical between tiles 17 and 19.  It is NOT tile 12's epilogue, which rounds to fp16
-// in front of the residual and again behind it.  The product and the two sums are rounded to fp32 one by one (smi_finish, compiled with
-// fp contract off): tile 17 adds its bias to a product that went through memory, so an fma here would be another function.
+// in front of the residual and again behind it.  The product and the two sums are rounded to fp32 one by one (sm_i8_affine and
+// gemm_value, fp contract off): tile 17 adds its bias to a product that went through memory, so an fma here would be another function.
 //
 // What differs from tile 12, and why:
 //   * WEIGHTS int8 [N][K] as the checkpoint holds them (weight_prep.h smgemm_i8_pack), through the LDS-DMA ring.  A wave's 16 weight
 //     rows of a K64 stage are 16 x 64 B = ONE 1-KB piece, so every wave fetches its own strip and nobody else reads it.  LDS image
-//     [16 rows][4 x 16 B], the 16-B chunk kc of row r at position kc ^ F((r >> 2) & 3), F = (0, 2, 3, 1), applied on the source address.
-//     A fragment read is lane (g, r16) -> row r16, chunk g.  A ds_read_b128 lane group ({0-3, 12-15, 20-27} / {4-11, 16-19, 28-31} of
-//     each 32-lane half) holds every row residue mod 4 four times: chunk c on row quads R = 0, 3 and chunk c ^ 1 on R = 1, 2 (or the
-//     other way round).  Their positions c ^ F(0), c ^ F(3), c ^ 1 ^ F(1), c ^ 1 ^ F(2) = c ^ (0, 1, 3, 2) and c ^ F(1), c ^ F(2),
-//     c ^ 1 ^ F(0), c ^ 1 ^ F(3) = c ^ (2, 3, 1, 0) are four different ones: 16 distinct 16-B slots of the 256-B bank row.  (The halo
-//     kernel's kc ^ ((r >> 2) & 3) serves lanes that all read the SAME chunk; here the two 16-lane rows of a group read different ones.)
+//     and fragment read: the piece of sm_i8_ring.h (sm_i8_swz), with its bank-conflict argument.
 //   * MFMA: v_mfma_i32_16x16x64_i8 - ONE instruction per 16 x 16 block and K64 stage (tile 12: two).  Operand / result layout: bit 4 of
 //     sd_selftest_mfma.  (A and B share the lane -> k map, so the sums do not depend on it; the result layout is tile 12's.)
 //   * QUANTIZATION SITE: once per activation element per workgroup, not once per wave.  All five waves consume the same BM activation
@@ -52,17 +47,16 @@
 #include "conv_plan.h"
 #include "kernels.h"
 #include "quantize8.h"
-#include "sm_tile.h"
+#include "sm_i8_ring.h"
 #include "weight_prep.h"
 
 namespace sd {
 
 namespace {
 
-constexpr int SMI_BK = 64;              // K per ring stage: 64-B weight rows, 128-B activation rows
+constexpr int SMI_BK = SM_I8_BK;        // K per ring stage: 64-B weight rows, 128-B activation rows
 constexpr int SMI_BN = 80;              // output columns per workgroup
 constexpr int SMI_NW = SMI_BN / 16;     // waves: one 16-column strip each
-constexpr int SMI_LDS = 160 * 1024;
 
 struct SmI8Args {
   const half_t* x;      // [M][K]
@@ -93,7 +87,7 @@ struct SmI8Cfg {
   static constexpr int TM = BM / 16;                             // 16 x 16 accumulator blocks per wave
   static constexpr int EPI = 2 + TM;                             // epilogue loads per lane: bias, cs, one residual quad per block
   static_assert(BM % 32 == 0 && XP * 8 == BM && PAD >= 0 && PAD < SMI_NW, "tile");
-  static_assert(NST >= 3 && LDS <= SMI_LDS, "LDS budget");
+  static_assert(NST >= 3 && LDS <= SM_I8_LDS, "LDS budget");
   static_assert(PPW * (NST - 2) + EPI <= 63, "vmcnt range");
 };
 
@@ -107,32 +101,10 @@ __device__ __forceinline__ int smi_piece(int wave, int j) {
   return wave >= 1 && wave <= 3 ? SMI_NW - 1 + wave : XP + (wave == 0 ? 0 : 1);
 }
 
-// position of the 16-B chunk kc in a 64-B row of row quad R = (row >> 2) & 3: kc ^ F(R), F = (0, 2, 3, 1)
-__device__ __forceinline__ int smi_swz(int kc, int row) { return kc ^ ((0x78 >> (2 * ((row >> 2) & 3))) & 3); }
-
-// counted wait + the LDS counter + raw barrier in one statement (no LDS access moves across)
-template <int N>
-__device__ __forceinline__ void smi_wait_barrier() {
-  asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
-}
-template <int PPW, int E, int A>
-__device__ __forceinline__ void smi_wait(int ahead) {   // (the immediate must be a literal, hence the ladder)
-  if constexpr (A > 0) {
-    if (ahead == A) {
-      smi_wait_barrier<PPW * A + E>();
-      return;
-    }
-    smi_wait<PPW, E, A - 1>(ahead);
-  } else {
-    smi_wait_barrier<E>();
-  }
-}
-
-// the epilogue's arithmetic for one element, each operation rounded on its own (hipcc contracts a * b + c into an fma by default)
-__device__ __forceinline__ float smi_finish(int acc, float cs, float bias, bool has_bias, float res, bool has_res) {
+// the epilogue's arithmetic for one element: the residual meets the fp32 value, in a rounding of its own
+__device__ __forceinline__ float gemm_value(int acc, float cs, float bias, bool has_bias, float res, bool has_res) {
 #pragma clang fp contract(off)
-  float v = (float)acc * cs;
-  if (has_bias) v = v + bias;
+  float v = sm_i8_affine(acc, cs, bias, has_bias);
   if (has_res) v = v + res;
   return v;
 }
@@ -154,7 +126,7 @@ __global__ __launch_bounds__(64 * SMI_NW, 1) void smgemm_i8_kernel(SmI8Args a) {
   const int8_t* wsrc;
   {
     const int r = lane >> 2;
-    wsrc = a.w + (size_t)(n_blk + 16 * wave + r) * a.K + smi_swz(lane & 3, r) * 16;   // logical chunk at position lane & 3 (position = chunk ^ F, so chunk = position ^ F)
+    wsrc = a.w + (size_t)(n_blk + 16 * wave + r) * a.K + sm_i8_swz(lane & 3, r) * 16;   // logical chunk at position lane & 3 (position = chunk ^ F, so chunk = position ^ F)
   }
   const half_t* xsrc[XPW];
   int qoff[XPW];   // where this lane's 8 quantized bytes of piece j go in an image
@@ -164,7 +136,7 @@ __global__ __launch_bounds__(64 * SMI_NW, 1) void smgemm_i8_kernel(SmI8Args a) {
     const int pr = p >= XP ? p - XP : p;                  // the padding pieces repeat activation rows
     const int r = pr * 8 + (lane >> 3), c8 = lane & 7;    // activation row of the tile, its 8 channels 8 c8 ..
     xsrc[j] = a.x + (size_t)(m_blk + r) * a.K + c8 * 8;
-    qoff[j] = r * 64 + smi_swz(c8 >> 1, r) * 16 + (c8 & 1) * 8;
+    qoff[j] = r * 64 + sm_i8_swz(c8 >> 1, r) * 16 + (c8 & 1) * 8;
   }
   // ring stage idx (< nk) into slot idx % NST
   auto issue = [&](int idx) __attribute__((always_inline)) {
@@ -212,20 +184,20 @@ __global__ __launch_bounds__(64 * SMI_NW, 1) void smgemm_i8_kernel(SmI8Args a) {
   __builtin_amdgcn_sched_barrier(0);
 
   // fragment offset inside a weight strip and inside a 16-row block of an image: row r16, logical chunk g
-  const int foff = r16 * 64 + smi_swz(g, r16) * 16;
+  const int foff = r16 * 64 + sm_i8_swz(g, r16) * 16;
 
   intx4 acc[TM];
 #pragma unroll
   for (int i = 0; i < TM; ++i) acc[i] = intx4{0, 0, 0, 0};
 
   // stage 0 has landed for this wave -> image 0 (the barrier of this wait is not needed, and harmless)
-  smi_wait<PPW, C::EPI, NST - 2>(min(NST - 2, a.nk - 1));
+  sm_wait<PPW, C::EPI, NST - 2, true>(min(NST - 2, a.nk - 1));
   quantize(0);
 
   for (int s = 0; s < a.nk; ++s) {
     const int ahead = max(0, min(NST - 3, a.nk - 2 - s));
-    if (s <= NST - 3) smi_wait<PPW, C::EPI, NST - 3>(ahead);
-    else smi_wait<PPW, 0, NST - 3>(ahead);
+    if (s <= NST - 3) sm_wait<PPW, C::EPI, NST - 3, true>(ahead);
+    else sm_wait<PPW, 0, NST - 3, true>(ahead);
     if (s + NST - 1 < a.nk) issue(s + NST - 1);
     const char* st = smem + (s % NST) * C::STAGE + wave * 1024;
     const char* img = smem + C::IMAGES + (s & 1) * C::IMG;
@@ -239,34 +211,23 @@ __global__ __launch_bounds__(64 * SMI_NW, 1) void smgemm_i8_kernel(SmI8Args a) {
       acc[i] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wf, xf[i], acc[i], 0, 0, 0);
   }
 
-  // ---- epilogue: one conversion, one product, bias and residual in fp32, ONE rounding; blocks (2p, 2p + 1) paired by sm_swap16 ->
+  // ---- epilogue: one conversion, one product, bias and residual in fp32, ONE rounding; blocks (2p, 2p + 1) paired by sm_pack16 ->
   // 16 B of one output row per lane ----
   const int n = n_blk + 16 * wave + 8 * (g >> 1);
 #pragma unroll
   for (int p = 0; p < TM / 2; ++p) {
-    unsigned lo[2], hi[2];   // [block 2p | block 2p + 1] x {columns 4 g, 4 g + 1 | 4 g + 2, 4 g + 3}
+    uintx2 h[2];   // block 2p | block 2p + 1: columns 4 g .. 4 g + 3 in fp16
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
-      float v[4];
+      floatx4 v;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = smi_finish(acc[2 * p + b][e], cs4[e], bias4[e], a.has_bias != 0, (float)resv[2 * p + b][e], a.has_res != 0);
-      const half2v h01 = {(half_t)v[0], (half_t)v[1]};
-      const half2v h23 = {(half_t)v[2], (half_t)v[3]};
-      lo[b] = __builtin_bit_cast(unsigned, h01);
-      hi[b] = __builtin_bit_cast(unsigned, h23);
+      for (int e = 0; e < 4; ++e) v[e] = gemm_value(acc[2 * p + b][e], cs4[e], bias4[e], a.has_bias != 0, (float)resv[2 * p + b][e], a.has_res != 0);
+      h[b] = sm_round4(v);
     }
-    const half8 o = sm_swap16(lo[0], lo[1], hi[0], hi[1]);
+    const half8 o = sm_pack16(h[0], h[1]);
     const int m = m_blk + 32 * p + 16 * (g & 1) + r16;
     out_store(reinterpret_cast<half8*>(a.out + (size_t)m * a.N + n), o);
   }
-}
-
-template <int BM>
-void launch_smi(const SmI8Args& a, hipStream_t s) {
-  static DynLdsOnce once;
-  auto k = smgemm_i8_kernel<BM>;
-  once.set(k, (size_t)SmI8Cfg<BM>::LDS);
-  hipLaunchKernelGGL(k, dim3(8 * a.order.per_xcd), dim3(64 * SMI_NW), SmI8Cfg<BM>::LDS, s, a);   // one workgroup per tile: 8 XCD runs
 }
 
 }  // namespace
@@ -296,8 +257,9 @@ void launch_smgemm_i8(const ConvDesc& d, const ConvPlan& p, hipStream_t s) {
   a.has_res = d.res != nullptr;
   a.order = sm_tile_order(M, d.N, K, M / bm, d.N / SMI_BN);   // tile 12's order, from the fp16 sizes
   conv_plan_log(d, p, a.order.n_fast);
-  if (bm == 32) launch_smi<32>(a, s);
-  else launch_smi<64>(a, s);
+  const unsigned nwg = 8 * a.order.per_xcd;   // one workgroup per tile: 8 XCD runs
+  if (bm == 32) sm_i8_launch<smgemm_i8_kernel<32>>(a, nwg, SMI_NW, SmI8Cfg<32>::LDS, s);
+  else sm_i8_launch<smgemm_i8_kernel<64>>(a, nwg, SMI_NW, SmI8Cfg<64>::LDS, s);
   SD_HIP(hipGetLastError());
 }
 

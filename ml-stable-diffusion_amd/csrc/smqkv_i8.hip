@@ -1,19 +1,10 @@
-// W8A8 form of the self-attention q|k|v projection (plan tile 22): smqkv_i8_kernel and its launcher.  The K loop is smgeglu_i8_kernel's
-// (smgeglu_i8.hip, plan tile 20) with one change of meaning: where tile 20's wave holds the value and the gate strip of ONE 16-column
-// unit, this wave holds the strips of TWO plain 16-column units - a BM x 160-column tile, BM = 128 / 256, ten waves = 5 unit pairs x 2
-// row halves, one workgroup per tile in the XCD runs of sm_tile.h.  Stage (K64: ten 16-row weight strips + BM / 16 activation strips, every
-// strip one 1-KiB LDS-DMA piece), LDS image (sgi_swz of tile 20, restated below), piece distribution, ring depth (8 / 6 stages) and the
-// counted-wait ladder are tile 20's, so its RAW / WAR argument and its vmcnt arithmetic hold word for word:
-//     step s:  [wait: this wave's pieces of stage s have landed | lgkmcnt(0) | s_barrier]
-//              issue stage s + NST - 1 -> slot (s - 1) % NST;  read the two weight fragments and the TM activation fragments;  MFMAs
-//   * RAW: a stage is read behind the barrier that follows every wave's counted wait for its own pieces of it.
-//   * WAR: slot (s - 1) % NST held stage s - 1; every wave has its fragments of that stage in registers (the lgkmcnt(0) in front of the
-//     barrier of step s) before any wave issues into the slot behind that barrier.
-//   * counted wait of step s: issued are stages 0 .. min(s + NST - 2, nk - 1); younger than stage s are min(NST - 2, nk - 1 - s) stages
-//     of this wave's pieces and, while s <= NST - 2, the EPI = 4 epilogue loads (two bias and two scale vectors, as in tile 20).
+// W8A8 form of the self-attention q|k|v projection (plan tile 22): smqkv_i8_kernel and its launcher.  The ring is the one of sm_i8_ring.h
+// as plan tile 20 runs it, with one change of meaning: where tile 20's wave holds the value and the gate strip of ONE 16-column unit,
+// this wave holds the strips of TWO plain 16-column units - a BM x 160-column tile, BM = 128 / 256, ten waves = 5 unit pairs x 2 row
+// halves, one workgroup per tile in the XCD runs of sm_tile.h.
 // The semantics are the int8 kernels' (sd_weights_quantize_w8a8 in sd_mi355x.h): exact int32 sums over the WHOLE K (kSmI8MaxK), one
 // conversion to fp32, one product with cs[n] = fp32(s_a * s_w[n]), the bias added in fp32, the queries' q_scale - each operation
-// rounded on its own, the fp32 value pinned in front of the one rounding to fp16 (sqi_value).
+// rounded on its own, the fp32 value pinned in front of the one rounding to fp16 (qkv_value).
 //
 // WEIGHTS: the stacked matrix [Wq | Wk | Wv] (3C, C) int8 in the order of smqkv_i8_pack (weight_prep.h): 16-row strips in row order, so
 // a tile reads the ten consecutive strips 10 n_tile .. 10 n_tile + 9.  C % 160 == 0 (smqkv_i8_shape_ok): a tile lies inside q, k or v,
@@ -23,29 +14,26 @@
 // of sd_selftest_mfma: A[i = l & 15][k = 16 (l >> 4) + e], B[k][j = l & 15], D lane l register r = D[i = 4 (l >> 4) + r][j = l & 15]), so
 // the two operands may trade places, and the result then arrives transposed:
 //   * q and k tiles: A = weights, B = activations (tile 20's order) - lane (g, r16) holds output columns 4 g + r of token r16;
-//     sm_swap16 pairs two row blocks into 16 B of one out_qk row, as tile 20 stores.
+//     sm_pack16 pairs two row blocks into 16 B of one out_qk row, as tile 20 stores.
 //   * v tiles:       A = activations, B = weights - lane (g, r16) holds TOKENS 4 g + r of output column r16: four consecutive tokens of
 //     one V^T row, one 8-byte store.  S % 16 == 0 (the shape rule) keeps a 16-token block inside one sample, and vt_perm - the two
 //     middle 4-token blocks of every 16 tokens swapped (AttnDesc::vt_perm) - is a permutation of whole lane groups: g -> (0, 2, 1, 3)[g].
-// The choice is one wave-uniform branch around two instances of the same loop text.
+// The choice is one wave-uniform branch around two instances of the K loop.
 #include <type_traits>
 
 #include "conv_plan.h"
 #include "igemm_device.h"
 #include "kernels.h"
 #include "quantize8.h"
-#include "sm_tile.h"
+#include "sm_i8_ring.h"
 #include "weight_prep.h"
 
 namespace sd {
 
 namespace {
 
-constexpr int SQI_BK = 64;                  // K bytes per ring stage and row
-constexpr int SQI_PAIRS = 5;                // pairs of 16-column units side by side
-constexpr int SQI_NW = 2 * SQI_PAIRS;       // waves: unit pair x row half
-constexpr int SQI_LDS = 160 * 1024;
-static_assert(kSmQkvCols == 32 * SQI_PAIRS, "tile width of plan tile 22");
+constexpr int SQV_PAIRS = SM_I8_WROWS / 32;   // pairs of 16-column units side by side
+static_assert(kSmQkvCols == SM_I8_WROWS, "tile width of plan tile 22");
 
 struct SqI8Args {
   const int8_t* xq;     // [M][K]
@@ -60,61 +48,24 @@ struct SqI8Args {
   SmTileOrder order;
 };
 
-template <int BM>
-struct SqI8Cfg {
-  static constexpr int PIECES = (kSmQkvCols + BM) / 16;         // 1-KiB LDS-DMA pieces (16 rows x 64 B) per stage: weights, then activations
-  static constexpr int PPW = (PIECES + SQI_NW - 1) / SQI_NW;    // pieces per wave per stage: the first FULL waves; the others one less
-  static constexpr int FULL = PIECES - SQI_NW * (PPW - 1);
-  static constexpr int STAGE = PIECES * 1024;
-  static constexpr int NST = SQI_LDS / STAGE;                   // ring depth: 8 / 6
-  static constexpr int TM = BM / 32;                            // 16-row blocks per wave (one row half)
-  static constexpr int EPI = 4;                                 // epilogue loads per lane: bias and cs of the two units
-  static constexpr size_t LDS = (size_t)NST * STAGE;
-  static_assert(BM % 128 == 0 && PPW >= 2 && FULL >= 1 && FULL <= SQI_NW && TM % 2 == 0, "tile");
-  static_assert(NST >= 3 && LDS <= SQI_LDS, "ring");
-  static_assert(PPW * (NST - 2) + EPI <= 63, "vmcnt range");
-};
-
-// position of the 16-B chunk kc in a 64-B row of row quad R = (row >> 2) & 3: kc ^ F(R), F = (0, 2, 3, 1) - tile 20's image (sgi_swz)
-__device__ __forceinline__ int sqi_swz(int kc, int row) { return kc ^ ((0x78 >> (2 * ((row >> 2) & 3))) & 3); }
-
-// counted wait + the LDS counter + raw barrier in one statement (no LDS access moves across)
-template <int N>
-__device__ __forceinline__ void sqi_wait_barrier() {
-  asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
-}
-template <int PPW, int E, int A>
-__device__ __forceinline__ void sqi_wait(int ahead) {   // (the immediate must be a literal, hence the ladder)
-  if constexpr (A > 0) {
-    if (ahead == A) {
-      sqi_wait_barrier<PPW * A + E>();
-      return;
-    }
-    sqi_wait<PPW, E, A - 1>(ahead);
-  } else {
-    sqi_wait_barrier<E>();
-  }
-}
-
 // one output value in fp32: every operation rounded on its own (no fma), and the result pinned in a register so that the last product
 // and the rounding to fp16 that follows stay two instructions (hipcc otherwise fuses them into v_fma_mixlo_f16: ONE rounding)
-__device__ __forceinline__ float sqi_value(int acc, float cs, float bias, bool has_bias, float q_scale, bool q_mul) {
+__device__ __forceinline__ float qkv_value(int acc, float cs, float bias, bool has_bias, float q_scale, bool q_mul) {
 #pragma clang fp contract(off)
-  float v = (float)acc * cs;
-  if (has_bias) v = v + bias;
+  float v = sm_i8_affine(acc, cs, bias, has_bias);
   if (q_mul) v = v * q_scale;
   asm volatile("" : "+v"(v));
   return v;
 }
 
 template <int BM>
-__global__ __launch_bounds__(64 * SQI_NW, 1) void smqkv_i8_kernel(SqI8Args a) {
-  using C = SqI8Cfg<BM>;
+__global__ __launch_bounds__(64 * SM_I8_NW, 1) void smqkv_i8_kernel(SqI8Args a) {
+  using C = SmI8RingCfg<BM, 4>;   // EPI = 4: bias0, bias1, cs0, cs1 below
   constexpr int NST = C::NST, PPW = C::PPW, TM = C::TM;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-  const int u = wave % SQI_PAIRS, h = wave / SQI_PAIRS;   // unit pair, row half
+  const int u = wave % SQV_PAIRS, h = wave / SQV_PAIRS;   // unit pair, row half
 
   int m_tile, n_tile;
   sm_tile_coords(a.order, m_tile, n_tile);
@@ -128,29 +79,19 @@ __global__ __launch_bounds__(64 * SQI_NW, 1) void smqkv_i8_kernel(SqI8Args a) {
   int pdst[PPW];
 #pragma unroll
   for (int j = 0; j < PPW; ++j) {
-    int p = wave + SQI_NW * j;
+    int p = wave + SM_I8_NW * j;
     if (p >= C::PIECES) p -= C::PIECES;                   // (never issued: keeps the address in range)
     pdst[j] = p * 1024;
     const int r = lane >> 2;
-    const int chunk = sqi_swz(lane & 3, r);               // logical chunk at physical position lane & 3
+    const int chunk = sm_i8_swz(lane & 3, r);             // logical chunk at physical position lane & 3
     const int wp = kSmQkvCols / 16;                       // weight pieces: strips 10 n_tile .. 10 n_tile + 9
     src[j] = (p < wp ? a.w + ((size_t)(n_blk + 16 * p) + r) * a.K : a.xq + (size_t)(m_blk + 16 * (p - wp) + r) * a.K) + chunk * 16;
   }
-  // ring stage into slot `slot`
-  auto issue = [&](int slot) __attribute__((always_inline)) {
-    char* st = smem + slot * C::STAGE;
-#pragma unroll
-    for (int j = 0; j < PPW; ++j) {
-      if (j == PPW - 1 && !full) break;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src[j],
-                                       (__attribute__((address_space(3))) void*)(st + pdst[j]), 16, 0, 0);
-      src[j] += SQI_BK;
-    }
-  };
+  const SmI8Ring<C> ring{smem, full, src, pdst};
 
 #pragma unroll
   for (int p = 0; p < NST - 1; ++p)
-    if (p < a.nk) issue(p);
+    if (p < a.nk) ring.issue(p);
   // the epilogue operands right behind the first ring stages: bias and cs of the lane's columns in both units, four 16-B loads whatever
   // the tile (bias absent: a readable dummy, so that every launch counts the same loads).  q / k tiles: columns 4 g .. 4 g + 3 of a
   // unit; v tiles: column r16, element r16 & 3 of the aligned four that hold it.
@@ -164,7 +105,7 @@ __global__ __launch_bounds__(64 * SQI_NW, 1) void smqkv_i8_kernel(SqI8Args a) {
   __builtin_amdgcn_sched_barrier(0);
 
   // fragment offset inside a piece: row r16, logical chunk g
-  const int foff = r16 * 64 + sqi_swz(g, r16) * 16;
+  const int foff = r16 * 64 + sm_i8_swz(g, r16) * 16;
   const int w_off = 2 * u * 1024;                                  // the pair's first strip; the second is the next piece
   const int x_off = (kSmQkvCols / 16 + h * TM) * 1024;             // the half's first row block
 
@@ -172,24 +113,13 @@ __global__ __launch_bounds__(64 * SQI_NW, 1) void smqkv_i8_kernel(SqI8Args a) {
 #pragma unroll
   for (int i = 0; i < TM; ++i) acc0[i] = acc1[i] = intx4{0, 0, 0, 0};
 
-  auto wait_stage = [&](int s) __attribute__((always_inline)) {
-    const int ahead = min(NST - 2, a.nk - 1 - s);
-    if (full) {
-      if (s <= NST - 2) sqi_wait<PPW, C::EPI, NST - 2>(ahead);
-      else sqi_wait<PPW, 0, NST - 2>(ahead);
-    } else {
-      if (s <= NST - 2) sqi_wait<PPW - 1, C::EPI, NST - 2>(ahead);
-      else sqi_wait<PPW - 1, 0, NST - 2>(ahead);
-    }
-  };
-
   // the K loop; VT: the activations are operand A, the result holds tokens along the registers
   auto k_loop = [&](auto vt) __attribute__((always_inline)) {
     constexpr bool VT = decltype(vt)::value;
     int slot = 0;   // slot of stage s
     for (int s = 0; s < a.nk; ++s) {
-      wait_stage(s);
-      if (s + NST - 1 < a.nk) issue(slot == 0 ? NST - 1 : slot - 1);
+      ring.wait_stage(s, a.nk);
+      if (s + NST - 1 < a.nk) ring.issue(slot == 0 ? NST - 1 : slot - 1);
       const char* st = smem + slot * C::STAGE;
       const intx4 w0 = *reinterpret_cast<const intx4*>(st + w_off + foff);
       const intx4 w1 = *reinterpret_cast<const intx4*>(st + w_off + 1024 + foff);
@@ -228,15 +158,15 @@ __global__ __launch_bounds__(64 * SQI_NW, 1) void smqkv_i8_kernel(SqI8Args a) {
       half4 o0, o1;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        o0[e] = (half_t)sqi_value(acc0[i][e], c0, b0, has_bias, 1.f, false);
-        o1[e] = (half_t)sqi_value(acc1[i][e], c1, b1, has_bias, 1.f, false);
+        o0[e] = (half_t)qkv_value(acc0[i][e], c0, b0, has_bias, 1.f, false);
+        o1[e] = (half_t)qkv_value(acc1[i][e], c1, b1, has_bias, 1.f, false);
       }
       half_t* dst = a.out_vt + ((size_t)b * a.C + nv) * a.ldT + sp;
       *reinterpret_cast<half4*>(dst) = o0;
       *reinterpret_cast<half4*>(dst + (size_t)16 * a.ldT) = o1;
     }
   } else {
-    // ---- q | k: blocks (2p, 2p + 1) paired by sm_swap16 -> 16 B of one out_qk row per lane and unit ----
+    // ---- q | k: blocks (2p, 2p + 1) paired by sm_pack16 -> 16 B of one out_qk row per lane and unit ----
     const int ldo = 2 * a.C;
 #pragma unroll
     for (int p = 0; p < TM / 2; ++p) {
@@ -244,32 +174,21 @@ __global__ __launch_bounds__(64 * SQI_NW, 1) void smqkv_i8_kernel(SqI8Args a) {
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const floatx4 cs = j ? cs1 : cs0, bias = j ? bias1 : bias0;
-        unsigned lo[2], hi[2];   // [block 2p | block 2p + 1] x {columns 4 g, 4 g + 1 | 4 g + 2, 4 g + 3}
+        uintx2 ho[2];   // block 2p | block 2p + 1: columns 4 g .. 4 g + 3 in fp16
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
           const intx4 acc = j ? acc1[2 * p + b] : acc0[2 * p + b];
-          float o[4];
+          floatx4 o;
 #pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = sqi_value(acc[e], cs[e], bias[e], has_bias, a.q_scale, q_mul);
-          const half2v h01 = {(half_t)o[0], (half_t)o[1]};
-          const half2v h23 = {(half_t)o[2], (half_t)o[3]};
-          lo[b] = __builtin_bit_cast(unsigned, h01);
-          hi[b] = __builtin_bit_cast(unsigned, h23);
+          for (int e = 0; e < 4; ++e) o[e] = qkv_value(acc[e], cs[e], bias[e], has_bias, a.q_scale, q_mul);
+          ho[b] = sm_round4(o);
         }
-        const half8 o8 = sm_swap16(lo[0], lo[1], hi[0], hi[1]);
+        const half8 o8 = sm_pack16(ho[0], ho[1]);
         const int n = n_blk + 32 * u + 16 * j + 8 * (g >> 1);
         out_store(reinterpret_cast<half8*>(a.out_qk + (size_t)m * ldo + n), o8);
       }
     }
   }
-}
-
-template <int BM>
-void launch_sqi(const SqI8Args& a, unsigned nwg, hipStream_t s) {
-  static DynLdsOnce once;
-  auto k = smqkv_i8_kernel<BM>;
-  once.set(k, SqI8Cfg<BM>::LDS);
-  hipLaunchKernelGGL(k, dim3(nwg), dim3(64 * SQI_NW), SqI8Cfg<BM>::LDS, s, a);
 }
 
 }  // namespace
@@ -290,7 +209,7 @@ void launch_smqkv_i8(const ConvDesc& d, const ConvPlan& p, hipStream_t s) {
   a.out_qk = d.out;
   a.out_vt = d.out_t;
   a.K = K;
-  a.nk = K / SQI_BK;
+  a.nk = K / SM_I8_BK;
   a.C = d.C0;
   a.S = d.Ho * d.Wo;
   a.ldT = d.ldT;
@@ -301,8 +220,8 @@ void launch_smqkv_i8(const ConvDesc& d, const ConvPlan& p, hipStream_t s) {
   a.order = sm_tile_order(M, d.N, K, M / bm, d.N / kSmQkvCols);   // from the fp16 operand sizes, as tiles 13 / 20
   const unsigned nwg = (unsigned)(M / bm) * (d.N / kSmQkvCols);
   conv_plan_log(d, p, a.order.n_fast);
-  if (bm == 128) launch_sqi<128>(a, nwg, s);
-  else launch_sqi<256>(a, nwg, s);
+  if (bm == 128) sm_i8_launch<smqkv_i8_kernel<128>>(a, nwg, SM_I8_NW, SmI8RingGeom<128>::LDS, s);
+  else sm_i8_launch<smqkv_i8_kernel<256>>(a, nwg, SM_I8_NW, SmI8RingGeom<256>::LDS, s);
   SD_HIP(hipGetLastError());
 }
 
