@@ -104,6 +104,12 @@ int sd_weights_read_palette(const sd_weights* w, const char* name, void* lut, ui
  * 640- and 1280-channel levels, not the 8 x 8 mid block); any other marked conv (one or two of the three, three ranges, the
  * 320-channel level's one-launch head, attn2.to_q / to_k / to_v, the merged transformer tail, two-source 1x1, GEGLUs off tile 13,
  * stride 2, channel counts off the tiles) runs fp16 as before - the reference's skipped layers.
+ * The tail of a transformer block: a marked ff.net.2 whose un-merged shape is on plan tile 24's rule (4C -> C at 256 <= M <= 2048 on
+ * 192 - 256 tiles of 32 / 64 x 80: the 640- and 1280-channel levels of SD2.1-base, not the mid block, C <= 2048) is NOT merged with
+ * proj_out: it runs from int8 (smgemm_q8.hip, plan tile 24, + h2) on the GEGLU product quantized with its act_absmax - written as int8
+ * by the GEGLU itself where that runs plan tile 20 (no fp16 product exists), else by one quantizer launch over the product - and
+ * proj_out then runs as a launch of its own, from int8 (plan tile 19) where it is marked too.  An unmarked ff.net.2 keeps the merged
+ * fp16 launch, and a proj_out marked beside it stays "marked, not applied".
  * sd_weights_w8a8_info: 1 when `name` is marked (*act_scale, may be NULL, = s_a), else 0.
  * sd_weights_observe_activations(on): handles created from the store while it is on put an absmax observer in front of every conv
  * that plan tile 17 could take (on = 1) or that plan tile 17 or 18 could take (on = 2) (sd_unet_activation_ranges) - calibration on
@@ -116,13 +122,18 @@ int sd_weights_read_palette(const sd_weights* w, const char* name, void* lut, ui
  * over it, named by the projection's weight; the GEGLU itself runs folded in fp16 as without the flag, so the outputs do not change.
  * sd_weights_observe_qkv(on): a third flag of the same kind (0 / 1, effective only while the store observes) - handles created from it
  * also run, for every fused q|k|v launch plan tile 22 could take, a LayerNorm of norm1 into a scratch tensor and ONE observer over it,
- * reported under the three weight names attn1.to_q / to_k / to_v with one value; the launch itself runs folded in fp16. */
+ * reported under the three weight names attn1.to_q / to_k / to_v with one value; the launch itself runs folded in fp16.
+ * sd_weights_observe_tails(on): a fourth flag of the same kind (0 / 1, effective only while the store observes) - handles created from
+ * it also put, for every ff.net.2 plan tile 24 could take, an observer over the GEGLU product it reads, named by ff.net.2's weight, and,
+ * where that block ends its SpatialTransformer, a scratch ff.net.2 GEMM (+ residual) with an observer over its result, named by
+ * proj_out's weight; the merged tail launch itself still runs, so the outputs do not change. */
 int sd_weights_quantize_w8a8(sd_weights* w, const char* name, float act_absmax, double* sq_err);
 int sd_weights_w8a8_info(const sd_weights* w, const char* name, float* act_scale);
 int sd_weights_observe_activations(sd_weights* w, int on);
 int sd_weights_observe_gemms(sd_weights* w, int on);
 int sd_weights_observe_geglus(sd_weights* w, int on);
 int sd_weights_observe_qkv(sd_weights* w, int on);
+int sd_weights_observe_tails(sd_weights* w, int on);
 
 /* ------------------------------------------------------------------------------------------
  * UNet / ControlNet.  Config mirrors UNet2DConditionModel.__init__ (unet.py:801-833) with the
@@ -415,7 +426,7 @@ int sd_op_conv2d(const void* x, const void* w, const float* bias, const void* re
  *                 (+ SiLU with twin_silu) of the result to out_twin (B, Cout, Ho, Wo) f16 - no GroupNorm launch (the low-res
  *                 conv1 -> norm2 path); refused where the combine cannot hold whole (sample, group) slices
  *   plan_out[4]   the plan the launch ran: tile (1-4 igemm.hip, 7 conv3x3_halo.hip, 9 wstream.hip, 11 bvgemm.hip, 12 smgemm.hip; the
- *                 entries of the compressed sources report theirs: 14 / 15 / 16 palettized, 17 / 18 / 19 / 20 / 22 W8A8),
+ *                 entries of the compressed sources report theirs: 14 / 15 / 16 palettized, 17 / 18 / 19 / 20 / 22 / 24 W8A8),
  *                 staging, resolved split-K, 1 if the output left through fp32 slabs; all -1: the direct (non-MFMA) kernels
  * res / out are (B, Cout, Ho, Wo). */
 int sd_op_conv2d_ex(const void* x, const void* x1, const void* w, const float* bias, const float* temb, const void* res, void* out, int B,
@@ -516,6 +527,27 @@ int sd_op_geglu_w8a8(const int8_t* xq, const int8_t* wq, const float* w_scale, f
  * (v = 1) rows of the output's 16-column unit U, every row whole - so a tile of 80 output columns stages ten consecutive strips.  N2 a
  * multiple of 32, K of 64.  *bytes = its size (N2 * K); packed may be NULL to ask for the size alone. */
 int sd_op_w8a8_pack_geglu(const int8_t* wq, int N2, int K, int8_t* packed, size_t* bytes);
+/* No reference counterpart as operators; the pair stands for ff.net.0.proj -> ff.net.2 (unet.py:591, :609-632) under
+ * quantize_cumulative_config (activation_quantization.py:141-203), which quantizes the GEGLU product v * gelu(g) that ff.net.2 reads and
+ * ff.net.2's un-merged weight: what a handle runs for a marked ff.net.2 on plan tile 24's rule (sd_weights_quantize_w8a8).
+ * sd_op_geglu_w8a8_q8 (plan tile 20 with an int8 output): sd_op_geglu_w8a8's arguments and checks, and out_absmax, the range of the
+ * PRODUCT -> out_q (M, N2 / 2) int8 = clip(rint(fp32(y) * (127 / out_absmax)), -127, 127), y the fp16 value sd_op_geglu_w8a8 stores for
+ * that element - the quantizer of sd_op_layernorm_q8 in plain form over that launch's output, bit for bit, with no fp16 tensor in
+ * between.  plan_out = {20, 1 | 2, 1, 0}.  The device output starts as -128 in front of a guard: SD_ERR_INTERNAL when the guard was
+ * written.  Checked in sd_op_geglu_w8a8's order, out_absmax (not a positive finite number) beside act_absmax in (5).
+ * sd_op_gemm_q8 (plan tile 24, smgemm_q8.hip): xq (M, K) int8 token-major, wq (N, K) int8, w_scale (N) f32, act_absmax the range xq was
+ * quantized with; bias (N) f32 / res (M, N) f16 token-major may be NULL -> out (M, N) f16 token-major
+ *   = fp16(((float(int32 sum over K) * fp32(fp32(act_absmax / 127) * w_scale[n])) + bias[n]) + float(res[m][n])), one rounding:
+ * sd_op_gemm_w8a8 behind its quantizer, the same function wherever that entry's x quantizes to xq.  bm = tile height 32 / 64, 0 = by M
+ * as plan tile 12; iters, ms as sd_op_conv2d_ex.  plan_out = {24, 1 | 2 (bm 32 | 64), 1, 0}.  The device output starts as NaN patterns
+ * in front of a guard: SD_ERR_INTERNAL when the guard was written.  Checked on the host in this order, before any device work, each
+ * SD_ERR_INVALID_ARGUMENT: (1) bm not 0 / 32 / 64; (2) NULL arguments or an empty problem; (3) a shape plan tile 12 does not tile (K a
+ * multiple of 64, N of 80, M of the tile height, at least 2 x 2 tiles and a multiple of 8 of them); (4) K > 133120 (the int32 sums must
+ * stay exact); (5) act_absmax not a positive finite number; (6) a w_scale that is not; (7) a weight of -128; (8) an activation of -128. */
+int sd_op_geglu_w8a8_q8(const int8_t* xq, const int8_t* wq, const float* w_scale, float act_absmax, const float* bias, float out_absmax,
+                        int8_t* out_q, int M, int C, int N2, int bm, int* plan_out, int iters, float* ms);
+int sd_op_gemm_q8(const int8_t* xq, const int8_t* wq, const float* w_scale, float act_absmax, const float* bias, const void* res, void* out,
+                  int M, int K, int N, int bm, int* plan_out, int iters, float* ms);
 /* No reference counterpart as an operator; behind sd_op_layernorm_q8 it stands for norm1 -> attn1.to_q / to_k / to_v (unet.py:583-586 ->
  * :74-84) under quantize_cumulative_config (activation_quantization.py:141-203), which quantizes the OUTPUT of the LayerNorm and the
  * three un-folded weights.  sd_op_qkv_w8a8 (plan tile 22, smqkv_i8.hip): xq (B * HW, C) int8 token-major, wq (3C, C) int8 =
@@ -706,14 +738,17 @@ int sd_op_sched_step(const float* noise_pred, float* latents, float* hist, const
  * descriptor of the fused q|k|v projection (N = 3 C0, n_trans = 2 C0, no flags) - the answer is 22 with the resolved tile height of
  * the same staging (1 / 2 = 128 / 256 rows, 0 = by the grid), split-K 1, no slab, no workspace, or SD_ERR_INVALID_ARGUMENT naming plan
  * tile 22 for a shape off its rule (sd_op_qkv_w8a8); it has no fp16 twin: a handle takes 22 for every fused q|k|v launch on the rule
- * whose three tensors carry W8A8 marks with one range),
+ * whose three tensors carry W8A8 marks with one range; tile = 24 asks for a W8A8 descriptor of the small-M 1x1 GEMM whose activations
+ * arrive as int8 - the answer is 24 with the resolved tile height of the same staging (1 / 2 = 32 / 64 rows), split-K 1, no slab, no
+ * workspace, or SD_ERR_INVALID_ARGUMENT naming plan tile 24 for a shape it does not take: tile 19's shapes (sd_op_gemm_q8); a handle
+ * takes it for a marked ff.net.2 on the rule stated at sd_weights_quantize_w8a8; 23 is not in use),
  * staging, resolved split-K, slab (0 / 1), then the copies a handle must hold for this conv: wstream, wsgemm, bvgemm (0 / 1 each).
  * *workspace_bytes: the slab workspace this launch needs. */
 int sd_op_conv_plan(int ksize, int stride, int up, int C0, int C1, int N, int B, int Ho, int Wo, int out_mode, int flags, int n_trans,
                     int n_twins, int gnf_groups, int tile, int staging, int splitk, int copies, int* plan, unsigned long long* workspace_bytes);
 /* No reference counterpart.  The same question with the same 18 descriptor arguments, answered with the kernel that launches: one
  * NUL-terminated line in text[text_bytes] (64 bytes hold every answer) in the format of csrc/conv_plan.h conv_plan_kernel_name, e.g.
- * "igemm 64x64 ring4 kg2", "gemm_pipe 128x64 ring3", "halo_ks ring6", "halo_i8 ring4", "wstream waves8", "bvgemm v3", "smgemm bm32", "smgemm_i8 bm32", "generic":
+ * "igemm 64x64 ring4 kg2", "gemm_pipe 128x64 ring3", "halo_ks ring6", "halo_i8 ring4", "wstream waves8", "bvgemm v3", "smgemm bm32", "smgemm_i8 bm32", "smgemm_q8 bm32", "generic":
  * kernel family, tile, the ring depth that runs after the fall-back to one that fits the LDS, in-workgroup K groups, register
  * staging, wave count, variant - what the (tile, staging) codes of sd_op_conv_plan mean for this descriptor.  Host only. */
 int sd_op_conv_plan_kernel(int ksize, int stride, int up, int C0, int C1, int N, int B, int Ho, int Wo, int out_mode, int flags, int n_trans,

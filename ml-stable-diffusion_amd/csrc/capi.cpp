@@ -167,6 +167,13 @@ int sd_weights_observe_qkv(sd_weights* w, int on) {
     w->store.set_observe_qkv(on != 0);
   });
 }
+int sd_weights_observe_tails(sd_weights* w, int on) {
+  return guarded([&] {
+    SD_REQUIRE(w, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(on == 0 || on == 1, kInvalidArgument, "sd_weights_observe_tails: %d (0 off, 1 on)", on);
+    w->store.set_observe_tails(on != 0);
+  });
+}
 void sd_weights_destroy(sd_weights* w) { delete w; }
 
 int sd_unet_create(const sd_unet_config* cfg, const sd_weights* w, int device, sd_unet** out) {

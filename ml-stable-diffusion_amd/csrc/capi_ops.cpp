@@ -731,13 +731,14 @@ int sd_op_layernorm_q8(const void* x, const float* ln_weight, const float* ln_bi
   });
 }
 
-// The GEGLU projection in W8A8 (plan tile 20).  Every check runs on the host in front of the first device call (Scratch), in the order
-// the header lists them.  The bias goes up interleaved as the UNet builder uploads it (upload_vec(..., geglu)).
-int sd_op_geglu_w8a8(const int8_t* xq, const int8_t* wq, const float* w_scale, float act_absmax, const float* bias, void* out, int M, int C,
-                     int N2, int bm, int* plan_out, int iters, float* ms) {
+// The GEGLU projection in W8A8 (plan tile 20): the body of sd_op_geglu_w8a8 (out) and sd_op_geglu_w8a8_q8 (out_q: the product leaves as
+// int8 by out_absmax).  Every check runs on the host in front of the first device call (Scratch), in the order the header lists them.
+// The bias goes up interleaved as the UNet builder uploads it (upload_vec(..., geglu)).
+static int geglu_w8a8_op(const int8_t* xq, const int8_t* wq, const float* w_scale, float act_absmax, const float* bias, void* out, float out_absmax,
+                         int8_t* out_q, bool q8, int M, int C, int N2, int bm, int* plan_out, int iters, float* ms) {
   return guarded([&] {
     SD_REQUIRE(bm == 0 || bm == 128 || bm == 256, kInvalidArgument, "geglu_w8a8: bm = %d, not 0, 128 or 256", bm);
-    SD_REQUIRE(xq && wq && w_scale && out && plan_out, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(xq && wq && w_scale && (q8 ? out_q != nullptr : out != nullptr) && plan_out, kInvalidArgument, "NULL argument");
     SD_REQUIRE(M > 0 && C > 0 && N2 > 0, kInvalidArgument, "geglu_w8a8: empty problem");
     ConvDesc d = token_gemm(nullptr, C, nullptr, nullptr, nullptr, nullptr, 1, M, N2);
     d.out_mode = kOutGeglu;
@@ -746,7 +747,14 @@ int sd_op_geglu_w8a8(const int8_t* xq, const int8_t* wq, const float* w_scale, f
                "geglu_w8a8: shape not eligible for plan tile 20 (smgeglu_i8.hip: M=%d C=%d N2=%d bm=%d - C a multiple of 64, N2 of 160, M of the "
                "tile height, at least 2 x 2 tiles and a multiple of 8 of them)", M, C, N2, bm);
     SD_REQUIRE(smgeglu_i8_shape_ok(d, code), kInvalidArgument, "geglu_w8a8: K = %d, the exact int32 sums of plan tile 20 hold up to %d", C, kSmI8MaxK);
-    // act_absmax, then w_scale, then the weight values (-128 is outside the symmetric range), then the activations
+    // act_absmax (and out_absmax), then w_scale, then the weight values (-128 is outside the symmetric range), then the activations
+    SD_REQUIRE(w8a8_absmax_ok(act_absmax), kInvalidArgument, "geglu_w8a8: act_absmax = %g, not a positive finite number", (double)act_absmax);
+    float out_inv_s = 0.f;
+    if (q8) {
+      SD_REQUIRE(w8a8_absmax_ok(out_absmax), kInvalidArgument, "geglu_w8a8: out_absmax = %g, not a positive finite number", (double)out_absmax);
+      out_inv_s = 1.0f / (out_absmax / 127.0f);   // (as w8a8_host_copy computes the factor the consumer's activations were quantized by)
+      SD_REQUIRE(std::isfinite(out_inv_s) && out_inv_s > 0.f, kInvalidArgument, "geglu_w8a8: out_absmax = %g has no finite inverse scale", (double)out_absmax);
+    }
     (void)w8a8_host_copy("geglu_w8a8", wq, w_scale, act_absmax, N2, C, 1, WeightSource::I8Geglu);
     for (size_t i = 0; i < (size_t)M * C; ++i)
       SD_REQUIRE(xq[i] != -128, kInvalidArgument, "geglu_w8a8: activation value -128 at element %zu, the symmetric range is [-127, 127]", i);
@@ -757,8 +765,19 @@ int sd_op_geglu_w8a8(const int8_t* xq, const int8_t* wq, const float* w_scale, f
       for (int o = 0; o < N2; ++o) bi[geglu_row(o, N2)] = bias[o];
       d.bias = sc.dev<float>(N2, bi.data());
     }
-    half_t* dout = sc.dev<half_t>((size_t)M * (N2 / 2));
-    d.out = dout;
+    const size_t n_out = (size_t)M * (N2 / 2);
+    half_t* dout = nullptr;
+    int8_t* dq = nullptr;
+    if (q8) {   // -128 in front of a guard of 0xff: an element the launch skipped reads back as a value the quantizer never writes
+      dq = guarded_buf<int8_t>(sc, n_out, kOpGuard);
+      SD_HIP(hipMemset(dq, 0x80, n_out));
+      SD_HIP(hipStreamSynchronize(nullptr));
+      d.out_q8 = dq;
+      d.out_inv_s = out_inv_s;
+    } else {
+      dout = sc.dev<half_t>(n_out);
+      d.out = dout;
+    }
     HostWeights h;
     h.kind = WeightSource::I8Geglu; h.q = wq; h.w_scale = w_scale; h.act_absmax = act_absmax;
     upload_compressed(sc, d, "geglu_w8a8", h, bm);
@@ -766,7 +785,59 @@ int sd_op_geglu_w8a8(const int8_t* xq, const int8_t* wq, const float* w_scale, f
     plan_out[0] = p.tile; plan_out[1] = p.staging; plan_out[2] = p.splitk; plan_out[3] = p.slab ? 1 : 0;
     ConvWorkspace ws;
     sc.timed(iters, ms, [&] { launch_conv(d, ws, sc.stream); });
-    SD_HIP(hipMemcpy(out, dout, (size_t)M * (N2 / 2) * 2, hipMemcpyDeviceToHost));
+    if (q8) {
+      check_guard(sc, dq, n_out, kOpGuard, "geglu_w8a8_q8");
+      SD_HIP(hipMemcpy(out_q, dq, n_out, hipMemcpyDeviceToHost));
+    } else {
+      SD_HIP(hipMemcpy(out, dout, n_out * 2, hipMemcpyDeviceToHost));
+    }
+  });
+}
+
+int sd_op_geglu_w8a8(const int8_t* xq, const int8_t* wq, const float* w_scale, float act_absmax, const float* bias, void* out, int M, int C,
+                     int N2, int bm, int* plan_out, int iters, float* ms) {
+  return geglu_w8a8_op(xq, wq, w_scale, act_absmax, bias, out, 0.f, nullptr, false, M, C, N2, bm, plan_out, iters, ms);
+}
+
+int sd_op_geglu_w8a8_q8(const int8_t* xq, const int8_t* wq, const float* w_scale, float act_absmax, const float* bias, float out_absmax,
+                        int8_t* out_q, int M, int C, int N2, int bm, int* plan_out, int iters, float* ms) {
+  return geglu_w8a8_op(xq, wq, w_scale, act_absmax, bias, nullptr, out_absmax, out_q, true, M, C, N2, bm, plan_out, iters, ms);
+}
+
+// The small-M 1x1 GEMM from int8 weights and int8 activations (plan tile 24), token-major.  Every check runs on the host in front of the
+// first device call (Scratch), in the order the header lists them.
+int sd_op_gemm_q8(const int8_t* xq, const int8_t* wq, const float* w_scale, float act_absmax, const float* bias, const void* res, void* out,
+                  int M, int K, int N, int bm, int* plan_out, int iters, float* ms) {
+  return guarded([&] {
+    SD_REQUIRE(bm == 0 || bm == 32 || bm == 64, kInvalidArgument, "gemm_q8: bm = %d, not 0, 32 or 64", bm);
+    SD_REQUIRE(xq && wq && w_scale && out && plan_out, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(M > 0 && K > 0 && N > 0, kInvalidArgument, "gemm_q8: empty problem");
+    ConvDesc d = token_gemm(nullptr, K, nullptr, nullptr, nullptr, nullptr, 1, M, N);
+    const int code = conv_plan_pin(WeightSource::I8GemmQ, bm).staging;
+    SD_REQUIRE(conv_fast_path_ok(d) && smgemm_shape_ok(d, code), kInvalidArgument,
+               "gemm_q8: shape not eligible for plan tile 24 (smgemm_q8.hip: M=%d K=%d N=%d bm=%d - K a multiple of 64, N of 80, M of the tile height, "
+               "at least 2 x 2 tiles and a multiple of 8 of them)", M, K, N, bm);
+    SD_REQUIRE(smgemm_q8_shape_ok(d, code), kInvalidArgument, "gemm_q8: K = %d, the exact int32 sums of plan tile 24 hold up to %d", K, kSmI8MaxK);
+    // act_absmax, then w_scale, then the weight values (-128 is outside the symmetric range), then the activations
+    (void)w8a8_host_copy("gemm_q8", wq, w_scale, act_absmax, N, K, 1, WeightSource::I8GemmQ);
+    for (size_t i = 0; i < (size_t)M * K; ++i)
+      SD_REQUIRE(xq[i] != -128, kInvalidArgument, "gemm_q8: activation value -128 at element %zu, the symmetric range is [-127, 127]", i);
+    Scratch sc;
+    d.x0_i8 = sc.dev<int8_t>((size_t)M * K, xq);
+    d.bias = bias ? sc.dev<float>(N, bias) : nullptr;
+    if (res) d.res = sc.dev<half_t>((size_t)M * N, f16(res));
+    const size_t n_out = (size_t)M * N;
+    half_t* dout = guarded_buf<half_t>(sc, n_out, kOpGuard);
+    d.out = dout;
+    HostWeights h;
+    h.kind = WeightSource::I8GemmQ; h.q = wq; h.w_scale = w_scale; h.act_absmax = act_absmax;
+    upload_compressed(sc, d, "gemm_q8", h, bm);
+    const ConvPlan p = conv_plan(d);
+    plan_out[0] = p.tile; plan_out[1] = p.staging; plan_out[2] = p.splitk; plan_out[3] = p.slab ? 1 : 0;
+    ConvWorkspace ws;
+    sc.timed(iters, ms, [&] { launch_conv(d, ws, sc.stream); });
+    check_guard(sc, dout, n_out, kOpGuard, "gemm_q8");
+    SD_HIP(hipMemcpy(out, dout, n_out * 2, hipMemcpyDeviceToHost));
   });
 }
 
@@ -1584,6 +1655,13 @@ static ConvPlan query_conv_plan(int ksize, int stride, int up, int C0, int C1, i
   if (tile == 20) {   // ... and one of the int8 GEGLU projection, whose activations arrive as int8 too
     d.w = nullptr;
     d.cw.kind = WeightSource::I8Geglu;
+    d.cw.stream = d.cw.scale = present;
+    d.cw.inv_s = 1.f;
+    d.x0_i8 = reinterpret_cast<const int8_t*>(present);
+  }
+  if (tile == 24) {   // ... and one of the int8 small-M GEMM whose activations arrive as int8
+    d.w = nullptr;
+    d.cw.kind = WeightSource::I8GemmQ;
     d.cw.stream = d.cw.scale = present;
     d.cw.inv_s = 1.f;
     d.x0_i8 = reinterpret_cast<const int8_t*>(present);

@@ -70,6 +70,8 @@ bool i8_gemm(const ConvDesc& d) { return d.cw.kind == WeightSource::I8Gemm; }
 bool i8_geglu(const ConvDesc& d) { return d.cw.kind == WeightSource::I8Geglu; }
 // plan tile 22: the fused q|k|v projection from int8 weights and int8 activations
 bool i8_qkv(const ConvDesc& d) { return d.cw.kind == WeightSource::I8Qkv; }
+// plan tile 24: the small-M 1x1 GEMM from int8 weights and int8 activations
+bool i8_gemm_q(const ConvDesc& d) { return d.cw.kind == WeightSource::I8GemmQ; }
 // tiles 9 / 14 / 17: the code's wave count (decode_plan)
 int wstream_waves(int code) { return code == 4 ? 4 : 8; }
 // fp32 slabs of a launch: one per split, one when only `slab` (weight stream, GroupNorm twins) asks for the slab path
@@ -340,6 +342,14 @@ bool smqkv_i8_tiles(const ConvDesc& d, int variant) {
   return M % bm == 0 && mt >= 2 && (mt * nt) % 8 == 0 && mt * nt <= 65535;
 }
 
+// plan tile 24 in a handle (the rule: conv_plan.h)
+bool smgemm_q8_wanted(const ConvDesc& d) {
+  if (!smgemm_q8_shape_ok(d, 0) || d.gn_partial) return false;
+  const long M = (long)d.B * d.Ho * d.Wo;
+  const long tiles = M / smgemm_bm(d, 0) * (d.N / 80);
+  return M >= 256 && M <= 2048 && tiles >= 192 && tiles <= 256;
+}
+
 namespace {
 
 // resolved split-K of plan tile 21: tile 7's rule (workgroups for every CU, a split keeps >= 2 chunks) over its grid of
@@ -381,6 +391,11 @@ ConvPlan plan_codes(const ConvDesc& d) {
                "plan tile 22 (smqkv_i8.hip, int8) needs the int8 weights, the scales and an un-folded q|k|v shape of its tiles with K <= %d "
                "(k=%d C0=%d C1=%d N=%d n_trans=%d M=%d S=%d mode=%d ln=%d%s)", kSmI8MaxK, d.ksize, d.C0, d.x1 ? d.C1 : 0, d.N, d.n_trans,
                d.B * d.Ho * d.Wo, d.Ho * d.Wo, d.out_mode, d.ln_colsum ? 1 : 0, switches().qkv_i8 ? "" : "; SD_QKV_I8=0");
+  // (nor has an int8 GEMM descriptor whose activations arrive quantized: tile 24 takes it or nobody does)
+  if (i8_gemm_q(d))
+    SD_REQUIRE(conv_fast_path_ok(d) && cw.stream && cw.scale && d.staging >= 0 && d.staging <= 2 && smgemm_q8_shape_ok(d, d.staging), kInvalidArgument,
+               "plan tile 24 (smgemm_q8.hip, int8) needs the int8 weights, the scales and a single-source shape of the small-M GEMM with K <= %d "
+               "(k=%d C0=%d C1=%d N=%d M=%d mode=%d)", kSmI8MaxK, d.ksize, d.C0, d.x1 ? d.C1 : 0, d.N, d.B * d.Ho * d.Wo, d.out_mode);
   // the sub-pixel upsampler holds the folded matrix and nothing else: tile 21 takes it or nobody does (no table row, no tuner candidate)
   if (d.subpix) {
     SD_REQUIRE(conv_fast_path_ok(d) && halo_sp_ok(d) && (d.tile == 0 || d.tile == 21), kInvalidArgument,
@@ -434,6 +449,8 @@ ConvPlan plan_codes(const ConvDesc& d) {
       return ConvPlan{20, smgeglu_bm(d, d.staging) == 128 ? 1 : 2, 1, false, 0};
     case WeightSource::I8Qkv:   // the tile height's code in (0 = by the grid), the resolved one out; no split-K, no slab, no workspace (checked above)
       return ConvPlan{22, smqkv_i8_bm(d, d.staging) == 128 ? 1 : 2, 1, false, 0};
+    case WeightSource::I8GemmQ:   // as I8Gemm
+      return ConvPlan{24, smgemm_bm(d, d.staging) == 32 ? 1 : 2, 1, false, 0};
   }
   const Switches& sw = switches();
   // the library's own rules for tiles 10-13 apply where nothing else was asked for (a tuner candidate in force also keeps them off)
@@ -492,7 +509,7 @@ ConvPlan plan_codes(const ConvDesc& d) {
 //   tile 18:   tile 7's codes; the int8 kernel has rings of 2 / 3 / 4 stages, a deeper code runs the 4-stage one
 //   tile 21:   tile 7's codes; the sub-pixel kernel has rings of 3 / 4 stages: 2 = 3 stages, anything else 4
 //   tiles 9 / 14 / 17: 4 = four waves per workgroup, anything else eight      tile 11: 1-6 = the variant, anything else the library's choice
-//   tiles 12 / 15 / 19 / 13 / 16 / 20 / 22: 1 / 2 = the lower / higher tile (32 / 64, 128 / 256 rows), 0 = by the shape
+//   tiles 12 / 15 / 19 / 24 / 13 / 16 / 20 / 22: 1 / 2 = the lower / higher tile (32 / 64, 128 / 256 rows), 0 = by the shape
 void decode_plan(const ConvDesc& d, ConvPlan& p) {
   const Dims a = dims_of(d);
   int code = p.staging;
@@ -507,8 +524,8 @@ void decode_plan(const ConvDesc& d, ConvPlan& p) {
       p.kernel = ConvKernel::Bvgemm;
       p.variant = code >= 1 && code <= 6 ? code : bvgemm_auto_variant(d);
       return;
-    case 12: case 15: case 19:
-      p.kernel = p.tile == 12 ? ConvKernel::Smgemm : p.tile == 15 ? ConvKernel::SmgemmPal : ConvKernel::SmgemmI8;
+    case 12: case 15: case 19: case 24:
+      p.kernel = p.tile == 12 ? ConvKernel::Smgemm : p.tile == 15 ? ConvKernel::SmgemmPal : p.tile == 19 ? ConvKernel::SmgemmI8 : ConvKernel::SmgemmQ8;
       p.bm = code >= 0 && code <= 2 ? smgemm_bm(d, code) : 0;   // (0: no such tile - the launcher refuses it)
       return;
     case 13: case 16: case 20:
@@ -599,6 +616,7 @@ std::string conv_plan_kernel_name(const ConvPlan& p) {
     case ConvKernel::Smgemm: return "smgemm bm" + std::to_string(p.bm);
     case ConvKernel::SmgemmPal: return "smgemm_pal bm" + std::to_string(p.bm);
     case ConvKernel::SmgemmI8: return "smgemm_i8 bm" + std::to_string(p.bm);
+    case ConvKernel::SmgemmQ8: return "smgemm_q8 bm" + std::to_string(p.bm);
     case ConvKernel::Smgeglu: return "smgeglu bm" + std::to_string(p.bm);
     case ConvKernel::SmgegluPal: return "smgeglu_pal bm" + std::to_string(p.bm);
     case ConvKernel::SmgegluI8: return "smgeglu_i8 bm" + std::to_string(p.bm);
@@ -614,7 +632,7 @@ std::string conv_plan_kernel_name(const ConvPlan& p) {
 //   - with the weight-stream copy present, its slab count at four waves per workgroup (the most slabs it writes);
 //   - the unresolved split-K (the launch may use fewer splits), one slab when only the GroupNorm twins ask for it.
 size_t conv_workspace_bytes(const ConvDesc& d) {
-  if (!conv_fast_path_ok(d) || pal_gemm(d) || pal_geglu(d) || i8_gemm(d) || i8_geglu(d) || i8_qkv(d)) return 0;   // (tiles 15 / 16 / 19 / 20 / 22: no slabs)
+  if (!conv_fast_path_ok(d) || pal_gemm(d) || pal_geglu(d) || i8_gemm(d) || i8_geglu(d) || i8_qkv(d) || i8_gemm_q(d)) return 0;   // (tiles 15 / 16 / 19 / 20 / 22 / 24: no slabs)
   const Dims a = dims_of(d);
   if (d.subpix) return halo_sp_ok(d) ? slab_bytes(a, subpix_splits(d, a), false) : 0;   // (tile 21: pinned, no candidate or table row moves its split)
   const Plan p = choose_plan(d, a);
@@ -665,6 +683,7 @@ WeightPin conv_plan_pin(WeightSource kind, int n) {
     case WeightSource::PalGeglu: return {kind, 16, n == 128 ? 1 : n == 256 ? 2 : 0};
     case WeightSource::I8Geglu: return {kind, 20, n == 128 ? 1 : n == 256 ? 2 : 0};
     case WeightSource::I8Qkv: return {kind, 22, n == 128 ? 1 : n == 256 ? 2 : 0};
+    case WeightSource::I8GemmQ: return {kind, 24, n == 32 ? 1 : n == 64 ? 2 : 0};
     default: return {};
   }
 }
@@ -686,6 +705,12 @@ WeightPin conv_plan_weights(const ConvDesc& d, StoredWeights held, bool opt_in) 
     ConvDesc plain = d;
     plain.ln_colsum = nullptr;
     if (p.kernel == ConvKernel::Smgeglu && smgeglu_i8_shape_ok(plain, p.bm == 128 ? 1 : 2)) return conv_plan_pin(WeightSource::I8Geglu, p.bm);
+  }
+  // a plain projection whose producer hands it int8 activations (d.x0_i8: ff.net.2 behind the GEGLU), for the int8 kernel that streams
+  // them: no fp16 twin to follow either - the rule of smgemm_q8_wanted alone, behind the switch that takes tile 12 away
+  if (opt_in && held == StoredWeights::W8A8 && d.ksize == 1 && !d.x1 && d.out_mode == kOutHalf && d.n_trans == 0 && d.x0_i8) {
+    if (sw.smgemm && !d.ln_colsum && smgemm_q8_wanted(d)) return conv_plan_pin(WeightSource::I8GemmQ, smgemm_bm(d, 0));
+    return {};
   }
   // the fused q|k|v launch (V columns transposed), for the int8 kernel that reads norm1's int8 output: no fp16 twin to follow - the
   // shape rule alone, asked of the descriptor without the fold's fields, at the height the grid gives
@@ -766,7 +791,7 @@ void conv_plan_log(const ConvDesc& d, const ConvPlan& p, int n_fast) {
   else if (p.tile == 15 || p.tile == 16)
     fprintf(stderr, "[sd conv] k1 s1 up1 C0=%d C1=%d M=%d N=%d K=%d mode=%d tile=%d bm=%d n_fast=%d bits=%d\n", d.C0, c1, a.M, a.N, a.K, d.out_mode,
             p.tile, p.bm, n_fast, d.cw.bits);
-  else if (p.tile == 19 || p.tile == 20 || p.tile == 22)
+  else if (p.tile == 19 || p.tile == 20 || p.tile == 22 || p.tile == 24)
     fprintf(stderr, "[sd conv] k1 s1 up1 C0=%d C1=%d M=%d N=%d K=%d mode=%d tile=%d bm=%d n_fast=%d bits=8\n", d.C0, c1, a.M, a.N, a.K, d.out_mode, p.tile,
             p.bm, n_fast);
   else if (p.tile == 18)

@@ -8,8 +8,8 @@
 
 namespace sd {
 
-// the kernel a plan launches (tile -1 / 1-4 / 7 / 18 / 21 / 9 / 14 / 17 / 10 / 11 / 12 / 15 / 19 / 13 / 16 / 20 / 22 of the wire format below)
-enum class ConvKernel { Generic, Igemm, GemmPipe, HaloKs, HaloI8, HaloSubpix, Wstream, WstreamPal, WstreamI8, Wsgemm, Bvgemm, Smgemm, SmgemmPal, SmgemmI8, Smgeglu, SmgegluPal, SmgegluI8, SmqkvI8 };
+// the kernel a plan launches (tile -1 / 1-4 / 7 / 18 / 21 / 9 / 14 / 17 / 10 / 11 / 12 / 15 / 19 / 13 / 16 / 20 / 22 / 24 of the wire format below)
+enum class ConvKernel { Generic, Igemm, GemmPipe, HaloKs, HaloI8, HaloSubpix, Wstream, WstreamPal, WstreamI8, Wsgemm, Bvgemm, Smgemm, SmgemmPal, SmgemmI8, Smgeglu, SmgegluPal, SmgegluI8, SmqkvI8, SmgemmQ8 };
 
 struct ConvPlan {
   // The wire format: what ConvDesc::tile / staging pins, tuned_convs.inc rows, SD_PLAN_TABLE and sd_tune_set_candidate say and what
@@ -24,6 +24,8 @@ struct ConvPlan {
                    // 21: the upsampler conv as four 2x2 phase convs on the low-res halo (conv3x3_halo_sp.hip; only with ConvDesc::subpix);
                    // 22: the self-attention q|k|v projection from int8 weights and int8 activations written by the LayerNorm in front
                    // of it (smqkv_i8.hip, BM x 160-column tiles at tile 20's two heights; never the library's own answer);
+                   // 24: the small-M GEMM from int8 weights and int8 activations written by their producer (smgemm_q8.hip, tile 12 / 19's
+                   // tiles; never the library's own answer; 23 is not in use);
                    // -1 = not on the MFMA path (launch_conv_generic)
   int staging;     // per-family code: decode_plan
   int splitk;      // resolved: what the launch runs, no empty splits (halo: over 64-channel chunks; tile 9: the slab count)
@@ -64,7 +66,10 @@ ConvWeightCopies conv_plan_copies(const ConvDesc& d);
 //            heights) - asked WITHOUT the LayerNorm fold's fields, which tile 20 does not take (the caller un-folds: UNet::transformer_block)
 //            - and the opted-in fused q|k|v launch (tile 22, which has no fp16 twin: taken wherever smqkv_i8_shape_ok admits the
 //            un-folded descriptor, at the height smqkv_i8_bm resolves; `held` then speaks for all three tensors - the caller has
-//            checked that each carries a mark and that the marks share one range)
+//            checked that each carries a mark and that the marks share one range) - and the opted-in plain projection whose
+//            descriptor says that its activations arrive as int8 (d.x0_i8 set: ff.net.2 behind the GEGLU, UNet::transformer_block; tile
+//            24, which has no fp16 twin to follow either - the un-merged ff.net.2 of the 1280-channel level is deeper than tile 12's own
+//            rule goes: taken wherever smgemm_q8_wanted admits the descriptor, while SD_SMGEMM leaves tile 12 on)
 enum class StoredWeights { Fp16, Palette, W8A8 };
 struct WeightPin {
   WeightSource kind = WeightSource::Fp16;
@@ -84,7 +89,7 @@ void conv_plan_log(const ConvDesc& d, const ConvPlan& p, int n_fast = 0);
 //   "conv3x3_halo_sp ring<stages>"
 //   "wstream waves<n>"   "wstream_pal waves<n>"    "wstream_i8 waves<n>"                 "wsgemm"    "bvgemm v<variant>"
 //   "smgemm bm<bm>"      "smgemm_pal bm<bm>"       "smgemm_i8 bm<bm>"                    "smgeglu bm<bm>"    "smgeglu_pal bm<bm>"
-//   "smgeglu_i8 bm<bm>"  "smqkv_i8 bm<bm>"        "generic"
+//   "smgeglu_i8 bm<bm>"  "smqkv_i8 bm<bm>"        "smgemm_q8 bm<bm>"                    "generic"
 std::string conv_plan_kernel_name(const ConvPlan& p);
 
 // Tile order inside an XCD's run of workgroup ids, from an estimate of the bytes each order pulls through the fabric into the 8 XCD L2s:
@@ -139,7 +144,8 @@ static_assert(127LL * 127 * 9 * kHaloI8MaxCtot < (1LL << 31) && 127LL * 127 * 9 
 // smgemm_i8_kernel (plan tile 19) sums the whole K of a 1x1 GEMM in int32: 127 * 127 * K < 2^31, the last multiple of 64 that fits
 constexpr int kSmI8MaxK = 133120;
 static_assert(127LL * 127 * kSmI8MaxK < (1LL << 31) && 127LL * 127 * (kSmI8MaxK + 64) >= (1LL << 31), "int32 bound of plan tile 19");
-// (smgeglu_i8_kernel, plan tile 20, and smqkv_i8_kernel, plan tile 22, sum the whole K of their 1x1 GEMMs the same way: the same bound)
+// (smgeglu_i8_kernel, plan tile 20, smqkv_i8_kernel, plan tile 22, and smgemm_q8_kernel, plan tile 24, sum the whole K of their 1x1 GEMMs
+// the same way: the same bound)
 
 // Plan tile 22 (smqkv_i8.hip): the fused q|k|v projection [Wq | Wk | Wv] (3C, C) of a self-attention from int8 weights and the int8
 // output of norm1 - BM x kSmQkvCols tiles, BM = 128 / 256 (variant 1 / 2; 0: by the grid, tile 13's rule - 128 rows while that grid
@@ -153,6 +159,10 @@ static_assert(127LL * 127 * kSmI8MaxK < (1LL << 31) && 127LL * 127 * (kSmI8MaxK 
 //   * S = Ho * Wo a multiple of 16: a lane's four V^T tokens and the 16-token blocks vt_perm permutes lie in one sample; ldT >= S, ldT % 8 == 0;
 //   * q_cols 0 (no q_scale) or C0 (the queries, whole tiles);
 //   * M % BM == 0, at least two tile rows, a tile count that is a multiple of 8 (the XCD runs of sm_tile.h) and at most 65535.
+// Plan tile 24 (smgemm_q8.hip) in a handle: smgemm_q8_shape_ok - tile 19's eligibility - on the grids tile 12's own rule takes (M from
+// 256 to 2048, 192 to 256 tiles: one round of the chip; the 8 x 8 mid block at M = 128 is not among them), at any K up to kSmI8MaxK, no
+// GroupNorm statistics wanted of the output.
+bool smgemm_q8_wanted(const ConvDesc& d);
 constexpr int kSmQkvCols = 160;
 bool smqkv_i8_shape_ok(const ConvDesc& d, int variant);
 bool smqkv_i8_tiles(const ConvDesc& d, int variant);   // the rule without the int32 bound (an operator entry names that refusal on its own)

@@ -1142,6 +1142,7 @@ int launch_conv(const ConvDesc& d, const ConvWorkspace& ws, hipStream_t s) {
     case ConvKernel::SmgemmPal: launch_smgemm_pal(d, p, s); return 0;   // (d.gn_partial set: no statistics, 0 entries - the GroupNorm runs its own pass)
     case ConvKernel::SmgemmI8: launch_smgemm_i8(d, p, s); return 0;     // (the same)
     case ConvKernel::SmgegluI8: launch_smgeglu_i8(d, p, s); return 0;
+    case ConvKernel::SmgemmQ8: launch_smgemm_q8(d, p, s); return 0;
     case ConvKernel::SmqkvI8: launch_smqkv_i8(d, p, s); return 0;
     default: break;
   }

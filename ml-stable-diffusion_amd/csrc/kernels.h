@@ -42,9 +42,12 @@ struct GnTwin {
 //               the activations arrive quantized (ConvDesc::x0_i8, written by launch_layernorm_q8)
 //   I8Qkv       tile 22, smqkv_i8.hip         smqkv_i8_kernel (W8A8)          stream of smqkv_i8_pack     staging: 1 / 2 = 128- / 256-row tiles (0 = by the
 //               grid); the stacked [Wq | Wk | Wv] of a fused q|k|v launch, activations quantized by their producer as for I8Geglu
-//   (tiles 19, 20, 22: LDS image, ladder, epilogue arithmetic and launch, and the ring geometry, issue and wait of tiles 20 and 22, are
-//   sm_i8_ring.h's)
-enum class WeightSource { Fp16, PalWstream, PalGemm, PalGeglu, I8Wstream, I8Halo, I8Gemm, I8Geglu, I8Qkv };
+//   I8GemmQ     tile 24, smgemm_q8.hip        smgemm_q8_kernel (W8A8)         stream of smgemm_i8_pack    staging: tile 12's code (0 = by M);
+//               tile 19's GEMM with the activations quantized by their producer (ConvDesc::x0_i8: tile 20 with an int8 output, or a
+//               plain-form launch_layernorm_q8)
+//   (tiles 19, 20, 22, 24: LDS image, ladder, epilogue arithmetic and launch, and the ring geometry, issue and wait of tiles 20 and 22,
+//   are sm_i8_ring.h's)
+enum class WeightSource { Fp16, PalWstream, PalGemm, PalGeglu, I8Wstream, I8Halo, I8Gemm, I8Geglu, I8Qkv, I8GemmQ };
 struct CompressedWeights {
   WeightSource kind = WeightSource::Fp16;
   const void* stream = nullptr;
@@ -54,21 +57,21 @@ struct CompressedWeights {
   // PalGeglu with the LayerNorm fold (ConvDesc::ln_colsum set): the fp32 norm weight [C0] - the kernel multiplies every LUT value by it
   // as fold_layernorm_rows does on the host; null without the fold
   const float* ln_gamma = nullptr;
-  // I8Wstream / I8Halo / I8Gemm / I8Geglu / I8Qkv: the output scale per column scale[n] = fp32(s_a * s_w[n]) (I8Geglu: rows in the
-  // interleaved order of the GEGLU upload, geglu_row) and inv_s = fp32(1 / s_a), the factor the kernel - for I8Geglu / I8Qkv the
-  // LayerNorm in front of it - quantizes its activations by
+  // I8Wstream / I8Halo / I8Gemm / I8Geglu / I8Qkv / I8GemmQ: the output scale per column scale[n] = fp32(s_a * s_w[n]) (I8Geglu: rows in the
+  // interleaved order of the GEGLU upload, geglu_row) and inv_s = fp32(1 / s_a), the factor the kernel - for I8Geglu / I8Qkv / I8GemmQ
+  // the producer in front of it - quantizes its activations by
   const float* scale = nullptr;
   float inv_s = 0.f;
   bool palettized() const { return kind == WeightSource::PalWstream || kind == WeightSource::PalGemm || kind == WeightSource::PalGeglu; }
   const uint8_t* pal() const { return palettized() ? static_cast<const uint8_t*>(stream) : nullptr; }
-  bool int8() const { return kind == WeightSource::I8Wstream || kind == WeightSource::I8Halo || kind == WeightSource::I8Gemm || kind == WeightSource::I8Geglu || kind == WeightSource::I8Qkv; }
+  bool int8() const { return kind == WeightSource::I8Wstream || kind == WeightSource::I8Halo || kind == WeightSource::I8Gemm || kind == WeightSource::I8Geglu || kind == WeightSource::I8Qkv || kind == WeightSource::I8GemmQ; }
   const int8_t* i8() const { return int8() ? static_cast<const int8_t*>(stream) : nullptr; }
 };
 
 struct ConvDesc {
   const half_t* x0 = nullptr;   // [B][Hi][Wi][C0]
   const half_t* x1 = nullptr;   // optional second source (channel concat), [B][Hi][Wi][C1]
-  const int8_t* x0_i8 = nullptr;   // cw of kind I8Geglu / I8Qkv: the source as int8 [M][C0], quantized by its producer (launch_layernorm_q8); x0 is not read
+  const int8_t* x0_i8 = nullptr;   // cw of kind I8Geglu / I8Qkv / I8GemmQ: the source as int8 [M][C0], quantized by its producer (launch_layernorm_q8, tile 20's int8 output); x0 is not read
   int C0 = 0, C1 = 0;
   const half_t* w = nullptr;    // [N][K] K-major, K = ksize*ksize*(C0+C1), tap-major
   const float* bias = nullptr;  // [N] or null
@@ -76,6 +79,10 @@ struct ConvDesc {
   int temb_stride = 0;
   const half_t* res = nullptr;  // [M][N] residual, or null
   half_t* out = nullptr;
+  // cw of kind I8Geglu only: the product leaves as int8 [M][N / 2] = ws_quantize8(the fp16 values `out` would hold, out_inv_s) - the
+  // activations of a plan-tile-24 GEMM behind it; `out` is then not written
+  int8_t* out_q8 = nullptr;
+  float out_inv_s = 0.f;
   int B = 1, Hi = 1, Wi = 1;    // source spatial size (before nearest x2 upsampling)
   int Ho = 1, Wo = 1;           // output spatial size
   int ksize = 1, stride = 1, up = 1;
@@ -208,6 +215,10 @@ void launch_smgemm_pal(const ConvDesc& d, const ConvPlan& p, hipStream_t s);
 // the semantics of the int8 weight stream (plan tile 17), not tile 12's rounding; K <= kSmI8MaxK
 bool smgemm_i8_shape_ok(const ConvDesc& d, int variant);              // smgemm_shape_ok, one source, inside the int32 bound
 void launch_smgemm_i8(const ConvDesc& d, const ConvPlan& p, hipStream_t s);
+// smgemm_q8.hip: tile 19's GEMM - tiles, eligibility, epilogue, the same function of the quantized activations - from int8 activations
+// written by the producer (W8A8, plan tile 24: d.cw of kind I8GemmQ, d.x0_i8); no quantizer in the K loop
+bool smgemm_q8_shape_ok(const ConvDesc& d, int variant);              // smgemm_i8_shape_ok
+void launch_smgemm_q8(const ConvDesc& d, const ConvPlan& p, hipStream_t s);
 
 // wfold.hip: two back-to-back linear maps folded into one - merged [N][K + J] = [fp16(Wp W2) | Wp], bm = bp + Wp b2 (Wp [N][J],
 // W2 [J][K]; fp32 accumulation in a fixed order, once per handle: UNet::transformer_block's merged tail)
@@ -226,7 +237,8 @@ size_t smgeglu_prof_entries(const ConvDesc& d, int variant);          // this ma
 bool smgeglu_pal_shape_ok(const ConvDesc& d, int variant);            // variant 0 / 1 resolving to 128-row tiles
 void launch_smgeglu_pal(const ConvDesc& d, const ConvPlan& p, hipStream_t s);
 // smgeglu_i8.hip: the projection WITHOUT the fold on the same tiles from int8 weights and int8 activations (W8A8, plan tile 20: d.cw of
-// kind I8Geglu, d.x0_i8) - exact int32 sums, scale and bias in fp32, then tile 13's v * gelu_erf(g); both tile heights, K <= kSmI8MaxK
+// kind I8Geglu, d.x0_i8) - exact int32 sums, scale and bias in fp32, then tile 13's v * gelu_erf(g); both tile heights, K <= kSmI8MaxK.
+// With d.out_q8 set the fp16 values leave through ws_quantize8(., d.out_inv_s) as int8 [M][N / 2] instead (the producer of plan tile 24)
 bool smgeglu_i8_shape_ok(const ConvDesc& d, int variant);             // smgeglu_shape_ok, no fold, inside the int32 bound
 void launch_smgeglu_i8(const ConvDesc& d, const ConvPlan& p, hipStream_t s);
 // smqkv_i8.hip: the fused q|k|v projection of a self-attention from int8 weights and int8 activations (W8A8, plan tile 22: d.cw of kind

@@ -154,6 +154,12 @@ bool Net::observes_geglu(const std::string& name, const Tensor& x, const ConvArg
   return conv_plan_weights(d, StoredWeights::W8A8, a.keep_compressed).kind == WeightSource::I8Geglu;
 }
 
+bool Net::observes_tail(const std::string& name, const Tensor& x, const ConvArgs& a) const {
+  if (f32_ || !ws_->observe() || !ws_->observe_tails() || ws_->palette(name + ".weight") || a.out_mode != kOutHalf) return false;
+  const WeightSource could = conv_plan_weights(conv_shape(name, x, a), StoredWeights::W8A8, a.keep_compressed).kind;
+  return could == (a.x_i8 ? WeightSource::I8GemmQ : WeightSource::I8Gemm);
+}
+
 void Net::observe_tensor(std::vector<Op>& ops, const std::string& name, const Tensor& t, const std::vector<std::string>& report_as) {
   float* slot = ll_.arena.alloc_n<float>(1);   // (the arena is zeroed: the running maximum starts at 0)
   if (report_as.empty()) observed_.push_back({name + ".weight", slot});
@@ -237,7 +243,7 @@ ConvWeights Net::upload_compressed(const std::string& name, const WeightPin& pin
   size_t bytes = 0;
   CompressedWeights cw;
   if (pin.kind == WeightSource::I8Wstream || pin.kind == WeightSource::I8Halo || pin.kind == WeightSource::I8Gemm ||
-      pin.kind == WeightSource::I8Geglu) {   // q in the kernel's layout, cs[n], inv_s: no fp16 copy
+      pin.kind == WeightSource::I8Geglu || pin.kind == WeightSource::I8GemmQ) {   // q in the kernel's layout, cs[n], inv_s: no fp16 copy
     const W8A8Mark* i8 = ws_->w8a8(wname);
     SD_REQUIRE(i8 && ws_->get(wname).numel() == expect && i8->q.size() == expect && i8->w_scale.size() == (size_t)a.cout, kInvalidArgument,
                "%s: expected %zu W8A8 values (%d,%d,%d,%d)", wname.c_str(), expect, a.cout, cin, a.k, a.k);
@@ -356,6 +362,11 @@ Tensor Net::conv_w(std::vector<Op>& ops, const std::string& name, const ConvWeig
   } else if (a.out_mode == kOutHalfT) {
     out.B = x.B; out.H = 1; out.W = a.ldT; out.C = cout;   // [B][cout][ldT]
     out.p = ll_.arena.alloc_n<half_t>((size_t)x.B * cout * a.ldT);
+  } else if (a.out_q8) {   // (plan tile 20 with an int8 output: the shape alone)
+    SD_REQUIRE(geglu && d.cw.kind == WeightSource::I8Geglu && a.out_inv_s > 0.f, kInternal, "%s: an int8 output needs the int8 GEGLU kernel", name.c_str());
+    out.B = x.B; out.H = d.Ho; out.W = d.Wo; out.C = cout / 2;
+    d.out_q8 = a.out_q8;
+    d.out_inv_s = a.out_inv_s;
   } else {
     out = new_tensor(x.B, d.Ho, d.Wo, geglu ? cout / 2 : cout);
   }
@@ -413,11 +424,12 @@ Tensor Net::conv_w(std::vector<Op>& ops, const std::string& name, const ConvWeig
   // trailing "#kind,ksize,stride,up,Ctot,N,M" is the plan-table key of this op (tools/tune_plans.py)
   const int kind = d.out_t ? 3 : (geglu ? 2 : (ln ? 1 : 0));
   // the weight source in the label: "[+ln]+pal<bits>" from a palette (plan tile 14 or 15), "geglu+pal<bits>[+ln]" for plan tile 16,
-  // "+w8a8" from int8 weights and quantized activations (plan tiles 17 / 18 / 19 / 20)
+  // "+w8a8" from int8 weights and quantized activations (plan tiles 17 / 18 / 19 / 20 / 22 / 24), "+q8out+w8a8" where plan tile 20 writes
+  // its product as int8
   const WeightSource src = d.cw.kind;
   const std::string lnmark = ln ? "+ln" : "", palmark = "+pal" + std::to_string(d.cw.bits);
   // "+subpix": the upsampler as four 2x2 phase convs (plan tile 21); flop below stays the algorithmic 9-tap count of the map it replaces
-  const std::string mark = d.subpix ? "+subpix" : src == WeightSource::PalGeglu ? palmark + lnmark : lnmark + (d.cw.i8() ? "+w8a8" : src != WeightSource::Fp16 ? palmark : "");
+  const std::string mark = d.subpix ? "+subpix" : src == WeightSource::PalGeglu ? palmark + lnmark : lnmark + (d.cw.i8() ? (d.out_q8 ? "+q8out+w8a8" : "+w8a8") : src != WeightSource::Fp16 ? palmark : "");
   snprintf(buf, sizeof(buf), "%s%s %d->%d @%dx%d M=%d K=%d %s #%d,%d,%d,%d,%d,%d,%d",
            k == 3 ? "conv3x3" : (geglu ? (src == WeightSource::PalGeglu ? "geglu" : "geglu1x1") : "gemm1x1"), mark.c_str(), cin, cout, d.Ho, d.Wo,
            x.B * d.Ho * d.Wo, cin * k * k, name.c_str(), kind, k, a.stride, a.up, cin, cout, x.B * d.Ho * d.Wo);

@@ -81,8 +81,14 @@ struct ConvArgs {
   // weights run from fp16 and subpixel_wanted says so (Net::conv); a W8A8-marked or palettized upsampler runs what it ran without it.
   bool subpix = false;
   // conv_w only - the source as int8 [M][C], written by a layernorm_q8 launch in front of this op (plan tiles 20 and 22 read nothing
-  // else; x still gives the shape).  With n_trans > 0 it is the fused q|k|v split without the fold (plan tile 22)
+  // else; x still gives the shape).  With n_trans > 0 it is the fused q|k|v split without the fold (plan tile 22); with the plain
+  // epilogue it is ff.net.2 behind the GEGLU (plan tile 24) - weight_plan is asked with any non-null pointer, the question being
+  // "would this projection run from int8 activations"
   const int8_t* x_i8 = nullptr;
+  // conv_w only, plan tile 20 - the GEGLU product leaves as int8 [M][cout / 2], quantized with out_inv_s (ConvDesc::out_q8): the
+  // activations of the plan-tile-24 ff.net.2 behind it.  The returned tensor then has the shape and NO storage (p == nullptr)
+  int8_t* out_q8 = nullptr;
+  float out_inv_s = 0.f;
 };
 
 // The weights conv_w runs from: an fp16 matrix on the device, or a compressed source with its pin (Net::upload_compressed)
@@ -152,6 +158,9 @@ class Net {
   // make this GEGLU run as plan tile 20?  Then the caller normalises the GEGLU's input into a scratch tensor and observe_tensor puts
   // an absmax launch over it, into a slot named <name>.weight - two ordinary launches that write nothing the model reads.
   bool observes_geglu(const std::string& name, const Tensor& x, const ConvArgs& a, bool ln) const;
+  // Calibration of the transformer tails (WeightStore::observe_tails while the store observes): would a W8A8 mark on <name>.weight make
+  // this projection (a: its ConvArgs with x_i8 set, as weight_plan is asked) run as plan tile 24 / (x_i8 null) as plan tile 19?
+  bool observes_tail(const std::string& name, const Tensor& x, const ConvArgs& a) const;
   // (report_as: the weight names, without ".weight", the one slot is reported under - <name> alone when empty)
   void observe_tensor(std::vector<Op>& ops, const std::string& name, const Tensor& t, const std::vector<std::string>& report_as = {});
   // The fused q|k|v launch `name` over the projections `parts` (to_q, to_k, to_v) in W8A8: qkv_plan answers I8Qkv (plan tile 22) when

@@ -1,5 +1,6 @@
-// What the int8 small-M kernels (smgemm_i8.hip, smgeglu_i8.hip, smqkv_i8.hip: plan tiles 19, 20, 22) share: the LDS image of a 1-KiB
-// LDS-DMA piece, the geometry, issue and counted wait of the ring of tiles 20 and 22, the epilogue's arithmetic and the host launch.
+// What the int8 small-M kernels (smgemm_i8.hip, smgeglu_i8.hip, smqkv_i8.hip, smgemm_q8.hip: plan tiles 19, 20, 22, 24) share: the LDS
+// image of a 1-KiB LDS-DMA piece, the geometry, issue and counted wait of the ring of tiles 20 and 22 (tile 24 runs the same issue and
+// wait over a five-wave geometry of its own, SmQ8Cfg in smgemm_q8.hip), the epilogue's arithmetic and the host launch.
 // (sm_ring.h: the ladder behind the counted waits, here with the LDS counter drained in front of the barrier; sm_tile.h: tile order,
 // sm_round4 / sm_pack16.)  As in sm_tile.h the device helpers hold no arithmetic the compiler re-associates with its surroundings.
 //
@@ -49,8 +50,15 @@ __device__ __forceinline__ float sm_i8_affine(int acc, float cs, float bias, boo
   if (has_bias) v = v + bias;
   return v;
 }
+// ... and the plain GEMM's ending (tiles 19 and 24) for one element: the residual meets the fp32 value, in a rounding of its own
+__device__ __forceinline__ float gemm_value(int acc, float cs, float bias, bool has_bias, float res, bool has_res) {
+#pragma clang fp contract(off)
+  float v = sm_i8_affine(acc, cs, bias, has_bias);
+  if (has_res) v = v + res;
+  return v;
+}
 
-constexpr int SM_I8_WROWS = 160;          // weight rows per workgroup of the ring: ten 16-row strips
+constexpr int SM_I8_WROWS = 160;         // weight rows per workgroup of the ring: ten 16-row strips
 constexpr int SM_I8_NW = 10;              // waves: strip pair x row half
 
 // geometry of the ring: what the host needs too
@@ -74,7 +82,7 @@ struct SmI8RingCfg : SmI8RingGeom<BM> {
 };
 
 // issue and counted wait over the kernel's ring state: full = this wave issues PPW pieces per stage (wave < FULL); slot j of the wave is
-// piece p = wave + 10 j (wrapped at PIECES: never issued), pdst[j] = 1024 p, src[j] = the lane's 16 B of it in the next stage to issue
+// piece p = wave + 10 j (tile 24: wave + 5 j; wrapped at PIECES: never issued), pdst[j] = 1024 p, src[j] = the lane's 16 B of it in the next stage to issue
 template <class C>
 struct SmI8Ring {
   static constexpr int NST = C::NST, PPW = C::PPW;

@@ -19,6 +19,10 @@
 //     keeps tile 13's eligibility rule C % 64 == 0 with no tail stage, the ring gets twice the depth in stages for the same bytes in
 //     flight, and a barrier still covers 8 / 16 MFMAs of 16 x 16 x 64 per wave - the MFMA time of a tile-13 K64 stage, whose barrier
 //     count this kernel therefore shares.  Not measured against a K128 build.
+//   * Q8OUT (a third and fourth instantiation; the two fp16 ones keep their text): behind sm_round4 and the exchange the lane holds the
+//     eight fp16 values it would store; it quantizes exactly those with ws_quantize8(o8, inv_s_out) and stores 8 B of out_q [M][N / 2]
+//     int8 instead - bit for bit the plain quantizer over what the fp16 launch stores, the tensor the reference calibrates for
+//     ff.net.2, and the activations of plan tile 24 (smgemm_q8.hip) with no launch in between.
 #include "conv_plan.h"
 #include "igemm_device.h"
 #include "kernels.h"
@@ -38,6 +42,8 @@ struct SgI8Args {
   const float* cs;      // [N] s_a * s_w, rows interleaved 32 value / 32 gate (geglu_row)
   const float* bias;    // [N], the same order; has_bias == 0: any readable float[N] (the loads keep their count)
   half_t* out;          // [M][N / 2]
+  int8_t* out_q;        // Q8OUT: [M][N / 2] int8 in place of out
+  float inv_s_out;      // Q8OUT: 1 / s of the output's range
   int K, nk, ldo;
   int has_bias;
   SmTileOrder order;
@@ -46,7 +52,7 @@ struct SgI8Args {
 // first row, in the upload's interleaved order, of 16-column unit U of the output: its 16 value rows; the gate rows are 32 further on
 __device__ __forceinline__ int geglu_unit_row(int U) { return 64 * (U >> 1) + 16 * (U & 1); }
 
-template <int BM>
+template <int BM, bool Q8OUT>
 __global__ __launch_bounds__(64 * SM_I8_NW, 1) void smgeglu_i8_kernel(SgI8Args a) {
   using C = SmI8RingCfg<BM, 4>;   // EPI = 4: bias_v, bias_g, cs_v, cs_g below
   constexpr int NST = C::NST, PPW = C::PPW, TM = C::TM;
@@ -137,7 +143,8 @@ __global__ __launch_bounds__(64 * SM_I8_NW, 1) void smgeglu_i8_kernel(SgI8Args a
     }
     const half8 o8 = sm_pack16(ho[0], ho[1]);
     const int m = m_blk + h * (BM / 2) + 32 * p + 16 * (g & 1) + r16;
-    out_store(reinterpret_cast<half8*>(a.out + (size_t)m * a.ldo + n), o8);
+    if constexpr (Q8OUT) out_store(reinterpret_cast<uintx2*>(a.out_q + (size_t)m * a.ldo + n), ws_quantize8(o8, a.inv_s_out));
+    else out_store(reinterpret_cast<half8*>(a.out + (size_t)m * a.ldo + n), o8);
   }
 }
 
@@ -148,7 +155,7 @@ bool smgeglu_i8_shape_ok(const ConvDesc& d, int variant) { return smgeglu_shape_
 void launch_smgeglu_i8(const ConvDesc& d, const ConvPlan& p, hipStream_t s) {
   const int bm = p.bm;
   SD_REQUIRE((bm == 128 || bm == 256) && smgeglu_i8_shape_ok(d, bm == 128 ? 1 : 2) && d.cw.kind == WeightSource::I8Geglu && d.cw.stream && d.cw.scale &&
-                 d.x0_i8,
+                 d.x0_i8 && (!d.out_q8 || (d.out_inv_s > 0.f && std::isfinite(d.out_inv_s))),
              kInvalidArgument,
              "plan tile 20 (smgeglu_i8.hip, int8): not a 1x1 GEGLU projection it tiles, or no int8 weights / activations (C0=%d N=%d M=%d bm=%d)", d.C0,
              d.N, d.B * d.Ho * d.Wo, bm);
@@ -159,6 +166,8 @@ void launch_smgeglu_i8(const ConvDesc& d, const ConvPlan& p, hipStream_t s) {
   a.cs = d.cw.scale;
   a.bias = d.bias ? d.bias : d.cw.scale;   // absent: the scales stand in, N floats (the loads keep their count)
   a.out = d.out;
+  a.out_q = d.out_q8;
+  a.inv_s_out = d.out_inv_s;
   a.K = K;
   a.nk = K / SM_I8_BK;
   a.ldo = d.N / 2;
@@ -166,8 +175,11 @@ void launch_smgeglu_i8(const ConvDesc& d, const ConvPlan& p, hipStream_t s) {
   a.order = sm_tile_order(M, d.N, K, M / bm, d.N / SM_I8_WROWS);   // tile 13's order, from the fp16 sizes
   const unsigned nwg = (unsigned)(M / bm) * (d.N / SM_I8_WROWS);
   conv_plan_log(d, p, a.order.n_fast);
-  if (bm == 128) sm_i8_launch<smgeglu_i8_kernel<128>>(a, nwg, SM_I8_NW, SmI8RingGeom<128>::LDS, s);
-  else sm_i8_launch<smgeglu_i8_kernel<256>>(a, nwg, SM_I8_NW, SmI8RingGeom<256>::LDS, s);
+  if (d.out_q8) {
+    if (bm == 128) sm_i8_launch<smgeglu_i8_kernel<128, true>>(a, nwg, SM_I8_NW, SmI8RingGeom<128>::LDS, s);
+    else sm_i8_launch<smgeglu_i8_kernel<256, true>>(a, nwg, SM_I8_NW, SmI8RingGeom<256>::LDS, s);
+  } else if (bm == 128) sm_i8_launch<smgeglu_i8_kernel<128, false>>(a, nwg, SM_I8_NW, SmI8RingGeom<128>::LDS, s);
+  else sm_i8_launch<smgeglu_i8_kernel<256, false>>(a, nwg, SM_I8_NW, SmI8RingGeom<256>::LDS, s);
   SD_HIP(hipGetLastError());
 }
 

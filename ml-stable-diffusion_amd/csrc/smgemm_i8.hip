@@ -101,14 +101,6 @@ __device__ __forceinline__ int smi_piece(int wave, int j) {
   return wave >= 1 && wave <= 3 ? SMI_NW - 1 + wave : XP + (wave == 0 ? 0 : 1);
 }
 
-// the epilogue's arithmetic for one element: the residual meets the fp32 value, in a rounding of its own
-__device__ __forceinline__ float gemm_value(int acc, float cs, float bias, bool has_bias, float res, bool has_res) {
-#pragma clang fp contract(off)
-  float v = sm_i8_affine(acc, cs, bias, has_bias);
-  if (has_res) v = v + res;
-  return v;
-}
-
 template <int BM>
 __global__ __launch_bounds__(64 * SMI_NW, 1) void smgemm_i8_kernel(SmI8Args a) {
   using C = SmI8Cfg<BM>;

@@ -199,7 +199,7 @@ Tensor UNet::attention(std::vector<Op>& ops, const Tensor& q, const half_t* k, c
 
 // unet.py:586-591 (+ CrossAttention :87-118, FeedForward/GEGLU :594-617)
 Tensor UNet::transformer_block(std::vector<Op>& ops, const std::string& b, const Tensor& h, int heads, const std::string* proj_out,
-                               const Tensor* tres, bool* tail_done, const PreQkv* pre) {
+                               const Tensor* tres, bool* tail_done, const PreQkv* pre, bool* tail_q8) {
   const int C = h.C, S = h.H * h.W, L = cfg_.context_len;
   // --- self attention.  MFMA-tileable widths: norm1 is folded into ONE fused q|k|v GEMM whose V
   // columns leave token-transposed (attention's V^T operand); otherwise LN + stacked q|k + V^T GEMMs.
@@ -374,8 +374,37 @@ Tensor UNet::transformer_block(std::vector<Op>& ops, const std::string& b, const
   const bool fold3 = can_fold_ln(h2, 8 * C, true);
   ConvArgs ga{.cout = 8 * C, .out_mode = kOutGeglu, .keep_compressed = true};
   const WeightPin gpin = weight_plan(gname, h2, ga, fold3);
+  // The tail, asked before the GEGLU is built.  A W8A8-marked ff.net.2 whose un-merged shape plan tile 24 takes (conv_plan.h
+  // smgemm_q8_wanted; not where the 320-channel level's one-launch tail runs) is NOT merged with proj_out: it runs from int8 on
+  // int8(v * gelu(g)) - the tensor the reference calibrates and quantizes for it - plus h2, and proj_out is a launch of its own behind
+  // it (UNet::transformer; from int8 too where it is marked: plan tile 19).  The GEGLU writes the int8 product itself where it runs plan
+  // tile 20 (no fp16 product is allocated); behind any other GEGLU one plain-form layernorm_q8 launch quantizes the product, the same
+  // flat buffer read as (4 M, C) rows.  An observing store (observe_tails) leaves the tail as it is and puts observers beside it.
+  static const int fp_mode = tune_env_int("SD_FFN_PROJ", 1);
+  const bool ffn_one_launch = proj_out && tres && tail_done && fp_mode != 0 && ffn_proj_ok(C, 4 * C, h.M(), S);
+  const std::string tname = b + ".ff.net.2";
+  Tensor gshape = h2;   // the GEGLU product as the planner sees it
+  gshape.C = 4 * C;
+  gshape.p = nullptr;
+  gshape.gn.reset();
+  static const int8_t i8_present = 0;   // the planner only tests the pointer
+  ConvArgs ta{.cout = C, .res = h2.p, .keep_compressed = true, .x_i8 = &i8_present};
+  const bool tail_rule = !ffn_one_launch && C % 8 == 0 && C <= 2048;   // (what the fall-back quantizer launch takes)
+  const WeightPin tpin = tail_rule ? weight_plan(tname, gshape, ta, false) : WeightPin{};
+  const bool tail_i8 = tpin.kind == WeightSource::I8GemmQ;
+  const bool tail_observed = tail_rule && observes_tail(tname, gshape, ta);
+  ConvWeights tw(nullptr);
+  int8_t* gq = nullptr;
+  if (tail_i8) {
+    tw = upload_compressed(tname, tpin, 4 * C, ta);
+    gq = ll_.arena.alloc_n<int8_t>((size_t)h2.M() * 4 * C);
+  }
   if (observes_geglu(gname, h2, ga, fold3)) observe_tensor(ops, gname, layer_norm(ops, b + ".norm3", h2));
   if (gpin.kind == WeightSource::I8Geglu) {
+    if (tail_i8) {
+      ga.out_q8 = gq;
+      ga.out_inv_s = tw.cw.inv_s;
+    }
     const ConvWeights gw = upload_compressed(gname, gpin, C, ga);
     const float* gb = ws_->has(gname + ".bias") ? upload_vec(gname + ".bias", 8 * C, true) : nullptr;
     const float* nw = upload_vec(b + ".norm3.weight", C);
@@ -398,12 +427,32 @@ Tensor UNet::transformer_block(std::vector<Op>& ops, const std::string& b, const
     Tensor n3 = layer_norm(ops, b + ".norm3", h2);
     g = conv(ops, b + ".ff.net.0.proj", n3, {.cout = 8 * C, .out_mode = kOutGeglu, .keep_compressed = true});
   }
+  if (tail_i8) {
+    if (!ga.out_q8) {   // the product exists in fp16: one quantizer launch over it
+      const int rows = 4 * h2.M();
+      const half_t* gp = g.p;
+      const float inv_s = tw.cw.inv_s;
+      ops.push_back([=](hipStream_t s) { launch_layernorm_q8(gp, nullptr, nullptr, gq, rows, C, 1e-5f, inv_s, s); });
+      ops.back().label = "quantize_q8 " + tname;
+    }
+    ta.x_i8 = gq;
+    if (tail_q8) *tail_q8 = true;
+    return conv_w(ops, tname, tw, upload_vec(tname + ".bias", C), g, ta);
+  }
+  if (tail_observed) {   // the range ff.net.2 would be quantized with and, through a scratch ff.net.2, the one its proj_out would be
+    observe_tensor(ops, tname, g);
+    if (proj_out && tres) {
+      const ConvArgs pa{.cout = C, .res = tres->p, .keep_compressed = true};
+      Tensor h3 = h2;   // (shape)
+      h3.gn.reset();
+      if (observes_tail(*proj_out, h3, pa)) observe_tensor(ops, *proj_out, conv(ops, tname, g, {.cout = C, .res = h2.p}));
+    }
+  }
   // the tail of the SpatialTransformer - ff.net.2 + residual -> proj_out + residual - as ONE launch at the 320-channel level
   // (ffn_proj_kernel: the intermediate never goes to HBM, the output's GroupNorm statistics for the next resnet come out of it);
   // five launches less per step, 5.402 -> 5.392 ms on the (slow) box it was measured on (profiles/r05_ffn_proj_ab_slow_box.log);
   // SD_FFN_PROJ=0 (with SD_TUNE): the two GEMM launches (A/B)
-  static const int fp_mode = tune_env_int("SD_FFN_PROJ", 1);
-  if (proj_out && tres && tail_done && fp_mode != 0 && g.C == 4 * C && ffn_proj_ok(C, 4 * C, h.M(), S)) {
+  if (ffn_one_launch && g.C == 4 * C) {
     const half_t* w1 = upload_conv_weight(b + ".ff.net.2", C, 4 * C, 1, false);
     half_t* w1_t = ll_.arena.alloc_n<half_t>((size_t)C * 4 * C);
     launch_xattn_out_retile_nk(w1, w1_t, C, 4 * C, ll_.stream);
@@ -576,15 +625,16 @@ Tensor UNet::transformer(std::vector<Op>& ops, const std::string& p, const Tenso
     Tensor t0 = group_norm(ops, p + ".norm", x, nullptr, 1e-6f, false);
     h = conv(ops, p + ".proj_in", t0, {.cout = x.C, .keep_compressed = true});
   }
-  bool tail_done = false;
+  bool tail_done = false, tail_q8 = false;
   const std::string proj_name = p + ".proj_out";
   for (int d = 0; d < depth; ++d) {
     const bool last = d == depth - 1;
     h = transformer_block(ops, p + ".transformer_blocks." + std::to_string(d), h, heads, last ? &proj_name : nullptr, last ? &x : nullptr,
-                          last ? &tail_done : nullptr, (gq && d == 0) ? &pre : nullptr);
+                          last ? &tail_done : nullptr, (gq && d == 0) ? &pre : nullptr, last ? &tail_q8 : nullptr);
   }
   if (tail_done) return h;
-  return conv(ops, p + ".proj_out", h, {.cout = x.C, .res = x.p});
+  // (behind an int8 ff.net.2 a marked proj_out may run pinned as plan tile 19; a GroupNorm over its output then runs its own statistics pass)
+  return conv(ops, p + ".proj_out", h, {.cout = x.C, .res = x.p, .keep_compressed = tail_q8});
 }
 
 // down blocks (unet.py:336-350, :389-403) + mid block (unet.py:789-795)

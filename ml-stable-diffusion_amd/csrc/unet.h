@@ -53,9 +53,10 @@ class UNet : public Net {
   Tensor transformer(std::vector<Op>& ops, const std::string& p, const Tensor& x, int heads, int depth);
   // proj_out / tres (last block of a SpatialTransformer only): the transformer's proj_out and its residual - where the tail
   // ff.net.2 + residual -> proj_out + residual runs as ONE launch (xattn_out.hip ffn_proj_kernel) *tail_done is set and the returned
-  // tensor is the transformer's output.  pre: the block's self-attention operands where the transformer's head launch already wrote them
+  // tensor is the transformer's output.  pre: the block's self-attention operands where the transformer's head launch already wrote them.
+  // *tail_q8 is set where a W8A8-marked ff.net.2 ran un-merged from int8 activations (plan tile 24): proj_out is then a launch of its own
   Tensor transformer_block(std::vector<Op>& ops, const std::string& b, const Tensor& h, int heads, const std::string* proj_out = nullptr,
-                           const Tensor* tres = nullptr, bool* tail_done = nullptr, const PreQkv* pre = nullptr);
+                           const Tensor* tres = nullptr, bool* tail_done = nullptr, const PreQkv* pre = nullptr, bool* tail_q8 = nullptr);
   Tensor attention(std::vector<Op>& ops, const Tensor& q, const half_t* k, const half_t* vt, int heads, int Sq,
                    int Sk, int ldk, int ldv, int ldq, bool vt_perm = false, bool q_prescaled = false);
   // scratch of attention8's balanced form (AttnDesc::sk_part / sk_cnt), shared by this handle's self-attention launches

@@ -186,7 +186,7 @@ inline void wstream_i8_pack(const int8_t* q, int N, int Ctot, int ksize, int8_t*
 // per weight - a (n, tap, 64-channel chunk) row is 64 contiguous bytes, what one DMA lane quartet fetches.  q [N][Ctot][k][k] (the
 // checkpoint's order); dst holds N * Ctot * k * k bytes.
 inline void halo_i8_pack(const int8_t* q, int N, int Ctot, int ksize, int8_t* dst) { retile_ohwi(q, N, Ctot, ksize, false, dst); }
-// The int8 weights of smgemm_i8.hip (plan tile 19): [N][K], the checkpoint's own order of a 1x1 conv / Linear - wave w of a tile
+// The int8 weights of smgemm_i8.hip and smgemm_q8.hip (plan tiles 19 and 24): [N][K], the checkpoint's own order of a 1x1 conv / Linear - wave w of a tile
 // fetches rows 16 w .. 16 w + 15 of a K64 stage as one 1-KB LDS-DMA piece, 16 rows x 64 contiguous bytes, and the swizzle of its LDS
 // image is applied on the source address.  The layout is stated here once: the function is a copy.  N % 16 == 0, K % 64 == 0.
 inline size_t smgemm_i8_bytes(int N, int K) { return (size_t)N * K; }
@@ -220,7 +220,7 @@ struct W8A8HostCopy {
 };
 inline bool w8a8_absmax_ok(float act_absmax) { return std::isfinite(act_absmax) && act_absmax > 0.f; }
 inline W8A8HostCopy w8a8_host_copy(const char* what, const int8_t* q, const float* w_scale, float act_absmax, int N, int Ctot, int ksize,
-                                   WeightSource kind = WeightSource::I8Wstream) {   // one of the five int8 kinds
+                                   WeightSource kind = WeightSource::I8Wstream) {   // one of the six int8 kinds
   SD_REQUIRE(w8a8_absmax_ok(act_absmax), kInvalidArgument, "%s: act_absmax = %g, not a positive finite number", what, (double)act_absmax);
   const size_t n_el = wstream_i8_bytes(N, Ctot, ksize);
   W8A8HostCopy h;
@@ -236,7 +236,7 @@ inline W8A8HostCopy w8a8_host_copy(const char* what, const int8_t* q, const floa
   for (size_t i = 0; i < n_el; ++i) SD_REQUIRE(q[i] != -128, kInvalidArgument, "%s: weight value -128 at element %zu, the symmetric range is [-127, 127]", what, i);
   h.stream.resize(n_el);
   if (kind == WeightSource::I8Halo) halo_i8_pack(q, N, Ctot, ksize, h.stream.data());
-  else if (kind == WeightSource::I8Gemm) smgemm_i8_pack(q, N, Ctot, h.stream.data());   // (ksize 1)
+  else if (kind == WeightSource::I8Gemm || kind == WeightSource::I8GemmQ) smgemm_i8_pack(q, N, Ctot, h.stream.data());   // (ksize 1; tile 24 reads tile 19's layout)
   else if (kind == WeightSource::I8Geglu) smgeglu_i8_pack(q, N, Ctot, h.stream.data());
   else if (kind == WeightSource::I8Qkv) smqkv_i8_pack(q, N, Ctot, h.stream.data());     // (ksize 1; N = 3C stacked rows)
   else wstream_i8_pack(q, N, Ctot, ksize, h.stream.data());

@@ -54,6 +54,9 @@ class WeightStore {
   // ... and over the output of norm1 in front of every fused q|k|v launch plan tile 22 could take (the same two launches)
   void set_observe_qkv(bool on) { observe_qkv_ = on; }
   bool observe_qkv() const { return observe_qkv_; }
+  // ... and over the GEGLU product in front of every ff.net.2 plan tile 24 could take, and over a scratch ff.net.2 output in front of its proj_out
+  void set_observe_tails(bool on) { observe_tails_ = on; }
+  bool observe_tails() const { return observe_tails_; }
   void add(const std::string& name, const void* data, int dtype /*0 f16, 1 f32, 2 bf16*/,
            const int64_t* shape, int ndim);
   void load_safetensors(const std::string& path, const std::string& prefix);
@@ -77,6 +80,7 @@ class WeightStore {
   bool observe_gemms_ = false;
   bool observe_geglus_ = false;
   bool observe_qkv_ = false;
+  bool observe_tails_ = false;
 };
 
 }  // namespace sd

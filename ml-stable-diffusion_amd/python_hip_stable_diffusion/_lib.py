@@ -103,6 +103,7 @@ SYMBOLS = [
     ("sd_weights_observe_gemms", _I, [_P, _I]),
     ("sd_weights_observe_geglus", _I, [_P, _I]),
     ("sd_weights_observe_qkv", _I, [_P, _I]),
+    ("sd_weights_observe_tails", _I, [_P, _I]),
     ("sd_unet_w8a8_info", _I, [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(C.c_size_t)]),
     ("sd_unet_w8a8_layer", _I, [_P, _I, C.c_char_p, _I]),
     ("sd_unet_activation_ranges", _I, [_P, _I, C.c_char_p, _I, _FP]),
@@ -118,6 +119,8 @@ SYMBOLS = [
     ("sd_op_layernorm_q8", _I, [_P, _FP, _FP, _F, _F, _P, _I, _I, _I, _FP]),
     ("sd_op_geglu_w8a8", _I, [_P, _P, _FP, _F, _FP, _P, _I, _I, _I, _I, C.POINTER(_I), _I, _FP]),
     ("sd_op_w8a8_pack_geglu", _I, [_P, _I, _I, _P, C.POINTER(C.c_size_t)]),
+    ("sd_op_geglu_w8a8_q8", _I, [_P, _P, _FP, _F, _FP, _F, _P, _I, _I, _I, _I, C.POINTER(_I), _I, _FP]),
+    ("sd_op_gemm_q8", _I, [_P, _P, _FP, _F, _FP, _P, _P, _I, _I, _I, _I, C.POINTER(_I), _I, _FP]),
     ("sd_op_qkv_w8a8", _I, [_P, _P, _FP, _F, _FP, _P, _P, _I, _I, _I, _F, _I, _I, C.POINTER(_I), _I, _FP]),
     ("sd_op_w8a8_pack_qkv", _I, [_P, _I, _P, C.POINTER(C.c_size_t)]),
     ("sd_op_quantize_weight", _I, [_FP, _I, C.c_size_t, _P, _FP, C.POINTER(C.c_double)]),
@@ -715,11 +718,13 @@ def layernorm_q8(x, ln_weight, ln_bias, act_absmax, eps=1e-5, out=None, iters=1)
     return out.reshape(-1)[:M * Cc].reshape(M, Cc), ms.value
 
 
-def geglu_w8a8(xq, wq, w_scale, act_absmax, bias=None, bm=0, out=None, iters=1):
+def geglu_w8a8(xq, wq, w_scale, act_absmax, bias=None, bm=0, out=None, iters=1, out_absmax=None):
     """The GEGLU projection in W8A8 (sd_op_geglu_w8a8, plan tile 20): xq (M, C) int8, wq (N2, C) int8 in the checkpoint's row order
     [values | gates], w_scale (N2,) f32, act_absmax the range xq was quantized with, bias (N2,) f32 or None; bm 0 / 128 / 256 = the tile
     height (0: by the grid).  ``out``: a C-contiguous float16 buffer of at least M * N2 / 2 elements (tests put guards behind it).  What
-    the library checks it refuses itself (ValueError, no GPU needed).  Returns (out (M, N2 / 2), plan, ms)."""
+    the library checks it refuses itself (ValueError, no GPU needed).  Returns (out (M, N2 / 2), plan, ms).
+    With ``out_absmax`` (sd_op_geglu_w8a8_q8) the product leaves as int8, quantized with that range: ``out`` is then an int8 buffer and
+    the first result (M, N2 / 2) int8 - the activations of ``gemm_q8``."""
     xq = np.ascontiguousarray(xq, dtype=np.int8)
     wq = np.ascontiguousarray(wq, dtype=np.int8)
     w_scale = f32(w_scale)
@@ -731,14 +736,48 @@ def geglu_w8a8(xq, wq, w_scale, act_absmax, bias=None, bm=0, out=None, iters=1):
     if bias is not None and bias.shape != (N2,):
         raise ValueError("geglu_w8a8: bias must be (N2,)")
     n = M * (N2 // 2)
+    dtype = np.float16 if out_absmax is None else np.int8
+    if out is None:
+        out = np.empty(n, dtype)
+    if out.dtype != dtype or not out.flags.c_contiguous or out.size < n:
+        raise ValueError("geglu_w8a8: out must be a C-contiguous float16 (with out_absmax: int8) buffer of at least M * N2 / 2 elements")
+    plan = (C.c_int * 4)()
+    ms = C.c_float(0)
+    if out_absmax is None:
+        check(lib().sd_op_geglu_w8a8(ptr(xq), ptr(wq), fptr(w_scale), float(act_absmax), fptr(bias), ptr(out), M, Cc, N2, bm, plan, iters, C.byref(ms)))
+    else:
+        check(lib().sd_op_geglu_w8a8_q8(ptr(xq), ptr(wq), fptr(w_scale), float(act_absmax), fptr(bias), float(out_absmax), ptr(out), M, Cc, N2, bm,
+                                        plan, iters, C.byref(ms)))
+    return out.reshape(-1)[:n].reshape(M, N2 // 2), list(plan), ms.value
+
+
+def gemm_q8(xq, wq, w_scale, act_absmax, bias=None, res=None, bm=0, out=None, iters=1):
+    """The small-M 1x1 GEMM from int8 weights and int8 activations (sd_op_gemm_q8, plan tile 24), token-major: xq (M, K) int8, wq (N, K)
+    int8, w_scale (N,) f32, act_absmax the range xq was quantized with, bias (N,) f32 / res (M, N) float16 or None; bm 0 / 32 / 64 = the
+    tile height (0: by M).  ``out``: a C-contiguous float16 buffer of at least M * N elements (tests put guards behind it).  What the
+    library checks - bm, shape, the int32 bound, act_absmax, w_scale, a weight or an activation of -128 - it refuses itself (ValueError,
+    no GPU needed).  Returns (out (M, N), plan, ms)."""
+    xq = np.ascontiguousarray(xq, dtype=np.int8)
+    wq = np.ascontiguousarray(wq, dtype=np.int8)
+    w_scale = f32(w_scale)
+    if xq.ndim != 2 or wq.ndim != 2 or wq.shape[1] != xq.shape[1] or w_scale.shape != (wq.shape[0],):
+        raise ValueError("gemm_q8: xq must be (M, K), wq (N, K) and w_scale (N,)")
+    M, K = xq.shape
+    N = wq.shape[0]
+    bias = None if bias is None else f32(bias)
+    res = None if res is None else f16(res)
+    if (bias is not None and bias.shape != (N,)) or (res is not None and res.shape != (M, N)):
+        raise ValueError("gemm_q8: bias must be (N,), res (M, N)")
+    n = M * N
     if out is None:
         out = np.empty(n, np.float16)
     if out.dtype != np.float16 or not out.flags.c_contiguous or out.size < n:
-        raise ValueError("geglu_w8a8: out must be a C-contiguous float16 buffer of at least M * N2 / 2 elements")
+        raise ValueError("gemm_q8: out must be a C-contiguous float16 buffer of at least M * N elements")
     plan = (C.c_int * 4)()
     ms = C.c_float(0)
-    check(lib().sd_op_geglu_w8a8(ptr(xq), ptr(wq), fptr(w_scale), float(act_absmax), fptr(bias), ptr(out), M, Cc, N2, bm, plan, iters, C.byref(ms)))
-    return out.reshape(-1)[:n].reshape(M, N2 // 2), list(plan), ms.value
+    check(lib().sd_op_gemm_q8(ptr(xq), ptr(wq), fptr(w_scale), float(act_absmax), fptr(bias), ptr(res), ptr(out), M, K, N, bm, plan, iters,
+                              C.byref(ms)))
+    return out.reshape(-1)[:n].reshape(M, N), list(plan), ms.value
 
 
 def w8a8_pack_geglu(wq):

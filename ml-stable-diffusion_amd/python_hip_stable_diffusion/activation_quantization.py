@@ -15,7 +15,10 @@ writes ``int8(norm3(x))``, the tensor the reference calibrates, and the GEGLU re
 writes ``int8(norm1(x))`` - when all three are named with the same range, which is what ``observe_activations="attn"`` reports; every
 other marked conv stays fp16 - the reference's skipped layers: one or two of the three q|k|v tensors or three different ranges, the
 8x8 mid block's and the 320-channel level's q|k|v, ``attn2.to_q`` (inside the fused cross-attention launch), the prompt-side
-``attn2.to_k`` / ``to_v``, the merged transformer tail, ``conv_shortcut`` s and stride-2 convs.  Parity with coremltools' quantizer is NOT pinned
+``attn2.to_k`` / ``to_v``, ``conv_shortcut`` s and stride-2 convs.  The tail of a transformer block of those levels: a marked ``ff.net.2``
+is not merged with ``proj_out`` - it runs from int8 on the GEGLU product (``smgemm_q8.hip``, plan tile 24), which the int8 GEGLU writes as
+int8 itself (no fp16 product exists; behind an fp16 GEGLU one quantizer launch writes it), and a marked ``proj_out`` then runs as plan
+tile 19; with ``ff.net.2`` unmarked the merged fp16 launch stays and a marked ``proj_out`` is skipped.  Parity with coremltools' quantizer is NOT pinned
 (coremltools is not a dependency of this project): the scales are plain absmax / 127, not the result of its calibration.
 
 Calibration happens on the device: ``HipModel(..., observe_activations=True)`` puts an absmax observer in front of every conv
@@ -23,7 +26,8 @@ the int8 weight stream could take, ``observe_activations="all"`` in front of eve
 the projections plan tile 19 could take, ``observe_activations="geglu"`` also over the output of ``norm3`` in front of every GEGLU
 projection plan tile 20 could take (a LayerNorm and an absmax launch beside the folded fp16 GEGLU, whose output does not change),
 ``observe_activations="attn"`` also over the output of ``norm1`` in front of every fused q|k|v launch plan tile 22 could take (the same
-two launches; the one range is reported under ``attn1.to_q``, ``to_k`` and ``to_v``) -
+two launches; the one range is reported under ``attn1.to_q``, ``to_k`` and ``to_v``), ``observe_activations="tail"`` also over the GEGLU
+product in front of every ``ff.net.2`` plan tile 24 could take and over a scratch ``ff.net.2`` output in front of its ``proj_out`` -
 every layer that could run from int8; after any number of forwards ``.activation_ranges()`` is the recipe's raw material.
 
 A recipe is JSON ``{layer: act_absmax}``, ``layer`` the conv's module name (its weight tensor without ``.weight``).
@@ -45,9 +49,18 @@ CALIBRATION_SCOPES = {"stream": True, "all": "all", "gemm": "gemm", "geglu": "ge
 ATTENTION_SCOPES = {"attn": "attn"}
 
 
+# ... and "tail" observes what "attn" does plus the transformer tails: the GEGLU product ff.net.2 reads and the input of proj_out
+TAIL_SCOPES = {"tail": "tail"}
+
+
 def calibration_scopes():
-    """every ``--calibrate-scope`` -> ``observe_activations``, in the order each adds to the one before"""
+    """the ``--calibrate-scope`` -> ``observe_activations`` up to "attn", in the order each adds to the one before"""
     return {**CALIBRATION_SCOPES, **ATTENTION_SCOPES}
+
+
+def all_calibration_scopes():
+    """every ``--calibrate-scope`` -> ``observe_activations``, in the order each adds to the one before: what the CLI offers"""
+    return {**calibration_scopes(), **TAIL_SCOPES}
 
 
 def layer_of(tensor_name):

@@ -202,11 +202,13 @@ class Weights(_lib.Handle):
         ``"gemm"`` also in front of the plain 1x1 projections the int8 small-M GEMM could take (plan tile 19), ``"geglu"`` also over
         the LayerNorm output in front of every GEGLU projection the int8 GEGLU kernel could take (plan tile 20), ``"attn"`` also over
         the output of ``norm1`` in front of every fused q|k|v launch the int8 q|k|v kernel could take (plan tile 22; one range,
-        reported under ``attn1.to_q``, ``to_k`` and ``to_v``)."""
+        reported under ``attn1.to_q``, ``to_k`` and ``to_v``), ``"tail"`` also over the GEGLU product in front of every ``ff.net.2``
+        the int8-activation GEMM could take (plan tile 24) and over a scratch ``ff.net.2`` output in front of its ``proj_out``."""
         _lib.check(_lib.lib().sd_weights_observe_activations(self._h, observe_level(on)))
-        _lib.check(_lib.lib().sd_weights_observe_gemms(self._h, int(on in ("gemm", "geglu", "attn"))))
-        _lib.check(_lib.lib().sd_weights_observe_geglus(self._h, int(on in ("geglu", "attn"))))
-        _lib.check(_lib.lib().sd_weights_observe_qkv(self._h, int(on == "attn")))
+        _lib.check(_lib.lib().sd_weights_observe_gemms(self._h, int(on in ("gemm", "geglu", "attn", "tail"))))
+        _lib.check(_lib.lib().sd_weights_observe_geglus(self._h, int(on in ("geglu", "attn", "tail"))))
+        _lib.check(_lib.lib().sd_weights_observe_qkv(self._h, int(on in ("attn", "tail"))))
+        _lib.check(_lib.lib().sd_weights_observe_tails(self._h, int(on == "tail")))
 
     @classmethod
     @contextlib.contextmanager
@@ -226,10 +228,11 @@ class Weights(_lib.Handle):
 def observe_level(on):
     """observe_activations as the level of sd_weights_observe_activations: False 0, True 1, "all" 2; "gemm" is level 2 with the
     projections' flag (sd_weights_observe_gemms) beside it, "geglu" level 2 with that flag and the GEGLUs' (sd_weights_observe_geglus),
-    "attn" level 2 with those two and the self-attention q|k|v launches' (sd_weights_observe_qkv)."""
+    "attn" level 2 with those two and the self-attention q|k|v launches' (sd_weights_observe_qkv), "tail" level 2 with those three and
+    the transformer tails' (sd_weights_observe_tails)."""
     if isinstance(on, str):
-        if on not in ("all", "gemm", "geglu", "attn"):
-            raise ValueError(f"observe_activations must be False, True, 'all', 'gemm', 'geglu' or 'attn', got {on!r}")
+        if on not in ("all", "gemm", "geglu", "attn", "tail"):
+            raise ValueError(f"observe_activations must be False, True, 'all', 'gemm', 'geglu', 'attn' or 'tail', got {on!r}")
         return 2
     return int(bool(on))
 

@@ -811,17 +811,19 @@ def build_parser():
                              "from int8 weights and activations where their kernel is the weight stream, the 3x3 halo conv or - for the plain 1x1 "
                              "projections proj_in / attn1.to_out.0 / attn2.to_out.0 of the 640- and 1280-channel levels - the small-M GEMM, "
                              "or - for their ff.net.0.proj - the GEGLU kernel behind a LayerNorm that writes int8, or - for their attn1.to_q / "
-                             "to_k / to_v, all three named with one range - the fused q|k|v launch behind such a LayerNorm")
+                             "to_k / to_v, all three named with one range - the fused q|k|v launch behind such a LayerNorm, or - for their "
+                             "ff.net.2 - the int8-activation GEMM behind the GEGLU, un-merged from proj_out, which then runs on its own")
     parser.add_argument("--calibrate-activations", default=None,                                 # activation_quantization.py --generate-calibration-data
                         help="Run the requested generation on a UNet that records the range of every quantizable conv's input and write "
                              "the W8A8 recipe to this file")
-    from .activation_quantization import calibration_scopes   # CALIBRATION_SCOPES and the scopes added since
-    parser.add_argument("--calibrate-scope", default="stream", choices=tuple(calibration_scopes()),
+    from .activation_quantization import all_calibration_scopes   # CALIBRATION_SCOPES and the scopes added since
+    parser.add_argument("--calibrate-scope", default="stream", choices=tuple(all_calibration_scopes()),
                         help="Which convs --calibrate-activations observes: 'stream' = those the int8 weight stream takes (the 8x8 level), "
                              "'all' = also every 3x3 / stride-1 conv the int8 halo conv takes, 'gemm' = also the plain 1x1 projections the "
                              "int8 small-M GEMM takes, 'geglu' = also the GEGLU projections ff.net.0.proj the int8 GEGLU kernel takes (the "
                              "output of their norm3), 'attn' = also the self-attention projections attn1.to_q / to_k / to_v the int8 q|k|v "
-                             "kernel takes (the output of their norm1: one range under the three names)")
+                             "kernel takes (the output of their norm1: one range under the three names), 'tail' = also ff.net.2 and proj_out of "
+                             "the transformer tails the int8-activation GEMM takes (the GEGLU product and ff.net.2's output)")
     return parser
 
 
@@ -842,7 +844,7 @@ def main(args):
         from .palettize import load_recipe
         recipe = load_recipe(args.pre_analysis_json_path, args.selected_recipe)
     aq_recipe, calibrate = getattr(args, "activation_quantization_recipe", None), getattr(args, "calibrate_activations", None)
-    from .activation_quantization import calibration_scopes
+    from .activation_quantization import all_calibration_scopes
     if aq_recipe and calibrate:
         raise ValueError("--calibrate-activations writes a recipe from the fp16 model; it does not go with --activation-quantization-recipe")
     pipe = get_hip_pipe(args.i, args.model_version, args.compute_unit, scheduler_override=scheduler,
@@ -852,7 +854,7 @@ def main(args):
                         disable_safety=getattr(args, "disable_safety", False), vae_encoder=bool(getattr(args, "image", None)),
                         quantize_nbits=getattr(args, "quantize_nbits", None), palettization_recipe=recipe,
                         device_postprocess=getattr(args, "device_postprocess", False), activation_quantization=aq_recipe,
-                        observe_activations=calibration_scopes()[getattr(args, "calibrate_scope", "stream")] if calibrate else False)
+                        observe_activations=all_calibration_scopes()[getattr(args, "calibrate_scope", "stream")] if calibrate else False)
     controlnet_cond = None
     if args.controlnet:
         controlnet_cond = [prepare_controlnet_cond(args.controlnet_inputs[i], pipe.height, pipe.width)
