@@ -62,6 +62,11 @@ int sd_weights_load_safetensors(sd_weights* w, const char* path, const char* pre
 int sd_weights_count(const sd_weights* w);
 /* tensor `index` (0 .. count - 1, in name order): its name (NUL-terminated, cut to name_bytes) and shape (at most 8 dims) */
 int sd_weights_tensor_info(const sd_weights* w, int index, char* name, int name_bytes, int64_t* shape8, int* ndim);
+/* Overwrites the values of the existing tensor `name` in place (SD_ERR_NOT_FOUND when absent; n must be its element count, else
+ * SD_ERR_INVALID_ARGUMENT).  A palette or W8A8 mark on the tensor is dropped: it is then a plain tensor holding `values`.  Host only.
+ * With sd_unet_reload_weights this is what replaces the reference's in-place `module.weight.data = ...` of its compression searches
+ * (mixed_bit_compression_pre_analysis.py:139-156 fake_palettize, :158-178 simulate_quant_fn and its restore). */
+int sd_weights_set_values(sd_weights* w, const char* name, const float* values, size_t n);
 void sd_weights_destroy(sd_weights* w);
 /* Palettized weights: the reference's conversion-time compression (torch2coreml.py:182-229 --quantize-nbits,
  * mixed_bit_compression_apply.py) with the semantics of its fake_palettize at one group per tensor
@@ -180,6 +185,19 @@ int sd_unet_create(const sd_unet_config* cfg, const sd_weights* w, int device, s
 /* ManagedMLModel.unloadResources (ManagedMLModel.swift:49-52) */
 void sd_unet_destroy(sd_unet* u);
 int sd_unet_set_attention(sd_unet* u, int impl);
+/* Swap the values of named tensors in a live UNet / ControlNet handle - what the reference does by assigning to a torch module's
+ * weight between two pipeline calls (mixed_bit_compression_pre_analysis.py:139-178, :206-262).  `w` is a complete store that differs
+ * from the store `u` last took its weights from only in the VALUES of the `n_names` tensors `names`.  Afterwards `u` computes bit
+ * for bit what a handle freshly created from `w` with the same configuration computes, eagerly and on replay of the graphs it has
+ * captured: every folded, stacked, merged and fragment-major device copy made from a named tensor is made again, into the same
+ * addresses; nothing is re-captured or allocated (sd_unet_arena_used_bytes / sd_unet_device_bytes do not move); the hoisted
+ * cross-attention K / V^T of the current prompt and a ControlNet's conditioning embedding are recomputed.  Only values are read (for
+ * a palettized tensor lut[indices]): which kernel a layer runs and the form the handle holds a tensor in do not change.
+ * Everything is checked before the first device write, so a refused call leaves the handle computing exactly what it did:
+ * SD_ERR_NOT_FOUND a name `w` does not hold; SD_ERR_INVALID_ARGUMENT a tensor whose shape differs from the one the handle was built
+ * with; SD_ERR_UNSUPPORTED a named tensor the handle holds compressed on the device (a palette stream, int8 - the message names it),
+ * a VAE handle, a handle built from an observing store.  A name the handle reads nowhere is accepted and changes nothing. */
+int sd_unet_reload_weights(sd_unet* u, const sd_weights* w, const char* const* names, int n_names);
 int sd_unet_num_residuals(const sd_unet* u); /* controlnet.py:191-197 */
 /* bytes of HBM held by the handle (weights + activations) */
 size_t sd_unet_device_bytes(const sd_unet* u);

@@ -174,12 +174,31 @@ int sd_weights_observe_tails(sd_weights* w, int on) {
     w->store.set_observe_tails(on != 0);
   });
 }
+int sd_weights_set_values(sd_weights* w, const char* name, const float* values, size_t n) {
+  return guarded([&] {
+    SD_REQUIRE(w && name && values, kInvalidArgument, "NULL argument");
+    w->store.set_values(name, values, n);
+  });
+}
 void sd_weights_destroy(sd_weights* w) { delete w; }
 
 int sd_unet_create(const sd_unet_config* cfg, const sd_weights* w, int device, sd_unet** out) {
   return guarded([&] { create_handle(cfg, w, device, out); });
 }
 void sd_unet_destroy(sd_unet* u) { delete u; }
+int sd_unet_reload_weights(sd_unet* u, const sd_weights* w, const char* const* names, int n_names) {
+  return guarded([&] {
+    SD_REQUIRE(u && w && n_names >= 0 && (n_names == 0 || names), kInvalidArgument, "NULL argument");
+    require_idle(u, "sd_unet_reload_weights");
+    SD_REQUIRE(dynamic_cast<UNet*>(u->impl.get()), kUnsupported, "sd_unet_reload_weights takes a UNet or ControlNet handle, not a VAE");
+    std::vector<std::string> v;
+    for (int i = 0; i < n_names; ++i) {
+      SD_REQUIRE(names[i], kInvalidArgument, "names[%d] is NULL", i);
+      v.emplace_back(names[i]);
+    }
+    u->impl->reload_weights(w->store, v);
+  });
+}
 int sd_unet_set_attention(sd_unet* u, int impl) {
   return guarded([&] {
     SD_REQUIRE(u, kInvalidArgument, "NULL handle");

@@ -14,7 +14,8 @@
 namespace sd {
 
 Net::Net(const sd_unet_config& cfg, const WeightStore& ws, int device)
-    : cfg_(cfg), ws_(&ws), f32_(cfg.compute_fp32 != 0), pal_tensors_((int)ws.palettes()), i8_marked_((int)ws.w8a8_marks()) {
+    : cfg_(cfg), ws_(&ws), f32_(cfg.compute_fp32 != 0), pal_tensors_((int)ws.palettes()), i8_marked_((int)ws.w8a8_marks()),
+      observing_(ws.observe() != 0) {
   SD_REQUIRE(cfg.n_levels >= 1 && cfg.n_levels <= SD_MAX_LEVELS, kInvalidArgument, "n_levels=%d", cfg.n_levels);
   SD_REQUIRE(cfg.batch >= 1 && cfg.height >= 1 && cfg.width >= 1, kInvalidArgument, "bad batch/size");
   SD_REQUIRE(cfg.norm_num_groups >= 1 && cfg.norm_num_groups <= 64, kUnsupported, "norm_num_groups=%d",
@@ -41,51 +42,103 @@ Tensor Net::new_tensor(int B, int H, int W, int C) {
 // unet.py:613-617): rows re-ordered so value/gate channels interleave in blocks of 32 and the
 // GEMM epilogue can multiply them in registers.
 half_t* Net::upload_conv_weight(const std::string& name, int cout, int cin, int k, bool geglu) {
-  const HostTensor& t = ws_->get(name + ".weight");
   const size_t expect = (size_t)cout * cin * k * k;
-  SD_REQUIRE(t.numel() == expect, kInvalidArgument, "%s.weight has %zu elements, expected %zu (%d,%d,%d,%d)",
-             name.c_str(), t.numel(), expect, cout, cin, k, k);
-  std::vector<half_t> host(expect);
-  retile_ohwi(t.data.data(), cout, cin, k, geglu, host.data());
   half_t* d = ll_.arena.alloc_n<half_t>(expect);
-  SD_HIP(hipMemcpy(d, host.data(), expect * sizeof(half_t), hipMemcpyHostToDevice));
+  refill({name + ".weight"}, d, [=](const WeightStore& ws) {
+    const HostTensor& t = ws.get(name + ".weight");
+    SD_REQUIRE(t.numel() == expect, kInvalidArgument, "%s.weight has %zu elements, expected %zu (%d,%d,%d,%d)",
+               name.c_str(), t.numel(), expect, cout, cin, k, k);
+    std::vector<half_t> host(expect);
+    retile_ohwi(t.data.data(), cout, cin, k, geglu, host.data());
+    SD_HIP(hipMemcpy(d, host.data(), expect * sizeof(half_t), hipMemcpyHostToDevice));
+  });
   return d;
 }
 
 // an upsampler's (Cout, Cin, 3, 3) tensor folded into the four 2x2 phase matrices of plan tile 21, [4][Cout][4][Cin] fp16 (subpixel_fold)
 half_t* Net::upload_subpixel_weight(const std::string& name, int cout, int cin) {
-  const HostTensor& t = ws_->get(name + ".weight");
   const size_t expect = (size_t)cout * cin * 9;
-  SD_REQUIRE(t.numel() == expect, kInvalidArgument, "%s.weight has %zu elements, expected %zu (%d,%d,3,3)", name.c_str(), t.numel(), expect, cout, cin);
-  std::vector<half_t> host(subpixel_fold_halves(cout, cin));
-  subpixel_fold(t.data.data(), cout, cin, host.data());
-  half_t* d = ll_.arena.alloc_n<half_t>(host.size());
-  SD_HIP(hipMemcpy(d, host.data(), host.size() * sizeof(half_t), hipMemcpyHostToDevice));
+  half_t* d = ll_.arena.alloc_n<half_t>(subpixel_fold_halves(cout, cin));
+  refill({name + ".weight"}, d, [=](const WeightStore& ws) {
+    const HostTensor& t = ws.get(name + ".weight");
+    SD_REQUIRE(t.numel() == expect, kInvalidArgument, "%s.weight has %zu elements, expected %zu (%d,%d,3,3)", name.c_str(), t.numel(), expect, cout, cin);
+    std::vector<half_t> host(subpixel_fold_halves(cout, cin));
+    subpixel_fold(t.data.data(), cout, cin, host.data());
+    SD_HIP(hipMemcpy(d, host.data(), host.size() * sizeof(half_t), hipMemcpyHostToDevice));
+  });
   return d;
 }
 
 // the same tensor in the same [Cout][k][k][Cin] layout, kept fp32: what the convs of a compute_fp32 handle read (ConvF32Desc::w_kind 1)
 float* Net::upload_conv_weight_f32(const std::string& name, int cout, int cin, int k) {
-  const HostTensor& t = ws_->get(name + ".weight");
   const size_t expect = (size_t)cout * cin * k * k;
-  SD_REQUIRE(t.numel() == expect, kInvalidArgument, "%s.weight has %zu elements, expected %zu (%d,%d,%d,%d)", name.c_str(), t.numel(), expect,
-             cout, cin, k, k);
-  std::vector<float> host(expect);
-  retile_ohwi(t.data.data(), cout, cin, k, false, host.data());
   float* d = ll_.arena.alloc_n<float>(expect);
-  SD_HIP(hipMemcpy(d, host.data(), expect * sizeof(float), hipMemcpyHostToDevice));
+  refill({name + ".weight"}, d, [=](const WeightStore& ws) {
+    const HostTensor& t = ws.get(name + ".weight");
+    SD_REQUIRE(t.numel() == expect, kInvalidArgument, "%s.weight has %zu elements, expected %zu (%d,%d,%d,%d)", name.c_str(), t.numel(), expect,
+               cout, cin, k, k);
+    std::vector<float> host(expect);
+    retile_ohwi(t.data.data(), cout, cin, k, false, host.data());
+    SD_HIP(hipMemcpy(d, host.data(), expect * sizeof(float), hipMemcpyHostToDevice));
+  });
   return d;
 }
 
 float* Net::upload_vec(const std::string& name, int n, bool geglu) {
-  const HostTensor& t = ws_->get(name);
-  SD_REQUIRE((int)t.numel() == n, kInvalidArgument, "%s has %zu elements, expected %d", name.c_str(), t.numel(), n);
-  std::vector<float> host(t.data);
-  if (geglu)
-    for (int o = 0; o < n; ++o) host[geglu_row(o, n)] = t.data[o];
+  SD_REQUIRE((int)ws_->get(name).numel() == n, kInvalidArgument, "%s has %zu elements, expected %d", name.c_str(), ws_->get(name).numel(), n);
   float* d = ll_.arena.alloc_n<float>(n);
-  SD_HIP(hipMemcpy(d, host.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+  refill({name}, d, [=](const WeightStore& ws) {
+    const HostTensor& t = ws.get(name);
+    SD_REQUIRE((int)t.numel() == n, kInvalidArgument, "%s has %zu elements, expected %d", name.c_str(), t.numel(), n);
+    std::vector<float> host(t.data);
+    if (geglu)
+      for (int o = 0; o < n; ++o) host[geglu_row(o, n)] = t.data[o];
+    SD_HIP(hipMemcpy(d, host.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+  });
   return d;
+}
+
+// ---- refill records ----------------------------------------------------------------------------
+void Net::refill(const std::vector<std::string>& sources, const void* made, Fill fill) {
+  for (const std::string& s : sources) source_shape_[s] = ws_->get(s).shape;
+  fill(*ws_);
+  if (made) made_from_[made] = sources;
+  refills_.push_back({sources, std::move(fill)});
+}
+
+void Net::derive(const void* from, std::function<void()> launch) {
+  auto it = made_from_.find(from);
+  SD_REQUIRE(it != made_from_.end(), kInternal, "a derived weight copy of a matrix no refill record made");
+  launch();
+  refills_.push_back({it->second, [launch](const WeightStore&) { launch(); }});
+}
+
+// Order: everything about every name and every record that will run is checked first; then the stream is drained, the records run
+// in build order (a blocking copy, then the launches that read it, on the handle's stream), and the stream is drained again.
+void Net::reload_weights(const WeightStore& ws, const std::vector<std::string>& names) {
+  SD_REQUIRE(!observing_, kUnsupported, "reload_weights: the handle was built from an observing store (its observers' ranges belong to the weights it was built with)");
+  const std::set<std::string> wanted(names.begin(), names.end());
+  for (const std::string& n : wanted) {
+    const HostTensor* t = ws.find(n);
+    if (!t) fail(kNotFound, "reload_weights: the store has no tensor '%s'", n.c_str());
+    SD_REQUIRE(!compressed_.count(n), kUnsupported, "reload_weights: the handle holds '%s' compressed on the device (a palette stream or int8); only fp16 / fp32 tensors reload",
+               n.c_str());
+  }
+  std::vector<const Refill*> run;
+  for (const Refill& r : refills_)
+    if (std::any_of(r.sources.begin(), r.sources.end(), [&](const std::string& s) { return wanted.count(s) != 0; })) run.push_back(&r);
+  for (const Refill* r : run)
+    for (const std::string& s : r->sources) {   // a record reads all its sources again: each must be there, in the shape it was built with
+      const HostTensor* t = ws.find(s);
+      if (!t) fail(kNotFound, "reload_weights: the store has no tensor '%s' (read together with a named one)", s.c_str());
+      SD_REQUIRE(t->shape == source_shape_.at(s), kInvalidArgument, "reload_weights: '%s' has another shape than the tensor the handle was built with", s.c_str());
+    }
+  if (run.empty()) return;
+  SD_HIP(hipSetDevice(ll_.device));
+  SD_HIP(hipStreamSynchronize(ll_.stream));
+  for (const Refill* r : run) r->fill(ws);
+  after_reload();
+  SD_HIP(hipStreamSynchronize(ll_.stream));
 }
 
 namespace {
@@ -228,7 +281,7 @@ ConvWeights Net::upload_qkv_i8(const std::vector<std::string>& parts, const Weig
                                            (int)parts.size() * cout_each, cin, 1, &bytes);
   i8_applied_ += (int)parts.size();
   i8_bytes_ += bytes;
-  for (const std::string& p : parts) i8_names_.push_back(p + ".weight");
+  for (const std::string& p : parts) i8_names_.push_back(p + ".weight"), holds_compressed(p + ".weight");
   return ConvWeights(cw, pin);
 }
 
@@ -263,6 +316,7 @@ ConvWeights Net::upload_compressed(const std::string& name, const WeightPin& pin
     ++pal_streamed_;
     pal_stream_bytes_ += bytes;
   }
+  holds_compressed(wname);
   return ConvWeights(cw, pin);
 }
 
@@ -395,17 +449,18 @@ Tensor Net::conv_w(std::vector<Op>& ops, const std::string& name, const ConvWeig
     const ConvWeightCopies copies = d.cw.kind != WeightSource::Fp16 ? ConvWeightCopies{false, false, false} : conv_plan_copies(d);
     if (copies.wstream && !ln) {   // small-M layers: the weight-streaming kernel (plan tile 9; never a LayerNorm-fold / q|k|v op)
       half_t* wt = ll_.arena.alloc_n<half_t>(wstream_tiled_halves(cout, cin, k));
-      launch_wstream_retile(w, wt, cout, cin, k, ll_.stream);
+      derive(w, [=] { launch_wstream_retile(w, wt, cout, cin, k, ll_.stream); });
       d.w_tiled = wt;
     }
     if (copies.wsgemm) {    // widest-M GEGLU projection (K = 320): the weight-stationary kernel (wsgemm.hip, plan tile 10)
       half_t* wt = ll_.arena.alloc_n<half_t>(wsgemm_tiled_halves(cout));
-      launch_wsgemm_retile(w, wt, cout, geglu, ll_.stream);
+      derive(w, [=] { launch_wsgemm_retile(w, wt, cout, geglu, ll_.stream); });
       d.w_ws = wt;
     }
     if (copies.bvgemm) {    // large-M 1x1 GEMMs: weights global -> VGPR (bvgemm.hip, plan tile 11)
       half_t* wt = ll_.arena.alloc_n<half_t>(bvgemm_tiled_halves(cout, x.C));
-      launch_bvgemm_retile(w, wt, cout, x.C, geglu, ll_.stream);
+      const int c0 = x.C;
+      derive(w, [=] { launch_bvgemm_retile(w, wt, cout, c0, geglu, ll_.stream); });
       d.w_bv = wt;
     }
     ll_.ws_need = std::max(ll_.ws_need, conv_workspace_bytes(d));

@@ -6,6 +6,10 @@
 #include "conv_plan.h"
 #include "launch_list.h"
 
+#include <functional>
+#include <map>
+#include <set>
+
 namespace sd {
 
 constexpr int kTembCap = 65536;      // floats per batch row for the batched time_emb_proj outputs
@@ -132,6 +136,9 @@ class Net {
   int activation_range(int index, std::string* name, float* absmax);
   const std::vector<std::string>& w8a8_applied() const { return i8_names_; }   // weight tensors of the convs that run from int8, in build order
   const sd_unet_config& config() const { return cfg_; }
+  // Swap the values of the tensors `names` for those `ws` holds (sd_unet_reload_weights): every refill record whose sources meet
+  // `names` runs again, into the addresses it filled at build time.  Everything is checked before the first byte is overwritten.
+  virtual void reload_weights(const WeightStore& ws, const std::vector<std::string>& names);
 
  protected:
   Net(const sd_unet_config& cfg, const WeightStore& ws, int device);   // checks the shared config fields, then open()
@@ -182,6 +189,17 @@ class Net {
   // temb: this resnet's row of time_emb_proj outputs (the UNet registers it), null without a time embedding (VAE)
   Tensor resnet(std::vector<Op>& ops, const std::string& p, const Tensor& x, const Tensor* x2, int cout, const float* temb);
 
+  // ---- refill records (host only, outside the arena) ----
+  // Every upload site states its layout ONCE, as a closure from a weight store to the device addresses it allocated: `refill` runs
+  // it on the store the handle is built from and keeps it with the names of the tensors it reads, reload_weights runs it again on
+  // another store.  `made` (may be null) is the device matrix the closure writes: a derived copy made from it by a device launch
+  // (`derive`: the fragment-major retiles) then follows the same sources.
+  using Fill = std::function<void(const WeightStore&)>;
+  void refill(const std::vector<std::string>& sources, const void* made, Fill fill);
+  void derive(const void* from, std::function<void()> launch);
+  void holds_compressed(const std::string& wname) { compressed_.insert(wname); }
+  virtual void after_reload() {}   // what a handle caches between calls from weights and inputs (the UNet's hoisted K / V^T)
+
   // ---- run ----
   void run_ops(const std::vector<Op>& ops) { run_ops_on(ops, ll_.stream); }
   void run_ops_on(const std::vector<Op>& ops, hipStream_t s);
@@ -206,6 +224,15 @@ class Net {
   size_t i8_bytes_ = 0;
   std::vector<std::pair<std::string, float*>> observed_;
   std::vector<std::string> i8_names_;
+  struct Refill {
+    std::vector<std::string> sources;
+    Fill fill;
+  };
+  std::vector<Refill> refills_;                                   // in build order: a derived copy behind the matrix it reads
+  std::map<std::string, std::vector<int64_t>> source_shape_;      // every tensor a record reads, as the handle was built with it
+  std::map<const void*, std::vector<std::string>> made_from_;     // device matrix -> the tensors it was made from
+  std::set<std::string> compressed_;                              // tensors held as a palette stream or int8: no fp16 / fp32 form to refill
+  bool observing_ = false;                                        // built from an observing store
   Tensor conv_f32(std::vector<Op>& ops, const std::string& name, const Tensor& x, const ConvArgs& a);
   Tensor group_norm_f32(std::vector<Op>& ops, const std::string& name, const Tensor& x, float eps, bool silu);
 };

@@ -69,14 +69,18 @@ UNet::~UNet() {
 // (attn1.to_q | attn1.to_k, unet.py:93-95): fewer launches, bigger N, same arithmetic.
 Tensor UNet::conv_stacked(std::vector<Op>& ops, const std::vector<std::string>& names, const Tensor& x, int cout_each) {
   const int cin = x.C, n = (int)names.size();
-  std::vector<half_t> host((size_t)n * cout_each * cin);
-  for (int i = 0; i < n; ++i) {
-    const HostTensor& t = ws_->get(names[i] + ".weight");
-    SD_REQUIRE(t.numel() == (size_t)cout_each * cin, kInvalidArgument, "%s.weight: bad shape", names[i].c_str());
-    for (size_t j = 0; j < t.numel(); ++j) host[(size_t)i * cout_each * cin + j] = (half_t)t.data[j];
-  }
-  half_t* d = ll_.arena.alloc_n<half_t>(host.size());
-  SD_HIP(hipMemcpy(d, host.data(), host.size() * sizeof(half_t), hipMemcpyHostToDevice));
+  std::vector<std::string> sources;
+  for (const std::string& nm : names) sources.push_back(nm + ".weight");
+  half_t* d = ll_.arena.alloc_n<half_t>((size_t)n * cout_each * cin);
+  refill(sources, d, [=](const WeightStore& ws) {
+    std::vector<half_t> host((size_t)n * cout_each * cin);
+    for (int i = 0; i < n; ++i) {
+      const HostTensor& t = ws.get(sources[i]);
+      SD_REQUIRE(t.numel() == (size_t)cout_each * cin, kInvalidArgument, "%s: bad shape", sources[i].c_str());
+      for (size_t j = 0; j < t.numel(); ++j) host[(size_t)i * cout_each * cin + j] = (half_t)t.data[j];
+    }
+    SD_HIP(hipMemcpy(d, host.data(), host.size() * sizeof(half_t), hipMemcpyHostToDevice));
+  });
   return conv_w(ops, names[0], d, nullptr, x, {.cout = n * cout_each});
 }
 
@@ -85,29 +89,38 @@ Tensor UNet::conv_stacked(std::vector<Op>& ops, const std::vector<std::string>& 
 // the separate LayerNorm launch, its HBM round trip and the fp16 rounding of LN(x) all disappear.
 UNet::LnFold UNet::fold_layernorm(const std::string& ln, const std::vector<std::string>& names, int cin, int cout_each,
                                   bool geglu, bool upload_w) {
-  const HostTensor& g = ws_->get(ln + ".weight");
-  const HostTensor& be = ws_->get(ln + ".bias");
-  SD_REQUIRE((int)g.numel() == cin && (int)be.numel() == cin, kInvalidArgument, "%s: expected %d channels", ln.c_str(),
-             cin);
   const int n = (int)names.size(), ntot = n * cout_each;
   SD_REQUIRE(!geglu || n == 1, kInternal, "GEGLU fold takes one projection");
-  std::vector<half_t> w((size_t)ntot * cin);
-  std::vector<float> colsum(ntot), bias(ntot);
+  // the sources: the LayerNorm's weight and bias, every projection's weight and - where the checkpoint has one - bias
+  std::vector<std::string> sources = {ln + ".weight", ln + ".bias"};
+  std::vector<char> has_bias(n);
   for (int i = 0; i < n; ++i) {
-    const HostTensor& t = ws_->get(names[i] + ".weight");
-    SD_REQUIRE(t.numel() == (size_t)cout_each * cin, kInvalidArgument, "%s.weight: bad shape", names[i].c_str());
-    const HostTensor* tb = ws_->has(names[i] + ".bias") ? &ws_->get(names[i] + ".bias") : nullptr;
-    SD_REQUIRE(!tb || (int)tb->numel() == cout_each, kInvalidArgument, "%s.bias: bad shape", names[i].c_str());
-    fold_layernorm_rows(t.data.data(), tb ? tb->data.data() : nullptr, g.data.data(), be.data.data(), cout_each, cin, i * cout_each,
-                        geglu, w.data(), colsum.data(), bias.data());
+    sources.push_back(names[i] + ".weight");
+    has_bias[i] = ws_->has(names[i] + ".bias");
+    if (has_bias[i]) sources.push_back(names[i] + ".bias");
   }
   LnFold f;
-  f.w = upload_w ? ll_.arena.alloc_n<half_t>(w.size()) : nullptr;
+  f.w = upload_w ? ll_.arena.alloc_n<half_t>((size_t)ntot * cin) : nullptr;
   f.colsum = ll_.arena.alloc_n<float>(ntot);
   f.bias = ll_.arena.alloc_n<float>(ntot);
-  if (upload_w) SD_HIP(hipMemcpy(f.w, w.data(), w.size() * sizeof(half_t), hipMemcpyHostToDevice));
-  SD_HIP(hipMemcpy(f.colsum, colsum.data(), ntot * sizeof(float), hipMemcpyHostToDevice));
-  SD_HIP(hipMemcpy(f.bias, bias.data(), ntot * sizeof(float), hipMemcpyHostToDevice));
+  refill(sources, f.w, [=](const WeightStore& ws) {
+    const HostTensor& g = ws.get(ln + ".weight");
+    const HostTensor& be = ws.get(ln + ".bias");
+    SD_REQUIRE((int)g.numel() == cin && (int)be.numel() == cin, kInvalidArgument, "%s: expected %d channels", ln.c_str(), cin);
+    std::vector<half_t> w((size_t)ntot * cin);
+    std::vector<float> colsum(ntot), bias(ntot);
+    for (int i = 0; i < n; ++i) {
+      const HostTensor& t = ws.get(names[i] + ".weight");
+      SD_REQUIRE(t.numel() == (size_t)cout_each * cin, kInvalidArgument, "%s.weight: bad shape", names[i].c_str());
+      const HostTensor* tb = has_bias[i] ? &ws.get(names[i] + ".bias") : nullptr;
+      SD_REQUIRE(!tb || (int)tb->numel() == cout_each, kInvalidArgument, "%s.bias: bad shape", names[i].c_str());
+      fold_layernorm_rows(t.data.data(), tb ? tb->data.data() : nullptr, g.data.data(), be.data.data(), cout_each, cin, i * cout_each,
+                          geglu, w.data(), colsum.data(), bias.data());
+    }
+    if (f.w) SD_HIP(hipMemcpy(f.w, w.data(), w.size() * sizeof(half_t), hipMemcpyHostToDevice));
+    SD_HIP(hipMemcpy(f.colsum, colsum.data(), ntot * sizeof(float), hipMemcpyHostToDevice));
+    SD_HIP(hipMemcpy(f.bias, bias.data(), ntot * sizeof(float), hipMemcpyHostToDevice));
+  });
   return f;
 }
 
@@ -232,15 +245,20 @@ Tensor UNet::transformer_block(std::vector<Op>& ops, const std::string& b, const
       const ConvWeights qw = upload_qkv_i8(parts, qpin, C, C);
       float* qb = nullptr;   // (SD checkpoints have no bias on to_q / to_k / to_v; one that has goes up stacked, absent parts zero)
       if (ws_->has(parts[0] + ".bias") || ws_->has(parts[1] + ".bias") || ws_->has(parts[2] + ".bias")) {
-        std::vector<float> hb((size_t)3 * C, 0.f);
+        std::vector<std::pair<int, std::string>> present;   // (part, its bias tensor)
+        std::vector<std::string> sources;
         for (int i = 0; i < 3; ++i)
-          if (ws_->has(parts[i] + ".bias")) {
-            const HostTensor& tb = ws_->get(parts[i] + ".bias");
-            SD_REQUIRE((int)tb.numel() == C, kInvalidArgument, "%s.bias: bad shape", parts[i].c_str());
+          if (ws_->has(parts[i] + ".bias")) present.push_back({i, parts[i] + ".bias"}), sources.push_back(parts[i] + ".bias");
+        qb = ll_.arena.alloc_n<float>((size_t)3 * C);
+        refill(sources, qb, [=](const WeightStore& ws) {
+          std::vector<float> hb((size_t)3 * C, 0.f);
+          for (const auto& [i, bname] : present) {
+            const HostTensor& tb = ws.get(bname);
+            SD_REQUIRE((int)tb.numel() == C, kInvalidArgument, "%s: bad shape", bname.c_str());
             std::copy(tb.data.begin(), tb.data.end(), hb.begin() + (size_t)i * C);
           }
-        qb = ll_.arena.alloc_n<float>(hb.size());
-        SD_HIP(hipMemcpy(qb, hb.data(), hb.size() * sizeof(float), hipMemcpyHostToDevice));
+          SD_HIP(hipMemcpy(qb, hb.data(), hb.size() * sizeof(float), hipMemcpyHostToDevice));
+        });
       }
       const float* nw = upload_vec(b + ".norm1.weight", C);
       const float* nb = upload_vec(b + ".norm1.bias", C);
@@ -286,17 +304,17 @@ Tensor UNet::transformer_block(std::vector<Op>& ops, const std::string& b, const
   if (xo_branch) {
     LnFold f = fold_layernorm(b + ".norm2", {b + ".attn2.to_q"}, C, C, false);
     half_t* wq_t = ll_.arena.alloc_n<half_t>((size_t)C * C);
-    launch_xattn_out_retile(f.w, wq_t, C, ll_.stream);
+    derive(f.w, [=] { launch_xattn_out_retile(f.w, wq_t, C, ll_.stream); });
     const half_t* wo = upload_conv_weight(b + ".attn2.to_out.0", C, C, 1, false);
     half_t* wo_t = ll_.arena.alloc_n<half_t>((size_t)C * C);
-    launch_xattn_out_retile(wo, wo_t, C, ll_.stream);
+    derive(wo, [=] { launch_xattn_out_retile(wo, wo_t, C, ll_.stream); });
     h2 = new_tensor(h.B, h.H, h.W, C);
     XAttnOutDesc xd;
     xd.x = xo_pre ? a1.p : h1.p;
     if (xo_pre) {
       const half_t* wo1 = upload_conv_weight(b + ".attn1.to_out.0", C, C, 1, false);
       half_t* wo1_t = ll_.arena.alloc_n<half_t>((size_t)C * C);
-      launch_xattn_out_retile(wo1, wo1_t, C, ll_.stream);
+      derive(wo1, [=] { launch_xattn_out_retile(wo1, wo1_t, C, ll_.stream); });
       xd.h0 = h.p;
       xd.wo1_t = wo1_t;
       xd.o1_bias = upload_vec(b + ".attn1.to_out.0.bias", C);
@@ -455,10 +473,10 @@ Tensor UNet::transformer_block(std::vector<Op>& ops, const std::string& b, const
   if (ffn_one_launch && g.C == 4 * C) {
     const half_t* w1 = upload_conv_weight(b + ".ff.net.2", C, 4 * C, 1, false);
     half_t* w1_t = ll_.arena.alloc_n<half_t>((size_t)C * 4 * C);
-    launch_xattn_out_retile_nk(w1, w1_t, C, 4 * C, ll_.stream);
+    derive(w1, [=] { launch_xattn_out_retile_nk(w1, w1_t, C, 4 * C, ll_.stream); });
     const half_t* w2 = upload_conv_weight(*proj_out, C, C, 1, false);
     half_t* w2_t = ll_.arena.alloc_n<half_t>((size_t)C * C);
-    launch_xattn_out_retile_nk(w2, w2_t, C, C, ll_.stream);
+    derive(w2, [=] { launch_xattn_out_retile_nk(w2, w2_t, C, C, ll_.stream); });
     Tensor out = new_tensor(h.B, h.H, h.W, C);
     FfnProjDesc d;
     d.g = g.p;
@@ -513,35 +531,38 @@ Tensor UNet::transformer_block(std::vector<Op>& ops, const std::string& b, const
   }
   if (merge) {
     const int K1 = 4 * C;
-    const HostTensor& t2 = ws_->get(b + ".ff.net.2.weight");
-    const HostTensor& tp = ws_->get(*proj_out + ".weight");
-    const HostTensor& tb2 = ws_->get(b + ".ff.net.2.bias");
-    const HostTensor& tbp = ws_->get(*proj_out + ".bias");
-    SD_REQUIRE(t2.numel() == (size_t)C * K1 && tp.numel() == (size_t)C * C && (int)tb2.numel() == C && (int)tbp.numel() == C, kInvalidArgument,
-               "%s: ff.net.2 / proj_out parameter shapes", b.c_str());
-    // staging buffer, freed below: [b2 | bp] fp32, then [W2 | Wp] fp16 as the two-launch form uploads them
-    std::vector<float> hb(2 * (size_t)C);
-    std::vector<half_t> hw((size_t)C * K1 + (size_t)C * C);
-    for (int i = 0; i < C; ++i) hb[i] = tb2.data[i], hb[C + i] = tbp.data[i];
-    for (size_t i = 0; i < t2.numel(); ++i) hw[i] = (half_t)t2.data[i];
-    for (size_t i = 0; i < tp.numel(); ++i) hw[t2.numel() + i] = (half_t)tp.data[i];
+    const std::string n2 = b + ".ff.net.2", np = *proj_out;
     half_t* wm = ll_.arena.alloc_n<half_t>((size_t)C * (K1 + C));
     float* bm = ll_.arena.alloc_n<float>(C);
-    char* tmp = nullptr;
-    const size_t b_bytes = hb.size() * sizeof(float), w_bytes = hw.size() * sizeof(half_t);
-    SD_HIP(hipMalloc(reinterpret_cast<void**>(&tmp), b_bytes + w_bytes));
-    try {
-      SD_HIP(hipMemcpy(tmp, hb.data(), b_bytes, hipMemcpyHostToDevice));
-      SD_HIP(hipMemcpy(tmp + b_bytes, hw.data(), w_bytes, hipMemcpyHostToDevice));
-      const float* db = reinterpret_cast<const float*>(tmp);
-      const half_t* dw = reinterpret_cast<const half_t*>(tmp + b_bytes);
-      launch_wfold(dw + (size_t)C * K1, db + C, dw, db, wm, bm, C, C, K1, ll_.stream);
-      SD_HIP(hipStreamSynchronize(ll_.stream));
-    } catch (...) {
-      (void)hipFree(tmp);
-      throw;
-    }
-    SD_HIP(hipFree(tmp));
+    refill({n2 + ".weight", np + ".weight", n2 + ".bias", np + ".bias"}, wm, [=](const WeightStore& ws) {
+      const HostTensor& t2 = ws.get(n2 + ".weight");
+      const HostTensor& tp = ws.get(np + ".weight");
+      const HostTensor& tb2 = ws.get(n2 + ".bias");
+      const HostTensor& tbp = ws.get(np + ".bias");
+      SD_REQUIRE(t2.numel() == (size_t)C * K1 && tp.numel() == (size_t)C * C && (int)tb2.numel() == C && (int)tbp.numel() == C, kInvalidArgument,
+                 "%s: ff.net.2 / proj_out parameter shapes", b.c_str());
+      // staging buffer, freed below: [b2 | bp] fp32, then [W2 | Wp] fp16 as the two-launch form uploads them
+      std::vector<float> hb(2 * (size_t)C);
+      std::vector<half_t> hw((size_t)C * K1 + (size_t)C * C);
+      for (int i = 0; i < C; ++i) hb[i] = tb2.data[i], hb[C + i] = tbp.data[i];
+      for (size_t i = 0; i < t2.numel(); ++i) hw[i] = (half_t)t2.data[i];
+      for (size_t i = 0; i < tp.numel(); ++i) hw[t2.numel() + i] = (half_t)tp.data[i];
+      char* tmp = nullptr;
+      const size_t b_bytes = hb.size() * sizeof(float), w_bytes = hw.size() * sizeof(half_t);
+      SD_HIP(hipMalloc(reinterpret_cast<void**>(&tmp), b_bytes + w_bytes));
+      try {
+        SD_HIP(hipMemcpy(tmp, hb.data(), b_bytes, hipMemcpyHostToDevice));
+        SD_HIP(hipMemcpy(tmp + b_bytes, hw.data(), w_bytes, hipMemcpyHostToDevice));
+        const float* db = reinterpret_cast<const float*>(tmp);
+        const half_t* dw = reinterpret_cast<const half_t*>(tmp + b_bytes);
+        launch_wfold(dw + (size_t)C * K1, db + C, dw, db, wm, bm, C, C, K1, ll_.stream);
+        SD_HIP(hipStreamSynchronize(ll_.stream));
+      } catch (...) {
+        (void)hipFree(tmp);
+        throw;
+      }
+      SD_HIP(hipFree(tmp));
+    });
     Tensor out = conv_w(ops, b + ".ff.net.2 + residual + proj_out + residual", wm, bm, g, {.x2 = &h2, .cout = C, .res = tres->p});
     ops.back().flop = 2.0 * h.M() * (double)C * K1 + 2.0 * h.M() * (double)C * C;   // the algorithmic count of the two maps
     *tail_done = true;
@@ -574,10 +595,10 @@ Tensor UNet::transformer(std::vector<Op>& ops, const std::string& p, const Tenso
     h = new_tensor(x.B, x.H, x.W, C);
     const half_t* wp = upload_conv_weight(p + ".proj_in", C, C, 1, false);
     half_t* wp_t = ll_.arena.alloc_n<half_t>((size_t)C * C);
-    launch_xattn_out_retile_nk(wp, wp_t, C, C, ll_.stream);
+    derive(wp, [=] { launch_xattn_out_retile_nk(wp, wp_t, C, C, ll_.stream); });
     LnFold f = fold_layernorm(b0 + ".norm1", {b0 + ".attn1.to_q", b0 + ".attn1.to_k", b0 + ".attn1.to_v"}, C, C, false);
     half_t* wq_t = ll_.arena.alloc_n<half_t>((size_t)3 * C * C);
-    launch_xattn_out_retile_nk(f.w, wq_t, 3 * C, C, ll_.stream);
+    derive(f.w, [=] { launch_xattn_out_retile_nk(f.w, wq_t, 3 * C, C, ll_.stream); });
     pre.qk = new_tensor(x.B, x.H, x.W, 2 * C);
     pre.vt = ll_.arena.alloc_n<half_t>((size_t)x.B * C * ldv0);
     pre.vt_perm = attention8_shape_ok(C / heads, HW, HW) && HW % 16 == 0;
@@ -667,22 +688,26 @@ void UNet::down_and_mid(std::vector<Op>& ops, Tensor& h, std::vector<Tensor>& sk
 void UNet::finalize_temb() {
   // one [sum Cout][temb_dim] matrix for all time_emb_proj layers (unet.py:442-444, :477)
   const int tdim = cfg_.block_out_channels[0] * 4;
-  std::vector<half_t> w((size_t)temb_used_ * tdim);
-  std::vector<float> b(temb_used_);
-  size_t row = 0;
-  for (auto& [name, cout] : temb_layers_) {
-    const HostTensor& tw = ws_->get(name + ".weight");
-    const HostTensor& tb = ws_->get(name + ".bias");
-    SD_REQUIRE(tw.numel() == (size_t)cout * tdim && (int)tb.numel() == cout, kInvalidArgument, "%s: bad shape",
-               name.c_str());
-    for (size_t i = 0; i < (size_t)cout * tdim; ++i) w[row * tdim + i] = (half_t)tw.data[i];
-    for (int i = 0; i < cout; ++i) b[row + i] = tb.data[i];
-    row += cout;
-  }
-  temb_w_all_ = ll_.arena.alloc_n<half_t>(w.size());
-  temb_b_all_ = ll_.arena.alloc_n<float>(b.size());
-  SD_HIP(hipMemcpy(temb_w_all_, w.data(), w.size() * sizeof(half_t), hipMemcpyHostToDevice));
-  SD_HIP(hipMemcpy(temb_b_all_, b.data(), b.size() * sizeof(float), hipMemcpyHostToDevice));
+  std::vector<std::string> sources;
+  for (auto& [name, cout] : temb_layers_) sources.push_back(name + ".weight"), sources.push_back(name + ".bias");
+  temb_w_all_ = ll_.arena.alloc_n<half_t>((size_t)temb_used_ * tdim);
+  temb_b_all_ = ll_.arena.alloc_n<float>((size_t)temb_used_);
+  refill(sources, temb_w_all_, [this, tdim](const WeightStore& ws) {
+    std::vector<half_t> w((size_t)temb_used_ * tdim);
+    std::vector<float> b(temb_used_);
+    size_t row = 0;
+    for (auto& [name, cout] : temb_layers_) {
+      const HostTensor& tw = ws.get(name + ".weight");
+      const HostTensor& tb = ws.get(name + ".bias");
+      SD_REQUIRE(tw.numel() == (size_t)cout * tdim && (int)tb.numel() == cout, kInvalidArgument, "%s: bad shape",
+                 name.c_str());
+      for (size_t i = 0; i < (size_t)cout * tdim; ++i) w[row * tdim + i] = (half_t)tw.data[i];
+      for (int i = 0; i < cout; ++i) b[row + i] = tb.data[i];
+      row += cout;
+    }
+    SD_HIP(hipMemcpy(temb_w_all_, w.data(), w.size() * sizeof(half_t), hipMemcpyHostToDevice));
+    SD_HIP(hipMemcpy(temb_b_all_, b.data(), b.size() * sizeof(float), hipMemcpyHostToDevice));
+  });
 }
 
 void UNet::build_unet() {
@@ -896,6 +921,20 @@ void UNet::build_unet() {
     time_ops_.back().label = "time_emb_proj of all resnets: one batched GEMV N=" + std::to_string(N);
   }
   // loop state (allocated lazily on first denoise_loop)
+}
+
+// What the handle keeps between calls that weights went into: the hoisted K / V^T of the prompt (ctx_ops_) and a ControlNet's
+// conditioning embedding (cond_ops_).  Their inputs are still on the device, so both are computed again from the new weights; the
+// host copies the "did it change" tests compare against stay valid.
+void UNet::after_reload() {
+  if (have_ctx_) run_ops(ctx_ops_);
+  if (have_cond_) run_ops(cond_ops_);
+}
+
+void UNet::reload_weights(const WeightStore& ws, const std::vector<std::string>& names) {
+  SD_HIP(hipSetDevice(ll_.device));
+  if (cn_stream_) SD_HIP(hipStreamSynchronize(cn_stream_));   // attached ControlNets run there, against this handle's inputs
+  Net::reload_weights(ws, names);
 }
 
 void UNet::invalidate_graphs() {

@@ -31,6 +31,7 @@ class UNet : public Net {
   void attach_controlnets(const std::vector<UNet*>& cns);
   void set_controlnet_cond(const void* cond, int flags);
   void set_attention(int impl) override;
+  void reload_weights(const WeightStore& ws, const std::vector<std::string>& names) override;
   int num_residuals() const { return (int)res_shapes_.size(); }
 
  private:
@@ -74,6 +75,7 @@ class UNet : public Net {
   void set_context_from(const half_t* ehs_dev, hipStream_t s);
   void run_attached();
   void invalidate_graphs() override;
+  void after_reload() override;
   void run_eager() override;       // in_ops_, attached ControlNets, run_main, out_ops_
   void run_main(bool with_time);   // the main list [behind time_ops_] with the join of the forked ControlNets in place
   std::vector<const std::vector<Op>*> forward_lists() const override { return {&in_ops_, &time_ops_, &ll_.ops, &out_ops_}; }

@@ -80,6 +80,15 @@ void WeightStore::add(const std::string& name, const void* data, int dtype, cons
   i8_.erase(name);    // ... and whatever W8A8 mark
 }
 
+void WeightStore::set_values(const std::string& name, const float* values, size_t n) {
+  auto it = map_.find(name);
+  if (it == map_.end()) fail(kNotFound, "set_values: the store has no tensor '%s'", name.c_str());
+  SD_REQUIRE(n == it->second.numel(), kInvalidArgument, "set_values(%s): %zu values for a tensor of %zu elements", name.c_str(), n, it->second.numel());
+  std::copy(values, values + n, it->second.data.begin());
+  pal_.erase(name);
+  i8_.erase(name);
+}
+
 // ---- W8A8 marks ------------------------------------------------------------------------------
 const W8A8Mark* WeightStore::w8a8(const std::string& name) const {
   auto it = i8_.find(name);

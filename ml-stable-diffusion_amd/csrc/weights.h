@@ -60,6 +60,9 @@ class WeightStore {
   void add(const std::string& name, const void* data, int dtype /*0 f16, 1 f32, 2 bf16*/,
            const int64_t* shape, int ndim);
   void load_safetensors(const std::string& path, const std::string& prefix);
+  // overwrites the values of an existing tensor in place (kNotFound when absent, kInvalidArgument unless n is its element count);
+  // a palette or a W8A8 mark on it is dropped: the tensor is then a plain one holding `values`
+  void set_values(const std::string& name, const float* values, size_t n);
   const HostTensor& get(const std::string& name) const;   // throws kNotFound
   const HostTensor* find(const std::string& name) const;  // nullptr when absent (deprecated VAE attention names accepted)
   bool has(const std::string& name) const { return find(name) != nullptr; }

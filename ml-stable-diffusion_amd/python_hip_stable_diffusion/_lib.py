@@ -92,6 +92,7 @@ SYMBOLS = [
     ("sd_weights_load_safetensors", _I, [_P, C.c_char_p, C.c_char_p]),
     ("sd_weights_count", _I, [_P]),
     ("sd_weights_destroy", None, [_P]),
+    ("sd_weights_set_values", _I, [_P, C.c_char_p, _FP, C.c_size_t]),
     ("sd_weights_tensor_info", _I, [_P, _I, C.c_char_p, _I, C.POINTER(C.c_int64), C.POINTER(_I)]),
     ("sd_weights_palettize", _I, [_P, C.c_char_p, _I, C.POINTER(C.c_double)]),
     ("sd_weights_add_palettized", _I, [_P, C.c_char_p, _P, _I, _P, C.POINTER(C.c_int64), _I]),
@@ -128,6 +129,7 @@ SYMBOLS = [
     ("sd_unet_create", _I, [C.POINTER(UNetConfig), _P, _I, C.POINTER(_P)]),
     ("sd_unet_destroy", None, [_P]),
     ("sd_unet_set_attention", _I, [_P, _I]),
+    ("sd_unet_reload_weights", _I, [_P, _P, C.POINTER(C.c_char_p), _I]),
     ("sd_unet_num_residuals", _I, [_P]),
     ("sd_unet_device_bytes", C.c_size_t, [_P]),
     ("sd_unet_arena_used_bytes", C.c_size_t, [_P]),

@@ -180,6 +180,15 @@ class Weights(_lib.Handle):
         _lib.check(_lib.lib().sd_weights_read_palette(self._h, name.encode(), _lib.ptr(lut), _lib.ptr(indices), None))
         return lut, indices
 
+    def set_values(self, name, values):
+        """Overwrite the values of the existing tensor ``name`` in place; a palette or W8A8 mark on it is dropped.  KeyError: unknown
+        name; ValueError: ``values`` has another element count than the tensor."""
+        values = np.ascontiguousarray(values, dtype=np.float32)
+        status = _lib.lib().sd_weights_set_values(self._h, name.encode(), _lib.fptr(values), values.size)
+        if status == -2:
+            raise KeyError(name)
+        _lib.check(status)
+
     # ---- W8A8 marks (sd_mi355x.h "W8A8 post-training quantization") ----
     def quantize_w8a8(self, name, act_absmax):
         """Mark conv weight ``name`` for W8A8 with the range of the activations its conv reads; returns the squared weight error.
@@ -398,6 +407,20 @@ class HipModel(_lib.Model):
             raise ValueError(f"--attention-implementation must be one of {list(_lib.ATTENTION_IMPLEMENTATIONS)}")
         _lib.check(_lib.lib().sd_unet_set_attention(self._h, _lib.ATTENTION_IMPLEMENTATIONS[name]))
         self.attention_implementation = name
+
+    def reload_weights(self, weights, names):
+        """Swap the values of the tensors ``names`` for those the ``Weights`` store ``weights`` holds (``sd_unet_reload_weights``):
+        the handle then computes bit for bit what one freshly built from ``weights`` computes, with no rebuild, no re-capture and no
+        new device memory.  ``weights`` is a complete store that differs from the one the handle last took its weights from only in
+        the values of ``names``.  KeyError: a name the store does not hold; ValueError: another shape than the handle was built with;
+        NotImplementedError: a tensor the handle holds compressed on the device (palette stream, int8), a handle built from an
+        observing store.  A refused call changes nothing."""
+        names = [n.encode() for n in names]
+        arr = (C.c_char_p * max(1, len(names)))(*names)
+        status = _lib.lib().sd_unet_reload_weights(self._h, weights._h, arr, len(names))
+        if status == -2:
+            raise KeyError(_lib.lib().sd_last_error().decode("utf-8", "replace"))
+        _lib.check(status)
 
     def time_forward(self, warmup=2, iters=10):
         """HIP-event milliseconds per forward on the handle's stream (inputs of the last call)."""

@@ -6,7 +6,8 @@ same thing happens to the weight store in front of ``sd_unet_create``: each chos
 ``2 ** nbits`` fp16 entries (``fake_palettize`` with one group, pre_analysis.py:139-156).  The clustering is the library's exact 1-D
 k-means (``sd_weights_palettize``); its parity with coremltools' ``_get_kmeans_lookup_table_and_weight`` is NOT pinned (coremltools is
 not a dependency of this project): the optimum cannot have a larger squared error than any k-means++ run, but the LUTs differ.
-The recipe SEARCH (pre_analysis) is out of scope: recipes are read, not made.
+The recipe SEARCH lives beside this module (``mixed_bit_compression_pre_analysis``): it makes the file ``load_recipe`` reads, on a
+live UNet handle through ``Weights.set_values`` and ``HipModel.reload_weights``.
 """
 import json
 

@@ -624,7 +624,7 @@ def get_hip_pipe(model_dir, model_version, compute_unit="ALL", scheduler_overrid
                  num_images=1, guidance_scale=7.5, unet_batch_one=False, latent_size=None, device=0,
                  refiner_dir=None, tokenizer_factory=None, text_encoder_factory=None, vae_dtype=None, disable_safety=False,
                  vae_encoder=False, quantize_nbits=None, palettization_recipe=None, device_postprocess=False,
-                 activation_quantization=None, observe_activations=False):
+                 activation_quantization=None, observe_activations=False, unet_weights=None):
     """``get_coreml_pipe`` (pipeline.py:607-697) without the conversion step: ``model_dir`` is a diffusers
     checkpoint directory (``unet/``, ``vae/``, ``text_encoder/``, ``tokenizer/``, ``scheduler/`` [,
     ``text_encoder_2/``, ``tokenizer_2/``]) instead of a folder of ``.mlpackage`` files; ControlNets are
@@ -647,7 +647,9 @@ def get_hip_pipe(model_dir, model_version, compute_unit="ALL", scheduler_overrid
     to the UNet alone (activation_quantization.py:141-203 ``--quantize-pytorch``; the refiner and the ControlNets stay as they are;
     parity with coremltools' quantizer unpinned).  ``observe_activations``: the UNet carries the calibration observers
     (``True``, ``"all"``, ``"gemm"``, ``"geglu"`` or ``"attn"``: ``Weights.observe_activations``; ``pipe.unet.activation_ranges()`` after a generation;
-    ``--calibrate-activations`` / ``--calibrate-scope``)."""
+    ``--calibrate-activations`` / ``--calibrate-scope``).
+    ``unet_weights``: a ``Weights`` store the UNet is built from instead of ``unet/``'s checkpoint file; it stays the caller's, who can
+    change it and ``reload_weights`` it into ``pipe.unet`` (``mixed_bit_compression_pre_analysis``)."""
     if not os.path.isdir(model_dir):
         raise FileNotFoundError(f"{model_dir} not found (coreml_model.py:176-178)")
     from . import text_encoder as te
@@ -670,17 +672,17 @@ def get_hip_pipe(model_dir, model_version, compute_unit="ALL", scheduler_overrid
             logger.warning("Overriding scheduler in pipeline: Override=%s", name)
         scheduler = SCHEDULER_MAP[name].from_config(sc_cfg)
 
-    def load_unet(folder, kind="unet", support_controlnet=False, recipe_strict=True, **w8a8):
+    def load_unet(folder, kind="unet", support_controlnet=False, recipe_strict=True, weights=None, **w8a8):
         cfg = dict(_read_json(os.path.join(folder, "config.json")))
         cfg["support_controlnet"] = support_controlnet
         size = latent_size or cfg.get("sample_size", 64)
-        return HipModel(cfg, _find_weights(folder), kind=kind, batch=batch, latent_height=size, latent_width=size,
+        return HipModel(cfg, weights if weights is not None else _find_weights(folder), kind=kind, batch=batch, latent_height=size, latent_width=size,
                         attention_implementation=attention_implementation, device=device, quantize_nbits=quantize_nbits,
                         palettization_recipe=palettization_recipe, recipe_strict=recipe_strict, **w8a8)
 
     kwargs = dict(xl=xl, force_zeros_for_empty_prompt=force_zeros_for_empty_prompt, safety_checker=None)
     logger.info("Loading models in HBM from %s", model_dir)
-    kwargs["unet"] = load_unet(os.path.join(model_dir, "unet"), support_controlnet=bool(controlnet_models),
+    kwargs["unet"] = load_unet(os.path.join(model_dir, "unet"), support_controlnet=bool(controlnet_models), weights=unet_weights,
                                activation_quantization=activation_quantization, observe_activations=observe_activations)
     kwargs["controlnet"] = ([load_unet(d, kind="controlnet", recipe_strict=False) for d in controlnet_models] if controlnet_models else None)
     vcfg = _read_json(os.path.join(model_dir, "vae", "config.json"))
