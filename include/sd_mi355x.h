@@ -405,10 +405,15 @@ int sd_text_encoder_encode(sd_text_encoder* t, const int32_t* input_ids, int eos
  * Operator-level entry points (what the parity tests and micro-benchmarks bind).  Host
  * pointers unless SD_FLAG_DEVICE_PTRS; each call is synchronous on an internal stream.
  * `ms` (may be NULL) returns HIP-event kernel time averaged over `iters` (>=1) launches.
+ * Every device buffer of an entry sits between a front and a back guard of 0xff bytes; outputs and workspaces start as 0xff too
+ * (fp16 / fp32 NaN patterns), so a skipped element or an unwritten split-K slab shows.  A guard byte that changed fails the call
+ * with SD_ERR_INTERNAL after the last launch; fills and checks are outside the timed region.  sd_op_harness_selftest proves it.
  * ------------------------------------------------------------------------------------------ */
 /* attention.py:24-168.  q (B, h*d, 1, Sq), k/v (B, h*d, 1, Sk) f16 BC1S -> out (B, h*d, 1, Sq) f16.
  * variant (A/B testing): 0 = default dispatch, 1 = never the software-pipelined d = 64 kernel, 2 = q arrives multiplied by
  * d^-0.5 * log2(e) (how the UNet's fused q|k|v GEMM hands its queries to that kernel: scaled in fp32, rounded once),
+ * 3 = the default dispatch with q and k uploaded interleaved as ONE [B][S][2 h d] buffer (row strides of 2 h d, how a UNet's
+ * self-attention reads the output of its fused q|k|v GEMM; needs Sq == Sk; bit-identical to variant 0),
  * 100 + u = that kernel's balanced grid with u (query tile, key tile) units per workgroup (0: the launch's own split). */
 int sd_op_attention(int impl, const void* q, const void* k, const void* v, void* out, int B, int heads, int d,
                     int Sq, int Sk, int variant, int iters, float* ms);
@@ -921,6 +926,12 @@ int sd_op_vit_patch_rows(const void* img, void* rows, int B, int I, int p, int K
 /* out[b][0] = cls + pos[0], out[b][1 + j] = patch[b][j] + pos[1 + j]: patch (B, S - 1, D), cls (D), pos (S, D) f16 -> out
  * (B, S, D) f16; D % 8 != 0 or S < 2 is SD_ERR_UNSUPPORTED */
 int sd_op_vit_tokens(const void* patch, const void* cls, const void* pos, void* out, int B, int S, int D);
+/* Self-check of the operator harness (the guarded, poisoned device buffers every sd_op_* entry allocates): dst = (float)src over
+ * n f16 values (2 <= n <= 2^24) with one deliberate off-by-one in the entry's own pointer arithmetic, inside its own allocations.
+ * mode 0 clean -> SD_OK; 1 one element written behind dst / 2 in front of dst / 3 behind src -> SD_ERR_INTERNAL, the error names
+ * the entry point, the buffer, "back guard" or "front guard" and the byte offset; 4 the last element skipped / 5 src read one
+ * element behind its end -> SD_OK with dst[n - 1] NaN.  dst is written in every mode. */
+int sd_op_harness_selftest(int mode, const void* src, float* dst, size_t n);
 
 #ifdef __cplusplus
 }

@@ -21,7 +21,11 @@
 //   sd_op_ffn_out_proj `fused`: 0 two 1x1 GEMMs, 1 one launch (xattn_out.hip ffn_proj), 2-5 the merged tail (wfold.hip, then ONE
 //     two-source GEMM): 2 the library's plan, 3 igemm_kernel's 64x64 tile, 4 / 5 smgemm.hip's 32- / 64-row tiles
 //   sd_op_attention `variant`: 0 default dispatch, 1 never the software-pipelined d = 64 kernel (attention8.hip), 2 that kernel with
-//     pre-scaled q, 100 + u its balanced form with u units per workgroup (0: the launch's own split)
+//     pre-scaled q, 3 default dispatch with q and k as rows of ONE [B][S][2C] buffer (ldq = ldk = 2C, what a handle's self-attention
+//     reads; Sq == Sk), 100 + u its balanced form with u units per workgroup (0: the launch's own split)
+//
+// Device buffers: every one comes from the entry point's Scratch (capi_util.h) - guards of 0xff in front and behind, outputs and
+// workspaces poisoned, every guard checked when the scratch leaves scope.  No entry point allocates device memory any other way.
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -92,17 +96,19 @@ FoldedProj upload_ln_folded(Scratch& sc, const void* w, const float* bias, const
   return {sc.dev<half_t>(wf.size(), wf.data()), sc.dev<float>(cout, bf.data()), sc.dev<float>(cout, cs.data())};
 }
 
-// GroupNorm partial buffer, poisoned: a consumer must only read what the producer wrote
+// GroupNorm partial buffer, poisoned: a consumer must only read what the producer wrote (1e30, finite: a folded statistic comes
+// out wrong, not NaN)
 float* poisoned_gn_partial(Scratch& sc, int B, int HW, int groups) {
   std::vector<float> poison(groupnorm_scratch_floats(B, HW, groups), 1.0e30f);
-  return sc.dev<float>(poison.size(), poison.data());
+  return sc.dev<float>(poison.size(), poison.data(), "GroupNorm partials");
 }
 
-// split-K workspace large enough for every one of these launches
+// split-K workspace large enough for every one of these launches; poisoned, as a handle reuses its workspace dirty: a slab that is
+// combined without having been written shows
 ConvWorkspace workspace_for(Scratch& sc, std::initializer_list<ConvDesc> descs) {
   ConvWorkspace ws;
   for (const ConvDesc& d : descs) ws.partial_bytes = std::max(ws.partial_bytes, conv_workspace_bytes(d));
-  if (ws.partial_bytes) ws.partial = reinterpret_cast<float*>(sc.dev<char>(ws.partial_bytes));
+  if (ws.partial_bytes) ws.partial = reinterpret_cast<float*>(sc.out<char>(ws.partial_bytes, "split-K workspace"));
   return ws;
 }
 
@@ -132,18 +138,18 @@ void apply_tile_code(ConvDesc& d, int code, bool gemm_codes = false) {
 int concat_channels(const ConvDesc& d) { return d.C0 + (d.x1 ? d.C1 : 0); }
 void tile_for_wstream(Scratch& sc, ConvDesc& d, const char* refusal) {
   SD_REQUIRE(wstream_shape_ok(d), kInvalidArgument, "%s", refusal);
-  half_t* wtd = sc.dev<half_t>(wstream_tiled_halves(d.N, concat_channels(d), d.ksize));
+  half_t* wtd = sc.out<half_t>(wstream_tiled_halves(d.N, concat_channels(d), d.ksize), "w_tiled (wstream.hip copy)");
   launch_wstream_retile(d.w, wtd, d.N, concat_channels(d), d.ksize, sc.stream);
   d.w_tiled = wtd;
 }
 void tile_for_wsgemm(Scratch& sc, ConvDesc& d) {
-  half_t* wtd = sc.dev<half_t>(wsgemm_tiled_halves(d.N));
+  half_t* wtd = sc.out<half_t>(wsgemm_tiled_halves(d.N), "w_ws (wsgemm.hip copy)");
   launch_wsgemm_retile(d.w, wtd, d.N, d.out_mode == kOutGeglu, sc.stream);
   d.w_ws = wtd;
 }
 void tile_for_bvgemm(Scratch& sc, ConvDesc& d, const char* refusal) {
   SD_REQUIRE(bvgemm_shape_ok(d), kInvalidArgument, "%s", refusal);
-  half_t* wtd = sc.dev<half_t>(bvgemm_tiled_halves(d.N, concat_channels(d)));
+  half_t* wtd = sc.out<half_t>(bvgemm_tiled_halves(d.N, concat_channels(d)), "w_bv (bvgemm.hip copy)");
   launch_bvgemm_retile(d.w, wtd, d.N, concat_channels(d), d.out_mode == kOutGeglu, sc.stream);
   d.w_bv = wtd;
 }
@@ -161,6 +167,7 @@ struct HostWeights {
 
 // What sd_op_conv2d_ex sets on top of sd_op_conv2d (header); default-constructed: sd_op_conv2d itself.
 struct ConvOpExtra {
+  const char* entry = "conv2d";   // the entry point that runs conv2d_op (what the scratch's guard report names)
   const void* x1 = nullptr;   // second source (B, C1, H, W) f16
   int C1 = 0;
   const float* temb = nullptr;   // (B, Cout) f32
@@ -209,7 +216,7 @@ void conv2d_op(const void* x, const void* w, const float* bias, const void* res,
              e.pad_mode, ksize, stride, upsample);
   SD_REQUIRE(e.twin_groups == 0 || (e.twin_groups > 0 && e.twin_gamma && e.twin_beta && e.out_twin), kInvalidArgument,
              "conv2d: a GroupNorm twin needs twin_gamma, twin_beta and out_twin (twin_groups %d)", e.twin_groups);
-  Scratch sc;
+  Scratch sc(e.entry);
   const int up = upsample ? 2 : 1, pad = ksize / 2;
   // pad_mode 1: one row / column of zeros behind the image only (the sizes of Net::conv_w)
   const int Ho = e.pad_mode ? (H * up + 1 - ksize) / stride + 1 : (H * up + 2 * pad - ksize) / stride + 1;
@@ -226,7 +233,7 @@ void conv2d_op(const void* x, const void* w, const float* bias, const void* res,
   d.bias = bias ? sc.dev<float>(Cout, bias) : nullptr;
   if (e.temb) d.temb = upload_temb_rows(sc, e.temb, B, Cout, &d.temb_stride);
   if (res) d.res = upload_nhwc(sc, res, B, Cout, Ho, Wo);
-  half_t* dout = sc.dev<half_t>((size_t)B * Ho * Wo * Cout);
+  half_t* dout = sc.out<half_t>((size_t)B * Ho * Wo * Cout, "out");
   d.out = dout;
   d.B = B; d.Hi = H; d.Wi = W; d.Ho = Ho; d.Wo = Wo;
   d.ksize = ksize; d.stride = stride; d.up = up; d.N = Cout;
@@ -234,7 +241,7 @@ void conv2d_op(const void* x, const void* w, const float* bias, const void* res,
   apply_tile_code(d, tile, true);
   d.splitk = splitk;
   d.debug = force_generic >= 2 ? force_generic - 1 : 0;   // 2: loads only, 3: compute only (ablation)
-  if (d.debug & 4) d.prof = sc.dev<long long>(8);
+  if (d.debug & 4) d.prof = sc.out<long long>(8, "phase clock");
   const bool fast = force_generic != 1 && conv_fast_path_ok(d);
   if (e.cw.kind == WeightSource::PalWstream)
     SD_REQUIRE(fast && wstream_shape_ok(d), kInvalidArgument, "conv2d_palettized: shape not eligible for plan tile 14 (wstream.hip: k=%d C0=%d C1=%d N=%d %dx%d)",
@@ -245,7 +252,7 @@ void conv2d_op(const void* x, const void* w, const float* bias, const void* res,
   half_t* dtwin = nullptr;
   if (e.twin_groups) {   // the GroupNorm as a twin of the conv's slab combine (sd_op_conv2d_groupnorm's producer_stats = 2)
     SD_REQUIRE(fast, kInvalidArgument, "conv2d: GroupNorm twins need the MFMA path");
-    dtwin = sc.dev<half_t>((size_t)B * Ho * Wo * Cout);
+    dtwin = sc.out<half_t>((size_t)B * Ho * Wo * Cout, "out_twin");
     d.n_twins = 1;
     d.twin[0].y = dtwin;
     d.twin[0].ld = Cout;
@@ -294,7 +301,7 @@ ConvDesc producer_conv(Scratch& sc, const void* x, const void* w, const float* b
                        int Cout, int ksize, int tile) {
   ConvDesc d = conv_desc(upload_nhwc(sc, x, B, Cin, H, W), Cin, upload_conv_weight(sc, w, Cout, Cin, ksize),
                          bias ? sc.dev<float>(Cout, bias) : nullptr, res ? upload_nhwc(sc, res, B, Cout, H, W) : nullptr,
-                         sc.dev<half_t>((size_t)B * H * W * Cout), B, H, W, Cout, ksize);
+                         sc.out<half_t>((size_t)B * H * W * Cout, "conv_out"), B, H, W, Cout, ksize);
   apply_tile_code(d, tile);
   d.splitk = 1;
   return d;
@@ -326,26 +333,6 @@ ConvDesc qkv_desc(const half_t* in, const FoldedProj& f, float ln_eps, half_t* q
   d.q_cols = C;
   return d;
 }
-
-// A device buffer of n elements in front of a guard of `guard` more, every byte 0xff (fp16 / fp32 NaN patterns), then the first n
-// elements of `host` copied in (NULL: the output stays poisoned too, so an element the launch skipped reads back as NaN)
-template <typename T>
-T* guarded_buf(Scratch& sc, size_t n, size_t guard, const T* host = nullptr) {
-  T* d = sc.dev<T>(n + guard);
-  SD_HIP(hipMemset(d, 0xff, (n + guard) * sizeof(T)));
-  SD_HIP(hipStreamSynchronize(nullptr));   // the fill runs on the null stream, which the scratch's non-blocking stream does not wait for
-  if (host) SD_HIP(hipMemcpy(d, host, n * sizeof(T), hipMemcpyHostToDevice));
-  return d;
-}
-// ... and the check behind the launch: the guard must still hold its pattern
-template <typename T>
-void check_guard(Scratch& sc, const T* d, size_t n, size_t guard, const char* what) {
-  SD_HIP(hipStreamSynchronize(sc.stream));
-  std::vector<uint8_t> g(guard * sizeof(T));
-  SD_HIP(hipMemcpy(g.data(), d + n, g.size(), hipMemcpyDeviceToHost));
-  for (uint8_t v : g) SD_REQUIRE(v == 0xff, kInternal, "%s wrote behind its %zu outputs", what, n);
-}
-constexpr size_t kOpGuard = 4096;   // elements
 
 // (B, C, HW) -> [B][HW][C] and back, on the host
 template <typename T>
@@ -382,21 +369,38 @@ int sd_op_attention(int impl, const void* q, const void* k, const void* v, void*
     SD_REQUIRE(q && k && v && out, kInvalidArgument, "NULL argument");
     SD_REQUIRE(impl >= 0 && impl <= 2, kInvalidArgument, "unknown attention implementation %d", impl);
     SD_REQUIRE(B > 0 && heads > 0 && d > 0 && Sq > 0 && Sk > 0, kInvalidArgument, "empty attention problem");
-    Scratch sc;
+    SD_REQUIRE(variant != 3 || Sq == Sk, kInvalidArgument, "attention variant 3 (q | k in one buffer) needs Sq == Sk (%d, %d)", Sq, Sk);
+    Scratch sc("attention");
     const int C = heads * d;
     const int ldv = (Sk + 7) / 8 * 8;
     // the software-pipelined d = 64 kernel reads V^T in its own key order (AttnDesc::vt_perm)
     const bool perm = variant != 1 && attention8_shape_ok(d, Sq, Sk);
     AttnDesc a;
-    a.q = upload_tokens(sc, q, B, C, Sq);
-    a.k = upload_tokens(sc, k, B, C, Sk);
+    a.ldq = C; a.ldk = C;
+    if (variant == 3) {   // q and k as a self-attention of a handle reads them: rows of ONE [B][S][2C] buffer (qkv_desc's qk)
+      const half_t *qs = f16(q), *ks = f16(k);
+      std::vector<half_t> qk((size_t)B * Sq * 2 * C);
+      for (int b = 0; b < B; ++b)
+        for (int c = 0; c < C; ++c)
+          for (int s = 0; s < Sq; ++s) {
+            qk[((size_t)b * Sq + s) * 2 * C + c] = qs[((size_t)b * C + c) * Sq + s];
+            qk[((size_t)b * Sq + s) * 2 * C + C + c] = ks[((size_t)b * C + c) * Sq + s];
+          }
+      const half_t* dqk = sc.dev<half_t>(qk.size(), qk.data(), "q | k");
+      a.q = dqk;
+      a.k = dqk + C;
+      a.ldq = a.ldk = 2 * C;
+    } else {
+      a.q = upload_tokens(sc, q, B, C, Sq);
+      a.k = upload_tokens(sc, k, B, C, Sk);
+    }
     a.vt = upload_vt(sc, v, B, C, Sk, ldv, perm);
-    half_t* o = sc.dev<half_t>((size_t)B * Sq * C);
+    half_t* o = sc.out<half_t>((size_t)B * Sq * C, "out");
     a.out = o;
     a.B = B; a.heads = heads; a.d = d; a.Sq = Sq; a.Sk = Sk;
-    a.ldq = C; a.ldk = C; a.ldv = ldv; a.ldo = C;
+    a.ldv = ldv; a.ldo = C;
     a.impl = impl;
-    a.variant = variant;
+    a.variant = variant == 3 ? 0 : variant;   // (3: the default dispatch, only the addresses differ)
     a.vt_perm = perm ? 1 : 0;
     if (variant == 2) {   // the caller multiplied d^-0.5 * log2(e) into q before rounding it to fp16 (what the UNet's q|k|v GEMM does)
       SD_REQUIRE(perm, kInvalidArgument, "attention variant 2 (pre-scaled q) needs attention8's shape (d %d Sq %d Sk %d)", d, Sq, Sk);
@@ -412,11 +416,10 @@ int sd_op_attention(int impl, const void* q, const void* k, const void* v, void*
       size_t pb = 0;
       int nc = 0;
       if (perm && attention8_sk_scratch(a, &pb, &nc)) {
-        a.sk_part = reinterpret_cast<float*>(sc.dev<char>(pb));
+        a.sk_part = reinterpret_cast<float*>(sc.out<char>(pb, "sk_part"));
         a.sk_part_bytes = pb;
-        a.sk_cnt = sc.dev<unsigned>(nc);
+        a.sk_cnt = sc.zeroed<unsigned>(nc, "sk_cnt");   // zeroed: AttnDesc::sk_cnt is "ZEROED once by the owner", the kernel leaves it at zero
         a.sk_cnt_n = nc;
-        SD_HIP(hipMemset(a.sk_cnt, 0, (size_t)nc * sizeof(unsigned)));
       } else {
         SD_REQUIRE(variant < 100, kInvalidArgument, "attention variant %d: the balanced form cannot run this shape", variant);
       }
@@ -430,9 +433,9 @@ int sd_op_layernorm(const void* x, const float* weight, const float* bias, void*
                     int iters, float* ms) {
   return guarded([&] {
     SD_REQUIRE(x && weight && bias && out, kInvalidArgument, "NULL argument");
-    Scratch sc;
+    Scratch sc("layernorm");
     half_t* dx = upload_tokens(sc, x, B, C, S);
-    half_t* dy = sc.dev<half_t>((size_t)B * S * C);
+    half_t* dy = sc.out<half_t>((size_t)B * S * C, "out");
     float* dw = sc.dev<float>(C, weight);
     float* db = sc.dev<float>(C, bias);
     sc.timed(iters, ms, [&] { launch_layernorm(dx, dw, db, dy, B * S, C, eps, sc.stream); });
@@ -444,12 +447,12 @@ int sd_op_groupnorm(const void* x, const float* weight, const float* bias, void*
                     int groups, float eps, int silu, int iters, float* ms) {
   return guarded([&] {
     SD_REQUIRE(x && weight && bias && out, kInvalidArgument, "NULL argument");
-    Scratch sc;
+    Scratch sc("groupnorm");
     half_t* dx = upload_nhwc(sc, x, B, C, H, W);
-    half_t* dy = sc.dev<half_t>((size_t)B * H * W * C);
+    half_t* dy = sc.out<half_t>((size_t)B * H * W * C, "out");
     float* dw = sc.dev<float>(C, weight);
     float* db = sc.dev<float>(C, bias);
-    float* partial = sc.dev<float>(groupnorm_scratch_floats(B, H * W, groups));
+    float* partial = poisoned_gn_partial(sc, B, H * W, groups);
     sc.timed(iters, ms, [&] {
       launch_groupnorm(dx, C, nullptr, 0, partial, dw, db, dy, B, H * W, groups, eps, silu, sc.stream);
     });
@@ -464,14 +467,14 @@ int sd_op_groupnorm_shortcut(const void* x0, const void* x1, const float* gn_wei
     SD_REQUIRE(x0 && gn_weight && gn_bias && w && out_gn && out_sc, kInvalidArgument, "NULL argument");
     if (!x1) C1 = 0;
     const int C = C0 + C1;
-    Scratch sc;
+    Scratch sc("groupnorm_shortcut");
     half_t* d0 = upload_nhwc(sc, x0, B, C0, H, W);
     half_t* d1 = x1 ? upload_nhwc(sc, x1, B, C1, H, W) : nullptr;
-    half_t* dy = sc.dev<half_t>((size_t)B * H * W * C);
-    half_t* ds = sc.dev<half_t>((size_t)B * H * W * N);
+    half_t* dy = sc.out<half_t>((size_t)B * H * W * C, "out_gn");
+    half_t* ds = sc.out<half_t>((size_t)B * H * W * N, "out_sc");
     float* dgw = sc.dev<float>(C, gn_weight);
     float* dgb = sc.dev<float>(C, gn_bias);
-    float* partial = sc.dev<float>(groupnorm_scratch_floats(B, H * W, groups));
+    float* partial = poisoned_gn_partial(sc, B, H * W, groups);
     // conv_shortcut: a 1x1 conv over the channel concat (x0 | x1), weights [N][C] as they are
     ConvDesc d = conv_desc(d0, C0, sc.dev<half_t>((size_t)N * C, f16(w)), bias ? sc.dev<float>(N, bias) : nullptr, nullptr, ds, B, H, W, N);
     d.x1 = d1;
@@ -507,6 +510,7 @@ int sd_op_conv2d_ex(const void* x, const void* x1, const void* w, const float* b
   return guarded([&] {
     SD_REQUIRE(plan_out, kInvalidArgument, "NULL argument");
     ConvOpExtra e;
+    e.entry = "conv2d_ex";
     e.x1 = x1; e.C1 = C1; e.temb = temb; e.pad_mode = pad_mode;
     e.twin_groups = twin_groups; e.twin_gamma = twin_gamma; e.twin_beta = twin_beta; e.twin_eps = twin_eps; e.twin_silu = twin_silu;
     e.out_twin = out_twin;
@@ -524,6 +528,7 @@ int sd_op_conv2d_palettized(const void* x, const void* x1, const void* lut, int 
     SD_REQUIRE(nw == 0 || nw == 4 || nw == 8, kInvalidArgument, "conv2d_palettized: nw = %d, not 0, 4 or 8", nw);
     SD_REQUIRE(B > 0 && Cin > 0 && C1 >= 0 && Cout > 0 && H > 0 && W > 0, kInvalidArgument, "conv2d_palettized: empty problem");
     ConvOpExtra e;
+    e.entry = "conv2d_palettized";
     e.x1 = x1; e.C1 = C1;
     e.plan_out = plan_out;
     e.cw.kind = WeightSource::PalWstream; e.cw.lut = lut; e.cw.indices = indices; e.cw.bits = nbits;
@@ -551,6 +556,7 @@ int sd_op_conv2d_w8a8(const void* x, const void* x1, const int8_t* wq, const flo
     // act_absmax, then w_scale, then the weight values (-128 is outside the symmetric range)
     (void)w8a8_host_copy("conv2d_w8a8", wq, w_scale, act_absmax, Cout, Cin + C1, ksize);
     ConvOpExtra e;
+    e.entry = "conv2d_w8a8";
     e.x1 = x1; e.C1 = C1;
     e.plan_out = plan_out;
     e.cw.kind = WeightSource::I8Wstream; e.cw.q = wq; e.cw.w_scale = w_scale; e.cw.act_absmax = act_absmax;
@@ -580,6 +586,7 @@ int sd_op_conv2d_w8a8_halo(const void* x, const void* x1, const int8_t* wq, cons
     // act_absmax, then w_scale, then the weight values (-128 is outside the symmetric range)
     (void)w8a8_host_copy("conv2d_w8a8_halo", wq, w_scale, act_absmax, Cout, Cin + C1, 3, WeightSource::I8Halo);
     ConvOpExtra e;
+    e.entry = "conv2d_w8a8_halo";
     e.x1 = x1; e.C1 = C1;
     e.temb = temb;
     e.plan_out = plan_out;
@@ -629,7 +636,7 @@ int sd_op_subpixel_refusal(int ksize, int stride, int up, int C0, int C1, int N,
 }
 
 // Nearest-x2 upsample + 3x3 / pad-1 conv as plan tile 21: w (Cout, Cin, 3, 3) f16 is folded by subpixel_fold, as a handle folds it.
-// The output buffer starts as NaN patterns in front of a guard that must survive; staging: tile 7's ring code (2: three stages, else
+// staging: tile 7's ring code (2: three stages, else
 // four), splitk 0: the plan's rule.  plan_out = {tile, staging, splitk, slab}.
 int sd_op_conv2d_subpixel(const void* x, const void* w, const float* bias, const void* res, void* out, int B, int Cin, int H, int W, int Cout, int splitk,
                           int staging, int* plan_out, int iters, float* ms) {
@@ -648,19 +655,18 @@ int sd_op_conv2d_subpixel(const void* x, const void* w, const float* bias, const
                halo_sp_refusal(d) ? halo_sp_refusal(d) : "off the MFMA path", Cin, Cout, H, W);
     std::vector<half_t> folded(subpixel_fold_halves(Cout, Cin));
     subpixel_fold(f16(w), Cout, Cin, folded.data());
-    Scratch sc;
+    Scratch sc("conv2d_subpixel");
     d.x0 = upload_nhwc(sc, x, B, Cin, H, W);
     d.w = sc.dev<half_t>(folded.size(), folded.data());
     d.bias = bias ? sc.dev<float>(Cout, bias) : nullptr;
     if (res) d.res = upload_nhwc(sc, res, B, Cout, d.Ho, d.Wo);
     const size_t n_out = (size_t)B * d.Ho * d.Wo * Cout;
-    half_t* dout = guarded_buf<half_t>(sc, n_out, kOpGuard);
+    half_t* dout = sc.out<half_t>(n_out, "out");
     d.out = dout;
     const ConvPlan p = conv_plan(d);
     plan_out[0] = p.tile; plan_out[1] = p.staging; plan_out[2] = p.splitk; plan_out[3] = p.slab ? 1 : 0;
     ConvWorkspace ws = workspace_for(sc, {d});
     sc.timed(iters, ms, [&] { launch_conv(d, ws, sc.stream); });
-    check_guard(sc, dout, n_out, kOpGuard, "conv2d_subpixel");
     download_nchw(dout, out, B, Cout, d.Ho, d.Wo);
   });
 }
@@ -683,11 +689,11 @@ int sd_op_gemm_w8a8(const void* x, const int8_t* wq, const float* w_scale, float
     SD_REQUIRE(smgemm_i8_shape_ok(d, code), kInvalidArgument, "gemm_w8a8: K = %d, the exact int32 sums of plan tile 19 hold up to %d", Cin, kSmI8MaxK);
     // act_absmax, then w_scale, then the weight values (-128 is outside the symmetric range)
     (void)w8a8_host_copy("gemm_w8a8", wq, w_scale, act_absmax, Cout, Cin, 1, WeightSource::I8Gemm);
-    Scratch sc;
+    Scratch sc("gemm_w8a8");
     d.x0 = upload_nhwc(sc, x, B, Cin, H, W);
     d.bias = bias ? sc.dev<float>(Cout, bias) : nullptr;
     if (res) d.res = upload_nhwc(sc, res, B, Cout, H, W);
-    half_t* dout = sc.dev<half_t>((size_t)B * H * W * Cout);
+    half_t* dout = sc.out<half_t>((size_t)B * H * W * Cout, "out");
     d.out = dout;
     HostWeights h;
     h.kind = WeightSource::I8Gemm; h.q = wq; h.w_scale = w_scale; h.act_absmax = act_absmax;
@@ -721,11 +727,11 @@ int sd_op_layernorm_q8(const void* x, const float* ln_weight, const float* ln_bi
     SD_REQUIRE(w8a8_absmax_ok(act_absmax), kInvalidArgument, "layernorm_q8: act_absmax = %g, not a positive finite number", (double)act_absmax);
     const float inv_s = 1.0f / (act_absmax / 127.0f);
     SD_REQUIRE(std::isfinite(inv_s) && inv_s > 0.f, kInvalidArgument, "layernorm_q8: act_absmax = %g has no finite inverse scale", (double)act_absmax);
-    Scratch sc;
+    Scratch sc("layernorm_q8");
     const half_t* dx = sc.dev<half_t>((size_t)M * C, f16(x));
     const float* dw = ln_weight ? sc.dev<float>(C, ln_weight) : nullptr;
     const float* db = ln_bias ? sc.dev<float>(C, ln_bias) : nullptr;
-    int8_t* dq = sc.dev<int8_t>((size_t)M * C);
+    int8_t* dq = sc.out<int8_t>((size_t)M * C, "xq", kOpGuard, 0x80);   // -128: a value the quantizer never writes (0xff is -1)
     sc.timed(iters, ms, [&] { launch_layernorm_q8(dx, dw, db, dq, M, C, eps, inv_s, sc.stream); });
     SD_HIP(hipMemcpy(xq, dq, (size_t)M * C, hipMemcpyDeviceToHost));
   });
@@ -758,7 +764,7 @@ static int geglu_w8a8_op(const int8_t* xq, const int8_t* wq, const float* w_scal
     (void)w8a8_host_copy("geglu_w8a8", wq, w_scale, act_absmax, N2, C, 1, WeightSource::I8Geglu);
     for (size_t i = 0; i < (size_t)M * C; ++i)
       SD_REQUIRE(xq[i] != -128, kInvalidArgument, "geglu_w8a8: activation value -128 at element %zu, the symmetric range is [-127, 127]", i);
-    Scratch sc;
+    Scratch sc(q8 ? "geglu_w8a8_q8" : "geglu_w8a8");
     d.x0_i8 = sc.dev<int8_t>((size_t)M * C, xq);
     if (bias) {
       std::vector<float> bi(N2);
@@ -768,14 +774,12 @@ static int geglu_w8a8_op(const int8_t* xq, const int8_t* wq, const float* w_scal
     const size_t n_out = (size_t)M * (N2 / 2);
     half_t* dout = nullptr;
     int8_t* dq = nullptr;
-    if (q8) {   // -128 in front of a guard of 0xff: an element the launch skipped reads back as a value the quantizer never writes
-      dq = guarded_buf<int8_t>(sc, n_out, kOpGuard);
-      SD_HIP(hipMemset(dq, 0x80, n_out));
-      SD_HIP(hipStreamSynchronize(nullptr));
+    if (q8) {   // -128: an element the launch skipped reads back as a value the quantizer never writes (0xff is -1)
+      dq = sc.out<int8_t>(n_out, "out_q", kOpGuard, 0x80);
       d.out_q8 = dq;
       d.out_inv_s = out_inv_s;
     } else {
-      dout = sc.dev<half_t>(n_out);
+      dout = sc.out<half_t>(n_out, "out");
       d.out = dout;
     }
     HostWeights h;
@@ -786,7 +790,6 @@ static int geglu_w8a8_op(const int8_t* xq, const int8_t* wq, const float* w_scal
     ConvWorkspace ws;
     sc.timed(iters, ms, [&] { launch_conv(d, ws, sc.stream); });
     if (q8) {
-      check_guard(sc, dq, n_out, kOpGuard, "geglu_w8a8_q8");
       SD_HIP(hipMemcpy(out_q, dq, n_out, hipMemcpyDeviceToHost));
     } else {
       SD_HIP(hipMemcpy(out, dout, n_out * 2, hipMemcpyDeviceToHost));
@@ -822,12 +825,12 @@ int sd_op_gemm_q8(const int8_t* xq, const int8_t* wq, const float* w_scale, floa
     (void)w8a8_host_copy("gemm_q8", wq, w_scale, act_absmax, N, K, 1, WeightSource::I8GemmQ);
     for (size_t i = 0; i < (size_t)M * K; ++i)
       SD_REQUIRE(xq[i] != -128, kInvalidArgument, "gemm_q8: activation value -128 at element %zu, the symmetric range is [-127, 127]", i);
-    Scratch sc;
+    Scratch sc("gemm_q8");
     d.x0_i8 = sc.dev<int8_t>((size_t)M * K, xq);
     d.bias = bias ? sc.dev<float>(N, bias) : nullptr;
     if (res) d.res = sc.dev<half_t>((size_t)M * N, f16(res));
     const size_t n_out = (size_t)M * N;
-    half_t* dout = guarded_buf<half_t>(sc, n_out, kOpGuard);
+    half_t* dout = sc.out<half_t>(n_out, "out");
     d.out = dout;
     HostWeights h;
     h.kind = WeightSource::I8GemmQ; h.q = wq; h.w_scale = w_scale; h.act_absmax = act_absmax;
@@ -836,7 +839,6 @@ int sd_op_gemm_q8(const int8_t* xq, const int8_t* wq, const float* w_scale, floa
     plan_out[0] = p.tile; plan_out[1] = p.staging; plan_out[2] = p.splitk; plan_out[3] = p.slab ? 1 : 0;
     ConvWorkspace ws;
     sc.timed(iters, ms, [&] { launch_conv(d, ws, sc.stream); });
-    check_guard(sc, dout, n_out, kOpGuard, "gemm_q8");
     SD_HIP(hipMemcpy(out, dout, n_out * 2, hipMemcpyDeviceToHost));
   });
 }
@@ -851,8 +853,7 @@ int sd_op_w8a8_pack_geglu(const int8_t* wq, int N2, int K, int8_t* packed, size_
 }
 
 // The fused q|k|v projection of a self-attention in W8A8 (plan tile 22).  Every check runs on the host in front of the first device call
-// (Scratch), in the order the header lists them.  Both outputs live in front of a poisoned guard on the device (guarded_buf): an
-// element the launch skipped reads back as NaN, and a guard that changed is an internal error.
+// (Scratch), in the order the header lists them.
 int sd_op_qkv_w8a8(const int8_t* xq, const int8_t* wq, const float* w_scale, float act_absmax, const float* bias, void* out_qk, void* out_vt,
                    int B, int HW, int C, float q_scale, int vt_perm, int bm, int* plan_out, int iters, float* ms) {
   return guarded([&] {
@@ -877,12 +878,12 @@ int sd_op_qkv_w8a8(const int8_t* xq, const int8_t* wq, const float* w_scale, flo
     (void)w8a8_host_copy("qkv_w8a8", wq, w_scale, act_absmax, N, C, 1, WeightSource::I8Qkv);
     for (size_t i = 0; i < (size_t)M * C; ++i)
       SD_REQUIRE(xq[i] != -128, kInvalidArgument, "qkv_w8a8: activation value -128 at element %zu, the symmetric range is [-127, 127]", i);
-    Scratch sc;
+    Scratch sc("qkv_w8a8");
     d.x0_i8 = sc.dev<int8_t>((size_t)M * C, xq);
     if (bias) d.bias = sc.dev<float>(N, bias);
-    const size_t n_qk = (size_t)M * 2 * C, n_vt = (size_t)B * C * d.ldT, guard = 4096;
-    half_t* dqk = guarded_buf<half_t>(sc, n_qk, guard);
-    half_t* dvt = guarded_buf<half_t>(sc, n_vt, guard);
+    const size_t n_qk = (size_t)M * 2 * C, n_vt = (size_t)B * C * d.ldT;
+    half_t* dqk = sc.out<half_t>(n_qk, "out_qk");
+    half_t* dvt = sc.out<half_t>(n_vt, "out_vt");
     d.out = dqk;
     d.out_t = dvt;
     HostWeights h;
@@ -894,11 +895,6 @@ int sd_op_qkv_w8a8(const int8_t* xq, const int8_t* wq, const float* w_scale, flo
     sc.timed(iters, ms, [&] { launch_conv(d, ws, sc.stream); });
     SD_HIP(hipMemcpy(out_qk, dqk, n_qk * 2, hipMemcpyDeviceToHost));
     SD_HIP(hipMemcpy(out_vt, dvt, n_vt * 2, hipMemcpyDeviceToHost));
-    std::vector<uint16_t> g(2 * guard);
-    SD_HIP(hipMemcpy(g.data(), dqk + n_qk, guard * 2, hipMemcpyDeviceToHost));
-    SD_HIP(hipMemcpy(g.data() + guard, dvt + n_vt, guard * 2, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < g.size(); ++i)
-      SD_REQUIRE(g[i] == 0xffff, kInternal, "qkv_w8a8: the guard behind %s was written (element %zu)", i < guard ? "out_qk" : "out_vt", i % guard);
   });
 }
 
@@ -932,10 +928,9 @@ int sd_op_quantize_weight(const float* w, int Cout, size_t per_row, int8_t* q, f
 int sd_op_absmax(const void* x, size_t n, float* absmax) {
   return guarded([&] {
     SD_REQUIRE(x && n > 0 && absmax, kInvalidArgument, "absmax: NULL argument or empty tensor");
-    Scratch sc;
+    Scratch sc("absmax");
     const half_t* dx = sc.dev<half_t>(n, f16(x));
-    const float zero = 0.f;
-    float* slot = sc.dev<float>(1, &zero);
+    float* slot = sc.zeroed<float>(1, "absmax slot");   // zeroed: the kernel folds into the slot with an atomic max; calibration clears it first
     launch_absmax_half(dx, n, nullptr, 0, slot, sc.stream);
     SD_HIP(hipStreamSynchronize(sc.stream));
     SD_HIP(hipMemcpy(absmax, slot, sizeof(float), hipMemcpyDeviceToHost));
@@ -968,11 +963,11 @@ int sd_op_gemm_palettized(const void* x, const void* lut, int nbits, const uint8
     SD_REQUIRE(conv_fast_path_ok(d) && smgemm_shape_ok(d, conv_plan_pin(WeightSource::PalGemm, bm).staging), kInvalidArgument,
                "gemm_palettized: shape not eligible for plan tile 15 (smgemm.hip: Cin=%d Cout=%d M=%d bm=%d - Cin a multiple of 64, Cout of 80, M of the "
                "tile height, at least 2 x 2 tiles and a multiple of 8 of them)", Cin, Cout, B * H * W, bm);
-    Scratch sc;
+    Scratch sc("gemm_palettized");
     d.x0 = upload_nhwc(sc, x, B, Cin, H, W);
     d.bias = bias ? sc.dev<float>(Cout, bias) : nullptr;
     if (res) d.res = upload_nhwc(sc, res, B, Cout, H, W);
-    half_t* dout = sc.dev<half_t>((size_t)B * H * W * Cout);
+    half_t* dout = sc.out<half_t>((size_t)B * H * W * Cout, "out");
     d.out = dout;
     HostWeights h;
     h.kind = WeightSource::PalGemm; h.lut = lut; h.indices = indices; h.bits = nbits;
@@ -1001,10 +996,10 @@ int sd_op_conv2d_groupnorm(const void* x, const void* w, const float* bias, cons
   return guarded([&] {
     SD_REQUIRE(x && w && gn_weight && gn_bias && out, kInvalidArgument, "NULL argument");
     SD_REQUIRE(ksize == 1 || ksize == 3, kInvalidArgument, "conv2d_groupnorm: ksize %d", ksize);
-    Scratch sc;
+    Scratch sc("conv2d_groupnorm");
     ConvDesc d = producer_conv(sc, x, w, bias, res, B, Cin, H, W, Cout, ksize, tile);
     half_t* dconv = d.out;
-    half_t* dy = sc.dev<half_t>((size_t)B * H * W * Cout);
+    half_t* dy = sc.out<half_t>((size_t)B * H * W * Cout, "out");
     const bool fast = conv_fast_path_ok(d);   // else: conv_in's 4-channel MFMA kernel / the direct kernels
     float* partial = poisoned_gn_partial(sc, B, H * W, groups);
     if (producer_stats == 1) {
@@ -1049,11 +1044,11 @@ int sd_op_conv2d_groupnorm_proj(const void* x, const void* w, const float* bias,
   return guarded([&] {
     SD_REQUIRE(x && w && gn_weight && gn_bias && proj_w && out, kInvalidArgument, "NULL argument");
     SD_REQUIRE(ksize == 1 || ksize == 3, kInvalidArgument, "conv2d_groupnorm_proj: ksize %d", ksize);
-    Scratch sc;
+    Scratch sc("conv2d_groupnorm_proj");
     ConvDesc d = producer_conv(sc, x, w, bias, res, B, Cin, H, W, Cout, ksize, tile);
     half_t* dconv = d.out;
-    half_t* dnorm = sc.dev<half_t>((size_t)B * H * W * Cout);
-    half_t* dy = sc.dev<half_t>((size_t)B * H * W * Nproj);
+    half_t* dnorm = sc.out<half_t>((size_t)B * H * W * Cout, "normalised tensor");
+    half_t* dy = sc.out<half_t>((size_t)B * H * W * Nproj, "out");
     SD_REQUIRE(conv_fast_path_ok(d), kInvalidArgument, "conv2d_groupnorm_proj: the producer must run on the MFMA path");
     float* partial = poisoned_gn_partial(sc, B, H * W, groups);
     d.gn_partial = partial;
@@ -1090,11 +1085,11 @@ int sd_op_conv2d_groupnorm_conv3x3(const void* x, const void* w, const float* bi
   return guarded([&] {
     SD_REQUIRE(x && w && gn_weight && gn_bias && w2 && out, kInvalidArgument, "NULL argument");
     SD_REQUIRE(ksize == 1 || ksize == 3, kInvalidArgument, "conv2d_groupnorm_conv3x3: ksize %d", ksize);
-    Scratch sc;
+    Scratch sc("conv2d_groupnorm_conv3x3");
     ConvDesc d = producer_conv(sc, x, w, bias, res, B, Cin, H, W, Cout, ksize, tile);
     half_t* dconv = d.out;
-    half_t* dnorm = sc.dev<half_t>((size_t)B * H * W * Cout);
-    half_t* dy = sc.dev<half_t>((size_t)B * H * W * N2);
+    half_t* dnorm = sc.out<half_t>((size_t)B * H * W * Cout, "normalised tensor");
+    half_t* dy = sc.out<half_t>((size_t)B * H * W * N2, "out");
     SD_REQUIRE(conv_fast_path_ok(d), kInvalidArgument, "conv2d_groupnorm_conv3x3: the producer must run on the MFMA path");
     float* partial = poisoned_gn_partial(sc, B, H * W, groups);
     d.gn_partial = partial;
@@ -1138,7 +1133,7 @@ int sd_op_cross_attention_fused(const void* x, const float* ln_weight, const flo
     const int C = heads * 64;
     SD_REQUIRE(B > 0 && heads > 0 && xattn_fused_ok(C, heads, Sq, Sk), kUnsupported,
                "cross_attention_fused: heads %d x 64 channels, Sq %d, Sk %d (<= 96)", heads, Sq, Sk);
-    Scratch sc;
+    Scratch sc("cross_attention_fused");
     const int ldv = (Sk + 7) / 8 * 8;
     const FoldedProj fq = upload_ln_folded(sc, wq, nullptr, ln_weight, ln_bias, C, C, false);
     XAttnDesc d;
@@ -1148,7 +1143,7 @@ int sd_op_cross_attention_fused(const void* x, const float* ln_weight, const flo
     d.colsum = fq.colsum;
     d.k = upload_tokens(sc, k, B, C, Sk);
     d.vt = upload_vt(sc, v, B, C, Sk, ldv, false);
-    half_t* o = sc.dev<half_t>((size_t)B * Sq * C);
+    half_t* o = sc.out<half_t>((size_t)B * Sq * C, "out");
     d.out = o;
     d.M = B * Sq; d.C = C; d.S = Sq; d.L = Sk; d.ldv = ldv; d.heads = heads;
     d.ln_eps = eps;
@@ -1170,7 +1165,7 @@ int sd_op_cross_attention_block(const void* x, const float* ln_weight, const flo
                "cross_attention_block: heads %d x 64 channels, Sq %d, Sk %d (<= 96)", heads, Sq, Sk);
     SD_REQUIRE(!fused || (xattn_out_ok(C, heads, Sq, Sk) && (!pre || heads == 5)), kUnsupported,
                "cross_attention_block: the one-launch form takes 5 or 10 heads (with a1: 5) and Sq %% 32 == 0 (heads %d, Sq %d)", heads, Sq);
-    Scratch sc;
+    Scratch sc("cross_attention_block");
     const int ldv = (Sk + 7) / 8 * 8;
     half_t* dx = upload_tokens(sc, x, B, C, Sq);
     half_t* da1 = pre ? upload_tokens(sc, a1, B, C, Sq) : nullptr;
@@ -1181,19 +1176,19 @@ int sd_op_cross_attention_block(const void* x, const float* ln_weight, const flo
     float* dbo = sc.dev<float>(C, bo);
     half_t* dwo1 = pre ? sc.dev<half_t>((size_t)C * C, f16(wo1)) : nullptr;
     float* dbo1 = pre ? sc.dev<float>(C, bo1) : nullptr;
-    half_t* dh1 = sc.dev<half_t>((size_t)B * Sq * C);
-    half_t* da2 = sc.dev<half_t>((size_t)B * Sq * C);
-    half_t* o = sc.dev<half_t>((size_t)B * Sq * C);
+    half_t* dh1 = sc.out<half_t>((size_t)B * Sq * C, "h1");
+    half_t* da2 = sc.out<half_t>((size_t)B * Sq * C, "attention output");
+    half_t* o = sc.out<half_t>((size_t)B * Sq * C, "out");
     if (fused) {
-      half_t* wq_t = sc.dev<half_t>((size_t)C * C);
-      half_t* wo_t = sc.dev<half_t>((size_t)C * C);
+      half_t* wq_t = sc.out<half_t>((size_t)C * C, "wq_t");
+      half_t* wo_t = sc.out<half_t>((size_t)C * C, "wo_t");
       launch_xattn_out_retile(fq.w, wq_t, C, sc.stream);
       launch_xattn_out_retile(dwo, wo_t, C, sc.stream);
       XAttnOutDesc d;
       d.x = pre ? da1 : dx; d.wq_t = wq_t; d.q_bias = fq.bias; d.q_colsum = fq.colsum; d.k = dk; d.vt = dvt; d.wo_t = wo_t; d.o_bias = dbo; d.out = o;
       d.M = B * Sq; d.C = C; d.S = Sq; d.L = Sk; d.ldv = ldv; d.heads = heads; d.ln_eps = eps;
       if (pre) {
-        half_t* wo1_t = sc.dev<half_t>((size_t)C * C);
+        half_t* wo1_t = sc.out<half_t>((size_t)C * C, "wo1_t");
         launch_xattn_out_retile(dwo1, wo1_t, C, sc.stream);
         d.h0 = dx; d.wo1_t = wo1_t; d.o1_bias = dbo1;
       }
@@ -1230,7 +1225,7 @@ int sd_op_ffn_out_proj(const void* g, const void* w1, const float* b1, const voi
     SD_REQUIRE(fused >= 0 && fused <= 5, kInvalidArgument, "ffn_out_proj: fused code %d", fused);
     SD_REQUIRE(fused != 1 || ffn_proj_ok(C, K1, M, S), kUnsupported, "ffn_out_proj: the one-launch form takes C = 320 and S %% 32 == 0 (C=%d S=%d)", C, S);
     SD_REQUIRE(!gn_sums || (groups >= 1 && C % groups == 0), kInvalidArgument, "ffn_out_proj: groups %d", groups);
-    Scratch sc;
+    Scratch sc("ffn_out_proj");
     half_t* dg = upload_tokens(sc, g, B, K1, S);
     half_t* dr1 = upload_tokens(sc, res1, B, C, S);
     half_t* dr2 = upload_tokens(sc, res2, B, C, S);
@@ -1238,14 +1233,14 @@ int sd_op_ffn_out_proj(const void* g, const void* w1, const float* b1, const voi
     half_t* dw2 = sc.dev<half_t>((size_t)C * C, f16(w2));
     float* db1 = sc.dev<float>(C, b1);
     float* db2 = sc.dev<float>(C, b2);
-    half_t* dh3 = sc.dev<half_t>((size_t)M * C);
-    half_t* o = sc.dev<half_t>((size_t)M * C);
+    half_t* dh3 = sc.out<half_t>((size_t)M * C, "h3");
+    half_t* o = sc.out<half_t>((size_t)M * C, "out");
     const size_t pf = gn_sums ? groupnorm_scratch_floats(B, S, groups) : 0;
     float* partial = gn_sums ? poisoned_gn_partial(sc, B, S, groups) : nullptr;   // only what the producer wrote may be folded
     int n_entries = 0;
     if (fused >= 2) {   // the merged tail: weight fold (once per handle, outside the timed region), then ONE two-source GEMM
-      half_t* wm = sc.dev<half_t>((size_t)C * (K1 + C));
-      float* bm = sc.dev<float>(C);
+      half_t* wm = sc.out<half_t>((size_t)C * (K1 + C), "merged weights");
+      float* bm = sc.out<float>(C, "merged bias");
       launch_wfold(dw2, db2, dw1, db1, wm, bm, C, C, K1, sc.stream);
       ConvDesc cd = token_gemm(dg, K1, wm, bm, dr2, o, B, S, C);
       cd.x1 = dr1;
@@ -1258,8 +1253,8 @@ int sd_op_ffn_out_proj(const void* g, const void* w1, const float* b1, const voi
       ConvWorkspace ws = workspace_for(sc, {cd});
       sc.timed(iters, ms, [&] { n_entries = launch_conv(cd, ws, sc.stream); });
     } else if (fused) {
-      half_t* w1_t = sc.dev<half_t>((size_t)C * K1);
-      half_t* w2_t = sc.dev<half_t>((size_t)C * C);
+      half_t* w1_t = sc.out<half_t>((size_t)C * K1, "w1_t");
+      half_t* w2_t = sc.out<half_t>((size_t)C * C, "w2_t");
       launch_xattn_out_retile_nk(dw1, w1_t, C, K1, sc.stream);
       launch_xattn_out_retile_nk(dw2, w2_t, C, C, sc.stream);
       FfnProjDesc d;
@@ -1299,13 +1294,13 @@ int sd_op_ffn_out_proj(const void* g, const void* w1, const float* b1, const voi
 int sd_op_fold_linear(const void* wp, const float* bp, const void* w2, const float* b2, void* wm_out, float* bm_out, int N, int J, int K) {
   return guarded([&] {
     SD_REQUIRE(wp && bp && w2 && b2 && wm_out && bm_out && N > 0 && J > 0 && K > 0, kInvalidArgument, "fold_linear: N=%d J=%d K=%d", N, J, K);
-    Scratch sc;
+    Scratch sc("fold_linear");
     half_t* dwp = sc.dev<half_t>((size_t)N * J, f16(wp));
     half_t* dw2 = sc.dev<half_t>((size_t)J * K, f16(w2));
     float* dbp = sc.dev<float>(N, bp);
     float* db2 = sc.dev<float>(J, b2);
-    half_t* merged = sc.dev<half_t>((size_t)N * (K + J));
-    float* bm = sc.dev<float>(N);
+    half_t* merged = sc.out<half_t>((size_t)N * (K + J), "merged weights");
+    float* bm = sc.out<float>(N, "merged bias");
     launch_wfold(dwp, dbp, dw2, db2, merged, bm, N, J, K, sc.stream);
     SD_HIP(hipStreamSynchronize(sc.stream));
     SD_HIP(hipMemcpy2D(wm_out, (size_t)K * 2, merged, (size_t)(K + J) * 2, (size_t)K * 2, N, hipMemcpyDeviceToHost));
@@ -1320,7 +1315,7 @@ int sd_op_fold_linear(const void* wp, const float* bp, const void* w2, const flo
 int sd_op_geglu(const void* x, const void* w, const float* bias, void* out, int M, int C, int N2, int iters, float* ms) {
   return guarded([&] {
     SD_REQUIRE(x && w && out && N2 % 2 == 0, kInvalidArgument, "bad GEGLU arguments");
-    Scratch sc;
+    Scratch sc("geglu");
     const int half_n = N2 / 2;
     SD_REQUIRE(half_n % 32 == 0, kUnsupported, "GEGLU needs (N/2) %% 32 == 0");
     std::vector<half_t> wt((size_t)N2 * C);
@@ -1328,7 +1323,7 @@ int sd_op_geglu(const void* x, const void* w, const float* bias, void* out, int 
     std::vector<float> bt(N2, 0.f);
     if (bias)
       for (int o = 0; o < N2; ++o) bt[geglu_row(o, N2)] = bias[o];
-    half_t* dout = sc.dev<half_t>((size_t)M * half_n);
+    half_t* dout = sc.out<half_t>((size_t)M * half_n, "out");
     ConvDesc d = token_gemm(sc.dev<half_t>((size_t)M * C, f16(x)), C, sc.dev<half_t>(wt.size(), wt.data()),
                             bias ? sc.dev<float>(N2, bt.data()) : nullptr, nullptr, dout, 1, M, N2);
     d.out_mode = kOutGeglu;
@@ -1358,10 +1353,10 @@ int sd_op_geglu_ln(const void* x, const float* ln_weight, const float* ln_bias, 
     kernel %= 10;
     SD_REQUIRE(x && w && out && N2 % 64 == 0 && (ln_weight == nullptr) == (ln_bias == nullptr) && kernel >= 0 && kernel <= 9 &&
                    (abl == 0 || kernel == 2), kInvalidArgument, "bad GEGLU arguments");
-    Scratch sc;
+    Scratch sc("geglu_ln");
     const int half_n = N2 / 2;
     const FoldedProj f = upload_ln_folded(sc, w, bias, ln_weight, ln_bias, N2, C, true);
-    half_t* dout = sc.dev<half_t>((size_t)M * half_n);
+    half_t* dout = sc.out<half_t>((size_t)M * half_n, "out");
     ConvDesc d = token_gemm(sc.dev<half_t>((size_t)M * C, f16(x)), C, f.w, f.bias, nullptr, dout, 1, M, N2);
     if (ln_weight) d.ln_colsum = f.colsum;
     d.ln_eps = eps;
@@ -1378,7 +1373,7 @@ int sd_op_geglu_ln(const void* x, const float* ln_weight, const float* ln_bias, 
       d.staging = sg_variant;
       if (sg_clock) {
         sg_prof = smgeglu_prof_entries(d, d.staging);
-        d.prof = sc.dev<long long>(sg_prof);
+        d.prof = sc.out<long long>(sg_prof, "phase clock");
       }
     } else if (kernel >= 3) {
       tile_for_bvgemm(sc, d, "GEGLU shape not eligible for plan tile 11 (bvgemm.hip)");
@@ -1387,7 +1382,7 @@ int sd_op_geglu_ln(const void* x, const float* ln_weight, const float* ln_bias, 
       d.staging = kernel - 3;
     }
     d.debug = abl;
-    if (abl == 5) d.prof = sc.dev<long long>(64);
+    if (abl == 5) d.prof = sc.out<long long>(64, "phase clock");
     ConvWorkspace ws;
     sc.timed(iters, ms, [&] { launch_conv(d, ws, sc.stream); });
     if (sg_prof) {   // every wave's stamps of the last launch: cycles from kernel entry to the end of each phase
@@ -1444,8 +1439,8 @@ int sd_op_geglu_palettized(const void* x, const float* ln_weight, const float* l
     for (size_t i = 0; i < w.size(); ++i) w[i] = f16(lut)[indices[i]];
     std::vector<float> bf(N2), cs(N2);
     fold_layernorm_rows(w.data(), bias, ln_weight, ln_bias, N2, C, 0, true, wf.data(), cs.data(), bf.data());
-    Scratch sc;
-    half_t* dout = sc.dev<half_t>((size_t)M * (N2 / 2));
+    Scratch sc("geglu_palettized");
+    half_t* dout = sc.out<half_t>((size_t)M * (N2 / 2), "out");
     d.x0 = sc.dev<half_t>((size_t)M * C, f16(x));
     d.out = dout;
     d.bias = sc.dev<float>(N2, bf.data());
@@ -1483,11 +1478,11 @@ int sd_op_qkv_ln(const void* x, const float* ln_weight, const float* ln_bias, co
   return guarded([&] {
     SD_REQUIRE(x && ln_weight && ln_bias && w && out_qk && out_vt && B >= 1 && HW >= 1 && C % 64 == 0 && kernel >= 0 && kernel <= 9,
                kInvalidArgument, "bad q|k|v arguments");
-    Scratch sc;
+    Scratch sc("qkv_ln");
     const int N = 3 * C, M = B * HW;
     const FoldedProj f = upload_ln_folded(sc, w, nullptr, ln_weight, ln_bias, N, C, false);
-    half_t* dqk = sc.dev<half_t>((size_t)M * 2 * C);
-    half_t* dvt = sc.dev<half_t>((size_t)B * C * HW);
+    half_t* dqk = sc.out<half_t>((size_t)M * 2 * C, "out_qk");
+    half_t* dvt = sc.out<half_t>((size_t)B * C * HW, "out_vt");
     ConvDesc d = qkv_desc(sc.dev<half_t>((size_t)M * C, f16(x)), f, eps, dqk, dvt, B, 1, HW, C, q_scale, vt_perm);
     SD_REQUIRE(conv_fast_path_ok(d), kUnsupported, "q|k|v shape off the MFMA path (C=%d)", C);
     const ConvWeightCopies copies = conv_plan_copies(d);   // what the library's own plan (kernel 0) reads
@@ -1524,8 +1519,8 @@ int sd_op_gn_proj_qkv(const void* x_in, const void* conv_w, const float* gn_weig
                kInvalidArgument, "NULL argument");
     const int HW = H * W, M = B * HW, N = 3 * C;
     SD_REQUIRE(gn_proj_qkv_ok(C, C / 64, HW, M, HW, groups), kInvalidArgument, "gn_proj_qkv: C=%d HW=%d groups=%d", C, HW, groups);
-    Scratch sc;
-    half_t* dx = sc.dev<half_t>((size_t)M * C);
+    Scratch sc("gn_proj_qkv");
+    half_t* dx = sc.out<half_t>((size_t)M * C, "producer's output x");
     // the producer
     ConvDesc d = conv_desc(upload_nhwc(sc, x_in, B, C, H, W), C, sc.dev<half_t>((size_t)C * C, f16(conv_w)), nullptr, nullptr, dx, B, H, W, C);
     d.splitk = 1;
@@ -1537,12 +1532,12 @@ int sd_op_gn_proj_qkv(const void* x_in, const void* conv_w, const float* gn_weig
     const FoldedProj fq = upload_ln_folded(sc, wqkv, nullptr, ln_weight, ln_bias, N, C, false);   // LayerNorm fold of the fused q|k|v
     half_t* dwp = sc.dev<half_t>((size_t)C * C, f16(proj_w));
     float* dpb = sc.dev<float>(C, proj_bias);
-    half_t* dnorm = sc.dev<half_t>((size_t)M * C);
-    half_t* dh = sc.dev<half_t>((size_t)M * C);
-    half_t* dqk = sc.dev<half_t>((size_t)M * 2 * C);
-    half_t* dvt = sc.dev<half_t>((size_t)B * C * HW);
-    half_t* dwp_t = sc.dev<half_t>((size_t)C * C);
-    half_t* dwq_t = sc.dev<half_t>((size_t)N * C);
+    half_t* dnorm = sc.out<half_t>((size_t)M * C, "normalised tensor");
+    half_t* dh = sc.out<half_t>((size_t)M * C, "out_h");
+    half_t* dqk = sc.out<half_t>((size_t)M * 2 * C, "out_qk");
+    half_t* dvt = sc.out<half_t>((size_t)B * C * HW, "out_vt");
+    half_t* dwp_t = sc.out<half_t>((size_t)C * C, "wp_t");
+    half_t* dwq_t = sc.out<half_t>((size_t)N * C, "wqkv_t");
     launch_xattn_out_retile_nk(dwp, dwp_t, C, C, sc.stream);
     launch_xattn_out_retile_nk(fq.w, dwq_t, N, C, sc.stream);
     ConvDesc pd = conv_desc(dnorm, C, dwp, dpb, nullptr, dh, B, H, W, C);                      // proj_in of the three-launch path
@@ -1552,7 +1547,7 @@ int sd_op_gn_proj_qkv(const void* x_in, const void* conv_w, const float* gn_weig
     int n_entries = 0;
     static const bool want_clk = tune_env_set("SD_GQ_CLOCK");   // phase clock of the one-launch kernel, printed to stderr
     const size_t n_clk = (size_t)(M / 32) * 5 * 16;
-    long long* dclk = want_clk && fused ? sc.dev<long long>(n_clk) : nullptr;
+    long long* dclk = want_clk && fused ? sc.out<long long>(n_clk, "phase clock") : nullptr;
     sc.timed(iters, ms, [&] {
       n_entries = launch_conv(d, ws, sc.stream);
       const bool have = n_entries >= 1 && n_entries <= 128;
@@ -1711,9 +1706,9 @@ int sd_op_timestep_embedding(const float* t, float* out, int n, int dim, int fli
   return guarded([&] {
     SD_REQUIRE(t && out && n > 0 && dim > 0 && dim % 2 == 0, kInvalidArgument, "bad arguments");
     SD_REQUIRE(flip_sin_to_cos == 1, kUnsupported, "flip_sin_to_cos=False is not on the path");
-    Scratch sc;
+    Scratch sc("timestep_embedding");
     float* dt = sc.dev<float>(n, t);
-    float* dout = sc.dev<float>((size_t)n * dim);
+    float* dout = sc.out<float>((size_t)n * dim, "out");
     std::vector<float> f = timestep_freq_table(dim, freq_shift);
     float* df = sc.dev<float>(f.size(), f.data());
     launch_timestep_embedding(dt, df, dout, n, dim, sc.stream);
@@ -1723,30 +1718,25 @@ int sd_op_timestep_embedding(const float* t, float* out, int n, int dim, int fli
 }
 
 // The image-to-image start on its own (misc.hip posterior_noise_kernel): moments (2 * Cz, h, w) f32 = [mean | logvar] of one image,
-// eps (Cz, h, w), noise / out (n_images, Cz, h, w) f32.  The device output sits in front of a poisoned guard that a launch must leave alone.
+// eps (Cz, h, w), noise / out (n_images, Cz, h, w) f32.
 int sd_op_posterior_noise(const float* moments, const float* eps, const float* noise, float* out, int Cz, int h, int w, int n_images,
                           float scale_factor, float sa, float sb, int iters, float* ms) {
   return guarded([&] {
     SD_REQUIRE(moments && eps && noise && out, kInvalidArgument, "NULL argument");
     SD_REQUIRE(Cz > 0 && h > 0 && w > 0 && n_images > 0, kInvalidArgument, "posterior_noise: Cz=%d h=%d w=%d n_images=%d", Cz, h, w, n_images);
-    Scratch sc;
-    const size_t n = (size_t)Cz * h * w, total = (size_t)n_images * n, guard = 256;
+    Scratch sc("posterior_noise");
+    const size_t n = (size_t)Cz * h * w, total = (size_t)n_images * n;
     float* dm = sc.dev<float>(2 * n, moments);
     float* de = sc.dev<float>(n, eps);
     float* dn = sc.dev<float>(total, noise);
-    float* dout = sc.dev<float>(total + guard);
-    SD_HIP(hipMemset(dout, 0xff, (total + guard) * sizeof(float)));   // 0xffffffff: a NaN
+    float* dout = sc.out<float>(total, "out");
     sc.timed(iters, ms, [&] { launch_posterior_noise(dm, de, dn, dout, n, n_images, scale_factor, sa, sb, sc.stream); });
-    SD_HIP(hipStreamSynchronize(sc.stream));
-    std::vector<uint32_t> g(guard);
-    SD_HIP(hipMemcpy(g.data(), dout + total, guard * sizeof(float), hipMemcpyDeviceToHost));
-    for (uint32_t v : g) SD_REQUIRE(v == 0xffffffffu, kInternal, "posterior_noise wrote behind its %zu outputs", total);
     SD_HIP(hipMemcpy(out, dout, total * sizeof(float), hipMemcpyDeviceToHost));
   });
 }
 
 // One launch of cfg_sched_step_kernel (misc.hip) the way the loop launches it, from a zeroed step counter and ticket; the one-row
-// tables sit at step 0.  Latents, history and the de-noised tap's output each sit in front of a poisoned guard.
+// tables sit at step 0.
 int sd_op_sched_step(const float* noise_pred, float* latents, float* hist, const float* coef, const float* pred, const float* step_noise,
                      float guidance, int cfg, int history, int n_images, int n, float* denoised, int* step_after) {
   return guarded([&] {
@@ -1755,24 +1745,15 @@ int sd_op_sched_step(const float* noise_pred, float* latents, float* hist, const
                "sched_step: cfg=%d history=%d n_images=%d n=%d", cfg, history, n_images, n);
     SD_REQUIRE((history == 0 || hist) && (pred != nullptr) == (denoised != nullptr), kInvalidArgument,
                "sched_step: history > 0 needs hist, and pred and denoised go together");
-    Scratch sc;
-    const size_t total = (size_t)n_images * n, guard = 256;
-    auto guarded_buf = [&](const float* host, size_t count) {
-      float* d = sc.dev<float>(count + guard);
-      SD_HIP(hipMemset(d, 0xff, (count + guard) * sizeof(float)));   // 0xffffffff: a NaN
-      if (host) SD_HIP(hipMemcpy(d, host, count * sizeof(float), hipMemcpyHostToDevice));
-      return d;
-    };
-    auto check_guard = [&](const float* d, size_t count, const char* what) {
-      std::vector<uint32_t> g(guard);
-      SD_HIP(hipMemcpy(g.data(), d + count, guard * sizeof(float), hipMemcpyDeviceToHost));
-      for (uint32_t v : g) SD_REQUIRE(v == 0xffffffffu, kInternal, "sched_step wrote behind its %zu %s", count, what);
-    };
+    Scratch sc("sched_step");
+    const size_t total = (size_t)n_images * n;
     float* dnp = sc.dev<float>((size_t)cfg * total, noise_pred);
-    float* dlat = guarded_buf(latents, total);
-    float* dhist = history ? guarded_buf(hist, (size_t)history * total) : nullptr;
-    float* dden = pred ? guarded_buf(nullptr, total) : nullptr;
-    int* dstep = sc.dev<int>(2);   // zeroed: [0] the step counter, [1] the ticket
+    float* dlat = sc.dev<float>(total, latents, "latents");
+    float* dhist = history ? sc.dev<float>((size_t)history * total, hist, "history entries") : nullptr;
+    float* dden = pred ? sc.out<float>(total, "de-noised latents") : nullptr;
+    // zeroed: [0] the step counter, which the loop starts at 0 and the kernel advances, [1] the arrival ticket, which the last
+    // workgroup to arrive puts back to 0
+    int* dstep = sc.zeroed<int>(2, "step counter | ticket");
     LoopTables tab{};
     tab.coef = sc.dev<float>(8, coef);
     tab.step = dstep;
@@ -1784,9 +1765,6 @@ int sd_op_sched_step(const float* noise_pred, float* latents, float* hist, const
     }
     launch_cfg_sched_step(dnp, dlat, dhist, tab, guidance, n_images, n, cfg, history, sc.stream);
     SD_HIP(hipStreamSynchronize(sc.stream));
-    check_guard(dlat, total, "latents");
-    if (dhist) check_guard(dhist, (size_t)history * total, "history entries");
-    if (dden) check_guard(dden, total, "de-noised latents");
     int st[2];
     SD_HIP(hipMemcpy(st, dstep, sizeof(st), hipMemcpyDeviceToHost));
     SD_REQUIRE(st[1] == 0, kInternal, "sched_step left its arrival ticket at %d", st[1]);
@@ -1809,29 +1787,22 @@ int sd_op_resample_coeffs(int in_size, int out_size, int* ksize, int32_t* bounds
   });
 }
 
-// imgpost.hip image_rgb8_kernel on host arrays: image (B, 3, H, W) f32 -> rgb8 (B, H, W, 3).  The device output sits in front of a
-// guard; both are filled with 0xa5 before the launch, and a launch that wrote into the guard fails the call.
+// imgpost.hip image_rgb8_kernel on host arrays: image (B, 3, H, W) f32 -> rgb8 (B, H, W, 3).
 int sd_op_image_rgb8(const float* image, uint8_t* rgb8, int B, int H, int W, int iters, float* ms) {
   return guarded([&] {
     SD_REQUIRE(image && rgb8, kInvalidArgument, "NULL argument");
     SD_REQUIRE(B > 0 && H > 0 && W > 0, kInvalidArgument, "image_rgb8: B=%d H=%d W=%d", B, H, W);
-    Scratch sc;
-    const size_t n = (size_t)B * H * W * 3, guard = 4096;
+    Scratch sc("image_rgb8");
+    const size_t n = (size_t)B * H * W * 3;
     float* din = sc.dev<float>(n, image);
-    uint8_t* dout = sc.dev<uint8_t>(n + guard);
-    SD_HIP(hipMemset(dout, 0xa5, n + guard));
+    uint8_t* dout = sc.out<uint8_t>(n, "rgb8", kOpGuard, 0xa5);   // (0xff is white: the bytes start as 0xa5)
     sc.timed(iters, ms, [&] { launch_image_rgb8(din, dout, B, H, W, sc.stream); });
-    SD_HIP(hipStreamSynchronize(sc.stream));
-    std::vector<uint8_t> g(guard);
-    SD_HIP(hipMemcpy(g.data(), dout + n, guard, hipMemcpyDeviceToHost));
-    for (uint8_t v : g) SD_REQUIRE(v == 0xa5, kInternal, "image_rgb8 wrote behind its %zu output bytes", n);
     SD_HIP(hipMemcpy(rgb8, dout, n, hipMemcpyDeviceToHost));
   });
 }
 
 // imgpost.hip clip_input_kernel on host arrays: rgb8 (B, H, W, 3) -> clip_input (B, 3, S, S) f16.  The geometry is checked and the
-// tables are built on the host before any device work.  The device output sits in front of a guard; both are filled with NaN patterns
-// before the launch, and a launch that wrote into the guard fails the call.
+// tables are built on the host before any device work.
 int sd_op_clip_input(const uint8_t* rgb8, void* clip_input, int B, int H, int W, int rh, int rw, int S, const float* mean3, const float* std3,
                      int iters, float* ms) {
   return guarded([&] {
@@ -1843,69 +1814,52 @@ int sd_op_clip_input(const uint8_t* rgb8, void* clip_input, int B, int H, int W,
       SD_REQUIRE(std3[c] != 0.f, kInvalidArgument, "clip_input: std[%d] is 0", c);
       d.mean[c] = mean3[c], d.std[c] = std3[c];
     }
-    Scratch sc;
+    Scratch sc("clip_input");
     d.hbounds = sc.dev<int32_t>(plan.hbounds.size(), plan.hbounds.data());
     d.hcoeffs = sc.dev<int32_t>(plan.hcoeffs.size(), plan.hcoeffs.data());
     d.vbounds = sc.dev<int32_t>(plan.vbounds.size(), plan.vbounds.data());
     d.vcoeffs = sc.dev<int32_t>(plan.vcoeffs.size(), plan.vcoeffs.data());
     d.H = H, d.W = W, d.S = S, d.top = (rh - S) / 2, d.left = (rw - S) / 2, d.ksh = plan.ksh, d.ksv = plan.ksv;
-    const size_t n = (size_t)B * 3 * S * S, guard = 4096;
+    const size_t n = (size_t)B * 3 * S * S;
     uint8_t* din = sc.dev<uint8_t>((size_t)B * H * W * 3, rgb8);
-    half_t* dout = sc.dev<half_t>(n + guard);
-    SD_HIP(hipMemset(dout, 0xff, (n + guard) * sizeof(half_t)));   // 0xffff: a NaN
+    half_t* dout = sc.out<half_t>(n, "clip_input");
     sc.timed(iters, ms, [&] { launch_clip_input(din, dout, B, d, plan.lds_bytes, sc.stream); });
-    SD_HIP(hipStreamSynchronize(sc.stream));
-    std::vector<uint16_t> g(guard);
-    SD_HIP(hipMemcpy(g.data(), dout + n, guard * sizeof(half_t), hipMemcpyDeviceToHost));
-    for (uint16_t v : g) SD_REQUIRE(v == 0xffff, kInternal, "clip_input wrote behind its %zu outputs", n);
     SD_HIP(hipMemcpy(clip_input, dout, n * sizeof(half_t), hipMemcpyDeviceToHost));
   });
 }
 
 // The safety checker's attention (vit.hip) on the layout its handle feeds it: qkv (B * S, 3 * heads * d) f16 rows [q | k | v] ->
-// out (B * S, heads * d) f16.  The device output sits in front of a guard of 64 rows; both are filled with NaN patterns before the
-// launch, and a launch that wrote into the guard fails the call.
+// out (B * S, heads * d) f16.
 int sd_op_vit_attention(const void* qkv, void* out, int B, int S, int heads, int d, int iters, float* ms) {
   return guarded([&] {
     SD_REQUIRE(qkv && out, kInvalidArgument, "NULL argument");
     SD_REQUIRE(B > 0 && S > 0 && heads > 0 && d > 0, kInvalidArgument, "empty attention problem");
     SD_REQUIRE(vit_attention_ok(d), kUnsupported, "vit_attention: head dim %d (the kernel is built for 64)", d);
-    Scratch sc;
+    Scratch sc("vit_attention");
     const int D = heads * d;
-    const size_t n = (size_t)B * S * D, guard = (size_t)64 * D;
+    const size_t n = (size_t)B * S * D;
     half_t* dq = sc.dev<half_t>((size_t)B * S * 3 * D, f16(qkv));
-    half_t* dout = sc.dev<half_t>(n + guard);
-    SD_HIP(hipMemset(dout, 0xff, (n + guard) * sizeof(half_t)));   // 0xffff: a NaN
+    half_t* dout = sc.out<half_t>(n, "out", (size_t)64 * D);   // a guard of 64 rows: one query tile
     sc.timed(iters, ms, [&] { launch_vit_attention(dq, dout, B, S, heads, d, sc.stream); });
-    SD_HIP(hipStreamSynchronize(sc.stream));
-    std::vector<uint16_t> g(guard);
-    SD_HIP(hipMemcpy(g.data(), dout + n, guard * sizeof(half_t), hipMemcpyDeviceToHost));
-    for (uint16_t v : g) SD_REQUIRE(v == 0xffff, kInternal, "vit_attention wrote behind its %d output rows", B * S);
     SD_HIP(hipMemcpy(out, dout, n * sizeof(half_t), hipMemcpyDeviceToHost));
   });
 }
 
 // The VAE's mid-block attention (vae_attention.hip) on the layout its handle feeds it: q / k / v (B * S, C) f16 -> out (B * S, C) f16.
-// Everything that can be refused is refused before any device work.  The device output sits in front of a guard of 64 rows; both are
-// filled with NaN patterns before the launch, and a launch that wrote into the guard fails the call.
+// Everything that can be refused is refused before any device work.
 int sd_op_vae_attention(const void* q, const void* k, const void* v, void* out, int B, int S, int C, int iters, float* ms) {
   return guarded([&] {
     SD_REQUIRE(q && k && v && out, kInvalidArgument, "NULL argument");
     SD_REQUIRE(B > 0 && S > 0 && C > 0, kInvalidArgument, "empty attention problem");
     SD_REQUIRE(vae_attention_ok(C), kUnsupported, "vae_attention: head dim %d (the kernel is built for 64, 128, 256 and 512)", C);
     SD_REQUIRE(B <= 65535, kInvalidArgument, "vae_attention: B=%d", B);
-    Scratch sc;
-    const size_t n = (size_t)B * S * C, guard = (size_t)64 * C;
+    Scratch sc("vae_attention");
+    const size_t n = (size_t)B * S * C;
     half_t* dq = sc.dev<half_t>(n, f16(q));
     half_t* dk = sc.dev<half_t>(n, f16(k));
     half_t* dv = sc.dev<half_t>(n, f16(v));
-    half_t* dout = sc.dev<half_t>(n + guard);
-    SD_HIP(hipMemset(dout, 0xff, (n + guard) * sizeof(half_t)));   // 0xffff: a NaN
+    half_t* dout = sc.out<half_t>(n, "out", (size_t)64 * C);   // a guard of 64 rows: one query tile
     sc.timed(iters, ms, [&] { launch_vae_attention(dq, dk, dv, dout, B, S, C, sc.stream); });
-    SD_HIP(hipStreamSynchronize(sc.stream));
-    std::vector<uint16_t> g(guard);
-    SD_HIP(hipMemcpy(g.data(), dout + n, guard * sizeof(half_t), hipMemcpyDeviceToHost));
-    for (uint16_t x : g) SD_REQUIRE(x == 0xffff, kInternal, "vae_attention wrote behind its %d output rows", B * S);
     SD_HIP(hipMemcpy(out, dout, n * sizeof(half_t), hipMemcpyDeviceToHost));
   });
 }
@@ -1918,15 +1872,15 @@ int sd_op_safety_head(const float* image_embeds, const float* concept_embeds, co
     SD_REQUIRE(image_embeds && concept_embeds && concept_w && has_nsfw && concept_scores, kInvalidArgument, "NULL argument");
     SD_REQUIRE(B > 0 && P > 0 && n_concepts > 0 && n_special >= 0 && (n_special == 0 || (special_embeds && special_w)), kInvalidArgument,
                "safety_head: B=%d P=%d concepts=%d special=%d", B, P, n_concepts, n_special);
-    Scratch sc;
+    Scratch sc("safety_head");
     float* di = sc.dev<float>((size_t)B * P, image_embeds);
     float* dc = sc.dev<float>((size_t)n_concepts * P, concept_embeds);
     float* dcw = sc.dev<float>(n_concepts, concept_w);
     float* ds = n_special ? sc.dev<float>((size_t)n_special * P, special_embeds) : nullptr;
     float* dsw = n_special ? sc.dev<float>(n_special, special_w) : nullptr;
     float* dadj = sc.dev<float>(1, &adjustment);
-    float* dflag = sc.dev<float>(B);
-    float* dscore = sc.dev<float>((size_t)B * n_concepts);
+    float* dflag = sc.out<float>(B, "has_nsfw");
+    float* dscore = sc.out<float>((size_t)B * n_concepts, "concept_scores");
     launch_safety_head(di, dc, ds, dcw, dsw, dadj, B, P, n_concepts, n_special, dflag, dscore, sc.stream);
     SD_HIP(hipStreamSynchronize(sc.stream));
     SD_HIP(hipMemcpy(has_nsfw, dflag, (size_t)B * sizeof(float), hipMemcpyDeviceToHost));
@@ -1958,7 +1912,7 @@ int sd_op_conv_f32(const float* x, const void* w, int w_kind, const float* bias,
     const int Wo = pad_mode ? (W * up + 1 - ksize) / stride + 1 : (W * up + 2 * pad - ksize) / stride + 1;
     SD_REQUIRE(Ho >= 1 && Wo >= 1, kInvalidArgument, "conv_f32: empty output (%dx%d)", Ho, Wo);
     const size_t nw = (size_t)N * Cin * ksize * ksize, nout = (size_t)B * Ho * Wo * N;
-    Scratch sc;
+    Scratch sc("conv_f32");
     ConvF32Desc d;
     const std::vector<float> xh = host_nhwc(x, B, Cin, H * W);
     d.x = sc.dev<float>(xh.size(), xh.data());
@@ -1979,13 +1933,13 @@ int sd_op_conv_f32(const float* x, const void* w, int w_kind, const float* bias,
       const std::vector<float> rh = host_nhwc(res, B, N, Ho * Wo);
       d.res = sc.dev<float>(rh.size(), rh.data());
     }
-    float* dout = guarded_buf<float>(sc, nout, kOpGuard);
+    float* dout = sc.out<float>(nout, "out");
     d.out = dout;
     d.B = B; d.Hi = H; d.Wi = W; d.Cin = Cin; d.Ho = Ho; d.Wo = Wo; d.N = N;
     d.ksize = ksize; d.stride = stride; d.up = up;
     if (pad_mode) d.pad = 0;
     launch_conv_f32(d, sc.stream);
-    check_guard(sc, dout, nout, kOpGuard, "conv_f32");
+    SD_HIP(hipStreamSynchronize(sc.stream));
     host_nchw(download(dout, nout), out, B, N, Ho * Wo);
   });
 }
@@ -1998,19 +1952,16 @@ int sd_op_groupnorm_f32(const float* x, const float* gamma, const float* beta, f
     SD_REQUIRE(x && gamma && beta && out, kInvalidArgument, "NULL argument");
     SD_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && groups > 0, kInvalidArgument, "groupnorm_f32: B=%d C=%d H=%d W=%d groups=%d", B, C, H, W, groups);
     SD_REQUIRE(C % groups == 0, kUnsupported, "groupnorm_f32: %d channels, %d groups", C, groups);
-    Scratch sc;
+    Scratch sc("groupnorm_f32");
     const size_t n = (size_t)B * C * H * W;
     const std::vector<float> xh = host_nhwc(x, B, C, H * W);
     float* dx = sc.dev<float>(n, xh.data());
-    const size_t sb = groupnorm_f32_scratch_bytes(B, groups);
-    char* scratch = sc.dev<char>(sb);
-    SD_HIP(hipMemset(scratch, 0xff, sb));
-    SD_HIP(hipStreamSynchronize(nullptr));
+    char* scratch = sc.out<char>(groupnorm_f32_scratch_bytes(B, groups), "statistics scratch");
     float* dg = sc.dev<float>(C, gamma);
     float* db = sc.dev<float>(C, beta);
-    float* dout = guarded_buf<float>(sc, n, kOpGuard);
+    float* dout = sc.out<float>(n, "out");
     launch_groupnorm_f32(dx, scratch, dg, db, dout, B, H * W, C, groups, eps, silu ? 1 : 0, sc.stream);
-    check_guard(sc, dout, n, kOpGuard, "groupnorm_f32");
+    SD_HIP(hipStreamSynchronize(sc.stream));
     host_nchw(download(dout, n), out, B, C, H * W);
   });
 }
@@ -2022,17 +1973,17 @@ int sd_op_row_softmax(void* x, int rows, int cols, float scale, int fp32) {
     SD_REQUIRE(x, kInvalidArgument, "NULL argument");
     SD_REQUIRE(rows > 0 && cols > 0 && (fp32 == 0 || fp32 == 1), kInvalidArgument, "row_softmax: rows=%d cols=%d fp32=%d", rows, cols, fp32);
     SD_REQUIRE(fp32 || (cols % 8 == 0 && cols <= 8192), kUnsupported, "row_softmax: cols=%d (need cols %% 8 == 0, <= 8192)", cols);
-    Scratch sc;
+    Scratch sc("row_softmax");
     const size_t n = (size_t)rows * cols;
     if (fp32) {
-      float* d = guarded_buf<float>(sc, n, kOpGuard, reinterpret_cast<const float*>(x));
+      float* d = sc.dev<float>(n, reinterpret_cast<const float*>(x), "x (in place)");
       launch_row_softmax_f32(d, rows, cols, scale, sc.stream);
-      check_guard(sc, d, n, kOpGuard, "row_softmax (fp32)");
+      SD_HIP(hipStreamSynchronize(sc.stream));
       SD_HIP(hipMemcpy(x, d, n * sizeof(float), hipMemcpyDeviceToHost));
     } else {
-      half_t* d = guarded_buf<half_t>(sc, n, kOpGuard, f16(x));
+      half_t* d = sc.dev<half_t>(n, f16(x), "x (in place)");
       launch_row_softmax(d, rows, cols, scale, sc.stream);
-      check_guard(sc, d, n, kOpGuard, "row_softmax");
+      SD_HIP(hipStreamSynchronize(sc.stream));
       SD_HIP(hipMemcpy(x, d, n * sizeof(half_t), hipMemcpyDeviceToHost));
     }
   });
@@ -2047,7 +1998,7 @@ int sd_op_gemv(const void* w, const float* bias, const float* x, float* out, int
     SD_REQUIRE(w && x && out, kInvalidArgument, "NULL argument");
     SD_REQUIRE(B > 0 && N > 0 && K > 0, kInvalidArgument, "gemv: B=%d N=%d K=%d", B, N, K);
     SD_REQUIRE(K % 8 == 0 && K <= 3072, kUnsupported, "gemv: K=%d must be a multiple of 8 and <= 3072", K);
-    Scratch sc;
+    Scratch sc("gemv");
     const int ldx = K + 8, ldo = N + 5, xoff = 4;
     std::vector<float> xr((size_t)B * ldx + xoff, 1.0e30f);
     for (int b = 0; b < B; ++b) std::copy(x + (size_t)b * K, x + (size_t)(b + 1) * K, xr.begin() + xoff + (size_t)b * ldx);
@@ -2055,10 +2006,10 @@ int sd_op_gemv(const void* w, const float* bias, const float* x, float* out, int
     half_t* dw = sc.dev<half_t>((size_t)N * K, f16(w));
     float* db = bias ? sc.dev<float>(N, bias) : nullptr;
     const size_t no = (size_t)B * ldo;
-    float* dout = guarded_buf<float>(sc, no, kOpGuard);
+    float* dout = sc.out<float>(no, "out rows");
     if (accumulate) SD_HIP(hipMemcpy2D(dout, ldo * sizeof(float), out, N * sizeof(float), N * sizeof(float), B, hipMemcpyHostToDevice));
     launch_gemv(dw, db, dx, ldx, dout, ldo, B, N, K, silu_in ? 1 : 0, silu_out ? 1 : 0, accumulate ? 1 : 0, sc.stream);
-    check_guard(sc, dout, no, kOpGuard, "gemv");
+    SD_HIP(hipStreamSynchronize(sc.stream));
     const std::vector<float> t = download(dout, no);
     for (int b = 0; b < B; ++b) {
       for (int c = N; c < ldo; ++c) {
@@ -2078,12 +2029,12 @@ int sd_op_clip_attention(const void* qkv, void* out, int S, int D, int heads) {
     SD_REQUIRE(qkv && out, kInvalidArgument, "NULL argument");
     SD_REQUIRE(S > 0 && D > 0 && heads > 0 && D % heads == 0, kInvalidArgument, "clip_attention: S=%d D=%d heads=%d", S, D, heads);
     SD_REQUIRE(S <= 80 && D / heads <= 128 && (D / heads) % 8 == 0, kUnsupported, "clip_attention: S=%d D=%d heads=%d", S, D, heads);
-    Scratch sc;
+    Scratch sc("clip_attention");
     const size_t n = (size_t)S * D;
     half_t* dq = sc.dev<half_t>(3 * n, f16(qkv));
-    half_t* dout = guarded_buf<half_t>(sc, n, kOpGuard);
+    half_t* dout = sc.out<half_t>(n, "out");
     launch_clip_attention(dq, dout, S, D, heads, sc.stream);
-    check_guard(sc, dout, n, kOpGuard, "clip_attention");
+    SD_HIP(hipStreamSynchronize(sc.stream));
     SD_HIP(hipMemcpy(out, dout, n * sizeof(half_t), hipMemcpyDeviceToHost));
   });
 }
@@ -2095,14 +2046,14 @@ int sd_op_clip_embed(const int32_t* ids, const void* tok, const void* pos, void*
     SD_REQUIRE(ids && tok && pos && out, kInvalidArgument, "NULL argument");
     SD_REQUIRE(S > 0 && D > 0 && vocab > 0, kInvalidArgument, "clip_embed: S=%d D=%d vocab=%d", S, D, vocab);
     SD_REQUIRE(D % 8 == 0, kUnsupported, "clip_embed: hidden size %d", D);
-    Scratch sc;
+    Scratch sc("clip_embed");
     const size_t n = (size_t)S * D;
     int* di = sc.dev<int>(S, ids);
     half_t* dt = sc.dev<half_t>((size_t)vocab * D, f16(tok));
     half_t* dp = sc.dev<half_t>(n, f16(pos));
-    half_t* dout = guarded_buf<half_t>(sc, n, kOpGuard);
+    half_t* dout = sc.out<half_t>(n, "out");
     launch_clip_embed(di, dt, dp, dout, S, D, vocab, sc.stream);
-    check_guard(sc, dout, n, kOpGuard, "clip_embed");
+    SD_HIP(hipStreamSynchronize(sc.stream));
     SD_HIP(hipMemcpy(out, dout, n * sizeof(half_t), hipMemcpyDeviceToHost));
   });
 }
@@ -2112,10 +2063,10 @@ int sd_op_clip_act(void* x, size_t n, int act) {
   return guarded([&] {
     SD_REQUIRE(x, kInvalidArgument, "NULL argument");
     SD_REQUIRE(n > 0 && n % 8 == 0 && (act == 0 || act == 1), kInvalidArgument, "clip_act: n=%zu act=%d", n, act);
-    Scratch sc;
-    half_t* d = guarded_buf<half_t>(sc, n, kOpGuard, f16(x));
+    Scratch sc("clip_act");
+    half_t* d = sc.dev<half_t>(n, f16(x), "x (in place)");
     launch_clip_act(d, n, act, sc.stream);
-    check_guard(sc, d, n, kOpGuard, "clip_act");
+    SD_HIP(hipStreamSynchronize(sc.stream));
     SD_HIP(hipMemcpy(x, d, n * sizeof(half_t), hipMemcpyDeviceToHost));
   });
 }
@@ -2132,13 +2083,13 @@ int sd_op_layout(int kind, const void* src, void* dst, int B, int C, int H, int 
     SD_REQUIRE(src && dst, kInvalidArgument, "NULL argument");
     SD_REQUIRE(kind >= 0 && kind <= 8, kInvalidArgument, "layout: kind %d", kind);
     SD_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && (kind != 6 || H == 1), kInvalidArgument, "layout: kind %d B=%d C=%d H=%d W=%d", kind, B, C, H, W);
-    Scratch sc;
+    Scratch sc("layout");
     const size_t n = (size_t)B * C * H * W;
     const bool src_f32 = kind == 1 || kind == 3 || kind == 5 || kind == 8;
     const bool dst_f32 = kind == 2 || kind == 3 || kind == 4 || kind == 5 || kind == 7;
     const void* ds = src_f32 ? (const void*)sc.dev<float>(n, reinterpret_cast<const float*>(src)) : (const void*)sc.dev<half_t>(n, f16(src));
-    float* df = dst_f32 ? guarded_buf<float>(sc, n, kOpGuard) : nullptr;
-    half_t* dh = dst_f32 ? nullptr : guarded_buf<half_t>(sc, n, kOpGuard);
+    float* df = dst_f32 ? sc.out<float>(n, "dst") : nullptr;
+    half_t* dh = dst_f32 ? nullptr : sc.out<half_t>(n, "dst");
     switch (kind) {
       case 0: case 1: launch_nchw_to_nhwc(ds, src_f32, dh, B, C, H, W, sc.stream); break;
       case 2: case 3: launch_nchw_to_nhwc_f32(ds, src_f32, df, B, C, H, W, sc.stream); break;
@@ -2148,13 +2099,11 @@ int sd_op_layout(int kind, const void* src, void* dst, int B, int C, int H, int 
       case 7: launch_half_to_float(f16(ds), df, n, sc.stream); break;
       default: launch_float_to_half(reinterpret_cast<const float*>(ds), dh, n, sc.stream); break;
     }
-    if (dst_f32) {
-      check_guard(sc, df, n, kOpGuard, "layout");
+    SD_HIP(hipStreamSynchronize(sc.stream));
+    if (dst_f32)
       SD_HIP(hipMemcpy(dst, df, n * sizeof(float), hipMemcpyDeviceToHost));
-    } else {
-      check_guard(sc, dh, n, kOpGuard, "layout");
+    else
       SD_HIP(hipMemcpy(dst, dh, n * sizeof(half_t), hipMemcpyDeviceToHost));
-    }
   });
 }
 
@@ -2166,15 +2115,15 @@ int sd_op_sum_half(const void* const* srcs, int nsrc, void* out, size_t n, int a
     SD_REQUIRE(n > 0 && n % 8 == 0 && nsrc >= 1 && nsrc <= 4 && (add == 0 || (add == 1 && nsrc == 2)), kInvalidArgument,
                "sum_half: n=%zu (a multiple of 8), %d sources (1-4; add_half: 2), add=%d", n, nsrc, add);
     for (int i = 0; i < nsrc; ++i) SD_REQUIRE(srcs[i], kInvalidArgument, "NULL argument");
-    Scratch sc;
+    Scratch sc("sum_half");
     const half_t* ds[4] = {nullptr, nullptr, nullptr, nullptr};
     for (int i = 0; i < nsrc; ++i) ds[i] = sc.dev<half_t>(n, f16(srcs[i]));
-    half_t* dout = guarded_buf<half_t>(sc, n, kOpGuard);
+    half_t* dout = sc.out<half_t>(n, "out");
     if (add)
       launch_add_half(ds[0], ds[1], dout, n, sc.stream);
     else
       launch_sum_half(ds, nsrc, dout, n, sc.stream);
-    check_guard(sc, dout, n, kOpGuard, "sum_half");
+    SD_HIP(hipStreamSynchronize(sc.stream));
     SD_HIP(hipMemcpy(out, dout, n * sizeof(half_t), hipMemcpyDeviceToHost));
   });
 }
@@ -2184,12 +2133,12 @@ int sd_op_vit_patch_rows(const void* img, void* rows, int B, int I, int p, int K
   return guarded([&] {
     SD_REQUIRE(img && rows, kInvalidArgument, "NULL argument");
     SD_REQUIRE(B > 0 && p >= 1 && I >= p && I % p == 0 && Kp >= 3 * p * p, kInvalidArgument, "vit_patch_rows: B=%d image %d patch %d row %d", B, I, p, Kp);
-    Scratch sc;
+    Scratch sc("vit_patch_rows");
     const size_t n = (size_t)B * (I / p) * (I / p) * Kp;
     half_t* di = sc.dev<half_t>((size_t)B * 3 * I * I, f16(img));
-    half_t* dout = guarded_buf<half_t>(sc, n, kOpGuard);
+    half_t* dout = sc.out<half_t>(n, "rows");
     launch_vit_patch_rows(di, dout, B, I, p, Kp, sc.stream);
-    check_guard(sc, dout, n, kOpGuard, "vit_patch_rows");
+    SD_HIP(hipStreamSynchronize(sc.stream));
     SD_HIP(hipMemcpy(rows, dout, n * sizeof(half_t), hipMemcpyDeviceToHost));
   });
 }
@@ -2200,15 +2149,41 @@ int sd_op_vit_tokens(const void* patch, const void* cls, const void* pos, void* 
     SD_REQUIRE(patch && cls && pos && out, kInvalidArgument, "NULL argument");
     SD_REQUIRE(B > 0 && S > 0 && D > 0, kInvalidArgument, "vit_tokens: B=%d S=%d D=%d", B, S, D);
     SD_REQUIRE(D % 8 == 0 && S >= 2, kUnsupported, "vit_tokens: hidden size %d, %d tokens", D, S);
-    Scratch sc;
+    Scratch sc("vit_tokens");
     const size_t n = (size_t)B * S * D;
     half_t* dp = sc.dev<half_t>((size_t)B * (S - 1) * D, f16(patch));
     half_t* dc = sc.dev<half_t>(D, f16(cls));
     half_t* de = sc.dev<half_t>((size_t)S * D, f16(pos));
-    half_t* dout = guarded_buf<half_t>(sc, n, kOpGuard);
+    half_t* dout = sc.out<half_t>(n, "out");
     launch_vit_tokens(dp, dc, de, dout, B, S, D, sc.stream);
-    check_guard(sc, dout, n, kOpGuard, "vit_tokens");
+    SD_HIP(hipStreamSynchronize(sc.stream));
     SD_HIP(hipMemcpy(out, dout, n * sizeof(half_t), hipMemcpyDeviceToHost));
+  });
+}
+
+// The proof that the scratch's guards and poison can fail: dst = (float)src over n f16 values (misc.hip half_to_float_kernel, one
+// element per thread), with one deliberate off-by-one made HERE, by the pointers and counts the launches get.  Every access stays
+// inside the two allocations of the scratch (data or guard), so no mode can fault.
+//   0 the clean launch                                         -> SD_OK
+//   1 + one element written behind dst                         -> SD_ERR_INTERNAL, "back guard"
+//   2 + one element written in front of dst                    -> SD_ERR_INTERNAL, "front guard"
+//   3 + one element written behind src (an input)              -> SD_ERR_INTERNAL, "back guard"
+//   4 the last element of dst skipped                          -> SD_OK, dst[n - 1] is NaN
+//   5 src read from its second element on, one behind its end  -> SD_OK, dst[n - 1] is NaN
+// dst is copied out in every mode, so a caller sees what a failed call left.
+int sd_op_harness_selftest(int mode, const void* src, float* dst, size_t n) {
+  return guarded([&] {
+    SD_REQUIRE(src && dst, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(mode >= 0 && mode <= 5 && n >= 2 && n <= ((size_t)1 << 24), kInvalidArgument, "harness_selftest: mode %d n %zu", mode, n);
+    Scratch sc("harness_selftest");
+    half_t* ds = sc.dev<half_t>(n, f16(src), "src");
+    float* dd = sc.out<float>(n, "dst");
+    launch_half_to_float(mode == 5 ? ds + 1 : ds, dd, mode == 4 ? n - 1 : n, sc.stream);
+    if (mode == 1) launch_half_to_float(ds, dd + n, 1, sc.stream);
+    if (mode == 2) launch_half_to_float(ds, dd - 1, 1, sc.stream);
+    if (mode == 3) launch_float_to_half(dd, ds + n, 1, sc.stream);
+    SD_HIP(hipStreamSynchronize(sc.stream));
+    SD_HIP(hipMemcpy(dst, dd, n * sizeof(float), hipMemcpyDeviceToHost));
   });
 }
 

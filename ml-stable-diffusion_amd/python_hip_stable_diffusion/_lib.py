@@ -213,6 +213,7 @@ SYMBOLS = [
     ("sd_op_sum_half", _I, [C.POINTER(_P), _I, _P, C.c_size_t, _I]),
     ("sd_op_vit_patch_rows", _I, [_P, _P, _I, _I, _I, _I]),
     ("sd_op_vit_tokens", _I, [_P, _P, _P, _P, _I, _I, _I]),
+    ("sd_op_harness_selftest", _I, [_I, _P, _FP, C.c_size_t]),
 ]
 
 
@@ -1435,6 +1436,15 @@ def sum_half(srcs, add=False):
     arr = (C.c_void_p * len(srcs))(*[a.ctypes.data for a in srcs])
     check(lib().sd_op_sum_half(arr, len(srcs), ptr(out), out.size, int(bool(add))))
     return out
+
+
+def harness_selftest(mode, src):
+    """Self-check of the operator harness (sd_mi355x.h sd_op_harness_selftest): float32(src) with the deliberate off-by-one of
+    ``mode`` (0 none).  Returns (status, error text, dst): nothing is raised, so that a test sees what a refused call left in dst."""
+    src = f16(src).ravel()
+    dst = np.zeros(src.size, np.float32)
+    status = lib().sd_op_harness_selftest(int(mode), ptr(src), fptr(dst), src.size)
+    return status, lib().sd_last_error().decode("utf-8", "replace"), dst
 
 
 def vit_patch_rows(img, patch, row):

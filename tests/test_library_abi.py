@@ -23,8 +23,20 @@ def test_library_exports_every_declared_symbol(sdlib):
     assert len(declared) >= 20
     bound = sorted(name for name, _, _ in _lib.SYMBOLS)
     assert declared == bound, set(declared) ^ set(bound)
+    assert "sd_op_harness_selftest" in declared
     for name in declared:
         assert hasattr(sdlib, name), name
+
+
+def test_harness_selftest_refuses_on_the_host(sdlib):
+    """mode and size are checked before any device work, and the strided q|k attention variant refuses unequal lengths there too."""
+    src = np.ones(16, np.float16)
+    for mode, n in ((-1, 16), (6, 16), (0, 1)):
+        status, text, _ = _lib.harness_selftest(mode, src[:n])
+        assert status == -1 and "harness_selftest" in text, (mode, n, status, text)
+    q, k = np.zeros((1, 64, 1, 64), np.float16), np.zeros((1, 64, 1, 77), np.float16)
+    with pytest.raises(ValueError, match="Sq == Sk"):
+        _lib.attention("ORIGINAL", q, k, k, 1, 64, variant=3)
 
 
 def test_version_and_error_string(sdlib):

@@ -129,6 +129,34 @@ def test_three_attention_schedules_agree_with_each_other():
         close(o, outs[0], "cross-schedule", min_psnr=55)
 
 
+QK_SHAPES = [  # (B, heads, d, S): attention8.hip, the general kernel at d = 64 with a ragged S, attention8 on two samples, head dims 40 / 16
+    (1, 1, 64, 64), (1, 3, 64, 127), (2, 2, 64, 448), (1, 2, 40, 256), (1, 2, 16, 64),
+]
+
+
+@pytest.mark.parametrize("impl", IMPLS)
+@pytest.mark.parametrize("shape", QK_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_self_attention_on_the_strided_qk_buffer(impl, shape):
+    """variant 3: q and k are rows of ONE [B][S][2C] device buffer (ldq = ldk = 2C), as every self-attention of a UNet handle reads
+    them from its fused q|k|v GEMM.  Same kernel, same arithmetic, other addresses: bit-equal to variant 0, and inside the gate."""
+    b, h, d, s = shape
+    rs = np.random.RandomState(1000 * d + s)
+    q, k, v = (h16(rs.randn(b, h * d, 1, s)) for _ in range(3))
+    ref = attention_ref.IMPLS[impl](q.astype(np.float32), k.astype(np.float32), v.astype(np.float32), h, d)
+    plain, _ = _lib.attention(impl, q, k, v, h, d, variant=0)
+    strided, _ = _lib.attention(impl, q, k, v, h, d, variant=3)
+    close(strided, ref, f"{impl} {shape} q|k interleaved")
+    assert np.array_equal(strided.view(np.uint16), plain.view(np.uint16)), \
+        f"{impl} {shape}: {(strided.view(np.uint16) != plain.view(np.uint16)).sum()} of {plain.size} values differ between ldq = C and ldq = 2C"
+
+
+def test_strided_qk_variant_needs_equal_lengths():
+    q = np.zeros((1, 64, 1, 64), np.float16)
+    k = np.zeros((1, 64, 1, 77), np.float16)
+    with pytest.raises(ValueError, match="Sq == Sk"):
+        _lib.attention("ORIGINAL", q, k, k, 1, 64, variant=3)
+
+
 # ------------------------------------------------------------------ norms
 def test_layernorm_reference_golden():
     g = load_golden("layernorm_golden.npz")
