@@ -84,6 +84,14 @@ int sd_weights_palettize(sd_weights* w, const char* name, int nbits, double* sq_
 int sd_weights_add_palettized(sd_weights* w, const char* name, const void* lut, int nbits, const uint8_t* indices, const int64_t* shape,
                               int ndim);
 int sd_weights_palette_bits(const sd_weights* w, const char* name);
+/* The palettized 3x3 halo convs, opt-in (host only; on = 0 / 1, any other value is SD_ERR_INVALID_ARGUMENT; off by default).  Handles
+ * created from the store while the switch is on run every palettized 3x3 / stride-1 conv whose fp16 plan is the K-split halo conv
+ * (plan tile 7, without GroupNorm in the loader) from its palette: conv3x3_halo_pal_kernel, plan tile 25, with that plan's ring code and
+ * split-K - resnet conv1 / conv2, the two-source convs of the up blocks and the upsamplers (which then take tile 25, not the
+ * sub-pixel tile 21, as a W8A8 one takes tile 18).  Such a conv holds the index stream (ceil(Cout / 64) * 64 * 9 * Ctot * nbits / 8
+ * bytes) and the LUT only - no fp16 copy, no sub-pixel fold - and computes bit for bit what it computed from fp16 lut[indices]; its
+ * profile label reads "conv3x3+pal<nbits> ...".  With the switch off a handle is, to the byte, what it was without it. */
+int sd_weights_palette_halo(sd_weights* w, int on);
 int sd_weights_read_palette(const sd_weights* w, const char* name, void* lut, uint8_t* indices, float* values);
 /* W8A8 post-training quantization: replaces activation_quantization.py:141-203 (quantize_cumulative_config + the calibration that
  * feeds it) with its scheme - symmetric int8, one scale per OUTPUT CHANNEL for a conv's weights, one scale per TENSOR for the
@@ -208,8 +216,10 @@ size_t sd_unet_arena_used_bytes(const sd_unet* u);
  * theirs on the device - the small-M weight-stream convs (plan tile 14) and the small-M 1x1 projections proj_in / attn1.to_out.0 /
  * attn2.to_out.0 whose plan is smgemm.hip (plan tile 15) and the GEGLU projections ff.net.0.proj whose plan is smgeglu.hip on
  * 128-row tiles (plan tile 16; beside stream and LUT they hold norm3.weight as fp32 where the LayerNorm is folded in), which hold only
- * the index bit stream and the LUT, no fp16 copy; *stream_bytes = the bytes of those streams and LUTs.  Every other palettized tensor
- * (q|k|v, attn2.to_q, the merged transformer tail, GEGLU projections on 256-row tiles) was uploaded as fp16 lut[indices]. */
+ * the index bit stream and the LUT, no fp16 copy - and, in a handle created while the store's sd_weights_palette_halo switch was on,
+ * the 3x3 halo convs (plan tile 25: resnet conv1 / conv2, the two-source convs of the up blocks, upsamplers);
+ * *stream_bytes = the bytes of those streams and LUTs.  Every other palettized tensor (q|k|v, attn2.to_q, the merged transformer
+ * tail, GEGLU projections on 256-row tiles, the halo convs with the switch off) was uploaded as fp16 lut[indices]. */
 int sd_unet_palette_info(const sd_unet* u, int* n_palettized, int* n_streamed, size_t* stream_bytes);
 /* W8A8 (activation_quantization.py:141-203; sd_weights_quantize_w8a8): *n_marked tensors of the handle's weight store arrived with a
  * mark; *n_applied convolutions run from int8 (plan tiles 17, 18, 19, 20 and 22) and hold the int8 weights in their kernel's layout and one fp32
@@ -470,6 +480,24 @@ int sd_op_conv2d_palettized(const void* x, const void* x1, const void* lut, int 
  * (j & 1) * 16 + (lane >> 5) * 8 + e, tap j >> 1) as little-endian nbits-wide fields, padded to whole 16-byte words, word q at
  * [strip][slice][q][lane][16 B]. */
 int sd_op_palette_pack(const uint8_t* indices, int Cout, int Ctot, int ksize, int nbits, uint8_t* stream, size_t* bytes);
+/* The 3x3 / stride-1 halo conv from PALETTIZED weights (plan tile 25, conv3x3_halo_pal.hip): w = lut[indices], lut
+ * 2^nbits f16 (nbits 1, 2, 4, 6, 8), indices (Cout, Cin + C1, 3, 3) uint8; x1 / C1, bias, temb, res, upsample, iters, ms as
+ * sd_op_conv2d_ex; staging = plan tile 7's ring code (0 / 2 / 3 / 4 / 5: 2 / 3 / 4 / 6 / 8 weight stages), splitk = split-K over
+ * 64-channel chunks (0 = the library's rule for tile 7).  plan_out = {25, ring code, resolved split-K, slab}.  The result is
+ * bit-identical to sd_op_conv2d_ex(tile = 7) on the fp16 weights lut[indices] at the same ring code and split-K.  Checked on the host in
+ * this order, before any device work, each SD_ERR_INVALID_ARGUMENT: NULL arguments; nbits not in {1, 2, 4, 6, 8}; an empty problem;
+ * upsample / staging / splitk off their ranges; a shape the halo conv does not take (channel counts multiples of 64 in and 4 out, an
+ * image of at least 8 x 8 outputs); an index >= 2^nbits (the message names it). */
+int sd_op_conv2d_palettized_halo(const void* x, const void* x1, const void* lut, int nbits, const uint8_t* indices, const float* bias,
+                                 const float* temb, const void* res, void* out, int B, int Cin, int C1, int H, int W, int Cout, int upsample,
+                                 int staging, int splitk, int* plan_out, int iters, float* ms);
+/* The index bit stream that entry and the UNet builder put on the device (host only): indices (Cout, Ctot, 3, 3) uint8, Ctot a multiple
+ * of 64 -> stream; *bytes = its size, ceil(Cout / 64) * 64 * 9 * Ctot * nbits / 8 (no padding bits; rows past Cout carry index 0);
+ * stream may be NULL to ask for the size alone.  Per (64-row n-tile, 64-channel chunk, tap), in that order, one block of nbits * 128
+ * dwords; dword j of stream (wk, lane) - K half wk = 0, 1, lane 0 .. 63 - at dword (j * 2 + wk) * 64 + lane of the block; a stream is
+ * 32 little-endian nbits-wide fields, field (2 s + j) * 8 + e = row 64 n_tile + 32 j + (lane & 31), channel 64 chunk +
+ * (2 (2 wk + s) + (lane >> 5)) * 8 + e (weight_prep.h halo_pal_pack). */
+int sd_op_palette_pack_halo(const uint8_t* indices, int Cout, int Ctot, int nbits, uint8_t* stream, size_t* bytes);
 /* The small-M weight-stream conv in W8A8 (plan tile 17; activation_quantization.py:141-203, semantics at sd_weights_quantize_w8a8):
  * wq (Cout, Cin + C1, k, k) int8, w_scale (Cout) f32, act_absmax the range of x (and x1); x1 / C1, bias, res, upsample, nw, plan_out,
  * iters, ms as sd_op_conv2d_palettized.  plan_out = {17, 4 for four waves else 0, slabs, 1}.  Checked on the host in this order,

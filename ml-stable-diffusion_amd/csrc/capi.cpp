@@ -139,6 +139,13 @@ int sd_weights_w8a8_info(const sd_weights* w, const char* name, float* act_scale
   if (m && act_scale) *act_scale = m->act_absmax / 127.0f;
   return m ? 1 : 0;
 }
+int sd_weights_palette_halo(sd_weights* w, int on) {
+  return guarded([&] {
+    SD_REQUIRE(w, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(on == 0 || on == 1, kInvalidArgument, "sd_weights_palette_halo: %d (0 off, 1 on)", on);
+    w->store.set_palette_halo(on != 0);
+  });
+}
 int sd_weights_observe_activations(sd_weights* w, int on) {
   return guarded([&] {
     SD_REQUIRE(w, kInvalidArgument, "NULL argument");

@@ -179,7 +179,7 @@ struct ConvOpExtra {
   void* out_twin = nullptr;
   int* plan_out = nullptr;       // {tile, staging, splitk, slab} of the plan that ran; -1: the direct kernels
   HostWeights cw;                // sd_op_conv2d_palettized / sd_op_conv2d_w8a8: the weights arrive compressed (w is NULL)
-  int nw = 0;                    // ... with this many waves per workgroup: 4, else 8 (sd_op_conv2d_w8a8_halo: tile 7's ring code)
+  int nw = 0;                    // ... with this many waves per workgroup: 4, else 8 (sd_op_conv2d_w8a8_halo / _palettized_halo: tile 7's ring code)
 };
 
 // The compressed weights of a descriptor as the UNet builder uploads them (Net::upload_compressed) - the packed stream of the kind
@@ -248,7 +248,7 @@ void conv2d_op(const void* x, const void* w, const float* bias, const void* res,
                ksize, Cin, e.C1, Cout, Ho, Wo);
   // (W8A8: shape and values were checked on the host by the entry point)
   if (e.cw.kind != WeightSource::Fp16)
-    upload_compressed(sc, d, e.cw.kind == WeightSource::PalWstream ? "palettized conv" : e.cw.kind == WeightSource::I8Halo ? "conv2d_w8a8_halo" : "conv2d_w8a8", e.cw, e.nw);
+    upload_compressed(sc, d, e.cw.kind == WeightSource::PalWstream ? "palettized conv" : e.cw.kind == WeightSource::PalHalo ? "conv2d_palettized_halo" : e.cw.kind == WeightSource::I8Halo ? "conv2d_w8a8_halo" : "conv2d_w8a8", e.cw, e.nw);
   half_t* dtwin = nullptr;
   if (e.twin_groups) {   // the GroupNorm as a twin of the conv's slab combine (sd_op_conv2d_groupnorm's producer_stats = 2)
     SD_REQUIRE(fast, kInvalidArgument, "conv2d: GroupNorm twins need the MFMA path");
@@ -534,6 +534,45 @@ int sd_op_conv2d_palettized(const void* x, const void* x1, const void* lut, int 
     e.cw.kind = WeightSource::PalWstream; e.cw.lut = lut; e.cw.indices = indices; e.cw.bits = nbits;
     e.nw = nw;
     conv2d_op(x, nullptr, bias, res, out, B, Cin, H, W, Cout, ksize, 1, upsample, 0, 0, 0, iters, ms, e);
+  });
+}
+
+// Every check runs on the host in front of the first device call (Scratch), in the order the header lists them.
+int sd_op_conv2d_palettized_halo(const void* x, const void* x1, const void* lut, int nbits, const uint8_t* indices, const float* bias, const float* temb,
+                                 const void* res, void* out, int B, int Cin, int C1, int H, int W, int Cout, int upsample, int staging, int splitk,
+                                 int* plan_out, int iters, float* ms) {
+  return guarded([&] {
+    SD_REQUIRE(x && lut && indices && out, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(palette_bits_ok(nbits), kInvalidArgument, "conv2d_palettized_halo: nbits = %d, not one of 1, 2, 4, 6, 8", nbits);
+    SD_REQUIRE(B > 0 && Cin > 0 && C1 >= 0 && Cout > 0 && H > 0 && W > 0 && (C1 == 0 || x1), kInvalidArgument, "conv2d_palettized_halo: empty problem");
+    SD_REQUIRE((upsample == 0 || upsample == 1) && staging >= 0 && staging <= 5 && staging != 1 && splitk >= 0, kInvalidArgument,
+               "conv2d_palettized_halo: upsample %d staging %d (plan tile 7's ring codes 0, 2-5) splitk %d", upsample, staging, splitk);
+    ConvDesc d;   // the shape alone: what the planner's predicates look at
+    d.C0 = Cin;
+    if (C1 > 0) d.x1 = f16(x1), d.C1 = C1;
+    d.B = B; d.Hi = H; d.Wi = W; d.Ho = H * (upsample ? 2 : 1); d.Wo = W * (upsample ? 2 : 1);
+    d.ksize = 3; d.up = upsample ? 2 : 1; d.N = Cout;
+    SD_REQUIRE(conv_fast_path_ok(d) && halo_pal_ok(d), kInvalidArgument,
+               "conv2d_palettized_halo: shape not eligible for plan tile 25 (conv3x3_halo_pal.hip: C0=%d C1=%d N=%d %dx%d)", Cin, C1, Cout, d.Ho, d.Wo);
+    palette_check_indices("conv2d_palettized_halo", indices, (size_t)Cout * (Cin + C1) * 9, nbits);
+    ConvOpExtra e;
+    e.entry = "conv2d_palettized_halo";
+    e.x1 = x1; e.C1 = C1;
+    e.temb = temb;
+    e.plan_out = plan_out;
+    e.cw.kind = WeightSource::PalHalo; e.cw.lut = lut; e.cw.indices = indices; e.cw.bits = nbits;
+    e.nw = staging;
+    conv2d_op(x, nullptr, bias, res, out, B, Cin, H, W, Cout, 3, 1, upsample, 0, splitk, 0, iters, ms, e);
+  });
+}
+
+// The index stream of plan tile 25 (weight_prep.h halo_pal_pack).  Host only.
+int sd_op_palette_pack_halo(const uint8_t* indices, int Cout, int Ctot, int nbits, uint8_t* stream, size_t* bytes) {
+  return guarded([&] {
+    SD_REQUIRE(indices && bytes, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(palette_bits_ok(nbits) && Cout > 0 && Ctot > 0 && Ctot % 64 == 0, kInvalidArgument, "palette_pack_halo: nbits %d Cout %d Ctot %d", nbits, Cout, Ctot);
+    *bytes = halo_pal_bytes(Cout, Ctot, nbits);
+    if (stream) halo_pal_pack(indices, Cout, Ctot, nbits, stream);
   });
 }
 
@@ -1640,6 +1679,13 @@ static ConvPlan query_conv_plan(int ksize, int stride, int up, int C0, int C1, i
     d.cw.kind = WeightSource::I8Halo;
     d.cw.stream = d.cw.scale = present;
     d.cw.inv_s = 1.f;
+  }
+  if (tile == 25) {   // ... and a palettized one of the halo conv its index stream and LUT
+    d.w = nullptr;
+    d.cw.kind = WeightSource::PalHalo;
+    d.cw.stream = present;
+    d.cw.lut = ph;
+    d.cw.bits = 8;
   }
   if (tile == 19) {   // ... and one of the int8 small-M GEMM
     d.w = nullptr;

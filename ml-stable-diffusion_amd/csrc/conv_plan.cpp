@@ -59,8 +59,10 @@ bool i8_stream(const ConvDesc& d) { return d.cw.kind == WeightSource::I8Wstream;
 // plan tile 18: the int8 halo conv - tile 7's shapes without the GroupNorm loader, inside the int32 bound
 bool i8_halo(const ConvDesc& d) { return d.cw.kind == WeightSource::I8Halo; }
 bool halo_i8_ok(const ConvDesc& d) {
-  return halo_ks_ok(d) && can_split(d) && !d.gnf_partial && !d.debug && d.C0 + (d.x1 ? d.C1 : 0) <= kHaloI8MaxCtot;
+  return halo_pal_ok(d) && d.C0 + (d.x1 ? d.C1 : 0) <= kHaloI8MaxCtot;   // (halo_pal_ok: the rule without the int32 bound)
 }
+// plan tile 25: the palettized halo conv - tile 7's shapes without the GroupNorm loader (halo_pal_ok below: no int32 bound)
+bool pal_halo(const ConvDesc& d) { return d.cw.kind == WeightSource::PalHalo; }
 // plan tile 15: the small-M 1x1 GEMM;  plan tile 16: the GEGLU projection
 bool pal_gemm(const ConvDesc& d) { return d.cw.kind == WeightSource::PalGemm; }
 bool pal_geglu(const ConvDesc& d) { return d.cw.kind == WeightSource::PalGeglu; }
@@ -187,9 +189,9 @@ Plan choose_plan(const ConvDesc& d, const Dims& a) {
     while (split_ok && s < 16 && ksteps(c) / (s * 2) >= per_min) s *= 2;
     return s;
   };
-  // the caller chose (operator-level A/B tests); an int8 halo conv is tile 7's plan whatever a table row or a tuner candidate says
-  const bool pinned = p.tile != 0 || p.splitk != 0 || p.staging != 0 || i8_halo(d);
-  if (i8_halo(d)) p.tile = 7;
+  // the caller chose (operator-level A/B tests); an int8 / palettized halo conv is tile 7's plan whatever a table row or a tuner candidate says
+  const bool pinned = p.tile != 0 || p.splitk != 0 || p.staging != 0 || i8_halo(d) || pal_halo(d);
+  if (i8_halo(d) || pal_halo(d)) p.tile = 7;
   if (!pinned && g_tune.tile != 0 && tile_ok(g_tune.tile)) {
     p.tile = g_tune.tile;
     p.staging = g_tune.staging;
@@ -262,6 +264,8 @@ bool halo_ks_ok(const ConvDesc& d) {
   return d.ksize == 3 && d.stride == 1 && (d.up == 1 || d.up == 2) && d.pad < 0 && d.out_mode == kOutHalf && d.Wo >= 8 && d.Ho >= 8 &&
          d.C0 % BK == 0 && c1 % BK == 0 && d.N % 4 == 0;
 }
+
+bool halo_pal_ok(const ConvDesc& d) { return halo_ks_ok(d) && can_split(d) && !d.gnf_partial && !d.debug; }
 
 const char* halo_sp_refusal(const ConvDesc& d) {
   if (d.x1) return "a second source";
@@ -374,6 +378,11 @@ ConvPlan plan_codes(const ConvDesc& d) {
     SD_REQUIRE(conv_fast_path_ok(d) && cw.stream && cw.scale && halo_i8_ok(d), kInvalidArgument,
                "plan tile 18 (conv3x3_halo_i8.hip, int8) needs the int8 weights, the scales and a 3x3 / stride-1 shape of the halo conv with "
                "at most %d input channels (k=%d stride=%d up=%d C0=%d C1=%d N=%d)", kHaloI8MaxCtot, d.ksize, d.stride, d.up, d.C0, d.x1 ? d.C1 : 0, d.N);
+  // (nor has a palettized halo descriptor: tile 25 takes it or nobody does)
+  if (pal_halo(d))
+    SD_REQUIRE(conv_fast_path_ok(d) && cw.stream && cw.lut && palette_bits_ok(cw.bits) && halo_pal_ok(d), kInvalidArgument,
+               "plan tile 25 (conv3x3_halo_pal.hip) needs the index stream, the LUT and a 3x3 / stride-1 shape of the halo conv without "
+               "GroupNorm in the loader (k=%d stride=%d up=%d C0=%d C1=%d N=%d %dx%d)", d.ksize, d.stride, d.up, d.C0, d.x1 ? d.C1 : 0, d.N, d.Ho, d.Wo);
   // (nor has an int8 GEMM descriptor: tile 19 takes it or nobody does)
   if (i8_gemm(d))
     SD_REQUIRE(conv_fast_path_ok(d) && cw.stream && cw.scale && d.staging >= 0 && d.staging <= 2 && smgemm_i8_shape_ok(d, d.staging), kInvalidArgument,
@@ -423,10 +432,11 @@ ConvPlan plan_codes(const ConvDesc& d) {
       r.workspace_bytes = slab_bytes(dims_of(d), r.splitk, true);
       return r;
     }
+    case WeightSource::PalHalo:
     case WeightSource::I8Halo: {   // tile 7's ring code, split-K rule and slab arithmetic (checked above)
       const Dims a = dims_of(d);
       const Plan p = choose_plan(d, a);
-      ConvPlan r{18, p.staging, 1, true, 0};
+      ConvPlan r{pal_halo(d) ? 25 : 18, p.staging, 1, true, 0};
       const int steps = a.Ctot / BK;
       r.splitk = cdiv(steps, cdiv(steps, p.splitk));
       r.slab = r.splitk > 1 || d.n_twins > 0;
@@ -507,6 +517,7 @@ ConvPlan plan_codes(const ConvDesc& d) {
 //              output (kOutHalfT) has register staging and rings of 2 / 3 stages only.
 //   tile 7:    0 / 2 / 3 / 4 / 5 = 2 / 3 / 4 / 6 / 8 weight stages; GroupNorm in the loader: 4 stages from code 3 where its table fits, else 3
 //   tile 18:   tile 7's codes; the int8 kernel has rings of 2 / 3 / 4 stages, a deeper code runs the 4-stage one
+//   tile 25:   tile 7's codes and depths as they are (no GroupNorm loader)
 //   tile 21:   tile 7's codes; the sub-pixel kernel has rings of 3 / 4 stages: 2 = 3 stages, anything else 4
 //   tiles 9 / 14 / 17: 4 = four waves per workgroup, anything else eight      tile 11: 1-6 = the variant, anything else the library's choice
 //   tiles 12 / 15 / 19 / 24 / 13 / 16 / 20 / 22: 1 / 2 = the lower / higher tile (32 / 64, 128 / 256 rows), 0 = by the shape
@@ -542,6 +553,12 @@ void decode_plan(const ConvDesc& d, ConvPlan& p) {
     tile_dims(7, p.bm, p.bn);
     p.kernel = ConvKernel::HaloI8;
     p.stages = code >= 3 ? 4 : code == 2 ? 3 : 2;
+    return;
+  }
+  if (p.tile == 25) {
+    tile_dims(7, p.bm, p.bn);
+    p.kernel = ConvKernel::HaloPal;
+    p.stages = code >= 5 ? 8 : code == 4 ? 6 : code == 3 ? 4 : code == 2 ? 3 : 2;
     return;
   }
   if (p.tile == 21) {
@@ -607,6 +624,7 @@ std::string conv_plan_kernel_name(const ConvPlan& p) {
     case ConvKernel::GemmPipe: return "gemm_pipe " + tile + ring;
     case ConvKernel::HaloKs: return "halo_ks" + ring;
     case ConvKernel::HaloI8: return "halo_i8" + ring;
+    case ConvKernel::HaloPal: return "halo_pal" + ring;
     case ConvKernel::HaloSubpix: return "conv3x3_halo_sp" + ring;
     case ConvKernel::Wstream: return "wstream waves" + std::to_string(p.waves);
     case ConvKernel::WstreamPal: return "wstream_pal waves" + std::to_string(p.waves);
@@ -678,6 +696,7 @@ WeightPin conv_plan_pin(WeightSource kind, int n) {
     case WeightSource::PalWstream: return {kind, 14, n == 4 ? 4 : 0};
     case WeightSource::I8Wstream: return {kind, 17, n == 4 ? 4 : 0};
     case WeightSource::I8Halo: return {kind, 18, n};   // n: tile 7's ring code as it is
+    case WeightSource::PalHalo: return {kind, 25, n};  // the same
     case WeightSource::PalGemm: return {kind, 15, n == 32 ? 1 : n == 64 ? 2 : 0};
     case WeightSource::I8Gemm: return {kind, 19, n == 32 ? 1 : n == 64 ? 2 : 0};
     case WeightSource::PalGeglu: return {kind, 16, n == 128 ? 1 : n == 256 ? 2 : 0};
@@ -690,7 +709,7 @@ WeightPin conv_plan_pin(WeightSource kind, int n) {
 
 // conv_plan itself answers each question (one predicate: an A/B switch, a tuner candidate, a forced plan, GroupNorm statistics asked
 // of the conv or a shape the twin's own rule refuses all give another kernel there).
-WeightPin conv_plan_weights(const ConvDesc& d, StoredWeights held, bool opt_in) {
+WeightPin conv_plan_weights(const ConvDesc& d, StoredWeights held, bool opt_in, bool pal_halo_on) {
   if (held == StoredWeights::Fp16 || !conv_fast_path_ok(d)) return {};
   const Switches& sw = switches();
   const bool palette = held == StoredWeights::Palette, one_by_one = opt_in && palette && d.ksize == 1 && !d.x1;
@@ -733,10 +752,11 @@ WeightPin conv_plan_weights(const ConvDesc& d, StoredWeights held, bool opt_in) 
     const ConvPlan p = fp16_plan(d, conv_plan_copies(d));
     if (p.kernel == ConvKernel::Smgemm && smgemm_i8_shape_ok(d, 0)) return conv_plan_pin(WeightSource::I8Gemm, p.bm);
   }
-  if (held == StoredWeights::W8A8 && halo_i8_ok(d)) {   // tile 7 without the GroupNorm loader: its ring code and resolved split-K
+  const bool i8h = held == StoredWeights::W8A8 && halo_i8_ok(d), palh = palette && pal_halo_on && halo_pal_ok(d);
+  if (i8h || palh) {   // tile 7 without the GroupNorm loader: its ring code and resolved split-K
     const ConvPlan p = fp16_plan(d, conv_plan_copies(d));
     if (p.kernel == ConvKernel::HaloKs) {
-      WeightPin pin = conv_plan_pin(WeightSource::I8Halo, p.staging);
+      WeightPin pin = conv_plan_pin(i8h ? WeightSource::I8Halo : WeightSource::PalHalo, p.staging);
       pin.splitk = p.splitk;
       return pin;
     }
@@ -794,6 +814,9 @@ void conv_plan_log(const ConvDesc& d, const ConvPlan& p, int n_fast) {
   else if (p.tile == 19 || p.tile == 20 || p.tile == 22 || p.tile == 24)
     fprintf(stderr, "[sd conv] k1 s1 up1 C0=%d C1=%d M=%d N=%d K=%d mode=%d tile=%d bm=%d n_fast=%d bits=8\n", d.C0, c1, a.M, a.N, a.K, d.out_mode, p.tile,
             p.bm, n_fast);
+  else if (p.tile == 25)
+    fprintf(stderr, "[sd conv] k%d s%d up%d C0=%d C1=%d M=%d N=%d K=%d mode=%d tile=%d splitk=%d bits=%d\n", d.ksize, d.stride, d.up, d.C0, c1, a.M, a.N,
+            a.K, d.out_mode, p.tile, p.splitk, d.cw.bits);
   else if (p.tile == 18)
     fprintf(stderr, "[sd conv] k%d s%d up%d C0=%d C1=%d M=%d N=%d K=%d mode=%d tile=%d splitk=%d bits=8\n", d.ksize, d.stride, d.up, d.C0, c1, a.M, a.N,
             a.K, d.out_mode, p.tile, p.splitk);

@@ -8,8 +8,8 @@
 
 namespace sd {
 
-// the kernel a plan launches (tile -1 / 1-4 / 7 / 18 / 21 / 9 / 14 / 17 / 10 / 11 / 12 / 15 / 19 / 13 / 16 / 20 / 22 / 24 of the wire format below)
-enum class ConvKernel { Generic, Igemm, GemmPipe, HaloKs, HaloI8, HaloSubpix, Wstream, WstreamPal, WstreamI8, Wsgemm, Bvgemm, Smgemm, SmgemmPal, SmgemmI8, Smgeglu, SmgegluPal, SmgegluI8, SmqkvI8, SmgemmQ8 };
+// the kernel a plan launches (tile -1 / 1-4 / 7 / 18 / 25 / 21 / 9 / 14 / 17 / 10 / 11 / 12 / 15 / 19 / 13 / 16 / 20 / 22 / 24 of the wire format below)
+enum class ConvKernel { Generic, Igemm, GemmPipe, HaloKs, HaloI8, HaloPal, HaloSubpix, Wstream, WstreamPal, WstreamI8, Wsgemm, Bvgemm, Smgemm, SmgemmPal, SmgemmI8, Smgeglu, SmgegluPal, SmgegluI8, SmqkvI8, SmgemmQ8 };
 
 struct ConvPlan {
   // The wire format: what ConvDesc::tile / staging pins, tuned_convs.inc rows, SD_PLAN_TABLE and sd_tune_set_candidate say and what
@@ -26,6 +26,8 @@ struct ConvPlan {
                    // of it (smqkv_i8.hip, BM x 160-column tiles at tile 20's two heights; never the library's own answer);
                    // 24: the small-M GEMM from int8 weights and int8 activations written by their producer (smgemm_q8.hip, tile 12 / 19's
                    // tiles; never the library's own answer; 23 is not in use);
+                   // 25: the halo conv from palettized weights (conv3x3_halo_pal.hip, tile 7's ring codes, split-K and
+                   // slabs; never the library's own answer);
                    // -1 = not on the MFMA path (launch_conv_generic)
   int staging;     // per-family code: decode_plan
   int splitk;      // resolved: what the launch runs, no empty splits (halo: over 64-channel chunks; tile 9: the slab count)
@@ -33,8 +35,8 @@ struct ConvPlan {
   size_t workspace_bytes;   // exactly what this launch needs of ConvWorkspace::partial
   // What the codes mean for this descriptor, resolved once by conv_plan(): all a launcher reads.
   ConvKernel kernel = ConvKernel::Generic;
-  int bm = 0, bn = 0;        // Igemm / GemmPipe / HaloKs / HaloI8 (128 x 64, as its tile counts): tile rows x columns; Smgemm* / Smgeglu* / SmqkvI8: bm, tile rows
-  int stages = 0;            // Igemm / GemmPipe / HaloKs / HaloI8 / HaloSubpix: the ring depth that runs, after the fall-back to one that fits the LDS
+  int bm = 0, bn = 0;        // Igemm / GemmPipe / HaloKs / HaloI8 / HaloPal (128 x 64, as its tile counts): tile rows x columns; Smgemm* / Smgeglu* / SmqkvI8: bm, tile rows
+  int stages = 0;            // Igemm / GemmPipe / HaloKs / HaloI8 / HaloPal / HaloSubpix: the ring depth that runs, after the fall-back to one that fits the LDS
   int kgroups = 1;           // Igemm: 2 = in-workgroup split-K, two K groups of four waves with a ring each
   bool reg_staged = false;   // Igemm: A / B travel HBM -> VGPR -> LDS (the A/B reference form), two stages
   int waves = 0;             // Wstream*: waves (K slices) per workgroup, 4 or 8
@@ -57,7 +59,9 @@ ConvWeightCopies conv_plan_copies(const ConvDesc& d);
 // staging), or Fp16: upload the de-compressed tensor and run as ever.  A kind is taken exactly where the plan of the fp16 conv, with
 // the copies a handle would hold, is the kind's fp16 twin by the library's own rule, with the twin's wave count / tile height:
 //   Palette: opted-in GEGLU (tile 16 for tile 13 on the 128-row tiles the palettized kernel has), then the weight stream (tile 14 for
-//            tile 9), then the opted-in single-source small-M GEMM (tile 15 for tile 12)
+//            tile 9), then the opted-in single-source small-M GEMM (tile 15 for tile 12), then - only where the store's halo switch
+//            is on (`pal_halo`, sd_weights_palette_halo) - the halo conv (tile 25 for tile 7 without the GroupNorm loader, with that
+//            plan's ring code and split-K: halo_pal_ok)
 //   W8A8:    the weight stream (tile 17) by tile 14's predicate, then the halo conv (tile 18 for tile 7 without the GroupNorm loader,
 //            with that plan's ring code and split-K; Ctot <= kHaloI8MaxCtot), then the opted-in single-source small-M GEMM (tile 19 for
 //            tile 12: tile 15's predicate; K <= kSmI8MaxK holds wherever tile 12 is the library's rule); an observing store asks this
@@ -74,9 +78,9 @@ enum class StoredWeights { Fp16, Palette, W8A8 };
 struct WeightPin {
   WeightSource kind = WeightSource::Fp16;
   int tile = 0, staging = 0;
-  int splitk = 0;   // I8Halo: the fp16 plan's resolved split-K (ConvDesc::splitk); 0 for the other kinds
+  int splitk = 0;   // I8Halo / PalHalo: the fp16 plan's resolved split-K (ConvDesc::splitk); 0 for the other kinds
 };
-WeightPin conv_plan_weights(const ConvDesc& d, StoredWeights held, bool opt_in);
+WeightPin conv_plan_weights(const ConvDesc& d, StoredWeights held, bool opt_in, bool pal_halo = false);
 // The pin of a kind by the caller's own choice (the operator entry points): n = waves per workgroup (4, anything else eight) of the
 // weight-stream kinds, the tile height of the others (32 / 64, 128 / 256; 0 = by the shape)
 WeightPin conv_plan_pin(WeightSource kind, int n);
@@ -86,7 +90,7 @@ void conv_plan_log(const ConvDesc& d, const ConvPlan& p, int n_fast = 0);
 
 // What launches, as one line (sd_op_conv_plan_kernel): the kernel's name, then only the fields that kernel has -
 //   "igemm <bm>x<bn> ring<stages>[ kg2][ regs]"    "gemm_pipe <bm>x<bn> ring<stages>"    "halo_ks ring<stages>"    "halo_i8 ring<stages>"
-//   "conv3x3_halo_sp ring<stages>"
+//   "conv3x3_halo_sp ring<stages>"                 "halo_pal ring<stages>"
 //   "wstream waves<n>"   "wstream_pal waves<n>"    "wstream_i8 waves<n>"                 "wsgemm"    "bvgemm v<variant>"
 //   "smgemm bm<bm>"      "smgemm_pal bm<bm>"       "smgemm_i8 bm<bm>"                    "smgeglu bm<bm>"    "smgeglu_pal bm<bm>"
 //   "smgeglu_i8 bm<bm>"  "smqkv_i8 bm<bm>"        "smgemm_q8 bm<bm>"                    "generic"
@@ -105,6 +109,9 @@ bool conv_reduce_stats_on();   // SD_REDUCE_STATS: the slab combine also leaves 
 // shape rules and tile geometry shared by the planner and the launchers
 constexpr int kConvBK = 64;   // K step (halves) of the MFMA kernels
 bool halo_ks_ok(const ConvDesc& d);
+// Plan tile 25, the one predicate: tile 7's shapes with the plain split-able epilogue, no GroupNorm in the loader, no ablation build
+// (tile 18's rule without its int32 bound - nothing here sums in int32)
+bool halo_pal_ok(const ConvDesc& d);
 // Plan tile 21 (ConvDesc::subpix): the general admissibility - halo_ks_ok's conditions on the LOW-RES image (3x3, stride 1, up 2,
 // kOutHalf, C0 % 64 == 0, N % 4 == 0, Hi >= 8, Wi >= 8), one source, fp16 weights, no GroupNorm loader, no twins, no LayerNorm fold /
 // q|k|v, 32-bit buffer offsets.  halo_sp_refusal names the first condition a descriptor misses, nullptr when it misses none.
@@ -138,6 +145,12 @@ constexpr int kHaloI8Pitch = 20, kHaloI8Rows = 204;
 constexpr size_t halo_i8_lds_bytes(int d) {
   return (size_t)kHaloLdsRows * kConvBK * sizeof(half_t) + (size_t)2 * kHaloI8Rows * kConvBK + (size_t)d * 64 * kConvBK + 2 * 64 * sizeof(float);
 }
+// conv3x3_halo_pal_kernel (plan tile 25): tile 7's two halo buffers, d stages of kHaloPalStageBytes (one block of the index stream,
+// 512 * nbits <= 4096 bytes, at a fixed pitch), then 1 KB: the 512-B LUT, [64] floats of epilogue constants, and the 256 B the LUT's
+// one DMA piece (64 lanes x 16 B) carries past them.  80 896 B at d = 8: two workgroups per CU at every depth.
+constexpr int kHaloPalStageBytes = 4096;
+constexpr size_t halo_pal_lds_bytes(int d) { return (size_t)2 * kHaloLdsRows * kConvBK * sizeof(half_t) + (size_t)d * kHaloPalStageBytes + 1024; }
+static_assert(2 * halo_pal_lds_bytes(8) <= kLdsBudget, "plan tile 25: two workgroups per CU with the deepest ring");
 // exact int32 sums: 127 * 127 * 9 * Ctot < 2^31
 constexpr int kHaloI8MaxCtot = 14784;
 static_assert(127LL * 127 * 9 * kHaloI8MaxCtot < (1LL << 31) && 127LL * 127 * 9 * (kHaloI8MaxCtot + 64) >= (1LL << 31), "int32 bound of plan tile 18");

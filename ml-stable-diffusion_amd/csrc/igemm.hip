@@ -1166,7 +1166,8 @@ int launch_conv(const ConvDesc& d, const ConvWorkspace& ws, hipStream_t s) {
       launch_wstream_i8(d, ws.partial, p.waves, s);
       break;
     case ConvKernel::HaloKs: gn_entries = launch_halo_ks(d, p, ws.partial, s); break;
-    case ConvKernel::HaloI8: gn_entries = launch_halo_i8(d, p, ws.partial, s); break;   // the same tiles from int8 weights and activations
+    case ConvKernel::HaloI8: gn_entries = launch_halo_i8(d, p, ws.partial, s); break;
+    case ConvKernel::HaloPal: gn_entries = launch_halo_pal(d, p, ws.partial, s); break;   // the same body from palettized weights   // the same tiles from int8 weights and activations
     case ConvKernel::HaloSubpix: gn_entries = launch_halo_sp(d, p, ws.partial, s); break;   // the upsampler as four 2x2 phase convs on the low-res halo
     case ConvKernel::Igemm:
     case ConvKernel::GemmPipe: {

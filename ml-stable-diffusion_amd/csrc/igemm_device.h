@@ -20,6 +20,8 @@ const half_t* zero_chunk();
 int launch_halo_ks(const ConvDesc& d, const ConvPlan& p, float* partial, hipStream_t s);
 // conv3x3_halo_i8.hip: the launch of plan tile 18 (d.cw of kind I8Halo), same return
 int launch_halo_i8(const ConvDesc& d, const ConvPlan& p, float* partial, hipStream_t s);
+// conv3x3_halo_pal.hip: the launch of plan tile 25 (d.cw of kind PalHalo), same return
+int launch_halo_pal(const ConvDesc& d, const ConvPlan& p, float* partial, hipStream_t s);
 // conv3x3_halo_sp.hip: the launch of plan tile 21 (d.subpix, d.w the folded matrix); writes no GroupNorm statistics (returns 0)
 int launch_halo_sp(const ConvDesc& d, const ConvPlan& p, float* partial, hipStream_t s);
 
@@ -471,7 +473,7 @@ IgemmArgs planned_args(const ConvDesc& d, const ConvPlan& p, float* partial) {
   a.partial = p.slab ? partial : nullptr;
   // (the weight stream has its own arguments: these then only feed the slab combine; the halo kernel splits whole 64-channel chunks)
   if (p.kernel != ConvKernel::Wstream && p.kernel != ConvKernel::WstreamPal && p.kernel != ConvKernel::WstreamI8)
-    a.nk_per_split = cdiv(p.kernel == ConvKernel::HaloKs || p.kernel == ConvKernel::HaloI8 ? a.Ctot / BK : a.nk_total, p.splitk);
+    a.nk_per_split = cdiv(p.kernel == ConvKernel::HaloKs || p.kernel == ConvKernel::HaloI8 || p.kernel == ConvKernel::HaloPal ? a.Ctot / BK : a.nk_total, p.splitk);
   return a;
 }
 

@@ -35,6 +35,7 @@ struct GnTwin {
 //   PalWstream  tile 14, wstream.hip  wstream_kernel NBITS > 0   stream of wstream_pal_pack   staging: tile 9's code
 //   PalGemm     tile 15, smgemm.hip   smgemm_pal_kernel          stream of smgemm_pal_pack    staging: tile 12's code (0 = by M)
 //   PalGeglu    tile 16, smgeglu.hip  smgeglu_pal_kernel         stream of smgeglu_pal_pack   staging: tile 13's code
+//   PalHalo     tile 25, conv3x3_halo_pal.hip  conv3x3_halo_pal_kernel  stream of halo_pal_pack      staging: tile 7's code
 //   I8Wstream   tile 17, wstream.hip  wstream_kernel NBITS = kWsI8 (W8A8)   stream of wstream_i8_pack   staging: tile 9's code
 //   I8Halo      tile 18, conv3x3_halo_i8.hip  conv3x3_halo_i8_kernel (W8A8)   stream of halo_i8_pack      staging: tile 7's code
 //   I8Gemm      tile 19, smgemm_i8.hip        smgemm_i8_kernel (W8A8)         stream of smgemm_i8_pack    staging: tile 12's code (0 = by M)
@@ -47,7 +48,7 @@ struct GnTwin {
 //               plain-form launch_layernorm_q8)
 //   (tiles 19, 20, 22, 24: LDS image, ladder, epilogue arithmetic and launch, and the ring geometry, issue and wait of tiles 20 and 22,
 //   are sm_i8_ring.h's)
-enum class WeightSource { Fp16, PalWstream, PalGemm, PalGeglu, I8Wstream, I8Halo, I8Gemm, I8Geglu, I8Qkv, I8GemmQ };
+enum class WeightSource { Fp16, PalWstream, PalGemm, PalGeglu, PalHalo, I8Wstream, I8Halo, I8Gemm, I8Geglu, I8Qkv, I8GemmQ };
 struct CompressedWeights {
   WeightSource kind = WeightSource::Fp16;
   const void* stream = nullptr;
@@ -62,7 +63,7 @@ struct CompressedWeights {
   // the producer in front of it - quantizes its activations by
   const float* scale = nullptr;
   float inv_s = 0.f;
-  bool palettized() const { return kind == WeightSource::PalWstream || kind == WeightSource::PalGemm || kind == WeightSource::PalGeglu; }
+  bool palettized() const { return kind == WeightSource::PalWstream || kind == WeightSource::PalGemm || kind == WeightSource::PalGeglu || kind == WeightSource::PalHalo; }
   const uint8_t* pal() const { return palettized() ? static_cast<const uint8_t*>(stream) : nullptr; }
   bool int8() const { return kind == WeightSource::I8Wstream || kind == WeightSource::I8Halo || kind == WeightSource::I8Gemm || kind == WeightSource::I8Geglu || kind == WeightSource::I8Qkv || kind == WeightSource::I8GemmQ; }
   const int8_t* i8() const { return int8() ? static_cast<const int8_t*>(stream) : nullptr; }

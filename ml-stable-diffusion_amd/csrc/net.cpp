@@ -157,7 +157,9 @@ ConvGeom conv_geom(const std::string& name, const Tensor& x, const ConvArgs& a) 
 }  // namespace
 
 // A tensor the store holds compressed stays compressed on the device where a kernel reads that form (conv_plan_weights): the handle
-// uploads the packed stream with its LUT / scales and no fp16 copy.  Everywhere else a palettized tensor goes up as lut[indices] and
+// uploads the packed stream with its LUT / scales and no fp16 copy (a palettized 3x3 halo conv - resnet conv1 / conv2, the two-source
+// convs of the up blocks, upsamplers, which then take plan tile 25 and not the sub-pixel tile 21 - only while the store's switch
+// sd_weights_palette_halo is on).  Everywhere else a palettized tensor goes up as lut[indices] and
 // a W8A8-marked one as fp16 (the reference's "skipped layer").
 Tensor Net::conv(std::vector<Op>& ops, const std::string& name, const Tensor& x, const ConvArgs& a) {
   if (f32_) return conv_f32(ops, name, x, a);
@@ -196,7 +198,7 @@ WeightPin Net::weight_plan(const std::string& name, const Tensor& x, const ConvA
   ConvDesc d = conv_shape(name, x, a);
   static const float present = 0.f;   // the planner only tests the pointers
   if (ln) d.ln_colsum = d.bias = &present;
-  return conv_plan_weights(d, held, a.keep_compressed);
+  return conv_plan_weights(d, held, a.keep_compressed, ws_->palette_halo());
 }
 
 bool Net::observes_geglu(const std::string& name, const Tensor& x, const ConvArgs& a, bool ln) const {
@@ -478,7 +480,7 @@ Tensor Net::conv_w(std::vector<Op>& ops, const std::string& name, const ConvWeig
   char buf[320];
   // trailing "#kind,ksize,stride,up,Ctot,N,M" is the plan-table key of this op (tools/tune_plans.py)
   const int kind = d.out_t ? 3 : (geglu ? 2 : (ln ? 1 : 0));
-  // the weight source in the label: "[+ln]+pal<bits>" from a palette (plan tile 14 or 15), "geglu+pal<bits>[+ln]" for plan tile 16,
+  // the weight source in the label: "[+ln]+pal<bits>" from a palette (plan tile 14, 15 or 25), "geglu+pal<bits>[+ln]" for plan tile 16,
   // "+w8a8" from int8 weights and quantized activations (plan tiles 17 / 18 / 19 / 20 / 22 / 24), "+q8out+w8a8" where plan tile 20 writes
   // its product as int8
   const WeightSource src = d.cw.kind;

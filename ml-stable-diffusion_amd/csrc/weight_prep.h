@@ -286,8 +286,47 @@ inline void smgeglu_pal_pack(const uint8_t* indices, int N2, int K, int nbits, u
   smgemm_pal_pack(rows.data(), N2, K, nbits, dst);
 }
 
+// The palettized index stream of the 3x3 halo conv (conv3x3_halo_pal.hip, plan tile 25), indices [N][Ctot][3][3] (the
+// checkpoint's order), Ctot % 64 == 0.  A compact bit stream without padding bits; the only padding is rows up to a multiple of 64,
+// which carry index 0 (their outputs are never stored).  Bytes: ceil(N / 64) * 64 * 9 * Ctot * nbits / 8.
+//   * per (64-row n-tile, 64-channel chunk, tap) one BLOCK of nbits * 128 dwords = 512 * nbits bytes; blocks in the order n-tile, chunk,
+//     tap - the order a workgroup walks them, so its DMA offset advances by the constant 512 * nbits bytes per tap step;
+//   * inside a block, dword j of stream (wk, lane), wk = 0, 1 the K half, lane = 0 .. 63, at dword index (j * 2 + wk) * 64 + lane;
+//   * a stream is the lane's 32 indices of that step as little-endian nbits-wide fields (field f at bits [f * nbits, (f + 1) * nbits)
+//     of its nbits dwords), in the order the fp16 kernel's read_step reads its fragments: field (2 s + j) * 8 + e, s, j = 0, 1,
+//     e = 0 .. 7, is row 64 n_tile + 32 j + (lane & 31), channel 64 chunk + (2 (2 wk + s) + (lane >> 5)) * 8 + e.  The two
+//     pixel-half waves of a K half read the same stream.
+inline size_t halo_pal_bytes(int N, int Ctot, int nbits) { return (size_t)((N + 63) / 64) * 64 * 9 * Ctot * nbits / 8; }
+// dst holds halo_pal_bytes(...) bytes
+inline void halo_pal_pack(const uint8_t* indices, int N, int Ctot, int nbits, uint8_t* dst) {
+  const int n_tiles = (N + 63) / 64, nch = Ctot / 64;
+  const size_t block = (size_t)512 * nbits;
+  for (int nt = 0; nt < n_tiles; ++nt)
+    for (int ch = 0; ch < nch; ++ch)
+      for (int tap = 0; tap < 9; ++tap) {
+        uint8_t* blk = dst + (((size_t)nt * nch + ch) * 9 + tap) * block;
+        for (int wk = 0; wk < 2; ++wk)
+          for (int lane = 0; lane < 64; ++lane) {
+            uint32_t words[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // nbits dwords (+ one for the last field's shift)
+            for (int f = 0; f < 32; ++f) {
+              const int s = f >> 4, j = (f >> 3) & 1, e = f & 7;
+              const int n = nt * 64 + j * 32 + (lane & 31), c = ch * 64 + (2 * (2 * wk + s) + (lane >> 5)) * 8 + e;
+              const uint64_t idx = n < N ? indices[((size_t)n * Ctot + c) * 9 + tap] : 0;
+              const int bit = f * nbits, dw = bit >> 5, sh = bit & 31;
+              const uint64_t v = idx << sh;
+              words[dw] |= (uint32_t)v;
+              words[dw + 1] |= (uint32_t)(v >> 32);
+            }
+            for (int j = 0; j < nbits; ++j) {
+              uint8_t* o = blk + ((size_t)(j * 2 + wk) * 64 + lane) * 4;
+              for (int b = 0; b < 4; ++b) o[b] = (uint8_t)(words[j] >> (8 * b));   // little-endian dwords
+            }
+          }
+      }
+}
+
 // What every upload of a palettized tensor starts from (the operator entry points of capi_ops.cpp, Net::conv): indices inside the
-// palette, the packed stream of the layout - wstream.hip's, smgemm.hip's or smgeglu.hip's (the latter two: indices [N][Ctot], ksize 1)
+// palette, the packed stream of the layout - wstream.hip's, smgemm.hip's, smgeglu.hip's (the latter two: indices [N][Ctot], ksize 1) or the halo conv's (ksize 3)
 // - and the LUT zero-padded to the kPalLutHalves entries the kernels copy.  The caller has checked the shape against the layout and owns the device memory.
 inline void palette_check_indices(const char* what, const uint8_t* indices, size_t n, int nbits) {
   for (size_t i = 0; i < n; ++i)
@@ -299,11 +338,14 @@ struct PaletteHostCopy {
   std::vector<half_t> lut;
 };
 inline PaletteHostCopy palette_host_copy(const char* what, const half_t* lut, int nbits, const uint8_t* indices, int N, int Ctot, int ksize,
-                                         WeightSource kind) {   // one of the three palettized kinds
+                                         WeightSource kind) {   // one of the four palettized kinds
   palette_check_indices(what, indices, (size_t)N * Ctot * ksize * ksize, nbits);
   PaletteHostCopy h;
-  h.stream.resize(kind == WeightSource::PalWstream ? wstream_pal_bytes(N, Ctot, ksize, nbits) : smgemm_pal_bytes(N, Ctot, nbits));
-  if (kind == WeightSource::PalGemm) smgemm_pal_pack(indices, N, Ctot, nbits, h.stream.data());
+  h.stream.resize(kind == WeightSource::PalWstream ? wstream_pal_bytes(N, Ctot, ksize, nbits)
+                  : kind == WeightSource::PalHalo  ? halo_pal_bytes(N, Ctot, nbits)
+                                                   : smgemm_pal_bytes(N, Ctot, nbits));
+  if (kind == WeightSource::PalHalo) halo_pal_pack(indices, N, Ctot, nbits, h.stream.data());
+  else if (kind == WeightSource::PalGemm) smgemm_pal_pack(indices, N, Ctot, nbits, h.stream.data());
   else if (kind == WeightSource::PalGeglu) smgeglu_pal_pack(indices, N, Ctot, nbits, h.stream.data());
   else wstream_pal_pack(indices, N, Ctot, ksize, nbits, h.stream.data());
   h.lut.assign(kPalLutHalves, (half_t)0);

@@ -72,6 +72,10 @@ class WeightStore {
   double palettize(const std::string& name, int nbits);
   void add_palettized(const std::string& name, const void* lut_f16, int nbits, const uint8_t* indices, const int64_t* shape, int ndim);
   const Palette* palette(const std::string& name) const;   // nullptr: the tensor has none
+  // handles built from this store while the switch is on also run the palettized 3x3 halo convs from their palette (plan tile 25); off
+  // by default, and with it off a handle is what it was before the switch existed
+  void set_palette_halo(bool on) { palette_halo_ = on; }
+  bool palette_halo() const { return palette_halo_; }
   size_t palettes() const { return pal_.size(); }
   const std::map<std::string, HostTensor>& tensors() const { return map_; }   // name order
 
@@ -84,6 +88,7 @@ class WeightStore {
   bool observe_geglus_ = false;
   bool observe_qkv_ = false;
   bool observe_tails_ = false;
+  bool palette_halo_ = false;
 };
 
 }  // namespace sd

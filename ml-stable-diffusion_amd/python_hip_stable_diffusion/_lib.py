@@ -100,6 +100,7 @@ SYMBOLS = [
     ("sd_weights_read_palette", _I, [_P, C.c_char_p, _P, _P, _FP]),
     ("sd_weights_quantize_w8a8", _I, [_P, C.c_char_p, _F, C.POINTER(C.c_double)]),
     ("sd_weights_w8a8_info", _I, [_P, C.c_char_p, _FP]),
+    ("sd_weights_palette_halo", _I, [_P, _I]),
     ("sd_weights_observe_activations", _I, [_P, _I]),
     ("sd_weights_observe_gemms", _I, [_P, _I]),
     ("sd_weights_observe_geglus", _I, [_P, _I]),
@@ -163,6 +164,8 @@ SYMBOLS = [
                              C.POINTER(_I), _I, _FP]),
     ("sd_op_conv2d_palettized", _I, [_P, _P, _P, _I, _P, _FP, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_I), _I, _FP]),
     ("sd_op_palette_pack", _I, [_P, _I, _I, _I, _I, _P, C.POINTER(C.c_size_t)]),
+    ("sd_op_conv2d_palettized_halo", _I, [_P, _P, _P, _I, _P, _FP, _FP, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_I), _I, _FP]),
+    ("sd_op_palette_pack_halo", _I, [_P, _I, _I, _I, _P, C.POINTER(C.c_size_t)]),
     ("sd_op_gemm_palettized", _I, [_P, _P, _I, _P, _FP, _P, _P, _I, _I, _I, _I, _I, _I, C.POINTER(_I), _I, _FP]),
     ("sd_op_palette_pack_gemm", _I, [_P, _I, _I, _I, _P, C.POINTER(C.c_size_t)]),
     ("sd_op_geglu_palettized", _I, [_P, _FP, _FP, _P, _I, _P, _FP, _P, _I, _I, _I, C.c_float, _I, C.POINTER(_I), _I, _FP]),
@@ -582,6 +585,57 @@ def conv2d_palettized(x, lut, indices, nbits, bias=None, res=None, x1=None, upsa
     check(lib().sd_op_conv2d_palettized(ptr(x), ptr(x1), ptr(lut), nbits, ptr(indices), fptr(bias), ptr(res), ptr(out), B, Cin, C1, H, W,
                                         Cout, k, int(upsample), nw, plan, iters, C.byref(ms)))
     return out.reshape(-1)[:n].reshape(B, Cout, Ho, Wo), list(plan), ms.value
+
+
+def conv2d_palettized_halo(x, lut, indices, nbits, bias=None, temb=None, res=None, x1=None, upsample=False, staging=3, splitk=0, out=None,
+                           iters=1):
+    """The 3x3 / stride-1 halo conv from palettized weights (sd_op_conv2d_palettized_halo, plan tile 25): w = lut[indices], lut
+    (2^nbits,) f16, indices (Cout, Cin + C1, 3, 3) uint8; temb (B, Cout) f32; staging = plan tile 7's ring code (0 / 2 / 3 / 4 / 5 =
+    2 / 3 / 4 / 6 / 8 stages), splitk 0 = the library's rule.  Bit-identical to conv2d_ex(tile=7) on lut[indices] at the same staging
+    and splitk.  What the library checks - nbits, the ranges, the shape, an index outside the palette - it refuses itself (ValueError, no
+    GPU needed).  Returns (out (B, Cout, Ho, Wo), plan, ms)."""
+    x, lut = f16(x), f16(lut)
+    indices = np.ascontiguousarray(indices, dtype=np.uint8)
+    x1 = None if x1 is None else f16(x1)
+    B, Cin, H, W = x.shape
+    C1 = 0 if x1 is None else x1.shape[1]
+    if indices.ndim != 4 or indices.shape[2:] != (3, 3):
+        raise ValueError("conv2d_palettized_halo: indices must be (Cout, Cin + C1, 3, 3)")
+    Cout, Ctot = indices.shape[:2]
+    if Ctot != Cin + C1 or (x1 is not None and x1.shape != (B, C1, H, W)):
+        raise ValueError("conv2d_palettized_halo: indices / second source shape does not match input")
+    if nbits in (1, 2, 4, 6, 8) and lut.shape != (1 << nbits,):
+        raise ValueError("conv2d_palettized_halo: lut must hold 2 ** nbits entries")
+    up = 2 if upsample else 1
+    Ho, Wo = H * up, W * up
+    bias = None if bias is None else f32(bias)
+    temb = None if temb is None else f32(temb)
+    res = None if res is None else f16(res)
+    if res is not None and res.shape != (B, Cout, Ho, Wo):
+        raise ValueError("conv2d_palettized_halo: res must be (B, Cout, Ho, Wo)")
+    if temb is not None and temb.shape != (B, Cout):
+        raise ValueError("conv2d_palettized_halo: temb must be (B, Cout)")
+    n = B * Cout * Ho * Wo
+    if out is None:
+        out = np.empty(n, np.float16)
+    if out.dtype != np.float16 or not out.flags.c_contiguous or out.size < n:
+        raise ValueError("conv2d_palettized_halo: out must be a C-contiguous float16 buffer of at least B * Cout * Ho * Wo elements")
+    plan = (C.c_int * 4)()
+    ms = C.c_float(0)
+    check(lib().sd_op_conv2d_palettized_halo(ptr(x), ptr(x1), ptr(lut), int(nbits), ptr(indices), fptr(bias), fptr(temb), ptr(res), ptr(out),
+                                             B, Cin, C1, H, W, Cout, int(upsample), staging, splitk, plan, iters, C.byref(ms)))
+    return out.reshape(-1)[:n].reshape(B, Cout, Ho, Wo), list(plan), ms.value
+
+
+def palette_pack_halo(indices, nbits):
+    """The index bit stream of the palettized halo conv (sd_op_palette_pack_halo; host only): indices (Cout, Ctot, 3, 3) uint8 -> uint8
+    array (n_tiles, chunks, 9, nbits, 2, 64, 4): per (64-row n-tile, 64-channel chunk, tap) dword j of stream (wk, lane) as four
+    little-endian bytes."""
+    indices = np.ascontiguousarray(indices, dtype=np.uint8)
+    if indices.ndim != 4 or indices.shape[2:] != (3, 3):
+        raise ValueError("palette_pack_halo: indices must be (Cout, Ctot, 3, 3)")
+    Cout, Ctot = indices.shape[:2]
+    return _packed(lib().sd_op_palette_pack_halo, ptr(indices), Cout, Ctot, nbits).reshape(-(-Cout // 64), Ctot // 64, 9, nbits, 2, 64, 4)
 
 
 def conv2d_w8a8(x, wq, w_scale, act_absmax, bias=None, res=None, x1=None, upsample=False, nw=0, out=None, iters=1):

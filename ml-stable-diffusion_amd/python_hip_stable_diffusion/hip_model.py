@@ -205,6 +205,15 @@ class Weights(_lib.Handle):
         s = C.c_float(0)
         return float(s.value) if _lib.lib().sd_weights_w8a8_info(self._h, name.encode(), C.byref(s)) else None
 
+    def palette_halo(self, on=True):
+        """Handles created from the store while this is on also run their palettized 3x3 / stride-1 halo convs - resnet ``conv1`` /
+        ``conv2``, the two-source convs of the up blocks, upsamplers - from the palette (``sd_weights_palette_halo``, plan tile 25):
+        the index stream and the LUT on the device, no fp16 copy, the same bits out.  Off by default."""
+        if on not in (False, True, 0, 1):
+            raise ValueError(f"palette_halo must be False or True, got {on!r}")
+        _lib.check(_lib.lib().sd_weights_palette_halo(self._h, int(on)))
+        self._palette_halo = bool(on)
+
     def observe_activations(self, on=True):
         """Handles created from the store while this is on carry the activation observers (calibration): ``True`` in front of the
         convs the int8 weight stream could take (plan tile 17), ``"all"`` in front of those of the int8 halo conv (plan tile 18) too,
@@ -252,7 +261,8 @@ class HipModel(_lib.Model):
 
     def __init__(self, config, weights, kind="unet", batch=2, latent_height=None, latent_width=None,
                  attention_implementation="SPLIT_EINSUM", device=0, use_graph=True, context_len=77, quantize_nbits=None,
-                 palettization_recipe=None, recipe_strict=True, activation_quantization=None, observe_activations=False):
+                 palettization_recipe=None, recipe_strict=True, activation_quantization=None, observe_activations=False,
+                 palette_halo=False):
         if kind not in ("unet", "controlnet"):
             raise ValueError(f"kind must be 'unet' or 'controlnet', got {kind!r}")
         if (activation_quantization is not None or observe_activations) and kind != "unet":
@@ -317,11 +327,16 @@ class HipModel(_lib.Model):
                 aq.apply(store, self.activation_quantization)
             if observe_activations:
                 store.observe_activations(observe_activations)
+            halo_was = getattr(store, "_palette_halo", False)
+            if palette_halo:   # the palettized 3x3 halo convs stay palettized on the device (plan tile 25)
+                store.palette_halo(True)
             try:
                 _lib.check(_lib.lib().sd_unet_create(C.byref(c), store._h, device, C.byref(self._h)))
             finally:
                 if observe_activations:
                     store.observe_activations(False)   # a lent store goes back as it came
+                if palette_halo and not halo_was:
+                    store.palette_halo(False)
         if self.activation_quantization is not None:
             applied = set(self.w8a8_layers())
             stayed = sorted(set(self.activation_quantization) - applied)
@@ -558,8 +573,8 @@ class HipModel(_lib.Model):
         return _lib.lib().sd_unet_arena_used_bytes(self._h)
 
     def palette_info(self):
-        """(tensors that arrived with a palette, convs that read theirs on the device - plan tile 14 -, bytes of those convs' index
-        streams and LUTs)."""
+        """(tensors that arrived with a palette, convs that read theirs on the device - plan tiles 14 / 15 / 16, and 25 in a handle built
+        with ``palette_halo`` -, bytes of those convs' index streams and LUTs)."""
         n_pal, n_str, nbytes = C.c_int(0), C.c_int(0), C.c_size_t(0)
         _lib.check(_lib.lib().sd_unet_palette_info(self._h, C.byref(n_pal), C.byref(n_str), C.byref(nbytes)))
         return n_pal.value, n_str.value, nbytes.value

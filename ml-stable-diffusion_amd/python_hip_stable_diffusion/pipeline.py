@@ -624,7 +624,7 @@ def get_hip_pipe(model_dir, model_version, compute_unit="ALL", scheduler_overrid
                  num_images=1, guidance_scale=7.5, unet_batch_one=False, latent_size=None, device=0,
                  refiner_dir=None, tokenizer_factory=None, text_encoder_factory=None, vae_dtype=None, disable_safety=False,
                  vae_encoder=False, quantize_nbits=None, palettization_recipe=None, device_postprocess=False,
-                 activation_quantization=None, observe_activations=False, unet_weights=None):
+                 activation_quantization=None, observe_activations=False, unet_weights=None, palette_halo=False):
     """``get_coreml_pipe`` (pipeline.py:607-697) without the conversion step: ``model_dir`` is a diffusers
     checkpoint directory (``unet/``, ``vae/``, ``text_encoder/``, ``tokenizer/``, ``scheduler/`` [,
     ``text_encoder_2/``, ``tokenizer_2/``]) instead of a folder of ``.mlpackage`` files; ControlNets are
@@ -642,6 +642,8 @@ def get_hip_pipe(model_dir, model_version, compute_unit="ALL", scheduler_overrid
     mixed_bit_compression_apply.py); the text encoder, the VAE and the safety checker stay as they are.  A recipe is the UNet's: a
     module of it that the UNet lacks raises ``KeyError``; the ControlNets and the refiner take the modules they share with it (a
     ControlNet has the UNet's down and mid blocks) and leave the rest of their weights fp16.
+    ``palette_halo``: those models also keep their palettized 3x3 resnet / upsampler convs palettized on the device (plan tile 25,
+    ``Weights.palette_halo``): less memory, the same images; off by default.
     ``device_postprocess``: the 8-bit image and the safety checker's input are made on the device (``HipStableDiffusionPipeline``).
     ``activation_quantization``: a W8A8 recipe, a path or a dict {layer: act_absmax} (``activation_quantization.load_recipe``), applied
     to the UNet alone (activation_quantization.py:141-203 ``--quantize-pytorch``; the refiner and the ControlNets stay as they are;
@@ -678,7 +680,7 @@ def get_hip_pipe(model_dir, model_version, compute_unit="ALL", scheduler_overrid
         size = latent_size or cfg.get("sample_size", 64)
         return HipModel(cfg, weights if weights is not None else _find_weights(folder), kind=kind, batch=batch, latent_height=size, latent_width=size,
                         attention_implementation=attention_implementation, device=device, quantize_nbits=quantize_nbits,
-                        palettization_recipe=palettization_recipe, recipe_strict=recipe_strict, **w8a8)
+                        palettization_recipe=palettization_recipe, recipe_strict=recipe_strict, palette_halo=palette_halo, **w8a8)
 
     kwargs = dict(xl=xl, force_zeros_for_empty_prompt=force_zeros_for_empty_prompt, safety_checker=None)
     logger.info("Loading models in HBM from %s", model_dir)
@@ -804,6 +806,10 @@ def build_parser():
     parser.add_argument("--quantize-nbits", default=None, choices=(1, 2, 4, 6, 8), type=int,       # torch2coreml.py:1705
                         help="If specified, the UNet / refiner / ControlNet weights are palettized to this many bits at load time "
                              "(k-means LUT per tensor; the conversion-time flag of torch2coreml.py)")
+    parser.add_argument("--palette-halo", action="store_true",
+                        help="With --quantize-nbits or a recipe: the palettized 3x3 resnet and upsampler convs also stay palettized on the "
+                             "GPU (index stream + LUT decoded in the kernel, plan tile 25) instead of being uploaded as fp16; same images, "
+                             "less device memory")
     parser.add_argument("--pre-analysis-json-path", default=None,                                # mixed_bit_compression_apply.py
                         help="The JSON file generated by mixed_bit_compression_pre_analysis.py: per-layer palettization recipes")
     parser.add_argument("--selected-recipe", default=None,
@@ -845,6 +851,9 @@ def main(args):
             raise ValueError("--pre-analysis-json-path and --selected-recipe go together, and not with --quantize-nbits")
         from .palettize import load_recipe
         recipe = load_recipe(args.pre_analysis_json_path, args.selected_recipe)
+    palette_halo = bool(getattr(args, "palette_halo", False))
+    if palette_halo and getattr(args, "quantize_nbits", None) is None and recipe is None:
+        raise ValueError("--palette-halo keeps palettized convs palettized: it goes with --quantize-nbits or --pre-analysis-json-path / --selected-recipe")
     aq_recipe, calibrate = getattr(args, "activation_quantization_recipe", None), getattr(args, "calibrate_activations", None)
     from .activation_quantization import all_calibration_scopes
     if aq_recipe and calibrate:
@@ -855,7 +864,7 @@ def main(args):
                         guidance_scale=args.guidance_scale, unet_batch_one=args.unet_batch_one, refiner_dir=args.refiner,
                         disable_safety=getattr(args, "disable_safety", False), vae_encoder=bool(getattr(args, "image", None)),
                         quantize_nbits=getattr(args, "quantize_nbits", None), palettization_recipe=recipe,
-                        device_postprocess=getattr(args, "device_postprocess", False), activation_quantization=aq_recipe,
+                        device_postprocess=getattr(args, "device_postprocess", False), activation_quantization=aq_recipe, palette_halo=palette_halo,
                         observe_activations=all_calibration_scopes()[getattr(args, "calibrate_scope", "stream")] if calibrate else False)
     controlnet_cond = None
     if args.controlnet:
