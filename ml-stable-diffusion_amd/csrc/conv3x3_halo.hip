@@ -72,13 +72,7 @@ __global__ __launch_bounds__(256, halo_lds_bytes(64, D) <= 80 * 1024 ? 2 : 1) vo
   const int n_tiles = (a.N + BN - 1) / BN;
   const int m_tiles = a.B * a.tiles_y * a.tiles_x;
   const int nwg = m_tiles * n_tiles;
-  int bid = blockIdx.x;
-  {
-    int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    bid = base + idx;
-  }
-  const int bn_idx = a.n_fast ? bid % n_tiles : bid / m_tiles, mt = a.n_fast ? bid / n_tiles : bid % m_tiles;
+  HALO_PLACE_WG                                 // -> bn_idx, mt
   const int b = mt / (a.tiles_y * a.tiles_x);
   const int trem = mt - b * (a.tiles_y * a.tiles_x);
   const int ty = trem / a.tiles_x, tx = trem - ty * a.tiles_x;
@@ -127,15 +121,7 @@ __global__ __launch_bounds__(256, halo_lds_bytes(64, D) <= 80 * 1024 ? 2 : 1) vo
     woff[i] = (unsigned)n * (unsigned)a.K * 2u + (unsigned)wchunk * 16u;
   }
 
-  // the halo of one channel chunk: which of the two concatenated sources it comes from is decided once per chunk
-  // (HALO_SRC declares rs / off[] / soff for chunk `ch` as plain locals)
-#define HALO_SRC(rs, off, soff, ch)                                                                                        \
-  const bool rs##_second = !GNL && (ch) * BK >= a.C0; /* wave-uniform; GNL: single source (6 VGPRs of offsets less) */    \
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(                                                     \
-      const_cast<half_t*>(rs##_second ? a.x1 : a.x0), 0, (int)(xpix * (rs##_second ? a.C1 : a.C0) * 2), 0x00020000);       \
-  const int soff = (rs##_second ? (ch) * BK - a.C0 : (ch) * BK) * 2;                                                       \
-  unsigned off[HALO_PPW];                                                                                                  \
-  _Pragma("unroll") for (int j_ = 0; j_ < HALO_PPW; ++j_) off[j_] = rs##_second ? hoff1[j_] : hoff0[j_];
+  // the halo of one channel chunk: HALO_SRC (halo_ring.h), single source with GNL
   auto issue_x_piece = [&](int j, const __amdgpu_buffer_rsrc_t& rs, unsigned off, int soff, int xstage) {
     if constexpr ((DBG & 8) != 0) return;
     char* dst = Xh + xstage * (HALO_LDS_ROWS * ROWB) + piece_of(j) * 1024;
@@ -270,7 +256,7 @@ __global__ __launch_bounds__(256, halo_lds_bytes(64, D) <= 80 * 1024 ? 2 : 1) vo
         gnl_b[i] = a.gnf_beta[k];
       }
     }
-    HALO_SRC(rs0, off0, soff0, ch_begin)
+    HALO_SRC(GNL, rs0, off0, soff0, ch_begin)
 #pragma unroll
     for (int j = 0; j < HALO_PPW; ++j) issue_x_piece(j, rs0, off0[j], soff0, 0);
 #pragma unroll
@@ -332,7 +318,7 @@ __global__ __launch_bounds__(256, halo_lds_bytes(64, D) <= 80 * 1024 ? 2 : 1) vo
     constexpr bool LAST = decltype(last)::value;
     const int xst = (ch - ch_begin) & 1;
     const bool first_chunk = ch == ch_begin;
-    HALO_SRC(rsn, offn, soffn, (LAST ? ch : ch + 1))
+    HALO_SRC(GNL, rsn, offn, soffn, (LAST ? ch : ch + 1))
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap, ++st) {
       auto body = [&](half8 (&cx)[2][2], half8 (&cw)[2][2], half8 (&nx)[2][2], half8 (&nw)[2][2]) {
@@ -398,123 +384,17 @@ __global__ __launch_bounds__(256, halo_lds_bytes(64, D) <= 80 * 1024 ? 2 : 1) vo
       __builtin_amdgcn_sched_barrier(0);
     }
   };
-  {
-    using T = std::true_type;
-    using F = std::false_type;
-    using P0 = std::integral_constant<int, 0>;
-    using P1 = std::integral_constant<int, 1>;
-    int ch = ch_begin;
-    for (; ch + 2 < ch_end; ch += 2) {
-      chunk(P0{}, F{}, ch);
-      chunk(P1{}, F{}, ch + 1);
-    }
-    if (ch + 2 == ch_end) {
-      chunk(P0{}, F{}, ch);
-      chunk(P1{}, T{}, ch + 1);
-    } else if (ch + 1 == ch_end) {
-      chunk(P0{}, T{}, ch);
-    }
-  }
+  HALO_WALK_CHUNKS(chunk, ch_begin, ch_end)
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __syncthreads();                                        // every wave is out of the K loop: LDS is free
 
-  // ---- epilogue.  acc[i][j][r]: n = j*32 + (r&3) + 8*(r>>2) + 4*hi ; pixel block 2*wm + i, pixel frow ----
-  // sum the two K halves: wave (wm, wk) keeps pixel block 2*wm + wk and hands the other one to its partner
-  {
-    floatx4* red = reinterpret_cast<floatx4*>(smem);      // [4 waves][2 j][4 q][64 lanes] = 32 KB
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        floatx4 v;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = wk ? acc[0][j][4 * q + e] : acc[1][j][4 * q + e];
-        red[((wave * 2 + j) * 4 + q) * 64 + lane] = v;
-      }
-    if (tid < BN) sconst[tid] = const_b + const_t;
-    __syncthreads();
-  }
-  floatx16 fin[2];
-  {
-    const floatx4* red = reinterpret_cast<const floatx4*>(smem);
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const floatx4 v = red[(((wave ^ 1) * 2 + j) * 4 + q) * 64 + lane];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) fin[j][4 * q + e] = (wk ? acc[1][j][4 * q + e] : acc[0][j][4 * q + e]) + v[e];
-      }
-  }
-  const int ml = (wm * 2 + wk) * 32 + frow;               // tile-local pixel of this lane
-  if (a.slab) {
-    const int y = y0 + (ml >> 4), x = x0 + (ml & 15);
-    if (y < H && x < W) {
-      const int m = (b * H + y) * W + x;
-      float* prow = a.partial + ((size_t)split * a.M + m) * a.N;
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int n = n_blk + j * 32 + 8 * q + 4 * hi;
-          if (n < a.N) {
-            floatx4 v = {fin[j][4 * q], fin[j][4 * q + 1], fin[j][4 * q + 2], fin[j][4 * q + 3]};
-            out_store(reinterpret_cast<floatx4*>(prow + n), v);
-          }
-        }
-    }
-    return;
-  }
-  constexpr int OROW = BN + 8;
-  half_t* ot = reinterpret_cast<half_t*>(smem + 32 * 1024);   // [BM][OROW], behind the reduction buffer
-#pragma unroll
-  for (int j = 0; j < 2; ++j)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int nl = j * 32 + 8 * q + 4 * hi;
-      const floatx4 bb = *reinterpret_cast<const floatx4*>(sconst + nl);   // 0 beyond N
-      half4 o = {(half_t)(fin[j][4 * q] + bb[0]), (half_t)(fin[j][4 * q + 1] + bb[1]), (half_t)(fin[j][4 * q + 2] + bb[2]),
-                 (half_t)(fin[j][4 * q + 3] + bb[3])};
-      *reinterpret_cast<half4*>(ot + ml * OROW + nl) = o;
-    }
-  __syncthreads();
-  constexpr int WC = BN / 8;
-  const bool gn = a.gn_partial != nullptr;   // block-uniform (launch_conv: N % 8 == 0)
-  float fs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, fq[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int idx = tid; idx < BM * WC; idx += 256) {
-    const int r = idx / WC, c = idx - r * WC;
-    const int y = y0 + (r >> 4), x = x0 + (r & 15);
-    const int n = n_blk + c * 8;
-    if (y < H && x < W && n < a.N) {
-      const size_t m = (size_t)(b * H + y) * W + x;
-      half8 v = *reinterpret_cast<const half8*>(ot + r * OROW + c * 8);
-      half_t* dst = a.out + m * a.N + n;
-      if (n + 8 <= a.N) {
-        if (a.res) {
-          const half8 rr = *reinterpret_cast<const half8*>(a.res + m * a.N + n);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] = (half_t)((float)v[e] + (float)rr[e]);
-        }
-        out_store(reinterpret_cast<half8*>(dst), v);
-        if (gn) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            const float f = (float)v[e];
-            fs[e] += f;
-            fq[e] = fmaf(f, f, fq[e]);
-          }
-        }
-      } else {
-        for (int e = 0; e < a.N - n; ++e) dst[e] = a.res ? (half_t)((float)v[e] + (float)a.res[m * a.N + n + e]) : v[e];
-      }
-    }
-  }
-  // GroupNorm statistics of the stored pixels (only those inside the image); the scratch is the K-half reduction
-  // buffer at the start of the LDS, which nobody reads after the barrier above
-  if (gn) tile_gn_stats<BN>(a, reinterpret_cast<float*>(smem), fs, fq, n_blk, b, ty * a.tiles_x + tx);
+  // ---- epilogue: halo_epilogue.inc, the statement tiles 21 and 25 include as well ----
+#define HALO_OUT_PIXEL(y, x) (b * H + y) * W + x
+#define HALO_GN_STATS true
+#include "halo_epilogue.inc"
+#undef HALO_OUT_PIXEL
+#undef HALO_GN_STATS
 }
-
-#undef HALO_SRC
 
 // 2 weight stages: two workgroups per CU.  GNL: halo_gnl_lds_bytes (conv_plan.h)
 template <int D, int DBG = 0, bool GNL = false>

@@ -35,6 +35,8 @@
 //   * RING: 2 / 3 / 4 stages of 4 KB (the transform schedule needs D <= 4; a plan code that names a deeper ring runs the 4-stage one).
 //     LDS: 23 KB staging + 2 x 12.75 KB int8 image + D x 4 KB: two workgroups per CU at every depth.
 //   * NOT HERE: GroupNorm in the loader, ablation builds, out modes other than the plain one.
+// Shared with tile 7 as text (halo_ring.h): workgroup placement, source switch, chunk walk.  NOT halo_epilogue.inc: this epilogue is
+// another statement - int32 exchange, fp32 staging, one rounding.
 #include "igemm_device.h"
 #include "halo_ring.h"
 #include "quantize8.h"
@@ -77,13 +79,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_i8_kernel(HaloI8Args ha) 
   const int n_tiles = (a.N + BN - 1) / BN;
   const int m_tiles = a.B * a.tiles_y * a.tiles_x;
   const int nwg = m_tiles * n_tiles;
-  int bid = blockIdx.x;
-  {
-    int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    bid = base + idx;
-  }
-  const int bn_idx = a.n_fast ? bid % n_tiles : bid / m_tiles, mt = a.n_fast ? bid / n_tiles : bid % m_tiles;
+  HALO_PLACE_WG                                 // -> bn_idx, mt
   const int b = mt / (a.tiles_y * a.tiles_x);
   const int trem = mt - b * (a.tiles_y * a.tiles_x);
   const int ty = trem / a.tiles_x, tx = trem - ty * a.tiles_x;
@@ -124,13 +120,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_i8_kernel(HaloI8Args ha) 
     woff = (unsigned)n * (unsigned)a.K + (unsigned)(pchunk ^ ((lrow >> 2) & 3)) * 16u;
   }
 
-#define HALO_SRC(rs, off, soff, ch)                                                                                        \
-  const bool rs##_second = (ch) * BK >= a.C0; /* wave-uniform */                                                           \
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(                                                     \
-      const_cast<half_t*>(rs##_second ? a.x1 : a.x0), 0, (int)(xpix * (rs##_second ? a.C1 : a.C0) * 2), 0x00020000);       \
-  const int soff = (rs##_second ? (ch) * BK - a.C0 : (ch) * BK) * 2;                                                       \
-  unsigned off[HALO_PPW];                                                                                                  \
-  _Pragma("unroll") for (int j_ = 0; j_ < HALO_PPW; ++j_) off[j_] = rs##_second ? hoff1[j_] : hoff0[j_];
+  // the halo of one channel chunk: HALO_SRC (halo_ring.h), always two sources
   auto issue_x_piece = [&](int j, const __amdgpu_buffer_rsrc_t& rs, unsigned off, int soff) {
     dma16_to_lds(rs, Xs + piece_of(j) * 1024, off, soff);
   };
@@ -200,7 +190,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_i8_kernel(HaloI8Args ha) 
 
   intx4 xfA[2], wfA[2], xfB[2], wfB[2];
   if (ch_begin < ch_end) {
-    HALO_SRC(rs0, off0, soff0, ch_begin)
+    HALO_SRC(false, rs0, off0, soff0, ch_begin)
 #pragma unroll
     for (int j = 0; j < HALO_PPW; ++j) issue_x_piece(j, rs0, off0[j], soff0);
 #pragma unroll
@@ -221,7 +211,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_i8_kernel(HaloI8Args ha) 
     constexpr int PAR = decltype(par)::value;
     constexpr bool LAST = decltype(last)::value;
     const int xst = (ch - ch_begin) & 1;
-    HALO_SRC(rsn, offn, soffn, (LAST ? ch : ch + 1))
+    HALO_SRC(false, rsn, offn, soffn, (LAST ? ch : ch + 1))
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap, ++st) {
       auto body = [&](intx4 (&cx)[2], intx4 (&cw)[2], intx4 (&nx)[2], intx4 (&nw)[2]) {
@@ -262,23 +252,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_i8_kernel(HaloI8Args ha) 
       __builtin_amdgcn_sched_barrier(0);
     }
   };
-  {
-    using T = std::true_type;
-    using F = std::false_type;
-    using P0 = std::integral_constant<int, 0>;
-    using P1 = std::integral_constant<int, 1>;
-    int ch = ch_begin;
-    for (; ch + 2 < ch_end; ch += 2) {
-      chunk(P0{}, F{}, ch);
-      chunk(P1{}, F{}, ch + 1);
-    }
-    if (ch + 2 == ch_end) {
-      chunk(P0{}, F{}, ch);
-      chunk(P1{}, T{}, ch + 1);
-    } else if (ch + 1 == ch_end) {
-      chunk(P0{}, T{}, ch);
-    }
-  }
+  HALO_WALK_CHUNKS(chunk, ch_begin, ch_end)
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __syncthreads();                                        // every wave is out of the K loop: LDS is free
 
@@ -391,8 +365,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_i8_kernel(HaloI8Args ha) 
   // GroupNorm statistics of the stored pixels, as tile 7 leaves them (the scratch is the K-half reduction buffer)
   if (gn) tile_gn_stats<BN>(a, reinterpret_cast<float*>(smem), fs, fq, n_blk, b, ty * a.tiles_x + tx);
 }
-
-#undef HALO_SRC
 
 template <int D>
 void launch_halo_i8_d(const HaloI8Args& ha, hipStream_t s) {

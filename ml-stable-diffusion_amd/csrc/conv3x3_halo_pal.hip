@@ -5,9 +5,9 @@
 // outside the image read as zeros through the buffer range check, the counted waits of halo_ring.h - so the planner's tile counts,
 // ring codes, split-K rule and workspace arithmetic are tile 7's, and so is the RESULT: the MFMAs (v_mfma_f32_32x32x16_f16), their
 // operand order and the accumulation order over (chunk, tap, s) are tile 7's on the fp16 bit patterns the LUT holds, the epilogue is
-// tile 7's arithmetic statement for statement (only the fetch of the bias / time-embedding row moved behind the K loop: two registers
-// the decode needs), so the plain store, the slabs and the GroupNorm statistics are bit-identical to tile 7 on
-// lut[indices] at the same ring code and split-K.
+// the statement tile 7 runs (halo_epilogue.inc, included by both; only the fetch of the bias / time-embedding row sits behind the K
+// loop here: two registers the decode needs), so the plain store, the slabs and the GroupNorm statistics are bit-identical to tile 7
+// on lut[indices] at the same ring code and split-K.  Workgroup placement and chunk walk: the statements of halo_ring.h.
 //
 // Only the weight side differs:
 //   * HBM: the index stream of weight_prep.h halo_pal_pack - per (64-row n-tile, chunk, tap) one block of NBITS * 128 dwords, blocks in
@@ -26,8 +26,8 @@
 //     lanes 32-63 carry the out-of-range offset and write zeros over the epilogue constants and the 256 B behind them
 //     (halo_pal_lds_bytes), which nobody reads before the epilogue writes them.
 //   * NOT HERE: GroupNorm in the loader, ablation builds, out modes other than the plain one.
-// Why a file of its own and a copy of tile 7's epilogue text: LAB_NOTES.md round 34 (one body for both changed the register allocation of
-// the fp16 instantiations).
+// Why a file of its own: LAB_NOTES.md round 34 (one body for both changed the register allocation of the fp16 instantiations).  What
+// the two share as text instead, and the proof that it left the generated code alone: round 35.
 #include "igemm_device.h"
 #include "halo_ring.h"
 #include "pal_decode.h"
@@ -71,13 +71,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_pal_kernel(HaloPalArgs pa
   const int n_tiles = (a.N + BN - 1) / BN;
   const int m_tiles = a.B * a.tiles_y * a.tiles_x;
   const int nwg = m_tiles * n_tiles;
-  int bid = blockIdx.x;
-  {
-    int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    bid = base + idx;
-  }
-  const int bn_idx = a.n_fast ? bid % n_tiles : bid / m_tiles, mt = a.n_fast ? bid / n_tiles : bid % m_tiles;
+  HALO_PLACE_WG                                 // -> bn_idx, mt
   const int b = mt / (a.tiles_y * a.tiles_x);
   const int trem = mt - b * (a.tiles_y * a.tiles_x);
   const int ty = trem / a.tiles_x, tx = trem - ty * a.tiles_x;
@@ -94,7 +88,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_pal_kernel(HaloPalArgs pa
   const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(pa.stream), 0, (int)pa.stream_bytes, 0x00020000);
   const size_t xpix = (size_t)a.B * a.Hi * a.Wi;
   // this lane's 16 bytes of halo piece j: pixel * 128 + swizzled 16-B slot (< 128), or kOob outside the image.  The byte offset at
-  // channel 0 of a source with C channels is pixel * 2 C + slot (C a multiple of 64): formed per chunk (HALO_SRC), so that one
+  // channel 0 of a source with C channels is pixel * 2 C + slot (C a multiple of 64): formed per chunk (HALO_PAL_SRC), so that one
   // register per piece lives through the tap steps where tile 7 keeps two (one per source) - the decode needs them
   unsigned hpix[HALO_PPW];
   // piece of slot j.  The 24th slot (wave 3, j = 5) has no piece of its own: it fetches piece 22 a second time (same bytes)
@@ -113,9 +107,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_pal_kernel(HaloPalArgs pa
   const unsigned woff = tid * 16 < BLOCKB ? (unsigned)tid * 16u : kOob;   // this thread's 16 bytes of a block
 
   // the halo of one channel chunk: which of the two concatenated sources it comes from is decided once per chunk
-  // (HALO_SRC declares rs / soff for chunk `ch` as plain locals and off(j), this lane's byte offset of piece j in that source - formed
+  // (HALO_PAL_SRC - halo_ring.h's HALO_SRC with one register per piece - declares rs / soff for chunk `ch` as plain locals and off(j), this lane's byte offset of piece j in that source - formed
   // where the piece is issued, so that no array of offsets lives through the tap steps)
-#define HALO_SRC(rs, off, soff, ch)                                                                                        \
+#define HALO_PAL_SRC(rs, off, soff, ch)                                                                                       \
   const bool rs##_second = (ch) * BK >= a.C0; /* wave-uniform */                                                           \
   const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(                                                     \
       const_cast<half_t*>(rs##_second ? a.x1 : a.x0), 0, (int)(xpix * (rs##_second ? a.C1 : a.C0) * 2), 0x00020000);       \
@@ -195,7 +189,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_pal_kernel(HaloPalArgs pa
       dma16_to_lds(rs_lut, Lut, lane * 16 < kPalLutHalves * 2 ? (unsigned)lane * 16u : kOob, 0);
       asm volatile("" ::: "memory");
     }
-    HALO_SRC(rs0, off0, soff0, ch_begin)
+    HALO_PAL_SRC(rs0, off0, soff0, ch_begin)
 #pragma unroll
     for (int j = 0; j < HALO_PPW; ++j) issue_x_piece(j, rs0, off0(j), soff0, 0);
 #pragma unroll
@@ -217,7 +211,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_pal_kernel(HaloPalArgs pa
     constexpr bool LAST = decltype(last)::value;
     const int xst = (ch - ch_begin) & 1;
     const bool first_chunk = ch == ch_begin;
-    HALO_SRC(rsn, offn, soffn, (LAST ? ch : ch + 1))
+    HALO_PAL_SRC(rsn, offn, soffn, (LAST ? ch : ch + 1))
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap, ++st) {
       auto body = [&](half8 (&cx)[2][2], half8 (&cw)[2][2], half8 (&nx)[2][2], half8 (&nw)[2][2]) {
@@ -252,128 +246,24 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_pal_kernel(HaloPalArgs pa
       __builtin_amdgcn_sched_barrier(0);
     }
   };
-  {
-    using T = std::true_type;
-    using F = std::false_type;
-    using P0 = std::integral_constant<int, 0>;
-    using P1 = std::integral_constant<int, 1>;
-    int ch = ch_begin;
-    for (; ch + 2 < ch_end; ch += 2) {
-      chunk(P0{}, F{}, ch);
-      chunk(P1{}, F{}, ch + 1);
-    }
-    if (ch + 2 == ch_end) {
-      chunk(P0{}, F{}, ch);
-      chunk(P1{}, T{}, ch + 1);
-    } else if (ch + 1 == ch_end) {
-      chunk(P0{}, T{}, ch);
-    }
-  }
+  HALO_WALK_CHUNKS(chunk, ch_begin, ch_end)
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __syncthreads();                                        // every wave is out of the K loop: LDS is free
 
-  // ---- epilogue: tile 7's, statement for statement.  acc[i][j][r]: n = j*32 + (r&3) + 8*(r>>2) + 4*hi ; pixel block 2*wm + i, pixel frow ----
+  // ---- epilogue: tile 7's (halo_epilogue.inc); the bias / time-embedding row is fetched here, not in front of the K loop (two registers) ----
   float const_b = 0.f, const_t = 0.f;
   if (!a.slab && tid < BN && n_blk + tid < a.N) {
     if (a.bias) const_b = a.bias[n_blk + tid];
     if (a.temb) const_t = a.temb[(size_t)b * a.temb_stride + n_blk + tid];
   }
-  // sum the two K halves: wave (wm, wk) keeps pixel block 2*wm + wk and hands the other one to its partner
-  {
-    floatx4* red = reinterpret_cast<floatx4*>(smem);      // [4 waves][2 j][4 q][64 lanes] = 32 KB
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        floatx4 v;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = wk ? acc[0][j][4 * q + e] : acc[1][j][4 * q + e];
-        red[((wave * 2 + j) * 4 + q) * 64 + lane] = v;
-      }
-    if (tid < BN) sconst[tid] = const_b + const_t;
-    __syncthreads();
-  }
-  floatx16 fin[2];
-  {
-    const floatx4* red = reinterpret_cast<const floatx4*>(smem);
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const floatx4 v = red[(((wave ^ 1) * 2 + j) * 4 + q) * 64 + lane];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) fin[j][4 * q + e] = (wk ? acc[1][j][4 * q + e] : acc[0][j][4 * q + e]) + v[e];
-      }
-  }
-  const int ml = (wm * 2 + wk) * 32 + frow;               // tile-local pixel of this lane
-  if (a.slab) {
-    const int y = y0 + (ml >> 4), x = x0 + (ml & 15);
-    if (y < H && x < W) {
-      const int m = (b * H + y) * W + x;
-      float* prow = a.partial + ((size_t)split * a.M + m) * a.N;
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int n = n_blk + j * 32 + 8 * q + 4 * hi;
-          if (n < a.N) {
-            floatx4 v = {fin[j][4 * q], fin[j][4 * q + 1], fin[j][4 * q + 2], fin[j][4 * q + 3]};
-            out_store(reinterpret_cast<floatx4*>(prow + n), v);
-          }
-        }
-    }
-    return;
-  }
-  constexpr int OROW = BN + 8;
-  half_t* ot = reinterpret_cast<half_t*>(smem + 32 * 1024);   // [BM][OROW], behind the reduction buffer
-#pragma unroll
-  for (int j = 0; j < 2; ++j)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int nl = j * 32 + 8 * q + 4 * hi;
-      const floatx4 bb = *reinterpret_cast<const floatx4*>(sconst + nl);   // 0 beyond N
-      half4 o = {(half_t)(fin[j][4 * q] + bb[0]), (half_t)(fin[j][4 * q + 1] + bb[1]), (half_t)(fin[j][4 * q + 2] + bb[2]),
-                 (half_t)(fin[j][4 * q + 3] + bb[3])};
-      *reinterpret_cast<half4*>(ot + ml * OROW + nl) = o;
-    }
-  __syncthreads();
-  constexpr int WC = BN / 8;
-  const bool gn = a.gn_partial != nullptr;   // block-uniform (launch_conv: N % 8 == 0)
-  float fs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, fq[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int idx = tid; idx < BM * WC; idx += 256) {
-    const int r = idx / WC, c = idx - r * WC;
-    const int y = y0 + (r >> 4), x = x0 + (r & 15);
-    const int n = n_blk + c * 8;
-    if (y < H && x < W && n < a.N) {
-      const size_t m = (size_t)(b * H + y) * W + x;
-      half8 v = *reinterpret_cast<const half8*>(ot + r * OROW + c * 8);
-      half_t* dst = a.out + m * a.N + n;
-      if (n + 8 <= a.N) {
-        if (a.res) {
-          const half8 rr = *reinterpret_cast<const half8*>(a.res + m * a.N + n);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] = (half_t)((float)v[e] + (float)rr[e]);
-        }
-        out_store(reinterpret_cast<half8*>(dst), v);
-        if (gn) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            const float f = (float)v[e];
-            fs[e] += f;
-            fq[e] = fmaf(f, f, fq[e]);
-          }
-        }
-      } else {
-        for (int e = 0; e < a.N - n; ++e) dst[e] = a.res ? (half_t)((float)v[e] + (float)a.res[m * a.N + n + e]) : v[e];
-      }
-    }
-  }
-  // GroupNorm statistics of the stored pixels (only those inside the image); the scratch is the K-half reduction
-  // buffer at the start of the LDS, which nobody reads after the barrier above
-  if (gn) tile_gn_stats<BN>(a, reinterpret_cast<float*>(smem), fs, fq, n_blk, b, ty * a.tiles_x + tx);
+#define HALO_OUT_PIXEL(y, x) (b * H + y) * W + x
+#define HALO_GN_STATS true
+#include "halo_epilogue.inc"
+#undef HALO_OUT_PIXEL
+#undef HALO_GN_STATS
 }
 
-#undef HALO_SRC
+#undef HALO_PAL_SRC
 
 template <int NBITS, int D>
 void launch_halo_pal_d(const HaloPalArgs& pa, hipStream_t s) {

@@ -14,6 +14,8 @@
 //   * a chunk runs the FOUR tap steps (ky, kx) in {a, a+1} x {b, b+1}: the LDS row shifts tile 7 uses for those taps, so its bank
 //     argument carries over unchanged;
 //   * output pixel (i, j) of the tile goes to (2 i + a, 2 j + b) of the 2H x 2W image; a pixel's 64 channels are one 128-B segment.
+// The epilogue is the statement tile 7 runs (halo_epilogue.inc, included by both) with that output pixel and without the GroupNorm
+// statistics; the workgroup placement is halo_ring.h's.
 #include "igemm_device.h"
 #include "halo_ring.h"
 
@@ -87,13 +89,7 @@ __global__ __launch_bounds__(256, halo_lds_bytes(64, D) <= 80 * 1024 ? 2 : 1) vo
   const int sp_tiles = a.B * a.tiles_y * a.tiles_x;
   const int m_tiles = 4 * sp_tiles;
   const int nwg = m_tiles * n_tiles;
-  int bid = blockIdx.x;
-  {
-    int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    bid = base + idx;
-  }
-  const int bn_idx = a.n_fast ? bid % n_tiles : bid / m_tiles, mt = a.n_fast ? bid / n_tiles : bid % m_tiles;
+  HALO_PLACE_WG                                 // -> bn_idx, mt
   const int phase = ha.phase_outer ? mt / sp_tiles : mt & 3;
   const int st_idx = ha.phase_outer ? mt - phase * sp_tiles : mt >> 2;
   const int pa = phase >> 1, pb = phase & 1;    // output rows Y = 2 i + pa, columns X = 2 j + pb
@@ -279,87 +275,12 @@ __global__ __launch_bounds__(256, halo_lds_bytes(64, D) <= 80 * 1024 ? 2 : 1) vo
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __syncthreads();                                        // every wave is out of the K loop: LDS is free
 
-  // ---- epilogue (tile 7's).  acc[i][j][r]: n = j*32 + (r&3) + 8*(r>>2) + 4*hi ; pixel block 2*wm + i, pixel frow ----
-  // sum the two K halves: wave (wm, wk) keeps pixel block 2*wm + wk and hands the other one to its partner
-  {
-    floatx4* red = reinterpret_cast<floatx4*>(smem);      // [4 waves][2 j][4 q][64 lanes] = 32 KB
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        floatx4 v;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = wk ? acc[0][j][4 * q + e] : acc[1][j][4 * q + e];
-        red[((wave * 2 + j) * 4 + q) * 64 + lane] = v;
-      }
-    if (tid < BN) sconst[tid] = const_b + const_t;
-    __syncthreads();
-  }
-  floatx16 fin[2];
-  {
-    const floatx4* red = reinterpret_cast<const floatx4*>(smem);
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const floatx4 v = red[(((wave ^ 1) * 2 + j) * 4 + q) * 64 + lane];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) fin[j][4 * q + e] = (wk ? acc[1][j][4 * q + e] : acc[0][j][4 * q + e]) + v[e];
-      }
-  }
-  const int ml = (wm * 2 + wk) * 32 + frow;               // tile-local low-res pixel of this lane
-  if (a.slab) {
-    const int y = y0 + (ml >> 4), x = x0 + (ml & 15);
-    if (y < H && x < W) {
-      const int m = (b * Ho + 2 * y + pa) * Wo + 2 * x + pb;
-      float* prow = a.partial + ((size_t)split * a.M + m) * a.N;
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int n = n_blk + j * 32 + 8 * q + 4 * hi;
-          if (n < a.N) {
-            floatx4 v = {fin[j][4 * q], fin[j][4 * q + 1], fin[j][4 * q + 2], fin[j][4 * q + 3]};
-            out_store(reinterpret_cast<floatx4*>(prow + n), v);
-          }
-        }
-    }
-    return;
-  }
-  constexpr int OROW = BN + 8;
-  half_t* ot = reinterpret_cast<half_t*>(smem + 32 * 1024);   // [BM][OROW], behind the reduction buffer
-#pragma unroll
-  for (int j = 0; j < 2; ++j)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int nl = j * 32 + 8 * q + 4 * hi;
-      const floatx4 bb = *reinterpret_cast<const floatx4*>(sconst + nl);   // 0 beyond N
-      half4 o = {(half_t)(fin[j][4 * q] + bb[0]), (half_t)(fin[j][4 * q + 1] + bb[1]), (half_t)(fin[j][4 * q + 2] + bb[2]),
-                 (half_t)(fin[j][4 * q + 3] + bb[3])};
-      *reinterpret_cast<half4*>(ot + ml * OROW + nl) = o;
-    }
-  __syncthreads();
-  constexpr int WC = BN / 8;
-  for (int idx = tid; idx < BM * WC; idx += 256) {
-    const int r = idx / WC, c = idx - r * WC;
-    const int y = y0 + (r >> 4), x = x0 + (r & 15);
-    const int n = n_blk + c * 8;
-    if (y < H && x < W && n < a.N) {
-      const size_t m = (size_t)(b * Ho + 2 * y + pa) * Wo + 2 * x + pb;
-      half8 v = *reinterpret_cast<const half8*>(ot + r * OROW + c * 8);
-      half_t* dst = a.out + m * a.N + n;
-      if (n + 8 <= a.N) {
-        if (a.res) {
-          const half8 rr = *reinterpret_cast<const half8*>(a.res + m * a.N + n);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] = (half_t)((float)v[e] + (float)rr[e]);
-        }
-        out_store(reinterpret_cast<half8*>(dst), v);
-      } else {
-        for (int e = 0; e < a.N - n; ++e) dst[e] = a.res ? (half_t)((float)v[e] + (float)a.res[m * a.N + n + e]) : v[e];
-      }
-    }
-  }
+  // ---- epilogue: tile 7's (halo_epilogue.inc); the output pixel is (2 y + pa, 2 x + pb) of the 2H x 2W image, no GroupNorm statistics ----
+#define HALO_OUT_PIXEL(y, x) (b * Ho + 2 * y + pa) * Wo + 2 * x + pb
+#define HALO_GN_STATS false
+#include "halo_epilogue.inc"
+#undef HALO_OUT_PIXEL
+#undef HALO_GN_STATS
 }
 
 template <int D>

@@ -1,5 +1,7 @@
-// The tap-step schedule shared by the 3x3 / stride-1 halo kernels (conv3x3_halo.hip plan tile 7, conv3x3_halo_i8.hip plan tile 18):
-// halo geometry, which halo pieces a wave issues in which tap step, and the counted waits that follow from that order.
+// What the 3x3 / stride-1 halo kernels share (conv3x3_halo.hip plan tile 7, conv3x3_halo_i8.hip plan tile 18, conv3x3_halo_sp.hip plan
+// tile 21, conv3x3_halo_pal.hip plan tile 25): halo geometry, which halo pieces a wave issues in which tap step, the counted waits that
+// follow from that order (tiles 7 / 18 / 25; tile 21 has a four-step schedule of its own), and at the end the statements they share
+// as text: workgroup placement, source switch, chunk walk.
 // Included behind igemm_device.h; everything sits in an unnamed namespace like the helpers there.
 #pragma once
 #include "igemm_device.h"
@@ -72,3 +74,52 @@ __device__ __forceinline__ void halo_ks_wait_last(int tap) {
 }  // namespace
 
 }  // namespace sd
+
+// ---- statements the halo kernels share as TEXT ----
+// Statement macros, not functions: by-value force-inlined helpers changed the generated code of 14 of tile 7's 16 instantiations
+// (LAB_NOTES.md round 35); as text every kernel compiles to what its own copy compiled to.  The epilogue of tiles 7 / 21 / 25 is
+// shared the same way: halo_epilogue.inc.
+
+// Workgroup placement (all four kernels): blockIdx.x -> a contiguous range of tiles per XCD (workgroups go to the eight XCDs round
+// robin), then -> (bn_idx, mt) in the order the launcher chose.  Reads nwg, n_tiles, m_tiles, a.n_fast; declares bid, bn_idx, mt.
+#define HALO_PLACE_WG                                                                                                      \
+  int bid = blockIdx.x;                                                                                                    \
+  {                                                                                                                        \
+    int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;                                                          \
+    int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;                                                    \
+    bid = base + idx;                                                                                                      \
+  }                                                                                                                        \
+  const int bn_idx = a.n_fast ? bid % n_tiles : bid / m_tiles, mt = a.n_fast ? bid / n_tiles : bid % m_tiles;
+
+// The halo of one channel chunk (tiles 7 and 18): which of the two concatenated sources it comes from is decided once per chunk.
+// Declares rs / off[] / soff for chunk `ch` as plain locals; reads a, xpix, hoff0[], hoff1[].  `single`: a compile-time switch - the
+// kernel has one source only (tile 7's GroupNorm loader: 6 VGPRs of offsets less).  (Tile 25 forms its offsets per piece: its own macro.)
+#define HALO_SRC(single, rs, off, soff, ch)                                                                                \
+  const bool rs##_second = !(single) && (ch) * BK >= a.C0; /* wave-uniform */                                              \
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(                                                     \
+      const_cast<half_t*>(rs##_second ? a.x1 : a.x0), 0, (int)(xpix * (rs##_second ? a.C1 : a.C0) * 2), 0x00020000);       \
+  const int soff = (rs##_second ? (ch) * BK - a.C0 : (ch) * BK) * 2;                                                       \
+  unsigned off[HALO_PPW];                                                                                                  \
+  _Pragma("unroll") for (int j_ = 0; j_ < HALO_PPW; ++j_) off[j_] = rs##_second ? hoff1[j_] : hoff0[j_];
+
+// The walk over a K range of nine-step chunks (tiles 7, 18 and 25): chunk(par, last, ch) with PAR = parity of the chunk's first step
+// and LAST = the final chunk as compile-time arguments - two chunks per trip, so the register set a chunk starts in is static.
+// (Tile 21's chunks have four steps, an even number: its own walk.)
+#define HALO_WALK_CHUNKS(chunk, ch_begin, ch_end)                                                                          \
+  {                                                                                                                        \
+    using T = std::true_type;                                                                                              \
+    using F = std::false_type;                                                                                             \
+    using P0 = std::integral_constant<int, 0>;                                                                             \
+    using P1 = std::integral_constant<int, 1>;                                                                             \
+    int ch = ch_begin;                                                                                                     \
+    for (; ch + 2 < ch_end; ch += 2) {                                                                                     \
+      chunk(P0{}, F{}, ch);                                                                                                \
+      chunk(P1{}, F{}, ch + 1);                                                                                            \
+    }                                                                                                                      \
+    if (ch + 2 == ch_end) {                                                                                                \
+      chunk(P0{}, F{}, ch);                                                                                                \
+      chunk(P1{}, T{}, ch + 1);                                                                                            \
+    } else if (ch + 1 == ch_end) {                                                                                         \
+      chunk(P0{}, T{}, ch);                                                                                                \
+    }                                                                                                                      \
+  }

@@ -28,7 +28,7 @@ def kernel_resources(src, tmp_path):
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 @pytest.mark.parametrize("src", ["igemm.hip", "conv3x3_halo.hip", "conv_small.hip", "attention.hip", "norm.hip", "misc.hip", "wstream.hip", "smgemm.hip",
-                                 "smgeglu.hip", "smgemm_i8.hip", "smgeglu_i8.hip", "smqkv_i8.hip", "conv3x3_halo_i8.hip", "conv3x3_halo_sp.hip"])
+                                 "smgeglu.hip", "smgemm_i8.hip", "smgeglu_i8.hip", "smqkv_i8.hip", "conv3x3_halo_i8.hip", "conv3x3_halo_sp.hip", "conv3x3_halo_pal.hip"])
 def test_no_kernel_spills_and_two_workgroups_per_cu_where_planned(src, tmp_path):
     res = kernel_resources(os.path.join(CSRC, src), tmp_path)
     assert res, "no kernels found"
