@@ -147,6 +147,27 @@ int sd_weights_observe_gemms(sd_weights* w, int on);
 int sd_weights_observe_geglus(sd_weights* w, int on);
 int sd_weights_observe_qkv(sd_weights* w, int on);
 int sd_weights_observe_tails(sd_weights* w, int on);
+/* W8A8 einsums.  The reference's get_quantizable_modules (activation_quantization.py:205-215) collects every Einsum beside every
+ * Conv2d: the two products of an attention (unet.py:45-59, called at :108-118).  An Einsum has no tensor, so the store keeps a mark of
+ * its own under the MODULE's name, <prefix>.einsum (for example down_blocks.1.attentions.0.transformer_blocks.0.attn1.einsum), with
+ * three activation ranges: max |.| of the module's inputs q, k and v.  The scheme is the project's own - symmetric, per tensor; parity
+ * with coremltools' quantizer is unpinned, as for every W8A8 layer - and is ONE function, stated at sd_op_attention_w8a8.
+ * sd_weights_quantize_einsum: SD_ERR_NOT_FOUND when `name` does not end in ".einsum" or <prefix>.to_q.weight is not in the store,
+ * SD_ERR_INVALID_ARGUMENT for a range that is not positive and finite.  A UNet handle built from the store runs a marked attn1.einsum
+ * as two launches - the quantizer over the q | k rows and the V^T its q|k|v producer left, and the int8 attention kernel
+ * (attention_i8.hip) - wherever it runs the fp16 head-dim-64 kernel (attention8.hip) today: head dim 64, S a multiple of 64 up to
+ * 133 120.  Every other marked einsum - attn2.einsum (inside the fused cross-attention launches), head dims other than 64, shapes off
+ * the rule, the general attention kernels - stays fp16: marked, not applied (sd_unet_einsum_info).  The einsum holds no weights:
+ * sd_unet_reload_weights is unaffected.
+ * sd_weights_einsum_info: 1 when `name` is marked (ranges[0..2], may be NULL, = the q, k and v ranges), else 0.
+ * sd_weights_observe_einsums(on): a fifth flag of the kind above (0 / 1, effective only while the store observes) - handles created
+ * from it put ONE observer launch behind every q|k|v producer whose self-attention the int8 kernel could take; it writes max |q|, max |k|
+ * and max |V^T| of what the producer stored.  sd_unet_activation_ranges reports three slots <prefix>.einsum.q / .k / .v, the q value
+ * divided by the factor the producer pre-scaled the queries by, so that it is the range of the q the reference's Einsum sees.  The
+ * outputs do not change. */
+int sd_weights_quantize_einsum(sd_weights* w, const char* name, float q_absmax, float k_absmax, float v_absmax);
+int sd_weights_einsum_info(const sd_weights* w, const char* name, float* ranges);
+int sd_weights_observe_einsums(sd_weights* w, int on);
 
 /* ------------------------------------------------------------------------------------------
  * UNet / ControlNet.  Config mirrors UNet2DConditionModel.__init__ (unet.py:801-833) with the
@@ -230,6 +251,11 @@ int sd_unet_w8a8_info(const sd_unet* u, int* n_marked, int* n_applied, size_t* b
 /* Which convs those are: returns n_applied (>= 0) or an error code (< 0); index >= 0 fills `name` with the weight tensor of the
  * index-th of them in build order (SD_ERR_INVALID_ARGUMENT when there is no such conv), index < 0 asks for the count alone. */
 int sd_unet_w8a8_layer(const sd_unet* u, int index, char* name, int name_bytes);
+/* W8A8 einsums (sd_weights_quantize_einsum): *n_marked einsum marks the handle's weight store arrived with; *n_applied attentions run
+ * on the int8 kernel.  sd_unet_w8a8_info / sd_unet_w8a8_layer count convs only.  sd_unet_einsum_layer: like sd_unet_w8a8_layer, `name`
+ * = the module (<prefix>.einsum) of the index-th applied einsum in build order. */
+int sd_unet_einsum_info(const sd_unet* u, int* n_marked, int* n_applied);
+int sd_unet_einsum_layer(const sd_unet* u, int index, char* name, int name_bytes);
 /* The activation observers of a handle created from an observing store (sd_weights_observe_activations), in launch order.  Returns
  * their number (>= 0) or an error code (< 0).  index >= 0 (SD_ERR_INVALID_ARGUMENT when there is no such slot): `name` = the conv's
  * weight tensor (NUL-terminated, cut to name_bytes), *absmax = max |x| over the conv's source tensor(s) of every forward since the
@@ -620,6 +646,32 @@ int sd_op_qkv_w8a8(const int8_t* xq, const int8_t* wq, const float* w_scale, flo
  * the ten consecutive strips 10 n_tile .. 10 n_tile + 9.  C a multiple of 64.  *bytes = its size (3C * C); packed may be NULL to ask
  * for the size alone. */
 int sd_op_w8a8_pack_qkv(const int8_t* wq, int C, int8_t* packed, size_t* bytes);
+/* The self-attention einsums in W8A8 (attention_i8.hip; activation_quantization.py:205-215, unet.py:45-59; marks:
+ * sd_weights_quantize_einsum).  Head dim 64, S_q = S_k = S, S a multiple of 64.  THE FUNCTION, with r_q, r_k, r_v the three ranges and
+ * s_x = fp32(r_x / 127):
+ *   1. x_q = clip(rint(fp32(x) * fp32(127 / r_x)), -127, 127), NaN -> 0, +-inf -> +-127 (sd_op_einsum_quantize; a handle's queries are
+ *      stored multiplied by d^-0.5 * log2(e), so their factor is fp32(127 / (r_q * that)): r_q is always the range of the un-scaled q);
+ *   2. t[q][k] = fp32(int32 sum_c q_q k_q) * c,  c = fp32(s_q * s_k * d^-0.5 * log2 e) (the product formed in double, rounded once);
+ *   3. m[q] = max_k t (the true row max);  p_q = rint(127 * exp2(t - m)), 0 .. 127 (t - m, the exp2 and the product each fp32);
+ *   4. N[q][c] = int32 sum_k p_q v_q,  L[q] = sum_k p_q: exact (127^2 S < 2^31 up to S = 133 120);
+ *   5. out = fp16(fp32(N) * (s_v / fp32(L))), every operation rounded to fp32 on its own.
+ * The result does not depend on the launch geometry; the only inexact step is the hardware exp2.
+ * sd_op_attention_w8a8: q_q, k_q, v_q (B * S, heads * 64) int8 token-major in natural key order -> out (B * S, heads * 64) f16
+ * token-major; the entry builds the device images (q | k rows of one matrix, V^T in the kernel's key order) on the host.  Host checks,
+ * in this order, each SD_ERR_INVALID_ARGUMENT before any device work: (1) a NULL pointer or B, heads or S < 1, (2) S not a multiple
+ * of 64, (3) S > 133 120, (4) a range that is not positive and finite, (5) an input value of -128 (q, then k, then v).
+ * sd_op_einsum_quantize: the quantizer launch on a handle's layouts - qk (B * S, 2C) f16 = q | k rows, vt (B, C, ldv) f16 V^T in the key
+ * order vt_perm_in (0 natural, 1 the fp16 kernel's: the middle 4-key blocks of every 16 keys swapped) -> qk_q (B * S, 2C) int8 and vt_q
+ * (B, C, S) int8 in the int8 kernel's key order; q_range_eff = the range of the STORED queries (r_q, times the pre-scale where the
+ * producer applied one).  S a multiple of 32, C of 8, ldv of 4.
+ * sd_op_w8a8_pack_vt (host only; *bytes = B * C * S, vt_q may be NULL): v (B * S, C) int8 token-major -> vt_q (B, C, S), position p of
+ * every 32 keys holding key (p & 3) + 8 * ((p >> 2) & 3) + 4 * (p >> 4) of them - the order in which a lane's score registers become
+ * the byte operand of the P.V MFMA. */
+int sd_op_attention_w8a8(const int8_t* q_q, const int8_t* k_q, const int8_t* v_q, float q_absmax, float k_absmax, float v_absmax, void* out, int B,
+                         int heads, int S, int iters, float* ms);
+int sd_op_einsum_quantize(const void* qk, const void* vt, int B, int S, int C, int ldv, int vt_perm_in, float q_range_eff, float k_absmax,
+                          float v_absmax, int8_t* qk_q, int8_t* vt_q, int iters, float* ms);
+int sd_op_w8a8_pack_vt(const int8_t* v, int B, int C, int S, int8_t* vt_q, size_t* bytes);
 /* The host weight quantizer of sd_weights_quantize_w8a8 on its own: w (Cout, per_row) f32 -> q (Cout, per_row) int8, w_scale (Cout)
  * f32, *sq_err (may be NULL).  A non-finite weight is SD_ERR_INVALID_ARGUMENT. */
 int sd_op_quantize_weight(const float* w, int Cout, size_t per_row, int8_t* q, float* w_scale, double* sq_err);

@@ -181,6 +181,24 @@ int sd_weights_observe_tails(sd_weights* w, int on) {
     w->store.set_observe_tails(on != 0);
   });
 }
+int sd_weights_observe_einsums(sd_weights* w, int on) {
+  return guarded([&] {
+    SD_REQUIRE(w, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(on == 0 || on == 1, kInvalidArgument, "sd_weights_observe_einsums: %d (0 off, 1 on)", on);
+    w->store.set_observe_einsums(on != 0);
+  });
+}
+int sd_weights_quantize_einsum(sd_weights* w, const char* name, float q_absmax, float k_absmax, float v_absmax) {
+  return guarded([&] {
+    SD_REQUIRE(w && name, kInvalidArgument, "NULL argument");
+    w->store.quantize_einsum(name, q_absmax, k_absmax, v_absmax);
+  });
+}
+int sd_weights_einsum_info(const sd_weights* w, const char* name, float* ranges) {
+  const EinsumMark* m = (w && name) ? w->store.einsum(name) : nullptr;
+  if (m && ranges) ranges[0] = m->q_absmax, ranges[1] = m->k_absmax, ranges[2] = m->v_absmax;
+  return m ? 1 : 0;
+}
 int sd_weights_set_values(sd_weights* w, const char* name, const float* values, size_t n) {
   return guarded([&] {
     SD_REQUIRE(w && name && values, kInvalidArgument, "NULL argument");
@@ -255,6 +273,23 @@ int sd_unet_w8a8_layer(const sd_unet* u, int index, char* name, int name_bytes) 
     const std::vector<std::string>& names = u->impl->w8a8_applied();
     n = (int)names.size();
     SD_REQUIRE(index < n && (index < 0 || (name && name_bytes > 1)), kInvalidArgument, "W8A8 layer %d of %d", index, n);
+    if (index >= 0) std::snprintf(name, (size_t)name_bytes, "%s", names[(size_t)index].c_str());
+  });
+  return st != kOk ? st : n;
+}
+int sd_unet_einsum_info(const sd_unet* u, int* n_marked, int* n_applied) {
+  return guarded([&] {
+    SD_REQUIRE(u && n_marked && n_applied, kInvalidArgument, "NULL argument");
+    u->impl->einsum_info(n_marked, n_applied);
+  });
+}
+int sd_unet_einsum_layer(const sd_unet* u, int index, char* name, int name_bytes) {
+  int n = 0;
+  const int st = guarded([&] {
+    SD_REQUIRE(u, kInvalidArgument, "NULL handle");
+    const std::vector<std::string>& names = u->impl->einsum_applied();
+    n = (int)names.size();
+    SD_REQUIRE(index < n && (index < 0 || (name && name_bytes > 1)), kInvalidArgument, "einsum layer %d of %d", index, n);
     if (index >= 0) std::snprintf(name, (size_t)name_bytes, "%s", names[(size_t)index].c_str());
   });
   return st != kOk ? st : n;

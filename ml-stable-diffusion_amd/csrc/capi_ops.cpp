@@ -429,6 +429,90 @@ int sd_op_attention(int impl, const void* q, const void* k, const void* v, void*
   });
 }
 
+// The einsum quantizer on a handle's layouts (attention_i8.hip einsum_quantize_kernel): qk (B * S, 2C) f16 = q | k rows, vt (B, C, ldv) f16
+// in the key order vt_perm_in (0 natural, 1 attention8's) -> qk_q (B * S, 2C) int8, vt_q (B, C, S) int8 in the int8 kernel's key order.
+// q_range_eff is the range of the STORED queries (r_q times the producer's pre-scale, or r_q itself).
+int sd_op_einsum_quantize(const void* qk, const void* vt, int B, int S, int C, int ldv, int vt_perm_in, float q_range_eff, float k_absmax,
+                          float v_absmax, int8_t* qk_q, int8_t* vt_q, int iters, float* ms) {
+  return guarded([&] {
+    SD_REQUIRE(qk && vt && qk_q && vt_q, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(B > 0 && S > 0 && C > 0 && S % 32 == 0 && C % 8 == 0 && ldv >= S && ldv % 4 == 0 && (vt_perm_in == 0 || vt_perm_in == 1), kInvalidArgument,
+               "einsum_quantize: B %d S %d C %d ldv %d vt_perm_in %d (S a multiple of 32, C of 8, ldv of 4 and at least S, vt_perm_in 0 or 1)", B, S, C,
+               ldv, vt_perm_in);
+    SD_REQUIRE(w8a8_absmax_ok(q_range_eff) && w8a8_absmax_ok(k_absmax) && w8a8_absmax_ok(v_absmax), kInvalidArgument,
+               "einsum_quantize: ranges %g, %g, %g: each must be a positive finite number", (double)q_range_eff, (double)k_absmax, (double)v_absmax);
+    const float inv_q = 127.0f / q_range_eff, inv_k = 127.0f / k_absmax, inv_v = 127.0f / v_absmax;
+    SD_REQUIRE(std::isfinite(inv_q) && std::isfinite(inv_k) && std::isfinite(inv_v), kInvalidArgument, "einsum_quantize: a range has no finite inverse scale");
+    Scratch sc("einsum_quantize");
+    const size_t n_qk = (size_t)B * S * 2 * C, n_vt = (size_t)B * C * ldv, n_vq = (size_t)B * C * S;
+    const half_t* dqk = sc.dev<half_t>(n_qk, f16(qk), "qk");
+    const half_t* dvt = sc.dev<half_t>(n_vt, f16(vt), "vt");
+    int8_t* dq = sc.out<int8_t>(n_qk, "qk_q", kOpGuard, 0x80);   // -128: a value the quantizer never writes (0xff is -1)
+    int8_t* dv = sc.out<int8_t>(n_vq, "vt_q", kOpGuard, 0x80);
+    sc.timed(iters, ms, [&] { launch_einsum_quantize(dqk, dvt, B, S, C, ldv, vt_perm_in, inv_q, inv_k, inv_v, dq, dv, sc.stream); });
+    SD_HIP(hipMemcpy(qk_q, dq, n_qk, hipMemcpyDeviceToHost));
+    SD_HIP(hipMemcpy(vt_q, dv, n_vq, hipMemcpyDeviceToHost));
+  });
+}
+
+// v (B * S, C) int8 token-major, natural key order -> vt_q (B, C, S): V^T with every 32 keys in attention_i8_vt_key's order (host only)
+static void pack_vt_i8(const int8_t* v, int B, int C, int S, int8_t* vt_q) {
+  for (int b = 0; b < B; ++b)
+    for (int c = 0; c < C; ++c)
+      for (int p = 0; p < S; ++p)
+        vt_q[((size_t)b * C + c) * S + p] = v[((size_t)b * S + (p & ~31) + attention_i8_vt_key(p & 31)) * C + c];
+}
+
+int sd_op_w8a8_pack_vt(const int8_t* v, int B, int C, int S, int8_t* vt_q, size_t* bytes) {
+  return guarded([&] {
+    SD_REQUIRE(v && bytes, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(B > 0 && C > 0 && S > 0 && S % 32 == 0, kInvalidArgument, "w8a8_pack_vt: B %d C %d S %d (S a multiple of 32)", B, C, S);
+    *bytes = (size_t)B * C * S;
+    if (vt_q) pack_vt_i8(v, B, C, S, vt_q);
+  });
+}
+
+// The self-attention einsums in W8A8 (attention_i8.hip): q_q, k_q, v_q (B * S, heads * 64) int8 token-major in natural key order ->
+// out (B * S, heads * 64) f16.  Every check runs on the host in front of the first device call (Scratch), in the order the header lists.
+int sd_op_attention_w8a8(const int8_t* q_q, const int8_t* k_q, const int8_t* v_q, float q_absmax, float k_absmax, float v_absmax, void* out, int B,
+                         int heads, int S, int iters, float* ms) {
+  return guarded([&] {
+    SD_REQUIRE(q_q && k_q && v_q && out, kInvalidArgument, "NULL argument");
+    SD_REQUIRE(B > 0 && heads > 0 && S > 0, kInvalidArgument, "attention_w8a8: empty problem");
+    SD_REQUIRE(S >= 64 && S % 64 == 0, kInvalidArgument, "attention_w8a8: S = %d is off the shape rule (head dim 64, S a positive multiple of 64)", S);
+    SD_REQUIRE(attention_i8_shape_ok(64, S, S), kInvalidArgument, "attention_w8a8: S = %d, the exact integer sums hold up to %d", S, kAttnI8MaxS);
+    SD_REQUIRE(w8a8_absmax_ok(q_absmax) && w8a8_absmax_ok(k_absmax) && w8a8_absmax_ok(v_absmax), kInvalidArgument,
+               "attention_w8a8: ranges %g, %g, %g: each must be a positive finite number", (double)q_absmax, (double)k_absmax, (double)v_absmax);
+    const int C = heads * 64;
+    const size_t n = (size_t)B * S * C;
+    const int8_t* const ins[3] = {q_q, k_q, v_q};
+    for (int t = 0; t < 3; ++t)
+      for (size_t i = 0; i < n; ++i)
+        SD_REQUIRE(ins[t][i] != -128, kInvalidArgument, "attention_w8a8: %s value -128 at element %zu, the symmetric range is [-127, 127]",
+                   t == 0 ? "q" : t == 1 ? "k" : "v", i);
+    // the device images a handle's quantizer leaves: q | k rows of one (B * S, 2C) matrix, V^T in the kernel's key order
+    std::vector<int8_t> qk(2 * n), vt(n);
+    for (size_t r = 0; r < (size_t)B * S; ++r) {
+      std::copy(q_q + r * C, q_q + (r + 1) * C, qk.begin() + r * 2 * C);
+      std::copy(k_q + r * C, k_q + (r + 1) * C, qk.begin() + r * 2 * C + C);
+    }
+    pack_vt_i8(v_q, B, C, S, vt.data());
+    Scratch sc("attention_w8a8");
+    const int8_t* dqk = sc.dev<int8_t>(qk.size(), qk.data(), "q | k");
+    AttnI8Desc d;
+    d.q = dqk;
+    d.k = dqk + C;
+    d.vt = sc.dev<int8_t>(vt.size(), vt.data(), "vt");
+    half_t* o = sc.out<half_t>(n, "out");
+    d.out = o;
+    d.B = B; d.heads = heads; d.S = S;
+    d.ldq = d.ldk = 2 * C; d.ldv = S; d.ldo = C;
+    d.q_absmax = q_absmax; d.k_absmax = k_absmax; d.v_absmax = v_absmax;
+    sc.timed(iters, ms, [&] { launch_attention_i8(d, sc.stream); });
+    SD_HIP(hipMemcpy(out, o, n * 2, hipMemcpyDeviceToHost));
+  });
+}
+
 int sd_op_layernorm(const void* x, const float* weight, const float* bias, void* out, int B, int C, int S, float eps,
                     int iters, float* ms) {
   return guarded([&] {

@@ -304,6 +304,36 @@ void launch_attention8(const AttnDesc& d, hipStream_t s);
 // merged by the last workgroup to arrive), with the scratch that takes: bytes for AttnDesc::sk_part, counters for sk_cnt
 bool attention8_sk_scratch(const AttnDesc& d, size_t* part_bytes, int* n_counters);
 
+// attention_i8.hip: the same self-attention from int8 q, k and V^T on the int8 MFMAs (W8A8: the reference's Einsum modules,
+// activation_quantization.py:205-215, unet.py:45-59; the function is stated at the top of attention_i8.hip).  q and k are rows of int8
+// matrices (head h at byte column 64 h; ldq / ldk in bytes), vt [B][heads * 64][ldv] int8 with every 32 keys in the order
+// attention_i8_vt_key, out [B][S][ldo] fp16.  The ranges are those of the un-scaled q, k and v the reference's Einsum sees.
+constexpr int kAttnI8MaxS = 133120;   // 127^2 S < 2^31: the integer sums of P.V are exact up to here
+struct AttnI8Desc {
+  const int8_t* q = nullptr;
+  const int8_t* k = nullptr;
+  const int8_t* vt = nullptr;
+  half_t* out = nullptr;
+  int B = 1, heads = 1, S = 0;
+  int ldq = 0, ldk = 0, ldv = 0, ldo = 0;
+  float q_absmax = 0.f, k_absmax = 0.f, v_absmax = 0.f;
+};
+// the shape rule, in one place: head dim 64, S_q == S_k, whole 64-key tiles, inside the exact integer sums
+bool attention_i8_shape_ok(int d, int Sq, int Sk);
+// position p (0 .. 31) of every 32-key group of the int8 V^T holds this key of the group: the order in which a lane's score registers
+// become the packed-byte operand of the P.V MFMA (what vt_perm == 1 is to attention8.hip)
+__host__ __device__ inline int attention_i8_vt_key(int p) { return (p & 3) + 8 * ((p >> 2) & 3) + 4 * (p >> 4); }
+float attention_i8_score_scale(float q_absmax, float k_absmax, int d);   // c = fp32(s_q * s_k * d^-0.5 * log2 e), s_x = fp32(r_x / 127)
+void launch_attention_i8(const AttnI8Desc& d, hipStream_t s);
+// the quantizer in front of it, one launch: qk [B * S][2C] fp16 -> qk_q int8 by inv_q (columns below C) and inv_k, vt [B][C][ldv] fp16
+// in the key order vt_perm_in (0 natural, 1 AttnDesc::vt_perm) -> vt_q [B][C][S] int8 in attention_i8_vt_key's order by inv_v; the
+// quantizer is ws_quantize8 (quantize8.h).  S % 32 == 0, C % 8 == 0.
+void launch_einsum_quantize(const half_t* qk, const half_t* vt, int B, int S, int C, int ldv, int vt_perm_in, float inv_q, float inv_k,
+                            float inv_v, int8_t* qk_q, int8_t* vt_q, hipStream_t s);
+// the observer of a calibrating handle, one launch: max |q|, |k| (columns of qk) and |V^T| (the S live columns of each row) folded
+// into slots[0..2] like launch_absmax_half
+void launch_einsum_absmax(const half_t* qk, const half_t* vt, int B, int S, int C, int ldv, float* slots, hipStream_t s);
+
 // Cross-attention front half in one launch (xattn.hip): out = softmax(to_q(LayerNorm(x)) k^T / sqrt(d)) v per head,
 // head dim 64, <= 96 keys (unet.py:87-118 with the prompt's K / V hoisted).  x [M][C] is the UN-normalised input; wq /
 // bias / colsum are the LayerNorm-folded projection (UNet::fold_layernorm); k [B][L][C], vt [B][C][ldv], out [M][C].

@@ -14,7 +14,7 @@
 namespace sd {
 
 Net::Net(const sd_unet_config& cfg, const WeightStore& ws, int device)
-    : cfg_(cfg), ws_(&ws), f32_(cfg.compute_fp32 != 0), pal_tensors_((int)ws.palettes()), i8_marked_((int)ws.w8a8_marks()),
+    : cfg_(cfg), ws_(&ws), f32_(cfg.compute_fp32 != 0), pal_tensors_((int)ws.palettes()), i8_marked_((int)ws.w8a8_marks()), einsum_marked_((int)ws.einsum_marks()),
       observing_(ws.observe() != 0) {
   SD_REQUIRE(cfg.n_levels >= 1 && cfg.n_levels <= SD_MAX_LEVELS, kInvalidArgument, "n_levels=%d", cfg.n_levels);
   SD_REQUIRE(cfg.batch >= 1 && cfg.height >= 1 && cfg.width >= 1, kInvalidArgument, "bad batch/size");
@@ -225,6 +225,15 @@ void Net::observe_tensor(std::vector<Op>& ops, const std::string& name, const Te
   ops.back().label = "absmax " + name;
 }
 
+void Net::observe_einsum(std::vector<Op>& ops, const std::string& module, const half_t* qk, const half_t* vt, int B, int S, int C, int ldv, float q_div) {
+  float* slots = ll_.arena.alloc_n<float>(3);   // (the arena is zeroed: the running maxima start at 0)
+  observed_.push_back({module + ".q", slots, q_div});
+  observed_.push_back({module + ".k", slots + 1});
+  observed_.push_back({module + ".v", slots + 2});
+  ops.push_back([=](hipStream_t s) { launch_einsum_absmax(qk, vt, B, S, C, ldv, slots, s); });
+  ops.back().label = "absmax " + module;
+}
+
 // the un-folded descriptor of the fused q|k|v launch, as the planner is asked about it
 ConvDesc Net::qkv_shape(const std::string& name, const Tensor& x, const ConvArgs& a) const {
   ConvArgs plain = a;
@@ -327,6 +336,7 @@ int Net::activation_range(int index, std::string* name, float* absmax) {
   SD_HIP(hipSetDevice(ll_.device));
   SD_HIP(hipStreamSynchronize(ll_.stream));
   SD_HIP(hipMemcpy(absmax, observed_[(size_t)index].second, sizeof(float), hipMemcpyDeviceToHost));
+  if (observed_[(size_t)index].div != 1.f) *absmax /= observed_[(size_t)index].div;
   *name = observed_[(size_t)index].first;
   return (int)observed_.size();
 }

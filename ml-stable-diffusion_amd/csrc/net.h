@@ -131,8 +131,16 @@ class Net {
     *n_applied = i8_applied_;
     *bytes = i8_bytes_;
   }
+  // W8A8 einsums (WeightStore::quantize_einsum): marks the handle's weight store arrived with, and the attentions that run on the int8
+  // kernel (attention_i8.hip), by module name in build order.  The convs' counters above do not count them.
+  void einsum_info(int* n_marked, int* n_applied) const {
+    *n_marked = einsum_marked_;
+    *n_applied = (int)einsum_names_.size();
+  }
+  const std::vector<std::string>& einsum_applied() const { return einsum_names_; }
   // the activation observers of a handle built from an observing store, in launch order: fills slot `index` (name of the conv's weight
-  // tensor, running max |x| of its source(s) since creation) when it exists; returns the number of slots
+  // tensor, running max |x| of its source(s) since creation) when it exists; returns the number of slots.  An einsum's three slots are
+  // named <module>.q / .k / .v (no weight tensor), the q value divided by the factor its producer pre-scaled the queries by.
   int activation_range(int index, std::string* name, float* absmax);
   const std::vector<std::string>& w8a8_applied() const { return i8_names_; }   // weight tensors of the convs that run from int8, in build order
   const sd_unet_config& config() const { return cfg_; }
@@ -170,6 +178,12 @@ class Net {
   bool observes_tail(const std::string& name, const Tensor& x, const ConvArgs& a) const;
   // (report_as: the weight names, without ".weight", the one slot is reported under - <name> alone when empty)
   void observe_tensor(std::vector<Op>& ops, const std::string& name, const Tensor& t, const std::vector<std::string>& report_as = {});
+  // Calibration of the einsums (WeightStore::observe_einsums while the store observes): ONE launch over the q | k rows and the V^T
+  // a q|k|v producer left, into three slots <module>.q / .k / .v; the q slot is reported divided by q_div (the producer's pre-scale)
+  bool observes_einsums() const { return !f32_ && ws_->observe() && ws_->observe_einsums(); }
+  void observe_einsum(std::vector<Op>& ops, const std::string& module, const half_t* qk, const half_t* vt, int B, int S, int C, int ldv, float q_div);
+  // the handle runs the einsum `module` on the int8 attention kernel
+  void einsum_applies(const std::string& module) { einsum_names_.push_back(module); }
   // The fused q|k|v launch `name` over the projections `parts` (to_q, to_k, to_v) in W8A8: qkv_plan answers I8Qkv (plan tile 22) when
   // every part carries a mark, none a palette, all marks share one act_absmax (one int8 tensor carries one scale) and the planner takes
   // the un-folded shape (a: cout, ldT, n_trans, vt_perm, q_scale, q_cols of the launch) - else Fp16: the folded launch as ever.
@@ -222,7 +236,14 @@ class Net {
   size_t pal_stream_bytes_ = 0;
   int i8_marked_ = 0, i8_applied_ = 0;
   size_t i8_bytes_ = 0;
-  std::vector<std::pair<std::string, float*>> observed_;
+  struct Observed {
+    std::string first;
+    float* second;
+    float div = 1.f;   // the value is reported divided by this (1: as observed)
+  };
+  std::vector<Observed> observed_;
+  int einsum_marked_ = 0;
+  std::vector<std::string> einsum_names_;
   std::vector<std::string> i8_names_;
   struct Refill {
     std::vector<std::string> sources;

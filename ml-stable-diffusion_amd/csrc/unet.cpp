@@ -161,8 +161,52 @@ Tensor UNet::time_resnet(std::vector<Op>& ops, const std::string& p, const Tenso
 }
 
 Tensor UNet::attention(std::vector<Op>& ops, const Tensor& q, const half_t* k, const half_t* vt, int heads, int Sq,
-                       int Sk, int ldk, int ldv, int ldq, bool vt_perm, bool q_prescaled) {
+                       int Sk, int ldk, int ldv, int ldq, bool vt_perm, bool q_prescaled, const std::string* einsum) {
   Tensor o = new_tensor(q.B, q.H, q.W, q.C);
+  // The reference's Einsum of this attention in W8A8 (activation_quantization.py:205-215, unet.py:45-59): where attention8 would run the
+  // launch (vt_perm) over one q | k buffer on the int8 kernel's shape rule, a marked einsum becomes two launches - the quantizer over
+  // what the q|k|v producer left, and attention_i8.hip - and an observing store gets one observer launch.  Anything else: today's op.
+  const bool i8_could = einsum && vt_perm && attention_i8_shape_ok(q.C / heads, Sq, Sk) && ldq == 2 * q.C && ldk == ldq && k == q.p + q.C &&
+                        ldv % 16 == 0;
+  if (i8_could && observes_einsums())
+    observe_einsum(ops, *einsum, q.p, vt, q.B, Sq, q.C, ldv, q_prescaled ? attention_q_prescale(q.C / heads) : 1.f);
+  if (const EinsumMark* em = i8_could ? ws_->einsum(*einsum) : nullptr) {
+    const int B = q.B, C = q.C, S = Sq;
+    int8_t* qk_q = ll_.arena.alloc_n<int8_t>((size_t)B * S * 2 * C);
+    int8_t* vt_q = ll_.arena.alloc_n<int8_t>((size_t)B * C * S);
+    // r_q is the range of the un-scaled q: the stored queries carry the producer's factor, so the quantizer divides it out
+    const float q_range_eff = q_prescaled ? em->q_absmax * attention_q_prescale(C / heads) : em->q_absmax;
+    const float inv_q = 127.0f / q_range_eff, inv_k = 127.0f / em->k_absmax, inv_v = 127.0f / em->v_absmax;
+    SD_REQUIRE(std::isfinite(inv_q) && std::isfinite(inv_k) && std::isfinite(inv_v), kInvalidArgument, "%s: a range has no finite inverse scale",
+               einsum->c_str());
+    const half_t *qkp = q.p, *vtp = vt;
+    ops.push_back([=](hipStream_t s) { launch_einsum_quantize(qkp, vtp, B, S, C, ldv, 1, inv_q, inv_k, inv_v, qk_q, vt_q, s); });
+    ops.back().label = "einsum_q8 " + einsum->substr(0, einsum->size() - std::string(".einsum").size());
+    AttnI8Desc d;
+    d.q = qk_q;
+    d.k = qk_q + C;
+    d.vt = vt_q;
+    d.out = o.p;
+    d.B = B;
+    d.heads = heads;
+    d.S = S;
+    d.ldq = d.ldk = 2 * C;
+    d.ldv = S;
+    d.ldo = C;
+    d.q_absmax = em->q_absmax;
+    d.k_absmax = em->k_absmax;
+    d.v_absmax = em->v_absmax;
+    ops.push_back([this, d](hipStream_t s) {
+      // (the run-time implementation switch only keeps its refusal: all three run this one kernel, as they run attention8)
+      SD_REQUIRE(cfg_.attention_impl != kAttnSplitEinsumV2 || d.S < 512 || d.S % 512 == 0, kInvalidArgument,
+                 "SPLIT_EINSUM_V2 needs S_q %% 512 == 0 (got %d); the reference would silently drop the tail (attention.py:86)", d.S);
+      launch_attention_i8(d, s);
+    });
+    ops.back().label = "attention+i8 h=" + std::to_string(heads) + " d=64 Sq=" + std::to_string(Sq) + " Sk=" + std::to_string(Sk);
+    ops.back().flop = 4.0 * q.B * (double)q.C * Sq * Sk;
+    einsum_applies(*einsum);
+    return o;
+  }
   AttnDesc d;
   d.q = q.p;
   d.k = k;
@@ -282,7 +326,8 @@ Tensor UNet::transformer_block(std::vector<Op>& ops, const std::string& b, const
   }
   Tensor q = qk;
   q.C = C;   // logical width of q; rows are 2C apart
-  Tensor a1 = attention(ops, q, qk.p + C, vtp, heads, S, S, 2 * C, ldv, 2 * C, vt_perm, q_pre);
+  const std::string einsum1 = b + ".attn1.einsum";
+  Tensor a1 = attention(ops, q, qk.p + C, vtp, heads, S, S, 2 * C, ldv, 2 * C, vt_perm, q_pre, &einsum1);
   // attn1.to_out + residual -> norm2 -> to_q -> cross-attention -> attn2.to_out + residual as ONE launch at the 5-head level
   // (xattn_out.hip: 32 tokens x all heads per workgroup; h1 never goes to HBM): three launches of 11.6 + 15.3 + 11.6 us become one of
   // 23.7, step 4.493 -> 4.443 ms (profiles/r05_xattn_out_stage2_ab.log).  SD_XATTN_OUT (with SD_TUNE) for the A/B: 0 = the three

@@ -59,7 +59,10 @@ class UNet : public Net {
   Tensor transformer_block(std::vector<Op>& ops, const std::string& b, const Tensor& h, int heads, const std::string* proj_out = nullptr,
                            const Tensor* tres = nullptr, bool* tail_done = nullptr, const PreQkv* pre = nullptr, bool* tail_q8 = nullptr);
   Tensor attention(std::vector<Op>& ops, const Tensor& q, const half_t* k, const half_t* vt, int heads, int Sq,
-                   int Sk, int ldk, int ldv, int ldq, bool vt_perm = false, bool q_prescaled = false);
+                   int Sk, int ldk, int ldv, int ldq, bool vt_perm = false, bool q_prescaled = false, const std::string* einsum = nullptr);
+  // (einsum: the attention's Einsum module, <block>.attn1.einsum, where the launch is a self-attention over a fused q | k buffer: a
+  // W8A8 mark on it - WeightStore::quantize_einsum - makes the launch the quantizer + the int8 attention where attention8 would run and
+  // attention_i8_shape_ok holds; an observing store with observe_einsums puts launch_einsum_absmax in front of it)
   // scratch of attention8's balanced form (AttnDesc::sk_part / sk_cnt), shared by this handle's self-attention launches
   float* sk_part_ = nullptr;
   size_t sk_part_bytes_ = 0;

@@ -114,6 +114,24 @@ double WeightStore::quantize_w8a8(const std::string& name, float act_absmax) {
   return err;
 }
 
+// ---- Einsum marks (activation_quantization.py:205-215, unet.py:45-59) -------------------------
+const EinsumMark* WeightStore::einsum(const std::string& name) const {
+  auto it = einsum_.find(name);
+  return it == einsum_.end() ? nullptr : &it->second;
+}
+
+void WeightStore::quantize_einsum(const std::string& name, float q_absmax, float k_absmax, float v_absmax) {
+  static const std::string suffix = ".einsum";
+  const bool named = name.size() > suffix.size() && name.compare(name.size() - suffix.size(), suffix.size(), suffix) == 0;
+  const std::string probe = named ? name.substr(0, name.size() - suffix.size()) + ".to_q.weight" : std::string();
+  if (!named || !has(probe))
+    fail(kNotFound, "quantize_einsum: '%s' names no attention of the store (<prefix>.einsum beside <prefix>.to_q.weight)", name.c_str());
+  SD_REQUIRE(w8a8_absmax_ok(q_absmax) && w8a8_absmax_ok(k_absmax) && w8a8_absmax_ok(v_absmax), kInvalidArgument,
+             "quantize_einsum(%s): ranges %g, %g, %g: each must be a positive finite number", name.c_str(), (double)q_absmax, (double)k_absmax,
+             (double)v_absmax);
+  einsum_[name] = EinsumMark{q_absmax, k_absmax, v_absmax};
+}
+
 // ---- palettes --------------------------------------------------------------------------------
 static inline uint16_t float_to_half_bits(float f) {
   const _Float16 v = (_Float16)f;

@@ -35,8 +35,25 @@ struct W8A8Mark {
   float act_absmax = 0.f;       // s_a = act_absmax / 127
 };
 
+// A W8A8 mark on an attention's Einsum (activation_quantization.py:205-215 collects every Einsum beside every Conv2d; unet.py:45-59 is
+// the module): the module has no tensor, so the mark stands on its own under the module's name, <prefix>.einsum beside
+// <prefix>.to_q.weight.  The three ranges are max |.| of the module's inputs q, k and v; a handle runs a marked attn1.einsum on the
+// int8 attention kernel (attention_i8.hip) where its shape rule holds, everything else in fp16 as ever.
+struct EinsumMark {
+  float q_absmax = 0.f, k_absmax = 0.f, v_absmax = 0.f;
+};
+
 class WeightStore {
  public:
+  // marks the Einsum module `name` = <prefix>.einsum (kNotFound when <prefix>.to_q.weight is absent or the name has no ".einsum" suffix;
+  // kInvalidArgument: a range that is not a positive finite number)
+  void quantize_einsum(const std::string& name, float q_absmax, float k_absmax, float v_absmax);
+  const EinsumMark* einsum(const std::string& name) const;   // nullptr: no mark
+  size_t einsum_marks() const { return einsum_.size(); }
+  const std::map<std::string, EinsumMark>& einsums() const { return einsum_; }   // name order
+  // ... and, while observing, ONE launch behind every q|k|v producer whose self-attention the int8 kernel could take: max |q|, |k|, |v|
+  void set_observe_einsums(bool on) { observe_einsums_ = on; }
+  bool observe_einsums() const { return observe_einsums_; }
   // marks the 4-D tensor `name` (kNotFound when absent; kInvalidArgument: not (Cout, Cin, k, k), a palette on it, act_absmax not a
   // positive finite number, a non-finite weight); returns the squared weight error
   double quantize_w8a8(const std::string& name, float act_absmax);
@@ -83,11 +100,13 @@ class WeightStore {
   std::map<std::string, HostTensor> map_;
   std::map<std::string, Palette> pal_;
   std::map<std::string, W8A8Mark> i8_;
+  std::map<std::string, EinsumMark> einsum_;
   int observe_ = 0;
   bool observe_gemms_ = false;
   bool observe_geglus_ = false;
   bool observe_qkv_ = false;
   bool observe_tails_ = false;
+  bool observe_einsums_ = false;
   bool palette_halo_ = false;
 };
 

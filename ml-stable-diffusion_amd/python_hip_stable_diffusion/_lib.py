@@ -106,6 +106,11 @@ SYMBOLS = [
     ("sd_weights_observe_geglus", _I, [_P, _I]),
     ("sd_weights_observe_qkv", _I, [_P, _I]),
     ("sd_weights_observe_tails", _I, [_P, _I]),
+    ("sd_weights_observe_einsums", _I, [_P, _I]),
+    ("sd_weights_quantize_einsum", _I, [_P, C.c_char_p, _F, _F, _F]),
+    ("sd_weights_einsum_info", _I, [_P, C.c_char_p, _FP]),
+    ("sd_unet_einsum_info", _I, [_P, C.POINTER(_I), C.POINTER(_I)]),
+    ("sd_unet_einsum_layer", _I, [_P, _I, C.c_char_p, _I]),
     ("sd_unet_w8a8_info", _I, [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(C.c_size_t)]),
     ("sd_unet_w8a8_layer", _I, [_P, _I, C.c_char_p, _I]),
     ("sd_unet_activation_ranges", _I, [_P, _I, C.c_char_p, _I, _FP]),
@@ -125,6 +130,9 @@ SYMBOLS = [
     ("sd_op_gemm_q8", _I, [_P, _P, _FP, _F, _FP, _P, _P, _I, _I, _I, _I, C.POINTER(_I), _I, _FP]),
     ("sd_op_qkv_w8a8", _I, [_P, _P, _FP, _F, _FP, _P, _P, _I, _I, _I, _F, _I, _I, C.POINTER(_I), _I, _FP]),
     ("sd_op_w8a8_pack_qkv", _I, [_P, _I, _P, C.POINTER(C.c_size_t)]),
+    ("sd_op_attention_w8a8", _I, [_P, _P, _P, _F, _F, _F, _P, _I, _I, _I, _I, _FP]),
+    ("sd_op_einsum_quantize", _I, [_P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _P, _P, _I, _FP]),
+    ("sd_op_w8a8_pack_vt", _I, [_P, _I, _I, _I, _P, C.POINTER(C.c_size_t)]),
     ("sd_op_quantize_weight", _I, [_FP, _I, C.c_size_t, _P, _FP, C.POINTER(C.c_double)]),
     ("sd_op_absmax", _I, [_P, C.c_size_t, _FP]),
     ("sd_unet_create", _I, [C.POINTER(UNetConfig), _P, _I, C.POINTER(_P)]),
@@ -888,6 +896,61 @@ def w8a8_pack_qkv(wq):
         raise ValueError("w8a8_pack_qkv: wq must be (3C, C)")
     Cc = wq.shape[1]
     return _packed(lib().sd_op_w8a8_pack_qkv, ptr(wq), Cc).view(np.int8).reshape(3 * Cc // 16, 16, Cc)
+
+
+def attention_w8a8(q_q, k_q, v_q, q_absmax, k_absmax, v_absmax, batch, heads, S=None, out=None, iters=1):
+    """The self-attention einsums in W8A8 (sd_op_attention_w8a8; the function is stated in sd_mi355x.h): q_q, k_q, v_q (batch * S,
+    heads * 64) int8 token-major in natural key order, the three ranges of the un-scaled q, k and v.  ``S``: the sequence length
+    (default: rows / batch).  ``out``: a C-contiguous float16 buffer of at least batch * S * heads * 64 elements (tests put guards
+    behind it).  What the library checks - shape, S, the ranges, a value of -128 - it refuses itself (ValueError, no GPU needed).
+    Returns (out (batch * S, heads * 64) float16, ms)."""
+    q_q, k_q, v_q = (np.ascontiguousarray(a, dtype=np.int8) for a in (q_q, k_q, v_q))
+    if q_q.ndim != 2 or k_q.shape != q_q.shape or v_q.shape != q_q.shape or batch < 1 or heads < 1:
+        raise ValueError("attention_w8a8: q_q, k_q and v_q must be (batch * S, heads * 64) int8")
+    if S is None:
+        if q_q.shape[0] % batch:
+            raise ValueError("attention_w8a8: q_q, k_q and v_q must be (batch * S, heads * 64) int8")
+        S = q_q.shape[0] // batch
+    n = batch * S * heads * 64
+    # an S the library refuses before it reads a value (off the rule, past the integer bound) may come with arrays of any size
+    refused_unread = S < 64 or S % 64 != 0 or S > 133120
+    if n != q_q.size and not refused_unread:
+        raise ValueError("attention_w8a8: q_q, k_q and v_q must be (batch * S, heads * 64) int8")
+    if out is None:
+        out = np.empty(0 if refused_unread else n, np.float16)
+    if out.dtype != np.float16 or not out.flags.c_contiguous or (out.size < n and not refused_unread):
+        raise ValueError("attention_w8a8: out must be a C-contiguous float16 buffer of at least batch * S * heads * 64 elements")
+    ms = C.c_float(0)
+    check(lib().sd_op_attention_w8a8(ptr(q_q), ptr(k_q), ptr(v_q), float(q_absmax), float(k_absmax), float(v_absmax), ptr(out), batch, heads, S,
+                                     iters, C.byref(ms)))
+    return out.reshape(-1)[:n].reshape(batch * S, heads * 64), ms.value
+
+
+def einsum_quantize(qk, vt, q_range_eff, k_absmax, v_absmax, vt_perm_in=0, iters=1):
+    """The quantizer launch in front of the int8 attention (sd_op_einsum_quantize): qk (batch * S, 2C) float16 = q | k rows, vt (batch, C,
+    ldv) float16 V^T in the key order ``vt_perm_in`` (0 natural, 1 the fp16 d = 64 kernel's); q_range_eff the range of the stored queries.
+    Returns (qk_q (batch * S, 2C) int8, vt_q (batch, C, S) int8 in the int8 kernel's key order, ms)."""
+    qk, vt = f16(qk), f16(vt)
+    if qk.ndim != 2 or vt.ndim != 3 or qk.shape[1] != 2 * vt.shape[1] or qk.shape[0] % vt.shape[0]:
+        raise ValueError("einsum_quantize: qk must be (batch * S, 2C), vt (batch, C, ldv)")
+    B, Cc, ldv = vt.shape
+    S = qk.shape[0] // B
+    qk_q = np.empty((B * S, 2 * Cc), np.int8)
+    vt_q = np.empty((B, Cc, S), np.int8)
+    ms = C.c_float(0)
+    check(lib().sd_op_einsum_quantize(ptr(qk), ptr(vt), B, S, Cc, ldv, int(vt_perm_in), float(q_range_eff), float(k_absmax), float(v_absmax),
+                                      ptr(qk_q), ptr(vt_q), iters, C.byref(ms)))
+    return qk_q, vt_q, ms.value
+
+
+def w8a8_pack_vt(v, batch):
+    """The int8 V^T of the W8A8 attention (sd_op_w8a8_pack_vt; host only): v (batch * S, C) int8 token-major -> (batch, C, S) int8,
+    position p of every 32 keys holding key (p & 3) + 8 * ((p >> 2) & 3) + 4 * (p >> 4) of them."""
+    v = np.ascontiguousarray(v, dtype=np.int8)
+    if v.ndim != 2 or batch < 1 or v.shape[0] % batch:
+        raise ValueError("w8a8_pack_vt: v must be (batch * S, C)")
+    S, Cc = v.shape[0] // batch, v.shape[1]
+    return _packed(lib().sd_op_w8a8_pack_vt, ptr(v), batch, Cc, S).view(np.int8).reshape(batch, Cc, S)
 
 
 def w8a8_pack(wq):

@@ -21,6 +21,14 @@ int8 itself (no fp16 product exists; behind an fp16 GEGLU one quantizer launch w
 tile 19; with ``ff.net.2`` unmarked the merged fp16 launch stays and a marked ``proj_out`` is skipped.  Parity with coremltools' quantizer is NOT pinned
 (coremltools is not a dependency of this project): the scales are plain absmax / 127, not the result of its calibration.
 
+The reference's second module class, the ``Einsum`` of every attention (``get_quantizable_modules``, :205-215; the ``'einsum'`` section
+of the layer-wise results, :368-372): a recipe names the module, ``<block>.attn1.einsum``, with THREE ranges ``[r_q, r_k, r_v]`` - max |.|
+of the module's inputs - and a handle runs a marked self-attention as a quantizer launch and the int8 attention kernel
+(``attention_i8.hip``: int8 Q.K^T and P.V MFMAs, the probabilities quantized relative to the true row max; ``sd_weights_quantize_einsum``)
+wherever it runs the fp16 head-dim-64 kernel today.  ``attn2.einsum`` (inside the fused cross-attention launches), head dims other
+than 64 and shapes off the rule stay fp16, logged once per layer.  The scheme is the project's own; parity with coremltools' quantizer
+is unpinned here too.
+
 Calibration happens on the device: ``HipModel(..., observe_activations=True)`` puts an absmax observer in front of every conv
 the int8 weight stream could take, ``observe_activations="all"`` in front of every conv either int8 conv kernel could take, ``observe_activations="gemm"`` also in front of
 the projections plan tile 19 could take, ``observe_activations="geglu"`` also over the output of ``norm3`` in front of every GEGLU
@@ -28,12 +36,16 @@ projection plan tile 20 could take (a LayerNorm and an absmax launch beside the 
 ``observe_activations="attn"`` also over the output of ``norm1`` in front of every fused q|k|v launch plan tile 22 could take (the same
 two launches; the one range is reported under ``attn1.to_q``, ``to_k`` and ``to_v``), ``observe_activations="tail"`` also over the GEGLU
 product in front of every ``ff.net.2`` plan tile 24 could take and over a scratch ``ff.net.2`` output in front of its ``proj_out`` -
+``observe_activations="einsum"`` also one launch behind every q|k|v producer whose self-attention the int8 attention kernel could take
+(three slots ``<module>.q`` / ``.k`` / ``.v``) -
 every layer that could run from int8; after any number of forwards ``.activation_ranges()`` is the recipe's raw material.
 
-A recipe is JSON ``{layer: act_absmax}``, ``layer`` the conv's module name (its weight tensor without ``.weight``).
+A recipe is JSON ``{layer: act_absmax}``, ``layer`` the conv's module name (its weight tensor without ``.weight``); a key ending in
+``.einsum`` names an attention's Einsum module and carries a list ``[r_q, r_k, r_v]``.
 
-Scope: the UNet.  The refiner, the ControlNets and the layer-wise PSNR sensitivity search (:384-413) are out of scope: recipes
-come from ranges, every observed layer unless ``skip`` names it.
+Scope: the UNet - its convs and its self-attention einsums.  ``attn2.einsum``, the refiner, the ControlNets and the layer-wise PSNR
+sensitivity search (:363-395, which can now fill both sections of its result file) are out of scope: recipes come from ranges, every
+observed layer unless ``skip`` names it.
 """
 import json
 import logging
@@ -53,14 +65,32 @@ ATTENTION_SCOPES = {"attn": "attn"}
 TAIL_SCOPES = {"tail": "tail"}
 
 
+# ... and "einsum" observes what "tail" does plus the inputs q, k, v of every self-attention the int8 attention kernel could take
+EINSUM_SCOPES = {"einsum": "einsum"}
+
+_EINSUM = ".einsum"
+_EINSUM_SLOTS = (".q", ".k", ".v")
+
+
+def is_einsum(layer):
+    """a recipe key that names an attention's Einsum module (three ranges), not a conv (one)"""
+    return layer.endswith(_EINSUM)
+
+
 def calibration_scopes():
     """the ``--calibrate-scope`` -> ``observe_activations`` up to "attn", in the order each adds to the one before"""
     return {**CALIBRATION_SCOPES, **ATTENTION_SCOPES}
 
 
 def all_calibration_scopes():
-    """every ``--calibrate-scope`` -> ``observe_activations``, in the order each adds to the one before: what the CLI offers"""
+    """the ``--calibrate-scope`` -> ``observe_activations`` up to "tail", in the order each adds to the one before"""
     return {**calibration_scopes(), **TAIL_SCOPES}
+
+
+def every_calibration_scope():
+    """``all_calibration_scopes()`` and the scope added since, "einsum": what the CLI offers.  (The two functions above keep the values
+    their callers pinned, as ``calibration_scopes()`` kept its own when "tail" arrived.)"""
+    return {**all_calibration_scopes(), **EINSUM_SCOPES}
 
 
 def layer_of(tensor_name):
@@ -73,15 +103,39 @@ def recipe_from_ranges(ranges, skip=()):
     search would drop).  A layer whose observed range is 0 (never run, or all-zero input) has no scale and raises ``ValueError``."""
     skip = {layer_of(s) for s in skip}
     recipe = {}
+    slots = {}   # einsum module -> {".q": r_q, ".k": r_k, ".v": r_v}
     for layer, absmax in ranges.items():
         layer = layer_of(layer)
+        if layer[-2:] in _EINSUM_SLOTS and is_einsum(layer[:-2]):   # the three slots of one observed Einsum fold into one entry
+            slots.setdefault(layer[:-2], {})[layer[-2:]] = absmax
+            continue
         if layer in skip:
             continue
         recipe[layer] = _checked(layer, absmax)
+    for module, got in slots.items():
+        if module in skip:
+            continue
+        if set(got) != set(_EINSUM_SLOTS):
+            raise ValueError(f"activation ranges of {module!r}: slots {sorted(got)} observed, an Einsum needs .q, .k and .v")
+        recipe[module] = _checked(module, [got[s] for s in _EINSUM_SLOTS])
     return recipe
 
 
 def _checked(layer, absmax):
+    layer = layer_of(str(layer))
+    if is_einsum(layer):
+        if isinstance(absmax, (str, bytes)) or not hasattr(absmax, "__len__"):
+            raise ValueError(f"{layer!r} names an Einsum: its recipe value is a list [r_q, r_k, r_v], got {absmax!r}")
+        if len(absmax) != 3:
+            raise ValueError(f"{layer!r} names an Einsum: its recipe value is a list [r_q, r_k, r_v], got {len(absmax)} values")
+        return [_checked_range(layer, r) for r in absmax]
+    if hasattr(absmax, "__len__") and not isinstance(absmax, (str, bytes)):
+        raise ValueError(f"{layer!r} names a conv: its recipe value is one act_absmax, got the list {list(absmax)!r} (only a key "
+                         "ending in '.einsum' carries three ranges)")
+    return _checked_range(layer, absmax)
+
+
+def _checked_range(layer, absmax):
     absmax = float(absmax)
     if not (math.isfinite(absmax) and absmax > 0.0):
         raise ValueError(f"activation range of {layer!r} is {absmax!r}: a W8A8 layer needs a positive finite act_absmax")
@@ -106,14 +160,23 @@ def load_recipe(path_or_dict):
 
 
 def apply(weights, recipe):
-    """Mark the layers of ``recipe`` in a ``Weights`` store; returns {layer: squared weight error}.  ``KeyError``: a layer the
-    checkpoint does not have (nothing is marked then); ``ValueError``: a layer whose tensor carries a palette, or is no conv weight."""
+    """Mark the layers of ``recipe`` in a ``Weights`` store; returns {layer: squared weight error} of its convs (an Einsum has no
+    weights: it is marked and returns nothing).  ``KeyError``: a layer the checkpoint does not have (nothing is marked then);
+    ``ValueError``: a layer whose tensor carries a palette, or is no conv weight."""
     recipe = load_recipe(recipe)
     names = weights.shapes()
     for layer in recipe:
+        if is_einsum(layer):
+            if layer[:-len(_EINSUM)] + ".to_q" + _SUFFIX not in names:
+                raise KeyError(f"activation-quantization recipe: einsum {layer!r} is not in the checkpoint (no tensor "
+                               f"{layer[:-len(_EINSUM)] + '.to_q' + _SUFFIX!r})")
+            continue
         if layer + _SUFFIX not in names:
             raise KeyError(f"activation-quantization recipe: layer {layer!r} is not in the checkpoint (no tensor {layer + _SUFFIX!r})")
         if weights.palette_bits(layer + _SUFFIX):
             raise ValueError(f"{layer!r} is palettized (quantize_nbits / palettization recipe) AND named by the activation-quantization "
                              "recipe: a tensor is one or the other")
-    return {layer: weights.quantize_w8a8(layer + _SUFFIX, absmax) for layer, absmax in recipe.items()}
+    for layer, ranges in recipe.items():
+        if is_einsum(layer):
+            weights.quantize_einsum(layer, *ranges)
+    return {layer: weights.quantize_w8a8(layer + _SUFFIX, absmax) for layer, absmax in recipe.items() if not is_einsum(layer)}

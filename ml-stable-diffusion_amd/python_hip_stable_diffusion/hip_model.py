@@ -205,6 +205,19 @@ class Weights(_lib.Handle):
         s = C.c_float(0)
         return float(s.value) if _lib.lib().sd_weights_w8a8_info(self._h, name.encode(), C.byref(s)) else None
 
+    def quantize_einsum(self, name, q_absmax, k_absmax, v_absmax):
+        """Mark the attention Einsum module ``name`` (``<prefix>.einsum``, beside ``<prefix>.to_q.weight``) for W8A8 with the ranges of
+        its inputs q, k and v (``sd_weights_quantize_einsum``).  KeyError: no such attention; ValueError: a range not positive and finite."""
+        status = _lib.lib().sd_weights_quantize_einsum(self._h, name.encode(), float(q_absmax), float(k_absmax), float(v_absmax))
+        if status == -2:
+            raise KeyError(name)
+        _lib.check(status)
+
+    def einsum_info(self, name):
+        """The (q, k, v) ranges of a marked Einsum module, None when it has no mark."""
+        r = (C.c_float * 3)()
+        return tuple(float(x) for x in r) if _lib.lib().sd_weights_einsum_info(self._h, name.encode(), r) else None
+
     def palette_halo(self, on=True):
         """Handles created from the store while this is on also run their palettized 3x3 / stride-1 halo convs - resnet ``conv1`` /
         ``conv2``, the two-source convs of the up blocks, upsamplers - from the palette (``sd_weights_palette_halo``, plan tile 25):
@@ -221,12 +234,15 @@ class Weights(_lib.Handle):
         the LayerNorm output in front of every GEGLU projection the int8 GEGLU kernel could take (plan tile 20), ``"attn"`` also over
         the output of ``norm1`` in front of every fused q|k|v launch the int8 q|k|v kernel could take (plan tile 22; one range,
         reported under ``attn1.to_q``, ``to_k`` and ``to_v``), ``"tail"`` also over the GEGLU product in front of every ``ff.net.2``
-        the int8-activation GEMM could take (plan tile 24) and over a scratch ``ff.net.2`` output in front of its ``proj_out``."""
+        the int8-activation GEMM could take (plan tile 24) and over a scratch ``ff.net.2`` output in front of its ``proj_out``,
+        ``"einsum"`` also ONE launch behind every q|k|v producer whose self-attention the int8 attention kernel could take: max |q|,
+        |k| and |v|, reported as ``<block>.attn1.einsum.q`` / ``.k`` / ``.v``."""
         _lib.check(_lib.lib().sd_weights_observe_activations(self._h, observe_level(on)))
-        _lib.check(_lib.lib().sd_weights_observe_gemms(self._h, int(on in ("gemm", "geglu", "attn", "tail"))))
-        _lib.check(_lib.lib().sd_weights_observe_geglus(self._h, int(on in ("geglu", "attn", "tail"))))
-        _lib.check(_lib.lib().sd_weights_observe_qkv(self._h, int(on in ("attn", "tail"))))
-        _lib.check(_lib.lib().sd_weights_observe_tails(self._h, int(on == "tail")))
+        _lib.check(_lib.lib().sd_weights_observe_gemms(self._h, int(on in ("gemm", "geglu", "attn", "tail", "einsum"))))
+        _lib.check(_lib.lib().sd_weights_observe_geglus(self._h, int(on in ("geglu", "attn", "tail", "einsum"))))
+        _lib.check(_lib.lib().sd_weights_observe_qkv(self._h, int(on in ("attn", "tail", "einsum"))))
+        _lib.check(_lib.lib().sd_weights_observe_tails(self._h, int(on in ("tail", "einsum"))))
+        _lib.check(_lib.lib().sd_weights_observe_einsums(self._h, int(on == "einsum")))
 
     @classmethod
     @contextlib.contextmanager
@@ -247,10 +263,11 @@ def observe_level(on):
     """observe_activations as the level of sd_weights_observe_activations: False 0, True 1, "all" 2; "gemm" is level 2 with the
     projections' flag (sd_weights_observe_gemms) beside it, "geglu" level 2 with that flag and the GEGLUs' (sd_weights_observe_geglus),
     "attn" level 2 with those two and the self-attention q|k|v launches' (sd_weights_observe_qkv), "tail" level 2 with those three and
-    the transformer tails' (sd_weights_observe_tails)."""
+    the transformer tails' (sd_weights_observe_tails), "einsum" level 2 with those four and the self-attention einsums'
+    (sd_weights_observe_einsums)."""
     if isinstance(on, str):
-        if on not in ("all", "gemm", "geglu", "attn", "tail"):
-            raise ValueError(f"observe_activations must be False, True, 'all', 'gemm', 'geglu', 'attn' or 'tail', got {on!r}")
+        if on not in ("all", "gemm", "geglu", "attn", "tail", "einsum"):
+            raise ValueError(f"observe_activations must be False, True, 'all', 'gemm', 'geglu', 'attn', 'tail' or 'einsum', got {on!r}")
         return 2
     return int(bool(on))
 
@@ -338,9 +355,18 @@ class HipModel(_lib.Model):
                 if palette_halo and not halo_was:
                     store.palette_halo(False)
         if self.activation_quantization is not None:
+            from . import activation_quantization as aq
+            einsums = {layer for layer in self.activation_quantization if aq.is_einsum(layer)}
             applied = set(self.w8a8_layers())
-            stayed = sorted(set(self.activation_quantization) - applied)
-            logger.info("W8A8: %d of %d recipe layers run from int8 (plan tiles 17 / 18 / 19 / 20 / 22)", len(applied), len(self.activation_quantization))
+            stayed = sorted(set(self.activation_quantization) - einsums - applied)
+            logger.info("W8A8: %d of %d recipe layers run from int8 (plan tiles 17 / 18 / 19 / 20 / 22)", len(applied),
+                        len(self.activation_quantization) - len(einsums))
+            if einsums:
+                on_i8 = set(self.einsum_layers())
+                logger.info("W8A8: %d of %d recipe einsums run on the int8 attention kernel", len(on_i8), len(einsums))
+                for layer in sorted(einsums - on_i8):
+                    logger.info("W8A8: %s stays fp16 (an attn2.einsum, a head dim other than 64, a shape off the int8 kernel's rule or an "
+                                "attention of the general kernels)", layer)
             if stayed:
                 logger.info("W8A8: these layers stay fp16 (their plan is none of the weight stream, the halo conv, the plain small-M projection, the "
                             "GEGLU kernel and the fused self-attention q|k|v launch with its three tensors under one range): %s", ", ".join(stayed))
@@ -599,9 +625,29 @@ class HipModel(_lib.Model):
             out.append(name.value.decode()[:-len(".weight")])
         return out
 
+    def einsum_info(self):
+        """(Einsum marks the weight store arrived with, attentions that run on the int8 attention kernel); ``w8a8_info`` counts convs."""
+        n_marked, n_applied = C.c_int(0), C.c_int(0)
+        _lib.check(_lib.lib().sd_unet_einsum_info(self._h, C.byref(n_marked), C.byref(n_applied)))
+        return n_marked.value, n_applied.value
+
+    def einsum_layers(self):
+        """Module names (``<block>.attn1.einsum``) of the attentions that run on the int8 attention kernel, in build order."""
+        n = _lib.lib().sd_unet_einsum_layer(self._h, -1, None, 0)
+        if n < 0:
+            _lib.check(n)
+        name = C.create_string_buffer(512)
+        out = []
+        for i in range(n):
+            if _lib.lib().sd_unet_einsum_layer(self._h, i, name, len(name)) < 0:
+                _lib.check(-1)
+            out.append(name.value.decode())
+        return out
+
     def activation_ranges(self):
         """{layer: max |x| over the conv's input(s) of every forward so far} of a handle built with ``observe_activations=True``
-        (empty otherwise): the calibration of ``activation_quantization.recipe_from_ranges``."""
+        (empty otherwise; an observed Einsum has three slots ``<module>.q`` / ``.k`` / ``.v``): the calibration of
+        ``activation_quantization.recipe_from_ranges``."""
         n = _lib.lib().sd_unet_activation_ranges(self._h, -1, None, 0, None)
         if n < 0:
             _lib.check(n)
@@ -612,7 +658,8 @@ class HipModel(_lib.Model):
             st = _lib.lib().sd_unet_activation_ranges(self._h, i, name, len(name), C.byref(v))
             if st < 0:
                 _lib.check(st)
-            out[name.value.decode()[:-len(".weight")]] = float(v.value)
+            slot = name.value.decode()   # a conv's weight tensor, or an einsum's <module>.q / .k / .v
+            out[slot[:-len(".weight")] if slot.endswith(".weight") else slot] = float(v.value)
         return out
 
     def close(self):

@@ -648,7 +648,7 @@ def get_hip_pipe(model_dir, model_version, compute_unit="ALL", scheduler_overrid
     ``activation_quantization``: a W8A8 recipe, a path or a dict {layer: act_absmax} (``activation_quantization.load_recipe``), applied
     to the UNet alone (activation_quantization.py:141-203 ``--quantize-pytorch``; the refiner and the ControlNets stay as they are;
     parity with coremltools' quantizer unpinned).  ``observe_activations``: the UNet carries the calibration observers
-    (``True``, ``"all"``, ``"gemm"``, ``"geglu"`` or ``"attn"``: ``Weights.observe_activations``; ``pipe.unet.activation_ranges()`` after a generation;
+    (``True``, ``"all"``, ``"gemm"``, ``"geglu"``, ``"attn"``, ``"tail"`` or ``"einsum"``: ``Weights.observe_activations``; ``pipe.unet.activation_ranges()`` after a generation;
     ``--calibrate-activations`` / ``--calibrate-scope``).
     ``unet_weights``: a ``Weights`` store the UNet is built from instead of ``unet/``'s checkpoint file; it stays the caller's, who can
     change it and ``reload_weights`` it into ``pipe.unet`` (``mixed_bit_compression_pre_analysis``)."""
@@ -824,14 +824,16 @@ def build_parser():
     parser.add_argument("--calibrate-activations", default=None,                                 # activation_quantization.py --generate-calibration-data
                         help="Run the requested generation on a UNet that records the range of every quantizable conv's input and write "
                              "the W8A8 recipe to this file")
-    from .activation_quantization import all_calibration_scopes   # CALIBRATION_SCOPES and the scopes added since
-    parser.add_argument("--calibrate-scope", default="stream", choices=tuple(all_calibration_scopes()),
+    from .activation_quantization import every_calibration_scope   # CALIBRATION_SCOPES and the scopes added since
+    parser.add_argument("--calibrate-scope", default="stream", choices=tuple(every_calibration_scope()),
                         help="Which convs --calibrate-activations observes: 'stream' = those the int8 weight stream takes (the 8x8 level), "
                              "'all' = also every 3x3 / stride-1 conv the int8 halo conv takes, 'gemm' = also the plain 1x1 projections the "
                              "int8 small-M GEMM takes, 'geglu' = also the GEGLU projections ff.net.0.proj the int8 GEGLU kernel takes (the "
                              "output of their norm3), 'attn' = also the self-attention projections attn1.to_q / to_k / to_v the int8 q|k|v "
                              "kernel takes (the output of their norm1: one range under the three names), 'tail' = also ff.net.2 and proj_out of "
-                             "the transformer tails the int8-activation GEMM takes (the GEGLU product and ff.net.2's output)")
+                             "the transformer tails the int8-activation GEMM takes (the GEGLU product and ff.net.2's output), 'einsum' = also "
+                             "the inputs q, k and v of every self-attention the int8 attention kernel takes (one recipe entry "
+                             "<block>.attn1.einsum: [r_q, r_k, r_v])")
     return parser
 
 
@@ -855,7 +857,7 @@ def main(args):
     if palette_halo and getattr(args, "quantize_nbits", None) is None and recipe is None:
         raise ValueError("--palette-halo keeps palettized convs palettized: it goes with --quantize-nbits or --pre-analysis-json-path / --selected-recipe")
     aq_recipe, calibrate = getattr(args, "activation_quantization_recipe", None), getattr(args, "calibrate_activations", None)
-    from .activation_quantization import all_calibration_scopes
+    from .activation_quantization import every_calibration_scope
     if aq_recipe and calibrate:
         raise ValueError("--calibrate-activations writes a recipe from the fp16 model; it does not go with --activation-quantization-recipe")
     pipe = get_hip_pipe(args.i, args.model_version, args.compute_unit, scheduler_override=scheduler,
@@ -865,7 +867,7 @@ def main(args):
                         disable_safety=getattr(args, "disable_safety", False), vae_encoder=bool(getattr(args, "image", None)),
                         quantize_nbits=getattr(args, "quantize_nbits", None), palettization_recipe=recipe,
                         device_postprocess=getattr(args, "device_postprocess", False), activation_quantization=aq_recipe, palette_halo=palette_halo,
-                        observe_activations=all_calibration_scopes()[getattr(args, "calibrate_scope", "stream")] if calibrate else False)
+                        observe_activations=every_calibration_scope()[getattr(args, "calibrate_scope", "stream")] if calibrate else False)
     controlnet_cond = None
     if args.controlnet:
         controlnet_cond = [prepare_controlnet_cond(args.controlnet_inputs[i], pipe.height, pipe.width)

@@ -1,0 +1,452 @@
+"""GPU suite of the W8A8 self-attention einsums (attention_i8.hip): the operator against the numpy restatement of its function
+(w8a8_einsum_ref.py), the quantizer launch bit for bit, the refusals in the header's order, and UNet handles - the ``einsum``
+calibration scope, a recipe made from its ranges, marks that are not applied, the CLI.
+
+THE CRITERIA of the operator are derived, not tuned.  Every step of the function but one is an exact integer sum or one correctly
+rounded fp32 operation; the one is the hardware exp2, which may move a p_q = rint(127 * exp2(t - m)) by one unit where 127 * exp2(x)
+sits on a rounding boundary.  One such flip changes N by <= 127 and L by 1 with L >= 127, so an output by at most 2 * r_v / 127:
+  (a) every element within 4 * r_v / 127 (two flips in a row) plus one fp16 ulp of the restatement;
+  (b) at most 2 % of the query rows with any element more than one fp16 ulp away;
+  (c) the rows of a query whose scores are all equal (every p_q is 127, exp2(0) is exact) are fp16(mean of v_q * s_v) to the bit.
+The restatement against itself with an exp2 perturbed by +-1 fp32 ulp (alternating sign per element) against a float64 exp2, on
+THIS file's inputs on the CPU: no probability moved and no output differed in any of the four cases - 0 of 4 096 at (1, 1, 64), 0 of
+262 144 at (2, 2, 256), 0 of 294 912 at (1, 2, 384), 0 of 1 048 576 at (1, 1, 1024) - so the restatement stays inside (a), whose bound
+is 0.0945 here, and (b); its all-equal rows meet (c) in all four.  (Scores with a standard deviation near 20 leave few probabilities
+between 0 and 127.)"""
+import json
+import os
+import re
+
+import numpy as np
+import pytest
+
+import w8a8_einsum_ref as ref
+from oracle import psnr, unet_ref, weights
+from python_hip_stable_diffusion import HipModel, _lib, activation_quantization as aq
+from test_w8a8_gpu import RANGE_DEV_GATE
+
+pytestmark = pytest.mark.gpu
+
+RING = 4                                                                         # stages of the kernel's LDS ring (attention_i8.hip launch_i8)
+SHAPES = [(1, 1, 64), (2, 2, 256), (1, 2, 384), (1, 1, 1024)]                    # (B, heads, S)
+ids3 = lambda s: "x".join(map(str, s))   # noqa: E731
+R_V = np.float32(3.0)
+TARGET_C = 1.5e-3                                                                # random scores then have a std near 20: logits reach +-60
+R_QK = np.float32(127.0 * np.sqrt(TARGET_C * 8.0 / 1.4426950408889634))          # r_q = r_k with c = TARGET_C
+Q_EQUAL, Q_DOMINANT = 5, 9
+
+
+def k_dominant(S):
+    return S - 27                                                                # behind the first key tile wherever there is a second one
+
+
+def test_the_shapes_reach_every_mechanism():
+    for B, heads, S in SHAPES:
+        assert _lib.lib() and S % 64 == 0 and 64 <= S <= ref.MAX_S                # the rule's answer for every shape of this file
+    tiles = [s[2] // 64 for s in SHAPES]
+    assert tiles[0] == 1                                                         # one key tile: the ring never wraps
+    assert tiles[2] % RING != 0 and tiles[2] > RING and tiles[2] % 2 == 0        # neither a multiple of the ring depth nor below it
+    assert SHAPES[3][2] > 256 and SHAPES[1][0] > 1 and SHAPES[1][1] > 1          # several query tiles per head; batch and head strides
+    assert abs(float(ref.score_scale(R_QK, R_QK)) / TARGET_C - 1.0) < 1e-3
+
+
+def make_case(shape, seed):
+    B, heads, S = shape
+    C = heads * 64
+    rs = np.random.RandomState(seed)
+    q, k, v = (np.clip(np.rint(rs.randn(B * S, C) * 40.0), -127, 127).astype(np.int8) for _ in range(3))
+    for a in (q, k, v):                                                          # +-127 in all three
+        a.reshape(-1)[rs.choice(a.size, 16, replace=False)] = np.array([-127, 127] * 8, np.int8)
+    if S > 64:                                                                   # head 0 of sample 0: the first key tile far below the rest
+        q[:S, 0:14] = 127
+        k[:S, 0:14] = 0
+        k[:64, 0:14] = -127
+    q[Q_EQUAL, :] = 0                                                            # every score of this query equal (all heads): every p_q is 127
+    k[k_dominant(S), :64] = np.where(rs.rand(64) < 0.5, -127, 127).astype(np.int8)
+    q[Q_DOMINANT, :64] = k[k_dominant(S), :64]                                   # one dominant key: 64 * 127^2 against a std of 12 800
+    return dict(B=B, heads=heads, S=S, q=q, k=k, v=v)
+
+
+def check_inputs(c):
+    """the inputs do what their comments say (CPU)"""
+    S, cs = c["S"], ref.score_scale(R_QK, R_QK)
+    s = c["q"][:S, :64].astype(np.int64) @ c["k"][:S, :64].astype(np.int64).T
+    t = s.astype(np.float32) * cs
+    assert np.abs(t).max() >= 60.0
+    if S > 64:                                                                   # (every query but the two special ones)
+        assert np.delete(t[:, :64], [Q_EQUAL, Q_DOMINANT], axis=0).max() <= -200.0 and np.delete(t[:, 64:], [Q_EQUAL], axis=0).max(axis=1).min() > -120.0
+    p = ref.probabilities(c["q"][:S, :64], c["k"][:S, :64], cs)
+    assert (p[Q_EQUAL] == 127).all()
+    assert p[Q_DOMINANT, k_dominant(S)] == 127 and p[Q_DOMINANT].sum() == 127
+    for a in (c["q"], c["k"], c["v"]):
+        assert a.min() == -127 and a.max() == 127
+
+
+def ulp16(x):
+    return np.spacing(np.abs(x).astype(np.float16)).astype(np.float32)
+
+
+def run_op(c, what):
+    n = c["B"] * c["S"] * c["heads"] * 64
+    buf = np.full(n + 4096, np.nan, np.float16)
+    out, _ = _lib.attention_w8a8(c["q"], c["k"], c["v"], R_QK, R_QK, R_V, c["B"], c["heads"], out=buf)
+    out = out.copy()
+    assert np.isnan(buf[n:]).all(), f"{what}: the guard behind the output was written"
+    assert np.isfinite(out).all(), f"{what}: the NaN prefill was not fully overwritten"
+    again, _ = _lib.attention_w8a8(c["q"], c["k"], c["v"], R_QK, R_QK, R_V, c["B"], c["heads"], iters=3)
+    assert np.array_equal(out.view(np.uint16), again.view(np.uint16)), f"{what}: two calls differ"
+    return out
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=ids3)
+def test_operator_against_the_restatement(shape):
+    c = make_case(shape, 31000 + SHAPES.index(shape))
+    check_inputs(c)
+    want = ref.attention(c["q"], c["k"], c["v"], R_QK, R_QK, R_V, c["B"], c["heads"])
+    got = run_op(c, str(shape))
+    diff = np.abs(got.astype(np.float32) - want.astype(np.float32))
+    one = ulp16(want)
+    rows_off = (diff > one).any(axis=1)
+    print(f"{shape}: {np.count_nonzero(got != want)} of {got.size} elements differ, {np.count_nonzero(rows_off)} of {rows_off.size} token rows more "
+          f"than one fp16 ulp away, largest difference {diff.max():.3e} (bound {4 * R_V / 127:.3e} + ulp)")
+    assert (diff <= np.float32(4.0) * R_V / np.float32(127.0) + one).all()                       # (a)
+    assert np.count_nonzero(rows_off) <= 0.02 * rows_off.size                                     # (b)
+    S = shape[2]                                                                                  # (c): the query sits in sample 0
+    exact = (c["v"][:S].astype(np.float64).mean(axis=0) * np.float64(ref.scale(R_V))).astype(np.float16)
+    assert np.array_equal(got[Q_EQUAL].view(np.uint16), exact.view(np.uint16)), "the all-equal query's row"
+    dom = (c["v"][k_dominant(S), :64].astype(np.float32) * ref.scale(R_V)).astype(np.float16)     # the dominant key alone: its value, exactly
+    assert np.array_equal(got[Q_DOMINANT, :64].view(np.uint16), dom.view(np.uint16))
+
+
+def test_operator_behind_poisoned_lds():
+    """SD_POISON_LDS=1 (with SD_TUNE) fills every CU's LDS with NaN bit patterns in front of the launch: the odd tile count of pass 1
+    (one key tile: half a stage never arrives) and the wrapped ring must give the same bits"""
+    import subprocess
+    import sys
+    root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+    env = dict(os.environ, SD_TUNE="1", SD_POISON_LDS="1")
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-q", "-x", "-k", "against_the_restatement and (1x1x64 or 1x2x384)"],
+                       env=env, cwd=root, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "2 passed" in r.stdout, r.stdout[-2000:]
+
+
+# ---- the quantizer launch, bit for bit ----
+Q_PRE = np.float32(1.4426950408889634) / np.float32(8.0)                         # attention_q_prescale(64)
+
+
+def perm1(S):
+    """position p of a V^T row in the fp16 kernel's order holds token perm1(S)[p] (test_w8a8_qkv_gpu.key_order)"""
+    return np.arange(S).reshape(-1, 4, 4)[:, [0, 2, 1, 3], :].reshape(-1)
+
+
+def perm2(S):
+    p = np.arange(S)
+    return (p & ~31) + ref.vt_key(p & 31)
+
+
+@pytest.mark.parametrize("prescale", [False, True], ids=["plain", "prescaled"])
+@pytest.mark.parametrize("vt_perm_in", [0, 1])
+@pytest.mark.parametrize("B, S, C, pad", [(1, 64, 64, 0), (2, 96, 128, 8)])
+def test_quantizer_is_the_numpy_quantizer_bit_for_bit(B, S, C, pad, vt_perm_in, prescale):
+    rs = np.random.RandomState(32000 + S + vt_perm_in + 2 * prescale)
+    r_q, r_k, r_v = np.float32(2.7), np.float32(3.3), np.float32(1.9)
+    qk = (rs.randn(B * S, 2 * C) * 1.2).astype(np.float16)
+    v = (rs.randn(B, C, S) * 0.8).astype(np.float16)                             # V^T in natural key order
+    specials = np.array([np.nan, np.inf, -np.inf, 65504.0, -65504.0, 0.0, 6e-8], np.float16)
+    qk.reshape(-1)[rs.choice(qk.size, specials.size, replace=False)] = specials
+    v.reshape(-1)[rs.choice(v.size, specials.size, replace=False)] = specials
+    if prescale:
+        qk[:, :C] = (qk[:, :C].astype(np.float32) * Q_PRE).astype(np.float16)    # what a handle's producer stores
+    q_eff = np.float32(r_q * Q_PRE) if prescale else r_q
+    vt_in = np.full((B, C, S + pad), np.nan, np.float16)                         # padding columns: never read
+    vt_in[:, :, :S] = v[:, :, perm1(S)] if vt_perm_in else v
+    qk_q, vt_q, _ = _lib.einsum_quantize(qk, vt_in, q_eff, r_k, r_v, vt_perm_in=vt_perm_in)
+    want_qk = np.concatenate([ref.quantize(qk[:, :C], q_eff), ref.quantize(qk[:, C:], r_k)], axis=1)
+    want_vt = ref.quantize(v, r_v)[:, :, perm2(S)]
+    assert np.abs(want_qk).max() == 127 and np.array_equal(qk_q, want_qk), f"{np.count_nonzero(qk_q != want_qk)} q | k values differ"
+    assert np.array_equal(vt_q, want_vt), f"{np.count_nonzero(vt_q != want_vt)} V^T values differ"
+
+
+def test_chain_quantizer_then_attention_is_the_operator_on_the_same_int8_values():
+    B, heads, S = 2, 2, 128
+    C = heads * 64
+    rs = np.random.RandomState(33000)
+    r_q, r_k, r_v = np.float32(4.0), np.float32(3.5), np.float32(2.5)
+    qk = (rs.randn(B * S, 2 * C) * 1.3).astype(np.float16)
+    v = (rs.randn(B, C, S) * 0.9).astype(np.float16)
+    qk_q, vt_q, _ = _lib.einsum_quantize(qk, v[:, :, perm1(S)], r_q, r_k, r_v, vt_perm_in=1)
+    v_nat = np.empty_like(vt_q)
+    v_nat[:, :, perm2(S)] = vt_q                                                 # back to natural key order, token-major
+    v_tok = np.ascontiguousarray(v_nat.transpose(0, 2, 1).reshape(B * S, C))
+    chain, _ = _lib.attention_w8a8(qk_q[:, :C], qk_q[:, C:], v_tok, r_q, r_k, r_v, B, heads)
+    direct, _ = _lib.attention_w8a8(ref.quantize(qk[:, :C], r_q), ref.quantize(qk[:, C:], r_k),
+                                    ref.quantize(v, r_v).transpose(0, 2, 1).reshape(B * S, C), r_q, r_k, r_v, B, heads)
+    assert np.isfinite(chain).all() and np.array_equal(chain.view(np.uint16), direct.view(np.uint16))
+
+
+# ---- refusals, each followed by a valid call ----
+def test_operator_refusals_in_the_headers_order_and_a_valid_call_right_after():
+    c = make_case(SHAPES[0], 34000)
+    want = ref.attention(c["q"], c["k"], c["v"], R_QK, R_QK, R_V, 1, 1)
+    first = run_op(c, "valid")
+
+    def valid():
+        out, _ = _lib.attention_w8a8(c["q"], c["k"], c["v"], R_QK, R_QK, R_V, 1, 1)
+        assert np.array_equal(out.view(np.uint16), first.view(np.uint16))
+
+    assert np.abs(first.astype(np.float32) - want.astype(np.float32)).max() <= 4 * R_V / 127 + ulp16(want).max()
+    bad = c["q"].copy()
+    bad[0, 0] = -128
+    nan = float("nan")
+    a = _lib.attention_w8a8
+    refused = [
+        (lambda: a(bad, bad, bad, nan, nan, nan, 1, 1, S=100), "off the shape rule"),
+        (lambda: a(bad, bad, bad, nan, nan, nan, 1, 1, S=ref.MAX_S + 64), "133120"),
+        (lambda: a(bad, bad, bad, nan, 1.0, 1.0, 1, 1), "positive finite"),
+        (lambda: a(bad, bad, bad, 1.0, 1.0, 0.0, 1, 1), "positive finite"),
+        (lambda: a(bad, c["k"], c["v"], 1.0, 1.0, 1.0, 1, 1), "q value -128"),
+        (lambda: a(c["q"], bad, c["v"], 1.0, 1.0, 1.0, 1, 1), "k value -128"),
+        (lambda: a(c["q"], c["k"], bad, 1.0, 1.0, 1.0, 1, 1), "v value -128"),
+    ]
+    for call, match in refused:
+        with pytest.raises(ValueError, match=match):
+            call()
+        valid()
+
+
+# ---- handles: the "mini" UNet (block channels 64 / 128 / 256 / 256 with 1 / 2 / 4 / 4 heads of 64) at 16 x 16 latents, batch 2: self-
+#      attentions at S = 256 (one head) and S = 64 (two heads) on the rule, S = 16 and S = 4 off it ----
+CFG = unet_ref.CONFIGS["mini"]
+BATCH = 2
+ATTN_LABEL = re.compile(r"^attention(\+i8)? h=(\d+) d=64 Sq=(\d+) Sk=(\d+)$")
+
+
+def state_dict():
+    return weights.make_state_dict(unet_ref.unet_param_shapes(CFG), seed=21, dtype=np.float16)
+
+
+def cfg_inputs():
+    hw = CFG["sample_size"]
+    return dict(sample=weights.seeded_normal((BATCH, 4, hw, hw), 1).astype(np.float16), timestep=np.array([981] * BATCH, np.float16),
+                encoder_hidden_states=weights.seeded_normal((BATCH, CFG["cross_attention_dim"], 1, 77), 2).astype(np.float16))
+
+
+def forward_twice(m):
+    inp = cfg_inputs()
+    return [m(**inp)["noise_pred"].copy() for _ in range(2)]
+
+
+def handle(**kw):
+    """outputs of eager x2 and capture + replay, labels, counters"""
+    r = {"outs": []}
+    for use_graph in (False, True):
+        m = HipModel(CFG, state_dict(), batch=BATCH, use_graph=use_graph, **kw)
+        r["outs"] += forward_twice(m)
+        if not use_graph:
+            r.update(labels=[lab for lab, _, _ in m.profile(1)], ranges=m.activation_ranges(), einsum=m.einsum_info(), layers=m.einsum_layers(),
+                     w8a8=m.w8a8_info(), used=m.arena_used_bytes)
+        m.close()
+    return r
+
+
+def self_attentions(labels):
+    """[(int8?, heads, S)] of the self-attention launches (S_q == S_k), in launch order"""
+    r = []
+    for lab in labels:
+        m = ATTN_LABEL.match(lab)
+        if m and m.group(3) == m.group(4):
+            r.append((m.group(1) is not None, int(m.group(2)), int(m.group(3))))
+    return r
+
+
+def oracle_forward(sd_t, attn1=None):
+    """unet_ref.unet_forward on this file's inputs; attn1(module, q, k, v, heads) -> attention output or None replaces the attention of
+    every self-attention for the call (q, k, v (B, C, 1, S) as unet_ref.cross_attention has them)"""
+    import torch
+    inp = cfg_inputs()
+    orig = unet_ref.cross_attention
+
+    def spy(sd, p, x, context, heads, impl):
+        if context is not None or attn1 is None:
+            return orig(sd, p, x, context, heads, impl)
+        q, k, v = (unet_ref.conv(sd, p + n, x) for n in (".to_q", ".to_k", ".to_v"))
+        o = attn1(p + ".einsum", q, k, v, heads)
+        if o is None:
+            from oracle import attention_ref
+            o = attention_ref.IMPLS[impl](q, k, v, heads, q.shape[1] // heads)
+        return unet_ref.conv(sd, p + ".to_out.0", o)
+
+    unet_ref.cross_attention = spy
+    try:
+        return unet_ref.unet_forward(sd_t, CFG, torch.from_numpy(inp["sample"].astype(np.float32)), torch.from_numpy(inp["timestep"].astype(np.float32)),
+                                     torch.from_numpy(inp["encoder_hidden_states"].astype(np.float32))).numpy()
+    finally:
+        unet_ref.cross_attention = orig
+
+
+@pytest.fixture(scope="module")
+def calibrated():
+    r = dict(plain=handle(), tail=handle(observe_activations="tail"), einsum=handle(observe_activations="einsum"))
+    seen = {}
+
+    def spy(module, q, k, v, heads):
+        for slot, t in ((".q", q), (".k", k), (".v", v)):
+            seen[module + slot] = max(seen.get(module + slot, 0.0), float(t.abs().max()))
+        return None
+
+    sd_t = weights.to_torch({k: v.astype(np.float32) for k, v in state_dict().items()})
+    r["oracle"] = oracle_forward(sd_t, spy)
+    r["oracle_ranges"], r["sd_t"] = seen, sd_t
+    return r
+
+
+def test_einsum_scope_adds_three_slots_and_one_launch_per_eligible_attention(calibrated):
+    r = calibrated
+    attns = self_attentions(r["plain"]["labels"])
+    eligible = [a for a in attns if a[2] % 64 == 0]
+    assert not any(i8 for i8, _, _ in attns) and len({s for _, _, s in eligible}) >= 2 and len(eligible) < len(attns), attns
+    before, after = r["tail"]["ranges"], r["einsum"]["ranges"]
+    extra = {k: v for k, v in after.items() if k not in before}
+    assert all(after[k] == before[k] for k in before) and len(extra) == 3 * len(eligible)
+    modules = sorted({k[:-2] for k in extra})
+    assert len(modules) == len(eligible) and all(m.endswith(".attn1.einsum") for m in modules)
+    assert set(extra) == {m + s for m in modules for s in (".q", ".k", ".v")}
+    labs = r["einsum"]["labels"]
+    assert len(labs) == len(r["tail"]["labels"]) + len(eligible)                 # one launch each
+    for m in modules:                                                            # ... directly in front of its attention
+        i = labs.index("absmax " + m)
+        assert ATTN_LABEL.match(labs[i + 1]) and not labs[i + 1].startswith("attention+i8")
+    assert len(r["einsum"]["outs"]) == 4 and r["einsum"]["einsum"] == (0, 0)
+    for a in r["einsum"]["outs"] + r["tail"]["outs"] + r["plain"]["outs"][1:]:   # outputs do not change, eager and replay
+        assert np.array_equal(a, r["plain"]["outs"][0])
+    devs = {k: abs(v - r["oracle_ranges"][k]) / r["oracle_ranges"][k] for k, v in extra.items()}
+    print("observed einsum ranges vs oracle:", {k: (round(extra[k], 4), round(r["oracle_ranges"][k], 4), f"{devs[k]:.2e}") for k in sorted(extra)})
+    assert max(devs.values()) <= RANGE_DEV_GATE, devs
+
+
+def restated_attn1(recipe):
+    """the oracle's self-attention replaced by the restatement for the einsums of the recipe"""
+    import torch
+
+    def attn1(module, q, k, v, heads):
+        if module not in recipe:
+            return None
+        r_q, r_k, r_v = recipe[module]
+        B, C, _, S = q.shape
+        tok = lambda t: np.ascontiguousarray(t.numpy().reshape(B, C, S).transpose(0, 2, 1).reshape(B * S, C)).astype(np.float16)   # noqa: E731
+        o = ref.attention(ref.quantize(tok(q), r_q), ref.quantize(tok(k), r_k), ref.quantize(tok(v), r_v), r_q, r_k, r_v, B, heads)
+        return torch.from_numpy(np.ascontiguousarray(o.astype(np.float32).reshape(B, S, C).transpose(0, 2, 1)).reshape(B, C, 1, S))
+
+    return attn1
+
+
+# PSNR of the handle with its eligible self-attentions on the int8 kernel against the oracle whose attn1 attention is the restatement,
+# measured on the MI355X (LAB_NOTES.md round 36); the gate is the project's rule, measured - 6 dB, beside the parameter-free one.
+W8A8_EINSUM_PSNR_MEASURED = 60.06    # 10 int8 self-attentions (the fp16 handle against the same oracle: 58.10 dB; against the fp32 oracle: 67.77 dB)
+
+
+def test_recipe_from_the_ranges_runs_every_eligible_attention_from_int8(calibrated):
+    r = calibrated
+    new = {k: v for k, v in r["einsum"]["ranges"].items() if k not in r["tail"]["ranges"]}
+    recipe = aq.recipe_from_ranges(new)
+    n = len([a for a in self_attentions(r["plain"]["labels"]) if a[2] % 64 == 0])
+    assert len(recipe) == n and all(aq.is_einsum(k) and len(v) == 3 for k, v in recipe.items())
+    q = handle(activation_quantization=recipe)
+    assert q["einsum"] == (n, n) and sorted(q["layers"]) == sorted(recipe) and q["w8a8"] == (0, 0, 0)
+    labs = q["labels"]
+    attns = self_attentions(labs)
+    assert [a[1:] for a in attns] == [a[1:] for a in self_attentions(r["plain"]["labels"])]
+    assert all(i8 == (s % 64 == 0) for i8, _, s in attns) and len({s for i8, _, s in attns if i8}) >= 2
+    q8 = [i for i, lab in enumerate(labs) if lab.startswith("einsum_q8 ")]
+    i8 = [i for i, lab in enumerate(labs) if lab.startswith("attention+i8 ")]
+    assert len(i8) == n and q8 == [i - 1 for i in i8]                            # directly in front of every attention+i8 and nowhere else
+    assert sorted(labs[i][len("einsum_q8 "):] + ".einsum" for i in q8) == sorted(recipe)
+    assert len(labs) == len(r["plain"]["labels"]) + n
+    assert len(q["outs"]) == 4
+    for a in q["outs"]:                                                          # eager x2, capture + replay
+        assert np.isfinite(a).all() and np.array_equal(a, q["outs"][0])
+    w8a8, plain = q["outs"][0], r["plain"]["outs"][0]
+    assert not np.array_equal(w8a8, plain)
+    # parity, free of parameters: the handle is closer to the oracle with the restated attn1 than the fp16 handle is to that oracle
+    restated = oracle_forward(r["sd_t"], restated_attn1(recipe))
+    p_w8a8, p_plain = psnr.compute_psnr(w8a8, restated), psnr.compute_psnr(plain, restated)
+    print(f"W8A8 handle, {n} int8 self-attentions: PSNR vs the oracle with the restated attn1 {p_w8a8:.2f} dB (the fp16 handle: {p_plain:.2f} dB); "
+          f"fp16 handle vs the fp32 oracle {psnr.compute_psnr(plain, r['oracle']):.2f} dB; W8A8 handle vs the fp16 handle "
+          f"{psnr.compute_psnr(w8a8, plain):.2f} dB; arena {q['used']} bytes (fp16 handle {r['plain']['used']})")
+    assert p_w8a8 > p_plain
+    if W8A8_EINSUM_PSNR_MEASURED is not None:
+        assert p_w8a8 >= W8A8_EINSUM_PSNR_MEASURED - 6.0
+
+
+def test_all_three_attention_implementations_run_the_one_kernel():
+    """block channels (64, 128) with 1 and 2 heads at 16 x 16 latents: every self-attention (S = 256 and S = 64) is on the rule and every
+    cross-attention runs the fused launch, which has one schedule - so no launch of the handle depends on the implementation flag once
+    the self-attentions run on the int8 kernel.  (The "mini" handle above also has self-attentions at S = 16 and S = 4 on the general
+    kernels, whose schedules follow the flag.)"""
+    cfg = unet_ref.make_config(sample_size=16, block_out_channels=(64, 128), down_block_types=(unet_ref.CA, unet_ref.CA),
+                               up_block_types=(unet_ref.CAUP, unet_ref.CAUP), layers_per_block=1, attention_head_dim=(1, 2), cross_attention_dim=128)
+    sd16 = weights.make_state_dict(unet_ref.unet_param_shapes(cfg), seed=36, dtype=np.float16)
+    inp = dict(sample=weights.seeded_normal((BATCH, 4, 16, 16), 3).astype(np.float16), timestep=np.array([500] * BATCH, np.float16),
+               encoder_hidden_states=weights.seeded_normal((BATCH, 128, 1, 77), 4).astype(np.float16))
+    obs = HipModel(cfg, sd16, batch=BATCH, observe_activations="einsum")
+    obs(**inp)
+    recipe = {k: v for k, v in aq.recipe_from_ranges(obs.activation_ranges()).items() if aq.is_einsum(k)}
+    obs.close()
+    outs, sizes = {}, set()
+    for impl in ("ORIGINAL", "SPLIT_EINSUM", "SPLIT_EINSUM_V2"):
+        m = HipModel(cfg, sd16, batch=BATCH, attention_implementation=impl, activation_quantization=recipe)
+        outs[impl] = m(**inp)["noise_pred"].copy()
+        attns = self_attentions([lab for lab, _, _ in m.profile(1)])
+        assert m.einsum_info() == (len(recipe), len(recipe)) and len(attns) == len(recipe) and all(i8 for i8, _, _ in attns), (impl, attns)
+        sizes |= {s for _, _, s in attns}
+        m.set_attention_implementation("ORIGINAL")                               # ... and the run-time switch changes nothing either
+        assert np.array_equal(m(**inp)["noise_pred"], outs[impl])
+        m.close()
+    assert sizes == {64, 256} and np.isfinite(outs["ORIGINAL"]).all()
+    assert np.array_equal(outs["SPLIT_EINSUM"], outs["ORIGINAL"]) and np.array_equal(outs["SPLIT_EINSUM_V2"], outs["ORIGINAL"])
+
+
+def test_marks_off_the_rule_and_attn2_are_marked_not_applied(calibrated):
+    r = calibrated
+    names = [k[:-len(".to_q.weight")] for k in state_dict() if k.endswith(".attn1.to_q.weight")]
+    eligible = {k[:-2] for k in r["einsum"]["ranges"] if k.endswith(".einsum.q")}
+    off_rule = sorted(n + ".einsum" for n in names if n + ".einsum" not in eligible)
+    assert off_rule                                                              # the S = 16 and S = 4 self-attentions
+    attn2 = sorted(n.replace(".attn1", ".attn2") + ".einsum" for n in names)
+    recipe = {m: [1.0, 2.0, 3.0] for m in off_rule + attn2}
+    q = handle(activation_quantization=recipe)
+    assert q["einsum"] == (len(recipe), 0) and q["layers"] == []
+    assert q["labels"] == r["plain"]["labels"] and q["used"] == r["plain"]["used"]
+    for a in q["outs"]:
+        assert np.array_equal(a, r["plain"]["outs"][0])
+
+
+# ---- pipeline ----
+def test_cli_calibrates_with_the_einsum_scope_then_applies_the_recipe(tmp_path, monkeypatch):
+    from PIL import Image
+    from python_hip_stable_diffusion import pipeline as P
+    from test_text_encoder_gpu import write_checkpoint_dir
+    root = str(tmp_path / "mini-sd")
+    os.makedirs(root)
+    write_checkpoint_dir(root)
+    path = str(tmp_path / "w8a8-einsum.json")
+    pipes = []
+    real = P.get_hip_pipe
+    monkeypatch.setattr(P, "get_hip_pipe", lambda *a, **kw: pipes.append(real(*a, **kw)) or pipes[-1])
+
+    def generate(tag, *flags):
+        args = P.build_parser().parse_args(["--prompt", "a photo of an astronaut riding a horse", "-i", root, "-o", str(tmp_path / tag), "--seed", "93",
+                                            "--model-version", "mini/stable-diffusion", "--scheduler", "DDIM", "--num-inference-steps", "2",
+                                            "--attention-implementation", "ORIGINAL", *flags])
+        return np.array(Image.open(P.main(args)))
+
+    plain = generate("plain")
+    image = generate("calib", "--calibrate-activations", path, "--calibrate-scope", "einsum")
+    assert np.array_equal(image, plain)                                          # observing changes no image
+    recipe = json.load(open(path))
+    assert recipe == aq.recipe_from_ranges(pipes[-1].unet.activation_ranges())
+    einsums = {k: v for k, v in recipe.items() if aq.is_einsum(k)}
+    assert len(einsums) >= 2 and all(isinstance(v, list) and len(v) == 3 for v in einsums.values())
+    quant = generate("w8a8", "--activation-quantization-recipe", path)
+    assert pipes[-1].unet.einsum_info() == (len(einsums), len(einsums))
+    assert quant.shape == plain.shape and not np.array_equal(quant, plain)       # the recipe really is applied
