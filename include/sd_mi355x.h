@@ -453,6 +453,20 @@ int sd_text_encoder_encode(sd_text_encoder* t, const int32_t* input_ids, int eos
  * 100 + u = that kernel's balanced grid with u (query tile, key tile) units per workgroup (0: the launch's own split). */
 int sd_op_attention(int impl, const void* q, const void* k, const void* v, void* out, int B, int heads, int d,
                     int Sq, int Sk, int variant, int iters, float* ms);
+/* Which kernel would sd_op_attention (int8 = 0; `variant` as that entry reads it, 100 + u included) or sd_op_attention_w8a8 (int8 != 0:
+ * S = Sq; impl, d, Sk and variant are not read) launch for this problem on the current device?  Host only: no device work, nothing
+ * launched; the compute-unit count the rules read is the device's, 256 where there is none.  It refuses what those entries refuse from
+ * the shape alone, with their errors.  The answer is what the launcher itself decides (one host function per launcher, which the launch
+ * calls), as one NUL-terminated line in text (text_bytes too small: SD_ERR_INVALID_ARGUMENT):
+ *   "attn d<d> original w4 qt1"                 attention.hip, the ORIGINAL schedule
+ *   "attn d<d> split w<4|8> qt<1|2>"            attention.hip, SPLIT_EINSUM (w4 qt1) and the 512-query chunks of SPLIT_EINSUM_V2: w = waves
+ *                                               per workgroup, qt = 32-query tiles per wave (qt2 only with w8 and d <= 64)
+ *   "attn8 w<4|8> classic"                      attention8.hip, one workgroup per query tile
+ *   "attn8 w<4|8> balanced upw=<u> seg=<s>"     attention8.hip, the balanced form: u (query tile, key tile) units per workgroup, at most s
+ *                                               query-tile segments per workgroup
+ *   "attn_i8 w<4|8>"                            attention_i8.hip
+ * attention8.hip and attention_i8.hip share ONE waves rule: w8 where B * heads * ceil(Sq / 256) >= compute units / 2. */
+int sd_op_attention_kernel(int int8, int impl, int B, int heads, int d, int Sq, int Sk, int variant, char* text, int text_bytes);
 /* layer_norm.py:51-80.  x (B, C, 1, S) f16, weight/bias (C) f32 -> out (B, C, 1, S) f16 */
 int sd_op_layernorm(const void* x, const float* weight, const float* bias, void* out, int B, int C, int S, float eps,
                     int iters, float* ms);

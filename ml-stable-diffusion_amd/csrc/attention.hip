@@ -532,28 +532,22 @@ void launch_one(const AttnArgs& a, int B, hipStream_t s) {
   hipLaunchKernelGGL(k, grid, dim3(WAVES * 64), lds, s, aa);
 }
 
+// one instantiation per form attention_kernel() can name for this head dim
 template <int DK16, int DC32>
-void launch_d(const AttnArgs& a, int B, int impl, hipStream_t s) {
-  if (impl == kAttnOriginal) {
+void launch_d(const AttnArgs& a, int B, const AttnKernel& c, hipStream_t s) {
+  if (c.mode == 0 && c.waves == 4 && c.q_tiles == 1) {
     launch_one<DK16, DC32, 0, 4, 1>(a, B, s);
-  } else if (impl == kAttnSplitEinsum) {
+  } else if (c.mode == 1 && c.waves == 4 && c.q_tiles == 1) {
     launch_one<DK16, DC32, 1, 4, 1>(a, B, s);
   } else {
-    // SPLIT_EINSUM_V2: the query axis is cut into 512-query chunks (attention.py:75-86).  A chunk is
-    // one 8-wave workgroup (64 queries per wave) when the launch has enough chunks to fill the 256
-    // CUs; with few chunks (CFG batch 2 at 64x64: 80) each chunk is split over two 256-query or four
-    // 128-query workgroups instead - same chunk arithmetic, more workgroups in flight.
-    const long chunks = (long)B * a.heads * cdiv(a.Sq, 512);
     if constexpr (DC32 <= 2) {
-      if (chunks >= 192) {
+      if (c.mode == 1 && c.waves == 8 && c.q_tiles == 2) {
         launch_one<DK16, DC32, 1, 8, 2>(a, B, s);
         return;
       }
     }
-    if (chunks * 2 >= 192)
-      launch_one<DK16, DC32, 1, 8, 1>(a, B, s);   // also: d > 64 (register budget of two query tiles per wave)
-    else
-      launch_one<DK16, DC32, 1, 4, 1>(a, B, s);
+    if (c.mode == 1 && c.waves == 8 && c.q_tiles == 1) launch_one<DK16, DC32, 1, 8, 1>(a, B, s);
+    else fail(kInternal, "attention: no instantiation for %s", attention_kernel_name(c).c_str());
   }
 }
 
@@ -561,7 +555,16 @@ void launch_d(const AttnArgs& a, int B, int impl, hipStream_t s) {
 
 bool attention_supported(int d) { return d > 0 && d % 8 == 0 && d <= 160; }
 
-void launch_attention(const AttnDesc& d, hipStream_t s) {
+std::string attention_kernel_name(const AttnKernel& k) {
+  char t[96];
+  if (k.family == kAttnFamilyI8) snprintf(t, sizeof t, "attn_i8 w%d", k.waves);
+  else if (k.family == kAttnFamily8 && k.balanced) snprintf(t, sizeof t, "attn8 w%d balanced upw=%d seg=%d", k.waves, k.upw, k.max_seg);
+  else if (k.family == kAttnFamily8) snprintf(t, sizeof t, "attn8 w%d classic", k.waves);
+  else snprintf(t, sizeof t, "attn d%d %s w%d qt%d", k.d, k.mode == 0 ? "original" : "split", k.waves, k.q_tiles);
+  return t;
+}
+
+AttnKernel attention_kernel(const AttnDesc& d) {
   SD_REQUIRE(attention_supported(d.d), kUnsupported, "attention: head dim %d unsupported (need d %% 8 == 0, d <= 160)",
              d.d);
   SD_REQUIRE(d.ldq % 8 == 0 && d.ldk % 8 == 0 && d.ldv % 8 == 0 && d.ldo % 4 == 0, kInvalidArgument,
@@ -580,24 +583,46 @@ void launch_attention(const AttnDesc& d, hipStream_t s) {
   if (d.vt_perm) {   // d = 64, whole key tiles: the software-pipelined two-waves-per-SIMD kernel (attention8.hip)
     SD_REQUIRE(attention8_ok(d), kInvalidArgument, "attention: permuted V^T but the shape is not attention8's (d %d Sq %d Sk %d)", d.d,
                d.Sq, d.Sk);
-    AttnDesc d8 = d;
-    d8.impl = impl;
-    launch_attention8(d8, s);
+    return attention8_kernel(d);
+  }
+  AttnKernel c;
+  c.d = d.d;
+  c.mode = impl == kAttnOriginal ? 0 : 1;
+  if (impl == kAttnSplitEinsumV2) {
+    // SPLIT_EINSUM_V2: the query axis is cut into 512-query chunks (attention.py:75-86).  A chunk is
+    // one 8-wave workgroup (64 queries per wave) when the launch has enough chunks to fill the 256
+    // CUs; with few chunks (CFG batch 2 at 64x64: 80) each chunk is split over two 256-query or four
+    // 128-query workgroups instead - same chunk arithmetic, more workgroups in flight.
+    const long chunks = (long)d.B * d.heads * cdiv(d.Sq, 512);
+    if (chunks >= 192 && d.d <= 64) {   // (d > 64: the register budget of two query tiles per wave)
+      c.waves = 8;
+      c.q_tiles = 2;
+    } else if (chunks * 2 >= 192) {
+      c.waves = 8;
+    }
+  }
+  return c;
+}
+
+void launch_attention(const AttnDesc& d, hipStream_t s) {
+  const AttnKernel c = attention_kernel(d);
+  if (c.family == kAttnFamily8) {
+    launch_attention8(d, s);
     return;
   }
   AttnArgs a{d.q, d.k, d.vt, d.out, d.heads, d.d, d.Sq, d.Sk, d.ldq, d.ldk, d.ldv, d.ldo,
              1.4426950408889634f / sqrtf((float)d.d)};
   const int dk16 = cdiv(d.d, 16), dc32 = cdiv(d.d, 32);
-  if (dk16 == 1 && dc32 == 1) launch_d<1, 1>(a, d.B, impl, s);
-  else if (dk16 == 2 && dc32 == 1) launch_d<2, 1>(a, d.B, impl, s);
-  else if (dk16 == 3 && dc32 == 2) launch_d<3, 2>(a, d.B, impl, s);
-  else if (dk16 == 4 && dc32 == 2) launch_d<4, 2>(a, d.B, impl, s);
-  else if (dk16 == 5 && dc32 == 3) launch_d<5, 3>(a, d.B, impl, s);
-  else if (dk16 == 6 && dc32 == 3) launch_d<6, 3>(a, d.B, impl, s);
-  else if (dk16 == 7 && dc32 == 4) launch_d<7, 4>(a, d.B, impl, s);
-  else if (dk16 == 8 && dc32 == 4) launch_d<8, 4>(a, d.B, impl, s);
-  else if (dk16 == 9 && dc32 == 5) launch_d<9, 5>(a, d.B, impl, s);
-  else if (dk16 == 10 && dc32 == 5) launch_d<10, 5>(a, d.B, impl, s);
+  if (dk16 == 1 && dc32 == 1) launch_d<1, 1>(a, d.B, c, s);
+  else if (dk16 == 2 && dc32 == 1) launch_d<2, 1>(a, d.B, c, s);
+  else if (dk16 == 3 && dc32 == 2) launch_d<3, 2>(a, d.B, c, s);
+  else if (dk16 == 4 && dc32 == 2) launch_d<4, 2>(a, d.B, c, s);
+  else if (dk16 == 5 && dc32 == 3) launch_d<5, 3>(a, d.B, c, s);
+  else if (dk16 == 6 && dc32 == 3) launch_d<6, 3>(a, d.B, c, s);
+  else if (dk16 == 7 && dc32 == 4) launch_d<7, 4>(a, d.B, c, s);
+  else if (dk16 == 8 && dc32 == 4) launch_d<8, 4>(a, d.B, c, s);
+  else if (dk16 == 9 && dc32 == 5) launch_d<9, 5>(a, d.B, c, s);
+  else if (dk16 == 10 && dc32 == 5) launch_d<10, 5>(a, d.B, c, s);
   else fail(kUnsupported, "attention: no kernel for head dim %d", d.d);
   SD_HIP(hipGetLastError());
 }

@@ -604,15 +604,6 @@ void launch8_sk(const Attn8Args& a, int grid, hipStream_t s) {
   hipLaunchKernelGGL(k, dim3(grid), dim3(WAVES * 64), lds, s, a);
 }
 
-int device_cus() {
-  static const int n = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-    return v;
-  }();
-  return n;
-}
-
 // Do consecutive workgroup ids go round-robin over eight XCDs (id % 8), as the locality walks of this library assume?  Probed once with a
 // grid that over-subscribes the chip; the balanced form may send its partial results through the XCD's L2 (sc0) instead of past it (sc1)
 // only when this held for every workgroup - an experiment (see below), not the product path.
@@ -642,6 +633,12 @@ bool xcd_round_robin() {
   return ok;
 }
 
+// waves per workgroup of either form: the library's rule (attention_waves), or SD_ATTN8_WAVES (with SD_TUNE)
+int attn8_waves(const AttnDesc& d) {
+  static const int force = tune_env_int("SD_ATTN8_WAVES", 0);
+  return force ? (force == 8 ? 8 : 4) : attention_waves(d.B, d.heads, d.Sq);
+}
+
 // The balanced form's launch geometry for a problem (nothing when the classic grid is the better one).
 struct SkPlan {
   bool on = false;
@@ -653,14 +650,12 @@ struct SkPlan {
 SkPlan sk_plan(const AttnDesc& d) {
   // SD_ATTN8_SK (with SD_TUNE): 0 = never, 1 = where the classic grid leaves CUs idle (default), 2 = wherever it can run
   static const int env_mode = tune_env_int("SD_ATTN8_SK", SD_ATTN8_SK_DEFAULT);
-  static const int force_waves = tune_env_int("SD_ATTN8_WAVES", 0);
   static const int min_upw = tune_env_int("SD_ATTN8_SK_MIN_UPW", 32);
   SkPlan p;
   const int mode = d.sk_force ? 2 : env_mode;
   if (mode == 0 || d.Sq % 32 != 0) return p;
   const int ncu = device_cus();
-  const long wg8 = (long)d.B * d.heads * cdiv(d.Sq, 256);
-  p.waves = force_waves ? (force_waves == 8 ? 8 : 4) : (wg8 >= 128 ? 8 : 4);
+  p.waves = attn8_waves(d);
   if (d.Sq % (p.waves * 32) != 0) return p;                  // whole query tiles only: every wave of a segment has 32 live queries
   p.q_tiles = d.Sq / (p.waves * 32);
   const long classic = (long)d.B * d.heads * p.q_tiles;
@@ -708,39 +703,62 @@ bool attention8_sk_scratch(const AttnDesc& d, size_t* part_bytes, int* n_counter
   return p.on;
 }
 
+int device_cus() {
+  static const int n = [] {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
+    return v;
+  }();
+  return n;
+}
+
+int attention_waves(int B, int heads, int Sq) { return (long)B * heads * cdiv(Sq, 256) >= device_cus() / 2 ? 8 : 4; }
+
+// The balanced form where the caller offers scratch and sk_plan() wants it, else the classic grid.
+AttnKernel attention8_kernel(const AttnDesc& d) {
+  AttnKernel c;
+  c.family = kAttnFamily8;
+  c.waves = attn8_waves(d);
+  if (d.sk_part && d.sk_cnt) {
+    const SkPlan p = sk_plan(d);
+    if (p.on && p.part_bytes <= d.sk_part_bytes && p.n_cnt <= d.sk_cnt_n) {
+      c.balanced = true;
+      c.waves = p.waves;
+      c.upw = p.upw;
+      c.max_seg = p.max_seg;
+    }
+  }
+  return c;
+}
+
 void launch_attention8(const AttnDesc& d, hipStream_t s) {
   Attn8Args a{d.q, d.k, d.vt, d.out, d.heads, d.Sq, d.Sk, d.ldq, d.ldk, d.ldv, d.ldo, 1.4426950408889634f / 8.0f, 0, d.q_prescaled};
   static const bool exact = tune_env_int("SD_ATTN8_EXACT", 0) != 0;
-  if (d.sk_part && d.sk_cnt) {   // the caller offers scratch: the balanced form where it pays
-    const SkPlan p = sk_plan(d);
-    if (p.on && p.part_bytes <= d.sk_part_bytes && p.n_cnt <= d.sk_cnt_n) {
-      a.q_tiles = p.q_tiles;
-      a.upw = p.upw;
-      a.total_units = p.total;
-      a.max_seg = p.max_seg;
-      a.xcd_local = p.xcd_local ? 1 : 0;
-      static const int dbg = tune_env_int("SD_ATTN8_SK_DBG", 0);
-      a.dbg = dbg;
-      static const bool verbose = tune_env_int("SD_ATTN8_SK_VERBOSE", 0) != 0;
-      if (verbose) fprintf(stderr, "attention8 balanced: grid %d x %d waves, %d units each, max_seg %d, xcd_local %d, dbg %d\n", p.grid, p.waves, p.upw, p.max_seg, a.xcd_local, dbg);
-      a.part = d.sk_part;
-      a.cnt = d.sk_cnt;
-      if (p.waves == 8) {
-        if (exact) launch8_sk<8, 4, true>(a, p.grid, s);
-        else launch8_sk<8, 4, false>(a, p.grid, s);
-      } else {
-        if (exact) launch8_sk<4, 4, true>(a, p.grid, s);
-        else launch8_sk<4, 4, false>(a, p.grid, s);
-      }
-      SD_HIP(hipGetLastError());
-      return;
+  const AttnKernel c = attention8_kernel(d);
+  if (c.balanced) {
+    const SkPlan p = sk_plan(d);   // (the plan attention8_kernel read: the rest of its geometry)
+    a.q_tiles = p.q_tiles;
+    a.upw = c.upw;
+    a.total_units = p.total;
+    a.max_seg = c.max_seg;
+    a.xcd_local = p.xcd_local ? 1 : 0;
+    static const int dbg = tune_env_int("SD_ATTN8_SK_DBG", 0);
+    a.dbg = dbg;
+    static const bool verbose = tune_env_int("SD_ATTN8_SK_VERBOSE", 0) != 0;
+    if (verbose) fprintf(stderr, "attention8 balanced: grid %d x %d waves, %d units each, max_seg %d, xcd_local %d, dbg %d\n", p.grid, c.waves, c.upw, c.max_seg, a.xcd_local, dbg);
+    a.part = d.sk_part;
+    a.cnt = d.sk_cnt;
+    if (c.waves == 8) {
+      if (exact) launch8_sk<8, 4, true>(a, p.grid, s);
+      else launch8_sk<8, 4, false>(a, p.grid, s);
+    } else {
+      if (exact) launch8_sk<4, 4, true>(a, p.grid, s);
+      else launch8_sk<4, 4, false>(a, p.grid, s);
     }
+    SD_HIP(hipGetLastError());
+    return;
   }
-  // 256-query workgroups when they give at least half the CUs one, else 128-query ones: more, smaller workgroups
-  const long wg8 = (long)d.B * d.heads * cdiv(d.Sq, 256);
-  static const int force = tune_env_int("SD_ATTN8_WAVES", 0);
-  const bool eight = force ? force == 8 : wg8 >= 128;
-  if (eight) {
+  if (c.waves == 8) {
     if (exact) launch8<8, 4, true>(a, d.B, s);
     else launch8<8, 4, false>(a, d.B, s);
   } else {

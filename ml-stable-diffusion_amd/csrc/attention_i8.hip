@@ -360,15 +360,6 @@ __global__ __launch_bounds__(256) void einsum_absmax_kernel(const half_t* qk, co
   }
 }
 
-int device_cus() {
-  static const int n = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-    return v;
-  }();
-  return n;
-}
-
 template <int WAVES, int D>
 void launch_i8(AttnI8Args a, int B, hipStream_t s) {
   a.q_tiles = cdiv(a.S, WAVES * 32);
@@ -389,17 +380,23 @@ float attention_i8_score_scale(float q_absmax, float k_absmax, int d) {
   return (float)((((double)s_q * (double)s_k) * (1.0 / std::sqrt((double)d))) * 1.4426950408889634);
 }
 
-void launch_attention_i8(const AttnI8Desc& d, hipStream_t s) {
-  const size_t lim = (size_t)1 << 31;
+AttnKernel attention_i8_kernel(const AttnI8Desc& d) {
   SD_REQUIRE(attention_i8_shape_ok(64, d.S, d.S) && d.B > 0 && d.heads > 0, kInvalidArgument, "attention_i8: S = %d (B %d, heads %d) is off the shape rule",
              d.S, d.B, d.heads);
+  AttnKernel c;
+  c.family = kAttnFamilyI8;
+  c.waves = attention_waves(d.B, d.heads, d.S);   // attention8's rule
+  return c;
+}
+
+void launch_attention_i8(const AttnI8Desc& d, hipStream_t s) {
+  const size_t lim = (size_t)1 << 31;
+  const AttnKernel c = attention_i8_kernel(d);
   SD_REQUIRE(d.ldq % 16 == 0 && d.ldk % 16 == 0 && d.ldv % 16 == 0 && d.ldo % 8 == 0 && (size_t)d.S * d.ldk < lim && (size_t)64 * d.ldv < lim,
              kInvalidArgument, "attention_i8: strides %d %d %d %d", d.ldq, d.ldk, d.ldv, d.ldo);
   AttnI8Args a{d.q, d.k, d.vt, d.out, d.heads, d.S, d.ldq, d.ldk, d.ldv, d.ldo, attention_i8_score_scale(d.q_absmax, d.k_absmax, 64),
                d.v_absmax / 127.0f, 0};
-  // attention8's rule: 256-query workgroups when they give at least half of 256 CUs one, else 128-query ones - more, smaller workgroups
-  const long wg8 = (long)d.B * d.heads * cdiv(d.S, 256);
-  if (wg8 >= device_cus() / 2) launch_i8<8, 4>(a, d.B, s);
+  if (c.waves == 8) launch_i8<8, 4>(a, d.B, s);
   else launch_i8<4, 4>(a, d.B, s);
   SD_HIP(hipGetLastError());
 }

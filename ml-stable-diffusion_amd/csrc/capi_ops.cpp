@@ -23,6 +23,7 @@
 //   sd_op_attention `variant`: 0 default dispatch, 1 never the software-pipelined d = 64 kernel (attention8.hip), 2 that kernel with
 //     pre-scaled q, 3 default dispatch with q and k as rows of ONE [B][S][2C] buffer (ldq = ldk = 2C, what a handle's self-attention
 //     reads; Sq == Sk), 100 + u its balanced form with u units per workgroup (0: the launch's own split)
+//     (sd_op_attention_kernel names the kernel a shape and variant launch: attention_op_desc below builds the descriptor for both)
 //
 // Device buffers: every one comes from the entry point's Scratch (capi_util.h) - guards of 0xff in front and behind, outputs and
 // workspaces poisoned, every guard checked when the scratch leaves scope.  No entry point allocates device memory any other way.
@@ -363,20 +364,59 @@ using namespace sd;
 
 extern "C" {
 
+// What sd_op_attention and sd_op_attention_kernel share: the entry's host refusals, in its order, and every field of the descriptor that
+// is not an address.
+static AttnDesc attention_op_desc(int impl, int B, int heads, int d, int Sq, int Sk, int variant) {
+  SD_REQUIRE(impl >= 0 && impl <= 2, kInvalidArgument, "unknown attention implementation %d", impl);
+  SD_REQUIRE(B > 0 && heads > 0 && d > 0 && Sq > 0 && Sk > 0, kInvalidArgument, "empty attention problem");
+  SD_REQUIRE(variant != 3 || Sq == Sk, kInvalidArgument, "attention variant 3 (q | k in one buffer) needs Sq == Sk (%d, %d)", Sq, Sk);
+  const int C = heads * d;
+  // the software-pipelined d = 64 kernel reads V^T in its own key order (AttnDesc::vt_perm)
+  const bool perm = variant != 1 && attention8_shape_ok(d, Sq, Sk);
+  AttnDesc a;
+  a.ldq = a.ldk = variant == 3 ? 2 * C : C;   // 3: q and k are rows of ONE [B][S][2C] buffer (qkv_desc's qk)
+  a.B = B; a.heads = heads; a.d = d; a.Sq = Sq; a.Sk = Sk;
+  a.ldv = (Sk + 7) / 8 * 8; a.ldo = C;
+  a.impl = impl;
+  a.variant = variant == 3 ? 0 : variant;   // (3: the default dispatch, only the addresses differ)
+  a.vt_perm = perm ? 1 : 0;
+  if (variant == 2) {   // the caller multiplied d^-0.5 * log2(e) into q before rounding it to fp16 (what the UNet's q|k|v GEMM does)
+    SD_REQUIRE(perm, kInvalidArgument, "attention variant 2 (pre-scaled q) needs attention8's shape (d %d Sq %d Sk %d)", d, Sq, Sk);
+    a.q_prescaled = 1;
+  }
+  if (variant >= 100) {   // attention8's balanced form, variant - 100 units per workgroup (0: the launch's own split)
+    SD_REQUIRE(perm, kInvalidArgument, "attention variant %d (balanced form) needs attention8's shape (d %d Sq %d Sk %d)", variant, d, Sq, Sk);
+    a.variant = 0;
+    a.sk_force = 1;
+    a.sk_upw = variant - 100;
+  }
+  return a;
+}
+// the scratch of the balanced form where attention8 wants it for this problem (sizes into the descriptor; false: the classic grid)
+static bool attention_op_wants_scratch(AttnDesc& a, int variant) {
+  size_t pb = 0;
+  int nc = 0;
+  if (a.vt_perm && attention8_sk_scratch(a, &pb, &nc)) {
+    a.sk_part_bytes = pb;
+    a.sk_cnt_n = nc;
+    return true;
+  }
+  SD_REQUIRE(variant < 100, kInvalidArgument, "attention variant %d: the balanced form cannot run this shape", variant);
+  return false;
+}
+static void check_attention_w8a8_shape(int B, int heads, int S) {
+  SD_REQUIRE(B > 0 && heads > 0 && S > 0, kInvalidArgument, "attention_w8a8: empty problem");
+  SD_REQUIRE(S >= 64 && S % 64 == 0, kInvalidArgument, "attention_w8a8: S = %d is off the shape rule (head dim 64, S a positive multiple of 64)", S);
+  SD_REQUIRE(attention_i8_shape_ok(64, S, S), kInvalidArgument, "attention_w8a8: S = %d, the exact integer sums hold up to %d", S, kAttnI8MaxS);
+}
+
 int sd_op_attention(int impl, const void* q, const void* k, const void* v, void* out, int B, int heads, int d,
                     int Sq, int Sk, int variant, int iters, float* ms) {
   return guarded([&] {
     SD_REQUIRE(q && k && v && out, kInvalidArgument, "NULL argument");
-    SD_REQUIRE(impl >= 0 && impl <= 2, kInvalidArgument, "unknown attention implementation %d", impl);
-    SD_REQUIRE(B > 0 && heads > 0 && d > 0 && Sq > 0 && Sk > 0, kInvalidArgument, "empty attention problem");
-    SD_REQUIRE(variant != 3 || Sq == Sk, kInvalidArgument, "attention variant 3 (q | k in one buffer) needs Sq == Sk (%d, %d)", Sq, Sk);
+    AttnDesc a = attention_op_desc(impl, B, heads, d, Sq, Sk, variant);
     Scratch sc("attention");
     const int C = heads * d;
-    const int ldv = (Sk + 7) / 8 * 8;
-    // the software-pipelined d = 64 kernel reads V^T in its own key order (AttnDesc::vt_perm)
-    const bool perm = variant != 1 && attention8_shape_ok(d, Sq, Sk);
-    AttnDesc a;
-    a.ldq = C; a.ldk = C;
     if (variant == 3) {   // q and k as a self-attention of a handle reads them: rows of ONE [B][S][2C] buffer (qkv_desc's qk)
       const half_t *qs = f16(q), *ks = f16(k);
       std::vector<half_t> qk((size_t)B * Sq * 2 * C);
@@ -389,43 +429,46 @@ int sd_op_attention(int impl, const void* q, const void* k, const void* v, void*
       const half_t* dqk = sc.dev<half_t>(qk.size(), qk.data(), "q | k");
       a.q = dqk;
       a.k = dqk + C;
-      a.ldq = a.ldk = 2 * C;
     } else {
       a.q = upload_tokens(sc, q, B, C, Sq);
       a.k = upload_tokens(sc, k, B, C, Sk);
     }
-    a.vt = upload_vt(sc, v, B, C, Sk, ldv, perm);
+    a.vt = upload_vt(sc, v, B, C, Sk, a.ldv, a.vt_perm != 0);
     half_t* o = sc.out<half_t>((size_t)B * Sq * C, "out");
     a.out = o;
-    a.B = B; a.heads = heads; a.d = d; a.Sq = Sq; a.Sk = Sk;
-    a.ldv = ldv; a.ldo = C;
-    a.impl = impl;
-    a.variant = variant == 3 ? 0 : variant;   // (3: the default dispatch, only the addresses differ)
-    a.vt_perm = perm ? 1 : 0;
-    if (variant == 2) {   // the caller multiplied d^-0.5 * log2(e) into q before rounding it to fp16 (what the UNet's q|k|v GEMM does)
-      SD_REQUIRE(perm, kInvalidArgument, "attention variant 2 (pre-scaled q) needs attention8's shape (d %d Sq %d Sk %d)", d, Sq, Sk);
-      a.q_prescaled = 1;
-    }
-    if (variant >= 100) {   // attention8's balanced form, variant - 100 units per workgroup (0: the launch's own split)
-      SD_REQUIRE(perm, kInvalidArgument, "attention variant %d (balanced form) needs attention8's shape (d %d Sq %d Sk %d)", variant, d, Sq, Sk);
-      a.variant = 0;
-      a.sk_force = 1;
-      a.sk_upw = variant - 100;
-    }
-    {
-      size_t pb = 0;
-      int nc = 0;
-      if (perm && attention8_sk_scratch(a, &pb, &nc)) {
-        a.sk_part = reinterpret_cast<float*>(sc.out<char>(pb, "sk_part"));
-        a.sk_part_bytes = pb;
-        a.sk_cnt = sc.zeroed<unsigned>(nc, "sk_cnt");   // zeroed: AttnDesc::sk_cnt is "ZEROED once by the owner", the kernel leaves it at zero
-        a.sk_cnt_n = nc;
-      } else {
-        SD_REQUIRE(variant < 100, kInvalidArgument, "attention variant %d: the balanced form cannot run this shape", variant);
-      }
+    if (attention_op_wants_scratch(a, variant)) {
+      a.sk_part = reinterpret_cast<float*>(sc.out<char>(a.sk_part_bytes, "sk_part"));
+      a.sk_cnt = sc.zeroed<unsigned>(a.sk_cnt_n, "sk_cnt");   // zeroed: AttnDesc::sk_cnt is "ZEROED once by the owner", the kernel leaves it at zero
     }
     sc.timed(iters, ms, [&] { launch_attention(a, sc.stream); });
     download_tokens(o, out, B, C, Sq);
+  });
+}
+
+// Which kernel would sd_op_attention (int8 == 0) or sd_op_attention_w8a8 (int8 != 0: impl, d, Sk and variant are not read) launch for
+// this problem?  The descriptor those entries build, handed to the choice function their launcher calls.  Host only: nothing launched.
+int sd_op_attention_kernel(int int8, int impl, int B, int heads, int d, int Sq, int Sk, int variant, char* text, int text_bytes) {
+  return guarded([&] {
+    SD_REQUIRE(text && text_bytes >= 1, kInvalidArgument, "bad attention_kernel arguments");
+    AttnKernel c;
+    if (int8) {
+      check_attention_w8a8_shape(B, heads, Sq);
+      AttnI8Desc di;
+      di.B = B; di.heads = heads; di.S = Sq;
+      c = attention_i8_kernel(di);
+    } else {
+      AttnDesc a = attention_op_desc(impl, B, heads, d, Sq, Sk, variant);
+      static float part_stand_in;      // never dereferenced: attention8_kernel asks only whether scratch is offered, and how much
+      static unsigned cnt_stand_in;
+      if (attention_op_wants_scratch(a, variant)) {
+        a.sk_part = &part_stand_in;
+        a.sk_cnt = &cnt_stand_in;
+      }
+      c = attention_kernel(a);
+    }
+    const std::string name = attention_kernel_name(c);
+    SD_REQUIRE((int)name.size() < text_bytes, kInvalidArgument, "attention_kernel: the text buffer holds %d bytes, the line needs %zu", text_bytes, name.size() + 1);
+    memcpy(text, name.c_str(), name.size() + 1);
   });
 }
 
@@ -478,9 +521,7 @@ int sd_op_attention_w8a8(const int8_t* q_q, const int8_t* k_q, const int8_t* v_q
                          int heads, int S, int iters, float* ms) {
   return guarded([&] {
     SD_REQUIRE(q_q && k_q && v_q && out, kInvalidArgument, "NULL argument");
-    SD_REQUIRE(B > 0 && heads > 0 && S > 0, kInvalidArgument, "attention_w8a8: empty problem");
-    SD_REQUIRE(S >= 64 && S % 64 == 0, kInvalidArgument, "attention_w8a8: S = %d is off the shape rule (head dim 64, S a positive multiple of 64)", S);
-    SD_REQUIRE(attention_i8_shape_ok(64, S, S), kInvalidArgument, "attention_w8a8: S = %d, the exact integer sums hold up to %d", S, kAttnI8MaxS);
+    check_attention_w8a8_shape(B, heads, S);
     SD_REQUIRE(w8a8_absmax_ok(q_absmax) && w8a8_absmax_ok(k_absmax) && w8a8_absmax_ok(v_absmax), kInvalidArgument,
                "attention_w8a8: ranges %g, %g, %g: each must be a positive finite number", (double)q_absmax, (double)k_absmax, (double)v_absmax);
     const int C = heads * 64;

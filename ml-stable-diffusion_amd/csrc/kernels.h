@@ -304,6 +304,30 @@ void launch_attention8(const AttnDesc& d, hipStream_t s);
 // merged by the last workgroup to arrive), with the scratch that takes: bytes for AttnDesc::sk_part, counters for sk_cnt
 bool attention8_sk_scratch(const AttnDesc& d, size_t* part_bytes, int* n_counters);
 
+// What a launcher of the three attention files decides for a problem, stated once per launcher by the host function that launcher itself
+// calls (attention_kernel, attention8_kernel, attention_i8_kernel): the launch switches on these fields and on nothing else, so the
+// answer sd_op_attention_kernel gives cannot drift from what runs.
+enum AttnFamily : int { kAttnFamilyGeneral = 0, kAttnFamily8 = 1, kAttnFamilyI8 = 2 };
+struct AttnKernel {
+  int family = kAttnFamilyGeneral;
+  int waves = 4;             // waves per workgroup: 4 or 8
+  int q_tiles = 1;           // 32-query tiles per wave (2: the general kernel's SPLIT_EINSUM_V2 form on whole 512-query chunks, d <= 64)
+  int d = 64;                // general kernel: the head dim
+  int mode = 0;              // general kernel: 0 the ORIGINAL schedule, 1 the split one (SPLIT_EINSUM, and V2's chunks)
+  bool balanced = false;     // attention8: the balanced form, with
+  int upw = 0, max_seg = 0;  // ... units per workgroup and the most segments one workgroup can touch
+};
+// one line: "attn d<d> original|split w<waves> qt<q_tiles>", "attn8 w<waves> classic", "attn8 w<waves> balanced upw=<u> seg=<s>",
+// "attn_i8 w<waves>"
+std::string attention_kernel_name(const AttnKernel& k);
+// compute units of the current device, 256 where there is none to ask
+int device_cus();
+// THE waves rule of attention8.hip and attention_i8.hip: 256-query (eight-wave) workgroups when they give at least half the CUs one,
+// else 128-query ones - more, smaller workgroups
+int attention_waves(int B, int heads, int Sq);
+AttnKernel attention_kernel(const AttnDesc& d);    // launch_attention's choice, with that launcher's refusals
+AttnKernel attention8_kernel(const AttnDesc& d);   // launch_attention8's
+
 // attention_i8.hip: the same self-attention from int8 q, k and V^T on the int8 MFMAs (W8A8: the reference's Einsum modules,
 // activation_quantization.py:205-215, unet.py:45-59; the function is stated at the top of attention_i8.hip).  q and k are rows of int8
 // matrices (head h at byte column 64 h; ldq / ldk in bytes), vt [B][heads * 64][ldv] int8 with every 32 keys in the order
@@ -325,6 +349,7 @@ bool attention_i8_shape_ok(int d, int Sq, int Sk);
 __host__ __device__ inline int attention_i8_vt_key(int p) { return (p & 3) + 8 * ((p >> 2) & 3) + 4 * (p >> 4); }
 float attention_i8_score_scale(float q_absmax, float k_absmax, int d);   // c = fp32(s_q * s_k * d^-0.5 * log2 e), s_x = fp32(r_x / 127)
 void launch_attention_i8(const AttnI8Desc& d, hipStream_t s);
+AttnKernel attention_i8_kernel(const AttnI8Desc& d);   // launch_attention_i8's choice, with its shape refusal
 // the quantizer in front of it, one launch: qk [B * S][2C] fp16 -> qk_q int8 by inv_q (columns below C) and inv_k, vt [B][C][ldv] fp16
 // in the key order vt_perm_in (0 natural, 1 AttnDesc::vt_perm) -> vt_q [B][C][S] int8 in attention_i8_vt_key's order by inv_v; the
 // quantizer is ws_quantize8 (quantize8.h).  S % 32 == 0, C % 8 == 0.

@@ -164,6 +164,7 @@ SYMBOLS = [
     ("sd_text_encoder_device_bytes", C.c_size_t, [_P]),
     ("sd_text_encoder_encode", _I, [_P, C.POINTER(C.c_int32), _I, _FP, _FP, _FP]),
     ("sd_op_attention", _I, [_I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _FP]),
+    ("sd_op_attention_kernel", _I, [_I] * 8 + [C.c_char_p, _I]),
     ("sd_op_layernorm", _I, [_P, _FP, _FP, _P, _I, _I, _I, _F, _I, _FP]),
     ("sd_op_groupnorm", _I, [_P, _FP, _FP, _P, _I, _I, _I, _I, _I, _F, _I, _I, _FP]),
     ("sd_op_groupnorm_shortcut", _I, [_P, _P, _FP, _FP, _P, _FP, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _I, _I, _I, _FP]),
@@ -344,6 +345,18 @@ def attention(impl, q, k, v, heads, dim_head, variant=0, iters=1):
     check(lib().sd_op_attention(ATTENTION_IMPLEMENTATIONS[impl], ptr(q), ptr(k), ptr(v), ptr(out), B, heads,
                                 dim_head, Sq, Sk, variant, iters, C.byref(ms)))
     return out, ms.value
+
+
+def attention_kernel(impl, batch, heads, dim_head, Sq, Sk=None, variant=0, int8=False):
+    """The kernel ``attention`` (or, with ``int8``, ``attention_w8a8``: dim_head 64, S = Sq; impl and variant are not read) would launch
+    for this problem on the current device, as the line sd_op_attention_kernel writes (sd_mi355x.h lists the forms): e.g.
+    'attn8 w8 classic', 'attn8 w8 balanced upw=3 seg=2', 'attn_i8 w8', 'attn d64 split w8 qt2'.  Host only; refuses as those entries do."""
+    if not int8 and impl not in ATTENTION_IMPLEMENTATIONS:
+        raise ValueError(f"unknown attention implementation {impl!r}")
+    text = C.create_string_buffer(96)
+    check(lib().sd_op_attention_kernel(int(bool(int8)), 0 if int8 else ATTENTION_IMPLEMENTATIONS[impl], batch, heads, dim_head, Sq,
+                                       Sq if Sk is None else Sk, variant, text, len(text)))
+    return text.value.decode()
 
 
 def vit_attention(qkv, heads, dim_head=64, out=None, iters=1):

@@ -9,10 +9,14 @@ sits on a rounding boundary.  One such flip changes N by <= 127 and L by 1 with 
   (b) at most 2 % of the query rows with any element more than one fp16 ulp away;
   (c) the rows of a query whose scores are all equal (every p_q is 127, exp2(0) is exact) are fp16(mean of v_q * s_v) to the bit.
 The restatement against itself with an exp2 perturbed by +-1 fp32 ulp (alternating sign per element) against a float64 exp2, on
-THIS file's inputs on the CPU: no probability moved and no output differed in any of the four cases - 0 of 4 096 at (1, 1, 64), 0 of
-262 144 at (2, 2, 256), 0 of 294 912 at (1, 2, 384), 0 of 1 048 576 at (1, 1, 1024) - so the restatement stays inside (a), whose bound
-is 0.0945 here, and (b); its all-equal rows meet (c) in all four.  (Scores with a standard deviation near 20 leave few probabilities
-between 0 and 127.)"""
+THIS file's inputs on the CPU, is a test (test_attention_kernel.py, which imports SHAPES, case_of and criteria from here): no
+probability moves and no output differs in any of the seven cases, so the restatement stays inside (a), whose bound is 0.0945 here,
+and (b); its all-equal rows meet (c) in all seven.  (Scores with a standard deviation near 20 leave few probabilities between 0 and
+127.)
+
+SHAPES: four that run attn_i8_kernel<4, 4> and three that run <8, 4>, which the launcher takes where B * heads * ceil(S / 256) fills
+half the compute units - every case asserts which of the two the device would run (_lib.attention_kernel: the launcher's own choice
+function), and the eight-wave results are also compared bit for bit with the four-wave kernel on single (sample, head) problems."""
 import json
 import os
 import re
@@ -28,7 +32,12 @@ from test_w8a8_gpu import RANGE_DEV_GATE
 pytestmark = pytest.mark.gpu
 
 RING = 4                                                                         # stages of the kernel's LDS ring (attention_i8.hip launch_i8)
-SHAPES = [(1, 1, 64), (2, 2, 256), (1, 2, 384), (1, 1, 1024)]                    # (B, heads, S)
+SHAPES = [(1, 1, 64), (2, 2, 256), (1, 2, 384), (1, 1, 1024),                    # (B, heads, S): attn_i8_kernel<4, 4> ...
+          (8, 16, 64), (4, 16, 320), (2, 16, 1024)]                              # ... and <8, 4>: many heads and samples, few tokens
+W8_SHAPES = SHAPES[4:]
+KERNEL = {s: "attn_i8 w4" for s in SHAPES[:4]}                                   # what _lib.attention_kernel must answer (256 CUs)
+KERNEL.update({s: "attn_i8 w8" for s in W8_SHAPES})
+PASSED_FORMS = []                                                                # the query's answer of every operator case that passed
 ids3 = lambda s: "x".join(map(str, s))   # noqa: E731
 R_V = np.float32(3.0)
 TARGET_C = 1.5e-3                                                                # random scores then have a std near 20: logits reach +-60
@@ -48,6 +57,13 @@ def test_the_shapes_reach_every_mechanism():
     assert tiles[2] % RING != 0 and tiles[2] > RING and tiles[2] % 2 == 0        # neither a multiple of the ring depth nor below it
     assert SHAPES[3][2] > 256 and SHAPES[1][0] > 1 and SHAPES[1][1] > 1          # several query tiles per head; batch and head strides
     assert abs(float(ref.score_scale(R_QK, R_QK)) / TARGET_C - 1.0) < 1e-3
+    for shape in SHAPES:                                                         # the wave count, from the launcher's own choice function
+        assert _lib.attention_kernel(None, *shape[:2], 64, shape[2], int8=True) == KERNEL[shape], shape
+    # eight waves: one key tile below the ring depth and six of eight waves without a query | five key tiles (odd, above the ring depth,
+    # no multiple of it: pass 1's second K tile of the last pair is dead) and a tail query tile with two live waves | whole query
+    # tiles, the ring wraps four times
+    assert SHAPES[4][2] == 64 and tiles[5] == 5 and tiles[5] % 2 == 1 and tiles[5] > RING and (SHAPES[5][2] % 256) // 32 == 2
+    assert SHAPES[6][2] % 256 == 0 and tiles[6] == 4 * RING
 
 
 def make_case(shape, seed):
@@ -98,36 +114,67 @@ def run_op(c, what):
     return out
 
 
-@pytest.mark.parametrize("shape", SHAPES, ids=ids3)
-def test_operator_against_the_restatement(shape):
-    c = make_case(shape, 31000 + SHAPES.index(shape))
-    check_inputs(c)
-    want = ref.attention(c["q"], c["k"], c["v"], R_QK, R_QK, R_V, c["B"], c["heads"])
-    got = run_op(c, str(shape))
+def case_of(shape):
+    return make_case(shape, 31000 + SHAPES.index(shape))
+
+
+def criteria(got, want, c, what):
+    """(a), (b) and (c) of this file for one case: ``got`` against the restatement ``want``"""
     diff = np.abs(got.astype(np.float32) - want.astype(np.float32))
     one = ulp16(want)
     rows_off = (diff > one).any(axis=1)
-    print(f"{shape}: {np.count_nonzero(got != want)} of {got.size} elements differ, {np.count_nonzero(rows_off)} of {rows_off.size} token rows more "
+    print(f"{what}: {np.count_nonzero(got != want)} of {got.size} elements differ, {np.count_nonzero(rows_off)} of {rows_off.size} token rows more "
           f"than one fp16 ulp away, largest difference {diff.max():.3e} (bound {4 * R_V / 127:.3e} + ulp)")
     assert (diff <= np.float32(4.0) * R_V / np.float32(127.0) + one).all()                       # (a)
     assert np.count_nonzero(rows_off) <= 0.02 * rows_off.size                                     # (b)
-    S = shape[2]                                                                                  # (c): the query sits in sample 0
+    S = c["S"]                                                                                    # (c): the query sits in sample 0
     exact = (c["v"][:S].astype(np.float64).mean(axis=0) * np.float64(ref.scale(R_V))).astype(np.float16)
     assert np.array_equal(got[Q_EQUAL].view(np.uint16), exact.view(np.uint16)), "the all-equal query's row"
     dom = (c["v"][k_dominant(S), :64].astype(np.float32) * ref.scale(R_V)).astype(np.float16)     # the dominant key alone: its value, exactly
     assert np.array_equal(got[Q_DOMINANT, :64].view(np.uint16), dom.view(np.uint16))
 
 
+@pytest.mark.parametrize("shape", SHAPES, ids=ids3)
+def test_operator_against_the_restatement(shape):
+    kernel = _lib.attention_kernel(None, *shape[:2], 64, shape[2], int8=True)
+    assert kernel == KERNEL[shape], f"{shape} is here for {KERNEL[shape]}, this device would run {kernel}"
+    c = case_of(shape)
+    check_inputs(c)
+    want = ref.attention(c["q"], c["k"], c["v"], R_QK, R_QK, R_V, c["B"], c["heads"])
+    got = run_op(c, str(shape))
+    criteria(got, want, c, f"{shape} {kernel}")
+    PASSED_FORMS.append(kernel)
+
+
+@pytest.mark.parametrize("shape", W8_SHAPES, ids=ids3)
+def test_eight_wave_result_is_the_four_wave_result_of_each_head(shape):
+    """attention_i8.hip: "the result does not depend on the tile walk, the ring depth or the wave count" - the rows and columns of a
+    (sample, head) in the eight-wave launch are, to the bit, the operator on that (1, 1, S) problem alone, which runs four waves"""
+    B, heads, S = shape
+    assert _lib.attention_kernel(None, B, heads, 64, S, int8=True) == "attn_i8 w8" and _lib.attention_kernel(None, 1, 1, 64, S, int8=True) == "attn_i8 w4"
+    c = case_of(shape)
+    got = run_op(c, str(shape))
+    for b in sorted({0, B - 1}):
+        for h in sorted({0, heads - 1}):
+            rows, cols = slice(b * S, (b + 1) * S), slice(h * 64, (h + 1) * 64)
+            sub = dict(B=1, heads=1, S=S, **{n: np.ascontiguousarray(c[n][rows, cols]) for n in "qkv"})
+            alone = run_op(sub, f"{shape} sample {b} head {h} alone")
+            n = np.count_nonzero(alone.view(np.uint16) != got[rows, cols].view(np.uint16))
+            print(f"{shape} sample {b} head {h}: {n} of {alone.size} values differ between eight and four waves")
+            assert n == 0, f"{shape} sample {b} head {h}: {n} of {alone.size} values differ between the eight- and the four-wave kernel"
+
+
 def test_operator_behind_poisoned_lds():
     """SD_POISON_LDS=1 (with SD_TUNE) fills every CU's LDS with NaN bit patterns in front of the launch: the odd tile count of pass 1
-    (one key tile: half a stage never arrives) and the wrapped ring must give the same bits"""
+    (one key tile: half a stage never arrives) and the wrapped ring must give the same bits, at four waves and at eight (whose waves
+    4-7 fetch the half that is dead)"""
     import subprocess
     import sys
     root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
     env = dict(os.environ, SD_TUNE="1", SD_POISON_LDS="1")
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-q", "-x", "-k", "against_the_restatement and (1x1x64 or 1x2x384)"],
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-q", "-x", "-k", "against_the_restatement and (1x1x64 or 1x2x384 or 8x16x64 or 4x16x320)"],
                        env=env, cwd=root, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "2 passed" in r.stdout, r.stdout[-2000:]
+    assert r.returncode == 0 and "4 passed" in r.stdout, r.stdout[-2000:]
 
 
 # ---- the quantizer launch, bit for bit ----
